@@ -32,6 +32,9 @@ N > 1 without a launcher (`python bench.py --gpus 8`) spawns its own N ranks und
 torch.distributed.run; a world size that differs from --gpus, or fewer GPUs than ranks with the
 RCCL backend, is an error.  The line carries what the collective layer saw: `ranks_seen`, per-rank
 device / PCI bus / NUMA node / own frames/s, `rccl_version`.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in its last step (rank 0: the frame's pose record, one
+row per tracker) as float64 DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -156,6 +159,29 @@ def _tracked(ret) -> bool:
     from pixtrack_amd.parallel import frame_tracked
 
     return frame_tracked(ret)
+
+
+def dump_outputs(out_dir, trackers, name):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step (frame `name`), one row per tracker, as
+    float64 .npy files: the frame's pose_history entry - `T_refined`, `T_init` as R (9, row-major) | t (3), `cost`,
+    `success` and `tracked` (0 / 1) - and `pose`, the pose the tracker carries into the next frame.  Called right after
+    the timed loop, before the untimed passes run more frames through the same trackers."""
+    def as12(T):
+        return T.as12().detach().cpu().double().numpy().reshape(12)
+
+    cols = {"T_refined": [], "T_init": [], "pose": [], "cost": [], "success": [], "tracked": []}
+    for tr in trackers:
+        ret = tr.pose_history[name]
+        cols["T_refined"].append(as12(ret.get("T_refined", ret["T_init"])))
+        cols["T_init"].append(as12(ret["T_init"]))
+        cols["pose"].append(as12(tr.pose))
+        cols["cost"].append(float(ret.get("cost", float("nan"))))
+        cols["success"].append(1.0 if ret["success"] else 0.0)
+        cols["tracked"].append(1.0 if _tracked(ret) else 0.0)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for k, v in cols.items():
+        np.save(out / f"{k}.npy", np.asarray(v, dtype=np.float64))
 
 
 class StageTimer:
@@ -550,6 +576,8 @@ def run_hd(args, rank, ws, dev, coll_dev, numa_node):
     if ws > 1:
         torch.distributed.barrier()
     own = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [tracker], names[mine[-1]])
     elapsed = parallel.max_over_ranks(own, coll_dev)
     gc.enable()
     report = rank_report(rank, dev.index, dev, numa_node, len(mine), own, coll_dev)
@@ -658,6 +686,8 @@ def run_objects8(args, rank, ws, dev, coll_dev, numa_node):
         torch.distributed.barrier()
     own = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trackers, names[n - 1])
     elapsed = parallel.max_over_ranks(own, coll_dev)
     report = rank_report(rank, dev.index, dev, numa_node, args.steps * len(units), own, coll_dev)
     timed = names[args.warmup:n]
@@ -907,7 +937,13 @@ def main():
     ap.add_argument("--cpu-baseline-frames", type=int, default=0,
                     help="CPU baseline: track exactly this many frames after 3 warm-up frames (BASELINE.md 3 asks for >= 20); "
                          "0 = as many as fit the default ~70 s budget after 1 warm-up frame")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (poses, cost, flags) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.extra:
+        ap.error("--dump-outputs needs the timed path; --extra runs an extra pass only")
     if args.first_frame_sigma is None:
         args.first_frame_sigma = 24.0 if args.config == "objects8" else 12.0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1017,6 +1053,8 @@ def main():
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [tracker], names[n_timed_end - 1])
     frame_ms = np.diff(np.array([t0] + frame_t)) * 1e3
     tracker.testbed.timing_enable(0)
     enc_ms, enc_launches = tracker.testbed.timing_read()

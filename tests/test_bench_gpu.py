@@ -6,6 +6,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +63,27 @@ def test_single_gpu_line_has_the_contract_fields(device):
     assert d["roofline"]["traffic_static"]["static"] is True and d["kernel_utilisation"]["static"] is True
     assert ex["value_two_renders"]["frames_per_s"] < d["value"] * 1.05
     assert ex["value_ycb_policy"]["renders_ahead_used"] >= ex["value_ycb_policy"]["frames"] - 2
+
+
+def test_dump_outputs_writes_the_last_timed_step(device, tmp_path):
+    """`--dump-outputs DIR`: the last timed frame's pose record as float64 .npy files; two runs of the same command track
+    the same seeded inputs to the same pose; `--steps` sets the timed frames."""
+    runs = []
+    for k in range(2):
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-extras",
+               "--no-cpu-baseline", "--dump-outputs", str(tmp_path / f"run{k}")]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+        assert out.returncode == 0, out.stderr[-3000:]
+        d = _last_json(out.stdout)
+        assert d["steps"] == 5 == d["frames_total"] and d["ms_per_step"] > 0
+        runs.append({f.stem: np.load(f) for f in sorted((tmp_path / f"run{k}").glob("*.npy"))})
+    a, b = runs
+    assert set(a) == {"T_refined", "T_init", "pose", "cost", "success", "tracked"}
+    for name, x in a.items():
+        assert x.dtype == np.float64 and x.shape == ((1, 12) if x.ndim == 2 else (1,)), (name, x.shape)
+        assert np.all(np.isfinite(x)), name
+        np.testing.assert_allclose(x, b[name], rtol=1e-5, atol=1e-6, err_msg=name)
+    assert a["tracked"][0] == 1.0 and np.array_equal(a["pose"], a["T_refined"])
 
 
 def test_objects8_and_hd_workloads_run(device):
@@ -205,8 +227,13 @@ def test_objects8_every_object_tracks_at_640x480(device, k):
 
 
 def test_eight_ranks_rehearsal_on_one_gpu(device):
-    """The driver's 8-GPU command shape with eight gloo ranks sharing cuda:0 (ports, NUMA binding, eight processes'
-    memory, the pose gather of eight ranks): the first real 8-GPU node must not also be the first 8-rank run."""
+    """The driver's 8-GPU command shape with eight gloo ranks (ports, NUMA binding, eight processes' memory, the pose gather
+    of eight ranks): the first real 8-GPU node must not also be the first 8-rank run.  Eight processes with a GPU open,
+    one per device: a node with fewer GPUs does not run it (the 2-rank shape below rehearses on one GPU)."""
+    import torch
+
+    if torch.cuda.device_count() < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {torch.cuda.device_count()}")
     env = dict(os.environ, PXT_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
@@ -227,10 +254,17 @@ def test_eight_ranks_rehearsal_on_one_gpu(device):
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     assert d["ranks_seen"] == list(range(8)) and d["frames_total"] == 32 == d["tracked_ok"]
-    # ... and on TWO ranks: four objects per rank in lock-step (rank 0: objects 0, 2, 4, 6; rank 1: 1, 3, 5, 7)
-    cmd[cmd.index("--nproc-per-node") + 1] = "2"
-    cmd[cmd.index("--gpus") + 1] = "2"
-    cmd[cmd.index("29563")] = "29565"
+
+
+def test_objects8_on_two_ranks_rehearsal_on_one_gpu(device):
+    """The objects8 workload on TWO gloo ranks sharing cuda:0: four objects per rank in lock-step (rank 0: objects 0, 2, 4,
+    6; rank 1: 1, 3, 5, 7)."""
+    env = dict(os.environ, PXT_DIST_BACKEND="gloo")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+           "127.0.0.1", "--master-port", "29565", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+           "--config", "objects8"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=str(ROOT), env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
