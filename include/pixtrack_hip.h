@@ -46,7 +46,7 @@ extern "C" {
 #define PXT_LM_LOG_STRIDE 20 /* floats per logged iteration, see pxt_lm_refine */
 
 /* Library / device info ---------------------------------------------------- */
-int pxt_version(void);               /* ABI version (11), bumps on any signature change or added entry point */
+int pxt_version(void);               /* ABI version (12), bumps on any signature change or added entry point */
 const char* pxt_last_error(void);    /* text of the last PXT_E_HIP on this thread */
 int pxt_device_cus(int* n_cus_host); /* multiprocessor count of the current device */
 
@@ -392,8 +392,9 @@ float* pxt_ngp_camera_slot(pxt_ngp* ctx); /* device float[12], owned by the cont
  *     pxt_ngp_create_shared;
  *   - K objects tracked in lock-step, one tracker (and one pyngp.Testbed) per object as
  *     pixtrack/pose_trackers/pixloc_tracker_r9.py:287-318 builds them: modes {2, 2, ...}.
- * Every launch of the chain carries a stage of every render (the shade stage of one half of the rays beside the march stage
- * of the other half: csrc/pxt_ngp.hip, ngp_stage_kernel), so nothing depends on how streams are dealt to hardware queues.
+ * The chain is three launches - ray generation, one persistent render kernel, resolve - and each of them carries every
+ * render of the batch (blockIdx.y = render, one parameter record per render), so nothing depends on how streams are dealt
+ * to hardware queues.
  * ctxs[k] / views_host[k] / modes[k] / outs_host[k] / stats[k] (stats or stats[k] may be NULL) are what K calls of
  * pxt_ngp_render_frame(ctxs[k], &views_host[k], modes[k], camera_from_slot, &outs_host[k], stats[k], stream) would take; the
  * images are bit for bit those calls' images.  Modes and sizes may differ per render.  batch_workspace: device memory of
@@ -411,19 +412,12 @@ int pxt_ngp_render_frame_batch(pxt_ngp* const* ctxs, const pxt_ngp_view* views_h
  * with pxt_ngp_destroy, in any order. */
 int pxt_ngp_create_shared(pxt_ngp* src, pxt_ngp** out_ctx);
 
-/* A render of >= 2^19 rays is cut into n pipes - equal slices of the rays - whose stages share the launches of the
- * render's chain one stage apart (the latency-bound march of one slice beside the gather-bound shade stage of
- * another): the image is bit for bit the same.  n = 0 restores the default (2, or $PXT_NGP_PIPES); n = 1: one pipe, every
- * launch carries ONE stage (isolated per-stage timing); n <= 4. */
-int pxt_ngp_set_pipelines(pxt_ngp* ctx, int32_t n);
-
-/* Live HIP-event timing of the renderer's dominant launches (those of ngp_stage_kernel that carry a shade stage: the hash-grid
- * gathers + both MLPs + compositing of a round's samples), for the
- * roofline line of bench.py.  every_nth > 0: those launches of every every_nth-th render
- * are bracketed by an event pair recorded on the render's own stream (an event record is a
- * marker packet between kernels, so sampling keeps the measurement from slowing what it
- * measures); 0 disables.  pxt_ngp_timing_read synchronises those events, returns their summed
- * duration (ms) and the number of timed launches, and clears the list. */
+/* Live HIP-event timing of the renderer's dominant launch, for the roofline line of bench.py: the persistent render kernel
+ * (march, hash-grid gathers, both MLPs and compositing of every ray) of a single-render chain (n_renders = 1; batched
+ * chains are not timed).  every_nth > 0: that launch of every every_nth-th render is bracketed by an event pair recorded
+ * on the render's own stream (an event record is a marker packet between kernels, so sampling keeps the measurement from
+ * slowing what it measures); 0 disables.  pxt_ngp_timing_read synchronises those events, returns their summed duration
+ * (ms) and the number of timed launches, and clears the list. */
 int pxt_ngp_timing_enable(pxt_ngp* ctx, int32_t every_nth);
 int pxt_ngp_timing_read(pxt_ngp* ctx, float* total_ms_host, int32_t* n_launches_host);
 

@@ -20,7 +20,7 @@ LIB_PATH = Path(os.environ["PIXTRACK_HIP_LIB"]) if os.environ.get("PIXTRACK_HIP_
 PXT_MAX_LEVELS = 8
 PXT_LM_LOG_STRIDE = 20
 PXT_E_TIMEOUT = -3
-ABI_VERSION = 11
+ABI_VERSION = 12
 PXT_LM_MAX_BATCH = 16
 PXT_UNET_MAX_BATCH = 16
 PXT_NGP_MAX_BATCH = 16
@@ -182,7 +182,6 @@ PROTOTYPES = {
     "pxt_ngp_render_frame_batch": (C.c_int, [C.POINTER(_VP), C.POINTER(NgpView), _I32, C.POINTER(_I32), _I32,
                                               C.POINTER(NgpOutputs), C.POINTER(_VP), _VP, _VP]),
     "pxt_ngp_create_shared": (C.c_int, [_VP, C.POINTER(_VP)]),
-    "pxt_ngp_set_pipelines": (C.c_int, [_VP, _I32]),
     "pxt_ngp_timing_enable": (C.c_int, [_VP, _I32]),
     "pxt_ngp_timing_read": (C.c_int, [_VP, C.POINTER(C.c_float), C.POINTER(_I32)]),
     "pxt_ngp_query": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP]),

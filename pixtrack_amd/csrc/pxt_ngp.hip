@@ -26,6 +26,7 @@
 #include "pxt_common.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -78,7 +79,6 @@ struct NgpParams {
   uint8_t* out_u8;   // optional [H][W][3]: (rgb * 255).astype(uint8) of the Shade image (modes 0, 2)
   uint8_t* out_nz;   // optional [H][W]: uint8(depth * 255) != 0 of the Depth image (modes 1, 2): get_mask's plane
   unsigned long long* stats;
-  long long enum_lo, enum_hi;  // the part of the ray enumeration this pipeline (slice) generates
 };
 
 __device__ inline float calc_dt(float t, float cone, float lo, float hi) {
@@ -386,7 +386,7 @@ __device__ inline void ngp_eval(const NgpParams& P, const half8* s_w, int lane, 
 // past a ray's termination point are discarded.
 // ===========================================================================
 constexpr int kK = 8;          // samples per ray per step
-constexpr int kCtrWords = 16;  // ints per counter block (one 64-B line per pipe)
+constexpr int kCtrWords = 16;  // ints per counter block (one 64-B line per render)
 
 
 struct Ray {
@@ -537,12 +537,12 @@ __device__ inline bool next_sample(const NgpParams& P, const Ray& r, float& t, f
   }
 }
 
-struct NgpWork {       // one pipe: a slice of a render's ray enumeration
+struct NgpWork {       // a render's scratch: its ray list, counter block and per-ray results
   unsigned* rid;       // [slot] pixel * spp + spp_index of the slot's ray (the compact list raygen writes)
   float* t0;           // [slot] its first lattice position
   float4* dir;         // [slot] (unit direction, d . camera z)
   int* counters;       // [0]: rays in the list
-  float4* sppbuf;      // [pixel][spp] finished rays (shared by the pipes of a render)
+  float4* sppbuf;      // [pixel][spp] finished rays
   float* sppbuf_d;     // mode 2: finished rays' depth
 };
 
@@ -593,12 +593,12 @@ __device__ inline float ray_start(const NgpParams& P, const Ray& r, int pix, int
 // Ray generation + order-preserving compaction of 2048-ray tiles: ONE global atomic per tile (a single
 // counter word sustains only ~90 atomics/us, MI355X_MICROARCH.md "dequeue").  Tiles land in the order of their atomics,
 // i.e. roughly in dispatch order: neighbours in the list are neighbours in the image.
-// (blk / nblk: this workgroup's index among the workgroups working on THIS pipe's slice.)
+// (blk / nblk: this workgroup's index among the workgroups working on THIS render.)
 constexpr int kTile = 2048;
 __device__ __forceinline__ void ngp_raygen_body(const NgpParams& P, const NgpWork& Wk, int blk, int nblk) {
   __shared__ int s_wave[4];
   __shared__ int s_base;
-  const long long n = P.enum_hi - P.enum_lo;
+  const long long n = enum_total(P);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long tiles = (n + kTile - 1) / kTile;
   for (long long tile = blk; tile < tiles; tile += nblk) {
@@ -618,7 +618,7 @@ __device__ __forceinline__ void ngp_raygen_body(const NgpParams& P, const NgpWor
       k[j] = false;
       t_start[j] = -1.f;
       rid_new[j] = 0u;
-      if (i < n && enum_ray(P, P.enum_lo + i, px, py, sp)) {
+      if (i < n && enum_ray(P, i, px, py, sp)) {
         const int pix = py * P.W + px;
         if (pix != last_pix) {
           r = make_ray(P, px, py);
@@ -818,7 +818,7 @@ __device__ __forceinline__ unsigned ngp_encode_level_patch(const unsigned* patch
   return ngp_trilinear_pk(vals, ax, ay, az);
 }
 
-// The render kernel's body: PERSISTENT waves over the ray list of one pipe.
+// The render kernel's body: PERSISTENT waves over the ray list of one render.
 //
 // A wave holds 8 rays (ray position r = lane >> 3, its 8 lanes k = lane & 7) and repeats
 //   march   ngp_march_group: every ray's next K = 8 occupied lattice samples, lane k ends up with the ray's k-th sample;
@@ -1121,13 +1121,11 @@ __device__ inline float srgb_to_linear(float c) {
   return __builtin_amdgcn_exp2f(2.4f * __builtin_amdgcn_logf((c + 0.055f) / 1.055f));
 }
 
-// The last kernel of a render also zeroes the round counters of every pipeline for the NEXT render (everything that
-// reads them has finished by now): no memset launch in front of a render's first kernel.
-struct NgpCounterList { int* p[4]; int n; };
-__device__ __forceinline__ void ngp_resolve_body(const NgpParams& P, const NgpWork& Wk, const NgpCounterList& zl, int blk) {
+// The last kernel of a render also zeroes the render's counter block for the NEXT render (everything that reads it has
+// finished by now): no memset launch in front of a render's first kernel.
+__device__ __forceinline__ void ngp_resolve_body(const NgpParams& P, const NgpWork& Wk, int blk) {
   if (blk == 0)
-    for (int w = 0; w < zl.n; ++w)
-      for (int i = threadIdx.x; i < kCtrWords; i += 256) zl.p[w][i] = 0;
+    for (int i = threadIdx.x; i < kCtrWords; i += 256) Wk.counters[i] = 0;
   // One lane per pixel: it reads the pixel's spp finished rays (contiguous: 16 B x spp, whole lines per lane)
   // and adds them in pass order - the fixed order of a sequential mean.  All passes of a pixel share one ray
   // (snap_to_pixel_centers), so a pixel whose ray misses the box has no finished rays to read: nothing
@@ -1197,20 +1195,18 @@ __device__ __forceinline__ void ngp_resolve_body(const NgpParams& P, const NgpWo
   if (P.out_nz && P.mode != 0) P.out_nz[pix] = (((long long)(depth_x * 255.0f) & 255) != 0) ? 1 : 0;
 }
 
-// ---- the launches.  blockIdx.y = pipe: a render is cut into pipes (slices of its ray enumeration, one by default), a chain
-// carries the pipes of one render, of a frame's two renders (the mask's Depth at the query camera + the reference image's
-// Shade at the reference camera, pixtrack/pose_trackers/pixloc_tracker_r9.py:145-152,207-214) or of K objects tracked in
-// lock-step - every launch carries all of them.  The pipes' parameter records travel by value in the kernel-argument segment
-// while they fit (<= 4: a render, a frame's pair), else they sit in device memory (uploaded from a pinned ring ahead of the
-// chain).  Read-only for the whole chain and addressed uniformly per workgroup: scalar loads either way.
+// ---- the launches.  blockIdx.y = render: a chain carries one render, a frame's two renders (the mask's Depth at the query
+// camera + the reference image's Shade at the reference camera, pixtrack/pose_trackers/pixloc_tracker_r9.py:145-152,207-214)
+// or K objects tracked in lock-step - every launch carries all of them, and all three launches read the same record per
+// render.  The records travel by value in the kernel-argument segment while they fit (<= 4: a render, a frame's pair), else
+// they sit in device memory (uploaded from a pinned ring ahead of the chain).  Read-only for the whole chain and addressed
+// uniformly per workgroup: scalar loads either way.
 // (By value they MUST be the kernel's first parameter: the kernels address them through the kernel-argument segment
 // pointer - indexing the by-value aggregate itself makes the compiler copy all of it to scratch first, 3 KB per lane.  In
 // memory the pointer is a __restrict__ kernel parameter, which is what lets the compiler keep the loads scalar.)
-constexpr int kMaxChainPipes = 4 * PXT_NGP_MAX_BATCH;  // (pxt_ngp::kMaxPipes per render)
 struct NgpBatchItem {
   NgpParams P;
   NgpWork W;
-  NgpCounterList zl;
 };
 template <int NV>
 struct NgpItemsByValue {
@@ -1229,7 +1225,7 @@ __global__ __launch_bounds__(256) void ngp_raygen_kernel_m(const NgpBatchItem* _
   ngp_raygen_body(it.P, it.W, blockIdx.x, gridDim.x);
 }
 
-// MODES: 0 / 1 / 2 = every pipe of the chain renders in that mode; 3 = per pipe (P.mode; a frame's Depth + Shade pair).
+// MODES: 0 / 1 / 2 = every render of the chain is in that mode; 3 = per render (P.mode; a frame's Depth + Shade pair).
 template <int MODES>
 __device__ __forceinline__ void ngp_render_impl(const NgpBatchItem& it, int rays_per_wg) {
   __shared__ half8 s_w[kNumFrags * 64];
@@ -1251,14 +1247,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   ngp_render_impl<MODES>(items[blockIdx.y], rays_per_wg);
 }
 
-// blockIdx.y = render (the items here are per RENDER: the whole view, the shared per-ray result buffers, every counter block)
 __global__ __launch_bounds__(256) void ngp_resolve_kernel_v(const NgpItemsByValue<4> items) {
   const NgpBatchItem& it = ngp_kernarg_item(blockIdx.y);
-  ngp_resolve_body(it.P, it.W, it.zl, blockIdx.x);
+  ngp_resolve_body(it.P, it.W, blockIdx.x);
 }
 __global__ __launch_bounds__(256) void ngp_resolve_kernel_m(const NgpBatchItem* __restrict__ items) {
   const NgpBatchItem& it = items[blockIdx.y];
-  ngp_resolve_body(it.P, it.W, it.zl, blockIdx.x);
+  ngp_resolve_body(it.P, it.W, blockIdx.x);
 }
 
 // Network query at caller-given points (unit tests / debugging): out[n] = (logit, r, g, b).
@@ -1304,7 +1299,7 @@ struct NgpTables {
   unsigned grid_bytes = 0;
   pxt::half8* wfrag = nullptr;
   uint8_t* occ = nullptr;
-  int refs = 1;
+  std::atomic<int> refs{1};  // contexts are created and destroyed from the trackers' threads
 };
 
 struct pxt_ngp {
@@ -1315,12 +1310,8 @@ struct pxt_ngp {
   // scratch of the wavefront renderer, grown on demand (rays = W*H*spp)
   void* scratch = nullptr;
   size_t scratch_rays = 0;
-  size_t scratch_cap = 0;   // rays one pipe's buffers hold
-  int scratch_pipes = 0;    // pipes the scratch was laid out for
-  bool counters_clean = false;  // the previous render's resolve kernel zeroed every pipe's round counters
-  static constexpr int kMaxPipes = 4;
-  pxt::NgpWork work[kMaxPipes];            // independent pipes over equal slices of the rays
-  int pipelines = 0;     // 0: default (PXT_NGP_PIPES or 2); else the number of ray slices a large render is cut into
+  bool counters_clean = false;  // the previous render's resolve kernel zeroed the counter block
+  pxt::NgpWork work;
   int timing = 0;        // > 0: HIP events around the shade-carrying launches of every timing-th render
   long long renders = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // recorded, not yet read
@@ -1437,7 +1428,6 @@ extern "C" int pxt_ngp_create_shared(pxt_ngp* src, pxt_ngp** out_ctx) {
   for (int l = 0; l < kMaxLevels; ++l) ctx->lv[l] = src->lv[l];
   ctx->tab = src->tab;
   ++ctx->tab->refs;
-  ctx->pipelines = src->pipelines;
   if (const int rc = init_camera_slot(ctx)) { pxt_ngp_destroy(ctx); return rc; }
   *out_ctx = ctx;
   return PXT_OK;
@@ -1484,16 +1474,11 @@ extern "C" int pxt_ngp_query(pxt_ngp* ctx, const float* pos, const float* dir, i
   return PXT_OK;
 }
 
-// Carves the renderer's scratch for `rays` rays out of one allocation (grown on demand).  Per-pipe: the ray list (id,
-// start, direction) sized for the pipe's whole slice of the rays (every ray of a slice may hit the box: `cap` = the largest
-// slice) and a counter block; the per-ray result buffers indexed by ray id are shared by the pipes of the render.
-static int ensure_scratch(pxt_ngp* ctx, size_t rays, int n_pipe) {
-  size_t cap = (rays + (size_t)n_pipe - 1) / (size_t)n_pipe + 2 * kTile;
-  if (ctx->scratch && ctx->scratch_rays >= rays && ctx->scratch_cap >= cap && ctx->scratch_pipes >= n_pipe) return PXT_OK;
-  // grow only: a context that alternates between pipe counts keeps the larger layout
-  cap = std::max(cap, ctx->scratch_cap);
-  n_pipe = std::max(n_pipe, ctx->scratch_pipes);
-  rays = std::max(rays, ctx->scratch_rays);
+// Carves the renderer's scratch for `rays` rays out of one allocation (grown on demand, never shrunk): the ray list (id,
+// start, direction) sized for every ray hitting the box, a counter block, and the per-ray result buffers indexed by ray id.
+static int ensure_scratch(pxt_ngp* ctx, size_t rays) {
+  if (ctx->scratch && ctx->scratch_rays >= rays) return PXT_OK;
+  const size_t cap = rays + 2 * kTile;
   if (ctx->scratch) {
     hipError_t e0 = hipDeviceSynchronize();
     (void)e0;
@@ -1503,27 +1488,19 @@ static int ensure_scratch(pxt_ngp* ctx, size_t rays, int n_pipe) {
   auto al = [](size_t x) { return (x + 255) / 256 * 256; };
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = al(off + bytes); return o; };
-  struct Offs { size_t rid, t0, dir, cnt; } o[pxt_ngp::kMaxPipes];
-  for (int w = 0; w < n_pipe; ++w) {
-    o[w].rid = take(cap * 4); o[w].t0 = take(cap * 4); o[w].dir = take(cap * 16);
-    o[w].cnt = take(kCtrWords * sizeof(int));
-  }
+  const size_t o_rid = take(cap * 4), o_t0 = take(cap * 4), o_dir = take(cap * 16), o_cnt = take(kCtrWords * sizeof(int));
   const size_t o_sppd = take(rays * 4), o_spp = take(rays * 16);
   hipError_t e = hipMalloc(&ctx->scratch, off);
   if (e != hipSuccess) { set_last_error("hipMalloc(ngp scratch)", e); ctx->scratch_rays = 0; return PXT_E_HIP; }
   char* b = (char*)ctx->scratch;
-  for (int w = 0; w < n_pipe; ++w) {
-    NgpWork& W = ctx->work[w];
-    W.rid = (unsigned*)(b + o[w].rid);
-    W.t0 = (float*)(b + o[w].t0);
-    W.dir = (float4*)(b + o[w].dir);
-    W.counters = (int*)(b + o[w].cnt);
-    W.sppbuf = (float4*)(b + o_spp);
-    W.sppbuf_d = (float*)(b + o_sppd);
-  }
+  NgpWork& W = ctx->work;
+  W.rid = (unsigned*)(b + o_rid);
+  W.t0 = (float*)(b + o_t0);
+  W.dir = (float4*)(b + o_dir);
+  W.counters = (int*)(b + o_cnt);
+  W.sppbuf = (float4*)(b + o_spp);
+  W.sppbuf_d = (float*)(b + o_sppd);
   ctx->scratch_rays = rays;
-  ctx->scratch_cap = cap;
-  ctx->scratch_pipes = n_pipe;
   ctx->counters_clean = false;
   return PXT_OK;
 }
@@ -1556,7 +1533,7 @@ static int fill_view(const pxt_ngp* ctx, const pxt_ngp_view* v, int mode, float*
   return PXT_OK;
 }
 
-// ---- a chain of K renders: raygen -> render -> resolve, each ONE launch for all pipes of all K renders.
+// ---- a chain of K renders: raygen -> render -> resolve, each ONE launch for all K renders.
 namespace {
 
 struct ChainRender {
@@ -1575,7 +1552,6 @@ struct NgpStageSlot {
   hipEvent_t copied = nullptr;
 };
 constexpr int kNgpStageSlots = 4;
-constexpr int kChainItems = kMaxChainPipes + PXT_NGP_MAX_BATCH;  // pipe records, then one record per render (resolve)
 
 void launch_render(int modes, const NgpItemsByValue<4>* pv, const NgpBatchItem* pm, dim3 grid, int rays_per_wg, hipStream_t s) {
   const dim3 blk(256);
@@ -1591,32 +1567,23 @@ void launch_render(int modes, const NgpItemsByValue<4>* pv, const NgpBatchItem* 
 #undef PXT_LAUNCH_RENDER
 }
 
-// ws_dev: device memory for the parameter records when they do not fit the kernel-argument segment (more than 4 pipes).
+// ws_dev: device memory for the parameter records when they do not fit the kernel-argument segment (more than 4 renders).
 int run_chain(ChainRender* R, int K, hipStream_t s0, void* ws_dev) {
-  // Workgroups of the render kernel per pipe (PXT_NGP_GRID) and rays per workgroup below which fewer take part
+  // Workgroups of the render kernel per render (PXT_NGP_GRID) and rays per workgroup below which fewer take part
   // (PXT_NGP_GRID_DIV): measured on the benchmark view (640 x 480 x 8 spp, ~345 k rays in the list, 4 waves per SIMD = 1024
   // resident workgroups): 2048 / 3072 / 4096 / 6144 / 8192 workgroups = 0.75 / 0.71 / 0.68 / 0.71 / 0.74 ms per render
   // (profiles/r06_experiments.md).  The grid is the queue: more waves than are resident, each with a short share.
   static const int g_render = env_int("PXT_NGP_GRID", 16384, 64, 16384), g_div = env_int("PXT_NGP_GRID_DIV", 64, 1, 1 << 20),
                    g_raygen = env_int("PXT_NGP_GRID_RAYGEN", 1024, 64, 8192);
-  static const int env_pipes = env_int("PXT_NGP_PIPES", 1, 1, pxt_ngp::kMaxPipes);
-  struct Pipe { int render, w; };
-  Pipe pipes[kMaxChainPipes];
-  int n_pipes = 0, n_per[PXT_NGP_MAX_BATCH];
-  for (int k = 0; k < K; ++k) {
-    pxt_ngp* ctx = R[k].ctx;
-    n_per[k] = std::min(std::max(ctx->pipelines > 0 ? ctx->pipelines : env_pipes, 1), pxt_ngp::kMaxPipes);
-    if (n_pipes + n_per[k] > kMaxChainPipes) return PXT_E_ARG;
-    if (const int rc = ensure_scratch(ctx, R[k].rays, n_per[k])) return rc;
-    for (int w = 0; w < n_per[k]; ++w, ++n_pipes) pipes[n_pipes] = {k, w};
-  }
-  const bool by_value = n_pipes <= 4;
+  for (int k = 0; k < K; ++k)
+    if (const int rc = ensure_scratch(R[k].ctx, R[k].rays)) return rc;
+  const bool by_value = K <= 4;
   if (!by_value && !ws_dev) return PXT_E_ARG;
   // the records
   static thread_local NgpStageSlot stage[16][kNgpStageSlots];
   static thread_local int stage_next[16] = {0};
-  NgpItemsByValue<4> pv{}, rv{};  // (by_value: pipes / renders)
-  NgpBatchItem* rec = nullptr;    // (!by_value: the pinned staging block, pipes then renders)
+  NgpItemsByValue<4> pv{};      // (by_value)
+  NgpBatchItem* rec = nullptr;  // (!by_value: the pinned staging block)
   NgpStageSlot* slot = nullptr;
   if (!by_value) {
     int dev_id = 0;
@@ -1625,7 +1592,7 @@ int run_chain(ChainRender* R, int K, hipStream_t s0, void* ws_dev) {
     slot = &stage[dev_id][stage_next[dev_id]];
     stage_next[dev_id] = (stage_next[dev_id] + 1) % kNgpStageSlots;
     if (!slot->host) {
-      PXT_HIP_CHECK(hipHostMalloc((void**)&slot->host, kChainItems * sizeof(NgpBatchItem), hipHostMallocDefault));
+      PXT_HIP_CHECK(hipHostMalloc((void**)&slot->host, PXT_NGP_MAX_BATCH * sizeof(NgpBatchItem), hipHostMallocDefault));
       PXT_HIP_CHECK(hipEventCreateWithFlags(&slot->copied, hipEventDisableTiming));
     } else {
       PXT_HIP_CHECK(hipEventSynchronize(slot->copied));
@@ -1637,39 +1604,21 @@ int run_chain(ChainRender* R, int K, hipStream_t s0, void* ws_dev) {
     pxt_ngp* ctx = R[k].ctx;
     if (R[k].P.mode != modes) modes = 3;
     max_pixels = std::max(max_pixels, R[k].P.W * R[k].P.H);
-    NgpBatchItem& ri = by_value ? rv.it[k] : rec[n_pipes + k];
-    ri.P = R[k].P;
-    ri.P.enum_lo = 0;
-    ri.P.enum_hi = (long long)R[k].rays;
-    ri.W = ctx->work[0];
-    ri.zl.n = std::min(ctx->scratch_pipes, 4);
-    for (int w = 0; w < 4; ++w) ri.zl.p[w] = w < ri.zl.n ? ctx->work[w].counters : nullptr;
-    if (!ctx->counters_clean)
-      for (int w = 0; w < ctx->scratch_pipes; ++w)
-        PXT_HIP_CHECK(hipMemsetAsync(ctx->work[w].counters, 0, kCtrWords * sizeof(int), s0));
-    ctx->counters_clean = false;  // (an error return below leaves them to the next render's memsets)
-  }
-  for (int p = 0; p < n_pipes; ++p) {
-    const int k = pipes[p].render, w = pipes[p].w, np = n_per[k];
-    NgpBatchItem& it = by_value ? pv.it[p] : rec[p];
+    NgpBatchItem& it = by_value ? pv.it[k] : rec[k];
     it.P = R[k].P;
-    const long long total = (long long)R[k].rays;
-    const long long per = np > 1 ? ((total / np + kTile - 1) / kTile) * kTile : total;
-    it.P.enum_lo = std::min(total, per * w);
-    it.P.enum_hi = (w == np - 1) ? total : std::min(total, per * (w + 1));
-    it.W = R[k].ctx->work[w];
-    it.zl.n = 0;
+    it.W = ctx->work;
+    if (!ctx->counters_clean) PXT_HIP_CHECK(hipMemsetAsync(ctx->work.counters, 0, kCtrWords * sizeof(int), s0));
+    ctx->counters_clean = false;  // (an error return below leaves them to the next render's memset)
   }
-  const NgpBatchItem *pm = nullptr, *rm = nullptr;
+  const NgpBatchItem* pm = nullptr;
   if (!by_value) {
-    PXT_HIP_CHECK(hipMemcpyAsync(ws_dev, rec, (size_t)(n_pipes + K) * sizeof(NgpBatchItem), hipMemcpyHostToDevice, s0));
+    PXT_HIP_CHECK(hipMemcpyAsync(ws_dev, rec, (size_t)K * sizeof(NgpBatchItem), hipMemcpyHostToDevice, s0));
     PXT_HIP_CHECK(hipEventRecord(slot->copied, s0));
     pm = (const NgpBatchItem*)ws_dev;
-    rm = pm + n_pipes;
   }
   const dim3 blk(256);
-  if (by_value) hipLaunchKernelGGL(ngp_raygen_kernel_v, dim3(g_raygen, n_pipes), blk, 0, s0, pv);
-  else hipLaunchKernelGGL(ngp_raygen_kernel_m, dim3(g_raygen, n_pipes), blk, 0, s0, pm);
+  if (by_value) hipLaunchKernelGGL(ngp_raygen_kernel_v, dim3(g_raygen, K), blk, 0, s0, pv);
+  else hipLaunchKernelGGL(ngp_raygen_kernel_m, dim3(g_raygen, K), blk, 0, s0, pm);
   // the render launch is the one the timing events bracket (bench.py's roofline)
   pxt_ngp* tctx = R[0].ctx;
   const bool timed = K == 1 && tctx->timing > 0 && (tctx->renders++ % tctx->timing) == 0;
@@ -1685,14 +1634,14 @@ int run_chain(ChainRender* R, int K, hipStream_t s0, void* ws_dev) {
     }
     PXT_HIP_CHECK(hipEventRecord(e0, s0));
   }
-  launch_render(modes, by_value ? &pv : nullptr, pm, dim3(g_render, n_pipes), g_div, s0);
+  launch_render(modes, by_value ? &pv : nullptr, pm, dim3(g_render, K), g_div, s0);
   if (e0) {
     PXT_HIP_CHECK(hipEventRecord(e1, s0));
     tctx->events.emplace_back(e0, e1);
   }
   const dim3 rgrid((max_pixels + 255) / 256, K);
-  if (by_value) hipLaunchKernelGGL(ngp_resolve_kernel_v, rgrid, blk, 0, s0, rv);
-  else hipLaunchKernelGGL(ngp_resolve_kernel_m, rgrid, blk, 0, s0, rm);
+  if (by_value) hipLaunchKernelGGL(ngp_resolve_kernel_v, rgrid, blk, 0, s0, pv);
+  else hipLaunchKernelGGL(ngp_resolve_kernel_m, rgrid, blk, 0, s0, pm);
   PXT_HIP_CHECK(hipGetLastError());
   for (int k = 0; k < K; ++k) R[k].ctx->counters_clean = true;
   return PXT_OK;
@@ -1752,7 +1701,7 @@ extern "C" int pxt_ngp_render_frame(pxt_ngp* ctx, const pxt_ngp_view* v, int32_t
 
 extern "C" int64_t pxt_ngp_batch_workspace_bytes(int32_t n_renders) {
   if (n_renders < 1 || n_renders > PXT_NGP_MAX_BATCH) return PXT_E_ARG;
-  return (int64_t)((size_t)(pxt_ngp::kMaxPipes + 1) * n_renders * sizeof(NgpBatchItem) + 255) / 256 * 256;  // pipes + 1 resolve record each
+  return (int64_t)(((size_t)n_renders * sizeof(NgpBatchItem) + 255) / 256 * 256);  // one record per render
 }
 
 // K renders of K contexts - a frame's Depth + Shade pair, or K objects tracked in lock-step - as ONE chain of three launches.
@@ -1777,12 +1726,6 @@ extern "C" int pxt_ngp_render_frame_batch(pxt_ngp* const* ctxs, const pxt_ngp_vi
     if (camera_from_slot) R[k].P.cam_dev = ctxs[k]->cam_dev;
   }
   return run_chain(R, K, (hipStream_t)stream, batch_workspace);
-}
-
-extern "C" int pxt_ngp_set_pipelines(pxt_ngp* ctx, int32_t n) {
-  if (!ctx || n < 0 || n > pxt_ngp::kMaxPipes) return PXT_E_ARG;
-  ctx->pipelines = n;
-  return PXT_OK;
 }
 
 extern "C" int pxt_ngp_timing_enable(pxt_ngp* ctx, int32_t enable) {

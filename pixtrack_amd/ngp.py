@@ -342,7 +342,6 @@ class Testbed:
         self._stats = None
         self.stats_accum = None
         self.n_renders = 0
-        self._pipelines = 0  # what set_pipelines() asked for (0: the library default); per-call overrides restore THIS
         self._cam_ring = None  # pinned camera records of pose-driven renders (see _next_cam_out)
         self._cam_next = 0
 
@@ -411,6 +410,11 @@ class Testbed:
         c = self._ctx_side
         return int(c.value) if hasattr(c, "value") else int(c)
 
+    def _check_renderable(self):
+        assert self._ctx is not None, "load_snapshot first"
+        if not self.snap_to_pixel_centers:
+            raise _lib.PxtError("only snap_to_pixel_centers=True is implemented (ingp_utils.py:36)")
+
     def set_nerf_camera_matrix(self, nerf_c2w_3x4):
         assert self._snap is not None, "load_snapshot first"
         self._cam_ngp = nerf_matrix_to_ngp(np.asarray(nerf_c2w_3x4), self._snap.scale, self._snap.offset)
@@ -430,26 +434,16 @@ class Testbed:
         return v
 
     def render_device(self, width: int, height: int, spp: int = 8, linear: bool = True,
-                      collect_stats: bool = False, side: bool = False, pipelines: int = 0) -> torch.Tensor:
-        """float32 [H, W, 4] on the device, linear premultiplied RGBA.  ``side`` / ``pipelines``: as
-        render_from_pose_device (two renders of different views side by side on two streams)."""
+                      collect_stats: bool = False) -> torch.Tensor:
+        """float32 [H, W, 4] on the device, linear premultiplied RGBA."""
         assert linear, "pixtrack renders with linear=True (run_vis_on_poses.py:51)"
-        assert self._ctx is not None, "load_snapshot first"
-        if not self.snap_to_pixel_centers:
-            raise _lib.PxtError("only snap_to_pixel_centers=True is implemented (ingp_utils.py:36)")
+        self._check_renderable()
         out = torch.empty(height, width, 4, device=self.device, dtype=torch.float32)
         stats = self.stats_accum  # running totals across launches when set (bench)
         if collect_stats:
             stats = torch.zeros(4, dtype=torch.int64, device=self.device)
-        ctx = self._side_ctx_int() if side else self._ctx_int()
-        if pipelines and not side:
-            _lib.check(_lib.lib().pxt_ngp_set_pipelines(self._ctx, int(pipelines)), "pxt_ngp_set_pipelines")
-        try:
-            ops.ngp_render(ctx, self._view_for(width, height), int(width), int(height), int(spp),
-                           int(self.render_mode), out, stats)
-        finally:
-            if pipelines and not side:
-                _lib.check(_lib.lib().pxt_ngp_set_pipelines(self._ctx, self._pipelines), "pxt_ngp_set_pipelines")
+        ops.ngp_render(self._ctx_int(), self._view_for(width, height), int(width), int(height), int(spp),
+                       int(self.render_mode), out, stats)
         if collect_stats:
             self._stats = stats
         self.n_renders += 1
@@ -458,9 +452,7 @@ class Testbed:
     def render_both_device(self, width: int, height: int, spp: int = 8):
         """(Shade RGBA, Depth RGBA) of the current view from ONE march; each equals what
         render_device returns in the corresponding render_mode, bit for bit."""
-        assert self._ctx is not None, "load_snapshot first"
-        if not self.snap_to_pixel_centers:
-            raise _lib.PxtError("only snap_to_pixel_centers=True is implemented (ingp_utils.py:36)")
+        self._check_renderable()
         rgba = torch.empty(height, width, 4, device=self.device, dtype=torch.float32)
         depth = torch.empty(height, width, 4, device=self.device, dtype=torch.float32)
         ops.ngp_render_both(self._ctx_int(), self._view_for(width, height), int(width), int(height), int(spp),
@@ -483,9 +475,7 @@ class Testbed:
         ENQUEUED refinement (optimizer.PendingLM.buf); the camera is derived from it on the device, in stream
         order.  Returns (rgba, depth, cam_out): cam_out (pinned, 16 floats) receives the 12 camera floats the
         render used and, last, cam_out[12] = 1."""
-        assert self._ctx is not None, "load_snapshot first"
-        if not self.snap_to_pixel_centers:
-            raise _lib.PxtError("only snap_to_pixel_centers=True is implemented (ingp_utils.py:36)")
+        self._check_renderable()
         rgba = torch.empty(height, width, 4, device=self.device, dtype=torch.float32)
         depth = torch.empty(height, width, 4, device=self.device, dtype=torch.float32)
         cam_out = self._next_cam_out()
@@ -494,29 +484,6 @@ class Testbed:
         self.n_renders += 1
         return rgba, depth, cam_out
 
-    def render_from_pose_device(self, width: int, height: int, spp: int, pose_record: torch.Tensor, conv: list,
-                                side: bool = False, pipelines: int = 0):
-        """render_device (in the current render_mode) for a pose that is still on the device; see
-        render_both_from_pose_device.  Returns (rgba, cam_out).  ``side``: through the second context
-        (_side_ctx_int; the caller puts the call on another stream); ``pipelines``: ray slices rendered side by
-        side by THIS call (0 = the default)."""
-        assert self._ctx is not None, "load_snapshot first"
-        if not self.snap_to_pixel_centers:
-            raise _lib.PxtError("only snap_to_pixel_centers=True is implemented (ingp_utils.py:36)")
-        out = torch.empty(height, width, 4, device=self.device, dtype=torch.float32)
-        cam_out = self._next_cam_out()
-        ctx = self._side_ctx_int() if side else self._ctx_int()
-        if pipelines and not side:
-            _lib.check(_lib.lib().pxt_ngp_set_pipelines(self._ctx, int(pipelines)), "pxt_ngp_set_pipelines")
-        try:
-            ops.ngp_render_both_from_pose(ctx, self._view_for(width, height), pose_record, conv, int(width),
-                                          int(height), int(spp), int(self.render_mode), out, None, cam_out, self.stats_accum)
-        finally:
-            if pipelines and not side:
-                _lib.check(_lib.lib().pxt_ngp_set_pipelines(self._ctx, self._pipelines), "pxt_ngp_set_pipelines")
-        self.n_renders += 1
-        return out, cam_out
-
     def camera_slot(self, side: bool = False) -> int:
         """Device address of the context's 12-float camera slot (pxt_ngp_camera_slot): the LM kernel's epilogue writes
         the next render's camera there (ops.lm_refine cam_slots) and render_frame_device(from_slot=True) reads it."""
@@ -524,15 +491,13 @@ class Testbed:
         return int(_lib.lib().pxt_ngp_camera_slot(ctx))
 
     def render_frame_device(self, width: int, height: int, spp: int = 8, mode: int = 2, from_slot: bool = False,
-                            side: bool = False, pipelines: int = 0, want_float: bool = False):
+                            want_float: bool = False):
         """One render whose last kernel writes what the tracking loop consumes (pxt_ngp_render_frame): returns a dict with
         ``rgb_u8`` uint8 [H, W, 3] (modes 0 / 2: get_nerf_image's image of the Shade render) and ``depth_nz`` uint8 [H, W]
         (modes 1 / 2: get_mask's `uint8(depth * 255) != 0` plane), plus the float images ``rgba`` / ``depth`` when
         ``want_float``.  mode 0 Shade, 1 Depth, 2 both from one march.  ``from_slot``: the camera is whatever the LM
-        kernel ahead in the stream wrote into camera_slot(side) - the render of a pose the host has not seen yet."""
-        assert self._ctx is not None, "load_snapshot first"
-        if not self.snap_to_pixel_centers:
-            raise _lib.PxtError("only snap_to_pixel_centers=True is implemented (ingp_utils.py:36)")
+        kernel ahead in the stream wrote into camera_slot() - the render of a pose the host has not seen yet."""
+        self._check_renderable()
         dev, out = self.device, {}
         if mode != 1:
             out["rgb_u8"] = torch.empty(height, width, 3, device=dev, dtype=torch.uint8)
@@ -542,23 +507,16 @@ class Testbed:
             out["rgba"] = torch.empty(height, width, 4, device=dev, dtype=torch.float32)
             if mode == 2:
                 out["depth"] = torch.empty(height, width, 4, device=dev, dtype=torch.float32)
-        ctx = self._side_ctx_int() if side else self._ctx_int()
-        if pipelines and not side:
-            _lib.check(_lib.lib().pxt_ngp_set_pipelines(self._ctx, int(pipelines)), "pxt_ngp_set_pipelines")
-        try:
-            ops.ngp_render_frame(ctx, self._view_for(width, height), int(width), int(height), int(spp), int(mode),
-                                 bool(from_slot), out.get("rgba"), out.get("depth"), out.get("rgb_u8"),
-                                 out.get("depth_nz"), self.stats_accum)
-        finally:
-            if pipelines and not side:
-                _lib.check(_lib.lib().pxt_ngp_set_pipelines(self._ctx, self._pipelines), "pxt_ngp_set_pipelines")
+        ops.ngp_render_frame(self._ctx_int(), self._view_for(width, height), int(width), int(height), int(spp), int(mode),
+                             bool(from_slot), out.get("rgba"), out.get("depth"), out.get("rgb_u8"),
+                             out.get("depth_nz"), self.stats_accum)
         self.n_renders += 1
         return out
 
     @staticmethod
     def render_frame_batch_device(testbeds, sizes, spp: int = 8, mode=2, from_slot: bool = False, workspace=None,
                                   sides=None, fovs=None):
-        """render_frame_device for K renders as ONE staged chain of launches (pxt_ngp_render_frame_batch): K testbeds (K objects,
+        """render_frame_device for K renders as ONE chain of launches (pxt_ngp_render_frame_batch): K testbeds (K objects,
         each with its own NeRF), or - ``sides[k]`` true - a testbed's second context (the second of a frame's two renders of one
         NeRF).  ``sizes[k]`` = (width, height); ``mode``: one int for all or one per render; ``fovs[k]`` (optional): the
         render's field of view instead of the testbed's current one.  Every testbed's current camera (or, with
@@ -573,9 +531,7 @@ class Testbed:
         dev = testbeds[0].device
         outs, views, flat_sizes, ctxs = [], [], [], []
         for k, (tb, (w, h)) in enumerate(zip(testbeds, sizes)):
-            assert tb._ctx is not None, "load_snapshot first"
-            if not tb.snap_to_pixel_centers:
-                raise _lib.PxtError("only snap_to_pixel_centers=True is implemented (ingp_utils.py:36)")
+            tb._check_renderable()
             o = {}
             if modes[k] != 1:
                 o["rgb_u8"] = torch.empty(h, w, 3, device=dev, dtype=torch.uint8)
@@ -617,18 +573,12 @@ class Testbed:
     def render(self, width: int, height: int, spp: int = 8, linear: bool = True) -> np.ndarray:
         return self.render_device(width, height, spp, linear).cpu().numpy()
 
-    def set_pipelines(self, n: int = 0):
-        """Number of ray slices (pipes) a large render is cut into (0: default of 2; 1: every launch carries one stage).
-        Per-call `pipelines=` overrides of render_device / render_from_pose_device return to this value afterwards."""
-        _lib.check(_lib.lib().pxt_ngp_set_pipelines(self._ctx, int(n)), "pxt_ngp_set_pipelines")
-        self._pipelines = int(n)
-
     def timing_enable(self, every_nth: int = 1):
-        """HIP events around the launches that carry a shade stage (ngp_stage_kernel) of every ``every_nth``-th render (0 / False: off)."""
+        """HIP events around the render kernel launch of every ``every_nth``-th single render (0 / False: off)."""
         _lib.check(_lib.lib().pxt_ngp_timing_enable(self._ctx, int(every_nth)), "pxt_ngp_timing_enable")
 
     def timing_read(self):
-        """(total ms, launches) of the shade-carrying launches since the last read (HIP events on the render stream)."""
+        """(total ms, launches) of the timed render kernel launches since the last read (HIP events on the render stream)."""
         ms, n = C.c_float(0), C.c_int32(0)
         _lib.check(_lib.lib().pxt_ngp_timing_read(self._ctx, C.byref(ms), C.byref(n)), "pxt_ngp_timing_read")
         return float(ms.value), int(n.value)

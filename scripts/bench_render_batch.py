@@ -1,7 +1,6 @@
-"""K renders (the eight config/*.sh boxes, 640x480, spp 8, Shade + Depth in one march) one after the other - two pipelines
-each (the one-object tracker's setting) or one (the lock-step groups' setting) - against ONE batched chain
-(pxt_ngp_render_frame_batch), and two batched chains of K / 2 side by side on two streams (what two lock-step groups do).
-PXT_NGP_BATCH_GRID=<n> overrides the per-object grid of the batched grid-stride kernels."""
+"""K renders (the eight config/*.sh boxes, 640x480, spp 8, Shade + Depth in one march) one after the other, against ONE
+batched chain (pxt_ngp_render_frame_batch), and two batched chains of K / 2 side by side on two streams (what two lock-step
+groups do)."""
 import math
 import sys
 from pathlib import Path
@@ -64,8 +63,7 @@ def main():
         sizes = [(W, H)] * K
         ws = torch.empty(Testbed.batch_workspace_bytes(K), dtype=torch.uint8, device=dev)
         ws2 = torch.empty(Testbed.batch_workspace_bytes(K), dtype=torch.uint8, device=dev)
-        t2 = timed(lambda: [tb.render_frame_device(W, H, spp, mode=2) for tb in sub])
-        t1 = timed(lambda: [tb.render_frame_device(W, H, spp, mode=2, pipelines=1) for tb in sub])
+        t1 = timed(lambda: [tb.render_frame_device(W, H, spp, mode=2) for tb in sub])
         tb_ = timed(lambda: Testbed.render_frame_batch_device(sub, sizes, spp, mode=2, workspace=ws))
 
         def two_streams():
@@ -85,16 +83,16 @@ def main():
             with torch.cuda.stream(side):
                 side.wait_event(ev)
                 for tb in sub[K // 2:]:
-                    tb.render_frame_device(W, H, spp, mode=2, pipelines=1)
+                    tb.render_frame_device(W, H, spp, mode=2)
                 ej = torch.cuda.Event()
                 ej.record(side)
             for tb in sub[:K // 2]:
-                tb.render_frame_device(W, H, spp, mode=2, pipelines=1)
+                tb.render_frame_device(W, H, spp, mode=2)
             torch.cuda.current_stream().wait_event(ej)
 
         tss = timed(two_streams_single)
         tbb = timed(two_streams)
-        print(f"K={K}: one after the other, 2 pipelines {t2:.3f} ms ({t2 / K:.3f} per render) | 1 pipeline {t1:.3f} ({t1 / K:.3f}) | "
+        print(f"K={K}: one after the other {t1:.3f} ms ({t1 / K:.3f} per render) | "
               f"two streams of single renders {tss:.3f} ({tss / K:.3f}) | ONE batched chain {tb_:.3f} ({tb_ / K:.3f}) | "
               f"two batched chains on two streams {tbb:.3f} ({tbb / K:.3f})", flush=True)
 

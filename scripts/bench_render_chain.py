@@ -2,8 +2,8 @@
   both   Shade + Depth in one march (the headline frame's render),
   pair   a frame's Depth 640x480 + Shade 960x720 (the r9 phone shape) as one chain (render_frame_pair_device),
   two    the same two renders one after the other.
-The chain's knobs are environment variables read once per process (PXT_NGP_PIPES, PXT_NGP_G_SHADE / _MARCH / _INIT / _COMPACT,
-PXT_NGP_ROUNDS, PXT_NGP_TAIL_GRID): run one process per setting.
+The chain's knobs are environment variables read once per process (PXT_NGP_GRID, PXT_NGP_GRID_DIV, PXT_NGP_GRID_RAYGEN,
+PXT_NGP_COOP): run one process per setting.
 
     python scripts/bench_render_chain.py [n_views]
 """

@@ -1,5 +1,5 @@
 """SHA-256 digests of one NeRF render pair, its depth mask and a two-image UNet pass on seeded inputs: run under
-different run-time knobs (PXT_NGP_FUSE_COMPACT_MARCH, PXT_UNET_STREAMS, PXT_MASK_BYTES, PXT_NGP_PIPES) the digests
+different run-time knobs (PXT_NGP_GRID / _GRID_DIV / _GRID_RAYGEN, PXT_NGP_COOP, PXT_UNET_STREAMS, PXT_MASK_BYTES) the digests
 must not change (tests/test_variants_gpu.py).  python scripts/variant_checksum.py [W H]"""
 import hashlib, math, sys
 from pathlib import Path

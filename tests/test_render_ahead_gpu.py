@@ -101,8 +101,8 @@ def test_a_queued_render_is_not_used_after_the_view_settings_changed(device):
 
 
 def test_one_pipeline_render_with_the_box_filling_the_view(device):
-    """A render below 2^19 rays runs as ONE pipeline over all rays: its buffers must hold every ray (a camera
-    close to the box sees it in nearly every pixel; the first layout sized a pipeline for half the rays)."""
+    """A render's ray list must hold every ray (a camera close to the box sees it in nearly every pixel; an early
+    layout sized the list for half the rays)."""
     from pixtrack_amd.synthetic import look_at_pose
 
     tb = Testbed(device=device)

@@ -48,7 +48,7 @@ def _objects(device):
 @pytest.mark.parametrize("mode", [2, 0, 1])
 def test_batched_renders_equal_the_single_renders(device, mode):
     objs = _objects(device)
-    want = [tb.render_frame_device(w, h, 4, mode=mode, pipelines=1) for tb, (w, h) in objs]
+    want = [tb.render_frame_device(w, h, 4, mode=mode) for tb, (w, h) in objs]
     ws = torch.empty(Testbed.batch_workspace_bytes(len(objs)), dtype=torch.uint8, device=device)
     for rep in range(2):  # (the second pass starts from counters the batch's own resolve kernel zeroed)
         got = Testbed.render_frame_batch_device([tb for tb, _ in objs], [s for _, s in objs], 4, mode=mode, workspace=ws)
@@ -59,7 +59,7 @@ def test_batched_renders_equal_the_single_renders(device, mode):
                 assert torch.equal(g[key], w_[key]), (mode, rep, k, key)
     if mode != 1:
         assert all(0.01 < float((w_["rgb_u8"].float().mean(-1) > 5).float().mean()) < 0.99 for w_ in want)  # (an object on black)
-    # a single render after the batch (two pipelines again) still sees clean counters
+    # a single render after the batch still sees clean counters
     tb, (w, h) = objs[0]
     again = tb.render_frame_device(w, h, 4, mode=mode)
     for key in again:
@@ -67,7 +67,7 @@ def test_batched_renders_equal_the_single_renders(device, mode):
 
 
 def test_batched_render_full_size_and_stats(device):
-    """640 x 480 x 8 spp (two-pipeline size for a single render): image and sample counts equal the single renders'."""
+    """640 x 480 x 8 spp: image and sample counts equal the single renders'."""
     lo, hi = np.array(PREMIER_PROTEIN_AABB)
     objs = [(_testbed(device, 21 + k, PREMIER_PROTEIN_AABB, 640, 1.6 + 0.2 * k, d), (640, 480))
             for k, d in enumerate(([0.9, 0.5, 0.3], [0.1, 0.3, 1.0], [-0.8, 0.2, 0.1]))]
