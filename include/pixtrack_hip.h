@@ -291,7 +291,7 @@ int pxt_conv3x3_nhwc_f16(const void* in, int32_t H, int32_t W, int32_t Cin, cons
  *   pxt_conv3x3_pack_weights   [Cout][3][3][Cin] fp16 (device) -> packed (device)
  *   pxt_conv3x3_packed         in / out as above; pool_out (optional) [H/2][W/2][Cout] receives the
  *                              2x2 max-pool of the output; cfg 0 = automatic, 1..6 = tile
- *                              configuration (csrc/pxt_unet.hip kV2Cfgs); splits > 1 = split-K over
+ *                              configuration (csrc/pxt_unet.hip kTileCfgs); splits > 1 = split-K over
  *                              the input-channel chunks with splitk_ws >= splits*H*W*Cout*4 bytes. */
 int64_t pxt_conv3x3_packed_bytes(int32_t Cin, int32_t Cout);
 int pxt_conv3x3_pack_weights(const void* weights, int32_t Cin, int32_t Cout, void* packed, void* stream);

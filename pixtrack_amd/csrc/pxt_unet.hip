@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 namespace pxt {
@@ -515,51 +516,99 @@ using namespace pxt;
 
 namespace {
 
-// ---- launch plan of one 3x3 layer ------------------------------------------------------------
-// Tile configurations of conv3x3_v2_kernel<CW, PBW, WC, WP>: a workgroup (4 waves, WC x WP) covers
-// TH = 2*PBW*WP rows x 16 columns of pixels and BNC = 32*CW*WC output channels.
-struct V2Cfg { int CW, PBW, WC, WP, KC, KS; };
+// ---- run-time knobs: read once, on first use -------------------------------------------------------------------
+// PXT_CONV_PLAN="layer:cfg:splits;..." (experiment) overrides the tile configuration / split-K factor of pyramid layer `layer`
+// (0 in a field = keep the default).  Set at all (even to something that does not parse), it turns tile skipping off.
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+std::vector<std::array<int, 3>> parse_plan(const char* e) {
+  std::vector<std::array<int, 3>> v;
+  for (; e && *e; e = strchr(e, ';') ? strchr(e, ';') + 1 : nullptr) {
+    std::array<int, 3> t = {0, 0, 0};
+    if (sscanf(e, "%d:%d:%d", &t[0], &t[1], &t[2]) >= 2) v.push_back(t);
+  }
+  return v;
+}
+struct Knobs {
+  int streams = env_int("PXT_UNET_STREAMS", 2);  // < 2: a batch of two images runs as one batched pass, not two passes
+  bool merge_heads = env_int("PXT_UNET_MERGE_HEADS", 1) != 0;  // the two coarse heads of a pass in one launch
+  bool skip = env_int("PXT_UNET_SKIP", 1) != 0;                // constant-tile skipping
+  bool fuse_first = env_int("PXT_UNET_FUSE_FIRST", 1) != 0;    // the first layer computed in the second one's staging
+  const char* plan_env = getenv("PXT_CONV_PLAN");
+  std::vector<std::array<int, 3>> plan = parse_plan(plan_env);
+  bool debug = getenv("PXT_CONV_DEBUG") != nullptr;  // one stderr line per convolution launched
+};
+const Knobs& knobs() { static const Knobs k; return k; }
+
+// ---- encoder geometry --------------------------------------------------------------------------------------------
+// Block b runs conv layers first .. first + n - 1 (cin -> c channels) at 1 / 2^b of the input resolution; the last layer
+// of blocks 0-3 also writes the next block's pooled input.  Layers 13..16 are the decoder.
+struct EncBlock { int first, n, cin, c; };
+constexpr int kNumEncLayers = 13;
+constexpr EncBlock kEnc[5] = {{0, 2, 3, 64}, {2, 2, 64, 128}, {4, 3, 128, 256}, {7, 3, 256, 512}, {10, 3, 512, 512}};
+inline int enc_block(int li) { int b = 4; while (kEnc[b].first > li) --b; return b; }
+inline bool enc_last(int li) { return li == kEnc[enc_block(li)].first + kEnc[enc_block(li)].n - 1; }
+
+// The first layer is computed inside the second layer's staging (pxt_conv_v2.h FusedFirst): its 39-MB output per image is
+// never written.  PXT_UNET_FUSE_FIRST=0 keeps the separate launch (A/B, tests/test_variants_gpu.py).
+inline bool fuses_first(const pxt_unet* ctx) { return knobs().fuse_first && ctx->conv[1].cin == 64 && ctx->conv[1].cout == 64; }
+
+// ---- tile configurations of a 3x3 layer ----------------------------------------------------------------------------
+// A workgroup of conv3x3_v2_kernel<CW, PBW, WC, WP> (pxt_conv_v2.h, 4 waves WC x WP) or of conv3x3_v3_kernel<CW, PBW, WC,
+// WP, KC, .., KS> (pxt_conv_v3.h: pixel fragments shared by the vertical taps, filter fragments through LDS, KC-channel
+// chunks, 4 * KS waves) covers TH = 2*PBW*WP rows x 16 columns of pixels and BNC = 32*CW*WC output channels.
+struct TileCfg {
+  int kernel;  // 2: conv3x3_v2_kernel, 3: conv3x3_v3_kernel, 0: no such configuration
+  int CW, PBW, WC, WP, KC, KS;
+  int upcat_c;  // decoder (upsample + concat) variant: 64 serves Cout % 64 == 0, 32 the other layers, 0: none
+  bool pool;    // can fuse the 2x2 max-pool (not the third kernel's tiles with an odd block count per wave)
+  int twin;     // eight waves (KS 2): the four-wave configuration taken when the K range does not split in two
+  bool deep;    // has a deeper tap-fragment ring variant, for <= 1 workgroup per CU
+  bool first;   // has a variant that computes the first layer in its staging (FusedFirst)
+};
 constexpr int kNumCfgs = 22;
-constexpr V2Cfg kV2Cfgs[kNumCfgs] = {{0, 0, 0, 0, 0},
-                                     {2, 4, 2, 2, 32},   // 1: 16x16 px x 128 ch  (wave: 64 ch x 128 px)
-                                     {2, 2, 1, 4, 32},   // 2: 16x16 px x  64 ch  (wave: 64 ch x  64 px)
-                                     {0, 0, 0, 0, 0},    // 3: (32x16 px x 64 ch: measured slower everywhere, removed)
-                                     {2, 2, 2, 2, 32},   // 4:  8x16 px x 128 ch
-                                     {0, 0, 0, 0, 0},    // 5: (32x16 px x 32 ch: removed)
-                                     {1, 2, 1, 4, 32},   // 6: 16x16 px x  32 ch
-                                     {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0},
-                                     // conv3x3_v3_kernel (pxt_conv_v3.h): pixel fragments shared by the vertical taps,
-                                     // filter fragments through LDS
-                                     {2, 4, 2, 2, 32},   // 11: 16x16 px x 128 ch
-                                     {0, 0, 0, 0, 0},
-                                     {2, 4, 1, 4, 16},   // 13: 32x16 px x  64 ch, 16-channel chunks
-                                     {2, 2, 2, 2, 32},   // 14:  8x16 px x 128 ch
-                                     {2, 3, 2, 2, 32},   // 15: 12x16 px x 128 ch (no fused pool: odd block count)
-                                     {1, 4, 1, 4, 16},   // 16: 32x16 px x  32 ch, 16-channel chunks
-                                     {2, 3, 1, 4, 16},   // 17: 24x16 px x  64 ch, 16-channel chunks (the decoder's 64-channel
-                                                         //     layers: the 32-row tile + the upsampling staging spills)
-                                     {2, 3, 2, 2, 32, 2},  // 18: as 15, eight waves: the K range split over two wave quartets
-                                     {2, 4, 2, 2, 32, 2},  // 19: as 11, eight waves
-                                     {1, 2, 1, 4, 16},     // 20: 16x16 px x 32 ch, 16-channel chunks: 33 KB of LDS, 4 workgroups per CU
-                                     {2, 2, 1, 4, 16}};    // 21: 16x16 px x 64 ch, 16-channel chunks
-inline bool cfg_valid(int cfg) { return cfg >= 1 && cfg < kNumCfgs && kV2Cfgs[cfg].CW != 0; }
-inline bool cfg_v3(int cfg) { return cfg >= 11; }
-inline int cfg_th(int cfg) { return 2 * kV2Cfgs[cfg].PBW * kV2Cfgs[cfg].WP; }
-inline int cfg_bnc(int cfg) { return 32 * kV2Cfgs[cfg].CW * kV2Cfgs[cfg].WC; }
+constexpr TileCfg kTileCfgs[kNumCfgs] = {
+    // kernel CW PBW WC WP KC KS upcat_c pool twin deep first
+    {},
+    {2, 2, 4, 2, 2, 32, 1, 0, true, 0, true, false},    // 1: 16x16 px x 128 ch  (wave: 64 ch x 128 px)
+    {2, 2, 2, 1, 4, 32, 1, 64, true, 0, false, true},   // 2: 16x16 px x  64 ch  (wave: 64 ch x  64 px)
+    {},                                                 // 3: (32x16 px x 64 ch: measured slower everywhere, removed)
+    {2, 2, 2, 2, 2, 32, 1, 0, true, 0, false, false},   // 4:  8x16 px x 128 ch
+    {},                                                 // 5: (32x16 px x 32 ch: removed)
+    {2, 1, 2, 1, 4, 32, 1, 32, true, 0, false, false},  // 6: 16x16 px x  32 ch
+    {}, {}, {}, {},
+    {3, 2, 4, 2, 2, 32, 1, 0, true, 0, false, false},   // 11: 16x16 px x 128 ch
+    {},
+    {3, 2, 4, 1, 4, 16, 1, 0, true, 0, false, false},   // 13: 32x16 px x  64 ch, 16-channel chunks
+    {3, 2, 2, 2, 2, 32, 1, 0, true, 0, false, false},   // 14:  8x16 px x 128 ch
+    {3, 2, 3, 2, 2, 32, 1, 0, false, 0, false, false},  // 15: 12x16 px x 128 ch
+    {3, 1, 4, 1, 4, 16, 1, 32, true, 0, false, false},  // 16: 32x16 px x  32 ch, 16-channel chunks
+    {3, 2, 3, 1, 4, 16, 1, 64, false, 0, false, false}, // 17: 24x16 px x  64 ch, 16-channel chunks (the decoder's 64-channel
+                                                        //     layers: the 32-row tile + the upsampling staging spills)
+    {3, 2, 3, 2, 2, 32, 2, 0, false, 15, false, false}, // 18: as 15, eight waves: the K range split over two wave quartets
+    {3, 2, 4, 2, 2, 32, 2, 0, true, 11, false, false},  // 19: as 11, eight waves
+    {3, 1, 2, 1, 4, 16, 1, 32, true, 0, false, false},  // 20: 16x16 px x 32 ch, 16-channel chunks: 33 KB of LDS, 4 workgroups per CU
+    {3, 2, 2, 1, 4, 16, 1, 64, true, 0, false, false}}; // 21: 16x16 px x 64 ch, 16-channel chunks
+inline bool cfg_valid(int cfg) { return cfg >= 1 && cfg < kNumCfgs && kTileCfgs[cfg].kernel != 0; }
+inline int cfg_th(int cfg) { return 2 * kTileCfgs[cfg].PBW * kTileCfgs[cfg].WP; }
+inline int cfg_bnc(int cfg) { return 32 * kTileCfgs[cfg].CW * kTileCfgs[cfg].WC; }
+// the packed buffer holds the second kernel's tap layout, then the third's (pxt_conv3x3_packed_bytes)
+inline const half_t* cfg_taps(int cfg, const half_t* wpk, int cin, int cout) {
+  return kTileCfgs[cfg].kernel == 3 ? wpk + (size_t)cout * 9 * cin : wpk;
+}
 
 struct ConvPlan { int cfg, tiles, nb, splits; };
 
-// Passes running side by side on the chip (2 while a batch of two runs as two single-image passes): the tile
-// configuration, the split-K factor and the deep-ring choice look at the workgroups of ALL of them - a lone
-// 120x160 layer has 160-300 workgroups and would take the one-wave-per-SIMD configuration, two of those do not
-// share a CU.
-thread_local int g_conv_peers = 1;
-thread_local int g_conv_layer = 0;  // index of the pyramid layer being launched (0: a stand-alone call)
-// pxt_unet_set_batch_plan(ctx, 1): a batch's layers take the tile configuration and the split-K factor a SINGLE image of
-// the frame's two-stream pair pass would take (n_img = 1, two passes sharing the chip), whatever the batch size - so an
-// image's maps are bit for bit those of the one-object tracker (the summation order of a layer is its tile's K walk and
-// its split-K partition, nothing else).  0: planned for the batch as launched (fewer splits, the fastest).
-thread_local bool g_plan_as_single = false;
+// What a layer is planned for.  `peers`: passes side by side on the chip (2 while a batch of two runs as two single-image
+// passes): the tile configuration, the split-K factor and the deep-ring choice count the workgroups of ALL of them - a lone
+// 120x160 layer would take the one-wave-per-SIMD configuration, two of those do not share a CU.  `single`
+// (pxt_unet_set_batch_plan(ctx, 1)): a batch is planned as ONE image of the frame's pair pass (n_img 1, peers 2), so an
+// image's maps are bit for bit those of the one-object tracker (a layer's summation order is its tile's K walk and its
+// split-K partition); otherwise for the batch as launched (fewer splits, the fastest).  `layer`: the pyramid layer (1..16;
+// 0: a stand-alone call).
+struct PlanScope {
+  int peers = 1; bool single = false; int layer = 0;
+  PlanScope at(int li) const { return {peers, single, li}; }
+};
 
 // Split-K factor: only the smallest maps (conv5: 12 tiles per image pair) leave most of the 256 CUs
 // without a workgroup; measured on the 60x80 layers (160 workgroups) every split loses to no split.
@@ -576,10 +625,10 @@ int choose_splits(int wgs, int n_chunks, bool upcat, int own = 1 << 30) {
   return std::max(1, std::min(splits, 16));
 }
 
-ConvPlan plan_conv(int n_img, int H, int W, int cin, int cout, bool allow_split, int force_cfg = 0,
-                   int force_splits = 0, bool upcat = false, bool wants_pool = false) {
+ConvPlan plan_conv(const PlanScope& sc, int n_img, int H, int W, int cin, int cout, bool allow_split, int force_cfg,
+                   int force_splits, bool upcat, bool wants_pool) {
   ConvPlan P;
-  const int plan_img = g_plan_as_single ? 1 : n_img, plan_peers = g_plan_as_single ? 2 : g_conv_peers;
+  const int plan_img = sc.single ? 1 : n_img, plan_peers = sc.single ? 2 : sc.peers;
   auto wgs_of = [&](int cfg) {
     const int th = cfg_th(cfg);
     return plan_peers * plan_img * ((H + th - 1) / th) * ((W + 15) / 16) * (cout / cfg_bnc(cfg));
@@ -606,22 +655,16 @@ ConvPlan plan_conv(int n_img, int H, int W, int cin, int cout, bool allow_split,
     }
     else if (cout % 64 == 0) cfg = 2;
     else cfg = 6;
-    // Round 4 experiment (profiles/r04_experiments.md #18; PXT_CONV_POOL14=1): the pooled layers (last convolution of
-    // encoder blocks 1-3) on the third kernel's 8-row x 128-channel tile.  With a device synchronisation after every pair
-    // pass it is worth 4 % of the pass (0.826 against 0.860 ms, five interleaved runs) - and NOTHING in the frame loop,
-    // where the host runs ahead of the device (bench.py: 680 / 680 / 682 against 682 / 682 / 683 frames/s, UNet stage 0.677
-    // against 0.675 ms): what it shortens is the pass's start-up while the host is still enqueueing.  Off by default.
-    static const bool pool14 = [] { const char* e = getenv("PXT_CONV_POOL14"); return e ? atoi(e) != 0 : false; }();
-    if (pool14 && wants_pool && cout % 128 == 0) cfg = 14;
+    // (the pooled layers on configuration 14: worth nothing in the frame loop, profiles/r04_experiments.md #18)
   }
-  if (cfg_valid(cfg) && kV2Cfgs[cfg].KS == 2 && (upcat || (cin / 32) % 2 != 0)) cfg = cfg == 18 ? 15 : 11;
+  if (cfg_valid(cfg) && kTileCfgs[cfg].KS == 2 && (upcat || (cin / 32) % 2 != 0)) cfg = kTileCfgs[cfg].twin;
   P.cfg = cfg;
   const int th = cfg_th(cfg);
   P.tiles = n_img * ((H + th - 1) / th) * ((W + 15) / 16);
   P.nb = cout / cfg_bnc(cfg);
   const int plan_tiles = P.tiles / n_img * plan_img;
   P.splits = allow_split ? (force_splits > 0 ? std::min(force_splits, std::max(1, cin / 32)) : choose_splits(plan_peers * plan_tiles * P.nb, cin / 32, upcat, plan_tiles * P.nb)) : 1;
-  if (kV2Cfgs[cfg].KS == 2) {  // every split must hold an even number of chunks: round the factor down to a divisor
+  if (kTileCfgs[cfg].KS == 2) {  // every split must hold an even number of chunks: round the factor down to a divisor
     while (P.splits > 1 && (cin / 32) % (2 * P.splits) != 0) --P.splits;
   }
   return P;
@@ -634,22 +677,16 @@ inline int upcat_cfg(int cout, int H, int W) {
   return cout % 64 == 0 ? ((long long)H * W >= 120 * 160 ? 21 : 2) : 20;
 }
 
-// Bytes of split-K partials a layer may need.  The launch-time plan depends on whether the layer's output is pooled and on
-// the number of passes sharing the chip (g_conv_peers), neither of which is known when the workspace is sized: the
-// largest factor over those four cases.  launch_conv checks its plan against the region it is given.
+// Bytes of split-K partials a layer may need.  The launch-time plan depends on whether the layer's output is pooled, on
+// the number of passes sharing the chip and on the batch plan, none of which is known when the workspace is sized: the
+// largest factor over those cases.  launch_conv checks its plan against the region it is given.
 size_t splitk_bytes(int n_img, int H, int W, int cin, int cout, bool upcat = false) {
   int splits = 1;
-  const int peers_before = g_conv_peers;
-  const bool single_before = g_plan_as_single;
   for (int single = 0; single < 2; ++single)
     for (int peers = 1; peers <= 2; ++peers)
-      for (int pool = 0; pool < (upcat ? 1 : 2); ++pool) {
-        g_conv_peers = peers;
-        g_plan_as_single = single != 0;
-        splits = std::max(splits, plan_conv(n_img, H, W, cin, cout, true, upcat ? upcat_cfg(cout, H, W) : 0, 0, upcat, pool != 0).splits);
-      }
-  g_conv_peers = peers_before;
-  g_plan_as_single = single_before;
+      for (int pool = 0; pool < (upcat ? 1 : 2); ++pool)
+        splits = std::max(splits, plan_conv(PlanScope{peers, single != 0, 0}, n_img, H, W, cin, cout, true,
+                                            upcat ? upcat_cfg(cout, H, W) : 0, 0, upcat, pool != 0).splits);
   return splits > 1 ? (size_t)splits * n_img * H * W * cout * sizeof(float) : 0;
 }
 
@@ -675,14 +712,12 @@ bool make_plan(const pxt_unet* ctx, int n_img, int H, int W, Plan& P) {
   for (int d = 0; d < 4; ++d) { ph *= 2; pw *= 2; P.dh[d] = ph; P.dw[d] = pw; }
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-  static const int enc_c[5] = {64, 128, 256, 512, 512};
-  static const int enc_in[5] = {3, 64, 128, 256, 512};
   for (int b = 0; b < 5; ++b) {
     const size_t px = (size_t)n_img * P.h[b] * P.w[b];
-    P.enc_pool[b] = (b > 0) ? take(px * enc_in[b] * 2) : 0;
-    P.enc_tmp[b][0] = take(px * enc_c[b] * 2);
-    P.enc_tmp[b][1] = take(px * enc_c[b] * 2);
-    P.enc_out[b] = take(px * enc_c[b] * 2);
+    P.enc_pool[b] = (b > 0) ? take(px * kEnc[b].cin * 2) : 0;
+    P.enc_tmp[b][0] = take(px * kEnc[b].c * 2);
+    P.enc_tmp[b][1] = take(px * kEnc[b].c * 2);
+    P.enc_out[b] = take(px * kEnc[b].c * 2);
   }
   for (int d = 0; d < 4; ++d) {
     const size_t px = (size_t)n_img * P.dh[d] * P.dw[d];
@@ -690,9 +725,8 @@ bool make_plan(const pxt_unet* ctx, int n_img, int H, int W, Plan& P) {
   }
   // one split-K partial buffer, sized for the hungriest layer
   size_t sk = 0;
-  static const int blk_of[13] = {0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4};
-  for (int i = 1; i < 13; ++i)
-    sk = std::max(sk, splitk_bytes(n_img, P.h[blk_of[i]], P.w[blk_of[i]], ctx->conv[i].cin, ctx->conv[i].cout));
+  for (int i = 1; i < kNumEncLayers; ++i)
+    sk = std::max(sk, splitk_bytes(n_img, P.h[enc_block(i)], P.w[enc_block(i)], ctx->conv[i].cin, ctx->conv[i].cout));
   for (int d = 0; d < 4; ++d)
     sk = std::max(sk, splitk_bytes(n_img, P.dh[d], P.dw[d], ctx->conv[13 + d].cin, ctx->conv[13 + d].cout, true));
   P.splitk = take(sk + 256);
@@ -706,157 +740,166 @@ bool make_plan(const pxt_unet* ctx, int n_img, int H, int W, Plan& P) {
   return true;
 }
 
+// workspace offset of encoder layer li's output
+inline size_t enc_out_offset(const Plan& P, int li) {
+  return enc_last(li) ? P.enc_out[enc_block(li)] : P.enc_tmp[enc_block(li)][(li - kEnc[enc_block(li)].first) & 1];
+}
+
+template <auto K, int LDS>
+void launch_with_lds(const ConvArgs& a, dim3 grid, int threads, hipStream_t s) {
+  // (once per kernel: the double-buffered halo of the 32-row tiles exceeds the 64 KiB default)
+  static const hipError_t attr = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  (void)attr;
+  hipLaunchKernelGGL(K, grid, dim3(threads), LDS, s, a);
+}
+
 template <int CW, int PBW, int WC, int WP, bool UPCAT, int AR = 3, bool FIRST = false>
 void launch_v2(const ConvArgs& a, dim3 grid, hipStream_t s) {
   constexpr int lds = 2 * (2 * PBW * WP + 2) * kV2RowBytes + (UPCAT ? (PBW * WP + 2) * 10 * 64 : 0) + 32 * CW * WC * 4 +
                       (FIRST ? (2 * PBW * WP + 4) * 20 * 3 * 4 : 0);
-  static bool attr_done = false;  // the double-buffered halo of the 32-row tiles exceeds the 64 KiB default
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv3x3_v2_kernel<CW, PBW, WC, WP, UPCAT, AR, FIRST>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv3x3_v2_kernel<CW, PBW, WC, WP, UPCAT, AR, FIRST>), grid, dim3(256), lds, s, a);
+  launch_with_lds<conv3x3_v2_kernel<CW, PBW, WC, WP, UPCAT, AR, FIRST>, lds>(a, grid, 256, s);
 }
 
 template <int CW, int PBW, int WC, int WP, int KC, bool UPCAT = false, int KS = 1>
 void launch_v3(const ConvArgs& a, dim3 grid, hipStream_t s) {
   constexpr int lds = v3_lds_bytes(CW, PBW, WC, WP, KC, UPCAT, KS);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv3x3_v3_kernel<CW, PBW, WC, WP, KC, UPCAT, KS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv3x3_v3_kernel<CW, PBW, WC, WP, KC, UPCAT, KS>), grid, dim3(256 * KS), lds, s, a);
+  launch_with_lds<conv3x3_v3_kernel<CW, PBW, WC, WP, KC, UPCAT, KS>, lds>(a, grid, 256 * KS, s);
 }
 
-void launch_v2_cfg(int cfg, bool upcat, const ConvArgs& a, dim3 grid, hipStream_t s) {
-  if (cfg_v3(cfg) && upcat) {
-    switch (cfg) {
-      case 17: launch_v3<2, 3, 1, 4, 16, true>(a, grid, s); break;
-      case 20: launch_v3<1, 2, 1, 4, 16, true>(a, grid, s); break;
-      case 21: launch_v3<2, 2, 1, 4, 16, true>(a, grid, s); break;
-      default: launch_v3<1, 4, 1, 4, 16, true>(a, grid, s); break;  // 16
-    }
-    return;
+// The kernel instance of configuration C: its decoder variant for an upsample + concat layer, else its deep-ring or
+// fused-first variant where it has one and the launch asks for it.  (Keep every decoder variant free of scratch: one build
+// whose 18-step loop was not unrolled indexed its offset table dynamically, 32 B of scratch per lane, and each launch -
+// plus the head kernels on the side stream - then took milliseconds waiting for scratch set-up.)
+template <size_t C>
+void launch_tile(bool upcat, bool deep, const ConvArgs& a, dim3 grid, hipStream_t s) {
+  constexpr TileCfg T = kTileCfgs[C];
+  if constexpr (T.kernel == 3) {
+    if constexpr (T.upcat_c != 0) { if (upcat) return launch_v3<T.CW, T.PBW, T.WC, T.WP, T.KC, true>(a, grid, s); }
+    launch_v3<T.CW, T.PBW, T.WC, T.WP, T.KC, false, T.KS>(a, grid, s);
+  } else if constexpr (T.kernel == 2) {
+    if constexpr (T.upcat_c != 0) { if (upcat) return launch_v2<T.CW, T.PBW, T.WC, T.WP, true>(a, grid, s); }
+    if constexpr (T.deep) { if (deep) return launch_v2<T.CW, T.PBW, T.WC, T.WP, false, 9>(a, grid, s); }
+    if constexpr (T.first) { if (a.first.enabled) return launch_v2<T.CW, T.PBW, T.WC, T.WP, false, 3, true>(a, grid, s); }
+    launch_v2<T.CW, T.PBW, T.WC, T.WP, false>(a, grid, s);
   }
-  if (cfg_v3(cfg)) {
-    switch (cfg) {
-      case 11: launch_v3<2, 4, 2, 2, 32>(a, grid, s); break;
-      case 13: launch_v3<2, 4, 1, 4, 16>(a, grid, s); break;
-      case 14: launch_v3<2, 2, 2, 2, 32>(a, grid, s); break;
-      case 15: launch_v3<2, 3, 2, 2, 32>(a, grid, s); break;
-      case 17: launch_v3<2, 3, 1, 4, 16>(a, grid, s); break;
-      case 18: launch_v3<2, 3, 2, 2, 32, false, 2>(a, grid, s); break;
-      case 19: launch_v3<2, 4, 2, 2, 32, false, 2>(a, grid, s); break;
-      case 20: launch_v3<1, 2, 1, 4, 16>(a, grid, s); break;
-      case 21: launch_v3<2, 2, 1, 4, 16>(a, grid, s); break;
-      default: launch_v3<1, 4, 1, 4, 16>(a, grid, s); break;
-    }
-    return;
-  }
-  if (upcat) {
-    // decoder layers (bilinear x2 + concat formed in the staging): the 16x16-pixel tiles.  (Keep every
-    // variant free of scratch: one build whose 18-step loop was not unrolled indexed its offset table
-    // dynamically, 32 B of scratch per lane, and each launch - plus the head kernels on the side
-    // stream - then took milliseconds waiting for scratch set-up.)
-    if (cfg == 2) launch_v2<2, 2, 1, 4, true>(a, grid, s);
-    else launch_v2<1, 2, 1, 4, true>(a, grid, s);
-    return;
-  }
+}
+
+template <size_t... C>
+constexpr auto tile_launches(std::index_sequence<C...>) { return std::array{&launch_tile<C>...}; }
+constexpr auto kTileLaunches = tile_launches(std::make_index_sequence<kNumCfgs>());
+
+int launch_tile_cfg(int cfg, bool upcat, const PlanScope& sc, const ConvArgs& a, dim3 grid, hipStream_t s) {
+  if (!cfg_valid(cfg) || (upcat && kTileCfgs[cfg].upcat_c == 0)) return PXT_E_ARG;
   // <= 1 workgroup per CU: nothing hides a miss on the streamed taps but a deeper fragment ring
-  const bool deep = (long long)g_conv_peers * grid.x * grid.y * grid.z <= 256;
-  switch (cfg) {
-    case 1:
-      if (deep) launch_v2<2, 4, 2, 2, false, 9>(a, grid, s);
-      else launch_v2<2, 4, 2, 2, false>(a, grid, s);
-      break;
-    case 2:
-      if (a.first.enabled) launch_v2<2, 2, 1, 4, false, 3, true>(a, grid, s);
-      else launch_v2<2, 2, 1, 4, false>(a, grid, s);
-      break;
-
-    case 4: launch_v2<2, 2, 2, 2, false>(a, grid, s); break;
-    default: launch_v2<1, 2, 1, 4, false>(a, grid, s); break;
-  }
+  const bool deep = (long long)sc.peers * grid.x * grid.y * grid.z <= 256;
+  kTileLaunches[cfg](upcat, deep, a, grid, s);
+  return PXT_OK;
 }
 
-// One 3x3 layer: `wpk` are the packed taps.  `pool_out` (optional) receives the 2x2 max-pool of the
-// output when the layer runs without split-K; returns (through *pooled) whether it was written.
-int launch_conv(int cin, int cout, const half_t* wpk, const float* bias, const half_t* in, int H, int W, half_t* out,
-                hipStream_t s, int relu = 1, float* partial = nullptr, int n_img = 1, const UpSrc* up = nullptr,
-                half_t* pool_out = nullptr, bool* pooled = nullptr, int force_cfg = 0, int force_splits = 0,
-                const FusedHead* head = nullptr, const FusedFirst* first = nullptr, size_t partial_cap = ~(size_t)0,
-                const TileSkip* skip = nullptr, int skip_cfg = 0) {
+// One 3x3 layer launch.  `wpk`: the packed taps (both layouts).  `partial` (nullptr: no split-K): a split-K region of
+// `partial_cap` bytes.  `up`: a decoder layer (bilinear x2 + concat formed in the staging).  `pool_out` (optional) receives
+// the 2x2 max-pool of the output when the plan allows.  `force_cfg` / `force_splits` (0: automatic) pin the plan.  `head` /
+// `first`: fusions.  `skip`: constant-tile skipping, only with the configuration `skip_cfg` it was made for.
+struct ConvLaunch {
+  const half_t* in = nullptr;
+  half_t* out = nullptr;
+  int H = 0, W = 0, cin = 0, cout = 0, n_img = 1, relu = 1;
+  const half_t* wpk = nullptr;
+  const float* bias = nullptr;
+  float* partial = nullptr;
+  size_t partial_cap = ~(size_t)0;
+  const UpSrc* up = nullptr;
+  half_t* pool_out = nullptr;
+  int force_cfg = 0, force_splits = 0, skip_cfg = 0;
+  const FusedHead* head = nullptr;
+  const FusedFirst* first = nullptr;
+  const TileSkip* skip = nullptr;
+};
+
+// The plan launch_conv takes for L: the layer's PXT_CONV_PLAN override, configuration 2 for the fused first layer, a
+// decoder layer's fallback to a configuration with a decoder variant, then plan_conv.
+ConvPlan resolve_plan(const ConvLaunch& L, const PlanScope& sc) {
+  int force_cfg = L.force_cfg, force_splits = L.force_splits;
+  for (const auto& t : knobs().plan)
+    if (t[0] == sc.layer && sc.layer > 0) {
+      if (t[1] > 0) force_cfg = t[1];
+      if (t[2] > 0) force_splits = t[2];
+    }
+  if (L.first) { force_cfg = 2; force_splits = 0; }
+  const bool up_ok = cfg_valid(force_cfg) && kTileCfgs[force_cfg].upcat_c == (L.cout % 64 == 0 ? 64 : 32);
+  if (L.up && !up_ok) force_cfg = upcat_cfg(L.cout, L.H, L.W);
+  return plan_conv(sc, L.n_img, L.H, L.W, L.cin, L.cout, L.partial != nullptr, force_cfg, force_splits, L.up != nullptr,
+                   L.pool_out != nullptr);
+}
+
+// Returns (through *pooled) whether the layer wrote L.pool_out.
+int launch_conv(const ConvLaunch& L, const PlanScope& sc, hipStream_t s, bool* pooled = nullptr) {
+  const int cin = L.cin, cout = L.cout, H = L.H, W = L.W;
+  const UpSrc* up = L.up;
   if (cin % 32 != 0 || cout % 32 != 0) return PXT_E_ARG;
   if (up && (up->Cp % 32 != 0 || up->Cp >= cin || H != 2 * up->Hp || W != 2 * up->Wp || up->Hs < H || up->Ws < W))
     return PXT_E_ARG;
-  // Experiment knob: PXT_CONV_PLAN="layer:cfg:splits;..." overrides the tile configuration / split-K factor of the
-  // pyramid's convolution `layer` (1..16 in pxt_unet's order; 0 in a field = keep the default).
-  {
-    static const std::vector<std::array<int, 3>> plan = [] {
-      std::vector<std::array<int, 3>> v;
-      const char* e = getenv("PXT_CONV_PLAN");
-      while (e && *e) {
-        std::array<int, 3> t = {0, 0, 0};
-        if (sscanf(e, "%d:%d:%d", &t[0], &t[1], &t[2]) >= 2) v.push_back(t);
-        e = strchr(e, ';');
-        if (e) ++e;
-      }
-      return v;
-    }();
-    for (const auto& t : plan)
-      if (t[0] == g_conv_layer && g_conv_layer > 0) {
-        if (t[1] > 0) force_cfg = t[1];
-        if (t[2] > 0) force_splits = t[2];
-      }
-  }
-  if (first) { force_cfg = 2; force_splits = 0; }
-  if (up) {  // decoder layers: 2 / 13 (64 channels), 6 / 16 (32 channels)
-    const bool ok = cout % 64 == 0 ? (force_cfg == 2 || force_cfg == 17 || force_cfg == 21) : (force_cfg == 6 || force_cfg == 16 || force_cfg == 20);
-    if (!ok) force_cfg = upcat_cfg(cout, H, W);
-  }
-  const ConvPlan cp = plan_conv(n_img, H, W, cin, cout, partial != nullptr, force_cfg, force_splits, up != nullptr, pool_out != nullptr);
+  const ConvPlan cp = resolve_plan(L, sc);
+  const TileCfg& T = kTileCfgs[cp.cfg];
   ConvArgs a;
-  // (the packed buffer holds the second kernel's layout, then the third's: pxt_conv3x3_packed_bytes)
-  a.in = in; a.H = H; a.W = W; a.Cin = cin; a.wpk = cfg_v3(cp.cfg) ? wpk + (size_t)cout * 9 * cin : wpk; a.bias = bias; a.Cout = cout; a.relu = relu;
-  a.out = out; a.partial = partial;
+  a.in = L.in; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.relu = L.relu; a.bias = L.bias;
+  a.wpk = cfg_taps(cp.cfg, L.wpk, cin, cout); a.out = L.out; a.partial = L.partial;
   a.up = up ? *up : UpSrc{nullptr, 0, 0, 0, 0, 0};
-  a.pool = (cp.splits == 1 && !(cfg_v3(cp.cfg) && (kV2Cfgs[cp.cfg].PBW & 1))) ? pool_out : nullptr;
-  if (kV2Cfgs[cp.cfg].KS == 2 && ((cin / 32) / cp.splits) % 2 != 0) return PXT_E_ARG;  // both quartets need equal K shares
+  a.pool = (cp.splits == 1 && T.pool) ? L.pool_out : nullptr;
+  if (T.KS == 2 && ((cin / 32) / cp.splits) % 2 != 0) return PXT_E_ARG;  // both quartets need equal K shares
   // the partials of this plan must fit the region the caller sized (a forced plan - PXT_CONV_PLAN - may ask for more)
-  if (cp.splits > 1 && (size_t)cp.splits * n_img * H * W * cout * sizeof(float) > partial_cap) return PXT_E_ARG;
+  if (cp.splits > 1 && (size_t)cp.splits * L.n_img * H * W * cout * sizeof(float) > L.partial_cap) return PXT_E_ARG;
   std::memset(&a.head, 0, sizeof(a.head));
-  if (head) {
+  if (L.head) {
     if (cout != 32 || cp.splits != 1 || cfg_bnc(cp.cfg) != 32) return PXT_E_ARG;
-    a.head = *head;
+    a.head = *L.head;
     a.head.enabled = 1;
   }
   std::memset(&a.first, 0, sizeof(a.first));
-  if (first) {  // the first layer computed in this layer's staging: the 64 -> 64 layer on its 16x16 x 64-channel tile only
-    if (cin != 64 || cp.cfg != 2 || cp.splits != 1 || up) return PXT_E_ARG;
-    a.first = *first;
+  if (L.first) {  // the first layer computed in this layer's staging: the 64 -> 64 layer on its 16x16 x 64-channel tile only
+    if (cin != 64 || !T.first || cp.splits != 1 || up) return PXT_E_ARG;
+    a.first = *L.first;
     a.first.enabled = 1;
   }
   // constant-tile skipping: only with the very tile configuration the flags (tile geometry) and the constant vector (K
   // walk) were made for, one K pass, no fused head
   a.skip.flags = nullptr;
   a.skip.value = nullptr;
-  if (skip && skip->flags && cp.splits == 1 && !head && !up && cp.cfg == skip_cfg) a.skip = *skip;
+  if (L.skip && L.skip->flags && cp.splits == 1 && !L.head && !up && cp.cfg == L.skip_cfg) a.skip = *L.skip;
   if (pooled) *pooled = a.pool != nullptr;
   const dim3 grid(cp.tiles, cp.nb, cp.splits);
-  static const bool debug_plan = getenv("PXT_CONV_DEBUG") != nullptr;
-  if (debug_plan)
-    fprintf(stderr, "conv layer %2d %4d->%4d @%dx%d x%d  cfg %2d  grid (%d, %d, %d)%s%s\n", g_conv_layer, cin, cout, W, H, n_img,
+  if (knobs().debug)
+    fprintf(stderr, "conv layer %2d %4d->%4d @%dx%d x%d  cfg %2d  grid (%d, %d, %d)%s%s\n", sc.layer, cin, cout, W, H, L.n_img,
             cp.cfg, cp.tiles, cp.nb, cp.splits, up ? "  upcat" : "", a.pool ? "  +pool" : "");
-  launch_v2_cfg(cp.cfg, up != nullptr, a, grid, s);
+  if (launch_tile_cfg(cp.cfg, up != nullptr, sc, a, grid, s) != PXT_OK) return PXT_E_ARG;
   if (cp.splits > 1) {
-    const long long n4 = (long long)n_img * H * W * cout / 4;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, partial, cp.splits,
-                       n4, cout, bias, relu, out);
+    const long long n4 = (long long)L.n_img * H * W * cout / 4;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, L.partial, cp.splits,
+                       n4, cout, L.bias, L.relu, L.out);
   }
   return PXT_OK;
+}
+
+// Pyramid layer li at H x W for n_img images, buffers and fusions aside.
+ConvLaunch pyramid_layer(const pxt_unet* ctx, int li, int H, int W, int n_img) {
+  ConvLaunch L;
+  L.H = H; L.W = W; L.n_img = n_img; L.cin = ctx->conv[li].cin; L.cout = ctx->conv[li].cout;
+  L.wpk = ctx->conv_packed[li]; L.bias = ctx->conv[li].b;
+  return L;
+}
+
+// Encoder layer li (1..12) of a pass over n_img images in the workspace `ws` laid out by P, its input aside: the block's
+// last layer also writes the next block's pooled input (epilogue fusion); `ff` (layer 1 only, or nullptr) is the first
+// layer fused into its staging.  The encoder launches it and the tile-skip set-up plans it: one description for both.
+ConvLaunch encoder_layer(const pxt_unet* ctx, const Plan& P, char* ws, int n_img, int li, const FusedFirst* ff) {
+  const int b = enc_block(li);
+  ConvLaunch L = pyramid_layer(ctx, li, P.h[b], P.w[b], n_img);
+  L.out = (half_t*)(ws + enc_out_offset(P, li));
+  L.pool_out = (enc_last(li) && b < 4) ? (half_t*)(ws + P.enc_pool[b + 1]) : nullptr;
+  L.first = li == 1 ? ff : nullptr;
+  L.partial = L.first ? nullptr : (float*)(ws + P.splitk);
+  L.partial_cap = P.splitk_bytes;
+  return L;
 }
 
 // ---- constant-tile skipping: the layers' output vectors for the constant input -------------------------------
@@ -864,11 +907,7 @@ int launch_conv(int cin, int cout, const half_t* wpk, const float* bias, const h
 // conv2_1(c1), ... is computed ONCE on the device by running each layer's own kernel configuration on a 48 x 48
 // constant map and taking the centre pixel: the same K walk, the same bits as a constant tile of the real pass.
 constexpr int kSkipS = 48, kSkipLayers = 6, kSkipMaxC = 256;
-bool conv_plan_env_set() {
-  static const bool set = getenv("PXT_CONV_PLAN") != nullptr;
-  return set;
-}
-int ensure_skip_values(pxt_unet* ctx, const int cfg[kSkipLayers], hipStream_t s, const half_t** values) {
+int ensure_skip_values(pxt_unet* ctx, const int cfg[kSkipLayers], const PlanScope& scope, hipStream_t s, const half_t** values) {
   ++ctx->skip_clock;
   pxt_unet::SkipEntry* victim = &ctx->skip_cache[0];
   for (auto& e : ctx->skip_cache) {
@@ -899,7 +938,7 @@ int ensure_skip_values(pxt_unet* ctx, const int cfg[kSkipLayers], hipStream_t s,
     ConvArgs a;
     std::memset(&a, 0, sizeof(a));
     a.H = kSkipS; a.W = kSkipS; a.Cin = cin; a.Cout = cout; a.relu = 1;
-    a.wpk = cfg_v3(cfg[k]) ? ctx->conv_packed[li] + (size_t)cout * 9 * cin : ctx->conv_packed[li];
+    a.wpk = cfg_taps(cfg[k], ctx->conv_packed[li], cin, cout);
     a.bias = ctx->conv[li].b;
     a.out = out_map;
     if (li == 1) {  // the first layer computed inside the second one's staging, from a raw zero image
@@ -915,7 +954,7 @@ int ensure_skip_values(pxt_unet* ctx, const int cfg[kSkipLayers], hipStream_t s,
     }
     const int th = cfg_th(cfg[k]);
     const dim3 grid(((kSkipS + th - 1) / th) * (kSkipS / 16), cout / cfg_bnc(cfg[k]), 1);
-    launch_v2_cfg(cfg[k], false, a, grid, s);
+    if (launch_tile_cfg(cfg[k], false, scope, a, grid, s) != PXT_OK) return PXT_E_ARG;
     hipLaunchKernelGGL(skip_copy_kernel, dim3((cout + 255) / 256), dim3(256), 0, s, victim->values + (size_t)k * kSkipMaxC,
                        (const half_t*)(out_map + ((size_t)(kSkipS / 2) * kSkipS + kSkipS / 2) * cout), cout);
   }
@@ -980,7 +1019,6 @@ extern "C" int pxt_unet_create(const void* weights_host, int64_t n_bytes, pxt_un
   // architecture checks (VGG16-UNet wiring the forward pass assumes)
   bool ok = ctx->conv[0].cin == 3 && ctx->conv[0].cout == 64;
   for (int i = 1; i < n_conv; ++i) ok = ok && (ctx->conv[i].cin % 32) == 0 && (ctx->conv[i].cout % 32) == 0;
-  for (int i = 0; i < n_heads; ++i) ok = ok && (ctx->head[i].cin % 8) == 0 && ctx->head[i].cout + 1 <= 192;
   for (int i = 0; i < n_heads; ++i) ok = ok && (ctx->head[i].cin % 16) == 0 && ctx->head[i].cout + 1 <= 160;
   if (!ok) { (void)hipFree(ctx->dev_blob); delete ctx; return PXT_E_ARG; }
   // 3x3 taps in the conv kernel's A-fragment order
@@ -1086,7 +1124,8 @@ extern "C" int64_t pxt_unet_workspace_bytes(const pxt_unet* ctx, int32_t H, int3
 static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* images,
                         const int32_t* image_is_u8, const uint8_t* const* masks, int32_t H,
                         int32_t W, float* const* out_maps, const int32_t out_cstride[3],
-                        const int32_t* normalize, void* workspace, void* stream, pxt_unet::SideSet& ss) {
+                        const int32_t* normalize, void* workspace, void* stream, pxt_unet::SideSet& ss,
+                        const PlanScope& sc) {
   if (!ctx || !images || !image_is_u8 || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
   Plan P;
   const int B = n_images;
@@ -1101,8 +1140,6 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   auto buf = [&](size_t off) { return (half_t*)(ws + off); };
-  static const int block_first[5] = {0, 2, 4, 7, 10};
-  static const int block_n[5] = {2, 2, 3, 3, 3};
   if (!ss.side) {
     ss.side = pxt::shared_side_stream(&ss == &ctx->sides[0] ? 1 : 2);  // shared by all contexts (pxt_core.hip)
     if (!ss.side) return PXT_E_HIP;
@@ -1114,18 +1151,17 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
   // flags).  The two coarse ones are small, latency-bound launches whose inputs (enc4, dec1) exist
   // long before the decoder finishes: they run on a side stream beside the decoder's convolutions.
   const half_t* pre[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // fine -> coarse: dec3, dec2, dec1, dec0, enc4
+  // head k reads pre[2 * k]: dec3, dec1 or enc4
+  auto head_npix = [&](int k) { return k == 2 ? (long long)P.h[4] * P.w[4] : (long long)P.dh[3 - 2 * k] * P.dw[3 - 2 * k]; };
   auto launch_head = [&](int k, hipStream_t hs) {
-    static const int head_src[3] = {0, 2, 4};
     const UnetLayer& Lh = ctx->head[k];
-    const int i = head_src[k];
-    const int hh = (i == 4) ? P.h[4] : P.dh[3 - i], ww = (i == 4) ? P.w[4] : P.dw[3 - i];
-    const long long npix = (long long)hh * ww;
+    const long long npix = head_npix(k);
     const long long waves = (npix + 31) / 32;
     // small maps: one wave per workgroup so the few waves spread over as many CUs
     const int tpb = waves < 1024 ? 64 : 256;
     const unsigned blocks = (unsigned)((waves * 64 + tpb - 1) / tpb);
     for (int im = 0; im < B; ++im) {
-      const half_t* src = pre[i] + (size_t)im * npix * Lh.cin;
+      const half_t* src = pre[2 * k] + (size_t)im * npix * Lh.cin;
       if (Lh.cout + 1 <= 64)
         hipLaunchKernelGGL(head_mfma_kernel<2>, dim3(blocks), dim3(tpb), 0, hs, src, npix, Lh.cin, ctx->head_w[k],
                            ctx->head_b[k], Lh.cout, normalize[im], out_maps[3 * im + k], out_cstride[k]);
@@ -1136,16 +1172,12 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
   };
 
   // both coarse heads of a single image in one launch (after dec1 exists); PXT_UNET_MERGE_HEADS=0 keeps the two launches
-  static const bool merge_heads_env = [] { const char* e = getenv("PXT_UNET_MERGE_HEADS"); return e ? atoi(e) != 0 : true; }();
-  const bool merge_heads = merge_heads_env && ctx->head[1].cout + 1 > 64 && ctx->head[2].cout + 1 > 64 &&
+  const bool merge_heads = knobs().merge_heads && ctx->head[1].cout + 1 > 64 && ctx->head[2].cout + 1 > 64 &&
                            ctx->head[1].cout + 1 <= 160 && ctx->head[2].cout + 1 <= 160;
   auto head_job = [&](int k) {
-    static const int head_src[3] = {0, 2, 4};
     const UnetLayer& Lh = ctx->head[k];
-    const int i = head_src[k];
-    const int hh = (i == 4) ? P.h[4] : P.dh[3 - i], ww = (i == 4) ? P.w[4] : P.dw[3 - i];
     HeadJob j;
-    j.in = pre[i]; j.npix = (long long)hh * ww; j.Cin = Lh.cin; j.wts = ctx->head_w[k]; j.bias = ctx->head_b[k];
+    j.in = pre[2 * k]; j.npix = head_npix(k); j.Cin = Lh.cin; j.wts = ctx->head_w[k]; j.bias = ctx->head_b[k];
     j.Cout = Lh.cout; j.normalize = normalize[0]; j.out = out_maps[k]; j.cstride = out_cstride[k];
     j.waves = (j.npix + 31) / 32;
     return j;
@@ -1157,29 +1189,31 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
   // constant: the masked query is 0 outside the dilated silhouette, the reference render 0 outside the object (15 % /
   // 12 % of the benchmark's 640 x 480 frame is not: 71-75 % of the first block's tiles, 66 % of the second's and 30-40 %
   // of the third's are skipped).
-  TileSkip tile_skip[kSkipLayers];
-  int tile_skip_cfg[kSkipLayers];
-  for (int k = 0; k < kSkipLayers; ++k) { tile_skip[k].flags = nullptr; tile_skip[k].value = nullptr; tile_skip_cfg[k] = 0; }
+  auto fill_images = [&](auto& r) {  // FirstImages / FusedFirst / SkipImages
+    for (int i = 0; i < B; ++i) { r.image[i] = images[i]; r.mask[i] = masks ? masks[i] : nullptr; r.is_u8[i] = image_is_u8[i]; }
+  };
+  const bool fuse_first = fuses_first(ctx);
+  FusedFirst ff = {};
+  fill_images(ff);
+  ff.w = (const float*)ctx->conv[0].w;
+  ff.b = ctx->conv[0].b;
+  TileSkip tile_skip[kSkipLayers] = {};
+  int tile_skip_cfg[kSkipLayers] = {};
   {
-    static const bool skip_env = [] { const char* e = getenv("PXT_UNET_SKIP"); return e ? atoi(e) != 0 : true; }();
-    static const bool fuse_first_env0 = [] { const char* e = getenv("PXT_UNET_FUSE_FIRST"); return e ? atoi(e) != 0 : true; }();
     bool any_source = false;
     for (int i = 0; i < B; ++i) any_source = any_source || (masks && masks[i]) || image_is_u8[i];
-    const bool can = skip_env && ctx->tile_skip && !conv_plan_env_set() && fuse_first_env0 && any_source && H >= 64 && W >= 64 &&
-                     ctx->conv[0].cout == 64 && ctx->conv[1].cin == 64 && ctx->conv[1].cout == 64;
+    const bool can = knobs().skip && ctx->tile_skip && !knobs().plan_env && fuse_first && any_source && H >= 64 && W >= 64 &&
+                     ctx->conv[0].cout == 64;
     if (can) {
-      static const int blk_of6[kSkipLayers] = {0, 1, 1, 2, 2, 2}, radius6[kSkipLayers] = {2, 4, 6, 10, 14, 18};
-      static const bool last6[kSkipLayers] = {true, false, true, false, false, true};  // the block's last conv (fused pool)
+      static const int radius6[kSkipLayers] = {2, 4, 6, 10, 14, 18};
       int cfgs[kSkipLayers];
       SkipGeo geo;
       geo.n_layers = kSkipLayers;
       int off = 0, max_tiles = 0;
       bool ok = true;
       for (int k = 0; k < kSkipLayers; ++k) {
-        const int li = k + 1, b = blk_of6[k];
-        // the plan launch_conv will take for this layer (same arguments: the fused first layer forces configuration 2)
-        const ConvPlan cp = plan_conv(B, P.h[b], P.w[b], ctx->conv[li].cin, ctx->conv[li].cout, li != 1, li == 1 ? 2 : 0, 0, false,
-                                      last6[k]);
+        const int li = k + 1, b = enc_block(li);
+        const ConvPlan cp = resolve_plan(encoder_layer(ctx, P, ws, B, li, &ff), sc.at(li));
         cfgs[k] = cp.cfg;
         ok = ok && cfg_valid(cp.cfg) && ctx->conv[li].cout <= kSkipMaxC && ctx->conv[li].cin <= kSkipMaxC;
         SkipLayerGeo& g = geo.l[k];
@@ -1191,9 +1225,9 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
       }
       const half_t* values = nullptr;
       if (ok && (size_t)off <= (size_t)B * 6 * ((size_t)(H / 8 + 2) * (W / 16 + 2)) &&
-          ensure_skip_values(ctx, cfgs, s, &values) == PXT_OK) {
+          ensure_skip_values(ctx, cfgs, sc, s, &values) == PXT_OK) {
         SkipImages si;
-        for (int i = 0; i < B; ++i) { si.image[i] = images[i]; si.mask[i] = masks ? masks[i] : nullptr; si.is_u8[i] = image_is_u8[i]; }
+        fill_images(si);
         uint8_t* grid_b = (uint8_t*)(ws + P.skip_grid);
         uint8_t* flags_b = (uint8_t*)(ws + P.skip_flags);
         const int nb = P.skip_bh * P.skip_bw;
@@ -1211,8 +1245,6 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
   const half_t* skip[5];
   const half_t* cur = nullptr;
   bool pooled_by_conv = false;
-  bool fuse_first = false;
-  FusedFirst ff;
   for (int b = 0; b < 5; ++b) {
     const int h = P.h[b], w = P.w[b];
     const half_t* x;
@@ -1221,53 +1253,30 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
       const UnetLayer& L0 = ctx->conv[0];
       const unsigned nblk = (unsigned)(((w + kFW - 1) / kFW) * ((h + kFH - 1) / kFH));
       half_t* o = buf(P.enc_tmp[0][0]);
-      FirstImages fi;
-      for (int i = 0; i < B; ++i) {
-        fi.image[i] = images[i];
-        fi.mask[i] = masks ? masks[i] : nullptr;
-        fi.is_u8[i] = image_is_u8[i];
-      }
       if (L0.cout != 64) return PXT_E_ARG;
-      // The first layer is computed inside the second layer's staging (pxt_conv_v2.h FusedFirst): its 39-MB output per
-      // image is never written.  PXT_UNET_FUSE_FIRST=0 keeps the separate launch (A/B, tests/test_variants_gpu.py).
-      static const bool fuse_first_env = [] { const char* e = getenv("PXT_UNET_FUSE_FIRST"); return e ? atoi(e) != 0 : true; }();
-      fuse_first = fuse_first_env && ctx->conv[1].cin == 64 && ctx->conv[1].cout == 64;
-      if (fuse_first) {
-        std::memset(&ff, 0, sizeof(ff));
-        for (int i = 0; i < B; ++i) { ff.image[i] = fi.image[i]; ff.mask[i] = fi.mask[i]; ff.is_u8[i] = fi.is_u8[i]; }
-        ff.w = (const float*)L0.w;
-        ff.b = L0.b;
-        x = nullptr;
-      } else {
+      x = fuse_first ? nullptr : o;
+      if (!fuse_first) {
+        FirstImages fi;
+        fill_images(fi);
         hipLaunchKernelGGL(conv_first_kernel<64>, dim3(nblk, B), dim3(256), 0, s, fi, h, w, (const float*)L0.w, L0.b, o);
-        x = o;
       }
     } else {
       half_t* o = buf(P.enc_pool[b]);
       if (!pooled_by_conv) {
-        const int cin = ctx->conv[block_first[b]].cin;
+        const int cin = ctx->conv[kEnc[b].first].cin;
         const long long n = (long long)B * h * w * (cin / 8);
         hipLaunchKernelGGL(maxpool2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cur, P.h[b - 1],
                            P.w[b - 1], cin, o, h, w, B);
       }
       x = o;
     }
-    pooled_by_conv = false;
-    for (int i = (b == 0 ? 1 : 0); i < block_n[b]; ++i) {
-      const bool last = i == block_n[b] - 1;
-      const int li = block_first[b] + i;
-      half_t* o = last ? buf(P.enc_out[b]) : buf(P.enc_tmp[b][i & 1]);
-      // the block's last conv also writes the next block's pooled input (epilogue fusion)
-      half_t* pool_to = (last && b < 4) ? buf(P.enc_pool[b + 1]) : nullptr;
-      g_conv_layer = li;
-      const bool with_first = li == 1 && fuse_first;
-      const bool can_skip = li >= 1 && li <= kSkipLayers && (li != 1 || with_first);
-      int rc = launch_conv(ctx->conv[li].cin, ctx->conv[li].cout, ctx->conv_packed[li], ctx->conv[li].b, x, h, w, o, s,
-                           1, with_first ? nullptr : (float*)(ws + P.splitk), B, nullptr, pool_to,
-                           pool_to ? &pooled_by_conv : nullptr, with_first ? 2 : 0, 0, nullptr, with_first ? &ff : nullptr,
-                           P.splitk_bytes, can_skip ? &tile_skip[li - 1] : nullptr, can_skip ? tile_skip_cfg[li - 1] : 0);
+    for (int li = std::max(kEnc[b].first, 1); li < kEnc[b].first + kEnc[b].n; ++li) {
+      ConvLaunch L = encoder_layer(ctx, P, ws, B, li, fuse_first ? &ff : nullptr);
+      L.in = x;
+      if (li <= kSkipLayers) { L.skip = &tile_skip[li - 1]; L.skip_cfg = tile_skip_cfg[li - 1]; }
+      const int rc = launch_conv(L, sc.at(li), s, &pooled_by_conv);  // (pooled_by_conv: the block's last layer decides)
       if (rc != PXT_OK) return rc;
-      x = o;
+      x = L.out;
     }
     skip[b] = x;
     cur = x;
@@ -1301,10 +1310,10 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
       fh.enabled = 1;
       head0_fused = true;
     }
-    g_conv_layer = 13 + d;
-    int rc = launch_conv(L.cin, L.cout, ctx->conv_packed[13 + d], L.b, skip[sb], P.dh[d], P.dw[d], o, s, 1,
-                         fuse_head ? nullptr : (float*)(ws + P.splitk), B, &up, nullptr, nullptr, 0, 0,
-                         fuse_head ? &fh : nullptr, nullptr, P.splitk_bytes);
+    ConvLaunch cl = pyramid_layer(ctx, 13 + d, P.dh[d], P.dw[d], B);
+    cl.in = skip[sb]; cl.out = o; cl.up = &up; cl.head = fuse_head ? &fh : nullptr;
+    cl.partial = fuse_head ? nullptr : (float*)(ws + P.splitk); cl.partial_cap = P.splitk_bytes;
+    const int rc = launch_conv(cl, sc.at(13 + d), s);
     if (rc != PXT_OK) return rc;
     prev = o;
     ph = P.dh[d]; pw = P.dw[d]; pc = L.cout;
@@ -1330,7 +1339,6 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
       }
     }
   }
-  g_conv_layer = 0;
   // (the heads were launched above: the two coarse ones on the side stream as soon as their input
   // existed, the fine one here)
   if (!head0_fused) launch_head(0, s);
@@ -1345,13 +1353,10 @@ extern "C" int pxt_unet_forward_batch(pxt_unet* ctx, int32_t n_images, const voi
                                       int32_t W, float* const* out_maps, const int32_t out_cstride[3],
                                       const int32_t* normalize, void* workspace, void* stream) {
   if (!ctx || !images || !image_is_u8 || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
-  static const int n_streams = [] { const char* e = getenv("PXT_UNET_STREAMS"); return e ? atoi(e) : 2; }();
   if (ctx->join_pending) { PXT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_join, 0)); ctx->join_pending = false; }
-  if (n_images != 2 || n_streams < 2) {
-    struct PlanMode { PlanMode(bool on) { g_plan_as_single = on; } ~PlanMode() { g_plan_as_single = false; } } plan_guard(ctx->plan_as_single && n_images > 2);
+  if (n_images != 2 || knobs().streams < 2)
     return forward_pass(ctx, n_images, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace,
-                        stream, ctx->sides[0]);
-  }
+                        stream, ctx->sides[0], PlanScope{1, ctx->plan_as_single && n_images > 2, 0});
   const int32_t Hs[2] = {H, H}, Ws[2] = {W, W};
   return pxt_unet_forward_pair(ctx, images, image_is_u8, masks, Hs, Ws, out_maps, out_cstride, normalize, workspace, stream);
 }
@@ -1385,12 +1390,11 @@ extern "C" int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, c
   PXT_HIP_CHECK(hipEventRecord(ctx->ev_fork, s));  // the second pass starts after the caller's earlier work
   PXT_HIP_CHECK(hipStreamWaitEvent(ctx->pass2, ctx->ev_fork, 0));
   const uint8_t* const no_mask[1] = {nullptr};
-  struct Peers { Peers() { g_conv_peers = 2; } ~Peers() { g_conv_peers = 1; } } peers_guard;
   const size_t second = (P0.total + 255) / 256 * 256;
   for (int im = 0; im < 2; ++im) {
     int rc = forward_pass(ctx, 1, images + im, image_is_u8 + im, masks ? masks + im : no_mask, H[im], W[im], out_maps + 3 * im,
                           out_cstride, normalize + im, (char*)workspace + (im ? second : 0),
-                          im == 0 ? (void*)s : (void*)ctx->pass2, ctx->sides[im]);
+                          im == 0 ? (void*)s : (void*)ctx->pass2, ctx->sides[im], PlanScope{2, false, 0});
     if (rc != PXT_OK) return rc;
   }
   PXT_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->pass2));
@@ -1450,22 +1454,15 @@ extern "C" int pxt_unet_activation_stats(pxt_unet* ctx, int32_t H, int32_t W, co
   // a pass left running by a deferred-join pair call may still be writing a workspace: wait for it first
   if (ctx->join_pending) { PXT_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_join, 0)); ctx->join_pending = false; }
   PXT_HIP_CHECK(hipMemsetAsync(stats, 0, kNumConv * 2 * sizeof(float), s));
-  static const int block_first[5] = {0, 2, 4, 7, 10};
-  static const int block_n[5] = {2, 2, 3, 3, 3};
   const char* ws = (const char*)workspace;
-  static const bool fuse_first = [] { const char* e = getenv("PXT_UNET_FUSE_FIRST"); return e ? atoi(e) != 0 : true; }();
-  std::vector<float> host_flags(kNumConv * 2, 0.f);
   for (int li = 0; li < kNumConv; ++li) {
     const half_t* x = nullptr;
     long long n = 0;
-    if (li < 13) {
-      int b = 4;
-      while (block_first[b] > li) --b;
-      const int i = li - block_first[b];
-      const bool last = i == block_n[b] - 1;
-      x = (const half_t*)(ws + (last ? P.enc_out[b] : P.enc_tmp[b][i & 1]));
+    if (li < kNumEncLayers) {
+      const int b = enc_block(li);
+      x = (const half_t*)(ws + enc_out_offset(P, li));
       n = (long long)P.h[b] * P.w[b] * ctx->conv[li].cout;
-      if (li == 0 && fuse_first && ctx->conv[1].cin == 64 && ctx->conv[1].cout == 64) x = nullptr;  // never materialised
+      if (li == 0 && fuses_first(ctx)) x = nullptr;  // never materialised
     } else {
       const int d = li - 13;
       x = (const half_t*)(ws + P.dec_out[d]);
@@ -1507,9 +1504,11 @@ extern "C" int pxt_conv3x3_packed(const void* in, int32_t H, int32_t W, int32_t 
   if (splits > 1 && (!splitk_ws || splitk_ws_bytes < (int64_t)splits * H * W * Cout * (int64_t)sizeof(float)))
     return PXT_E_ARG;
   if (cfg != 0 && (!cfg_valid(cfg) || Cout % cfg_bnc(cfg) != 0)) return PXT_E_ARG;
-  int rc = launch_conv(Cin, Cout, (const half_t*)packed, bias, (const half_t*)in, H, W, (half_t*)out,
-                       (hipStream_t)stream, relu, splits > 1 ? (float*)splitk_ws : nullptr, 1, nullptr,
-                       (half_t*)pool_out, nullptr, cfg, splits > 1 ? splits : 0);
+  ConvLaunch L;
+  L.in = (const half_t*)in; L.out = (half_t*)out; L.H = H; L.W = W; L.cin = Cin; L.cout = Cout; L.relu = relu;
+  L.wpk = (const half_t*)packed; L.bias = bias; L.pool_out = (half_t*)pool_out;
+  L.partial = splits > 1 ? (float*)splitk_ws : nullptr; L.force_cfg = cfg; L.force_splits = splits > 1 ? splits : 0;
+  int rc = launch_conv(L, PlanScope{}, (hipStream_t)stream);
   if (rc != PXT_OK) return rc;
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;
