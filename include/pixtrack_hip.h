@@ -46,7 +46,7 @@ extern "C" {
 #define PXT_LM_LOG_STRIDE 20 /* floats per logged iteration, see pxt_lm_refine */
 
 /* Library / device info ---------------------------------------------------- */
-int pxt_version(void);               /* ABI version (12), bumps on any signature change or added entry point */
+int pxt_version(void);               /* ABI version (13), bumps on any signature change or added entry point */
 const char* pxt_last_error(void);    /* text of the last PXT_E_HIP on this thread */
 int pxt_device_cus(int* n_cus_host); /* multiprocessor count of the current device */
 
@@ -276,12 +276,36 @@ int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, const int32_
 int pxt_unet_set_defer_join(pxt_unet* ctx, int32_t on);
 int pxt_unet_pair_join(pxt_unet* ctx, void* stream);
 
+/* fp32 pass (ABI 13).  pxt_unet_create_f32 takes the fp32 pack of pixtrack_amd/unet.py (pack_unet_weights(w,
+ * precision="fp32"): every 3x3 filter float32) and makes a context on which the whole network runs in fp32: fp32 NHWC
+ * activations, 3x3 convolutions on the exact f32-input MFMA, the same output maps as the fp16 pass.  This is pixloc's own
+ * precision and range: a checkpoint whose activations leave fp16's range runs unchanged.  Every pxt_unet_* entry point
+ * above accepts such a context with the same signature:
+ *   - the workspace_bytes* functions return the fp32 pass's sizes (about twice the fp16 ones);
+ *   - forward / forward_batch / forward_pair run the fp32 pass.  Each image's maps are the same bits alone, in a batch
+ *     of any size and in a pair (no split-K, no atomics: every value is one fixed-order chain);
+ *   - set_tile_skip and set_batch_plan are accepted and have no effect (the pass computes every tile, and its bits do not
+ *     depend on the batch);
+ *   - a pair runs both images on the caller's stream, image 0 first, so set_defer_join's contract holds trivially and
+ *     pair_join has nothing to wait for;
+ *   - activation_stats reports all 17 layers (none is left unmaterialised) as fp32 values: a maximum above 65504 is
+ *     a layer the fp16 pass cannot store.
+ * pxt_unet_precision returns 16 or 32 (the context's storage precision), < 0 on a NULL context. */
+int pxt_unet_create_f32(const void* weights_host, int64_t n_bytes, pxt_unet** out_ctx);
+int pxt_unet_precision(const pxt_unet* ctx);
+
 
 /* One 3x3 convolution (pad 1) of the pyramid as a stand-alone call, for layer-by-layer
  * parity tests against torch.nn.functional.conv2d (SURVEY KAT-6) and for profiling:
  * in  [H][W][Cin]  fp16 NHWC (Cin % 32 == 0), weights [Cout][3][3][Cin] fp16
  * (Cout % 32 == 0), bias [Cout] float32, out [H][W][Cout] fp16; fused bias (+ReLU). */
 int pxt_conv3x3_nhwc_f16(const void* in, int32_t H, int32_t W, int32_t Cin, const void* weights,
+                         const float* bias, int32_t Cout, int32_t relu, void* out, void* stream);
+
+/* One 3x3 convolution (pad 1) of the fp32 pass, for layer-level tests: in [H][W][Cin] float32 NHWC (Cin % 16 == 0),
+ * weights [Cout][3][3][Cin] float32 on the device (Cout % 32 == 0), bias [Cout], out [H][W][Cout] float32; fused bias
+ * (+ReLU).  The taps are repacked into the kernel's fragment order on every call. */
+int pxt_conv3x3_nhwc_f32(const void* in, int32_t H, int32_t W, int32_t Cin, const void* weights,
                          const float* bias, int32_t Cout, int32_t relu, void* out, void* stream);
 
 /* The same layer with the taps already in the kernel's MFMA-fragment order (what pxt_unet_create

@@ -20,7 +20,7 @@ LIB_PATH = Path(os.environ["PIXTRACK_HIP_LIB"]) if os.environ.get("PIXTRACK_HIP_
 PXT_MAX_LEVELS = 8
 PXT_LM_LOG_STRIDE = 20
 PXT_E_TIMEOUT = -3
-ABI_VERSION = 12
+ABI_VERSION = 13
 PXT_LM_MAX_BATCH = 16
 PXT_UNET_MAX_BATCH = 16
 PXT_NGP_MAX_BATCH = 16
@@ -144,6 +144,8 @@ PROTOTYPES = {
     "pxt_lm_refine_batch": (C.c_int, [C.POINTER(LmProblem), _I32, C.POINTER(LmConf), _VP, _VP]),
     "pxt_sample_sparse": (C.c_int, [_VP, _I32, _VP, C.POINTER(SampleLevel), _I32, _I32, _I32, _VP, _VP]),
     "pxt_unet_create": (C.c_int, [_VP, _I64, C.POINTER(_VP)]),
+    "pxt_unet_create_f32": (C.c_int, [_VP, _I64, C.POINTER(_VP)]),
+    "pxt_unet_precision": (C.c_int, [_VP]),
     "pxt_unet_destroy": (C.c_int, [_VP]),
     "pxt_unet_workspace_bytes": (_I64, [_VP, _I32, _I32]),
     "pxt_unet_forward": (
@@ -168,6 +170,7 @@ PROTOTYPES = {
          C.POINTER(_I32), C.POINTER(_I32), _VP, _VP],
     ),
     "pxt_conv3x3_nhwc_f16": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP]),
+    "pxt_conv3x3_nhwc_f32": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP]),
     "pxt_conv3x3_packed_bytes": (_I64, [_I32, _I32]),
     "pxt_conv3x3_pack_weights": (C.c_int, [_VP, _I32, _I32, _VP, _VP]),
     "pxt_conv3x3_packed": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _I64, _VP]),

@@ -15,6 +15,7 @@
 // Bias (or the folded BatchNorm affine), ReLU and the encoder's 2x2 max-pool are fused into the
 // epilogue.
 #include "pxt_common.h"
+#include "pxt_unet_f32.h"
 
 #include <algorithm>
 #include <array>
@@ -478,6 +479,7 @@ struct UnetLayer {
 }  // namespace pxt
 
 struct pxt_unet {
+  pxt::UnetF32* f32 = nullptr;        // pxt_unet_create_f32: the fp32 pass (pxt_unet_f32.hip) serves every entry point
   void* dev_head = nullptr;            // fp16 [32*NT][Cin] head weights + fp32 padded biases
   const pxt::half_t* head_w[pxt::kNumHeads];
   const float* head_b[pxt::kNumHeads];
@@ -1089,8 +1091,25 @@ extern "C" int pxt_unet_create(const void* weights_host, int64_t n_bytes, pxt_un
   return PXT_OK;
 }
 
+extern "C" int pxt_unet_create_f32(const void* weights_host, int64_t n_bytes, pxt_unet** out_ctx) {
+  if (!out_ctx) return PXT_E_ARG;
+  pxt::UnetF32* net = nullptr;
+  const int rc = pxt::f32_create(weights_host, n_bytes, &net);
+  if (rc != PXT_OK) return rc;
+  pxt_unet* ctx = new pxt_unet();
+  ctx->f32 = net;
+  *out_ctx = ctx;
+  return PXT_OK;
+}
+
+extern "C" int pxt_unet_precision(const pxt_unet* ctx) {
+  if (!ctx) return PXT_E_ARG;
+  return ctx->f32 ? 32 : 16;
+}
+
 extern "C" int pxt_unet_destroy(pxt_unet* ctx) {
   if (!ctx) return PXT_E_ARG;
+  if (ctx->f32) pxt::f32_destroy(ctx->f32);
   if (ctx->dev_blob) (void)hipFree(ctx->dev_blob);
   if (ctx->dev_head) (void)hipFree(ctx->dev_head);
   if (ctx->dev_packed) (void)hipFree(ctx->dev_packed);
@@ -1111,6 +1130,7 @@ extern "C" int pxt_unet_destroy(pxt_unet* ctx) {
 
 extern "C" int64_t pxt_unet_workspace_bytes_batch(const pxt_unet* ctx, int32_t n_images, int32_t H, int32_t W) {
   if (!ctx) return PXT_E_ARG;
+  if (ctx->f32) return pxt::f32_workspace_bytes_batch(ctx->f32, n_images, H, W);
   Plan P, P1;
   if (!make_plan(ctx, n_images, H, W, P) || !make_plan(ctx, 1, H, W, P1)) return 0;
   // (a batch of two may run as two single-image passes in the two halves of the workspace)
@@ -1353,6 +1373,9 @@ extern "C" int pxt_unet_forward_batch(pxt_unet* ctx, int32_t n_images, const voi
                                       int32_t W, float* const* out_maps, const int32_t out_cstride[3],
                                       const int32_t* normalize, void* workspace, void* stream) {
   if (!ctx || !images || !image_is_u8 || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
+  if (ctx->f32)
+    return pxt::f32_forward_batch(ctx->f32, n_images, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize,
+                                  workspace, (hipStream_t)stream);
   if (ctx->join_pending) { PXT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_join, 0)); ctx->join_pending = false; }
   if (n_images != 2 || knobs().streams < 2)
     return forward_pass(ctx, n_images, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace,
@@ -1363,6 +1386,7 @@ extern "C" int pxt_unet_forward_batch(pxt_unet* ctx, int32_t n_images, const voi
 
 extern "C" int64_t pxt_unet_workspace_bytes_pair(const pxt_unet* ctx, const int32_t H[2], const int32_t W[2]) {
   if (!ctx || !H || !W) return PXT_E_ARG;
+  if (ctx->f32) return pxt::f32_workspace_bytes_pair(ctx->f32, H, W);
   Plan P0, P1;
   if (!make_plan(ctx, 1, H[0], W[0], P0) || !make_plan(ctx, 1, H[1], W[1], P1)) return 0;
   return (int64_t)((P0.total + 255) / 256 * 256 + P1.total);
@@ -1377,6 +1401,9 @@ extern "C" int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, c
                                      float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
                                      void* workspace, void* stream) {
   if (!ctx || !images || !image_is_u8 || !H || !W || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
+  if (ctx->f32)
+    return pxt::f32_forward_pair(ctx->f32, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace,
+                                 (hipStream_t)stream);
   Plan P0, P1;
   if (!make_plan(ctx, 1, H[0], W[0], P0) || !make_plan(ctx, 1, H[1], W[1], P1)) return PXT_E_ARG;
   if (!ctx->pass2) {
@@ -1448,6 +1475,7 @@ extern "C" int pxt_unet_forward(pxt_unet* ctx, const void* image, int32_t image_
 extern "C" int pxt_unet_activation_stats(pxt_unet* ctx, int32_t H, int32_t W, const void* workspace, float* stats,
                                          void* stream) {
   if (!ctx || !workspace || !stats) return PXT_E_ARG;
+  if (ctx->f32) return pxt::f32_activation_stats(ctx->f32, H, W, workspace, stats, (hipStream_t)stream);
   Plan P;
   if (!make_plan(ctx, 1, H, W, P)) return PXT_E_ARG;
   hipStream_t s = (hipStream_t)stream;

@@ -261,7 +261,8 @@ def gpu_checks(rep: Report, snap, weights, aabb, cams):
         if bad or worst > 3.0e4:
             rep.fail("fp16 activations", f"largest |activation| {worst:.0f}, {bad} non-finite value(s) on the thumbnail",
                      "activations stay inside fp16 (max 65504): pixloc runs this network in fp32; unet.auto_rescale_for_fp16(weights, device, images) "
-                     "returns exactly rescaled weights")
+                     "returns exactly rescaled weights, and where it cannot, unet_precision=\"fp32\" (--unet_precision fp32) runs "
+                     "the checkpoint in fp32")
         else:
             rep.ok("fp16 activations", f"largest |activation| {worst:.0f} on the thumbnail render (fp16 max 65504)")
 

@@ -66,12 +66,13 @@ class MultiObjectTracker:
             # ground-truth-gated updates, pixloc_tracker_ycb.py:241-295) would silently run r9's policy here
             if type(tr).refine is not PixLocPoseTrackerR9.refine or type(tr)._frame_policy is not PixLocPoseTrackerR9._frame_policy:
                 raise _lib.PxtError(f"{type(tr).__name__} overrides refine(): lock-step tracking implements PixLocPoseTrackerR9's policy only")
-        # one UNet context runs every image of a group's step: the trackers must hold the same checkpoint
-        # (pixloc_megadepth is one network for all objects; reference pixloc_pose_refiners.py:49-60)
+        # one UNet context runs every image of a group's step: the trackers must hold the same checkpoint in the same
+        # precision (pixloc_megadepth is one network for all objects; reference pixloc_pose_refiners.py:49-60; the
+        # signature names the precision)
         sig = getattr(self.trackers[0].localizer.extractor.model, "weights_signature", None)
         for tr in self.trackers[1:]:
             if getattr(tr.localizer.extractor.model, "weights_signature", None) != sig:
-                raise _lib.PxtError("lock-step trackers must share one UNet checkpoint")
+                raise _lib.PxtError("lock-step trackers must share one UNet checkpoint and unet_precision")
         self.groups: List[_Group] = []
         # a group's queued renders as ONE chain of launches carrying the rays of all its objects (pxt_ngp_render_frame_batch;
         # bit for bit the single renders); PXT_BATCH_RENDERS=0: one chain per object, one after the other
@@ -356,6 +357,8 @@ def main(argv=None):
     ap.add_argument("--debug", type=int, default=0)
     ap.add_argument("--groups", type=int, default=2)
     ap.add_argument("--pixloc_pickles", action="store_true")
+    ap.add_argument("--unet_precision", choices=("fp16", "fp32"), default="fp16",
+                    help="UNet activations of every object: fp16 (default, fastest) or fp32 (pixloc's precision)")
     args = ap.parse_args(argv)
     K = len(args.object_path)
     if len(args.query) != K or len(args.out_dir) != K:
@@ -378,7 +381,7 @@ def main(argv=None):
         os.makedirs(args.out_dir[k], exist_ok=True)
         trackers.append(PixLocPoseTrackerR9(object_path=str(obj), data_path=str(obj / "pixtrack/pixsfm/dataset"),
                                             eval_path=str(args.out_dir[k]), loc_path=str(obj / "pixtrack/aug_nerf_sfm"),
-                                            debug=args.debug))
+                                            debug=args.debug, unet_precision=args.unet_precision))
     multi = MultiObjectTracker(trackers, n_groups=args.groups)
     its = [tr.get_query_frame_iterator(q, args.frames if args.frames is not None else np.inf)
            for tr, q in zip(trackers, args.query)]

@@ -47,14 +47,17 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
 
 
 class PixLocPoseTrackerR9(PoseTracker):
-    def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None):
+    def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
+                 unet_precision="fp16"):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
-        synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img)."""
+        synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
+        ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet)."""
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
                               query_list="*_with_intrinsics.txt", global_descriptors="features.h5",
                               retrieval_pairs="pairs_query.txt", results="pixloc_object.txt")
         pixloc_conf = {
             "experiment": "pixloc_megadepth",
+            "unet_precision": unet_precision,
             "features": {},
             "optimizer": {"num_iters": 150, "pad": 1},
             "refinement": {"num_dbs": 1, "multiscale": [1], "point_selection": "all",
@@ -489,6 +492,8 @@ def main(argv=None):
     parser.add_argument("--debug", type=int, default=0)
     parser.add_argument("--pixloc_pickles", action="store_true",
                         help="write poses.pkl/trackers.pkl with pixloc's Pose/Camera class paths")
+    parser.add_argument("--unet_precision", choices=("fp16", "fp32"), default="fp16",
+                        help="UNet activations: fp16 (default, fastest) or fp32 (pixloc's precision)")
     args = parser.parse_args(argv)
     data_path = args.object_path / "pixtrack/pixsfm/dataset"
     eval_path = args.out_dir
@@ -499,7 +504,8 @@ def main(argv=None):
 
         bind_to_device_numa(0)
     tracker = PixLocPoseTrackerR9(object_path=str(args.object_path), data_path=str(data_path),
-                                  eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug)
+                                  eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
+                                  unet_precision=args.unet_precision)
     import gc
 
     gc.collect()

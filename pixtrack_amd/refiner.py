@@ -508,7 +508,8 @@ class PoseTrackerLocalizer:
     (reference pixloc_pose_refiners.py:28-118).  ``experiment`` weights come either from a
     dict of tensors (``conf["weights"]``: UNet names of pixtrack_amd.unet + "optimizer.{i}.
     dampingnet.const") or from ``conf["weights_path"]`` (a torch file of that dict, or a pixloc
-    ``checkpoint_best.tar``; see unet.load_weights)."""
+    ``checkpoint_best.tar``; see unet.load_weights).  ``conf["unet_precision"]``: "fp16" (default) or "fp32" (the
+    UNet's fp32 pass: pixloc's precision, for checkpoints whose activations fp16 cannot hold)."""
 
     def __init__(self, paths, conf, device: Optional[torch.device] = None, model3d: Optional[Model3D] = None):
         if device is None:
@@ -525,7 +526,7 @@ class PoseTrackerLocalizer:
 
             weights = load_weights(conf["weights_path"])
         conf_optim = merge({"num_iters": 100}, conf.get("optimizer", {}))
-        extractor = UNet(weights, self.device)
+        extractor = UNet(weights, self.device, precision=conf.get("unet_precision", "fp16"))
         optimizer = []
         for i in range(3):
             opt = PixTrackOptimizer(conf_optim, device=self.device)

@@ -9,6 +9,10 @@ The forward pass is a chain of hand-written HIP kernels behind ``pxt_unet_forwar
 fp32 accumulation, BatchNorm folded into the decoder convolutions, and 1x1 heads that
 write the HWC float32 maps (descriptor + confidence channel) the LM kernel reads.
 This module only packs weights and marshals pointers; there is no PyTorch conv path.
+
+``precision="fp32"`` selects the fp32 pass instead (csrc/pxt_unet_f32.hip, pxt_unet_create_f32): fp32 activations,
+convolutions on the exact f32-input MFMA - pixloc's own precision and range, for checkpoints fp16 cannot hold and for
+parity at the oracle's precision.  Its maps do not depend on the batch an image rides in.
 """
 from __future__ import annotations
 
@@ -32,6 +36,8 @@ OUTPUT_DIMS = [32, 128, 128]
 HEAD_INPUTS = [32, 64, 512]
 BN_EPS = 1e-5
 MAGIC = b"PXTUNET1"
+MAGIC_F32 = b"PXTUNF32"
+PRECISIONS = ("fp16", "fp32")
 
 
 def conv_layer_names() -> List[str]:
@@ -226,7 +232,8 @@ def auto_rescale_for_fp16(w: Dict[str, torch.Tensor], device, images, target: fl
             too_big = [k for k, v in fixed.items() if k.endswith(".weight") and v.dim() == 4 and float(v.abs().max()) > 6.0e4]
             if too_big:  # (the compensating factors live in fp16 weights: a cumulative factor beyond ~2^17 does not fit)
                 raise _lib.PxtError(f"auto_rescale_for_fp16: the compensated weights of {too_big} leave fp16's range "
-                                    f"(factors {c}); this checkpoint needs wider storage than fp16")
+                                    f"(factors {c}); this checkpoint needs wider storage than fp16: run it with "
+                                    f"unet_precision=\"fp32\" (UNet(weights, device, precision=\"fp32\"))")
             return fixed, c
         l, mx, bad = worst
         f = 256.0 if bad > 0 else 2.0 ** math.ceil(math.log2(mx / target))
@@ -239,17 +246,21 @@ def _align16(n: int) -> int:
     return (n + 15) // 16 * 16
 
 
-def pack_unet_weights(w: Dict[str, torch.Tensor]) -> bytes:
-    """Flat blob consumed by ``pxt_unet_create``.
+def pack_unet_weights(w: Dict[str, torch.Tensor], precision: str = "fp16") -> bytes:
+    """Flat blob consumed by ``pxt_unet_create`` (``precision="fp16"``) or ``pxt_unet_create_f32`` (``"fp32"``).
 
     Layout: MAGIC(8) | int32 n_conv(17) | int32 n_heads(3) | n_conv x (int32 cin, cout) |
     n_heads x (int32 cin, cout) | n_arrays x (int64 offset, int64 bytes) | data.
+    MAGIC is "PXTUNET1" for fp16, "PXTUNF32" for fp32.
     Arrays, in order: for every conv layer [weights, bias]; for every head [weights, bias].
       * layer 0 weights: float32 [cout][ky][kx][cin]
-      * other conv weights: float16 [cout][ky][kx][cin]  (BatchNorm folded for decoders)
+      * other conv weights: float16 [cout][ky][kx][cin] (fp32 pack: float32)  (BatchNorm folded for decoders, in fp32)
       * conv bias: float32 [cout]
       * head weights: float32 [cin][cout+1] (column `cout` = uncertainty row); bias [cout+1]
     """
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    conv_dtype = np.float16 if precision == "fp16" else np.float32
     names, dims = conv_layer_names(), conv_layer_dims()
     arrays: List[bytes] = []
     for li, (name, (cin, cout)) in enumerate(zip(names, dims)):
@@ -262,7 +273,7 @@ def pack_unet_weights(w: Dict[str, torch.Tensor]) -> bytes:
         else:
             b = w[f"{name}.bias"].detach().float()
         Wk = W.permute(0, 2, 3, 1).contiguous()  # [cout][ky][kx][cin]
-        arrays.append(Wk.numpy().astype(np.float32 if li == 0 else np.float16).tobytes())
+        arrays.append(Wk.numpy().astype(np.float32 if li == 0 else conv_dtype).tobytes())
         arrays.append(b.numpy().astype(np.float32).tobytes())
     for k, (cin, dim) in enumerate(zip(HEAD_INPUTS, OUTPUT_DIMS)):
         Wa = w[f"adapt{k}.weight"].detach().float().reshape(dim, cin)
@@ -272,7 +283,7 @@ def pack_unet_weights(w: Dict[str, torch.Tensor]) -> bytes:
         arrays.append(Wt.numpy().astype(np.float32).tobytes())
         arrays.append(bt.numpy().astype(np.float32).tobytes())
     head = bytearray()
-    head += MAGIC
+    head += MAGIC if precision == "fp16" else MAGIC_F32
     head += struct.pack("<ii", len(names), len(OUTPUT_DIMS))
     for cin, cout in dims:
         head += struct.pack("<ii", cin, cout)
@@ -299,17 +310,23 @@ class UNet:
     scales = [1, 4, 16]
     output_dims = OUTPUT_DIMS
 
-    def __init__(self, weights: Dict[str, torch.Tensor], device: torch.device):
+    def __init__(self, weights: Dict[str, torch.Tensor], device: torch.device, precision: str = "fp16"):
+        """precision: "fp16" (fp16 activations, the default and the fast path) or "fp32" (the fp32 pass)."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.PxtError("UNet needs a ROCm device; no CPU path exists")
-        blob = pack_unet_weights(weights)
+        if precision not in PRECISIONS:
+            raise _lib.PxtError(f"UNet precision must be one of {PRECISIONS}, got {precision!r}")
+        self.precision = precision
+        blob = pack_unet_weights(weights, precision)
         import hashlib
 
-        self.weights_signature = hashlib.sha1(blob).hexdigest()  # (lock-step trackers check that they share a checkpoint)
+        # (lock-step trackers check that they share a checkpoint AND a precision)
+        self.weights_signature = f"{precision}:{hashlib.sha1(blob).hexdigest()}"
         self._ctx = C.c_void_p()
+        create = "pxt_unet_create" if precision == "fp16" else "pxt_unet_create_f32"
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().pxt_unet_create(blob, len(blob), C.byref(self._ctx)), "pxt_unet_create")
+            _lib.check(getattr(_lib.lib(), create)(blob, len(blob), C.byref(self._ctx)), create)
         self._ws: Optional[torch.Tensor] = None
 
     def __del__(self):
@@ -397,7 +414,8 @@ class UNet:
         """Range check of the fp16 activations for one image (HWC 0..255 on the device): runs a single-image pass and
         returns [(largest |activation|, number of non-finite values)] for the 17 convolutions (None for the two layers
         that are never written to memory).  pixloc runs this network in fp32; with a real checkpoint, call this on a few
-        frames before trusting the poses: a count > 0 or a maximum near 65504 means fp16 storage overflows there."""
+        frames before trusting the poses: a count > 0 or a maximum near 65504 means fp16 storage overflows there.
+        On an fp32 network every layer is reported, as fp32 values: a maximum above 65504 is a layer fp16 cannot store."""
         self.forward_packed(image, mask, normalize=False)
         H, W = int(image.shape[0]), int(image.shape[1])
         stats = torch.zeros(34, dtype=torch.float32, device=self.device)

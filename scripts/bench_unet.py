@@ -1,4 +1,9 @@
-"""Per-image time of the HIP UNet and achieved MFMA rate (241.4 GFLOP @ 640x480)."""
+"""Per-image time of the HIP UNet and achieved MFMA rate (241.4 GFLOP @ 640x480).
+
+    python scripts/bench_unet.py                    # the fp16 pass
+    python scripts/bench_unet.py --precision fp32   # the fp32 pass (f32 MFMA peak 157 TFLOP/s)
+"""
+import argparse
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -13,9 +18,12 @@ def flops(H, W):
         tot += 2 * 9 * cin * cout * hs[r][0] * hs[r][1]
     return tot
 
-def main():
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", choices=("fp16", "fp32"), default="fp16")
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
-    net = UNet(make_synthetic_unet_weights(7), dev)
+    net = UNet(make_synthetic_unet_weights(7), dev, precision=args.precision)
     for (H, W) in [(240, 320), (480, 640), (576, 1024)]:
         img = torch.rand(H, W, 3, device=dev) * 255
         for _ in range(3):
@@ -29,7 +37,7 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / reps
-        print(f"{W}x{H}: {ms:.3f} ms/image  {flops(H, W)/ms/1e9:.1f} TFLOP/s", flush=True)
+        print(f"{args.precision} {W}x{H}: {ms:.3f} ms/image  {flops(H, W)/ms/1e9:.1f} TFLOP/s", flush=True)
 
 if __name__ == "__main__":
     main()

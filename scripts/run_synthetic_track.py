@@ -13,12 +13,13 @@ def main():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--seed", type=int, default=1002)
+    ap.add_argument("--unet_precision", choices=("fp16", "fp32"), default="fp16")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     t0 = time.time()
     assets = make_tracking_assets(seed=args.seed, width=args.width, height=args.height, n_frames=args.frames)
     print(f"assets: {time.time()-t0:.1f}s", flush=True)
-    tr = PixLocPoseTrackerR9("", "", "", "/tmp", debug=1, device=dev, assets=assets)
+    tr = PixLocPoseTrackerR9("", "", "", "/tmp", debug=1, device=dev, assets=assets, unet_precision=args.unet_precision)
     t0 = time.time()
     frames = render_query_frames(assets, tr.testbed)
     torch.cuda.synchronize()
