@@ -16,11 +16,17 @@ Workloads (--config): `frames640` (default; BASELINE configs[1], the metric's co
 reference's config/*.sh), `hd` (configs[4]: 1920x1080 queries, 10 000 points, the 4-level stress
 pyramid, ONE video cut into per-rank frame segments that cold-start, stitched by the final gather).
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line, which
+carries the live roofline of the dominant kernel from the timed steps.  `--full` adds what takes
+runs of its own: the untimed per-stage and roofline passes (`stage_ms_per_frame`,
+`roofline_stages`), the extra passes (`extras`, N = 1), the CPU baseline (N = 1) and, for
+objects8, the phase times and the one-object comparison passes.
+
 The timed loop carries only the roofline's instrumentation (HIP events around the dominant
-kernel's launches of every 4th render, one sample-count atomic per workgroup); per-stage times
-and the dominant kernel's isolated timing come from a separate untimed pass over the next 20
-frames.  Garbage is collected and frozen BEFORE the warm-up frames (collected between them and the
-timed region it left the GPU idle and the first timed frame 0.75 ms slow).  The per-frame cost
+kernel's launches of every 4th render, one sample-count atomic per workgroup); with --full,
+per-stage times come from a separate untimed pass over the next 20 frames.  Garbage is collected
+and frozen BEFORE the warm-up frames (collected between them and the timed region it left the
+GPU idle and the first timed frame 0.75 ms slow).  The per-frame cost
 varies along the synthetic orbit (longer rays as the object turns: render 0.66 ms on the first
 frames, 0.70-0.79 later), so `value` depends a little on K: 680-692 frames/s at the driver's K = 20
 and at K = 60, 652-665 over 200 frames (`extras.value_k200`); `extras.value_two_renders` (549-552) is
@@ -385,8 +391,8 @@ def run_extras(tracker, assets, frames, names, warmup, n_timed_end, first_free, 
         except Exception as e:  # (reported, never fatal: the headline line must come out)
             out[key] = {"frames_per_s": None, "error": repr(e)[:300]}
     # BASELINE configs[3] / [4] at N = 1, each as its own `--config` run of this file: one driver record for all three workloads
-    for key, argv in (("value_objects8_one_gpu", ["--config", "objects8", "--steps", "20", "--warmup", "5"]),
-                      ("value_hd", ["--config", "hd", "--steps", "12", "--warmup", "3"])):
+    for key, argv in (("value_objects8_one_gpu", ["--config", "objects8", "--steps", "20", "--warmup", "5", "--full"]),
+                      ("value_hd", ["--config", "hd", "--steps", "12", "--warmup", "3", "--full"])):
         out[key] = other_config_extra(argv)
     return out
 
@@ -594,9 +600,10 @@ def run_hd(args, rank, ws, dev, coll_dev, numa_node):
             rot.append(float(np.arccos(np.clip((np.trace(Rr @ Rg.T) - 1) / 2, -1, 1))))
             tra.append(float(np.linalg.norm(tt - tg)))
     lm = tracker.localizer.refiner.last_lm
-    # untimed: where a frame of this workload goes (HIP events per stage, the last frames of this rank's last segment again)
+    # untimed (--full): where a frame of this workload goes (HIP events per stage, the last frames of this rank's last segment
+    # again)
     stage_hd = None
-    if mine:
+    if mine and args.full:
         timer = StageTimer()
         for attr in ("render_device", "render_both_device", "render_frame_device", "render_frame_pair_device"):
             timer.wrap(tracker.testbed, attr, "nerf_render")
@@ -638,13 +645,53 @@ def run_hd(args, rank, ws, dev, coll_dev, numa_node):
     print(json.dumps(out), flush=True)
 
 
+def objects8_phase_stages(args, multi, trackers, units, frames, names, n, n_diag):
+    """Untimed (--full): per-phase HIP-event times of a lock-step step over frames [n, n + n_diag) (render-ahead off:
+    nothing rides behind the LM launch) and the live rooflines of the batched UNet pass and the batched LM launch."""
+    ahead = [tr.render_ahead for tr in trackers]
+    for tr in trackers:
+        tr.render_ahead = False
+        tr._ahead_ok = None
+    phases, lm_iters = [], []
+    multi.set_groups(1)  # (one group: the phases of a step follow each other on one stream)
+    for i in range(n, n + n_diag):
+        multi.timing = {}
+        multi.run_single_frames([(names[i], frames[u][i]) for u in units])
+        torch.cuda.synchronize()
+        t = multi.timing
+        order = ["step_begin", "renders_enqueued", "unet_enqueued", "sampling_enqueued", "lm_enqueued", "step_end"]
+        phases.append([t[a][0].elapsed_time(t[b][0]) for a, b in zip(order[:-1], order[1:])])
+        lm_iters.append([[list(r.iters) for r in tr.localizer.refiner.last_lm][0] for tr in trackers])
+    multi.timing = None
+    for tr, a in zip(trackers, ahead):
+        tr.render_ahead = a
+    ph = np.mean(np.array(phases[1:]), 0)  # (the first diagnostic step still consumed queued renders)
+    K = len(units)
+    gf = 2 * K * unet_gflop(args.height, args.width)
+    n_pts = [int(tr.localizer.refiner._points_of(tr.reference_ids)[1].shape[0]) for tr in trackers]
+    lm_mb = float(np.mean([sum(lm_algorithmic_mb(npt, it, [128, 128, 32]) for npt, it in zip(n_pts, per)) for per in lm_iters[1:]]))
+    return {
+        "phase_ms_per_step": {"renders": round(float(ph[0]), 4), "unet": round(float(ph[1]), 4), "sampling": round(float(ph[2]), 4),
+                              "lm": round(float(ph[3]), 4), "host_policy": round(float(ph[4]), 4)},
+        "unet": {"bound": "mfma", "images_per_call": 2 * K, "gflop_per_call": round(gf, 1), "ms": round(float(ph[1]), 4),
+                 "achieved": round(gf / float(ph[1]), 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                 "frac": round(gf / float(ph[1]) / MFMA_PEAK_TFLOPS, 4), "ms_per_image_pair": round(float(ph[1]) / K, 4)},
+        "lm": {"bound": "hbm", "problems_per_launch": K, "algorithmic_mb": round(lm_mb, 1), "kernel_us": round(float(ph[3]) * 1e3, 1),
+               "us_per_problem": round(float(ph[3]) * 1e3 / K, 1), "achieved": round(lm_mb / (float(ph[3]) * 1e3) * 1e3, 1),
+               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(lm_mb / (float(ph[3]) * 1e3) * 1e3 / HBM_PEAK_GBS, 4),
+               "iterations_per_level_mean": [round(float(x), 2) for x in np.mean(np.array(lm_iters[1:], float), (0, 1))]},
+        "what": "HIP events between the phases of an untimed lock-step step (render-ahead off), mean of 3 steps",
+    }
+
+
 def run_objects8(args, rank, ws, dev, coll_dev, numa_node):
     """BASELINE configs[3]: the eight objects of the reference's config/*.sh tracked CONCURRENTLY on N GPUs - rank r carries
     objects r, r + N, ... (8 / N per rank), advanced in lock-step by a MultiObjectTracker: their 2 K images of a step in one
     batched UNet pass, their K refinements in one persistent launch (pxt_lm_refine_batch), one renderer context per object.
     A step = one frame of every object of the rank; value = frames of all 8 objects / slowest rank's time (the work is
-    the same 8 objects whatever N: "strong" scaling).  At N = 1 an untimed second pass tracks the same frames with
-    eight one-object trackers, one after the other, for the comparison the line carries (solo aggregate, pose differences)."""
+    the same 8 objects whatever N: "strong" scaling).  With --full, untimed passes follow: per-phase HIP-event times of a
+    lock-step step and, at N = 1, the same frames tracked by eight one-object trackers, one after the other, for the
+    comparison the line carries (solo aggregate, pose differences)."""
     import gc
 
     from pixtrack_amd import parallel
@@ -655,7 +702,7 @@ def run_objects8(args, rank, ws, dev, coll_dev, numa_node):
     objs = parallel.load_object_configs()
     units = parallel.shard_units(len(objs), rank, ws)
     n = args.warmup + args.steps
-    n_diag = 4
+    n_diag = 4 if args.full else 0
     names = [f"{i:06d}.png" for i in range(n + n_diag)]
     assets = {u: make_tracking_assets(seed=1002 + u, width=args.width, height=args.height, n_frames=n + n_diag,
                                       aabb=objs[u]["aabb"]) for u in units}
@@ -696,44 +743,10 @@ def run_objects8(args, rank, ws, dev, coll_dev, numa_node):
     units_all = parallel.gather_objects(units)
     n_ok = int(sum(float(g[:, 12].sum()) for g in gathered))
     total_frames = sum(g.shape[0] for g in gathered)
-    # untimed: per-phase HIP-event times of a lock-step step (render-ahead off: nothing rides behind the LM launch) and the
-    # live rooflines of the batched UNet pass and the batched LM launch
-    ahead = [tr.render_ahead for tr in trackers]
-    for tr in trackers:
-        tr.render_ahead = False
-        tr._ahead_ok = None
-    phases, lm_iters = [], []
-    multi.set_groups(1)  # (one group: the phases of a step follow each other on one stream)
-    for i in range(n, n + n_diag):
-        multi.timing = {}
-        multi.run_single_frames([(names[i], frames[u][i]) for u in units])
-        torch.cuda.synchronize()
-        t = multi.timing
-        order = ["step_begin", "renders_enqueued", "unet_enqueued", "sampling_enqueued", "lm_enqueued", "step_end"]
-        phases.append([t[a][0].elapsed_time(t[b][0]) for a, b in zip(order[:-1], order[1:])])
-        lm_iters.append([[list(r.iters) for r in tr.localizer.refiner.last_lm][0] for tr in trackers])
-    multi.timing = None
-    for tr, a in zip(trackers, ahead):
-        tr.render_ahead = a
-    ph = np.mean(np.array(phases[1:]), 0)  # (the first diagnostic step still consumed queued renders)
-    K = len(units)
-    gf = 2 * K * unet_gflop(args.height, args.width)
-    n_pts = [int(tr.localizer.refiner._points_of(tr.reference_ids)[1].shape[0]) for tr in trackers]
-    lm_mb = float(np.mean([sum(lm_algorithmic_mb(npt, it, [128, 128, 32]) for npt, it in zip(n_pts, per)) for per in lm_iters[1:]]))
-    stages = {
-        "phase_ms_per_step": {"renders": round(float(ph[0]), 4), "unet": round(float(ph[1]), 4), "sampling": round(float(ph[2]), 4),
-                              "lm": round(float(ph[3]), 4), "host_policy": round(float(ph[4]), 4)},
-        "unet": {"bound": "mfma", "images_per_call": 2 * K, "gflop_per_call": round(gf, 1), "ms": round(float(ph[1]), 4),
-                 "achieved": round(gf / float(ph[1]), 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                 "frac": round(gf / float(ph[1]) / MFMA_PEAK_TFLOPS, 4), "ms_per_image_pair": round(float(ph[1]) / K, 4)},
-        "lm": {"bound": "hbm", "problems_per_launch": K, "algorithmic_mb": round(lm_mb, 1), "kernel_us": round(float(ph[3]) * 1e3, 1),
-               "us_per_problem": round(float(ph[3]) * 1e3 / K, 1), "achieved": round(lm_mb / (float(ph[3]) * 1e3) * 1e3, 1),
-               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(lm_mb / (float(ph[3]) * 1e3) * 1e3 / HBM_PEAK_GBS, 4),
-               "iterations_per_level_mean": [round(float(x), 2) for x in np.mean(np.array(lm_iters[1:], float), (0, 1))]},
-        "what": "HIP events between the phases of an untimed lock-step step (render-ahead off), mean of 3 steps",
-    }
-    solo = None
-    if ws == 1 and not args.no_solo:
+    stages, solo = None, None
+    if args.full:
+        stages = objects8_phase_stages(args, multi, trackers, units, frames, names, n, n_diag)
+    if args.full and ws == 1 and not args.no_solo:
         # the same frames through eight ONE-object trackers, one after the other: what the lock-step run is compared with
         fps, diffs, solo_err, lock_err, solo_ok = [], [], [], [], 0
         for u, tr_multi in zip(units, trackers):
@@ -939,9 +952,14 @@ def main():
                          "0 = as many as fit the default ~70 s budget after 1 warm-up frame")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path computed in its last step (poses, cost, flags) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed per-stage and roofline passes, the "
+                         "extra passes, the CPU baseline and (objects8) the one-object comparison passes")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.cpu_baseline_frames and not args.full:
+        ap.error("--cpu-baseline-frames needs --full (a plain run does not run the CPU baseline)")
     if args.dump_outputs and args.extra:
         ap.error("--dump-outputs needs the timed path; --extra runs an extra pass only")
     if args.first_frame_sigma is None:
@@ -991,10 +1009,11 @@ def main():
         return run_objects8(args, rank, ws, dev, coll_dev, numa_node)
     args.object_index = max(args.object_index, 0)
 
-    n_diag = min(20, args.steps)  # untimed diagnostic pass (per-stage HIP-event times)
-    n_roof = 8                    # untimed pass of the per-stage rooflines (UNet TFLOP/s, LM TB/s)
+    # (frames are generated in order from one seeded stream: frame i is the same whatever the number after it)
+    n_diag = min(20, args.steps) if args.full else 0  # untimed diagnostic pass (per-stage HIP-event times)
+    n_roof = 8 if args.full else 0                    # untimed pass of the per-stage rooflines (UNet TFLOP/s, LM TB/s)
     n_timed_end = args.warmup + args.steps
-    extras_on = ws == 1 and not args.no_extras and args.config == "frames640"
+    extras_on = args.full and ws == 1 and not args.no_extras and args.config == "frames640"
     n_extra = 200 if extras_on else 0
     n_frames = n_timed_end + n_diag + n_roof + n_extra
     unit = parallel.shard_units(ws, rank, ws)[0]  # one sequence per rank, seeds 1002, 1003, ...
@@ -1063,26 +1082,28 @@ def main():
     report = rank_report(rank, local_rank, dev, numa_node, args.steps, own_elapsed, coll_dev)
     stats = tracker.testbed.stats_accum.cpu().tolist()
     n_renders = tracker.testbed.n_renders - n_renders0
-    # Two untimed passes over the next frames of the same sequence.
-    # (1) per-stage times: event pairs around every stage cost ~10 % of a frame, so they stay out
-    #     of the timed region;
-    #     with the tracker's render-ahead off: a render enqueued behind the LM launch would be booked to "lm"
-    n_stage = n_diag // 2
     render_ahead = getattr(tracker, "render_ahead", False)
-    tracker.render_ahead = False
-    tracker._ahead_ok = None  # (the render queued behind the last timed frame's LM launch is not used either)
-    torch.cuda.synchronize()
-    timer.enabled = True
-    for i in range(n_timed_end, n_timed_end + n_stage):
-        tracker.run_single_frame((names[i], frames[i]))
-    torch.cuda.synchronize()
-    timer.enabled = False
-    for i in range(n_timed_end + n_stage, n_timed_end + n_diag):  # (frames kept in step with the earlier rounds' passes)
-        tracker.run_single_frame((names[i], frames[i]))
-    torch.cuda.synchronize()
-    tracker.render_ahead = render_ahead
-    # (3) live rooflines of the other two stages (the UNet is ~47 % of the frame, the LM ~6 %)
-    roofline_stages = stage_rooflines(tracker, frames, names, n_timed_end + n_diag, n_timed_end + n_diag + n_roof, dev)
+    roofline_stages = None
+    if args.full:
+        # Two untimed passes over the next frames of the same sequence.
+        # (1) per-stage times: event pairs around every stage cost ~10 % of a frame, so they stay out
+        #     of the timed region;
+        #     with the tracker's render-ahead off: a render enqueued behind the LM launch would be booked to "lm"
+        n_stage = n_diag // 2
+        tracker.render_ahead = False
+        tracker._ahead_ok = None  # (the render queued behind the last timed frame's LM launch is not used either)
+        torch.cuda.synchronize()
+        timer.enabled = True
+        for i in range(n_timed_end, n_timed_end + n_stage):
+            tracker.run_single_frame((names[i], frames[i]))
+        torch.cuda.synchronize()
+        timer.enabled = False
+        for i in range(n_timed_end + n_stage, n_timed_end + n_diag):  # (frames kept in step with the earlier rounds' passes)
+            tracker.run_single_frame((names[i], frames[i]))
+        torch.cuda.synchronize()
+        tracker.render_ahead = render_ahead
+        # (3) live rooflines of the other two stages (the UNet is ~47 % of the frame, the LM ~6 %)
+        roofline_stages = stage_rooflines(tracker, frames, names, n_timed_end + n_diag, n_timed_end + n_diag + n_roof, dev)
 
     extras = None
     if extras_on:
@@ -1194,16 +1215,18 @@ def main():
         "frames_total": total_frames,
         "mean_rot_err_vs_gt_rad": round(float(np.mean(rot_err)), 6) if rot_err else None,
         "mean_trans_err_vs_gt": round(float(np.mean(tr_err)), 6) if tr_err else None,
-        "stage_ms_per_frame": {k: round(v[0] / max(n_diag // 2, 1), 4) for k, v in stage.items()},
         "frame_ms": {"p50": round(float(np.percentile(frame_ms, 50)), 4), "p90": round(float(np.percentile(frame_ms, 90)), 4),
                      "max": round(float(frame_ms.max()), 4), "argmax": int(frame_ms.argmax())},
-        "stage_ms_note": (f"HIP-event times of a separate untimed pass over the next {n_diag // 2} frames; `unet` ends when the "
-                          "reference pass ends on the caller's stream - the query pass is joined behind the sparse sampling "
-                          "(deferred join), so its last ~20-40 us are booked to `sample` / `lm`"),
         "roofline": roofline,
-        "roofline_stages": roofline_stages,
+        "full": bool(args.full),
         **report,
     }
+    if args.full:
+        out["stage_ms_per_frame"] = {k: round(v[0] / max(n_diag // 2, 1), 4) for k, v in stage.items()}
+        out["stage_ms_note"] = (f"HIP-event times of a separate untimed pass over the next {n_diag // 2} frames; `unet` ends when "
+                                "the reference pass ends on the caller's stream - the query pass is joined behind the sparse "
+                                "sampling (deferred join), so its last ~20-40 us are booked to `sample` / `lm`")
+        out["roofline_stages"] = roofline_stages
     # other kernels' utilisation from the committed rocprofv3 SQ counter pass of this command
     # (profiles/r02_pmc_sq.json; scripts/pmc_sq_summary.py): matrix-pipe busy of the UNet convolutions,
     # VALU busy of the march (a serial DDA per ray: latency- and tail-bound, not VALU-bound)
@@ -1222,7 +1245,7 @@ def main():
                                      or PROFILE_COMMITS.get(sq.name[:3]), "kernels": pick}
     if extras is not None:
         out["extras"] = extras
-    if not args.no_cpu_baseline and ws == 1:
+    if args.full and not args.no_cpu_baseline and ws == 1:
         try:
             if args.cpu_baseline_frames > 0:  # BASELINE.md 3 to the letter: 3 warm-up frames, then exactly this many
                 out["cpu_baseline"] = cpu_baseline(assets, frames, args.warmup, ref_id_start, budget_s=1e9,
@@ -1235,7 +1258,7 @@ def main():
                                    "sample": f"failed: {e!r}"}
     else:
         out["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": os.cpu_count(), "kind": "port",
-                               "sample": "timed on rank 0 at N=1 only"}
+                               "sample": "timed on rank 0 at N=1 only" if args.full or ws > 1 else "not run: `--full` runs it"}
     print(json.dumps(out), flush=True)
 
 

@@ -6,7 +6,7 @@ r=${1:-r05}
 root=$GRAFT_REPO_ROOT; [ -z "$root" ] && root=$(pwd)
 out=$root/gpurun_out/$r; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
-cmd="python $root/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras"
+cmd="python $root/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- $cmd > $out/${r}_bench_under_rocprof.log 2>&1
 python $root/scripts/rocpd_summary.py $out/kt/kt_results.db > $out/${r}_kernel_stats.csv
 python $root/scripts/unet_timeline.py $out/kt/kt_results.db > $out/${r}_unet_timeline.txt 2>&1
@@ -36,7 +36,7 @@ for e in ycb_refshape r9_phone; do
   python $root/scripts/pmc_sq_summary.py $out/rsq_$e > $out/${r}_refshape_${e}_pmc_sq.json
 done
 # ---- the eight objects in lock-step on one GPU (configs[3], N = 1): kernel trace + step summary + SQ pass of the batched passes
-o8="python $root/bench.py --config objects8 --steps 12 --warmup 4 --no-solo"
+o8="python $root/bench.py --config objects8 --steps 12 --warmup 4 --full --no-solo"
 rocprofv3 --kernel-trace --stats -d $out/o8 -o o8 -- $o8 > $out/${r}_objects8_under_rocprof.log 2>&1
 python $root/scripts/rocpd_summary.py $out/o8/o8_results.db > $out/${r}_objects8_kernel_stats.csv
 python $root/scripts/multiobj_trace.py $out/o8/o8_results.db 6 2 4 > $out/${r}_objects8_step_summary.txt 2>&1
@@ -44,11 +44,11 @@ rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_VA
   --kernel-trace --output-format csv -d $out/o8sq -- $o8 --groups 1 > $out/o8sq.log 2>&1
 python $root/scripts/pmc_sq_summary.py $out/o8sq > $out/${r}_objects8_pmc_sq.json
 cd $root
-python bench.py --config objects8 > $out/${r}_bench_objects8.json 2> $out/${r}_bench_objects8.err
+python bench.py --config objects8 --full > $out/${r}_bench_objects8.json 2> $out/${r}_bench_objects8.err
 python scripts/bench_lm_batch.py 2341 > $out/${r}_bench_lm_batch.log 2>&1
 python scripts/bench_unet_batch.py --sizes 2,4,8,16 > $out/${r}_bench_unet_batch.log 2>&1
 python scripts/bench_conv.py --all-cfgs > $out/${r}_conv_cfgs.log 2>&1
-python bench.py > $out/${r}_bench.json 2> $out/${r}_bench.err
-python bench.py --steps 200 --warmup 5 --no-cpu-baseline --no-extras > $out/${r}_bench_k200.json 2>/dev/null
+python bench.py --full > $out/${r}_bench.json 2> $out/${r}_bench.err
+python bench.py --steps 200 --warmup 5 --full --no-cpu-baseline --no-extras > $out/${r}_bench_k200.json 2>/dev/null
 rm -rf $out/pf $out/pw $out/psq $out/pl1 $out/pl2 $out/ut $out/rs_* $out/rsq_* $out/o8 $out/o8sq  # (databases: too large to carry back)
 ls -la $out | head -60

@@ -1,7 +1,7 @@
 """Per-step summary of a rocprofv3 kernel trace (rocpd database) of a lock-step multi-object run
 (scripts/bench_multiobj.py / bench.py --config objects8): wall time per step, GPU busy (union of all queues), summed kernel
 time per family, the largest kernels.   python scripts/multiobj_trace.py results.db [steps=8] [launches_per_step=1] [skip_last=0]
-(skip_last: trailing lm_refine_batch launches to leave out - bench.py --config objects8 ends with 4 one-group diagnostic steps
+(skip_last: trailing lm_refine_batch launches to leave out - bench.py --config objects8 --full ends with 4 one-group diagnostic steps
 with render-ahead off)"""
 import sqlite3
 import sys

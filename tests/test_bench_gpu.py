@@ -21,7 +21,7 @@ def _last_json(stdout: str) -> dict:
 
 def test_single_gpu_line_has_the_contract_fields(device):
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -65,6 +65,28 @@ def test_single_gpu_line_has_the_contract_fields(device):
     assert ex["value_ycb_policy"]["renders_ahead_used"] >= ex["value_ycb_policy"]["frames"] - 2
 
 
+def test_plain_run_times_the_steps_and_nothing_else(device):
+    """A plain `--gpus 1 --steps K --warmup W` run prints the headline line without the passes `--full` adds (untimed
+    stage and roofline passes, extras, CPU baseline); the dominant kernel's roofline comes from the timed steps."""
+    import time
+
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3"],
+                         capture_output=True, text=True, timeout=300, cwd=str(ROOT))
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = _last_json(out.stdout)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert k in d, k
+    assert d["full"] is False and d["steps"] == 12 and d["warmup"] == 3 and d["tracked_ok"] == d["frames_total"] == 12
+    assert not {"extras", "roofline_stages", "stage_ms_per_frame"} & set(d), sorted(d)
+    assert d["cpu_baseline"]["value"] is None and 0.05 < d["roofline"]["frac"] < 1.0
+    # (a plain run's budget outside its steps is 30 s; the bound leaves room for a busy host and still catches a pass
+    # that creeps back in - the CPU baseline alone takes over 70 s)
+    assert wall - 15 * d["ms_per_step"] * 1e-3 < 60.0, wall
+
+
 def test_dump_outputs_writes_the_last_timed_step(device, tmp_path):
     """`--dump-outputs DIR`: the last timed frame's pose record as float64 .npy files; two runs of the same command track
     the same seeded inputs to the same pose; `--steps` sets the timed frames."""
@@ -90,7 +112,7 @@ def test_objects8_and_hd_workloads_run(device):
     """configs[3] (one config/*.sh object per rank) and configs[4] (1920x1080, 4-level stress pyramid,
     frame segments) at N = 1."""
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", "objects8", "--steps", "8", "--warmup", "3",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     # configs[3] on ONE GPU: all eight config/*.sh objects in lock-step (MultiObjectTracker), 8 frames each
