@@ -46,7 +46,8 @@ extern "C" {
 #define PXT_LM_LOG_STRIDE 20 /* floats per logged iteration, see pxt_lm_refine */
 
 /* Library / device info ---------------------------------------------------- */
-int pxt_version(void);               /* ABI version (13), bumps on any signature change or added entry point */
+int pxt_version(void);               /* ABI version (13); bumps when an existing entry point's signature or a
+                                        struct layout changes (added entry points and structs keep it) */
 const char* pxt_last_error(void);    /* text of the last PXT_E_HIP on this thread */
 int pxt_device_cus(int* n_cus_host); /* multiprocessor count of the current device */
 
@@ -191,6 +192,41 @@ typedef struct {
 int pxt_sample_sparse(const float* p3d, int32_t n_points, const float* T_host /* 12 floats */,
                       const pxt_sample_level* levels_host, int32_t n_levels, int32_t pad,
                       int32_t normalize, uint8_t* valid /* [n_points] */, void* stream);
+
+/* -------------------------------------------------------------------------
+ * Pose hypothesis scoring (relocalisation: pixtrack_amd/relocalizer.py).
+ *
+ * The reference has no relocaliser (PixLocPoseTrackerR9.relocalize only counts).  One launch scores M pose
+ * hypotheses against ONE query feature map (typically the stride-16 level, C = 128): hypothesis h has a pose
+ * (poses[h], 12 floats, row-major R then t) and a contiguous range [begin, begin + count) = ranges[h] of one flat
+ * point bank.  For each VALID point (the LM's rule: in front of the camera, inside the image with conf->pad, and
+ * bank->valid[n] != 0 when a mask is given) the map is sampled bilinearly and, with r = F_q - F_ref over the C
+ * descriptor channels and w = (query confidence) * (reference confidence):
+ *   out[h][0] = sum rho(|r|^2)   out[h][1] = n_valid   out[h][2] = sum w * rho   out[h][3] = sum w
+ * rho is the LM's loss (conf->loss, loss_alpha, loss_scale; the other conf fields are ignored).  out[h][0] / out[h][1]
+ * is the masked-mean cost pxt_lm_refine logs at k = 0 of its first iteration for the same pose, points and level, and
+ * out[h][1] that log's k = 1.  Deterministic: a hypothesis's four values depend on its own inputs only (fixed-order
+ * reduction, one workgroup per hypothesis), not on M or on the other hypotheses.  A range outside the bank yields
+ * {NaN, -1, NaN, NaN}.  poses, ranges and out are device arrays (M is bounded by memory); no workspace is needed.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  const float* fmap;   /* query map, HWC [h][w][cstride], descriptor L2-normalised, confidence at channel C */
+  int32_t h, w, C, cstride;
+  float cam[10];       /* query camera scaled to this level (as pxt_lm_level holds it) */
+  int32_t ndist;
+} pxt_reloc_map;
+
+typedef struct {
+  const float* p3d;      /* [n_points][3] world points */
+  const float* fref;     /* [n_points][cstride] reference records: descriptor L2-normalised, confidence at C */
+  const uint8_t* valid;  /* [n_points] point mask, or NULL */
+  int32_t n_points;
+} pxt_reloc_bank;
+
+int pxt_score_pose_hypotheses(const pxt_reloc_map* map_host, const pxt_reloc_bank* bank_host,
+                              const float* poses /* device [M][12] */, const int32_t* ranges /* device [M][2] */,
+                              int32_t n_hypotheses, const pxt_lm_conf* conf_host, float* out /* device [M][4] */,
+                              void* stream);
 
 /* -------------------------------------------------------------------------
  * UNet feature pyramid (pixloc `UNet`, experiment pixloc_megadepth).

@@ -123,6 +123,22 @@ class LmProblem(C.Structure):
                 ("out", C.c_void_p), ("log", C.c_void_p), ("workspace", C.c_void_p), ("cam_host", C.POINTER(LmCamera))]
 
 
+class RelocMap(C.Structure):
+    _fields_ = [
+        ("fmap", C.c_void_p),
+        ("h", C.c_int32),
+        ("w", C.c_int32),
+        ("C", C.c_int32),
+        ("cstride", C.c_int32),
+        ("cam", C.c_float * 10),
+        ("ndist", C.c_int32),
+    ]
+
+
+class RelocBank(C.Structure):
+    _fields_ = [("p3d", C.c_void_p), ("fref", C.c_void_p), ("valid", C.c_void_p), ("n_points", C.c_int32)]
+
+
 _lib: Optional[C.CDLL] = None
 
 # name -> (restype, argtypes); every symbol include/pixtrack_hip.h declares.
@@ -143,6 +159,8 @@ PROTOTYPES = {
     "pxt_lm_batch_workspace_bytes": (_I64, [_I32]),
     "pxt_lm_refine_batch": (C.c_int, [C.POINTER(LmProblem), _I32, C.POINTER(LmConf), _VP, _VP]),
     "pxt_sample_sparse": (C.c_int, [_VP, _I32, _VP, C.POINTER(SampleLevel), _I32, _I32, _I32, _VP, _VP]),
+    "pxt_score_pose_hypotheses": (
+        C.c_int, [C.POINTER(RelocMap), C.POINTER(RelocBank), _VP, _VP, _I32, C.POINTER(LmConf), _VP, _VP]),
     "pxt_unet_create": (C.c_int, [_VP, _I64, C.POINTER(_VP)]),
     "pxt_unet_create_f32": (C.c_int, [_VP, _I64, C.POINTER(_VP)]),
     "pxt_unet_precision": (C.c_int, [_VP]),

@@ -8,6 +8,7 @@ Reference call sites the ops stand in for:
   lm_refine            pixloc BaseRefiner.refine_pose_using_features -> opt.run per level
                        (pixtrack/localization/pixloc_pose_refiners.py:255-262)
   sample_sparse        PoseTrackerRefiner.interp_sparse_observations (:327-368, interpolator :351)
+  score_pose_hypotheses  (no reference counterpart) M pose hypotheses scored in one launch (relocalizer.py)
   unet_forward_batch   self.model({"image": ...}) (pixtrack/localization/feature_extractor.py:48)
   ngp_render[_both]    testbed.render(w, h, spp, True) (pixtrack/visualization/run_vis_on_poses.py:51)
   depth_mask           get_mask morphology (pixtrack/pose_trackers/pixloc_tracker_r9.py:207-214)
@@ -50,6 +51,11 @@ SCHEMAS = {
     "sample_sparse": (
         "(Tensor p3d, float[] T, Tensor[] fmaps, int[] channels, float[] cameras, int[] ndist, int pad, "
         "bool normalize, Tensor(a!)[] outs, Tensor(b!) valid, int[]? windows=None) -> ()"),
+    # M pose hypotheses against one query map (pxt_score_pose_hypotheses): poses [M, 12], ranges [M, 2] int32 into the
+    # bank (p3d [N, 3], fref [N, cstride], valid [N] uint8 or None), out [M, 4]
+    "score_pose_hypotheses": (
+        "(Tensor fmap, int channels, float[] camera, int ndist, Tensor p3d, Tensor fref, Tensor? valid, Tensor poses, "
+        "Tensor ranges, int pad, int loss, float loss_alpha, float loss_scale, Tensor(a!) out) -> ()"),
     "unet_forward_batch": (
         "(int ctx, Tensor[] images, Tensor?[] masks, bool[] normalize, Tensor(a!)[] outs, Tensor(b!) workspace) -> ()"),
     "ngp_render": (
@@ -264,6 +270,52 @@ def _sample_sparse(p3d, T, fmaps, channels, cameras, ndist, pad, normalize, outs
     T12 = (C.c_float * 12)(*[float(x) for x in T])
     _lib.check(L.pxt_sample_sparse(p3d.data_ptr(), n, T12, arr, n_levels, int(pad), int(bool(normalize)),
                                    valid.data_ptr(), _stream(p3d)), "pxt_sample_sparse")
+
+
+# ------------------------------------------------------------------------------ relocalisation
+def _score_pose_hypotheses(fmap, channels, camera, ndist, p3d, fref, valid, poses, ranges, pad, loss, loss_alpha, loss_scale,
+                           out):
+    L = _lib.lib()
+    _f32c(fmap, "fmap")
+    _f32c(p3d, "p3d")
+    _f32c(fref, "fref")
+    _f32c(poses, "poses")
+    _f32c(out, "out")
+    if fmap.dim() != 3 or len(camera) != 10:
+        raise _lib.PxtError("score_pose_hypotheses: fmap is [h, w, cstride], camera 10 floats")
+    h, w, cs = (int(x) for x in fmap.shape)
+    n = int(p3d.shape[0])
+    if tuple(p3d.shape) != (n, 3) or tuple(fref.shape) != (n, cs):
+        raise _lib.PxtError(f"score_pose_hypotheses: p3d {tuple(p3d.shape)} / fref {tuple(fref.shape)}, expected "
+                            f"{(n, 3)} / {(n, cs)}")
+    if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or valid.numel() != n):
+        raise _lib.PxtError("score_pose_hypotheses: valid must be contiguous uint8 [n_points]")
+    M = int(poses.shape[0]) if poses.dim() == 2 else -1
+    if M < 1 or tuple(poses.shape) != (M, 12):
+        raise _lib.PxtError(f"score_pose_hypotheses: poses is {tuple(poses.shape)}, expected [M >= 1, 12]")
+    if ranges.dtype != torch.int32 or not ranges.is_contiguous() or tuple(ranges.shape) != (M, 2):
+        raise _lib.PxtError("score_pose_hypotheses: ranges must be contiguous int32 [M, 2]")
+    if out.numel() != 4 * M:
+        raise _lib.PxtError("score_pose_hypotheses: out holds 4 floats per hypothesis")
+    # every buffer the kernel reads or writes must be device memory of the map's device (a host pointer in the kernel
+    # would be a memory fault, not an error)
+    for t, name in ((fmap, "fmap"), (p3d, "p3d"), (fref, "fref"), (valid, "valid"), (poses, "poses"), (ranges, "ranges"),
+                    (out, "out")):
+        if t is None:
+            continue
+        _lib.require_gpu(t, name)
+        if t.device != fmap.device:
+            raise _lib.PxtError(f"score_pose_hypotheses: {name} is on {t.device}, the map on {fmap.device}")
+    mp = _lib.RelocMap()
+    mp.fmap, mp.h, mp.w, mp.C, mp.cstride = fmap.data_ptr(), h, w, int(channels), cs
+    mp.cam[:] = [float(x) for x in camera]
+    mp.ndist = int(ndist)
+    bank = _lib.RelocBank()
+    bank.p3d, bank.fref, bank.valid, bank.n_points = p3d.data_ptr(), fref.data_ptr(), _lib.dptr(valid), n
+    conf = _lib.LmConf()
+    conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale = int(pad), int(loss), float(loss_alpha), float(loss_scale)
+    _lib.check(L.pxt_score_pose_hypotheses(C.byref(mp), C.byref(bank), poses.data_ptr(), ranges.data_ptr(), M, C.byref(conf),
+                                           out.data_ptr(), _stream(fmap)), "pxt_score_pose_hypotheses")
 
 
 # ---------------------------------------------------------------------------------------- UNet
@@ -500,6 +552,7 @@ _IMPLS = {
     "lm_refine": _lm_refine,
     "lm_refine_batch": _lm_refine_batch,
     "sample_sparse": _sample_sparse,
+    "score_pose_hypotheses": _score_pose_hypotheses,
     "unet_forward_batch": _unet_forward_batch,
     "conv3x3_nhwc_f16": _conv3x3,
     "ngp_render": _ngp_render,

@@ -19,6 +19,7 @@ import ast
 import os
 import pickle as pkl
 from pathlib import Path
+from typing import Optional
 
 import numpy as np
 import torch
@@ -48,10 +49,13 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
 
 class PixLocPoseTrackerR9(PoseTracker):
     def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
-                 unet_precision="fp16"):
+                 unet_precision="fp16", relocalizer=None):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
         synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
-        ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet)."""
+        ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet).
+        ``relocalizer``: None / "off" (default: the reference's behaviour - cold start from the upright view, nothing
+        relocalises), "views" (a relocalizer.Relocalizer over the mapping views) or a Relocalizer instance: the cold
+        start and the frame after a failed frame then take their pose from Relocalizer.localize."""
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
                               query_list="*_with_intrinsics.txt", global_descriptors="features.h5",
                               retrieval_pairs="pairs_query.txt", results="pixloc_object.txt")
@@ -128,6 +132,11 @@ class PixLocPoseTrackerR9(PoseTracker):
         # queued renders: consumed / camera record never arrived within the poll bound / host and device disagree on a camera
         # bit / view settings changed between enqueue and use
         self.renders_ahead_used = self.renders_ahead_dropped = self.renders_ahead_rejected = self.renders_ahead_stale = 0
+        self.relocalizer = self._make_relocalizer(relocalizer)
+        self._lost = False  # a frame failed: the next one is relocalised (relocalizer on only)
+        self._accepted_pose = None  # the last pose a frame accepted (the relocaliser scores it as one more hypothesis)
+        self.last_relocalization = None  # RelocResult of the last relocalisation
+        self._relocalized_frame = False  # this frame's pose came from the relocaliser (history key "relocalized")
 
     # ------------------------------------------------------------------ per-variant set-up
     def _initial_reference_ids(self, assets):
@@ -140,26 +149,78 @@ class PixLocPoseTrackerR9(PoseTracker):
         return assets["aabb"] if assets is not None else ast.literal_eval(os.environ["OBJ_AABB"])
 
     # ------------------------------------------------------------------ relocalisation
+    def _make_relocalizer(self, relocalizer):
+        if relocalizer is None or relocalizer == "off":
+            return None
+        if relocalizer == "views":
+            from ..relocalizer import Relocalizer
+
+            return Relocalizer(self.localizer, render=self.get_reference_image)
+        if isinstance(relocalizer, str):
+            raise ValueError(f"relocalizer must be 'off', 'views' or a Relocalizer (got {relocalizer!r})")
+        return relocalizer
+
     def relocalize(self, query):
+        if self.relocalizer is not None and not self.cold_start:
+            # called by run_single_frame after a failed frame: the NEXT frame is relocalised (_frame_setup)
+            self._lost = True
+            return
         if self.cold_start:
             self.camera = self.get_query_camera(query)
             self.cold_start = False
+        if self.relocalizer is not None and self.pose is None:
+            self._relocalize_from(query)
+            return
         if self.pose is None:
             ref_img = self.localizer.model3d.dbs[self.reference_ids[0]]
             self.pose = Pose.from_Rt(ref_img.qvec2rotmat(), ref_img.tvec)
         self.relocalization_count += 1
 
-    def start_segment(self, pose_init: Pose):
+    def _relocalize_from(self, query):
+        """The pose of this query frame from the relocaliser; the reference image becomes the db view nearest to it by
+        rotation (as start_segment picks it).  Keeps the last pose when every candidate's refinement failed."""
+        image = query[1] if isinstance(query, tuple) else query
+        if isinstance(image, (str, os.PathLike)):
+            from ..utils.io import read_image
+
+            image = read_image(image)
+        # (the last ACCEPTED pose: self.pose may be a relocalised pose whose frame then failed the gate)
+        res = self.relocalizer.localize(image, self.camera, last_pose=self._accepted_pose)
+        self.last_relocalization = res
+        self._relocalized_frame = True
+        self.relocalization_count += 1
+        self._lost = False
+        if res.pose is None:
+            if self.pose is None:  # nothing better than the reference's cold start
+                ref_img = self.localizer.model3d.dbs[self.reference_ids[0]]
+                self.pose = Pose.from_Rt(ref_img.qvec2rotmat(), ref_img.tvec)
+            return
+        self.pose = res.pose
+        if not self.keep_feature_history:
+            self.localizer.refiner.features_dicts.pop(self.dynamic_id, None)
+        self.dynamic_id, self.cache_hit = None, False
+        self.reference_ids = self._nearest_reference_ids(self.pose)
+
+    def _nearest_reference_ids(self, pose):
+        R_qry = pose.numpy()[0]
+        dbs = self.localizer.model3d.dbs
+        return sorted(dbs, key=lambda r: geodesic_distance_for_rotations(R_qry, dbs[r].qvec2rotmat()))[:1]
+
+    def start_segment(self, pose_init: Optional[Pose]):
         """Cold start of a frame SEGMENT that does not begin at the video's first frame (BASELINE configs[4]: one video cut
         into per-GPU segments).  The reference has no such entry point - its only cold start is the upright reference pose
-        of frame 0 (:95-106) - so a segment head needs a pose from outside (a relocaliser; the synthetic runs pass a
-        perturbed ground truth).  What follows is the reference's cold-start policy: image scales [4, 1], no mask, nearest
-        reference image by rotation, cost threshold frozen again from this segment's first frame."""
+        of frame 0 (:95-106) - so a segment head needs a pose from outside: ``pose_init``, or None to have the relocaliser
+        find it on the segment's first frame (needs a tracker built with ``relocalizer``).  What follows is the
+        reference's cold-start policy: image scales [4, 1], no mask, nearest reference image by rotation, cost threshold
+        frozen again from this segment's first frame."""
+        if pose_init is None and self.relocalizer is None:
+            raise ValueError("start_segment(None) needs a tracker with a relocalizer")
         self.pose, self.cold_start, self.success = pose_init, True, True
+        self._accepted_pose = pose_init
         self.cost_threshold, self.dynamic_id, self.cache_hit = None, None, False
-        R_qry = pose_init.numpy()[0]
-        dbs = self.localizer.model3d.dbs
-        self.reference_ids = sorted(dbs, key=lambda r: geodesic_distance_for_rotations(R_qry, dbs[r].qvec2rotmat()))[:1]
+        self._lost = False
+        if pose_init is not None:
+            self.reference_ids = self._nearest_reference_ids(pose_init)
 
     def get_query_camera(self, query):
         """Camera of the query stream from the frame size (EXIF-less pycolmap heuristic)."""
@@ -401,6 +462,12 @@ class PixLocPoseTrackerR9(PoseTracker):
             self.relocalize(query)
             self.cold_start = False
             kind = "cold"
+        elif self._lost:
+            # relocaliser on and the last frame failed: relocalise, then the cold-start policy from that pose (image scales
+            # [4, 1], no mask); the cost gate stays frozen
+            refiner.conf.multiscale = [4, 1]
+            self._relocalize_from(query)
+            kind = "cold"
         elif self.success:
             refiner.conf.multiscale = list(self.steady_multiscale)
             refiner.query_mask = self.get_mask(self.pose)  # multiplied inside the first conv
@@ -447,7 +514,7 @@ class PixLocPoseTrackerR9(PoseTracker):
 
         success = bool(ret["success"] and min(costs.values()) <= self.cost_threshold)
         if success:
-            self.pose = ret["T_refined"]
+            self.pose = self._accepted_pose = ret["T_refined"]
         self.success = success
         refiner.after_lm_enqueued = None
         refiner.lm_camera = None
@@ -456,6 +523,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         # decision: refiner success AND the cost gate.  bench.py and the pose gather count THIS one.)
         ret["tracked"] = success
         ret["camera"] = self.camera
+        if self.relocalizer is not None:  # (an added key only where the option is on: the default history is unchanged)
+            ret["relocalized"], self._relocalized_frame = self._relocalized_frame, False
         ret["reference_ids"] = self.reference_ids
         ret["query_path"] = query_path
         ret["cost"] = costs[best_ref_id]
@@ -494,6 +563,9 @@ def main(argv=None):
                         help="write poses.pkl/trackers.pkl with pixloc's Pose/Camera class paths")
     parser.add_argument("--unet_precision", choices=("fp16", "fp32"), default="fp16",
                         help="UNet activations: fp16 (default, fastest) or fp32 (pixloc's precision)")
+    parser.add_argument("--relocalize", choices=("off", "views"), default="off",
+                        help="off (default: cold start from the upright view, a lost track stays lost) or views "
+                             "(relocalise the cold start and the frame after a failed frame against the mapping views)")
     args = parser.parse_args(argv)
     data_path = args.object_path / "pixtrack/pixsfm/dataset"
     eval_path = args.out_dir
@@ -505,7 +577,7 @@ def main(argv=None):
         bind_to_device_numa(0)
     tracker = PixLocPoseTrackerR9(object_path=str(args.object_path), data_path=str(data_path),
                                   eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
-                                  unet_precision=args.unet_precision)
+                                  unet_precision=args.unet_precision, relocalizer=args.relocalize)
     import gc
 
     gc.collect()
