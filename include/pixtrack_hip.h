@@ -229,6 +229,58 @@ int pxt_score_pose_hypotheses(const pxt_reloc_map* map_host, const pxt_reloc_ban
                               void* stream);
 
 /* -------------------------------------------------------------------------
+ * Pose information (the LM's normal equations at a given pose, evaluated once).
+ *
+ * The reference has no counterpart: pixloc forms H = J^T W J on every iteration and drops it.  One launch evaluates, for
+ * n_problems independent (points, level, pose) problems, the sums of ONE LM iteration at the given pose - validity,
+ * bilinear taps, central-difference map gradients, w_unc = conf_query * conf_ref and the robust weight rho' are those
+ * of pxt_lm_refine (restated in csrc/pxt_lm_info.hip), parameter order as the LM's delta (translation 3, rotation 3,
+ * left update) - with NO damping, solve or update.  conf_host supplies pad, loss, loss_alpha, loss_scale and
+ * min_valid; level.lambda is ignored.
+ *
+ * pose: device-readable, 16-byte aligned.  pose_is_lm_record = 0: 12 floats.  1: an output record of pxt_lm_refine*
+ * (pose at [0..11], failed at [12], status at [13]), read ON THE DEVICE, so the launch can be queued behind the
+ * refinement with no host round trip; when failed or status is non-zero the problem is skipped: no work is done and
+ * ONLY word 47 of the record is written (-1.0).
+ *
+ * Output record (PXT_LM_INFO_RECORD = 48 floats, device or pinned host; word 47 is stored last with system-scope
+ * release, so a host may poll it in pinned memory):
+ *   [0]      sum over valid points of rho(|r|^2)        [1] n_valid
+ *   [2]      sum w |r|^2   (w = rho' * w_unc * valid)    [3] sum w
+ *   [4..9]   g = sum w J^T r
+ *   [10..30] H = sum w J^T J, upper triangle row-major, UNDAMPED
+ *   [31]     0
+ *   [32..43] the pose that was evaluated
+ *   [44..46] 0
+ *   [47]     1.0 ok; -1.0 skipped (LM record failed or timed out: nothing else was written); -2.0 evaluated with
+ *            n_valid < min_valid (the LM's own failure rule at this pose: the sums are written, but the LM would not
+ *            have used them)
+ * [0] / [1] is the masked-mean cost pxt_lm_refine logs at k = 0 of an iteration started at that pose, [1] its k = 1.
+ *
+ * Deterministic: a problem's points are dealt to a number of workgroups that depends on its n_points and C only;
+ * sums are folded in a fixed order inside a workgroup (LDS) and across a problem's workgroups (partials in the
+ * workspace, folded by a second small launch; no floating-point atomics).  A record therefore depends on its own
+ * problem only - not on n_problems, the other problems, their order, or the run.
+ * workspace: device, pxt_lm_information_workspace_bytes(n_problems); it holds the parameter records (more than two
+ * problems: copied there from pinned staging memory ahead of the launch in `stream`) and the partial sums; one
+ * workspace serves one launch at a time.
+ * ---------------------------------------------------------------------- */
+#define PXT_LM_INFO_RECORD 48
+#define PXT_LM_INFO_MAX_PROBLEMS 64
+typedef struct {
+  const float* p3d;           /* [n_points][3] */
+  const uint8_t* point_mask;  /* [n_points] or NULL */
+  int32_t n_points;
+  pxt_lm_level level;         /* query map, reference records, camera scaled to the level; lambda ignored */
+  const float* pose;          /* device-readable, 16-byte aligned: 12 floats or an LM output record */
+  int32_t pose_is_lm_record;
+  float* out;                 /* PXT_LM_INFO_RECORD floats, device or pinned host */
+} pxt_lm_info_problem;
+int64_t pxt_lm_information_workspace_bytes(int32_t n_problems);
+int pxt_lm_information(const pxt_lm_info_problem* problems_host, int32_t n_problems, const pxt_lm_conf* conf_host,
+                       void* workspace, void* stream);
+
+/* -------------------------------------------------------------------------
  * UNet feature pyramid (pixloc `UNet`, experiment pixloc_megadepth).
  *
  * Replaces `pred = self.model({"image": image_tensor})`

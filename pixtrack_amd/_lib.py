@@ -24,6 +24,8 @@ ABI_VERSION = 13
 PXT_LM_MAX_BATCH = 16
 PXT_UNET_MAX_BATCH = 16
 PXT_NGP_MAX_BATCH = 16
+PXT_LM_INFO_RECORD = 48
+PXT_LM_INFO_MAX_PROBLEMS = 64
 
 
 class PxtError(RuntimeError):
@@ -123,6 +125,11 @@ class LmProblem(C.Structure):
                 ("out", C.c_void_p), ("log", C.c_void_p), ("workspace", C.c_void_p), ("cam_host", C.POINTER(LmCamera))]
 
 
+class LmInfoProblem(C.Structure):
+    _fields_ = [("p3d", C.c_void_p), ("point_mask", C.c_void_p), ("n_points", C.c_int32), ("level", LmLevel),
+                ("pose", C.c_void_p), ("pose_is_lm_record", C.c_int32), ("out", C.c_void_p)]
+
+
 class RelocMap(C.Structure):
     _fields_ = [
         ("fmap", C.c_void_p),
@@ -158,6 +165,8 @@ PROTOTYPES = {
     "pxt_lm_workspace_bytes": (_I64, []),
     "pxt_lm_batch_workspace_bytes": (_I64, [_I32]),
     "pxt_lm_refine_batch": (C.c_int, [C.POINTER(LmProblem), _I32, C.POINTER(LmConf), _VP, _VP]),
+    "pxt_lm_information_workspace_bytes": (_I64, [_I32]),
+    "pxt_lm_information": (C.c_int, [C.POINTER(LmInfoProblem), _I32, C.POINTER(LmConf), _VP, _VP]),
     "pxt_sample_sparse": (C.c_int, [_VP, _I32, _VP, C.POINTER(SampleLevel), _I32, _I32, _I32, _VP, _VP]),
     "pxt_score_pose_hypotheses": (
         C.c_int, [C.POINTER(RelocMap), C.POINTER(RelocBank), _VP, _VP, _I32, C.POINTER(LmConf), _VP, _VP]),

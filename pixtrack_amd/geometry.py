@@ -171,6 +171,14 @@ class Pose(TensorWrapper):
         J_rot = -skew_symmetric(p3d_out)
         return torch.cat([J_t, J_rot], dim=-1)
 
+    def adjoint(self) -> torch.Tensor:
+        """The 6 x 6 adjoint of this pose for twists in the LM's parameter order (translation 3, rotation 3):
+        ``exp(xi) T == T exp(Ad(T^-1) xi)`` with the SE(3) exponential (se3_exp), ``Ad(T) = [[R, [t]x R], [0, R]]``."""
+        R, t = self.R, self.t
+        top = torch.cat([R, skew_symmetric(t) @ R], dim=-1)
+        bottom = torch.cat([torch.zeros_like(R), R], dim=-1)
+        return torch.cat([top, bottom], dim=-2)
+
     def numpy(self) -> Tuple[np.ndarray, np.ndarray]:
         a = self._data.numpy()  # one conversion (this sits on the per-frame critical path)
         return a[..., :9].reshape(a.shape[:-1] + (3, 3)), a[..., 9:]
@@ -186,6 +194,37 @@ class Pose(TensorWrapper):
     def as12(self) -> torch.Tensor:
         """The raw [..., 12] encoding handed to the C ABI."""
         return self._data
+
+
+def se3_exp(xi: torch.Tensor) -> Pose:
+    """The SE(3) exponential of a twist (translation part first, then rotation): R = exp([w]x), t = V(w) v.  (The LM's
+    own update composes so3exp(w) with the translation part taken as is - pixloc's convention; the two agree to first
+    order, which is all an information matrix speaks about.  This is the group exponential Pose.adjoint refers to.)"""
+    v, w = xi[..., :3], xi[..., 3:]
+    theta = w.norm(dim=-1, keepdim=True)[..., None]
+    Wx = skew_symmetric(w)
+    eye = torch.eye(3, dtype=xi.dtype, device=xi.device).expand(Wx.shape)
+    small = theta < 1e-6
+    th = torch.where(small, torch.ones_like(theta), theta)
+    a = torch.where(small, 1 - theta**2 / 6, torch.sin(th) / th)
+    b = torch.where(small, 0.5 - theta**2 / 24, (1 - torch.cos(th)) / th**2)
+    c = torch.where(small, 1.0 / 6 - theta**2 / 120, (th - torch.sin(th)) / th**3)
+    R = eye + a * Wx + b * (Wx @ Wx)
+    V = eye + b * Wx + c * (Wx @ Wx)
+    return Pose.from_Rt(R, (V @ v.unsqueeze(-1)).squeeze(-1))
+
+
+def to_object_frame(M, pose: Pose, covariance: bool = False):
+    """A 6 x 6 matrix over LEFT (camera-frame) perturbations of ``pose`` (exp(xi_c) T, the LM's update) re-expressed over
+    perturbations in the object's own frame (T exp(xi_o)): xi_c = Ad(T) xi_o, hence an information matrix (the default)
+    becomes Ad(T)^T M Ad(T) and a covariance (``covariance=True``) Ad(T^-1) M Ad(T^-1)^T.  float64 numpy in and out."""
+    M = np.asarray(M, np.float64)
+    P = Pose(pose.as12().detach().cpu().double().reshape(12))
+    if covariance:
+        A = P.inv().adjoint().numpy()
+        return A @ M @ A.T
+    A = P.adjoint().numpy()
+    return A.T @ M @ A
 
 
 class Camera(TensorWrapper):

@@ -344,6 +344,41 @@ class PixTrackOptimizer:
         return [PendingLM(buf, want_log, nl, conf.num_iters, (p3d, mk, list(pr["packs"]), ws), done)
                 for buf, nl, p3d, mk, pr, ws in zip(recs, n_levels, p3ds, masks, problems, wss)]
 
+    @staticmethod
+    def information_levels(items: Sequence[dict], conf: _lib.LmConf, workspace: torch.Tensor, pool_key=0) -> "PendingInfo":
+        """Enqueue ONE pxt_lm_information launch for K problems: ``items[k]`` = dict(p3d, mask (uint8 or None), pack
+        (LevelPack), pose) where ``pose`` is a Pose (12 host floats, staged in pinned memory) or a PendingLM - its pinned
+        record is then read on the device, so the launch rides behind the refinement with no host round trip.  All K
+        poses of a launch are of one kind.  Returns a handle; ``.result()`` waits for the K pinned records.
+        The records (and the staged host poses) are a ring of two per (K, pool_key): at most two launches of one
+        pool_key may be in flight - await a launch's result before enqueueing the launch after next (every caller in
+        this package awaits each launch before the next)."""
+        K = len(items)
+        assert 1 <= K <= _lib.PXT_LM_INFO_MAX_PROBLEMS
+        from_lm = isinstance(items[0]["pose"], PendingLM)
+        n_rec = _lib.PXT_LM_INFO_RECORD
+        recs = _pinned_records([n_rec] * K + ([] if from_lm else [16] * K), ("info", pool_key))
+        poses, cams, ndist = [], [], []
+        for k, it in enumerate(items):
+            recs[k][47] = 0.0
+            lp = it["pack"]
+            cams += lp.camera.as10().tolist()
+            ndist.append(int(lp.camera._data.shape[-1] - 6))
+            if from_lm:
+                poses.append(it["pose"].buf)
+            else:
+                T = it["pose"]
+                recs[K + k][:12] = (T.as12() if hasattr(T, "as12") else torch.as_tensor(T)).detach().cpu().reshape(-1).float()
+                poses.append(recs[K + k])
+        p3ds = [it["p3d"].to(torch.float32).contiguous() for it in items]
+        masks = [None if it.get("mask") is None else it["mask"].to(p3ds[0].device, torch.uint8).contiguous() for it in items]
+        ops.lm_information(p3ds, masks, [it["pack"].fmap for it in items], [it["pack"].fref for it in items],
+                           [int(it["pack"].C) for it in items], cams, ndist, poses, from_lm, conf.pad, conf.loss,
+                           conf.loss_alpha, conf.loss_scale, conf.min_valid, recs[:K], workspace)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(p3ds[0].device))
+        return PendingInfo(recs[:K], (p3ds, masks, [it["pack"] for it in items], poses, workspace), done)
+
     def run(self, p3D, F_ref, F_query, T_init: Pose, camera: Camera, mask=None, W_ref_query=None):
         """One pyramid level, pixloc calling convention:
         p3D [N,3] (numpy or tensor), F_ref [N,C], F_query [C,h,w], W_ref_query =
@@ -421,6 +456,33 @@ def _pinned_records(sizes: Sequence[int], pool_key=0) -> List[torch.Tensor]:
     bufs = ring[0][ring[1]]
     ring[1] ^= 1
     return bufs
+
+
+class PendingInfo:
+    """Result handle of an enqueued pxt_lm_information launch: ``result()`` -> one float64 numpy record (48) per problem."""
+
+    def __init__(self, recs, keepalive, done):
+        self.recs, self._keep, self._done = recs, keepalive, done
+        self._out: Optional[List[np.ndarray]] = None
+
+    def result(self) -> List[np.ndarray]:
+        if self._out is not None:  # (the K problems of a batched launch each ask once)
+            return self._out
+        out = []
+        for rec in self.recs:
+            flag = rec.numpy()
+            spins = 0
+            if not PendingLM.poll:
+                self._done.synchronize()
+            while flag[47] == 0.0:  # stored last, with system-scope release
+                spins += 1
+                if spins > 2_000_000 or (spins & 0x3FFF) == 0 and self._done.query():
+                    self._done.synchronize()
+                    break
+            out.append(flag.astype(np.float64))  # (a copy: the pinned record is reused two launches later)
+        self._keep = None
+        self._out = out
+        return out
 
 
 class PendingLM:

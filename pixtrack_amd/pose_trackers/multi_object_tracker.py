@@ -44,6 +44,7 @@ class _Group:
     def __init__(self, index, members, stream, model):
         self.index, self.members, self.stream, self.model = index, members, stream, model
         self.batch_ws: Optional[torch.Tensor] = None
+        self.info_ws: Optional[torch.Tensor] = None  # parameter records and partial sums of the step's information launch
         self.render_ws: Optional[torch.Tensor] = None  # parameter records of the batched render chain
         self.unet_done: Optional[torch.cuda.Event] = None
         self.pend = None  # what _enqueue left for _finish
@@ -51,8 +52,12 @@ class _Group:
 
 class MultiObjectTracker:
     def __init__(self, trackers: Sequence[PixLocPoseTrackerR9], lm_workgroups: int = 0, per_image_plan: bool = False,
-                 max_unet_batch: int = _lib.PXT_UNET_MAX_BATCH, n_groups: int = 1, batch_renders: Optional[bool] = None):
-        """``n_groups`` > 1: the trackers are dealt to that many groups, each with its own stream, batched UNet pass and
+                 max_unet_batch: int = _lib.PXT_UNET_MAX_BATCH, n_groups: int = 1, batch_renders: Optional[bool] = None,
+                 uncertainty: Optional[bool] = None):
+        """``uncertainty``: None keeps each tracker's own setting, True / False sets it for all of them (the ``uncertainty``
+        option of PixLocPoseTrackerR9): the information problems of a group's step then go out as ONE pxt_lm_information
+        launch behind its batched LM launch and its queued renders.
+        ``n_groups`` > 1: the trackers are dealt to that many groups, each with its own stream, batched UNet pass and
         batched LM launch per step; the groups' UNet passes take turns (an event token), so that one group's MFMA-bound
         UNet pass runs beside the other group's latency-bound renders instead of beside its UNet pass."""
         if not trackers:
@@ -73,6 +78,9 @@ class MultiObjectTracker:
         for tr in self.trackers[1:]:
             if getattr(tr.localizer.extractor.model, "weights_signature", None) != sig:
                 raise _lib.PxtError("lock-step trackers must share one UNet checkpoint and unet_precision")
+        if uncertainty is not None:
+            for tr in self.trackers:
+                tr.uncertainty = tr.localizer.refiner.information = bool(uncertainty)
         self.groups: List[_Group] = []
         # a group's queued renders as ONE chain of launches carrying the rays of all its objects (pxt_ngp_render_frame_batch;
         # bit for bit the single renders); PXT_BATCH_RENDERS=0: one chain per object, one after the other
@@ -242,6 +250,17 @@ class MultiObjectTracker:
             if handle is not None and hook is not None and k not in batched:
                 hook(handle)
         self._mark("ahead_enqueued")
+        # ---- the step's pose information (opt-in): ONE launch for every object that asked, behind the renders
+        asked = [(x, handle, tr.localizer.refiner) for (_k, tr, _p, _r, _d, status, x, handle) in grp.pend
+                 if status == "lm" and tr.localizer.refiner.information]
+        if asked:
+            if grp.info_ws is None:
+                need = int(_lib.lib().pxt_lm_information_workspace_bytes(_lib.PXT_LM_MAX_BATCH))
+                grp.info_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            info = PixTrackOptimizer.information_levels([rf.information_item(x, h) for x, h, rf in asked], asked[0][0]["conf"],
+                                                        grp.info_ws, pool_key=("group", grp.index))
+            for i, (x, _h, _rf) in enumerate(asked):
+                x["info"] = (info, i)
 
     def _batched_renders_ahead(self, grp: _Group) -> set:
         """The group's queued renders (behind the batched LM launch, cameras from its epilogue's slots) in one batched
@@ -359,6 +378,8 @@ def main(argv=None):
     ap.add_argument("--pixloc_pickles", action="store_true")
     ap.add_argument("--unet_precision", choices=("fp16", "fp32"), default="fp16",
                     help="UNet activations of every object: fp16 (default, fastest) or fp32 (pixloc's precision)")
+    ap.add_argument("--uncertainty", action="store_true",
+                    help="add the pose information matrix, covariance and observability of every frame to poses.pkl")
     args = ap.parse_args(argv)
     K = len(args.object_path)
     if len(args.query) != K or len(args.out_dir) != K:
@@ -381,7 +402,8 @@ def main(argv=None):
         os.makedirs(args.out_dir[k], exist_ok=True)
         trackers.append(PixLocPoseTrackerR9(object_path=str(obj), data_path=str(obj / "pixtrack/pixsfm/dataset"),
                                             eval_path=str(args.out_dir[k]), loc_path=str(obj / "pixtrack/aug_nerf_sfm"),
-                                            debug=args.debug, unet_precision=args.unet_precision))
+                                            debug=args.debug, unet_precision=args.unet_precision,
+                                            uncertainty=args.uncertainty))
     multi = MultiObjectTracker(trackers, n_groups=args.groups)
     its = [tr.get_query_frame_iterator(q, args.frames if args.frames is not None else np.inf)
            for tr, q in zip(trackers, args.query)]

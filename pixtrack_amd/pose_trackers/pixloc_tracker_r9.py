@@ -49,13 +49,18 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
 
 class PixLocPoseTrackerR9(PoseTracker):
     def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
-                 unet_precision="fp16", relocalizer=None):
+                 unet_precision="fp16", relocalizer=None, uncertainty=False):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
         synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
         ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet).
         ``relocalizer``: None / "off" (default: the reference's behaviour - cold start from the upright view, nothing
         relocalises), "views" (a relocalizer.Relocalizer over the mapping views) or a Relocalizer instance: the cold
-        start and the frame after a failed frame then take their pose from Relocalizer.localize."""
+        start and the frame after a failed frame then take their pose from Relocalizer.localize.
+        ``uncertainty``: False (default: nothing changes) or True - every LM launch is followed by one
+        pxt_lm_information problem at the pose it returns, and a frame's history entry gains ``pose_info`` (6 x 6),
+        ``pose_cov`` (6 x 6 or None), ``observability``, ``info_level`` and ``info_n_valid`` from the frame's last LM
+        launch (uncertainty.py); None for a frame whose refinement failed.  The cost gate, the pose update and
+        ``tracked`` never read them."""
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
                               query_list="*_with_intrinsics.txt", global_descriptors="features.h5",
                               retrieval_pairs="pairs_query.txt", results="pixloc_object.txt")
@@ -105,6 +110,8 @@ class PixLocPoseTrackerR9(PoseTracker):
             self.nerf2sfm = load_nerf2sfm(str(Path(data_path) / "nerf2sfm.pkl"))
             snapshot = str(Path(object_path) / "pixtrack/instant-ngp/snapshots/weights.msgpack")
         self.testbed = initialize_ingp(snapshot, self._render_aabb(assets), device=self.device)
+        self.uncertainty = bool(uncertainty)
+        self.localizer.refiner.information = self.uncertainty
         self.localizer.refiner.warm_reference_points()  # static per-reference tables, off the frame path
         self.dynamic_id, self.cache_hit, self.cost_threshold, self.camera = None, False, None, None
         self.hits = self.misses = self.relocalization_count = 0
@@ -563,6 +570,8 @@ def main(argv=None):
                         help="write poses.pkl/trackers.pkl with pixloc's Pose/Camera class paths")
     parser.add_argument("--unet_precision", choices=("fp16", "fp32"), default="fp16",
                         help="UNet activations: fp16 (default, fastest) or fp32 (pixloc's precision)")
+    parser.add_argument("--uncertainty", action="store_true",
+                        help="add the pose information matrix, covariance and observability of every frame to poses.pkl")
     parser.add_argument("--relocalize", choices=("off", "views"), default="off",
                         help="off (default: cold start from the upright view, a lost track stays lost) or views "
                              "(relocalise the cold start and the frame after a failed frame against the mapping views)")
@@ -577,7 +586,8 @@ def main(argv=None):
         bind_to_device_numa(0)
     tracker = PixLocPoseTrackerR9(object_path=str(args.object_path), data_path=str(data_path),
                                   eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
-                                  unet_precision=args.unet_precision, relocalizer=args.relocalize)
+                                  unet_precision=args.unet_precision, relocalizer=args.relocalize,
+                                  uncertainty=args.uncertainty)
     import gc
 
     gc.collect()

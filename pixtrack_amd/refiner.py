@@ -107,6 +107,12 @@ class PoseTrackerRefiner:
         self._p3d_host: Dict[int, np.ndarray] = {}
         self._ws = torch.zeros(int(_lib.lib().pxt_lm_workspace_bytes()), dtype=torch.uint8, device=self.device)
         self.last_lm = []  # LMResult per image scale of the last refine (costs for the tracker gate)
+        # Opt-in pose information (uncertainty.py): True queues one pxt_lm_information problem behind every LM launch -
+        # the launch's last level, at the pose the LM kernel leaves in its record - and adds INFO_KEYS to the result
+        # dictionary.  Nothing on the tracking path reads them.
+        self.information = False
+        self._info_ws: Optional[torch.Tensor] = None
+        self.last_information = None  # {"record", "p3d", "mask", "pack", "level"} of the last launch (option on only)
 
     # ---- logging hooks (pixloc BaseRefiner) -----------------------------------
     def log_dense(self, **kwargs):
@@ -261,6 +267,7 @@ class PoseTrackerRefiner:
             maps, scales = self.dense_feature_extraction(image, ref_img.name, image_scale)
             self.last_reference_wh = self.feature_extractor.last_input_wh  # (w, h) the reference pass ran at
             features[str(image_scale)] = self.interp_sparse_observations(maps, scales, dbids[0], p3dids, pose, p3d, window)
+            features[str(image_scale)].p3d_host = self._p3d_host[int(dbids[0])]  # (read by the opt-in pose information)
         return features
 
     # ---- pre-extracted reference features (reference :175-198) ---------------------------
@@ -340,10 +347,58 @@ class PoseTrackerRefiner:
                 f.create_dataset(k, data=v)
         return target
 
+    # ---- pose information (opt-in) -----------------------------------------------------
+    def _no_information(self) -> Dict:
+        """What a result that ran no (successful) refinement carries for the information keys: None with the option on,
+        nothing with it off."""
+        from .uncertainty import INFO_KEYS
+
+        return {k: None for k in INFO_KEYS} if self.information else {}
+
+    def information_item(self, prob: Dict, pending) -> Dict:
+        """The information problem of one refinement: its last level in execution order, the pose read from the LM's
+        own record on the device."""
+        ref = prob["ref"]
+        return {"p3d": ref.p3d, "mask": ref.valid, "pack": prob["packs"][-1], "pose": pending}
+
+    def enqueue_information(self, prob: Dict, pending) -> None:
+        if self._info_ws is None:
+            self._info_ws = torch.zeros(int(_lib.lib().pxt_lm_information_workspace_bytes(1)), dtype=torch.uint8,
+                                        device=self.device)
+        handle = PixTrackOptimizer.information_levels([self.information_item(prob, pending)], prob["conf"], self._info_ws,
+                                                      pool_key=id(self))
+        prob["info"] = (handle, 0)
+
+    @staticmethod
+    def _host_points(ref) -> np.ndarray:
+        """The reference's points as float64 on the host, kept on the reference-features object itself (filled from the
+        static per-reference table where one exists: extract_reference_features; else copied from the device once)."""
+        pts = ref.__dict__.get("p3d_host")
+        if pts is None:
+            pts = ref.p3d_host = ref.p3d.detach().cpu().double().numpy()
+        return pts
+
+    def _collect_information(self, prob: Dict, res) -> Dict:
+        """The information keys of one finished refinement (the record is awaited here, before the LM's pinned record
+        can be recycled: the device reads the pose out of it)."""
+        from .uncertainty import frame_entries
+
+        info = prob.pop("info", None)
+        if info is None:
+            return self._no_information()
+        handle, index = info
+        rec = handle.result()[index]
+        pack, level = prob["packs"][-1], prob["order"][-1]
+        self.last_information = {"record": rec, "p3d": prob["ref"].p3d, "mask": prob["ref"].valid, "pack": pack,
+                                 "level": level}
+        if res.failed:
+            return self._no_information()
+        return frame_entries(rec, int(pack.C), level, Pose(res.T.as12().double()), self._host_points(prob["ref"]))
+
     # ---- refinement ------------------------------------------------------------------
     def refine(self, qname: str, qcamera: Camera, pose_init: Pose, dbids: List[int], loc=None,
                image_query=None, pose: Optional[Pose] = None, reference_images=None, dynamic_id=None) -> Dict:
-        fail = {"success": False, "T_init": pose_init, "dbids": dbids}
+        fail = {"success": False, "T_init": pose_init, "dbids": dbids, **self._no_information()}
         p3dids, _ = self._points_of(dbids)
         if len(p3dids) < self.conf.min_points_opt:
             logger.debug("Not enough valid 3D points to optimize")
@@ -370,7 +425,7 @@ class PoseTrackerRefiner:
         else:
             features_dict = self.features_dicts[dynamic_id]["features"]
         self.last_lm = []
-        ret = {"success": False, "T_init": T_init}
+        ret = {"success": False, "T_init": T_init, **self._no_information()}
         for image_scale in multiscales:
             ref = features_dict[str(image_scale)]
             maps_q, scales_q = self.dense_feature_extraction(image_query, qname, image_scale, mask=self.query_mask,
@@ -400,6 +455,8 @@ class PoseTrackerRefiner:
         hook = getattr(self, "after_lm_enqueued", None)
         if hook is not None:
             hook(pending)
+        if self.information:  # (after the render-ahead chain: the next frame's render does not wait for it)
+            self.enqueue_information(prob, pending)
         return self.lm_finish(prob, pending.result())
 
     def lm_problem(self, features_query, scales_query, qcamera: Camera, T_init: Pose, ref: SparseReferenceFeatures,
@@ -438,7 +495,7 @@ class PoseTrackerRefiner:
             T_level = Pose(res.log[k, res.iters[k] - 1, 8:20].clone())
             self.log_optim(i=k, T_opt=T_level, fail=res.failed, level=level, p3d=None, p3d_ids=ref.p3dids_all,
                            T_init=T_init, camera=packs[k].camera)
-        ret = {"T_init": T_init}
+        ret = {"T_init": T_init, **self._collect_information(prob, res)}
         if res.failed:
             return {**ret, "success": False}
         T_opt = Pose(res.T.as12().double())  # already on the host (pixloc: T_opt.cpu().double())
@@ -456,7 +513,7 @@ class PoseTrackerRefiner:
         """refine() -> refine_query_pose() of ONE image scale up to, but without, the LM launch: returns
         ("done", ret) when the reference's early exits apply (too few points), else ("lm", problem) - the problem goes
         into a batched launch and comes back through finish_refine.  Same calls in the same order as refine()."""
-        fail = {"success": False, "T_init": pose_init, "dbids": dbids}
+        fail = {"success": False, "T_init": pose_init, "dbids": dbids, **self._no_information()}
         p3dids, _ = self._points_of(dbids)
         if len(p3dids) < self.conf.min_points_opt:
             logger.debug("Not enough valid 3D points to optimize")

@@ -1,0 +1,477 @@
+"""pxt_lm_information (csrc/pxt_lm_info.hip) against the float64 oracle (oracle/lm_oracle.py: residual_jacobian +
+build_system + make_loss), against the LM kernel's own log, and against itself (determinism).
+
+Cases and bars
+  SCENES below: make_lm_scene at 320x240 and 640x480, one with k1 != 0, one with a point mask; all three levels; the
+  initial pose and the LM's refined pose; the three loss kinds on the first scene; one scene (initial pose) whose
+  object overfills the image, so that 26-42 % of the points are rejected by the padded border.
+  n_valid must be EQUAL: the seeds were chosen on the CPU (`python tests/test_pose_uncertainty_gpu.py`, no GPU needed) such that the
+  float32 and the float64 oracle agree on every point's validity at the initial pose and at the oracle's refined pose
+  (no point within 1e-3 px of the padded border); the test re-checks that margin at the pose it evaluates.
+  g, H, [0], [2], [3]: relative error |d|_F / |ref|_F.  The float32 oracle against the float64 oracle on these cases
+  measured at most F32_ORACLE_WORST = 2.5e-4 (the worst of all cases and quantities; it is g at a refined pose, where g is a
+  sum of cancelling terms); the bar is 4x that (different summation order across lane groups and workgroups).
+  Degenerate line scene: lambda_min / lambda_max of the float32 oracle is LINE_F32_RATIO = 1.67e-7; the bar is 10x that.
+"""
+import ctypes as C
+import sys
+from pathlib import Path
+
+if __name__ == "__main__":  # (run as a script: the repository root is not on the path yet)
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import lm_oracle as O
+from pixtrack_amd import _lib
+from pixtrack_amd.geometry import Pose, to_object_frame
+from pixtrack_amd.ops import ops
+from pixtrack_amd.optimizer import LevelPack, PixTrackOptimizer, cstride_for
+from pixtrack_amd.synthetic import make_lm_scene
+from pixtrack_amd.uncertainty import information_from_record
+
+pytestmark = pytest.mark.gpu
+
+# measured on the CPU by this file's __main__ (float32 oracle vs float64 oracle, worst case / quantity)
+F32_ORACLE_WORST = 2.5e-4  # g, scene vga, level 0, refined pose; H alone: 1.1e-5
+BAR = 4 * F32_ORACLE_WORST
+LINE_F32_RATIO = 1.67e-7  # (the float64 oracle: 4e-16)
+LINE_BAR = 10 * LINE_F32_RATIO
+
+# name -> make_lm_scene arguments (+ "mask_seed": a point mask keeping ~85 % of the points)
+SCENES = {
+    "qvga": dict(seed=1301, width=320, height=240, n_points=2048),
+    "vga": dict(seed=1302, width=640, height=480, n_points=2341),
+    "radial": dict(seed=1303, width=320, height=240, n_points=1500, k1=-0.08, sigma_px=2.0),
+    "masked": dict(seed=1304, width=320, height=240, n_points=2048, mask_seed=4),
+    # the object overfills the image: a good part of the points projects outside the padded border at every level, so
+    # the kernel's own validity rule (and the clamped reads of the points it rejects) decides n_valid
+    "cropped": dict(seed=1305, width=320, height=240, n_points=2048, fill=1.5),
+}
+LEAVES_THE_VIEW = {"cropped": (0.4, 0.9)}  # scene -> the share of points that must be valid lies in this range
+LOSSES = {"squared": (0, 2.0, 1.0), "huber": (1, 0.0, 0.1), "barron": (2, 0.0, 0.1)}
+PAD = 1
+
+
+def build_scene(name):
+    kw = dict(SCENES[name])
+    mask_seed = kw.pop("mask_seed", None)
+    sc = make_lm_scene(**kw)
+    mask = None
+    if mask_seed is not None:
+        mask = (np.random.default_rng(mask_seed).uniform(size=sc.p3d.shape[0]) > 0.15).astype(np.uint8)
+    return sc, mask
+
+
+def pack_level(scene, level):
+    fq = scene.feats_query[level]
+    Cc = fq.shape[0] - 1
+    cs = cstride_for(Cc)
+    h, w = fq.shape[1:]
+    fmap = torch.zeros(h, w, cs)
+    fmap[..., :Cc] = O.l2_normalize(fq[:-1], dim=0).permute(1, 2, 0)
+    fmap[..., Cc] = fq[-1]
+    fr = scene.feats_ref[level]
+    fref = torch.zeros(fr.shape[0], cs)
+    fref[:, :Cc] = O.l2_normalize(fr[:, :-1], dim=1)
+    fref[:, Cc] = fr[:, -1]
+    return fmap, fref, Cc, scene.camera.scale(scene.scales[level])
+
+
+def oracle_sums(fmap, fref, Cc, cam, p3d, pose12, loss, mask, dtype, pad=PAD):
+    """The record's words from the oracle in `dtype`, plus the per-point validity and border margin."""
+    kind, alpha, scale = loss
+    name = {0: "squared", 1: "huber", 2: "barron"}[kind]
+    loss_fn = O.make_loss(name) if kind == 0 else O.make_loss(name, alpha, scale)
+    chw = fmap[..., :Cc + 1].permute(2, 0, 1).contiguous().to(dtype)
+    fr = fref.to(dtype)
+    cam_t = cam._data.to(dtype)
+    pose = torch.as_tensor(np.asarray(pose12, np.float64)).to(dtype)
+    R, t = pose[:9].reshape(3, 3), pose[9:]
+    pts = torch.as_tensor(np.asarray(p3d)).to(dtype)
+    res, valid, w_unc, J = O.residual_jacobian(R, t, cam_t, pts, fr[:, :Cc], chw[:Cc], fr[:, Cc:Cc + 1], chw[Cc:Cc + 1], pad)
+    if mask is not None:
+        valid = valid & torch.as_tensor(np.asarray(mask)).bool()
+    cost = (res ** 2).sum(-1)
+    rho, wl = loss_fn(cost)
+    v = valid.to(dtype)
+    weights = wl * v * w_unc
+    g, H = O.build_system(J, res, weights)
+    p2d, _ = O.world2image(cam_t, O.pose_transform(R, t, pts))
+    h, w = chw.shape[1:]
+    lim = torch.tensor([w - pad - 1, h - pad - 1], dtype=dtype)
+    margin = torch.minimum((p2d - pad).abs().min(-1).values, (lim - p2d).abs().min(-1).values)
+    return {"rho": float((v * rho).sum()), "n": int(valid.sum()), "wr2": float((weights * cost).sum()),
+            "w": float(weights.sum()), "g": g.double().numpy(), "H": H.double().numpy(), "valid": valid.numpy(),
+            "margin": float(margin.min())}
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+def compare(got, want):
+    """-> {quantity: relative error} of a record-like dict against the float64 oracle."""
+    return {"rho": rel(got["rho"], want["rho"]), "wr2": rel(got["wr2"], want["wr2"]), "w": rel(got["w"], want["w"]),
+            "g": rel(got["g"], want["g"]), "H": rel(got["H"], want["H"])}
+
+
+def record_dict(rec):
+    g, H = information_from_record(rec)
+    r = np.asarray(rec, np.float64)
+    return {"rho": r[0], "n": int(r[1]), "wr2": r[2], "w": r[3], "g": g, "H": H}
+
+
+def line_scene():
+    """All points on one line through a point c of the object, direction a, all in view: a rotation about the line moves
+    no point, so H has one exact null direction."""
+    sc = make_lm_scene(seed=1310, width=320, height=240, n_points=600, sigma_px=3.0)
+    rng = np.random.default_rng(7)
+    a = np.array([0.3, 0.5, 0.81])
+    a /= np.linalg.norm(a)
+    c = sc.center + np.array([0.01, -0.02, 0.015])
+    s = rng.uniform(-0.06, 0.06, size=sc.p3d.shape[0])
+    p3d = c[None] + s[:, None] * a[None]
+    return sc, p3d, a, c
+
+
+# ------------------------------------------------------------------------------------------------ device helpers
+class Dev:
+    def __init__(self, device):
+        self.device = device
+        self.ws = {}
+        self.lm_ws = torch.zeros(int(_lib.lib().pxt_lm_workspace_bytes()), dtype=torch.uint8, device=device)
+
+    def workspace(self, K):
+        K = min(K, _lib.PXT_LM_INFO_MAX_PROBLEMS)  # (the out-of-range case brings the largest workspace)
+        if K not in self.ws:
+            self.ws[K] = torch.zeros(int(_lib.lib().pxt_lm_information_workspace_bytes(K)), dtype=torch.uint8,
+                                     device=self.device)
+        return self.ws[K]
+
+
+def to_dev(device, fmap, fref, Cc, cam, p3d, mask):
+    return {"fmap": fmap.to(device).contiguous(), "fref": fref.to(device).contiguous(), "C": Cc, "cam": cam,
+            "p3d": torch.as_tensor(np.asarray(p3d)).float().to(device).contiguous(),
+            "mask": None if mask is None else torch.as_tensor(mask).to(device)}
+
+
+def information(dv, problems, poses, loss=LOSSES["barron"], records=None, is_record=False, min_valid=10, pad=PAD):
+    K = len(problems)
+    dev = dv.device
+    if records is None:
+        records = [torch.full((48,), -7.0, device=dev) for _ in range(K)]
+    cams, ndist = [], []
+    for p in problems:
+        cams += [float(x) for x in p["cam"].as10().tolist()]
+        ndist.append(int(p["cam"]._data.shape[-1] - 6))
+    pose_t = [q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q, np.float32)).to(dev) for q in poses]
+    ops.lm_information([p["p3d"] for p in problems], [p["mask"] for p in problems], [p["fmap"] for p in problems],
+                       [p["fref"] for p in problems], [p["C"] for p in problems], cams, ndist, pose_t, is_record, pad,
+                       loss[0], loss[1], loss[2], min_valid, records, dv.workspace(K))
+    return records
+
+
+@pytest.fixture(scope="module")
+def dv(device):
+    return Dev(device)
+
+
+@pytest.fixture(scope="module")
+def scenes(device, dv):
+    """Per scene: the three levels on the host and the device, the initial pose and the LM kernel's refined pose."""
+    out = {}
+    for name in SCENES:
+        sc, mask = build_scene(name)
+        levels = [pack_level(sc, l) for l in range(3)]
+        devl = [to_dev(device, *lv, sc.p3d, mask) for lv in levels]
+        init = np.concatenate([sc.R_init.reshape(-1), sc.t_init])
+        opt = PixTrackOptimizer(dict(num_iters=100, pad=PAD))
+        lam = torch.full((6,), 1e-2)
+        packs = [LevelPack(devl[l]["fmap"], devl[l]["fref"], devl[l]["C"], levels[l][3], lam) for l in (2, 1, 0)]
+        res = PixTrackOptimizer.refine_levels(devl[0]["p3d"], packs, Pose(torch.from_numpy(init).float()), opt.native_conf(),
+                                              dv.lm_ws, mask=devl[0]["mask"]).result()
+        assert not res.failed
+        out[name] = {"scene": sc, "mask": mask, "levels": levels, "dev": devl, "init": init.astype(np.float32),
+                     "refined": res.T.as12().numpy().astype(np.float32)}
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ 1. the oracle
+# (the cropped scene at its initial pose only: that pose is known on the CPU, where its seed was checked - the nearest
+# point is 2.3e-3 px from a border; where the LM's refined pose puts the border points is the device's business)
+ORACLE_POSES = {"cropped": ("init",)}
+CASES = [(s, l, p, "barron") for s in SCENES for l in (0, 1, 2) for p in ORACLE_POSES.get(s, ("init", "refined"))] + \
+        [("qvga", l, "init", k) for l in (0, 1, 2) for k in ("squared", "huber")]
+
+
+@pytest.mark.parametrize("scene,level,which,loss", CASES, ids=["-".join(map(str, c)) for c in CASES])
+def test_record_matches_the_float64_oracle(dv, scenes, scene, level, which, loss):
+    S = scenes[scene]
+    fmap, fref, Cc, cam = S["levels"][level]
+    pose = S[which]
+    rec = information(dv, [S["dev"][level]], [pose], LOSSES[loss])[0].cpu().numpy()
+    want = oracle_sums(fmap, fref, Cc, cam, S["scene"].p3d, pose, LOSSES[loss], S["mask"], torch.float64)
+    assert want["margin"] > 1e-3, f"a point sits within 1e-3 px of the border ({want['margin']}): the seed is unfair"
+    assert want["n"] > 500
+    if scene in LEAVES_THE_VIEW:
+        lo, hi = LEAVES_THE_VIEW[scene]
+        assert lo * S["scene"].p3d.shape[0] < want["n"] < hi * S["scene"].p3d.shape[0], want["n"]
+    got = record_dict(rec)
+    errs = compare(got, want)
+    print(scene, level, which, loss, "n_valid", got["n"], want["n"], {k: f"{v:.2e}" for k, v in errs.items()})
+    assert rec[47] == 1.0 and rec[31] == 0.0 and np.all(rec[44:47] == 0.0)
+    np.testing.assert_array_equal(rec[32:44].view(np.uint32), np.asarray(pose, np.float32).view(np.uint32))
+    assert got["n"] == want["n"]
+    for k, v in errs.items():
+        assert v <= BAR, (k, v, BAR)
+
+
+# ------------------------------------------------------------------------------------------------ 2. the LM's log
+G_LOG_UNDERFLOWS = {"qvga": [(2, "init"), (2, "refined")], "masked": [(2, "init"), (2, "refined")]}
+
+
+@pytest.mark.parametrize("scene", list(SCENES))
+def test_record_agrees_with_the_lm_log(dv, scenes, scene):
+    """A one-iteration refinement started at P logs k = 0 (masked-mean cost), k = 1 (n_valid) and k = 4 (|g|) AT P."""
+    S = scenes[scene]
+    opt = PixTrackOptimizer(dict(num_iters=1, pad=PAD))
+    conf = opt.native_conf()
+    loss = (conf.loss, conf.loss_alpha, conf.loss_scale)
+    lam = torch.full((6,), 1e-2)
+    exempt = []
+    for level in (0, 1, 2):
+        d = S["dev"][level]
+        for which in ("init", "refined"):
+            pose = S[which]
+            pack = LevelPack(d["fmap"], d["fref"], d["C"], d["cam"], lam)
+            res = PixTrackOptimizer.refine_levels(d["p3d"], [pack], Pose(torch.from_numpy(pose)), conf, dv.lm_ws,
+                                                  mask=d["mask"]).result()
+            k0, k1, k4 = (float(res.log[0, 0, k]) for k in (0, 1, 4))
+            rec = information(dv, [d], [pose], loss)[0].cpu().numpy().astype(np.float64)
+            gnorm = float(np.linalg.norm(rec[4:10]))
+            print(scene, level, which, rec[0] / rec[1], k0, rec[1], k1, gnorm, k4)
+            assert rec[1] == k1
+            assert rec[0] / rec[1] == pytest.approx(k0, rel=1e-6)
+            # The LM forms |g| = sqrt(sum g_i^2) in float32.  The coarsest level of these scenes carries confidences of
+            # about 1e-11 per map (weights 1e-22, |g| 1e-23): g_i^2 then lies below float32's normal range and the LOGGED
+            # norm is off by tens of per cent (3.74e-23 logged, 4.68e-23 from this record AND from the float64 oracle).
+            # The logged norm is a yardstick only where its own squares are normal numbers; g itself is held to the
+            # oracle at every level by test_record_matches_the_float64_oracle.
+            if k4 * k4 > 1e-30:
+                assert abs(gnorm - k4) <= BAR * k4
+            else:
+                exempt.append((level, which))
+    # exactly these cases are exempt, no others: the coarsest level of the two scenes whose confidence there is 1e-11
+    assert exempt == G_LOG_UNDERFLOWS.get(scene, []), exempt
+
+
+# ------------------------------------------------------------------------------------------------ 3. degenerate geometry
+def test_points_on_a_line_leave_the_rotation_about_it_unobserved(dv, device):
+    sc, p3d, a, c = line_scene()
+    level = 1
+    fmap, _fref, Cc, cam = pack_level(sc, level)
+    # reference records: the query map sampled at a slightly different pose, so that residuals are not zero
+    pose_gt = np.concatenate([sc.R_gt.reshape(-1), sc.t_gt])
+    pose = np.concatenate([sc.R_init.reshape(-1), sc.t_init]).astype(np.float32)
+    chw = fmap[..., :Cc + 1].permute(2, 0, 1).contiguous().double()
+    R, t = torch.from_numpy(sc.R_gt), torch.from_numpy(sc.t_gt)
+    p2d, vis = O.world2image(cam._data.double(), O.pose_transform(R, t, torch.from_numpy(p3d)))
+    F, inimg, _ = O.interpolator(chw, p2d, PAD)
+    assert bool((vis & inimg).all()), "all points in view"
+    fref = torch.zeros(p3d.shape[0], fmap.shape[2])
+    fref[:, :Cc + 1] = F.float()
+    d = to_dev(device, fmap, fref, Cc, cam, p3d, None)
+    rec = information(dv, [d], [pose])[0].cpu().numpy()
+    assert rec[47] == 1.0 and rec[1] == p3d.shape[0]
+    _, H = information_from_record(rec)
+    T = Pose(torch.from_numpy(pose).double())
+    Ho = to_object_frame(H, T)
+    # the expected null twist, object frame: rotation part a, translation part c x a (up to sign); checked against
+    # to_object_frame's own definition T exp(xi_o): the twist moves no point, v + w x p = 0
+    twist = np.concatenate([np.cross(c, a), a])
+    moved = twist[None, :3] + np.cross(twist[None, 3:], p3d)
+    assert np.abs(moved).max() < 1e-12
+    twist /= np.linalg.norm(twist)
+    lam, vec = np.linalg.eigh(Ho)
+    cosv = abs(float(vec[:, 0] @ twist))
+    ratio = abs(lam[0]) / lam[-1]
+    want = oracle_sums(fmap, fref, Cc, cam, p3d, pose, LOSSES["barron"], None, torch.float64)
+    lam64 = np.linalg.eigvalsh(to_object_frame(want["H"], T))
+    print("line scene: |cos|", cosv, "lambda_min / lambda_max", ratio, "float64 oracle", abs(lam64[0]) / lam64[-1])
+    assert cosv >= 0.999
+    assert ratio <= LINE_BAR
+
+
+# ------------------------------------------------------------------------------------------------ 4. determinism
+def test_bit_identical_across_launches_orders_and_streams(dv, scenes, device):
+    probs, poses = [], []
+    for i in range(24):  # 24 problems: scenes x levels x poses, all different
+        name = list(SCENES)[i % 4]
+        S = scenes[name]
+        probs.append(S["dev"][(i // 4) % 3])
+        poses.append(S["init" if (i // 12) == 0 else "refined"])
+    a = torch.stack(information(dv, probs, poses)).cpu()
+    b = torch.stack(information(dv, probs, poses)).cpu()
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert bool((a[:, 47] == 1.0).all())
+    perm = np.random.default_rng(3).permutation(24)
+    c = torch.stack(information(dv, [probs[i] for i in perm], [poses[i] for i in perm])).cpu()
+    assert torch.equal(c.view(torch.int32), a[perm].view(torch.int32))
+    for i in (0, 5, 17):
+        one = information(dv, [probs[i]], [poses[i]])[0].cpu()
+        assert torch.equal(one.view(torch.int32), a[i].view(torch.int32)), i
+    # ... and beside another stream's UNet passes, 100 launches
+    from pixtrack_amd.unet import UNet, make_synthetic_unet_weights
+
+    net = UNet(make_synthetic_unet_weights(7), device)
+    img = torch.rand(240, 320, 3, device=device) * 255
+    side = torch.cuda.Stream(device=device)
+    main = torch.cuda.current_stream(device)
+    side.wait_stream(main)
+    outs = []
+    for _ in range(100):
+        with torch.cuda.stream(side):
+            net.forward_packed(img, None, True)
+        recs = information(dv, probs, poses)
+        outs.append(torch.stack(recs))  # (a device-side copy in stream order: the workspace serves one launch at a time)
+    torch.cuda.synchronize(device)
+    bad = [i for i, o in enumerate(outs) if not torch.equal(o.cpu().view(torch.int32), a.view(torch.int32))]
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------ 5. pose from the LM record
+def test_pose_read_from_the_lm_record_on_the_device(dv, scenes, device):
+    S = scenes["qvga"]
+    d = S["dev"][0]
+    opt = PixTrackOptimizer(dict(num_iters=100, pad=PAD))
+    conf = opt.native_conf()
+    lam = torch.full((6,), 1e-2)
+    packs = [LevelPack(S["dev"][l]["fmap"], S["dev"][l]["fref"], S["dev"][l]["C"], S["dev"][l]["cam"], lam) for l in (2, 1, 0)]
+    pending = PixTrackOptimizer.refine_levels(d["p3d"], packs, Pose(torch.from_numpy(S["init"])), conf, dv.lm_ws, mask=None)
+    rec = torch.zeros(48).pin_memory()
+    information(dv, [d], [pending.buf], (conf.loss, conf.loss_alpha, conf.loss_scale), records=[rec], is_record=True)
+    res = pending.result()  # (no synchronisation between the two launches)
+    torch.cuda.synchronize(device)
+    r = rec.numpy()
+    assert r[47] == 1.0 and not res.failed
+    np.testing.assert_array_equal(r[32:44].view(np.uint32), res.T.as12().numpy().astype(np.float32).view(np.uint32))
+    again = information(dv, [d], [res.T.as12().numpy()], (conf.loss, conf.loss_alpha, conf.loss_scale))[0].cpu().numpy()
+    np.testing.assert_array_equal(again.view(np.uint32), r.view(np.uint32))
+    # a refinement that reports `failed` (a point mask keeping fewer than min_valid points): skipped, H untouched
+    few = torch.zeros(d["p3d"].shape[0], dtype=torch.uint8, device=device)
+    few[:5] = 1
+    pending = PixTrackOptimizer.refine_levels(d["p3d"], packs, Pose(torch.from_numpy(S["init"])), conf, dv.lm_ws, mask=few)
+    rec2 = torch.full((48,), 123.0).pin_memory()
+    rec2[47] = 0.0
+    information(dv, [dict(d, mask=few)], [pending.buf], (conf.loss, conf.loss_alpha, conf.loss_scale), records=[rec2],
+                is_record=True)
+    res = pending.result()
+    torch.cuda.synchronize(device)
+    assert res.failed
+    r2 = rec2.numpy()
+    assert r2[47] == -1.0
+    assert np.all(r2[:47] == 123.0)
+
+
+# ------------------------------------------------------------------------------------------------ 6. arguments
+def test_invalid_arguments_raise(dv, scenes, device):
+    S = scenes["qvga"]
+    d = S["dev"][1]
+    pose = torch.from_numpy(S["init"]).to(device)
+    with pytest.raises(_lib.PxtError):  # no problem
+        ops.lm_information([], [], [], [], [], [], [], [], False, 1, 2, 0.0, 0.1, 10, [], dv.workspace(1))
+    with pytest.raises(_lib.PxtError):  # too many problems
+        information(dv, [d] * 65, [pose] * 65, records=[torch.zeros(48, device=device) for _ in range(65)])
+    with pytest.raises(_lib.PxtError):  # a host-memory map
+        information(dv, [dict(d, fmap=d["fmap"].cpu())], [pose])
+    with pytest.raises(_lib.PxtError):  # fref / map cstride mismatch
+        information(dv, [dict(d, fmap=torch.zeros(15, 20, 136, device=device))], [pose])
+    L = _lib.lib()
+    q = (_lib.LmInfoProblem * 2)()
+    out = torch.zeros(2, 48, device=device)
+    for k in range(2):
+        q[k].p3d, q[k].point_mask, q[k].n_points = d["p3d"].data_ptr(), None, d["p3d"].shape[0]
+        h, w, cs = d["fmap"].shape
+        q[k].level.fmap, q[k].level.fref = d["fmap"].data_ptr(), d["fref"].data_ptr()
+        q[k].level.h, q[k].level.w, q[k].level.C, q[k].level.cstride = h, w, d["C"], cs
+        q[k].level.cam[:] = [float(x) for x in d["cam"].as10().tolist()]
+        q[k].level.ndist = int(d["cam"]._data.shape[-1] - 6)
+        q[k].pose, q[k].pose_is_lm_record, q[k].out = pose.data_ptr(), 0, out[k].data_ptr()
+    conf = _lib.LmConf()
+    conf.pad, conf.loss, conf.loss_scale, conf.min_valid = 1, 2, 0.1, 10
+    ws = dv.workspace(2)
+    s = _lib.stream_ptr(device)
+
+    def call(K=2, c=conf, w=ws):
+        return L.pxt_lm_information(q, K, C.byref(c) if c is not None else None, w.data_ptr() if w is not None else None, s)
+
+    assert call() == 0
+    assert call(K=0) == -1 and call(K=-2) == -1 and call(K=_lib.PXT_LM_INFO_MAX_PROBLEMS + 1) == -1
+    assert call(c=None) == -1 and call(w=None) == -1
+    keep = q[1].level.fmap
+    q[1].level.fmap = None  # a null map
+    assert call() == -1
+    q[1].level.fmap = keep
+    q[1].level.cstride = cs + 2  # misaligned cstride
+    assert call() == -1
+    q[1].level.cstride = cs
+    q[1].out = q[0].out  # two problems, one record
+    assert call() == -1
+    q[1].out = out[1].data_ptr()
+    q[1].pose = pose.data_ptr() + 4  # misaligned pose
+    assert call() == -1
+    q[1].pose = pose.data_ptr()
+    assert call() == 0
+    assert int(L.pxt_lm_information_workspace_bytes(0)) < 0 and int(L.pxt_lm_information_workspace_bytes(48)) > 0
+    torch.cuda.synchronize(device)
+
+
+# ------------------------------------------------------------------------------------------------ CPU calibration
+if __name__ == "__main__":
+    # float32 oracle vs float64 oracle on the cases above (the refined pose: the float32 oracle's own refinement), the
+    # validity agreement of the seeds, and the degenerate scene's float32 eigenvalue ratio.  No GPU.
+    worst = 0.0
+    for name in SCENES:
+        sc, mask = build_scene(name)
+        levels = [pack_level(sc, l) for l in range(3)]
+        conf = O.LMConf(num_iters=100, pad=PAD)
+        fq = [torch.cat([lv[0][..., :lv[2]], lv[0][..., lv[2]:lv[2] + 1]], -1).permute(2, 0, 1) for lv in levels]
+        fr = [lv[1][:, :lv[2] + 1] for lv in levels]
+        ret = O.refine_pose_using_features(fq, sc.scales, sc.camera._data, torch.from_numpy(sc.R_init), torch.from_numpy(sc.t_init),
+                                           fr, torch.from_numpy(sc.p3d), [torch.full((6,), 1e-2)] * 3, conf,
+                                           mask=None if mask is None else torch.from_numpy(mask).bool())
+        assert ret["success"]
+        poses = {"init": np.concatenate([sc.R_init.reshape(-1), sc.t_init]).astype(np.float32),
+                 "refined": np.concatenate([ret["R"].numpy().reshape(-1), ret["t"].numpy()]).astype(np.float32)}
+        for level in range(3):
+            fmap, fref, Cc, cam = levels[level]
+            for which, pose in poses.items():
+                if which not in ORACLE_POSES.get(name, ("init", "refined")):
+                    continue
+                for lname in (LOSSES if (name == "qvga" and which == "init") else ("barron",)):
+                    a = oracle_sums(fmap, fref, Cc, cam, sc.p3d, pose, LOSSES[lname], mask, torch.float32)
+                    b = oracle_sums(fmap, fref, Cc, cam, sc.p3d, pose, LOSSES[lname], mask, torch.float64)
+                    errs = compare(a, b)
+                    same = bool((a["valid"] == b["valid"]).all())
+                    worst = max(worst, max(errs.values()))
+                    print(f"{name:7s} L{level} {which:7s} {lname:7s} n {a['n']:5d}/{b['n']:5d} same_validity {same} "
+                          f"margin {b['margin']:.4f} " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    print("worst float32-vs-float64 relative error:", worst)
+    sc, p3d, a_, c_ = line_scene()
+    fmap, _f, Cc, cam = pack_level(sc, 1)
+    chw = fmap[..., :Cc + 1].permute(2, 0, 1).contiguous().double()
+    p2d, vis = O.world2image(cam._data.double(), O.pose_transform(torch.from_numpy(sc.R_gt), torch.from_numpy(sc.t_gt), torch.from_numpy(p3d)))
+    F, inimg, _ = O.interpolator(chw, p2d, PAD)
+    print("line scene: all in view", bool((vis & inimg).all()))
+    fref = torch.zeros(p3d.shape[0], fmap.shape[2])
+    fref[:, :Cc + 1] = F.float()
+    pose = np.concatenate([sc.R_init.reshape(-1), sc.t_init]).astype(np.float32)
+    T = Pose(torch.from_numpy(pose).double())
+    for dt in (torch.float32, torch.float64):
+        o = oracle_sums(fmap, fref, Cc, cam, p3d, pose, LOSSES["barron"], None, dt)
+        lam = np.linalg.eigvalsh(to_object_frame(o["H"], T))
+        print("line scene", dt, "lambda_min / lambda_max", abs(lam[0]) / lam[-1], "n", o["n"], "margin", o["margin"])
