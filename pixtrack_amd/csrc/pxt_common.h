@@ -100,6 +100,36 @@ __device__ inline float group_allreduce_sum(float v) {
   return v;
 }
 
+// ---- vector loads of wave-uniform data ----------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ const T* vector_pointer(const T* p) {
+  asm volatile("" : "+v"(p));  // an opaque VGPR value: the loads through it are vector loads
+  return p;
+}
+
+// A value every lane loaded alike (parameter record, pose), moved to a scalar register: what was read through a vector
+// load stays uniform for the compiler from here on (addresses, loop bounds and the camera cost no VGPRs).
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float uniform(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+template <typename T>
+__device__ __forceinline__ T* uniform(T* p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return (T*)(((unsigned long long)hi << 32) | lo);
+}
+
+// A pose (row-major R, then t; 16-byte aligned) read as three 16-byte loads.
+__device__ __forceinline__ void load_pose12(const float* pose, float* T) {
+  const float4* tp = (const float4*)pose;
+  const float4 a = tp[0], b = tp[1], d = tp[2];
+  T[0] = a.x; T[1] = a.y; T[2] = a.z; T[3] = a.w;
+  T[4] = b.x; T[5] = b.y; T[6] = b.z; T[7] = b.w;
+  T[8] = d.x; T[9] = d.y; T[10] = d.z; T[11] = d.w;
+}
+
 
 // ---- pose -> renderer camera -------------------------------------------------------------------------------
 // Pose (world -> camera, row-major R then t: the LM kernel's record) -> the NeRF renderer's camera (3x4, ngp
@@ -159,5 +189,45 @@ __device__ inline void pose_to_camera_f64(const float* pose12, const PoseConv& c
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 4; ++j) cam12[4 * i + j] = (float)m[4 * perm[i] + j];
 }
+
+// ---- host: argument checks and staging shared by the LM, information and scoring entry points ----------------
+// A level's query map and reference records as the point kernels read them (four channels per lane, dwordx4 texels,
+// the confidence at channel C): PXT_OK or PXT_E_ARG.
+inline int check_level(const float* fmap, const float* fref, int h, int w, int C, int cstride, int ndist) {
+  if (!fmap || !fref || C < 4 || (C % 4) != 0 || (cstride % 4) != 0 || cstride < C + 1 || h < 2 || w < 2) return PXT_E_ARG;
+  if (((uintptr_t)fmap % 16) != 0 || ((uintptr_t)fref % 16) != 0) return PXT_E_ARG;
+  if (ndist != 0 && ndist != 2 && ndist != 4) return PXT_E_ARG;
+  return PXT_OK;
+}
+inline int check_level(const pxt_lm_level& l) { return check_level(l.fmap, l.fref, l.h, l.w, l.C, l.cstride, l.ndist); }
+
+// Pinned staging records for parameter blocks that travel by hipMemcpyAsync, a ring of four slots (N records each) per
+// thread and device: a slot is reused only after the copy that read it has completed (its event, recorded by the caller
+// behind the copy), which by then is several launches old.  Keep one as a `static thread_local`.
+template <typename T, int N>
+struct StageRing {
+  struct Slot {
+    T* host = nullptr;
+    hipEvent_t copied = nullptr;
+  };
+  Slot slots[16][4];
+  int next[16] = {0};
+  // -> the next slot of the current device, allocated on first use, else waited for
+  int acquire(Slot** out) {
+    int dev_id = 0;
+    PXT_HIP_CHECK(hipGetDevice(&dev_id));
+    if (dev_id < 0 || dev_id >= 16) return PXT_E_ARG;
+    Slot& slot = slots[dev_id][next[dev_id]];
+    next[dev_id] = (next[dev_id] + 1) % 4;
+    if (!slot.host) {
+      PXT_HIP_CHECK(hipHostMalloc((void**)&slot.host, N * sizeof(T), hipHostMallocDefault));
+      PXT_HIP_CHECK(hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
+    } else {
+      PXT_HIP_CHECK(hipEventSynchronize(slot.copied));
+    }
+    *out = &slot;
+    return PXT_OK;
+  }
+};
 
 }  // namespace pxt

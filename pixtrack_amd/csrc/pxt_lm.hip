@@ -28,6 +28,7 @@
 //    iteration is the only inter-workgroup synchronisation (cdna_hip_programming.md
 //    G16 R2; results are bit-identical across workgroups and across runs).
 #include "pxt_common.h"
+#include "pxt_lm_point.h"
 
 #include <algorithm>
 
@@ -73,121 +74,13 @@ struct LmParams {
   float* cam_out;
 };
 
-__device__ inline void robust_loss(int kind, float alpha, float scale, float x, float& loss,
-                                   float& w) {
-  // pixloc losses.py: scaled_loss(x, fn, a) = (a^2 fn(x/a^2), fn'(x/a^2)).
-  if (kind == 0) {
-    loss = x;
-    w = 1.f;
-    return;
-  }
-  float a2 = scale * scale;
-  float y = x / a2;
-  float l, d;
-  if (kind == 1) {  // huber
-    if (y <= 1.f) {
-      l = y;
-      d = 1.f;
-    } else {
-      float sy = sqrtf(y);
-      l = 2.f * sy - 1.f;
-      d = fmaxf(1.1920929e-07f, 1.f / sy);
-    }
-  } else {  // barron(alpha)
-    if (alpha == 0.f) {
-      l = 2.f * log1pf(fminf(0.5f * y, 33e37f));
-      d = 2.f / (y + 2.f);
-    } else if (alpha == 2.f) {
-      l = y;
-      d = 1.f;
-    } else {
-      float beta = fmaxf(fabsf(alpha - 2.f), 1e-7f);
-      float as = (alpha >= 0.f ? 1.f : -1.f) * fmaxf(fabsf(alpha), 1e-7f);
-      l = 2.f * (beta / as) * (powf(y / beta + 1.f, 0.5f * alpha) - 1.f);
-      d = powf(y / beta + 1.f, 0.5f * alpha - 1.f);
-    }
-  }
-  loss = l * a2;
-  w = d;
-}
-
-// Accumulates this workgroup's share of one LM iteration at one level.
-// acc[0..5] = g, acc[6..26] = upper-triangular H (row-major), acc[27] = sum of
-// valid robust costs, acc[28] = number of valid points.
-// LG (lanes per point) is 8 or 32, wave-uniform at run time.
-// Sum over the LG lanes of a point's group, every lane receiving the total.  The first four butterfly
-// steps are DPP moves inside a 16-lane row (quad_perm xor 1 / xor 2, row_half_mirror, row_mirror: for values
-// that are already uniform over the smaller group a mirror is as good as an xor); only the 32-lane step
-// crosses rows (one ds_bpermute).  (Six sums x five dependent __shfl_xor = 3.2k cycles per point round with
-// hipcc's ds_bpermute lowering; stamps.)
-__device__ inline float lm_dpp_add(float v, int ctrl_tag) {
-  const int iv = __builtin_bit_cast(int, v);
-  int o;
-  if (ctrl_tag == 0) o = __builtin_amdgcn_update_dpp(iv, iv, 0xB1, 0xF, 0xF, false);        // quad_perm [1,0,3,2]
-  else if (ctrl_tag == 1) o = __builtin_amdgcn_update_dpp(iv, iv, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  else if (ctrl_tag == 2) o = __builtin_amdgcn_update_dpp(iv, iv, 0x141, 0xF, 0xF, false);  // row_half_mirror
-  else o = __builtin_amdgcn_update_dpp(iv, iv, 0x140, 0xF, 0xF, false);                     // row_mirror
-  return v + __builtin_bit_cast(float, o);
-}
-
-__device__ inline float lm_group_sum(float v, bool wide) {
-  v = lm_dpp_add(v, 0);
-  v = lm_dpp_add(v, 1);
-  v = lm_dpp_add(v, 2);
-  if (wide) {
-    v = lm_dpp_add(v, 3);
-    v += __shfl_xor(v, 16, PXT_WAVE);
-  }
-  return v;
-}
-
-// The same for a compile-time group width of 8, 16 or 32 lanes.
-template <int LG>
-__device__ inline float lm_group_sum_t(float v) {
-  v = lm_dpp_add(v, 0);
-  v = lm_dpp_add(v, 1);
-  v = lm_dpp_add(v, 2);
-  if (LG >= 16) v = lm_dpp_add(v, 3);
-  if (LG >= 32) v += __shfl_xor(v, 16, PXT_WAVE);
-  return v;
-}
-
-// Sum over the 16 lanes of a DPP row, every lane receiving the total (a fixed tree: the same bits in every workgroup).
-__device__ inline float lm_row16_sum(float v) {
-  v = lm_dpp_add(v, 0);
-  v = lm_dpp_add(v, 1);
-  v = lm_dpp_add(v, 2);
-  return lm_dpp_add(v, 3);
-}
-
 // One point's contribution to g (acc[0..5]), the upper triangle of H (acc[6..26]), the cost sum and the valid count,
-// from the six group-reduced scalars A = gradF^T r (2), B = gradF^T gradF (3) and its robust weight:
-// J = gradF (C x 2) * Jp (2 x 6)  =>  J^T r = Jp^T A,  J^T J = Jp^T B Jp.
+// from its six group-reduced scalars and its robust weight (pxt_lm_point.h).
 __device__ inline void lm_add_point(float* acc, float wgt, float rcost, const float* Jw, float px, float py, float pz,
                                     float A0, float A1, float B00, float B01, float B11) {
-  // Jp = d(u,v)/d(delta) = Jw (2x3) * [I | -[p]x] (3x6), translation columns first.
   float J0[6], J1[6];
-  J0[0] = Jw[0]; J0[1] = Jw[1]; J0[2] = Jw[2];
-  J1[0] = Jw[3]; J1[1] = Jw[4]; J1[2] = Jw[5];
-  // -[p]x = [[0, pz, -py], [-pz, 0, px], [py, -px, 0]]
-  J0[3] = -Jw[1] * pz + Jw[2] * py;
-  J0[4] = Jw[0] * pz - Jw[2] * px;
-  J0[5] = -Jw[0] * py + Jw[1] * px;
-  J1[3] = -Jw[4] * pz + Jw[5] * py;
-  J1[4] = Jw[3] * pz - Jw[5] * px;
-  J1[5] = -Jw[3] * py + Jw[4] * px;
-  float M0[6], M1[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    M0[k] = B00 * J0[k] + B01 * J1[k];
-    M1[k] = B01 * J0[k] + B11 * J1[k];
-    acc[k] += wgt * (J0[k] * A0 + J1[k] * A1);
-  }
-  int idx = 6;
-#pragma unroll
-  for (int k = 0; k < 6; ++k)
-#pragma unroll
-    for (int l = k; l < 6; ++l) acc[idx++] += wgt * (J0[k] * M0[l] + J1[k] * M1[l]);
+  point_jacobian(Jw, px, py, pz, J0, J1);
+  point_normal_terms<true>(acc, wgt, J0, J1, A0, A1, B00, B01, B11);
   acc[27] += rcost;
   acc[28] += 1.f;
 }
@@ -197,31 +90,17 @@ __device__ inline void lm_add_point(float* acc, float wgt, float rcost, const fl
 __device__ inline void lm_point_record(float* dst, bool leader, float wgt, float rcost, const float* Jw, float px, float py,
                                        float pz, float A0, float A1, float B00, float B01, float B11) {
   float J0[6], J1[6];
-  J0[0] = Jw[0]; J0[1] = Jw[1]; J0[2] = Jw[2];
-  J1[0] = Jw[3]; J1[1] = Jw[4]; J1[2] = Jw[5];
-  J0[3] = -Jw[1] * pz + Jw[2] * py;
-  J0[4] = Jw[0] * pz - Jw[2] * px;
-  J0[5] = -Jw[0] * py + Jw[1] * px;
-  J1[3] = -Jw[4] * pz + Jw[5] * py;
-  J1[4] = Jw[3] * pz - Jw[5] * px;
-  J1[5] = -Jw[3] * py + Jw[4] * px;
+  point_jacobian(Jw, px, py, pz, J0, J1);
   if (!leader) return;
-  float M0[6], M1[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    M0[k] = B00 * J0[k] + B01 * J1[k];
-    M1[k] = B01 * J0[k] + B11 * J1[k];
-    dst[k] = 0.f + wgt * (J0[k] * A0 + J1[k] * A1);
-  }
-  int idx = 6;
-#pragma unroll
-  for (int k = 0; k < 6; ++k)
-#pragma unroll
-    for (int l = k; l < 6; ++l) dst[idx++] = 0.f + wgt * (J0[k] * M0[l] + J1[k] * M1[l]);
+  point_normal_terms<false>(dst, wgt, J0, J1, A0, A1, B00, B01, B11);
   dst[27] = rcost;
   dst[28] = 1.f;
 }
 
+// Accumulates this workgroup's share of one LM iteration at one level.
+// acc[0..5] = g, acc[6..26] = upper-triangular H (row-major), acc[27] = sum of
+// valid robust costs, acc[28] = number of valid points.
+// LG (lanes per point) is 8 or 32, wave-uniform at run time.
 __device__ inline void lm_accumulate(const LmParams& P, const LmGrid grid, const LmLevelDev& L, const float* T,
                                      float* acc, const int LG, unsigned long long* dbg = nullptr) {
   const bool wide = LG == 32;
@@ -251,20 +130,14 @@ __device__ inline void lm_accumulate(const LmParams& P, const LmGrid grid, const
 #if PXT_EXP_STAMPS
     if (dbg && dbg_round == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); dbg[8] = __builtin_amdgcn_s_memtime(); }
 #endif
-    const float px = T[0] * X + T[1] * Y + T[2] * Z + T[9];
-    const float py = T[3] * X + T[4] * Y + T[5] * Z + T[10];
-    const float pz = T[6] * X + T[7] * Y + T[8] * Z + T[11];
-    float u, v, Jw[6];
-    valid = project_point(cam, px, py, pz, u, v, Jw) && valid;
-    valid = valid && (u >= pad) && (v >= pad) && (u <= (float)(W - 1) - pad) &&
-            (v <= (float)(H - 1) - pad);
+    float px, py, pz, u, v, Jw[6];
+    transform_point(T, X, Y, Z, px, py, pz);
+    point_in_window(cam, px, py, pz, valid, W, H, pad, u, v, Jw);
     if (!valid) continue;  // group-uniform: contributes nothing (weight 0, not counted)
 
-    const float fu = floorf(u), fv = floorf(v);
-    const int ix0 = (int)fu, iy0 = (int)fv;
-    const float ax = u - fu, ay = v - fv;
-    const float w00 = (1.f - ax) * (1.f - ay), w10 = ax * (1.f - ay), w01 = (1.f - ax) * ay,
-                w11 = ax * ay;
+    int ix0, iy0;
+    float w00, w10, w01, w11;
+    bilinear_weights(u, v, ix0, iy0, w00, w10, w01, w11);
     // Column / row indices of the 4x4 neighbourhood, clamped for addressing; texels
     // outside the map count as zero (grid_sample padding_mode='zeros').
     int xi[4], yi[4];
@@ -304,25 +177,10 @@ __device__ inline void lm_accumulate(const LmParams& P, const LmGrid grid, const
       const float m20 = ym[2] * xm[0], m21 = ym[2] * xm[1], m22 = ym[2] * xm[2],
                   m23 = ym[2] * xm[3];
       const float m31 = ym[3] * xm[1], m32 = ym[3] * xm[2];
-#define PXT_LM_CH(q)                                                                          \
-  {                                                                                           \
-    const float a01 = t01.q * m01, a02 = t02.q * m02, a10 = t10.q * m10, a11 = t11.q * m11,   \
-                a12 = t12.q * m12, a13 = t13.q * m13, a20 = t20.q * m20, a21 = t21.q * m21,   \
-                a22 = t22.q * m22, a23 = t23.q * m23, a31 = t31.q * m31, a32 = t32.q * m32;   \
-    const float F = w00 * a11 + w10 * a12 + w01 * a21 + w11 * a22;                            \
-    const float Fxp = w00 * a12 + w10 * a13 + w01 * a22 + w11 * a23;                          \
-    const float Fxm = w00 * a10 + w10 * a11 + w01 * a20 + w11 * a21;                          \
-    const float Fyp = w00 * a21 + w10 * a22 + w01 * a31 + w11 * a32;                          \
-    const float Fym = w00 * a01 + w10 * a02 + w01 * a11 + w11 * a12;                          \
-    const float gx = 0.5f * (Fxp - Fxm), gy = 0.5f * (Fyp - Fym);                             \
-    const float r = F - fr.q;                                                                 \
-    s_cost += r * r;                                                                          \
-    A0 += r * gx;                                                                             \
-    A1 += r * gy;                                                                             \
-    B00 += gx * gx;                                                                           \
-    B01 += gx * gy;                                                                           \
-    B11 += gy * gy;                                                                           \
-  }
+#define PXT_LM_CH(q)                                                                                              \
+  PXT_LM_POINT_CH(w00, w10, w01, w11, t01.q * m01, t02.q * m02, t10.q * m10, t11.q * m11, t12.q * m12, t13.q * m13, \
+                  t20.q * m20, t21.q * m21, t22.q * m22, t23.q * m23, t31.q * m31, t32.q * m32, fr.q, s_cost, A0,   \
+                  A1, B00, B01, B11)
       PXT_LM_CH(x) PXT_LM_CH(y) PXT_LM_CH(z) PXT_LM_CH(w)
 #undef PXT_LM_CH
     }
@@ -417,17 +275,14 @@ __device__ inline void lm_accumulate_cached(const LmParams& P, const LmLevelDev&
 #if PXT_EXP_STAMPS
   if (dbg) dbg[8] = __builtin_amdgcn_s_memtime();
 #endif
-  const float px = T[0] * pt.X + T[1] * pt.Y + T[2] * pt.Z + T[9];
-  const float py = T[3] * pt.X + T[4] * pt.Y + T[5] * pt.Z + T[10];
-  const float pz = T[6] * pt.X + T[7] * pt.Y + T[8] * pt.Z + T[11];
-  float u, v, Jw[6];
-  bool valid = project_point(cam, px, py, pz, u, v, Jw) && pt.valid;
-  valid = valid && (u >= pad) && (v >= pad) && (u <= (float)(W - 1) - pad) && (v <= (float)(H - 1) - pad);
+  float px, py, pz, u, v, Jw[6];
+  transform_point(T, pt.X, pt.Y, pt.Z, px, py, pz);
+  bool valid = pt.valid;
+  point_in_window(cam, px, py, pz, valid, W, H, pad, u, v, Jw);
   if (valid) {  // group-uniform
-    const float fu = floorf(u), fv = floorf(v);
-    const int ix0 = (int)fu, iy0 = (int)fv;
-    const float ax = u - fu, ay = v - fv;
-    const float w00 = (1.f - ax) * (1.f - ay), w10 = ax * (1.f - ay), w01 = (1.f - ax) * ay, w11 = ax * ay;
+    int ix0, iy0;
+    float w00, w10, w01, w11;
+    bilinear_weights(u, v, ix0, iy0, w00, w10, w01, w11);
     int xi[4], yi[4];
     float xm[4], ym[4];
 #pragma unroll
@@ -477,24 +332,9 @@ __device__ inline void lm_accumulate_cached(const LmParams& P, const LmLevelDev&
     for (int k = 0; k < CB; ++k) {
       const float4 fr = CI <= 2 ? pt.fr[CI <= 2 ? k : 0] : frl[k];
 #define PXT_LM_CH(q)                                                                                              \
-  {                                                                                                               \
-    const float a01 = t[k][0].q * m01, a02 = t[k][1].q * m02, a10 = t[k][2].q * m10, a11 = t[k][3].q * m11,        \
-                a12 = t[k][4].q * m12, a13 = t[k][5].q * m13, a20 = t[k][6].q * m20, a21 = t[k][7].q * m21,        \
-                a22 = t[k][8].q * m22, a23 = t[k][9].q * m23, a31 = t[k][10].q * m31, a32 = t[k][11].q * m32;      \
-    const float F = w00 * a11 + w10 * a12 + w01 * a21 + w11 * a22;                                                \
-    const float Fxp = w00 * a12 + w10 * a13 + w01 * a22 + w11 * a23;                                              \
-    const float Fxm = w00 * a10 + w10 * a11 + w01 * a20 + w11 * a21;                                              \
-    const float Fyp = w00 * a21 + w10 * a22 + w01 * a31 + w11 * a32;                                              \
-    const float Fym = w00 * a01 + w10 * a02 + w01 * a11 + w11 * a12;                                              \
-    const float gx = 0.5f * (Fxp - Fxm), gy = 0.5f * (Fyp - Fym);                                                 \
-    const float r = F - fr.q;                                                                                     \
-    s_cost += r * r;                                                                                              \
-    A0 += r * gx;                                                                                                 \
-    A1 += r * gy;                                                                                                 \
-    B00 += gx * gx;                                                                                               \
-    B01 += gx * gy;                                                                                               \
-    B11 += gy * gy;                                                                                               \
-  }
+  PXT_LM_POINT_CH(w00, w10, w01, w11, t[k][0].q * m01, t[k][1].q * m02, t[k][2].q * m10, t[k][3].q * m11,           \
+                  t[k][4].q * m12, t[k][5].q * m13, t[k][6].q * m20, t[k][7].q * m21, t[k][8].q * m22,              \
+                  t[k][9].q * m23, t[k][10].q * m31, t[k][11].q * m32, fr.q, s_cost, A0, A1, B00, B01, B11)
       PXT_LM_CH(x) PXT_LM_CH(y) PXT_LM_CH(z) PXT_LM_CH(w)
 #undef PXT_LM_CH
     }
@@ -991,9 +831,8 @@ __device__ inline bool sample_level(const SampleParams& P, const SampleLevelDev&
   const int FW = L.fw, FH = L.fh;  // the full level (projection, visibility, padded in-image test)
   const float pad = (float)P.pad;
   float u = 0.f, v = 0.f;
-  bool valid = project_point(cam, px, py, pz, u, v, nullptr) && active;
-  valid = valid && (u >= pad) && (v >= pad) && (u <= (float)(FW - 1) - pad) &&
-          (v <= (float)(FH - 1) - pad);
+  bool valid = active;
+  point_in_window(cam, px, py, pz, valid, FW, FH, pad, u, v, nullptr);
   if (!active) return false;
   float* o = L.out + (size_t)n * cs;
   if (!valid) {
@@ -1058,10 +897,8 @@ __global__ __launch_bounds__(256) void sample_sparse_kernel(const SampleParams P
     Y = P.p3d[3 * n + 1];
     Z = P.p3d[3 * n + 2];
   }
-  const float* T = P.T;
-  const float px = T[0] * X + T[1] * Y + T[2] * Z + T[9];
-  const float py = T[3] * X + T[4] * Y + T[5] * Z + T[10];
-  const float pz = T[6] * X + T[7] * Y + T[8] * Z + T[11];
+  float px, py, pz;
+  transform_point(P.T, X, Y, Z, px, py, pz);
   bool all_valid = active;
   for (int l = 0; l < P.n_levels; ++l)
     all_valid = sample_level<LG>(P, P.lv[l], n, active, px, py, pz, sub) && all_valid;
@@ -1101,11 +938,7 @@ int lm_fill_params(LmParams& P, const float* p3d, const uint8_t* point_mask, int
   P.n_levels = n_levels;
   for (int l = 0; l < n_levels; ++l) {
     const pxt_lm_level& s = levels[l];
-    if (!s.fmap || !s.fref || s.C < 4 || (s.C % 4) != 0 || (s.cstride % 4) != 0 ||
-        s.cstride < s.C + 1 || s.h < 2 || s.w < 2)
-      return PXT_E_ARG;
-    if (((uintptr_t)s.fmap % 16) != 0 || ((uintptr_t)s.fref % 16) != 0) return PXT_E_ARG;
-    if (s.ndist != 0 && s.ndist != 2 && s.ndist != 4) return PXT_E_ARG;
+    if (const int rc = check_level(s)) return rc;
     LmLevelDev& d = P.lv[l];
     d.fmap = s.fmap;
     d.fref = s.fref;
@@ -1155,14 +988,6 @@ int lm_resident_cap(int* cap, bool whole_device = false) {
   return PXT_OK;
 }
 
-// Pinned staging records of the batched entry, a ring of four per thread and device: a slot is reused only after the
-// copy that read it has completed (its event), which by then is several launches old.
-struct LmStageSlot {
-  LmParams* host = nullptr;
-  hipEvent_t copied = nullptr;
-};
-constexpr int kLmStageSlots = 4;
-
 }  // namespace
 
 extern "C" int pxt_lm_refine_cam(const float* p3d, const uint8_t* point_mask, int32_t n_points,
@@ -1199,19 +1024,11 @@ extern "C" int pxt_lm_refine_batch(const pxt_lm_problem* problems, int32_t n_pro
   for (int a = 0; a < K; ++a)  // every problem spins on ITS OWN granules: two problems on one workspace would read each other's
     for (int b = a + 1; b < K; ++b)
       if (problems[a].workspace == problems[b].workspace || problems[a].out == problems[b].out) return PXT_E_ARG;
-  static thread_local LmStageSlot stage[16][kLmStageSlots];
-  static thread_local int stage_next[16] = {0};
-  int dev_id = 0;
-  PXT_HIP_CHECK(hipGetDevice(&dev_id));
-  if (dev_id < 0 || dev_id >= 16) return PXT_E_ARG;
-  LmStageSlot& slot = stage[dev_id][stage_next[dev_id]];
-  stage_next[dev_id] = (stage_next[dev_id] + 1) % kLmStageSlots;
-  if (!slot.host) {
-    PXT_HIP_CHECK(hipHostMalloc((void**)&slot.host, PXT_LM_MAX_BATCH * sizeof(LmParams), hipHostMallocDefault));
-    PXT_HIP_CHECK(hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
-  } else {
-    PXT_HIP_CHECK(hipEventSynchronize(slot.copied));
-  }
+  using Stage = StageRing<LmParams, PXT_LM_MAX_BATCH>;
+  static thread_local Stage stage;
+  Stage::Slot* slot_p = nullptr;
+  if (const int rc = stage.acquire(&slot_p)) return rc;
+  Stage::Slot& slot = *slot_p;
   for (int k = 0; k < K; ++k) {
     const pxt_lm_problem& q = problems[k];
     const int rc = lm_fill_params(slot.host[k], q.p3d, q.point_mask, q.n_points, q.levels_host, q.n_levels, q.T_init_host, conf,

@@ -4,8 +4,8 @@
 // the given pose - sum rho, n_valid, sum w |r|^2, sum w, g = sum w J^T r and the upper triangle of the UNDAMPED
 // H = sum w J^T J - and a second small launch folds them into a 48-float record.  Validity, projection, the 12-texel
 // cross footprint of the five bilinear taps, the central-difference map gradients, w_unc = conf_query * conf_ref and
-// rho / rho' are those of lm_accumulate (pxt_lm.hip), restated here (that file holds 256 VGPRs, is pinned by its tests
-// and stays untouched); the parameter order is the LM's delta (translation 3, rotation 3, left update).
+// rho / rho' are the LM's own (pxt_lm_point.h, which lm_accumulate is written in as well); the parameter order is the
+// LM's delta (translation 3, rotation 3, left update).
 //
 // Mapping
 //  * A point is owned by a lane GROUP as in the LM (4 consecutive channels per lane, dwordx4 texel reads: 32 lanes per
@@ -22,6 +22,7 @@
 //    pose and the LM record's status words are read through vector loads (pointers made opaque VGPR values, as
 //    pxt_reloc.hip does): the pose may have been written by the kernel just ahead in the stream.
 #include "pxt_common.h"
+#include "pxt_lm_point.h"
 
 #include <algorithm>
 
@@ -59,116 +60,17 @@ struct InfoConf {
   float loss_alpha, loss_scale;
 };
 
-template <typename T>
-__device__ __forceinline__ const T* vector_pointer(const T* p) {
-  asm volatile("" : "+v"(p));  // an opaque VGPR value: the loads through it are vector loads
-  return p;
-}
-
-// A value every lane loaded alike (parameter record, pose), moved to a scalar register: what was read through a vector
-// load stays uniform for the compiler from here on (addresses, loop bounds and the camera cost no VGPRs).
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ float uniform(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-template <typename T>
-__device__ __forceinline__ T* uniform(T* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return (T*)(((unsigned long long)hi << 32) | lo);
-}
-
-// pixloc scaled_loss(x, fn, a) = (a^2 fn(x / a^2), fn'(x / a^2)): the LM's robust_loss (pxt_lm.hip).
-__device__ inline void info_robust_loss(int kind, float alpha, float scale, float x, float& loss, float& w) {
-  if (kind == 0) {
-    loss = x;
-    w = 1.f;
-    return;
-  }
-  const float a2 = scale * scale;
-  const float y = x / a2;
-  float l, d;
-  if (kind == 1) {  // huber
-    if (y <= 1.f) {
-      l = y;
-      d = 1.f;
-    } else {
-      const float sy = sqrtf(y);
-      l = 2.f * sy - 1.f;
-      d = fmaxf(1.1920929e-07f, 1.f / sy);
-    }
-  } else {  // barron(alpha)
-    if (alpha == 0.f) {
-      l = 2.f * log1pf(fminf(0.5f * y, 33e37f));
-      d = 2.f / (y + 2.f);
-    } else if (alpha == 2.f) {
-      l = y;
-      d = 1.f;
-    } else {
-      const float beta = fmaxf(fabsf(alpha - 2.f), 1e-7f);
-      const float as = (alpha >= 0.f ? 1.f : -1.f) * fmaxf(fabsf(alpha), 1e-7f);
-      l = 2.f * (beta / as) * (powf(y / beta + 1.f, 0.5f * alpha) - 1.f);
-      d = powf(y / beta + 1.f, 0.5f * alpha - 1.f);
-    }
-  }
-  loss = l * a2;
-  w = d;
-}
-
-// Sum over a point's lane group, every lane receiving the total: the LM's fixed butterfly (DPP inside a 16-lane row,
-// one cross-row step for 32 lanes), so a point's six scalars are formed in the LM's order.
-__device__ inline float info_dpp_add(float v, int ctrl_tag) {
-  const int iv = __builtin_bit_cast(int, v);
-  int o;
-  if (ctrl_tag == 0) o = __builtin_amdgcn_update_dpp(iv, iv, 0xB1, 0xF, 0xF, false);        // quad_perm [1,0,3,2]
-  else if (ctrl_tag == 1) o = __builtin_amdgcn_update_dpp(iv, iv, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  else if (ctrl_tag == 2) o = __builtin_amdgcn_update_dpp(iv, iv, 0x141, 0xF, 0xF, false);  // row_half_mirror
-  else o = __builtin_amdgcn_update_dpp(iv, iv, 0x140, 0xF, 0xF, false);                     // row_mirror
-  return v + __builtin_bit_cast(float, o);
-}
-
-__device__ inline float info_group_sum(float v, bool wide) {
-  v = info_dpp_add(v, 0);
-  v = info_dpp_add(v, 1);
-  v = info_dpp_add(v, 2);
-  if (wide) {
-    v = info_dpp_add(v, 3);
-    v += __shfl_xor(v, 16, PXT_WAVE);
-  }
-  return v;
-}
-
 // One point's terms added to the group's sums, in the record's order: acc[0] sum rho, [1] n_valid, [2] sum w |r|^2,
-// [3] sum w, [4..9] g, [10..30] upper H.  J = gradF (C x 2) * Jp (2 x 6)  =>  J^T r = Jp^T A,  J^T J = Jp^T B Jp.
+// [3] sum w, [4..9] g, [10..30] upper H.
 __device__ inline void info_add_point(float* acc, float wgt, float rcost, float r2, const float* Jw, float px, float py,
                                       float pz, float A0, float A1, float B00, float B01, float B11) {
-  // Jp = d(u,v)/d(delta) = Jw (2x3) * [I | -[p]x] (3x6), translation columns first.
   float J0[6], J1[6];
-  J0[0] = Jw[0]; J0[1] = Jw[1]; J0[2] = Jw[2];
-  J1[0] = Jw[3]; J1[1] = Jw[4]; J1[2] = Jw[5];
-  J0[3] = -Jw[1] * pz + Jw[2] * py;
-  J0[4] = Jw[0] * pz - Jw[2] * px;
-  J0[5] = -Jw[0] * py + Jw[1] * px;
-  J1[3] = -Jw[4] * pz + Jw[5] * py;
-  J1[4] = Jw[3] * pz - Jw[5] * px;
-  J1[5] = -Jw[3] * py + Jw[4] * px;
+  point_jacobian(Jw, px, py, pz, J0, J1);
   acc[0] += rcost;
   acc[1] += 1.f;
   acc[2] += wgt * r2;
   acc[3] += wgt;
-  float M0[6], M1[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    M0[k] = B00 * J0[k] + B01 * J1[k];
-    M1[k] = B01 * J0[k] + B11 * J1[k];
-    acc[4 + k] += wgt * (J0[k] * A0 + J1[k] * A1);
-  }
-  int idx = 10;
-#pragma unroll
-  for (int k = 0; k < 6; ++k)
-#pragma unroll
-    for (int l = k; l < 6; ++l) acc[idx++] += wgt * (J0[k] * M0[l] + J1[k] * M1[l]);
+  point_normal_terms<true>(acc + 4, wgt, J0, J1, A0, A1, B00, B01, B11);
 }
 
 // What a point needs between its projection and its arithmetic.
@@ -202,15 +104,12 @@ __device__ inline const InfoParams* info_params(const InfoParams* ws_params, int
 
 // -> false when the problem is skipped (its LM record reports failed / a status).
 __device__ inline bool info_load_pose(const InfoParams* q, float* T) {
-  const float4* tp = (const float4*)vector_pointer(q->pose);
-  const float4 a = tp[0], b = tp[1], d = tp[2];
-  T[0] = a.x; T[1] = a.y; T[2] = a.z; T[3] = a.w;
-  T[4] = b.x; T[5] = b.y; T[6] = b.z; T[7] = b.w;
-  T[8] = d.x; T[9] = d.y; T[10] = d.z; T[11] = d.w;
+  const float* pose = vector_pointer(q->pose);
+  load_pose12(pose, T);
 #pragma unroll
   for (int i = 0; i < 12; ++i) T[i] = uniform(T[i]);
   if (uniform(q->pose_is_record)) {
-    const float4 st = tp[3];  // failed, status, total iterations, completion word
+    const float4 st = ((const float4*)pose)[3];  // failed, status, total iterations, completion word
     if (uniform(st.x) != 0.f || uniform(st.y) != 0.f) return false;
   }
   return true;
@@ -266,18 +165,13 @@ __global__ __launch_bounds__(kInfoBlock) void lm_info_accumulate_kernel(const In
       const float X = info_word(p3d, 12u * (unsigned)p.n), Y = info_word(p3d, 12u * (unsigned)p.n + 4u),
                   Z = info_word(p3d, 12u * (unsigned)p.n + 8u);
       if (mask) valid = valid && *((const __attribute__((address_space(1))) uint8_t*)mask + (unsigned)p.n) != 0;
-      p.px = T[0] * X + T[1] * Y + T[2] * Z + T[9];
-      p.py = T[3] * X + T[4] * Y + T[5] * Z + T[10];
-      p.pz = T[6] * X + T[7] * Y + T[8] * Z + T[11];
+      transform_point(T, X, Y, Z, p.px, p.py, p.pz);
       float u, v;
-      valid = project_point(cam, p.px, p.py, p.pz, u, v, p.Jw) && valid;
-      valid = valid && (u >= pad) && (v >= pad) && (u <= (float)(W - 1) - pad) && (v <= (float)(H - 1) - pad);
+      point_in_window(cam, p.px, p.py, p.pz, valid, W, H, pad, u, v, p.Jw);
       if (!valid) u = v = 0.f;  // (u, v may be anything, NaN included: keep the address arithmetic defined)
       p.valid = valid;
-      const float fu = floorf(u), fv = floorf(v);
-      const int ix0 = (int)fu, iy0 = (int)fv;
-      const float ax = u - fu, ay = v - fv;
-      p.w00 = (1.f - ax) * (1.f - ay); p.w10 = ax * (1.f - ay); p.w01 = (1.f - ax) * ay; p.w11 = ax * ay;
+      int ix0, iy0;
+      bilinear_weights(u, v, ix0, iy0, p.w00, p.w10, p.w01, p.w11);
       p.xin = p.yin = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -322,25 +216,11 @@ __global__ __launch_bounds__(kInfoBlock) void lm_info_accumulate_kernel(const In
         const float m10 = p.in(1, 0), m11 = p.in(1, 1), m12 = p.in(1, 2), m13 = p.in(1, 3);
         const float m20 = p.in(2, 0), m21 = p.in(2, 1), m22 = p.in(2, 2), m23 = p.in(2, 3);
         const float m31 = p.in(3, 1), m32 = p.in(3, 2);
-#define PXT_INFO_CH(q_)                                                                                       \
-  {                                                                                                           \
-    const float a01 = t01[j].q_ * m01, a02 = t02[j].q_ * m02, a10 = t10[j].q_ * m10, a11 = t11[j].q_ * m11,   \
-                a12 = t12[j].q_ * m12, a13 = t13[j].q_ * m13, a20 = t20[j].q_ * m20, a21 = t21[j].q_ * m21,   \
-                a22 = t22[j].q_ * m22, a23 = t23[j].q_ * m23, a31 = t31[j].q_ * m31, a32 = t32[j].q_ * m32;   \
-    const float F = w00 * a11 + w10 * a12 + w01 * a21 + w11 * a22;                                            \
-    const float Fxp = w00 * a12 + w10 * a13 + w01 * a22 + w11 * a23;                                          \
-    const float Fxm = w00 * a10 + w10 * a11 + w01 * a20 + w11 * a21;                                          \
-    const float Fyp = w00 * a21 + w10 * a22 + w01 * a31 + w11 * a32;                                          \
-    const float Fym = w00 * a01 + w10 * a02 + w01 * a11 + w11 * a12;                                          \
-    const float gx = 0.5f * (Fxp - Fxm), gy = 0.5f * (Fyp - Fym);                                             \
-    const float r = F - fr[j].q_;                                                                             \
-    s_cost[j] += r * r;                                                                                       \
-    A0[j] += r * gx;                                                                                          \
-    A1[j] += r * gy;                                                                                          \
-    B00[j] += gx * gx;                                                                                        \
-    B01[j] += gx * gy;                                                                                        \
-    B11[j] += gy * gy;                                                                                        \
-  }
+#define PXT_INFO_CH(q_)                                                                                          \
+  PXT_LM_POINT_CH(w00, w10, w01, w11, t01[j].q_ * m01, t02[j].q_ * m02, t10[j].q_ * m10, t11[j].q_ * m11,          \
+                  t12[j].q_ * m12, t13[j].q_ * m13, t20[j].q_ * m20, t21[j].q_ * m21, t22[j].q_ * m22,             \
+                  t23[j].q_ * m23, t31[j].q_ * m31, t32[j].q_ * m32, fr[j].q_, s_cost[j], A0[j], A1[j], B00[j],    \
+                  B01[j], B11[j])
         PXT_INFO_CH(x) PXT_INFO_CH(y) PXT_INFO_CH(z) PXT_INFO_CH(w)
 #undef PXT_INFO_CH
       }
@@ -356,12 +236,12 @@ __global__ __launch_bounds__(kInfoBlock) void lm_info_accumulate_kernel(const In
       const float q22 = info_word(fmap, p.yo[2] + p.xo[2] + cb) * p.in(2, 2);
       const float wq = p.w00 * q11 + p.w10 * q12 + p.w01 * q21 + p.w11 * q22;
       const float wref = info_word(fref, 4u * (unsigned)(p.n * cs) + cb);
-      const float sc = info_group_sum(s_cost[j], wide);
-      const float a0 = info_group_sum(A0[j], wide), a1 = info_group_sum(A1[j], wide);
-      const float b00 = info_group_sum(B00[j], wide), b01 = info_group_sum(B01[j], wide),
-                  b11 = info_group_sum(B11[j], wide);
+      const float sc = lm_group_sum(s_cost[j], wide);
+      const float a0 = lm_group_sum(A0[j], wide), a1 = lm_group_sum(A1[j], wide);
+      const float b00 = lm_group_sum(B00[j], wide), b01 = lm_group_sum(B01[j], wide),
+                  b11 = lm_group_sum(B11[j], wide);
       float rcost, wl;
-      info_robust_loss(cf.loss, cf.loss_alpha, cf.loss_scale, sc, rcost, wl);
+      robust_loss(cf.loss, cf.loss_alpha, cf.loss_scale, sc, rcost, wl);
       const float wgt = wl * (wref * wq);
       if (p.valid)  // group-uniform: an invalid point contributes nothing (weight 0, not counted)
         info_add_point(acc, wgt, rcost, sc, p.Jw, p.px, p.py, p.pz, a0, a1, b00, b01, b11);
@@ -421,13 +301,7 @@ int info_workgroups(int n_points, int C) {
 
 size_t info_params_bytes(int n_problems) { return ((size_t)n_problems * sizeof(InfoParams) + 255) / 256 * 256; }
 
-// Pinned staging records, a ring of four per thread and device (as the LM batch keeps them): a slot is reused only
-// after the copy that read it has completed.
-struct InfoStageSlot {
-  InfoParams* host = nullptr;
-  hipEvent_t copied = nullptr;
-};
-constexpr int kInfoStageSlots = 4;
+using InfoStage = StageRing<InfoParams, PXT_LM_INFO_MAX_PROBLEMS>;
 
 }  // namespace
 }  // namespace pxt
@@ -449,21 +323,10 @@ extern "C" int pxt_lm_information(const pxt_lm_info_problem* problems, int32_t n
   const bool from_args = K <= kInfoArgProblems;
   InfoArgs args = {};
   InfoParams* rec = args.p;
-  InfoStageSlot* slot = nullptr;
+  InfoStage::Slot* slot = nullptr;
   if (!from_args) {
-    static thread_local InfoStageSlot stage[16][kInfoStageSlots];
-    static thread_local int stage_next[16] = {0};
-    int dev_id = 0;
-    PXT_HIP_CHECK(hipGetDevice(&dev_id));
-    if (dev_id < 0 || dev_id >= 16) return PXT_E_ARG;
-    slot = &stage[dev_id][stage_next[dev_id]];
-    stage_next[dev_id] = (stage_next[dev_id] + 1) % kInfoStageSlots;
-    if (!slot->host) {
-      PXT_HIP_CHECK(hipHostMalloc((void**)&slot->host, PXT_LM_INFO_MAX_PROBLEMS * sizeof(InfoParams), hipHostMallocDefault));
-      PXT_HIP_CHECK(hipEventCreateWithFlags(&slot->copied, hipEventDisableTiming));
-    } else {
-      PXT_HIP_CHECK(hipEventSynchronize(slot->copied));
-    }
+    static thread_local InfoStage stage;
+    if (const int rc = stage.acquire(&slot)) return rc;
     rec = slot->host;
   }
   int max_wgs = 1;
@@ -471,13 +334,8 @@ extern "C" int pxt_lm_information(const pxt_lm_info_problem* problems, int32_t n
     const pxt_lm_info_problem& q = problems[k];
     const pxt_lm_level& l = q.level;
     if (!q.p3d || !q.pose || !q.out || q.n_points < 1) return PXT_E_ARG;
-    if (!l.fmap || !l.fref || l.C < 4 || (l.C % 4) != 0 || (l.cstride % 4) != 0 || l.cstride < l.C + 1 || l.h < 2 ||
-        l.w < 2)
-      return PXT_E_ARG;
-    if (l.ndist != 0 && l.ndist != 2 && l.ndist != 4) return PXT_E_ARG;
-    if (((uintptr_t)l.fmap % 16) != 0 || ((uintptr_t)l.fref % 16) != 0 || ((uintptr_t)q.pose % 16) != 0 ||
-        ((uintptr_t)q.out % 4) != 0)
-      return PXT_E_ARG;
+    if (const int rc = check_level(l)) return rc;
+    if (((uintptr_t)q.pose % 16) != 0 || ((uintptr_t)q.out % 4) != 0) return PXT_E_ARG;
     // (byte offsets inside the map and the reference records are 32-bit in the kernel)
     if ((long long)l.h * l.w * l.cstride >= (1ll << 30) || (long long)q.n_points * l.cstride >= (1ll << 30)) return PXT_E_ARG;
     for (int j = 0; j < k; ++j)

@@ -419,9 +419,7 @@ __device__ inline void ray_clip(const NgpParams& P, Ray& r) {
 // over 22,000 such renders; the mechanism is NOT established (the defect moves with the instruction stream around the
 // loads: profiles/r06_experiments.md section 8), tests/test_edge_cases_gpu.py holds the regression test.
 __device__ __forceinline__ const float* camera_pointer(const NgpParams& P) {
-  const float* c = P.cam_dev ? P.cam_dev : P.cam;
-  asm volatile("" : "+v"(c));
-  return c;
+  return vector_pointer(P.cam_dev ? P.cam_dev : P.cam);
 }
 __device__ inline void load_camera(const NgpParams& P, float* cam) {
   const float* c = camera_pointer(P);
