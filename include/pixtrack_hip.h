@@ -566,6 +566,33 @@ int pxt_resize_linear(const float* src, int32_t H, int32_t W, int32_t C, float* 
 int pxt_resize_activity(const uint8_t* mask, const uint8_t* image_u8, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                         uint8_t* active_out, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Reference points from a Depth render (opt-in; csrc/pxt_points.hip).
+ *
+ * Stands in for the reference's use of the SfM points of the nearest mapping image as the points a frame is refined on
+ * (pixtrack/localization/pixloc_pose_refiners.py:282-290): the points are a lattice of the render's own pixels,
+ * back-projected with the renderer's pixel convention (pixel centre at +0.5, principal point at the image centre).
+ *   depth [H][W][4] float32 (16-byte aligned): what a Depth-mode render writes - channel 0 the composited
+ *       t * zdot * depth_scale after the spp mean, channel 3 alpha (background alpha 0).
+ *   base test of a pixel: alpha >= min_alpha && depth0 > 0.  ACCEPTED: the base test holds on the whole
+ *       (2 erode + 1)^2 square around it (erode 0..2; a square that leaves the image fails).
+ *   stride s (chosen on the device): the smallest integer >= 1 with s * s * n_max >= A, A = accepted pixels.
+ *   candidates: accepted pixels with x % s == s / 2 && y % s == s / 2; points: the first n_max candidates in row-major
+ *       order (order-preserving compaction without atomics: the same bits every launch).
+ *   point: z = depth0 / (alpha * depth_scale); p = b + z * M ((x + 0.5 - W/2) / focal, (y + 0.5 - H/2) / focal, 1)^T with
+ *       xform_host = [M | b] (3x4 row-major, host): render camera-to-ngp chained with ngp -> SfM object coordinates.
+ *       No lens undistortion: the caller refuses a Depth view with k1 != 0.
+ *   p3d [n_max][3], slot_valid [n_max]: slots >= n_points get slot_valid 0 and p = b (the camera centre, which
+ *       pxt_sample_sparse rejects at the reference pose: z > eps fails, so the LM gives them weight 0).
+ *   record (4 int32, device or pinned host) = {A, s, n_points, n_candidates}, written by the last launch;
+ *       n_candidates > n_max: the tail was cut.
+ *   workspace: device memory of the size the _workspace_bytes call returns (< 0: unsupported size), 8-byte aligned,
+ *       untouched until the launches have finished.  Three launches on `stream`, no host synchronisation. */
+int64_t pxt_points_from_depth_workspace_bytes(int32_t width, int32_t height);
+int pxt_points_from_depth(const float* depth, int32_t width, int32_t height, const float* xform_host, float focal,
+                          float depth_scale, float min_alpha, int32_t erode, int32_t n_max, float* p3d,
+                          uint8_t* slot_valid, int32_t* record, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,9 @@ PROTOTYPES = {
     "pxt_rgba_to_u8": (C.c_int, [_VP, _I32, _I32, C.c_float, _VP, _VP]),
     "pxt_resize_linear": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I32, _I32, _VP]),
     "pxt_resize_activity": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP]),
+    "pxt_points_from_depth_workspace_bytes": (_I64, [_I32, _I32]),
+    "pxt_points_from_depth": (C.c_int, [_VP, _I32, _I32, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, _I32, _I32,
+                                        _VP, _VP, _VP, _VP, _VP]),
 }
 
 

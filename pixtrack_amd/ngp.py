@@ -304,6 +304,24 @@ def nerf_matrix_to_ngp(nerf_c2w: np.ndarray, scale: float, offset: float) -> np.
     return m[[1, 2, 0], :]
 
 
+def ngp_to_sfm_affine(nerf2sfm, scale: float, offset: float) -> np.ndarray:
+    """3 x 4 float64 [G | g] with p_sfm = G p_ngp + g for POINTS: instant-ngp's nerf_matrix_to_ngp undone (axis cycle,
+    offset, scale), then the inverse of sfm_to_nerf_pose (utils/ingp_utils.nerf_to_sfm_pose), read off the images of the
+    origin and the three unit vectors."""
+    from .utils.ingp_utils import nerf_to_sfm_pose
+
+    def to_sfm(p_ngp):
+        nerf = np.empty(3)
+        nerf[[1, 2, 0]] = (np.asarray(p_ngp, np.float64) - offset) / scale  # ngp row i is nerf row (1, 2, 0)[i]
+        T = np.eye(4)
+        T[:3, 3] = nerf
+        return nerf_to_sfm_pose(nerf2sfm, T)[:3, 3]
+
+    g = to_sfm(np.zeros(3))
+    G = np.stack([to_sfm(e) - g for e in np.eye(3)], axis=1)
+    return np.concatenate([G, g[:, None]], axis=1)
+
+
 class _Aabb:
     def __init__(self):
         self.min = [0.0, 0.0, 0.0]
@@ -495,7 +513,7 @@ class Testbed:
         """One render whose last kernel writes what the tracking loop consumes (pxt_ngp_render_frame): returns a dict with
         ``rgb_u8`` uint8 [H, W, 3] (modes 0 / 2: get_nerf_image's image of the Shade render) and ``depth_nz`` uint8 [H, W]
         (modes 1 / 2: get_mask's `uint8(depth * 255) != 0` plane), plus the float images ``rgba`` / ``depth`` when
-        ``want_float``.  mode 0 Shade, 1 Depth, 2 both from one march.  ``from_slot``: the camera is whatever the LM
+        ``want_float`` (``want_float="depth"``: the float Depth image alone).  mode 0 Shade, 1 Depth, 2 both from one march.  ``from_slot``: the camera is whatever the LM
         kernel ahead in the stream wrote into camera_slot() - the render of a pose the host has not seen yet."""
         self._check_renderable()
         dev, out = self.device, {}
@@ -503,7 +521,9 @@ class Testbed:
             out["rgb_u8"] = torch.empty(height, width, 3, device=dev, dtype=torch.uint8)
         if mode != 0:
             out["depth_nz"] = torch.empty(height, width, device=dev, dtype=torch.uint8)
-        if want_float:
+        if want_float == "depth":  # only the float Depth image (mode 2: ``depth``; mode 1: ``rgba``)
+            out["depth" if mode == 2 else "rgba"] = torch.empty(height, width, 4, device=dev, dtype=torch.float32)
+        elif want_float:
             out["rgba"] = torch.empty(height, width, 4, device=dev, dtype=torch.float32)
             if mode == 2:
                 out["depth"] = torch.empty(height, width, 4, device=dev, dtype=torch.float32)
@@ -515,7 +535,7 @@ class Testbed:
 
     @staticmethod
     def render_frame_batch_device(testbeds, sizes, spp: int = 8, mode=2, from_slot: bool = False, workspace=None,
-                                  sides=None, fovs=None):
+                                  sides=None, fovs=None, depth_float: bool = False):
         """render_frame_device for K renders as ONE chain of launches (pxt_ngp_render_frame_batch): K testbeds (K objects,
         each with its own NeRF), or - ``sides[k]`` true - a testbed's second context (the second of a frame's two renders of one
         NeRF).  ``sizes[k]`` = (width, height); ``mode``: one int for all or one per render; ``fovs[k]`` (optional): the
@@ -523,7 +543,8 @@ class Testbed:
         ``from_slot``, the context's camera slot) is used as render_frame_device would.  Returns one dict per render
         (``rgb_u8``, ``depth_nz`` as its mode provides), bit for bit what K render_frame_device calls return.
         ``workspace``: a device uint8 tensor of batch_workspace_bytes(K) the caller keeps per stream (made here when None;
-        K <= 2 needs none: the records travel as kernel arguments)."""
+        K <= 2 needs none: the records travel as kernel arguments).  ``depth_float``: every render of mode 1 / 2 also
+        writes its float32 [H, W, 4] Depth image (``depth`` in its dict)."""
         K = len(testbeds)
         assert K >= 1 and len(sizes) == K
         modes = [int(mode)] * K if isinstance(mode, int) else [int(m) for m in mode]
@@ -537,6 +558,8 @@ class Testbed:
                 o["rgb_u8"] = torch.empty(h, w, 3, device=dev, dtype=torch.uint8)
             if modes[k] != 0:
                 o["depth_nz"] = torch.empty(h, w, device=dev, dtype=torch.uint8)
+                if depth_float:
+                    o["depth"] = torch.empty(h, w, 4, device=dev, dtype=torch.float32)
             outs.append(o)
             views += tb._view_for(w, h, None if fovs is None else fovs[k])
             flat_sizes += [int(w), int(h)]
@@ -546,21 +569,26 @@ class Testbed:
         stats = [tb.stats_accum for tb in testbeds] if all(tb.stats_accum is not None for tb in testbeds) else []
         ops.ngp_render_frame_batch(ctxs, views, flat_sizes, int(spp), modes, bool(from_slot),
                                    [o["rgb_u8"] for o in outs if "rgb_u8" in o],
-                                   [o["depth_nz"] for o in outs if "depth_nz" in o], workspace, stats)
+                                   [o["depth_nz"] for o in outs if "depth_nz" in o], workspace, stats,
+                                   [o["depth"] for o in outs if "depth" in o] if depth_float else None)
         for tb in testbeds:
             tb.n_renders += 1
         return outs
 
-    def render_frame_pair_device(self, depth_view, shade_view, spp: int = 8, from_slot: bool = False, workspace=None):
+    def render_frame_pair_device(self, depth_view, shade_view, spp: int = 8, from_slot: bool = False, workspace=None,
+                                 depth_float: bool = False):
         """A frame's two renders of DIFFERENT cameras at one pose - ``depth_view`` = (width, height, fov) of the mask's Depth
         render (the query camera), ``shade_view`` of the reference image's Shade render (SfM camera 1 x reference_scale) - as
         ONE chain of launches on the current stream (pixtrack/pose_trackers/pixloc_tracker_r9.py:145-152, 207-214 render them
         one after the other through one testbed).  The Depth render runs through this testbed's first context, the Shade
         render through its second (shared tables).  Returns (depth_nz, rgb_u8), bit for bit what render_frame_device
-        returns for each."""
+        returns for each.  ``depth_float``: a third value, the Depth render's float32 [H, W, 4] image."""
         (dw, dh, dfov), (sw, sh, sfov) = depth_view, shade_view
         outs = Testbed.render_frame_batch_device([self, self], [(dw, dh), (sw, sh)], spp, mode=[1, 0], from_slot=from_slot,
-                                                 workspace=workspace, sides=[False, True], fovs=[dfov, sfov])
+                                                 workspace=workspace, sides=[False, True], fovs=[dfov, sfov],
+                                                 depth_float=depth_float)
+        if depth_float:
+            return outs[0]["depth_nz"], outs[1]["rgb_u8"], outs[0]["depth"]
         return outs[0]["depth_nz"], outs[1]["rgb_u8"]
 
     @staticmethod

@@ -15,6 +15,8 @@ Reference call sites the ops stand in for:
   depth_mask           get_mask morphology (pixtrack/pose_trackers/pixloc_tracker_r9.py:207-214)
   rgba_to_u8           get_nerf_image's alpha threshold / *255 / uint8 (run_vis_on_poses.py:52-54)
   resize_linear        pixloc resize(image, size, max, "linear") (feature_extractor.py:45)
+  points_from_depth    (opt-in) stands in for the SfM points of the nearest mapping image as the points a frame is
+                       refined on (pixloc_pose_refiners.py:282-290): a lattice of the Depth render, back-projected
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -79,16 +81,22 @@ SCHEMAS = {
         "Tensor(b!)? depth, Tensor(c!)? rgb_u8, Tensor(d!)? depth_nz, Tensor(e!)? stats) -> ()"),
     # K renders of K different contexts as one chain of launches (pxt_ngp_render_frame_batch): views = K x 25 floats, sizes =
     # K x (width, height), modes = K x {0 Shade, 1 Depth, 2 both}; rgb_u8: one tensor per render whose mode is 0 / 2, in render
-    # order; depth_nz: one per render whose mode is 1 / 2
+    # order; depth_nz: one per render whose mode is 1 / 2; depth_float (optional): the float32 [H, W, 4] Depth image of
+    # every render whose mode is 1 / 2, in render order
     "ngp_render_frame_batch": (
         "(int[] ctxs, float[] views, int[] sizes, int spp, int[] modes, bool camera_from_slot, Tensor(a!)[] rgb_u8, "
-        "Tensor(b!)[] depth_nz, Tensor(c!) workspace, Tensor(d!)[] stats) -> ()"),
+        "Tensor(b!)[] depth_nz, Tensor(c!) workspace, Tensor(d!)[] stats, Tensor(e!)[]? depth_float=None) -> ()"),
     "depth_mask": "(Tensor depth_rgba, int n_erode, int n_dilate, Tensor(a!) mask, Tensor(b!) scratch) -> ()",
     "depth_mask_plane": "(Tensor depth_nz, int n_erode, int n_dilate, Tensor(a!) mask) -> ()",
     "rgba_to_u8": "(Tensor rgba, float alpha_thresh, Tensor(a!) out) -> ()",
     "resize_linear": "(Tensor src, Tensor(a!) dst) -> ()",
     "resize_activity": "(Tensor? mask, Tensor? image_u8, int H, int W, Tensor(a!) active) -> ()",
     "conv3x3_nhwc_f16": "(Tensor x, Tensor weight, Tensor bias, bool relu, Tensor(a!) out) -> ()",
+    # depth [H, W, 4] of a Depth render -> p3d [n_max, 3], slot_valid uint8 [n_max], record int32 [4] (device or pinned):
+    # {accepted pixels, stride, points, candidates}; xform = 12 floats [M | b] (pxt_points_from_depth)
+    "points_from_depth": (
+        "(Tensor depth, float[] xform, float focal, float depth_scale, float min_alpha, int erode, int n_max, "
+        "Tensor(a!) p3d, Tensor(b!) slot_valid, Tensor(c!) record, Tensor(d!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -510,7 +518,8 @@ def _ngp_render_frame(ctx, view, width, height, spp, mode, camera_from_slot, rgb
                                                _lib.dptr(stats), _stream(ref)), "pxt_ngp_render_frame")
 
 
-def _ngp_render_frame_batch(ctxs, views, sizes, spp, modes, camera_from_slot, rgb_u8, depth_nz, workspace, stats):
+def _ngp_render_frame_batch(ctxs, views, sizes, spp, modes, camera_from_slot, rgb_u8, depth_nz, workspace, stats,
+                            depth_float=None):
     """pxt_ngp_render_frame_batch: K renders of K renderer contexts - a frame's Depth + Shade pair, or K objects in lock-step -
     as ONE staged chain of launches; bit for bit K calls of ngp_render_frame.  8-bit outputs only (what the tracker consumes)."""
     K, modes = len(ctxs), [int(m) for m in modes]
@@ -521,6 +530,8 @@ def _ngp_render_frame_batch(ctxs, views, sizes, spp, modes, camera_from_slot, rg
         raise _lib.PxtError("ngp_render_frame_batch: a mode is 0 (Shade), 1 (Depth) or 2 (both)")
     if len(rgb_u8) != sum(m != 1 for m in modes) or len(depth_nz) != sum(m != 0 for m in modes):
         raise _lib.PxtError("ngp_render_frame_batch: one rgb_u8 per render of mode 0 / 2, one depth_nz per render of mode 1 / 2")
+    if depth_float is not None and len(depth_float) != len(depth_nz):
+        raise _lib.PxtError("ngp_render_frame_batch: depth_float holds one image per render of mode 1 / 2")
     L = _lib.lib()
     need = int(L.pxt_ngp_batch_workspace_bytes(K)) if K > 2 else 0  # (<= 2 renders: the records travel as kernel arguments)
     if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() < need:
@@ -536,18 +547,25 @@ def _ngp_render_frame_batch(ctxs, views, sizes, spp, modes, camera_from_slot, rg
     for k in range(K):
         w, h = int(sizes[2 * k]), int(sizes[2 * k + 1])
         vs[k] = _view(views[k * VIEW_FLOATS:(k + 1) * VIEW_FLOATS], w, h, spp, 0 if modes[k] == 2 else modes[k])
-        u8 = nz = None
+        u8 = nz = df = None
         if modes[k] != 1:
             u8, i_u8 = rgb_u8[i_u8], i_u8 + 1
         if modes[k] != 0:
             nz, i_nz = depth_nz[i_nz], i_nz + 1
+            if depth_float is not None:
+                df = depth_float[i_nz - 1]
+                _check_frame(df, w, h, "depth_float")
+                if df.device != workspace.device:
+                    raise _lib.PxtError("ngp_render_frame_batch: depth_float lives on the workspace's device")
         if u8 is not None and (u8.dtype != torch.uint8 or tuple(u8.shape) != (h, w, 3) or not u8.is_contiguous()
                                or u8.device != workspace.device):
             raise _lib.PxtError("ngp_render_frame_batch: rgb_u8 is a contiguous device uint8 [H, W, 3]")
         if nz is not None and (nz.dtype != torch.uint8 or tuple(nz.shape) != (h, w) or not nz.is_contiguous()
                                or nz.device != workspace.device):
             raise _lib.PxtError("ngp_render_frame_batch: depth_nz is a contiguous device uint8 [H, W]")
-        outs[k] = _lib.NgpOutputs(None, None, _lib.dptr(u8), _lib.dptr(nz))
+        # (a Depth render writes its float image through `rgba`, a two-output march through `depth_rgba`)
+        outs[k] = _lib.NgpOutputs(_lib.dptr(df) if modes[k] == 1 else None, _lib.dptr(df) if modes[k] == 2 else None,
+                                  _lib.dptr(u8), _lib.dptr(nz))
         sp[k] = stats[k].data_ptr() if stats else None
     _lib.check(L.pxt_ngp_render_frame_batch(cp, vs, K, mp, int(bool(camera_from_slot)), outs,
                                             sp if stats else None, workspace.data_ptr() if workspace.numel() else None,
@@ -610,7 +628,44 @@ def _resize_activity(mask, image_u8, H, W, active):
                                               _stream(active)), "pxt_resize_activity")
 
 
+def _points_from_depth(depth, xform, focal, depth_scale, min_alpha, erode, n_max, p3d, slot_valid, record, workspace):
+    L = _lib.lib()
+    _f32c(depth, "depth")
+    _f32c(p3d, "p3d")
+    if depth.dim() != 3 or int(depth.shape[2]) != 4:
+        raise _lib.PxtError(f"points_from_depth: depth is [H, W, 4] (got {tuple(depth.shape)})")
+    H, W, n_max = int(depth.shape[0]), int(depth.shape[1]), int(n_max)
+    if len(xform) != 12:
+        raise _lib.PxtError("points_from_depth: xform holds 12 floats ([M | b], 3 x 4 row-major)")
+    if int(erode) not in (0, 1, 2) or n_max < 1:
+        raise _lib.PxtError("points_from_depth: erode is 0, 1 or 2 and n_max >= 1")
+    if tuple(p3d.shape) != (n_max, 3):
+        raise _lib.PxtError(f"points_from_depth: p3d is {tuple(p3d.shape)}, expected {(n_max, 3)}")
+    if slot_valid.dtype != torch.uint8 or slot_valid.numel() != n_max or not slot_valid.is_contiguous():
+        raise _lib.PxtError("points_from_depth: slot_valid is a contiguous uint8 [n_max]")
+    if record.dtype != torch.int32 or record.numel() < 4 or not record.is_contiguous():
+        raise _lib.PxtError("points_from_depth: record holds 4 contiguous int32 values")
+    need = int(L.pxt_points_from_depth_workspace_bytes(W, H))
+    if need <= 0:
+        raise _lib.PxtError(f"points_from_depth: a {W} x {H} image is not supported")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"points_from_depth: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of the depth image's device (a host pointer there is a memory fault,
+    # not an error); the record may also be pinned host memory
+    for t, name in ((depth, "depth"), (p3d, "p3d"), (slot_valid, "slot_valid"), (workspace, "workspace")):
+        _lib.require_gpu(t, name)
+        if t.device != depth.device:
+            raise _lib.PxtError(f"points_from_depth: {name} is on {t.device}, the depth image on {depth.device}")
+    if not ((record.is_cuda and record.device == depth.device) or record.is_pinned()):
+        raise _lib.PxtError("points_from_depth: record must be memory of the depth image's device or pinned host memory")
+    xf = (C.c_float * 12)(*[float(x) for x in xform])
+    _lib.check(L.pxt_points_from_depth(depth.data_ptr(), W, H, xf, float(focal), float(depth_scale), float(min_alpha),
+                                       int(erode), n_max, p3d.data_ptr(), slot_valid.data_ptr(), record.data_ptr(),
+                                       workspace.data_ptr(), _stream(depth)), "pxt_points_from_depth")
+
+
 _IMPLS = {
+    "points_from_depth": _points_from_depth,
     "lm_refine": _lm_refine,
     "lm_refine_batch": _lm_refine_batch,
     "lm_information": _lm_information,

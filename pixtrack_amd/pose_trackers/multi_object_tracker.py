@@ -71,6 +71,9 @@ class MultiObjectTracker:
             # ground-truth-gated updates, pixloc_tracker_ycb.py:241-295) would silently run r9's policy here
             if type(tr).refine is not PixLocPoseTrackerR9.refine or type(tr)._frame_policy is not PixLocPoseTrackerR9._frame_policy:
                 raise _lib.PxtError(f"{type(tr).__name__} overrides refine(): lock-step tracking implements PixLocPoseTrackerR9's policy only")
+            if getattr(tr, "reference_points", "sfm") != "sfm":
+                # (the batched render chain carries no float Depth image and the batched reference pass encodes the SfM window)
+                raise ValueError("reference_points='render' is not supported by lock-step tracking yet")
         # one UNet context runs every image of a group's step: the trackers must hold the same checkpoint in the same
         # precision (pixloc_megadepth is one network for all objects; reference pixloc_pose_refiners.py:49-60; the
         # signature names the precision)

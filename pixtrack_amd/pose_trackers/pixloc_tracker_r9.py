@@ -49,7 +49,7 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
 
 class PixLocPoseTrackerR9(PoseTracker):
     def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
-                 unet_precision="fp16", relocalizer=None, uncertainty=False):
+                 unet_precision="fp16", relocalizer=None, uncertainty=False, reference_points="sfm"):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
         synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
         ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet).
@@ -60,7 +60,15 @@ class PixLocPoseTrackerR9(PoseTracker):
         pxt_lm_information problem at the pose it returns, and a frame's history entry gains ``pose_info`` (6 x 6),
         ``pose_cov`` (6 x 6 or None), ``observability``, ``info_level`` and ``info_n_valid`` from the frame's last LM
         launch (uncertainty.py); None for a frame whose refinement failed.  The cost gate, the pose update and
-        ``tracked`` never read them."""
+        ``tracked`` never read them.
+        ``reference_points``: "sfm" (default: the reference's behaviour - a frame is refined on the SfM points of the
+        nearest mapping image) or "render" - on up to ``reference_points_max`` points back-projected from a lattice of the
+        frame's own Depth render (refiner.points_from_render): they cover the visible side, do not change when
+        update_reference_ids switches and need no triangulated points.  A frame's history entry then gains
+        ``n_reference_points`` and ``reference_point_stride``; nothing on the policy path reads them.  Not combined
+        with ``relocalizer`` or ``uncertainty`` yet (ValueError)."""
+        self._check_reference_points(reference_points, relocalizer, uncertainty)
+        self.reference_points = reference_points
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
                               query_list="*_with_intrinsics.txt", global_descriptors="features.h5",
                               retrieval_pairs="pairs_query.txt", results="pixloc_object.txt")
@@ -71,7 +79,7 @@ class PixLocPoseTrackerR9(PoseTracker):
             "optimizer": {"num_iters": 150, "pad": 1},
             "refinement": {"num_dbs": 1, "multiscale": [1], "point_selection": "all",
                            "normalize_descriptors": True, "average_observations": False,
-                           "do_pose_approximation": False},
+                           "do_pose_approximation": False, "reference_points": reference_points},
         }
         self.debug = debug
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -119,6 +127,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         self.spp = 8  # run_vis_on_poses.py:29
         self.batch_frame_images = True  # reference render + masked query in one batched UNet pass
         self._fused_reference = None  # (pose object, uint8 image) handed from get_mask to get_reference_image
+        self._fused_depth = None  # (pose object, float Depth render) beside it: reference_points="render" only
         self._ref_cam_cache = self._coincide_cache = None
         self.keep_feature_history = False  # the reference leaks one entry per frame (Appendix D.2)
         self.steady_multiscale = [1]  # image scales of a tracked (non-cold-start) frame (:223)
@@ -135,7 +144,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         self.render_ahead = os.environ.get("PXT_RENDER_AHEAD", "1") != "0"
         self._ahead_cam = None   # the pinned camera record the LM epilogue of this frame writes
         self._ahead = None       # the render queued behind the last LM launch
-        self._ahead_ok = None    # ... once verified: (pose object it is valid for, mask, uint8 reference image)
+        self._ahead_ok = None    # ... once verified: (pose object it is valid for, mask, uint8 reference image, views, depth)
         # queued renders: consumed / camera record never arrived within the poll bound / host and device disagree on a camera
         # bit / view settings changed between enqueue and use
         self.renders_ahead_used = self.renders_ahead_dropped = self.renders_ahead_rejected = self.renders_ahead_stale = 0
@@ -146,6 +155,20 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._relocalized_frame = False  # this frame's pose came from the relocaliser (history key "relocalized")
 
     # ------------------------------------------------------------------ per-variant set-up
+    supports_render_points = True  # (the YCB policy does not yet)
+
+    def _check_reference_points(self, reference_points, relocalizer, uncertainty):
+        if reference_points not in ("sfm", "render"):
+            raise ValueError(f"reference_points must be 'sfm' or 'render' (got {reference_points!r})")
+        if reference_points == "render":
+            if not self.supports_render_points:
+                raise ValueError(f"reference_points='render' is not supported by {type(self).__name__} yet")
+            if relocalizer is not None and relocalizer != "off":
+                raise ValueError("reference_points='render' is not combined with a relocalizer yet (its feature bank is "
+                                 "built from the SfM points)")
+            if uncertainty:
+                raise ValueError("reference_points='render' is not combined with uncertainty=True yet")
+
     def _initial_reference_ids(self, assets):
         """r9: the upright reference image named by $UPRIGHT_REF_IMG (:77-78)."""
         upright_ref_img = assets["upright_ref_img"] if assets is not None else os.environ["UPRIGHT_REF_IMG"]
@@ -289,12 +312,44 @@ class PixLocPoseTrackerR9(PoseTracker):
         return rgba_to_u8(rgba, 0.0)
 
     def create_dynamic_reference_image(self, pose):
+        if self.reference_points == "render":
+            return self._create_dynamic_reference_from_render(pose)
         nerf_img = self.get_reference_image(pose)
         # (the reference hashes str(R); the id is only a dictionary key - the bytes of R serve, without numpy's
         # array printer on the per-frame host path)
         dynamic_id = hash(pose.numpy()[0].tobytes())
         features = self.localizer.refiner.extract_reference_features(self.reference_ids, pose, nerf_img)
         return dynamic_id, features
+
+    def _create_dynamic_reference_from_render(self, pose):
+        """create_dynamic_reference_image with reference_points="render": the points come from the frame's Depth render
+        at ``pose`` - the one get_mask made (or the render queued behind the last LM launch); a frame that renders no
+        mask (cold start, the frame after a failed one) renders Depth + reference here."""
+        if self._fused_depth is None or self._fused_depth[0] is not pose:
+            self._mask_and_reference(pose, from_slot=False)
+        depth, self._fused_depth = self._fused_depth[1], None
+        nerf_img = self.get_reference_image(pose)
+        dynamic_id = hash(pose.numpy()[0].tobytes())
+        features = self.localizer.refiner.extract_reference_features(self.reference_ids, pose, nerf_img, depth=depth,
+                                                                     depth_view=self._depth_view(pose))
+        return dynamic_id, features
+
+    def _depth_view(self, pose) -> dict:
+        """The view record of the frame's Depth render at ``pose`` for refiner.points_from_render: xform = [M | b], the
+        render's camera-to-ngp matrix (the 12 floats the renderer used) chained with ngp -> SfM object coordinates, in
+        float64; focal and k1 as the render's view record holds them."""
+        from ..ngp import ngp_to_sfm_affine, nerf_matrix_to_ngp
+
+        snap = self.testbed._snap
+        A = self.__dict__.get("_ngp2sfm")
+        if A is None:
+            A = self._ngp2sfm = ngp_to_sfm_affine(self.nerf2sfm, float(snap.scale), float(snap.offset))
+        cam = nerf_matrix_to_ngp(np.asarray(self._nerf_pose(pose))[:3, :], snap.scale, snap.offset)
+        cam = np.asarray(cam, np.float32).astype(np.float64)
+        xform = np.concatenate([A[:, :3] @ cam[:, :3], (A[:, :3] @ cam[:, 3] + A[:, 3])[:, None]], axis=1)
+        width, height, fov = self._frame_views()[0]
+        view = self.testbed._view_for(width, height, fov)
+        return {"xform": xform.reshape(-1).tolist(), "focal": view[12], "k1": view[13], "depth_scale": 1.0 / float(snap.scale)}
 
     def get_dynamic_id(self, pose):
         features_dicts = self.localizer.refiner.features_dicts
@@ -319,12 +374,13 @@ class PixLocPoseTrackerR9(PoseTracker):
     def get_mask(self, pose) -> torch.Tensor:
         """uint8 [H,W] on the device: depth render != 0, erode 5x5 x1, dilate 5x5 x5."""
         if self._ahead_ok is not None and self._ahead_ok[0] is pose:
-            _, mask, ref_u8, views = self._ahead_ok
+            _, mask, ref_u8, views, depth = self._ahead_ok
             self._ahead_ok = None
             # (it also baked in focal length, size, spp, lens, render box, background and minimum transmittance as they were
             # when it was enqueued: it stands in for this frame's render only if they are what this frame would use)
             if views == self._ahead_views_now():
                 self._fused_reference = (pose, ref_u8)
+                self._fused_depth = (pose, depth) if depth is not None else None
                 self.renders_ahead_used += 1
                 return mask
             self.renders_ahead_stale += 1
@@ -348,21 +404,29 @@ class PixLocPoseTrackerR9(PoseTracker):
         views coincide, otherwise the Depth render (query camera) and the Shade render (reference camera) as one chain of
         launches on this stream.  ``from_slot``: the camera is the one the LM kernel ahead in the stream derived from its
         final pose (render-ahead); otherwise the host's conversion of ``pose``.  Sets ``_fused_reference`` when a pose
-        object is given; returns (mask, ref_u8)."""
+        object is given; returns (mask, ref_u8).  With reference_points="render" the Depth render also keeps its float
+        image (``_fused_depth`` / ``_last_depth``)."""
         tb, spp = self.testbed, int(self.spp)
+        want_depth = self.reference_points == "render"
         if not from_slot:
             tb.set_nerf_camera_matrix(np.asarray(self._nerf_pose(pose))[:3, :])
         views = self._frame_views()
         width, height, fov_q = views[0]
         if len(views) == 1:
             tb.fov = fov_q
-            out = tb.render_frame_device(width, height, spp, mode=2, from_slot=from_slot)
-            ref_u8, nz = out["rgb_u8"], out["depth_nz"]
+            out = tb.render_frame_device(width, height, spp, mode=2, from_slot=from_slot,
+                                         want_float="depth" if want_depth else False)
+            ref_u8, nz, depth = out["rgb_u8"], out["depth_nz"], out.get("depth")
+        elif want_depth:
+            nz, ref_u8, depth = tb.render_frame_pair_device(views[0], views[1], spp, from_slot=from_slot, depth_float=True)
         else:
             nz, ref_u8 = tb.render_frame_pair_device(views[0], views[1], spp, from_slot=from_slot)
+            depth = None
         mask = self._mask_of(nz)
+        self._last_depth = depth
         if pose is not None:
             self._fused_reference = (pose, ref_u8)
+            self._fused_depth = (pose, depth) if want_depth else None
         return mask, ref_u8
 
     def _mask_of(self, nz):
@@ -390,7 +454,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         camera the LM kernel's epilogue writes into the renderer's camera slot(s)."""
         views = self._ahead_views_now()
         mask, ref_u8 = self._mask_and_reference(None, from_slot=True)
-        self._ahead = ([self._ahead_cam], mask, ref_u8, views)
+        self._ahead = ([self._ahead_cam], mask, ref_u8, views, self._last_depth)
 
     def _render_ahead_request(self):
         """For a caller that merges the queued renders of several trackers into one batched chain (lock-step tracking,
@@ -404,7 +468,7 @@ class PixLocPoseTrackerR9(PoseTracker):
 
     def _render_ahead_accept(self, out):
         """What _render_ahead() does after its render, for a render that was part of a batched chain."""
-        self._ahead = ([self._ahead_cam], self._mask_of(out["depth_nz"]), out["rgb_u8"], self._ahead_views_now())
+        self._ahead = ([self._ahead_cam], self._mask_of(out["depth_nz"]), out["rgb_u8"], self._ahead_views_now(), None)
 
     def _ahead_views_now(self):
         """What a render queued now bakes in besides the camera pose, per render of the frame: focal length, lens, render
@@ -420,7 +484,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._ahead_ok = None
         if ahead is None or not success:
             return
-        cams, mask, ref_u8, views = ahead
+        cams, mask, ref_u8, views, depth = ahead
         self.testbed.set_nerf_camera_matrix(np.asarray(self._nerf_pose(self.pose))[:3, :])
         want = np.asarray(self.testbed._cam_ngp, np.float32).reshape(-1)
         for cam_out in cams:
@@ -434,7 +498,7 @@ class PixLocPoseTrackerR9(PoseTracker):
             if not np.array_equal(want.view(np.uint32), got[:12].view(np.uint32)):
                 self.renders_ahead_rejected += 1
                 return
-        self._ahead_ok = (self.pose, mask, ref_u8, views)
+        self._ahead_ok = (self.pose, mask, ref_u8, views, depth)
 
     # ------------------------------------------------------------------ one frame
     def refine(self, query):
@@ -532,6 +596,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         ret["camera"] = self.camera
         if self.relocalizer is not None:  # (an added key only where the option is on: the default history is unchanged)
             ret["relocalized"], self._relocalized_frame = self._relocalized_frame, False
+        if self.reference_points == "render":  # (added keys only where the option is on)
+            # the pinned record of this frame's extraction: its kernels ran ahead of the LM launch whose result is here
+            rec = refiner.last_points_record
+            ret["n_reference_points"], ret["reference_point_stride"] = (int(rec[2]), int(rec[1])) if rec is not None else (0, 0)
         ret["reference_ids"] = self.reference_ids
         ret["query_path"] = query_path
         ret["cost"] = costs[best_ref_id]
@@ -559,7 +627,7 @@ def _dump(obj, path, pixloc_pickles: bool):
             pkl.dump(obj, f)
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser()
     parser.add_argument("--object_path", type=Path)
     parser.add_argument("--query", type=Path)
@@ -572,10 +640,17 @@ def main(argv=None):
                         help="UNet activations: fp16 (default, fastest) or fp32 (pixloc's precision)")
     parser.add_argument("--uncertainty", action="store_true",
                         help="add the pose information matrix, covariance and observability of every frame to poses.pkl")
+    parser.add_argument("--reference_points", choices=("sfm", "render"), default="sfm",
+                        help="the points a frame is refined on: sfm (default: the SfM points of the nearest mapping image) "
+                             "or render (a lattice of the frame's own depth render, back-projected)")
     parser.add_argument("--relocalize", choices=("off", "views"), default="off",
                         help="off (default: cold start from the upright view, a lost track stays lost) or views "
                              "(relocalise the cold start and the frame after a failed frame against the mapping views)")
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     data_path = args.object_path / "pixtrack/pixsfm/dataset"
     eval_path = args.out_dir
     loc_path = args.object_path / "pixtrack/aug_nerf_sfm"
@@ -587,7 +662,7 @@ def main(argv=None):
     tracker = PixLocPoseTrackerR9(object_path=str(args.object_path), data_path=str(data_path),
                                   eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
                                   unet_precision=args.unet_precision, relocalizer=args.relocalize,
-                                  uncertainty=args.uncertainty)
+                                  uncertainty=args.uncertainty, reference_points=args.reference_points)
     import gc
 
     gc.collect()

@@ -58,11 +58,11 @@ class GTFrameIterator:
 
 class PixLocPoseTrackerYCB(PixLocPoseTrackerR9):
     def __init__(self, data_path, loc_path, eval_path, object_path, debug=False, device=None, assets=None,
-                 ycb_root=None, unet_precision="fp16", uncertainty=False):
+                 ycb_root=None, unet_precision="fp16", uncertainty=False, reference_points="sfm"):
         self.object_path = object_path
         self.ycb_root = Path(ycb_root or os.environ.get("YCB_ROOT", "/data/ycb/"))
         super().__init__(object_path, data_path, loc_path, eval_path, debug=int(debug), device=device, assets=assets,
-                         unet_precision=unet_precision, uncertainty=uncertainty)
+                         unet_precision=unet_precision, uncertainty=uncertainty, reference_points=reference_points)
         self.reference_scale = 0.3
         self.localizer.refiner.reference_scale = self.reference_scale
         self.localizer.refiner.conf.multiscale = [1]
@@ -70,6 +70,8 @@ class PixLocPoseTrackerYCB(PixLocPoseTrackerR9):
         self.gt_pose = None
         self.gt_camera = None
         self.t_err = self.r_err = float("nan")
+
+    supports_render_points = False  # (its refine() renders the mask every frame: a follow-up)
 
     def _initial_reference_ids(self, assets):
         return None  # chosen from the GT pose at the first relocalisation (:117-130)

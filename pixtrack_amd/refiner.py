@@ -83,6 +83,12 @@ class PoseTrackerRefiner:
         # workload ({4: [2], 1: [2, 1, 0]}: the 1/64 map of the downscaled image + the three native ones)
         level_plan=None,
         reference_window=True,  # encode only the window of the reference render the sampled points depend on (see reference_window)
+        # where the points a frame is refined on come from: "sfm" (the reference: the SfM points of the nearest mapping
+        # image, _points_of) or "render" (a lattice of the frame's own Depth render, back-projected: points_from_render)
+        reference_points="sfm",
+        reference_points_max=2048,       # point slots of a "render" frame (the benchmark's LM problem size)
+        reference_points_min_alpha=0.5,  # a pixel's base test: alpha >= this and depth > 0 ...
+        reference_points_erode=1,        # ... on the whole (2 erode + 1)^2 square around it (keeps silhouette pixels out)
         filter_covisibility=False,
         do_pose_approximation=False,
         do_inlier_ranking=False,
@@ -102,6 +108,12 @@ class PoseTrackerRefiner:
         self.paths = paths
         self.conf = merge(self.base_default_config, self.default_config, conf or {})
         assert self.conf.normalize_descriptors and self.conf.compute_uncertainty
+        if self.conf.reference_points not in ("sfm", "render"):
+            raise ValueError(f"reference_points must be 'sfm' or 'render' (got {self.conf.reference_points!r})")
+        self._points_ws: Dict[Tuple[int, int], torch.Tensor] = {}  # (w, h) -> workspace of pxt_points_from_depth
+        self._points_records = None  # pinned {A, s, n_points, n_candidates} records, recycled round-robin
+        self._points_next = 0
+        self.last_points_record: Optional[torch.Tensor] = None  # the record of the last "render" extraction
         self.query_mask: Optional[torch.Tensor] = None  # device uint8 [H,W], set by the tracker
         self._p3d_cache: Dict[int, Tuple[List[int], torch.Tensor]] = {}
         self._p3d_host: Dict[int, np.ndarray] = {}
@@ -136,6 +148,47 @@ class PoseTrackerRefiner:
             self._p3d_cache[key] = (p3dids, torch.from_numpy(xyz).to(self.device))
             self._p3d_host[key] = xyz.astype(np.float64)
         return self._p3d_cache[key]
+
+    @property
+    def render_points(self) -> bool:
+        return self.conf.reference_points == "render"
+
+    def _next_points_record(self) -> torch.Tensor:
+        """A pinned int32 [4] record for pxt_points_from_depth.  The kernel receives the raw pointer, so the records
+        live as long as the refiner and are recycled round-robin: one is written per frame, and a frame's kernels have
+        finished (its LM result was read) long before eight more extractions are queued."""
+        if self._points_records is None:
+            self._points_records = [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(8)]
+        rec = self._points_records[self._points_next]
+        self._points_next = (self._points_next + 1) % len(self._points_records)
+        return rec
+
+    def points_from_render(self, depth: torch.Tensor, depth_view: Dict):
+        """The points of a "render" frame: -> (p3d [n_max, 3] in SfM object coordinates, slot_valid uint8 [n_max],
+        record): a lattice of the accepted pixels of ``depth`` (the float image of a Depth render, [H, W, 4]),
+        back-projected along the renderer's rays.  ``depth_view``: {"xform": 12 floats [M | b] (render camera -> SfM
+        object coordinates), "focal", "k1", "depth_scale"} of that render.  Everything is enqueued on the current
+        stream; the pinned record {accepted pixels, stride, points, candidates} may be read once a later result of the
+        stream (the frame's LM record) has arrived."""
+        if float(depth_view.get("k1", 0.0)) != 0.0:
+            raise ValueError("reference_points='render' back-projects without lens undistortion: the Depth view's k1 "
+                             f"must be 0 (got {depth_view['k1']})")
+        n_max = int(self.conf.reference_points_max)
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        ws = self._points_ws.get((W, H))
+        if ws is None:
+            need = int(_lib.lib().pxt_points_from_depth_workspace_bytes(W, H))
+            if need <= 0:
+                raise _lib.PxtError(f"a {W} x {H} Depth render is not supported by pxt_points_from_depth")
+            ws = self._points_ws[(W, H)] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        p3d = torch.empty(n_max, 3, dtype=torch.float32, device=self.device)
+        slot_valid = torch.empty(n_max, dtype=torch.uint8, device=self.device)
+        record = self._next_points_record()
+        ops.points_from_depth(depth, [float(x) for x in depth_view["xform"]], float(depth_view["focal"]),
+                              float(depth_view["depth_scale"]), float(self.conf.reference_points_min_alpha),
+                              int(self.conf.reference_points_erode), n_max, p3d, slot_valid, record, ws)
+        self.last_points_record = record
+        return p3d, slot_valid, record
 
     # ---- the reference pass on a window of the reference render ---------------------------------------------
     # The reference computes the reference image's dense maps only to sample them at the projected 3-D points
@@ -252,22 +305,39 @@ class PoseTrackerRefiner:
                           True, outs, valid, windows)
         return SparseReferenceFeatures(outs, valid, list(p3dids), p3d, OUTPUT_DIMS)
 
-    def extract_reference_features(self, dbids, pose: Optional[Pose] = None, reference_image=None):
+    def extract_reference_features(self, dbids, pose: Optional[Pose] = None, reference_image=None, depth=None,
+                                   depth_view=None):
+        """``depth`` / ``depth_view`` (conf.reference_points == "render" only): the float Depth render at ``pose`` and
+        its view record (points_from_render); the points then come from it instead of the SfM model, their ids are the
+        slot indices, and the whole reference render is encoded (reference_window is derived from the SfM points)."""
         multiscales = self.conf.multiscale or [1]
         if reference_image is None:
             raise NotImplementedError("static reference images on disk (r5/r7 mode) are out of scope: "
                                       "r9 always passes the NeRF render (pixloc_tracker_r9.py:157-159)")
-        p3dids, p3d = self._points_of(dbids)
         ref_img = self.model3d.dbs[dbids[0]]
         if pose is None:
             pose = Pose.from_Rt(ref_img.qvec2rotmat(), ref_img.tvec)
+        render_points = self.render_points
+        if render_points:
+            if depth is None or depth_view is None:
+                raise ValueError("reference_points='render' needs the frame's Depth render (depth, depth_view)")
+            p3d, slot_valid, record = self.points_from_render(depth, depth_view)
+            p3dids = self.__dict__.get("_slot_ids")
+            if p3dids is None or len(p3dids) != int(p3d.shape[0]):
+                p3dids = self._slot_ids = list(range(int(p3d.shape[0])))
+        else:
+            p3dids, p3d = self._points_of(dbids)
         features = {}
         for image_scale in multiscales:
-            image, window = self.reference_window(dbids, pose, reference_image)
+            image, window = (reference_image, None) if render_points else self.reference_window(dbids, pose, reference_image)
             maps, scales = self.dense_feature_extraction(image, ref_img.name, image_scale)
             self.last_reference_wh = self.feature_extractor.last_input_wh  # (w, h) the reference pass ran at
             features[str(image_scale)] = self.interp_sparse_observations(maps, scales, dbids[0], p3dids, pose, p3d, window)
-            features[str(image_scale)].p3d_host = self._p3d_host[int(dbids[0])]  # (read by the opt-in pose information)
+            if render_points:
+                # (unused slots hold the camera centre of the render, which the sampler has just rejected at ``pose``)
+                features[str(image_scale)].slot_valid, features[str(image_scale)].points_record = slot_valid, record
+            else:
+                features[str(image_scale)].p3d_host = self._p3d_host[int(dbids[0])]  # (read by the opt-in pose information)
         return features
 
     # ---- pre-extracted reference features (reference :175-198) ---------------------------
@@ -399,8 +469,8 @@ class PoseTrackerRefiner:
     def refine(self, qname: str, qcamera: Camera, pose_init: Pose, dbids: List[int], loc=None,
                image_query=None, pose: Optional[Pose] = None, reference_images=None, dynamic_id=None) -> Dict:
         fail = {"success": False, "T_init": pose_init, "dbids": dbids, **self._no_information()}
-        p3dids, _ = self._points_of(dbids)
-        if len(p3dids) < self.conf.min_points_opt:
+        # (points of the frame's render are counted on the device: too few of them fail the LM's own min_valid rule)
+        if not self.render_points and len(self._points_of(dbids)[0]) < self.conf.min_points_opt:
             logger.debug("Not enough valid 3D points to optimize")
             return fail
         ret = self.refine_query_pose(qname, qcamera, pose_init, dbids, self.conf.multiscale, image_query, pose,
