@@ -281,6 +281,55 @@ int pxt_lm_information(const pxt_lm_info_problem* problems_host, int32_t n_probl
                        void* workspace, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Per-point residual report (which points carried the pose; opt-in, off the default path).
+ *
+ * The reference keeps the point set of a refinement at debug >= 2 (pixtrack/localization/tracker.py:26-30, filled from
+ * pixtrack/localization/pixloc_pose_refiners.py:200-271) and leaves the per-point terms to pixloc's plots.  One launch
+ * evaluates, for n_problems independent (points, level, pose) problems, the POINT terms of ONE LM iteration at the
+ * given pose and writes them out instead of summing them into normal equations: validity, the 2 x 2 bilinear taps, the
+ * loss and w_unc = conf_query * conf_ref are those of pxt_lm_refine (csrc/pxt_lm_point.h); no gradients, no Jacobian.
+ * conf_host supplies pad, loss, loss_alpha, loss_scale and min_valid; level.lambda is ignored.  pose and
+ * pose_is_lm_record are those of pxt_lm_information: a failed / timed-out LM record skips the problem - ONLY word 15 of
+ * the summary is written (-1.0), `points` stays untouched.
+ *
+ * Point record n (PXT_LM_POINT_RECORD = 8 floats; `points` is device memory, 16-byte aligned, or NULL: summary only):
+ *   [0]    valid (1.0 / 0.0)
+ *   [1,2]  (u, v) at the level's scale, in the LM's pixel convention; NaN when the point is not in front of the camera
+ *   [3]    |r|^2 over the C descriptor channels           [4] rho(|r|^2)
+ *   [5]    rho' (the robust weight)                       [6] w_unc              ([3..6] are 0 for an invalid point)
+ *   [7]    reject code: 0 valid, 1 masked out, 2 projection failed (behind the camera or outside the distortion
+ *          model's range), 3 outside the padded image
+ * Summary (PXT_LM_REPORT_SUMMARY = 16 floats, device or pinned host; word 15 is stored last with system-scope release):
+ *   [0] sum rho over valid points     [1] n_valid     [2] n_inliers: valid points with rho' >= inlier_weight
+ *   [3] sum rho' * w_unc over valid points            [4] sum w_unc over valid points
+ *   [5,6,7] the counts of reject codes 1, 2, 3        [8..14] 0
+ *   [15] 1.0 ok; -1.0 skipped; -2.0 evaluated with n_valid < min_valid
+ * [0] / [1] is the masked-mean cost pxt_lm_refine logs at k = 0 of an iteration started at that pose, [1] its k = 1.
+ *
+ * Deterministic in the way pxt_lm_information is: points are dealt to workgroups by n_points and C only, sums fold in
+ * a fixed order in LDS and then across a problem's workgroups (partials in the workspace, a second small launch), no
+ * floating-point atomics; a problem's output depends on that problem alone.
+ * workspace: device, pxt_lm_point_report_workspace_bytes(n_problems); one workspace serves one launch at a time.
+ * ---------------------------------------------------------------------- */
+#define PXT_LM_POINT_RECORD 8
+#define PXT_LM_REPORT_SUMMARY 16
+#define PXT_LM_REPORT_MAX_PROBLEMS 64
+typedef struct {
+  const float* p3d;           /* [n_points][3] */
+  const uint8_t* point_mask;  /* [n_points] or NULL */
+  int32_t n_points;
+  pxt_lm_level level;         /* as pxt_lm_info_problem: lambda ignored */
+  const float* pose;          /* device-readable, 16-byte aligned: 12 floats or an LM output record */
+  int32_t pose_is_lm_record;
+  float inlier_weight;        /* a valid point is an inlier when its robust weight rho' >= this */
+  float* points;              /* device [n_points][PXT_LM_POINT_RECORD], or NULL: summary only */
+  float* summary;             /* PXT_LM_REPORT_SUMMARY floats, device or pinned host */
+} pxt_lm_report_problem;
+int64_t pxt_lm_point_report_workspace_bytes(int32_t n_problems);
+int pxt_lm_point_report(const pxt_lm_report_problem* problems_host, int32_t n_problems, const pxt_lm_conf* conf_host,
+                        void* workspace, void* stream);
+
+/* -------------------------------------------------------------------------
  * UNet feature pyramid (pixloc `UNet`, experiment pixloc_megadepth).
  *
  * Replaces `pred = self.model({"image": image_tensor})`

@@ -26,6 +26,9 @@ PXT_UNET_MAX_BATCH = 16
 PXT_NGP_MAX_BATCH = 16
 PXT_LM_INFO_RECORD = 48
 PXT_LM_INFO_MAX_PROBLEMS = 64
+PXT_LM_POINT_RECORD = 8
+PXT_LM_REPORT_SUMMARY = 16
+PXT_LM_REPORT_MAX_PROBLEMS = 64
 
 
 class PxtError(RuntimeError):
@@ -130,6 +133,12 @@ class LmInfoProblem(C.Structure):
                 ("pose", C.c_void_p), ("pose_is_lm_record", C.c_int32), ("out", C.c_void_p)]
 
 
+class LmReportProblem(C.Structure):
+    _fields_ = [("p3d", C.c_void_p), ("point_mask", C.c_void_p), ("n_points", C.c_int32), ("level", LmLevel),
+                ("pose", C.c_void_p), ("pose_is_lm_record", C.c_int32), ("inlier_weight", C.c_float),
+                ("points", C.c_void_p), ("summary", C.c_void_p)]
+
+
 class RelocMap(C.Structure):
     _fields_ = [
         ("fmap", C.c_void_p),
@@ -167,6 +176,8 @@ PROTOTYPES = {
     "pxt_lm_refine_batch": (C.c_int, [C.POINTER(LmProblem), _I32, C.POINTER(LmConf), _VP, _VP]),
     "pxt_lm_information_workspace_bytes": (_I64, [_I32]),
     "pxt_lm_information": (C.c_int, [C.POINTER(LmInfoProblem), _I32, C.POINTER(LmConf), _VP, _VP]),
+    "pxt_lm_point_report_workspace_bytes": (_I64, [_I32]),
+    "pxt_lm_point_report": (C.c_int, [C.POINTER(LmReportProblem), _I32, C.POINTER(LmConf), _VP, _VP]),
     "pxt_sample_sparse": (C.c_int, [_VP, _I32, _VP, C.POINTER(SampleLevel), _I32, _I32, _I32, _VP, _VP]),
     "pxt_score_pose_hypotheses": (
         C.c_int, [C.POINTER(RelocMap), C.POINTER(RelocBank), _VP, _VP, _I32, C.POINTER(LmConf), _VP, _VP]),

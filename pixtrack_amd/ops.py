@@ -8,6 +8,8 @@ Reference call sites the ops stand in for:
   lm_refine            pixloc BaseRefiner.refine_pose_using_features -> opt.run per level
                        (pixtrack/localization/pixloc_pose_refiners.py:255-262)
   lm_information       (no reference counterpart) the LM's normal equations at a given pose, K problems per launch
+  lm_point_report      (opt-in) the per-point terms of one LM iteration at a given pose, K problems per launch: what
+                       DebugTracker keeps of a refinement's points at debug >= 2 (pixtrack/localization/tracker.py:26-30)
   sample_sparse        PoseTrackerRefiner.interp_sparse_observations (:327-368, interpolator :351)
   score_pose_hypotheses  (no reference counterpart) M pose hypotheses scored in one launch (relocalizer.py)
   unet_forward_batch   self.model({"image": ...}) (pixtrack/localization/feature_extractor.py:48)
@@ -58,6 +60,13 @@ SCHEMAS = {
         "(Tensor[] p3d, Tensor?[] point_masks, Tensor[] fmaps, Tensor[] frefs, int[] channels, float[] cameras, "
         "int[] ndist, Tensor[] poses, bool pose_is_lm_record, int pad, int loss, float loss_alpha, float loss_scale, "
         "int min_valid, Tensor(a!)[] records, Tensor(b!) workspace) -> ()"),
+    # K (points, level, pose) problems in one launch (pxt_lm_point_report): the arguments of lm_information, with per
+    # problem the inlier threshold on rho', an optional device tensor [N, 8] of point records (None: summary only) and a
+    # 16-float summary (device or pinned host)
+    "lm_point_report": (
+        "(Tensor[] p3d, Tensor?[] point_masks, Tensor[] fmaps, Tensor[] frefs, int[] channels, float[] cameras, "
+        "int[] ndist, Tensor[] poses, bool pose_is_lm_record, int pad, int loss, float loss_alpha, float loss_scale, "
+        "int min_valid, float[] inlier_weights, Tensor(a!)?[] points, Tensor(b!)[] summaries, Tensor(c!) workspace) -> ()"),
     "sample_sparse": (
         "(Tensor p3d, float[] T, Tensor[] fmaps, int[] channels, float[] cameras, int[] ndist, int pad, "
         "bool normalize, Tensor(a!)[] outs, Tensor(b!) valid, int[]? windows=None) -> ()"),
@@ -311,6 +320,66 @@ def _lm_information(p3d, point_masks, fmaps, frefs, channels, cameras, ndist, po
     conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale = int(pad), int(loss), float(loss_alpha), float(loss_scale)
     conf.min_valid = int(min_valid)
     _lib.check(L.pxt_lm_information(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), "pxt_lm_information")
+
+
+def _lm_point_report(p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record, pad, loss,
+                     loss_alpha, loss_scale, min_valid, inlier_weights, points, summaries, workspace):
+    L = _lib.lib()
+    K = len(p3d)
+    if not (1 <= K <= _lib.PXT_LM_REPORT_MAX_PROBLEMS):
+        raise _lib.PxtError(f"lm_point_report: {K} problems (1..{_lib.PXT_LM_REPORT_MAX_PROBLEMS})")
+    if any(len(x) != K for x in (point_masks, fmaps, frefs, channels, ndist, poses, inlier_weights, points, summaries)) \
+            or len(cameras) != 10 * K:
+        raise _lib.PxtError("lm_point_report: per problem one mask slot, map, reference table, channel count, ndist, pose, "
+                            "inlier weight, points slot, summary and 10 camera floats")
+    _lib.require_gpu(workspace, "workspace")
+    dev = workspace.device
+    probs = (_lib.LmReportProblem * K)()
+    for k in range(K):
+        pts, fm, fr = _f32c(p3d[k], "p3d"), _f32c(fmaps[k], "fmap"), _f32c(frefs[k], "fref")
+        n = int(pts.shape[0])
+        if fm.dim() != 3 or tuple(pts.shape) != (n, 3) or tuple(fr.shape) != (n, int(fm.shape[2])):
+            raise _lib.PxtError(f"lm_point_report: problem {k}: p3d {tuple(pts.shape)}, fmap {tuple(fm.shape)}, fref "
+                                f"{tuple(fr.shape)}; expected [N, 3], [h, w, cstride], [N, cstride]")
+        mk, out = point_masks[k], points[k]
+        if mk is not None and (mk.dtype != torch.uint8 or not mk.is_contiguous() or mk.numel() != n):
+            raise _lib.PxtError("lm_point_report: point masks are contiguous uint8 [n_points]")
+        if out is not None and (out.dtype != torch.float32 or not out.is_contiguous()
+                                or tuple(out.shape) != (n, _lib.PXT_LM_POINT_RECORD)):
+            raise _lib.PxtError(f"lm_point_report: points of problem {k} are a contiguous float32 [{n}, "
+                                f"{_lib.PXT_LM_POINT_RECORD}] tensor (got {tuple(out.shape)}, {out.dtype})")
+        # what the kernel dereferences must be device memory of one device (a host pointer there is a memory fault,
+        # not an error); the pose and the summary may also be pinned host memory
+        for t, name in ((pts, "p3d"), (fm, "fmap"), (fr, "fref"), (mk, "point_mask"), (out, "points")):
+            if t is None:
+                continue
+            _lib.require_gpu(t, name)
+            if t.device != dev:
+                raise _lib.PxtError(f"lm_point_report: {name} of problem {k} is on {t.device}, the workspace on {dev}")
+        pose, rec = poses[k], summaries[k]
+        need = 16 if pose_is_lm_record else 12
+        if pose.dtype != torch.float32 or not pose.is_contiguous() or pose.numel() < need \
+                or not ((pose.is_cuda and pose.device == dev) or pose.is_pinned()):
+            raise _lib.PxtError(f"lm_point_report: pose {k} needs {need} contiguous float32 values in device or pinned memory")
+        if rec.dtype != torch.float32 or not rec.is_contiguous() or rec.numel() < _lib.PXT_LM_REPORT_SUMMARY \
+                or not ((rec.is_cuda and rec.device == dev) or rec.is_pinned()):
+            raise _lib.PxtError(f"lm_point_report: summary {k} needs {_lib.PXT_LM_REPORT_SUMMARY} contiguous float32 values "
+                                "in device or pinned memory")
+        q = probs[k]
+        q.p3d, q.point_mask, q.n_points = pts.data_ptr(), _lib.dptr(mk), n
+        h, w, cs = (int(x) for x in fm.shape)
+        q.level.fmap, q.level.fref = fm.data_ptr(), fr.data_ptr()
+        q.level.h, q.level.w, q.level.C, q.level.cstride = h, w, int(channels[k]), cs
+        q.level.cam[:] = [float(x) for x in cameras[10 * k:10 * k + 10]]
+        q.level.ndist = int(ndist[k])
+        q.pose, q.pose_is_lm_record, q.inlier_weight = pose.data_ptr(), int(bool(pose_is_lm_record)), float(inlier_weights[k])
+        q.points, q.summary = _lib.dptr(out), rec.data_ptr()
+    if workspace.numel() * workspace.element_size() < int(L.pxt_lm_point_report_workspace_bytes(K)):
+        raise _lib.PxtError("lm_point_report: workspace smaller than pxt_lm_point_report_workspace_bytes(K)")
+    conf = _lib.LmConf()
+    conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale = int(pad), int(loss), float(loss_alpha), float(loss_scale)
+    conf.min_valid = int(min_valid)
+    _lib.check(L.pxt_lm_point_report(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), "pxt_lm_point_report")
 
 
 # ------------------------------------------------------------------------------------ sampling
@@ -669,6 +738,7 @@ _IMPLS = {
     "lm_refine": _lm_refine,
     "lm_refine_batch": _lm_refine_batch,
     "lm_information": _lm_information,
+    "lm_point_report": _lm_point_report,
     "sample_sparse": _sample_sparse,
     "score_pose_hypotheses": _score_pose_hypotheses,
     "unet_forward_batch": _unet_forward_batch,

@@ -379,6 +379,43 @@ class PixTrackOptimizer:
         done.record(torch.cuda.current_stream(p3ds[0].device))
         return PendingInfo(recs[:K], (p3ds, masks, [it["pack"] for it in items], poses, workspace), done)
 
+    @staticmethod
+    def point_report_levels(items: Sequence[dict], conf: _lib.LmConf, workspace: torch.Tensor, pool_key=0) -> "PendingReport":
+        """Enqueue ONE pxt_lm_point_report launch for K problems: ``items[k]`` = dict(p3d, mask, pack, pose) as for
+        information_levels, plus ``inlier_weight`` (default 0.5) and ``points``: None (summary
+        only) or True - a device tensor [N, 8] is then allocated for the point records and kept by the handle.
+        ``.result()`` waits for the K pinned 16-float summaries; the records are recycled as information_levels' are
+        (a ring of two per (K, pool_key): await a launch's result before enqueueing the launch after next)."""
+        K = len(items)
+        assert 1 <= K <= _lib.PXT_LM_REPORT_MAX_PROBLEMS
+        from_lm = isinstance(items[0]["pose"], PendingLM)
+        n_rec = _lib.PXT_LM_REPORT_SUMMARY
+        recs = _pinned_records([n_rec] * K + ([] if from_lm else [16] * K), ("report", pool_key))
+        poses, cams, ndist = [], [], []
+        for k, it in enumerate(items):
+            recs[k][15] = 0.0
+            lp = it["pack"]
+            cams += lp.camera.as10().tolist()
+            ndist.append(int(lp.camera._data.shape[-1] - 6))
+            if from_lm:
+                poses.append(it["pose"].buf)
+            else:
+                T = it["pose"]
+                recs[K + k][:12] = (T.as12() if hasattr(T, "as12") else torch.as_tensor(T)).detach().cpu().reshape(-1).float()
+                poses.append(recs[K + k])
+        p3ds = [it["p3d"].to(torch.float32).contiguous() for it in items]
+        dev = p3ds[0].device
+        masks = [None if it.get("mask") is None else it["mask"].to(dev, torch.uint8).contiguous() for it in items]
+        points = [torch.empty(int(p.shape[0]), _lib.PXT_LM_POINT_RECORD, dtype=torch.float32, device=dev)
+                  if it.get("points") else None for it, p in zip(items, p3ds)]
+        ops.lm_point_report(p3ds, masks, [it["pack"].fmap for it in items], [it["pack"].fref for it in items],
+                            [int(it["pack"].C) for it in items], cams, ndist, poses, from_lm, conf.pad, conf.loss,
+                            conf.loss_alpha, conf.loss_scale, conf.min_valid,
+                            [float(it.get("inlier_weight", 0.5)) for it in items], points, recs[:K], workspace)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        return PendingReport(recs[:K], points, (p3ds, masks, [it["pack"] for it in items], poses, workspace), done)
+
     def run(self, p3D, F_ref, F_query, T_init: Pose, camera: Camera, mask=None, W_ref_query=None):
         """One pyramid level, pixloc calling convention:
         p3D [N,3] (numpy or tensor), F_ref [N,C], F_query [C,h,w], W_ref_query =
@@ -475,6 +512,34 @@ class PendingInfo:
             if not PendingLM.poll:
                 self._done.synchronize()
             while flag[47] == 0.0:  # stored last, with system-scope release
+                spins += 1
+                if spins > 2_000_000 or (spins & 0x3FFF) == 0 and self._done.query():
+                    self._done.synchronize()
+                    break
+            out.append(flag.astype(np.float64))  # (a copy: the pinned record is reused two launches later)
+        self._keep = None
+        self._out = out
+        return out
+
+
+class PendingReport:
+    """Result handle of an enqueued pxt_lm_point_report launch: ``result()`` -> one float64 numpy summary (16) per
+    problem; ``points[k]`` is problem k's device tensor [N, 8] (or None), complete once its summary has arrived."""
+
+    def __init__(self, recs, points, keepalive, done):
+        self.recs, self.points, self._keep, self._done = recs, points, keepalive, done
+        self._out: Optional[List[np.ndarray]] = None
+
+    def result(self) -> List[np.ndarray]:
+        if self._out is not None:  # (the K problems of a batched launch each ask once)
+            return self._out
+        out = []
+        for rec in self.recs:
+            flag = rec.numpy()
+            spins = 0
+            if not PendingLM.poll:
+                self._done.synchronize()
+            while flag[15] == 0.0:  # stored last, with system-scope release
                 spins += 1
                 if spins > 2_000_000 or (spins & 0x3FFF) == 0 and self._done.query():
                     self._done.synchronize()

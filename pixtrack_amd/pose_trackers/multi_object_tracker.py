@@ -35,6 +35,7 @@ import torch
 from .. import _lib
 from ..optimizer import PixTrackOptimizer
 from ..tracker import DebugTracker
+from ..point_report import parse_mode
 from .pixloc_tracker_r9 import PixLocPoseTrackerR9
 
 
@@ -45,6 +46,7 @@ class _Group:
         self.index, self.members, self.stream, self.model = index, members, stream, model
         self.batch_ws: Optional[torch.Tensor] = None
         self.info_ws: Optional[torch.Tensor] = None  # parameter records and partial sums of the step's information launch
+        self.report_ws: Optional[torch.Tensor] = None  # ... and of the step's point-report launch
         self.render_ws: Optional[torch.Tensor] = None  # parameter records of the batched render chain
         self.unet_done: Optional[torch.cuda.Event] = None
         self.pend = None  # what _enqueue left for _finish
@@ -53,15 +55,20 @@ class _Group:
 class MultiObjectTracker:
     def __init__(self, trackers: Sequence[PixLocPoseTrackerR9], lm_workgroups: int = 0, per_image_plan: bool = False,
                  max_unet_batch: int = _lib.PXT_UNET_MAX_BATCH, n_groups: int = 1, batch_renders: Optional[bool] = None,
-                 uncertainty: Optional[bool] = None):
+                 uncertainty: Optional[bool] = None, point_report=None):
         """``uncertainty``: None keeps each tracker's own setting, True / False sets it for all of them (the ``uncertainty``
         option of PixLocPoseTrackerR9): the information problems of a group's step then go out as ONE pxt_lm_information
         launch behind its batched LM launch and its queued renders.
+        ``point_report``: None keeps each tracker's own setting; False / "off", "summary" or "full" sets it for all of
+        them (the ``point_report`` option of PixLocPoseTrackerR9): the report problems of a group's step then go out as
+        ONE pxt_lm_point_report launch, next to the information launch.
         ``n_groups`` > 1: the trackers are dealt to that many groups, each with its own stream, batched UNet pass and
         batched LM launch per step; the groups' UNet passes take turns (an event token), so that one group's MFMA-bound
         UNet pass runs beside the other group's latency-bound renders instead of beside its UNet pass."""
         if not trackers:
             raise ValueError("MultiObjectTracker needs at least one tracker")
+        if point_report is not None:
+            point_report = parse_mode(point_report)  # (ValueError before anything is touched)
         self.trackers: List[PixLocPoseTrackerR9] = list(trackers)
         self.device = self.trackers[0].device
         for tr in self.trackers:
@@ -84,6 +91,9 @@ class MultiObjectTracker:
         if uncertainty is not None:
             for tr in self.trackers:
                 tr.uncertainty = tr.localizer.refiner.information = bool(uncertainty)
+        if point_report is not None:
+            for tr in self.trackers:
+                tr.point_report = tr.localizer.refiner.point_report = point_report
         self.groups: List[_Group] = []
         # a group's queued renders as ONE chain of launches carrying the rays of all its objects (pxt_ngp_render_frame_batch;
         # bit for bit the single renders); PXT_BATCH_RENDERS=0: one chain per object, one after the other
@@ -264,6 +274,17 @@ class MultiObjectTracker:
                                                         grp.info_ws, pool_key=("group", grp.index))
             for i, (x, _h, _rf) in enumerate(asked):
                 x["info"] = (info, i)
+        # ---- the step's point reports (opt-in): ONE launch for every object that asked, next to the information launch
+        asked = [(x, handle, tr.localizer.refiner) for (_k, tr, _p, _r, _d, status, x, handle) in grp.pend
+                 if status == "lm" and tr.localizer.refiner.point_report]
+        if asked:
+            if grp.report_ws is None:
+                need = int(_lib.lib().pxt_lm_point_report_workspace_bytes(_lib.PXT_LM_MAX_BATCH))
+                grp.report_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            report = PixTrackOptimizer.point_report_levels([rf.point_report_item(x, h) for x, h, rf in asked],
+                                                           asked[0][0]["conf"], grp.report_ws, pool_key=("group", grp.index))
+            for i, (x, _h, _rf) in enumerate(asked):
+                x["report"] = (report, i)
 
     def _batched_renders_ahead(self, grp: _Group) -> set:
         """The group's queued renders (behind the batched LM launch, cameras from its epilogue's slots) in one batched
@@ -354,19 +375,9 @@ def parse_config_sh(path) -> dict:
     return out
 
 
-def main(argv=None):
-    """Several objects, one GPU: the reference's tracker command line (pixloc_tracker_r9.py:288-318) once per object, in
-    lock-step.  Every list takes one entry per object; an object's OBJ_AABB / UPRIGHT_REF_IMG come from --config (a
-    reference config/<object>.sh) or from --obj_aabb / --upright_ref_img.  Outputs per object as r9's CLI writes them:
-    <out_dir>/poses.pkl, <out_dir>/trackers.pkl, and the `Cache hits / Done` lines per object."""
+def build_parser():
     import argparse
-    import gc
-    import os
     from pathlib import Path
-
-    import numpy as np
-
-    from .pixloc_tracker_r9 import _dump
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--object_path", type=Path, nargs="+", required=True)
@@ -383,6 +394,26 @@ def main(argv=None):
                     help="UNet activations of every object: fp16 (default, fastest) or fp32 (pixloc's precision)")
     ap.add_argument("--uncertainty", action="store_true",
                     help="add the pose information matrix, covariance and observability of every frame to poses.pkl")
+    ap.add_argument("--point_report", choices=("off", "summary", "full"), default="off",
+                    help="add every frame's valid / inlier point counts and mean robust weight to poses.pkl (summary), and "
+                         "the per-point projections, residuals and weights as well (full)")
+    return ap
+
+
+def main(argv=None):
+    """Several objects, one GPU: the reference's tracker command line (pixloc_tracker_r9.py:288-318) once per object, in
+    lock-step.  Every list takes one entry per object; an object's OBJ_AABB / UPRIGHT_REF_IMG come from --config (a
+    reference config/<object>.sh) or from --obj_aabb / --upright_ref_img.  Outputs per object as r9's CLI writes them:
+    <out_dir>/poses.pkl, <out_dir>/trackers.pkl, and the `Cache hits / Done` lines per object."""
+    import gc
+    import os
+    from pathlib import Path
+
+    import numpy as np
+
+    from .pixloc_tracker_r9 import _dump
+
+    ap = build_parser()
     args = ap.parse_args(argv)
     K = len(args.object_path)
     if len(args.query) != K or len(args.out_dir) != K:
@@ -406,7 +437,7 @@ def main(argv=None):
         trackers.append(PixLocPoseTrackerR9(object_path=str(obj), data_path=str(obj / "pixtrack/pixsfm/dataset"),
                                             eval_path=str(args.out_dir[k]), loc_path=str(obj / "pixtrack/aug_nerf_sfm"),
                                             debug=args.debug, unet_precision=args.unet_precision,
-                                            uncertainty=args.uncertainty))
+                                            uncertainty=args.uncertainty, point_report=args.point_report))
     multi = MultiObjectTracker(trackers, n_groups=args.groups)
     its = [tr.get_query_frame_iterator(q, args.frames if args.frames is not None else np.inf)
            for tr, q in zip(trackers, args.query)]

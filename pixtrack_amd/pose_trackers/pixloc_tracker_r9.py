@@ -30,6 +30,7 @@ from ..ops import ops
 from ..geometry import Camera as PixCamera, Pose
 from ..model3d import Model3D, extract_covisibility
 from ..refiner import Paths, PoseTrackerLocalizer
+from ..point_report import parse_mode
 from ..tracker import DebugTracker
 from ..utils.colmap import ColmapCamera
 from ..utils.ingp_utils import initialize_ingp, load_nerf2sfm, sfm_to_nerf_pose
@@ -49,7 +50,8 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
 
 class PixLocPoseTrackerR9(PoseTracker):
     def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
-                 unet_precision="fp16", relocalizer=None, uncertainty=False, reference_points="sfm"):
+                 unet_precision="fp16", relocalizer=None, uncertainty=False, reference_points="sfm",
+                 point_report=False):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
         synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
         ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet).
@@ -66,7 +68,15 @@ class PixLocPoseTrackerR9(PoseTracker):
         frame's own Depth render (refiner.points_from_render): they cover the visible side, do not change when
         update_reference_ids switches and need no triangulated points.  A frame's history entry then gains
         ``n_reference_points`` and ``reference_point_stride``; nothing on the policy path reads them.  Not combined
-        with ``relocalizer`` or ``uncertainty`` yet (ValueError)."""
+        with ``relocalizer`` or ``uncertainty`` yet (ValueError).
+        ``point_report``: False / "off" (default: nothing changes), "summary" or "full" - every LM launch is followed by
+        one pxt_lm_point_report problem at the pose it returns (its last level), and a frame's history entry gains
+        ``n_valid_points``, ``n_inliers``, ``inlier_ratio``, ``mean_robust_weight`` and ``rejected_points``
+        (point_report.py; None for a frame whose refinement failed); "full" also adds ``point_report``, a dict of numpy
+        arrays per point (p2d, valid, cost, rho, robust_weight, confidence, reject), and fills the DebugTracker's
+        ``p3d`` / ``p3d_ids`` / ``point_report`` at debug >= 2.  Works with both ``reference_points`` settings.  The
+        cost gate, the pose update and ``tracked`` never read any of it."""
+        point_report = parse_mode(point_report)  # (a bad value: ValueError before anything is built)
         self._check_reference_points(reference_points, relocalizer, uncertainty)
         self.reference_points = reference_points
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
@@ -120,6 +130,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         self.testbed = initialize_ingp(snapshot, self._render_aabb(assets), device=self.device)
         self.uncertainty = bool(uncertainty)
         self.localizer.refiner.information = self.uncertainty
+        self.point_report = self.localizer.refiner.point_report = point_report
         self.localizer.refiner.warm_reference_points()  # static per-reference tables, off the frame path
         self.dynamic_id, self.cache_hit, self.cost_threshold, self.camera = None, False, None, None
         self.hits = self.misses = self.relocalization_count = 0
@@ -640,6 +651,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="UNet activations: fp16 (default, fastest) or fp32 (pixloc's precision)")
     parser.add_argument("--uncertainty", action="store_true",
                         help="add the pose information matrix, covariance and observability of every frame to poses.pkl")
+    parser.add_argument("--point_report", choices=("off", "summary", "full"), default="off",
+                        help="add every frame's valid / inlier point counts and mean robust weight to poses.pkl (summary), "
+                             "and the per-point projections, residuals and weights as well (full)")
     parser.add_argument("--reference_points", choices=("sfm", "render"), default="sfm",
                         help="the points a frame is refined on: sfm (default: the SfM points of the nearest mapping image) "
                              "or render (a lattice of the frame's own depth render, back-projected)")
@@ -662,7 +676,8 @@ def main(argv=None):
     tracker = PixLocPoseTrackerR9(object_path=str(args.object_path), data_path=str(data_path),
                                   eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
                                   unet_precision=args.unet_precision, relocalizer=args.relocalize,
-                                  uncertainty=args.uncertainty, reference_points=args.reference_points)
+                                  uncertainty=args.uncertainty, reference_points=args.reference_points,
+                                  point_report=args.point_report)
     import gc
 
     gc.collect()

@@ -58,11 +58,13 @@ class GTFrameIterator:
 
 class PixLocPoseTrackerYCB(PixLocPoseTrackerR9):
     def __init__(self, data_path, loc_path, eval_path, object_path, debug=False, device=None, assets=None,
-                 ycb_root=None, unet_precision="fp16", uncertainty=False, reference_points="sfm"):
+                 ycb_root=None, unet_precision="fp16", uncertainty=False, reference_points="sfm",
+                 point_report=False):
         self.object_path = object_path
         self.ycb_root = Path(ycb_root or os.environ.get("YCB_ROOT", "/data/ycb/"))
         super().__init__(object_path, data_path, loc_path, eval_path, debug=int(debug), device=device, assets=assets,
-                         unet_precision=unet_precision, uncertainty=uncertainty, reference_points=reference_points)
+                         unet_precision=unet_precision, uncertainty=uncertainty, reference_points=reference_points,
+                         point_report=point_report)
         self.reference_scale = 0.3
         self.localizer.refiner.reference_scale = self.reference_scale
         self.localizer.refiner.conf.multiscale = [1]
@@ -178,13 +180,17 @@ def main(argv=None):
     parser.add_argument("--pixloc_pickles", action="store_true")
     parser.add_argument("--uncertainty", action="store_true",
                         help="add the pose information matrix, covariance and observability of every frame to poses.pkl")
+    parser.add_argument("--point_report", choices=("off", "summary", "full"), default="off",
+                        help="add every frame's valid / inlier point counts and mean robust weight to poses.pkl (summary), "
+                             "and the per-point projections, residuals and weights as well (full)")
     args = parser.parse_args(argv)
     obj_path = args.object_path
     eval_path = Path(args.out_dir)
     os.makedirs(eval_path, exist_ok=True)
     tracker = PixLocPoseTrackerYCB(data_path=str(obj_path / "pixtrack/pixsfm/dataset"), eval_path=str(eval_path),
                                    loc_path=str(obj_path / "pixtrack/aug_nerf_sfm"), object_path=obj_path,
-                                   debug=args.debug, ycb_root=args.ycb_root, uncertainty=args.uncertainty)
+                                   debug=args.debug, ycb_root=args.ycb_root, uncertainty=args.uncertainty,
+                                   point_report=args.point_report)
     tracker.run(args.query, max_frames=args.frames)
     print("Relocalization count: ", tracker.relocalization_count)
     tracker.save_poses(args.pixloc_pickles)

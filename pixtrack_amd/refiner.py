@@ -89,6 +89,9 @@ class PoseTrackerRefiner:
         reference_points_max=2048,       # point slots of a "render" frame (the benchmark's LM problem size)
         reference_points_min_alpha=0.5,  # a pixel's base test: alpha >= this and depth > 0 ...
         reference_points_erode=1,        # ... on the whole (2 erode + 1)^2 square around it (keeps silhouette pixels out)
+        # the opt-in point report counts a valid point as an inlier when its robust weight rho' is at least this: for the
+        # default loss the residual at which the loss has halved the point's weight - a convention, not a tuned value
+        point_report_inlier_weight=0.5,
         filter_covisibility=False,
         do_pose_approximation=False,
         do_inlier_ranking=False,
@@ -125,6 +128,13 @@ class PoseTrackerRefiner:
         self.information = False
         self._info_ws: Optional[torch.Tensor] = None
         self.last_information = None  # {"record", "p3d", "mask", "pack", "level"} of the last launch (option on only)
+        # Opt-in per-point residual report (point_report.py): "summary" queues one pxt_lm_point_report problem behind
+        # every LM launch (and behind the information launch, if that is on) - the launch's last level, at the pose the
+        # LM kernel leaves in its record - and adds SUMMARY_KEYS to the result dictionary; "full" also keeps the [N, 8]
+        # point records and adds ``point_report``.  Nothing on the tracking path reads them.
+        self.point_report = False
+        self._report_ws: Optional[torch.Tensor] = None
+        self.last_point_report = None  # {"summary", "points" (device [N, 8] or None), "level"} of the last launch
 
     # ---- logging hooks (pixloc BaseRefiner) -----------------------------------
     def log_dense(self, **kwargs):
@@ -465,10 +475,55 @@ class PoseTrackerRefiner:
             return self._no_information()
         return frame_entries(rec, int(pack.C), level, Pose(res.T.as12().double()), self._host_points(prob["ref"]))
 
+    # ---- per-point residual report (opt-in) ----------------------------------------------
+    def _no_point_report(self) -> Dict:
+        """What a result that ran no (successful) refinement carries for the report keys: None with the option on,
+        nothing with it off."""
+        from .point_report import frame_entries
+
+        return frame_entries(None, None, self.point_report == "full") if self.point_report else {}
+
+    def point_report_item(self, prob: Dict, pending) -> Dict:
+        """The report problem of one refinement: its last level in execution order, the pose read from the LM's own
+        record on the device, the points and mask the launch itself used (SfM table or the frame's lattice slots)."""
+        ref = prob["ref"]
+        return {"p3d": ref.p3d, "mask": ref.valid, "pack": prob["packs"][-1], "pose": pending,
+                "points": self.point_report == "full", "inlier_weight": float(self.conf.point_report_inlier_weight)}
+
+    def enqueue_point_report(self, prob: Dict, pending) -> None:
+        if self._report_ws is None:
+            self._report_ws = torch.zeros(int(_lib.lib().pxt_lm_point_report_workspace_bytes(1)), dtype=torch.uint8,
+                                          device=self.device)
+        handle = PixTrackOptimizer.point_report_levels([self.point_report_item(prob, pending)], prob["conf"],
+                                                       self._report_ws, pool_key=id(self))
+        prob["report"] = (handle, 0)
+
+    def _collect_point_report(self, prob: Dict, res) -> Dict:
+        """The report keys of one finished refinement (the summary is awaited here, before the LM's pinned record can be
+        recycled: the device reads the pose out of it); "full" downloads the point records and hands the point set to
+        the tracker (DebugTracker.log_point_report: p3d, p3d_ids, point_report at debug >= 2)."""
+        from .point_report import decode_points, frame_entries
+
+        report = prob.pop("report", None)
+        if report is None:
+            return self._no_point_report()
+        handle, index = report
+        summary = handle.result()[index]
+        points = handle.points[index]
+        self.last_point_report = {"summary": summary, "points": points, "level": prob["order"][-1]}
+        if res.failed or summary[15] == -1.0:
+            return self._no_point_report()
+        full = self.point_report == "full"
+        decoded = decode_points(points) if full and points is not None else None
+        if decoded is not None and self.tracker is not None and hasattr(self.tracker, "log_point_report"):
+            ref = prob["ref"]
+            self.tracker.log_point_report(p3d=ref.p3d.detach().cpu().numpy(), p3d_ids=list(ref.p3dids_all), report=decoded)
+        return frame_entries(summary, decoded, full)
+
     # ---- refinement ------------------------------------------------------------------
     def refine(self, qname: str, qcamera: Camera, pose_init: Pose, dbids: List[int], loc=None,
                image_query=None, pose: Optional[Pose] = None, reference_images=None, dynamic_id=None) -> Dict:
-        fail = {"success": False, "T_init": pose_init, "dbids": dbids, **self._no_information()}
+        fail = {"success": False, "T_init": pose_init, "dbids": dbids, **self._no_information(), **self._no_point_report()}
         # (points of the frame's render are counted on the device: too few of them fail the LM's own min_valid rule)
         if not self.render_points and len(self._points_of(dbids)[0]) < self.conf.min_points_opt:
             logger.debug("Not enough valid 3D points to optimize")
@@ -495,7 +550,7 @@ class PoseTrackerRefiner:
         else:
             features_dict = self.features_dicts[dynamic_id]["features"]
         self.last_lm = []
-        ret = {"success": False, "T_init": T_init, **self._no_information()}
+        ret = {"success": False, "T_init": T_init, **self._no_information(), **self._no_point_report()}
         for image_scale in multiscales:
             ref = features_dict[str(image_scale)]
             maps_q, scales_q = self.dense_feature_extraction(image_query, qname, image_scale, mask=self.query_mask,
@@ -527,6 +582,8 @@ class PoseTrackerRefiner:
             hook(pending)
         if self.information:  # (after the render-ahead chain: the next frame's render does not wait for it)
             self.enqueue_information(prob, pending)
+        if self.point_report:  # (behind the information launch, if any)
+            self.enqueue_point_report(prob, pending)
         return self.lm_finish(prob, pending.result())
 
     def lm_problem(self, features_query, scales_query, qcamera: Camera, T_init: Pose, ref: SparseReferenceFeatures,
@@ -565,7 +622,7 @@ class PoseTrackerRefiner:
             T_level = Pose(res.log[k, res.iters[k] - 1, 8:20].clone())
             self.log_optim(i=k, T_opt=T_level, fail=res.failed, level=level, p3d=None, p3d_ids=ref.p3dids_all,
                            T_init=T_init, camera=packs[k].camera)
-        ret = {"T_init": T_init, **self._collect_information(prob, res)}
+        ret = {"T_init": T_init, **self._collect_information(prob, res), **self._collect_point_report(prob, res)}
         if res.failed:
             return {**ret, "success": False}
         T_opt = Pose(res.T.as12().double())  # already on the host (pixloc: T_opt.cpu().double())
@@ -583,7 +640,7 @@ class PoseTrackerRefiner:
         """refine() -> refine_query_pose() of ONE image scale up to, but without, the LM launch: returns
         ("done", ret) when the reference's early exits apply (too few points), else ("lm", problem) - the problem goes
         into a batched launch and comes back through finish_refine.  Same calls in the same order as refine()."""
-        fail = {"success": False, "T_init": pose_init, "dbids": dbids, **self._no_information()}
+        fail = {"success": False, "T_init": pose_init, "dbids": dbids, **self._no_information(), **self._no_point_report()}
         p3dids, _ = self._points_of(dbids)
         if len(p3dids) < self.conf.min_points_opt:
             logger.debug("Not enough valid 3D points to optimize")

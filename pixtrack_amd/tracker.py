@@ -52,6 +52,8 @@ class BaseTracker:
 class DebugTracker(BaseTracker):
     """debug >= 1 keeps the iteration record, debug >= 2 also the dense maps and the point set."""
 
+    point_report = None  # debug >= 2 and the refiner's point_report="full": the decoded per-point arrays (point_report.py)
+
     def __init__(self, refiner, debug=0):
         self.debug = int(debug)
         self.costs = []      # one list per optimised level: cost before each update
@@ -99,6 +101,12 @@ class DebugTracker(BaseTracker):
     def log_optim_done(self, *, p3d, p3d_ids, **_unused) -> None:
         if self.debug >= 2:
             self.p3d, self.p3d_ids = p3d, p3d_ids
+
+    def log_point_report(self, *, p3d, p3d_ids, report, **_unused) -> None:
+        """The point set a refinement ran on and its per-point report (refiner.point_report == "full"): on the HIP path
+        this is what fills ``p3d`` / ``p3d_ids``, which the reference keeps at debug >= 2 (tracker.py:26-30)."""
+        if self.debug >= 2:
+            self.p3d, self.p3d_ids, self.point_report = p3d, p3d_ids, report
 
     def __getstate__(self):
         # trackers.pkl must not drag the refiner (device buffers, native handles) along
