@@ -642,6 +642,34 @@ int pxt_points_from_depth(const float* depth, int32_t width, int32_t height, con
                           float depth_scale, float min_alpha, int32_t erode, int32_t n_max, float* p3d,
                           uint8_t* slot_valid, int32_t* record, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Pose-error evaluation (opt-in; csrc/pxt_eval.hip).
+ *
+ * Replaces, for a whole run in one call, the per-frame Python loop of the reference's notebooks/GetMetrics.ipynb
+ * (`get_metrics`: mean one-to-one vertex distance, ADD) and pixtrack_amd/evaluation.py's adds_distance (ADD-S, one frame
+ * at a time, O(V^2) numpy): F frames x V model points, F * V^2 distance evaluations for ADD-S.
+ *   vertices  [V][3] float32, object frame, CENTRED by the caller (centroid subtracted).
+ *   rel_poses [F][12]: R row-major then t of T_rel = T_gt^-1 T_est expressed for the centred vertices
+ *       (evaluation.relative_poses forms it in float64 and rounds once).  In the ground-truth object frame
+ *       |T_est v_j - T_gt v_i| = |T_rel v_j - v_i|, so the kernel works on object-sized numbers only.
+ *   record of frame f (PXT_POSE_ERR_RECORD = 8 floats):
+ *       [0] ADD   = mean_i |T_rel v_i - v_i|               [1] max_i of that distance
+ *       [2] ADD-S = mean_i min_j |T_rel v_j - v_i|         [3] max_i of that minimum
+ *           (adds_distance's direction: for every ground-truth point the nearest estimated point)
+ *       [4] V as float      [5], [6] 0
+ *       [7] status: 1.0 ok; -1.0 when the frame's pose holds a non-finite value - then ONLY [7] is written
+ *       want_adds == 0: ADD only (O(V) per frame); [2] and [3] are written as 0, [0] and [1] keep their bits.
+ *   Bounds: 1 <= V <= 2^20, 1 <= F <= 65535, every pointer 4-byte aligned; anything else is PXT_E_ARG.
+ *   Deterministic: fixed-order reductions (wave butterfly, LDS, partials in the workspace folded in block order by a
+ *   second launch), no atomics: a frame's record depends on its own pose and the vertex set only - not on F, on the
+ *   frame's index or on the other frames.
+ *   workspace: device memory of pxt_pose_errors_workspace_bytes(F, V) bytes (< 0: unsupported sizes); one workspace
+ *   serves one call at a time.  Two launches on `stream`, no host synchronisation. */
+#define PXT_POSE_ERR_RECORD 8
+int64_t pxt_pose_errors_workspace_bytes(int32_t n_frames, int32_t n_vertices);
+int pxt_pose_errors(const float* vertices, int32_t n_vertices, const float* rel_poses, int32_t n_frames,
+                    int32_t want_adds, float* records, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ PXT_LM_INFO_MAX_PROBLEMS = 64
 PXT_LM_POINT_RECORD = 8
 PXT_LM_REPORT_SUMMARY = 16
 PXT_LM_REPORT_MAX_PROBLEMS = 64
+PXT_POSE_ERR_RECORD = 8
 
 
 class PxtError(RuntimeError):
@@ -234,6 +235,8 @@ PROTOTYPES = {
     "pxt_points_from_depth_workspace_bytes": (_I64, [_I32, _I32]),
     "pxt_points_from_depth": (C.c_int, [_VP, _I32, _I32, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, _I32, _I32,
                                         _VP, _VP, _VP, _VP, _VP]),
+    "pxt_pose_errors_workspace_bytes": (_I64, [_I32, _I32]),
+    "pxt_pose_errors": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _VP, _VP]),
 }
 
 

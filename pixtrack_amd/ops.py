@@ -19,6 +19,8 @@ Reference call sites the ops stand in for:
   resize_linear        pixloc resize(image, size, max, "linear") (feature_extractor.py:45)
   points_from_depth    (opt-in) stands in for the SfM points of the nearest mapping image as the points a frame is
                        refined on (pixloc_pose_refiners.py:282-290): a lattice of the Depth render, back-projected
+  pose_errors          (opt-in) ADD / ADD-S of F frames against ground truth in one call: the per-frame loop of
+                       notebooks/GetMetrics.ipynb (get_metrics) and evaluation.adds_distance
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -106,6 +108,10 @@ SCHEMAS = {
     "points_from_depth": (
         "(Tensor depth, float[] xform, float focal, float depth_scale, float min_alpha, int erode, int n_max, "
         "Tensor(a!) p3d, Tensor(b!) slot_valid, Tensor(c!) record, Tensor(d!) workspace) -> ()"),
+    # centred vertices [V, 3], rel_poses [F, 12] (evaluation.relative_poses) -> records [F, 8]: ADD, its max, ADD-S, its
+    # max, V, 0, 0, status (pxt_pose_errors); workspace: uint8, pxt_pose_errors_workspace_bytes(F, V)
+    "pose_errors": (
+        "(Tensor vertices, Tensor rel_poses, bool want_adds, Tensor(a!) records, Tensor(b!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -733,7 +739,33 @@ def _points_from_depth(depth, xform, focal, depth_scale, min_alpha, erode, n_max
                                        workspace.data_ptr(), _stream(depth)), "pxt_points_from_depth")
 
 
+def _pose_errors(vertices, rel_poses, want_adds, records, workspace):
+    L = _lib.lib()
+    _f32c(vertices, "vertices")
+    _f32c(rel_poses, "rel_poses")
+    _f32c(records, "records")
+    if vertices.dim() != 2 or int(vertices.shape[1]) != 3 or rel_poses.dim() != 2 or int(rel_poses.shape[1]) != 12:
+        raise _lib.PxtError(f"pose_errors: vertices {tuple(vertices.shape)} / rel_poses {tuple(rel_poses.shape)}, expected "
+                            "[V, 3] / [F, 12]")
+    V, F = int(vertices.shape[0]), int(rel_poses.shape[0])
+    if tuple(records.shape) != (F, _lib.PXT_POSE_ERR_RECORD):
+        raise _lib.PxtError(f"pose_errors: records is {tuple(records.shape)}, expected {(F, _lib.PXT_POSE_ERR_RECORD)}")
+    need = int(L.pxt_pose_errors_workspace_bytes(F, V))
+    if need <= 0:
+        raise _lib.PxtError(f"pose_errors: {F} frames x {V} vertices is not supported (1..65535 frames, 1..2^20 vertices)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"pose_errors: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    for t, name in ((vertices, "vertices"), (rel_poses, "rel_poses"), (records, "records"), (workspace, "workspace")):
+        _lib.require_gpu(t, name)
+        if t.device != vertices.device:
+            raise _lib.PxtError(f"pose_errors: {name} is on {t.device}, the vertices on {vertices.device}")
+    _lib.check(L.pxt_pose_errors(vertices.data_ptr(), V, rel_poses.data_ptr(), F, int(bool(want_adds)), records.data_ptr(),
+                                 workspace.data_ptr(), _stream(vertices)), "pxt_pose_errors")
+
+
 _IMPLS = {
+    "pose_errors": _pose_errors,
     "points_from_depth": _points_from_depth,
     "lm_refine": _lm_refine,
     "lm_refine_batch": _lm_refine_batch,
