@@ -591,12 +591,15 @@ int pxt_ngp_query(pxt_ngp* ctx, const float* pos, const float* dir, int32_t n, f
  * Small image ops on the path (host cv2/numpy calls in the reference).
  * ---------------------------------------------------------------------- */
 /* get_mask (pixloc_tracker_r9.py:207-214): depth RGBA -> uint8((d*255)) != 0 ->
- * erode 5x5 x n_erode -> dilate 5x5 x n_dilate.  tmp: 2*H*W bytes. */
+ * erode 5x5 x n_erode -> dilate 5x5 x n_dilate.  tmp: 2*H*W bytes.
+ * mask_out is a dense uint8 [H][W] (row stride W).  When W % 4 == 0 it must be 4-byte aligned: the single-pass
+ * kernel (2 * (n_erode + n_dilate) <= 16) then stores four mask bytes as one dword.  No requirement otherwise. */
 int pxt_depth_mask(const float* depth_rgba, int32_t H, int32_t W, int32_t n_erode,
                    int32_t n_dilate, uint8_t* mask_out, uint8_t* tmp, void* stream);
 /* The same mask from the `uint8(depth * 255) != 0` byte plane a render wrote itself (pxt_ngp_render_frame's depth_nz):
  * bit for bit pxt_depth_mask of that render's float depth image.  tmp (2*H*W bytes) is only needed when
- * 2 * (n_erode + n_dilate) > 16 and may be NULL otherwise. */
+ * 2 * (n_erode + n_dilate) > 16 and may be NULL otherwise.  mask_out: dense uint8 [H][W], 4-byte aligned when
+ * W % 4 == 0 (as for pxt_depth_mask). */
 int pxt_depth_mask_plane(const uint8_t* depth_nz, int32_t H, int32_t W, int32_t n_erode, int32_t n_dilate,
                          uint8_t* mask_out, uint8_t* tmp, void* stream);
 /* get_nerf_image tail (run_vis_on_poses.py:52-54): alpha threshold, *255, ->uint8. */

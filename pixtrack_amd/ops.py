@@ -649,12 +649,23 @@ def _ngp_render_frame_batch(ctxs, views, sizes, spp, modes, camera_from_slot, rg
 
 
 # ----------------------------------------------------------------------------------- image ops
+def _mask_out(mask, H, W, like, what):
+    """The output of the two mask entries: the kernels write it as a dense [H][W] byte plane on the input's device, and
+    store four bytes as one dword when W % 4 == 0 (include/pixtrack_hip.h)."""
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W):
+        raise _lib.PxtError(f"{what}: mask is uint8 [H, W]")
+    if not mask.is_contiguous() or mask.device != like.device:
+        raise _lib.PxtError(f"{what}: mask is contiguous and on the input's device (got strides {tuple(mask.stride())}, "
+                            f"{mask.device} vs {like.device})")
+    if W % 4 == 0 and mask.data_ptr() % 4 != 0:
+        raise _lib.PxtError(f"{what}: mask must be 4-byte aligned when W % 4 == 0 (W = {W})")
+
+
 def _depth_mask_plane(depth_nz, n_erode, n_dilate, mask):
     if depth_nz.dtype != torch.uint8 or depth_nz.dim() != 2 or not depth_nz.is_contiguous():
         raise _lib.PxtError("depth_mask_plane: depth_nz is a contiguous uint8 [H, W]")
     H, W = int(depth_nz.shape[0]), int(depth_nz.shape[1])
-    if mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W):
-        raise _lib.PxtError("depth_mask_plane: mask is uint8 [H, W]")
+    _mask_out(mask, H, W, depth_nz, "depth_mask_plane")
     tmp = None
     if 2 * (int(n_erode) + int(n_dilate)) > 16:
         tmp = torch.empty(2 * H * W, dtype=torch.uint8, device=depth_nz.device)
@@ -662,12 +673,12 @@ def _depth_mask_plane(depth_nz, n_erode, n_dilate, mask):
                                                _lib.dptr(tmp), _stream(depth_nz)), "pxt_depth_mask_plane")
 
 
-
 def _depth_mask(depth_rgba, n_erode, n_dilate, mask, scratch):
     _f32c(depth_rgba, "depth_rgba")
     H, W = int(depth_rgba.shape[0]), int(depth_rgba.shape[1])
-    if mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or scratch.numel() < 2 * H * W:
-        raise _lib.PxtError("depth_mask: mask is uint8 [H, W], scratch holds 2*H*W bytes")
+    _mask_out(mask, H, W, depth_rgba, "depth_mask")
+    if scratch.numel() < 2 * H * W:
+        raise _lib.PxtError("depth_mask: scratch holds 2*H*W bytes")
     _lib.check(_lib.lib().pxt_depth_mask(depth_rgba.data_ptr(), H, W, int(n_erode), int(n_dilate), mask.data_ptr(),
                                          scratch.data_ptr(), _stream(depth_rgba)), "pxt_depth_mask")
 

@@ -49,6 +49,35 @@ def test_entry_points_reject_bad_arguments(device):
         _lib.check(-1, "probe")
 
 
+def test_mask_ops_reject_outputs_the_kernels_cannot_write(device):
+    """The mask kernels write a dense [H][W] byte plane, four bytes per store when W % 4 == 0 (include/pixtrack_hip.h):
+    a strided view, a host tensor or - at such a W - a misaligned one is an error, and nothing is written."""
+    from pixtrack_amd.ops import ops
+
+    H, W = 8, 12
+    nz = torch.ones(H, W, dtype=torch.uint8, device=device)
+    depth = torch.ones(H, W, 4, device=device)
+    scratch = torch.empty(2 * H * W, dtype=torch.uint8, device=device)
+    wide = torch.full((H, 2 * W), 7, dtype=torch.uint8, device=device)
+    flat = torch.full((H * W + 4,), 7, dtype=torch.uint8, device=device)
+    tall = torch.full((W, H), 7, dtype=torch.uint8, device=device)
+    bad = {"strided": wide[:, :W], "transposed": tall.t(), "host": torch.full((H, W), 7, dtype=torch.uint8),
+           "misaligned": flat[1:1 + H * W].view(H, W), "wrong shape": flat[:H * W].view(W, H),
+           "wrong dtype": torch.zeros(H, W, dtype=torch.int8, device=device)}
+    assert bad["misaligned"].data_ptr() % 4 == 1 and bad["misaligned"].is_contiguous()
+    for name, mask in bad.items():
+        with pytest.raises(_lib.PxtError):
+            ops.depth_mask_plane(nz, 1, 1, mask)
+        with pytest.raises(_lib.PxtError):
+            ops.depth_mask(depth, 1, 1, mask, scratch)
+    with pytest.raises(_lib.PxtError):  # the float entry's scratch holds 2 * H * W bytes
+        ops.depth_mask(depth, 1, 1, flat[:H * W].view(H, W), scratch[:H * W])
+    torch.cuda.synchronize()
+    assert bool((wide == 7).all()) and bool((flat == 7).all()) and bool((tall == 7).all())
+    ops.depth_mask_plane(nz, 1, 1, flat[4:4 + H * W].view(H, W))  # aligned: runs, and an all-lit plane stays all lit
+    assert bool((flat[4:] == 1).all()) and bool((flat[:4] == 7).all())
+
+
 def test_unet_rejects_images_it_cannot_encode(device):
     net = UNet(make_synthetic_unet_weights(1), device)
     with pytest.raises(_lib.PxtError):  # 8 px: the fourth pooling would have nothing left

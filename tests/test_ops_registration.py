@@ -27,3 +27,19 @@ def test_schemas_are_out_variants_and_cuda_only():
     with pytest.raises(NotImplementedError):
         torch.ops.pixtrack.depth_mask(torch.zeros(4, 4, 4), 1, 5, torch.zeros(4, 4, dtype=torch.uint8),
                                       torch.zeros(32, dtype=torch.uint8))
+
+
+def test_mask_ops_check_their_output_before_any_launch():
+    """The op bodies refuse a mask the kernels would write as if it were dense and aligned (a strided view; a
+    misaligned one when W % 4 == 0) before they touch the native library - checked here on host tensors, directly."""
+    H, W = 8, 12
+    nz = torch.ones(H, W, dtype=torch.uint8)
+    wide = torch.zeros(H, 2 * W, dtype=torch.uint8)
+    flat = torch.zeros(H * W + 4, dtype=torch.uint8)
+    assert flat.data_ptr() % 4 == 0
+    for mask in (wide[:, :W], flat[1:1 + H * W].view(H, W), flat[:H * W].view(W, H)):
+        with pytest.raises(_lib.PxtError):
+            ops._depth_mask_plane(nz, 1, 5, mask)
+        with pytest.raises(_lib.PxtError):
+            ops._depth_mask(torch.ones(H, W, 4), 1, 5, mask, torch.zeros(2 * H * W, dtype=torch.uint8))
+    assert not wide.any() and not flat.any()
