@@ -9,35 +9,18 @@
 // summary per problem.  Validity, projection, the 2 x 2 bilinear taps of the centre sample (PXT_LM_POINT_CH_COST: only
 // the cost is needed - no map gradients, no Jacobian), w_unc = conf_query * conf_ref and rho / rho' are the LM's own.
 //
-// Mapping (pxt_lm_info.hip's, which see for the reasons)
-//  * A point is owned by a lane GROUP as in the LM (4 consecutive channels per lane, dwordx4 texel reads: 32 lanes per
-//    point for C > 32, 8 otherwise); TWO points are in flight per group.
-//  * The points of ONE problem are dealt round-robin to the groups of n_wgs workgroups (blockIdx.x), the problems are
-//    blockIdx.y.  n_wgs depends on the problem's n_points and C only, so a problem's summation order does not depend on
-//    what else is in the launch.
+// The mapping of points to lanes and workgroups, the folds, the loads and the launch are the evaluation frame's
+// (pxt_lm_eval.h, which see for the reasons).  This kernel's own:
 //  * A point's record is 32 contiguous bytes: the group's lane 0 stores words 0..3, lane 1 words 4..7 (one dwordx4
 //    each; every lane of the group holds the reduced values).  Plain vector stores.
-//  * The group leaders' 8 sums are folded in a fixed order through LDS; across a problem's workgroups the partials go to
-//    the workspace and the fold kernel (one wave per problem) adds them in workgroup order and writes the summary, word
-//    15 last.  No atomics anywhere.  (The counts are sums of 1.f: exact below 2^24 points, which the entry point bounds.)
-//  * The parameter record, the pose and the LM record's status words are read through vector loads: the pose may have
-//    been written by the kernel just ahead in the stream.
-#include "pxt_common.h"
-#include "pxt_lm_point.h"
-
-#include <algorithm>
+//  * The group leaders fold 8 sums.  (The counts are sums of 1.f: exact below 2^24 points, which the entry point bounds.)
+#include "pxt_lm_eval.h"
 
 namespace pxt {
 namespace {
 
-constexpr int kRepBlock = 256;
-constexpr int kRepWaves = kRepBlock / PXT_WAVE;
-constexpr int kRepMaxGroups = kRepBlock / 8;  // groups per workgroup at 8 lanes per point
-constexpr int kRepMaxWgs = 128;               // workgroups per problem, at most
-constexpr int kRepPointsPerGroup = 4;         // target; more when n_wgs is capped
-constexpr int kRepAcc = 8;                    // floats per partial: words 0..7 of the summary
-constexpr int kRepGrpStride = 9;              // padded: leaders of one wave hit distinct LDS banks
-constexpr int kRepArgProblems = 2;            // parameter records that travel as kernel arguments
+constexpr int kRepAcc = 8;        // floats per partial: words 0..7 of the summary
+constexpr int kRepGrpStride = 9;  // padded: leaders of one wave hit distinct LDS banks
 
 struct RepParams {  // 144 bytes
   const float* p3d;
@@ -46,7 +29,7 @@ struct RepParams {  // 144 bytes
   const float* fref;
   const float* pose;
   float* points;
-  float* summary;
+  float* out;  // the summary
   int n, h, w, C, cs, ndist, pose_is_record, n_wgs;
   float inlier_weight;
   float cam[10];
@@ -54,54 +37,12 @@ struct RepParams {  // 144 bytes
 };
 static_assert(sizeof(RepParams) == 144, "parameter records are read as aligned vectors");
 
-struct RepArgs {
-  RepParams p[kRepArgProblems];
-};
-
-struct RepConf {
-  int pad, loss, min_valid;
-  float loss_alpha, loss_scale;
-};
-
 // What a point needs between its projection and its arithmetic.
-struct RepPoint {
+struct RepPoint : EvalPoint<2, 0> {
   bool valid, live;  // live: the point exists (i < N)
-  int n;             // clamped into the bank: an invalid point's loads stay in bounds and are discarded
   int i;
   float code, u, v;
-  float w00, w10, w01, w11;
-  unsigned xo[2], yo[2];  // BYTE offsets of the 2 columns / rows of the taps, clamped into the map
-  int xin, yin;           // bit k: column / row k lies inside the map (outside counts as zero: grid_sample 'zeros')
-  __device__ __forceinline__ float in(int r, int c) const { return ((yin >> r) & (xin >> c) & 1) ? 1.f : 0.f; }
 };
-
-typedef const __attribute__((address_space(1))) char* RepGlobal;
-typedef float RepVec4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 rep_texel(const float* base, unsigned byte_offset) {
-  const RepVec4 v = *(const __attribute__((address_space(1))) RepVec4*)((RepGlobal)base + byte_offset);
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ float rep_word(const float* base, unsigned byte_offset) {
-  return *(const __attribute__((address_space(1))) float*)((RepGlobal)base + byte_offset);
-}
-
-__device__ inline const RepParams* rep_params(const RepParams* ws_params, int from_args, int prob) {
-  const RepParams* base = from_args ? (const RepParams*)__builtin_amdgcn_kernarg_segment_ptr() : ws_params;
-  return vector_pointer(base + prob);
-}
-
-// -> false when the problem is skipped (its LM record reports failed / a status).
-__device__ __forceinline__ bool rep_load_pose(const RepParams* q, float* T) {
-  const float* pose = vector_pointer(q->pose);
-  load_pose12(pose, T);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) T[i] = uniform(T[i]);
-  if (uniform(q->pose_is_record)) {
-    const float4 st = ((const float4*)pose)[3];  // failed, status, total iterations, completion word
-    if (uniform(st.x) != 0.f || uniform(st.y) != 0.f) return false;
-  }
-  return true;
-}
 
 // project_point's own "in front of the camera" and "inside the distortion model's range" tests, for the reject code
 // (validity itself is point_in_window's).
@@ -118,35 +59,18 @@ __device__ inline bool rep_projectable(const Cam& c, float x, float y, float z) 
   return r2 < fabsf(limit);
 }
 
-__global__ __launch_bounds__(kRepBlock) void lm_report_points_kernel(const RepArgs args, const RepParams* ws_params,
-                                                                     float* partials, const RepConf cf,
-                                                                     const int from_args) {
-  __shared__ float part[kRepMaxGroups * kRepGrpStride];
+__global__ __launch_bounds__(kEvalBlock) void lm_report_points_kernel(const EvalArgs<RepParams> args,
+                                                                      const RepParams* ws_params, float* partials,
+                                                                      const EvalConf cf, const int from_args) {
+  __shared__ float part[kEvalMaxGroups * kRepGrpStride];
   const int prob = blockIdx.y, b = blockIdx.x;
-  const RepParams* q = rep_params(ws_params, from_args, prob);
+  const RepParams* q = eval_params(ws_params, from_args, prob);
   const int n_wgs = uniform(q->n_wgs);
   if (b >= n_wgs) return;  // (workgroup-uniform)
   float T[12];
-  if (!rep_load_pose(q, T)) return;  // skipped: the fold kernel marks the summary
+  if (!eval_load_pose(q, T)) return;  // skipped: the fold kernel marks the summary
 
-  const int N = uniform(q->n), W = uniform(q->w), H = uniform(q->h), C = uniform(q->C), cs = uniform(q->cs);
-  const bool wide = C > 32;
-  const int LG = wide ? 32 : 8;
-  const int GPW = PXT_WAVE / LG, G = kRepWaves * GPW;  // groups per wave / per workgroup
-  const int lane = threadIdx.x & (PXT_WAVE - 1);
-  const int sub = lane & (LG - 1);
-  const int grp = (threadIdx.x / PXT_WAVE) * GPW + lane / LG;
-  float c10[10];
-  {
-    const float* c = q->cam;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) c10[i] = uniform(c[i]);
-  }
-  const Cam cam = make_cam(c10, uniform(q->ndist));
-  const float* p3d = uniform(q->p3d);
-  const uint8_t* mask = uniform(q->mask);
-  const float* fmap = uniform(q->fmap);
-  const float* fref = uniform(q->fref);
+  PXT_EVAL_LANES(q);  // declares N, W, H, C, cs, wide, LG, G, sub, grp, cam, p3d, mask, fmap, fref
   float* points = uniform(q->points);
   const float inlier_weight = uniform(q->inlier_weight);
   const float pad = (float)cf.pad;
@@ -167,8 +91,8 @@ __global__ __launch_bounds__(kRepBlock) void lm_report_points_kernel(const RepAr
       p.i = i0 + j * TG;
       p.live = p.i < N;
       p.n = min(p.i, N - 1);
-      const float X = rep_word(p3d, 12u * (unsigned)p.n), Y = rep_word(p3d, 12u * (unsigned)p.n + 4u),
-                  Z = rep_word(p3d, 12u * (unsigned)p.n + 8u);
+      const float X = eval_word(p3d, 12u * (unsigned)p.n), Y = eval_word(p3d, 12u * (unsigned)p.n + 4u),
+                  Z = eval_word(p3d, 12u * (unsigned)p.n + 8u);
       bool kept = true;
       if (mask) kept = *((const __attribute__((address_space(1))) uint8_t*)mask + (unsigned)p.n) != 0;
       float px, py, pz;
@@ -184,15 +108,7 @@ __global__ __launch_bounds__(kRepBlock) void lm_report_points_kernel(const RepAr
       if (!valid) u = v = 0.f;  // (u, v may be anything, NaN included: keep the address arithmetic defined)
       int ix0, iy0;
       bilinear_weights(u, v, ix0, iy0, p.w00, p.w10, p.w01, p.w11);
-      p.xin = p.yin = 0;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int xx = ix0 + k, yy = iy0 + k;
-        p.xin |= (xx >= 0 && xx < W) ? 1 << k : 0;
-        p.yin |= (yy >= 0 && yy < H) ? 1 << k : 0;
-        p.xo[k] = (unsigned)(min(max(xx, 0), W - 1) * cs) * 4u;
-        p.yo[k] = (unsigned)(min(max(yy, 0), H - 1) * W * cs) * 4u;
-      }
+      PXT_EVAL_PLACE(p, ix0, iy0, W, H, cs);
     }
 
     float s_cost[2] = {0.f, 0.f};
@@ -204,11 +120,11 @@ __global__ __launch_bounds__(kRepBlock) void lm_report_points_kernel(const RepAr
       for (int j = 0; j < 2; ++j) {
         const RepPoint& p = pt[j];
         const unsigned cb = 4u * (unsigned)c0;
-        t11[j] = rep_texel(fmap, p.yo[0] + p.xo[0] + cb);
-        t12[j] = rep_texel(fmap, p.yo[0] + p.xo[1] + cb);
-        t21[j] = rep_texel(fmap, p.yo[1] + p.xo[0] + cb);
-        t22[j] = rep_texel(fmap, p.yo[1] + p.xo[1] + cb);
-        fr[j] = rep_texel(fref, 4u * (unsigned)(p.n * cs) + cb);
+        t11[j] = eval_texel(fmap, p.yo[0] + p.xo[0] + cb);
+        t12[j] = eval_texel(fmap, p.yo[0] + p.xo[1] + cb);
+        t21[j] = eval_texel(fmap, p.yo[1] + p.xo[0] + cb);
+        t22[j] = eval_texel(fmap, p.yo[1] + p.xo[1] + cb);
+        fr[j] = eval_texel(fref, 4u * (unsigned)(p.n * cs) + cb);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -224,14 +140,7 @@ __global__ __launch_bounds__(kRepBlock) void lm_report_points_kernel(const RepAr
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const RepPoint& p = pt[j];
-      // confidence: bilinear sample of channel C (one address for the whole group)
-      const unsigned cb = 4u * (unsigned)C;
-      const float q11 = rep_word(fmap, p.yo[0] + p.xo[0] + cb) * p.in(0, 0);
-      const float q12 = rep_word(fmap, p.yo[0] + p.xo[1] + cb) * p.in(0, 1);
-      const float q21 = rep_word(fmap, p.yo[1] + p.xo[0] + cb) * p.in(1, 0);
-      const float q22 = rep_word(fmap, p.yo[1] + p.xo[1] + cb) * p.in(1, 1);
-      const float wq = p.w00 * q11 + p.w10 * q12 + p.w01 * q21 + p.w11 * q22;
-      const float wref = rep_word(fref, 4u * (unsigned)(p.n * cs) + cb);
+      PXT_EVAL_CONFIDENCE(p, fmap, fref, C, cs);  // declares wq, wref (and cb, c_, q11..q22)
       const float sc = lm_group_sum(s_cost[j], wide);
       float rcost, wl;
       robust_loss(cf.loss, cf.loss_alpha, cf.loss_scale, sc, rcost, wl);
@@ -252,64 +161,28 @@ __global__ __launch_bounds__(kRepBlock) void lm_report_points_kernel(const RepAr
         const float4 lo = make_float4(ok, p.u, p.v, p.valid ? sc : 0.f);
         const float4 hi = make_float4(p.valid ? rcost : 0.f, p.valid ? wl : 0.f, p.valid ? wunc : 0.f, p.code);
         const float4 half = sub == 0 ? lo : hi;
-        RepVec4 o;
+        EvalVec4 o;
         o.x = half.x; o.y = half.y; o.z = half.z; o.w = half.w;
-        ((__attribute__((address_space(1))) RepVec4*)points)[2 * (size_t)p.i + sub] = o;
+        ((__attribute__((address_space(1))) EvalVec4*)points)[2 * (size_t)p.i + sub] = o;
       }
     }
   }
 
-  if (sub == 0) {
-#pragma unroll
-    for (int k = 0; k < kRepAcc; ++k) part[grp * kRepGrpStride + k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kRepAcc) {  // the groups' sums in a fixed order
-    float v = 0.f;
-    for (int g = 0; g < G; ++g) v += part[g * kRepGrpStride + threadIdx.x];
-    partials[((size_t)prob * kRepMaxWgs + b) * kRepAcc + threadIdx.x] = v;
-  }
+  eval_fold_groups<kRepAcc, kRepGrpStride, kRepAcc>(part, acc, sub, grp, G, partials, prob, b);
 }
 
-// One wave per problem: the workgroups' partials in workgroup order, then the summary; word 15 last.
-__global__ __launch_bounds__(PXT_WAVE) void lm_report_fold_kernel(const RepArgs args, const RepParams* ws_params,
-                                                                  const float* partials, const RepConf cf,
+// One wave per problem: the summary's 8 sums, zeros; word 15 last.
+__global__ __launch_bounds__(PXT_WAVE) void lm_report_fold_kernel(const EvalArgs<RepParams> args, const RepParams* ws_params,
+                                                                  const float* partials, const EvalConf cf,
                                                                   const int from_args) {
-  __shared__ float rec[kRepAcc];
-  const int prob = blockIdx.x;
-  const RepParams* q = rep_params(ws_params, from_args, prob);
-  float* out = uniform(q->summary);
-  float T[12];
-  const bool run = rep_load_pose(q, T);
-  if (!run) {
-    if (threadIdx.x == 0) __hip_atomic_store(&out[15], -1.f, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    return;
-  }
-  const int n_wgs = uniform(q->n_wgs);
-  if (threadIdx.x < kRepAcc) {
-    const float* p = partials + (size_t)prob * kRepMaxWgs * kRepAcc + threadIdx.x;
-    float v = 0.f;
-    for (int b = 0; b < n_wgs; ++b) v += p[(size_t)b * kRepAcc];
-    rec[threadIdx.x] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {  // one thread writes the summary, so that its release covers every word
+  // declares prob, q, out, T, rec; RETURNS when the problem is skipped
+  PXT_EVAL_FOLD_SUMS(RepParams, kRepAcc, 15, ws_params, from_args, partials);
+  if (threadIdx.x == 0) {
     for (int k = 0; k < kRepAcc; ++k) out[k] = rec[k];
     for (int k = kRepAcc; k < 15; ++k) out[k] = 0.f;
-    const float ok = rec[1] >= (float)cf.min_valid ? 1.f : -2.f;  // -2: evaluated, but the LM would call it failed
-    __hip_atomic_store(&out[15], ok, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    PXT_EVAL_FOLD_DONE(15, cf);  // reads rec[1], stores out[LAST]
   }
 }
-
-int rep_workgroups(int n_points, int C) {
-  const int groups = kRepBlock / (C > 32 ? 32 : 8);
-  const int per_wg = groups * kRepPointsPerGroup;
-  return std::max(1, std::min(kRepMaxWgs, (n_points + per_wg - 1) / per_wg));
-}
-
-size_t rep_params_bytes(int n_problems) { return ((size_t)n_problems * sizeof(RepParams) + 255) / 256 * 256; }
-
-using RepStage = StageRing<RepParams, PXT_LM_REPORT_MAX_PROBLEMS>;
 
 }  // namespace
 }  // namespace pxt
@@ -317,73 +190,23 @@ using RepStage = StageRing<RepParams, PXT_LM_REPORT_MAX_PROBLEMS>;
 using namespace pxt;
 
 extern "C" int64_t pxt_lm_point_report_workspace_bytes(int32_t n_problems) {
-  if (n_problems < 1 || n_problems > PXT_LM_REPORT_MAX_PROBLEMS) return PXT_E_ARG;
-  return (int64_t)(rep_params_bytes(n_problems) + (size_t)n_problems * kRepMaxWgs * kRepAcc * sizeof(float));
+  return eval_workspace_bytes<RepParams, kRepAcc>(n_problems, PXT_LM_REPORT_MAX_PROBLEMS);
 }
 
 extern "C" int pxt_lm_point_report(const pxt_lm_report_problem* problems, int32_t n_problems, const pxt_lm_conf* conf,
                                    void* workspace, void* stream) {
-  if (!problems || !conf || !workspace) return PXT_E_ARG;
-  if (n_problems < 1 || n_problems > PXT_LM_REPORT_MAX_PROBLEMS) return PXT_E_ARG;
-  if (((uintptr_t)workspace % 16) != 0) return PXT_E_ARG;
-  if (conf->pad < 0 || conf->loss < 0 || conf->loss > 2 || conf->min_valid < 0) return PXT_E_ARG;
-  const int K = n_problems;
-  const bool from_args = K <= kRepArgProblems;
-  RepArgs args = {};
-  RepParams* rec = args.p;
-  RepStage::Slot* slot = nullptr;
-  if (!from_args) {
-    static thread_local RepStage stage;
-    if (const int rc = stage.acquire(&slot)) return rc;
-    rec = slot->host;
-  }
-  int max_wgs = 1;
-  for (int k = 0; k < K; ++k) {
+  const auto fill = [&](int k, RepParams& r) {
     const pxt_lm_report_problem& q = problems[k];
-    const pxt_lm_level& l = q.level;
-    if (!q.p3d || !q.pose || !q.summary || q.n_points < 1 || q.n_points > (1 << 24)) return PXT_E_ARG;
-    if (const int rc = check_level(l)) return rc;
-    if (((uintptr_t)q.pose % 16) != 0 || ((uintptr_t)q.summary % 4) != 0 || ((uintptr_t)q.points % 16) != 0) return PXT_E_ARG;
+    if (!q.summary || q.n_points > (1 << 24)) return PXT_E_ARG;
+    if (((uintptr_t)q.summary % 4) != 0 || ((uintptr_t)q.points % 16) != 0) return PXT_E_ARG;
     if (!(q.inlier_weight == q.inlier_weight)) return PXT_E_ARG;  // NaN
-    // (byte offsets inside the map and the reference records are 32-bit in the kernel)
-    if ((long long)l.h * l.w * l.cstride >= (1ll << 30) || (long long)q.n_points * l.cstride >= (1ll << 30)) return PXT_E_ARG;
     for (int j = 0; j < k; ++j)
       if (problems[j].summary == q.summary || (q.points && problems[j].points == q.points)) return PXT_E_ARG;
-    RepParams& P = rec[k];
-    P.p3d = q.p3d;
-    P.mask = q.point_mask;
-    P.fmap = l.fmap;
-    P.fref = l.fref;
-    P.pose = q.pose;
-    P.points = q.points;
-    P.summary = q.summary;
-    P.n = q.n_points;
-    P.h = l.h; P.w = l.w; P.C = l.C; P.cs = l.cstride; P.ndist = l.ndist;
-    P.pose_is_record = q.pose_is_lm_record != 0;
-    P.n_wgs = rep_workgroups(q.n_points, l.C);
-    P.inlier_weight = q.inlier_weight;
-    for (int i = 0; i < 10; ++i) P.cam[i] = l.cam[i];
-    P.pad_[0] = P.pad_[1] = P.pad_[2] = 0;
-    max_wgs = std::max(max_wgs, P.n_wgs);
-  }
-  RepConf cf;
-  cf.pad = conf->pad;
-  cf.loss = conf->loss;
-  cf.min_valid = conf->min_valid;
-  cf.loss_alpha = conf->loss_alpha;
-  cf.loss_scale = conf->loss_scale;
-  hipStream_t s = (hipStream_t)stream;
-  const RepParams* ws_params = (const RepParams*)workspace;
-  float* partials = (float*)((char*)workspace + rep_params_bytes(K));
-  if (!from_args) {
-    PXT_HIP_CHECK(hipMemcpyAsync(workspace, slot->host, (size_t)K * sizeof(RepParams), hipMemcpyHostToDevice, s));
-    PXT_HIP_CHECK(hipEventRecord(slot->copied, s));
-  }
-  hipLaunchKernelGGL(lm_report_points_kernel, dim3(max_wgs, K), dim3(kRepBlock), 0, s, args, ws_params, partials, cf,
-                     (int)from_args);
-  PXT_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(lm_report_fold_kernel, dim3(K), dim3(PXT_WAVE), 0, s, args, ws_params, (const float*)partials, cf,
-                     (int)from_args);
-  PXT_HIP_CHECK(hipGetLastError());
-  return PXT_OK;
+    r.points = q.points;
+    r.out = q.summary;
+    r.inlier_weight = q.inlier_weight;
+    return PXT_OK;
+  };
+  return eval_launch<RepParams, PXT_LM_REPORT_MAX_PROBLEMS>(problems, n_problems, conf, workspace, stream, fill,
+                                                            lm_report_points_kernel, lm_report_fold_kernel);
 }

@@ -274,118 +274,94 @@ def _lm_refine_batch(p3d, point_masks, n_levels, fmaps, frefs, channels, cameras
                "pxt_lm_refine_batch")
 
 
-def _lm_information(p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record, pad, loss,
-                    loss_alpha, loss_scale, min_valid, records, workspace):
-    L = _lib.lib()
+def _lm_evaluate(op, problems, conf, records, workspace, *, entry, workspace_bytes, Problem, max_problems, record_name,
+                 n_record, own, extras=(), extra_names=""):
+    """The K (points, level, pose) problems of lm_information / lm_point_report: checked, packed and launched through
+    ``entry``.  ``problems`` = the ops' common per-problem arguments in schema order (p3d ... pose_is_lm_record),
+    ``conf`` = (pad, loss, loss_alpha, loss_scale, min_valid).  ``own(q, k, n)`` checks and sets what only ``op`` has
+    (one list per problem in ``extras``, and the record's pointer) and returns the (tensor, name) pairs the kernel
+    dereferences besides."""
+    p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record = problems
+    pad, loss, loss_alpha, loss_scale, min_valid = conf
     K = len(p3d)
-    if not (1 <= K <= _lib.PXT_LM_INFO_MAX_PROBLEMS):
-        raise _lib.PxtError(f"lm_information: {K} problems (1..{_lib.PXT_LM_INFO_MAX_PROBLEMS})")
-    if any(len(x) != K for x in (point_masks, fmaps, frefs, channels, ndist, poses, records)) or len(cameras) != 10 * K:
-        raise _lib.PxtError("lm_information: per problem one mask slot, map, reference table, channel count, ndist, pose, "
-                            "record and 10 camera floats")
+    if not (1 <= K <= max_problems):
+        raise _lib.PxtError(f"{op}: {K} problems (1..{max_problems})")
+    if any(len(x) != K for x in (point_masks, fmaps, frefs, channels, ndist, poses, records, *extras)) \
+            or len(cameras) != 10 * K:
+        raise _lib.PxtError(f"{op}: per problem one mask slot, map, reference table, channel count, ndist, pose, "
+                            f"{extra_names}{record_name} and 10 camera floats")
     _lib.require_gpu(workspace, "workspace")
     dev = workspace.device
-    probs = (_lib.LmInfoProblem * K)()
+    probs = (Problem * K)()
     for k in range(K):
         pts, fm, fr = _f32c(p3d[k], "p3d"), _f32c(fmaps[k], "fmap"), _f32c(frefs[k], "fref")
         n = int(pts.shape[0])
         if fm.dim() != 3 or tuple(pts.shape) != (n, 3) or tuple(fr.shape) != (n, int(fm.shape[2])):
-            raise _lib.PxtError(f"lm_information: problem {k}: p3d {tuple(pts.shape)}, fmap {tuple(fm.shape)}, fref "
+            raise _lib.PxtError(f"{op}: problem {k}: p3d {tuple(pts.shape)}, fmap {tuple(fm.shape)}, fref "
                                 f"{tuple(fr.shape)}; expected [N, 3], [h, w, cstride], [N, cstride]")
         mk = point_masks[k]
         if mk is not None and (mk.dtype != torch.uint8 or not mk.is_contiguous() or mk.numel() != n):
-            raise _lib.PxtError("lm_information: point masks are contiguous uint8 [n_points]")
+            raise _lib.PxtError(f"{op}: point masks are contiguous uint8 [n_points]")
+        q = probs[k]
+        more = own(q, k, n)
         # what the kernel dereferences must be device memory of one device (a host pointer there is a memory fault,
         # not an error); the pose and the record may also be pinned host memory
-        for t, name in ((pts, "p3d"), (fm, "fmap"), (fr, "fref"), (mk, "point_mask")):
+        for t, name in ((pts, "p3d"), (fm, "fmap"), (fr, "fref"), (mk, "point_mask"), *more):
             if t is None:
                 continue
             _lib.require_gpu(t, name)
             if t.device != dev:
-                raise _lib.PxtError(f"lm_information: {name} of problem {k} is on {t.device}, the workspace on {dev}")
-        pose, rec = poses[k], records[k]
+                raise _lib.PxtError(f"{op}: {name} of problem {k} is on {t.device}, the workspace on {dev}")
         need = 16 if pose_is_lm_record else 12
-        if pose.dtype != torch.float32 or not pose.is_contiguous() or pose.numel() < need \
-                or not ((pose.is_cuda and pose.device == dev) or pose.is_pinned()):
-            raise _lib.PxtError(f"lm_information: pose {k} needs {need} contiguous float32 values in device or pinned memory")
-        if rec.dtype != torch.float32 or not rec.is_contiguous() or rec.numel() < _lib.PXT_LM_INFO_RECORD \
-                or not ((rec.is_cuda and rec.device == dev) or rec.is_pinned()):
-            raise _lib.PxtError(f"lm_information: record {k} needs {_lib.PXT_LM_INFO_RECORD} contiguous float32 values in "
-                                "device or pinned memory")
-        q = probs[k]
+        for t, name, count in ((poses[k], "pose", need), (records[k], record_name, n_record)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < count \
+                    or not ((t.is_cuda and t.device == dev) or t.is_pinned()):
+                raise _lib.PxtError(f"{op}: {name} {k} needs {count} contiguous float32 values in device or pinned memory")
         q.p3d, q.point_mask, q.n_points = pts.data_ptr(), _lib.dptr(mk), n
         h, w, cs = (int(x) for x in fm.shape)
         q.level.fmap, q.level.fref = fm.data_ptr(), fr.data_ptr()
         q.level.h, q.level.w, q.level.C, q.level.cstride = h, w, int(channels[k]), cs
         q.level.cam[:] = [float(x) for x in cameras[10 * k:10 * k + 10]]
         q.level.ndist = int(ndist[k])
-        q.pose, q.pose_is_lm_record, q.out = pose.data_ptr(), int(bool(pose_is_lm_record)), rec.data_ptr()
-    if workspace.numel() * workspace.element_size() < int(L.pxt_lm_information_workspace_bytes(K)):
-        raise _lib.PxtError("lm_information: workspace smaller than pxt_lm_information_workspace_bytes(K)")
+        q.pose, q.pose_is_lm_record = poses[k].data_ptr(), int(bool(pose_is_lm_record))
+    if workspace.numel() * workspace.element_size() < int(workspace_bytes(K)):
+        raise _lib.PxtError(f"{op}: workspace smaller than {workspace_bytes.__name__}(K)")
     conf = _lib.LmConf()
     conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale = int(pad), int(loss), float(loss_alpha), float(loss_scale)
     conf.min_valid = int(min_valid)
-    _lib.check(L.pxt_lm_information(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), "pxt_lm_information")
+    _lib.check(entry(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), entry.__name__)
+
+
+def _lm_information(p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record, pad, loss,
+                    loss_alpha, loss_scale, min_valid, records, workspace):
+    def own(q, k, n):
+        q.out = records[k].data_ptr()
+        return ()
+
+    L = _lib.lib()
+    _lm_evaluate("lm_information", (p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record),
+                 (pad, loss, loss_alpha, loss_scale, min_valid), records, workspace, entry=L.pxt_lm_information,
+                 workspace_bytes=L.pxt_lm_information_workspace_bytes, Problem=_lib.LmInfoProblem,
+                 max_problems=_lib.PXT_LM_INFO_MAX_PROBLEMS, record_name="record", n_record=_lib.PXT_LM_INFO_RECORD, own=own)
 
 
 def _lm_point_report(p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record, pad, loss,
                      loss_alpha, loss_scale, min_valid, inlier_weights, points, summaries, workspace):
-    L = _lib.lib()
-    K = len(p3d)
-    if not (1 <= K <= _lib.PXT_LM_REPORT_MAX_PROBLEMS):
-        raise _lib.PxtError(f"lm_point_report: {K} problems (1..{_lib.PXT_LM_REPORT_MAX_PROBLEMS})")
-    if any(len(x) != K for x in (point_masks, fmaps, frefs, channels, ndist, poses, inlier_weights, points, summaries)) \
-            or len(cameras) != 10 * K:
-        raise _lib.PxtError("lm_point_report: per problem one mask slot, map, reference table, channel count, ndist, pose, "
-                            "inlier weight, points slot, summary and 10 camera floats")
-    _lib.require_gpu(workspace, "workspace")
-    dev = workspace.device
-    probs = (_lib.LmReportProblem * K)()
-    for k in range(K):
-        pts, fm, fr = _f32c(p3d[k], "p3d"), _f32c(fmaps[k], "fmap"), _f32c(frefs[k], "fref")
-        n = int(pts.shape[0])
-        if fm.dim() != 3 or tuple(pts.shape) != (n, 3) or tuple(fr.shape) != (n, int(fm.shape[2])):
-            raise _lib.PxtError(f"lm_point_report: problem {k}: p3d {tuple(pts.shape)}, fmap {tuple(fm.shape)}, fref "
-                                f"{tuple(fr.shape)}; expected [N, 3], [h, w, cstride], [N, cstride]")
-        mk, out = point_masks[k], points[k]
-        if mk is not None and (mk.dtype != torch.uint8 or not mk.is_contiguous() or mk.numel() != n):
-            raise _lib.PxtError("lm_point_report: point masks are contiguous uint8 [n_points]")
+    def own(q, k, n):
+        out = points[k]
         if out is not None and (out.dtype != torch.float32 or not out.is_contiguous()
                                 or tuple(out.shape) != (n, _lib.PXT_LM_POINT_RECORD)):
             raise _lib.PxtError(f"lm_point_report: points of problem {k} are a contiguous float32 [{n}, "
                                 f"{_lib.PXT_LM_POINT_RECORD}] tensor (got {tuple(out.shape)}, {out.dtype})")
-        # what the kernel dereferences must be device memory of one device (a host pointer there is a memory fault,
-        # not an error); the pose and the summary may also be pinned host memory
-        for t, name in ((pts, "p3d"), (fm, "fmap"), (fr, "fref"), (mk, "point_mask"), (out, "points")):
-            if t is None:
-                continue
-            _lib.require_gpu(t, name)
-            if t.device != dev:
-                raise _lib.PxtError(f"lm_point_report: {name} of problem {k} is on {t.device}, the workspace on {dev}")
-        pose, rec = poses[k], summaries[k]
-        need = 16 if pose_is_lm_record else 12
-        if pose.dtype != torch.float32 or not pose.is_contiguous() or pose.numel() < need \
-                or not ((pose.is_cuda and pose.device == dev) or pose.is_pinned()):
-            raise _lib.PxtError(f"lm_point_report: pose {k} needs {need} contiguous float32 values in device or pinned memory")
-        if rec.dtype != torch.float32 or not rec.is_contiguous() or rec.numel() < _lib.PXT_LM_REPORT_SUMMARY \
-                or not ((rec.is_cuda and rec.device == dev) or rec.is_pinned()):
-            raise _lib.PxtError(f"lm_point_report: summary {k} needs {_lib.PXT_LM_REPORT_SUMMARY} contiguous float32 values "
-                                "in device or pinned memory")
-        q = probs[k]
-        q.p3d, q.point_mask, q.n_points = pts.data_ptr(), _lib.dptr(mk), n
-        h, w, cs = (int(x) for x in fm.shape)
-        q.level.fmap, q.level.fref = fm.data_ptr(), fr.data_ptr()
-        q.level.h, q.level.w, q.level.C, q.level.cstride = h, w, int(channels[k]), cs
-        q.level.cam[:] = [float(x) for x in cameras[10 * k:10 * k + 10]]
-        q.level.ndist = int(ndist[k])
-        q.pose, q.pose_is_lm_record, q.inlier_weight = pose.data_ptr(), int(bool(pose_is_lm_record)), float(inlier_weights[k])
-        q.points, q.summary = _lib.dptr(out), rec.data_ptr()
-    if workspace.numel() * workspace.element_size() < int(L.pxt_lm_point_report_workspace_bytes(K)):
-        raise _lib.PxtError("lm_point_report: workspace smaller than pxt_lm_point_report_workspace_bytes(K)")
-    conf = _lib.LmConf()
-    conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale = int(pad), int(loss), float(loss_alpha), float(loss_scale)
-    conf.min_valid = int(min_valid)
-    _lib.check(L.pxt_lm_point_report(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), "pxt_lm_point_report")
+        q.inlier_weight, q.points, q.summary = float(inlier_weights[k]), _lib.dptr(out), summaries[k].data_ptr()
+        return ((out, "points"),)
+
+    L = _lib.lib()
+    _lm_evaluate("lm_point_report", (p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record),
+                 (pad, loss, loss_alpha, loss_scale, min_valid), summaries, workspace, entry=L.pxt_lm_point_report,
+                 workspace_bytes=L.pxt_lm_point_report_workspace_bytes, Problem=_lib.LmReportProblem,
+                 max_problems=_lib.PXT_LM_REPORT_MAX_PROBLEMS, record_name="summary", n_record=_lib.PXT_LM_REPORT_SUMMARY,
+                 own=own, extras=(inlier_weights, points), extra_names="inlier weight, points slot, ")
 
 
 # ------------------------------------------------------------------------------------ sampling

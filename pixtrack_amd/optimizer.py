@@ -345,22 +345,17 @@ class PixTrackOptimizer:
                 for buf, nl, p3d, mk, pr, ws in zip(recs, n_levels, p3ds, masks, problems, wss)]
 
     @staticmethod
-    def information_levels(items: Sequence[dict], conf: _lib.LmConf, workspace: torch.Tensor, pool_key=0) -> "PendingInfo":
-        """Enqueue ONE pxt_lm_information launch for K problems: ``items[k]`` = dict(p3d, mask (uint8 or None), pack
-        (LevelPack), pose) where ``pose`` is a Pose (12 host floats, staged in pinned memory) or a PendingLM - its pinned
-        record is then read on the device, so the launch rides behind the refinement with no host round trip.  All K
-        poses of a launch are of one kind.  Returns a handle; ``.result()`` waits for the K pinned records.
-        The records (and the staged host poses) are a ring of two per (K, pool_key): at most two launches of one
-        pool_key may be in flight - await a launch's result before enqueueing the launch after next (every caller in
-        this package awaits each launch before the next)."""
+    def _stage_evaluation(kind: str, items: Sequence[dict], n_rec: int, pool_key):
+        """What information_levels and point_report_levels hand to their op: K pinned records of n_rec floats (a ring
+        of two per (kind, pool_key, K), completion word - the last - cleared), the poses (PendingLM records, or 12
+        floats each staged in pinned memory), cameras, ndist, contiguous p3d and masks.
+        -> (recs, poses, from_lm, cams, ndist, p3ds, masks)"""
         K = len(items)
-        assert 1 <= K <= _lib.PXT_LM_INFO_MAX_PROBLEMS
         from_lm = isinstance(items[0]["pose"], PendingLM)
-        n_rec = _lib.PXT_LM_INFO_RECORD
-        recs = _pinned_records([n_rec] * K + ([] if from_lm else [16] * K), ("info", pool_key))
+        recs = _pinned_records([n_rec] * K + ([] if from_lm else [16] * K), (kind, pool_key))
         poses, cams, ndist = [], [], []
         for k, it in enumerate(items):
-            recs[k][47] = 0.0
+            recs[k][n_rec - 1] = 0.0
             lp = it["pack"]
             cams += lp.camera.as10().tolist()
             ndist.append(int(lp.camera._data.shape[-1] - 6))
@@ -372,12 +367,26 @@ class PixTrackOptimizer:
                 poses.append(recs[K + k])
         p3ds = [it["p3d"].to(torch.float32).contiguous() for it in items]
         masks = [None if it.get("mask") is None else it["mask"].to(p3ds[0].device, torch.uint8).contiguous() for it in items]
+        return recs[:K], poses, from_lm, cams, ndist, p3ds, masks
+
+    @staticmethod
+    def information_levels(items: Sequence[dict], conf: _lib.LmConf, workspace: torch.Tensor, pool_key=0) -> "PendingInfo":
+        """Enqueue ONE pxt_lm_information launch for K problems: ``items[k]`` = dict(p3d, mask (uint8 or None), pack
+        (LevelPack), pose) where ``pose`` is a Pose (12 host floats, staged in pinned memory) or a PendingLM - its pinned
+        record is then read on the device, so the launch rides behind the refinement with no host round trip.  All K
+        poses of a launch are of one kind.  Returns a handle; ``.result()`` waits for the K pinned records.
+        The records (and the staged host poses) are a ring of two per (K, pool_key): at most two launches of one
+        pool_key may be in flight - await a launch's result before enqueueing the launch after next (every caller in
+        this package awaits each launch before the next)."""
+        assert 1 <= len(items) <= _lib.PXT_LM_INFO_MAX_PROBLEMS
+        recs, poses, from_lm, cams, ndist, p3ds, masks = PixTrackOptimizer._stage_evaluation(
+            "info", items, _lib.PXT_LM_INFO_RECORD, pool_key)
         ops.lm_information(p3ds, masks, [it["pack"].fmap for it in items], [it["pack"].fref for it in items],
                            [int(it["pack"].C) for it in items], cams, ndist, poses, from_lm, conf.pad, conf.loss,
-                           conf.loss_alpha, conf.loss_scale, conf.min_valid, recs[:K], workspace)
+                           conf.loss_alpha, conf.loss_scale, conf.min_valid, recs, workspace)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(p3ds[0].device))
-        return PendingInfo(recs[:K], (p3ds, masks, [it["pack"] for it in items], poses, workspace), done)
+        return PendingInfo(recs, (p3ds, masks, [it["pack"] for it in items], poses, workspace), done)
 
     @staticmethod
     def point_report_levels(items: Sequence[dict], conf: _lib.LmConf, workspace: torch.Tensor, pool_key=0) -> "PendingReport":
@@ -386,35 +395,19 @@ class PixTrackOptimizer:
         only) or True - a device tensor [N, 8] is then allocated for the point records and kept by the handle.
         ``.result()`` waits for the K pinned 16-float summaries; the records are recycled as information_levels' are
         (a ring of two per (K, pool_key): await a launch's result before enqueueing the launch after next)."""
-        K = len(items)
-        assert 1 <= K <= _lib.PXT_LM_REPORT_MAX_PROBLEMS
-        from_lm = isinstance(items[0]["pose"], PendingLM)
-        n_rec = _lib.PXT_LM_REPORT_SUMMARY
-        recs = _pinned_records([n_rec] * K + ([] if from_lm else [16] * K), ("report", pool_key))
-        poses, cams, ndist = [], [], []
-        for k, it in enumerate(items):
-            recs[k][15] = 0.0
-            lp = it["pack"]
-            cams += lp.camera.as10().tolist()
-            ndist.append(int(lp.camera._data.shape[-1] - 6))
-            if from_lm:
-                poses.append(it["pose"].buf)
-            else:
-                T = it["pose"]
-                recs[K + k][:12] = (T.as12() if hasattr(T, "as12") else torch.as_tensor(T)).detach().cpu().reshape(-1).float()
-                poses.append(recs[K + k])
-        p3ds = [it["p3d"].to(torch.float32).contiguous() for it in items]
+        assert 1 <= len(items) <= _lib.PXT_LM_REPORT_MAX_PROBLEMS
+        recs, poses, from_lm, cams, ndist, p3ds, masks = PixTrackOptimizer._stage_evaluation(
+            "report", items, _lib.PXT_LM_REPORT_SUMMARY, pool_key)
         dev = p3ds[0].device
-        masks = [None if it.get("mask") is None else it["mask"].to(dev, torch.uint8).contiguous() for it in items]
         points = [torch.empty(int(p.shape[0]), _lib.PXT_LM_POINT_RECORD, dtype=torch.float32, device=dev)
                   if it.get("points") else None for it, p in zip(items, p3ds)]
         ops.lm_point_report(p3ds, masks, [it["pack"].fmap for it in items], [it["pack"].fref for it in items],
                             [int(it["pack"].C) for it in items], cams, ndist, poses, from_lm, conf.pad, conf.loss,
                             conf.loss_alpha, conf.loss_scale, conf.min_valid,
-                            [float(it.get("inlier_weight", 0.5)) for it in items], points, recs[:K], workspace)
+                            [float(it.get("inlier_weight", 0.5)) for it in items], points, recs, workspace)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
-        return PendingReport(recs[:K], points, (p3ds, masks, [it["pack"] for it in items], poses, workspace), done)
+        return PendingReport(recs, (p3ds, masks, [it["pack"] for it in items], poses, workspace), done, points)
 
     def run(self, p3D, F_ref, F_query, T_init: Pose, camera: Camera, mask=None, W_ref_query=None):
         """One pyramid level, pixloc calling convention:
@@ -495,8 +488,23 @@ def _pinned_records(sizes: Sequence[int], pool_key=0) -> List[torch.Tensor]:
     return bufs
 
 
+def _wait(flag: np.ndarray, word: int, done) -> None:
+    """Wait until a kernel's last store (system-scope release) has set ``flag[word]`` in a pinned record: poll it -
+    cheaper than an event wake-up on the frame's critical path.  The event is the fallback for a kernel that never
+    gets there, and the whole wait when PendingLM.poll is off."""
+    spins = 0
+    if not PendingLM.poll:  # several trackers on threads: a Python spin would hold the GIL
+        done.synchronize()
+    while flag[word] == 0.0:
+        spins += 1
+        if spins > 2_000_000 or (spins & 0x3FFF) == 0 and done.query():
+            done.synchronize()
+            break
+
+
 class PendingInfo:
-    """Result handle of an enqueued pxt_lm_information launch: ``result()`` -> one float64 numpy record (48) per problem."""
+    """Result handle of an enqueued pxt_lm_information launch: ``result()`` -> one float64 numpy record (48) per problem,
+    complete once its last word - stored last - is set."""
 
     def __init__(self, recs, keepalive, done):
         self.recs, self._keep, self._done = recs, keepalive, done
@@ -508,46 +516,20 @@ class PendingInfo:
         out = []
         for rec in self.recs:
             flag = rec.numpy()
-            spins = 0
-            if not PendingLM.poll:
-                self._done.synchronize()
-            while flag[47] == 0.0:  # stored last, with system-scope release
-                spins += 1
-                if spins > 2_000_000 or (spins & 0x3FFF) == 0 and self._done.query():
-                    self._done.synchronize()
-                    break
+            _wait(flag, flag.shape[0] - 1, self._done)
             out.append(flag.astype(np.float64))  # (a copy: the pinned record is reused two launches later)
         self._keep = None
         self._out = out
         return out
 
 
-class PendingReport:
+class PendingReport(PendingInfo):
     """Result handle of an enqueued pxt_lm_point_report launch: ``result()`` -> one float64 numpy summary (16) per
     problem; ``points[k]`` is problem k's device tensor [N, 8] (or None), complete once its summary has arrived."""
 
-    def __init__(self, recs, points, keepalive, done):
-        self.recs, self.points, self._keep, self._done = recs, points, keepalive, done
-        self._out: Optional[List[np.ndarray]] = None
-
-    def result(self) -> List[np.ndarray]:
-        if self._out is not None:  # (the K problems of a batched launch each ask once)
-            return self._out
-        out = []
-        for rec in self.recs:
-            flag = rec.numpy()
-            spins = 0
-            if not PendingLM.poll:
-                self._done.synchronize()
-            while flag[15] == 0.0:  # stored last, with system-scope release
-                spins += 1
-                if spins > 2_000_000 or (spins & 0x3FFF) == 0 and self._done.query():
-                    self._done.synchronize()
-                    break
-            out.append(flag.astype(np.float64))  # (a copy: the pinned record is reused two launches later)
-        self._keep = None
-        self._out = out
-        return out
+    def __init__(self, recs, keepalive, done, points):
+        super().__init__(recs, keepalive, done)
+        self.points = points
 
 
 class PendingLM:
@@ -564,18 +546,8 @@ class PendingLM:
     def result(self) -> LMResult:
         # This sits on the frame's critical path (the next frame's render waits for the pose):
         # one blocking copy, then plain numpy/Python on the host record.
-        # The kernel's last store (system-scope release) sets out[15]: poll it in the pinned
-        # buffer - cheaper than an event wake-up on the frame's critical path.  The event is the
-        # fallback for a kernel that never gets there (it then reports through `status`).
-        flag = self.buf.numpy()
-        spins = 0
-        if not PendingLM.poll:  # several trackers on threads: a Python spin would hold the GIL
-            self._done.synchronize()
-        while flag[15] == 0.0:
-            spins += 1
-            if spins > 2_000_000 or (spins & 0x3FFF) == 0 and self._done.query():
-                self._done.synchronize()
-                break
+        # The kernel's last store sets out[15] (a kernel that never gets there reports through `status`).
+        _wait(self.buf.numpy(), 15, self._done)
         host = self.buf.clone()  # the pinned buffer is reused two refinements later
         h = host.numpy()
         nh = 16 + _lib.PXT_MAX_LEVELS
