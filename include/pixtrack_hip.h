@@ -553,8 +553,8 @@ float* pxt_ngp_camera_slot(pxt_ngp* ctx); /* device float[12], owned by the cont
  *     pxt_ngp_create_shared;
  *   - K objects tracked in lock-step, one tracker (and one pyngp.Testbed) per object as
  *     pixtrack/pose_trackers/pixloc_tracker_r9.py:287-318 builds them: modes {2, 2, ...}.
- * The chain is three launches - ray generation, one persistent render kernel, resolve - and each of them carries every
- * render of the batch (blockIdx.y = render, one parameter record per render), so nothing depends on how streams are dealt
+ * The chain is four launches - ray generation, the first-hit pass, one persistent render kernel, resolve - and each of them
+ * carries every render of the batch (blockIdx.y = render, one parameter record per render), so nothing depends on how streams are dealt
  * to hardware queues.
  * ctxs[k] / views_host[k] / modes[k] / outs_host[k] / stats[k] (stats or stats[k] may be NULL) are what K calls of
  * pxt_ngp_render_frame(ctxs[k], &views_host[k], modes[k], camera_from_slot, &outs_host[k], stats[k], stream) would take; the

@@ -357,10 +357,16 @@ __device__ inline void ngp_eval(const NgpParams& P, const half8* s_w, int lane, 
 }
 
 // ===========================================================================
-// The renderer: three launches per render (or per chain of K renders), all on the caller's stream.
+// The renderer: four launches per render (or per chain of K renders), all on the caller's stream.
 //
 //   raygen   : ngp_raygen_kernel - a ray per (pixel, spp pass), box test, start jitter, order-preserving compaction of the
 //              rays that hit the render box into a list (ray id, start t, unit direction)
+//   first hit: ngp_first_hit_kernel - one lane per entry of that list walks the entry's ray along the dt lattice to its
+//              first occupied point (the serial next_sample) and writes a SECOND list with that point as the start t.  A group
+//              of 8 entries (the passes of a pixel) none of whose rays meets an occupied cell is finished here - zero results
+//              - and left out of the second list: the walk through empty space costs one lane per ray instead of the render
+//              kernel's eight, and a ray without samples no longer holds a ray position of a wave for a step.
+//              PXT_NGP_FIRST_HIT=0 leaves the launch out (the render kernel then reads the first list).
 //   render   : ngp_render_kernel - PERSISTENT waves: a wave holds 8 rays of the list and repeats two steps until its
 //              share of the list is used up: every ray's next K = 8 occupied lattice samples (ngp_march_group: the 8 lanes
 //              of a ray probe 8 lattice points per trip), then the wave's 8 x 8 samples through the hash grid (16 levels x
@@ -380,7 +386,8 @@ __device__ inline void ngp_eval(const NgpParams& P, const half8* s_w, int lane, 
 // hipExtAnyOrderLaunch is ignored on gfx9.  On ONE stream the persistent loop alone beats every rounds configuration
 // (render of the benchmark view: 0.68 ms against 0.82 for 4 rounds, 0.75 for 1; a frame's Depth + Shade pair 1.19 against
 // 1.39): no sample buffers (160 MB written and read back per round), no per-round state traffic, no compaction, 3
-// launches instead of 12 - and nothing left for a queue assignment to decide.  The rounds were removed.
+// launches instead of 12 - and nothing left for a queue assignment to decide.  The rounds were removed.  (The first-hit
+// launch came later: profiles/first_hit_ab.md.)
 //
 // Every ray performs exactly the arithmetic of oracle/ngp_oracle.py on exactly the same samples; samples a step evaluates
 // past a ray's termination point are discarded.
@@ -535,11 +542,13 @@ __device__ inline bool next_sample(const NgpParams& P, const Ray& r, float& t, f
   }
 }
 
-struct NgpWork {       // a render's scratch: its ray list, counter block and per-ray results
+struct NgpWork {       // a render's scratch: a ray list, its counter and the per-ray results
   unsigned* rid;       // [slot] pixel * spp + spp_index of the slot's ray (the compact list raygen writes)
   float* t0;           // [slot] its first lattice position
   float4* dir;         // [slot] (unit direction, d . camera z)
-  int* counters;       // [0]: rays in the list
+  int* counters;       // [0]: rays in the list.  (A render's record holds two of these structs - NgpBatchItem: the list the
+                       // ray generator writes with word 0 of the render's counter block, and the list the render kernel
+                       // reads: the same, or the first-hit kernel's with word 1.)
   float4* sppbuf;      // [pixel][spp] finished rays
   float* sppbuf_d;     // mode 2: finished rays' depth
 };
@@ -661,6 +670,74 @@ __device__ __forceinline__ void ngp_raygen_body(const NgpParams& P, const NgpWor
         Wk.dir[dst] = make_float4(rr.d[0], rr.d[1], rr.d[2], rr.zdot);
       }
       ++dst;
+    }
+    __syncthreads();
+  }
+}
+
+// The first-hit pass: one lane per entry of the ray generator's list.  The lane rebuilds the entry's ray and runs the
+// serial walk (next_sample: probe_cell / advance_past_cell, the oracle's arithmetic) from the entry's start to the first
+// lattice point whose cell is occupied, or out of the box.  The walk is memoryless - its only state is t, and the lattice
+// t' = t + dt(t) does not depend on what the cells hold - so the render kernel started at that point visits exactly the
+// samples it visits when started at the box entry.
+// What goes into the second list is decided per GROUP of 8 consecutive entries (with spp = 8 the passes of one pixel; the
+// first list holds them aligned, the ray generator adds 0 or 8 rays per thread).  A group with no occupied point on any of
+// its rays is finished here: each ray gets the result the render kernel writes for a ray without samples, zero (the resolve
+// kernel never zero-fills).  Every other group moves over whole, in order - a ray of it that left the box carries its last
+// t (>= tmax: the render kernel closes it in its first trip) - so that a wave's 8 ray positions keep receiving the 8 passes
+// of ONE pixel, which is what the wave-cooperative box fetch of ngp_render_body needs; dropping single rays shifts every
+// later group across two pixels (`per_ray`: that compaction, PXT_NGP_FIRST_HIT=2, kept for the A/B of
+// profiles/first_hit_ab.md).  Order-preserving compaction of 1024-entry tiles, one global atomic per tile, as in the ray
+// generator.
+constexpr int kHitTile = 1024;
+__device__ __forceinline__ void ngp_first_hit_body(const NgpParams& P, const NgpWork& Wk, const NgpWork& Wr, int per_ray, int blk,
+                                                   int nblk) {
+  __shared__ int s_wave[kHitTile / 64];
+  __shared__ int s_base;
+  const int n = Wk.counters[0];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i0 = blk * kHitTile; i0 < n; i0 += nblk * kHitTile) {  // (workgroup-uniform)
+    const int i = i0 + (int)threadIdx.x;
+    bool found = false;
+    unsigned rid = 0u;
+    float t = 0.f;
+    float4 rd = make_float4(0.f, 0.f, 1.f, 0.f);
+    if (i < n) {
+      rid = Wk.rid[i];
+      t = Wk.t0[i];
+      rd = Wk.dir[i];
+      const Ray r = ray_from_record(P, rd);
+      float pos[3], dt;
+      found = next_sample(P, r, t, pos, dt);
+    }
+    const unsigned long long fm = __ballot(found);
+    const bool keep = i < n && (per_ray ? found : ((fm >> (lane & ~7)) & 0xFFull) != 0ull);
+    if (i < n && !keep) {
+      Wk.sppbuf[rid] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (P.mode == 2) Wk.sppbuf_d[rid] = 0.f;
+    }
+    const unsigned long long km = __ballot(keep);
+    if (lane == 0) s_wave[wave] = __popcll(km);
+    __syncthreads();
+    int wave_off = 0, tile_total = 0;
+#pragma unroll
+    for (int w = 0; w < kHitTile / 64; ++w) {
+      if (w < wave) wave_off += s_wave[w];
+      tile_total += s_wave[w];
+    }
+    if (threadIdx.x == 0) {
+      s_base = tile_total ? atomicAdd(Wr.counters, tile_total) : 0;
+      // stats[1] stays "rays that hit the render box": the render kernel adds the length of the list it reads, the rays
+      // finished here are added here
+      const int dropped = min(n - i0, kHitTile) - tile_total;
+      if (P.stats && dropped) atomicAdd(P.stats + 1, (unsigned long long)dropped);
+    }
+    __syncthreads();
+    if (keep) {
+      const int dst = s_base + wave_off + __popcll(km & ((1ull << lane) - 1ull));
+      Wr.rid[dst] = rid;
+      Wr.t0[dst] = t;
+      Wr.dir[dst] = rd;
     }
     __syncthreads();
   }
@@ -1195,7 +1272,7 @@ __device__ __forceinline__ void ngp_resolve_body(const NgpParams& P, const NgpWo
 
 // ---- the launches.  blockIdx.y = render: a chain carries one render, a frame's two renders (the mask's Depth at the query
 // camera + the reference image's Shade at the reference camera, pixtrack/pose_trackers/pixloc_tracker_r9.py:145-152,207-214)
-// or K objects tracked in lock-step - every launch carries all of them, and all three launches read the same record per
+// or K objects tracked in lock-step - every launch carries all of them, and all four launches read the same record per
 // render.  The records travel by value in the kernel-argument segment while they fit (<= 4: a render, a frame's pair), else
 // they sit in device memory (uploaded from a pinned ring ahead of the chain).  Read-only for the whole chain and addressed
 // uniformly per workgroup: scalar loads either way.
@@ -1204,7 +1281,8 @@ __device__ __forceinline__ void ngp_resolve_body(const NgpParams& P, const NgpWo
 // memory the pointer is a __restrict__ kernel parameter, which is what lets the compiler keep the loads scalar.)
 struct NgpBatchItem {
   NgpParams P;
-  NgpWork W;
+  NgpWork W;   // the ray generator's list (first-hit kernel: input; resolve: the per-ray results, the counter block)
+  NgpWork Wr;  // the list the render kernel reads: the first-hit kernel's, or - without that launch - W again
 };
 template <int NV>
 struct NgpItemsByValue {
@@ -1223,6 +1301,15 @@ __global__ __launch_bounds__(256) void ngp_raygen_kernel_m(const NgpBatchItem* _
   ngp_raygen_body(it.P, it.W, blockIdx.x, gridDim.x);
 }
 
+__global__ __launch_bounds__(kHitTile) void ngp_first_hit_kernel_v(const NgpItemsByValue<4> items, int per_ray) {
+  const NgpBatchItem& it = ngp_kernarg_item(blockIdx.y);
+  ngp_first_hit_body(it.P, it.W, it.Wr, per_ray, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(kHitTile) void ngp_first_hit_kernel_m(const NgpBatchItem* __restrict__ items, int per_ray) {
+  const NgpBatchItem& it = items[blockIdx.y];
+  ngp_first_hit_body(it.P, it.W, it.Wr, per_ray, blockIdx.x, gridDim.x);
+}
+
 // MODES: 0 / 1 / 2 = every render of the chain is in that mode; 3 = per render (P.mode; a frame's Depth + Shade pair).
 template <int MODES>
 __device__ __forceinline__ void ngp_render_impl(const NgpBatchItem& it, int rays_per_wg) {
@@ -1230,9 +1317,9 @@ __device__ __forceinline__ void ngp_render_impl(const NgpBatchItem& it, int rays
   __shared__ unsigned s_feat[4 * 8 * 64];
   __shared__ float s_rays[4 * 8 * 8];
   const int mode = MODES == 3 ? it.P.mode : MODES;
-  if (mode == 0) ngp_render_body<0>(it.P, it.W, rays_per_wg, blockIdx.x, gridDim.x, s_w, s_feat, s_rays);
-  else if (mode == 1) ngp_render_body<1>(it.P, it.W, rays_per_wg, blockIdx.x, gridDim.x, s_w, s_feat, s_rays);
-  else ngp_render_body<2>(it.P, it.W, rays_per_wg, blockIdx.x, gridDim.x, s_w, s_feat, s_rays);
+  if (mode == 0) ngp_render_body<0>(it.P, it.Wr, rays_per_wg, blockIdx.x, gridDim.x, s_w, s_feat, s_rays);
+  else if (mode == 1) ngp_render_body<1>(it.P, it.Wr, rays_per_wg, blockIdx.x, gridDim.x, s_w, s_feat, s_rays);
+  else ngp_render_body<2>(it.P, it.Wr, rays_per_wg, blockIdx.x, gridDim.x, s_w, s_feat, s_rays);
 }
 template <int MODES>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void ngp_render_kernel_v(const NgpItemsByValue<4> items,
@@ -1309,7 +1396,8 @@ struct pxt_ngp {
   void* scratch = nullptr;
   size_t scratch_rays = 0;
   bool counters_clean = false;  // the previous render's resolve kernel zeroed the counter block
-  pxt::NgpWork work;
+  pxt::NgpWork work;      // the ray generator's list, the counter block, the per-ray results
+  pxt::NgpWork work_hit;  // the first-hit kernel's list (word 1 of the counter block), sized like the first
   int timing = 0;        // > 0: HIP events around the shade-carrying launches of every timing-th render
   long long renders = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // recorded, not yet read
@@ -1472,8 +1560,8 @@ extern "C" int pxt_ngp_query(pxt_ngp* ctx, const float* pos, const float* dir, i
   return PXT_OK;
 }
 
-// Carves the renderer's scratch for `rays` rays out of one allocation (grown on demand, never shrunk): the ray list (id,
-// start, direction) sized for every ray hitting the box, a counter block, and the per-ray result buffers indexed by ray id.
+// Carves the renderer's scratch for `rays` rays out of one allocation (grown on demand, never shrunk): the two ray lists (id,
+// start, direction), each sized for every ray hitting the box, a counter block, and the per-ray result buffers indexed by ray id.
 static int ensure_scratch(pxt_ngp* ctx, size_t rays) {
   if (ctx->scratch && ctx->scratch_rays >= rays) return PXT_OK;
   const size_t cap = rays + 2 * kTile;
@@ -1488,6 +1576,7 @@ static int ensure_scratch(pxt_ngp* ctx, size_t rays) {
   auto take = [&](size_t bytes) { size_t o = off; off = al(off + bytes); return o; };
   const size_t o_rid = take(cap * 4), o_t0 = take(cap * 4), o_dir = take(cap * 16), o_cnt = take(kCtrWords * sizeof(int));
   const size_t o_sppd = take(rays * 4), o_spp = take(rays * 16);
+  const size_t o_rid2 = take(cap * 4), o_t02 = take(cap * 4), o_dir2 = take(cap * 16);
   hipError_t e = hipMalloc(&ctx->scratch, off);
   if (e != hipSuccess) { set_last_error("hipMalloc(ngp scratch)", e); ctx->scratch_rays = 0; return PXT_E_HIP; }
   char* b = (char*)ctx->scratch;
@@ -1498,6 +1587,11 @@ static int ensure_scratch(pxt_ngp* ctx, size_t rays) {
   W.counters = (int*)(b + o_cnt);
   W.sppbuf = (float4*)(b + o_spp);
   W.sppbuf_d = (float*)(b + o_sppd);
+  NgpWork& Wh = ctx->work_hit = W;
+  Wh.rid = (unsigned*)(b + o_rid2);
+  Wh.t0 = (float*)(b + o_t02);
+  Wh.dir = (float4*)(b + o_dir2);
+  Wh.counters = W.counters + 1;
   ctx->scratch_rays = rays;
   ctx->counters_clean = false;
   return PXT_OK;
@@ -1531,7 +1625,7 @@ static int fill_view(const pxt_ngp* ctx, const pxt_ngp_view* v, int mode, float*
   return PXT_OK;
 }
 
-// ---- a chain of K renders: raygen -> render -> resolve, each ONE launch for all K renders.
+// ---- a chain of K renders: raygen -> first hit -> render -> resolve, each ONE launch for all K renders.
 namespace {
 
 struct ChainRender {
@@ -1573,6 +1667,9 @@ int run_chain(ChainRender* R, int K, hipStream_t s0, void* ws_dev) {
   // (profiles/r06_experiments.md).  The grid is the queue: more waves than are resident, each with a short share.
   static const int g_render = env_int("PXT_NGP_GRID", 16384, 64, 16384), g_div = env_int("PXT_NGP_GRID_DIV", 64, 1, 1 << 20),
                    g_raygen = env_int("PXT_NGP_GRID_RAYGEN", 1024, 64, 8192);
+  // The first-hit launch between the ray generator and the render kernel: 1 (default) on, 0 off (the three-launch chain),
+  // 2 on with single rays dropped instead of whole groups of 8 (ngp_first_hit_body).
+  static const int g_first_hit = env_int("PXT_NGP_FIRST_HIT", 1, 0, 2);
   for (int k = 0; k < K; ++k)
     if (const int rc = ensure_scratch(R[k].ctx, R[k].rays)) return rc;
   const bool by_value = K <= 4;
@@ -1598,13 +1695,16 @@ int run_chain(ChainRender* R, int K, hipStream_t s0, void* ws_dev) {
     rec = slot->host;
   }
   int modes = R[0].P.mode, max_pixels = 0;
+  size_t max_rays = 0;
   for (int k = 0; k < K; ++k) {
     pxt_ngp* ctx = R[k].ctx;
     if (R[k].P.mode != modes) modes = 3;
     max_pixels = std::max(max_pixels, R[k].P.W * R[k].P.H);
+    max_rays = std::max(max_rays, R[k].rays);
     NgpBatchItem& it = by_value ? pv.it[k] : rec[k];
     it.P = R[k].P;
     it.W = ctx->work;
+    it.Wr = g_first_hit ? ctx->work_hit : ctx->work;
     if (!ctx->counters_clean) PXT_HIP_CHECK(hipMemsetAsync(ctx->work.counters, 0, kCtrWords * sizeof(int), s0));
     ctx->counters_clean = false;  // (an error return below leaves them to the next render's memset)
   }
@@ -1617,6 +1717,12 @@ int run_chain(ChainRender* R, int K, hipStream_t s0, void* ws_dev) {
   const dim3 blk(256);
   if (by_value) hipLaunchKernelGGL(ngp_raygen_kernel_v, dim3(g_raygen, K), blk, 0, s0, pv);
   else hipLaunchKernelGGL(ngp_raygen_kernel_m, dim3(g_raygen, K), blk, 0, s0, pm);
+  if (g_first_hit) {
+    // a workgroup per 1024-entry tile of the longest list there can be, at most 2048 (they stride over longer lists)
+    const dim3 hgrid((unsigned)std::min<size_t>((max_rays + kHitTile - 1) / kHitTile, 2048), K), hblk(kHitTile);
+    if (by_value) hipLaunchKernelGGL(ngp_first_hit_kernel_v, hgrid, hblk, 0, s0, pv, g_first_hit == 2 ? 1 : 0);
+    else hipLaunchKernelGGL(ngp_first_hit_kernel_m, hgrid, hblk, 0, s0, pm, g_first_hit == 2 ? 1 : 0);
+  }
   // the render launch is the one the timing events bracket (bench.py's roofline)
   pxt_ngp* tctx = R[0].ctx;
   const bool timed = K == 1 && tctx->timing > 0 && (tctx->renders++ % tctx->timing) == 0;
@@ -1702,7 +1808,7 @@ extern "C" int64_t pxt_ngp_batch_workspace_bytes(int32_t n_renders) {
   return (int64_t)(((size_t)n_renders * sizeof(NgpBatchItem) + 255) / 256 * 256);  // one record per render
 }
 
-// K renders of K contexts - a frame's Depth + Shade pair, or K objects tracked in lock-step - as ONE chain of three launches.
+// K renders of K contexts - a frame's Depth + Shade pair, or K objects tracked in lock-step - as ONE chain of four launches.
 extern "C" int pxt_ngp_render_frame_batch(pxt_ngp* const* ctxs, const pxt_ngp_view* views, int32_t n_renders,
                                           const int32_t* modes, int32_t camera_from_slot, const pxt_ngp_outputs* outs,
                                           uint64_t* const* stats, void* batch_workspace, void* stream) {
