@@ -673,6 +673,38 @@ int64_t pxt_pose_errors_workspace_bytes(int32_t n_frames, int32_t n_vertices);
 int pxt_pose_errors(const float* vertices, int32_t n_vertices, const float* rel_poses, int32_t n_frames,
                     int32_t want_adds, float* records, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Mesh-free pose evaluation: two Depth renders compared pixel by pixel (opt-in; csrc/pxt_eval_render.hip).
+ *
+ * No reference counterpart.  For P (estimated, ground-truth) pairs of Depth renders it counts what the BOP benchmark's
+ * Visible Surface Discrepancy, the silhouette IoU and the mean depth error on the overlap are made of
+ * (pixtrack_amd/render_evaluation.py): no mesh and no symmetry flag are involved.
+ *   depth_est, depth_gt [P][H][W][4] float32 (16-byte aligned; may be the same pointer): what a Depth-mode render
+ *       writes - channel 0 the composited t * zdot * depth_scale after the spp mean, channel 3 alpha.
+ *   per pixel, all fp32: vis(v) = v.w >= min_alpha && v.x > 0 (pxt_points_from_depth's base test); q(v) = v.x / v.w
+ *       (correctly rounded); both = vis(e) && vis(g); dq = |q(e) - q(g)|; within_k = both && dq < tq[k] (strict; false
+ *       for a NaN).  A `both` pixel whose dq is NaN or inf counts in n_both, is within no threshold and adds nothing to
+ *       the sum or the max.
+ *   tq_host [n_taus] (host; travels as kernel arguments): the thresholds in units of q - the caller divides a
+ *       distance by the depth-to-distance factor in float64 and rounds once, so that the kernel multiplies no depth.
+ *   record of pair p (PXT_DEPTH_AGREE_RECORD = 24 uint32 words, all written by the last launch):
+ *       [0] n_est   [1] n_gt   [2] n_both   [3] n_union = n_est + n_gt - n_both
+ *       [4] bits of float sum of dq over the `both` pixels with a finite dq   [5] bits of float max of the same (+0.0: none)
+ *       [6] n_taus  [7] 1      [8 + k] n_within_k for k < n_taus, 0 for the rest
+ *   Bounds: 1 <= P <= 65535, 1 <= n_taus <= 16, width, height >= 1 and width * height <= 2^28, the images and the
+ *       workspace 16-byte aligned, records 4-byte aligned; anything else is PXT_E_ARG and nothing is launched or written.
+ *   Deterministic: counts by ballot + population count, the float sum and max through fixed-order reductions (wave
+ *   butterfly, LDS, one partial per workgroup in the workspace, folded in a fixed order by a second launch), no
+ *   atomics: a pair's record depends on its own two images and the thresholds only - not on P or on the pair's index.
+ *   workspace: device memory of pxt_depth_agreement_workspace_bytes(P, width, height) bytes (< 0: unsupported sizes);
+ *   one workspace serves one call at a time.  Two launches on `stream`, no host synchronisation. */
+#define PXT_DEPTH_AGREE_MAX_TAUS 16
+#define PXT_DEPTH_AGREE_RECORD 24
+int64_t pxt_depth_agreement_workspace_bytes(int32_t n_pairs, int32_t width, int32_t height);
+int pxt_depth_agreement(const float* depth_est, const float* depth_gt, int32_t n_pairs, int32_t width, int32_t height,
+                        float min_alpha, const float* tq_host, int32_t n_taus, uint32_t* records, void* workspace,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

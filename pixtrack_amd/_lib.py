@@ -30,6 +30,8 @@ PXT_LM_POINT_RECORD = 8
 PXT_LM_REPORT_SUMMARY = 16
 PXT_LM_REPORT_MAX_PROBLEMS = 64
 PXT_POSE_ERR_RECORD = 8
+PXT_DEPTH_AGREE_MAX_TAUS = 16
+PXT_DEPTH_AGREE_RECORD = 24
 
 
 class PxtError(RuntimeError):
@@ -237,6 +239,8 @@ PROTOTYPES = {
                                         _VP, _VP, _VP, _VP, _VP]),
     "pxt_pose_errors_workspace_bytes": (_I64, [_I32, _I32]),
     "pxt_pose_errors": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _VP, _VP]),
+    "pxt_depth_agreement_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "pxt_depth_agreement": (C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_float, C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
 }
 
 

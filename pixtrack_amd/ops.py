@@ -21,6 +21,8 @@ Reference call sites the ops stand in for:
                        refined on (pixloc_pose_refiners.py:282-290): a lattice of the Depth render, back-projected
   pose_errors          (opt-in) ADD / ADD-S of F frames against ground truth in one call: the per-frame loop of
                        notebooks/GetMetrics.ipynb (get_metrics) and evaluation.adds_distance
+  depth_agreement      (opt-in, no reference counterpart) P pairs of Depth renders compared pixel by pixel: the counts
+                       behind VSD, silhouette IoU and depth error of a run without a mesh (render_evaluation.py)
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -112,6 +114,12 @@ SCHEMAS = {
     # max, V, 0, 0, status (pxt_pose_errors); workspace: uint8, pxt_pose_errors_workspace_bytes(F, V)
     "pose_errors": (
         "(Tensor vertices, Tensor rel_poses, bool want_adds, Tensor(a!) records, Tensor(b!) workspace) -> ()"),
+    # depth_est, depth_gt [P, H, W, 4] (Depth renders; may be the same tensor), tq = 1..16 thresholds in units of
+    # depth / alpha -> records int32 [P, 24] (the uint32 words of pxt_depth_agreement); workspace: uint8,
+    # pxt_depth_agreement_workspace_bytes(P, W, H)
+    "depth_agreement": (
+        "(Tensor depth_est, Tensor depth_gt, float min_alpha, float[] tq, Tensor(a!) records, "
+        "Tensor(b!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -751,7 +759,36 @@ def _pose_errors(vertices, rel_poses, want_adds, records, workspace):
                                  workspace.data_ptr(), _stream(vertices)), "pxt_pose_errors")
 
 
+def _depth_agreement(depth_est, depth_gt, min_alpha, tq, records, workspace):
+    L = _lib.lib()
+    _f32c(depth_est, "depth_est")
+    _f32c(depth_gt, "depth_gt")
+    if depth_est.dim() != 4 or int(depth_est.shape[3]) != 4 or tuple(depth_gt.shape) != tuple(depth_est.shape):
+        raise _lib.PxtError(f"depth_agreement: depth_est {tuple(depth_est.shape)} / depth_gt {tuple(depth_gt.shape)}, "
+                            "expected two [P, H, W, 4] tensors of one shape")
+    P, H, W = (int(x) for x in depth_est.shape[:3])
+    if not (1 <= len(tq) <= _lib.PXT_DEPTH_AGREE_MAX_TAUS):
+        raise _lib.PxtError(f"depth_agreement: {len(tq)} thresholds (1..{_lib.PXT_DEPTH_AGREE_MAX_TAUS})")
+    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_DEPTH_AGREE_RECORD):
+        raise _lib.PxtError(f"depth_agreement: records is a contiguous int32 [{P}, {_lib.PXT_DEPTH_AGREE_RECORD}] tensor "
+                            f"(got {tuple(records.shape)}, {records.dtype})")
+    need = int(L.pxt_depth_agreement_workspace_bytes(P, W, H))
+    if need <= 0:
+        raise _lib.PxtError(f"depth_agreement: {P} pairs of {W} x {H} are not supported (1..65535 pairs, 1..2^28 pixels)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"depth_agreement: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    for t, name in ((depth_est, "depth_est"), (depth_gt, "depth_gt"), (records, "records"), (workspace, "workspace")):
+        _lib.require_gpu(t, name)
+        if t.device != depth_est.device:
+            raise _lib.PxtError(f"depth_agreement: {name} is on {t.device}, depth_est on {depth_est.device}")
+    tqs = (C.c_float * len(tq))(*[float(x) for x in tq])
+    _lib.check(L.pxt_depth_agreement(depth_est.data_ptr(), depth_gt.data_ptr(), P, W, H, float(min_alpha), tqs, len(tq),
+                                     records.data_ptr(), workspace.data_ptr(), _stream(depth_est)), "pxt_depth_agreement")
+
+
 _IMPLS = {
+    "depth_agreement": _depth_agreement,
     "pose_errors": _pose_errors,
     "points_from_depth": _points_from_depth,
     "lm_refine": _lm_refine,

@@ -1,0 +1,408 @@
+"""Mesh-free pose evaluation: VSD, silhouette IoU and depth error of a run from the NeRF's own Depth renders.
+
+``evaluation.py`` scores a run with ADD / ADD-S and needs the model's vertices.  An object captured with a phone exists
+only as an SfM model and a NeRF snapshot: there is no mesh.  The renderer is in the library, though: the object's Depth
+image at the estimated pose and at the ground-truth pose, compared pixel by pixel, gives the BOP benchmark's Visible
+Surface Discrepancy (Hodan et al., "BOP: Benchmark for 6D Object Pose Estimation", ECCV 2018) - symmetry-agnostic by
+construction, no symmetry flag to set - the silhouette IoU and the mean depth error on the overlap.  The comparison of
+all pairs runs on the device beside the renders (``torch.ops.pixtrack.depth_agreement``, csrc/pxt_eval_render.hip); one
+24-word record per frame is downloaded, no image.
+
+What differs from BOP's VSD
+  * There is no sensor depth image, so the two visibility masks are the two renders' silhouettes: no occluder is taken
+    into account and there is no ``delta`` tolerance of a visibility test.
+  * Depth is camera-axis depth (the renderer's ``t * zdot``), not the length of the ray.
+  * The surface is the NeRF's alpha-composited expected depth divided by alpha, and a pixel belongs to a silhouette
+    when ``alpha >= min_alpha`` and its depth is positive (the base test of the render's reference points).
+  * ``vsd = 1 - (overlap pixels with |dz| < tau) / (pixels of either silhouette)``; an object visible in neither render
+    scores ``vsd = 1``, ``iou = 0`` (BOP's convention).
+
+The host functions (``depth_agreement_reference``, ``frame_figures``, ``summarize``, ``z_scale``) need no GPU;
+everything that renders has no CPU path.
+
+    python -m pixtrack_amd.render_evaluation --poses poses.pkl --object_path P [--obj_aabb "[[..],[..]]"]
+        [--diameter D] [--min_alpha A] [--spp 8] [--json OUT] [--device cuda:0]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+
+from .evaluation import _poses_4x4
+
+MAX_PAIRS_PER_CALL = 65535            # pxt_depth_agreement's bound on P (one grid row per pair)
+MAX_TAUS = 16                         # PXT_DEPTH_AGREE_MAX_TAUS
+RECORD = 24                           # PXT_DEPTH_AGREE_RECORD
+CHUNK_BYTES = 256 << 20               # the two render buffers of a chunk stay under this together
+TAU_FRACTIONS = tuple(0.05 * k for k in range(1, 11))  # BOP: 5 % ... 50 % of the diameter
+THETAS = tuple(0.05 * k for k in range(1, 11))         # BOP: correct when vsd < theta, theta = 0.05 ... 0.5
+DEFAULT_MIN_ALPHA = 0.5               # refiner's reference_points_min_alpha
+
+
+def _require_device(device):
+    import torch
+
+    from . import _lib
+
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.PxtError(f"render evaluation runs on a ROCm device (got {dev}); no CPU path exists - "
+                            "depth_agreement_reference is the host function")
+    return dev
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Host: the kernel's per-pixel rules restated, and the figures made of its counts.
+# ------------------------------------------------------------------------------------------------------------------
+def depth_agreement_reference(depth_est, depth_gt, min_alpha, tq):
+    """numpy float32 restatement of pxt_depth_agreement's per-pixel rules on ``[P, H, W, 4]`` (or ``[H, W, 4]``) Depth
+    images: ``vis(v) = v.w >= min_alpha and v.x > 0``, ``q = v.x / v.w``, ``dq = |q_est - q_gt|``, within threshold k
+    when both are visible and ``dq < tq[k]`` (strict; false for a NaN); a ``both`` pixel whose dq is NaN or inf counts in
+    n_both, is within no threshold and adds nothing to the sum or the max.
+
+    Returns ``(records, sums)``: ``records`` uint32 ``[P, 24]`` - the kernel's words, word 4 being the bits of the float32
+    rounding of the sum - and ``sums`` float64 ``[P]``, the sum of the float32 dq values in float64."""
+    e, g = np.asarray(depth_est, np.float32), np.asarray(depth_gt, np.float32)
+    if e.ndim == 3:
+        e, g = e[None], g[None]
+    if e.ndim != 4 or e.shape[3] != 4 or g.shape != e.shape:
+        raise ValueError(f"depth images must be two [P, H, W, 4] arrays of one shape (got {e.shape}, {g.shape})")
+    tq = np.asarray(tq, np.float32).reshape(-1)
+    if not (1 <= len(tq) <= MAX_TAUS):
+        raise ValueError(f"{len(tq)} thresholds (1..{MAX_TAUS})")
+    ma = np.float32(min_alpha)
+    P = e.shape[0]
+    e, g = e.reshape(P, -1, 4), g.reshape(P, -1, 4)
+    with np.errstate(all="ignore"):
+        vis_e = (e[..., 3] >= ma) & (e[..., 0] > 0)
+        vis_g = (g[..., 3] >= ma) & (g[..., 0] > 0)
+        dq = np.abs(e[..., 0] / e[..., 3] - g[..., 0] / g[..., 3])
+        assert dq.dtype == np.float32
+        both = vis_e & vis_g
+        finite = both & np.isfinite(dq)
+        rec = np.zeros((P, RECORD), np.uint32)
+        rec[:, 0], rec[:, 1], rec[:, 2] = vis_e.sum(axis=1), vis_g.sum(axis=1), both.sum(axis=1)
+        rec[:, 3] = rec[:, 0] + rec[:, 1] - rec[:, 2]
+        sums = np.where(finite, dq, np.float32(0)).astype(np.float64).sum(axis=1)
+        rec[:, 4] = sums.astype(np.float32).view(np.uint32)
+        rec[:, 5] = np.where(finite, dq, np.float32(0)).max(axis=1).astype(np.float32).view(np.uint32)
+        rec[:, 6], rec[:, 7] = len(tq), 1
+        for k, t in enumerate(tq):
+            rec[:, 8 + k] = (both & (dq < t)).sum(axis=1)
+    return rec, sums
+
+
+def frame_figures(records, z_scale: float, n_taus: Optional[int] = None, finite_slot: Optional[int] = None,
+                  sums=None) -> Dict[str, np.ndarray]:
+    """Per-frame figures from pxt_depth_agreement's records (uint32 ``[F, 24]``): ``vsd`` ``[F, n_taus]`` =
+    ``1 - n_within_k / n_union``, ``iou`` = ``n_both / n_union``, ``n_est``, ``n_gt``, ``n_both``, ``n_union``,
+    ``mean_abs_dz`` = ``z_scale * sum / (both pixels with a finite dq)``, ``max_abs_dz`` and ``ok`` (word 7 == 1).
+    ``n_union == 0`` gives ``vsd = 1``, ``iou = 0``: BOP's convention for an object that is not visible.
+
+    ``n_taus``: how many threshold slots are taus (default: word 6).  ``finite_slot``: the threshold slot that held +inf,
+    whose count is the number of ``both`` pixels with a finite dq; None: every ``both`` pixel is taken to be finite.
+    ``sums``: the sums in float64 (``depth_agreement_reference``) instead of word 4."""
+    rec = np.ascontiguousarray(records).view(np.uint32).reshape(-1, RECORD)
+    F = len(rec)
+    if n_taus is None:
+        n_taus = int(rec[0, 6]) if F else 0
+    n_est, n_gt, n_both, n_union = (rec[:, i].astype(np.int64) for i in range(4))
+    within = rec[:, 8:8 + n_taus].astype(np.float64)
+    seen = n_union > 0
+    denom = np.where(seen, n_union, 1).astype(np.float64)
+    vsd = np.where(seen[:, None], 1.0 - within / denom[:, None], 1.0)
+    iou = np.where(seen, n_both / denom, 0.0)
+    n_finite = n_both if finite_slot is None else rec[:, 8 + finite_slot].astype(np.int64)
+    total = rec[:, 4].copy().view(np.float32).astype(np.float64) if sums is None else np.asarray(sums, np.float64)
+    with np.errstate(all="ignore"):
+        mean_abs_dz = np.where(n_finite > 0, float(z_scale) * total / np.maximum(n_finite, 1), np.nan)
+    max_abs_dz = float(z_scale) * rec[:, 5].copy().view(np.float32).astype(np.float64)
+    return dict(vsd=vsd, iou=iou, n_est=n_est, n_gt=n_gt, n_both=n_both, n_union=n_union, mean_abs_dz=mean_abs_dz,
+                max_abs_dz=max_abs_dz, ok=rec[:, 7] == 1)
+
+
+def average_recall(vsd, thetas: Sequence[float] = THETAS) -> float:
+    """BOP's average recall of VSD: the mean over frames x taus x thetas of ``[vsd < theta]``; ``vsd`` ``[F, n_taus]``.
+    A missed frame (vsd = 1) is below no theta.  No frames: NaN."""
+    v = np.asarray(vsd, np.float64)
+    if v.size == 0:
+        return float("nan")
+    return float(np.mean(v[..., None] < np.asarray(thetas, np.float64)))
+
+
+def summarize(vsd, iou, mean_abs_dz, evaluated, thetas: Sequence[float] = THETAS) -> Dict:
+    """Summary of a run from per-frame figures over ALL its frames: a frame that was not evaluated (lost, no ground
+    truth, a non-finite pose) must already hold ``vsd = 1`` at every tau and ``iou = 0`` - it counts in ``ar_vsd`` as a
+    miss and is left out of the means."""
+    vsd = np.asarray(vsd, np.float64).reshape(len(iou), -1)
+    ev = np.asarray(evaluated, bool)
+    out = {"n_evaluated": int(ev.sum())}
+    if ev.any():
+        out["vsd_mean"] = [float(x) for x in vsd[ev].mean(axis=0)]
+        out["iou_mean"] = float(np.asarray(iou, np.float64)[ev].mean())
+        dz = np.asarray(mean_abs_dz, np.float64)[ev]
+        out["mean_abs_dz_mean"] = float(np.nanmean(dz)) if np.isfinite(dz).any() else float("nan")
+    else:
+        out["vsd_mean"] = [float("nan")] * vsd.shape[1]
+        out["iou_mean"] = out["mean_abs_dz_mean"] = float("nan")
+    out["ar_vsd"] = average_recall(vsd, thetas)
+    return out
+
+
+def z_scale(testbed, nerf2sfm) -> float:
+    """The factor that turns ``q = depth / alpha`` of a Depth render into camera-axis depth in SfM object units:
+    ``s_G / depth_scale``, where ``depth_scale = 1 / snapshot.scale`` (what the renderer multiplies ``t * zdot`` by)
+    and ``s_G`` is the scale of the similarity ``ngp.ngp_to_sfm_affine(nerf2sfm, scale, offset)``, the cube root of
+    ``|det G|``.  ``testbed``: a Testbed with a snapshot loaded, or the NerfSnapshot itself.  A ``G`` whose three column
+    norms differ by more than 1e-9 relative is no similarity and is refused."""
+    from .ngp import ngp_to_sfm_affine
+
+    snap = getattr(testbed, "_snap", testbed)
+    if snap is None:
+        raise ValueError("z_scale: the testbed has no snapshot loaded")
+    G = ngp_to_sfm_affine(nerf2sfm, float(snap.scale), float(snap.offset))[:, :3]
+    norms = np.linalg.norm(G, axis=0)
+    if not np.all(np.isfinite(norms)) or norms.min() <= 0 or (norms.max() - norms.min()) > 1e-9 * norms.max():
+        raise ValueError(f"z_scale: ngp -> SfM is not a similarity (column norms {norms.tolist()})")
+    s_G = float(np.cbrt(abs(np.linalg.det(G))))
+    depth_scale = 1.0 / float(snap.scale)
+    return s_G / depth_scale
+
+
+def bounding_box_diagonal(model3d) -> float:
+    """The diagonal of the SfM points' axis-aligned bounding box: the command line's default ``diameter``."""
+    xyz = np.stack([p.xyz for p in model3d.points3D.values()]).astype(np.float64)
+    return float(np.linalg.norm(xyz.max(axis=0) - xyz.min(axis=0)))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Device: the comparison, the renders, a whole run.
+# ------------------------------------------------------------------------------------------------------------------
+def depth_agreement(depth_est, depth_gt, tq, min_alpha: float = DEFAULT_MIN_ALPHA, device="cuda:0") -> np.ndarray:
+    """pxt_depth_agreement's records, uint32 ``[P, 24]``, of ``[P, H, W, 4]`` Depth images (device tensors, or arrays
+    that are uploaded): pairs go through ``torch.ops.pixtrack.depth_agreement`` in calls of at most 65535 with one
+    workspace, and the records come back in one download at the end."""
+    import torch
+
+    from . import ops as _ops
+
+    dev = _require_device(device)
+    e, g = (t.to(dev) if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t, np.float32)).to(dev)
+            for t in (depth_est, depth_gt))
+    if e.dim() == 3:
+        e, g = e[None], g[None]
+    if e.dim() != 4 or int(e.shape[3]) != 4 or tuple(g.shape) != tuple(e.shape):
+        raise ValueError(f"depth images must be two [P, H, W, 4] tensors of one shape (got {tuple(e.shape)}, {tuple(g.shape)})")
+    P, H, W = (int(x) for x in e.shape[:3])
+    if P == 0:
+        return np.zeros((0, RECORD), np.uint32)
+    tq = [float(x) for x in tq]
+    records = torch.zeros(P, RECORD, dtype=torch.int32, device=dev)
+    need = int(_ops._lib.lib().pxt_depth_agreement_workspace_bytes(min(P, MAX_PAIRS_PER_CALL), W, H))
+    if need <= 0:
+        raise _ops._lib.PxtError(f"depth_agreement: {W} x {H} images are not supported (1..2^28 pixels)")
+    workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    for s in range(0, P, MAX_PAIRS_PER_CALL):
+        t = min(P, s + MAX_PAIRS_PER_CALL)
+        _ops.ops.depth_agreement(e[s:t], g[s:t], float(min_alpha), tq, records[s:t], workspace)
+    return records.cpu().numpy().view(np.uint32)
+
+
+def _thresholds(diameter, taus, zs):
+    """(taus, tq): the taus as given or BOP's fractions of the diameter; tq = tau / z_scale in float64, rounded once, and
+    one more slot holding +inf (its count is the number of overlap pixels with a finite difference)."""
+    taus = [f * float(diameter) for f in TAU_FRACTIONS] if taus is None else [float(t) for t in taus]
+    if not (1 <= len(taus) <= MAX_TAUS - 1):
+        raise ValueError(f"{len(taus)} taus (1..{MAX_TAUS - 1}: one threshold slot counts the finite pixels)")
+    return taus, [float(np.float32(t / zs)) for t in taus] + [math.inf]
+
+
+def _render_depth(testbed, nerf2sfm, T, camera, spp, out):
+    """The Depth image of world-to-camera pose ``T`` (4x4) as the tracker's mask render sees it, written into ``out``."""
+    import torch
+
+    from .geometry import Pose
+    from .ngp import RenderMode
+    from .ops import ops
+    from .utils.ingp_utils import sfm_to_nerf_pose
+    from .utils.pose_utils import get_camera_in_world_from_pixpose
+
+    width, height = (int(x) for x in camera.size)
+    cIw = get_camera_in_world_from_pixpose(Pose.from_4x4mat(torch.from_numpy(np.ascontiguousarray(T))))
+    testbed.fov = math.atan(width / (float(camera.f[0]) * 2)) * 2 * 180 / np.pi  # get_nerf_image_device's rule
+    testbed.set_nerf_camera_matrix(sfm_to_nerf_pose(nerf2sfm, cIw)[:3, :])
+    testbed._check_renderable()
+    ops.ngp_render(testbed._ctx_int(), testbed._view_for(width, height), width, height, int(spp), int(RenderMode.Depth),
+                   out, testbed.stats_accum)
+    testbed.n_renders += 1
+
+
+def render_pose_errors(testbed, nerf2sfm, camera, T_est, T_gt, diameter: float, taus: Optional[Sequence[float]] = None,
+                       min_alpha: float = DEFAULT_MIN_ALPHA, spp: int = 8, device=None) -> Dict[str, np.ndarray]:
+    """VSD, silhouette IoU and depth error of F (estimated, ground-truth) world-to-camera poses (``[F, 4, 4]``, or
+    lists of matrices / Pose objects) of the object ``testbed`` renders, seen by ``camera`` (one Camera, or one per
+    frame, all of one size).
+
+    Every pose's Depth image is rendered (``spp`` samples per pixel, the tracker's own camera chain) straight into one
+    of two ``[chunk, H, W, 4]`` device buffers - the chunk sized so that both stay under 256 MB together - and each chunk
+    is compared in one ``depth_agreement`` call; the records are downloaded once at the end, no image ever is.
+
+    Returns per frame ``vsd`` ``[F, len(taus)]``, ``iou``, ``n_est``, ``n_gt``, ``n_both``, ``n_union``, ``mean_abs_dz``
+    and ``max_abs_dz`` (SfM units; NaN / 0 without an overlap), ``ok`` (False where a pose holds a non-finite value: that
+    frame is not rendered and scores ``vsd = 1``, ``iou = 0``), and ``taus``.  ``taus`` default to BOP's 5 % ... 50 % of
+    ``diameter`` (at most 15 of them), ``min_alpha`` to the reference points' 0.5."""
+    import torch
+
+    from . import _lib
+    from .ops import ops
+
+    dev = _require_device(testbed.device if device is None else device)
+    A, B = _poses_4x4(T_est), _poses_4x4(T_gt)
+    if A.shape != B.shape:
+        raise ValueError(f"{A.shape[0]} estimated and {B.shape[0]} ground-truth poses")
+    F = len(A)
+    cams = list(camera) if isinstance(camera, (list, tuple)) else [camera] * F
+    if len(cams) != F:
+        raise ValueError(f"{len(cams)} cameras for {F} frames")
+    zs = z_scale(testbed, nerf2sfm)
+    taus, tq = _thresholds(diameter, taus, zs)
+    usable = np.isfinite(A).all(axis=(1, 2)) & np.isfinite(B).all(axis=(1, 2))
+    idx = np.nonzero(usable)[0]
+    rec = np.zeros((F, RECORD), np.uint32)
+    if len(idx):
+        sizes = {tuple(int(x) for x in cams[i].size) for i in idx}
+        if len(sizes) != 1:
+            raise ValueError(f"the frames of one call share one image size (got {sorted(sizes)})")
+        (W, H), = sizes
+        chunk = int(max(1, min(len(idx), MAX_PAIRS_PER_CALL, CHUNK_BYTES // (2 * H * W * 16))))
+        buf_e = torch.empty(chunk, H, W, 4, dtype=torch.float32, device=dev)
+        buf_g = torch.empty(chunk, H, W, 4, dtype=torch.float32, device=dev)
+        records = torch.zeros(len(idx), RECORD, dtype=torch.int32, device=dev)
+        need = int(_lib.lib().pxt_depth_agreement_workspace_bytes(chunk, W, H))
+        if need <= 0:
+            raise ValueError(f"{W} x {H} images are not supported (1..2^28 pixels)")
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        keep = (testbed.fov, testbed._cam_ngp)
+        try:
+            for s in range(0, len(idx), chunk):
+                part = idx[s:s + chunk]
+                for j, i in enumerate(part):
+                    _render_depth(testbed, nerf2sfm, A[i], cams[i], spp, buf_e[j])
+                    _render_depth(testbed, nerf2sfm, B[i], cams[i], spp, buf_g[j])
+                n = len(part)
+                ops.depth_agreement(buf_e[:n], buf_g[:n], float(min_alpha), tq, records[s:s + n], workspace)
+        finally:
+            testbed.fov, testbed._cam_ngp = keep
+        rec[idx] = records.cpu().numpy().view(np.uint32)
+    out = frame_figures(rec, zs, n_taus=len(taus), finite_slot=len(taus))
+    out["ok"] = out["ok"] & usable
+    out["taus"] = np.asarray(taus, np.float64)
+    return out
+
+
+def evaluate_poses_rendered(poses_file: Dict, testbed, nerf2sfm, diameter: float,
+                            taus: Optional[Sequence[float]] = None, min_alpha: float = DEFAULT_MIN_ALPHA, spp: int = 8,
+                            device=None) -> Dict:
+    """The mesh-free scoreboard of a run: ``poses_file`` is a ``poses.pkl``-style dict (frame name -> ``T_refined``,
+    ``gt_pose``, ``success``, ``camera`` and, where present, ``tracked``).
+
+    The frames that are evaluated are ``evaluation.evaluate_poses``': ``success``, ``gt_pose`` and ``T_refined`` present,
+    both poses finite.  Each is rendered with its own record's ``camera``; consecutive frames of one image size share
+    a chunk of ``render_pose_errors``.  Any other frame is a miss: ``vsd = 1`` at every tau, ``iou = 0``; it counts in
+    the recalls and is left out of the means.
+
+    Returns ``frames`` (frame name -> ``vsd`` list, ``iou``, ``n_est``, ``n_gt``, ``mean_abs_dz``, ``max_abs_dz``,
+    ``ok``) and, beside it, the summary: ``n_frames``, ``n_success`` (``n_tracked`` where the run has that key),
+    ``n_evaluated``, ``vsd_mean`` (one per tau), ``iou_mean``, ``mean_abs_dz_mean``, ``ar_vsd`` (BOP's average recall: the
+    mean over the taus x the thetas 0.05 ... 0.5 of ``[vsd < theta]``, over all frames), ``taus`` and ``diameter``."""
+    dev = _require_device(testbed.device if device is None else device)
+    names = list(poses_file)
+    usable = [bool(poses_file[k].get("success")) and poses_file[k].get("gt_pose") is not None
+              and poses_file[k].get("T_refined") is not None and poses_file[k].get("camera") is not None for k in names]
+    n = len(names)
+    taus_used, _ = _thresholds(diameter, taus, 1.0)
+    K = len(taus_used)
+    vsd, iou = np.ones((n, K)), np.zeros(n)
+    cols = {k: np.zeros(n, np.int64) for k in ("n_est", "n_gt")}
+    dz = {k: np.full(n, np.nan) for k in ("mean_abs_dz", "max_abs_dz")}
+    ok = np.zeros(n, bool)
+    idx = [i for i, u in enumerate(usable) if u]
+    size_of = {i: tuple(int(x) for x in poses_file[names[i]]["camera"].size) for i in idx}
+    s = 0
+    while s < len(idx):  # runs of consecutive usable frames of one image size
+        e = s + 1
+        while e < len(idx) and size_of[idx[e]] == size_of[idx[s]]:
+            e += 1
+        run = idx[s:e]
+        res = render_pose_errors(testbed, nerf2sfm, [poses_file[names[i]]["camera"] for i in run],
+                                 [_poses_4x4([poses_file[names[i]]["T_refined"]])[0] for i in run],
+                                 [_poses_4x4([poses_file[names[i]]["gt_pose"]])[0] for i in run], diameter, taus=taus_used,
+                                 min_alpha=min_alpha, spp=spp, device=dev)
+        vsd[run], iou[run], ok[run] = res["vsd"], res["iou"], res["ok"]
+        for k in cols:
+            cols[k][run] = res[k]
+        for k in dz:
+            dz[k][run] = res[k]
+        s = e
+    out = {"frames": {name: dict(vsd=[float(x) for x in vsd[i]], iou=float(iou[i]), n_est=int(cols["n_est"][i]),
+                                 n_gt=int(cols["n_gt"][i]), mean_abs_dz=float(dz["mean_abs_dz"][i]),
+                                 max_abs_dz=float(dz["max_abs_dz"][i]), ok=bool(ok[i])) for i, name in enumerate(names)}}
+    out["n_frames"] = n
+    out["n_success"] = int(sum(bool(poses_file[k].get("success")) for k in names))
+    if any("tracked" in poses_file[k] for k in names):
+        out["n_tracked"] = int(sum(bool(poses_file[k].get("tracked")) for k in names))
+    out.update(summarize(vsd, iou, dz["mean_abs_dz"], ok))
+    out["taus"] = [float(t) for t in taus_used]
+    out["diameter"] = float(diameter)
+    return out
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m pixtrack_amd.render_evaluation",
+                                 description="VSD, silhouette IoU and depth error of a poses.pkl from the object's NeRF "
+                                             "(no mesh, no vertex file)")
+    ap.add_argument("--poses", required=True, help="poses.pkl of a run (frames need gt_pose and camera)")
+    ap.add_argument("--object_path", required=True, help="the object's directory (SfM model, nerf2sfm.pkl, NeRF snapshot)")
+    ap.add_argument("--obj_aabb", type=str, default="", help="render box [[min], [max]] instead of the one derived from the SfM points")
+    ap.add_argument("--diameter", type=float, default=None,
+                    help="object diameter in SfM units (default: the diagonal of the SfM points' bounding box)")
+    ap.add_argument("--min_alpha", type=float, default=DEFAULT_MIN_ALPHA, help="a pixel is on the object when alpha >= this")
+    ap.add_argument("--spp", type=int, default=8, help="samples per pixel of the Depth renders")
+    ap.add_argument("--json", default=None, help="write the summary and the per-frame figures to this file")
+    ap.add_argument("--device", default="cuda:0")
+    return ap
+
+
+def main(argv: Optional[Sequence[str]] = None) -> Dict:
+    import ast
+    from pathlib import Path
+
+    args = build_parser().parse_args(argv)
+    _require_device(args.device)
+    from .model3d import Model3D
+    from .utils.ingp_utils import get_nerf_aabb_from_sfm, initialize_ingp, load_nerf2sfm
+    from .utils.io import load_reference_pickle
+
+    obj = Path(args.object_path)
+    model3d = Model3D(str(obj / "pixtrack/aug_nerf_sfm/aug_sfm"))
+    nerf2sfm = load_nerf2sfm(str(obj / "pixtrack/pixsfm/dataset/nerf2sfm.pkl"))
+    aabb = ast.literal_eval(args.obj_aabb) if args.obj_aabb else get_nerf_aabb_from_sfm(model3d, nerf2sfm)
+    testbed = initialize_ingp(str(obj / "pixtrack/instant-ngp/snapshots/weights.msgpack"), aabb, device=args.device)
+    poses = load_reference_pickle(args.poses)
+    diameter = bounding_box_diagonal(model3d) if args.diameter is None else float(args.diameter)
+    res = evaluate_poses_rendered(poses, testbed, nerf2sfm, diameter, min_alpha=args.min_alpha, spp=args.spp,
+                                  device=args.device)
+    summary = {k: v for k, v in res.items() if k != "frames"}
+    print(json.dumps(summary))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f)
+    return res
+
+
+if __name__ == "__main__":
+    main()
