@@ -705,6 +705,42 @@ int pxt_depth_agreement(const float* depth_est, const float* depth_gt, int32_t n
                         float min_alpha, const float* tq_host, int32_t n_taus, uint32_t* records, void* workspace,
                         void* stream);
 
+/* -------------------------------------------------------------------------
+ * Symmetry-aware pose errors: BOP's MSSD and MSPD (opt-in; csrc/pxt_eval_sym.hip).
+ *
+ * No reference counterpart.  For F frames, V model points and a set of S symmetry transforms of the object
+ * (pixtrack_amd/symmetry.py) it evaluates the F * S * V point pairs behind the BOP benchmark's Maximum Symmetry-aware
+ * Surface Distance and Maximum Symmetry-aware Projection Distance:
+ *       MSSD = min_s max_i |T_est v_i - T_gt S_s v_i|          MSPD = min_s max_i |pi(T_est v_i) - pi(T_gt S_s v_i)|
+ *   vertices [V][3] float32, object frame, CENTRED by the caller (centroid c subtracted), as for pxt_pose_errors.
+ *   syms     [S][12]: R row-major then t of every symmetry transform, expressed for the centred vertices
+ *       (t' = R c + t - c).  The caller puts the identity first if it wants it in the set.
+ *   frames   [F][PXT_SYM_ERR_FRAME = 40]: rel(12) = T_gt^-1 T_est for the centred vertices (exactly
+ *       evaluation.relative_poses), est(12) and gt(12) the world-to-camera poses for the centred vertices
+ *       (t' = R c + t), then fx, fy, cx, cy.  All formed on the host in float64 and rounded once.
+ *   per (f, s, i), all fp32, u the centred vertex: w = S_s u; d3 = |T_rel u - w| (the relative form of pxt_pose_errors:
+ *       object-sized numbers only); d2 = |pi(T_est u) - pi(T_gt w)| with pi(p) = (fx p.x / p.z + cx, fy p.y / p.z + cy),
+ *       IEEE division, a pinhole without lens terms as in BOP; d2 = +inf when either p.z is <= 0 or not finite.
+ *       e3[s] = max_i d3, e2[s] = max_i d2; squared distances are compared and one sqrtf is taken at the end.
+ *   record of frame f (PXT_SYM_ERR_RECORD = 8 floats):
+ *       [0] MSSD = min_s e3[s]        [1] its s as a float (a tie takes the lowest index)
+ *       [2] MSPD = min_s e2[s], in pixels; may be +inf        [3] its s
+ *       [4] V    [5] S    [6] 0
+ *       [7] status: 1.0 ok; -1.0 when the frame's 40 floats hold a non-finite value - then ONLY [7] is written
+ *   Bounds: 1 <= V <= 2^20, 1 <= S <= PXT_SYM_ERR_MAX_SYMS, 1 <= F <= 65535, every pointer 4-byte aligned; anything
+ *       else is PXT_E_ARG and nothing is launched or written.
+ *   Deterministic: per-block maxima in the workspace, folded by a second launch; max and min are order-independent and
+ *   there are no atomics: a frame's record depends on its own 40 floats, the vertices and the set only - not on F, on
+ *   the frame's index or on the other frames.
+ *   workspace: device memory of pxt_symmetric_pose_errors_workspace_bytes(F, S, V) bytes (< 0: unsupported sizes; up
+ *   to 2 MiB per frame); one workspace serves one call at a time.  Two launches on `stream`, no host synchronisation. */
+#define PXT_SYM_ERR_RECORD 8
+#define PXT_SYM_ERR_FRAME 40
+#define PXT_SYM_ERR_MAX_SYMS 1024
+int64_t pxt_symmetric_pose_errors_workspace_bytes(int32_t n_frames, int32_t n_syms, int32_t n_vertices);
+int pxt_symmetric_pose_errors(const float* vertices, int32_t n_vertices, const float* syms, int32_t n_syms,
+                              const float* frames, int32_t n_frames, float* records, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

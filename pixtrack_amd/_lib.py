@@ -32,6 +32,9 @@ PXT_LM_REPORT_MAX_PROBLEMS = 64
 PXT_POSE_ERR_RECORD = 8
 PXT_DEPTH_AGREE_MAX_TAUS = 16
 PXT_DEPTH_AGREE_RECORD = 24
+PXT_SYM_ERR_RECORD = 8
+PXT_SYM_ERR_FRAME = 40
+PXT_SYM_ERR_MAX_SYMS = 1024
 
 
 class PxtError(RuntimeError):
@@ -241,6 +244,8 @@ PROTOTYPES = {
     "pxt_pose_errors": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _VP, _VP]),
     "pxt_depth_agreement_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "pxt_depth_agreement": (C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_float, C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
+    "pxt_symmetric_pose_errors_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "pxt_symmetric_pose_errors": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP]),
 }
 
 

@@ -23,6 +23,8 @@ Reference call sites the ops stand in for:
                        notebooks/GetMetrics.ipynb (get_metrics) and evaluation.adds_distance
   depth_agreement      (opt-in, no reference counterpart) P pairs of Depth renders compared pixel by pixel: the counts
                        behind VSD, silhouette IoU and depth error of a run without a mesh (render_evaluation.py)
+  symmetric_pose_errors  (opt-in, no reference counterpart) BOP's MSSD / MSPD of F frames over a set of S symmetry
+                       transforms in one call: F * S * V transform-project-compare triples (evaluation.py, symmetry.py)
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -120,6 +122,11 @@ SCHEMAS = {
     "depth_agreement": (
         "(Tensor depth_est, Tensor depth_gt, float min_alpha, float[] tq, Tensor(a!) records, "
         "Tensor(b!) workspace) -> ()"),
+    # centred vertices [V, 3], syms [S, 12] and frames [F, 40] (rel, est, gt, fx fy cx cy; evaluation.symmetric_frames)
+    # -> records [F, 8]: MSSD, its symmetry, MSPD, its symmetry, V, S, 0, status (pxt_symmetric_pose_errors); workspace:
+    # uint8, pxt_symmetric_pose_errors_workspace_bytes(F, S, V)
+    "symmetric_pose_errors": (
+        "(Tensor vertices, Tensor syms, Tensor frames, Tensor(a!) records, Tensor(b!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -787,7 +794,39 @@ def _depth_agreement(depth_est, depth_gt, min_alpha, tq, records, workspace):
                                      records.data_ptr(), workspace.data_ptr(), _stream(depth_est)), "pxt_depth_agreement")
 
 
+def _symmetric_pose_errors(vertices, syms, frames, records, workspace):
+    L = _lib.lib()
+    _f32c(vertices, "vertices")
+    _f32c(syms, "syms")
+    _f32c(frames, "frames")
+    _f32c(records, "records")
+    if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or syms.dim() != 2 or int(syms.shape[1]) != 12
+            or frames.dim() != 2 or int(frames.shape[1]) != _lib.PXT_SYM_ERR_FRAME):
+        raise _lib.PxtError(f"symmetric_pose_errors: vertices {tuple(vertices.shape)} / syms {tuple(syms.shape)} / frames "
+                            f"{tuple(frames.shape)}, expected [V, 3] / [S, 12] / [F, {_lib.PXT_SYM_ERR_FRAME}]")
+    V, S, F = int(vertices.shape[0]), int(syms.shape[0]), int(frames.shape[0])
+    if tuple(records.shape) != (F, _lib.PXT_SYM_ERR_RECORD):
+        raise _lib.PxtError(f"symmetric_pose_errors: records is {tuple(records.shape)}, expected "
+                            f"{(F, _lib.PXT_SYM_ERR_RECORD)}")
+    need = int(L.pxt_symmetric_pose_errors_workspace_bytes(F, S, V))
+    if need <= 0:
+        raise _lib.PxtError(f"symmetric_pose_errors: {F} frames x {S} symmetries x {V} vertices is not supported "
+                            f"(1..65535 frames, 1..{_lib.PXT_SYM_ERR_MAX_SYMS} symmetries, 1..2^20 vertices)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"symmetric_pose_errors: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    for t, name in ((vertices, "vertices"), (syms, "syms"), (frames, "frames"), (records, "records"),
+                    (workspace, "workspace")):
+        _lib.require_gpu(t, name)
+        if t.device != vertices.device:
+            raise _lib.PxtError(f"symmetric_pose_errors: {name} is on {t.device}, the vertices on {vertices.device}")
+    _lib.check(L.pxt_symmetric_pose_errors(vertices.data_ptr(), V, syms.data_ptr(), S, frames.data_ptr(), F,
+                                           records.data_ptr(), workspace.data_ptr(), _stream(vertices)),
+               "pxt_symmetric_pose_errors")
+
+
 _IMPLS = {
+    "symmetric_pose_errors": _symmetric_pose_errors,
     "depth_agreement": _depth_agreement,
     "pose_errors": _pose_errors,
     "points_from_depth": _points_from_depth,

@@ -22,6 +22,10 @@ everything that renders has no CPU path.
 
     python -m pixtrack_amd.render_evaluation --poses poses.pkl --object_path P [--obj_aabb "[[..],[..]]"]
         [--diameter D] [--min_alpha A] [--spp 8] [--json OUT] [--device cuda:0]
+        [--bop [--vertices FILE] [--models_info models_info.json [--obj_id N] [--models_info_scale X]]]
+
+``--bop`` also scores BOP's symmetry-aware MSSD / MSPD (``evaluation.evaluate_poses_bop``) over the SfM model's points
+(or ``--vertices``) and adds ``ar_mssd``, ``ar_mspd`` and ``ar_bop = (ar_vsd + ar_mssd + ar_mspd) / 3`` to the summary.
 """
 from __future__ import annotations
 
@@ -374,6 +378,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--spp", type=int, default=8, help="samples per pixel of the Depth renders")
     ap.add_argument("--json", default=None, help="write the summary and the per-frame figures to this file")
     ap.add_argument("--device", default="cuda:0")
+    from .evaluation import add_bop_arguments
+
+    add_bop_arguments(ap)
+    ap.add_argument("--vertices", default=None,
+                    help="with --bop: the model points MSSD / MSPD run over (.npy or x y z rows; default: the SfM points)")
     return ap
 
 
@@ -396,6 +405,13 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     diameter = bounding_box_diagonal(model3d) if args.diameter is None else float(args.diameter)
     res = evaluate_poses_rendered(poses, testbed, nerf2sfm, diameter, min_alpha=args.min_alpha, spp=args.spp,
                                   device=args.device)
+    if args.bop:  # the full BOP figure of a mesh-free object: MSSD / MSPD over the SfM points (or --vertices)
+        from .evaluation import bop_symmetries, evaluate_poses_bop, merge_bop, read_vertices
+
+        vertices = (read_vertices(args.vertices) if args.vertices else
+                    np.stack([p.xyz for p in model3d.points3D.values()]).astype(np.float64))
+        merge_bop(res, evaluate_poses_bop(poses, vertices, args.device, diameter, symmetries=bop_symmetries(args),
+                                          ar_vsd=res["ar_vsd"]))
     summary = {k: v for k, v in res.items() if k != "frames"}
     print(json.dumps(summary))
     if args.json:
