@@ -303,6 +303,30 @@ def optimizer_step(g, H, lambda_, ok: bool, eps: float = 1e-6):
     return delta
 
 
+def lm_step(R, t, cam, p3d, F_ref, F_q, W_ref, W_q, lambda_, conf: "LMConf", mask=None, failed: bool = False):
+    """ONE iteration of ``lm_run``'s loop at the pose (R, t), in the dtype of its arguments: the same calls in the same
+    order, nothing carried over but ``failed`` (sticky in lm_run: a level that has once seen fewer than
+    ``conf.min_valid`` valid points keeps taking the masked identity step).
+    Returns (delta [6]: translation part first, g [6], H [6, 6], n_valid, masked-mean robust cost); g and H are the
+    undamped sums, also when the step is masked."""
+    loss_fn = make_loss(conf.loss, conf.loss_alpha, conf.loss_scale)
+    res, valid, w_unc, J = residual_jacobian(R, t, cam, p3d, F_ref, F_q, W_ref, W_q, conf.pad)
+    if mask is not None:
+        valid = valid & mask
+    n_valid = int(valid.long().sum(-1))
+    failed = failed or n_valid < conf.min_valid
+    cost = (res**2).sum(-1)
+    cost, w_loss = loss_fn(cost)
+    weights = w_loss * valid.to(res.dtype)
+    if w_unc is not None:
+        weights = weights * w_unc
+    g, H = build_system(J, res, weights)
+    delta = optimizer_step(g, H, lambda_, ok=not failed)
+    v = valid.to(res.dtype)
+    mean_cost = float((v * cost).sum(-1) / v.sum(-1)) if n_valid else float("nan")
+    return delta, g, H, n_valid, mean_cost
+
+
 @dataclass
 class LMLog:
     """What DebugTracker.log_optim_iter records (tracker.py:32-46), per level."""
