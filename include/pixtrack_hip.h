@@ -741,6 +741,52 @@ int64_t pxt_symmetric_pose_errors_workspace_bytes(int32_t n_frames, int32_t n_sy
 int pxt_symmetric_pose_errors(const float* vertices, int32_t n_vertices, const float* syms, int32_t n_syms,
                               const float* frames, int32_t n_frames, float* records, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * BOP's sensor-depth Visible Surface Discrepancy: two Depth renders and the frame's sensor depth image compared pixel
+ * by pixel (opt-in; csrc/pxt_eval_vsd.hip).
+ *
+ * No reference counterpart.  pxt_depth_agreement takes the two render silhouettes as the visibility masks; with a
+ * sensor depth image the masks are BOP's (Hodan et al., ECCV 2018 / BOP 2019, visib_mode = bop19, step cost): a pixel
+ * an occluder hides counts neither for nor against the estimate, and the object's visible fraction falls out of the
+ * same counts (pixtrack_amd/sensor_evaluation.py).
+ *   depth_est, depth_gt [P][H][W][4] float32 (16-byte aligned; may be the same pointer): as for pxt_depth_agreement.
+ *   sensor [P][H][W] uint16 (2-byte aligned; never NULL): the raw counts of the depth sensor, 0 = no measurement.
+ *   ray    [H][W] float32 (4-byte aligned) or NULL (= 1.0f everywhere): the factor that turns a camera-axis depth into
+ *       the length of the pixel's ray; shared by every pair.
+ *   shift_x, shift_y: the sensor pixel of render pixel (x, y) is (x + shift_x, y + shift_y); a position outside the
+ *       image reads nothing and counts as raw = 0.  No address outside the pair's own H x W counts is ever formed.
+ *   per pixel, all fp32, every product and difference rounded on its own (no FMA contraction):
+ *       sil(v) = v.w >= min_alpha && v.x > 0;  q(v) = v.x / v.w (correctly rounded);  r = ray[y][x];
+ *       d_e = q(e) * r;  d_g = q(g) * r;  d_s = (float(raw) * sensor_q) * r;
+ *       vis(d, sil) = sil && (d - d_s <= delta_q || raw == 0)      (bop19 visibility);
+ *       vis_g = vis(d_g, sil(g));  vis_e = vis(d_e, sil(e)) || (vis_g && sil(e));  inter = vis_g && vis_e;
+ *       dd = |d_e - d_g|;  within_k = inter && dd < tq[k] (strict; false for a NaN).  An `inter` pixel whose dd is NaN
+ *       or inf counts in n_inter, is within no threshold and adds nothing to the sum or the max.
+ *   sensor_q, delta_q, tq_host [n_taus] (host; they travel as kernel arguments): the distance of one raw count, the
+ *       visibility tolerance and the thresholds, all in units of q - the caller divides by the depth-to-distance factor
+ *       in float64 and rounds once.
+ *   record of pair p (PXT_SENSOR_VSD_RECORD = 32 uint32 words, all written by the last launch):
+ *       [0] n_vis_est   [1] n_vis_gt   [2] n_inter   [3] n_union = n_vis_est + n_vis_gt - n_inter
+ *       [4] bits of float sum of the finite dd over `inter`   [5] bits of float max of the same (+0.0: none)
+ *       [6] n_taus  [7] 1   [8] n_sil_est   [9] n_sil_gt   [10] pixels whose shifted sensor count is != 0
+ *       [11..15] 0          [16 + k] n_within_k for k < n_taus, 0 for the rest
+ *   Bounds: 1 <= P <= 65535, 1 <= n_taus <= 16, width, height >= 1 and width * height <= 2^28, |shift_x|, |shift_y| <=
+ *       32767, the float images and the workspace 16-byte aligned, records and ray 4-byte, sensor 2-byte aligned;
+ *       anything else is PXT_E_ARG and nothing is launched or written.
+ *   Deterministic: counts by ballot + population count, the float sum and max through fixed-order reductions (wave
+ *   butterfly, LDS, one partial per workgroup in the workspace, folded in a fixed order by a second launch), no
+ *   atomics: a pair's record depends on its own three images, ray, the shift and the scalars only - not on P or on the
+ *   pair's index.
+ *   workspace: device memory of pxt_sensor_vsd_workspace_bytes(P, width, height) bytes (< 0: unsupported sizes); one
+ *   workspace serves one call at a time.  Two launches on `stream`, no host synchronisation. */
+#define PXT_SENSOR_VSD_MAX_TAUS 16
+#define PXT_SENSOR_VSD_RECORD 32
+int64_t pxt_sensor_vsd_workspace_bytes(int32_t n_pairs, int32_t width, int32_t height);
+int pxt_sensor_vsd(const float* depth_est, const float* depth_gt, const uint16_t* sensor, const float* ray,
+                   int32_t n_pairs, int32_t width, int32_t height, int32_t shift_x, int32_t shift_y, float min_alpha,
+                   float sensor_q, float delta_q, const float* tq_host, int32_t n_taus, uint32_t* records,
+                   void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,8 @@ PXT_DEPTH_AGREE_RECORD = 24
 PXT_SYM_ERR_RECORD = 8
 PXT_SYM_ERR_FRAME = 40
 PXT_SYM_ERR_MAX_SYMS = 1024
+PXT_SENSOR_VSD_MAX_TAUS = 16
+PXT_SENSOR_VSD_RECORD = 32
 
 
 class PxtError(RuntimeError):
@@ -246,6 +248,9 @@ PROTOTYPES = {
     "pxt_depth_agreement": (C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_float, C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
     "pxt_symmetric_pose_errors_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "pxt_symmetric_pose_errors": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP]),
+    "pxt_sensor_vsd_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "pxt_sensor_vsd": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, C.c_float, C.c_float, C.c_float,
+                                 C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
 }
 
 

@@ -25,6 +25,9 @@ Reference call sites the ops stand in for:
                        behind VSD, silhouette IoU and depth error of a run without a mesh (render_evaluation.py)
   symmetric_pose_errors  (opt-in, no reference counterpart) BOP's MSSD / MSPD of F frames over a set of S symmetry
                        transforms in one call: F * S * V transform-project-compare triples (evaluation.py, symmetry.py)
+  sensor_vsd           (opt-in, no reference counterpart) P pairs of Depth renders compared with each other and with the
+                       frames' sensor depth images: the counts behind BOP's occlusion-aware VSD and the visible
+                       fraction (sensor_evaluation.py)
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -127,6 +130,13 @@ SCHEMAS = {
     # uint8, pxt_symmetric_pose_errors_workspace_bytes(F, S, V)
     "symmetric_pose_errors": (
         "(Tensor vertices, Tensor syms, Tensor frames, Tensor(a!) records, Tensor(b!) workspace) -> ()"),
+    # depth_est, depth_gt [P, H, W, 4] (Depth renders), sensor [P, H, W] uint16 (or int16 holding the same bits) raw depth
+    # counts, ray [H, W] float32 or None, shift = (shift_x, shift_y), tq = 1..16 thresholds in units of depth / alpha
+    # -> records int32 [P, 32] (the uint32 words of pxt_sensor_vsd); workspace: uint8,
+    # pxt_sensor_vsd_workspace_bytes(P, W, H)
+    "sensor_vsd": (
+        "(Tensor depth_est, Tensor depth_gt, Tensor sensor, Tensor? ray, int[] shift, float min_alpha, float sensor_q, "
+        "float delta_q, float[] tq, Tensor(a!) records, Tensor(b!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -825,7 +835,49 @@ def _symmetric_pose_errors(vertices, syms, frames, records, workspace):
                "pxt_symmetric_pose_errors")
 
 
+def _sensor_vsd(depth_est, depth_gt, sensor, ray, shift, min_alpha, sensor_q, delta_q, tq, records, workspace):
+    L = _lib.lib()
+    _f32c(depth_est, "depth_est")
+    _f32c(depth_gt, "depth_gt")
+    if depth_est.dim() != 4 or int(depth_est.shape[3]) != 4 or tuple(depth_gt.shape) != tuple(depth_est.shape):
+        raise _lib.PxtError(f"sensor_vsd: depth_est {tuple(depth_est.shape)} / depth_gt {tuple(depth_gt.shape)}, "
+                            "expected two [P, H, W, 4] tensors of one shape")
+    P, H, W = (int(x) for x in depth_est.shape[:3])
+    if sensor.dtype not in (torch.uint16, torch.int16) or not sensor.is_contiguous() or tuple(sensor.shape) != (P, H, W):
+        raise _lib.PxtError(f"sensor_vsd: sensor is a contiguous uint16 (or int16) [{P}, {H}, {W}] tensor "
+                            f"(got {tuple(sensor.shape)}, {sensor.dtype})")
+    if ray is not None:
+        _f32c(ray, "ray")
+        if tuple(ray.shape) != (H, W):
+            raise _lib.PxtError(f"sensor_vsd: ray is {tuple(ray.shape)}, expected {(H, W)}")
+    if len(shift) != 2 or any(abs(int(v)) > 32767 for v in shift):
+        raise _lib.PxtError(f"sensor_vsd: shift is (shift_x, shift_y), each within +-32767 (got {list(shift)})")
+    if not (1 <= len(tq) <= _lib.PXT_SENSOR_VSD_MAX_TAUS):
+        raise _lib.PxtError(f"sensor_vsd: {len(tq)} thresholds (1..{_lib.PXT_SENSOR_VSD_MAX_TAUS})")
+    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_SENSOR_VSD_RECORD):
+        raise _lib.PxtError(f"sensor_vsd: records is a contiguous int32 [{P}, {_lib.PXT_SENSOR_VSD_RECORD}] tensor "
+                            f"(got {tuple(records.shape)}, {records.dtype})")
+    need = int(L.pxt_sensor_vsd_workspace_bytes(P, W, H))
+    if need <= 0:
+        raise _lib.PxtError(f"sensor_vsd: {P} pairs of {W} x {H} are not supported (1..65535 pairs, 1..2^28 pixels)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"sensor_vsd: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    named = [(depth_est, "depth_est"), (depth_gt, "depth_gt"), (sensor, "sensor"), (records, "records"),
+             (workspace, "workspace")] + ([(ray, "ray")] if ray is not None else [])
+    for t, name in named:
+        _lib.require_gpu(t, name)
+        if t.device != depth_est.device:
+            raise _lib.PxtError(f"sensor_vsd: {name} is on {t.device}, depth_est on {depth_est.device}")
+    tqs = (C.c_float * len(tq))(*[float(x) for x in tq])
+    _lib.check(L.pxt_sensor_vsd(depth_est.data_ptr(), depth_gt.data_ptr(), sensor.data_ptr(),
+                                None if ray is None else ray.data_ptr(), P, W, H, int(shift[0]), int(shift[1]),
+                                float(min_alpha), float(sensor_q), float(delta_q), tqs, len(tq), records.data_ptr(),
+                                workspace.data_ptr(), _stream(depth_est)), "pxt_sensor_vsd")
+
+
 _IMPLS = {
+    "sensor_vsd": _sensor_vsd,
     "symmetric_pose_errors": _symmetric_pose_errors,
     "depth_agreement": _depth_agreement,
     "pose_errors": _pose_errors,
