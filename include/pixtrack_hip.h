@@ -404,6 +404,45 @@ int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, const int32_
                           const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
                           float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
                           void* workspace, void* stream);
+/* Reference tiles.  The reference image's dense maps exist only to be sampled at the projected 3-D points
+ * (pixloc_pose_refiners.py:282-290, then `del`), and the last two decoder layers feed nothing but the fine head.  A pass
+ * that is told the points its fine map WILL be sampled at - the arguments of the pxt_sample_sparse call that follows: the
+ * points, the pose, the fine level's camera, pad and window - computes only the tiles of those two layers that a sample
+ * depends on (the sampler's own arithmetic names the 2 x 2 texels of every point valid on the fine level; the layer
+ * before takes the tiles under the needed tiles' up-sampling patches).  Every other tile of the fine map is NOT WRITTEN
+ * (the buffer keeps what it held); the computed tiles, the other two maps and hence every sampled value are bit for bit
+ * those of the full pass.  Never pass points for a map that anything else reads (the query, dumps, logs).
+ * `p3d` is a device pointer [n_points][3]; everything else is read on the host.  full_w = 0: no window, else the pass's
+ * fine map is the window [x0, x0 + w) x [y0, y0 + h) of a full_w x full_h level (pxt_sample_level).  The _sampled entry
+ * points take the arguments of pxt_unet_forward / pxt_unet_forward_pair plus the points (NULL, or a NULL entry: as
+ * the plain call).  They are ignored - every tile is computed - by an fp32 context, with $PXT_UNET_REF_TILES=0, after
+ * pxt_unet_set_reference_tiles(ctx, 0), when $PXT_UNET_STREAMS=1 batches an equal-sized pair, and for a layer planned
+ * with split-K. */
+typedef struct {
+  const float* p3d;
+  int32_t n_points;
+  float T[12];
+  float cam[10];
+  int32_t ndist, pad;
+  int32_t x0, y0, full_w, full_h;
+} pxt_unet_sample_points;
+int pxt_unet_forward_sampled(pxt_unet* ctx, const void* image, int32_t image_is_u8, const uint8_t* mask, int32_t H,
+                             int32_t W, float* const out_maps[3], const int32_t out_cstride[3], int32_t normalize,
+                             void* workspace, void* stream, const pxt_unet_sample_points* points_host);
+int pxt_unet_forward_pair_sampled(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
+                                  const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
+                                  float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
+                                  void* workspace, void* stream,
+                                  const pxt_unet_sample_points* const* points_host /* [2], entries may be NULL */);
+int pxt_unet_set_reference_tiles(pxt_unet* ctx, int32_t on);
+/* The flag rule alone, on the HOST (every pointer, `p3d` too, is host memory; no device is touched): for a fine_h x
+ * fine_w fine map (even sizes) cut into fine_tile_rows x 16 tiles and the (fine_h / 2) x (fine_w / 2) layer before it cut
+ * into low_tile_rows x 16 tiles, writes 1 for every tile a sampled pass computes and 0 for the others, row-major.  The
+ * same functions the device kernel runs: what the tests hold against their own replica of the rule. */
+int pxt_unet_reference_tiles_host(const pxt_unet_sample_points* points_host, int32_t fine_h, int32_t fine_w,
+                                  int32_t fine_tile_rows, int32_t low_tile_rows, uint8_t* fine_flags_host,
+                                  uint8_t* low_flags_host);
+
 /* Deferred join of the pair entry (round 4): with pxt_unet_set_defer_join(ctx, 1), pxt_unet_forward_pair (and the
  * two-image pxt_unet_forward_batch that runs through it) returns with image 0's maps complete in the caller's stream
  * order and image 1's pass still running on the library's side stream; the caller may enqueue work that needs image 0

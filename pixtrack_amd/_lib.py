@@ -91,6 +91,21 @@ class SampleLevel(C.Structure):
     ]
 
 
+class UnetSamplePoints(C.Structure):
+    _fields_ = [
+        ("p3d", C.c_void_p),
+        ("n_points", C.c_int32),
+        ("T", C.c_float * 12),
+        ("cam", C.c_float * 10),
+        ("ndist", C.c_int32),
+        ("pad", C.c_int32),
+        ("x0", C.c_int32),
+        ("y0", C.c_int32),
+        ("full_w", C.c_int32),
+        ("full_h", C.c_int32),
+    ]
+
+
 class NgpModel(C.Structure):
     _fields_ = [
         ("n_levels", C.c_int32),
@@ -198,6 +213,17 @@ PROTOTYPES = {
         C.c_int,
         [_VP, _VP, _I32, _VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), _I32, _VP, _VP],
     ),
+    "pxt_unet_forward_sampled": (
+        C.c_int,
+        [_VP, _VP, _I32, _VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), _I32, _VP, _VP, C.POINTER(UnetSamplePoints)],
+    ),
+    "pxt_unet_forward_pair_sampled": (
+        C.c_int,
+        [_VP, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_VP),
+         C.POINTER(_I32), C.POINTER(_I32), _VP, _VP, C.POINTER(C.POINTER(UnetSamplePoints))],
+    ),
+    "pxt_unet_set_reference_tiles": (C.c_int, [_VP, _I32]),
+    "pxt_unet_reference_tiles_host": (C.c_int, [C.POINTER(UnetSamplePoints), _I32, _I32, _I32, _I32, _VP, _VP]),
     "pxt_unet_set_defer_join": (C.c_int, [_VP, _I32]),
     "pxt_unet_set_batch_plan": (C.c_int, [_VP, _I32]),
     "pxt_unet_set_tile_skip": (C.c_int, [_VP, _I32]),

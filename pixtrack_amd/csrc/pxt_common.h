@@ -42,7 +42,7 @@ constexpr float kCamEps = 1e-3f;
 // Projects a camera-frame point.  Returns validity (z > eps, inside the
 // distortion model's monotone range, inside the image); writes pixel coords and,
 // if J != nullptr, the 2x3 Jacobian d(u,v)/d(p) in row-major order.
-__device__ inline bool project_point(const Cam& c, float x, float y, float z, float& u, float& v,
+__host__ __device__ inline bool project_point(const Cam& c, float x, float y, float z, float& u, float& v,
                                      float* J /* 6 or nullptr */) {
   bool visible = z > kCamEps;
   float zc = fmaxf(z, kCamEps);

@@ -60,9 +60,12 @@ struct FusedFirst {
 // every pixel.  `flags[blockIdx.x]` == 0 marks such a tile (computed conservatively from the mask / the image,
 // pxt_unet.hip); the workgroup then stores `value` (the layer's output for that constant input, obtained once by
 // running THIS kernel configuration on a constant map: bit for bit what the tile would have computed) and leaves.
+// With `value` == nullptr a flagged-off tile is one whose output NOBODY READS (the reference pass's last two decoder
+// layers, whose maps exist only to be sampled at the projected points: pxt_unet.hip "reference tiles"): the workgroup
+// leaves at once and stores nothing - with a fused head, no record either; the memory keeps what it held.
 struct TileSkip {
   const uint8_t* flags;  // [gridDim.x] or nullptr
-  const half_t* value;   // [Cout]
+  const half_t* value;   // [Cout], or nullptr: store nothing
 };
 
 template <int TH, int BNC, int NT>
@@ -86,6 +89,14 @@ __device__ __forceinline__ void conv_fill_constant_tile(const half_t* __restrict
   }
 }
 
+// The low-resolution patch an UPCAT (bilinear x2 + concat) workgroup stages for a TH-row x 16-column tile at (ty0, tx0):
+// rows up_patch_origin(ty0) .. + up_patch_rows(TH) - 1 and columns up_patch_origin(tx0) .. + kUpPatchW - 1 of `prev`,
+// coordinates clamped into the map.  One statement for the two kernels' staging and for the host-side rule that derives
+// which tiles of `prev` a tile reads (pxt_unet.hip reference tiles).
+constexpr int kUpPatchW = 10;
+__host__ __device__ constexpr int up_patch_rows(int TH) { return TH / 2 + 2; }
+__host__ __device__ constexpr int up_patch_origin(int t0) { return (t0 >> 1) - 1; }
+
 struct ConvArgs {
   const half_t* in;      // [n_img][H][W][Cin]  (UPCAT: the skip tensor [n_img][Hs][Ws][Cin - Cp])
   int H, W, Cin;
@@ -98,7 +109,7 @@ struct ConvArgs {
   half_t* pool;          // optional [n_img][H/2][W/2][Cout]: 2x2 max-pool of `out` (gridDim.z == 1 only)
   FusedHead head;        // head.enabled: Cout == 32, gridDim.z == 1
   FusedFirst first;      // first.enabled: Cin == 64, gridDim.z == 1, the FIRST kernel variant
-  TileSkip skip;         // skip.flags: gridDim.z == 1, no fused head
+  TileSkip skip;         // skip.flags: gridDim.z == 1; with a value to fill in, no fused head
 };
 
 // Host-side mirror of the packed layout: element (cout, tap, cin) lives at
@@ -208,6 +219,7 @@ __global__ __launch_bounds__(256, AR > 3 ? 1 : 2) void conv3x3_v2_kernel(const C
   const half_t* in = a.in + (size_t)img * (UPCAT ? a.up.Hs : H) * in_w * Cs;
   const half_t* prev = UPCAT ? a.up.prev + (size_t)img * a.up.Hp * a.up.Wp * a.up.Cp : nullptr;
   if (a.skip.flags != nullptr && a.skip.flags[blockIdx.x] == 0) {  // (workgroup-uniform) a constant tile: fill and leave
+    if (a.skip.value == nullptr) return;  // a tile nobody reads: nothing is stored (no LDS use, no barrier before this)
     conv_fill_constant_tile<TH, BNC, 256>(a.skip.value, a.out + (size_t)img * H * W * Cout,
                                           a.pool ? a.pool + (size_t)img * (H >> 1) * (W >> 1) * Cout : nullptr, H, W, Cout, ty0,
                                           tx0, co0);
@@ -292,13 +304,13 @@ __global__ __launch_bounds__(256, AR > 3 ? 1 : 2) void conv3x3_v2_kernel(const C
   // of `prev`, one chunk) is copied raw into LDS, then every thread forms its halo pieces from it with
   // the bilinear x2 weights (exactly 0, 1/4, 3/4; align_corners = False) -- LDS latency instead of
   // four dependent global loads per piece, and each low-resolution pixel is fetched once.
-  constexpr int PH = TH / 2 + 2, PW = 10;
+  constexpr int PH = up_patch_rows(TH), PW = kUpPatchW;
   constexpr int kPatchElems = PH * PW * 4, KP = (kPatchElems + 255) / 256;
   static_assert(!UPCAT || KP <= KB, "the patch pieces reuse the halo staging registers");
   char* const patch = smem + 2 * kBuf;
   unsigned poff[UPCAT ? KP : 1], up_src[UPCAT ? KH : 1];
   if (UPCAT) {
-    const int py0 = (ty0 >> 1) - 1, px0 = (tx0 >> 1) - 1;
+    const int py0 = up_patch_origin(ty0), px0 = up_patch_origin(tx0);
 #pragma unroll
     for (int kp = 0; kp < KP; ++kp) {
       const int i = min(tid + 256 * kp, kPatchElems - 1);

@@ -105,7 +105,8 @@ __global__ __launch_bounds__(256 * KS, 2) void conv3x3_v3_kernel(const ConvArgs 
   const int cp0 = UPCAT ? a.up.Cp : 0;         // channels [0, cp0) of the conv input come from `prev`
   const half_t* in = a.in + (size_t)img * (UPCAT ? a.up.Hs : H) * in_w * Cs;
   const half_t* prev = UPCAT ? a.up.prev + (size_t)img * a.up.Hp * a.up.Wp * a.up.Cp : nullptr;
-  if (a.skip.flags != nullptr && a.skip.flags[blockIdx.x] == 0) {  // (workgroup-uniform) a constant tile: pxt_conv_v2.h TileSkip
+  if (a.skip.flags != nullptr && a.skip.flags[blockIdx.x] == 0) {  // (workgroup-uniform) pxt_conv_v2.h TileSkip
+    if (a.skip.value == nullptr) return;  // a tile nobody reads: nothing is stored (no LDS use, no barrier before this)
     conv_fill_constant_tile<TH, BNC, 256 * KS>(a.skip.value, a.out + (size_t)img * H * W * Cout,
                                                a.pool ? a.pool + (size_t)img * (H >> 1) * (W >> 1) * Cout : nullptr, H, W, Cout,
                                                ty0, tx0, co0);
@@ -187,12 +188,12 @@ __global__ __launch_bounds__(256 * KS, 2) void conv3x3_v3_kernel(const ConvArgs 
   // ---- UPCAT, channels below Cp: the low-resolution patch under this tile's halo ((TH/2 + 2) x 10 pixels of `prev`,
   // one chunk) is copied raw into LDS, then every thread forms its halo pieces from it with the bilinear x2 weights
   // (exactly 0, 1/4, 3/4; align_corners = False): each low-resolution pixel is fetched once.
-  constexpr int PH = TH / 2 + 2, PW = 10;
+  constexpr int PH = up_patch_rows(TH), PW = kUpPatchW;
   constexpr int kPatchElems = PH * PW * G::kNP, KP = (kPatchElems + 255) / 256;
   static_assert(!UPCAT || KP <= KH, "the patch pieces reuse the halo staging registers");
   unsigned poff[UPCAT ? KP : 1], up_src[UPCAT ? KH : 1];
   if constexpr (UPCAT) {
-    const int py0 = (ty0 >> 1) - 1, px0 = (tx0 >> 1) - 1;
+    const int py0 = up_patch_origin(ty0), px0 = up_patch_origin(tx0);
 #pragma unroll
     for (int kp = 0; kp < KP; ++kp) {
       const int i = min(tid + 256 * kp, kPatchElems - 1);

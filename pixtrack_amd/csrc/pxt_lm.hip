@@ -839,17 +839,11 @@ __device__ inline bool sample_level(const SampleParams& P, const SampleLevelDev&
     for (int c0 = 4 * sub; c0 < cs; c0 += 4 * LG) *(float4*)(o + c0) = make_float4(0, 0, 0, 0);
     return false;
   }
-  const float fu = floorf(u), fv = floorf(v);
-  const int ix0f = (int)fu, iy0f = (int)fv;
-  const float ax = u - fu, ay = v - fv;
-  const int x1f = min(ix0f + 1, FW - 1), y1f = min(iy0f + 1, FH - 1);
-  const float mx = (ix0f + 1 < FW) ? 1.f : 0.f, my = (iy0f + 1 < FH) ? 1.f : 0.f;
+  const SampleTexels tx = sample_texels(u, v, FW, FH, L.x0, L.y0, W, H);  // (pxt_lm_point.h: shared with the UNet's tile marking)
+  const float ax = tx.ax, ay = tx.ay, mx = tx.mx, my = tx.my;
   const float w00 = (1.f - ax) * (1.f - ay), w10 = ax * (1.f - ay) * mx, w01 = (1.f - ax) * ay * my,
               w11 = ax * ay * mx * my;
-  // window coordinates (the caller's window holds every texel a valid point reads; the clamps only keep a caller's
-  // mistake from reading outside the buffer)
-  const int ix0 = min(max(ix0f - L.x0, 0), W - 1), iy0 = min(max(iy0f - L.y0, 0), H - 1);
-  const int x1 = min(max(x1f - L.x0, 0), W - 1), y1 = min(max(y1f - L.y0, 0), H - 1);
+  const int ix0 = tx.ix0, iy0 = tx.iy0, x1 = tx.x1, y1 = tx.y1;
   const float* p00 = L.fmap + ((size_t)iy0 * W + ix0) * cs;
   const float* p10 = L.fmap + ((size_t)iy0 * W + x1) * cs;
   const float* p01 = L.fmap + ((size_t)y1 * W + ix0) * cs;

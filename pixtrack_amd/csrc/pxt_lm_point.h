@@ -98,7 +98,7 @@ __device__ inline float lm_row16_sum(float v) {
 }
 
 // p = R X + t, the pose as 12 floats (row-major R, then t).
-__device__ inline void transform_point(const float* T, float X, float Y, float Z, float& px, float& py, float& pz) {
+__host__ __device__ inline void transform_point(const float* T, float X, float Y, float Z, float& px, float& py, float& pz) {
   px = T[0] * X + T[1] * Y + T[2] * Z + T[9];
   py = T[3] * X + T[4] * Y + T[5] * Z + T[10];
   pz = T[6] * X + T[7] * Y + T[8] * Z + T[11];
@@ -107,7 +107,7 @@ __device__ inline void transform_point(const float* T, float X, float Y, float Z
 // The validity rule: `valid` so far (in range, mask bit) is narrowed by the projection's own test (project_point: in
 // front of the camera, inside the distortion model's range, inside the image) and by (u, v) lying at least `pad`
 // texels inside the W x H map.  (In/out, not returned: with a returned value lm_refine_kernel's code moves.)
-__device__ inline void point_in_window(const Cam& cam, float px, float py, float pz, bool& valid, int W, int H, float pad,
+__host__ __device__ inline void point_in_window(const Cam& cam, float px, float py, float pz, bool& valid, int W, int H, float pad,
                                        float& u, float& v, float* Jw /* 6 or nullptr */) {
   valid = project_point(cam, px, py, pz, u, v, Jw) && valid;
   valid = valid && (u >= pad) && (v >= pad) && (u <= (float)(W - 1) - pad) && (v <= (float)(H - 1) - pad);
@@ -124,6 +124,34 @@ __device__ inline void bilinear_weights(float u, float v, int& ix0, int& iy0, fl
   w10 = ax * (1.f - ay);
   w01 = (1.f - ax) * ay;
   w11 = ax * ay;
+}
+
+// The 2 x 2 texels the sparse sampler (pxt_lm.hip sample_level) reads for a valid point at (u, v) of an FW x FH level
+// whose map holds the window [x0, x0 + W) x [y0, y0 + H): columns ix0 / x1 and rows iy0 / y1 in WINDOW coordinates, the
+// fractions and the masks of the second column / row (0.f where it would leave the full level; the texel is still read,
+// clamped onto the first).  All four texels are read whatever their weights.  Shared with the reference pass's tile
+// marking (pxt_unet.hip reference_tiles_mark), which must name exactly the texels the sampler will read.
+struct SampleTexels {
+  int ix0, iy0, x1, y1;
+  float ax, ay, mx, my;
+};
+__host__ __device__ inline int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__host__ __device__ inline SampleTexels sample_texels(float u, float v, int FW, int FH, int x0, int y0, int W, int H) {
+  SampleTexels t;
+  const float fu = floorf(u), fv = floorf(v);
+  const int ix0f = (int)fu, iy0f = (int)fv;
+  t.ax = u - fu;
+  t.ay = v - fv;
+  const int x1f = ix0f + 1 < FW ? ix0f + 1 : FW - 1, y1f = iy0f + 1 < FH ? iy0f + 1 : FH - 1;
+  t.mx = (ix0f + 1 < FW) ? 1.f : 0.f;
+  t.my = (iy0f + 1 < FH) ? 1.f : 0.f;
+  // window coordinates (the caller's window holds every texel a valid point reads; the clamps only keep a caller's
+  // mistake from reading outside the buffer)
+  t.ix0 = clamp_int(ix0f - x0, 0, W - 1);
+  t.iy0 = clamp_int(iy0f - y0, 0, H - 1);
+  t.x1 = clamp_int(x1f - x0, 0, W - 1);
+  t.y1 = clamp_int(y1f - y0, 0, H - 1);
+  return t;
 }
 
 // One channel of a point: residual and central-difference map gradients from the 12-texel cross footprint of the five

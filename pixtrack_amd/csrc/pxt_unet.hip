@@ -15,6 +15,7 @@
 // Bias (or the folded BatchNorm affine), ReLU and the encoder's 2x2 max-pool are fused into the
 // epilogue.
 #include "pxt_common.h"
+#include "pxt_lm_point.h"
 #include "pxt_unet_f32.h"
 
 #include <algorithm>
@@ -468,6 +469,69 @@ __global__ void skip_copy_kernel(half_t* __restrict__ dst, const half_t* __restr
 }
 
 // ---------------------------------------------------------------------------
+// Reference tiles: the last two decoder layers of a pass whose maps are only SAMPLED at projected 3-D points (the
+// tracker's reference pass, pixloc_pose_refiners.py:282-290) compute only the tiles a sample depends on.  Their outputs
+// feed nothing but the fine head (the mid head reads the 1/4 decoder layer, the coarse head the encoder), so a tile no
+// sampled texel depends on is dropped exactly; a computed tile keeps its tile plan and K walk, hence its bits.
+//  * fine layer: the tiles that hold one of the 2 x 2 texels of a point that is valid ON THE FINE LEVEL - the sampler's
+//    own arithmetic (pxt_lm_point.h: transform_point, point_in_window, sample_texels), all four texels whatever their
+//    weights (a texel with weight 0 is still read, and 0 x an uncomputed NaN is a NaN);
+//  * the layer before it (half the resolution): the tiles that intersect the low-resolution patch a needed fine tile
+//    stages (pxt_conv_v2.h up_patch_origin / up_patch_rows / kUpPatchW, clamped as the staging clamps) - the whole
+//    patch, since the blend reads patch texels with weight 0 as well.
+// One workgroup does all three steps (clear, mark, spread) behind workgroup barriers: one small launch per pass.
+// ---------------------------------------------------------------------------
+struct RefPoints {
+  const float* p3d;
+  int n;
+  float T[12], cam[10];
+  int ndist;
+  float pad;
+  int x0, y0, fw, fh;  // the fine map is the window [x0, x0 + W) x [y0, y0 + H) of an fw x fh level
+  int W, H;
+};
+struct RefTileGeo {
+  int th, tiles_x, tiles_y;  // tile rows (x 16 columns) and the tile grid of a layer
+};
+// point n: the fine tiles of its four texels
+__host__ __device__ inline void reference_tiles_mark(const RefPoints& P, int n, const RefTileGeo& fine, uint8_t* fine_flags) {
+  const Cam cam = make_cam(P.cam, P.ndist);
+  float px, py, pz, u = 0.f, v = 0.f;
+  transform_point(P.T, P.p3d[3 * n], P.p3d[3 * n + 1], P.p3d[3 * n + 2], px, py, pz);
+  bool valid = true;
+  point_in_window(cam, px, py, pz, valid, P.fw, P.fh, P.pad, u, v, nullptr);
+  if (!valid) return;
+  const SampleTexels t = sample_texels(u, v, P.fw, P.fh, P.x0, P.y0, P.W, P.H);  // (clamped into [0, W) x [0, H))
+  const int c0 = t.ix0 >> 4, c1 = t.x1 >> 4, r0 = t.iy0 / fine.th, r1 = t.y1 / fine.th;
+  fine_flags[r0 * fine.tiles_x + c0] = 1;
+  fine_flags[r0 * fine.tiles_x + c1] = 1;
+  fine_flags[r1 * fine.tiles_x + c0] = 1;
+  fine_flags[r1 * fine.tiles_x + c1] = 1;
+}
+// fine tile i, if needed: the tiles of the low_h x low_w layer before it under its up-sampling patch
+__host__ __device__ inline void reference_tiles_spread(int i, const RefTileGeo& fine, const uint8_t* fine_flags,
+                                                       const RefTileGeo& low, int low_h, int low_w, uint8_t* low_flags) {
+  if (!fine_flags[i]) return;
+  const int ty0 = (i / fine.tiles_x) * fine.th, tx0 = (i % fine.tiles_x) * 16;
+  const int py0 = up_patch_origin(ty0), px0 = up_patch_origin(tx0);
+  const int ya = clamp_int(py0, 0, low_h - 1), yb = clamp_int(py0 + up_patch_rows(fine.th) - 1, 0, low_h - 1);
+  const int xa = clamp_int(px0, 0, low_w - 1), xb = clamp_int(px0 + kUpPatchW - 1, 0, low_w - 1);
+  for (int r = ya / low.th; r <= yb / low.th; ++r)
+    for (int c = xa >> 4; c <= (xb >> 4); ++c) low_flags[r * low.tiles_x + c] = 1;
+}
+__global__ __launch_bounds__(1024) void reference_tiles_kernel(const RefPoints P, const RefTileGeo fine, const RefTileGeo low,
+                                                               int low_h, int low_w, uint8_t* __restrict__ fine_flags,
+                                                               uint8_t* __restrict__ low_flags) {
+  const int n_fine = fine.tiles_x * fine.tiles_y, n_low = low.tiles_x * low.tiles_y;
+  for (int i = threadIdx.x; i < n_fine; i += blockDim.x) fine_flags[i] = 0;
+  for (int i = threadIdx.x; i < n_low; i += blockDim.x) low_flags[i] = 0;
+  __syncthreads();
+  for (int n = threadIdx.x; n < P.n; n += blockDim.x) reference_tiles_mark(P, n, fine, fine_flags);
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_fine; i += blockDim.x) reference_tiles_spread(i, fine, fine_flags, low, low_h, low_w, low_flags);
+}
+
+// ---------------------------------------------------------------------------
 // Context
 // ---------------------------------------------------------------------------
 struct UnetLayer {
@@ -506,6 +570,7 @@ struct pxt_unet {
   } skip_cache[8];
   unsigned long long skip_clock = 0;
   bool tile_skip = true;         // pxt_unet_set_tile_skip
+  bool ref_tiles = true;         // pxt_unet_set_reference_tiles
   void* skip_scratch = nullptr;  // device: raw zero image 48 x 48 x 3 f32 | in map 48 x 48 x 256 f16 | out map | pooled map
   bool plan_as_single = false;  // pxt_unet_set_batch_plan
   bool defer_join = false;    // pxt_unet_set_defer_join: the pair entry leaves the second pass un-joined ...
@@ -530,11 +595,13 @@ std::vector<std::array<int, 3>> parse_plan(const char* e) {
   }
   return v;
 }
+constexpr int kRefTilesDefault = 1;  // (profiles/reference_tiles_ab.md)
 struct Knobs {
   int streams = env_int("PXT_UNET_STREAMS", 2);  // < 2: a batch of two images runs as one batched pass, not two passes
   bool merge_heads = env_int("PXT_UNET_MERGE_HEADS", 1) != 0;  // the two coarse heads of a pass in one launch
   bool skip = env_int("PXT_UNET_SKIP", 1) != 0;                // constant-tile skipping
   bool fuse_first = env_int("PXT_UNET_FUSE_FIRST", 1) != 0;    // the first layer computed in the second one's staging
+  bool ref_tiles = env_int("PXT_UNET_REF_TILES", kRefTilesDefault) != 0;  // a sampled pass computes only the fine tiles it needs
   const char* plan_env = getenv("PXT_CONV_PLAN");
   std::vector<std::array<int, 3>> plan = parse_plan(plan_env);
   bool debug = getenv("PXT_CONV_DEBUG") != nullptr;  // one stderr line per convolution launched
@@ -698,6 +765,7 @@ struct Plan {
   // byte offsets into the workspace
   size_t enc_tmp[5][2], enc_pool[5], enc_out[5], dec_out[4], splitk, splitk_bytes, total;
   size_t skip_grid, skip_flags;  // constant-tile skipping: the 8 x 8 block grid, then the tile flags of layers 1..6
+  size_t ref_flags, ref_flags_each;  // reference tiles: the tile flags of the last decoder layer, then of the one before it
   int skip_bh, skip_bw;
 };
 
@@ -738,6 +806,8 @@ bool make_plan(const pxt_unet* ctx, int n_img, int H, int W, Plan& P) {
   P.skip_grid = take((size_t)n_img * P.skip_bh * P.skip_bw);
   // tiles of a layer: at most (h / 8 + 1) x (w / 16 + 1) (the smallest tile is 8 rows), six layers at strides 1, 2, 2, 4, 4, 4
   P.skip_flags = take((size_t)n_img * 6 * ((size_t)(H / 8 + 2) * (W / 16 + 2)));
+  P.ref_flags_each = align256((size_t)(H / 8 + 2) * (W / 16 + 2));  // (a single-image pass: one image's tiles per layer)
+  P.ref_flags = take(2 * P.ref_flags_each);
   P.total = off;
   return true;
 }
@@ -801,7 +871,8 @@ int launch_tile_cfg(int cfg, bool upcat, const PlanScope& sc, const ConvArgs& a,
 // One 3x3 layer launch.  `wpk`: the packed taps (both layouts).  `partial` (nullptr: no split-K): a split-K region of
 // `partial_cap` bytes.  `up`: a decoder layer (bilinear x2 + concat formed in the staging).  `pool_out` (optional) receives
 // the 2x2 max-pool of the output when the plan allows.  `force_cfg` / `force_splits` (0: automatic) pin the plan.  `head` /
-// `first`: fusions.  `skip`: constant-tile skipping, only with the configuration `skip_cfg` it was made for.
+// `first`: fusions.  `skip`: constant-tile skipping, only with the configuration `skip_cfg` it was made for.  `needed`:
+// tiles nobody reads are left out (TileSkip without a value), only with the configuration `needed_cfg` and one K pass.
 struct ConvLaunch {
   const half_t* in = nullptr;
   half_t* out = nullptr;
@@ -816,6 +887,8 @@ struct ConvLaunch {
   const FusedHead* head = nullptr;
   const FusedFirst* first = nullptr;
   const TileSkip* skip = nullptr;
+  const uint8_t* needed = nullptr;  // reference tiles: per tile of configuration `needed_cfg`, 0 = nobody reads it
+  int needed_cfg = 0;
 };
 
 // The plan launch_conv takes for L: the layer's PXT_CONV_PLAN override, configuration 2 for the fused first layer, a
@@ -868,6 +941,8 @@ int launch_conv(const ConvLaunch& L, const PlanScope& sc, hipStream_t s, bool* p
   a.skip.flags = nullptr;
   a.skip.value = nullptr;
   if (L.skip && L.skip->flags && cp.splits == 1 && !L.head && !up && cp.cfg == L.skip_cfg) a.skip = *L.skip;
+  // reference tiles: a split-K layer computes every tile (its reduction pass walks the whole map)
+  if (L.needed && !a.skip.flags && cp.splits == 1 && L.n_img == 1 && cp.cfg == L.needed_cfg) a.skip.flags = L.needed;
   if (pooled) *pooled = a.pool != nullptr;
   const dim3 grid(cp.tiles, cp.nb, cp.splits);
   if (knobs().debug)
@@ -1145,7 +1220,7 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
                         const int32_t* image_is_u8, const uint8_t* const* masks, int32_t H,
                         int32_t W, float* const* out_maps, const int32_t out_cstride[3],
                         const int32_t* normalize, void* workspace, void* stream, pxt_unet::SideSet& ss,
-                        const PlanScope& sc) {
+                        const PlanScope& sc, const pxt_unet_sample_points* pts = nullptr) {
   if (!ctx || !images || !image_is_u8 || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
   Plan P;
   const int B = n_images;
@@ -1311,6 +1386,57 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
   const half_t* prev = skip[4];
   bool head0_fused = false;
   int ph = P.h[4], pw = P.w[4], pc = ctx->conv[12].cout;
+  const bool fuse_head3 = ctx->dev_head0 != nullptr && out_cstride[0] >= 36;
+  // decoder layer d as launched below, buffers and fusions aside (the reference-tile set-up plans layers 2 and 3 with it)
+  auto decoder_layer = [&](int d, const UpSrc* up) {
+    ConvLaunch cl = pyramid_layer(ctx, 13 + d, P.dh[d], P.dw[d], B);
+    cl.up = up;
+    cl.partial = (d == 3 && fuse_head3) ? nullptr : (float*)(ws + P.splitk);
+    cl.partial_cap = P.splitk_bytes;
+    return cl;
+  };
+  // ---- reference tiles (see reference_tiles_kernel): PXT_UNET_REF_TILES=0 computes every tile ---------------------
+  // Only for a single-image pass that was handed the points its maps will be sampled at, and only with the fused fine
+  // head (a separate head launch would read the whole last layer).  The flags are made for the tile configurations the
+  // two layers are about to take; launch_conv drops them for a layer that ends up with another one or with split-K.
+  const uint8_t* ref_needed[2] = {nullptr, nullptr};  // decoder layers 2 and 3
+  int ref_cfg[2] = {0, 0};
+  if (pts && pts->p3d && B == 1 && knobs().ref_tiles && ctx->ref_tiles && fuse_head3) {
+    const int FW = P.dw[3], FH = P.dh[3];
+    const bool windowed = pts->full_w > 0;
+    if (pts->n_points < 0 || pts->pad < 0 ||
+        (windowed && (pts->full_h < 1 || pts->x0 < 0 || pts->y0 < 0 || pts->x0 + FW > pts->full_w || pts->y0 + FH > pts->full_h)))
+      return PXT_E_ARG;
+    const UpSrc planned{prev, 1, 1, 32, 1, 1};  // (only "a decoder layer" matters to the plan)
+    RefTileGeo geo[2];
+    bool ok = true;
+    for (int k = 0; k < 2; ++k) {
+      const ConvPlan cp = resolve_plan(decoder_layer(2 + k, &planned), sc.at(15 + k));
+      ok = ok && cfg_valid(cp.cfg);
+      if (!ok) break;
+      ref_cfg[k] = cp.cfg;
+      geo[k].th = cfg_th(cp.cfg);
+      geo[k].tiles_x = (P.dw[2 + k] + 15) / 16;
+      geo[k].tiles_y = (P.dh[2 + k] + geo[k].th - 1) / geo[k].th;
+      ok = ok && (size_t)geo[k].tiles_x * geo[k].tiles_y <= P.ref_flags_each;
+    }
+    if (ok) {
+      RefPoints rp;
+      rp.p3d = pts->p3d; rp.n = pts->n_points;
+      for (int i = 0; i < 12; ++i) rp.T[i] = pts->T[i];
+      for (int i = 0; i < 10; ++i) rp.cam[i] = pts->cam[i];
+      rp.ndist = pts->ndist; rp.pad = (float)pts->pad;
+      rp.x0 = windowed ? pts->x0 : 0; rp.y0 = windowed ? pts->y0 : 0;
+      rp.fw = windowed ? pts->full_w : FW; rp.fh = windowed ? pts->full_h : FH;
+      rp.W = FW; rp.H = FH;
+      uint8_t* fine_flags = (uint8_t*)(ws + P.ref_flags);
+      uint8_t* low_flags = fine_flags + P.ref_flags_each;
+      hipLaunchKernelGGL(reference_tiles_kernel, dim3(1), dim3(1024), 0, s, rp, geo[1], geo[0], P.dh[2], P.dw[2], fine_flags,
+                         low_flags);
+      ref_needed[0] = low_flags;
+      ref_needed[1] = fine_flags;
+    }
+  }
   for (int d = 0; d < 4; ++d) {
     const UnetLayer& L = ctx->conv[13 + d];
     const int sb = 3 - d;
@@ -1319,7 +1445,7 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
     const UpSrc up{prev, ph, pw, pc, P.h[sb], P.w[sb]};  // upsample + concat happen in the conv's staging
     half_t* o = buf(P.dec_out[d]);
     FusedHead fh;
-    const bool fuse_head = d == 3 && ctx->dev_head0 != nullptr && out_cstride[0] >= 36;
+    const bool fuse_head = d == 3 && fuse_head3;
     if (fuse_head) {  // the fine head runs in this layer's epilogue; its own output is not materialised
       const char* hb = (const char*)ctx->dev_head0;
       fh.wfrag = (const half8*)hb;
@@ -1330,9 +1456,9 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
       fh.enabled = 1;
       head0_fused = true;
     }
-    ConvLaunch cl = pyramid_layer(ctx, 13 + d, P.dh[d], P.dw[d], B);
-    cl.in = skip[sb]; cl.out = o; cl.up = &up; cl.head = fuse_head ? &fh : nullptr;
-    cl.partial = fuse_head ? nullptr : (float*)(ws + P.splitk); cl.partial_cap = P.splitk_bytes;
+    ConvLaunch cl = decoder_layer(d, &up);
+    cl.in = skip[sb]; cl.out = o; cl.head = fuse_head ? &fh : nullptr;
+    if (d >= 2) { cl.needed = ref_needed[d - 2]; cl.needed_cfg = ref_cfg[d - 2]; }
     const int rc = launch_conv(cl, sc.at(13 + d), s);
     if (rc != PXT_OK) return rc;
     prev = o;
@@ -1396,14 +1522,20 @@ extern "C" int64_t pxt_unet_workspace_bytes_pair(const pxt_unet* ctx, const int3
 // second on a side stream, in two parts of the workspace.  (The frame's reference render and its masked query: equal sizes
 // in the benchmark, different ones with real assets - reference camera x 0.5 / x 0.3 - where the two passes used to run
 // one after the other: 0.54 + 0.54 ms against 0.72 ms side by side.)
-extern "C" int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
-                                     const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
-                                     float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
-                                     void* workspace, void* stream) {
+extern "C" int pxt_unet_forward_pair_sampled(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
+                                             const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
+                                             float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
+                                             void* workspace, void* stream,
+                                             const pxt_unet_sample_points* const* points_host) {
   if (!ctx || !images || !image_is_u8 || !H || !W || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
   if (ctx->f32)
     return pxt::f32_forward_pair(ctx->f32, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace,
                                  (hipStream_t)stream);
+  // (a sampled call stands in for the two-image pxt_unet_forward_batch: with PXT_UNET_STREAMS=1 that one is ONE batched
+  // pass, which computes every tile)
+  if (points_host && knobs().streams < 2 && H[0] == H[1] && W[0] == W[1])
+    return pxt_unet_forward_batch(ctx, 2, images, image_is_u8, masks, H[0], W[0], out_maps, out_cstride, normalize, workspace,
+                                  stream);
   Plan P0, P1;
   if (!make_plan(ctx, 1, H[0], W[0], P0) || !make_plan(ctx, 1, H[1], W[1], P1)) return PXT_E_ARG;
   if (!ctx->pass2) {
@@ -1421,7 +1553,8 @@ extern "C" int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, c
   for (int im = 0; im < 2; ++im) {
     int rc = forward_pass(ctx, 1, images + im, image_is_u8 + im, masks ? masks + im : no_mask, H[im], W[im], out_maps + 3 * im,
                           out_cstride, normalize + im, (char*)workspace + (im ? second : 0),
-                          im == 0 ? (void*)s : (void*)ctx->pass2, ctx->sides[im], PlanScope{2, false, 0});
+                          im == 0 ? (void*)s : (void*)ctx->pass2, ctx->sides[im], PlanScope{2, false, 0},
+                          points_host ? points_host[im] : nullptr);
     if (rc != PXT_OK) return rc;
   }
   PXT_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->pass2));
@@ -1430,6 +1563,50 @@ extern "C" int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, c
     return PXT_OK;
   }
   PXT_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_join, 0));
+  return PXT_OK;
+}
+
+extern "C" int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
+                                     const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
+                                     float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
+                                     void* workspace, void* stream) {
+  return pxt_unet_forward_pair_sampled(ctx, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace,
+                                       stream, nullptr);
+}
+
+extern "C" int pxt_unet_set_reference_tiles(pxt_unet* ctx, int32_t on) {
+  if (!ctx) return PXT_E_ARG;
+  ctx->ref_tiles = on != 0;
+  return PXT_OK;
+}
+
+// The flag rule on the host (tests): reference_tiles_kernel's three steps, the same functions.
+extern "C" int pxt_unet_reference_tiles_host(const pxt_unet_sample_points* points_host, int32_t fine_h, int32_t fine_w,
+                                             int32_t fine_tile_rows, int32_t low_tile_rows, uint8_t* fine_flags_host,
+                                             uint8_t* low_flags_host) {
+  const pxt_unet_sample_points* pts = points_host;
+  if (!pts || (!pts->p3d && pts->n_points > 0) || pts->n_points < 0 || pts->pad < 0 || !fine_flags_host || !low_flags_host)
+    return PXT_E_ARG;
+  if (fine_h < 2 || fine_w < 2 || (fine_h % 2) != 0 || (fine_w % 2) != 0 || fine_tile_rows < 2 || low_tile_rows < 1) return PXT_E_ARG;
+  const bool windowed = pts->full_w > 0;
+  if (windowed && (pts->full_h < 1 || pts->x0 < 0 || pts->y0 < 0 || pts->x0 + fine_w > pts->full_w || pts->y0 + fine_h > pts->full_h))
+    return PXT_E_ARG;
+  RefPoints rp;
+  rp.p3d = pts->p3d; rp.n = pts->n_points;
+  for (int i = 0; i < 12; ++i) rp.T[i] = pts->T[i];
+  for (int i = 0; i < 10; ++i) rp.cam[i] = pts->cam[i];
+  rp.ndist = pts->ndist; rp.pad = (float)pts->pad;
+  rp.x0 = windowed ? pts->x0 : 0; rp.y0 = windowed ? pts->y0 : 0;
+  rp.fw = windowed ? pts->full_w : fine_w; rp.fh = windowed ? pts->full_h : fine_h;
+  rp.W = fine_w; rp.H = fine_h;
+  const int low_h = fine_h / 2, low_w = fine_w / 2;
+  const RefTileGeo fine{fine_tile_rows, (fine_w + 15) / 16, (fine_h + fine_tile_rows - 1) / fine_tile_rows};
+  const RefTileGeo low{low_tile_rows, (low_w + 15) / 16, (low_h + low_tile_rows - 1) / low_tile_rows};
+  std::memset(fine_flags_host, 0, (size_t)fine.tiles_x * fine.tiles_y);
+  std::memset(low_flags_host, 0, (size_t)low.tiles_x * low.tiles_y);
+  for (int n = 0; n < rp.n; ++n) reference_tiles_mark(rp, n, fine, fine_flags_host);
+  for (int i = 0; i < fine.tiles_x * fine.tiles_y; ++i)
+    reference_tiles_spread(i, fine, fine_flags_host, low, low_h, low_w, low_flags_host);
   return PXT_OK;
 }
 
@@ -1460,15 +1637,27 @@ extern "C" int pxt_unet_pair_join(pxt_unet* ctx, void* stream) {
   return PXT_OK;
 }
 
+extern "C" int pxt_unet_forward_sampled(pxt_unet* ctx, const void* image, int32_t image_is_u8, const uint8_t* mask,
+                                        int32_t H, int32_t W, float* const out_maps[3], const int32_t out_cstride[3],
+                                        int32_t normalize, void* workspace, void* stream,
+                                        const pxt_unet_sample_points* points_host) {
+  if (!out_maps) return PXT_E_ARG;
+  const void* images[1] = {image};
+  const uint8_t* masks[1] = {mask};
+  if (!ctx || ctx->f32 || !points_host)
+    return pxt_unet_forward_batch(ctx, 1, images, &image_is_u8, masks, H, W, out_maps, out_cstride, &normalize, workspace,
+                                  stream);
+  if (ctx->join_pending) { PXT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_join, 0)); ctx->join_pending = false; }
+  return forward_pass(ctx, 1, images, &image_is_u8, masks, H, W, out_maps, out_cstride, &normalize, workspace, stream,
+                      ctx->sides[0], PlanScope{1, false, 0}, points_host);
+}
+
 extern "C" int pxt_unet_forward(pxt_unet* ctx, const void* image, int32_t image_is_u8,
                                 const uint8_t* mask, int32_t H, int32_t W, float* const out_maps[3],
                                 const int32_t out_cstride[3], int32_t normalize, void* workspace,
                                 void* stream) {
-  if (!out_maps) return PXT_E_ARG;
-  const void* images[1] = {image};
-  const uint8_t* masks[1] = {mask};
-  return pxt_unet_forward_batch(ctx, 1, images, &image_is_u8, masks, H, W, out_maps, out_cstride, &normalize,
-                                workspace, stream);
+  return pxt_unet_forward_sampled(ctx, image, image_is_u8, mask, H, W, out_maps, out_cstride, normalize, workspace, stream,
+                                  nullptr);
 }
 
 // Per-layer range of the fp16 activations a single-image pass left in `workspace` (see activation_stats_kernel).

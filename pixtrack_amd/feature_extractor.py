@@ -125,9 +125,20 @@ class PixTrackFeatureExtractor:
             img = dst
         return img, mask, scale_resize
 
+    def _arm(self, sample_points) -> None:
+        """The model's next pass is the one these points describe (timing hooks wrap the model's forward methods with
+        their own signatures, so the record does not travel as an argument)."""
+        arm = getattr(self.model, "arm_sample_points", None)
+        if sample_points is not None and arm is not None:
+            arm(sample_points)
+
     def extract_packed(self, image, scale_image: int = 1, mask: Optional[torch.Tensor] = None,
-                       normalize: bool = False):
-        """-> (maps [h,w,cstride] x3 on device, scales [(sx,sy)] x3)."""
+                       normalize: bool = False, sample_points=None):
+        """-> (maps [h,w,cstride] x3 on device, scales [(sx,sy)] x3).
+
+        ``sample_points`` (UNet.forward_packed_batch): the points THIS image's fine map will be sampled at, when that is
+        all that will read it; dropped when the image is resized on the way in (the record describes the unresized
+        levels) and when the maps come from a batched pass elsewhere (preload)."""
         for k, r in enumerate(self._preloaded):
             if r[0] is image and r[1] == scale_image and r[2] is mask and r[3] == normalize:
                 del self._preloaded[k]
@@ -142,6 +153,8 @@ class PixTrackFeatureExtractor:
         a_img, a_mask, a_sr = self._prepare(image, scale_image, mask)
         self.last_input_wh = (int(a_img.shape[1]), int(a_img.shape[0]))
         scales = [(a_sr[0] / s, a_sr[1] / s) for s in self.model.scales]
+        if sample_points is not None and (a_sr != (1.0, 1.0) or tuple(a_img.shape[:2]) != tuple(image.shape[:2])):
+            sample_points = None
         if self._staged is not None:
             st_image, st_scale, st_mask, st_norm = self._staged
             self._staged = None
@@ -151,6 +164,7 @@ class PixTrackFeatureExtractor:
                 if self.defer_join:
                     self.model.set_defer_join(True)
                 try:
+                    self._arm(sample_points)
                     both = self.model.forward_packed_batch([(a_img, a_mask, normalize), (b_img, b_mask, st_norm)])
                 finally:
                     if self.defer_join:
@@ -160,6 +174,7 @@ class PixTrackFeatureExtractor:
                 self._ready = (st_image, st_scale, st_mask, st_norm, both[1],
                                [(b_sr[0] / s, b_sr[1] / s) for s in self.model.scales], b_img, b_mask)
                 return both[0], scales
+        self._arm(sample_points)
         return self.model.forward_packed(a_img, a_mask, normalize=normalize), scales
 
     @torch.no_grad()

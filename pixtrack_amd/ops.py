@@ -85,7 +85,8 @@ SCHEMAS = {
         "(Tensor fmap, int channels, float[] camera, int ndist, Tensor p3d, Tensor fref, Tensor? valid, Tensor poses, "
         "Tensor ranges, int pad, int loss, float loss_alpha, float loss_scale, Tensor(a!) out) -> ()"),
     "unet_forward_batch": (
-        "(int ctx, Tensor[] images, Tensor?[] masks, bool[] normalize, Tensor(a!)[] outs, Tensor(b!) workspace) -> ()"),
+        "(int ctx, Tensor[] images, Tensor?[] masks, bool[] normalize, Tensor(a!)[] outs, Tensor(b!) workspace, "
+        "Tensor? sample_p3d=None, float[]? sample_pose_camera=None, int[]? sample_ints=None) -> ()"),
     "ngp_render": (
         "(int ctx, float[] view, int width, int height, int spp, int mode, Tensor(a!) out, Tensor(b!)? stats) -> ()"),
     "ngp_render_both": (
@@ -465,9 +466,27 @@ def _score_pose_hypotheses(fmap, channels, camera, ndist, p3d, fref, valid, pose
 
 
 # ---------------------------------------------------------------------------------------- UNet
-def _unet_forward_batch(ctx, images, masks, normalize, outs, workspace):
+def _unet_forward_batch(ctx, images, masks, normalize, outs, workspace, sample_p3d=None, sample_pose_camera=None,
+                        sample_ints=None):
+    """``sample_*`` (optional, one or two images): the points the FIRST image's fine map will be sampled at and nothing
+    else will read it for (pxt_unet_sample_points: p3d [N, 3] on the device; 12 pose + 10 fine-level camera floats;
+    ndist, pad, x0, y0, full_w, full_h) - the pass then computes only the fine tiles those samples depend on."""
     L = _lib.lib()
     n = len(images)
+    points = None
+    if sample_p3d is not None:
+        if n > 2 or sample_pose_camera is None or sample_ints is None or len(sample_pose_camera) != 22 or len(sample_ints) != 6:
+            raise _lib.PxtError("unet_forward_batch: sample points go with one image or a pair, 22 floats (pose, camera) "
+                                "and 6 ints (ndist, pad, x0, y0, full_w, full_h)")
+        _f32c(sample_p3d, "sample_p3d")
+        _lib.require_gpu(sample_p3d, "sample_p3d")
+        if sample_p3d.dim() != 2 or sample_p3d.shape[1] != 3 or sample_p3d.device != images[0].device:
+            raise _lib.PxtError("unet_forward_batch: sample_p3d is [N, 3] on the images' device")
+        points = _lib.UnetSamplePoints()
+        points.p3d, points.n_points = sample_p3d.data_ptr(), int(sample_p3d.shape[0])
+        points.T[:] = [float(x) for x in sample_pose_camera[:12]]
+        points.cam[:] = [float(x) for x in sample_pose_camera[12:]]
+        points.ndist, points.pad, points.x0, points.y0, points.full_w, points.full_h = (int(x) for x in sample_ints)
     if n == 0 or len(masks) != n or len(normalize) != n or len(outs) != 3 * n:
         raise _lib.PxtError("unet_forward_batch: per image one mask slot, one normalize flag and three output maps")
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
@@ -497,7 +516,14 @@ def _unet_forward_batch(ctx, images, masks, normalize, outs, workspace):
     norm = (C.c_int32 * n)(*[int(bool(x)) for x in normalize])
     ptrs = (C.c_void_p * (3 * n))(*[o.data_ptr() for o in outs])
     cs = (C.c_int32 * 3)(*[int(o.shape[2]) for o in outs[:3]])
-    if pair:
+    if points is not None and n == 1:
+        _lib.check(L.pxt_unet_forward_sampled(ctx, imgs[0], is_u8[0], mks[0], H, W, ptrs, cs, norm[0], workspace.data_ptr(),
+                                              _stream(images[0]), C.byref(points)), "pxt_unet_forward_sampled")
+    elif points is not None:  # (equal sizes too: the two-image batch entry runs through the pair entry)
+        pp = (C.POINTER(_lib.UnetSamplePoints) * 2)(C.pointer(points), None)
+        _lib.check(L.pxt_unet_forward_pair_sampled(ctx, imgs, is_u8, mks, Hs, Ws, ptrs, cs, norm, workspace.data_ptr(),
+                                                   _stream(images[0]), pp), "pxt_unet_forward_pair_sampled")
+    elif pair:
         _lib.check(L.pxt_unet_forward_pair(ctx, imgs, is_u8, mks, Hs, Ws, ptrs, cs, norm, workspace.data_ptr(),
                                            _stream(images[0])), "pxt_unet_forward_pair")
     else:

@@ -272,10 +272,17 @@ class PoseTrackerRefiner:
             self._points_of([int(dbid)])
 
     # ---- dense features ----------------------------------------------------------
-    def dense_feature_extraction(self, image, name: str, image_scale: int = 1, mask=None, normalize=False):
-        """-> (HWC maps [h,w,cstride] x3 with the confidence as channel C, scales)."""
-        maps, scales = self.feature_extractor.extract_packed(image, image_scale, mask, normalize)
-        if self.tracker is not None and getattr(self.tracker, "debug", 0) >= 2:
+    def dense_feature_extraction(self, image, name: str, image_scale: int = 1, mask=None, normalize=False,
+                                 sample_points=None):
+        """-> (HWC maps [h,w,cstride] x3 with the confidence as channel C, scales).  ``sample_points``
+        (reference_sample_points): the fine map will only be sampled at these points, so the pass may leave the rest of it
+        unwritten - dropped here when the dense maps are handed to the tracker's log."""
+        log_dense = self.tracker is not None and getattr(self.tracker, "debug", 0) >= 2
+        if sample_points is not None and not log_dense:
+            maps, scales = self.feature_extractor.extract_packed(image, image_scale, mask, normalize, sample_points)
+        else:
+            maps, scales = self.feature_extractor.extract_packed(image, image_scale, mask, normalize)
+        if log_dense:
             feats = [m[..., :c].permute(2, 0, 1) for m, c in zip(maps, OUTPUT_DIMS)]
             weight = [m[..., c : c + 1].permute(2, 0, 1) for m, c in zip(maps, OUTPUT_DIMS)]
             self.log_dense(name=name, image=image, image_scale=image_scale, features=feats, scales=scales,
@@ -283,6 +290,37 @@ class PoseTrackerRefiner:
         return maps, scales
 
     # ---- sparse reference observations --------------------------------------------
+    def _level_windows(self, window, n_levels: int):
+        """(x0, y0, full_w, full_h) per level, flattened, of a pass that ran on ``window`` of the reference image."""
+        if window is None:
+            return None
+        x0, y0, fw, fh = window
+        windows = []
+        for level, stride in zip(range(n_levels), self.feature_extractor.model.scales):
+            # level l of the full image: the sizes UNet.level_shapes gives it; the window starts at x0 / stride
+            lh, lw = self.feature_extractor.model.level_shapes(fh, fw)[level]
+            windows += [x0 // stride, y0 // stride, lw, lh]
+        return windows
+
+    def reference_sample_points(self, image_id: int, pose: Pose, p3d: torch.Tensor, image, image_scale: int, window):
+        """What interp_sparse_observations will ask of the FINE map of ``image`` (the arguments of its level 0, built by
+        the same calls), for the UNet pass that is about to compute it: {"p3d", "pose_camera", "ints"}
+        (ops.unet_forward_batch sample_*), or None where the pass has to compute the whole map: an image the extractor
+        resizes (the level cameras then carry the resize factor and the maps another size)."""
+        if not hasattr(image, "shape") or int(p3d.shape[0]) < 1:
+            return None
+        H, W = int(image.shape[0]), int(image.shape[1])
+        h_new, w_new, scale_resize = self.feature_extractor.target_size(H, W, image_scale)
+        if (h_new, w_new) != (H, W):
+            return None
+        camera = self._reference_camera_of(self.model3d.dbs[image_id].camera_id)
+        s0 = self.feature_extractor.model.scales[0]
+        cam_l = camera.scale((scale_resize[0] / s0, scale_resize[1] / s0))
+        pad = self.optimizer[0].interpolator.pad
+        windows = self._level_windows(window, 1) or [0, 0, 0, 0]
+        return {"p3d": p3d, "pose_camera": pose.as12().detach().cpu().reshape(-1).tolist() + cam_l.as10().tolist(),
+                "ints": [int(cam_l._data.shape[-1] - 6), int(pad)] + [int(x) for x in windows]}
+
     def interp_sparse_observations(self, feature_maps: List[torch.Tensor], feature_scales, image_id: int,
                                    p3dids: List[int], pose: Optional[Pose] = None,
                                    p3d: Optional[torch.Tensor] = None, window=None) -> SparseReferenceFeatures:
@@ -303,14 +341,7 @@ class PoseTrackerRefiner:
         valid = torch.empty(n, dtype=torch.uint8, device=self.device)
         pad = self.optimizer[0].interpolator.pad
         T12 = T_w2cam.as12().detach().cpu().reshape(-1).tolist()
-        windows = None
-        if window is not None:
-            x0, y0, fw, fh = window
-            windows = []
-            for fm, stride in zip(feature_maps, self.feature_extractor.model.scales):
-                # level l of the full image: the sizes UNet.level_shapes gives it; the window starts at x0 / stride
-                lh, lw = self.feature_extractor.model.level_shapes(fh, fw)[len(windows) // 4]
-                windows += [x0 // stride, y0 // stride, lw, lh]
+        windows = self._level_windows(window, len(feature_maps))
         ops.sample_sparse(p3d, T12, list(feature_maps), list(OUTPUT_DIMS[:len(feature_maps)]), cams, ndist, int(pad),
                           True, outs, valid, windows)
         return SparseReferenceFeatures(outs, valid, list(p3dids), p3d, OUTPUT_DIMS)
@@ -340,7 +371,11 @@ class PoseTrackerRefiner:
         features = {}
         for image_scale in multiscales:
             image, window = (reference_image, None) if render_points else self.reference_window(dbids, pose, reference_image)
-            maps, scales = self.dense_feature_extraction(image, ref_img.name, image_scale)
+            # the maps of this pass are sampled below and dropped: the pass is told where (not in "render" mode, whose
+            # points are still being made on the device when the pass is planned)
+            sample_points = None if render_points else self.reference_sample_points(dbids[0], pose, p3d, image, image_scale,
+                                                                                    window)
+            maps, scales = self.dense_feature_extraction(image, ref_img.name, image_scale, sample_points=sample_points)
             self.last_reference_wh = self.feature_extractor.last_input_wh  # (w, h) the reference pass ran at
             features[str(image_scale)] = self.interp_sparse_observations(maps, scales, dbids[0], p3dids, pose, p3d, window)
             if render_points:

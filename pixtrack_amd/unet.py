@@ -360,14 +360,23 @@ class UNet:
         return [dec[3], dec[1], (hs[4], ws[4])]  # strides 1, 4, 16
 
     def forward_packed(self, image: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                       normalize: bool = False) -> List[torch.Tensor]:
+                       normalize: bool = False, sample_points=None) -> List[torch.Tensor]:
         """image: HWC, 3 channels, 0..255, float32 or uint8, on the device.  Returns the
-        three HWC float32 maps [h,w,cstride] (descriptor channels then confidence)."""
+        three HWC float32 maps [h,w,cstride] (descriptor channels then confidence).  ``sample_points``: see
+        forward_packed_batch."""
+        if sample_points is not None:
+            self.arm_sample_points(sample_points)
         return self.forward_packed_batch([(image, mask, normalize)])[0]
 
-    def forward_packed_batch(self, items) -> List[List[torch.Tensor]]:
+    def forward_packed_batch(self, items, sample_points=None) -> List[List[torch.Tensor]]:
         """items: [(image, mask or None, normalize)], images of one size (or exactly two of different sizes) -> per
-        image the three maps of forward_packed (pxt_unet_forward_batch / pxt_unet_forward_pair)."""
+        image the three maps of forward_packed (pxt_unet_forward_batch / pxt_unet_forward_pair).
+
+        ``sample_points`` (one image or a pair only): {"p3d", "pose_camera", "ints"} - the points the FIRST image's fine
+        map will be sampled at (ops.unet_forward_batch sample_*).  Tiles of that map no sample depends on are then left
+        unwritten: pass it only when sampling at these points is all that will ever read the map."""
+        # (arm_sample_points: for callers that reach this method through a wrapper taking `items` alone)
+        armed, self._armed_points = getattr(self, "_armed_points", None), None
         n = len(items)
         sizes = [(int(it[0].shape[0]), int(it[0].shape[1])) for it in items]
         H, W = sizes[0]
@@ -384,8 +393,10 @@ class UNet:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         outs = [[torch.empty(h, w, cstride_for(c), device=self.device, dtype=torch.float32)
                  for (h, w), c in zip(self.level_shapes(*hw), OUTPUT_DIMS)] for hw in sizes]
+        sp = (sample_points if sample_points is not None else armed) if n <= 2 else None
         ops.unet_forward_batch(int(self._ctx.value), [it[0] for it in items], [it[1] for it in items],
-                               [bool(it[2]) for it in items], [o for per in outs for o in per], self._ws)
+                               [bool(it[2]) for it in items], [o for per in outs for o in per], self._ws,
+                               *((sp["p3d"], sp["pose_camera"], sp["ints"]) if sp else ()))
         return outs
 
     def set_batch_plan(self, per_image_plan: bool) -> None:
@@ -399,6 +410,16 @@ class UNet:
         cone lies where the input is constant (masked-out query, background of the reference render) are filled with
         the layer's constant output instead of being computed - the same bits."""
         _lib.check(_lib.lib().pxt_unet_set_tile_skip(self._ctx, int(bool(on))), "pxt_unet_set_tile_skip")
+
+    def arm_sample_points(self, sample_points) -> None:
+        """Hands the NEXT forward_packed_batch call its ``sample_points`` (the call consumes them, whatever it does):
+        the same as passing the argument, for a call that goes through a hook wrapped around that method."""
+        self._armed_points = sample_points
+
+    def set_reference_tiles(self, on: bool) -> None:
+        """Whether a pass that is handed sample points computes only the fine tiles they need (pxt_unet_set_reference_tiles;
+        the process-wide A/B knob is PXT_UNET_REF_TILES).  Sampled values are the same bits either way."""
+        _lib.check(_lib.lib().pxt_unet_set_reference_tiles(self._ctx, int(bool(on))), "pxt_unet_set_reference_tiles")
 
     def set_defer_join(self, on: bool) -> None:
         """With True, a two-image call returns with the FIRST image's maps complete in the current stream's order and
