@@ -826,6 +826,96 @@ int pxt_sensor_vsd(const float* depth_est, const float* depth_gt, const uint16_t
                    float sensor_q, float delta_q, const float* tq_host, int32_t n_taus, uint32_t* records,
                    void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Sensor-depth pose refinement behind the LM (opt-in; csrc/pxt_depth_refine.hip).
+ *
+ * No reference counterpart: the reference tracker is monocular.  Starting at a given pose - 12 floats, or the output
+ * record of a pxt_lm_refine* launch queued ahead in the same stream, read ON THE DEVICE - a damped Gauss-Newton
+ * minimises, over the problem's 3-D points X, the robust sum of r = D(u, v) - p.z: the depth sensor's value under the
+ * projected point against the point's own camera depth.  All iterations of all problems run in ONE launch.
+ *
+ * Per point at pose T, all fp32, operation order of csrc/pxt_lm_point.h / pxt_common.h:
+ *   p = transform_point(T, X);  (u, v), Jw = project_point, narrowed by point_in_window with conf.pad.
+ *   reject codes: 1 masked out (point_mask), 2 projection failed (behind the camera or outside the distortion model's
+ *       range), 3 outside the padded image - as pxt_lm_point_report - then
+ *   bilinear_weights(u, v) -> (ix0, iy0), w00..w11; the twelve raw counts of the LM's cross footprint around (ix0, iy0)
+ *       (rows 0 and 3: columns 1, 2; rows 1 and 2: columns 0..3, (ix0, iy0) being row 1, column 1).  A tap outside the
+ *       image reads nothing and counts as raw 0; no address outside the height x width counts is formed.
+ *       4 any raw == 0 (no measurement);  5 float(max raw - min raw) * sensor_scale > max_edge (depth edge);
+ *   a_k = float(raw_k) * sensor_scale;  F, gx, gy: five bilinear values and central differences, as PXT_LM_POINT_CH;
+ *   r = F - p.z;  6 |r| > max_residual (an occluder in front, the far side behind);  else 0, valid.
+ *   rho, w = robust_loss(loss, loss_alpha, loss_scale, r * r);  J0, J1 = point_jacobian(Jw, p);
+ *   J = gx * J0 + gy * J1 - (0, 0, 1, p.y, -p.x, 0)     (translation 3, rotation 3, left update: the LM's delta).
+ * Per evaluation: cost = sum rho, n_valid, g = sum w r J, H = sum w J J^T over the valid points, the counts of codes
+ *   1..6; then the prior: g += P a, H += P, a being the sum of the deltas applied so far (the first-order log of the
+ *   accumulated update).  "Mean cost" is cost / max(n_valid, 1).
+ * Per iteration: the LM's damped solve (H_kk += max(H_kk * lambda_k, 1e-6); Cholesky, pivoted LU when a pivot is not
+ *   positive), the LM's update T <- (so3exp(dw), dt) T, a += delta, the log line, the LM's stop rule (|g| < grad_stop,
+ *   or dt < dt_stop and dR < dR_stop; g includes the prior's term).  After the last update one more evaluation without
+ *   an update gives the final cost.  n_valid < min_valid at ANY evaluation ends the run: failed, the pose stays the one
+ *   that evaluation was made at.
+ * log (optional): line i, PXT_DEPTH_LOG_STRIDE floats, in PXT_LM_LOG_STRIDE's layout: k = 0 mean cost before the update
+ *   of iteration i, 1 n_valid, 2 dR (deg), 3 dt, 4 |g|, 5 1 if the solve fell back to LU, 6, 7 0, 8..19 the pose after the
+ *   update.  codes (optional): row i holds the reject codes of evaluation i (iterations run + 1 rows are written).
+ *
+ * Output record (PXT_DEPTH_RECORD = 32 floats, device or pinned host; word 31 is stored last with system-scope release):
+ *   [0..11] final pose   [12] failed   [13] iterations run (updates applied)
+ *   [14] / [15] mean cost and n_valid at the initial pose      [16] / [17] the same at the final pose
+ *   [18..23] counts of codes 1..6 at the final pose            [24..29] a, the accumulated update   [30] 0
+ *   [31] 1.0 ok; -1.0 skipped (pose_is_lm_record and the LM record failed or timed out: ONLY word 31 is written, log
+ *        and codes stay untouched); -2.0 stopped on n_valid < min_valid.
+ *
+ * One workgroup of 1024 threads per problem; point n belongs to thread n % 1024; sums fold in a fixed order (16-lane
+ * DPP rows, the wave, the waves' partials in LDS by index), no atomics: a problem's output depends on that problem
+ * alone - not on n_problems, its index, or the run.
+ * Bounds: 1 <= n_problems <= PXT_DEPTH_MAX_PROBLEMS, 1 <= n_points <= PXT_DEPTH_MAX_POINTS, 0 <= num_iters <=
+ * PXT_DEPTH_MAX_ITERS, pad >= 0, loss 0..2, min_valid >= 0, width, height >= 4 and width * height <= 2^30, ndist 0 / 2 /
+ * 4; p3d, pose, out and the workspace 16-byte aligned, log 4-byte, sensor 2-byte aligned; the problems' `out` all
+ * different.  Anything else is PXT_E_ARG and nothing is launched or written.
+ * workspace: device, pxt_depth_refine_workspace_bytes(n_problems): the parameter records of a launch of more than two
+ * problems (copied there from pinned staging memory ahead of the launch in `stream`; up to two travel as kernel
+ * arguments); one workspace serves one launch at a time.
+ * Measured on the MI355X: 102 us per call at 600 points, 154 us at 2048 (10 iterations, 640 x 480
+ * sensor image; 9 - 14 us per evaluation), the same for 8 problems per launch as for one.
+ * ---------------------------------------------------------------------- */
+#define PXT_DEPTH_MAX_POINTS 4096
+#define PXT_DEPTH_MAX_ITERS 32
+#define PXT_DEPTH_MAX_PROBLEMS 16
+#define PXT_DEPTH_RECORD 32        /* floats */
+#define PXT_DEPTH_LOG_STRIDE 20    /* floats per logged iteration, layout of PXT_LM_LOG_STRIDE */
+typedef struct {
+  int32_t num_iters;               /* 0..PXT_DEPTH_MAX_ITERS; 0 = evaluate only */
+  int32_t pad;                     /* as pxt_lm_conf.pad */
+  int32_t loss;                    /* robust_loss on x = r * r, as the LM: 0 squared, 1 huber, 2 barron(alpha) */
+  float loss_alpha, loss_scale;
+  float lambda[6];                 /* damping, the LM's rule: H_kk += max(H_kk * lambda_k, 1e-6) */
+  float max_residual;              /* |r| above this: rejected (occluder in front, far side behind) */
+  float max_edge;                  /* depth range over the footprint above this: rejected (depth edge) */
+  float grad_stop, dt_stop, dR_stop;  /* the LM's stop rule */
+  int32_t min_valid;
+} pxt_depth_conf;
+
+typedef struct {
+  const float* p3d;                /* [n_points][3] */
+  const uint8_t* point_mask;       /* [n_points] or NULL */
+  int32_t n_points;                /* 1..PXT_DEPTH_MAX_POINTS */
+  const uint16_t* sensor;          /* [height][width] raw counts, 0 = no measurement */
+  int32_t width, height;
+  float sensor_scale;              /* SfM units per count */
+  float cam[10];                   /* the query camera at the sensor image's size, LM convention */
+  int32_t ndist;
+  const float* pose;               /* device-readable, 16-byte aligned: 12 floats or an LM output record */
+  int32_t pose_is_lm_record;       /* as pxt_lm_info_problem */
+  float prior[21];                 /* symmetric 6x6 prior, upper triangle row-major, (t, w) order; zeros = none */
+  float* out;                      /* PXT_DEPTH_RECORD floats, device or pinned host */
+  float* log;                      /* [num_iters][PXT_DEPTH_LOG_STRIDE] or NULL */
+  uint8_t* codes;                  /* [num_iters + 1][n_points] reject codes or NULL */
+} pxt_depth_problem;
+
+int64_t pxt_depth_refine_workspace_bytes(int32_t n_problems);
+int pxt_depth_refine(const pxt_depth_problem* problems_host, int32_t n_problems, const pxt_depth_conf* conf_host,
+                     void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

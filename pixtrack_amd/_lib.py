@@ -37,6 +37,11 @@ PXT_SYM_ERR_FRAME = 40
 PXT_SYM_ERR_MAX_SYMS = 1024
 PXT_SENSOR_VSD_MAX_TAUS = 16
 PXT_SENSOR_VSD_RECORD = 32
+PXT_DEPTH_MAX_POINTS = 4096
+PXT_DEPTH_MAX_ITERS = 32
+PXT_DEPTH_MAX_PROBLEMS = 16
+PXT_DEPTH_RECORD = 32
+PXT_DEPTH_LOG_STRIDE = 20
 
 
 class PxtError(RuntimeError):
@@ -162,6 +167,20 @@ class LmReportProblem(C.Structure):
                 ("points", C.c_void_p), ("summary", C.c_void_p)]
 
 
+class DepthConf(C.Structure):
+    _fields_ = [("num_iters", C.c_int32), ("pad", C.c_int32), ("loss", C.c_int32), ("loss_alpha", C.c_float),
+                ("loss_scale", C.c_float), ("lambda_", C.c_float * 6), ("max_residual", C.c_float),
+                ("max_edge", C.c_float), ("grad_stop", C.c_float), ("dt_stop", C.c_float), ("dR_stop", C.c_float),
+                ("min_valid", C.c_int32)]
+
+
+class DepthProblem(C.Structure):
+    _fields_ = [("p3d", C.c_void_p), ("point_mask", C.c_void_p), ("n_points", C.c_int32), ("sensor", C.c_void_p),
+                ("width", C.c_int32), ("height", C.c_int32), ("sensor_scale", C.c_float), ("cam", C.c_float * 10),
+                ("ndist", C.c_int32), ("pose", C.c_void_p), ("pose_is_lm_record", C.c_int32), ("prior", C.c_float * 21),
+                ("out", C.c_void_p), ("log", C.c_void_p), ("codes", C.c_void_p)]
+
+
 class RelocMap(C.Structure):
     _fields_ = [
         ("fmap", C.c_void_p),
@@ -277,6 +296,8 @@ PROTOTYPES = {
     "pxt_sensor_vsd_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "pxt_sensor_vsd": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, C.c_float, C.c_float, C.c_float,
                                  C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
+    "pxt_depth_refine_workspace_bytes": (_I64, [_I32]),
+    "pxt_depth_refine": (C.c_int, [C.POINTER(DepthProblem), _I32, C.POINTER(DepthConf), _VP, _VP]),
 }
 
 

@@ -28,6 +28,8 @@ Reference call sites the ops stand in for:
   sensor_vsd           (opt-in, no reference counterpart) P pairs of Depth renders compared with each other and with the
                        frames' sensor depth images: the counts behind BOP's occlusion-aware VSD and the visible
                        fraction (sensor_evaluation.py)
+  depth_refine         (opt-in, no reference counterpart) K sensor-depth pose refinements in one launch, each started at
+                       12 floats or at an lm_refine record read on the device (depth_refinement.py)
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -138,6 +140,16 @@ SCHEMAS = {
     "sensor_vsd": (
         "(Tensor depth_est, Tensor depth_gt, Tensor sensor, Tensor? ray, int[] shift, float min_alpha, float sensor_q, "
         "float delta_q, float[] tq, Tensor(a!) records, Tensor(b!) workspace) -> ()"),
+    # K sensor-depth refinements in one launch (pxt_depth_refine): per problem p3d [N, 3] (N <= 4096), an optional uint8
+    # mask, the sensor image [H, W] uint16 (or int16 holding the same bits), its scale, 10 camera floats, a pose tensor
+    # (device or pinned host: 12 floats, or an lm_refine record when pose_is_lm_record), 21 prior floats, a 32-float
+    # record (device or pinned), an optional log [num_iters, 20] and optional codes uint8 [num_iters + 1, N]
+    "depth_refine": (
+        "(Tensor[] p3d, Tensor?[] point_masks, Tensor[] sensors, float[] sensor_scales, float[] cameras, int[] ndist, "
+        "Tensor[] poses, bool pose_is_lm_record, float[] priors, int num_iters, int pad, int loss, float loss_alpha, "
+        "float loss_scale, float[] lambdas, float max_residual, float max_edge, float grad_stop, float dt_stop, "
+        "float dR_stop, int min_valid, Tensor(a!)[] records, Tensor(b!)?[] logs, Tensor(c!)?[] codes, "
+        "Tensor(d!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -902,7 +914,79 @@ def _sensor_vsd(depth_est, depth_gt, sensor, ray, shift, min_alpha, sensor_q, de
                                 workspace.data_ptr(), _stream(depth_est)), "pxt_sensor_vsd")
 
 
+def _depth_refine(p3d, point_masks, sensors, sensor_scales, cameras, ndist, poses, pose_is_lm_record, priors, num_iters,
+                  pad, loss, loss_alpha, loss_scale, lambdas, max_residual, max_edge, grad_stop, dt_stop, dR_stop,
+                  min_valid, records, logs, codes, workspace):
+    L = _lib.lib()
+    K = len(p3d)
+    if not (1 <= K <= _lib.PXT_DEPTH_MAX_PROBLEMS):
+        raise _lib.PxtError(f"depth_refine: {K} problems (1..{_lib.PXT_DEPTH_MAX_PROBLEMS})")
+    if any(len(x) != K for x in (point_masks, sensors, sensor_scales, ndist, poses, records, logs, codes)) \
+            or len(cameras) != 10 * K or len(priors) != 21 * K or len(lambdas) != 6:
+        raise _lib.PxtError("depth_refine: per problem one mask slot, sensor image, scale, ndist, pose, record, log slot, "
+                            "codes slot, 10 camera floats and 21 prior floats; 6 lambdas")
+    if not (0 <= int(num_iters) <= _lib.PXT_DEPTH_MAX_ITERS):
+        raise _lib.PxtError(f"depth_refine: num_iters {num_iters} (0..{_lib.PXT_DEPTH_MAX_ITERS})")
+    _lib.require_gpu(workspace, "workspace")
+    dev = workspace.device
+    rows = int(num_iters)
+    probs = (_lib.DepthProblem * K)()
+    for k in range(K):
+        pts = _f32c(p3d[k], "p3d")
+        n = int(pts.shape[0])
+        if tuple(pts.shape) != (n, 3) or not (1 <= n <= _lib.PXT_DEPTH_MAX_POINTS):
+            raise _lib.PxtError(f"depth_refine: problem {k}: p3d {tuple(pts.shape)}, expected [N, 3] with 1 <= N <= "
+                                f"{_lib.PXT_DEPTH_MAX_POINTS}")
+        mk, sen, lg, cd = point_masks[k], sensors[k], logs[k], codes[k]
+        if mk is not None and (mk.dtype != torch.uint8 or not mk.is_contiguous() or mk.numel() != n):
+            raise _lib.PxtError("depth_refine: point masks are contiguous uint8 [n_points]")
+        if sen.dtype not in (torch.uint16, torch.int16) or not sen.is_contiguous() or sen.dim() != 2 \
+                or min(int(x) for x in sen.shape) < 4:
+            raise _lib.PxtError(f"depth_refine: sensor {k} is a contiguous uint16 (or int16) [H, W] tensor, H, W >= 4 "
+                                f"(got {tuple(sen.shape)}, {sen.dtype})")
+        if lg is not None and (lg.dtype != torch.float32 or not lg.is_contiguous()
+                               or tuple(lg.shape) != (rows, _lib.PXT_DEPTH_LOG_STRIDE)):
+            raise _lib.PxtError(f"depth_refine: log {k} is a contiguous float32 [{rows}, {_lib.PXT_DEPTH_LOG_STRIDE}] tensor")
+        if cd is not None and (cd.dtype != torch.uint8 or not cd.is_contiguous() or tuple(cd.shape) != (rows + 1, n)):
+            raise _lib.PxtError(f"depth_refine: codes {k} is a contiguous uint8 [{rows + 1}, {n}] tensor")
+        # what the kernel dereferences must be device memory of one device (a host pointer there is a memory fault,
+        # not an error); the pose, the record and the log may also be pinned host memory
+        for t, name in ((pts, "p3d"), (mk, "point_mask"), (sen, "sensor"), (cd, "codes")):
+            if t is None:
+                continue
+            _lib.require_gpu(t, name)
+            if t.device != dev:
+                raise _lib.PxtError(f"depth_refine: {name} of problem {k} is on {t.device}, the workspace on {dev}")
+        need = 16 if pose_is_lm_record else 12
+        for t, name, count in ((poses[k], "pose", need), (records[k], "record", _lib.PXT_DEPTH_RECORD), (lg, "log", 0)):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < count \
+                    or not ((t.is_cuda and t.device == dev) or t.is_pinned()):
+                raise _lib.PxtError(f"depth_refine: {name} {k} needs {count} contiguous float32 values in device or pinned "
+                                    "memory")
+        q = probs[k]
+        q.p3d, q.point_mask, q.n_points = pts.data_ptr(), _lib.dptr(mk), n
+        q.sensor, q.height, q.width = sen.data_ptr(), int(sen.shape[0]), int(sen.shape[1])
+        q.sensor_scale = float(sensor_scales[k])
+        q.cam[:] = [float(x) for x in cameras[10 * k:10 * k + 10]]
+        q.ndist = int(ndist[k])
+        q.pose, q.pose_is_lm_record = poses[k].data_ptr(), int(bool(pose_is_lm_record))
+        q.prior[:] = [float(x) for x in priors[21 * k:21 * k + 21]]
+        q.out, q.log, q.codes = records[k].data_ptr(), _lib.dptr(lg), _lib.dptr(cd)
+    if workspace.numel() * workspace.element_size() < int(L.pxt_depth_refine_workspace_bytes(K)):
+        raise _lib.PxtError("depth_refine: workspace smaller than pxt_depth_refine_workspace_bytes(K)")
+    conf = _lib.DepthConf()
+    conf.num_iters, conf.pad, conf.loss = int(num_iters), int(pad), int(loss)
+    conf.loss_alpha, conf.loss_scale = float(loss_alpha), float(loss_scale)
+    conf.lambda_[:] = [float(x) for x in lambdas]
+    conf.max_residual, conf.max_edge = float(max_residual), float(max_edge)
+    conf.grad_stop, conf.dt_stop, conf.dR_stop, conf.min_valid = float(grad_stop), float(dt_stop), float(dR_stop), int(min_valid)
+    _lib.check(L.pxt_depth_refine(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), "pxt_depth_refine")
+
+
 _IMPLS = {
+    "depth_refine": _depth_refine,
     "sensor_vsd": _sensor_vsd,
     "symmetric_pose_errors": _symmetric_pose_errors,
     "depth_agreement": _depth_agreement,

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import argparse
 import ast
+import logging
 import os
 import pickle as pkl
 from pathlib import Path
@@ -40,6 +41,8 @@ from ..utils.pose_utils import (geodesic_distance_for_rotations, geodesic_distan
 from ..visualization.run_vis_on_poses import get_nerf_image_device, rgba_to_u8
 from .base_pose_tracker import PoseTracker
 
+logger = logging.getLogger(__name__)
+
 
 def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
     """pycolmap.infer_camera_from_image without EXIF: SIMPLE_RADIAL, f = 1.2 max(w, h),
@@ -51,7 +54,7 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
 class PixLocPoseTrackerR9(PoseTracker):
     def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
                  unet_precision="fp16", relocalizer=None, uncertainty=False, reference_points="sfm",
-                 point_report=False):
+                 point_report=False, depth_refine=None):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
         synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
         ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet).
@@ -75,9 +78,21 @@ class PixLocPoseTrackerR9(PoseTracker):
         (point_report.py; None for a frame whose refinement failed); "full" also adds ``point_report``, a dict of numpy
         arrays per point (p2d, valid, cost, rho, robust_weight, confidence, reject), and fills the DebugTracker's
         ``p3d`` / ``p3d_ids`` / ``point_report`` at debug >= 2.  Works with both ``reference_points`` settings.  The
-        cost gate, the pose update and ``tracked`` never read any of it."""
+        cost gate, the pose update and ``tracked`` never read any of it.
+        ``depth_refine``: None (default: nothing changes) or a depth_refinement.DepthRefine (a conf, the sensor's scale, a
+        ``lookup(frame_name) -> uint16 [H, W]`` and an optional diagonal prior): one pxt_depth_refine problem is queued
+        behind the frame's last LM launch - its points, mask and unscaled query camera, the start pose read from the LM's
+        record on the device - and the frame's pose becomes the depth-refined one when the frame succeeded (the LM's
+        success and the cost gate are decided as ever, on the feature cost), the record's status is 1.0, it did not fail
+        and its final mean depth cost is not above the initial one.  The history entry gains ``T_lm``,
+        ``depth_refined``, ``depth_cost_before``, ``depth_cost_after``, ``depth_n_valid`` and ``depth_iters``;
+        ``T_refined`` is the pose carried forward.  The sensor image is fetched and its upload queued before the frame's
+        first launch; a frame with more than 4096 points uses the first 4096 (logged once).  Switches ``render_ahead`` off: the render queued behind the LM launch
+        takes its camera from the LM kernel's epilogue, which is no longer the pose the next frame starts from.  Not
+        combined with a relocalizer yet."""
         point_report = parse_mode(point_report)  # (a bad value: ValueError before anything is built)
         self._check_reference_points(reference_points, relocalizer, uncertainty)
+        self._check_depth_refine(depth_refine, relocalizer)
         self.reference_points = reference_points
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
                               query_list="*_with_intrinsics.txt", global_descriptors="features.h5",
@@ -164,6 +179,18 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._accepted_pose = None  # the last pose a frame accepted (the relocaliser scores it as one more hypothesis)
         self.last_relocalization = None  # RelocResult of the last relocalisation
         self._relocalized_frame = False  # this frame's pose came from the relocaliser (history key "relocalized")
+        self.depth_refine = depth_refine
+        self._depth_conf = self._depth_ws = self._depth_host = self._depth_dev = self._depth_sensor = None
+        self._depth_recs, self._depth_slot, self._depth_warned_points = [], 0, False
+        if depth_refine is not None:
+            from ..depth_refinement import points_extent
+
+            self.render_ahead = False
+            # the conf's lengths are fractions of the model's extent: resolved once, on the host
+            pts = np.array([p.xyz for p in self.localizer.model3d.points3D.values()])
+            self._depth_conf = depth_refine.conf if not depth_refine.conf.relative else depth_refine.conf.resolve(
+                points_extent(pts))
+            self.localizer.refiner.depth_hook = self._enqueue_depth_refine
 
     # ------------------------------------------------------------------ per-variant set-up
     supports_render_points = True  # (the YCB policy does not yet)
@@ -179,6 +206,71 @@ class PixLocPoseTrackerR9(PoseTracker):
                                  "built from the SfM points)")
             if uncertainty:
                 raise ValueError("reference_points='render' is not combined with uncertainty=True yet")
+
+    supports_depth_refine = True  # (the YCB policy does not yet: its refine() does not end in _frame_policy)
+
+    def _check_depth_refine(self, depth_refine, relocalizer):
+        if depth_refine is None:
+            return
+        if not self.supports_depth_refine:
+            raise ValueError(f"depth_refine is not supported by {type(self).__name__} yet")
+        if relocalizer is not None and relocalizer != "off":
+            raise ValueError("depth_refine is not combined with a relocalizer yet")
+        if not callable(getattr(depth_refine, "lookup", None)) or not float(depth_refine.sensor_depth_scale) > 0:
+            raise ValueError("depth_refine: a depth_refinement.DepthRefine with a lookup and a positive sensor_depth_scale")
+
+    def _stage_depth_sensor(self, query_path):
+        """Before the frame's first launch: fetch the frame's sensor image and queue its upload, from a pinned buffer
+        into a device buffer that both live as long as the tracker.  What then stands between the LM launch and the
+        depth problem is the enqueue alone."""
+        self._depth_sensor, self._depth_slot = None, 0
+        sensor = self.depth_refine.lookup(os.path.basename(str(query_path)))
+        if sensor is None:
+            return
+        sensor = np.ascontiguousarray(np.asarray(sensor))
+        if sensor.dtype != np.uint16 or sensor.ndim != 2:
+            raise ValueError(f"the sensor depth image of {query_path} is {sensor.dtype} {sensor.shape}, not uint16 [H, W]")
+        if self._depth_host is None or tuple(self._depth_host.shape) != sensor.shape:
+            self._depth_host = torch.empty(sensor.shape, dtype=torch.int16).pin_memory()
+            self._depth_dev = torch.empty(sensor.shape, dtype=torch.int16, device=self.device)
+            self._depth_uploaded = torch.cuda.Event()
+        else:
+            self._depth_uploaded.synchronize()  # (the last frame's upload: over long ago, unless that frame ended early)
+        self._depth_host.numpy()[...] = sensor.view(np.int16)
+        self._depth_dev.copy_(self._depth_host, non_blocking=True)
+        self._depth_uploaded.record(torch.cuda.current_stream(self.device))
+        self._depth_sensor = self._depth_dev
+
+    def _enqueue_depth_refine(self, prob, pending, qcamera):
+        """The refiner's depth_hook: one pxt_depth_refine problem behind the LM launch `pending`, no host wait between
+        them, on the sensor image `_stage_depth_sensor` uploaded.  None when the frame has no depth image (its pose
+        stays the LM's).  A frame refined against several references queues one problem per reference; `_frame_policy`
+        waits for all of them, so that the records and the sensor buffer are free when the next frame begins."""
+        from ..depth_refinement import MAX_POINTS, RECORD, depth_refine_batch
+
+        opt = self.depth_refine
+        sensor = self._depth_sensor
+        if sensor is None:
+            return None
+        w, h = (int(round(float(x))) for x in qcamera.size.tolist())
+        if tuple(sensor.shape) != (h, w):
+            raise ValueError(f"the sensor depth image of {self._depth_frame_name} is {tuple(sensor.shape)}, the query "
+                             f"{(h, w)}")
+        ref = prob["ref"]
+        if ref.p3d.shape[0] > MAX_POINTS and not self._depth_warned_points:
+            self._depth_warned_points = True
+            logger.warning(f"depth_refine: {ref.p3d.shape[0]} points in a frame, the first {MAX_POINTS} are used")
+        p3d, mask = ref.p3d[:MAX_POINTS], (None if ref.valid is None else ref.valid[:MAX_POINTS])
+        if self._depth_ws is None:
+            self._depth_ws = torch.zeros(int(_lib.lib().pxt_depth_refine_workspace_bytes(1)), dtype=torch.uint8,
+                                         device=self.device)
+        if self._depth_slot == len(self._depth_recs):
+            self._depth_recs.append(torch.zeros(RECORD, dtype=torch.float32).pin_memory())
+        rec = self._depth_recs[self._depth_slot]
+        self._depth_slot += 1
+        return depth_refine_batch([dict(points=p3d, mask=mask, sensor=sensor, sensor_scale=float(opt.sensor_depth_scale),
+                                        camera=qcamera, pose=pending, prior=opt.prior)], self._depth_conf,
+                                  workspace=self._depth_ws, records=[rec])
 
     def _initial_reference_ids(self, assets):
         """r9: the upright reference image named by $UPRIGHT_REF_IMG (:77-78)."""
@@ -515,6 +607,9 @@ class PixLocPoseTrackerR9(PoseTracker):
     def refine(self, query):
         query_path, query_image = query
         refiner = self.localizer.refiner
+        self._depth_frame_name = query_path
+        if self.depth_refine is not None:
+            self._stage_depth_sensor(query_path)
         self._frame_setup(query)
         self.dynamic_id = self.get_dynamic_id(self.pose)
         trackers, rets, costs = {}, {}, {}
@@ -595,6 +690,21 @@ class PixLocPoseTrackerR9(PoseTracker):
             self.cost_threshold = thresh + 0.1 * thresh
 
         success = bool(ret["success"] and min(costs.values()) <= self.cost_threshold)
+        if self.depth_refine is not None:  # (added keys only where the option is on; the LM decided `success` above)
+            from ..depth_refinement import accept, decode_record
+
+            handles = {k: r.pop("depth_pending", None) for k, r in rets.items()}
+            records = {k: None if h is None else h.result()[0] for k, h in handles.items()}  # (waits for every one)
+            rec = decode_record(records[best_ref_id]) if records[best_ref_id] is not None else None
+            ret["T_lm"] = ret.get("T_refined")
+            ret["depth_refined"] = accept(rec, success)
+            seen = rec is not None and rec["status"] != -1.0
+            ret["depth_cost_before"] = rec["cost_before"] if seen else None
+            ret["depth_cost_after"] = rec["cost_after"] if seen else None
+            ret["depth_n_valid"] = rec["n_valid_after"] if seen else 0
+            ret["depth_iters"] = rec["iterations"] if seen else 0
+            if ret["depth_refined"]:
+                ret["T_refined"] = Pose(torch.from_numpy(rec["T"]).double())
         if success:
             self.pose = self._accepted_pose = ret["T_refined"]
         self.success = success
@@ -657,10 +767,46 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--reference_points", choices=("sfm", "render"), default="sfm",
                         help="the points a frame is refined on: sfm (default: the SfM points of the nearest mapping image) "
                              "or render (a lattice of the frame's own depth render, back-projected)")
+    parser.add_argument("--depth_refine", action="store_true",
+                        help="refine every frame's pose on its sensor depth image after the LM (needs --sensor_depth_dir "
+                             "and --sensor_depth_scale)")
+    parser.add_argument("--sensor_depth_dir", type=Path, default=None, help="the 16-bit depth images, one per frame")
+    parser.add_argument("--sensor_depth_scale", type=float, default=None, help="SfM units per raw count")
+    parser.add_argument("--sensor_depth_template", default="{stem}.png",
+                        help="file name of a frame's depth image: {stem} / {name} of the frame (default {stem}.png)")
+    parser.add_argument("--sensor_depth_sub", nargs=2, metavar=("OLD", "NEW"), default=None,
+                        help="replace OLD by NEW in the frame's name first (YCB-Video: color depth)")
+    parser.add_argument("--depth_prior", nargs=2, type=float, metavar=("WT", "WR"), default=None,
+                        help="diagonal prior on the depth refinement's accumulated update: translation, rotation weight")
     parser.add_argument("--relocalize", choices=("off", "views"), default="off",
                         help="off (default: cold start from the upright view, a lost track stays lost) or views "
                              "(relocalise the cold start and the frame after a failed frame against the mapping views)")
     return parser
+
+
+def depth_option_from_args(args):
+    """--depth_refine and its companions -> a depth_refinement.DepthRefine (None when the option is off)."""
+    if not getattr(args, "depth_refine", False):
+        return None
+    if args.sensor_depth_dir is None or args.sensor_depth_scale is None:
+        raise ValueError("--depth_refine needs --sensor_depth_dir and --sensor_depth_scale")
+    from ..depth_refinement import DepthRefine
+    from ..sensor_evaluation import read_sensor_depth, sensor_file_name
+
+    found = []
+
+    def lookup(frame_name):
+        path = Path(args.sensor_depth_dir) / sensor_file_name(frame_name, args.sensor_depth_template, args.sensor_depth_sub)
+        if path.is_file():
+            found.append(path)
+            return read_sensor_depth(path)
+        if not found:  # (a wrong directory, template or substitution: not a run that silently does nothing)
+            raise FileNotFoundError(f"--depth_refine: no sensor depth image {path} for frame {frame_name}")
+        logger.warning(f"depth_refine: no sensor depth image {path}: the pose of {frame_name} stays the LM's")
+        return None
+
+    return DepthRefine(lookup=lookup, sensor_depth_scale=float(args.sensor_depth_scale),
+                       prior=tuple(args.depth_prior) if args.depth_prior else None)
 
 
 def main(argv=None):
@@ -673,7 +819,8 @@ def main(argv=None):
         from ..parallel import bind_to_device_numa
 
         bind_to_device_numa(0)
-    tracker = PixLocPoseTrackerR9(object_path=str(args.object_path), data_path=str(data_path),
+    tracker = PixLocPoseTrackerR9(depth_refine=depth_option_from_args(args),
+                                  object_path=str(args.object_path), data_path=str(data_path),
                                   eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
                                   unet_precision=args.unet_precision, relocalizer=args.relocalize,
                                   uncertainty=args.uncertainty, reference_points=args.reference_points,

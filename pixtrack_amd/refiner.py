@@ -134,6 +134,10 @@ class PoseTrackerRefiner:
         # point records and adds ``point_report``.  Nothing on the tracking path reads them.
         self.point_report = False
         self._report_ws: Optional[torch.Tensor] = None
+        # Opt-in sensor-depth refinement (depth_refinement.py): a callable(prob, pending, qcamera) the tracker sets; it
+        # queues one pxt_depth_refine problem behind the LM launch of a frame's LAST image scale and returns its handle,
+        # which travels back in the result as ``depth_pending``.  None (default): nothing changes.
+        self.depth_hook = None
         self.last_point_report = None  # {"summary", "points" (device [N, 8] or None), "level"} of the last launch
 
     # ---- logging hooks (pixloc BaseRefiner) -----------------------------------
@@ -595,7 +599,8 @@ class PoseTrackerRefiner:
             # reference's bare `except:` at :259-265 would have hidden both).
             plan = self.conf.level_plan
             levels = None if not plan else plan.get(image_scale, plan.get(str(image_scale)))
-            ret = self.refine_pose_using_features(maps_q, scales_q, qcamera, T_init, ref, levels)
+            ret = self.refine_pose_using_features(maps_q, scales_q, qcamera, T_init, ref, levels,
+                                                  last_scale=image_scale == multiscales[-1])
             if not ret["success"]:
                 logger.info(f"Optimization failed for query {qname}")
                 break
@@ -603,10 +608,11 @@ class PoseTrackerRefiner:
         return ret
 
     def refine_pose_using_features(self, features_query: List[torch.Tensor], scales_query, qcamera: Camera,
-                                   T_init: Pose, ref: SparseReferenceFeatures, levels=None) -> Dict:
+                                   T_init: Pose, ref: SparseReferenceFeatures, levels=None, last_scale=True) -> Dict:
         """pixloc BaseRefiner.refine_pose_using_features on packed buffers: coarse -> fine,
         optimizer[level] per level, all levels in one kernel launch.  ``levels`` (optional) keeps
-        only those pyramid levels (conf.level_plan)."""
+        only those pyramid levels (conf.level_plan).  ``last_scale``: this is the frame's last image scale, the one
+        the depth_hook (if set) queues its problem behind."""
         prob = self.lm_problem(features_query, scales_query, qcamera, T_init, ref, levels)
         pending = PixTrackOptimizer.refine_levels(ref.p3d, prob["packs"], T_init, prob["conf"], self._ws, mask=ref.valid,
                                                   camera=prob["camera"])
@@ -619,7 +625,11 @@ class PoseTrackerRefiner:
             self.enqueue_information(prob, pending)
         if self.point_report:  # (behind the information launch, if any)
             self.enqueue_point_report(prob, pending)
-        return self.lm_finish(prob, pending.result())
+        depth = self.depth_hook(prob, pending, qcamera) if (self.depth_hook is not None and last_scale) else None
+        ret = self.lm_finish(prob, pending.result())
+        if depth is not None:
+            ret["depth_pending"] = depth
+        return ret
 
     def lm_problem(self, features_query, scales_query, qcamera: Camera, T_init: Pose, ref: SparseReferenceFeatures,
                    levels=None) -> Dict:
