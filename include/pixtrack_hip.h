@@ -916,6 +916,69 @@ int64_t pxt_depth_refine_workspace_bytes(int32_t n_problems);
 int pxt_depth_refine(const pxt_depth_problem* problems_host, int32_t n_problems, const pxt_depth_conf* conf_host,
                      void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Occlusion handling from the frame's sensor depth image (opt-in; csrc/pxt_occlusion.hip).
+ *
+ * No reference counterpart: the reference tracker masks the query with the silhouette at the last pose and refines on
+ * every point that projects into the image - a hand in front of the object sits inside that silhouette.  With a sensor
+ * depth image the pixels that show something IN FRONT of the object can be told (the bop19 visibility rule of
+ * pxt_sensor_vsd, turned round), taken out of the frame's mask, and the points that project onto them out of the LM's
+ * point mask.
+ *
+ * pxt_occlusion_mask - one image pair:
+ *   depth  [H][W][4] float32 (16-byte aligned): a Depth render; .x = composited depth * depth_scale, .w = alpha (what
+ *       pxt_points_from_depth and pxt_sensor_vsd read).
+ *   sensor [H][W] uint16 (2-byte aligned): the raw counts of the depth sensor, 0 = no measurement.
+ *   shift_x, shift_y: the sensor pixel of render pixel (x, y) is (x + shift_x, y + shift_y); a position outside the
+ *       image reads nothing and counts as raw = 0.  No address outside the H x W counts is ever formed.
+ *   mask_in [H][W] uint8: the frame's plain mask (pxt_depth_mask_plane's output; != 0 counts as 1).
+ *   per pixel, all fp32, every step a single IEEE operation (no FMA contraction):
+ *       sil = v.w >= min_alpha && v.x > 0;  q = v.x / v.w (correctly rounded);  d_s = float(raw) * sensor_q;
+ *       O = sil && raw != 0 && (q - d_s > delta_q)           (false for a NaN; q - d_s == delta_q is NOT occluded);
+ *   E = erosion of O with the (2 r_open + 1)^2 box, pixels outside the image ignored (OpenCV's default border, as
+ *       pxt_depth_mask);  G = dilation of E with the (2 r_grow + 1)^2 box, inside the image;
+ *   mask_out [H][W] uint8 = mask_in && !G;  occluder [H][W] uint8 = G; both 0 / 1, dense (four bytes are stored as one
+ *       dword when W % 4 == 0 and mask_in, mask_out and occluder are all 4-byte aligned).  mask_out != occluder.
+ *   sensor_q, delta_q (host; kernel arguments): the distance of one raw count and the tolerance in units of q - the
+ *       caller divides by the depth-to-distance factor in float64 and rounds once.
+ *   record (PXT_OCCLUSION_RECORD = 16 int32 words, device or pinned host, all written by the last launch):
+ *       [0] n_sil   [1] n_measured (sil && raw != 0)   [2] n_occluded (O)   [3] n_opened (E)   [4] n_occluder (G)
+ *       [5] n_mask_in   [6] n_mask_out   [7] n_sil_occluder (sil && G)   [8..10] 0: pxt_points_visible's   [11..15] 0
+ *   Bounds: width, height >= 1 and width * height <= 2^28, r_open, r_grow >= 0 and r_open + r_grow <=
+ *       PXT_OCCLUSION_MAX_RADIUS, |shift_x|, |shift_y| <= 32767, depth and the workspace 16-byte, record 4-byte, sensor
+ *       2-byte aligned, no NULL; anything else is PXT_E_ARG and nothing is launched or written.
+ *   Deterministic: 64 x 16 tiles on bit planes (wave ballots; shift-AND / shift-OR along x, row AND / OR along y), the
+ *   counts by population count, one partial per workgroup in the workspace, folded in a fixed order by a second
+ *   launch; no atomics: the outputs depend on the call's own inputs only.
+ *   workspace: device memory of pxt_occlusion_mask_workspace_bytes(width, height) bytes (< 0: unsupported sizes); one
+ *   workspace serves one call at a time.  Two launches on `stream`, no host synchronisation, no allocation.
+ *
+ * pxt_points_visible - the point gate, one launch behind it:
+ *   p3d [N][3] float32; valid_in [N] uint8 or NULL (= all 1); pose12_host: the pose the points are seen from (row-major
+ *   R, then t; host, by value); cam10_host / ndist: the UNSCALED query camera as in pxt_depth_problem.cam, cam[0] ==
+ *   width and cam[1] == height; occluder [H][W] uint8: pxt_occlusion_mask's plane.
+ *   per point: p = transform_point(T, X); (u, v) = project_point (csrc/pxt_common.h: the LM's projection, distortion
+ *   included).  Texel k's centre is at coordinate k - the addressing of pxt_depth_refine's centre tap, whose weight is 1
+ *   exactly there - so the point's pixel is (floor(u + 0.5), floor(v + 0.5)).  A point project_point refuses (behind the
+ *   camera, outside the distortion model's range or outside the image) or whose texel is outside the image keeps its
+ *   input value: the LM judges it as before.  Otherwise valid_out = valid_in && !occluder[texel].
+ *   valid_out [N] uint8 (0 / 1; may be valid_in); record: the SAME 16 words, of which [8] n_points, [9] n_points_in
+ *   (valid_in set) and [10] n_points_out (valid_out set) are written; integer counts by ballot, no atomics.
+ *   Bounds: 0 <= N <= 2^24 (N = 0 writes the three words only; p3d and valid_out may then be NULL), ndist 0 / 2 / 4,
+ *   sizes as above; anything else is PXT_E_ARG and nothing is launched or written.
+ * Measured on the MI355X: DESIGN.md 3.13.
+ * ---------------------------------------------------------------------- */
+#define PXT_OCCLUSION_RECORD 16
+#define PXT_OCCLUSION_MAX_RADIUS 16
+int64_t pxt_occlusion_mask_workspace_bytes(int32_t width, int32_t height);
+int pxt_occlusion_mask(const float* depth, const uint16_t* sensor, const uint8_t* mask_in, int32_t width,
+                       int32_t height, int32_t shift_x, int32_t shift_y, float min_alpha, float sensor_q,
+                       float delta_q, int32_t r_open, int32_t r_grow, uint8_t* mask_out, uint8_t* occluder,
+                       int32_t* record, void* workspace, void* stream);
+int pxt_points_visible(const float* p3d, const uint8_t* valid_in, int32_t n_points, const float* pose12_host,
+                       const float* cam10_host, int32_t ndist, const uint8_t* occluder, int32_t width, int32_t height,
+                       uint8_t* valid_out, int32_t* record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,8 @@ PXT_DEPTH_MAX_ITERS = 32
 PXT_DEPTH_MAX_PROBLEMS = 16
 PXT_DEPTH_RECORD = 32
 PXT_DEPTH_LOG_STRIDE = 20
+PXT_OCCLUSION_RECORD = 16
+PXT_OCCLUSION_MAX_RADIUS = 16
 
 
 class PxtError(RuntimeError):
@@ -298,6 +300,11 @@ PROTOTYPES = {
                                  C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
     "pxt_depth_refine_workspace_bytes": (_I64, [_I32]),
     "pxt_depth_refine": (C.c_int, [C.POINTER(DepthProblem), _I32, C.POINTER(DepthConf), _VP, _VP]),
+    "pxt_occlusion_mask_workspace_bytes": (_I64, [_I32, _I32]),
+    "pxt_occlusion_mask": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, C.c_float, C.c_float, C.c_float, _I32, _I32,
+                                     _VP, _VP, _VP, _VP, _VP]),
+    "pxt_points_visible": (C.c_int, [_VP, _VP, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _VP, _I32, _I32,
+                                     _VP, _VP, _VP]),
 }
 
 

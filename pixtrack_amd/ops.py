@@ -30,6 +30,10 @@ Reference call sites the ops stand in for:
                        fraction (sensor_evaluation.py)
   depth_refine         (opt-in, no reference counterpart) K sensor-depth pose refinements in one launch, each started at
                        12 floats or at an lm_refine record read on the device (depth_refinement.py)
+  occlusion_mask       (opt-in, no reference counterpart) get_mask's plane minus the pixels where the frame's sensor depth
+                       image lies in front of the mask view's Depth render, opened and grown (occlusion.py)
+  points_visible       (opt-in, no reference counterpart) the LM's point mask minus the points that project onto that
+                       occluder plane
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -150,6 +154,17 @@ SCHEMAS = {
         "float loss_scale, float[] lambdas, float max_residual, float max_edge, float grad_stop, float dt_stop, "
         "float dR_stop, int min_valid, Tensor(a!)[] records, Tensor(b!)?[] logs, Tensor(c!)?[] codes, "
         "Tensor(d!) workspace) -> ()"),
+    # depth [H, W, 4] (a Depth render), sensor [H, W] uint16 (or int16 holding the same bits), the frame's plain mask
+    # uint8 [H, W], shift = (shift_x, shift_y), radii = (r_open, r_grow) -> mask uint8 [H, W], occluder uint8 [H, W],
+    # record int32 [16] (device or pinned); workspace: uint8, pxt_occlusion_mask_workspace_bytes(W, H)
+    "occlusion_mask": (
+        "(Tensor depth, Tensor sensor, Tensor mask_in, int[] shift, float min_alpha, float sensor_q, float delta_q, "
+        "int[] radii, Tensor(a!) mask, Tensor(b!) occluder, Tensor(c!) record, Tensor(d!) workspace) -> ()"),
+    # p3d [N, 3], an optional uint8 mask [N], 12 pose floats, the unscaled query camera (10 floats, ndist), the occluder
+    # plane of occlusion_mask -> valid uint8 [N] and words 8..10 of the same record (pxt_points_visible)
+    "points_visible": (
+        "(Tensor p3d, Tensor? valid_in, float[] pose, float[] camera, int ndist, Tensor occluder, Tensor(a!) valid, "
+        "Tensor(b!) record) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -985,7 +1000,88 @@ def _depth_refine(p3d, point_masks, sensors, sensor_scales, cameras, ndist, pose
     _lib.check(L.pxt_depth_refine(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), "pxt_depth_refine")
 
 
+def _occlusion_record(record, what):
+    if record.dtype != torch.int32 or not record.is_contiguous() or record.numel() < _lib.PXT_OCCLUSION_RECORD \
+            or not (record.is_cuda or record.is_pinned()):
+        raise _lib.PxtError(f"{what}: record needs {_lib.PXT_OCCLUSION_RECORD} contiguous int32 words in device or pinned "
+                            "memory")
+
+
+def _occlusion_mask(depth, sensor, mask_in, shift, min_alpha, sensor_q, delta_q, radii, mask, occluder, record, workspace):
+    L = _lib.lib()
+    _f32c(depth, "depth")
+    if depth.dim() != 3 or int(depth.shape[2]) != 4:
+        raise _lib.PxtError(f"occlusion_mask: depth is {tuple(depth.shape)}, expected [H, W, 4]")
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    if sensor.dtype not in (torch.uint16, torch.int16) or not sensor.is_contiguous() or tuple(sensor.shape) != (H, W):
+        raise _lib.PxtError(f"occlusion_mask: sensor is a contiguous uint16 (or int16) [{H}, {W}] tensor "
+                            f"(got {tuple(sensor.shape)}, {sensor.dtype})")
+    if mask_in.dtype != torch.uint8 or not mask_in.is_contiguous() or tuple(mask_in.shape) != (H, W):
+        raise _lib.PxtError(f"occlusion_mask: mask_in is a contiguous uint8 [{H}, {W}] tensor")
+    _mask_out(mask, H, W, depth, "occlusion_mask")
+    _mask_out(occluder, H, W, depth, "occlusion_mask")
+    if mask.data_ptr() == occluder.data_ptr():
+        raise _lib.PxtError("occlusion_mask: mask and occluder are two tensors")
+    if len(shift) != 2 or any(abs(int(v)) > 32767 for v in shift):
+        raise _lib.PxtError(f"occlusion_mask: shift is (shift_x, shift_y), each within +-32767 (got {list(shift)})")
+    if len(radii) != 2 or min(int(r) for r in radii) < 0 or int(radii[0]) + int(radii[1]) > _lib.PXT_OCCLUSION_MAX_RADIUS:
+        raise _lib.PxtError(f"occlusion_mask: radii are (r_open, r_grow) >= 0 with r_open + r_grow <= "
+                            f"{_lib.PXT_OCCLUSION_MAX_RADIUS} (got {list(radii)})")
+    _occlusion_record(record, "occlusion_mask")
+    need = int(L.pxt_occlusion_mask_workspace_bytes(W, H))
+    if need <= 0:
+        raise _lib.PxtError(f"occlusion_mask: {W} x {H} is not supported (1..2^28 pixels)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"occlusion_mask: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    for t, name in ((depth, "depth"), (sensor, "sensor"), (mask_in, "mask_in"), (workspace, "workspace")):
+        _lib.require_gpu(t, name)
+        if t.device != depth.device:
+            raise _lib.PxtError(f"occlusion_mask: {name} is on {t.device}, depth on {depth.device}")
+    if record.is_cuda and record.device != depth.device:
+        raise _lib.PxtError(f"occlusion_mask: record is on {record.device}, depth on {depth.device}")
+    _lib.check(L.pxt_occlusion_mask(depth.data_ptr(), sensor.data_ptr(), mask_in.data_ptr(), W, H, int(shift[0]),
+                                    int(shift[1]), float(min_alpha), float(sensor_q), float(delta_q), int(radii[0]),
+                                    int(radii[1]), mask.data_ptr(), occluder.data_ptr(), record.data_ptr(),
+                                    workspace.data_ptr(), _stream(depth)), "pxt_occlusion_mask")
+
+
+def _points_visible(p3d, valid_in, pose, camera, ndist, occluder, valid, record):
+    L = _lib.lib()
+    _f32c(p3d, "p3d")
+    n = int(p3d.shape[0])
+    if tuple(p3d.shape) != (n, 3):
+        raise _lib.PxtError(f"points_visible: p3d is {tuple(p3d.shape)}, expected [N, 3]")
+    if occluder.dtype != torch.uint8 or occluder.dim() != 2 or not occluder.is_contiguous():
+        raise _lib.PxtError("points_visible: occluder is a contiguous uint8 [H, W]")
+    H, W = int(occluder.shape[0]), int(occluder.shape[1])
+    if len(pose) != 12 or len(camera) != 10:
+        raise _lib.PxtError("points_visible: pose holds 12 floats, camera 10")
+    if (float(camera[0]), float(camera[1])) != (float(W), float(H)):
+        raise _lib.PxtError(f"points_visible: the camera is {camera[0]:g} x {camera[1]:g}, the occluder plane {W} x {H}")
+    for t, name in ((valid_in, "valid_in"), (valid, "valid")):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != (n,)):
+            raise _lib.PxtError(f"points_visible: {name} is a contiguous uint8 [{n}] tensor")
+    _occlusion_record(record, "points_visible")
+    _lib.require_gpu(occluder, "occluder")
+    for t, name in ((p3d, "p3d"), (valid_in, "valid_in"), (valid, "valid")):
+        if t is None:
+            continue
+        _lib.require_gpu(t, name)
+        if t.device != occluder.device:
+            raise _lib.PxtError(f"points_visible: {name} is on {t.device}, the occluder plane on {occluder.device}")
+    if record.is_cuda and record.device != occluder.device:
+        raise _lib.PxtError(f"points_visible: record is on {record.device}, the occluder plane on {occluder.device}")
+    T = (C.c_float * 12)(*[float(x) for x in pose])
+    cam = (C.c_float * 10)(*[float(x) for x in camera])
+    _lib.check(L.pxt_points_visible(p3d.data_ptr() if n else None, _lib.dptr(valid_in) if n else None, n, T, cam,
+                                    int(ndist), occluder.data_ptr(), W, H, valid.data_ptr() if n else None,
+                                    record.data_ptr(), _stream(occluder)), "pxt_points_visible")
+
+
 _IMPLS = {
+    "occlusion_mask": _occlusion_mask,
+    "points_visible": _points_visible,
     "depth_refine": _depth_refine,
     "sensor_vsd": _sensor_vsd,
     "symmetric_pose_errors": _symmetric_pose_errors,

@@ -54,7 +54,7 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
 class PixLocPoseTrackerR9(PoseTracker):
     def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
                  unet_precision="fp16", relocalizer=None, uncertainty=False, reference_points="sfm",
-                 point_report=False, depth_refine=None):
+                 point_report=False, depth_refine=None, occlusion=None):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
         synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
         ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet).
@@ -89,10 +89,23 @@ class PixLocPoseTrackerR9(PoseTracker):
         ``T_refined`` is the pose carried forward.  The sensor image is fetched and its upload queued before the frame's
         first launch; a frame with more than 4096 points uses the first 4096 (logged once).  Switches ``render_ahead`` off: the render queued behind the LM launch
         takes its camera from the LM kernel's epilogue, which is no longer the pose the next frame starts from.  Not
-        combined with a relocalizer yet."""
+        combined with a relocalizer yet.
+        ``occlusion``: None (default: nothing changes) or an occlusion.OcclusionMask (a conf, the sensor's scale and a
+        ``lookup(frame_name) -> uint16 [H, W]``): on a frame that gets a mask, the pixels where the frame's sensor depth
+        image lies in front of the mask view's Depth render - opened and grown, pxt_occlusion_mask - leave the query
+        mask, and the reference points that project onto them at the start pose leave the LM's point mask
+        (pxt_points_visible; uncertainty, point report and depth refinement of that frame use the same gated mask).  A
+        frame without a mask (cold start, after a failed frame) or without a sensor image runs as without the option.
+        The history entry gains ``occluded_fraction``, ``n_occluder_pixels``, ``n_points_gated`` and
+        ``occlusion_applied`` (None / 0 / 0 / False where no pass ran); ``last_occlusion`` keeps the frame's tensors.
+        The cost gate, success and ``tracked`` are decided as ever.  ``render_ahead`` stays on: the render queued
+        behind the LM launch keeps its float Depth image, and the pass runs in get_mask of the frame that consumes it.
+        Shares the frame's one sensor upload with ``depth_refine`` (the two options must then name the same lookup and
+        scale).  Not combined with a relocalizer yet."""
         point_report = parse_mode(point_report)  # (a bad value: ValueError before anything is built)
         self._check_reference_points(reference_points, relocalizer, uncertainty)
         self._check_depth_refine(depth_refine, relocalizer)
+        self._check_occlusion(occlusion, relocalizer, depth_refine)
         self.reference_points = reference_points
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
                               query_list="*_with_intrinsics.txt", global_descriptors="features.h5",
@@ -191,6 +204,22 @@ class PixLocPoseTrackerR9(PoseTracker):
             self._depth_conf = depth_refine.conf if not depth_refine.conf.relative else depth_refine.conf.resolve(
                 points_extent(pts))
             self.localizer.refiner.depth_hook = self._enqueue_depth_refine
+        self.occlusion = occlusion
+        self.sensor_uploads = 0       # sensor images staged so far (one per frame that has one, whoever reads it)
+        self.last_occlusion = None    # the tensors and figures of the last frame's occlusion pass (None: none ran)
+        self._occ_conf = self._occ_q = self._occ_shift = self._occ_record = self._occ_ws = self._occ_frame = None
+        if occlusion is not None:
+            from ..depth_refinement import points_extent
+            from ..occlusion import RECORD as OCC_RECORD, quantize
+            from ..render_evaluation import z_scale
+
+            pts = np.array([p.xyz for p in self.localizer.model3d.points3D.values()])
+            self._occ_conf = occlusion.conf if not occlusion.conf.relative else occlusion.conf.resolve(points_extent(pts))
+            # sensor_q, delta_q: formed in float64, rounded once (as sensor_evaluation does)
+            self._occ_q = quantize(self._occ_conf.delta, occlusion.sensor_depth_scale, z_scale(self.testbed, self.nerf2sfm))
+            self._occ_record = torch.zeros(OCC_RECORD, dtype=torch.int32).pin_memory()
+            self._occ_done = torch.cuda.Event()
+            self.localizer.refiner.point_gate = self._gate_points
 
     # ------------------------------------------------------------------ per-variant set-up
     supports_render_points = True  # (the YCB policy does not yet)
@@ -219,12 +248,31 @@ class PixLocPoseTrackerR9(PoseTracker):
         if not callable(getattr(depth_refine, "lookup", None)) or not float(depth_refine.sensor_depth_scale) > 0:
             raise ValueError("depth_refine: a depth_refinement.DepthRefine with a lookup and a positive sensor_depth_scale")
 
+    supports_occlusion = True  # (the YCB policy does not yet: its refine() renders its own mask and has its own tail)
+
+    def _check_occlusion(self, occlusion, relocalizer, depth_refine):
+        if occlusion is None:
+            return
+        if not self.supports_occlusion:
+            raise ValueError(f"occlusion is not supported by {type(self).__name__} yet")
+        if relocalizer is not None and relocalizer != "off":
+            raise ValueError("occlusion is not combined with a relocalizer yet")
+        if not callable(getattr(occlusion, "lookup", None)) or not float(occlusion.sensor_depth_scale) > 0 \
+                or not hasattr(getattr(occlusion, "conf", None), "resolve"):
+            raise ValueError("occlusion: an occlusion.OcclusionMask with a lookup, a positive sensor_depth_scale and a conf")
+        if depth_refine is not None and (depth_refine.lookup is not occlusion.lookup or float(
+                depth_refine.sensor_depth_scale) != float(occlusion.sensor_depth_scale)):
+            raise ValueError("depth_refine and occlusion read ONE sensor image per frame: they must be given the same "
+                             "lookup and the same sensor_depth_scale")
+
     def _stage_depth_sensor(self, query_path):
         """Before the frame's first launch: fetch the frame's sensor image and queue its upload, from a pinned buffer
         into a device buffer that both live as long as the tracker.  What then stands between the LM launch and the
-        depth problem is the enqueue alone."""
+        depth problem is the enqueue alone.  Either option (depth_refine, occlusion) triggers it; one upload per frame
+        serves both - they name the same lookup (_check_occlusion)."""
         self._depth_sensor, self._depth_slot = None, 0
-        sensor = self.depth_refine.lookup(os.path.basename(str(query_path)))
+        option = self.depth_refine if self.depth_refine is not None else self.occlusion  # (one lookup: _check_occlusion)
+        sensor = option.lookup(os.path.basename(str(query_path)))
         if sensor is None:
             return
         sensor = np.ascontiguousarray(np.asarray(sensor))
@@ -240,6 +288,50 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._depth_dev.copy_(self._depth_host, non_blocking=True)
         self._depth_uploaded.record(torch.cuda.current_stream(self.device))
         self._depth_sensor = self._depth_dev
+        self.sensor_uploads += 1
+
+    def _apply_occlusion(self, mask, depth):
+        """get_mask's tail with the option on: the frame's plain mask minus the pixels where the sensor image - staged
+        before the frame's first launch - lies in front of the mask view's Depth render.  Two launches on the frame's
+        stream, nothing awaited; the pinned record is read in _frame_policy.  The plain mask as it is when the option
+        is off, the frame has no sensor image or no float Depth image came with the mask."""
+        if self.occlusion is None or self._depth_sensor is None or depth is None:
+            return mask
+        from ..occlusion import alignment, occlusion_mask
+
+        sensor, conf = self._depth_sensor, self._occ_conf
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        if tuple(sensor.shape) != (H, W):
+            raise ValueError(f"the sensor depth image of {self._depth_frame_name} is {tuple(sensor.shape)}, the query "
+                             f"{(H, W)}")
+        if self._occ_shift is None or self._occ_shift[0] is not self.camera:
+            self._occ_shift = (self.camera, alignment(self.camera, conf.allow_misaligned))
+        sx, sy, _ = self._occ_shift[1]
+        if self._occ_ws is None or self._occ_ws[0] != (W, H):
+            self._occ_ws = ((W, H), torch.empty(int(_lib.lib().pxt_occlusion_mask_workspace_bytes(W, H)), dtype=torch.uint8,
+                                                 device=self.device))
+        out = occlusion_mask(depth, sensor, mask, (sx, sy), conf.min_alpha, self._occ_q[0], self._occ_q[1], conf.r_open,
+                             conf.r_grow, record=self._occ_record, workspace=self._occ_ws[1])
+        self._occ_frame = {"depth": depth, "sensor": sensor, "mask_in": mask, "mask": out["mask"],
+                           "occluder": out["occluder"], "shift": (sx, sy), "min_alpha": conf.min_alpha,
+                           "sensor_q": self._occ_q[0], "delta_q": self._occ_q[1], "radii": (conf.r_open, conf.r_grow),
+                           "gates": []}
+        self._occ_done.record(torch.cuda.current_stream(self.device))
+        return out["mask"]
+
+    def _gate_points(self, ref, T_init, qcamera):
+        """The refiner's point_gate: the LM's point mask of a frame whose occlusion pass ran - ref.valid minus the
+        points whose projection at the start pose falls on the occluder plane (one launch, ahead of the LM's).  None:
+        no pass ran this frame, the LM takes ref.valid."""
+        frame = self._occ_frame
+        if frame is None:
+            return None
+        from ..occlusion import points_visible
+
+        valid, _ = points_visible(ref.p3d, ref.valid, T_init, qcamera, frame["occluder"], record=self._occ_record)
+        frame["gates"].append({"p3d": ref.p3d, "valid_in": ref.valid, "valid": valid, "T_init": T_init, "camera": qcamera})
+        self._occ_done.record(torch.cuda.current_stream(self.device))
+        return valid
 
     def _enqueue_depth_refine(self, prob, pending, qcamera):
         """The refiner's depth_hook: one pxt_depth_refine problem behind the LM launch `pending`, no host wait between
@@ -260,7 +352,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         if ref.p3d.shape[0] > MAX_POINTS and not self._depth_warned_points:
             self._depth_warned_points = True
             logger.warning(f"depth_refine: {ref.p3d.shape[0]} points in a frame, the first {MAX_POINTS} are used")
-        p3d, mask = ref.p3d[:MAX_POINTS], (None if ref.valid is None else ref.valid[:MAX_POINTS])
+        valid = prob.get("mask") if prob.get("mask") is not None else ref.valid  # (the occlusion option's gated mask)
+        p3d, mask = ref.p3d[:MAX_POINTS], (None if valid is None else valid[:MAX_POINTS])
         if self._depth_ws is None:
             self._depth_ws = torch.zeros(int(_lib.lib().pxt_depth_refine_workspace_bytes(1)), dtype=torch.uint8,
                                          device=self.device)
@@ -483,12 +576,13 @@ class PixLocPoseTrackerR9(PoseTracker):
             # when it was enqueued: it stands in for this frame's render only if they are what this frame would use)
             if views == self._ahead_views_now():
                 self._fused_reference = (pose, ref_u8)
-                self._fused_depth = (pose, depth) if depth is not None else None
+                self._fused_depth = (pose, depth) if (depth is not None and self.reference_points == "render") else None
                 self.renders_ahead_used += 1
-                return mask
+                return self._apply_occlusion(mask, depth)
             self.renders_ahead_stale += 1
         self._ahead_ok = None
-        return self._mask_and_reference(pose, from_slot=False)[0]
+        mask = self._mask_and_reference(pose, from_slot=False)[0]
+        return self._apply_occlusion(mask, self._last_depth)
 
     def _frame_views(self):
         """(width, height, fov in degrees on x) of the frame's renders as get_nerf_image sets them up
@@ -510,7 +604,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         object is given; returns (mask, ref_u8).  With reference_points="render" the Depth render also keeps its float
         image (``_fused_depth`` / ``_last_depth``)."""
         tb, spp = self.testbed, int(self.spp)
-        want_depth = self.reference_points == "render"
+        want_depth = self.reference_points == "render" or self.occlusion is not None
         if not from_slot:
             tb.set_nerf_camera_matrix(np.asarray(self._nerf_pose(pose))[:3, :])
         views = self._frame_views()
@@ -529,7 +623,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._last_depth = depth
         if pose is not None:
             self._fused_reference = (pose, ref_u8)
-            self._fused_depth = (pose, depth) if want_depth else None
+            self._fused_depth = (pose, depth) if self.reference_points == "render" else None
         return mask, ref_u8
 
     def _mask_of(self, nz):
@@ -608,9 +702,16 @@ class PixLocPoseTrackerR9(PoseTracker):
         query_path, query_image = query
         refiner = self.localizer.refiner
         self._depth_frame_name = query_path
-        if self.depth_refine is not None:
+        self._occ_frame = None
+        if self.depth_refine is not None or self.occlusion is not None:
             self._stage_depth_sensor(query_path)
         self._frame_setup(query)
+        if self.occlusion is not None and self._depth_sensor is not None:
+            # (on every frame, also one that gets no mask: a wrong sensor directory is not found out frames later)
+            w, h = (int(round(float(x))) for x in self.camera.size.tolist())
+            if tuple(self._depth_sensor.shape) != (h, w):
+                raise ValueError(f"the sensor depth image of {query_path} is {tuple(self._depth_sensor.shape)}, the query "
+                                 f"{(h, w)}")
         self.dynamic_id = self.get_dynamic_id(self.pose)
         trackers, rets, costs = {}, {}, {}
         for ref_id in self.reference_ids:
@@ -705,6 +806,20 @@ class PixLocPoseTrackerR9(PoseTracker):
             ret["depth_iters"] = rec["iterations"] if seen else 0
             if ret["depth_refined"]:
                 ret["T_refined"] = Pose(torch.from_numpy(rec["T"]).double())
+        if self.occlusion is not None:  # (added keys only where the option is on; nothing above read them)
+            # the pinned record: its launches sit ahead of the LM launch whose result is here (the event is over by then;
+            # it is waited for only on a frame that ended before any LM launch)
+            frame, self._occ_frame = self._occ_frame, None
+            if frame is not None:
+                self._occ_done.synchronize()
+            rec = None if frame is None else [int(x) for x in self._occ_record.tolist()]
+            ret["occluded_fraction"] = None if rec is None else (rec[2] / rec[0] if rec[0] else 0.0)
+            ret["n_occluder_pixels"] = 0 if rec is None else rec[4]
+            ret["n_points_gated"] = 0 if rec is None else rec[9] - rec[10]
+            ret["occlusion_applied"] = rec is not None
+            if frame is not None:
+                frame["record"] = rec
+            self.last_occlusion = frame
         if success:
             self.pose = self._accepted_pose = ret["T_refined"]
         self.success = success
@@ -778,19 +893,29 @@ def build_parser() -> argparse.ArgumentParser:
                         help="replace OLD by NEW in the frame's name first (YCB-Video: color depth)")
     parser.add_argument("--depth_prior", nargs=2, type=float, metavar=("WT", "WR"), default=None,
                         help="diagonal prior on the depth refinement's accumulated update: translation, rotation weight")
+    parser.add_argument("--occlusion_mask", action="store_true",
+                        help="take the pixels where the sensor depth image lies in front of the object out of every "
+                             "frame's mask and point set (needs --sensor_depth_dir and --sensor_depth_scale)")
+    parser.add_argument("--occlusion_delta", type=float, default=None,
+                        help="how much closer the sensor's surface must be, as a fraction of the model's extent (default 0.1)")
+    parser.add_argument("--occlusion_radii", nargs=2, type=int, metavar=("OPEN", "GROW"), default=None,
+                        help="box radii of the opening and the growth of the occluder plane (default 1 3)")
     parser.add_argument("--relocalize", choices=("off", "views"), default="off",
                         help="off (default: cold start from the upright view, a lost track stays lost) or views "
                              "(relocalise the cold start and the frame after a failed frame against the mapping views)")
     return parser
 
 
-def depth_option_from_args(args):
-    """--depth_refine and its companions -> a depth_refinement.DepthRefine (None when the option is off)."""
-    if not getattr(args, "depth_refine", False):
-        return None
+def _sensor_lookup_from_args(args, flag: str):
+    """The frame name -> sensor depth image lookup of --sensor_depth_dir / _template / _sub, kept on ``args`` so that
+    --depth_refine and --occlusion_mask share ONE (the tracker uploads a frame's image once for both).  A file missing
+    before any was found raises (a wrong directory, template or substitution: not a run that silently does nothing);
+    later ones are logged and the frame runs without its image."""
     if args.sensor_depth_dir is None or args.sensor_depth_scale is None:
-        raise ValueError("--depth_refine needs --sensor_depth_dir and --sensor_depth_scale")
-    from ..depth_refinement import DepthRefine
+        raise ValueError(f"{flag} needs --sensor_depth_dir and --sensor_depth_scale")
+    lookup = getattr(args, "_sensor_lookup", None)
+    if lookup is not None:
+        return lookup
     from ..sensor_evaluation import read_sensor_depth, sensor_file_name
 
     found = []
@@ -800,13 +925,39 @@ def depth_option_from_args(args):
         if path.is_file():
             found.append(path)
             return read_sensor_depth(path)
-        if not found:  # (a wrong directory, template or substitution: not a run that silently does nothing)
-            raise FileNotFoundError(f"--depth_refine: no sensor depth image {path} for frame {frame_name}")
-        logger.warning(f"depth_refine: no sensor depth image {path}: the pose of {frame_name} stays the LM's")
+        if not found:
+            raise FileNotFoundError(f"{flag}: no sensor depth image {path} for frame {frame_name}")
+        logger.warning(f"{flag}: no sensor depth image {path}: {frame_name} runs without it")
         return None
+
+    args._sensor_lookup = lookup
+    return lookup
+
+
+def depth_option_from_args(args):
+    """--depth_refine and its companions -> a depth_refinement.DepthRefine (None when the option is off)."""
+    if not getattr(args, "depth_refine", False):
+        return None
+    lookup = _sensor_lookup_from_args(args, "--depth_refine")
+    from ..depth_refinement import DepthRefine
 
     return DepthRefine(lookup=lookup, sensor_depth_scale=float(args.sensor_depth_scale),
                        prior=tuple(args.depth_prior) if args.depth_prior else None)
+
+
+def occlusion_option_from_args(args):
+    """--occlusion_mask and its companions -> an occlusion.OcclusionMask (None when the option is off)."""
+    if not getattr(args, "occlusion_mask", False):
+        return None
+    lookup = _sensor_lookup_from_args(args, "--occlusion_mask")
+    from ..occlusion import OcclusionConf, OcclusionMask
+
+    kw = {}
+    if getattr(args, "occlusion_delta", None) is not None:
+        kw["delta"] = float(args.occlusion_delta)
+    if getattr(args, "occlusion_radii", None):
+        kw["r_open"], kw["r_grow"] = (int(x) for x in args.occlusion_radii)
+    return OcclusionMask(lookup=lookup, sensor_depth_scale=float(args.sensor_depth_scale), conf=OcclusionConf(**kw))
 
 
 def main(argv=None):
@@ -819,7 +970,7 @@ def main(argv=None):
         from ..parallel import bind_to_device_numa
 
         bind_to_device_numa(0)
-    tracker = PixLocPoseTrackerR9(depth_refine=depth_option_from_args(args),
+    tracker = PixLocPoseTrackerR9(depth_refine=depth_option_from_args(args), occlusion=occlusion_option_from_args(args),
                                   object_path=str(args.object_path), data_path=str(data_path),
                                   eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
                                   unet_precision=args.unet_precision, relocalizer=args.relocalize,

@@ -59,12 +59,12 @@ class GTFrameIterator:
 class PixLocPoseTrackerYCB(PixLocPoseTrackerR9):
     def __init__(self, data_path, loc_path, eval_path, object_path, debug=False, device=None, assets=None,
                  ycb_root=None, unet_precision="fp16", uncertainty=False, reference_points="sfm",
-                 point_report=False, depth_refine=None):
+                 point_report=False, depth_refine=None, occlusion=None):
         self.object_path = object_path
         self.ycb_root = Path(ycb_root or os.environ.get("YCB_ROOT", "/data/ycb/"))
         super().__init__(object_path, data_path, loc_path, eval_path, debug=int(debug), device=device, assets=assets,
                          unet_precision=unet_precision, uncertainty=uncertainty, reference_points=reference_points,
-                         point_report=point_report, depth_refine=depth_refine)
+                         point_report=point_report, depth_refine=depth_refine, occlusion=occlusion)
         self.reference_scale = 0.3
         self.localizer.refiner.reference_scale = self.reference_scale
         self.localizer.refiner.conf.multiscale = [1]
@@ -75,6 +75,7 @@ class PixLocPoseTrackerYCB(PixLocPoseTrackerR9):
 
     supports_render_points = False  # (its refine() renders the mask every frame: a follow-up)
     supports_depth_refine = False   # (its refine() has its own ground-truth-gated tail, not _frame_policy)
+    supports_occlusion = False      # (the same tail; and its refine() renders the mask itself)
 
     def _initial_reference_ids(self, assets):
         return None  # chosen from the GT pose at the first relocalisation (:117-130)

@@ -138,6 +138,11 @@ class PoseTrackerRefiner:
         # queues one pxt_depth_refine problem behind the LM launch of a frame's LAST image scale and returns its handle,
         # which travels back in the result as ``depth_pending``.  None (default): nothing changes.
         self.depth_hook = None
+        # Opt-in occlusion handling (occlusion.py): a callable(ref, T_init, qcamera) the tracker sets; it returns the
+        # point mask this refinement's LM launch takes instead of ref.valid (uint8 [N] on the device; the launch that
+        # makes it sits ahead of the LM's on the stream), or None for ref.valid.  The information, point report and
+        # depth problems queued behind the launch take the same mask.  None (default): nothing changes.
+        self.point_gate = None
         self.last_point_report = None  # {"summary", "points" (device [N, 8] or None), "level"} of the last launch
 
     # ---- logging hooks (pixloc BaseRefiner) -----------------------------------
@@ -478,7 +483,7 @@ class PoseTrackerRefiner:
         """The information problem of one refinement: its last level in execution order, the pose read from the LM's
         own record on the device."""
         ref = prob["ref"]
-        return {"p3d": ref.p3d, "mask": ref.valid, "pack": prob["packs"][-1], "pose": pending}
+        return {"p3d": ref.p3d, "mask": self._point_mask(prob), "pack": prob["packs"][-1], "pose": pending}
 
     def enqueue_information(self, prob: Dict, pending) -> None:
         if self._info_ws is None:
@@ -508,7 +513,7 @@ class PoseTrackerRefiner:
         handle, index = info
         rec = handle.result()[index]
         pack, level = prob["packs"][-1], prob["order"][-1]
-        self.last_information = {"record": rec, "p3d": prob["ref"].p3d, "mask": prob["ref"].valid, "pack": pack,
+        self.last_information = {"record": rec, "p3d": prob["ref"].p3d, "mask": self._point_mask(prob), "pack": pack,
                                  "level": level}
         if res.failed:
             return self._no_information()
@@ -526,7 +531,7 @@ class PoseTrackerRefiner:
         """The report problem of one refinement: its last level in execution order, the pose read from the LM's own
         record on the device, the points and mask the launch itself used (SfM table or the frame's lattice slots)."""
         ref = prob["ref"]
-        return {"p3d": ref.p3d, "mask": ref.valid, "pack": prob["packs"][-1], "pose": pending,
+        return {"p3d": ref.p3d, "mask": self._point_mask(prob), "pack": prob["packs"][-1], "pose": pending,
                 "points": self.point_report == "full", "inlier_weight": float(self.conf.point_report_inlier_weight)}
 
     def enqueue_point_report(self, prob: Dict, pending) -> None:
@@ -614,8 +619,11 @@ class PoseTrackerRefiner:
         only those pyramid levels (conf.level_plan).  ``last_scale``: this is the frame's last image scale, the one
         the depth_hook (if set) queues its problem behind."""
         prob = self.lm_problem(features_query, scales_query, qcamera, T_init, ref, levels)
-        pending = PixTrackOptimizer.refine_levels(ref.p3d, prob["packs"], T_init, prob["conf"], self._ws, mask=ref.valid,
-                                                  camera=prob["camera"])
+        gated = self.point_gate(ref, T_init, qcamera) if self.point_gate is not None else None
+        if gated is not None:
+            prob["mask"] = gated  # (read by the problems queued behind the launch: _point_mask)
+        pending = PixTrackOptimizer.refine_levels(ref.p3d, prob["packs"], T_init, prob["conf"], self._ws,
+                                                  mask=self._point_mask(prob), camera=prob["camera"])
         # the refinement is enqueued, its result not yet awaited: a caller may queue work behind it that reads the
         # pose record on the device (the tracker's next render, pixloc_tracker_r9._render_ahead)
         hook = getattr(self, "after_lm_enqueued", None)
@@ -630,6 +638,12 @@ class PoseTrackerRefiner:
         if depth is not None:
             ret["depth_pending"] = depth
         return ret
+
+    @staticmethod
+    def _point_mask(prob: Dict):
+        """The point mask of a refinement: the gated one a point_gate made for it, else the reference's own."""
+        mask = prob.get("mask")
+        return prob["ref"].valid if mask is None else mask
 
     def lm_problem(self, features_query, scales_query, qcamera: Camera, T_init: Pose, ref: SparseReferenceFeatures,
                    levels=None) -> Dict:
