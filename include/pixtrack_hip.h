@@ -979,6 +979,74 @@ int pxt_points_visible(const float* p3d, const uint8_t* valid_in, int32_t n_poin
                        const float* cam10_host, int32_t ndist, const uint8_t* occluder, int32_t width, int32_t height,
                        uint8_t* valid_out, int32_t* record, void* stream);
 
+/* -------------------------------------------------------------------------
+ * NeRF mesh extraction: the iso-surface of a scalar lattice as an indexed triangle mesh, and BOP's diameter of a point
+ * set (opt-in; csrc/pxt_iso.hip, pixtrack_amd/mesh.py).
+ *
+ * Reference: testbed.compute_and_save_marching_cubes_mesh (pixtrack/pose_trackers/pixloc_tracker_ycb.py:94).  The
+ * triangulation here is marching TETRAHEDRA on the Freudenthal (Kuhn) split, about twice the triangles of marching
+ * cubes: every cell with base corner c is cut into the six tetrahedra {c, c + e_a, c + e_a + e_b, c + (1,1,1)}, one per
+ * permutation (a, b, .) of the axes in the order (x,y,z) (x,z,y) (y,x,z) (y,z,x) (z,x,y) (z,y,x).  Neighbouring cells
+ * agree on every face diagonal: the mesh is a closed oriented 2-manifold wherever the surface stays inside the lattice.
+ *
+ * The rule (pixtrack_amd/mesh.py iso_surface_reference restates it in numpy; the two agree bit for bit):
+ *   values [nz][ny][nx] float32; point p = (z * ny + y) * nx + x; inside when v >= iso (a NaN is outside).
+ *   A point owns up to seven edges: E0 +x, E1 +y, E2 +z, E3 +x+y, E4 +y+z, E5 +x+z, E6 +x+y+z.  An edge exists when its
+ *   far end is in the lattice and carries a vertex when its ends differ in inside-ness; vertex id = rank of
+ *   (p, edge type) among the vertex-carrying edges.
+ *   position: t = (iso - v_a) / (v_b - v_a), a NaN -> 0.5, else clamped to [0, 1];
+ *       pos = origin + ((x, y, z) + t * d) * spacing per component, every product and sum a single fp32 operation.
+ *   triangles: by cell (= its base point p), then tetrahedron, then triangle within the case.  One or three inside
+ *       corners: one triangle over the three crossing edges, in the order of the three corners on the other side; two
+ *       inside corners {a, b} and two outside {c, d}, each sorted by tet-local index: the quad ac, ad, bd, bc as
+ *       (ac, ad, bd) and (ac, bd, bc).  Each triangle is wound so that its normal points from inside to outside; where
+ *       that needs a turn, its second and third vertex are exchanged.  The winding is part of the case table, decided
+ *       on the unit cube when the table is built, never from the data.
+ *   normals (optional): the central-difference gradient of the lattice at the edge's two ends (one-sided at the border,
+ *       0 along an axis of extent 1; divided by the spacing), interpolated with t, negated, normalised; a zero or
+ *       non-finite length gives (0, 0, 0).
+ *
+ * pxt_iso_case_table: host only, needs no GPU.  out_host [6][16][7] int32: per (tetrahedron, code; bit i of the code =
+ *   tet corner i inside): the number of triangles, then their vertices as (owner corner << 3) | edge type, the owner
+ *   corner being dx | dy << 1 | dz << 2 inside the cell; unused slots -1.  The table is computed by the compiler from
+ *   the unit cube; this copies what the kernels use.
+ * pxt_iso_surface_count: three launches on `stream` - one thread per lattice point (edge mask, counts, exclusive scan per
+ *   workgroup), then two levels that scan the workgroup totals.  counts (device or pinned host) [2] int32: vertices,
+ *   triangles.  The workspace keeps the per-point records for pxt_iso_surface_emit.
+ * pxt_iso_surface_emit: one launch, after the caller has read the counts and allocated vertices [n_vertices][3] float32,
+ *   normals the same or NULL, triangles [n_triangles][3] int32.  values, grid and workspace are those of the count call,
+ *   unchanged.  n_vertices / n_triangles are the sizes of the caller's arrays: nothing is written past them.
+ * Bounds: every extent >= 1 and nx * ny * nz <= 2^27; a lattice without cells (any extent 1) is valid and has no
+ *   triangles; values and the arrays 4-byte, the workspace 16-byte aligned; anything else is PXT_E_ARG and nothing is
+ *   launched or written.  No atomics: the output is a pure function of the input.
+ * workspace: device memory of pxt_iso_surface_workspace_bytes(nx, ny, nz) bytes (< 0: unsupported sizes).
+ *
+ * pxt_max_pairwise_distance - BOP's diameter: the maximum over all pairs of sqrt(dx^2 + dy^2 + dz^2) in fp32.
+ *   points [n][3] float32.  out (device or pinned host) [4] int32: the bits of float d, i, j (i <= j), 1.  The squared
+ *   distances are compared and one square root taken (sqrtf is monotone); ties go to the lowest (i, j); n = 1 gives
+ *   (0, 0, 0); a point with a NaN is in no pair; no comparable pair at all gives (NaN, -1, -1).
+ *   Targets tiled through LDS as in pxt_pose_errors, a partial per workgroup in the workspace, folded in a fixed order
+ *   by a second launch; no atomics.  Bounds: 1 <= n <= 2^22, 4-byte alignment.  workspace: device memory of
+ *   pxt_max_pairwise_distance_workspace_bytes(n) bytes.
+ * Measured on the MI355X: DESIGN.md 3.14.
+ * ---------------------------------------------------------------------- */
+#define PXT_ISO_CASE_TABLE_WORDS (6 * 16 * 7)
+typedef struct {
+  int32_t nx, ny, nz;
+  float iso;
+  float origin[3];                 /* position of lattice point (0, 0, 0) */
+  float spacing[3];                /* distance between neighbouring lattice points along x, y, z */
+} pxt_iso_grid;
+
+int pxt_iso_case_table(int32_t* out_host);
+int64_t pxt_iso_surface_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int pxt_iso_surface_count(const float* values, const pxt_iso_grid* grid_host, void* workspace, int32_t* counts,
+                          void* stream);
+int pxt_iso_surface_emit(const float* values, const pxt_iso_grid* grid_host, const void* workspace, float* vertices,
+                         int32_t n_vertices, float* normals, int32_t* triangles, int32_t n_triangles, void* stream);
+int64_t pxt_max_pairwise_distance_workspace_bytes(int32_t n_points);
+int pxt_max_pairwise_distance(const float* points, int32_t n_points, void* workspace, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

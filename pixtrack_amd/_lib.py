@@ -44,6 +44,7 @@ PXT_DEPTH_RECORD = 32
 PXT_DEPTH_LOG_STRIDE = 20
 PXT_OCCLUSION_RECORD = 16
 PXT_OCCLUSION_MAX_RADIUS = 16
+PXT_ISO_CASE_TABLE_WORDS = 6 * 16 * 7
 
 
 class PxtError(RuntimeError):
@@ -183,6 +184,11 @@ class DepthProblem(C.Structure):
                 ("out", C.c_void_p), ("log", C.c_void_p), ("codes", C.c_void_p)]
 
 
+class IsoGrid(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("iso", C.c_float), ("origin", C.c_float * 3),
+                ("spacing", C.c_float * 3)]
+
+
 class RelocMap(C.Structure):
     _fields_ = [
         ("fmap", C.c_void_p),
@@ -305,6 +311,12 @@ PROTOTYPES = {
                                      _VP, _VP, _VP, _VP, _VP]),
     "pxt_points_visible": (C.c_int, [_VP, _VP, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _VP, _I32, _I32,
                                      _VP, _VP, _VP]),
+    "pxt_iso_case_table": (C.c_int, [C.POINTER(_I32)]),
+    "pxt_iso_surface_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "pxt_iso_surface_count": (C.c_int, [_VP, C.POINTER(IsoGrid), _VP, _VP, _VP]),
+    "pxt_iso_surface_emit": (C.c_int, [_VP, C.POINTER(IsoGrid), _VP, _VP, _I32, _VP, _VP, _I32, _VP]),
+    "pxt_max_pairwise_distance_workspace_bytes": (_I64, [_I32]),
+    "pxt_max_pairwise_distance": (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
 }
 
 

@@ -601,6 +601,28 @@ class Testbed:
     def render(self, width: int, height: int, spp: int = 8, linear: bool = True) -> np.ndarray:
         return self.render_device(width, height, spp, linear).cpu().numpy()
 
+    def compute_marching_cubes_mesh(self, resolution=(128, 128, 128), aabb=None, thresh: float = 2.5) -> Dict[str, np.ndarray]:
+        """pyngp's ``compute_marching_cubes_mesh``: ``{"V", "N", "C", "F"}`` as host arrays in ngp coordinates (vertices,
+        unit normals, colours 0..1, int32 triangles), every connected component kept.  ``aabb``: [[min], [max]] (default: the
+        render box); ``thresh``: iso value of the density LOGIT - 2.5 is instant-ngp's default number and an untuned
+        starting value here.  The triangulation is TETRAHEDRAL (mesh.extract_mesh; csrc/pxt_iso.hip), not instant-ngp's
+        marching cubes: about twice the triangles for the same lattice, closed and consistently oriented."""
+        from .mesh import extract_mesh
+
+        m = extract_mesh(self, list(resolution) if not np.isscalar(resolution) else int(resolution), thresh, aabb,
+                         keep="all")
+        return {k: m[k] for k in ("V", "N", "C", "F")}
+
+    def compute_and_save_marching_cubes_mesh(self, filename, resolution=(128, 128, 128), aabb=None, thresh: float = 2.5):
+        """pyngp's ``compute_and_save_marching_cubes_mesh`` (pixtrack/pose_trackers/pixloc_tracker_ycb.py:94): the mesh of
+        ``compute_marching_cubes_mesh`` written as OBJ, or PLY when ``filename`` ends in ``.ply``, with vertex colours.  The
+        triangulation is tetrahedral: about twice the triangles of marching cubes."""
+        from .mesh import write_mesh
+
+        m = self.compute_marching_cubes_mesh(resolution, aabb, thresh)
+        write_mesh(filename, m["V"], m["F"], m["N"], m["C"])
+        return m
+
     def timing_enable(self, every_nth: int = 1):
         """HIP events around the render kernel launch of every ``every_nth``-th single render (0 / False: off)."""
         _lib.check(_lib.lib().pxt_ngp_timing_enable(self._ctx, int(every_nth)), "pxt_ngp_timing_enable")

@@ -165,6 +165,20 @@ SCHEMAS = {
     "points_visible": (
         "(Tensor p3d, Tensor? valid_in, float[] pose, float[] camera, int ndist, Tensor occluder, Tensor(a!) valid, "
         "Tensor(b!) record) -> ()"),
+    # network query (pxt_ngp_query): pos, dir [n, 3] (ngp coordinates, unit view directions) -> out [n, 4] = (density
+    # logit, r, g, b)
+    "ngp_query": "(int ctx, Tensor pos, Tensor dir, Tensor(a!) out) -> ()",
+    # values [nz, ny, nx] float32, grid = (iso, origin xyz, spacing xyz) -> counts int32 [2] (vertices, triangles; device
+    # or pinned) and the per-point records in workspace: uint8, pxt_iso_surface_workspace_bytes(nx, ny, nz)
+    "iso_surface_count": "(Tensor values, float[] grid, Tensor(a!) workspace, Tensor(b!) counts) -> ()",
+    # the same values, grid and workspace -> vertices [n, 3] float32, normals the same or None, triangles [m, 3] int32,
+    # n and m as iso_surface_count gave them
+    "iso_surface_emit": (
+        "(Tensor values, float[] grid, Tensor workspace, Tensor(a!) vertices, Tensor(b!)? normals, "
+        "Tensor(c!) triangles) -> ()"),
+    # points [n, 3] -> out int32 [4] (device or pinned): bits of float d, i, j, 1 (pxt_max_pairwise_distance); workspace:
+    # uint8, pxt_max_pairwise_distance_workspace_bytes(n)
+    "max_pairwise_distance": "(Tensor points, Tensor(a!) out, Tensor(b!) workspace) -> ()",
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -1079,7 +1093,105 @@ def _points_visible(p3d, valid_in, pose, camera, ndist, occluder, valid, record)
                                     record.data_ptr(), _stream(occluder)), "pxt_points_visible")
 
 
+def _ngp_query(ctx, pos, dir, out):
+    _f32c(pos, "pos")
+    _f32c(dir, "dir")
+    _f32c(out, "out")
+    n = int(pos.shape[0])
+    if tuple(pos.shape) != (n, 3) or tuple(dir.shape) != (n, 3) or tuple(out.shape) != (n, 4) or n < 1:
+        raise _lib.PxtError(f"ngp_query: pos {tuple(pos.shape)} / dir {tuple(dir.shape)} / out {tuple(out.shape)}, expected "
+                            "[n, 3] / [n, 3] / [n, 4], n >= 1")
+    for t, name in ((pos, "pos"), (dir, "dir"), (out, "out")):
+        _lib.require_gpu(t, name)
+        if t.device != pos.device:
+            raise _lib.PxtError(f"ngp_query: {name} is on {t.device}, pos on {pos.device}")
+    _lib.check(_lib.lib().pxt_ngp_query(int(ctx), pos.data_ptr(), dir.data_ptr(), n, out.data_ptr(), _stream(pos)),
+               "pxt_ngp_query")
+
+
+def _iso_grid(values, grid, what):
+    _f32c(values, "values")
+    if values.dim() != 3 or len(grid) != 7:
+        raise _lib.PxtError(f"{what}: values is [nz, ny, nx] (got {tuple(values.shape)}), grid holds iso, origin xyz, "
+                            "spacing xyz")
+    nz, ny, nx = (int(v) for v in values.shape)
+    need = int(_lib.lib().pxt_iso_surface_workspace_bytes(nx, ny, nz)) if min(nx, ny, nz) >= 1 else -1
+    if need <= 0:
+        raise _lib.PxtError(f"{what}: a {nz} x {ny} x {nx} lattice is not supported (every extent >= 1, <= 2^27 points)")
+    g = [float(v) for v in grid]
+    return _lib.IsoGrid(nx, ny, nz, g[0], (C.c_float * 3)(*g[1:4]), (C.c_float * 3)(*g[4:7])), need
+
+
+def _iso_workspace(workspace, need, values, what):
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    for t, name in ((values, "values"), (workspace, "workspace")):
+        _lib.require_gpu(t, name)
+        if t.device != values.device:
+            raise _lib.PxtError(f"{what}: {name} is on {t.device}, the values on {values.device}")
+
+
+def _iso_surface_count(values, grid, workspace, counts):
+    g, need = _iso_grid(values, grid, "iso_surface_count")
+    _iso_workspace(workspace, need, values, "iso_surface_count")
+    if counts.dtype != torch.int32 or not counts.is_contiguous() or counts.numel() < 2 \
+            or not ((counts.is_cuda and counts.device == values.device) or counts.is_pinned()):
+        raise _lib.PxtError("iso_surface_count: counts needs 2 contiguous int32 words on the values' device or in pinned memory")
+    _lib.check(_lib.lib().pxt_iso_surface_count(values.data_ptr(), C.byref(g), workspace.data_ptr(), counts.data_ptr(),
+                                                _stream(values)), "pxt_iso_surface_count")
+
+
+def _iso_surface_emit(values, grid, workspace, vertices, normals, triangles):
+    g, need = _iso_grid(values, grid, "iso_surface_emit")
+    _iso_workspace(workspace, need, values, "iso_surface_emit")
+    _f32c(vertices, "vertices")
+    n, m = int(vertices.shape[0]), int(triangles.shape[0])
+    if tuple(vertices.shape) != (n, 3) or triangles.dtype != torch.int32 or not triangles.is_contiguous() \
+            or tuple(triangles.shape) != (m, 3):
+        raise _lib.PxtError(f"iso_surface_emit: vertices is float32 [n, 3], triangles contiguous int32 [m, 3] (got "
+                            f"{tuple(vertices.shape)}, {tuple(triangles.shape)} {triangles.dtype})")
+    if normals is not None and (_f32c(normals, "normals").shape != vertices.shape):
+        raise _lib.PxtError(f"iso_surface_emit: normals is float32 {tuple(vertices.shape)}")
+    for t, name in ((vertices, "vertices"), (normals, "normals"), (triangles, "triangles")):
+        if t is None:
+            continue
+        _lib.require_gpu(t, name)
+        if t.device != values.device:
+            raise _lib.PxtError(f"iso_surface_emit: {name} is on {t.device}, the values on {values.device}")
+    _lib.check(_lib.lib().pxt_iso_surface_emit(values.data_ptr(), C.byref(g), workspace.data_ptr(),
+                                               vertices.data_ptr() if n else None, n,
+                                               _lib.dptr(normals) if n else None, triangles.data_ptr() if m else None, m,
+                                               _stream(values)), "pxt_iso_surface_emit")
+
+
+def _max_pairwise_distance(points, out, workspace):
+    L = _lib.lib()
+    _f32c(points, "points")
+    n = int(points.shape[0])
+    if tuple(points.shape) != (n, 3):
+        raise _lib.PxtError(f"max_pairwise_distance: points is {tuple(points.shape)}, expected [n, 3]")
+    need = int(L.pxt_max_pairwise_distance_workspace_bytes(n))
+    if need <= 0:
+        raise _lib.PxtError(f"max_pairwise_distance: {n} points is not supported (1..2^22)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"max_pairwise_distance: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() < 4 \
+            or not ((out.is_cuda and out.device == points.device) or out.is_pinned()):
+        raise _lib.PxtError("max_pairwise_distance: out needs 4 contiguous int32 words on the points' device or in pinned "
+                            "memory")
+    for t, name in ((points, "points"), (workspace, "workspace")):
+        _lib.require_gpu(t, name)
+        if t.device != points.device:
+            raise _lib.PxtError(f"max_pairwise_distance: {name} is on {t.device}, the points on {points.device}")
+    _lib.check(L.pxt_max_pairwise_distance(points.data_ptr(), n, workspace.data_ptr(), out.data_ptr(), _stream(points)),
+               "pxt_max_pairwise_distance")
+
+
 _IMPLS = {
+    "ngp_query": _ngp_query,
+    "iso_surface_count": _iso_surface_count,
+    "iso_surface_emit": _iso_surface_emit,
+    "max_pairwise_distance": _max_pairwise_distance,
     "occlusion_mask": _occlusion_mask,
     "points_visible": _points_visible,
     "depth_refine": _depth_refine,
