@@ -1047,6 +1047,67 @@ int pxt_iso_surface_emit(const float* values, const pxt_iso_grid* grid_host, con
 int64_t pxt_max_pairwise_distance_workspace_bytes(int32_t n_points);
 int pxt_max_pairwise_distance(const float* points, int32_t n_points, void* workspace, int32_t* out, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Mesh rasteriser: depth images of a triangle mesh through a pinhole camera (opt-in; csrc/pxt_raster.hip,
+ * pixtrack_amd/mesh_render.py, pixtrack_amd/mesh_evaluation.py).
+ *
+ * Reference: render_image (pixtrack/utils/pytorch3d_render_utils.py:55-93) and the YCB ground-truth renders built on
+ * it.  BOP's VSD compares depth renders of the model's mesh at the estimated and the ground-truth pose; this draws
+ * them.  An evaluation rasteriser for an object in front of the camera: no colour, no shading, no anti-aliasing, no
+ * near-plane clipping, no lens terms.
+ *
+ * The rule (mesh_render.rasterize_reference restates it in numpy; the two agree bit for bit on every output):
+ *   vertices [V][3] float32 (object frame); triangles [T][3] int32; views [P][PXT_MESH_VIEW = 20] float32:
+ *       [0..8] R row-major, [9..11] t (world -> camera), [12..15] fx fy cx cy, [16] near, [17] depth_q, [18..19] 0 -
+ *       formed on the host in float64 and rounded once.  A pinhole as in pxt_symmetric_pose_errors, in the Camera
+ *       convention: pixel centres at integer coordinates, pixel (i, j) is sampled at image point (i, j).
+ *   per vertex, every operation a single fp32 operation (no contraction, IEEE division):
+ *       p_k = ((R_k0 v0 + R_k1 v1) + R_k2 v2) + t_k;   x = fx * (p.x / p.z) + cx, y likewise;
+ *       X = (int) rintf(x * 256), Y likewise (eight sub-pixel bits);   iz = 1 / p.z.
+ *       The vertex is "guard" when p is not finite; else "near" when p.z <= near; else "guard" when
+ *       |rintf(x * 256)| < 2^23 does not hold, or the same for y (a non-finite x or y fails it too).
+ *   per triangle, culled whole and counted under the FIRST of these causes that holds:
+ *       bad index (one outside [0, V); no address outside the vertex array is formed); guard (any vertex); near (any
+ *       vertex); zero area; off-screen.  A = (X1 - X0) (Y2 - Y0) - (Y1 - Y0) (X2 - X0) in int64; A == 0 is zero area;
+ *       A < 0 exchanges the second and third vertex (X, Y, iz) and negates A.  No back-face culling.  Off-screen: the
+ *       sub-pixel bounding box misses [0, 256 (W - 1)] x [0, 256 (H - 1)].  Every other triangle counts as drawn,
+ *       whether or not a pixel centre falls inside it.
+ *   coverage of pixel (i, j), P = (256 i, 256 j), inside the box clipped to the image: the edge functions
+ *       e_0 over (v1, v2), e_1 over (v2, v0), e_2 over (v0, v1), e(a, b) = (Xb - Xa) (P.y - Ya) - (Yb - Ya) (P.x - Xa),
+ *       in int64 (exact: |X| < 2^23).  The pixel belongs to the triangle when every e_k > 0, or e_k == 0 on a top or
+ *       left edge: Yb - Ya < 0, or Yb - Ya == 0 and Xb - Xa > 0.  Two triangles that share an edge never both claim a
+ *       pixel or both miss it; a closed mesh covers every pixel an even number of times.
+ *   depth, perspective-correct: l_k = (float) e_k / (float) A; inv = (l_0 iz_0 + l_1 iz_1) + l_2 iz_2; z = 1 / inv.  A
+ *       z that is not a positive finite number is not written by that triangle.
+ *   depth test: the smallest z wins; on equal bits the lowest triangle index.
+ *
+ * out_depth [P][H][W][4] float32: a covered pixel holds z * depth_q in channels 0..2 and 1.0 in channel 3, background
+ *   is four zeros - what a Depth-mode render writes (.x / .w the depth, .w the alpha), so the images go into
+ *   pxt_depth_agreement, pxt_sensor_vsd, pxt_points_from_depth and pxt_occlusion_mask unchanged.
+ * out_tri [P][H][W] int32 or NULL: the winning triangle's index, -1 on the background.
+ * records [P][PXT_MESH_RASTER_RECORD = 16] uint32 (device memory, all written by the call):
+ *   [0] covered pixels  [1] triangles drawn  [2] near  [3] guard  [4] zero area  [5] bad index  [6] off-screen
+ *   [7] the bits of the smallest z written (0xffffffff when no pixel is covered)  [8] of the largest (0 likewise)
+ *   [9] status: 0, or 0xffffffff (-1) when one of the view's 20 floats is not finite - that view's image is all
+ *   background and its counts are 0  [10..15] 0.
+ * Deterministic: every pixel owns a 64-bit key (z bits << 32 | triangle index) in the workspace, resolved with a vector
+ *   atomicMin (z > 0: the bits order as the floats; the minimum of a total order does not depend on arrival); the counts
+ *   are integer adds, min / max z bit-pattern atomics.  A view's outputs are a pure function of the mesh and its 20
+ *   floats: they do not depend on P, on the view's index or on scheduling.
+ * Bounds: 1 <= P <= 4096, 1 <= V, T <= 2^24, width, height >= 1 and width * height <= 2^26, out_depth and the workspace
+ *   16-byte, everything else 4-byte aligned, no NULL but out_tri; anything else is PXT_E_ARG and nothing is launched
+ *   or written.
+ * workspace: device memory of pxt_mesh_raster_workspace_bytes(P, T, width, height) bytes (< 0: unsupported sizes); one
+ *   workspace serves one call at a time.  Four launches on `stream`, no host synchronisation, no allocation.
+ * Measured on the MI355X: DESIGN.md 3.15.
+ * ---------------------------------------------------------------------- */
+#define PXT_MESH_VIEW 20
+#define PXT_MESH_RASTER_RECORD 16
+int64_t pxt_mesh_raster_workspace_bytes(int32_t n_views, int32_t n_triangles, int32_t width, int32_t height);
+int pxt_mesh_raster(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                    const float* views, int32_t n_views, int32_t width, int32_t height, float* out_depth,
+                    int32_t* out_tri, uint32_t* records, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,9 @@ FLAGS = [
 # 64 samples with v_accvgpr_read: a quarter of the shade kernel's VALU instructions)
 EXTRA = {"pxt_ngp": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # the iso-surface's vertices are held bit for bit to numpy float32 arithmetic (mesh.iso_surface_reference)
-         "pxt_iso": ["-ffp-contract=off"]}
+         "pxt_iso": ["-ffp-contract=off"],
+         # the rasteriser's depths are held bit for bit to numpy float32 arithmetic (mesh_render.rasterize_reference)
+         "pxt_raster": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -45,6 +45,8 @@ PXT_DEPTH_LOG_STRIDE = 20
 PXT_OCCLUSION_RECORD = 16
 PXT_OCCLUSION_MAX_RADIUS = 16
 PXT_ISO_CASE_TABLE_WORDS = 6 * 16 * 7
+PXT_MESH_VIEW = 20
+PXT_MESH_RASTER_RECORD = 16
 
 
 class PxtError(RuntimeError):
@@ -317,6 +319,8 @@ PROTOTYPES = {
     "pxt_iso_surface_emit": (C.c_int, [_VP, C.POINTER(IsoGrid), _VP, _VP, _I32, _VP, _VP, _I32, _VP]),
     "pxt_max_pairwise_distance_workspace_bytes": (_I64, [_I32]),
     "pxt_max_pairwise_distance": (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
+    "pxt_mesh_raster_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "pxt_mesh_raster": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
 }
 
 

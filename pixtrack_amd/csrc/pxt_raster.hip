@@ -1,0 +1,401 @@
+// Depth rasteriser for triangle meshes (pxt_mesh_raster, include/pixtrack_hip.h; pixtrack_amd/mesh_render.py).
+//
+// The reference draws meshes with pytorch3d (pixtrack/utils/pytorch3d_render_utils.py:55-93, render_image) for its
+// YCB ground-truth renders; this is the depth part of that for the evaluation stack: BOP's VSD compares depth renders
+// of the model's mesh through the camera's real intrinsics.  The rule is stated in the header, restated in numpy by
+// mesh_render.rasterize_reference and held to it bit for bit.
+//
+// Every pixel of a view owns one 64-bit key, (bits of z) << 32 | triangle index, in the workspace; a triangle that
+// covers the pixel offers its key with a vector atomicMin.  z > 0, so its bits order as the floats do, and the minimum
+// of a totally ordered key does not depend on who arrives first: the image is a pure function of the mesh and the view.
+//
+// Launches (all on the caller's stream, no host synchronisation)
+//  1. rs_clear_kernel: the key planes to "empty", the records to their start values (the status word included), the
+//     per-view list counters to 0.
+//  2. rs_triangle_kernel, one lane per (view, triangle): the three vertices are transformed in place - the workspace is
+//     sized without the vertex count, and a vertex costs about thirty operations - then the culls, the signed area in
+//     int64, the bounding box clipped to the image.  A box of at most kRsLaneMax pixels is walked by its lane; a larger
+//     one is handed to the whole wave (its set-up travels by lane broadcast, the 64 lanes take a tile of the box per
+//     step); one of more than kRsWaveMax pixels goes to the view's list for launch 3 while the list has room, else it
+//     takes the wave path too.  Which path a triangle takes changes nothing in the image.
+//  3. rs_list_kernel, one workgroup per 16 x 16 pixel tile and view: walks the view's list, skips the entries whose box
+//     misses the tile, evaluates the others at its lane's pixel and keeps the smallest key in a register: one atomicMin
+//     per pixel at the end.  A full-screen triangle is 1200 workgroups' work, not one wave's.
+//  4. rs_resolve_kernel, four pixels per lane: key -> the float4 image, the optional id plane; covered / min z / max z
+//     are folded per workgroup and reach the record through integer and bit-pattern atomics.
+// The edge functions are products of int32 differences in int64 (exact); they are evaluated per pixel, not stepped.
+//
+// This file is compiled with -ffp-contract=off (pixtrack_amd/_build.py EXTRA): every product, sum and quotient is
+// rounded on its own, as numpy does it.
+#include "pxt_common.h"
+
+#include <algorithm>
+
+namespace pxt {
+namespace {
+
+constexpr int kRsBlock = 256;
+constexpr int kRsWaves = kRsBlock / PXT_WAVE;
+constexpr int kRsTriBlock = 1024;  // rs_triangle_kernel: one add per workgroup and cause reaches the record
+constexpr int kRsResolvePixels = 4;  // rs_resolve_kernel: pixels per lane
+constexpr int kRsLaneMax = 32;     // box pixels one lane walks alone
+constexpr int kRsWaveMax = 1024;   // box pixels the wave walks together; larger boxes go to the list
+constexpr int kRsListCap = 1024;   // list entries per view
+constexpr int kRsTile = 16;        // rs_list_kernel: kRsTile x kRsTile pixels per workgroup
+constexpr int kRsSub = 256;        // sub-pixel steps per pixel
+constexpr float kRsGuard = 8388608.f;  // 2^23
+constexpr float kRsFltMax = 3.402823466e+38f;
+constexpr unsigned long long kRsEmpty = ~0ull;
+static_assert(kRsTile * kRsTile == kRsBlock, "one lane per pixel of a tile");
+
+enum { RS_DRAWN = 0, RS_NEAR = 1, RS_GUARD = 2, RS_ZERO = 3, RS_INDEX = 4, RS_OFF = 5 };
+// record words
+enum { RS_W_COVERED = 0, RS_W_DRAWN = 1, RS_W_NEAR = 2, RS_W_GUARD = 3, RS_W_ZERO = 4, RS_W_INDEX = 5, RS_W_OFF = 6,
+       RS_W_ZMIN = 7, RS_W_ZMAX = 8, RS_W_STATUS = 9 };
+
+struct RsView {
+  float R[9], t[3], fx, fy, cx, cy, near, depth_q;
+};
+
+struct RsTri {
+  int x[3], y[3];
+  float iz[3];
+  long long area;
+  int ix0, ix1, iy0, iy1;  // the clipped box, empty when ix0 > ix1 or iy0 > iy1
+};
+
+struct RsArgs {
+  const float* vertices;
+  const int* triangles;
+  const float* views;
+  int V, T, P, W, H, cap;
+  unsigned long long* keys;  // [P][H][W]
+  unsigned* list_count;      // [P]
+  uint4* list;               // [P][cap]: triangle, ix0 | ix1 << 16, iy0 | iy1 << 16, 0
+  float* out_depth;
+  int* out_tri;
+  unsigned* records;
+};
+
+__device__ __forceinline__ bool rs_finite(float v) { return fabsf(v) <= kRsFltMax; }  // false for a NaN
+
+// The view's 20 floats; -> every one of them is finite.
+__device__ __forceinline__ bool rs_load_view(const float* __restrict__ v20, RsView* v) {
+  bool ok = true;
+  float f[PXT_MESH_VIEW];
+#pragma unroll
+  for (int i = 0; i < PXT_MESH_VIEW; ++i) {
+    f[i] = v20[i];
+    ok = ok && rs_finite(f[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) v->R[i] = f[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) v->t[i] = f[9 + i];
+  v->fx = f[12]; v->fy = f[13]; v->cx = f[14]; v->cy = f[15];
+  v->near = f[16];
+  v->depth_q = f[17];
+  return ok;
+}
+
+// One vertex -> RS_DRAWN (X, Y, iz written), RS_GUARD or RS_NEAR.
+__device__ __forceinline__ int rs_vertex(const RsView& v, const float* __restrict__ q, int* X, int* Y, float* iz) {
+  const float a = q[0], b = q[1], c = q[2];
+  float p[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] = ((v.R[3 * k] * a + v.R[3 * k + 1] * b) + v.R[3 * k + 2] * c) + v.t[k];
+  if (!(rs_finite(p[0]) && rs_finite(p[1]) && rs_finite(p[2]))) return RS_GUARD;
+  if (p[2] <= v.near) return RS_NEAR;
+  const float x = v.fx * (p[0] / p[2]) + v.cx, y = v.fy * (p[1] / p[2]) + v.cy;
+  const float xs = rintf(x * (float)kRsSub), ys = rintf(y * (float)kRsSub);
+  if (!(fabsf(xs) < kRsGuard) || !(fabsf(ys) < kRsGuard)) return RS_GUARD;  // a NaN or an infinity fails here too
+  *X = (int)xs;
+  *Y = (int)ys;
+  *iz = 1.0f / p[2];
+  return RS_DRAWN;
+}
+
+// Triangle t of the view -> its cause (RS_DRAWN: s is complete).  No address outside the vertex array is formed.
+__device__ __forceinline__ int rs_setup(const RsView& v, const float* __restrict__ vertices, int V, int ia, int ib,
+                                        int ic, int W, int H, RsTri* s) {
+  if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) return RS_INDEX;
+  const int c0 = rs_vertex(v, vertices + 3 * (size_t)ia, &s->x[0], &s->y[0], &s->iz[0]);
+  const int c1 = rs_vertex(v, vertices + 3 * (size_t)ib, &s->x[1], &s->y[1], &s->iz[1]);
+  const int c2 = rs_vertex(v, vertices + 3 * (size_t)ic, &s->x[2], &s->y[2], &s->iz[2]);
+  if (c0 == RS_GUARD || c1 == RS_GUARD || c2 == RS_GUARD) return RS_GUARD;
+  if (c0 == RS_NEAR || c1 == RS_NEAR || c2 == RS_NEAR) return RS_NEAR;
+  long long area = (long long)(s->x[1] - s->x[0]) * (s->y[2] - s->y[0]) - (long long)(s->y[1] - s->y[0]) * (s->x[2] - s->x[0]);
+  if (area == 0) return RS_ZERO;
+  if (area < 0) {
+    const int tx = s->x[1], ty = s->y[1];
+    const float tz = s->iz[1];
+    s->x[1] = s->x[2]; s->y[1] = s->y[2]; s->iz[1] = s->iz[2];
+    s->x[2] = tx; s->y[2] = ty; s->iz[2] = tz;
+    area = -area;
+  }
+  s->area = area;
+  const int lo_x = min(s->x[0], min(s->x[1], s->x[2])), hi_x = max(s->x[0], max(s->x[1], s->x[2]));
+  const int lo_y = min(s->y[0], min(s->y[1], s->y[2])), hi_y = max(s->y[0], max(s->y[1], s->y[2]));
+  if (hi_x < 0 || hi_y < 0 || (long long)lo_x > (long long)kRsSub * (W - 1) || (long long)lo_y > (long long)kRsSub * (H - 1))
+    return RS_OFF;
+  s->ix0 = max(0, (lo_x + kRsSub - 1) >> 8);  // arithmetic shifts: floor
+  s->iy0 = max(0, (lo_y + kRsSub - 1) >> 8);
+  s->ix1 = min(W - 1, hi_x >> 8);
+  s->iy1 = min(H - 1, hi_y >> 8);
+  return RS_DRAWN;
+}
+
+// Pixel (i, j) of the triangle's clipped box: covered, and with a positive finite z?  -> the bits of z.
+__device__ __forceinline__ bool rs_pixel(const RsTri& s, int i, int j, unsigned* zbits) {
+  const int px = i << 8, py = j << 8;  // inside the box: below 2^23
+  long long e[3];
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int a = (k + 1) % 3, b = (k + 2) % 3;
+    const int dx = s.x[b] - s.x[a], dy = s.y[b] - s.y[a];
+    e[k] = (long long)dx * (py - s.y[a]) - (long long)dy * (px - s.x[a]);
+    const bool top_left = dy < 0 || (dy == 0 && dx > 0);
+    in = in && (e[k] > 0 || (e[k] == 0 && top_left));
+  }
+  if (!in) return false;
+  const float A = (float)s.area;
+  const float l0 = (float)e[0] / A, l1 = (float)e[1] / A, l2 = (float)e[2] / A;
+  const float inv = (l0 * s.iz[0] + l1 * s.iz[1]) + l2 * s.iz[2];
+  const float z = 1.0f / inv;
+  if (!(z > 0.f && z <= kRsFltMax)) return false;
+  *zbits = __builtin_bit_cast(unsigned, z);
+  return true;
+}
+
+__device__ __forceinline__ unsigned long long rs_key(unsigned zbits, int tri) {
+  return ((unsigned long long)zbits << 32) | (unsigned)tri;
+}
+
+__global__ __launch_bounds__(kRsBlock) void rs_clear_kernel(const RsArgs a, const size_t n_units) {
+  const size_t stride = (size_t)gridDim.x * kRsBlock;
+  const size_t g = (size_t)blockIdx.x * kRsBlock + threadIdx.x;
+  ulonglong2* k2 = (ulonglong2*)a.keys;  // the key region is padded to whole 16-byte units
+  for (size_t u = g; u < n_units; u += stride) k2[u] = make_ulonglong2(kRsEmpty, kRsEmpty);
+  for (size_t u = g; u < (size_t)a.P * PXT_MESH_RASTER_RECORD; u += stride) {
+    const int view = (int)(u / PXT_MESH_RASTER_RECORD), w = (int)(u % PXT_MESH_RASTER_RECORD);
+    unsigned val = 0u;
+    if (w == RS_W_ZMIN) val = 0xffffffffu;
+    if (w == RS_W_STATUS) {
+      RsView v;
+      val = rs_load_view(a.views + (size_t)view * PXT_MESH_VIEW, &v) ? 0u : 0xffffffffu;
+    }
+    a.records[u] = val;
+  }
+  for (size_t u = g; u < (size_t)a.P; u += stride) a.list_count[u] = 0u;
+}
+
+__global__ __launch_bounds__(kRsTriBlock) void rs_triangle_kernel(const RsArgs a) {
+  __shared__ unsigned counts[6];
+  const int view = blockIdx.y, lane = threadIdx.x & (PXT_WAVE - 1);
+  RsView v;
+  if (!rs_load_view(a.views + (size_t)view * PXT_MESH_VIEW, &v)) return;  // the whole workgroup alike
+  if (threadIdx.x < 6) counts[threadIdx.x] = 0u;
+  __syncthreads();
+  const int t = blockIdx.x * kRsTriBlock + threadIdx.x;
+  unsigned long long* keys = a.keys + (size_t)view * a.W * a.H;
+  RsTri s;
+  int cause = -1;  // no triangle
+  if (t < a.T) {
+    const int* f = a.triangles + 3 * (size_t)t;
+    cause = rs_setup(v, a.vertices, a.V, f[0], f[1], f[2], a.W, a.H, &s);
+  }
+  // the counts: the waves' ballots meet in LDS, one add per workgroup and cause reaches the record (thousands of adds
+  // to one address cost more than the triangles' own work)
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const unsigned n = (unsigned)__popcll(__ballot(cause == c));
+    if (lane == 0 && n) atomicAdd(&counts[c], n);
+  }
+  __syncthreads();
+  if (threadIdx.x < 6 && counts[threadIdx.x]) {
+    const int c = threadIdx.x;
+    const int word = c == RS_DRAWN ? RS_W_DRAWN : c == RS_NEAR ? RS_W_NEAR : c == RS_GUARD ? RS_W_GUARD
+                     : c == RS_ZERO ? RS_W_ZERO : c == RS_INDEX ? RS_W_INDEX : RS_W_OFF;
+    atomicAdd(a.records + (size_t)view * PXT_MESH_RASTER_RECORD + word, counts[c]);
+  }
+  int npx = 0;
+  if (cause == RS_DRAWN && s.ix0 <= s.ix1 && s.iy0 <= s.iy1) npx = (s.ix1 - s.ix0 + 1) * (s.iy1 - s.iy0 + 1);  // < 2^30
+  if (npx > kRsWaveMax) {  // to the list while it has room
+    const unsigned slot = atomicAdd(a.list_count + view, 1u);
+    if (slot < (unsigned)a.cap) {
+      a.list[(size_t)view * a.cap + slot] = make_uint4((unsigned)t, (unsigned)s.ix0 | ((unsigned)s.ix1 << 16),
+                                                       (unsigned)s.iy0 | ((unsigned)s.iy1 << 16), 0u);
+      npx = 0;
+    }
+  }
+  if (npx > 0 && npx <= kRsLaneMax) {
+    for (int j = s.iy0; j <= s.iy1; ++j)
+      for (int i = s.ix0; i <= s.ix1; ++i) {
+        unsigned zb;
+        if (rs_pixel(s, i, j, &zb)) atomicMin(keys + (size_t)j * a.W + i, rs_key(zb, t));
+      }
+  }
+  // the larger boxes, one after the other, by the whole wave
+  unsigned long long todo = __ballot(npx > kRsLaneMax);
+  while (todo) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    RsTri w;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      w.x[k] = __shfl(s.x[k], src, PXT_WAVE);
+      w.y[k] = __shfl(s.y[k], src, PXT_WAVE);
+      w.iz[k] = __shfl(s.iz[k], src, PXT_WAVE);
+    }
+    w.area = ((long long)__shfl((int)(s.area >> 32), src, PXT_WAVE) << 32) |
+             (unsigned)__shfl((int)(unsigned)s.area, src, PXT_WAVE);
+    w.ix0 = __shfl(s.ix0, src, PXT_WAVE); w.ix1 = __shfl(s.ix1, src, PXT_WAVE);
+    w.iy0 = __shfl(s.iy0, src, PXT_WAVE); w.iy1 = __shfl(s.iy1, src, PXT_WAVE);
+    const int wt = __shfl(t, src, PXT_WAVE);
+    const int bw = w.ix1 - w.ix0 + 1;
+    const int ltw = bw > 32 ? 6 : bw > 16 ? 5 : bw > 8 ? 4 : 3;  // the wave's tile: 2^ltw wide, 64 >> ltw high
+    const int tw = 1 << ltw, th = PXT_WAVE >> ltw;
+    const int lx = lane & (tw - 1), ly = lane >> ltw;
+    for (int j0 = w.iy0; j0 <= w.iy1; j0 += th)
+      for (int i0 = w.ix0; i0 <= w.ix1; i0 += tw) {
+        const int i = i0 + lx, j = j0 + ly;
+        unsigned zb;
+        if (i <= w.ix1 && j <= w.iy1 && rs_pixel(w, i, j, &zb)) atomicMin(keys + (size_t)j * a.W + i, rs_key(zb, wt));
+      }
+  }
+}
+
+__global__ __launch_bounds__(kRsBlock) void rs_list_kernel(const RsArgs a, const int tiles_x) {
+  const int view = blockIdx.y;
+  const int n = (int)min(a.list_count[view], (unsigned)a.cap);
+  if (n == 0) return;
+  RsView v;
+  if (!rs_load_view(a.views + (size_t)view * PXT_MESH_VIEW, &v)) return;  // never: such a view lists nothing
+  const int tx0 = ((int)blockIdx.x % tiles_x) * kRsTile, ty0 = ((int)blockIdx.x / tiles_x) * kRsTile;
+  const int i = tx0 + ((int)threadIdx.x & (kRsTile - 1)), j = ty0 + ((int)threadIdx.x / kRsTile);
+  const uint4* list = a.list + (size_t)view * a.cap;
+  unsigned long long best = kRsEmpty;
+  for (int e = 0; e < n; ++e) {
+    const uint4 ent = list[e];
+    const int bx0 = (int)(ent.y & 0xffffu), bx1 = (int)(ent.y >> 16), by0 = (int)(ent.z & 0xffffu), by1 = (int)(ent.z >> 16);
+    if (bx1 < tx0 || bx0 >= tx0 + kRsTile || by1 < ty0 || by0 >= ty0 + kRsTile) continue;  // the whole workgroup alike
+    const int t = (int)ent.x;
+    if (t < 0 || t >= a.T) continue;
+    const int* f = a.triangles + 3 * (size_t)t;
+    RsTri s;
+    if (rs_setup(v, a.vertices, a.V, f[0], f[1], f[2], a.W, a.H, &s) != RS_DRAWN) continue;
+    unsigned zb;
+    if (i >= s.ix0 && i <= s.ix1 && j >= s.iy0 && j <= s.iy1 && rs_pixel(s, i, j, &zb)) best = min(best, rs_key(zb, t));
+  }
+  if (best != kRsEmpty && i < a.W && j < a.H) atomicMin(a.keys + (size_t)view * a.W * a.H + (size_t)j * a.W + i, best);
+}
+
+__global__ __launch_bounds__(kRsBlock) void rs_resolve_kernel(const RsArgs a) {
+  __shared__ unsigned red[3][kRsWaves];
+  const int view = blockIdx.y, tid = threadIdx.x;
+  const size_t wh = (size_t)a.W * a.H;
+  const float depth_q = a.views[(size_t)view * PXT_MESH_VIEW + 17];
+  unsigned mn = 0xffffffffu, mx = 0u, cnt = 0u;
+#pragma unroll
+  for (int k = 0; k < kRsResolvePixels; ++k) {
+    const size_t pix = ((size_t)blockIdx.x * kRsResolvePixels + k) * kRsBlock + tid;
+    if (pix >= wh) continue;
+    const unsigned long long key = a.keys[(size_t)view * wh + pix];
+    const bool cov = key != kRsEmpty;
+    const unsigned zb = (unsigned)(key >> 32);
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cov) {
+      const float d = __builtin_bit_cast(float, zb) * depth_q;
+      o = make_float4(d, d, d, 1.0f);
+      mn = min(mn, zb);
+      mx = max(mx, zb);
+      ++cnt;
+    }
+    ((float4*)a.out_depth)[(size_t)view * wh + pix] = o;
+    if (a.out_tri) a.out_tri[(size_t)view * wh + pix] = cov ? (int)(unsigned)(key & 0xffffffffull) : -1;
+  }
+#pragma unroll
+  for (int m = 1; m < PXT_WAVE; m <<= 1) {
+    mn = min(mn, (unsigned)__shfl_xor((int)mn, m, PXT_WAVE));
+    mx = max(mx, (unsigned)__shfl_xor((int)mx, m, PXT_WAVE));
+    cnt += (unsigned)__shfl_xor((int)cnt, m, PXT_WAVE);
+  }
+  if ((tid & (PXT_WAVE - 1)) == 0) {
+    red[0][tid / PXT_WAVE] = cnt;
+    red[1][tid / PXT_WAVE] = mn;
+    red[2][tid / PXT_WAVE] = mx;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned c = 0u, lo = 0xffffffffu, hi = 0u;
+#pragma unroll
+    for (int w = 0; w < kRsWaves; ++w) {
+      c += red[0][w];
+      lo = min(lo, red[1][w]);
+      hi = max(hi, red[2][w]);
+    }
+    if (c) {  // min and max only where they can still move the record: its words only ever move one way
+      unsigned* rec = a.records + (size_t)view * PXT_MESH_RASTER_RECORD;
+      atomicAdd(rec + RS_W_COVERED, c);
+      if (lo < __hip_atomic_load(rec + RS_W_ZMIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(rec + RS_W_ZMIN, lo);
+      if (hi > __hip_atomic_load(rec + RS_W_ZMAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(rec + RS_W_ZMAX, hi);
+    }
+  }
+}
+
+constexpr int64_t kRsMaxPixels = (int64_t)1 << 26;
+constexpr int kRsMaxViews = 4096, kRsMaxCount = 1 << 24;
+
+bool rs_sizes_ok(int P, int T, int W, int H) {
+  return P >= 1 && P <= kRsMaxViews && T >= 1 && T <= kRsMaxCount && W >= 1 && H >= 1 && (int64_t)W * H <= kRsMaxPixels;
+}
+int rs_cap(int T) { return std::min(T, kRsListCap); }
+int64_t rs_key_bytes(int P, int W, int H) { return ((int64_t)P * W * H * 8 + 15) / 16 * 16; }
+int64_t rs_count_bytes(int P) { return ((int64_t)P * 4 + 15) / 16 * 16; }
+
+}  // namespace
+}  // namespace pxt
+
+using namespace pxt;
+
+extern "C" int64_t pxt_mesh_raster_workspace_bytes(int32_t n_views, int32_t n_triangles, int32_t width, int32_t height) {
+  if (!rs_sizes_ok(n_views, n_triangles, width, height)) return PXT_E_ARG;
+  return rs_key_bytes(n_views, width, height) + rs_count_bytes(n_views) + (int64_t)n_views * rs_cap(n_triangles) * 16;
+}
+
+extern "C" int pxt_mesh_raster(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                               const float* views, int32_t n_views, int32_t width, int32_t height, float* out_depth,
+                               int32_t* out_tri, uint32_t* records, void* workspace, void* stream) {
+  if (!rs_sizes_ok(n_views, n_triangles, width, height) || n_vertices < 1 || n_vertices > kRsMaxCount) return PXT_E_ARG;
+  if (!vertices || !triangles || !views || !out_depth || !records || !workspace) return PXT_E_ARG;
+  if (((uintptr_t)vertices % 4) != 0 || ((uintptr_t)triangles % 4) != 0 || ((uintptr_t)views % 4) != 0 ||
+      ((uintptr_t)out_tri % 4) != 0 || ((uintptr_t)records % 4) != 0 || ((uintptr_t)out_depth % 16) != 0 ||
+      ((uintptr_t)workspace % 16) != 0)
+    return PXT_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  RsArgs a;
+  a.vertices = vertices; a.triangles = (const int*)triangles; a.views = views;
+  a.V = n_vertices; a.T = n_triangles; a.P = n_views; a.W = width; a.H = height; a.cap = rs_cap(n_triangles);
+  const int64_t key_bytes = rs_key_bytes(n_views, width, height);
+  a.keys = (unsigned long long*)workspace;
+  a.list_count = (unsigned*)((char*)workspace + key_bytes);
+  a.list = (uint4*)((char*)workspace + key_bytes + rs_count_bytes(n_views));
+  a.out_depth = out_depth; a.out_tri = (int*)out_tri; a.records = (unsigned*)records;
+
+  const size_t n_units = (size_t)(key_bytes / 16);
+  const size_t clear_work = std::max(n_units, (size_t)n_views * PXT_MESH_RASTER_RECORD);
+  const unsigned clear_blocks = (unsigned)std::min<size_t>((clear_work + kRsBlock - 1) / kRsBlock, 8192);
+  hipLaunchKernelGGL(rs_clear_kernel, dim3(clear_blocks), dim3(kRsBlock), 0, s, a, n_units);
+  PXT_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(rs_triangle_kernel, dim3((n_triangles + kRsTriBlock - 1) / kRsTriBlock, n_views), dim3(kRsTriBlock), 0, s, a);
+  PXT_HIP_CHECK(hipGetLastError());
+  const int tiles_x = (width + kRsTile - 1) / kRsTile, tiles_y = (height + kRsTile - 1) / kRsTile;  // product <= 2^26
+  hipLaunchKernelGGL(rs_list_kernel, dim3((unsigned)tiles_x * (unsigned)tiles_y, n_views), dim3(kRsBlock), 0, s, a, tiles_x);
+  PXT_HIP_CHECK(hipGetLastError());
+  const int64_t res_pixels = (int64_t)kRsBlock * kRsResolvePixels;
+  const unsigned res_blocks = (unsigned)(((int64_t)width * height + res_pixels - 1) / res_pixels);
+  hipLaunchKernelGGL(rs_resolve_kernel, dim3(res_blocks, n_views), dim3(kRsBlock), 0, s, a);
+  PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}

@@ -531,6 +531,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--keep", choices=("largest", "all"), default="largest", help="connected components to keep")
     ap.add_argument("--frame", choices=("sfm", "ngp"), default="sfm", help="coordinates of what is written")
     ap.add_argument("--out_dir", required=True)
+    ap.add_argument("--check_render", type=int, default=0, metavar="N",
+                    help="draw the mesh beside the NeRF's Depth render from N views around the box and add the mean "
+                         "silhouette IoU and depth error to the JSON line (mesh_evaluation.mesh_nerf_agreement)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -564,6 +567,17 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
                "invariants": inv, "volume": inv["volume"], "area": inv["area"], "diameter": mesh["diameter"],
                "seconds_lattice": mesh["times"]["lattice"], "seconds_extraction": mesh["times"]["extraction"],
                "seconds_diameter": mesh["times"]["diameter"], "out_dir": str(out)}
+    if args.check_render > 0:
+        from .mesh_evaluation import mesh_nerf_agreement
+        from .ngp import ngp_to_sfm_affine
+
+        V_ngp = mesh["V"]
+        if mesh["frame"] == "sfm":  # back into the renderer's frame
+            A = ngp_to_sfm_affine(nerf2sfm, testbed._snap.scale, testbed._snap.offset)
+            V_ngp = (np.asarray(V_ngp, np.float64) - A[:, 3]) @ np.linalg.inv(A[:, :3]).T
+        check = mesh_nerf_agreement(testbed, V_ngp, mesh["F"], n_views=args.check_render)
+        summary["check_render"] = {"n_views": check["n_views"], "iou_mean": check["iou_mean"],
+                                   "mean_abs_dz_mean": check["mean_abs_dz_mean"]}
     print(json.dumps(summary))
     return summary
 

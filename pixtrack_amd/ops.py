@@ -179,6 +179,12 @@ SCHEMAS = {
     # points [n, 3] -> out int32 [4] (device or pinned): bits of float d, i, j, 1 (pxt_max_pairwise_distance); workspace:
     # uint8, pxt_max_pairwise_distance_workspace_bytes(n)
     "max_pairwise_distance": "(Tensor points, Tensor(a!) out, Tensor(b!) workspace) -> ()",
+    # vertices [V, 3] float32, triangles [T, 3] int32, views [P, 20] float32 (mesh_render.view_record) -> depth
+    # [P, H, W, 4] (a Depth render's layout), triangle_ids int32 [P, H, W] or None, records int32 [P, 16] (the uint32
+    # words of pxt_mesh_raster); workspace: uint8, pxt_mesh_raster_workspace_bytes(P, T, W, H)
+    "mesh_raster": (
+        "(Tensor vertices, Tensor triangles, Tensor views, Tensor(a!) depth, Tensor(b!)? triangle_ids, "
+        "Tensor(c!) records, Tensor(d!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -1187,7 +1193,48 @@ def _max_pairwise_distance(points, out, workspace):
                "pxt_max_pairwise_distance")
 
 
+def _mesh_raster(vertices, triangles, views, depth, triangle_ids, records, workspace):
+    L = _lib.lib()
+    _f32c(vertices, "vertices")
+    _f32c(views, "views")
+    _f32c(depth, "depth")
+    if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or triangles.dim() != 2 or int(triangles.shape[1]) != 3
+            or triangles.dtype != torch.int32 or not triangles.is_contiguous() or views.dim() != 2
+            or int(views.shape[1]) != _lib.PXT_MESH_VIEW):
+        raise _lib.PxtError(f"mesh_raster: vertices {tuple(vertices.shape)} / triangles {tuple(triangles.shape)} "
+                            f"{triangles.dtype} / views {tuple(views.shape)}, expected float32 [V, 3] / contiguous int32 "
+                            f"[T, 3] / float32 [P, {_lib.PXT_MESH_VIEW}]")
+    V, T, P = int(vertices.shape[0]), int(triangles.shape[0]), int(views.shape[0])
+    if depth.dim() != 4 or int(depth.shape[0]) != P or int(depth.shape[3]) != 4:
+        raise _lib.PxtError(f"mesh_raster: depth is {tuple(depth.shape)}, expected [{P}, H, W, 4]")
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    if triangle_ids is not None and (triangle_ids.dtype != torch.int32 or not triangle_ids.is_contiguous()
+                                     or tuple(triangle_ids.shape) != (P, H, W)):
+        raise _lib.PxtError(f"mesh_raster: triangle_ids is a contiguous int32 [{P}, {H}, {W}] tensor (got "
+                            f"{tuple(triangle_ids.shape)}, {triangle_ids.dtype})")
+    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
+        raise _lib.PxtError(f"mesh_raster: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
+                            f"(got {tuple(records.shape)}, {records.dtype})")
+    need = int(L.pxt_mesh_raster_workspace_bytes(P, T, W, H)) if min(P, T, W, H) >= 1 else -1
+    if need <= 0 or not (1 <= V <= 1 << 24):
+        raise _lib.PxtError(f"mesh_raster: {P} views of {W} x {H}, {V} vertices, {T} triangles are not supported "
+                            "(1..4096 views, 1..2^26 pixels, 1..2^24 vertices and triangles)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"mesh_raster: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    named = [(vertices, "vertices"), (triangles, "triangles"), (views, "views"), (depth, "depth"), (records, "records"),
+             (workspace, "workspace")] + ([(triangle_ids, "triangle_ids")] if triangle_ids is not None else [])
+    for t, name in named:
+        _lib.require_gpu(t, name)
+        if t.device != vertices.device:
+            raise _lib.PxtError(f"mesh_raster: {name} is on {t.device}, the vertices on {vertices.device}")
+    _lib.check(L.pxt_mesh_raster(vertices.data_ptr(), V, triangles.data_ptr(), T, views.data_ptr(), P, W, H,
+                                 depth.data_ptr(), _lib.dptr(triangle_ids), records.data_ptr(), workspace.data_ptr(),
+                                 _stream(vertices)), "pxt_mesh_raster")
+
+
 _IMPLS = {
+    "mesh_raster": _mesh_raster,
     "ngp_query": _ngp_query,
     "iso_surface_count": _iso_surface_count,
     "iso_surface_emit": _iso_surface_emit,
