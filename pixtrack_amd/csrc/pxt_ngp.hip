@@ -154,6 +154,10 @@ __device__ inline half8 relu_pack8(const f32x16& a, int base, bool relu) {
   return r;
 }
 
+// idx % size for an index below 2 size (a dense level's corner index, or - both scaled by 4 - its byte offset): below size the
+// unsigned difference wraps to a huge value and the minimum is idx itself - a subtract and a v_min_u32
+__device__ __forceinline__ unsigned ngp_dense_wrap(unsigned idx, unsigned size) { return min(idx, idx - size); }
+
 // One hash-grid level at a warped position in [0,1]^3 -> packed (f0, f1) fp16 pair.
 __device__ inline unsigned ngp_encode_level(const unsigned* __restrict__ grid, const NgpLevel& Lv, float ux,
                                             float uy, float uz) {
@@ -166,13 +170,16 @@ __device__ inline unsigned ngp_encode_level(const unsigned* __restrict__ grid, c
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     const unsigned cx = gx + (c & 1), cy = gy + ((c >> 1) & 1), cz = gz + ((c >> 2) & 1);
-    // tcnn: index % level_size.  A hashed level has exactly 2^log2_hashmap entries (mask), a
-    // dense level's index is already < res^3 <= size: no integer division either way.
+    // tcnn: index % level_size.  A hashed level has exactly 2^log2_hashmap entries (mask).  A dense level's corner
+    // reaches coordinate res at the top of the unit cube (cz == res, or cx == res in the last row), so its index
+    // passes size - but stays below res + res^2 + res^3 < 2 size: one compare and subtract is the modulo, no integer
+    // division either way.  The min() behind it changes nothing for a position of the unit cube; it keeps the plain
+    // pointer load of a caller-given point OUTSIDE the scene cube (pxt_ngp_query) inside the level.
     unsigned idx;
     if (Lv.hashed)
       idx = ((cx * 1u) ^ (cy * 2654435761u) ^ (cz * 805459861u)) & (Lv.size - 1u);
     else
-      idx = min(cx + cy * Lv.res + cz * Lv.res * Lv.res, Lv.size - 1u);
+      idx = min(ngp_dense_wrap(cx + cy * Lv.res + cz * Lv.res * Lv.res, Lv.size), Lv.size - 1u);
     vals[c] = grid[idx + Lv.offset];
   }
   float f0 = 0.f, f1 = 0.f;
@@ -240,12 +247,12 @@ __device__ inline unsigned ngp_encode_level_uniform(const __amdgpu_buffer_rsrc_t
       vals[c] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(grid, (int)off, base, 0);
     }
   } else {
-    const unsigned r4 = Lv.res * 4u, r24 = Lv.res * Lv.res * 4u, last4 = (Lv.size - 1u) << 2;
+    const unsigned r4 = Lv.res * 4u, r24 = Lv.res * Lv.res * 4u, size4 = Lv.size << 2;
     const unsigned ry[2] = {gy * r4, gy * r4 + r4};
     const unsigned rz[2] = {gz * r24, gz * r24 + r24};
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      const unsigned off = min(gx4[c & 1] + ry[(c >> 1) & 1] + rz[(c >> 2) & 1], last4);
+      const unsigned off = ngp_dense_wrap(gx4[c & 1] + ry[(c >> 1) & 1] + rz[(c >> 2) & 1], size4);  // (index % size)
       vals[c] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(grid, (int)off, base, 0);
     }
   }
@@ -875,7 +882,8 @@ __device__ __forceinline__ int ngp_patch_point_offset(const NgpLevel& Lv, int la
   const unsigned lx = lox + (unsigned)(lane & 3), ly = loy + (unsigned)((lane >> 2) & 3), lz = loz + (unsigned)(lane >> 4);
   unsigned idx;
   if (Lv.hashed) idx = (lx ^ (ly * 2654435761u) ^ (lz * 805459861u)) & (Lv.size - 1u);
-  else idx = min(lx + ly * Lv.res + lz * Lv.res * Lv.res, Lv.size - 1u);
+  // (index % size as in ngp_encode_level; the min() only bounds lattice points of the box that no sample's cell touches)
+  else idx = min(ngp_dense_wrap(lx + ly * Lv.res + lz * Lv.res * Lv.res, Lv.size), Lv.size - 1u);
   return (int)(idx << 2);
 }
 // One level's features of this lane's sample from the wave's patch (the arithmetic of ngp_encode_level_uniform).

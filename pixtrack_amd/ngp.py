@@ -67,6 +67,15 @@ class NerfSnapshot:
         return out
 
 
+def _as_float32(x) -> float:
+    """per_level_scale as the renderer holds it: pxt_ngp_model carries a float (as tiny-cuda-nn's GridEncoding does), and
+    every level's scale is derived from that float32 value.  A snapshot read from a file states the rounded value, so
+    that the level layout computed here (_grid_entries) is the library's and an oracle fed from the snapshot sees the
+    device's level scales: the double 2048^(1/15) and its float32 neighbour put the finest level of an aabb_scale 16
+    snapshot 0.0095 cells apart ("Snapshot geometries")."""
+    return float(np.float32(x))
+
+
 def save_snapshot(path: str, snap: NerfSnapshot) -> None:
     """msgpack container with instant-ngp-like keys (encoding / network / snapshot)."""
     import msgpack
@@ -108,7 +117,7 @@ def load_snapshot_file(path: str) -> NerfSnapshot:
         mlp=np.frombuffer(s["mlp_binary"], np.float16).copy(),
         occupancy=np.frombuffer(s["density_grid_binary"], np.uint8).copy(),
         n_levels=enc["n_levels"], n_features=enc["n_features_per_level"], log2_hashmap=enc["log2_hashmap_size"],
-        base_res=enc["base_resolution"], per_level_scale=enc["per_level_scale"], cascades=nerf["cascades"],
+        base_res=enc["base_resolution"], per_level_scale=_as_float32(enc["per_level_scale"]), cascades=nerf["cascades"],
         aabb_scale=nerf["aabb_scale"], cone_angle=nerf["cone_angle_constant"], scale=nerf["dataset"]["scale"],
         offset=nerf["dataset"]["offset"][0], k1=nerf["dataset"].get("k1", 0.0),
         linear_colors=bool(nerf.get("linear_colors", False)),
@@ -200,6 +209,7 @@ def from_instant_ngp(d: Dict) -> NerfSnapshot:
     if pls <= 0.0:  # instant-ngp derives it from desired_resolution (2048) x aabb_scale
         desired = float(enc.get("desired_resolution", 2048.0))
         pls = math.exp(math.log(desired * aabb_scale / base) / (n_levels - 1))
+    pls = _as_float32(pls)
     params = np.frombuffer(s["params_binary"], np.float16)
     n_grid = _grid_entries(n_levels, log2_T, base, pls) * F
     if params.size != _MLP_PARAMS + n_grid:

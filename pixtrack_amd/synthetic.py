@@ -317,6 +317,156 @@ def make_synthetic_nerf(seed: int = 11, aabb=PREMIER_PROTEIN_AABB, aabb_scale: f
                         aabb_scale=aabb_scale)
 
 
+def make_synthetic_nerf_variant(seed: int = 11, aabb=PREMIER_PROTEIN_AABB, aabb_scale: float = 4.0, cascades: int = 3,
+                                cone_angle: float = 1.0 / 256.0, log2_hashmap: int = 19, base_res: int = 16,
+                                per_level_scale: float = 1.51572):
+    """make_synthetic_nerf for any snapshot geometry the renderer accepts: the same construction (random fp16 table,
+    the same MLP recipe in the same order of random draws, occupancy from the indicator at the cell corners of every
+    cascade) on the level layout of (log2_hashmap, base_res, per_level_scale), with the shape indicator on the FINEST
+    DENSE level of that layout, and every parameter carried by the returned snapshot.  With the default parameters it
+    returns make_synthetic_nerf(seed)'s grid, MLP and occupancy byte for byte (tests/test_ngp_geometries_host.py);
+    make_synthetic_nerf itself stays as it is - golden files depend on its bits.  (per_level_scale reaches the renderer
+    as a float32: for a comparison with an oracle that derives its level scales in double precision, pass a value that
+    float32 holds exactly, as NERF_VARIANTS does.)"""
+    from .ngp import NerfSnapshot
+
+    rng = np.random.default_rng(seed)
+    layout, n_entries = ngp_grid_layout(16, log2_hashmap, base_res, per_level_scale)
+    grid = rng.uniform(-0.5, 0.5, size=(n_entries, 2)).astype(np.float32)
+    shape_level = max(l for l, lv in enumerate(layout) if not lv[4])
+    scale, res, off, size, _ = layout[shape_level]
+    g = np.arange(res, dtype=np.float64)
+    gx, gy, gz = np.meshgrid(g, g, g, indexing="ij")
+    scene_lo = 0.5 - aabb_scale / 2
+    xw = (np.stack([gx, gy, gz], -1) - 0.5) / scale
+    x_ngp = xw * aabb_scale + scene_lo
+    val = np.clip(SHAPE_SHARPNESS * shape_value(x_ngp, aabb), -1.0, 1.0)
+    idx = (gx + gy * res + gz * res * res).astype(np.int64)
+    grid[off + idx.ravel(), 0] = val.ravel()
+
+    def he(o, i, gain=1.0):
+        return rng.normal(size=(o, i)) * math.sqrt(2.0 / i) * gain
+
+    d1 = he(64, 32, 2.0)
+    d1[0, :] = 0.0
+    d1[1, :] = 0.0
+    d1[0, 2 * shape_level] = 4.0
+    d1[1, 2 * shape_level] = -4.0
+    d2 = he(16, 64, 2.0)
+    d2[0, :] = 0.0
+    d2[0, 0], d2[0, 1] = DENSITY_LOGIT / 4.0, -DENSITY_LOGIT / 4.0
+    d2[1:, 0:2] = 0.0
+    c1 = he(64, 32, 2.0)
+    c1[:, 0] = 0.0
+    c1[:, 16:] *= 0.15
+    w = he(32, 64, 1.0)
+    w -= w.mean(axis=1, keepdims=True)
+    c2 = np.concatenate([w, -w], 0)
+    v = rng.normal(size=(3, 32)) * C3_GAIN / math.sqrt(32)
+    c3 = np.zeros((16, 64))
+    c3[:3, :32] = v
+    c3[:3, 32:] = -v
+    mlp = np.concatenate([m.astype(np.float16).ravel() for m in (d1, d2, c1, c2, c3)])
+
+    vol = val.astype(np.float32)
+
+    def indicator(x_ngp_pts):
+        q = ((x_ngp_pts - scene_lo) / aabb_scale) * scale + 0.5
+        q = np.clip(q, 0.0, res - 1.000001)
+        i0 = np.floor(q).astype(np.int64)
+        f = (q - i0).astype(np.float32)
+        out = np.zeros(q.shape[:-1], np.float32)
+        for dx in (0, 1):
+            for dy in (0, 1):
+                for dz in (0, 1):
+                    wt = ((f[..., 0] if dx else 1 - f[..., 0]) * (f[..., 1] if dy else 1 - f[..., 1])
+                          * (f[..., 2] if dz else 1 - f[..., 2]))
+                    out += wt * vol[i0[..., 0] + dx, i0[..., 1] + dy, i0[..., 2] + dz]
+        return out
+
+    thresh = math.log(0.01 / (math.sqrt(3) / 1024)) / DENSITY_LOGIT - 0.02
+    G = 128
+    occ_bits = np.zeros(cascades * G**3, np.uint8)
+    for c in range(cascades):
+        span = 2.0**c
+        e = np.arange(G + 1) / G
+        ez, ey, ex = np.meshgrid(e, e, e, indexing="ij")
+        corners = (np.stack([ex, ey, ez], -1) - 0.5) * span + 0.5
+        ind = indicator(corners.reshape(-1, 3)).reshape(G + 1, G + 1, G + 1)
+        m = ind[:-1, :-1, :-1]
+        for dz in (0, 1):
+            for dy in (0, 1):
+                for dx in (0, 1):
+                    m = np.maximum(m, ind[dz:G + dz, dy:G + dy, dx:G + dx])
+        occ_bits[c * G**3:(c + 1) * G**3] = (m > thresh).ravel().astype(np.uint8)
+    occupancy = np.packbits(occ_bits, bitorder="little")
+    return NerfSnapshot(grid=grid.astype(np.float16), mlp=mlp, occupancy=occupancy, log2_hashmap=log2_hashmap,
+                        base_res=base_res, per_level_scale=per_level_scale, cascades=cascades, aabb_scale=aabb_scale,
+                        cone_angle=cone_angle)
+
+
+def _loader_per_level_scale(aabb_scale: float, base_res: int = 16) -> float:
+    """per_level_scale as ngp.from_instant_ngp derives it: desired resolution 2048 x aabb_scale over 15 level steps,
+    rounded to the float32 the renderer holds it in."""
+    return float(np.float32(math.exp(math.log(2048.0 * aabb_scale / base_res) / 15)))
+
+
+# The snapshot geometries the renderer is verified on besides make_synthetic_nerf(11)'s (DESIGN.md, "Snapshot
+# geometries"): builder arguments of make_synthetic_nerf_variant.  unit_cube, scale2 and scale16 carry exactly what
+# ngp.from_instant_ngp derives for their aabb_scale (cascades, cone_angle, per_level_scale).
+NERF_VARIANT_SEED = 7
+_UNIT_BOX = [[0.2, 0.15, 0.25], [0.8, 0.9, 0.7]]
+_UNIT_CUT_BOX = [[0.2, 0.15, 0.3], [0.8, 0.9, 1.3]]  # the object runs through the scene cube's face z = 1
+_SCALE2_BOX = [[-0.2, 0.1, 0.2], [0.7, 1.2, 0.9]]
+_SCALE16_BOX = [[-3.0, -1.0, -2.5], [2.5, 4.0, 3.0]]
+NERF_VARIANTS = {
+    "unit_cube": dict(aabb=_UNIT_BOX, aabb_scale=1.0, cascades=1, cone_angle=0.0, log2_hashmap=19, base_res=16,
+                      per_level_scale=_loader_per_level_scale(1.0)),
+    "unit_cube_cut": dict(aabb=_UNIT_CUT_BOX, aabb_scale=1.0, cascades=1, cone_angle=0.0, log2_hashmap=19, base_res=16,
+                          per_level_scale=_loader_per_level_scale(1.0)),
+    "scale2": dict(aabb=_SCALE2_BOX, aabb_scale=2.0, cascades=2, cone_angle=1.0 / 256.0, log2_hashmap=15, base_res=16,
+                   per_level_scale=_loader_per_level_scale(2.0)),
+    "scale16": dict(aabb=_SCALE16_BOX, aabb_scale=16.0, cascades=5, cone_angle=1.0 / 256.0, log2_hashmap=14,
+                    base_res=16, per_level_scale=_loader_per_level_scale(16.0)),
+    "pow2": dict(aabb=PREMIER_PROTEIN_AABB, aabb_scale=4.0, cascades=3, cone_angle=1.0 / 256.0, log2_hashmap=16,
+                 base_res=8, per_level_scale=2.0),
+}
+_DIR = (0.9, 0.5, 0.3)
+# view cases: model, render box, eye = look_at + direction / |direction| x distance (up = +y), image size, passes, and the
+# cascades in which the march finds its samples there (probes of empty cells on the way in reach one cascade further in
+# scale16_far, scale16_near and pow2).  look_at None: the render box's centre.
+NERF_VARIANT_CASES = {
+    "unit_cube": dict(model="unit_cube", box=_UNIT_BOX, look_at=None, direction=_DIR, dist=1.3, size=(48, 36), spp=2,
+                      cascades_probed=(0,)),
+    "unit_cube_cut": dict(model="unit_cube_cut", box=_UNIT_CUT_BOX, look_at=(0.5, 0.525, 0.65), direction=(0.3, 0.4, 1.0),
+                          dist=1.4, size=(48, 36), spp=2, cascades_probed=(0,)),
+    "scale2": dict(model="scale2", box=_SCALE2_BOX, look_at=None, direction=_DIR, dist=2.0, size=(48, 36), spp=2,
+                   cascades_probed=(1,)),
+    "scale16_far": dict(model="scale16", box=_SCALE16_BOX, look_at=None, direction=_DIR, dist=11.0, size=(48, 36), spp=2,
+                        cascades_probed=(4,)),
+    "scale16_mid": dict(model="scale16", box=_SCALE16_BOX, look_at=None, direction=_DIR, dist=8.0, size=(48, 36), spp=2,
+                        cascades_probed=(3, 4)),
+    "scale16_near": dict(model="scale16", box=_SCALE16_BOX, look_at=None, direction=_DIR, dist=6.0, size=(32, 24), spp=2,
+                         cascades_probed=(2, 3)),
+    "pow2": dict(model="pow2", box=PREMIER_PROTEIN_AABB, look_at=None, direction=_DIR, dist=1.2, size=(48, 36), spp=2,
+                 cascades_probed=(1,)),
+}
+
+
+def make_nerf_variant(name: str):
+    return make_synthetic_nerf_variant(NERF_VARIANT_SEED, **NERF_VARIANTS[name])
+
+
+def nerf_variant_camera(case) -> np.ndarray:
+    """3 x 4 camera-to-world matrix (ngp coordinates) of a NERF_VARIANT_CASES entry."""
+    box = np.asarray(case["box"], float)
+    at = 0.5 * (box[0] + box[1]) if case["look_at"] is None else np.asarray(case["look_at"], float)
+    d = np.asarray(case["direction"], float)
+    eye = at + d / np.linalg.norm(d) * case["dist"]
+    R, _ = look_at_pose(eye, at, up=np.array([0.0, 1.0, 0.0]))
+    return np.concatenate([R.T, eye[:, None]], 1)
+
+
 # ---------------------------------------------------------------------------
 # Full-pipeline synthetic object (BASELINE configs 2-4): NeRF snapshot + SfM model
 # (reference cameras, surface points with tracks) + nerf2sfm + network weights + a

@@ -54,6 +54,25 @@ def single(name, tb, W, H, spp, mode):
     return out
 
 
+def variants():
+    """`render_checksum.py variants`: one 32 x 24, spp 8, mode-2 render of every case of synthetic.NERF_VARIANT_CASES (the
+    snapshot geometries besides the default one: aabb_scale 1 / 2 / 16, integer level scales)."""
+    from pixtrack_amd.synthetic import NERF_VARIANT_CASES, make_nerf_variant, nerf_variant_camera
+
+    snaps = {}
+    for name, case in NERF_VARIANT_CASES.items():
+        if case["model"] not in snaps:
+            snaps[case["model"]] = make_nerf_variant(case["model"])
+        t = testbed(snaps[case["model"]], [0.0, 0.0, 1.0], 1.0, 32)
+        t.render_aabb.min, t.render_aabb.max = [list(map(float, b)) for b in case["box"]]
+        t._cam_ngp = nerf_variant_camera(case)
+        single(name, t, 32, 24, 8, 2)
+
+
+if sys.argv[1:] == ["variants"]:
+    variants()
+    sys.exit(0)
+
 snap = make_synthetic_nerf(11)
 tb = testbed(snap, [0.9, 0.5, 0.3], 1.2, 64)
 for spp in (8, 3):
