@@ -1053,8 +1053,8 @@ int pxt_max_pairwise_distance(const float* points, int32_t n_points, void* works
  *
  * Reference: render_image (pixtrack/utils/pytorch3d_render_utils.py:55-93) and the YCB ground-truth renders built on
  * it.  BOP's VSD compares depth renders of the model's mesh at the estimated and the ground-truth pose; this draws
- * them.  An evaluation rasteriser for an object in front of the camera: no colour, no shading, no anti-aliasing, no
- * near-plane clipping, no lens terms.
+ * them.  An evaluation rasteriser for an object in front of the camera: no shading, no anti-aliasing, no near-plane
+ * clipping, no lens terms (vertex colours: pxt_mesh_render below).
  *
  * The rule (mesh_render.rasterize_reference restates it in numpy; the two agree bit for bit on every output):
  *   vertices [V][3] float32 (object frame); triangles [T][3] int32; views [P][PXT_MESH_VIEW = 20] float32:
@@ -1107,6 +1107,41 @@ int64_t pxt_mesh_raster_workspace_bytes(int32_t n_views, int32_t n_triangles, in
 int pxt_mesh_raster(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
                     const float* views, int32_t n_views, int32_t width, int32_t height, float* out_depth,
                     int32_t* out_tri, uint32_t* records, void* workspace, void* stream);
+
+/* -------------------------------------------------------------------------
+ * Colour renders of a mesh with vertex colours: pxt_mesh_raster's images plus the colour half of the reference's
+ * render_image (pixtrack/utils/pytorch3d_render_utils.py:55-93; scripts/create_sfm_from_obj.py renders its mapping
+ * images with it: ambient light only, black background), and the two 8-bit planes the tracker takes from the NeRF
+ * renderer.  csrc/pxt_raster.hip; mesh_render.shade_reference restates the rule in numpy and the two agree bit for bit
+ * on every output.
+ *
+ * vertices, triangles, views, width, height, records, workspace (pxt_mesh_raster_workspace_bytes) and the bounds are
+ * pxt_mesh_raster's; colors [V][3] float32, 0..1.  Coverage, depth, the depth test, out_depth, out_tri and records
+ * follow the rule above and equal what pxt_mesh_raster writes for the same inputs bit for bit.
+ *
+ * The colour of a covered pixel whose winning triangle is t: the triangle is set up again exactly as for the depth
+ *   (the same snapped X, Y, the same iz, the same exchange of the second and third vertex when A < 0 - the vertex colours
+ *   are exchanged with them), the three int64 edge functions are evaluated at the pixel, and then, every step a single
+ *   fp32 operation with IEEE division,
+ *       l_k = (float) e_k / (float) A;   w_k = l_k * iz_k;   inv = (w_0 + w_1) + w_2   (the bits of the depth rule's inv);
+ *       c = ((w_0 c_0 + w_1 c_1) + w_2 c_2) / inv   per channel;   c = fminf(fmaxf(c, 0), 1)   (a NaN becomes 0):
+ *   perspective-correct interpolation of the vertex colours, no lighting term.
+ * out_rgba [P][H][W][4] float32 or NULL: (r, g, b, 1) on a covered pixel, four zeros on the background.
+ * out_rgb_u8 [P][H][W][3] uint8 or NULL: pxt_rgba_to_u8's rule on out_rgba with threshold 0, (long long)(c * 255.0f) & 255.
+ * out_depth [P][H][W][4] float32 or NULL, out_tri [P][H][W] int32 or NULL: as pxt_mesh_raster.
+ * out_depth_nz [P][H][W] uint8 or NULL: pxt_ngp_render_frame's depth_nz rule on out_depth's first channel d,
+ *   ((long long)(d * 255.0f) & 255) != 0 - a d whose product with 255 lands in [256, 257) gives 0, as in the reference.
+ *   (d * 255 below 2^63; the conversion of a larger product is not part of the rule.)
+ * At least one of the five outputs is not NULL.  Alignment: out_rgba, out_depth and the workspace 16-byte; colors,
+ *   out_rgb_u8, out_depth_nz, out_tri and everything else 4-byte (the byte planes are stored as whole dwords, whatever
+ *   width * height is).  Anything else is PXT_E_ARG and nothing is launched or written.
+ * Four launches on `stream`: pxt_mesh_raster's first three unchanged, then one resolve that writes every requested
+ *   output and folds the record.  No host synchronisation, no allocation.  Measured on the MI355X: DESIGN.md 3.16.
+ * ---------------------------------------------------------------------- */
+int pxt_mesh_render(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                    const float* colors, const float* views, int32_t n_views, int32_t width, int32_t height,
+                    float* out_rgba, uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz, int32_t* out_tri,
+                    uint32_t* records, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,5 @@
-// Depth rasteriser for triangle meshes (pxt_mesh_raster, include/pixtrack_hip.h; pixtrack_amd/mesh_render.py).
+// Depth rasteriser for triangle meshes (pxt_mesh_raster, include/pixtrack_hip.h; pixtrack_amd/mesh_render.py), and
+// further down its colour resolve for meshes with vertex colours (pxt_mesh_render).
 //
 // The reference draws meshes with pytorch3d (pixtrack/utils/pytorch3d_render_utils.py:55-93, render_image) for its
 // YCB ground-truth renders; this is the depth part of that for the evaluation stack: BOP's VSD compares depth renders
@@ -344,6 +345,172 @@ __global__ __launch_bounds__(kRsBlock) void rs_resolve_kernel(const RsArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// pxt_mesh_render: the same clear, triangle and list launches, then rs_shade_resolve_kernel instead of
+// rs_resolve_kernel.  It writes every requested output from the key plane in one pass: the depth image, the id plane and
+// the record as rs_resolve_kernel does, and the colour of the winning triangle at the pixel, for which the triangle is
+// set up again from its three vertices (the key holds its index; neighbouring pixels share the gathers).
+//
+// The pixels of all views are numbered in one row, g = view * W * H + pixel, and a workgroup takes kRsShadePixels of
+// them from a multiple of four on: the lane's pixels are g0 + k * kRsBlock + tid (coalesced keys, float4 images and
+// ids), the 8-bit results meet in LDS, and then lane tid owns the four pixels g0 + 4 tid ..: bytes 12 (g0 / 4 + tid) of
+// the colour plane and 4 (g0 / 4 + tid) of the depth_nz plane, whole aligned dwords whatever W * H is.  A group of four
+// that a view shares with its neighbour (or that ends past the last view) is stored bytewise by each view's workgroup.
+struct RsShade {
+  const float* colors;  // [V][3]
+  float* out_rgba;
+  unsigned char* out_rgb_u8;
+  unsigned char* out_nz;
+};
+
+constexpr int kRsShadePixels = kRsBlock * 4;
+
+__device__ __forceinline__ unsigned rs_u8(float c) { return (unsigned)((long long)(c * 255.0f) & 255); }
+
+// The colour of triangle t at pixel (i, j): set up as rs_setup does (the same rs_vertex, area and exchange; the colours
+// follow the exchange), no cull - t won the pixel, so it was drawn.  -> rgb, zeros if t cannot have been drawn.
+__device__ __forceinline__ void rs_shade(const RsArgs& a, const float* __restrict__ colors, const RsView& v, int t, int i,
+                                         int j, float* rgb) {
+  rgb[0] = rgb[1] = rgb[2] = 0.f;
+  if ((unsigned)t >= (unsigned)a.T) return;
+  const int* f = a.triangles + 3 * (size_t)t;
+  int idx[3] = {f[0], f[1], f[2]};
+  if ((unsigned)idx[0] >= (unsigned)a.V || (unsigned)idx[1] >= (unsigned)a.V || (unsigned)idx[2] >= (unsigned)a.V) return;
+  int x[3], y[3];
+  float iz[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (rs_vertex(v, a.vertices + 3 * (size_t)idx[k], &x[k], &y[k], &iz[k]) != RS_DRAWN) return;
+  long long area = (long long)(x[1] - x[0]) * (y[2] - y[0]) - (long long)(y[1] - y[0]) * (x[2] - x[0]);
+  if (area == 0) return;
+  if (area < 0) {
+    const int tx = x[1], ty = y[1], ti = idx[1];
+    const float tz = iz[1];
+    x[1] = x[2]; y[1] = y[2]; iz[1] = iz[2]; idx[1] = idx[2];
+    x[2] = tx; y[2] = ty; iz[2] = tz; idx[2] = ti;
+    area = -area;
+  }
+  const int px = i << 8, py = j << 8;
+  const float A = (float)area;
+  float w[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int p = (k + 1) % 3, q = (k + 2) % 3;
+    const long long e = (long long)(x[q] - x[p]) * (py - y[p]) - (long long)(y[q] - y[p]) * (px - x[p]);
+    const float l = (float)e / A;
+    w[k] = l * iz[k];
+  }
+  const float inv = (w[0] + w[1]) + w[2];
+  const float* c0 = colors + 3 * (size_t)idx[0];
+  const float* c1 = colors + 3 * (size_t)idx[1];
+  const float* c2 = colors + 3 * (size_t)idx[2];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float c = ((w[0] * c0[ch] + w[1] * c1[ch]) + w[2] * c2[ch]) / inv;
+    rgb[ch] = fminf(fmaxf(c, 0.f), 1.0f);  // a NaN -> 0
+  }
+}
+
+__global__ __launch_bounds__(kRsBlock) void rs_shade_resolve_kernel(const RsArgs a, const RsShade o) {
+  __shared__ unsigned red[3][kRsWaves];
+  __shared__ __attribute__((aligned(16))) unsigned packed[kRsShadePixels];  // r | g << 8 | b << 16 | depth_nz << 24
+  const int view = blockIdx.y, tid = threadIdx.x;
+  const size_t wh = (size_t)a.W * a.H;
+  const size_t start = (size_t)view * wh, end = start + wh;  // the view's pixels in the row of all views
+  const size_t g0 = (start & ~(size_t)3) + (size_t)blockIdx.x * kRsShadePixels;
+  const bool want_rgb = o.out_rgba || o.out_rgb_u8, want_bytes = o.out_rgb_u8 || o.out_nz;
+  RsView v;
+  rs_load_view(a.views + (size_t)view * PXT_MESH_VIEW, &v);  // a view that is not finite has no covered pixel
+  unsigned mn = 0xffffffffu, mx = 0u, cnt = 0u;
+  unsigned long long keys[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const size_t g = g0 + (size_t)k * kRsBlock + tid;
+    keys[k] = g >= start && g < end ? a.keys[g] : kRsEmpty;
+  }
+#pragma unroll 1
+  for (int k = 0; k < 4; ++k) {
+    const size_t g = g0 + (size_t)k * kRsBlock + tid;
+    unsigned pk = 0u;
+    if (g >= start && g < end) {
+      const unsigned long long key = keys[k];
+      const bool cov = key != kRsEmpty;
+      const unsigned zb = (unsigned)(key >> 32);
+      const int t = (int)(unsigned)(key & 0xffffffffull);
+      float d = 0.f, rgb[3] = {0.f, 0.f, 0.f};
+      if (cov) {
+        d = __builtin_bit_cast(float, zb) * v.depth_q;
+        mn = min(mn, zb);
+        mx = max(mx, zb);
+        ++cnt;
+        if (want_rgb) {
+          const int pix = (int)(g - start);  // < 2^26
+          rs_shade(a, o.colors, v, t, pix % a.W, pix / a.W, rgb);
+        }
+      }
+      const float alpha = cov ? 1.0f : 0.f;
+      if (a.out_depth) ((float4*)a.out_depth)[g] = make_float4(d, d, d, alpha);
+      if (o.out_rgba) ((float4*)o.out_rgba)[g] = make_float4(rgb[0], rgb[1], rgb[2], alpha);
+      if (a.out_tri) a.out_tri[g] = cov ? t : -1;
+      pk = rs_u8(rgb[0]) | (rs_u8(rgb[1]) << 8) | (rs_u8(rgb[2]) << 16) | (rs_u8(d) != 0u ? 1u << 24 : 0u);
+    }
+    if (want_bytes) packed[k * kRsBlock + tid] = pk;
+  }
+  if (want_bytes) {  // the whole workgroup alike
+    __syncthreads();
+    const uint4 q = ((const uint4*)packed)[tid];
+    const size_t g = g0 + 4 * (size_t)tid;  // a multiple of four
+    if (g >= start && g + 4 <= end) {
+      if (o.out_rgb_u8) {
+        unsigned* p = (unsigned*)(o.out_rgb_u8 + 3 * g);
+        p[0] = (q.x & 0xffffffu) | (q.y << 24);
+        p[1] = ((q.y >> 8) & 0xffffu) | (q.z << 16);
+        p[2] = ((q.z >> 16) & 0xffu) | (q.w << 8);
+      }
+      if (o.out_nz) *(unsigned*)(o.out_nz + g) = (q.x >> 24) | ((q.y >> 24) << 8) | ((q.z >> 24) << 16) | ((q.w >> 24) << 24);
+    } else {
+      const unsigned qs[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (g + k < start || g + k >= end) continue;
+        if (o.out_rgb_u8) {
+          o.out_rgb_u8[3 * (g + k) + 0] = (unsigned char)(qs[k] & 0xffu);
+          o.out_rgb_u8[3 * (g + k) + 1] = (unsigned char)((qs[k] >> 8) & 0xffu);
+          o.out_rgb_u8[3 * (g + k) + 2] = (unsigned char)((qs[k] >> 16) & 0xffu);
+        }
+        if (o.out_nz) o.out_nz[g + k] = (unsigned char)(qs[k] >> 24);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < PXT_WAVE; m <<= 1) {
+    mn = min(mn, (unsigned)__shfl_xor((int)mn, m, PXT_WAVE));
+    mx = max(mx, (unsigned)__shfl_xor((int)mx, m, PXT_WAVE));
+    cnt += (unsigned)__shfl_xor((int)cnt, m, PXT_WAVE);
+  }
+  if ((tid & (PXT_WAVE - 1)) == 0) {
+    red[0][tid / PXT_WAVE] = cnt;
+    red[1][tid / PXT_WAVE] = mn;
+    red[2][tid / PXT_WAVE] = mx;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned c = 0u, lo = 0xffffffffu, hi = 0u;
+#pragma unroll
+    for (int w = 0; w < kRsWaves; ++w) {
+      c += red[0][w];
+      lo = min(lo, red[1][w]);
+      hi = max(hi, red[2][w]);
+    }
+    if (c) {  // as rs_resolve_kernel
+      unsigned* rec = a.records + (size_t)view * PXT_MESH_RASTER_RECORD;
+      atomicAdd(rec + RS_W_COVERED, c);
+      if (lo < __hip_atomic_load(rec + RS_W_ZMIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(rec + RS_W_ZMIN, lo);
+      if (hi > __hip_atomic_load(rec + RS_W_ZMAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(rec + RS_W_ZMAX, hi);
+    }
+  }
+}
+
 constexpr int64_t kRsMaxPixels = (int64_t)1 << 26;
 constexpr int kRsMaxViews = 4096, kRsMaxCount = 1 << 24;
 
@@ -396,6 +563,48 @@ extern "C" int pxt_mesh_raster(const float* vertices, int32_t n_vertices, const 
   const int64_t res_pixels = (int64_t)kRsBlock * kRsResolvePixels;
   const unsigned res_blocks = (unsigned)(((int64_t)width * height + res_pixels - 1) / res_pixels);
   hipLaunchKernelGGL(rs_resolve_kernel, dim3(res_blocks, n_views), dim3(kRsBlock), 0, s, a);
+  PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}
+
+extern "C" int pxt_mesh_render(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                               const float* colors, const float* views, int32_t n_views, int32_t width, int32_t height,
+                               float* out_rgba, uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz,
+                               int32_t* out_tri, uint32_t* records, void* workspace, void* stream) {
+  if (!rs_sizes_ok(n_views, n_triangles, width, height) || n_vertices < 1 || n_vertices > kRsMaxCount) return PXT_E_ARG;
+  if (!vertices || !triangles || !colors || !views || !records || !workspace) return PXT_E_ARG;
+  if (!out_rgba && !out_rgb_u8 && !out_depth && !out_depth_nz && !out_tri) return PXT_E_ARG;
+  if (((uintptr_t)vertices % 4) != 0 || ((uintptr_t)triangles % 4) != 0 || ((uintptr_t)colors % 4) != 0 ||
+      ((uintptr_t)views % 4) != 0 || ((uintptr_t)out_tri % 4) != 0 || ((uintptr_t)records % 4) != 0 ||
+      ((uintptr_t)out_rgb_u8 % 4) != 0 || ((uintptr_t)out_depth_nz % 4) != 0 || ((uintptr_t)out_rgba % 16) != 0 ||
+      ((uintptr_t)out_depth % 16) != 0 || ((uintptr_t)workspace % 16) != 0)
+    return PXT_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  RsArgs a;
+  a.vertices = vertices; a.triangles = (const int*)triangles; a.views = views;
+  a.V = n_vertices; a.T = n_triangles; a.P = n_views; a.W = width; a.H = height; a.cap = rs_cap(n_triangles);
+  const int64_t key_bytes = rs_key_bytes(n_views, width, height);
+  a.keys = (unsigned long long*)workspace;
+  a.list_count = (unsigned*)((char*)workspace + key_bytes);
+  a.list = (uint4*)((char*)workspace + key_bytes + rs_count_bytes(n_views));
+  a.out_depth = out_depth; a.out_tri = (int*)out_tri; a.records = (unsigned*)records;
+  RsShade o;
+  o.colors = colors; o.out_rgba = out_rgba; o.out_rgb_u8 = out_rgb_u8; o.out_nz = out_depth_nz;
+
+  // launches 1 to 3 as pxt_mesh_raster makes them
+  const size_t n_units = (size_t)(key_bytes / 16);
+  const size_t clear_work = std::max(n_units, (size_t)n_views * PXT_MESH_RASTER_RECORD);
+  const unsigned clear_blocks = (unsigned)std::min<size_t>((clear_work + kRsBlock - 1) / kRsBlock, 8192);
+  hipLaunchKernelGGL(rs_clear_kernel, dim3(clear_blocks), dim3(kRsBlock), 0, s, a, n_units);
+  PXT_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(rs_triangle_kernel, dim3((n_triangles + kRsTriBlock - 1) / kRsTriBlock, n_views), dim3(kRsTriBlock), 0, s, a);
+  PXT_HIP_CHECK(hipGetLastError());
+  const int tiles_x = (width + kRsTile - 1) / kRsTile, tiles_y = (height + kRsTile - 1) / kRsTile;
+  hipLaunchKernelGGL(rs_list_kernel, dim3((unsigned)tiles_x * (unsigned)tiles_y, n_views), dim3(kRsBlock), 0, s, a, tiles_x);
+  PXT_HIP_CHECK(hipGetLastError());
+  // a view's pixels begin up to three past a multiple of four in the row of all views
+  const unsigned res_blocks = (unsigned)(((int64_t)width * height + 3 + kRsShadePixels - 1) / kRsShadePixels);
+  hipLaunchKernelGGL(rs_shade_resolve_kernel, dim3(res_blocks, n_views), dim3(kRsBlock), 0, s, a, o);
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;
 }

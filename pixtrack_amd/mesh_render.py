@@ -1,5 +1,5 @@
-"""Depth renders of a triangle mesh: the GPU rasteriser (pxt_mesh_raster, csrc/pxt_raster.hip), its numpy restatement and
-the readers that feed it.
+"""Depth and colour renders of a triangle mesh: the GPU rasteriser (pxt_mesh_raster, pxt_mesh_render;
+csrc/pxt_raster.hip), its numpy restatement and the readers that feed it.
 
 The reference draws meshes with pytorch3d (``pixtrack/utils/pytorch3d_render_utils.py:55-93``, ``render_image``;
 ``scripts/create_sfm_from_obj.py``; the YCB ground-truth notebook).  Here the renders serve the evaluation stack: BOP's
@@ -9,6 +9,11 @@ intrinsics (``mesh_evaluation.py``), and the mesh ``mesh.py`` extracts can be he
 ``rasterize_reference`` restates the rule of ``include/pixtrack_hip.h`` in numpy float32 / int64 arithmetic; the kernel
 is held to it bit for bit on the depth image, the triangle ids and the records.  There is no CPU product path: the
 restatement draws a few thousand triangles per second and exists for the tests.
+
+Colour (``MeshRenderer.render``, ``shade_reference``): the vertex colours of the winning triangle, interpolated
+perspective-correctly, no lighting term and a black background - the reference's ambient-lit ``render_image`` as
+``scripts/create_sfm_from_obj.py`` uses it - written as the float image and as the 8-bit planes the tracker takes from
+the NeRF renderer (``rgb_u8``, ``depth_nz``).  ``mesh_dataset.py`` builds a reference model from such renders.
 """
 from __future__ import annotations
 
@@ -103,17 +108,10 @@ def _evaluate(x, y, iz, area, px, py):
     return ins, valid, np.ascontiguousarray(np.broadcast_to(z, np.broadcast(ins, z).shape)).view(np.uint32)
 
 
-def _raster_view(V, F, view, W, H, want_cov):
-    key = np.full(H * W, _EMPTY, np.uint64)
-    cov = np.zeros(H * W, np.int32) if want_cov else None
-    rec = np.zeros(RECORD, np.uint32)
-    rec[W_ZMIN] = 0xFFFFFFFF
-    if not np.all(np.isfinite(view)):
-        rec[W_STATUS] = 0xFFFFFFFF
-        return key, cov, rec
+def _project_vertices(V, view):
+    """The per-vertex part of the rule for a finite view -> near, guard, X, Y (int64, 0 where not fine), iz."""
     R, t = view[:9].reshape(3, 3), view[9:12]
     fx, fy, cx, cy, near = view[12], view[13], view[14], view[15], view[16]
-    nV = len(V)
     with np.errstate(all="ignore"):
         p = np.stack([(((R[k, 0] * V[:, 0] + R[k, 1] * V[:, 1]).astype(_F) + R[k, 2] * V[:, 2]).astype(_F) + t[k]).astype(_F)
                       for k in range(3)], 1)
@@ -128,6 +126,19 @@ def _raster_view(V, F, view, W, H, want_cov):
         X = np.where(fine, xs, 0).astype(np.int64)
         Y = np.where(fine, ys, 0).astype(np.int64)
         iz = (_F(1.0) / p[:, 2]).astype(_F)
+    return is_near, is_guard, X, Y, iz
+
+
+def _raster_view(V, F, view, W, H, want_cov):
+    key = np.full(H * W, _EMPTY, np.uint64)
+    cov = np.zeros(H * W, np.int32) if want_cov else None
+    rec = np.zeros(RECORD, np.uint32)
+    rec[W_ZMIN] = 0xFFFFFFFF
+    if not np.all(np.isfinite(view)):
+        rec[W_STATUS] = 0xFFFFFFFF
+        return key, cov, rec
+    nV = len(V)
+    is_near, is_guard, X, Y, iz = _project_vertices(V, view)
     idx_ok = ((F >= 0) & (F < nV)).all(1)
     Fc = np.clip(F, 0, nV - 1)
     guard = idx_ok & is_guard[Fc].any(1)
@@ -207,13 +218,71 @@ def rasterize_reference(V, F, views, width: int, height: int, coverage: bool = F
     return (depth, ids, recs, cov) if coverage else (depth, ids, recs)
 
 
+def _shade_view(V, F, C, view, ids, W):
+    """The colour rule for the covered pixels of one view, all at once: ``ids`` [H * W] -> (pixels, rgb [n, 3] float32)."""
+    pix = np.nonzero(ids >= 0)[0]
+    if len(pix) == 0:
+        return pix, np.zeros((0, 3), _F)
+    _, _, X, Y, iz = _project_vertices(V, view)
+    idx = F[ids[pix]]
+    idx = [idx[:, 0], idx[:, 1], idx[:, 2]]
+    x3, y3, z3 = [X[i] for i in idx], [Y[i] for i in idx], [iz[i] for i in idx]
+    area = (x3[1] - x3[0]) * (y3[2] - y3[0]) - (y3[1] - y3[0]) * (x3[2] - x3[0])
+    flip = area < 0
+    for a3 in (x3, y3, z3, idx):  # the colours follow the exchange through their indices
+        a3[1], a3[2] = np.where(flip, a3[2], a3[1]), np.where(flip, a3[1], a3[2])
+    px, py = (pix % W) * SUB, (pix // W) * SUB
+    with np.errstate(all="ignore"):
+        A = np.abs(area).astype(_F)
+        w = []
+        for k in range(3):
+            a, b = (k + 1) % 3, (k + 2) % 3
+            e = (x3[b] - x3[a]) * (py - y3[a]) - (y3[b] - y3[a]) * (px - x3[a])
+            w.append(((e.astype(_F) / A).astype(_F) * z3[k]).astype(_F))
+        inv = ((w[0] + w[1]).astype(_F) + w[2]).astype(_F)
+        c = [C[i] for i in idx]
+        num = ((w[0][:, None] * c[0]).astype(_F) + (w[1][:, None] * c[1]).astype(_F)).astype(_F) + (w[2][:, None] * c[2]).astype(_F)
+        rgb = np.fmin(np.fmax((num.astype(_F) / inv[:, None]).astype(_F), _F(0)), _F(1))  # a NaN -> 0
+    return pix, rgb.astype(_F)
+
+
+def _u8(x):
+    """``(long long)(x * 255.0f) & 255`` on float32 values."""
+    with np.errstate(all="ignore"):
+        return ((np.asarray(x, _F) * _F(255.0)).astype(_F).astype(np.int64) & 255).astype(np.uint8)
+
+
+def shade_reference(V, F, C, views, width: int, height: int):
+    """The rule of pxt_mesh_render in numpy, on ``rasterize_reference``'s depth and ids.  ``C`` [n, 3] float32 vertex
+    colours -> ``(rgba [P, H, W, 4] float32, rgb_u8 [P, H, W, 3] uint8, depth [P, H, W, 4] float32, depth_nz [P, H, W]
+    uint8, triangle ids [P, H, W] int32, records [P, 16] uint32)``."""
+    V = np.ascontiguousarray(np.asarray(V, np.float32).reshape(-1, 3))
+    F = np.asarray(F).reshape(-1, 3).astype(np.int64)
+    C = np.ascontiguousarray(np.asarray(C, np.float32).reshape(-1, 3))
+    if len(C) != len(V):
+        raise ValueError(f"{len(C)} colours for {len(V)} vertices")
+    views = np.asarray(views, np.float32).reshape(-1, VIEW)
+    P, W, H = len(views), int(width), int(height)
+    depth, ids, recs = rasterize_reference(V, F, views, W, H)
+    rgba = np.zeros((P, H, W, 4), np.float32)
+    for p in range(P):
+        pix, rgb = _shade_view(V, F, C, views[p], ids[p].reshape(-1), W)
+        plane = rgba[p].reshape(-1, 4)
+        plane[pix, :3] = rgb
+        plane[pix, 3] = 1.0
+    return rgba, _u8(rgba[..., :3]), depth, (_u8(depth[..., 0]) != 0).astype(np.uint8), ids, recs
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the GPU renderer
 # ---------------------------------------------------------------------------------------------------------------------
 class MeshRenderer:
-    """Holds a mesh on the device and draws depth images of it (``torch.ops.pixtrack.mesh_raster``)."""
+    """Holds a mesh on the device and draws depth images of it (``torch.ops.pixtrack.mesh_raster``) and, given vertex
+    colours, colour images and the tracker's 8-bit planes (``torch.ops.pixtrack.mesh_render``)."""
 
-    def __init__(self, V, F, device="cuda:0"):
+    OUTPUTS = ("rgba", "rgb_u8", "depth", "depth_nz", "ids")
+
+    def __init__(self, V, F, device="cuda:0", colors=None):
         from . import ops  # registers the ops
 
         self._ops = ops.ops
@@ -226,11 +295,52 @@ class MeshRenderer:
             raise _lib.PxtError(f"a mesh needs vertices and triangles (got {len(Vn)}, {len(Fn)})")
         if Fn.min() < -(1 << 31) or Fn.max() >= (1 << 31):
             raise _lib.PxtError("triangle indices do not fit int32")
+        if colors is not None:
+            Cn = np.ascontiguousarray(np.asarray(colors.detach().cpu().numpy() if torch.is_tensor(colors) else colors, np.float32))
+            if Cn.shape != Vn.shape:
+                raise _lib.PxtError(f"colors is {Cn.shape}, expected one r g b per vertex {Vn.shape}")
+            if not np.isfinite(Cn).all() or Cn.min() < 0.0 or Cn.max() > 1.0:
+                raise _lib.PxtError("colors must be finite and inside [0, 1]")
         self.device = dev
         self.vertices_host = Vn
         self.vertices = torch.from_numpy(Vn).to(dev)
         self.triangles = torch.from_numpy(np.ascontiguousarray(Fn.astype(np.int32))).to(dev)
         self._workspace: Optional[torch.Tensor] = None
+        self.colors = None if colors is None else torch.from_numpy(Cn).to(dev)
+
+    def _views_and_workspace(self, views, width, height, what):
+        vh = views.detach().cpu().numpy() if torch.is_tensor(views) else views
+        vh = np.ascontiguousarray(np.asarray(vh, np.float32).reshape(-1, VIEW))
+        P, W, H = len(vh), int(width), int(height)
+        need = int(_lib.lib().pxt_mesh_raster_workspace_bytes(P, self.n_triangles, W, H)) if min(P, W, H) >= 1 else -1
+        if need <= 0:
+            raise _lib.PxtError(f"{what}: {P} views of {W} x {H} are not supported (1..4096 views, 1..2^26 pixels)")
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return torch.from_numpy(vh).to(self.device), P, W, H
+
+    def render(self, views, width: int, height: int, want: Sequence[str] = ("rgb_u8", "depth_nz"),
+               download_records: bool = True) -> dict:
+        """``views`` [P, 20] -> a dict of device tensors for the outputs named in ``want`` (of ``rgba`` [P, H, W, 4],
+        ``rgb_u8`` uint8 [P, H, W, 3], ``depth`` [P, H, W, 4], ``depth_nz`` uint8 [P, H, W], ``ids`` int32 [P, H, W]) and
+        ``records`` ([P, 16] uint32 numpy, or the int32 device tensor with ``download_records=False``).  One call, four
+        launches; the default is what the tracker takes from the NeRF renderer per frame."""
+        if self.colors is None:
+            raise _lib.PxtError("render needs vertex colours: MeshRenderer(V, F, device, colors=...)")
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.OUTPUTS]
+        if unknown or not want:
+            raise _lib.PxtError(f"render: want names outputs of {self.OUTPUTS} (got {want})")
+        v, P, W, H = self._views_and_workspace(views, width, height, "mesh_render")
+        shapes = {"rgba": ((P, H, W, 4), torch.float32), "rgb_u8": ((P, H, W, 3), torch.uint8),
+                  "depth": ((P, H, W, 4), torch.float32), "depth_nz": ((P, H, W), torch.uint8),
+                  "ids": ((P, H, W), torch.int32)}
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in want}
+        records = torch.empty((P, RECORD), dtype=torch.int32, device=self.device)
+        self._ops.mesh_render(self.vertices, self.triangles, self.colors, v, W, H, out.get("rgba"), out.get("rgb_u8"),
+                              out.get("depth"), out.get("depth_nz"), out.get("ids"), records, self._workspace)
+        out["records"] = records.cpu().numpy().view(np.uint32) if download_records else records
+        return out
 
     @property
     def n_vertices(self) -> int:
@@ -245,20 +355,12 @@ class MeshRenderer:
         """``views`` [P, 20] (numpy or tensor) -> ``(depth [P, H, W, 4] device tensor, ids int32 [P, H, W] device tensor or
         None, records [P, 16] uint32 numpy)``.  Nothing but the records is downloaded; with ``download_records=False``
         not even those (the int32 device tensor is returned, and the host does not wait for the launches)."""
-        vh = views.detach().cpu().numpy() if torch.is_tensor(views) else views
-        vh = np.ascontiguousarray(np.asarray(vh, np.float32).reshape(-1, VIEW))
-        P, W, H = len(vh), int(width), int(height)
-        need = int(_lib.lib().pxt_mesh_raster_workspace_bytes(P, self.n_triangles, W, H)) if min(P, W, H) >= 1 else -1
-        if need <= 0:
-            raise _lib.PxtError(f"mesh_raster: {P} views of {W} x {H} are not supported (1..4096 views, 1..2^26 pixels)")
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        v, P, W, H = self._views_and_workspace(views, width, height, "mesh_raster")
         if out is None:
             out = torch.empty((P, H, W, 4), dtype=torch.float32, device=self.device)
         ids = torch.empty((P, H, W), dtype=torch.int32, device=self.device) if triangle_ids else None
         records = torch.empty((P, RECORD), dtype=torch.int32, device=self.device)
-        self._ops.mesh_raster(self.vertices, self.triangles, torch.from_numpy(vh).to(self.device), out, ids, records,
-                              self._workspace)
+        self._ops.mesh_raster(self.vertices, self.triangles, v, out, ids, records, self._workspace)
         return out, ids, (records.cpu().numpy().view(np.uint32) if download_records else records)
 
 
@@ -308,6 +410,42 @@ def torus(major: float = 1.0, minor: float = 0.35, n_major: int = 24, n_minor: i
     return V, np.asarray(F, np.int64)
 
 
+def look_at_views(V, fx: float, fy: float, cx: float, cy: float, width: int, height: int, subdivisions: int = 2,
+                  near: float = 1e-6, depth_q: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
+    """Views around a mesh that look at it and hold all of it: ``(views [P, 20] float32, poses [P, 4, 4] float64,
+    world -> camera)``, P = 12 / 42 / 162 for 0 / 1 / 2 subdivisions.
+
+    The reference's rule (``create_look_at_poses_for_mesh``, ``scripts/create_sfm_from_obj.py``): the eyes sit on a
+    sphere about the target in the directions of an icosphere's vertices, at the distance from which a sphere of the
+    mesh's radius ``r`` (half the diagonal of its bounding box) fills the narrower field of view,
+    ``max(r / sin(atan(W / 2 fx)), r / sin(atan(H / 2 fy)))``.  The camera frame is the project's: x right, y down, z
+    forward; z points from the eye to the target, ``up`` is +y (+z where the direction's ``|y| > 0.999``), x =
+    normalize(z x up), y = z x x; R has the rows x, y, z and t = -R eye.  ``cx, cy`` are in the ``Camera`` convention
+    (pixel centres at integer coordinates).
+
+    Two departures from the reference: the directions, and so the order of the views, are ``icosphere(subdivisions)``'s
+    vertices, not trimesh's; and the target is the centre of the bounding box, not the origin - the same thing for
+    BOP's centred models."""
+    V = np.asarray(V, np.float64).reshape(-1, 3)
+    lo, hi = V.min(0), V.max(0)
+    centre, r = 0.5 * (lo + hi), 0.5 * float(np.linalg.norm(hi - lo))
+    dist = max(r / np.sin(np.arctan(width / (2.0 * fx))), r / np.sin(np.arctan(height / (2.0 * fy))))
+    dirs, _ = icosphere(subdivisions)
+    views, poses = [], []
+    for d in dirs:
+        eye = centre + dist * d
+        z = -d
+        up = np.asarray([0.0, 0.0, 1.0]) if abs(d[1]) > 0.999 else np.asarray([0.0, 1.0, 0.0])
+        x = np.cross(z, up)
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = R, -R @ eye
+        poses.append(T)
+        views.append(pack_view(R, T[:3, 3], fx, fy, cx, cy, near, depth_q))
+    return np.stack(views), np.stack(poses)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # readers
 # ---------------------------------------------------------------------------------------------------------------------
@@ -327,7 +465,7 @@ def fan_triangles(polygons: Sequence[Sequence[int]]) -> np.ndarray:
     return np.asarray(out, np.int64).reshape(-1, 3)
 
 
-def _read_ply(path):
+def _read_ply(path, colors=False):
     with open(str(path), "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
@@ -368,7 +506,7 @@ def _read_ply(path):
         pos[0] += struct.calcsize(c)
         return val
 
-    V, polys, seen = None, None, set()
+    V, C, polys, seen = None, None, None, set()
     for name, count, props in elements:
         seen.add(name)
         if name == "vertex":
@@ -381,9 +519,14 @@ def _read_ply(path):
                 rows = np.frombuffer(data, dt, count, pos[0])
                 pos[0] += count * dt.itemsize
                 V = np.stack([rows[k].astype(np.float64) for k in "xyz"], 1).reshape(-1, 3)
+                column = lambda k: rows[k].astype(np.float64)
             else:
-                rows = [[scalar(p[2]) for p in props] for _ in range(count)]
-                V = np.asarray(rows, np.float64).reshape(count, len(props))[:, cols]
+                rows = np.asarray([[scalar(p[2]) for p in props] for _ in range(count)], np.float64).reshape(count, len(props))
+                V = rows[:, cols]
+                column = lambda k: rows[:, names.index(k)]
+            if colors and all(k in names for k in ("red", "green", "blue")):  # integers are 0..255, floats 0..1
+                C = np.stack([column(k) / (1.0 if _PLY_TYPES[props[names.index(k)][2]] in "fd" else 255.0)
+                              for k in ("red", "green", "blue")], 1).reshape(-1, 3)
         elif name == "face":
             lists = [p for p in props if p[0] == "list"]
             if len(lists) != 1 or lists[0][1] not in ("vertex_indices", "vertex_index"):
@@ -408,7 +551,7 @@ def _read_ply(path):
     for need in ("vertex", "face"):
         if need not in seen:
             raise ValueError(f"{path}: no element {need}")
-    return V, fan_triangles(polys)
+    return (V, fan_triangles(polys), C) if colors else (V, fan_triangles(polys))
 
 
 def _read_obj_polygons(path):
@@ -448,3 +591,20 @@ def read_mesh(path) -> Tuple[np.ndarray, np.ndarray]:
     if F.min() < 0 or F.max() >= len(V):
         raise ValueError(f"{path}: face indices outside the {len(V)} vertices")
     return V, F
+
+
+def read_mesh_colors(path) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    """``read_mesh`` plus the vertex colours: ``(V, F, C [n, 3] float64 in 0..1, or None for a file without them)``.
+    PLY: the vertex properties ``red green blue`` - integer types (BOP's uchar) are divided by 255, float types are
+    taken as 0..1; an ``alpha`` property is ignored.  OBJ: ``v x y z r g b`` (what ``mesh.write_obj`` writes).  Texture
+    maps (OBJ ``vt`` / ``usemtl``, PLY ``texture_u``) are not read: a textured model without vertex colours comes back
+    with ``None``."""
+    from . import mesh
+
+    V, F = read_mesh(path)
+    if Path(str(path)).suffix.lower() == ".ply":
+        C = _read_ply(path, colors=True)[2]
+    else:
+        C = mesh.read_obj(path)[2]
+        C = C if C is not None and len(C) == len(V) else None
+    return V, F, C

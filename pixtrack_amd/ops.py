@@ -185,6 +185,13 @@ SCHEMAS = {
     "mesh_raster": (
         "(Tensor vertices, Tensor triangles, Tensor views, Tensor(a!) depth, Tensor(b!)? triangle_ids, "
         "Tensor(c!) records, Tensor(d!) workspace) -> ()"),
+    # the same mesh with colors [V, 3] float32 (0..1) -> any of rgba [P, H, W, 4], rgb_u8 uint8 [P, H, W, 3], depth
+    # [P, H, W, 4], depth_nz uint8 [P, H, W], triangle_ids int32 [P, H, W] (at least one; pxt_mesh_render), records
+    # and workspace as mesh_raster.  width / height say the size: no output is mandatory
+    "mesh_render": (
+        "(Tensor vertices, Tensor triangles, Tensor colors, Tensor views, int width, int height, Tensor(a!)? rgba, "
+        "Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, Tensor(e!)? triangle_ids, Tensor(f!) records, "
+        "Tensor(g!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -1233,8 +1240,55 @@ def _mesh_raster(vertices, triangles, views, depth, triangle_ids, records, works
                                  _stream(vertices)), "pxt_mesh_raster")
 
 
+def _mesh_render(vertices, triangles, colors, views, width, height, rgba, rgb_u8, depth, depth_nz, triangle_ids,
+                 records, workspace):
+    L = _lib.lib()
+    _f32c(vertices, "vertices")
+    _f32c(views, "views")
+    _f32c(colors, "colors")
+    if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or triangles.dim() != 2 or int(triangles.shape[1]) != 3
+            or triangles.dtype != torch.int32 or not triangles.is_contiguous() or views.dim() != 2
+            or int(views.shape[1]) != _lib.PXT_MESH_VIEW):
+        raise _lib.PxtError(f"mesh_render: vertices {tuple(vertices.shape)} / triangles {tuple(triangles.shape)} "
+                            f"{triangles.dtype} / views {tuple(views.shape)}, expected float32 [V, 3] / contiguous int32 "
+                            f"[T, 3] / float32 [P, {_lib.PXT_MESH_VIEW}]")
+    V, T, P, W, H = int(vertices.shape[0]), int(triangles.shape[0]), int(views.shape[0]), int(width), int(height)
+    if tuple(colors.shape) != (V, 3):
+        raise _lib.PxtError(f"mesh_render: colors is {tuple(colors.shape)}, expected float32 [{V}, 3]")
+    outs = [(rgba, "rgba", torch.float32, (P, H, W, 4)), (rgb_u8, "rgb_u8", torch.uint8, (P, H, W, 3)),
+            (depth, "depth", torch.float32, (P, H, W, 4)), (depth_nz, "depth_nz", torch.uint8, (P, H, W)),
+            (triangle_ids, "triangle_ids", torch.int32, (P, H, W))]
+    for t, name, dtype, shape in outs:
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise _lib.PxtError(f"mesh_render: {name} is a contiguous {dtype} {list(shape)} tensor (got "
+                                f"{tuple(t.shape)}, {t.dtype})")
+    if all(t is None for t, *_ in outs):
+        raise _lib.PxtError("mesh_render: no output was asked for")
+    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
+        raise _lib.PxtError(f"mesh_render: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
+                            f"(got {tuple(records.shape)}, {records.dtype})")
+    need = int(L.pxt_mesh_raster_workspace_bytes(P, T, W, H)) if min(P, T, W, H) >= 1 else -1
+    if need <= 0 or not (1 <= V <= 1 << 24):
+        raise _lib.PxtError(f"mesh_render: {P} views of {W} x {H}, {V} vertices, {T} triangles are not supported "
+                            "(1..4096 views, 1..2^26 pixels, 1..2^24 vertices and triangles)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"mesh_render: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    named = [(vertices, "vertices"), (triangles, "triangles"), (colors, "colors"), (views, "views"), (records, "records"),
+             (workspace, "workspace")] + [(t, name) for t, name, *_ in outs if t is not None]
+    for t, name in named:
+        _lib.require_gpu(t, name)
+        if t.device != vertices.device:
+            raise _lib.PxtError(f"mesh_render: {name} is on {t.device}, the vertices on {vertices.device}")
+    _lib.check(L.pxt_mesh_render(vertices.data_ptr(), V, triangles.data_ptr(), T, colors.data_ptr(), views.data_ptr(), P,
+                                 W, H, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth), _lib.dptr(depth_nz),
+                                 _lib.dptr(triangle_ids), records.data_ptr(), workspace.data_ptr(), _stream(vertices)),
+               "pxt_mesh_render")
+
+
 _IMPLS = {
     "mesh_raster": _mesh_raster,
+    "mesh_render": _mesh_render,
     "ngp_query": _ngp_query,
     "iso_surface_count": _iso_surface_count,
     "iso_surface_emit": _iso_surface_emit,
