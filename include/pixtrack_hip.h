@@ -353,6 +353,28 @@ int64_t pxt_unet_workspace_bytes(const pxt_unet* ctx, int32_t H, int32_t W);
 int pxt_unet_activation_stats(pxt_unet* ctx, int32_t H, int32_t W, const void* workspace, float* stats_device /* [34] */,
                               void* stream);
 
+/* Read-only view of an fp16 pass, for tests that replay it layer by layer from a copy of the workspace (host arithmetic,
+ * nothing is launched; PXT_E_ARG for an fp32 context).  For a pass over n_images images of H x W, out[0..16] describe the
+ * 17 convolutions' outputs and out[17..20] the pooled inputs of encoder blocks 1..4: `offset` bytes into the pass's
+ * workspace, fp16 [n_images][h][w][c]; in_memory == 0 for the two layers pxt_unet_activation_stats reports as -1.  The
+ * fine head is fused only into fine maps of out_cstride[0] >= 36: layer 16's in_memory AND its plan (no split-K under
+ * the fused head) are those of such a pass; a pass with a narrower fine map writes layer 16 and may split it, which
+ * this view does not describe.  For the 3x3 layers 1..16 also the plan the pass takes: tile
+ * configuration, split-K factor, whether the 2x2 max-pool of the output is written by the layer itself (else by a
+ * separate kernel; out[17..20] repeat the flag of the layer they pool), and whether it is a decoder (upsample + concat)
+ * layer.  peers == 1: a pass on its own (pxt_unet_forward, pxt_unet_forward_batch of n_images != 2); peers == 2
+ * (n_images == 1): one image of pxt_unet_forward_pair - the second image's workspace starts at
+ * pxt_unet_workspace_bytes(ctx, H[0], W[0]). */
+typedef struct {
+  int64_t offset;
+  int32_t h, w, c;
+  int32_t in_memory;
+  int32_t cfg, splits, pool_fused, decoder;
+  int32_t deep_ring, reserved; /* deep_ring: the configuration's deeper tap-fragment ring variant (few workgroups) */
+} pxt_unet_layer_view;
+int pxt_unet_layer_views(const pxt_unet* ctx, int32_t n_images, int32_t H, int32_t W, int32_t peers,
+                         pxt_unet_layer_view* out /* [21] */);
+
 /* image: HWC, 3 channels, values 0..255 (float32 if image_is_u8 == 0, else uint8).
  * mask: optional H x W uint8 (0/1) multiplied into the image first
  *       (pixloc_tracker_r9.py:224-225), NULL for none.
@@ -498,6 +520,16 @@ int pxt_conv3x3_pack_weights(const void* weights, int32_t Cin, int32_t Cout, voi
 int pxt_conv3x3_packed(const void* in, int32_t H, int32_t W, int32_t Cin, const void* packed, const float* bias,
                        int32_t Cout, int32_t relu, void* out, void* pool_out, int32_t cfg, int32_t splits,
                        void* splitk_ws, int64_t splitk_ws_bytes, void* stream);
+
+/* A decoder layer of the pyramid as a stand-alone call: the 3x3 convolution of
+ * cat([bilinear x2 upsample (align_corners = false) of prev [Hp][Wp][Cp], skip [Hs][Ws][Cs] cropped to [2Hp][2Wp]])
+ * -> out [2Hp][2Wp][Cout], the concatenation formed in the kernel's staging.  Cp, Cs, Cout multiples of 32, Hs >= 2Hp,
+ * Ws >= 2Wp; packed: the taps of the Cp + Cs input channels (pxt_conv3x3_pack_weights); cfg 0 = automatic, else a tile
+ * configuration that has a decoder variant for this Cout (kTileCfgs upcat_c: 64 for Cout % 64 == 0, else 32);
+ * splits / splitk_ws as for pxt_conv3x3_packed. */
+int pxt_conv3x3_upcat_packed(const void* prev, int32_t Hp, int32_t Wp, int32_t Cp, const void* skip, int32_t Hs, int32_t Ws,
+                             int32_t Cs, const void* packed, const float* bias, int32_t Cout, int32_t relu, void* out,
+                             int32_t cfg, int32_t splits, void* splitk_ws, int64_t splitk_ws_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
  * instant-ngp style NeRF inference renderer.

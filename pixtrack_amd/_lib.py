@@ -101,6 +101,22 @@ class SampleLevel(C.Structure):
     ]
 
 
+class UnetLayerView(C.Structure):
+    _fields_ = [
+        ("offset", C.c_int64),
+        ("h", C.c_int32),
+        ("w", C.c_int32),
+        ("c", C.c_int32),
+        ("in_memory", C.c_int32),
+        ("cfg", C.c_int32),
+        ("splits", C.c_int32),
+        ("pool_fused", C.c_int32),
+        ("decoder", C.c_int32),
+        ("deep_ring", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class UnetSamplePoints(C.Structure):
     _fields_ = [
         ("p3d", C.c_void_p),
@@ -258,6 +274,7 @@ PROTOTYPES = {
     "pxt_unet_set_tile_skip": (C.c_int, [_VP, _I32]),
     "pxt_unet_pair_join": (C.c_int, [_VP, _VP]),
     "pxt_unet_activation_stats": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
+    "pxt_unet_layer_views": (C.c_int, [_VP, _I32, _I32, _I32, _I32, C.POINTER(UnetLayerView)]),
     "pxt_unet_workspace_bytes_batch": (_I64, [_VP, _I32, _I32, _I32]),
     "pxt_unet_forward_batch": (
         C.c_int,
@@ -275,6 +292,8 @@ PROTOTYPES = {
     "pxt_conv3x3_packed_bytes": (_I64, [_I32, _I32]),
     "pxt_conv3x3_pack_weights": (C.c_int, [_VP, _I32, _I32, _VP, _VP]),
     "pxt_conv3x3_packed": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _I64, _VP]),
+    "pxt_conv3x3_upcat_packed": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _I32, _I32,
+                                           _VP, _I64, _VP]),
     "pxt_ngp_create": (C.c_int, [C.POINTER(NgpModel), _VP, _I64, _VP, _I64, _VP, _I64, C.POINTER(_VP)]),
     "pxt_ngp_destroy": (C.c_int, [_VP]),
     "pxt_ngp_render": (C.c_int, [_VP, C.POINTER(NgpView), _VP, _VP, _VP]),

@@ -860,10 +860,13 @@ template <size_t... C>
 constexpr auto tile_launches(std::index_sequence<C...>) { return std::array{&launch_tile<C>...}; }
 constexpr auto kTileLaunches = tile_launches(std::make_index_sequence<kNumCfgs>());
 
+// <= 1 workgroup per CU: nothing hides a miss on the streamed taps but a deeper fragment ring (the configurations that
+// have one: TileCfg::deep; a decoder layer takes its decoder variant instead)
+inline bool wants_deep_ring(const PlanScope& sc, long long workgroups) { return sc.peers * workgroups <= 256; }
+
 int launch_tile_cfg(int cfg, bool upcat, const PlanScope& sc, const ConvArgs& a, dim3 grid, hipStream_t s) {
   if (!cfg_valid(cfg) || (upcat && kTileCfgs[cfg].upcat_c == 0)) return PXT_E_ARG;
-  // <= 1 workgroup per CU: nothing hides a miss on the streamed taps but a deeper fragment ring
-  const bool deep = (long long)sc.peers * grid.x * grid.y * grid.z <= 256;
+  const bool deep = wants_deep_ring(sc, (long long)grid.x * grid.y * grid.z);
   kTileLaunches[cfg](upcat, deep, a, grid, s);
   return PXT_OK;
 }
@@ -907,6 +910,11 @@ ConvPlan resolve_plan(const ConvLaunch& L, const PlanScope& sc) {
                    L.pool_out != nullptr);
 }
 
+// Whether a layer launched with plan cp writes L.pool_out in its epilogue (else maxpool2_kernel runs after it).
+inline bool plan_fuses_pool(const ConvPlan& cp, const ConvLaunch& L) {
+  return L.pool_out != nullptr && cp.splits == 1 && kTileCfgs[cp.cfg].pool;
+}
+
 // Returns (through *pooled) whether the layer wrote L.pool_out.
 int launch_conv(const ConvLaunch& L, const PlanScope& sc, hipStream_t s, bool* pooled = nullptr) {
   const int cin = L.cin, cout = L.cout, H = L.H, W = L.W;
@@ -920,7 +928,7 @@ int launch_conv(const ConvLaunch& L, const PlanScope& sc, hipStream_t s, bool* p
   a.in = L.in; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.relu = L.relu; a.bias = L.bias;
   a.wpk = cfg_taps(cp.cfg, L.wpk, cin, cout); a.out = L.out; a.partial = L.partial;
   a.up = up ? *up : UpSrc{nullptr, 0, 0, 0, 0, 0};
-  a.pool = (cp.splits == 1 && T.pool) ? L.pool_out : nullptr;
+  a.pool = plan_fuses_pool(cp, L) ? L.pool_out : nullptr;
   if (T.KS == 2 && ((cin / 32) / cp.splits) % 2 != 0) return PXT_E_ARG;  // both quartets need equal K shares
   // the partials of this plan must fit the region the caller sized (a forced plan - PXT_CONV_PLAN - may ask for more)
   if (cp.splits > 1 && (size_t)cp.splits * L.n_img * H * W * cout * sizeof(float) > L.partial_cap) return PXT_E_ARG;
@@ -978,6 +986,48 @@ ConvLaunch encoder_layer(const pxt_unet* ctx, const Plan& P, char* ws, int n_img
   L.partial_cap = P.splitk_bytes;
   return L;
 }
+
+// The fine head runs in the last decoder layer's epilogue (pxt_conv_v2.h FusedHead) when the context holds it in that form
+// and the fine map's records have room for it; the layer's own output is then never written.
+inline bool has_fused_head(const pxt_unet* ctx) { return ctx->dev_head0 != nullptr; }
+
+// Decoder layer d (0..3, conv layer 13 + d) of a pass over n_img images, its input and output buffers and the head aside: `up` forms
+// its input (to a plan only "a decoder layer" matters); with the fine head fused into it (`fused_head`, d == 3 only) it
+// takes no split-K.  The decoder launches it, the reference-tile set-up and pxt_unet_layer_views plan it.
+ConvLaunch decoder_layer(const pxt_unet* ctx, const Plan& P, char* ws, int n_img, int d, const UpSrc* up, bool fused_head) {
+  ConvLaunch L = pyramid_layer(ctx, 13 + d, P.dh[d], P.dw[d], n_img);
+  L.up = up;
+  L.partial = (d == 3 && fused_head) ? nullptr : (float*)(ws + P.splitk);
+  L.partial_cap = P.splitk_bytes;
+  return L;
+}
+
+// Where conv layer li's output sits in the workspace of a pass laid out by P, and whether it is written at all: not the
+// first layer when it is computed inside the second one's staging, nor the last one when the fine head is fused into it.
+struct LayerOut {
+  size_t offset;
+  int h, w, c;
+  bool in_memory;
+};
+LayerOut layer_output(const pxt_unet* ctx, const Plan& P, int li) {
+  LayerOut o;
+  o.c = ctx->conv[li].cout;
+  if (li < kNumEncLayers) {
+    const int b = enc_block(li);
+    o.offset = enc_out_offset(P, li); o.h = P.h[b]; o.w = P.w[b];
+    o.in_memory = !(li == 0 && fuses_first(ctx));
+  } else {
+    const int d = li - kNumEncLayers;
+    o.offset = P.dec_out[d]; o.h = P.dh[d]; o.w = P.dw[d];
+    o.in_memory = !(d == 3 && has_fused_head(ctx));
+  }
+  return o;
+}
+
+// What the forward entries plan their passes for: a batch as launched on its own (pxt_unet_set_batch_plan: a batch of
+// more than two as single images of the pair pass), and one image of the pair pass (two passes side by side).
+inline PlanScope batch_scope(const pxt_unet* ctx, int n_images) { return PlanScope{1, ctx->plan_as_single && n_images > 2, 0}; }
+inline PlanScope pair_scope() { return PlanScope{2, false, 0}; }
 
 // ---- constant-tile skipping: the layers' output vectors for the constant input -------------------------------
 // For a plan signature (the tile configuration of conv layers 1..6) the chain c1 = conv1_2(conv1_1(0-pixel)), c2 =
@@ -1386,15 +1436,7 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
   const half_t* prev = skip[4];
   bool head0_fused = false;
   int ph = P.h[4], pw = P.w[4], pc = ctx->conv[12].cout;
-  const bool fuse_head3 = ctx->dev_head0 != nullptr && out_cstride[0] >= 36;
-  // decoder layer d as launched below, buffers and fusions aside (the reference-tile set-up plans layers 2 and 3 with it)
-  auto decoder_layer = [&](int d, const UpSrc* up) {
-    ConvLaunch cl = pyramid_layer(ctx, 13 + d, P.dh[d], P.dw[d], B);
-    cl.up = up;
-    cl.partial = (d == 3 && fuse_head3) ? nullptr : (float*)(ws + P.splitk);
-    cl.partial_cap = P.splitk_bytes;
-    return cl;
-  };
+  const bool fuse_head3 = has_fused_head(ctx) && out_cstride[0] >= 36;
   // ---- reference tiles (see reference_tiles_kernel): PXT_UNET_REF_TILES=0 computes every tile ---------------------
   // Only for a single-image pass that was handed the points its maps will be sampled at, and only with the fused fine
   // head (a separate head launch would read the whole last layer).  The flags are made for the tile configurations the
@@ -1411,7 +1453,7 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
     RefTileGeo geo[2];
     bool ok = true;
     for (int k = 0; k < 2; ++k) {
-      const ConvPlan cp = resolve_plan(decoder_layer(2 + k, &planned), sc.at(15 + k));
+      const ConvPlan cp = resolve_plan(decoder_layer(ctx, P, ws, B, 2 + k, &planned, fuse_head3), sc.at(15 + k));
       ok = ok && cfg_valid(cp.cfg);
       if (!ok) break;
       ref_cfg[k] = cp.cfg;
@@ -1456,7 +1498,7 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
       fh.enabled = 1;
       head0_fused = true;
     }
-    ConvLaunch cl = decoder_layer(d, &up);
+    ConvLaunch cl = decoder_layer(ctx, P, ws, B, d, &up, fuse_head3);
     cl.in = skip[sb]; cl.out = o; cl.head = fuse_head ? &fh : nullptr;
     if (d >= 2) { cl.needed = ref_needed[d - 2]; cl.needed_cfg = ref_cfg[d - 2]; }
     const int rc = launch_conv(cl, sc.at(13 + d), s);
@@ -1505,7 +1547,7 @@ extern "C" int pxt_unet_forward_batch(pxt_unet* ctx, int32_t n_images, const voi
   if (ctx->join_pending) { PXT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_join, 0)); ctx->join_pending = false; }
   if (n_images != 2 || knobs().streams < 2)
     return forward_pass(ctx, n_images, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace,
-                        stream, ctx->sides[0], PlanScope{1, ctx->plan_as_single && n_images > 2, 0});
+                        stream, ctx->sides[0], batch_scope(ctx, n_images));
   const int32_t Hs[2] = {H, H}, Ws[2] = {W, W};
   return pxt_unet_forward_pair(ctx, images, image_is_u8, masks, Hs, Ws, out_maps, out_cstride, normalize, workspace, stream);
 }
@@ -1553,7 +1595,7 @@ extern "C" int pxt_unet_forward_pair_sampled(pxt_unet* ctx, const void* const* i
   for (int im = 0; im < 2; ++im) {
     int rc = forward_pass(ctx, 1, images + im, image_is_u8 + im, masks ? masks + im : no_mask, H[im], W[im], out_maps + 3 * im,
                           out_cstride, normalize + im, (char*)workspace + (im ? second : 0),
-                          im == 0 ? (void*)s : (void*)ctx->pass2, ctx->sides[im], PlanScope{2, false, 0},
+                          im == 0 ? (void*)s : (void*)ctx->pass2, ctx->sides[im], pair_scope(),
                           points_host ? points_host[im] : nullptr);
     if (rc != PXT_OK) return rc;
   }
@@ -1649,7 +1691,7 @@ extern "C" int pxt_unet_forward_sampled(pxt_unet* ctx, const void* image, int32_
                                   stream);
   if (ctx->join_pending) { PXT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_join, 0)); ctx->join_pending = false; }
   return forward_pass(ctx, 1, images, &image_is_u8, masks, H, W, out_maps, out_cstride, &normalize, workspace, stream,
-                      ctx->sides[0], PlanScope{1, false, 0}, points_host);
+                      ctx->sides[0], batch_scope(ctx, 1), points_host);
 }
 
 extern "C" int pxt_unet_forward(pxt_unet* ctx, const void* image, int32_t image_is_u8,
@@ -1673,19 +1715,9 @@ extern "C" int pxt_unet_activation_stats(pxt_unet* ctx, int32_t H, int32_t W, co
   PXT_HIP_CHECK(hipMemsetAsync(stats, 0, kNumConv * 2 * sizeof(float), s));
   const char* ws = (const char*)workspace;
   for (int li = 0; li < kNumConv; ++li) {
-    const half_t* x = nullptr;
-    long long n = 0;
-    if (li < kNumEncLayers) {
-      const int b = enc_block(li);
-      x = (const half_t*)(ws + enc_out_offset(P, li));
-      n = (long long)P.h[b] * P.w[b] * ctx->conv[li].cout;
-      if (li == 0 && fuses_first(ctx)) x = nullptr;  // never materialised
-    } else {
-      const int d = li - 13;
-      x = (const half_t*)(ws + P.dec_out[d]);
-      n = (long long)P.dh[d] * P.dw[d] * ctx->conv[li].cout;
-      if (d == 3 && ctx->dev_head0 != nullptr) x = nullptr;  // consumed by the fused fine head in registers
-    }
+    const LayerOut lo = layer_output(ctx, P, li);
+    const half_t* x = lo.in_memory ? (const half_t*)(ws + lo.offset) : nullptr;
+    const long long n = (long long)lo.h * lo.w * lo.c;
     if (!x) {  // not in memory in this configuration: reported as -1 (0xBF800000: byte-wise memsets, no host source buffer
                // whose lifetime an asynchronous copy would depend on)
       PXT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(stats + 2 * li), 0xBF800000u, 1, s));
@@ -1694,6 +1726,42 @@ extern "C" int pxt_unet_activation_stats(pxt_unet* ctx, int32_t H, int32_t W, co
     hipLaunchKernelGGL(activation_stats_kernel, dim3(512), dim3(256), 0, s, x, n / 8, stats + 2 * li);
   }
   PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}
+
+// Where a pass leaves every layer and how it plans it (host arithmetic only, nothing is launched): the pass's own
+// make_plan / layer_output / encoder_layer / decoder_layer / resolve_plan / plan_fuses_pool, so that a test replaying the
+// layers from a copy of the workspace reads what the kernels wrote and knows which kernel wrote it.  Layer 16 is described
+// with the fine head fused wherever the context can fuse it (forward_pass also asks for out_cstride[0] >= 36: the header says so).
+extern "C" int pxt_unet_layer_views(const pxt_unet* ctx, int32_t n_images, int32_t H, int32_t W, int32_t peers,
+                                    pxt_unet_layer_view* out) {
+  if (!ctx || !out || ctx->f32) return PXT_E_ARG;
+  if (peers != 1 && !(peers == 2 && n_images == 1)) return PXT_E_ARG;
+  Plan P;
+  if (!make_plan(ctx, n_images, H, W, P)) return PXT_E_ARG;
+  const PlanScope sc = peers == 2 ? pair_scope() : batch_scope(ctx, n_images);
+  // (to a plan only the presence of a buffer or a fusion matters: nothing below is dereferenced)
+  char* const ws = reinterpret_cast<char*>((uintptr_t)256);
+  const FusedFirst ff = {};
+  const UpSrc up{nullptr, 1, 1, 32, 1, 1};
+  std::memset(out, 0, (kNumConv + 4) * sizeof(pxt_unet_layer_view));
+  for (int li = 0; li < kNumConv; ++li) {
+    const LayerOut lo = layer_output(ctx, P, li);
+    pxt_unet_layer_view& v = out[li];
+    v.offset = (int64_t)lo.offset; v.h = lo.h; v.w = lo.w; v.c = lo.c; v.in_memory = lo.in_memory ? 1 : 0;
+    if (li == 0) continue;  // (conv_first_kernel, or the second layer's staging: no tile plan)
+    const ConvLaunch L = li < kNumEncLayers
+                             ? encoder_layer(ctx, P, ws, n_images, li, fuses_first(ctx) ? &ff : nullptr)
+                             : decoder_layer(ctx, P, ws, n_images, li - kNumEncLayers, &up, has_fused_head(ctx));
+    const ConvPlan cp = resolve_plan(L, sc.at(li));
+    v.cfg = cp.cfg; v.splits = cp.splits; v.pool_fused = plan_fuses_pool(cp, L) ? 1 : 0; v.decoder = L.up != nullptr ? 1 : 0;
+    v.deep_ring = (kTileCfgs[cp.cfg].deep && !L.up && wants_deep_ring(sc, (long long)cp.tiles * cp.nb * cp.splits)) ? 1 : 0;
+  }
+  for (int b = 1; b < 5; ++b) {  // the pooled input of block b: written by the layer before it, or by maxpool2_kernel
+    pxt_unet_layer_view& v = out[kNumConv + b - 1];
+    v.offset = (int64_t)P.enc_pool[b]; v.h = P.h[b]; v.w = P.w[b]; v.c = kEnc[b].cin; v.in_memory = 1;
+    v.pool_fused = out[kEnc[b].first - 1].pool_fused;
+  }
   return PXT_OK;
 }
 
@@ -1725,6 +1793,29 @@ extern "C" int pxt_conv3x3_packed(const void* in, int32_t H, int32_t W, int32_t 
   L.in = (const half_t*)in; L.out = (half_t*)out; L.H = H; L.W = W; L.cin = Cin; L.cout = Cout; L.relu = relu;
   L.wpk = (const half_t*)packed; L.bias = bias; L.pool_out = (half_t*)pool_out;
   L.partial = splits > 1 ? (float*)splitk_ws : nullptr; L.force_cfg = cfg; L.force_splits = splits > 1 ? splits : 0;
+  int rc = launch_conv(L, PlanScope{}, (hipStream_t)stream);
+  if (rc != PXT_OK) return rc;
+  PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}
+
+// A decoder layer on its own: pxt_conv3x3_packed with ConvLaunch::up set (launch_conv checks the geometry).
+extern "C" int pxt_conv3x3_upcat_packed(const void* prev, int32_t Hp, int32_t Wp, int32_t Cp, const void* skip, int32_t Hs,
+                                        int32_t Ws, int32_t Cs, const void* packed, const float* bias, int32_t Cout,
+                                        int32_t relu, void* out, int32_t cfg, int32_t splits, void* splitk_ws,
+                                        int64_t splitk_ws_bytes, void* stream) {
+  if (!prev || !skip || !packed || !bias || !out || Hp < 1 || Wp < 1 || Cp < 32 || Cs < 32 || Cout < 32) return PXT_E_ARG;
+  const int H = 2 * Hp, W = 2 * Wp;
+  if (splits > 1 && (!splitk_ws || splitk_ws_bytes < (int64_t)splits * H * W * Cout * (int64_t)sizeof(float)))
+    return PXT_E_ARG;
+  // (resolve_plan would quietly replace a configuration without a matching decoder variant: a stand-alone call refuses it)
+  if (cfg != 0 && (!cfg_valid(cfg) || Cout % 32 != 0 || kTileCfgs[cfg].upcat_c != (Cout % 64 == 0 ? 64 : 32))) return PXT_E_ARG;
+  const UpSrc up{(const half_t*)prev, Hp, Wp, Cp, Hs, Ws};
+  ConvLaunch L;
+  L.in = (const half_t*)skip; L.out = (half_t*)out; L.H = H; L.W = W; L.cin = Cp + Cs; L.cout = Cout; L.relu = relu;
+  L.wpk = (const half_t*)packed; L.bias = bias; L.up = &up;
+  L.partial = splits > 1 ? (float*)splitk_ws : nullptr; L.force_cfg = cfg; L.force_splits = splits > 1 ? splits : 0;
+  if (splits > 1) L.partial_cap = (size_t)splitk_ws_bytes;
   int rc = launch_conv(L, PlanScope{}, (hipStream_t)stream);
   if (rc != PXT_OK) return rc;
   PXT_HIP_CHECK(hipGetLastError());

@@ -446,6 +446,18 @@ class UNet:
         counts = h.view(torch.int32)
         return [None if float(h[2 * l]) < 0 else (float(h[2 * l]), int(counts[2 * l + 1])) for l in range(17)]
 
+    def layer_views(self, n_images: int, H: int, W: int, peers: int = 1) -> List[Dict[str, int]]:
+        """Where a pass over ``n_images`` images of H x W leaves its layers in the workspace and how it plans them
+        (pxt_unet_layer_views; fp16 only, nothing is launched): 21 dicts - the 17 convolutions, then the pooled inputs of
+        encoder blocks 1..4 - with ``offset`` (bytes), ``h``, ``w``, ``c`` (fp16 [n_images][h][w][c]), ``in_memory`` and,
+        for the 3x3 layers, ``cfg``, ``splits``, ``pool_fused``, ``decoder`` and ``deep_ring`` (the configuration's
+        deeper tap-fragment ring variant: another kernel instance); ``reserved`` is padding, always 0.  ``peers=2``: one
+        image of a two-image call; the second image's workspace starts ``pxt_unet_workspace_bytes`` of the first one's
+        size further on.  Layer 16 is described for fine maps of cstride >= 36 (what forward_packed allocates)."""
+        views = (_lib.UnetLayerView * 21)()
+        _lib.check(_lib.lib().pxt_unet_layer_views(self._ctx, n_images, H, W, peers, views), "pxt_unet_layer_views")
+        return [{name: int(getattr(v, name)) for name, _ in _lib.UnetLayerView._fields_} for v in views]
+
     def __call__(self, data: Dict[str, torch.Tensor]) -> Dict[str, List[torch.Tensor]]:
         image = data["image"]  # 1 x 3 x H x W in [0, 1]
         assert image.dim() == 4 and image.shape[0] == 1 and image.shape[1] == 3

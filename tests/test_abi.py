@@ -49,8 +49,8 @@ def test_struct_layouts_match_header_sizes():
         #include <stdio.h>
         #include "pixtrack_hip.h"
         int main(void) {
-          printf("%zu %zu %zu %zu %zu\\n", sizeof(pxt_lm_level), sizeof(pxt_lm_conf),
-                 sizeof(pxt_sample_level), sizeof(pxt_ngp_model), sizeof(pxt_ngp_view));
+          printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(pxt_lm_level), sizeof(pxt_lm_conf),
+                 sizeof(pxt_sample_level), sizeof(pxt_ngp_model), sizeof(pxt_ngp_view), sizeof(pxt_unet_layer_view));
           return 0;
         }
         """
@@ -60,7 +60,8 @@ def test_struct_layouts_match_header_sizes():
         subprocess.check_call(["gcc", "-I", str(ROOT / "include"), str(Path(d) / "s.c"), "-o", str(Path(d) / "s")])
         out = subprocess.check_output([str(Path(d) / "s")]).decode().split()
     sizes = [int(x) for x in out]
-    got = [ctypes.sizeof(c) for c in (_lib.LmLevel, _lib.LmConf, _lib.SampleLevel, _lib.NgpModel, _lib.NgpView)]
+    got = [ctypes.sizeof(c) for c in (_lib.LmLevel, _lib.LmConf, _lib.SampleLevel, _lib.NgpModel, _lib.NgpView,
+                                      _lib.UnetLayerView)]
     assert got == sizes
 
 
