@@ -41,6 +41,7 @@ extern "C" {
 #define PXT_E_HIP -2     /* a HIP runtime call failed (pxt_last_error() has text) */
 #define PXT_E_TIMEOUT -3 /* in-kernel spin bound exceeded (reported via status words) */
 #define PXT_E_STATE -4   /* context misuse */
+#define PXT_E_GUARD -5   /* pxt_lm_refine read a map tile its level's tile_flags call uncomputed (status word only) */
 
 #define PXT_MAX_LEVELS 8
 #define PXT_LM_LOG_STRIDE 20 /* floats per logged iteration, see pxt_lm_refine */
@@ -94,7 +95,7 @@ typedef struct {
 
 /* Output record (device, floats):
  *   out[0..11]  T_refined (12)        out[12] failed (0/1)
- *   out[13]     status (0 ok, PXT_E_TIMEOUT as float if a spin bound tripped)
+ *   out[13]     status (0 ok, PXT_E_TIMEOUT as float if a spin bound tripped, PXT_E_GUARD if a level's tile guard did)
  *   out[14]     total iterations      out[15] 1.0, stored last with system-scope release
  *               (a host polling `out` in pinned memory may read the record once it sees it)
  *   out[16 + l] iterations run at level l (execution order), l < n_levels
@@ -102,6 +103,7 @@ typedef struct {
  *   k=0 masked-mean cost BEFORE the update of iteration i (tracker.py:40-41)
  *   k=1 number of valid points   k=2 dR (deg) of the step   k=3 dt of the step
  *   k=4 ||g||                    k=5 1 if the solve fell back from Cholesky to LU
+ *   k=6 points that read an uncomputed tile (0 without tile_flags)
  *   k=8..19 pose after the update (12)
  */
 int pxt_lm_refine(const float* p3d, const uint8_t* point_mask /* may be NULL */,
@@ -125,6 +127,25 @@ typedef struct {
 int pxt_lm_refine_cam(const float* p3d, const uint8_t* point_mask, int32_t n_points, const pxt_lm_level* levels_host,
                       int32_t n_levels, const float* T_init_host, const pxt_lm_conf* conf_host, float* out, float* log,
                       void* workspace, const pxt_lm_camera* cam_host, void* stream);
+
+/* pxt_lm_refine_cam with a tile guard on ONE level (guard_host == NULL: pxt_lm_refine_cam; cam_host may be NULL too).
+ * That level's fmap was written in tiles of tile_rows x 16 texels, tiles_per_row of them per row of tiles, texel (0, 0)
+ * of fmap being texel (tile_x0, tile_y0) of the tile grid, and only the tiles whose byte in tile_flags (device,
+ * row-major) is 1 hold data - the query map of pxt_unet_forward_pair_tiles.  A valid point (an invalid one loads
+ * nothing) whose 4 x 4 footprint box - columns ix0-1..ix0+2, rows iy0-1..iy0+2, clamped into the map as the loads are -
+ * meets a tile with flag 0 is counted in the iteration's log word 6.  A non-zero count ends the launch at that
+ * iteration, through the path a failed level takes: out[12] = 1, out[13] = PXT_E_GUARD, out[0..11] the pose that
+ * iteration started from, the camera slots left alone and the camera record marked -1.  The count travels with the
+ * iteration's other sums (accumulator slot 29): no atomics, barriers or exchanges of its own.  The batched launch and
+ * every other reader of pxt_lm_level take no guard. */
+typedef struct {
+  int32_t level;              /* index into levels_host (execution order) */
+  const uint8_t* tile_flags;  /* device */
+  int32_t tile_rows, tiles_per_row, tile_x0, tile_y0;
+} pxt_lm_tile_guard;
+int pxt_lm_refine_guarded(const float* p3d, const uint8_t* point_mask, int32_t n_points, const pxt_lm_level* levels_host,
+                          int32_t n_levels, const float* T_init_host, const pxt_lm_conf* conf_host, float* out, float* log,
+                          void* workspace, const pxt_lm_camera* cam_host, const pxt_lm_tile_guard* guard_host, void* stream);
 
 /* K independent refinements in ONE persistent launch - K objects tracked in lock-step on one GPU (BASELINE configs[3]:
  * the eight objects of /root/reference/config/<object>.sh, one tracker per object as
@@ -448,6 +469,17 @@ typedef struct {
   int32_t ndist, pad;
   int32_t x0, y0, full_w, full_h;
 } pxt_unet_sample_points;
+/* Query tiles: the record of a QUERY whose fine map will be read by nothing but the fine level of the pxt_lm_refine*
+ * launch that starts from pose points.T (camera: the query's fine-level camera; pad: the LM's) and moves the points.
+ * Every point in front of the camera, valid at that pose or not, takes the bounding box of the texels the LM's point
+ * evaluation loads around floor(u, v) - columns ix0-1..ix0+2, rows iy0-1..iy0+2, clamped into the map as the kernel
+ * clamps - grown by `margin` texels on every side and clipped to the map; every tile of the last layer the box meets
+ * is computed, the layer before follows as for reference tiles, and the flags stay in the pass's workspace for the
+ * LM's tile guard (pxt_unet_query_tiles, pxt_lm_refine_guarded), which sees a refinement that outruns the margin. */
+typedef struct {
+  pxt_unet_sample_points points;
+  int32_t margin;
+} pxt_unet_query_points;
 int pxt_unet_forward_sampled(pxt_unet* ctx, const void* image, int32_t image_is_u8, const uint8_t* mask, int32_t H,
                              int32_t W, float* const out_maps[3], const int32_t out_cstride[3], int32_t normalize,
                              void* workspace, void* stream, const pxt_unet_sample_points* points_host);
@@ -457,6 +489,33 @@ int pxt_unet_forward_pair_sampled(pxt_unet* ctx, const void* const* images, cons
                                   void* workspace, void* stream,
                                   const pxt_unet_sample_points* const* points_host /* [2], entries may be NULL */);
 int pxt_unet_set_reference_tiles(pxt_unet* ctx, int32_t on);
+/* pxt_unet_forward_pair_sampled whose SECOND image is a query with its own record (reference_points_host: the first
+ * image's reference record or NULL; query_points_host NULL: the plain pair).  Gated like reference tiles: single-image
+ * passes side by side, fused fine head, one K pass, the tile configuration the flags were made for.  Both passes launch
+ * their flag kernel on their side stream at the head of the pass; decoder layer 2 waits for it. */
+int pxt_unet_forward_pair_tiles(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
+                                const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
+                                float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
+                                void* workspace, void* stream, const pxt_unet_sample_points* reference_points_host,
+                                const pxt_unet_query_points* query_points_host);
+/* Query tiles on / off for this context; $PXT_UNET_QUERY_TILES=0 turns them off for the process.  Off: the query's
+ * record is ignored and every tile is computed. */
+int pxt_unet_set_query_tiles(pxt_unet* ctx, int32_t on);
+/* Where the pair pass over H[i] x W[i] images keeps the flags of image 1's last decoder layer, and that layer's tile
+ * geometry: out[0] byte offset into the pair workspace, out[1] tile rows, out[2] tiles per row, out[3] rows of tiles,
+ * out[4] 1 if the LAST forward call on this context was a pair call whose query pass used its record and wrote the
+ * flags (0: that call computed every tile and wrote no flags - hand the LM no guard).  Ask after the pair call and
+ * before any other forward call: the answer is the pass's own, whatever knob, stride, size or batching decided it.
+ * Host only; nothing is launched. */
+int pxt_unet_query_tiles(const pxt_unet* ctx, const int32_t H[2], const int32_t W[2], int64_t out[5]);
+/* Image 1 of a pair call over H[i] x W[i] images again, alone and IN FULL (no record), on `stream`: into out_maps[3], in
+ * image 1's part of the same pair `workspace`, and planned as one image of the pair - so the maps are bit for bit those
+ * image 1 has in a pair call without a query record (a lone pxt_unet_forward plans its layers for an empty chip:
+ * other tile configurations and split-K partitions, other bits).  What a caller runs after the LM's tile guard tripped.
+ * fp16 contexts only. */
+int pxt_unet_forward_pair_second(pxt_unet* ctx, const void* image, int32_t image_is_u8, const uint8_t* mask,
+                                 const int32_t H[2], const int32_t W[2], float* const out_maps[3],
+                                 const int32_t out_cstride[3], int32_t normalize, void* workspace, void* stream);
 /* The flag rule alone, on the HOST (every pointer, `p3d` too, is host memory; no device is touched): for a fine_h x
  * fine_w fine map (even sizes) cut into fine_tile_rows x 16 tiles and the (fine_h / 2) x (fine_w / 2) layer before it cut
  * into low_tile_rows x 16 tiles, writes 1 for every tile a sampled pass computes and 0 for the others, row-major.  The
@@ -464,6 +523,10 @@ int pxt_unet_set_reference_tiles(pxt_unet* ctx, int32_t on);
 int pxt_unet_reference_tiles_host(const pxt_unet_sample_points* points_host, int32_t fine_h, int32_t fine_w,
                                   int32_t fine_tile_rows, int32_t low_tile_rows, uint8_t* fine_flags_host,
                                   uint8_t* low_flags_host);
+/* The same for a query's record (margin >= 0). */
+int pxt_unet_query_tiles_host(const pxt_unet_query_points* query_points_host, int32_t fine_h, int32_t fine_w,
+                              int32_t fine_tile_rows, int32_t low_tile_rows, uint8_t* fine_flags_host,
+                              uint8_t* low_flags_host);
 
 /* Deferred join of the pair entry (round 4): with pxt_unet_set_defer_join(ctx, 1), pxt_unet_forward_pair (and the
  * two-image pxt_unet_forward_batch that runs through it) returns with image 0's maps complete in the caller's stream

@@ -20,6 +20,7 @@ LIB_PATH = Path(os.environ["PIXTRACK_HIP_LIB"]) if os.environ.get("PIXTRACK_HIP_
 PXT_MAX_LEVELS = 8
 PXT_LM_LOG_STRIDE = 20
 PXT_E_TIMEOUT = -3
+PXT_E_GUARD = -5
 ABI_VERSION = 13
 PXT_LM_MAX_BATCH = 16
 PXT_UNET_MAX_BATCH = 16
@@ -65,6 +66,11 @@ class LmLevel(C.Structure):
         ("ndist", C.c_int32),
         ("lambda_", C.c_float * 6),
     ]
+
+
+class LmTileGuard(C.Structure):
+    _fields_ = [("level", C.c_int32), ("tile_flags", C.c_void_p), ("tile_rows", C.c_int32), ("tiles_per_row", C.c_int32),
+                ("tile_x0", C.c_int32), ("tile_y0", C.c_int32)]
 
 
 class LmConf(C.Structure):
@@ -130,6 +136,10 @@ class UnetSamplePoints(C.Structure):
         ("full_w", C.c_int32),
         ("full_h", C.c_int32),
     ]
+
+
+class UnetQueryPoints(C.Structure):
+    _fields_ = [("points", UnetSamplePoints), ("margin", C.c_int32)]
 
 
 class NgpModel(C.Structure):
@@ -239,6 +249,11 @@ PROTOTYPES = {
         C.c_int,
         [_VP, _VP, _I32, C.POINTER(LmLevel), _I32, _VP, C.POINTER(LmConf), _VP, _VP, _VP, C.POINTER(LmCamera), _VP],
     ),
+    "pxt_lm_refine_guarded": (
+        C.c_int,
+        [_VP, _VP, _I32, C.POINTER(LmLevel), _I32, _VP, C.POINTER(LmConf), _VP, _VP, _VP, C.POINTER(LmCamera),
+         C.POINTER(LmTileGuard), _VP],
+    ),
     "pxt_lm_workspace_bytes": (_I64, []),
     "pxt_lm_batch_workspace_bytes": (_I64, [_I32]),
     "pxt_lm_refine_batch": (C.c_int, [C.POINTER(LmProblem), _I32, C.POINTER(LmConf), _VP, _VP]),
@@ -269,6 +284,18 @@ PROTOTYPES = {
     ),
     "pxt_unet_set_reference_tiles": (C.c_int, [_VP, _I32]),
     "pxt_unet_reference_tiles_host": (C.c_int, [C.POINTER(UnetSamplePoints), _I32, _I32, _I32, _I32, _VP, _VP]),
+    "pxt_unet_set_query_tiles": (C.c_int, [_VP, _I32]),
+    "pxt_unet_query_tiles": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64)]),
+    "pxt_unet_query_tiles_host": (C.c_int, [C.POINTER(UnetQueryPoints), _I32, _I32, _I32, _I32, _VP, _VP]),
+    "pxt_unet_forward_pair_tiles": (
+        C.c_int,
+        [_VP, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_VP),
+         C.POINTER(_I32), C.POINTER(_I32), _VP, _VP, C.POINTER(UnetSamplePoints), C.POINTER(UnetQueryPoints)],
+    ),
+    "pxt_unet_forward_pair_second": (
+        C.c_int,
+        [_VP, _VP, _I32, _VP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_VP), C.POINTER(_I32), _I32, _VP, _VP],
+    ),
     "pxt_unet_set_defer_join": (C.c_int, [_VP, _I32]),
     "pxt_unet_set_batch_plan": (C.c_int, [_VP, _I32]),
     "pxt_unet_set_tile_skip": (C.c_int, [_VP, _I32]),

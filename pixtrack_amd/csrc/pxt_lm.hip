@@ -37,7 +37,9 @@ namespace pxt {
 constexpr int kLmBlock = 512;
 constexpr int kLmWaves = kLmBlock / PXT_WAVE;
 constexpr int kLmMaxGrid = 256;
-constexpr int kNAcc = 32;  // 6 g + 21 H + cost sum + n_valid + pad
+constexpr int kNAcc = 32;  // 6 g + 21 H + cost sum + n_valid + guard count + pad
+constexpr int kNUsed = 30;  // slots that carry a value (the fold and the park stop here)
+constexpr int kGuardSlot = 29;  // points whose footprint touched a tile the level's flags call uncomputed
 constexpr int kGrpStride = 33;  // padded: leaders of one wave hit distinct banks
 constexpr unsigned kSpinLimit = 1u << 22;  // polls of ~1.5 us before a spin gives up (pxt_lm_conf.spin_limit overrides)
 
@@ -48,7 +50,27 @@ struct LmLevelDev {
   float cam[10];
   int ndist;
   float lambda[6];
+  // Tile guard (pxt_lm_tile_guard): null = no check.  The map was written tile by tile (tile_rows x 16 texels,
+  // tiles_x per row, the map's texel (0, 0) being texel (tile_x0, tile_y0) of the tile grid) and only where flags[] is 1.
+  const uint8_t* flags;
+  int tile_rows, tiles_x, tile_x0, tile_y0;
 };
+
+// 1.f when any texel of the footprint's bounding box - columns xi[0]..xi[3], rows yi[0]..yi[3], already clamped into the
+// map as the loads clamp them - lies in a tile whose flag is 0.  The same addresses in every lane of a point's group; the
+// byte loads are issued beside the footprint's own and cost no round trip of their own.
+__device__ inline float lm_tile_guard(const LmLevelDev& L, const int* xi, const int* yi) {
+  if (!L.flags) return 0.f;
+  const int c0 = (xi[0] + L.tile_x0) >> 4, c1 = (xi[3] + L.tile_x0) >> 4;
+  const int r0 = (yi[0] + L.tile_y0) / L.tile_rows, r1 = (yi[3] + L.tile_y0) / L.tile_rows;
+  unsigned all = 1u;
+#pragma unroll 1
+  for (int r = r0; r <= r1; ++r) {
+    const uint8_t* f = L.flags + (size_t)r * L.tiles_x;
+    all &= (unsigned)f[c0] & (unsigned)f[c1];  // (a 4-texel span meets at most two 16-texel columns of tiles)
+  }
+  return all ? 0.f : 1.f;
+}
 
 // Which workgroups work on a problem: G of them, this one being number b.  The single-problem kernel's grid IS the
 // problem's (G = gridDim.x, b = blockIdx.x); the batched kernel deals its grid to the problems (pxt_lm_refine_batch).
@@ -77,29 +99,32 @@ struct LmParams {
 // One point's contribution to g (acc[0..5]), the upper triangle of H (acc[6..26]), the cost sum and the valid count,
 // from its six group-reduced scalars and its robust weight (pxt_lm_point.h).
 __device__ inline void lm_add_point(float* acc, float wgt, float rcost, const float* Jw, float px, float py, float pz,
-                                    float A0, float A1, float B00, float B01, float B11) {
+                                    float A0, float A1, float B00, float B01, float B11, float guard) {
   float J0[6], J1[6];
   point_jacobian(Jw, px, py, pz, J0, J1);
   point_normal_terms<true>(acc, wgt, J0, J1, A0, A1, B00, B01, B11);
   acc[27] += rcost;
   acc[28] += 1.f;
+  acc[kGuardSlot] += guard;
 }
 
-// The same for a group that serves ONE point per iteration: the 29 values go straight to the group's LDS record
+// The same for a group that serves ONE point per iteration: the 30 values go straight to the group's LDS record
 // (no accumulator array: passed through the variant switch it would live in scratch).
 __device__ inline void lm_point_record(float* dst, bool leader, float wgt, float rcost, const float* Jw, float px, float py,
-                                       float pz, float A0, float A1, float B00, float B01, float B11) {
+                                       float pz, float A0, float A1, float B00, float B01, float B11, float guard) {
   float J0[6], J1[6];
   point_jacobian(Jw, px, py, pz, J0, J1);
   if (!leader) return;
   point_normal_terms<false>(dst, wgt, J0, J1, A0, A1, B00, B01, B11);
   dst[27] = rcost;
   dst[28] = 1.f;
+  dst[kGuardSlot] = guard;
 }
 
 // Accumulates this workgroup's share of one LM iteration at one level.
 // acc[0..5] = g, acc[6..26] = upper-triangular H (row-major), acc[27] = sum of
-// valid robust costs, acc[28] = number of valid points.
+// valid robust costs, acc[28] = number of valid points, acc[29] = how many of them read an unflagged tile (an invalid
+// point loads nothing - the `continue` below - so it cannot reach a sum and is not counted).
 // LG (lanes per point) is 8 or 32, wave-uniform at run time.
 __device__ inline void lm_accumulate(const LmParams& P, const LmGrid grid, const LmLevelDev& L, const float* T,
                                      float* acc, const int LG, unsigned long long* dbg = nullptr) {
@@ -150,6 +175,7 @@ __device__ inline void lm_accumulate(const LmParams& P, const LmGrid grid, const
       xi[k] = min(max(xx, 0), W - 1);
       yi[k] = min(max(yy, 0), H - 1);
     }
+    const float guard = lm_tile_guard(L, xi, yi);
     const float* row[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) row[k] = L.fmap + (size_t)yi[k] * W * cs;
@@ -206,7 +232,7 @@ __device__ inline void lm_accumulate(const LmParams& P, const LmGrid grid, const
     robust_loss(P.conf.loss, P.conf.loss_alpha, P.conf.loss_scale, s_cost, rcost, wl);
     const float wgt = wl * (wref * wq);
 
-    lm_add_point(acc, wgt, rcost, Jw, px, py, pz, A0, A1, B00, B01, B11);
+    lm_add_point(acc, wgt, rcost, Jw, px, py, pz, A0, A1, B00, B01, B11, guard);
 #if PXT_EXP_STAMPS
     if (dbg && dbg_round == 0) dbg[10] = __builtin_amdgcn_s_memtime();
     ++dbg_round;
@@ -293,6 +319,7 @@ __device__ inline void lm_accumulate_cached(const LmParams& P, const LmLevelDev&
       xi[k] = min(max(xx, 0), W - 1);
       yi[k] = min(max(yy, 0), H - 1);
     }
+    const float guard = lm_tile_guard(L, xi, yi);
     const float* row[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) row[k] = L.fmap + (size_t)yi[k] * W * cs + 4 * sub;
@@ -351,10 +378,10 @@ __device__ inline void lm_accumulate_cached(const LmParams& P, const LmLevelDev&
     B11 = lm_group_sum_t<LG>(B11);
     float rcost, wl;
     robust_loss(P.conf.loss, P.conf.loss_alpha, P.conf.loss_scale, s_cost, rcost, wl);
-    lm_point_record(dst, sub == 0, wl * (pt.wref * wq), rcost, Jw, px, py, pz, A0, A1, B00, B01, B11);
+    lm_point_record(dst, sub == 0, wl * (pt.wref * wq), rcost, Jw, px, py, pz, A0, A1, B00, B01, B11, guard);
   } else if (sub == 0) {
 #pragma unroll
-    for (int i = 0; i < 29; ++i) dst[i] = 0.f;
+    for (int i = 0; i < kNUsed; ++i) dst[i] = 0.f;
   }
 #if PXT_EXP_STAMPS
   if (dbg) { dbg[10] = dbg[11] = __builtin_amdgcn_s_memtime(); dbg[12] = 1; }
@@ -527,13 +554,13 @@ struct LmShared {
   float red[kLmMaxGrid * kRedStride];       // every workgroup's 32 sums of this epoch
   float tot[kNAcc];
   float T[12];
-  int flags[4];  // 0 stop level, 1 failed, 2 abort
+  int flags[4];  // 0 stop level, 1 failed, 2 abort, 3 tile guard tripped
 };
 
 struct LmRun {
   unsigned epoch, base, launch_id, spin_limit;
   int total_iters;
-  bool failed, aborted;
+  bool failed, aborted, guard;
 };
 
 // One iteration after the accumulation: the group leaders' sums are in sh.grp (n_groups records).  Fold them, publish,
@@ -557,7 +584,7 @@ __device__ inline bool lm_step(const LmParams& P, const LmGrid grid, const LmLev
   {  // the workgroup's own sums in a fixed order: 16 strided partials per slot, then a fixed 16-lane DPP tree - the
      // row's first lane stores the granule itself (round 3 went through LDS twice more and one wave published)
     float v = 0.f;
-    if (slot < 29)
+    if (slot < kNUsed)
       for (int q = part; q < n_groups; q += 16) v += sh.grp[q * kGrpStride + slot];
     v = lm_row16_sum(v);
     if (part == 0)
@@ -614,7 +641,10 @@ __device__ inline bool lm_step(const LmParams& P, const LmGrid grid, const LmLev
   LM_STAMP(6);
   if (tid == 0) {
     const float n_valid = sh.tot[28];
-    const bool fl = (sh.flags[1] != 0) || (n_valid < (float)P.conf.min_valid);
+    // a point read a tile that was never computed: the sums are worthless, the launch ends as a failed level does and
+    // reports PXT_E_GUARD (every workgroup folded the same sh.tot, so all of them decide alike)
+    const bool guard = sh.tot[kGuardSlot] != 0.f;
+    const bool fl = (sh.flags[1] != 0) || (n_valid < (float)P.conf.min_valid) || guard;
     float delta[6];
     const bool chol = solve6(sh.tot, L.lambda, !fl, delta);
     float Tn[12];
@@ -629,6 +659,7 @@ __device__ inline bool lm_step(const LmParams& P, const LmGrid grid, const LmLev
     const bool small_grad = gn < P.conf.grad_stop;
     sh.flags[0] = (small_step || small_grad) ? 1 : 0;
     sh.flags[1] = fl ? 1 : 0;
+    if (guard) sh.flags[3] = 1;
     if (grid.b == 0 && P.log) {
       float* lg = P.log + ((size_t)li * P.conf.num_iters + it) * PXT_LM_LOG_STRIDE;
       lg[0] = sh.tot[27] / n_valid;
@@ -637,7 +668,7 @@ __device__ inline bool lm_step(const LmParams& P, const LmGrid grid, const LmLev
       lg[3] = dt;
       lg[4] = gn;
       lg[5] = chol ? 0.f : 1.f;
-      lg[6] = 0.f;
+      lg[6] = sh.tot[kGuardSlot];
       lg[7] = 0.f;
       for (int i = 0; i < 12; ++i) lg[8 + i] = Tn[i];
     }
@@ -647,6 +678,7 @@ __device__ inline bool lm_step(const LmParams& P, const LmGrid grid, const LmLev
   ++run.epoch;
   ++run.total_iters;
   run.failed = sh.flags[1] != 0;
+  run.guard = sh.flags[3] != 0;
   return sh.flags[0] != 0 || run.failed;
 }
 
@@ -656,7 +688,7 @@ __device__ inline void lm_park(const float* acc, LmShared& sh) {
   if ((threadIdx.x & (LG - 1)) == 0) {
     float* dst = sh.grp + (threadIdx.x / LG) * kGrpStride;
 #pragma unroll
-    for (int i = 0; i < 29; ++i) dst[i] = acc[i];
+    for (int i = 0; i < kNUsed; ++i) dst[i] = acc[i];
   }
 }
 
@@ -691,6 +723,7 @@ __device__ __forceinline__ void lm_refine_problem(const LmParams& P, const LmGri
     sh.flags[0] = 0;
     sh.flags[1] = 0;
     sh.flags[2] = 0;
+    sh.flags[3] = 0;
   }
   __syncthreads();
 
@@ -706,6 +739,7 @@ __device__ __forceinline__ void lm_refine_problem(const LmParams& P, const LmGri
   run.total_iters = 0;
   run.failed = false;
   run.aborted = false;
+  run.guard = false;
   const int groups32 = G * kLmWaves * 2, groups16 = groups32 * 2, groups8 = groups32 * 4;
   const bool one_round_ok = P.conf.path != 2;  // (2: always the general path - A/B and tests)
 
@@ -755,7 +789,7 @@ __device__ __forceinline__ void lm_refine_problem(const LmParams& P, const LmGri
     P.err[1] = run.base + run.epoch + 1u + (run.aborted ? 8u : 0u);
     for (int i = 0; i < 12; ++i) P.out[i] = sh.T[i];
     P.out[12] = run.failed ? 1.f : 0.f;
-    P.out[13] = run.aborted ? (float)PXT_E_TIMEOUT : 0.f;
+    P.out[13] = run.aborted ? (float)PXT_E_TIMEOUT : run.guard ? (float)PXT_E_GUARD : 0.f;
     P.out[14] = (float)run.total_iters;
     // out[15] flips to 1 once the record and the log (all written by this thread) are visible
     // system-wide: a host that keeps `out` in pinned memory can poll this word instead of
@@ -922,7 +956,7 @@ namespace {
 // Host records -> the kernel's parameter block (shared by the single-problem and the batched entry).
 int lm_fill_params(LmParams& P, const float* p3d, const uint8_t* point_mask, int32_t n_points, const pxt_lm_level* levels,
                    int32_t n_levels, const float* T_init, const pxt_lm_conf* conf, float* out, float* log, void* workspace,
-                   const pxt_lm_camera* cam) {
+                   const pxt_lm_camera* cam, const pxt_lm_tile_guard* guard) {
   if (!p3d || !levels || !T_init || !conf || !out || !workspace) return PXT_E_ARG;
   if (n_levels < 1 || n_levels > PXT_MAX_LEVELS || n_points < 1) return PXT_E_ARG;
   if (conf->num_iters < 1 || conf->pad < 0) return PXT_E_ARG;
@@ -940,6 +974,17 @@ int lm_fill_params(LmParams& P, const float* p3d, const uint8_t* point_mask, int
     for (int i = 0; i < 10; ++i) d.cam[i] = s.cam[i];
     d.ndist = s.ndist;
     for (int i = 0; i < 6; ++i) d.lambda[i] = s.lambda[i];
+    d.flags = nullptr;
+    d.tile_rows = 1; d.tiles_x = 1; d.tile_x0 = 0; d.tile_y0 = 0;
+  }
+  if (guard) {  // (the guard reads flags[r * tiles_per_row + c] for the tiles the level's texels lie in and nothing else)
+    if (guard->level < 0 || guard->level >= n_levels || !guard->tile_flags || guard->tile_rows < 1 ||
+        guard->tiles_per_row < 1 || guard->tile_x0 < 0 || guard->tile_y0 < 0 ||
+        (guard->tile_x0 + levels[guard->level].w + 15) / 16 > guard->tiles_per_row)
+      return PXT_E_ARG;
+    LmLevelDev& d = P.lv[guard->level];
+    d.flags = guard->tile_flags;
+    d.tile_rows = guard->tile_rows; d.tiles_x = guard->tiles_per_row; d.tile_x0 = guard->tile_x0; d.tile_y0 = guard->tile_y0;
   }
   for (int i = 0; i < 12; ++i) P.T_init[i] = T_init[i];
   P.conf = *conf;
@@ -988,8 +1033,16 @@ extern "C" int pxt_lm_refine_cam(const float* p3d, const uint8_t* point_mask, in
                                  const pxt_lm_level* levels, int32_t n_levels, const float* T_init,
                                  const pxt_lm_conf* conf, float* out, float* log, void* workspace,
                                  const pxt_lm_camera* cam, void* stream) {
+  return pxt_lm_refine_guarded(p3d, point_mask, n_points, levels, n_levels, T_init, conf, out, log, workspace, cam, nullptr,
+                               stream);
+}
+
+extern "C" int pxt_lm_refine_guarded(const float* p3d, const uint8_t* point_mask, int32_t n_points,
+                                     const pxt_lm_level* levels, int32_t n_levels, const float* T_init,
+                                     const pxt_lm_conf* conf, float* out, float* log, void* workspace,
+                                     const pxt_lm_camera* cam, const pxt_lm_tile_guard* guard, void* stream) {
   LmParams P;
-  const int rc = lm_fill_params(P, p3d, point_mask, n_points, levels, n_levels, T_init, conf, out, log, workspace, cam);
+  const int rc = lm_fill_params(P, p3d, point_mask, n_points, levels, n_levels, T_init, conf, out, log, workspace, cam, guard);
   if (rc != PXT_OK) return rc;
   int grid = conf->n_workgroups;
   // 128 workgroups: scripts/bench_lm.py, round 4, N = 2341: 8.7 us per iteration at 64, 8.5 at 128, 8.5 at 192 (where every
@@ -1026,7 +1079,7 @@ extern "C" int pxt_lm_refine_batch(const pxt_lm_problem* problems, int32_t n_pro
   for (int k = 0; k < K; ++k) {
     const pxt_lm_problem& q = problems[k];
     const int rc = lm_fill_params(slot.host[k], q.p3d, q.point_mask, q.n_points, q.levels_host, q.n_levels, q.T_init_host, conf,
-                                  q.out, q.log, q.workspace, q.cam_host);
+                                  q.out, q.log, q.workspace, q.cam_host, nullptr);  // (a lock-step batch never guards)
     if (rc != PXT_OK) return rc;
   }
   // Workgroups per problem: the chip's 256 CUs dealt to the problems, one workgroup per CU (a 32-workgroup grid runs an

@@ -489,6 +489,7 @@ struct RefPoints {
   float pad;
   int x0, y0, fw, fh;  // the fine map is the window [x0, x0 + W) x [y0, y0 + H) of an fw x fh level
   int W, H;
+  int kind, margin;  // 0: a reference's record (the sampler's texels); 1: a query's (pxt_unet_query_points), with its margin
 };
 struct RefTileGeo {
   int th, tiles_x, tiles_y;  // tile rows (x 16 columns) and the tile grid of a layer
@@ -508,6 +509,28 @@ __host__ __device__ inline void reference_tiles_mark(const RefPoints& P, int n, 
   fine_flags[r1 * fine.tiles_x + c0] = 1;
   fine_flags[r1 * fine.tiles_x + c1] = 1;
 }
+// Query tiles (pxt_unet_query_points): the map's one reader is the LM's fine level (pxt_lm.hip), which starts at P.T and moves the
+// points.  Point n, if it lies in front of the camera - valid at P.T or not: a point that enters the image during the
+// refinement should find its tiles computed - takes the bounding box of the texels the refine kernel's point evaluation
+// loads around floor(u, v) (lm_accumulate: columns ix0 - 1 .. ix0 + 2, rows iy0 - 1 .. iy0 + 2, each clamped into the
+// map), grown by the margin and clipped to the map; every fine tile the box meets is marked.  The LM's tile guard counts a
+// point whose box (without the margin) meets an unmarked tile, so a refinement that outruns the margin is seen and redone.
+__host__ __device__ inline void query_tiles_mark(const RefPoints& P, int n, const RefTileGeo& fine, uint8_t* fine_flags) {
+  const Cam cam = make_cam(P.cam, P.ndist);
+  float px, py, pz, u = 0.f, v = 0.f;
+  transform_point(P.T, P.p3d[3 * n], P.p3d[3 * n + 1], P.p3d[3 * n + 2], px, py, pz);
+  project_point(cam, px, py, pz, u, v, nullptr);
+  if (!(pz > kCamEps)) return;
+  // (u, v) may be anything for a point far outside the image: bring it next to the level before the conversion
+  const float uc = fminf(fmaxf(u, -8.f), (float)P.fw + 8.f), vc = fminf(fmaxf(v, -8.f), (float)P.fh + 8.f);
+  const int ix0 = (int)floorf(uc) - P.x0, iy0 = (int)floorf(vc) - P.y0;  // window coordinates
+  const int xa = clamp_int(clamp_int(ix0 - 1, 0, P.W - 1) - P.margin, 0, P.W - 1);
+  const int xb = clamp_int(clamp_int(ix0 + 2, 0, P.W - 1) + P.margin, 0, P.W - 1);
+  const int ya = clamp_int(clamp_int(iy0 - 1, 0, P.H - 1) - P.margin, 0, P.H - 1);
+  const int yb = clamp_int(clamp_int(iy0 + 2, 0, P.H - 1) + P.margin, 0, P.H - 1);
+  for (int r = ya / fine.th; r <= yb / fine.th; ++r)
+    for (int c = xa >> 4; c <= (xb >> 4); ++c) fine_flags[r * fine.tiles_x + c] = 1;
+}
 // fine tile i, if needed: the tiles of the low_h x low_w layer before it under its up-sampling patch
 __host__ __device__ inline void reference_tiles_spread(int i, const RefTileGeo& fine, const uint8_t* fine_flags,
                                                        const RefTileGeo& low, int low_h, int low_w, uint8_t* low_flags) {
@@ -526,7 +549,10 @@ __global__ __launch_bounds__(1024) void reference_tiles_kernel(const RefPoints P
   for (int i = threadIdx.x; i < n_fine; i += blockDim.x) fine_flags[i] = 0;
   for (int i = threadIdx.x; i < n_low; i += blockDim.x) low_flags[i] = 0;
   __syncthreads();
-  for (int n = threadIdx.x; n < P.n; n += blockDim.x) reference_tiles_mark(P, n, fine, fine_flags);
+  if (P.kind == 1)
+    for (int n = threadIdx.x; n < P.n; n += blockDim.x) query_tiles_mark(P, n, fine, fine_flags);
+  else
+    for (int n = threadIdx.x; n < P.n; n += blockDim.x) reference_tiles_mark(P, n, fine, fine_flags);
   __syncthreads();
   for (int i = threadIdx.x; i < n_fine; i += blockDim.x) reference_tiles_spread(i, fine, fine_flags, low, low_h, low_w, low_flags);
 }
@@ -559,6 +585,7 @@ struct pxt_unet {
   struct SideSet {
     hipStream_t side = nullptr;
     hipEvent_t ev_enc4 = nullptr, ev_dec1 = nullptr, ev_side = nullptr;
+    hipEvent_t ev_head = nullptr, ev_flags = nullptr;  // the tile-flag launch: forked at the head of the pass, joined before decoder layer 2
   } sides[2];
   hipStream_t pass2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -571,6 +598,8 @@ struct pxt_unet {
   unsigned long long skip_clock = 0;
   bool tile_skip = true;         // pxt_unet_set_tile_skip
   bool ref_tiles = true;         // pxt_unet_set_reference_tiles
+  bool query_tiles = true;       // pxt_unet_set_query_tiles
+  bool qry_flags_live = false;   // the last pair call's query pass launched its flag kernel (pxt_unet_query_tiles out[4])
   void* skip_scratch = nullptr;  // device: raw zero image 48 x 48 x 3 f32 | in map 48 x 48 x 256 f16 | out map | pooled map
   bool plan_as_single = false;  // pxt_unet_set_batch_plan
   bool defer_join = false;    // pxt_unet_set_defer_join: the pair entry leaves the second pass un-joined ...
@@ -596,12 +625,14 @@ std::vector<std::array<int, 3>> parse_plan(const char* e) {
   return v;
 }
 constexpr int kRefTilesDefault = 1;  // (profiles/reference_tiles_ab.md)
+constexpr int kQueryTilesDefault = 1;  // (profiles/query_tiles_ab.md)
 struct Knobs {
   int streams = env_int("PXT_UNET_STREAMS", 2);  // < 2: a batch of two images runs as one batched pass, not two passes
   bool merge_heads = env_int("PXT_UNET_MERGE_HEADS", 1) != 0;  // the two coarse heads of a pass in one launch
   bool skip = env_int("PXT_UNET_SKIP", 1) != 0;                // constant-tile skipping
   bool fuse_first = env_int("PXT_UNET_FUSE_FIRST", 1) != 0;    // the first layer computed in the second one's staging
   bool ref_tiles = env_int("PXT_UNET_REF_TILES", kRefTilesDefault) != 0;  // a sampled pass computes only the fine tiles it needs
+  bool query_tiles = env_int("PXT_UNET_QUERY_TILES", kQueryTilesDefault) != 0;  // the same for a query's record
   const char* plan_env = getenv("PXT_CONV_PLAN");
   std::vector<std::array<int, 3>> plan = parse_plan(plan_env);
   bool debug = getenv("PXT_CONV_DEBUG") != nullptr;  // one stderr line per convolution launched
@@ -766,6 +797,7 @@ struct Plan {
   size_t enc_tmp[5][2], enc_pool[5], enc_out[5], dec_out[4], splitk, splitk_bytes, total;
   size_t skip_grid, skip_flags;  // constant-tile skipping: the 8 x 8 block grid, then the tile flags of layers 1..6
   size_t ref_flags, ref_flags_each;  // reference tiles: the tile flags of the last decoder layer, then of the one before it
+  size_t qry_flags;                  // query tiles: the same two regions for a query's record (read by the LM afterwards)
   int skip_bh, skip_bw;
 };
 
@@ -808,6 +840,7 @@ bool make_plan(const pxt_unet* ctx, int n_img, int H, int W, Plan& P) {
   P.skip_flags = take((size_t)n_img * 6 * ((size_t)(H / 8 + 2) * (W / 16 + 2)));
   P.ref_flags_each = align256((size_t)(H / 8 + 2) * (W / 16 + 2));  // (a single-image pass: one image's tiles per layer)
   P.ref_flags = take(2 * P.ref_flags_each);
+  P.qry_flags = take(2 * P.ref_flags_each);
   P.total = off;
   return true;
 }
@@ -1246,6 +1279,8 @@ extern "C" int pxt_unet_destroy(pxt_unet* ctx) {
     if (ss.ev_enc4) (void)hipEventDestroy(ss.ev_enc4);
     if (ss.ev_dec1) (void)hipEventDestroy(ss.ev_dec1);
     if (ss.ev_side) (void)hipEventDestroy(ss.ev_side);
+    if (ss.ev_head) (void)hipEventDestroy(ss.ev_head);
+    if (ss.ev_flags) (void)hipEventDestroy(ss.ev_flags);
   }
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -1266,11 +1301,27 @@ extern "C" int64_t pxt_unet_workspace_bytes(const pxt_unet* ctx, int32_t H, int3
   return pxt_unet_workspace_bytes_batch(ctx, 1, H, W);
 }
 
+// The device record of a points record for a fine map of FH x FW (validated by the caller).
+static RefPoints make_ref_points(const pxt_unet_sample_points& pts, int FH, int FW, int kind, int margin) {
+  const bool windowed = pts.full_w > 0;
+  RefPoints rp;
+  rp.p3d = pts.p3d; rp.n = pts.n_points;
+  for (int i = 0; i < 12; ++i) rp.T[i] = pts.T[i];
+  for (int i = 0; i < 10; ++i) rp.cam[i] = pts.cam[i];
+  rp.ndist = pts.ndist; rp.pad = (float)pts.pad;
+  rp.x0 = windowed ? pts.x0 : 0; rp.y0 = windowed ? pts.y0 : 0;
+  rp.fw = windowed ? pts.full_w : FW; rp.fh = windowed ? pts.full_h : FH;
+  rp.W = FW; rp.H = FH;
+  rp.kind = kind; rp.margin = margin;
+  return rp;
+}
+
 static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* images,
                         const int32_t* image_is_u8, const uint8_t* const* masks, int32_t H,
                         int32_t W, float* const* out_maps, const int32_t out_cstride[3],
                         const int32_t* normalize, void* workspace, void* stream, pxt_unet::SideSet& ss,
-                        const PlanScope& sc, const pxt_unet_sample_points* pts = nullptr) {
+                        const PlanScope& sc, const pxt_unet_sample_points* pts = nullptr, int pts_kind = 0,
+                        int pts_margin = 0) {
   if (!ctx || !images || !image_is_u8 || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
   Plan P;
   const int B = n_images;
@@ -1291,6 +1342,56 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
     PXT_HIP_CHECK(hipEventCreateWithFlags(&ss.ev_enc4, hipEventDisableTiming));
     PXT_HIP_CHECK(hipEventCreateWithFlags(&ss.ev_dec1, hipEventDisableTiming));
     PXT_HIP_CHECK(hipEventCreateWithFlags(&ss.ev_side, hipEventDisableTiming));
+    PXT_HIP_CHECK(hipEventCreateWithFlags(&ss.ev_head, hipEventDisableTiming));
+    PXT_HIP_CHECK(hipEventCreateWithFlags(&ss.ev_flags, hipEventDisableTiming));
+  }
+  const bool fuse_head3 = has_fused_head(ctx) && out_cstride[0] >= 36;
+  // ---- reference / query tiles (see reference_tiles_kernel): PXT_UNET_REF_TILES=0 / PXT_UNET_QUERY_TILES=0 compute every tile
+  // Only for a single-image pass that was handed the points its maps will be read at, and only with the fused fine
+  // head (a separate head launch would read the whole last layer).  The flags are made for the tile configurations the
+  // two layers are about to take; launch_conv drops them for a layer that ends up with another one or with split-K.
+  // The flag launch needs nothing the pass computes: it runs on the side stream from the head of the pass, beside the
+  // encoder, and decoder layer 2 waits for it (it used to sit between encoder and decoder, 8.5 us of the pass's chain).
+  const uint8_t* ref_needed[2] = {nullptr, nullptr};  // decoder layers 2 and 3
+  int ref_cfg[2] = {0, 0};
+  bool flags_forked = false;
+  const bool query_kind = pts && pts_kind == 1;
+  if (pts && pts->p3d && B == 1 && fuse_head3 &&
+      (query_kind ? (knobs().query_tiles && ctx->query_tiles) : (knobs().ref_tiles && ctx->ref_tiles))) {
+    const int FW = P.dw[3], FH = P.dh[3];
+    const bool windowed = pts->full_w > 0;
+    if (pts->n_points < 0 || pts->pad < 0 || (query_kind && pts_margin < 0) ||
+        (windowed && (pts->full_h < 1 || pts->x0 < 0 || pts->y0 < 0 || pts->x0 + FW > pts->full_w || pts->y0 + FH > pts->full_h)))
+      return PXT_E_ARG;
+    const UpSrc planned{(const half_t*)ws, 1, 1, 32, 1, 1};  // (only "a decoder layer" matters to the plan)
+    RefTileGeo geo[2];
+    bool ok = true;
+    for (int k = 0; k < 2; ++k) {
+      const ConvPlan cp = resolve_plan(decoder_layer(ctx, P, ws, B, 2 + k, &planned, fuse_head3), sc.at(15 + k));
+      ok = ok && cfg_valid(cp.cfg);
+      // (a query's flags go on to the LM's guard: none are made for a last layer that would drop them and compute every tile)
+      if (query_kind && k == 1 && cp.splits != 1) ok = false;
+      if (!ok) break;
+      ref_cfg[k] = cp.cfg;
+      geo[k].th = cfg_th(cp.cfg);
+      geo[k].tiles_x = (P.dw[2 + k] + 15) / 16;
+      geo[k].tiles_y = (P.dh[2 + k] + geo[k].th - 1) / geo[k].th;
+      ok = ok && (size_t)geo[k].tiles_x * geo[k].tiles_y <= P.ref_flags_each;
+    }
+    if (ok) {
+      const RefPoints rp = make_ref_points(*pts, FH, FW, pts_kind, pts_margin);
+      uint8_t* fine_flags = (uint8_t*)(ws + (query_kind ? P.qry_flags : P.ref_flags));
+      uint8_t* low_flags = fine_flags + P.ref_flags_each;
+      PXT_HIP_CHECK(hipEventRecord(ss.ev_head, s));  // (behind the caller's earlier work: last frame's LM may still read the flags)
+      PXT_HIP_CHECK(hipStreamWaitEvent(ss.side, ss.ev_head, 0));
+      hipLaunchKernelGGL(reference_tiles_kernel, dim3(1), dim3(1024), 0, ss.side, rp, geo[1], geo[0], P.dh[2], P.dw[2],
+                         fine_flags, low_flags);
+      PXT_HIP_CHECK(hipEventRecord(ss.ev_flags, ss.side));
+      flags_forked = true;
+      if (query_kind) ctx->qry_flags_live = true;
+      ref_needed[0] = low_flags;
+      ref_needed[1] = fine_flags;
+    }
   }
   // 1x1 heads at output scales 0, 2, 4 (per image: separate output tensors and normalisation
   // flags).  The two coarse ones are small, latency-bound launches whose inputs (enc4, dec1) exist
@@ -1436,49 +1537,6 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
   const half_t* prev = skip[4];
   bool head0_fused = false;
   int ph = P.h[4], pw = P.w[4], pc = ctx->conv[12].cout;
-  const bool fuse_head3 = has_fused_head(ctx) && out_cstride[0] >= 36;
-  // ---- reference tiles (see reference_tiles_kernel): PXT_UNET_REF_TILES=0 computes every tile ---------------------
-  // Only for a single-image pass that was handed the points its maps will be sampled at, and only with the fused fine
-  // head (a separate head launch would read the whole last layer).  The flags are made for the tile configurations the
-  // two layers are about to take; launch_conv drops them for a layer that ends up with another one or with split-K.
-  const uint8_t* ref_needed[2] = {nullptr, nullptr};  // decoder layers 2 and 3
-  int ref_cfg[2] = {0, 0};
-  if (pts && pts->p3d && B == 1 && knobs().ref_tiles && ctx->ref_tiles && fuse_head3) {
-    const int FW = P.dw[3], FH = P.dh[3];
-    const bool windowed = pts->full_w > 0;
-    if (pts->n_points < 0 || pts->pad < 0 ||
-        (windowed && (pts->full_h < 1 || pts->x0 < 0 || pts->y0 < 0 || pts->x0 + FW > pts->full_w || pts->y0 + FH > pts->full_h)))
-      return PXT_E_ARG;
-    const UpSrc planned{prev, 1, 1, 32, 1, 1};  // (only "a decoder layer" matters to the plan)
-    RefTileGeo geo[2];
-    bool ok = true;
-    for (int k = 0; k < 2; ++k) {
-      const ConvPlan cp = resolve_plan(decoder_layer(ctx, P, ws, B, 2 + k, &planned, fuse_head3), sc.at(15 + k));
-      ok = ok && cfg_valid(cp.cfg);
-      if (!ok) break;
-      ref_cfg[k] = cp.cfg;
-      geo[k].th = cfg_th(cp.cfg);
-      geo[k].tiles_x = (P.dw[2 + k] + 15) / 16;
-      geo[k].tiles_y = (P.dh[2 + k] + geo[k].th - 1) / geo[k].th;
-      ok = ok && (size_t)geo[k].tiles_x * geo[k].tiles_y <= P.ref_flags_each;
-    }
-    if (ok) {
-      RefPoints rp;
-      rp.p3d = pts->p3d; rp.n = pts->n_points;
-      for (int i = 0; i < 12; ++i) rp.T[i] = pts->T[i];
-      for (int i = 0; i < 10; ++i) rp.cam[i] = pts->cam[i];
-      rp.ndist = pts->ndist; rp.pad = (float)pts->pad;
-      rp.x0 = windowed ? pts->x0 : 0; rp.y0 = windowed ? pts->y0 : 0;
-      rp.fw = windowed ? pts->full_w : FW; rp.fh = windowed ? pts->full_h : FH;
-      rp.W = FW; rp.H = FH;
-      uint8_t* fine_flags = (uint8_t*)(ws + P.ref_flags);
-      uint8_t* low_flags = fine_flags + P.ref_flags_each;
-      hipLaunchKernelGGL(reference_tiles_kernel, dim3(1), dim3(1024), 0, s, rp, geo[1], geo[0], P.dh[2], P.dw[2], fine_flags,
-                         low_flags);
-      ref_needed[0] = low_flags;
-      ref_needed[1] = fine_flags;
-    }
-  }
   for (int d = 0; d < 4; ++d) {
     const UnetLayer& L = ctx->conv[13 + d];
     const int sb = 3 - d;
@@ -1501,6 +1559,7 @@ static int forward_pass(pxt_unet* ctx, int32_t n_images, const void* const* imag
     ConvLaunch cl = decoder_layer(ctx, P, ws, B, d, &up, fuse_head3);
     cl.in = skip[sb]; cl.out = o; cl.head = fuse_head ? &fh : nullptr;
     if (d >= 2) { cl.needed = ref_needed[d - 2]; cl.needed_cfg = ref_cfg[d - 2]; }
+    if (d == 2 && flags_forked) PXT_HIP_CHECK(hipStreamWaitEvent(s, ss.ev_flags, 0));
     const int rc = launch_conv(cl, sc.at(13 + d), s);
     if (rc != PXT_OK) return rc;
     prev = o;
@@ -1541,6 +1600,7 @@ extern "C" int pxt_unet_forward_batch(pxt_unet* ctx, int32_t n_images, const voi
                                       int32_t W, float* const* out_maps, const int32_t out_cstride[3],
                                       const int32_t* normalize, void* workspace, void* stream) {
   if (!ctx || !images || !image_is_u8 || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
+  ctx->qry_flags_live = false;
   if (ctx->f32)
     return pxt::f32_forward_batch(ctx->f32, n_images, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize,
                                   workspace, (hipStream_t)stream);
@@ -1564,12 +1624,12 @@ extern "C" int64_t pxt_unet_workspace_bytes_pair(const pxt_unet* ctx, const int3
 // second on a side stream, in two parts of the workspace.  (The frame's reference render and its masked query: equal sizes
 // in the benchmark, different ones with real assets - reference camera x 0.5 / x 0.3 - where the two passes used to run
 // one after the other: 0.54 + 0.54 ms against 0.72 ms side by side.)
-extern "C" int pxt_unet_forward_pair_sampled(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
-                                             const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
-                                             float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
-                                             void* workspace, void* stream,
-                                             const pxt_unet_sample_points* const* points_host) {
+static int forward_pair(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
+                        const uint8_t* const* masks, const int32_t H[2], const int32_t W[2], float* const* out_maps,
+                        const int32_t out_cstride[3], const int32_t* normalize, void* workspace, void* stream,
+                        const pxt_unet_sample_points* const* points_host, int kind1, int margin1) {
   if (!ctx || !images || !image_is_u8 || !H || !W || !out_maps || !out_cstride || !normalize || !workspace) return PXT_E_ARG;
+  ctx->qry_flags_live = false;  // (set by the query's own pass below, when it makes flags: never by a batched or fp32 one)
   if (ctx->f32)
     return pxt::f32_forward_pair(ctx->f32, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace,
                                  (hipStream_t)stream);
@@ -1596,7 +1656,7 @@ extern "C" int pxt_unet_forward_pair_sampled(pxt_unet* ctx, const void* const* i
     int rc = forward_pass(ctx, 1, images + im, image_is_u8 + im, masks ? masks + im : no_mask, H[im], W[im], out_maps + 3 * im,
                           out_cstride, normalize + im, (char*)workspace + (im ? second : 0),
                           im == 0 ? (void*)s : (void*)ctx->pass2, ctx->sides[im], pair_scope(),
-                          points_host ? points_host[im] : nullptr);
+                          points_host ? points_host[im] : nullptr, im == 1 ? kind1 : 0, im == 1 ? margin1 : 0);
     if (rc != PXT_OK) return rc;
   }
   PXT_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->pass2));
@@ -1606,6 +1666,25 @@ extern "C" int pxt_unet_forward_pair_sampled(pxt_unet* ctx, const void* const* i
   }
   PXT_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_join, 0));
   return PXT_OK;
+}
+
+extern "C" int pxt_unet_forward_pair_sampled(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
+                                             const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
+                                             float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
+                                             void* workspace, void* stream,
+                                             const pxt_unet_sample_points* const* points_host) {
+  return forward_pair(ctx, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace, stream, points_host,
+                      0, 0);
+}
+
+extern "C" int pxt_unet_forward_pair_tiles(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
+                                           const uint8_t* const* masks, const int32_t H[2], const int32_t W[2],
+                                           float* const* out_maps, const int32_t out_cstride[3], const int32_t* normalize,
+                                           void* workspace, void* stream, const pxt_unet_sample_points* reference_points,
+                                           const pxt_unet_query_points* query_points) {
+  const pxt_unet_sample_points* both[2] = {reference_points, query_points ? &query_points->points : nullptr};
+  return forward_pair(ctx, images, image_is_u8, masks, H, W, out_maps, out_cstride, normalize, workspace, stream, both,
+                      query_points ? 1 : 0, query_points ? query_points->margin : 0);
 }
 
 extern "C" int pxt_unet_forward_pair(pxt_unet* ctx, const void* const* images, const int32_t* image_is_u8,
@@ -1623,33 +1702,87 @@ extern "C" int pxt_unet_set_reference_tiles(pxt_unet* ctx, int32_t on) {
 }
 
 // The flag rule on the host (tests): reference_tiles_kernel's three steps, the same functions.
-extern "C" int pxt_unet_reference_tiles_host(const pxt_unet_sample_points* points_host, int32_t fine_h, int32_t fine_w,
-                                             int32_t fine_tile_rows, int32_t low_tile_rows, uint8_t* fine_flags_host,
-                                             uint8_t* low_flags_host) {
-  const pxt_unet_sample_points* pts = points_host;
+static int tiles_host(const pxt_unet_sample_points* pts, int kind, int margin, int32_t fine_h, int32_t fine_w, int32_t fine_tile_rows,
+                      int32_t low_tile_rows, uint8_t* fine_flags_host, uint8_t* low_flags_host) {
   if (!pts || (!pts->p3d && pts->n_points > 0) || pts->n_points < 0 || pts->pad < 0 || !fine_flags_host || !low_flags_host)
     return PXT_E_ARG;
+  if (kind == 1 && margin < 0) return PXT_E_ARG;
   if (fine_h < 2 || fine_w < 2 || (fine_h % 2) != 0 || (fine_w % 2) != 0 || fine_tile_rows < 2 || low_tile_rows < 1) return PXT_E_ARG;
   const bool windowed = pts->full_w > 0;
   if (windowed && (pts->full_h < 1 || pts->x0 < 0 || pts->y0 < 0 || pts->x0 + fine_w > pts->full_w || pts->y0 + fine_h > pts->full_h))
     return PXT_E_ARG;
-  RefPoints rp;
-  rp.p3d = pts->p3d; rp.n = pts->n_points;
-  for (int i = 0; i < 12; ++i) rp.T[i] = pts->T[i];
-  for (int i = 0; i < 10; ++i) rp.cam[i] = pts->cam[i];
-  rp.ndist = pts->ndist; rp.pad = (float)pts->pad;
-  rp.x0 = windowed ? pts->x0 : 0; rp.y0 = windowed ? pts->y0 : 0;
-  rp.fw = windowed ? pts->full_w : fine_w; rp.fh = windowed ? pts->full_h : fine_h;
-  rp.W = fine_w; rp.H = fine_h;
+  const RefPoints rp = make_ref_points(*pts, fine_h, fine_w, kind, margin);
   const int low_h = fine_h / 2, low_w = fine_w / 2;
   const RefTileGeo fine{fine_tile_rows, (fine_w + 15) / 16, (fine_h + fine_tile_rows - 1) / fine_tile_rows};
   const RefTileGeo low{low_tile_rows, (low_w + 15) / 16, (low_h + low_tile_rows - 1) / low_tile_rows};
   std::memset(fine_flags_host, 0, (size_t)fine.tiles_x * fine.tiles_y);
   std::memset(low_flags_host, 0, (size_t)low.tiles_x * low.tiles_y);
-  for (int n = 0; n < rp.n; ++n) reference_tiles_mark(rp, n, fine, fine_flags_host);
+  for (int n = 0; n < rp.n; ++n) {
+    if (kind == 1) query_tiles_mark(rp, n, fine, fine_flags_host);
+    else reference_tiles_mark(rp, n, fine, fine_flags_host);
+  }
   for (int i = 0; i < fine.tiles_x * fine.tiles_y; ++i)
     reference_tiles_spread(i, fine, fine_flags_host, low, low_h, low_w, low_flags_host);
   return PXT_OK;
+}
+extern "C" int pxt_unet_reference_tiles_host(const pxt_unet_sample_points* points_host, int32_t fine_h, int32_t fine_w,
+                                             int32_t fine_tile_rows, int32_t low_tile_rows, uint8_t* fine_flags_host,
+                                             uint8_t* low_flags_host) {
+  return tiles_host(points_host, 0, 0, fine_h, fine_w, fine_tile_rows, low_tile_rows, fine_flags_host, low_flags_host);
+}
+extern "C" int pxt_unet_query_tiles_host(const pxt_unet_query_points* query_host, int32_t fine_h, int32_t fine_w,
+                                         int32_t fine_tile_rows, int32_t low_tile_rows, uint8_t* fine_flags_host,
+                                         uint8_t* low_flags_host) {
+  if (!query_host) return PXT_E_ARG;
+  return tiles_host(&query_host->points, 1, query_host->margin, fine_h, fine_w, fine_tile_rows, low_tile_rows,
+                    fine_flags_host, low_flags_host);
+}
+
+extern "C" int pxt_unet_set_query_tiles(pxt_unet* ctx, int32_t on) {
+  if (!ctx) return PXT_E_ARG;
+  ctx->query_tiles = on != 0;
+  return PXT_OK;
+}
+
+// Where the pair pass keeps the flags of image 1's last decoder layer, and that layer's tiles (the LM's tile guard).
+extern "C" int pxt_unet_query_tiles(const pxt_unet* ctx, const int32_t H[2], const int32_t W[2], int64_t out[5]) {
+  if (!ctx || !H || !W || !out) return PXT_E_ARG;
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  if (ctx->f32) return PXT_OK;
+  Plan P0, P1;
+  if (!make_plan(ctx, 1, H[0], W[0], P0) || !make_plan(ctx, 1, H[1], W[1], P1)) return PXT_E_ARG;
+  char base = 0;  // (planning only reads whether pointers are null)
+  const UpSrc planned{(const half_t*)&base, 1, 1, 32, 1, 1};
+  const bool fused = has_fused_head(ctx);
+  const ConvPlan cp = resolve_plan(decoder_layer(ctx, P1, &base, 1, 3, &planned, fused), pair_scope().at(16));
+  if (!cfg_valid(cp.cfg)) return PXT_OK;
+  out[0] = (int64_t)((P0.total + 255) / 256 * 256 + P1.qry_flags);
+  out[1] = cfg_th(cp.cfg);
+  out[2] = (P1.dw[3] + 15) / 16;
+  out[3] = (P1.dh[3] + cfg_th(cp.cfg) - 1) / cfg_th(cp.cfg);
+  // Not a second copy of the pass's gates (knobs, fused head, map stride, batched or side by side, split-K): the query's
+  // pass itself says whether it launched its flag kernel, and only then does it leave any tile out.
+  out[4] = (ctx->qry_flags_live && (size_t)out[2] * out[3] <= P1.ref_flags_each) ? 1 : 0;
+  return PXT_OK;
+}
+
+// Image 1 of a pair call again, alone and in full: on the caller's stream, in image 1's part of the pair workspace and
+// planned as one image of the pair (pair_scope: every layer's tile configuration, split-K partition and ring variant
+// are the pair pass's, so the maps are the bits image 1 has in a pair call without a record).
+extern "C" int pxt_unet_forward_pair_second(pxt_unet* ctx, const void* image, int32_t image_is_u8, const uint8_t* mask,
+                                            const int32_t H[2], const int32_t W[2], float* const out_maps[3],
+                                            const int32_t out_cstride[3], int32_t normalize, void* workspace, void* stream) {
+  if (!ctx || !image || !H || !W || !out_maps || !out_cstride || !workspace) return PXT_E_ARG;
+  if (ctx->f32) return PXT_E_ARG;  // (an fp32 context never leaves a tile out)
+  Plan P0, P1;
+  if (!make_plan(ctx, 1, H[0], W[0], P0) || !make_plan(ctx, 1, H[1], W[1], P1)) return PXT_E_ARG;
+  if (ctx->join_pending) { PXT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_join, 0)); ctx->join_pending = false; }
+  ctx->qry_flags_live = false;
+  const void* images[1] = {image};
+  const uint8_t* masks[1] = {mask};
+  const size_t second = (P0.total + 255) / 256 * 256;
+  return forward_pass(ctx, 1, images, &image_is_u8, masks, H[1], W[1], out_maps, out_cstride, &normalize,
+                      (char*)workspace + second, stream, ctx->sides[1], pair_scope());
 }
 
 extern "C" int pxt_unet_set_tile_skip(pxt_unet* ctx, int32_t on) {
@@ -1690,6 +1823,7 @@ extern "C" int pxt_unet_forward_sampled(pxt_unet* ctx, const void* image, int32_
     return pxt_unet_forward_batch(ctx, 1, images, &image_is_u8, masks, H, W, out_maps, out_cstride, &normalize, workspace,
                                   stream);
   if (ctx->join_pending) { PXT_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_join, 0)); ctx->join_pending = false; }
+  ctx->qry_flags_live = false;
   return forward_pass(ctx, 1, images, &image_is_u8, masks, H, W, out_maps, out_cstride, &normalize, workspace, stream,
                       ctx->sides[0], batch_scope(ctx, 1), points_host);
 }

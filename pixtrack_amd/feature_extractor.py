@@ -36,6 +36,9 @@ class PixTrackFeatureExtractor:
         self._join_pending = False
         self._preloaded = []  # [(image, scale_image, mask, normalize, maps, scales)] handed over by preload()
         self.last_input_wh = None  # (w, h) the UNet ran the last extract_packed image at (after the resize rule)
+        # query tiles: the maps of the last staged (query) pass that was handed the query's own record, its tile flags for
+        # the LM's guard (UNet.query_tiles), and what redoing that pass in full needs (recompute_query)
+        self.query_tiles_maps = self.query_tiles_flags = self._query_redo = None
         assert hasattr(self.model, "scales")
         assert self.conf.resize_by in ["max", "max_force"], self.conf.resize_by
 
@@ -91,6 +94,7 @@ class PixTrackFeatureExtractor:
     def unstage(self) -> None:
         self._join()
         self._staged = self._ready = None
+        self.query_tiles_maps = self.query_tiles_flags = self._query_redo = None
         self._preloaded.clear()
 
     def _join(self) -> None:
@@ -153,14 +157,25 @@ class PixTrackFeatureExtractor:
         a_img, a_mask, a_sr = self._prepare(image, scale_image, mask)
         self.last_input_wh = (int(a_img.shape[1]), int(a_img.shape[0]))
         scales = [(a_sr[0] / s, a_sr[1] / s) for s in self.model.scales]
+        second = sample_points.get("second") if sample_points is not None else None
         if sample_points is not None and (a_sr != (1.0, 1.0) or tuple(a_img.shape[:2]) != tuple(image.shape[:2])):
             sample_points = None
+        self.query_tiles_maps = self.query_tiles_flags = self._query_redo = None
         if self._staged is not None:
             st_image, st_scale, st_mask, st_norm = self._staged
             self._staged = None
             if st_image is not image:
                 # equal sizes: one batched call; two sizes: the pair entry - both images side by side either way
                 b_img, b_mask, b_sr = self._prepare(st_image, st_scale, st_mask)
+                # the query's own record (refiner.query_sample_points) describes the unresized query's levels
+                query_tiles = getattr(self.model, "query_tiles", None)
+                if second is not None and (query_tiles is None or b_sr != (1.0, 1.0)
+                                           or tuple(b_img.shape[:2]) != tuple(st_image.shape[:2])):
+                    second = None
+                if sample_points is not None or second is not None:
+                    sample_points = {k: v for k, v in (sample_points or {}).items() if k != "second"}
+                    if second is not None:
+                        sample_points["second"] = second
                 if self.defer_join:
                     self.model.set_defer_join(True)
                 try:
@@ -170,12 +185,29 @@ class PixTrackFeatureExtractor:
                     if self.defer_join:
                         self.model.set_defer_join(False)
                         self._join_pending = True
+                if second is not None:
+                    # (the pass's own word, asked before anything else runs on the model.  None: it computed every tile
+                    # and wrote no flags - then the LM gets none)
+                    pair_sizes = [tuple(int(x) for x in a_img.shape[:2]), tuple(int(x) for x in b_img.shape[:2])]
+                    self.query_tiles_flags = query_tiles(pair_sizes)
+                    if self.query_tiles_flags is not None:
+                        self.query_tiles_maps, self._query_redo = both[1], ((b_img, b_mask, st_norm), pair_sizes)
                 # (b_img / b_mask ride along: the side stream may still be reading them until the join)
                 self._ready = (st_image, st_scale, st_mask, st_norm, both[1],
                                [(b_sr[0] / s, b_sr[1] / s) for s in self.model.scales], b_img, b_mask)
                 return both[0], scales
         self._arm(sample_points)
         return self.model.forward_packed(a_img, a_mask, normalize=normalize), scales
+
+    def recompute_query(self) -> None:
+        """The last staged pass that computed only its query tiles, again: alone, in full, into the same maps and planned
+        as the pair's second image, so that the maps are the bits of a pair pass without the record (after the LM's tile
+        guard tripped: the refinement left the tiles the pass was told about)."""
+        item, pair_sizes = self._query_redo
+        maps = self.query_tiles_maps
+        self.query_tiles_maps = self.query_tiles_flags = self._query_redo = None
+        self._join()
+        self.model.forward_pair_second(item, maps, pair_sizes)
 
     @torch.no_grad()
     def __call__(self, image: np.ndarray, scale_image: int = 1):

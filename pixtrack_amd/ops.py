@@ -58,7 +58,8 @@ SCHEMAS = {
         "int[] ndist, float[] lambdas, float[] T_init, int num_iters, int pad, int loss, float loss_alpha, "
         "float loss_scale, float grad_stop, float dt_stop, float dR_stop, int min_valid, int n_workgroups, "
         "Tensor(a!) record, Tensor(b!) workspace, bool want_log, int spin_limit=0, float[]? cam_conv=None, "
-        "int[]? cam_slots=None, Tensor(c!)? cam_out=None, int lm_path=0) -> ()"),
+        "int[]? cam_slots=None, Tensor(c!)? cam_out=None, int lm_path=0, int guard_level=-1, Tensor? guard_flags=None, "
+        "int[]? guard_geo=None) -> ()"),
     # K problems in one persistent launch (pxt_lm_refine_batch): per-problem tensors as lists, per-level tensors and
     # records flattened problem-major (n_levels[k] entries each), conf shared; n_workgroups is per problem
     "lm_refine_batch": (
@@ -92,7 +93,8 @@ SCHEMAS = {
         "Tensor ranges, int pad, int loss, float loss_alpha, float loss_scale, Tensor(a!) out) -> ()"),
     "unet_forward_batch": (
         "(int ctx, Tensor[] images, Tensor?[] masks, bool[] normalize, Tensor(a!)[] outs, Tensor(b!) workspace, "
-        "Tensor? sample_p3d=None, float[]? sample_pose_camera=None, int[]? sample_ints=None) -> ()"),
+        "Tensor? sample_p3d=None, float[]? sample_pose_camera=None, int[]? sample_ints=None, Tensor? second_p3d=None, "
+        "float[]? second_pose_camera=None, int[]? second_ints=None) -> ()"),
     "ngp_render": (
         "(int ctx, float[] view, int width, int height, int spp, int mode, Tensor(a!) out, Tensor(b!)? stats) -> ()"),
     "ngp_render_both": (
@@ -212,7 +214,11 @@ def _f32c(t: torch.Tensor, what: str) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------- LM
 def _lm_refine(p3d, point_mask, fmaps, frefs, channels, cameras, ndist, lambdas, T_init, num_iters, pad, loss,
                loss_alpha, loss_scale, grad_stop, dt_stop, dR_stop, min_valid, n_workgroups, record, workspace,
-               want_log, spin_limit=0, cam_conv=None, cam_slots=None, cam_out=None, lm_path=0):
+               want_log, spin_limit=0, cam_conv=None, cam_slots=None, cam_out=None, lm_path=0, guard_level=-1,
+               guard_flags=None, guard_geo=None):
+    """``guard_level`` (index in execution order), ``guard_flags`` (uint8 device tensor) and ``guard_geo`` = [tile_rows,
+    tiles_per_row, tile_x0, tile_y0]: that level's map holds data only in the tiles whose flag is 1
+    (pxt_lm_tile_guard, pxt_lm_refine_guarded); a launch that reads another tile ends with status PXT_E_GUARD."""
     L = _lib.lib()
     n_levels = len(fmaps)
     if not (1 <= n_levels <= _lib.PXT_MAX_LEVELS) or len(frefs) != n_levels or len(channels) != n_levels:
@@ -232,6 +238,21 @@ def _lm_refine(p3d, point_mask, fmaps, frefs, channels, cameras, ndist, lambdas,
         arr[i].cam[:] = cameras[10 * i:10 * i + 10]
         arr[i].ndist = int(ndist[i])
         arr[i].lambda_[:] = lambdas[6 * i:6 * i + 6]
+    guard = None
+    if guard_flags is not None:
+        if guard_geo is None or len(guard_geo) != 4:
+            raise _lib.PxtError("lm_refine: guard_geo holds tile_rows, tiles_per_row, tile_x0, tile_y0")
+        gl, flags = guard_level, guard_flags
+        tile_rows, tiles_per_row, tile_x0, tile_y0 = guard_geo
+        if not (0 <= int(gl) < n_levels) or flags.dtype != torch.uint8 or not flags.is_cuda or not flags.is_contiguous():
+            raise _lib.PxtError("lm_refine: tile_guard names a level and a contiguous uint8 device tensor of flags")
+        rows = (int(tile_y0) + arr[int(gl)].h - 1) // max(int(tile_rows), 1) + 1
+        if int(tile_rows) < 1 or flags.numel() < rows * int(tiles_per_row):
+            raise _lib.PxtError(f"lm_refine: tile_guard needs {rows} x {int(tiles_per_row)} flags, got {flags.numel()}")
+        guard = _lib.LmTileGuard()
+        guard.level, guard.tile_flags = int(gl), flags.data_ptr()
+        guard.tile_rows, guard.tiles_per_row, guard.tile_x0, guard.tile_y0 = (int(tile_rows), int(tiles_per_row),
+                                                                              int(tile_x0), int(tile_y0))
     conf = _lib.LmConf()
     conf.num_iters, conf.pad, conf.loss = int(num_iters), int(pad), int(loss)
     conf.loss_alpha, conf.loss_scale = float(loss_alpha), float(loss_scale)
@@ -248,6 +269,7 @@ def _lm_refine(p3d, point_mask, fmaps, frefs, channels, cameras, ndist, lambdas,
         raise _lib.PxtError("lm_refine: point_mask must be contiguous uint8")
     base = record.data_ptr()
     T0 = (C.c_float * 12)(*[float(x) for x in T_init])
+    cam = None
     if cam_conv is not None:  # the kernel's epilogue also derives the next render's camera (pxt_lm_refine_cam)
         if len(cam_conv) != 27:
             raise _lib.PxtError("lm_refine: cam_conv holds 27 doubles (Testbed.pose_conversion)")
@@ -263,10 +285,18 @@ def _lm_refine(p3d, point_mask, fmaps, frefs, channels, cameras, ndist, lambdas,
             if cam_out.dtype != torch.float32 or cam_out.numel() < 13 or not (cam_out.is_cuda or cam_out.is_pinned()):
                 raise _lib.PxtError("lm_refine: cam_out must be a pinned host (or device) float32 tensor of >= 13 elements")
             cam.cam_out13 = cam_out.data_ptr()
+        if guard is None:
+            _lib.check(
+                L.pxt_lm_refine_cam(p3d.data_ptr(), _lib.dptr(point_mask), n, arr, n_levels, T0, C.byref(conf), base,
+                                    base + 4 * nh if want_log else None, workspace.data_ptr(), C.byref(cam), _stream(p3d)),
+                "pxt_lm_refine_cam")
+            return
+    if guard is not None:
         _lib.check(
-            L.pxt_lm_refine_cam(p3d.data_ptr(), _lib.dptr(point_mask), n, arr, n_levels, T0, C.byref(conf), base,
-                                base + 4 * nh if want_log else None, workspace.data_ptr(), C.byref(cam), _stream(p3d)),
-            "pxt_lm_refine_cam")
+            L.pxt_lm_refine_guarded(p3d.data_ptr(), _lib.dptr(point_mask), n, arr, n_levels, T0, C.byref(conf), base,
+                                    base + 4 * nh if want_log else None, workspace.data_ptr(),
+                                    C.byref(cam) if cam is not None else None, C.byref(guard), _stream(p3d)),
+            "pxt_lm_refine_guarded")
         return
     _lib.check(
         L.pxt_lm_refine(p3d.data_ptr(), _lib.dptr(point_mask), n, arr, n_levels, T0, C.byref(conf), base,
@@ -520,16 +550,10 @@ def _score_pose_hypotheses(fmap, channels, camera, ndist, p3d, fref, valid, pose
 
 
 # ---------------------------------------------------------------------------------------- UNet
-def _unet_forward_batch(ctx, images, masks, normalize, outs, workspace, sample_p3d=None, sample_pose_camera=None,
-                        sample_ints=None):
-    """``sample_*`` (optional, one or two images): the points the FIRST image's fine map will be sampled at and nothing
-    else will read it for (pxt_unet_sample_points: p3d [N, 3] on the device; 12 pose + 10 fine-level camera floats;
-    ndist, pad, x0, y0, full_w, full_h) - the pass then computes only the fine tiles those samples depend on."""
-    L = _lib.lib()
-    n = len(images)
+def _unet_points(images, n, sample_p3d, sample_pose_camera, sample_ints):
     points = None
     if sample_p3d is not None:
-        if n > 2 or sample_pose_camera is None or sample_ints is None or len(sample_pose_camera) != 22 or len(sample_ints) != 6:
+        if n > 2 or sample_pose_camera is None or sample_ints is None or len(sample_pose_camera) != 22 or len(sample_ints) < 6:
             raise _lib.PxtError("unet_forward_batch: sample points go with one image or a pair, 22 floats (pose, camera) "
                                 "and 6 ints (ndist, pad, x0, y0, full_w, full_h)")
         _f32c(sample_p3d, "sample_p3d")
@@ -540,7 +564,29 @@ def _unet_forward_batch(ctx, images, masks, normalize, outs, workspace, sample_p
         points.p3d, points.n_points = sample_p3d.data_ptr(), int(sample_p3d.shape[0])
         points.T[:] = [float(x) for x in sample_pose_camera[:12]]
         points.cam[:] = [float(x) for x in sample_pose_camera[12:]]
-        points.ndist, points.pad, points.x0, points.y0, points.full_w, points.full_h = (int(x) for x in sample_ints)
+        points.ndist, points.pad, points.x0, points.y0, points.full_w, points.full_h = (int(x) for x in sample_ints[:6])
+    return points
+
+
+def _unet_forward_batch(ctx, images, masks, normalize, outs, workspace, sample_p3d=None, sample_pose_camera=None,
+                        sample_ints=None, second_p3d=None, second_pose_camera=None, second_ints=None):
+    """``sample_*`` (optional, one or two images): the points the FIRST image's fine map will be sampled at and nothing
+    else will read it for (pxt_unet_sample_points: p3d [N, 3] on the device; 12 pose + 10 fine-level camera floats;
+    ndist, pad, x0, y0, full_w, full_h) - the pass then computes only the fine tiles those samples
+    depend on.  ``second_*`` (a pair only): the SECOND image's record as a QUERY (pxt_unet_query_points; second_ints holds
+    a seventh value, the margin), whose flags the LM's tile guard reads afterwards (UNet.query_tiles)."""
+    L = _lib.lib()
+    n = len(images)
+    points = _unet_points(images, n, sample_p3d, sample_pose_camera, sample_ints)
+    second = None
+    if second_p3d is not None:
+        if n != 2:
+            raise _lib.PxtError("unet_forward_batch: the second image's points go with a pair of images")
+        if second_ints is None or len(second_ints) != 7:
+            raise _lib.PxtError("unet_forward_batch: second_ints holds ndist, pad, x0, y0, full_w, full_h, margin")
+        second = _lib.UnetQueryPoints()
+        second.points = _unet_points(images, n, second_p3d, second_pose_camera, second_ints)
+        second.margin = int(second_ints[6])
     if n == 0 or len(masks) != n or len(normalize) != n or len(outs) != 3 * n:
         raise _lib.PxtError("unet_forward_batch: per image one mask slot, one normalize flag and three output maps")
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
@@ -573,6 +619,10 @@ def _unet_forward_batch(ctx, images, masks, normalize, outs, workspace, sample_p
     if points is not None and n == 1:
         _lib.check(L.pxt_unet_forward_sampled(ctx, imgs[0], is_u8[0], mks[0], H, W, ptrs, cs, norm[0], workspace.data_ptr(),
                                               _stream(images[0]), C.byref(points)), "pxt_unet_forward_sampled")
+    elif second is not None:
+        _lib.check(L.pxt_unet_forward_pair_tiles(ctx, imgs, is_u8, mks, Hs, Ws, ptrs, cs, norm, workspace.data_ptr(),
+                                                 _stream(images[0]), C.byref(points) if points is not None else None,
+                                                 C.byref(second)), "pxt_unet_forward_pair_tiles")
     elif points is not None:  # (equal sizes too: the two-image batch entry runs through the pair entry)
         pp = (C.POINTER(_lib.UnetSamplePoints) * 2)(C.pointer(points), None)
         _lib.check(L.pxt_unet_forward_pair_sampled(ctx, imgs, is_u8, mks, Hs, Ws, ptrs, cs, norm, workspace.data_ptr(),

@@ -76,6 +76,7 @@ class LMResult:
     costs: List[List[float]]  # per level, per iteration masked-mean cost
     log: torch.Tensor  # host [n_levels, num_iters, 20]
     total_iters: int = 0
+    guard: bool = False  # the launch ended on its tile guard (PXT_E_GUARD): T is the pose before that iteration
 
 
 class Interpolator:
@@ -248,6 +249,7 @@ class PixTrackOptimizer:
         mask: Optional[torch.Tensor] = None,
         want_log: bool = True,
         camera=None,
+        tile_guard=None,
     ) -> "PendingLM":
         """Enqueue the fused multi-level refinement (levels in EXECUTION order,
         coarse -> fine).  Returns a handle; ``.result()`` synchronises.
@@ -281,8 +283,10 @@ class PixTrackOptimizer:
                       bool(want_log), int(conf.spin_limit),
                       None if camera is None else [float(x) for x in camera[0]],
                       None if camera is None else [int(x) for x in camera[1]],
-                      None if camera is None else camera[2], int(conf.path))
-        keep = list(levels)
+                      None if camera is None else camera[2], int(conf.path),
+                      -1 if tile_guard is None else int(tile_guard[0]), None if tile_guard is None else tile_guard[1],
+                      None if tile_guard is None else [int(x) for x in tile_guard[2:6]])
+        keep = list(levels) + [tile_guard]
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
         return PendingLM(buf, want_log, n_levels, conf.num_iters, (p3d, mask, keep, workspace), done)
@@ -552,7 +556,7 @@ class PendingLM:
         h = host.numpy()
         nh = 16 + _lib.PXT_MAX_LEVELS
         status = int(h[13])
-        if status != 0:
+        if status != 0 and status != _lib.PXT_E_GUARD:
             # a timed-out launch may leave granules of epochs it never finished behind: the next launch on this
             # workspace starts from zeroed tags (the kernel also advances its tag base by a margin)
             if self._keep is not None:
@@ -568,4 +572,5 @@ class PendingLM:
         else:
             log, costs = torch.zeros(self.n_levels, 0, _lib.PXT_LM_LOG_STRIDE), []
         self._keep = None
-        return LMResult(Pose(host[:12].clone()), bool(h[12] != 0), iters, costs, log, int(h[14]))
+        return LMResult(Pose(host[:12].clone()), bool(h[12] != 0), iters, costs, log, int(h[14]),
+                        guard=status == _lib.PXT_E_GUARD)

@@ -187,6 +187,16 @@ class PixLocPoseTrackerR9(PoseTracker):
         # queued renders: consumed / camera record never arrived within the poll bound / host and device disagree on a camera
         # bit / view settings changed between enqueue and use
         self.renders_ahead_used = self.renders_ahead_dropped = self.renders_ahead_rejected = self.renders_ahead_stale = 0
+        # Query tiles: on a steady frame the query's fine map has one reader, the LM's fine level, so its pass computes only
+        # the tiles around the points' projections at the frame's initial pose, grown by `query_tile_margin` fine pixels
+        # (scripts/query_tile_share.py measures it), and the LM launch guards every read; a launch that leaves the computed
+        # tiles has its frame redone in full (same bits as with the option off) and the option rests for 8 frames.
+        # (the library's knobs decide beneath this: pxt_unet_set_query_tiles, PXT_UNET_QUERY_TILES=0)
+        self.query_tiles = unet_precision == "fp16"
+        self.query_tile_margin = 8
+        self.query_tile_fallbacks = 0
+        self._query_tile_rest = 0  # frames the option still stays off after a fallback
+        self.unet_precision = unet_precision
         self.relocalizer = self._make_relocalizer(relocalizer)
         self._lost = False  # a frame failed: the next one is relocalised (relocalizer on only)
         self._accepted_pose = None  # the last pose a frame accepted (the relocaliser scores it as one more hypothesis)
@@ -763,7 +773,27 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._ahead = None
         refiner.after_lm_enqueued = self._render_ahead if (self.render_ahead and steady) else None
         refiner.lm_camera = self._lm_camera if (self.render_ahead and steady) else None
+        # the query computes only its LM's tiles on a steady frame of the staged pair pass, where nothing else reads its
+        # fine map: no dense-map log, no relocaliser scoring, none of the opt-ins the refiner itself checks
+        refiner.query_tiles = None
+        refiner.after_query_tile_fallback = self._query_tile_fallback
+        if self._query_tile_rest > 0:
+            self._query_tile_rest -= 1
+        elif (self.query_tiles and steady and not lockstep and self.batch_frame_images and self.debug < 2
+              and self.relocalizer is None and self.reference_points != "render"):
+            refiner.query_tiles = {"pose": self._frame_pose_init(), "camera": self.camera,
+                                   "margin": int(self.query_tile_margin)}
         return "steady" if steady else kind
+
+    def _query_tile_fallback(self):
+        """The LM's tile guard ended this frame's launch (the refiner redoes the frame in full): the render queued behind
+        that launch goes the way of a rejected one, and the option rests for the next 8 frames - a sequence whose motion
+        exceeds the margin does not pay the redo on every frame."""
+        self.query_tile_fallbacks += 1
+        self._query_tile_rest = 8
+        if self._ahead is not None:
+            self._ahead = None
+            self.renders_ahead_rejected += 1
 
     def _frame_pose_init(self) -> Pose:
         rotation, translation = self.pose.numpy()

@@ -143,6 +143,11 @@ class PoseTrackerRefiner:
         # makes it sits ahead of the LM's on the stream), or None for ref.valid.  The information, point report and
         # depth problems queued behind the launch take the same mask.  None (default): nothing changes.
         self.point_gate = None
+        # Query tiles (query_sample_points): set per frame by the tracker, None = the query pass computes every tile.
+        # query_tile_frames: launches that carried the tile guard; query_tile_fallbacks: those it ended (frame redone in full)
+        self.query_tiles = None
+        self.after_query_tile_fallback = None
+        self.query_tile_frames = self.query_tile_fallbacks = 0
         self.last_point_report = None  # {"summary", "points" (device [N, 8] or None), "level"} of the last launch
 
     # ---- logging hooks (pixloc BaseRefiner) -----------------------------------
@@ -330,6 +335,24 @@ class PoseTrackerRefiner:
         return {"p3d": p3d, "pose_camera": pose.as12().detach().cpu().reshape(-1).tolist() + cam_l.as10().tolist(),
                 "ints": [int(cam_l._data.shape[-1] - 6), int(pad)] + [int(x) for x in windows]}
 
+    def query_sample_points(self, p3d: torch.Tensor):
+        """The QUERY's record for the pair pass that is about to run (pxt_unet_query_points), from what the
+        tracker announced for this frame in ``query_tiles`` = {"pose": the pose the LM launch will start from, "camera":
+        the query camera, "margin": fine pixels}: the LM's fine level is then the query map's one reader, and the pass
+        computes only the tiles its points can reach (plus the margin).  None: the pass computes the whole map."""
+        qt = self.query_tiles
+        if qt is None or int(p3d.shape[0]) < 1:
+            return None
+        # (nothing but the LM may read the query's fine map: not the information / report kernels queued behind the
+        # launch, not a gate or a hook that takes the problem's maps)
+        if self.information or self.point_report or self.depth_hook is not None or self.point_gate is not None:
+            return None
+        s0 = self.feature_extractor.model.scales[0]
+        cam_l = qt["camera"].scale((1.0 / s0, 1.0 / s0))  # (an unresized query: the extractor drops the record otherwise)
+        pad = self.optimizer[0].interpolator.pad
+        return {"p3d": p3d, "pose_camera": qt["pose"].as12().detach().cpu().reshape(-1).tolist() + cam_l.as10().tolist(),
+                "ints": [int(cam_l._data.shape[-1] - 6), int(pad), 0, 0, 0, 0, int(qt["margin"])]}
+
     def interp_sparse_observations(self, feature_maps: List[torch.Tensor], feature_scales, image_id: int,
                                    p3dids: List[int], pose: Optional[Pose] = None,
                                    p3d: Optional[torch.Tensor] = None, window=None) -> SparseReferenceFeatures:
@@ -384,6 +407,9 @@ class PoseTrackerRefiner:
             # points are still being made on the device when the pass is planned)
             sample_points = None if render_points else self.reference_sample_points(dbids[0], pose, p3d, image, image_scale,
                                                                                     window)
+            second = None if (render_points or multiscales != [1]) else self.query_sample_points(p3d)
+            if second is not None:  # (rides with the reference's record: the staged query is the pass's second image)
+                sample_points = {**(sample_points or {}), "second": second}
             maps, scales = self.dense_feature_extraction(image, ref_img.name, image_scale, sample_points=sample_points)
             self.last_reference_wh = self.feature_extractor.last_input_wh  # (w, h) the reference pass ran at
             features[str(image_scale)] = self.interp_sparse_observations(maps, scales, dbids[0], p3dids, pose, p3d, window)
@@ -618,17 +644,44 @@ class PoseTrackerRefiner:
         optimizer[level] per level, all levels in one kernel launch.  ``levels`` (optional) keeps
         only those pyramid levels (conf.level_plan).  ``last_scale``: this is the frame's last image scale, the one
         the depth_hook (if set) queues its problem behind."""
-        prob = self.lm_problem(features_query, scales_query, qcamera, T_init, ref, levels)
         gated = self.point_gate(ref, T_init, qcamera) if self.point_gate is not None else None
-        if gated is not None:
-            prob["mask"] = gated  # (read by the problems queued behind the launch: _point_mask)
-        pending = PixTrackOptimizer.refine_levels(ref.p3d, prob["packs"], T_init, prob["conf"], self._ws,
-                                                  mask=self._point_mask(prob), camera=prob["camera"])
-        # the refinement is enqueued, its result not yet awaited: a caller may queue work behind it that reads the
-        # pose record on the device (the tracker's next render, pixloc_tracker_r9._render_ahead)
-        hook = getattr(self, "after_lm_enqueued", None)
-        if hook is not None:
-            hook(pending)
+        ext = self.feature_extractor
+
+        def enqueue(guarded: bool):
+            prob = self.lm_problem(features_query, scales_query, qcamera, T_init, ref, levels)
+            if gated is not None:
+                prob["mask"] = gated  # (read by the problems queued behind the launch: _point_mask)
+            # Query tiles: these maps come from a pass that computed only the fine tiles around the points' projections
+            # at T_init; the launch checks every footprint against the pass's flags and ends with `guard` set when it
+            # left them.
+            guard = None
+            if guarded and getattr(ext, "query_tiles_maps", None) is features_query and 0 in prob["order"]:
+                flags, tile_rows, tiles_per_row = ext.query_tiles_flags
+                guard = (prob["order"].index(0), flags, tile_rows, tiles_per_row, 0, 0)
+            pending = PixTrackOptimizer.refine_levels(ref.p3d, prob["packs"], T_init, prob["conf"], self._ws,
+                                                      mask=self._point_mask(prob), camera=prob["camera"], tile_guard=guard)
+            # the refinement is enqueued, its result not yet awaited: a caller may queue work behind it that reads the
+            # pose record on the device (the tracker's next render, pixloc_tracker_r9._render_ahead)
+            hook = getattr(self, "after_lm_enqueued", None)
+            if hook is not None:
+                hook(pending)
+            return prob, pending, guard is not None
+
+        prob, pending, guarded = enqueue(True)
+        if guarded:
+            self.query_tile_frames += 1
+            res = pending.result()
+            if not res.guard:
+                return self.lm_finish(prob, res)
+            # The guard tripped: the query pass again, alone and in full, into the same maps, and the frame's refinement
+            # again from the same pose - the launch, and what follows it, of a frame with the option off.  The render
+            # queued behind the first launch ran on the slot's old camera (the kernel marked its record -1): dropped.
+            self.query_tile_fallbacks += 1
+            dropped = getattr(self, "after_query_tile_fallback", None)
+            if dropped is not None:
+                dropped()
+            ext.recompute_query()
+            prob, pending, _ = enqueue(False)
         if self.information:  # (after the render-ahead chain: the next frame's render does not wait for it)
             self.enqueue_information(prob, pending)
         if self.point_report:  # (behind the information launch, if any)

@@ -394,9 +394,12 @@ class UNet:
         outs = [[torch.empty(h, w, cstride_for(c), device=self.device, dtype=torch.float32)
                  for (h, w), c in zip(self.level_shapes(*hw), OUTPUT_DIMS)] for hw in sizes]
         sp = (sample_points if sample_points is not None else armed) if n <= 2 else None
+        first = (sp["p3d"], sp["pose_camera"], sp["ints"]) if sp and sp.get("p3d") is not None else (None, None, None)
+        s2 = sp.get("second") if (sp and n == 2) else None
+        second = (s2["p3d"], s2["pose_camera"], s2["ints"]) if s2 else (None, None, None)
         ops.unet_forward_batch(int(self._ctx.value), [it[0] for it in items], [it[1] for it in items],
                                [bool(it[2]) for it in items], [o for per in outs for o in per], self._ws,
-                               *((sp["p3d"], sp["pose_camera"], sp["ints"]) if sp else ()))
+                               *first, *second)
         return outs
 
     def set_batch_plan(self, per_image_plan: bool) -> None:
@@ -415,6 +418,49 @@ class UNet:
         """Hands the NEXT forward_packed_batch call its ``sample_points`` (the call consumes them, whatever it does):
         the same as passing the argument, for a call that goes through a hook wrapped around that method."""
         self._armed_points = sample_points
+
+    def forward_pair_second(self, item, maps, sizes, workspace: Optional[torch.Tensor] = None) -> None:
+        """The SECOND image of the last pair call over images of ``sizes`` = [(H0, W0), (H1, W1)] again, alone and in full:
+        ``item`` = (image, mask or None, normalize), into ``maps`` (the three maps that call returned for it) and the same
+        workspace, planned as one image of the pair - the bits that image has in a pair call without a record, which a
+        lone forward_packed does not give (pxt_unet_forward_pair_second).  The query pass redone after a tile-guard trip."""
+        image, mask, normalize = item
+        _lib.require_gpu(image, "image")
+        ws = self._ws if workspace is None else workspace
+        Hs, Ws = (C.c_int32 * 2)(sizes[0][0], sizes[1][0]), (C.c_int32 * 2)(sizes[0][1], sizes[1][1])
+        if sizes[1] != sizes[0]:
+            need = int(_lib.lib().pxt_unet_workspace_bytes_pair(self._ctx, Hs, Ws))
+        else:
+            need = int(_lib.lib().pxt_unet_workspace_bytes_batch(self._ctx, 2, *sizes[0]))
+        if (tuple(image.shape) != (*sizes[1], 3) or not image.is_contiguous() or image.dtype not in (torch.float32, torch.uint8)
+                or need <= 0 or ws is None or ws.numel() < need or len(maps) != 3):
+            raise _lib.PxtError("forward_pair_second: the second image, the maps and the workspace of the last pair call")
+        if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(sizes[1]) or not mask.is_contiguous()):
+            raise _lib.PxtError("forward_pair_second: masks are contiguous uint8 [H, W]")
+        for m, (h, w), c in zip(maps, self.level_shapes(*sizes[1]), OUTPUT_DIMS):
+            if tuple(m.shape) != (h, w, cstride_for(c)) or m.dtype != torch.float32 or not m.is_contiguous():
+                raise _lib.PxtError("forward_pair_second: maps are the three float32 maps of forward_packed_batch")
+        ptrs = (C.c_void_p * 3)(*[m.data_ptr() for m in maps])
+        cs = (C.c_int32 * 3)(*[int(m.shape[2]) for m in maps])
+        _lib.check(_lib.lib().pxt_unet_forward_pair_second(
+            self._ctx, image.data_ptr(), int(image.dtype == torch.uint8), _lib.dptr(mask), Hs, Ws, ptrs, cs,
+            int(bool(normalize)), ws.data_ptr(), _lib.stream_ptr(self.device)), "pxt_unet_forward_pair_second")
+
+    def set_query_tiles(self, on: bool) -> None:
+        """Whether a pair pass that is handed the query's record computes only the fine tiles the LM will read
+        (pxt_unet_set_query_tiles; the process-wide A/B knob is PXT_UNET_QUERY_TILES)."""
+        _lib.check(_lib.lib().pxt_unet_set_query_tiles(self._ctx, int(bool(on))), "pxt_unet_set_query_tiles")
+
+    def query_tiles(self, sizes):
+        """Right after a pair pass over images of ``sizes`` = [(H0, W0), (H1, W1)]: (flags, tile_rows, tiles_per_row) of the
+        SECOND image's fine map - ``flags`` a uint8 view of the pass's workspace, one byte per tile, written by that pass
+        from the query's record - or None when that pass computed every tile (it says so itself: pxt_unet_query_tiles)."""
+        Hs, Ws = (C.c_int32 * 2)(sizes[0][0], sizes[1][0]), (C.c_int32 * 2)(sizes[0][1], sizes[1][1])
+        out = (C.c_int64 * 5)()
+        _lib.check(_lib.lib().pxt_unet_query_tiles(self._ctx, Hs, Ws, out), "pxt_unet_query_tiles")
+        if not out[4] or self._ws is None or self._ws.numel() < out[0] + out[2] * out[3]:
+            return None
+        return self._ws[out[0]:out[0] + out[2] * out[3]], int(out[1]), int(out[2])
 
     def set_reference_tiles(self, on: bool) -> None:
         """Whether a pass that is handed sample points computes only the fine tiles they need (pxt_unet_set_reference_tiles;
