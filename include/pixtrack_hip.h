@@ -200,7 +200,7 @@ typedef struct {
   float* out;         /* [n_points][cstride] */
   int32_t h, w, C, cstride;
   float cam[10];      /* reference camera scaled by reference_scale and level scale */
-  int32_t ndist;
+  int32_t ndist;      /* 0, 2 or 4 (anything else: PXT_E_ARG, nothing launched) */
   /* The map may be a WINDOW of the level's full map (round 5: the reference pass runs on a crop of the reference render
    * that holds every input pixel the sampled points depend on - the pyramid's dependency radius around the points'
    * bounding box - instead of on the whole render; pixloc_pose_refiners.py:282-290 computes the dense maps only to sample

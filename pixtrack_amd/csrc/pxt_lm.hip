@@ -1132,6 +1132,7 @@ extern "C" int pxt_sample_sparse(const float* p3d, int32_t n_points, const float
         s.cstride < s.C + 1 || s.h < 2 || s.w < 2)
       return PXT_E_ARG;
     if (((uintptr_t)s.fmap % 16) != 0 || ((uintptr_t)s.out % 16) != 0) return PXT_E_ARG;
+    if (s.ndist != 0 && s.ndist != 2 && s.ndist != 4) return PXT_E_ARG;  // (as check_level: the camera models project_point knows)
     SampleLevelDev& d = P.lv[l];
     d.fmap = s.fmap;
     d.out = s.out;

@@ -140,13 +140,22 @@ def make_lm_scene(
     sigma_px: float = 4.0,
     fill: float = 0.5,
     k1: float = 0.0,
+    camera: Optional[dict] = None,
 ) -> LMScene:
+    """``camera``: a COLMAP camera dict (``model``, ``params``; ``width`` / ``height`` default to the scene's) used in
+    place of the SIMPLE_RADIAL(f, k1) one, with an optional ``focal`` entry: the focal length the eye distance is sized
+    by (default: the model's first parameter, f or fx).  It draws nothing from the generator: with ``camera=None`` every
+    array of the scene keeps its bits."""
     rng = np.random.default_rng(seed)
     lo, hi = ngp_aabb_to_nerf_box(aabb)
     p3d = rng.uniform(lo, hi, size=(n_points, 3))
     center = 0.5 * (lo + hi)
     extent = float(np.max(hi - lo))
     f = 1.2 * max(width, height)
+    if camera is not None:
+        assert k1 == 0.0, "camera= carries its own distortion"
+        assert camera.get("width", width) == width and camera.get("height", height) == height
+        f = float(camera.get("focal", np.asarray(camera["params"], dtype=np.float64)[0]))
     dist = f * extent / (fill * min(width, height))
     direction = rng.normal(size=3)
     direction[2] = abs(direction[2]) * 0.3
@@ -156,6 +165,9 @@ def make_lm_scene(
     R_init, t_init = perturb_pose(R_gt, t_gt, rng, init_rot_deg, init_trans, center)
     colmap_cam = dict(model="SIMPLE_RADIAL", width=width, height=height,
                       params=np.array([f, width / 2.0, height / 2.0, k1]))
+    if camera is not None:
+        colmap_cam = dict(model=camera["model"], width=width, height=height,
+                          params=np.asarray(camera["params"], dtype=np.float64))
     camera = Camera.from_colmap(colmap_cam)
 
     feats_query, feats_ref, scales = [], [], []

@@ -23,6 +23,10 @@ band along all four borders (inside and outside the padded window; with pad 0 th
 of the image), points behind the camera, and single texels zeroed under the footprints of object points.  The host
 test's hand-placed points run through the kernel as well, at both pads, against the codes written down by hand.
 __main__ requires every reject code 1..6 to occur among the cases.
+Two cases carry the distortion of a camera of tests/camera_cases.py: ``opencv`` (ndist 4: the tangential terms of the
+Jacobian the step is built from) and ``k2_limit``, with twenty points beyond the model's range (reject code 2) and
+twenty inside it but outside the image (code 3) - dr_projectable restates project_point's range test by hand.  The
+float32 statement stays below every constant above on both.
 """
 import ctypes as C
 import sys
@@ -35,6 +39,7 @@ import numpy as np
 import pytest
 import torch
 
+import camera_cases as CC
 from pixtrack_amd import _lib
 from pixtrack_amd import depth_refinement as DR
 from pixtrack_amd.depth_scene import CAM10, SCALE, make_scene, pose12, rodrigues
@@ -87,8 +92,14 @@ CASES.update({
     "natural_stop": (600, dict(conf="default", rot_deg=0.3, trans=0.001)),
     "border_pad0": (600, dict(conf=dict(pad=0), border=True)),
     "border_pad2": (600, dict(border=True)),
+    # the distortion of two cameras of tests/camera_cases.py on this scene's camera: OPENCV (p1, p2 in the point and in
+    # the four Jd terms the step is built from) and the k2 > 0 range limit, with points placed on either side of it -
+    # dr_projectable is a hand copy of project_point's range test and must tell code 2 from code 3
+    "opencv": (600, dict(dist=CC.CAMERAS["opencv"]["params"][4:])),
+    "k2_limit": (600, dict(dist=CC.CAMERAS["k2_limit"]["params"][3:], range_band=True)),
 })
 N_BAND, N_BEHIND, N_HOLES = 80, 10, 8
+N_RANGE = 40  # half beyond the range limit (code 2), half inside it and outside the image (code 3)
 
 _SCENES = {}
 
@@ -125,6 +136,17 @@ def border_extras(sc, size, good, rng):
     return extras, sensor
 
 
+def range_extras(sc, dist, rng):
+    """-> points [N_RANGE, 3] in front of the camera at the ground-truth pose: the first half at r^2 = 1.05 .. 1.5 x the
+    model's range limit, the second at 0.8 .. 0.95 x (where the distorted point lies 150 px from the principal point:
+    outside the 160 x 120 image in every direction)."""
+    lim = CC.r2_limit(dist)
+    r = np.sqrt(lim * np.concatenate([rng.uniform(1.05, 1.5, N_RANGE // 2), rng.uniform(0.8, 0.95, N_RANGE - N_RANGE // 2)]))
+    phi = rng.uniform(0, 2 * np.pi, N_RANGE)
+    p = 0.45 * np.stack([r * np.cos(phi), r * np.sin(phi), np.ones(N_RANGE)], 1)
+    return (p - sc["t"]) @ sc["R"]
+
+
 def build_case(name):
     """The float32 inputs of a case (and the conf as the kernel receives it)."""
     if name in _BUILT:
@@ -134,13 +156,15 @@ def build_case(name):
     sc = scene_for(size)
     rng = np.random.default_rng(sum(map(ord, name)))
     n_bad = 0 if n <= 10 else int(round(0.15 * n))
-    n_extra = N_BAND + N_BEHIND if opt.get("border") else 0
+    n_extra = N_BAND + N_BEHIND if opt.get("border") else (N_RANGE if opt.get("range_band") else 0)
     good = sc["points"][rng.permutation(len(sc["points"]))[:n - n_bad - n_extra]]
     bad = sc["all_points"][rng.permutation(len(sc["all_points"]))[:n_bad]]
     sensor = sc["sensor"]
-    if n_extra:
+    if opt.get("border"):
         extras, sensor = border_extras(sc, size, good, rng)
         bad = np.concatenate([bad, extras])
+    elif opt.get("range_band"):
+        bad = np.concatenate([bad, range_extras(sc, opt["dist"], rng)])
     pts = np.concatenate([good, bad])[rng.permutation(n)].astype(np.float32)
     assert len(pts) == n
     rot, trans = (0.2, 0.0005) if n <= 10 else (opt.get("rot_deg", 0.5), opt.get("trans", 0.002))
@@ -154,6 +178,9 @@ def build_case(name):
     if "k1" in opt:
         cam10[6] = opt["k1"]
         ndist = 2
+    if "dist" in opt:
+        ndist = len(opt["dist"])
+        cam10[6:6 + ndist] = opt["dist"]
     conf = opt.get("conf", {})
     if conf == "default":  # the package's defaults at the point set's extent; room for the stop rule to act
         conf = DR.DepthRefineConf(num_iters=32).resolve(DR.points_extent(sc["points"]))
@@ -286,6 +313,10 @@ def test_every_iteration_against_the_float64_replay(device, name):
     if name.startswith("border"):  # the gates these cases are for acted on the device, at every evaluation
         for row in out["codes"][:iters + 1]:
             assert {2, 3, 4} <= set(row.tolist()), np.bincount(row, minlength=7)
+    if name == "k2_limit":  # beyond the range: code 2, all of them and no other point; inside it and off the image: code 3
+        assert iters >= 1
+        for row in out["codes"][:iters + 1]:
+            assert int((row == 2).sum()) == N_RANGE // 2 and int((row == 3).sum()) >= N_RANGE // 2, np.bincount(row, minlength=7)
     # rows the run did not reach stay as the caller left them
     assert not out["log"][iters:].any() and not out["codes"][iters + 1:].any()
 
@@ -513,6 +544,9 @@ if __name__ == "__main__":
         seen += hist
         if name.startswith("border"):
             assert all({2, 3, 4} <= set(row.tolist()) for row in ref["codes"]), (name, hist)
+        if name == "k2_limit":
+            assert iters >= 1 and all(int((row == 2).sum()) == N_RANGE // 2 and int((row == 3).sum()) >= N_RANGE // 2
+                                      for row in ref["codes"][:iters + 1]), (name, hist)
         print(f"{name:18s} N {len(case['points']):5d} iters {iters:2d} status {out['record'][31]:+.0f} n_valid "
               f"{int(out['record'][15]):5d} -> {int(out['record'][17]):5d} LU {int(out['log'][:n, 5].sum())} fragile64 {frag64:.4f} "
               + " ".join(f"{k} {v:.2e}" for k, v in dev.items()) + f" codes {hist.tolist()}")

@@ -27,7 +27,14 @@ Cases (CASES, BATCH)
   * three-level runs with the default thresholds, pose carried from level to level, natural stops: one single launch and
     one refine_levels_batch of three unlike problems;
   * an object that overfills the image (fill = 1.5, pad 0): valid points whose 12-texel footprint reads zero-padded
-    texels, ONE step per level at the initial pose (where a device trajectory puts border points the CPU cannot decide).
+    texels, ONE step per level at the initial pose (where a device trajectory puts border points the CPU cannot decide);
+  * the camera table of tests/camera_cases.py: OPENCV (ndist 4: p1, p2 in the point and in the four distortion terms of
+    the Jacobian) on every accumulation variant, the general path and lm_path = 2; PINHOLE (ndist 0) over three levels;
+    and the k2 > 0 range limit inside an overfilled image, one step per level, both paths, 8 and 128 workgroups: the
+    points inside the image and beyond the range (31 to 49 per level) must drop out of n_valid exactly.  The float32
+    oracle stays below every constant of this file on them (__main__ asserts it; the worst new relative step is 1.1e-4,
+    opencv-v2-n100 at its 1.2e-3 step, against 2.85e-4), so the constants stand as they were.  No replayed pose may hold a point nearer than relative 1e-5 (in
+    r^2) to the range limit (FAIR_R2_MARGIN), as none may sit within 1e-3 px of the padded border.
 
 Bars (measured by this file's __main__ on the CPU: the float32 oracle against the float64 oracle over the same cases, on
 the float64 trajectory rounded to float32 after every step; the bar is 4x the worst value - another summation order
@@ -62,6 +69,7 @@ import numpy as np
 import pytest
 import torch
 
+import camera_cases as CC
 from oracle import lm_oracle as O
 from pixtrack_amd import _lib
 from pixtrack_amd.geometry import Pose
@@ -81,6 +89,7 @@ REL_GTERMS = 4 * F32_GTERMS
 COS_ABS = 4 * 2.0 ** -24
 BIG_STEP = 1e-3  # a step at or above this length is held by the relative term
 FAIR_MARGIN = 1e-3  # px: no point of a replayed pose may sit nearer to the padded border
+FAIR_R2_MARGIN = CC.R2_REL_MARGIN  # ... nor nearer (relative, in r^2) to the range limit of its distortion model
 
 
 def pose_rounding(t_norm):
@@ -100,6 +109,11 @@ SCENES = {
     # the object overfills the image: valid points read zero-padded texels at pad 0 (test_pose_uncertainty_gpu's "cropped")
     "E": dict(seed=1305, fill=1.5),
     "F": dict(seed=1305, fill=1.5, k1=-0.08),
+    # the camera table (tests/camera_cases.py): ndist 4 (tangential terms in the point and its Jacobian), ndist 0, and
+    # a range limit inside an overfilled image (k2 > 0 branch)
+    "opencv": dict(seed=1401, sigma_px=2.0, **CC.SCENE_KW["opencv"]),
+    "pinhole": dict(seed=1402, sigma_px=2.0, **CC.SCENE_KW["pinhole"]),
+    "k2_limit": dict(seed=1305, **CC.SCENE_KW["k2_limit"]),
 }
 LEVEL_C = {0: 32, 1: 128, 2: 128}
 ZERO_STOPS = dict(grad_stop_criteria=0.0, dt_stop_criteria=0.0, dR_stop_criteria=0.0)
@@ -184,6 +198,14 @@ CASES = [
     _case("mask-leaves-9", "A", [2, 1, 0], 300, 8, [4, 4, 1], mask=("exact", 9), iters=30, natural=True, kind="failed"),
     # ---- the default thresholds, pose carried over three levels, natural stops (n_workgroups 0: the library's 128)
     _case("three-levels-n777", "B", [2, 1, 0], 777, 0, [2, 2, 1], iters=30, natural=True, kind="natural"),
+    # ---- the camera table: OPENCV (p1, p2 in the point and in Jd00 / Jd01 / Jd10 / Jd11) on every accumulation variant,
+    # the general path and lm_path = 2; PINHOLE over three levels
+    _traj("opencv-v2-n100", "opencv", 2, 100, 8, 2),
+    _traj("opencv-v3-n200", "opencv", 1, 200, 8, 3, lam="heavy"),
+    _traj("opencv-v1-n400", "opencv", 0, 400, 8, 1, loss="squared", lam="heavy"),
+    _traj("opencv-gen32-n600", "opencv", 1, 600, 8, 0, pad=0, lam="heavy"),
+    _traj("opencv-v3-n200-path2", "opencv", 1, 200, 8, 0, path=2, lam="heavy"),
+    _case("pinhole-three-levels-n777", "pinhole", [2, 1, 0], 777, 0, [2, 2, 1], iters=30, natural=True, kind="natural"),
 ]
 # ---- border reads: one step per level at the initial pose, pad 0, both paths, two grids
 for _scene, _runs in (("E", [(0, 128), (2, 128), (0, 8), (2, 8)]), ("F", [(0, 128), (2, 8)])):
@@ -192,6 +214,12 @@ for _scene, _runs in (("E", [(0, 128), (2, 128), (0, 8), (2, 8)]), ("F", [(0, 12
             CASES.append(_case(f"border-{_scene}-L{_level}-path{_path}-g{_G}", _scene, [_level], 2048, _G,
                                [lm_variant(LEVEL_C[_level], 2048, _G, _path)], path=_path, pad=0, iters=1, natural=True,
                                kind="border"))
+# ---- the k2 > 0 range limit inside the image: points beyond it must drop out of n_valid exactly (one step, pad 0)
+for _level in (0, 1, 2):
+    for _path, _G in [(0, 128), (2, 128), (0, 8), (2, 8)]:
+        CASES.append(_case(f"border-k2_limit-L{_level}-path{_path}-g{_G}", "k2_limit", [_level], 2048, _G,
+                           [lm_variant(LEVEL_C[_level], 2048, _G, _path)], path=_path, pad=0, iters=1, natural=True,
+                           kind="border"))
 # ---- one refine_levels_batch of three unlike problems (8 workgroups each, default thresholds)
 BATCH = [
     _case("batch-0", "B", [2, 1, 0], 500, 8, [4, 4, 1], iters=30, natural=True, kind="natural"),
@@ -281,6 +309,10 @@ def oracle_step(hp, lv, T12, dtype, failed=False):
     lim = torch.tensor([w - pad - 1, h - pad - 1], dtype=dtype)
     margin = float(torch.minimum((p2d - pad).abs().min(-1).values, (lim - p2d).abs().min(-1).values).min())
     valid = visible & O.mask_in_image(p2d, w, h, pad)
+    p_cam = O.pose_transform(R, t, p3d).double().numpy()
+    r2_margin = float(CC.r2_margin(cam[6:], p_cam).min())
+    in_img = torch.all((p2d >= 0) & (p2d <= cam[:2] - 1), -1) & torch.from_numpy(p_cam[:, 2] > O.CAM_EPS)
+    beyond_range = int((in_img & ~visible).sum())  # inside the image, in front of the camera, outside the model's range
     if hp["mask"] is not None:
         valid = valid & hp["mask"]
     assert int(valid.sum()) == n_valid
@@ -294,7 +326,7 @@ def oracle_step(hp, lv, T12, dtype, failed=False):
     outside = (i0[:, 0] - 1 < 0) | (i0[:, 0] + 2 > w - 1) | (i0[:, 1] - 1 < 0) | (i0[:, 1] + 2 > h - 1)
     return dict(delta=delta.double().numpy(), g=g.double().numpy(), H=H.double().numpy(), n_valid=n_valid, cost=cost,
                 failed=failed or n_valid < hp["conf"].min_valid, margin=margin, readers=int((valid & outside).sum()),
-                t_norm=float(t.double().norm()), g_terms=g_terms)
+                t_norm=float(t.double().norm()), g_terms=g_terms, r2_margin=r2_margin, beyond_range=beyond_range)
 
 
 def compose64(delta, T12):
@@ -347,6 +379,7 @@ def replay(hp, res, native_conf):
             want = oracle_step(hp, lv, T_prev, torch.float64, failed)
             where = (case["name"], lv["level"], it)
             assert want["margin"] >= FAIR_MARGIN, f"unfair seed: a point {want['margin']:.2e} px from the border at {where}"
+            assert want["r2_margin"] >= FAIR_R2_MARGIN, f"unfair seed: a point {want['r2_margin']:.2e} from the range limit at {where}"
             assert float(row[1]) == want["n_valid"], (where, float(row[1]), want["n_valid"])
             assert row[5] == 0.0, (where, "Cholesky failed")
             d64 = want["delta"]
@@ -495,7 +528,8 @@ def simulate(hp):
             a = oracle_step(hp, lv, T, torch.float32, failed)
             b = oracle_step(hp, lv, T, torch.float64, failed)
             d = float(np.linalg.norm(b["delta"]))
-            rec = dict(level=lv["level"], it=it, d=d, margin=b["margin"], readers=b["readers"], n_valid=b["n_valid"],
+            rec = dict(level=lv["level"], it=it, d=d, margin=b["margin"], r2_margin=b["r2_margin"],
+                       beyond_range=b["beyond_range"], readers=b["readers"], n_valid=b["n_valid"],
                        same_validity=a["n_valid"] == b["n_valid"], failed=b["failed"],
                        step_err=float(np.linalg.norm(a["delta"] - b["delta"])), cost=float("nan"), gnorm=float("nan"),
                        gterms=float("nan"))
@@ -542,7 +576,8 @@ if __name__ == "__main__":
         iters = [sum(r["level"] == l for r in recs) for l in case["levels"]]
         margin = min(r["margin"] for r in recs)
         for r in recs:
-            assert r["same_validity"] and r["margin"] >= FAIR_MARGIN, ("unfair seed", case["name"], r)
+            assert r["same_validity"] and r["margin"] >= FAIR_MARGIN and r["r2_margin"] >= FAIR_R2_MARGIN, \
+                ("unfair seed", case["name"], r)
             big_step = r["d"] >= BIG_STEP or r["failed"]  # (a masked step: |g| is that of the pose the level started at)
             if r["n_valid"] > 0:
                 worst["cost"] = max(worst["cost"], r["cost"])
@@ -565,6 +600,9 @@ if __name__ == "__main__":
             assert iters == [1, 0, 0] and recs[0]["failed"] and recs[0]["n_valid"] < 10, (case["name"], iters)
         elif case["kind"] == "border":
             assert iters == [1] and recs[0]["readers"] > 0 and not recs[0]["failed"], (case["name"], recs[0])
+            if case["scene"] == "k2_limit":  # in-image points beyond the range exist: n_valid is exact only if they drop out
+                print(f"{'':28s} {recs[0]['beyond_range']} points inside the image and beyond the range")
+                assert recs[0]["beyond_range"] >= 20, (case["name"], recs[0])
         else:
             assert not recs[-1]["failed"] and all(1 <= n < case["iters"] for n in iters), (case["name"], iters)
     # every row of the accumulation matrix is populated

@@ -9,13 +9,16 @@ The point gate projects with the LM's project_point, which the compiler contract
 whose projection lies within 1e-3 px of a texel boundary (a half-integer coordinate) is *fragile* and left out of the
 comparison; at most 2 % of a case may be.  The seeded inputs keep the reference itself under that cap (about 0.4 %, the
 share of a 2e-3 px band in a texel for uniform projections - asserted below, on the host) and place no point within
-1e-3 px of the edge of project_point's image test."""
+1e-3 px of the edge of project_point's image test.  The gate also runs under two cameras of tests/camera_cases.py:
+OPENCV (ndist 4) and a range limit inside the image, where points beyond the range land on occluder texels and must
+be kept."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
+import camera_cases as CC
 from pixtrack_amd import _lib, ops
 from pixtrack_amd import occlusion as OC
 
@@ -216,18 +219,19 @@ CAM10 = [float(PW), float(PH), 190.0, 185.0, 79.5, 59.5, -0.12, 0.0, 0.0, 0.0]
 NDIST = 2
 
 
-def point_inputs(n, seed):
+def point_inputs(n, seed, cam10=None):
     """n points seen from a seeded pose: a tenth behind the camera, the rest in a frustum one and a half times as wide
     as the image; a mask that keeps four in five; an occluder plane of two rectangles and a little salt."""
     from scipy.spatial.transform import Rotation
 
+    cam10 = CAM10 if cam10 is None else cam10
     rng = np.random.default_rng(seed)
     Rm = Rotation.from_rotvec(rng.normal(size=3) * 0.4).as_matrix()
     t = rng.normal(size=3) * 0.3 + np.array([0.0, 0.0, 2.0])
     z = rng.uniform(1.0, 3.0, size=n)
     z[rng.random(n) < 0.1] *= -1.0
-    xn = rng.uniform(-1.5, 1.5, size=n) * (PW / 2) / CAM10[2]
-    yn = rng.uniform(-1.5, 1.5, size=n) * (PH / 2) / CAM10[3]
+    xn = rng.uniform(-1.5, 1.5, size=n) * (PW / 2) / cam10[2]
+    yn = rng.uniform(-1.5, 1.5, size=n) * (PH / 2) / cam10[3]
     pc = np.stack([xn * z, yn * z, z], 1)
     X = ((pc - t) @ Rm).astype(np.float32)  # R^T (p - t)
     T12 = np.concatenate([Rm.reshape(-1), t]).astype(np.float32)
@@ -266,6 +270,54 @@ def test_points_match_the_restatement(device, n, with_mask):
     n_in = n if vin is None else int(vin.sum())
     assert words[8:11].tolist() == [n, n_in, int(got.sum())]  # exact given the output bits
     assert (words[:8] == SENTINEL).all() and (words[11:] == SENTINEL).all()  # the mask call's words stay
+    if not fragile.any():
+        assert words[8:11].tolist() == list(ref["counts"])
+
+
+# two cameras of tests/camera_cases.py at this plane's size (focal lengths and principal points halved): OPENCV, and
+# the k1 > 0 range limit, whose radius (78 px from the principal point, distorted) lies inside the image - a point beyond
+# it does not project, so the plane must not gate it, whatever texel its (u, v) would name
+TABLE_CAMERAS = {
+    "opencv": ([float(PW), float(PH), 192.0, 189.5, 77.75, 62.0, -0.08, 0.03, 0.004, -0.007], 4),
+    "k1_limit": ([float(PW), float(PH), 96.0, 96.0, 78.75, 60.75, 0.9, 0.0, 0.0, 0.0], 2),
+}
+
+
+@pytest.mark.parametrize("n", (65, 4097))
+@pytest.mark.parametrize("name", list(TABLE_CAMERAS))
+def test_points_match_the_restatement_on_the_camera_table(device, name, n):
+    cam10, ndist = TABLE_CAMERAS[name]
+    assert cam10[6:6 + ndist] == CC.CAMERAS[name]["params"][-ndist:] and ndist == CC.NDIST[name]
+    X, T12, valid, occ = point_inputs(n, 5500 + n, cam10)
+    ref = OC.points_visible_reference(X, valid, T12, (cam10, ndist), occ)
+    T = T12.astype(np.float64)
+    pc = X.astype(np.float64) @ T[:9].reshape(3, 3).T + T[9:]
+    at_limit = CC.r2_margin(cam10[6:6 + ndist], pc) <= CC.R2_REL_MARGIN
+    fragile = ref["fragile"] | at_limit
+    assert fragile.sum() <= 0.02 * n and not ref["near_edge"].any()
+    with np.errstate(all="ignore"):
+        xt, yt = np.floor(ref["u"] + 0.5), np.floor(ref["v"] + 0.5)
+        lands = (pc[:, 2] > 1e-3) & ~ref["projects"] & (ref["u"] >= 0) & (ref["v"] >= 0) & (ref["u"] <= PW - 1) & (ref["v"] <= PH - 1)
+        lands &= occ[np.where(lands, yt, 0).astype(int), np.where(lands, xt, 0).astype(int)] != 0
+    lands &= valid != 0
+    if n >= 1025:
+        assert ref["gated"].sum() > n // 20 and (~ref["projects"]).sum() > n // 10 and (ref["valid"] != 0).sum() > n // 10
+        if name in CC.LIMIT_CASES:  # beyond the range, inside the image, over an occluder texel: kept
+            assert lands.sum() >= 10, lands.sum()
+    d_occ = torch.from_numpy(occ).to(device)
+    rec = torch.full((OC.RECORD,), SENTINEL, dtype=torch.int32, device=device)
+    out_all = torch.full((n + TAIL,), CANARY, dtype=torch.uint8, device=device)
+    out = out_all[:n]
+    got, _ = OC.points_visible(torch.from_numpy(X).to(device).reshape(n, 3), torch.from_numpy(valid).to(device), T12,
+                               (cam10, ndist), d_occ, record=rec, valid=out)
+    torch.cuda.synchronize()
+    got = got.cpu().numpy()
+    words = rec.cpu().numpy()
+    assert (out_all[n:] == CANARY).all() and set(np.unique(got)) <= {0, 1}
+    keep = ~fragile
+    assert np.array_equal(got[keep], ref["valid"][keep]), np.nonzero(got[keep] != ref["valid"][keep])
+    assert (got[lands & keep] == 1).all()
+    assert words[8:11].tolist() == [n, int(valid.sum()), int(got.sum())]
     if not fragile.any():
         assert words[8:11].tolist() == list(ref["counts"])
 

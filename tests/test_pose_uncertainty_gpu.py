@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+import camera_cases as CC
 from oracle import lm_oracle as O
 from pixtrack_amd import _lib
 from pixtrack_amd.geometry import Pose, to_object_frame
@@ -49,8 +50,12 @@ SCENES = {
     # the object overfills the image: a good part of the points projects outside the padded border at every level, so
     # the kernel's own validity rule (and the clamped reads of the points it rejects) decides n_valid
     "cropped": dict(seed=1305, width=320, height=240, n_points=2048, fill=1.5),
+    # the camera table (tests/camera_cases.py): OPENCV, whose p1 / p2 enter the point and four terms of its Jacobian, and
+    # a range limit (k2 > 0 branch) inside an overfilled image - points beyond it are in the image and must not count
+    "opencv": dict(seed=1303, width=320, height=240, n_points=1500, sigma_px=2.0, **CC.SCENE_KW["opencv"]),
+    "k2_limit": dict(seed=1305, width=320, height=240, n_points=2048, **CC.SCENE_KW["k2_limit"]),
 }
-LEAVES_THE_VIEW = {"cropped": (0.4, 0.9)}  # scene -> the share of points that must be valid lies in this range
+LEAVES_THE_VIEW = {"cropped": (0.4, 0.9), "k2_limit": (0.3, 0.6)}  # scene -> the share of points that must be valid lies in this range
 LOSSES = {"squared": (0, 2.0, 1.0), "huber": (1, 0.0, 0.1), "barron": (2, 0.0, 0.1)}
 PAD = 1
 
@@ -105,7 +110,8 @@ def oracle_sums(fmap, fref, Cc, cam, p3d, pose12, loss, mask, dtype, pad=PAD):
     margin = torch.minimum((p2d - pad).abs().min(-1).values, (lim - p2d).abs().min(-1).values)
     return {"rho": float((v * rho).sum()), "n": int(valid.sum()), "wr2": float((weights * cost).sum()),
             "w": float(weights.sum()), "g": g.double().numpy(), "H": H.double().numpy(), "valid": valid.numpy(),
-            "margin": float(margin.min())}
+            "margin": float(margin.min()),
+            "r2_margin": float(CC.r2_margin(cam_t[6:], O.pose_transform(R, t, pts).double().numpy()).min())}
 
 
 def rel(a, b):
@@ -203,7 +209,10 @@ def scenes(device, dv):
 # ------------------------------------------------------------------------------------------------ 1. the oracle
 # (the cropped scene at its initial pose only: that pose is known on the CPU, where its seed was checked - the nearest
 # point is 2.3e-3 px from a border; where the LM's refined pose puts the border points is the device's business)
-ORACLE_POSES = {"cropped": ("init",)}
+# (opencv at its initial pose only as well: at the refined pose of its finest level g is what is left of cancelling terms
+# and the float32 oracle itself is 1.0e-3 off in g - four times F32_ORACLE_WORST, a bar that would hold nothing; the
+# tangential terms of the Jacobian are held where g is large)
+ORACLE_POSES = {"cropped": ("init",), "k2_limit": ("init",), "opencv": ("init",)}
 CASES = [(s, l, p, "barron") for s in SCENES for l in (0, 1, 2) for p in ORACLE_POSES.get(s, ("init", "refined"))] + \
         [("qvga", l, "init", k) for l in (0, 1, 2) for k in ("squared", "huber")]
 
@@ -216,6 +225,7 @@ def test_record_matches_the_float64_oracle(dv, scenes, scene, level, which, loss
     rec = information(dv, [S["dev"][level]], [pose], LOSSES[loss])[0].cpu().numpy()
     want = oracle_sums(fmap, fref, Cc, cam, S["scene"].p3d, pose, LOSSES[loss], S["mask"], torch.float64)
     assert want["margin"] > 1e-3, f"a point sits within 1e-3 px of the border ({want['margin']}): the seed is unfair"
+    assert want["r2_margin"] > CC.R2_REL_MARGIN, f"a point sits at the range limit ({want['r2_margin']}): the seed is unfair"
     assert want["n"] > 500
     if scene in LEAVES_THE_VIEW:
         lo, hi = LEAVES_THE_VIEW[scene]
@@ -459,7 +469,7 @@ if __name__ == "__main__":
                     same = bool((a["valid"] == b["valid"]).all())
                     worst = max(worst, max(errs.values()))
                     print(f"{name:7s} L{level} {which:7s} {lname:7s} n {a['n']:5d}/{b['n']:5d} same_validity {same} "
-                          f"margin {b['margin']:.4f} " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+                          f"margin {b['margin']:.4f} r2 margin {b['r2_margin']:.1e} " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
     print("worst float32-vs-float64 relative error:", worst)
     sc, p3d, a_, c_ = line_scene()
     fmap, _f, Cc, cam = pack_level(sc, 1)

@@ -70,8 +70,27 @@ def tiles_info(net, sizes):
     return tuple(int(x) for x in info)
 
 
-def pair_problem(net, device, hw, margin, ref_hw=None):
-    """Two random images (the reference of ``ref_hw``, the query of ``hw``) and their records."""
+def table_camera(name, fw, fh):
+    """-> (10 floats, ndist): the camera `name` of tests/camera_cases.py scaled to an fw x fh map."""
+    import camera_cases as CC
+    from pixtrack_amd.geometry import Camera
+
+    cam = Camera.from_colmap(CC.colmap(name)).scale((fw / CC.WIDTH, fh / CC.HEIGHT))
+    return [float(x) for x in cam.as10()], CC.NDIST[name]
+
+
+def behind_pinhole(xyz, cam10):
+    """Points given as (u, v, z) with pixel coordinates of a unit camera -> camera-frame points whose PINHOLE projection
+    through cam10 is (u, v): the distortion then moves them by a fraction of a texel."""
+    xyz = np.asarray(xyz, np.float64)
+    z = xyz[:, 2]
+    return np.ascontiguousarray(np.stack([(xyz[:, 0] - cam10[4]) / cam10[2] * z, (xyz[:, 1] - cam10[5]) / cam10[3] * z, z],
+                                         1).astype(np.float32))
+
+
+def pair_problem(net, device, hw, margin, ref_hw=None, camera=None):
+    """Two random images (the reference of ``ref_hw``, the query of ``hw``) and their records.  ``camera``: a name of
+    tests/camera_cases.py - the query's record carries that camera (scaled to the fine map) in place of the unit one."""
     H, W = hw
     g = torch.Generator().manual_seed(H * 7 + W)
     images = [(torch.rand(h, w, 3, generator=g) * 255).to(device).contiguous() for h, w in (ref_hw or hw, hw)]
@@ -83,8 +102,12 @@ def pair_problem(net, device, hw, margin, ref_hw=None):
                                                for _ in range(40)], np.float32))
     first = {"p3d": torch.from_numpy(ref_xyz).to(device), "ints": [0, 0, 0, 0, 0, 0],
              "pose_camera": IDENTITY + [float(rw), float(rh), 1.0, 1.0, 0.0, 0.0, 0, 0, 0, 0]}
-    second = {"p3d": torch.from_numpy(xyz).to(device), "ints": [0, 4, 0, 0, 0, 0, margin],
-              "pose_camera": IDENTITY + [float(fw), float(fh), 1.0, 1.0, 0.0, 0.0, 0, 0, 0, 0]}
+    cam10, ndist = [float(fw), float(fh), 1.0, 1.0, 0.0, 0.0, 0, 0, 0, 0], 0
+    if camera is not None:
+        cam10, ndist = table_camera(camera, fw, fh)
+        xyz = behind_pinhole(xyz, cam10)
+    second = {"p3d": torch.from_numpy(xyz).to(device), "ints": [ndist, 4, 0, 0, 0, 0, margin],
+              "pose_camera": IDENTITY + cam10}
     return images, xyz, first, second
 
 
@@ -92,12 +115,12 @@ def same_bits(maps_a, maps_b):
     return all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(maps_a, maps_b))
 
 
-def check_pair_pass(net, device, hw, margin, ref_hw=None, uses_record=True):
+def check_pair_pass(net, device, hw, margin, ref_hw=None, uses_record=True, camera=None):
     """The pair pass with the query's record against the dense one.  ``uses_record`` False: a pass that has to compute
     every tile (one batched pass) - it says so, and the map is the dense pass's throughout."""
     H, W = hw
     sizes = [ref_hw or hw, hw]
-    images, xyz, first, second = pair_problem(net, device, hw, margin, ref_hw)
+    images, xyz, first, second = pair_problem(net, device, hw, margin, ref_hw, camera)
     fh, fw = net.level_shapes(H, W)[0]
     net.set_query_tiles(False)
     try:
@@ -118,8 +141,13 @@ def check_pair_pass(net, device, hw, margin, ref_hw=None, uses_record=True):
     # the device flags are the host replica's, which is the rule's restatement (tests/test_query_tiles.py)
     assert used == 1
     dev_flags = ws[off:off + per_row * n_rows].cpu().numpy().reshape(n_rows, per_row)
-    want = replica_fine(xyz, fh, fw, margin)
-    host, _ = host_flags(record(xyz, margin, (0, 0, fw, fh), False), fh, fw)
+    rec = record(xyz, margin, (0, 0, fw, fh), False)
+    if camera is None:
+        want = replica_fine(xyz, fh, fw, margin)
+    else:  # (the host statement against a float64 restatement on this camera: tests/test_projection_host.py)
+        rec.points.cam[:], rec.points.ndist = table_camera(camera, fw, fh)
+        want, _ = host_flags(rec, fh, fw)
+    host, _ = host_flags(rec, fh, fw)
     assert np.array_equal(host, want) and np.array_equal(dev_flags, want)
     assert 0 < want.sum() < want.size
     # every flagged tile is the dense pass's, bit for bit; every other record is still NaN
@@ -136,6 +164,13 @@ def check_pair_pass(net, device, hw, margin, ref_hw=None, uses_record=True):
 @pytest.mark.parametrize("hw,margin", [((76, 100), 4), ((76, 100), 0), ((48, 64), 4)])
 def test_pair_pass_with_the_query_record_equals_the_dense_pass_on_its_tiles(net, device, hw, margin):
     check_pair_pass(net, device, hw, margin)
+
+
+@pytest.mark.gpu
+def test_pair_pass_under_the_opencv_camera(net, device):
+    """The smallest image of this file, the query's record carrying the OPENCV camera (ndist 4): the device's flags are
+    the host statement's, every flagged tile is the dense pass's bit for bit, no other tile is written."""
+    check_pair_pass(net, device, (48, 64), 4, camera="opencv")
 
 
 @pytest.mark.gpu
@@ -195,24 +230,35 @@ def smooth_map(h, w, C, cs, stride, seed):
     return m, g
 
 
-def lm_problem(n, device):
+def lm_problem(n, device, cam10=None, ndist=0):
+    """``cam10`` / ``ndist``: the fine level's camera in place of the unit one; the points are then camera-frame points
+    whose pinhole projections are the same pixels, and the references are the maps' functions at their float64
+    projections through the whole model (the identity pose is the optimum, as with the unit camera)."""
     rng = np.random.default_rng(n)
     # (their footprints stay right of x = 17, and the margin-8 tiles of case (b) leave the last column of tiles out)
     xy = np.stack([rng.uniform(21, 34, n), rng.uniform(12, 30, n)], 1)
     xy[0] = KNOWN
     p3d = np.concatenate([xy, np.ones((n, 1))], 1).astype(np.float32)
+    if cam10 is not None:
+        from oracle import lm_oracle as O
+
+        p3d = behind_pinhole(p3d, cam10)
+        uv, ok = O.world2image(torch.tensor(cam10[:6 + ndist], dtype=torch.float64), torch.from_numpy(p3d).double())
+        assert bool(ok.all())
+        xy = uv.numpy()
     fine, g_fine = smooth_map(FH, FW, 32, 36, 1, 11)
     coarse, g_coarse = smooth_map(FH // 4, FW // 4, 128, 132, 4, 12)
     fref_f = np.zeros((n, 36), np.float32)
-    fref_f[:, :32], fref_f[:, 32] = g_fine(p3d[:, 0], p3d[:, 1]), 1.0
+    fref_f[:, :32], fref_f[:, 32] = g_fine(xy[:, 0], xy[:, 1]), 1.0
     fref_c = np.zeros((n, 132), np.float32)
-    fref_c[:, :128], fref_c[:, 128] = g_coarse(p3d[:, 0], p3d[:, 1]), 1.0
+    fref_c[:, :128], fref_c[:, 128] = g_coarse(xy[:, 0], xy[:, 1]), 1.0
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
     return {"p3d": t(p3d), "xyz": p3d, "fine": t(fine), "coarse": t(coarse), "fref_f": t(fref_f), "fref_c": t(fref_c)}
 
 
-def lm_launch(prob, path, fine_map=None, flags=None):
-    """The C = 128 level without flags, then the fine level; -> (record [NH], log [2, iters, 20], camera record [13])."""
+def lm_launch(prob, path, fine_map=None, flags=None, cam10=None, ndist=0, T0=None):
+    """The C = 128 level without flags, then the fine level; -> (record [NH], log [2, iters, 20], camera record [13]).
+    ``cam10`` / ``ndist``: the fine level's camera (the coarse level's is its quarter, as with the unit camera)."""
     from pixtrack_amd.ops import ops
 
     dev = prob["p3d"].device
@@ -221,11 +267,13 @@ def lm_launch(prob, path, fine_map=None, flags=None):
     cam_out = torch.zeros(16, dtype=torch.float32).pin_memory()
     ws = torch.zeros(int(_lib.lib().pxt_lm_workspace_bytes()), dtype=torch.uint8, device=dev)
     cams = [FW / 4, FH / 4, 0.25, 0.25, 0.0, 0.0, 0, 0, 0, 0, float(FW), float(FH), 1.0, 1.0, 0.0, 0.0, 0, 0, 0, 0]
+    if cam10 is not None:
+        cams = [FW / 4, FH / 4] + [x / 4 for x in cam10[2:6]] + list(cam10[6:]) + list(cam10)
     conv27 = [0.0, 0.0, 0.0, 1.0] + [1.0 if i % 5 == 0 else 0.0 for i in range(16)] + [0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
-    T0 = IDENTITY[:9] + [SHIFT[0], SHIFT[1], 0.0]
+    T0 = IDENTITY[:9] + [SHIFT[0], SHIFT[1], 0.0] if T0 is None else T0
     guard = (-1, None, None) if flags is None else (1, flags, [TILE, FW // 16, 0, 0])
     ops.lm_refine(prob["p3d"], None, [prob["coarse"], prob["fine"] if fine_map is None else fine_map],
-                  [prob["fref_c"], prob["fref_f"]], [128, 32], cams, [0, 0], [0.01] * 12, T0, num_iters, 2, 0, 0.0, 1.0,
+                  [prob["fref_c"], prob["fref_f"]], [128, 32], cams, [ndist, ndist], [0.01] * 12, T0, num_iters, 2, 0, 0.0, 1.0,
                   1e-9, 1e-4, 1e-4, 10, 0, rec, ws, True, 0, conv27, None, cam_out, path, *guard)
     torch.cuda.synchronize()
     r = rec.numpy().copy()
@@ -290,6 +338,33 @@ def test_lm_tile_guard(device, n, path):
     assert np.array_equal(log[1, :k].view(np.uint32), plain_log[1, :k].view(np.uint32))
     before = plain_log[1, k - 1, 8:20] if k > 0 else plain_log[0, it_c - 1, 8:20]
     assert np.array_equal(head[:12].view(np.uint32), before.view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", [0, 2])
+def test_lm_tile_guard_reports_nothing_under_the_opencv_camera(device, path):
+    """Case (b) above with the OPENCV camera (ndist 4) on the fine level: the flags of the marking rule at the start pose
+    (margin 8), the map NaN wherever they are 0.  The marking and the LM project through the same project_point, so the
+    guard reports no unmarked tile and the run is the all-flags run bit for bit."""
+    cam10, ndist = table_camera("opencv", FW, FH)
+    n = 64
+    prob = lm_problem(n, device, cam10, ndist)
+    T0 = IDENTITY[:9] + [SHIFT[0] / cam10[2], SHIFT[1] / cam10[3], 0.0]  # (3, 2) fine pixels at z = 1
+    ones = torch.ones(FH // TILE, FW // 16, dtype=torch.uint8, device=device)
+    a = lm_launch(prob, path, flags=ones, cam10=cam10, ndist=ndist, T0=T0)
+    assert a[0][12] == 0 and a[0][13] == 0 and a[0][15] == 1 and not a[1][:, :, 6].any()
+    assert int(a[0][16]) >= 1 and int(a[0][17]) >= 2
+    pts = record(prob["xyz"], 8, (0, 0, FW, FH), False, pad=2)
+    pts.points.T[:] = T0
+    pts.points.cam[:], pts.points.ndist = cam10, ndist
+    host, _ = host_flags(pts, FH, FW)
+    assert 0 < host.sum() < host.size
+    holes = prob["fine"].clone()
+    mask = torch.from_numpy(np.repeat(np.repeat(host, TILE, 0), TILE, 1)[:FH, :FW].astype(bool)).to(device)
+    holes[~mask] = float("nan")
+    b = lm_launch(prob, path, fine_map=holes, flags=torch.from_numpy(host).to(device), cam10=cam10, ndist=ndist, T0=T0)
+    assert b[0][13] == 0 and not b[1][:, :, 6].any()  # the guard reports no unmarked tile
+    assert all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(b, a))
 
 
 # ---- the tracker ---------------------------------------------------------------------------------------------------------

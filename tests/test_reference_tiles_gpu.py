@@ -143,8 +143,9 @@ def run_pass(net, image, sample_points, poison):
     return outs
 
 
-def sample(maps, p3d, pad, window):
-    """pxt_sample_sparse of the three levels with the unit cameras; window = (x0, y0, full_w, full_h) of the fine level."""
+def sample(maps, p3d, pad, window, camera=None):
+    """pxt_sample_sparse of the three levels with the unit cameras; window = (x0, y0, full_w, full_h) of the fine level.
+    camera = (geometry.Camera of the fine level, ndist): that camera, scaled to each level, in place of the unit ones."""
     from pixtrack_amd.ops import ops
     from pixtrack_amd.unet import OUTPUT_DIMS
 
@@ -152,12 +153,16 @@ def sample(maps, p3d, pad, window):
     cams, windows = [], []
     for m, s in zip(maps, (1, 4, 16)):
         full_w, full_h = (window[2] // s, window[3] // s) if window else (int(m.shape[1]), int(m.shape[0]))
-        cams += [float(full_w), float(full_h), 1.0 / s, 1.0 / s, 0.0, 0.0, 0, 0, 0, 0]
+        if camera is not None:
+            cams += [float(x) for x in camera[0].scale((full_w / float(camera[0].size[0]), full_h / float(camera[0].size[1]))).as10()]
+        else:
+            cams += [float(full_w), float(full_h), 1.0 / s, 1.0 / s, 0.0, 0.0, 0, 0, 0, 0]
         if window:
             windows += [window[0] // s, window[1] // s, full_w, full_h]
     outs = [torch.full((n, int(m.shape[2])), 5.0, device=p3d.device) for m in maps]
     valid = torch.full((n,), 7, dtype=torch.uint8, device=p3d.device)
-    ops.sample_sparse(p3d, IDENTITY, list(maps), list(OUTPUT_DIMS), cams, [0, 0, 0], pad, True, outs, valid, windows or None)
+    ndist = [0, 0, 0] if camera is None else [camera[1]] * 3
+    ops.sample_sparse(p3d, IDENTITY, list(maps), list(OUTPUT_DIMS), cams, ndist, pad, True, outs, valid, windows or None)
     return outs, valid
 
 
@@ -218,6 +223,63 @@ def test_sampled_pass_equals_the_dense_pass_where_it_is_read(net, device, hw, pa
         assert bool(torch.isfinite(b).all()) and torch.equal(a, b)
     fine_valid = (outs_d[0] != 0).any(1)
     assert int(fine_valid.sum()) >= 20 and not bool(fine_valid.all())
+
+
+@pytest.mark.gpu
+def test_sampled_pass_equals_the_dense_pass_under_the_opencv_camera(net, device):
+    """The smallest pyramid (32 x 32: two by two fine tiles) under the OPENCV camera of tests/camera_cases.py scaled to
+    the fine map (ndist 4: project_point's tangential terms decide the texels): the marked tiles are those the host
+    statement of the rule names with the same record, the sampled observations are the dense pass's bit for bit, and no
+    unmarked tile is written."""
+    import camera_cases as CC
+    from pixtrack_amd.geometry import Camera
+
+    H, W, pad = 32, 32, 0
+    image = (torch.rand(H, W, 3, generator=torch.Generator().manual_seed(H * 7 + W + 1)) * 255).to(device).contiguous()
+    fh, fw = net.level_shapes(H, W)[0]
+    cam = Camera.from_colmap(CC.colmap("opencv")).scale((fw / CC.WIDTH, fh / CC.HEIGHT))
+    cam10 = [float(x) for x in cam.as10()]
+    ndist = CC.NDIST["opencv"]
+    # camera-frame points whose pinhole projections fill the upper left tile and straddle its right seam; the distortion
+    # then moves them by a fraction of a texel; a few outside the map and behind the camera
+    rng = np.random.default_rng(41)
+    uv = np.concatenate([rng.uniform(0.5, 14.0, (40, 2)), np.stack([rng.uniform(14.5, 17.5, 12), rng.uniform(1.0, 12.0, 12)], 1),
+                         [[-3.0, 5.0], [fw + 2.0, 5.0], [5.0, fh + 0.5]]])
+    z = np.concatenate([rng.uniform(0.7, 1.6, len(uv) - 2), [-1.0, 0.0]])
+    uv = np.concatenate([uv[:-2], [[8.0, 8.0], [9.0, 9.0]]])
+    xyz = np.stack([(uv[:, 0] - cam10[4]) / cam10[2] * z, (uv[:, 1] - cam10[5]) / cam10[3] * z, z], 1).astype(np.float32)
+    xyz = np.ascontiguousarray(xyz)
+    p3d = torch.from_numpy(xyz).to(device)
+    points = {"p3d": p3d, "pose_camera": IDENTITY + cam10, "ints": [ndist, pad, 0, 0, 0, 0]}
+    net.set_reference_tiles(False)
+    try:
+        dense = run_pass(net, image, points, poison=True)
+    finally:
+        net.set_reference_tiles(True)
+    got = run_pass(net, image, points, poison=True)
+    pts = record(xyz.ctypes.data, len(xyz), pad, (0, 0, fw, fh), False)
+    pts.cam[:] = cam10
+    pts.ndist = ndist
+    want_fine = np.full((-(-fh // TILE), -(-fw // 16)), 9, np.uint8)
+    want_low = np.full((-(-(fh // 2) // TILE), -(-(fw // 2) // 16)), 9, np.uint8)
+    _lib.check(_lib.lib().pxt_unet_reference_tiles_host(C.byref(pts), fh, fw, TILE, TILE, want_fine.ctypes.data,
+                                                        want_low.ctypes.data), "pxt_unet_reference_tiles_host")
+    assert 0 < want_fine.sum() < want_fine.size, want_fine
+    assert torch.equal(got[1], dense[1]) and torch.equal(got[2], dense[2])
+    for r in range(want_fine.shape[0]):
+        for c in range(want_fine.shape[1]):
+            a = got[0][r * TILE:(r + 1) * TILE, c * TILE:(c + 1) * TILE]
+            if want_fine[r, c]:
+                assert torch.equal(a, dense[0][r * TILE:(r + 1) * TILE, c * TILE:(c + 1) * TILE]), (r, c)
+            else:
+                assert bool((a == SENTINEL).all()), (r, c)
+    outs_d, valid_d = sample(dense, p3d, pad, None, camera=(cam, ndist))
+    outs_g, valid_g = sample(got, p3d, pad, None, camera=(cam, ndist))
+    assert torch.equal(valid_d, valid_g)
+    for a, b in zip(outs_d, outs_g):
+        assert bool(torch.isfinite(b).all()) and torch.equal(a, b)
+    fine_valid = (outs_d[0] != 0).any(1)
+    assert int(fine_valid.sum()) >= 40 and not bool(fine_valid.all())
 
 
 @pytest.mark.gpu

@@ -1,5 +1,7 @@
 """The relocaliser on the device: pxt_score_pose_hypotheses against a float64 CPU restatement and against the LM's own
-first logged cost, its determinism, and relocalisation / lost-track recovery on the synthetic assets."""
+first logged cost, its determinism, and relocalisation / lost-track recovery on the synthetic assets.  The restatement
+runs on the SIMPLE_RADIAL bank and, with the same hypothesis recipe, on an OPENCV bank and on a bank whose camera has its
+range limit inside the image (tests/camera_cases.py)."""
 import ctypes as C
 import math
 
@@ -7,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import camera_cases as CC
 from oracle import lm_oracle as O
 from pixtrack_amd import _lib
 from pixtrack_amd.geometry import Pose
@@ -36,9 +39,8 @@ def _pack(scene, level, device):
     return fmap, fref, Cc, scene.camera.scale(scene.scales[level])
 
 
-@pytest.fixture(scope="module")
-def scene_bank(device):
-    sc = make_lm_scene(seed=1201, width=320, height=240, n_points=1500, sigma_px=2.0, k1=-0.08)
+def _make_bank(device, **scene_kw):
+    sc = make_lm_scene(seed=1201, width=320, height=240, n_points=1500, sigma_px=2.0, **scene_kw)
     fmap, fref, Cc, cam = _pack(sc, LEVEL, device)
     rng = np.random.default_rng(12)
     n = sc.p3d.shape[0]
@@ -58,6 +60,17 @@ def scene_bank(device):
         ranges.append((begin, count))
     return dict(scene=sc, fmap=fmap, fref=fref, C=Cc, cam=cam, p3d=sc.p3d, valid=valid,
                 poses=np.asarray(poses, np.float64), ranges=np.asarray(ranges, np.int32))
+
+
+@pytest.fixture(scope="module")
+def scene_bank(device):
+    return _make_bank(device, k1=-0.08)
+
+
+@pytest.fixture(scope="module", params=["opencv", "k1_limit"])
+def table_bank(request, device):
+    """The same hypothesis recipe on a camera of tests/camera_cases.py: ndist 4, and a range limit inside the image."""
+    return request.param, _make_bank(device, **CC.SCENE_KW[request.param])
 
 
 def _launch(sb, device, loss=(2, 0.0, 0.1), pad=1, poses=None, ranges=None, out=None, fmap=None):
@@ -81,8 +94,9 @@ def _launch(sb, device, loss=(2, 0.0, 0.1), pad=1, poses=None, ranges=None, out=
 
 def _restatement(sb, loss_kind, alpha, scale, pad=1):
     """float64: the oracle's world2image / interpolator / make_loss over each hypothesis's valid points.  Returns the four
-    sums per hypothesis and, per hypothesis, how many points lie within 1e-3 px of the padded image border (where float32
-    and float64 may decide validity differently)."""
+    sums per hypothesis and, per hypothesis, how many points lie within 1e-3 px of the padded image border or within
+    relative 1e-5 (in r^2) of the distortion model's range limit (where float32 and float64 may decide validity
+    differently)."""
     name = {0: "squared", 1: "huber", 2: "barron"}[loss_kind]
     loss = O.make_loss(name) if loss_kind == 0 else O.make_loss(name, alpha, scale)
     fmap = sb["fmap"].double()
@@ -109,7 +123,8 @@ def _restatement(sb, loss_kind, alpha, scale, pad=1):
         ok = vis & inimg & valid[b:b + n]
         lim = torch.tensor([w - pad - 1, h - pad - 1], dtype=torch.float64)
         margin = torch.minimum((p2d - pad).abs().min(-1).values, (lim - p2d).abs().min(-1).values)
-        edge.append(int((vis & valid[b:b + n] & (margin < 1e-3)).sum()))
+        near_limit = torch.from_numpy(CC.r2_margin(cam[6:], pc.numpy()) <= CC.R2_REL_MARGIN)
+        edge.append(int((valid[b:b + n] & ((vis & (margin < 1e-3)) | near_limit)).sum()))
         r = F[:, :C_] - fref[b:b + n, :C_]
         rho = loss(((r * r).sum(-1)))[0]
         wgt = F[:, C_] * fref[b:b + n, C_]
@@ -131,6 +146,28 @@ def test_kernel_matches_float64_restatement(device, scene_bank, loss):
     for k in (0, 2, 3):
         # (atol: float32 cancellation in r = F_q - F_ref for near-identical descriptors; seen up to 2e-8 on sums of few points)
         np.testing.assert_allclose(got[exact, k], want[exact, k], rtol=1e-5, atol=1e-7)
+
+
+@pytest.mark.parametrize("loss", [(0, 2.0, 1.0), (1, 0.0, 0.1), (2, 0.0, 0.1)], ids=["squared", "huber", "barron"])
+def test_kernel_matches_float64_restatement_on_the_camera_table(device, table_bank, loss):
+    name, bank = table_bank
+    got = _launch(bank, device, loss).cpu().double().numpy()
+    want, edge = _restatement(bank, *loss)
+    assert (want[:, 1] == 0).sum() >= 10 and (want[:, 1] > 100).sum() >= 50  # the cases are there
+    exact = edge == 0
+    print(f"{name}: {int((~exact).sum())} of {len(edge)} hypotheses hold a point the two precisions may decide differently")
+    assert exact.mean() > 0.95, edge
+    np.testing.assert_array_equal(got[exact, 1], want[exact, 1])
+    assert np.all(np.abs(got[~exact, 1] - want[~exact, 1]) <= edge[~exact])
+    for k in (0, 2, 3):
+        np.testing.assert_allclose(got[exact, k], want[exact, k], rtol=1e-5, atol=1e-7)
+    if name in CC.LIMIT_CASES:
+        # hypotheses near the ground truth see points inside the image and beyond the range: they must not count
+        sc, cam = bank["scene"], bank["cam"]._data.double()
+        pc = torch.from_numpy(sc.p3d @ sc.R_gt.T + sc.t_gt)
+        p2d, vis = O.world2image(cam, pc)
+        in_img = torch.all((p2d >= 0) & (p2d <= cam[:2] - 1), -1)
+        assert int((in_img & ~vis).sum()) >= 10
 
 
 # ------------------------------------------------------------------------------------------------ 2. the LM's cost
