@@ -1238,6 +1238,47 @@ int pxt_mesh_render(const float* vertices, int32_t n_vertices, const int32_t* tr
                     float* out_rgba, uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz, int32_t* out_tri,
                     uint32_t* records, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Colour renders of a textured mesh: pxt_mesh_render with the colour read from a texture map through per-corner UVs,
+ * what the reference's render_image draws for the meshes load_objs_as_meshes gives it (YCB's textured.obj with
+ * texture_map.png; BOP's PLYs with texture_u / texture_v).  csrc/pxt_raster.hip; mesh_render.shade_textured_reference
+ * restates the rule in numpy and the two agree bit for bit on every output.
+ *
+ * Everything but the colour is pxt_mesh_render's: vertices, triangles, views, the five outputs and their rules, records,
+ * workspace, bounds and alignment; coverage, depth, out_depth, out_depth_nz, out_tri and records equal what
+ * pxt_mesh_raster and pxt_mesh_render write for the same mesh bit for bit.  In place of colors:
+ *   uvs [n_uvs][2] float32;   triangle_uvs [T][3] int32: corner k of triangle t uses uvs[triangle_uvs[t][k]] - corner
+ *   attributes, so a vertex on a seam may carry different UVs in different triangles;   texture [Ht][Wt][4] uint8: r, g,
+ *   b and a fourth byte that is ignored, one texel one aligned dword.
+ *
+ * The colour of a covered pixel whose winning triangle is t: the set-up, l_k, w_k and inv are pxt_mesh_render's (the UV
+ *   indices follow the exchange of the second and third corner when A < 0), and then, every step a single fp32 operation
+ *   with IEEE division,
+ *       u = ((w_0 u_0 + w_1 u_1) + w_2 u_2) / inv, v likewise;
+ *       x = u * (float)(Wt - 1);   y = (1.0f - v) * (float)(Ht - 1)   (row 0 of the map is v = 1);
+ *       x = fminf(fmaxf(x, 0), Wt - 1), y likewise   (a NaN becomes 0; the border texels continue outwards);
+ *       x0 = floorf(x), ax = x - x0, i0 = (int) x0, i1 = min(i0 + 1, Wt - 1);   j0, j1, ay from y likewise;
+ *       per channel, a texel's value being tau = (float) byte / 255.0f:
+ *       top = tau00 + ax (tau01 - tau00);   bot = tau10 + ax (tau11 - tau10);   c = top + ay (bot - top)
+ *       (tau_ji = texel (i_i, j_j));   c = fminf(fmaxf(c, 0), 1):
+ *   pytorch3d's TexturesUV with its defaults as render_image uses it - the map flipped vertically, align_corners=True,
+ *   bilinear, padding_mode="border".  No lighting term, no mip levels, no wrap mode: the reference has none.
+ * out_rgb_u8 truncates, (long long)(c * 255.0f) & 255: where (byte / 255.0f) * 255.0f rounds below the integer, the
+ *   byte written is one less than the texel's, even on a pixel that reads one texel alone.  The reference's
+ *   (image * 255).astype(uint8) does the same.
+ * A triangle with a vertex index outside [0, V) is never drawn; one with a UV index outside [0, n_uvs) shades black
+ *   (alpha 1, its depth and id as ever).  No address outside uvs or the texture is formed.
+ * Bounds in addition to pxt_mesh_render's: uvs, triangle_uvs and texture not NULL and 4-byte aligned, 1 <= n_uvs <= 2^24,
+ *   1 <= tex_width, tex_height <= 16384.  Anything else is PXT_E_ARG and nothing is launched or written.
+ * Four launches on `stream`: pxt_mesh_raster's first three unchanged, then pxt_mesh_render's resolve instantiated with
+ *   this shading rule.  No host synchronisation, no allocation.  Measured on the MI355X: DESIGN.md 3.17.
+ * ---------------------------------------------------------------------- */
+int pxt_mesh_render_textured(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                             const float* uvs, int32_t n_uvs, const int32_t* triangle_uvs, const uint8_t* texture,
+                             int32_t tex_width, int32_t tex_height, const float* views, int32_t n_views, int32_t width,
+                             int32_t height, float* out_rgba, uint8_t* out_rgb_u8, float* out_depth,
+                             uint8_t* out_depth_nz, int32_t* out_tri, uint32_t* records, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

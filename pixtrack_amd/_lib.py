@@ -368,6 +368,8 @@ PROTOTYPES = {
     "pxt_mesh_raster_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "pxt_mesh_raster": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     "pxt_mesh_render": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pxt_mesh_render_textured": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _I32, _I32, _I32,
+                                           _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 

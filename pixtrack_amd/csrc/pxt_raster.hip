@@ -1,5 +1,6 @@
 // Depth rasteriser for triangle meshes (pxt_mesh_raster, include/pixtrack_hip.h; pixtrack_amd/mesh_render.py), and
-// further down its colour resolve for meshes with vertex colours (pxt_mesh_render).
+// further down its colour resolve for meshes with vertex colours (pxt_mesh_render) or a texture map
+// (pxt_mesh_render_textured).
 //
 // The reference draws meshes with pytorch3d (pixtrack/utils/pytorch3d_render_utils.py:55-93, render_image) for its
 // YCB ground-truth renders; this is the depth part of that for the evaluation stack: BOP's VSD compares depth renders
@@ -356,8 +357,11 @@ __global__ __launch_bounds__(kRsBlock) void rs_resolve_kernel(const RsArgs a) {
 // ids), the 8-bit results meet in LDS, and then lane tid owns the four pixels g0 + 4 tid ..: bytes 12 (g0 / 4 + tid) of
 // the colour plane and 4 (g0 / 4 + tid) of the depth_nz plane, whole aligned dwords whatever W * H is.  A group of four
 // that a view shares with its neighbour (or that ends past the last view) is stored bytewise by each view's workgroup.
+// What differs between the two colour calls is the shading rule alone: Attr turns the winning triangle's exchanged
+// corners and their weights into r, g, b.  RsShade<RsVertexColors> is laid out as the one struct it replaced.
+template <class Attr>
 struct RsShade {
-  const float* colors;  // [V][3]
+  Attr attr;
   float* out_rgba;
   unsigned char* out_rgb_u8;
   unsigned char* out_nz;
@@ -367,10 +371,71 @@ constexpr int kRsShadePixels = kRsBlock * 4;
 
 __device__ __forceinline__ unsigned rs_u8(float c) { return (unsigned)((long long)(c * 255.0f) & 255); }
 
-// The colour of triangle t at pixel (i, j): set up as rs_setup does (the same rs_vertex, area and exchange; the colours
-// follow the exchange), no cull - t won the pixel, so it was drawn.  -> rgb, zeros if t cannot have been drawn.
-__device__ __forceinline__ void rs_shade(const RsArgs& a, const float* __restrict__ colors, const RsView& v, int t, int i,
-                                         int j, float* rgb) {
+// pxt_mesh_render's rule: the vertex colours of the exchanged corners idx, c = ((w_0 c_0 + w_1 c_1) + w_2 c_2) / inv.
+struct RsVertexColors {
+  const float* colors;  // [V][3]
+  __device__ __forceinline__ void operator()(int, const int* idx, bool, const float* w, float inv, float* rgb) const {
+    const float* c0 = colors + 3 * (size_t)idx[0];
+    const float* c1 = colors + 3 * (size_t)idx[1];
+    const float* c2 = colors + 3 * (size_t)idx[2];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float c = ((w[0] * c0[ch] + w[1] * c1[ch]) + w[2] * c2[ch]) / inv;
+      rgb[ch] = fminf(fmaxf(c, 0.f), 1.0f);  // a NaN -> 0
+    }
+  }
+};
+
+// pxt_mesh_render_textured's rule: the corner UVs of triangle t (exchanged as the vertices were), interpolated as the
+// colours are, then one bilinear read of the map: row 0 is v = 1, corners aligned, the border clamped (pytorch3d's
+// TexturesUV defaults).  A UV index outside [0, n_uvs) leaves the pixel black; no address outside uvs is formed, and
+// the clamps keep the four texels inside the map whatever u and v are.
+struct RsTexture {
+  const float* uvs;         // [n_uvs][2]
+  const int* triangle_uvs;  // [T][3]
+  const unsigned* texture;  // [Ht][Wt] dwords: r | g << 8 | b << 16 | ignored << 24
+  int n_uvs, Wt, Ht;
+
+  static __device__ __forceinline__ float coordinate(float x, int n, int* i0, int* i1) {
+    x = fminf(fmaxf(x, 0.f), (float)(n - 1));  // a NaN -> 0
+    const float x0 = floorf(x);
+    *i0 = (int)x0;
+    *i1 = min(*i0 + 1, n - 1);
+    return x - x0;
+  }
+
+  __device__ __forceinline__ void operator()(int t, const int*, bool exchanged, const float* w, float inv, float* rgb) const {
+    const int* f = triangle_uvs + 3 * (size_t)t;  // t < T: rs_shade checked it
+    const int k0 = f[0], k1 = exchanged ? f[2] : f[1], k2 = exchanged ? f[1] : f[2];
+    if ((unsigned)k0 >= (unsigned)n_uvs || (unsigned)k1 >= (unsigned)n_uvs || (unsigned)k2 >= (unsigned)n_uvs) return;
+    const float* a0 = uvs + 2 * (size_t)k0;
+    const float* a1 = uvs + 2 * (size_t)k1;
+    const float* a2 = uvs + 2 * (size_t)k2;
+    const float u = ((w[0] * a0[0] + w[1] * a1[0]) + w[2] * a2[0]) / inv;
+    const float v = ((w[0] * a0[1] + w[1] * a1[1]) + w[2] * a2[1]) / inv;
+    int i0, i1, j0, j1;
+    const float ax = coordinate(u * (float)(Wt - 1), Wt, &i0, &i1);
+    const float ay = coordinate((1.0f - v) * (float)(Ht - 1), Ht, &j0, &j1);
+    const unsigned* r0 = texture + (size_t)j0 * Wt;
+    const unsigned* r1 = texture + (size_t)j1 * Wt;
+    const unsigned t00 = r0[i0], t01 = r0[i1], t10 = r1[i0], t11 = r1[i1];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float c00 = (float)((t00 >> (8 * ch)) & 0xffu) / 255.0f, c01 = (float)((t01 >> (8 * ch)) & 0xffu) / 255.0f;
+      const float c10 = (float)((t10 >> (8 * ch)) & 0xffu) / 255.0f, c11 = (float)((t11 >> (8 * ch)) & 0xffu) / 255.0f;
+      const float top = c00 + ax * (c01 - c00);
+      const float bot = c10 + ax * (c11 - c10);
+      const float c = top + ay * (bot - top);
+      rgb[ch] = fminf(fmaxf(c, 0.f), 1.0f);
+    }
+  }
+};
+
+// The colour of triangle t at pixel (i, j): set up as rs_setup does (the same rs_vertex, area and exchange; the corner
+// attributes follow the exchange), no cull - t won the pixel, so it was drawn.  -> rgb, zeros if t cannot have been drawn.
+template <class Attr>
+__device__ __forceinline__ void rs_shade(const RsArgs& a, const Attr& attr, const RsView& v, int t, int i, int j,
+                                         float* rgb) {
   rgb[0] = rgb[1] = rgb[2] = 0.f;
   if ((unsigned)t >= (unsigned)a.T) return;
   const int* f = a.triangles + 3 * (size_t)t;
@@ -383,7 +448,8 @@ __device__ __forceinline__ void rs_shade(const RsArgs& a, const float* __restric
     if (rs_vertex(v, a.vertices + 3 * (size_t)idx[k], &x[k], &y[k], &iz[k]) != RS_DRAWN) return;
   long long area = (long long)(x[1] - x[0]) * (y[2] - y[0]) - (long long)(y[1] - y[0]) * (x[2] - x[0]);
   if (area == 0) return;
-  if (area < 0) {
+  const bool exchanged = area < 0;
+  if (exchanged) {
     const int tx = x[1], ty = y[1], ti = idx[1];
     const float tz = iz[1];
     x[1] = x[2]; y[1] = y[2]; iz[1] = iz[2]; idx[1] = idx[2];
@@ -401,17 +467,11 @@ __device__ __forceinline__ void rs_shade(const RsArgs& a, const float* __restric
     w[k] = l * iz[k];
   }
   const float inv = (w[0] + w[1]) + w[2];
-  const float* c0 = colors + 3 * (size_t)idx[0];
-  const float* c1 = colors + 3 * (size_t)idx[1];
-  const float* c2 = colors + 3 * (size_t)idx[2];
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float c = ((w[0] * c0[ch] + w[1] * c1[ch]) + w[2] * c2[ch]) / inv;
-    rgb[ch] = fminf(fmaxf(c, 0.f), 1.0f);  // a NaN -> 0
-  }
+  attr(t, idx, exchanged, w, inv, rgb);
 }
 
-__global__ __launch_bounds__(kRsBlock) void rs_shade_resolve_kernel(const RsArgs a, const RsShade o) {
+template <class Attr>
+__global__ __launch_bounds__(kRsBlock) void rs_shade_resolve_kernel(const RsArgs a, const RsShade<Attr> o) {
   __shared__ unsigned red[3][kRsWaves];
   __shared__ __attribute__((aligned(16))) unsigned packed[kRsShadePixels];  // r | g << 8 | b << 16 | depth_nz << 24
   const int view = blockIdx.y, tid = threadIdx.x;
@@ -445,7 +505,7 @@ __global__ __launch_bounds__(kRsBlock) void rs_shade_resolve_kernel(const RsArgs
         ++cnt;
         if (want_rgb) {
           const int pix = (int)(g - start);  // < 2^26
-          rs_shade(a, o.colors, v, t, pix % a.W, pix / a.W, rgb);
+          rs_shade(a, o.attr, v, t, pix % a.W, pix / a.W, rgb);
         }
       }
       const float alpha = cov ? 1.0f : 0.f;
@@ -512,7 +572,7 @@ __global__ __launch_bounds__(kRsBlock) void rs_shade_resolve_kernel(const RsArgs
 }
 
 constexpr int64_t kRsMaxPixels = (int64_t)1 << 26;
-constexpr int kRsMaxViews = 4096, kRsMaxCount = 1 << 24;
+constexpr int kRsMaxViews = 4096, kRsMaxCount = 1 << 24, kRsMaxTexture = 16384;
 
 bool rs_sizes_ok(int P, int T, int W, int H) {
   return P >= 1 && P <= kRsMaxViews && T >= 1 && T <= kRsMaxCount && W >= 1 && H >= 1 && (int64_t)W * H <= kRsMaxPixels;
@@ -567,14 +627,17 @@ extern "C" int pxt_mesh_raster(const float* vertices, int32_t n_vertices, const 
   return PXT_OK;
 }
 
-extern "C" int pxt_mesh_render(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
-                               const float* colors, const float* views, int32_t n_views, int32_t width, int32_t height,
-                               float* out_rgba, uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz,
-                               int32_t* out_tri, uint32_t* records, void* workspace, void* stream) {
+// The two colour calls: the shared argument checks, launches 1 to 3 as pxt_mesh_raster makes them and the resolve
+// instantiated for the call's shading rule.  `attr_ok` is the caller's verdict on its own arguments.
+template <class Attr>
+static int rs_render(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                     const Attr& attr, bool attr_ok, const float* views, int32_t n_views, int32_t width, int32_t height,
+                     float* out_rgba, uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz, int32_t* out_tri,
+                     uint32_t* records, void* workspace, void* stream) {
   if (!rs_sizes_ok(n_views, n_triangles, width, height) || n_vertices < 1 || n_vertices > kRsMaxCount) return PXT_E_ARG;
-  if (!vertices || !triangles || !colors || !views || !records || !workspace) return PXT_E_ARG;
+  if (!vertices || !triangles || !attr_ok || !views || !records || !workspace) return PXT_E_ARG;
   if (!out_rgba && !out_rgb_u8 && !out_depth && !out_depth_nz && !out_tri) return PXT_E_ARG;
-  if (((uintptr_t)vertices % 4) != 0 || ((uintptr_t)triangles % 4) != 0 || ((uintptr_t)colors % 4) != 0 ||
+  if (((uintptr_t)vertices % 4) != 0 || ((uintptr_t)triangles % 4) != 0 ||
       ((uintptr_t)views % 4) != 0 || ((uintptr_t)out_tri % 4) != 0 || ((uintptr_t)records % 4) != 0 ||
       ((uintptr_t)out_rgb_u8 % 4) != 0 || ((uintptr_t)out_depth_nz % 4) != 0 || ((uintptr_t)out_rgba % 16) != 0 ||
       ((uintptr_t)out_depth % 16) != 0 || ((uintptr_t)workspace % 16) != 0)
@@ -588,8 +651,8 @@ extern "C" int pxt_mesh_render(const float* vertices, int32_t n_vertices, const 
   a.list_count = (unsigned*)((char*)workspace + key_bytes);
   a.list = (uint4*)((char*)workspace + key_bytes + rs_count_bytes(n_views));
   a.out_depth = out_depth; a.out_tri = (int*)out_tri; a.records = (unsigned*)records;
-  RsShade o;
-  o.colors = colors; o.out_rgba = out_rgba; o.out_rgb_u8 = out_rgb_u8; o.out_nz = out_depth_nz;
+  RsShade<Attr> o;
+  o.attr = attr; o.out_rgba = out_rgba; o.out_rgb_u8 = out_rgb_u8; o.out_nz = out_depth_nz;
 
   // launches 1 to 3 as pxt_mesh_raster makes them
   const size_t n_units = (size_t)(key_bytes / 16);
@@ -604,7 +667,34 @@ extern "C" int pxt_mesh_render(const float* vertices, int32_t n_vertices, const 
   PXT_HIP_CHECK(hipGetLastError());
   // a view's pixels begin up to three past a multiple of four in the row of all views
   const unsigned res_blocks = (unsigned)(((int64_t)width * height + 3 + kRsShadePixels - 1) / kRsShadePixels);
-  hipLaunchKernelGGL(rs_shade_resolve_kernel, dim3(res_blocks, n_views), dim3(kRsBlock), 0, s, a, o);
+  hipLaunchKernelGGL(rs_shade_resolve_kernel<Attr>, dim3(res_blocks, n_views), dim3(kRsBlock), 0, s, a, o);
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;
+}
+
+extern "C" int pxt_mesh_render(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                               const float* colors, const float* views, int32_t n_views, int32_t width, int32_t height,
+                               float* out_rgba, uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz,
+                               int32_t* out_tri, uint32_t* records, void* workspace, void* stream) {
+  RsVertexColors attr;
+  attr.colors = colors;
+  return rs_render(vertices, n_vertices, triangles, n_triangles, attr, colors && ((uintptr_t)colors % 4) == 0, views,
+                   n_views, width, height, out_rgba, out_rgb_u8, out_depth, out_depth_nz, out_tri, records, workspace,
+                   stream);
+}
+
+extern "C" int pxt_mesh_render_textured(const float* vertices, int32_t n_vertices, const int32_t* triangles,
+                                        int32_t n_triangles, const float* uvs, int32_t n_uvs, const int32_t* triangle_uvs,
+                                        const uint8_t* texture, int32_t tex_width, int32_t tex_height, const float* views,
+                                        int32_t n_views, int32_t width, int32_t height, float* out_rgba,
+                                        uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz, int32_t* out_tri,
+                                        uint32_t* records, void* workspace, void* stream) {
+  RsTexture attr;
+  attr.uvs = uvs; attr.triangle_uvs = (const int*)triangle_uvs; attr.texture = (const unsigned*)texture;
+  attr.n_uvs = n_uvs; attr.Wt = tex_width; attr.Ht = tex_height;
+  const bool ok = uvs && triangle_uvs && texture && ((uintptr_t)uvs % 4) == 0 && ((uintptr_t)triangle_uvs % 4) == 0 &&
+                  ((uintptr_t)texture % 4) == 0 && n_uvs >= 1 && n_uvs <= kRsMaxCount && tex_width >= 1 &&
+                  tex_width <= kRsMaxTexture && tex_height >= 1 && tex_height <= kRsMaxTexture;
+  return rs_render(vertices, n_vertices, triangles, n_triangles, attr, ok, views, n_views, width, height, out_rgba,
+                   out_rgb_u8, out_depth, out_depth_nz, out_tri, records, workspace, stream);
 }

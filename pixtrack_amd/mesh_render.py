@@ -14,6 +14,12 @@ Colour (``MeshRenderer.render``, ``shade_reference``): the vertex colours of the
 perspective-correctly, no lighting term and a black background - the reference's ambient-lit ``render_image`` as
 ``scripts/create_sfm_from_obj.py`` uses it - written as the float image and as the 8-bit planes the tracker takes from
 the NeRF renderer (``rgb_u8``, ``depth_nz``).  ``mesh_dataset.py`` builds a reference model from such renders.
+
+Texture (``MeshRenderer(V, F, device, uvs=, triangle_uvs=, texture=)``, ``shade_textured_reference``,
+pxt_mesh_render_textured): the same call with the colour read from one texture map through per-corner UVs, by
+pytorch3d's ``TexturesUV`` defaults as the reference's ``load_objs_as_meshes`` + ``render_image`` use them - row 0 of the
+map is v = 1, corners aligned, bilinear, the border clamped.  ``read_mesh_textured`` reads YCB's ``textured.obj`` with its
+``.mtl`` and BOP's ``texture_u`` / ``texture_v`` PLYs.
 """
 from __future__ import annotations
 
@@ -218,18 +224,19 @@ def rasterize_reference(V, F, views, width: int, height: int, coverage: bool = F
     return (depth, ids, recs, cov) if coverage else (depth, ids, recs)
 
 
-def _shade_view(V, F, C, view, ids, W):
-    """The colour rule for the covered pixels of one view, all at once: ``ids`` [H * W] -> (pixels, rgb [n, 3] float32)."""
+def _shade_setup(V, F, view, ids, W):
+    """What the two colour rules share for the covered pixels of one view, all at once: ``ids`` [H * W] -> (pixels,
+    their triangles, exchanged [n] bool, the corners' vertex indices after the exchange [3][n], w [3][n] float32, inv
+    [n] float32)."""
     pix = np.nonzero(ids >= 0)[0]
-    if len(pix) == 0:
-        return pix, np.zeros((0, 3), _F)
     _, _, X, Y, iz = _project_vertices(V, view)
-    idx = F[ids[pix]]
+    tri = ids[pix]
+    idx = F[tri]
     idx = [idx[:, 0], idx[:, 1], idx[:, 2]]
     x3, y3, z3 = [X[i] for i in idx], [Y[i] for i in idx], [iz[i] for i in idx]
     area = (x3[1] - x3[0]) * (y3[2] - y3[0]) - (y3[1] - y3[0]) * (x3[2] - x3[0])
     flip = area < 0
-    for a3 in (x3, y3, z3, idx):  # the colours follow the exchange through their indices
+    for a3 in (x3, y3, z3, idx):  # the corner attributes follow the exchange through their indices
         a3[1], a3[2] = np.where(flip, a3[2], a3[1]), np.where(flip, a3[1], a3[2])
     px, py = (pix % W) * SUB, (pix // W) * SUB
     with np.errstate(all="ignore"):
@@ -240,16 +247,74 @@ def _shade_view(V, F, C, view, ids, W):
             e = (x3[b] - x3[a]) * (py - y3[a]) - (y3[b] - y3[a]) * (px - x3[a])
             w.append(((e.astype(_F) / A).astype(_F) * z3[k]).astype(_F))
         inv = ((w[0] + w[1]).astype(_F) + w[2]).astype(_F)
-        c = [C[i] for i in idx]
-        num = ((w[0][:, None] * c[0]).astype(_F) + (w[1][:, None] * c[1]).astype(_F)).astype(_F) + (w[2][:, None] * c[2]).astype(_F)
-        rgb = np.fmin(np.fmax((num.astype(_F) / inv[:, None]).astype(_F), _F(0)), _F(1))  # a NaN -> 0
+    return pix, tri, flip, idx, w, inv
+
+
+def _interpolate(w, inv, c):
+    """``((w_0 c_0 + w_1 c_1) + w_2 c_2) / inv`` per column of the corner attributes ``c`` [3][n, m], float32."""
+    num = ((w[0][:, None] * c[0]).astype(_F) + (w[1][:, None] * c[1]).astype(_F)).astype(_F) + (w[2][:, None] * c[2]).astype(_F)
+    return (num.astype(_F) / inv[:, None]).astype(_F)
+
+
+def _shade_view(V, F, C, view, ids, W):
+    """The colour rule for the covered pixels of one view, all at once: ``ids`` [H * W] -> (pixels, rgb [n, 3] float32)."""
+    if not (ids >= 0).any():
+        return np.zeros(0, np.int64), np.zeros((0, 3), _F)
+    pix, _, _, idx, w, inv = _shade_setup(V, F, view, ids, W)
+    with np.errstate(all="ignore"):
+        rgb = np.fmin(np.fmax(_interpolate(w, inv, [C[i] for i in idx]), _F(0)), _F(1))  # a NaN -> 0
     return pix, rgb.astype(_F)
+
+
+def _texel_coordinate(x, n):
+    """The clamp and split of one texture axis: x [m] float32 in texels, ``n`` texels -> (i0, i1 int64, the weight of i1)."""
+    x = np.fmin(np.fmax(x, _F(0)), _F(n - 1))  # a NaN -> 0
+    x0 = np.floor(x).astype(_F)
+    i0 = x0.astype(np.int64)
+    return i0, np.minimum(i0 + 1, n - 1), (x - x0).astype(_F)
+
+
+def _shade_view_textured(V, F, UV, FUV, tex, view, ids, W):
+    """The texture rule for the covered pixels of one view: ``tex`` [Ht, Wt, 3] uint8 -> (pixels, rgb [n, 3] float32)."""
+    if not (ids >= 0).any():
+        return np.zeros(0, np.int64), np.zeros((0, 3), _F)
+    pix, tri, flip, _, w, inv = _shade_setup(V, F, view, ids, W)
+    Ht, Wt = tex.shape[:2]
+    k = FUV[tri]
+    k = [k[:, 0], np.where(flip, k[:, 2], k[:, 1]), np.where(flip, k[:, 1], k[:, 2])]
+    ok = np.all([(ki >= 0) & (ki < len(UV)) for ki in k], 0)
+    with np.errstate(all="ignore"):
+        uv = _interpolate(w, inv, [UV[np.clip(ki, 0, len(UV) - 1)] for ki in k])
+        i0, i1, ax = _texel_coordinate((uv[:, 0] * _F(Wt - 1)).astype(_F), Wt)
+        j0, j1, ay = _texel_coordinate(((_F(1.0) - uv[:, 1]).astype(_F) * _F(Ht - 1)).astype(_F), Ht)
+        tau = lambda j, i: (tex[j, i].astype(_F) / _F(255.0)).astype(_F)
+        t00, t01, t10, t11 = tau(j0, i0), tau(j0, i1), tau(j1, i0), tau(j1, i1)
+        ax, ay = ax[:, None], ay[:, None]
+        top = (t00 + (ax * (t01 - t00).astype(_F)).astype(_F)).astype(_F)
+        bot = (t10 + (ax * (t11 - t10).astype(_F)).astype(_F)).astype(_F)
+        c = (top + (ay * (bot - top).astype(_F)).astype(_F)).astype(_F)
+        rgb = np.fmin(np.fmax(c, _F(0)), _F(1))
+    return pix, np.where(ok[:, None], rgb, _F(0)).astype(_F)
 
 
 def _u8(x):
     """``(long long)(x * 255.0f) & 255`` on float32 values."""
     with np.errstate(all="ignore"):
         return ((np.asarray(x, _F) * _F(255.0)).astype(_F).astype(np.int64) & 255).astype(np.uint8)
+
+
+def _shade_all(V, F, views, width, height, shade_view):
+    """``rasterize_reference`` plus ``shade_view(view, ids [H * W], W) -> (pixels, rgb)`` per view -> the six outputs."""
+    views = np.asarray(views, np.float32).reshape(-1, VIEW)
+    P, W, H = len(views), int(width), int(height)
+    depth, ids, recs = rasterize_reference(V, F, views, W, H)
+    rgba = np.zeros((P, H, W, 4), np.float32)
+    for p in range(P):
+        pix, rgb = shade_view(views[p], ids[p].reshape(-1), W)
+        plane = rgba[p].reshape(-1, 4)
+        plane[pix, :3] = rgb
+        plane[pix, 3] = 1.0
+    return rgba, _u8(rgba[..., :3]), depth, (_u8(depth[..., 0]) != 0).astype(np.uint8), ids, recs
 
 
 def shade_reference(V, F, C, views, width: int, height: int):
@@ -261,16 +326,31 @@ def shade_reference(V, F, C, views, width: int, height: int):
     C = np.ascontiguousarray(np.asarray(C, np.float32).reshape(-1, 3))
     if len(C) != len(V):
         raise ValueError(f"{len(C)} colours for {len(V)} vertices")
-    views = np.asarray(views, np.float32).reshape(-1, VIEW)
-    P, W, H = len(views), int(width), int(height)
-    depth, ids, recs = rasterize_reference(V, F, views, W, H)
-    rgba = np.zeros((P, H, W, 4), np.float32)
-    for p in range(P):
-        pix, rgb = _shade_view(V, F, C, views[p], ids[p].reshape(-1), W)
-        plane = rgba[p].reshape(-1, 4)
-        plane[pix, :3] = rgb
-        plane[pix, 3] = 1.0
-    return rgba, _u8(rgba[..., :3]), depth, (_u8(depth[..., 0]) != 0).astype(np.uint8), ids, recs
+    return _shade_all(V, F, views, width, height, lambda view, ids, W: _shade_view(V, F, C, view, ids, W))
+
+
+def texture_rgb(texture) -> np.ndarray:
+    """A texture map as uint8 [Ht, Wt, 3]: a uint8 [Ht, Wt, 3 or 4] array, the fourth byte dropped."""
+    tex = np.asarray(texture)
+    if tex.dtype != np.uint8 or tex.ndim != 3 or tex.shape[2] not in (3, 4) or not (1 <= tex.shape[0] <= 16384) \
+            or not (1 <= tex.shape[1] <= 16384):
+        raise ValueError(f"texture is {tex.shape} {tex.dtype}, expected uint8 [1..16384, 1..16384, 3 or 4]")
+    return np.ascontiguousarray(tex[..., :3])
+
+
+def shade_textured_reference(V, F, UV, FUV, texture, views, width: int, height: int):
+    """The rule of pxt_mesh_render_textured in numpy, on ``rasterize_reference``'s depth and ids.  ``UV`` [n, 2] float32,
+    ``FUV`` [m, 3] (corner k of triangle t uses ``UV[FUV[t, k]]``), ``texture`` uint8 [Ht, Wt, 3 or 4] (row 0 is v = 1)
+    -> the six outputs of ``shade_reference``."""
+    V = np.ascontiguousarray(np.asarray(V, np.float32).reshape(-1, 3))
+    F = np.asarray(F).reshape(-1, 3).astype(np.int64)
+    UV = np.ascontiguousarray(np.asarray(UV, np.float32).reshape(-1, 2))
+    FUV = np.asarray(FUV).reshape(-1, 3).astype(np.int64)
+    tex = texture_rgb(texture)
+    if len(FUV) != len(F) or len(UV) < 1:
+        raise ValueError(f"{len(FUV)} UV triangles for {len(F)} triangles, {len(UV)} UVs")
+    return _shade_all(V, F, views, width, height,
+                      lambda view, ids, W: _shade_view_textured(V, F, UV, FUV, tex, view, ids, W))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -278,35 +358,68 @@ def shade_reference(V, F, C, views, width: int, height: int):
 # ---------------------------------------------------------------------------------------------------------------------
 class MeshRenderer:
     """Holds a mesh on the device and draws depth images of it (``torch.ops.pixtrack.mesh_raster``) and, given vertex
-    colours, colour images and the tracker's 8-bit planes (``torch.ops.pixtrack.mesh_render``)."""
+    colours, colour images and the tracker's 8-bit planes (``torch.ops.pixtrack.mesh_render``); given ``uvs`` [n, 2],
+    ``triangle_uvs`` [T, 3] (default: the triangles, when there is one UV per vertex) and ``texture`` (uint8 [Ht, Wt, 3
+    or 4], row 0 is v = 1) instead, the same from the texture map (``torch.ops.pixtrack.mesh_render_textured``)."""
 
     OUTPUTS = ("rgba", "rgb_u8", "depth", "depth_nz", "ids")
 
-    def __init__(self, V, F, device="cuda:0", colors=None):
+    def __init__(self, V, F, device="cuda:0", colors=None, uvs=None, triangle_uvs=None, texture=None):
         from . import ops  # registers the ops
 
         self._ops = ops.ops
         dev = torch.device(device)
         if dev.type != "cuda":
             raise _lib.PxtError("the mesh rasteriser runs on a ROCm device; no CPU path exists")
-        Vn = np.ascontiguousarray(np.asarray(V.detach().cpu().numpy() if torch.is_tensor(V) else V, np.float32).reshape(-1, 3))
-        Fn = np.asarray(F.detach().cpu().numpy() if torch.is_tensor(F) else F).reshape(-1, 3)
+        host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        Vn = np.ascontiguousarray(np.asarray(host(V), np.float32).reshape(-1, 3))
+        Fn = np.asarray(host(F)).reshape(-1, 3)
         if len(Vn) < 1 or len(Fn) < 1:
             raise _lib.PxtError(f"a mesh needs vertices and triangles (got {len(Vn)}, {len(Fn)})")
         if Fn.min() < -(1 << 31) or Fn.max() >= (1 << 31):
             raise _lib.PxtError("triangle indices do not fit int32")
         if colors is not None:
-            Cn = np.ascontiguousarray(np.asarray(colors.detach().cpu().numpy() if torch.is_tensor(colors) else colors, np.float32))
+            if uvs is not None or triangle_uvs is not None or texture is not None:
+                raise _lib.PxtError("a mesh is drawn with vertex colours or with a texture map, not both")
+            Cn = np.ascontiguousarray(np.asarray(host(colors), np.float32))
             if Cn.shape != Vn.shape:
                 raise _lib.PxtError(f"colors is {Cn.shape}, expected one r g b per vertex {Vn.shape}")
             if not np.isfinite(Cn).all() or Cn.min() < 0.0 or Cn.max() > 1.0:
                 raise _lib.PxtError("colors must be finite and inside [0, 1]")
+        elif uvs is not None or triangle_uvs is not None or texture is not None:
+            if uvs is None or texture is None:
+                raise _lib.PxtError("a textured mesh needs uvs and texture (triangle_uvs defaults to the triangles)")
+            Un = np.ascontiguousarray(np.asarray(host(uvs), np.float32))
+            if Un.ndim != 2 or Un.shape[1] != 2 or not (1 <= len(Un) <= 1 << 24):
+                raise _lib.PxtError(f"uvs is {Un.shape}, expected [1..2^24, 2]")
+            if not np.isfinite(Un).all():
+                raise _lib.PxtError("uvs must be finite")
+            if triangle_uvs is None:
+                if len(Un) != len(Vn):
+                    raise _lib.PxtError(f"triangle_uvs is needed: {len(Un)} uvs for {len(Vn)} vertices")
+                FUn = Fn
+            else:
+                FUn = np.asarray(host(triangle_uvs))
+            if FUn.shape != Fn.shape or FUn.dtype.kind not in "iu":
+                raise _lib.PxtError(f"triangle_uvs is {FUn.shape} {FUn.dtype}, expected integers {Fn.shape}")
+            if FUn.min() < 0 or FUn.max() >= len(Un):
+                raise _lib.PxtError(f"triangle_uvs holds indices outside the {len(Un)} uvs")
+            try:
+                Tn = texture_rgb(host(texture))
+            except ValueError as e:
+                raise _lib.PxtError(str(e)) from None
+            Tn = np.concatenate([Tn, np.full(Tn.shape[:2] + (1,), 255, np.uint8)], 2)  # one texel, one dword
         self.device = dev
         self.vertices_host = Vn
         self.vertices = torch.from_numpy(Vn).to(dev)
         self.triangles = torch.from_numpy(np.ascontiguousarray(Fn.astype(np.int32))).to(dev)
         self._workspace: Optional[torch.Tensor] = None
         self.colors = None if colors is None else torch.from_numpy(Cn).to(dev)
+        self.uvs = self.triangle_uvs = self.texture = None
+        if colors is None and uvs is not None:
+            self.uvs = torch.from_numpy(Un).to(dev)
+            self.triangle_uvs = torch.from_numpy(np.ascontiguousarray(FUn.astype(np.int32))).to(dev)
+            self.texture = torch.from_numpy(np.ascontiguousarray(Tn)).to(dev)
 
     def _views_and_workspace(self, views, width, height, what):
         vh = views.detach().cpu().numpy() if torch.is_tensor(views) else views
@@ -325,8 +438,9 @@ class MeshRenderer:
         ``rgb_u8`` uint8 [P, H, W, 3], ``depth`` [P, H, W, 4], ``depth_nz`` uint8 [P, H, W], ``ids`` int32 [P, H, W]) and
         ``records`` ([P, 16] uint32 numpy, or the int32 device tensor with ``download_records=False``).  One call, four
         launches; the default is what the tracker takes from the NeRF renderer per frame."""
-        if self.colors is None:
-            raise _lib.PxtError("render needs vertex colours: MeshRenderer(V, F, device, colors=...)")
+        if self.colors is None and self.texture is None:
+            raise _lib.PxtError("render needs vertex colours or a texture map: MeshRenderer(V, F, device, colors=...) or "
+                                "MeshRenderer(V, F, device, uvs=..., triangle_uvs=..., texture=...)")
         want = tuple(want)
         unknown = [w for w in want if w not in self.OUTPUTS]
         if unknown or not want:
@@ -337,8 +451,12 @@ class MeshRenderer:
                   "ids": ((P, H, W), torch.int32)}
         out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in want}
         records = torch.empty((P, RECORD), dtype=torch.int32, device=self.device)
-        self._ops.mesh_render(self.vertices, self.triangles, self.colors, v, W, H, out.get("rgba"), out.get("rgb_u8"),
-                              out.get("depth"), out.get("depth_nz"), out.get("ids"), records, self._workspace)
+        outs = (out.get("rgba"), out.get("rgb_u8"), out.get("depth"), out.get("depth_nz"), out.get("ids"))
+        if self.texture is None:
+            self._ops.mesh_render(self.vertices, self.triangles, self.colors, v, W, H, *outs, records, self._workspace)
+        else:
+            self._ops.mesh_render_textured(self.vertices, self.triangles, self.uvs, self.triangle_uvs, self.texture, v, W, H,
+                                           *outs, records, self._workspace)
         out["records"] = records.cpu().numpy().view(np.uint32) if download_records else records
         return out
 
@@ -465,16 +583,18 @@ def fan_triangles(polygons: Sequence[Sequence[int]]) -> np.ndarray:
     return np.asarray(out, np.int64).reshape(-1, 3)
 
 
-def _read_ply(path, colors=False):
+def _read_ply(path, colors=False, uvs=False):
     with open(str(path), "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
     if not data.startswith(b"ply") or end < 0:
         raise ValueError(f"{path}: not a PLY file")
     body = data.index(b"\n", end) + 1
-    fmt, elements = None, []  # elements: [name, count, [(kind, name, types...)]]
+    fmt, elements, texture_file = None, [], None  # elements: [name, count, [(kind, name, types...)]]
     for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
         w = line.split()
+        if len(w) >= 3 and w[0] == "comment" and w[1] == "TextureFile" and texture_file is None:
+            texture_file = line.split(None, 2)[2].strip()
         if not w or w[0] in ("comment", "obj_info"):
             continue
         if w[0] == "format":
@@ -506,7 +626,7 @@ def _read_ply(path, colors=False):
         pos[0] += struct.calcsize(c)
         return val
 
-    V, C, polys, seen = None, None, None, set()
+    V, C, UV, polys, seen = None, None, None, None, set()
     for name, count, props in elements:
         seen.add(name)
         if name == "vertex":
@@ -527,6 +647,9 @@ def _read_ply(path, colors=False):
             if colors and all(k in names for k in ("red", "green", "blue")):  # integers are 0..255, floats 0..1
                 C = np.stack([column(k) / (1.0 if _PLY_TYPES[props[names.index(k)][2]] in "fd" else 255.0)
                               for k in ("red", "green", "blue")], 1).reshape(-1, 3)
+            for ku, kv in (("texture_u", "texture_v"), ("s", "t")):
+                if uvs and UV is None and ku in names and kv in names:
+                    UV = np.stack([column(ku), column(kv)], 1).reshape(-1, 2)
         elif name == "face":
             lists = [p for p in props if p[0] == "list"]
             if len(lists) != 1 or lists[0][1] not in ("vertex_indices", "vertex_index"):
@@ -551,6 +674,8 @@ def _read_ply(path, colors=False):
     for need in ("vertex", "face"):
         if need not in seen:
             raise ValueError(f"{path}: no element {need}")
+    if uvs:
+        return V, fan_triangles(polys), UV, texture_file
     return (V, fan_triangles(polys), C) if colors else (V, fan_triangles(polys))
 
 
@@ -597,8 +722,8 @@ def read_mesh_colors(path) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]
     """``read_mesh`` plus the vertex colours: ``(V, F, C [n, 3] float64 in 0..1, or None for a file without them)``.
     PLY: the vertex properties ``red green blue`` - integer types (BOP's uchar) are divided by 255, float types are
     taken as 0..1; an ``alpha`` property is ignored.  OBJ: ``v x y z r g b`` (what ``mesh.write_obj`` writes).  Texture
-    maps (OBJ ``vt`` / ``usemtl``, PLY ``texture_u``) are not read: a textured model without vertex colours comes back
-    with ``None``."""
+    maps (OBJ ``vt`` / ``usemtl``, PLY ``texture_u``) are ``read_mesh_textured``'s: a textured model without vertex
+    colours comes back with ``None`` here."""
     from . import mesh
 
     V, F = read_mesh(path)
@@ -608,3 +733,101 @@ def read_mesh_colors(path) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]
         C = mesh.read_obj(path)[2]
         C = C if C is not None and len(C) == len(V) else None
     return V, F, C
+
+
+def _read_obj_textured(path, require_image=True):
+    """The textured half of an OBJ: ``v``, ``vt``, ``f v/vt[/vn]``, ``mtllib`` and ``usemtl`` -> (V, F, UV, FUV, the
+    texture's path), or None for a file none of whose faces names a ``vt``."""
+    path = Path(str(path))
+    V, UV, faces, libs, used = [], [], [], [], []
+    with open(str(path)) as f:
+        for n, line in enumerate(f, 1):
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == "v":
+                V.append([float(x) for x in w[1:4]])
+            elif w[0] == "vt":
+                UV.append([float(x) for x in w[1:3]])
+            elif w[0] == "f":
+                faces.append((n, [c.split("/") for c in w[1:]], len(V), len(UV)))
+            elif w[0] == "mtllib":
+                libs.append(line.split(None, 1)[1].strip())
+            elif w[0] == "usemtl" and w[1:] and w[1] not in used:
+                used.append(w[1])
+    textured = [all(len(c) >= 2 and c[1] != "" for c in corners) for _, corners, _, _ in faces]
+    if not any(textured):
+        return None
+    polys, uv_polys = [], []
+    for (n, corners, nv, nt), has in zip(faces, textured):
+        if not has:
+            raise ValueError(f"{path}: line {n}: a face without vt in a file with textured faces")
+        vi, ti = [int(c[0]) for c in corners], [int(c[1]) for c in corners]
+        polys.append([i - 1 if i > 0 else nv + i for i in vi])  # 1-based; negative = from the last one read so far
+        uv_polys.append([i - 1 if i > 0 else nt + i for i in ti])
+    F, FUV = fan_triangles(polys), fan_triangles(uv_polys)
+    V, UV = np.asarray(V, np.float64).reshape(-1, 3), np.asarray(UV, np.float64).reshape(-1, 2)
+    if F.min() < 0 or F.max() >= len(V) or FUV.min() < 0 or FUV.max() >= len(UV):
+        raise ValueError(f"{path}: face indices outside the {len(V)} vertices or the {len(UV)} texture coordinates")
+    if not libs:
+        raise ValueError(f"{path}: textured faces but no mtllib")
+    maps = {}  # material -> map_Kd
+    for lib in libs:
+        mtl = path.parent / lib
+        if not mtl.is_file():
+            raise ValueError(f"{path}: material library {mtl} is missing")
+        current = None
+        for line in mtl.read_text().splitlines():
+            w = line.split()
+            if w[:1] == ["newmtl"] and len(w) > 1:
+                current = w[1]
+            elif w[:1] == ["map_Kd"] and len(w) > 1 and current is not None:
+                maps[current] = w[-1]  # options (-clamp on ...) come before the file name
+    wanted = used if used else sorted(maps)
+    unknown = [m for m in wanted if m not in maps]
+    names = sorted({maps[m] for m in wanted if m in maps})
+    if len(names) > 1:
+        raise ValueError(f"{path}: several texture maps ({', '.join(names)}); one map_Kd per mesh is supported")
+    if not names or (unknown and used):
+        raise ValueError(f"{path}: no map_Kd for material {(unknown or wanted or ['?'])[0]!r} in {', '.join(libs)}")
+    image = path.parent / names[0]
+    if require_image and not image.is_file():
+        raise ValueError(f"{path}: texture map {image} is missing")
+    return V, F, UV, FUV, image
+
+
+def read_mesh_textured(path, require_image: bool = True):
+    """``(V [n, 3], F [m, 3], UV [k, 2] float64, FUV [m, 3] int64, the texture map's path)`` of a textured mesh, or None
+    for a file without texture coordinates.
+
+    OBJ: ``vt`` lines and faces ``v/vt`` or ``v/vt/vn`` (1-based and negative indices, polygons fanned with their UVs);
+    ``mtllib`` names the ``.mtl`` beside the OBJ and ``usemtl`` the material whose ``map_Kd`` is the map, relative to the
+    OBJ's folder.  One map per mesh: materials with different maps, a missing ``.mtl`` or image and a face without ``vt``
+    among textured ones are refused by name.  PLY: the vertex properties ``texture_u texture_v`` (or ``s t``) and
+    ``comment TextureFile NAME`` (BOP's models); ``FUV = F``.  Texture coordinates in PLY face lists are not read.
+    ``require_image=False`` returns the map's path without asking that the file be there (the caller has another)."""
+    path = Path(str(path))
+    suffix = path.suffix.lower()
+    if suffix == ".obj":
+        return _read_obj_textured(path, require_image)
+    if suffix != ".ply":
+        raise ValueError(f"{path}: mesh format {suffix!r} is not supported (.obj, .ply)")
+    V, F, UV, name = _read_ply(path, uvs=True)
+    if UV is None:
+        return None
+    if len(V) == 0 or len(F) == 0 or F.min() < 0 or F.max() >= len(V):
+        raise ValueError(f"{path}: face indices outside the {len(V)} vertices")
+    if name is None:
+        raise ValueError(f"{path}: texture_u / texture_v but no comment TextureFile")
+    image = path.parent / name
+    if require_image and not image.is_file():
+        raise ValueError(f"{path}: texture map {image} is missing")
+    return V, F, UV, F.copy(), image
+
+
+def read_texture(path) -> np.ndarray:
+    """An image file as a uint8 [Ht, Wt, 3] texture map (row 0 on top, v = 1)."""
+    from PIL import Image
+
+    with Image.open(str(path)) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), np.uint8))

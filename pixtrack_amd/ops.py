@@ -194,6 +194,13 @@ SCHEMAS = {
         "(Tensor vertices, Tensor triangles, Tensor colors, Tensor views, int width, int height, Tensor(a!)? rgba, "
         "Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, Tensor(e!)? triangle_ids, Tensor(f!) records, "
         "Tensor(g!) workspace) -> ()"),
+    # the same with a texture map in place of the colours: uvs [n, 2] float32, triangle_uvs int32 [T, 3] (corner k of
+    # triangle t uses uvs[triangle_uvs[t, k]]), texture uint8 [Ht, Wt, 4] (r g b and an ignored byte;
+    # pxt_mesh_render_textured)
+    "mesh_render_textured": (
+        "(Tensor vertices, Tensor triangles, Tensor uvs, Tensor triangle_uvs, Tensor texture, Tensor views, int width, "
+        "int height, Tensor(a!)? rgba, Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, "
+        "Tensor(e!)? triangle_ids, Tensor(f!) records, Tensor(g!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -1290,55 +1297,94 @@ def _mesh_raster(vertices, triangles, views, depth, triangle_ids, records, works
                                  _stream(vertices)), "pxt_mesh_raster")
 
 
-def _mesh_render(vertices, triangles, colors, views, width, height, rgba, rgb_u8, depth, depth_nz, triangle_ids,
-                 records, workspace):
+def _mesh_render_checked(what, vertices, triangles, attrs, check_attrs, views, width, height, rgba, rgb_u8, depth,
+                         depth_nz, triangle_ids, records, workspace):
+    """The checks mesh_render and mesh_render_textured share -> (V, T, P, W, H).  ``attrs``: [(tensor, name)] of the
+    call's own inputs, ``check_attrs(V, T)`` their shapes."""
     L = _lib.lib()
     _f32c(vertices, "vertices")
     _f32c(views, "views")
-    _f32c(colors, "colors")
     if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or triangles.dim() != 2 or int(triangles.shape[1]) != 3
             or triangles.dtype != torch.int32 or not triangles.is_contiguous() or views.dim() != 2
             or int(views.shape[1]) != _lib.PXT_MESH_VIEW):
-        raise _lib.PxtError(f"mesh_render: vertices {tuple(vertices.shape)} / triangles {tuple(triangles.shape)} "
+        raise _lib.PxtError(f"{what}: vertices {tuple(vertices.shape)} / triangles {tuple(triangles.shape)} "
                             f"{triangles.dtype} / views {tuple(views.shape)}, expected float32 [V, 3] / contiguous int32 "
                             f"[T, 3] / float32 [P, {_lib.PXT_MESH_VIEW}]")
     V, T, P, W, H = int(vertices.shape[0]), int(triangles.shape[0]), int(views.shape[0]), int(width), int(height)
-    if tuple(colors.shape) != (V, 3):
-        raise _lib.PxtError(f"mesh_render: colors is {tuple(colors.shape)}, expected float32 [{V}, 3]")
+    check_attrs(V, T)
     outs = [(rgba, "rgba", torch.float32, (P, H, W, 4)), (rgb_u8, "rgb_u8", torch.uint8, (P, H, W, 3)),
             (depth, "depth", torch.float32, (P, H, W, 4)), (depth_nz, "depth_nz", torch.uint8, (P, H, W)),
             (triangle_ids, "triangle_ids", torch.int32, (P, H, W))]
     for t, name, dtype, shape in outs:
         if t is not None and (t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape):
-            raise _lib.PxtError(f"mesh_render: {name} is a contiguous {dtype} {list(shape)} tensor (got "
+            raise _lib.PxtError(f"{what}: {name} is a contiguous {dtype} {list(shape)} tensor (got "
                                 f"{tuple(t.shape)}, {t.dtype})")
     if all(t is None for t, *_ in outs):
-        raise _lib.PxtError("mesh_render: no output was asked for")
+        raise _lib.PxtError(f"{what}: no output was asked for")
     if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
-        raise _lib.PxtError(f"mesh_render: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
+        raise _lib.PxtError(f"{what}: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
                             f"(got {tuple(records.shape)}, {records.dtype})")
     need = int(L.pxt_mesh_raster_workspace_bytes(P, T, W, H)) if min(P, T, W, H) >= 1 else -1
     if need <= 0 or not (1 <= V <= 1 << 24):
-        raise _lib.PxtError(f"mesh_render: {P} views of {W} x {H}, {V} vertices, {T} triangles are not supported "
+        raise _lib.PxtError(f"{what}: {P} views of {W} x {H}, {V} vertices, {T} triangles are not supported "
                             "(1..4096 views, 1..2^26 pixels, 1..2^24 vertices and triangles)")
     if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"mesh_render: workspace is a contiguous uint8 tensor of >= {need} bytes")
+        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {need} bytes")
     # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    named = [(vertices, "vertices"), (triangles, "triangles"), (colors, "colors"), (views, "views"), (records, "records"),
+    named = [(vertices, "vertices"), (triangles, "triangles"), *attrs, (views, "views"), (records, "records"),
              (workspace, "workspace")] + [(t, name) for t, name, *_ in outs if t is not None]
     for t, name in named:
         _lib.require_gpu(t, name)
         if t.device != vertices.device:
-            raise _lib.PxtError(f"mesh_render: {name} is on {t.device}, the vertices on {vertices.device}")
-    _lib.check(L.pxt_mesh_render(vertices.data_ptr(), V, triangles.data_ptr(), T, colors.data_ptr(), views.data_ptr(), P,
-                                 W, H, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth), _lib.dptr(depth_nz),
-                                 _lib.dptr(triangle_ids), records.data_ptr(), workspace.data_ptr(), _stream(vertices)),
-               "pxt_mesh_render")
+            raise _lib.PxtError(f"{what}: {name} is on {t.device}, the vertices on {vertices.device}")
+    return V, T, P, W, H
+
+
+def _mesh_render(vertices, triangles, colors, views, width, height, rgba, rgb_u8, depth, depth_nz, triangle_ids,
+                 records, workspace):
+    _f32c(colors, "colors")
+
+    def check(V, T):
+        if tuple(colors.shape) != (V, 3):
+            raise _lib.PxtError(f"mesh_render: colors is {tuple(colors.shape)}, expected float32 [{V}, 3]")
+
+    V, T, P, W, H = _mesh_render_checked("mesh_render", vertices, triangles, [(colors, "colors")], check, views, width,
+                                         height, rgba, rgb_u8, depth, depth_nz, triangle_ids, records, workspace)
+    _lib.check(_lib.lib().pxt_mesh_render(
+        vertices.data_ptr(), V, triangles.data_ptr(), T, colors.data_ptr(), views.data_ptr(), P, W, H, _lib.dptr(rgba),
+        _lib.dptr(rgb_u8), _lib.dptr(depth), _lib.dptr(depth_nz), _lib.dptr(triangle_ids), records.data_ptr(),
+        workspace.data_ptr(), _stream(vertices)), "pxt_mesh_render")
+
+
+def _mesh_render_textured(vertices, triangles, uvs, triangle_uvs, texture, views, width, height, rgba, rgb_u8, depth,
+                          depth_nz, triangle_ids, records, workspace):
+    _f32c(uvs, "uvs")
+
+    def check(V, T):
+        if uvs.dim() != 2 or int(uvs.shape[1]) != 2 or not (1 <= int(uvs.shape[0]) <= 1 << 24):
+            raise _lib.PxtError(f"mesh_render_textured: uvs is {tuple(uvs.shape)}, expected float32 [1..2^24, 2]")
+        if triangle_uvs.dtype != torch.int32 or not triangle_uvs.is_contiguous() or tuple(triangle_uvs.shape) != (T, 3):
+            raise _lib.PxtError(f"mesh_render_textured: triangle_uvs is a contiguous int32 [{T}, 3] tensor (got "
+                                f"{tuple(triangle_uvs.shape)}, {triangle_uvs.dtype})")
+        if (texture.dtype != torch.uint8 or not texture.is_contiguous() or texture.dim() != 3 or int(texture.shape[2]) != 4
+                or not (1 <= int(texture.shape[0]) <= 16384 and 1 <= int(texture.shape[1]) <= 16384)):
+            raise _lib.PxtError("mesh_render_textured: texture is a contiguous uint8 [1..16384, 1..16384, 4] tensor (got "
+                                f"{tuple(texture.shape)}, {texture.dtype})")
+
+    V, T, P, W, H = _mesh_render_checked(
+        "mesh_render_textured", vertices, triangles, [(uvs, "uvs"), (triangle_uvs, "triangle_uvs"), (texture, "texture")],
+        check, views, width, height, rgba, rgb_u8, depth, depth_nz, triangle_ids, records, workspace)
+    _lib.check(_lib.lib().pxt_mesh_render_textured(
+        vertices.data_ptr(), V, triangles.data_ptr(), T, uvs.data_ptr(), int(uvs.shape[0]), triangle_uvs.data_ptr(),
+        texture.data_ptr(), int(texture.shape[1]), int(texture.shape[0]), views.data_ptr(), P, W, H, _lib.dptr(rgba),
+        _lib.dptr(rgb_u8), _lib.dptr(depth), _lib.dptr(depth_nz), _lib.dptr(triangle_ids), records.data_ptr(),
+        workspace.data_ptr(), _stream(vertices)), "pxt_mesh_render_textured")
 
 
 _IMPLS = {
     "mesh_raster": _mesh_raster,
     "mesh_render": _mesh_render,
+    "mesh_render_textured": _mesh_render_textured,
     "ngp_query": _ngp_query,
     "iso_surface_count": _iso_surface_count,
     "iso_surface_emit": _iso_surface_emit,
