@@ -1279,6 +1279,59 @@ int pxt_mesh_render_textured(const float* vertices, int32_t n_vertices, const in
                              int32_t height, float* out_rgba, uint8_t* out_rgb_u8, float* out_depth,
                              uint8_t* out_depth_nz, int32_t* out_tri, uint32_t* records, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * A tracker frame's renders of a mesh in one call: up to PXT_MESH_FRAME_MAX_VIEWS = 8 views of one mesh, each with its
+ * own size, its own supersampling factor and its own choice of outputs (opt-in; csrc/pxt_raster.hip,
+ * mesh_render.frame_reference restates the rule in numpy and the two agree bit for bit on every output and record;
+ * pixtrack_amd/mesh_template.py draws the tracker's depth_nz plane at the query camera and its anti-aliased 8-bit
+ * template at the reference camera with it).
+ *
+ * vertices, triangles, views [P][20], records [P][16] and their bounds are pxt_mesh_raster's.  The mesh is shaded by
+ * vertex colours (colors [V][3] as pxt_mesh_render; uvs, triangle_uvs and texture NULL) or by a texture map (uvs, n_uvs,
+ * triangle_uvs, texture, tex_width, tex_height as pxt_mesh_render_textured; colors NULL): exactly one of the two.
+ * geometry [P][3] int32 (HOST memory): width W, height H and supersample S of each view, S in {1, 2, 4}.
+ *
+ * The fine view.  View p is rasterised on the fine lattice W' = S W, H' = S H through the fine view record, formed on
+ *   the device from its 20 floats, each step a single fp32 operation:
+ *       fx' = fx * (float)S;   fy' = fy * (float)S;   cx' = cx * (float)S + 0.5f * (float)(S - 1);   cy' likewise;
+ *   everything else unchanged.  In the Camera convention (pixel centres at integer coordinates) fine pixel
+ *   (S i + a, S j + b) is the sample of output pixel (i, j) at offset ((a + 0.5) / S - 0.5, (b + 0.5) / S - 0.5).
+ *   Coverage, the depth test and the colour of a fine pixel are exactly pxt_mesh_raster's and
+ *   pxt_mesh_render(_textured)'s rules on that W' x H' view.
+ * out_rgba, per view [H][W][4] float32: per channel, the fine pixels of the S x S block in row-major order (b outer, a
+ *   inner) - a covered one contributes (r, g, b, 1), an uncovered one four zeros; start from the first, add the next
+ *   with one fp32 add each, multiply by 1.0f / (S * S) (exact).  Colour premultiplied over black, alpha the covered
+ *   fraction: what a Shade render on the black background gives at a silhouette.
+ * out_rgb_u8, per view [H][W][3] uint8: (long long)(c * 255.0f) & 255 on the first three channels of that.
+ * out_depth, per view [H][W][4] float32, and out_depth_nz, per view [H][W] uint8: pxt_mesh_render's, for S = 1 alone.
+ * Where the outputs go.  The four out_* pointers are the bases of four buffers of out_bytes[0..3] bytes (HOST array;
+ *   a buffer no view uses may be NULL); out_offsets [P][4] int64 (HOST memory) holds, per view and in the order rgba,
+ *   rgb_u8, depth, depth_nz, the byte offset of that view's plane in its buffer, or -1 for an output the view does not
+ *   ask for.  Every view names at least one.  The planes of one call must not overlap.
+ * records: pxt_mesh_raster's record of the fine view - the counts are fine pixels; the status is -1 and the image all
+ *   background when one of the fine view's 20 floats is not finite.
+ * With S = 1 every output and record equals pxt_mesh_render(_textured) on the same view bit for bit.  A view's outputs
+ *   are a pure function of the mesh and that view's 20 floats, size and S: they do not depend on P, on the view's
+ *   index, on the other views' sizes or on scheduling.
+ * Bounds: 1 <= P <= 8; W, H >= 1 and W' * H' <= 2^26 per view; a depth output asked for with S > 1, an offset that is not
+ *   a multiple of 16 (rgba, depth) or 4 (the byte planes: they are stored as whole dwords), a plane that does not fit
+ *   its buffer, a view without output, both or neither shading inputs; plus the alignment and NULL rules of
+ *   pxt_mesh_render(_textured).  Anything else is PXT_E_ARG and nothing is launched or written.
+ * workspace: device memory of pxt_mesh_render_frame_workspace_bytes(P, T, geometry) bytes (< 0: unsupported), 16-byte
+ *   aligned.  Four launches on `stream` for any P - clear, triangle and list as pxt_mesh_raster's, generalised to a
+ *   per-view table (fine size, key-plane offset, S) that rides in the kernel arguments with the view as the grid's
+ *   second dimension, and one resolve, one lane per output pixel.  No host synchronisation, no allocation.
+ *   Measured on the MI355X: DESIGN.md 3.18.
+ * ---------------------------------------------------------------------- */
+#define PXT_MESH_FRAME_MAX_VIEWS 8
+int64_t pxt_mesh_render_frame_workspace_bytes(int32_t n_views, int32_t n_triangles, const int32_t* geometry);
+int pxt_mesh_render_frame(const float* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                          const float* colors, const float* uvs, int32_t n_uvs, const int32_t* triangle_uvs,
+                          const uint8_t* texture, int32_t tex_width, int32_t tex_height, const float* views,
+                          int32_t n_views, const int32_t* geometry, const int64_t* out_offsets, float* out_rgba,
+                          uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
+                          uint32_t* records, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

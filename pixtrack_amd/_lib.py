@@ -48,6 +48,7 @@ PXT_OCCLUSION_MAX_RADIUS = 16
 PXT_ISO_CASE_TABLE_WORDS = 6 * 16 * 7
 PXT_MESH_VIEW = 20
 PXT_MESH_RASTER_RECORD = 16
+PXT_MESH_FRAME_MAX_VIEWS = 8
 
 
 class PxtError(RuntimeError):
@@ -370,6 +371,9 @@ PROTOTYPES = {
     "pxt_mesh_render": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pxt_mesh_render_textured": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _I32, _I32, _I32,
                                            _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pxt_mesh_render_frame_workspace_bytes": (_I64, [_I32, _I32, _VP]),
+    "pxt_mesh_render_frame": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _I32, _VP, _VP,
+                                        _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 

@@ -43,6 +43,8 @@ constexpr int kRsResolvePixels = 4;  // rs_resolve_kernel: pixels per lane
 constexpr int kRsLaneMax = 32;     // box pixels one lane walks alone
 constexpr int kRsWaveMax = 1024;   // box pixels the wave walks together; larger boxes go to the list
 constexpr int kRsListCap = 1024;   // list entries per view
+constexpr int kRfListCap = 16384;  // ... of pxt_mesh_render_frame (rf_list_kernel)
+constexpr int kRfWaveMax = 256;    // ... and its threshold: its list kernel gathers per tile, a tile's worth of box is enough
 constexpr int kRsTile = 16;        // rs_list_kernel: kRsTile x kRsTile pixels per workgroup
 constexpr int kRsSub = 256;        // sub-pixel steps per pixel
 constexpr float kRsGuard = 8388608.f;  // 2^23
@@ -192,20 +194,20 @@ __global__ __launch_bounds__(kRsBlock) void rs_clear_kernel(const RsArgs a, cons
   for (size_t u = g; u < (size_t)a.P; u += stride) a.list_count[u] = 0u;
 }
 
-__global__ __launch_bounds__(kRsTriBlock) void rs_triangle_kernel(const RsArgs a) {
-  __shared__ unsigned counts[6];
-  const int view = blockIdx.y, lane = threadIdx.x & (PXT_WAVE - 1);
-  RsView v;
-  if (!rs_load_view(a.views + (size_t)view * PXT_MESH_VIEW, &v)) return;  // the whole workgroup alike
+// The work of one workgroup of launch 2 on a finite view of W x H pixels whose key plane is `keys`; `counts`: six words
+// of LDS; a box of more than `wave_max` pixels goes to the list.  a.W, a.H and a.keys are not read:
+// pxt_mesh_render_frame's views each have their own.
+__device__ __forceinline__ void rs_triangle_view(const RsArgs& a, const RsView& v, const int view, const int W, const int H,
+                                                 unsigned long long* __restrict__ keys, unsigned* counts, const int wave_max) {
+  const int lane = threadIdx.x & (PXT_WAVE - 1);
   if (threadIdx.x < 6) counts[threadIdx.x] = 0u;
   __syncthreads();
   const int t = blockIdx.x * kRsTriBlock + threadIdx.x;
-  unsigned long long* keys = a.keys + (size_t)view * a.W * a.H;
   RsTri s;
   int cause = -1;  // no triangle
   if (t < a.T) {
     const int* f = a.triangles + 3 * (size_t)t;
-    cause = rs_setup(v, a.vertices, a.V, f[0], f[1], f[2], a.W, a.H, &s);
+    cause = rs_setup(v, a.vertices, a.V, f[0], f[1], f[2], W, H, &s);
   }
   // the counts: the waves' ballots meet in LDS, one add per workgroup and cause reaches the record (thousands of adds
   // to one address cost more than the triangles' own work)
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(kRsTriBlock) void rs_triangle_kernel(const RsArgs a
   }
   int npx = 0;
   if (cause == RS_DRAWN && s.ix0 <= s.ix1 && s.iy0 <= s.iy1) npx = (s.ix1 - s.ix0 + 1) * (s.iy1 - s.iy0 + 1);  // < 2^30
-  if (npx > kRsWaveMax) {  // to the list while it has room
+  if (npx > wave_max && (s.ix1 | s.iy1) < 65536) {  // to the list while it has room (its boxes are 16-bit)
     const unsigned slot = atomicAdd(a.list_count + view, 1u);
     if (slot < (unsigned)a.cap) {
       a.list[(size_t)view * a.cap + slot] = make_uint4((unsigned)t, (unsigned)s.ix0 | ((unsigned)s.ix1 << 16),
@@ -235,7 +237,7 @@ __global__ __launch_bounds__(kRsTriBlock) void rs_triangle_kernel(const RsArgs a
     for (int j = s.iy0; j <= s.iy1; ++j)
       for (int i = s.ix0; i <= s.ix1; ++i) {
         unsigned zb;
-        if (rs_pixel(s, i, j, &zb)) atomicMin(keys + (size_t)j * a.W + i, rs_key(zb, t));
+        if (rs_pixel(s, i, j, &zb)) atomicMin(keys + (size_t)j * W + i, rs_key(zb, t));
       }
   }
   // the larger boxes, one after the other, by the whole wave
@@ -263,18 +265,24 @@ __global__ __launch_bounds__(kRsTriBlock) void rs_triangle_kernel(const RsArgs a
       for (int i0 = w.ix0; i0 <= w.ix1; i0 += tw) {
         const int i = i0 + lx, j = j0 + ly;
         unsigned zb;
-        if (i <= w.ix1 && j <= w.iy1 && rs_pixel(w, i, j, &zb)) atomicMin(keys + (size_t)j * a.W + i, rs_key(zb, wt));
+        if (i <= w.ix1 && j <= w.iy1 && rs_pixel(w, i, j, &zb)) atomicMin(keys + (size_t)j * W + i, rs_key(zb, wt));
       }
   }
 }
 
-__global__ __launch_bounds__(kRsBlock) void rs_list_kernel(const RsArgs a, const int tiles_x) {
+__global__ __launch_bounds__(kRsTriBlock) void rs_triangle_kernel(const RsArgs a) {
+  __shared__ unsigned counts[6];
   const int view = blockIdx.y;
-  const int n = (int)min(a.list_count[view], (unsigned)a.cap);
-  if (n == 0) return;
   RsView v;
-  if (!rs_load_view(a.views + (size_t)view * PXT_MESH_VIEW, &v)) return;  // never: such a view lists nothing
-  const int tx0 = ((int)blockIdx.x % tiles_x) * kRsTile, ty0 = ((int)blockIdx.x / tiles_x) * kRsTile;
+  if (!rs_load_view(a.views + (size_t)view * PXT_MESH_VIEW, &v)) return;  // the whole workgroup alike
+  rs_triangle_view(a, v, view, a.W, a.H, a.keys + (size_t)view * a.W * a.H, counts, kRsWaveMax);
+}
+
+// The work of one workgroup of launch 3: tile `tile` of a view of W x H pixels with `tiles_x` tiles per row.
+__device__ __forceinline__ void rs_list_view(const RsArgs& a, const RsView& v, const int view, const int W, const int H,
+                                             unsigned long long* __restrict__ keys, const int n, const int tiles_x,
+                                             const int tile) {
+  const int tx0 = (tile % tiles_x) * kRsTile, ty0 = (tile / tiles_x) * kRsTile;
   const int i = tx0 + ((int)threadIdx.x & (kRsTile - 1)), j = ty0 + ((int)threadIdx.x / kRsTile);
   const uint4* list = a.list + (size_t)view * a.cap;
   unsigned long long best = kRsEmpty;
@@ -286,11 +294,20 @@ __global__ __launch_bounds__(kRsBlock) void rs_list_kernel(const RsArgs a, const
     if (t < 0 || t >= a.T) continue;
     const int* f = a.triangles + 3 * (size_t)t;
     RsTri s;
-    if (rs_setup(v, a.vertices, a.V, f[0], f[1], f[2], a.W, a.H, &s) != RS_DRAWN) continue;
+    if (rs_setup(v, a.vertices, a.V, f[0], f[1], f[2], W, H, &s) != RS_DRAWN) continue;
     unsigned zb;
     if (i >= s.ix0 && i <= s.ix1 && j >= s.iy0 && j <= s.iy1 && rs_pixel(s, i, j, &zb)) best = min(best, rs_key(zb, t));
   }
-  if (best != kRsEmpty && i < a.W && j < a.H) atomicMin(a.keys + (size_t)view * a.W * a.H + (size_t)j * a.W + i, best);
+  if (best != kRsEmpty && i < W && j < H) atomicMin(keys + (size_t)j * W + i, best);
+}
+
+__global__ __launch_bounds__(kRsBlock) void rs_list_kernel(const RsArgs a, const int tiles_x) {
+  const int view = blockIdx.y;
+  const int n = (int)min(a.list_count[view], (unsigned)a.cap);
+  if (n == 0) return;
+  RsView v;
+  if (!rs_load_view(a.views + (size_t)view * PXT_MESH_VIEW, &v)) return;  // never: such a view lists nothing
+  rs_list_view(a, v, view, a.W, a.H, a.keys + (size_t)view * a.W * a.H, n, tiles_x, (int)blockIdx.x);
 }
 
 __global__ __launch_bounds__(kRsBlock) void rs_resolve_kernel(const RsArgs a) {
@@ -431,43 +448,62 @@ struct RsTexture {
   }
 };
 
-// The colour of triangle t at pixel (i, j): set up as rs_setup does (the same rs_vertex, area and exchange; the corner
-// attributes follow the exchange), no cull - t won the pixel, so it was drawn.  -> rgb, zeros if t cannot have been drawn.
-template <class Attr>
-__device__ __forceinline__ void rs_shade(const RsArgs& a, const Attr& attr, const RsView& v, int t, int i, int j,
-                                         float* rgb) {
-  rgb[0] = rgb[1] = rgb[2] = 0.f;
+// The winning triangle of a pixel, set up for shading as rs_setup does (the same rs_vertex, area and exchange; the
+// corner indices follow the exchange), no cull - t won the pixel, so it was drawn.  `ok` is false if it cannot have been.
+struct RsShadeTri {
+  int x[3], y[3], idx[3];
+  float iz[3], A;
+  bool exchanged, ok;
+};
+
+__device__ __forceinline__ void rs_shade_setup(const RsArgs& a, const RsView& v, int t, RsShadeTri* s) {
+  s->ok = false;
   if ((unsigned)t >= (unsigned)a.T) return;
   const int* f = a.triangles + 3 * (size_t)t;
-  int idx[3] = {f[0], f[1], f[2]};
-  if ((unsigned)idx[0] >= (unsigned)a.V || (unsigned)idx[1] >= (unsigned)a.V || (unsigned)idx[2] >= (unsigned)a.V) return;
-  int x[3], y[3];
-  float iz[3];
+  s->idx[0] = f[0]; s->idx[1] = f[1]; s->idx[2] = f[2];
+  if ((unsigned)s->idx[0] >= (unsigned)a.V || (unsigned)s->idx[1] >= (unsigned)a.V || (unsigned)s->idx[2] >= (unsigned)a.V)
+    return;
 #pragma unroll
   for (int k = 0; k < 3; ++k)
-    if (rs_vertex(v, a.vertices + 3 * (size_t)idx[k], &x[k], &y[k], &iz[k]) != RS_DRAWN) return;
-  long long area = (long long)(x[1] - x[0]) * (y[2] - y[0]) - (long long)(y[1] - y[0]) * (x[2] - x[0]);
+    if (rs_vertex(v, a.vertices + 3 * (size_t)s->idx[k], &s->x[k], &s->y[k], &s->iz[k]) != RS_DRAWN) return;
+  long long area = (long long)(s->x[1] - s->x[0]) * (s->y[2] - s->y[0]) - (long long)(s->y[1] - s->y[0]) * (s->x[2] - s->x[0]);
   if (area == 0) return;
-  const bool exchanged = area < 0;
-  if (exchanged) {
-    const int tx = x[1], ty = y[1], ti = idx[1];
-    const float tz = iz[1];
-    x[1] = x[2]; y[1] = y[2]; iz[1] = iz[2]; idx[1] = idx[2];
-    x[2] = tx; y[2] = ty; iz[2] = tz; idx[2] = ti;
+  s->exchanged = area < 0;
+  if (s->exchanged) {
+    const int tx = s->x[1], ty = s->y[1], ti = s->idx[1];
+    const float tz = s->iz[1];
+    s->x[1] = s->x[2]; s->y[1] = s->y[2]; s->iz[1] = s->iz[2]; s->idx[1] = s->idx[2];
+    s->x[2] = tx; s->y[2] = ty; s->iz[2] = tz; s->idx[2] = ti;
     area = -area;
   }
+  s->A = (float)area;
+  s->ok = true;
+}
+
+// The colour of the set-up triangle t at pixel (i, j) -> rgb, zeros if !s.ok.
+template <class Attr>
+__device__ __forceinline__ void rs_shade_at(const Attr& attr, const RsShadeTri& s, int t, int i, int j, float* rgb) {
+  rgb[0] = rgb[1] = rgb[2] = 0.f;
+  if (!s.ok) return;
   const int px = i << 8, py = j << 8;
-  const float A = (float)area;
   float w[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int p = (k + 1) % 3, q = (k + 2) % 3;
-    const long long e = (long long)(x[q] - x[p]) * (py - y[p]) - (long long)(y[q] - y[p]) * (px - x[p]);
-    const float l = (float)e / A;
-    w[k] = l * iz[k];
+    const long long e = (long long)(s.x[q] - s.x[p]) * (py - s.y[p]) - (long long)(s.y[q] - s.y[p]) * (px - s.x[p]);
+    const float l = (float)e / s.A;
+    w[k] = l * s.iz[k];
   }
   const float inv = (w[0] + w[1]) + w[2];
-  attr(t, idx, exchanged, w, inv, rgb);
+  attr(t, s.idx, s.exchanged, w, inv, rgb);
+}
+
+template <class Attr>
+__device__ __forceinline__ void rs_shade(const RsArgs& a, const Attr& attr, const RsView& v, int t, int i, int j,
+                                         float* rgb) {
+  RsShadeTri s;
+  rs_shade_setup(a, v, t, &s);
+  rs_shade_at(attr, s, t, i, j, rgb);
 }
 
 template <class Attr>
@@ -571,6 +607,268 @@ __global__ __launch_bounds__(kRsBlock) void rs_shade_resolve_kernel(const RsArgs
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// pxt_mesh_render_frame: up to PXT_MESH_FRAME_MAX_VIEWS views of one mesh in one call, each with its own size, its own
+// supersampling factor S and its own choice of outputs - the two images a tracker frame needs (the depth_nz plane at
+// the query camera, the anti-aliased 8-bit image at the reference camera) in four launches.  The first three launches
+// are pxt_mesh_raster's bodies on each view's fine lattice (S W x S H): what differs per view - the fine size, where its
+// key plane starts, S, where its outputs go - rides in the kernel arguments as a small table, the grid's second
+// dimension is the view, and a workgroup beyond its view's own extent exits at once.
+//
+// rf_resolve_kernel is the new part: one lane per OUTPUT pixel.  It reads the pixel's S x S keys in row-major order,
+// sets the winning triangle up again only when the key names another triangle than the previous subsample's (inside a
+// triangle all S^2 share one set-up; the three vertex transforms with their divisions are most of a subsample's work),
+// shades by the existing rule at the fine pixel, adds in the fixed order and scales by 1 / S^2.  A view's planes start
+// on aligned addresses of their own, so the byte planes go out as whole dwords through LDS as in
+// rs_shade_resolve_kernel, with only the view's last one to three pixels stored bytewise.
+struct RfView {
+  int W, H, S, Wf, Hf;     // output size, S, fine size
+  size_t key_off;          // the view's first key (an even number: the clear writes pairs)
+  float* out_rgba;         // each NULL when the view did not ask for it
+  unsigned char* out_rgb_u8;
+  float* out_depth;
+  unsigned char* out_nz;
+};
+
+struct RfArgs {
+  RsArgs a;  // W, H unused; keys: all views' planes
+  RfView g[PXT_MESH_FRAME_MAX_VIEWS];
+};
+
+// The fine view of a view's 20 floats (the header's rule, each step one fp32 operation); -> all of it is finite.
+__device__ __forceinline__ bool rf_load_view(const float* __restrict__ v20, const int S, RsView* v) {
+  const bool ok = rs_load_view(v20, v);
+  const float s = (float)S, h = 0.5f * (float)(S - 1);
+  v->fx = v->fx * s;
+  v->fy = v->fy * s;
+  v->cx = v->cx * s + h;
+  v->cy = v->cy * s + h;
+  return ok && rs_finite(v->fx) && rs_finite(v->fy) && rs_finite(v->cx) && rs_finite(v->cy);
+}
+
+__global__ __launch_bounds__(kRsBlock) void rf_clear_kernel(const RfArgs f, const size_t n_units) {
+  const RsArgs& a = f.a;
+  const size_t stride = (size_t)gridDim.x * kRsBlock;
+  const size_t g = (size_t)blockIdx.x * kRsBlock + threadIdx.x;
+  ulonglong2* k2 = (ulonglong2*)a.keys;
+  for (size_t u = g; u < n_units; u += stride) k2[u] = make_ulonglong2(kRsEmpty, kRsEmpty);
+  if (g < (size_t)a.P * PXT_MESH_RASTER_RECORD) {
+    const int view = (int)(g / PXT_MESH_RASTER_RECORD), w = (int)(g % PXT_MESH_RASTER_RECORD);
+    unsigned val = 0u;
+    if (w == RS_W_ZMIN) val = 0xffffffffu;
+    if (w == RS_W_STATUS) {
+      RsView v;
+      val = rf_load_view(a.views + (size_t)view * PXT_MESH_VIEW, f.g[view].S, &v) ? 0u : 0xffffffffu;
+    }
+    a.records[g] = val;
+  }
+  if (g < (size_t)a.P) a.list_count[g] = 0u;
+}
+
+__global__ __launch_bounds__(kRsTriBlock) void rf_triangle_kernel(const RfArgs f) {
+  __shared__ unsigned counts[6];
+  const int view = blockIdx.y;
+  const RfView& g = f.g[view];
+  RsView v;
+  if (!rf_load_view(f.a.views + (size_t)view * PXT_MESH_VIEW, g.S, &v)) return;  // the whole workgroup alike
+  rs_triangle_view(f.a, v, view, g.Wf, g.Hf, f.a.keys + g.key_off, counts, kRfWaveMax);
+}
+
+// Launch 3 of the frame call.  On a fine lattice the triangles of an ordinary mesh are "large" by the thousand (a
+// triangle 12 pixels wide is 48 fine pixels wide at S = 4), so the list is longer (kRfListCap) and a tile does not walk
+// it entry by entry: the workgroup tests 256 entries at once, one per lane, gathers the few whose box meets its tile in
+// LDS, and only those are set up and evaluated by every lane.  The smallest key is kept in a register as in
+// rs_list_view; the order in which the entries arrive does not matter to a minimum.
+__global__ __launch_bounds__(kRsBlock) void rf_list_kernel(const RfArgs f) {
+  __shared__ unsigned hits[kRsBlock];
+  __shared__ unsigned n_hits;
+  const int view = blockIdx.y, tid = threadIdx.x;
+  const RfView& g = f.g[view];
+  const RsArgs& a = f.a;
+  const int W = g.Wf, H = g.Hf;
+  const int tiles_x = (W + kRsTile - 1) / kRsTile, tiles_y = (H + kRsTile - 1) / kRsTile;
+  if ((int)blockIdx.x >= tiles_x * tiles_y) return;  // the grid is the largest view's
+  const int n = (int)min(a.list_count[view], (unsigned)a.cap);
+  if (n == 0) return;
+  RsView v;
+  if (!rf_load_view(a.views + (size_t)view * PXT_MESH_VIEW, g.S, &v)) return;  // never: such a view lists nothing
+  const int tx0 = ((int)blockIdx.x % tiles_x) * kRsTile, ty0 = ((int)blockIdx.x / tiles_x) * kRsTile;
+  const int i = tx0 + (tid & (kRsTile - 1)), j = ty0 + (tid / kRsTile);
+  const uint4* list = a.list + (size_t)view * a.cap;
+  unsigned long long best = kRsEmpty;
+  for (int base = 0; base < n; base += kRsBlock) {  // the whole workgroup alike
+    if (tid == 0) n_hits = 0u;
+    __syncthreads();
+    if (base + tid < n) {
+      const uint4 ent = list[base + tid];
+      const int bx0 = (int)(ent.y & 0xffffu), bx1 = (int)(ent.y >> 16), by0 = (int)(ent.z & 0xffffu), by1 = (int)(ent.z >> 16);
+      if (!(bx1 < tx0 || bx0 >= tx0 + kRsTile || by1 < ty0 || by0 >= ty0 + kRsTile)) hits[atomicAdd(&n_hits, 1u)] = ent.x;
+    }
+    __syncthreads();
+    const int m = (int)n_hits;  // <= kRsBlock
+    for (int e = 0; e < m; ++e) {
+      const int t = (int)hits[e];
+      if (t < 0 || t >= a.T) continue;
+      const int* tri = a.triangles + 3 * (size_t)t;
+      RsTri s;
+      if (rs_setup(v, a.vertices, a.V, tri[0], tri[1], tri[2], W, H, &s) != RS_DRAWN) continue;
+      unsigned zb;
+      if (i >= s.ix0 && i <= s.ix1 && j >= s.iy0 && j <= s.iy1 && rs_pixel(s, i, j, &zb)) best = min(best, rs_key(zb, t));
+    }
+    __syncthreads();  // hits is rewritten by the next round
+  }
+  if (best != kRsEmpty && i < W && j < H) atomicMin(a.keys + g.key_off + (size_t)j * W + i, best);
+}
+
+// The work of one workgroup of the resolve on a view whose supersample is S (a template argument: a row of the block
+// is unrolled and its keys are loaded before the first is used).
+template <class Attr, int S>
+__device__ __forceinline__ void rf_resolve_view(const RfArgs& f, const Attr& attr, const RfView& g, const int view,
+                                                const int wh, const int p0, unsigned (*red)[kRsWaves], unsigned* packed) {
+  const int tid = threadIdx.x;
+  const int Wf = g.Wf;
+  const bool want_rgb = g.out_rgba || g.out_rgb_u8, want_bytes = g.out_rgb_u8 || g.out_nz;
+  const unsigned long long* __restrict__ keys = f.a.keys + g.key_off;
+  const float scale = 1.0f / (float)(S * S);  // exact
+  RsView v;
+  rf_load_view(f.a.views + (size_t)view * PXT_MESH_VIEW, S, &v);  // a view that is not finite has no covered pixel
+  unsigned mn = 0xffffffffu, mx = 0u, cnt = 0u;
+  unsigned long long ahead[4] = {kRsEmpty, kRsEmpty, kRsEmpty, kRsEmpty};
+  if (S == 1) {  // one key per pixel: the lane's four are in flight together, as in rs_shade_resolve_kernel
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int pix = p0 + k * kRsBlock + tid;
+      if (pix < wh) ahead[k] = keys[pix];
+    }
+  }
+#pragma unroll 1
+  for (int k = 0; k < 4; ++k) {
+    const int pix = p0 + k * kRsBlock + tid;
+    unsigned pk = 0u;
+    if (pix < wh) {
+      const int i = pix % g.W, j = pix / g.W;
+      float acc[4] = {0.f, 0.f, 0.f, 0.f}, d = 0.f;
+      RsShadeTri tri;
+      tri.ok = false;
+      int tri_t = 0;
+      bool have = false;
+#pragma unroll 1
+      for (int sb = 0; sb < S; ++sb) {
+        unsigned long long ks[S];  // a row of the block: its keys are in flight together
+        if (S == 1) {
+          ks[0] = k == 0 ? ahead[0] : k == 1 ? ahead[1] : k == 2 ? ahead[2] : ahead[3];
+        } else {
+#pragma unroll
+          for (int sa = 0; sa < S; ++sa) ks[sa] = keys[(size_t)(S * j + sb) * Wf + (size_t)S * i + sa];
+        }
+#pragma unroll
+        for (int sa = 0; sa < S; ++sa) {
+          const unsigned long long key = ks[sa];
+          const bool cov = key != kRsEmpty;
+          float c[4] = {0.f, 0.f, 0.f, 0.f};
+          if (cov) {
+            const unsigned zb = (unsigned)(key >> 32);
+            const int t = (int)(unsigned)(key & 0xffffffffull);
+            mn = min(mn, zb);
+            mx = max(mx, zb);
+            ++cnt;
+            d = __builtin_bit_cast(float, zb) * v.depth_q;  // read for S == 1 alone
+            if (want_rgb) {
+              if (!have || t != tri_t) {  // neighbouring subsamples mostly share their triangle
+                rs_shade_setup(f.a, v, t, &tri);
+                tri_t = t;
+                have = true;
+              }
+              rs_shade_at(attr, tri, t, S * i + sa, S * j + sb, c);
+            }
+            c[3] = 1.0f;
+          }
+          if (sa == 0 && sb == 0) {
+#pragma unroll
+            for (int ch = 0; ch < 4; ++ch) acc[ch] = c[ch];
+          } else {
+#pragma unroll
+            for (int ch = 0; ch < 4; ++ch) acc[ch] = acc[ch] + c[ch];
+          }
+        }
+      }
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) acc[ch] = acc[ch] * scale;
+      if (g.out_depth) ((float4*)g.out_depth)[pix] = make_float4(d, d, d, acc[3]);  // S == 1: alpha is 0 or 1
+      if (g.out_rgba) ((float4*)g.out_rgba)[pix] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      pk = rs_u8(acc[0]) | (rs_u8(acc[1]) << 8) | (rs_u8(acc[2]) << 16) | (rs_u8(d) != 0u ? 1u << 24 : 0u);
+    }
+    if (want_bytes) packed[k * kRsBlock + tid] = pk;
+  }
+  if (want_bytes) {  // the whole workgroup alike
+    __syncthreads();
+    const uint4 q = ((const uint4*)packed)[tid];
+    const int p = p0 + 4 * tid;  // a multiple of four, and the planes are 4-byte aligned
+    if (p + 4 <= wh) {
+      if (g.out_rgb_u8) {
+        unsigned* o = (unsigned*)(g.out_rgb_u8 + 3 * (size_t)p);
+        o[0] = (q.x & 0xffffffu) | (q.y << 24);
+        o[1] = ((q.y >> 8) & 0xffffu) | (q.z << 16);
+        o[2] = ((q.z >> 16) & 0xffu) | (q.w << 8);
+      }
+      if (g.out_nz) *(unsigned*)(g.out_nz + p) = (q.x >> 24) | ((q.y >> 24) << 8) | ((q.z >> 24) << 16) | ((q.w >> 24) << 24);
+    } else {
+      const unsigned qs[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (p + k >= wh) continue;
+        if (g.out_rgb_u8) {
+          g.out_rgb_u8[3 * (size_t)(p + k) + 0] = (unsigned char)(qs[k] & 0xffu);
+          g.out_rgb_u8[3 * (size_t)(p + k) + 1] = (unsigned char)((qs[k] >> 8) & 0xffu);
+          g.out_rgb_u8[3 * (size_t)(p + k) + 2] = (unsigned char)((qs[k] >> 16) & 0xffu);
+        }
+        if (g.out_nz) g.out_nz[p + k] = (unsigned char)(qs[k] >> 24);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < PXT_WAVE; m <<= 1) {
+    mn = min(mn, (unsigned)__shfl_xor((int)mn, m, PXT_WAVE));
+    mx = max(mx, (unsigned)__shfl_xor((int)mx, m, PXT_WAVE));
+    cnt += (unsigned)__shfl_xor((int)cnt, m, PXT_WAVE);
+  }
+  if ((tid & (PXT_WAVE - 1)) == 0) {
+    red[0][tid / PXT_WAVE] = cnt;
+    red[1][tid / PXT_WAVE] = mn;
+    red[2][tid / PXT_WAVE] = mx;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned c = 0u, lo = 0xffffffffu, hi = 0u;
+#pragma unroll
+    for (int w = 0; w < kRsWaves; ++w) {
+      c += red[0][w];
+      lo = min(lo, red[1][w]);
+      hi = max(hi, red[2][w]);
+    }
+    if (c) {  // as rs_resolve_kernel
+      unsigned* rec = f.a.records + (size_t)view * PXT_MESH_RASTER_RECORD;
+      atomicAdd(rec + RS_W_COVERED, c);
+      if (lo < __hip_atomic_load(rec + RS_W_ZMIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(rec + RS_W_ZMIN, lo);
+      if (hi > __hip_atomic_load(rec + RS_W_ZMAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(rec + RS_W_ZMAX, hi);
+    }
+  }
+}
+
+template <class Attr>
+__global__ __launch_bounds__(kRsBlock) void rf_resolve_kernel(const RfArgs f, const Attr attr) {
+  __shared__ unsigned red[3][kRsWaves];
+  __shared__ __attribute__((aligned(16))) unsigned packed[kRsShadePixels];  // r | g << 8 | b << 16 | depth_nz << 24
+  const int view = blockIdx.y;
+  const RfView& g = f.g[view];
+  const int wh = g.W * g.H;  // <= 2^26
+  const int p0 = (int)blockIdx.x * kRsShadePixels;
+  if (p0 >= wh) return;  // the grid is the largest view's; the whole workgroup alike
+  if (g.S == 1) rf_resolve_view<Attr, 1>(f, attr, g, view, wh, p0, red, packed);
+  else if (g.S == 2) rf_resolve_view<Attr, 2>(f, attr, g, view, wh, p0, red, packed);
+  else rf_resolve_view<Attr, 4>(f, attr, g, view, wh, p0, red, packed);
+}
+
 constexpr int64_t kRsMaxPixels = (int64_t)1 << 26;
 constexpr int kRsMaxViews = 4096, kRsMaxCount = 1 << 24, kRsMaxTexture = 16384;
 
@@ -578,8 +876,47 @@ bool rs_sizes_ok(int P, int T, int W, int H) {
   return P >= 1 && P <= kRsMaxViews && T >= 1 && T <= kRsMaxCount && W >= 1 && H >= 1 && (int64_t)W * H <= kRsMaxPixels;
 }
 int rs_cap(int T) { return std::min(T, kRsListCap); }
+int rf_cap(int T) { return std::min(T, kRfListCap); }
 int64_t rs_key_bytes(int P, int W, int H) { return ((int64_t)P * W * H * 8 + 15) / 16 * 16; }
 int64_t rs_count_bytes(int P) { return ((int64_t)P * 4 + 15) / 16 * 16; }
+
+// pxt_mesh_render_frame's geometry [P][3] (width, height, S) -> the fine sizes are supported; *keys: the key planes'
+// total, each padded to an even number of keys.
+bool rf_geometry_ok(int P, int T, const int32_t* geometry, int64_t* keys) {
+  if (P < 1 || P > PXT_MESH_FRAME_MAX_VIEWS || T < 1 || T > kRsMaxCount || !geometry) return false;
+  int64_t n = 0;
+  for (int p = 0; p < P; ++p) {
+    const int64_t W = geometry[3 * p], H = geometry[3 * p + 1], S = geometry[3 * p + 2];
+    if (W < 1 || H < 1 || W > kRsMaxPixels || H > kRsMaxPixels || !(S == 1 || S == 2 || S == 4)) return false;
+    if (W * S * H * S > kRsMaxPixels) return false;  // < 2^58
+    n += (W * S * H * S + 1) / 2 * 2;
+  }
+  *keys = n;
+  return true;
+}
+
+template <class Attr>
+int rf_launch(const RfArgs& f, const Attr& attr, int64_t n_keys, hipStream_t s) {
+  const RsArgs& a = f.a;
+  int64_t tiles = 1, res = 1;
+  for (int p = 0; p < a.P; ++p) {
+    const RfView& g = f.g[p];
+    tiles = std::max<int64_t>(tiles, (int64_t)((g.Wf + kRsTile - 1) / kRsTile) * ((g.Hf + kRsTile - 1) / kRsTile));
+    res = std::max<int64_t>(res, ((int64_t)g.W * g.H + kRsShadePixels - 1) / kRsShadePixels);
+  }
+  const size_t n_units = (size_t)(n_keys / 2);
+  const size_t clear_work = std::max(n_units, (size_t)a.P * PXT_MESH_RASTER_RECORD);
+  const unsigned clear_blocks = (unsigned)std::min<size_t>((clear_work + kRsBlock - 1) / kRsBlock, 8192);
+  hipLaunchKernelGGL(rf_clear_kernel, dim3(clear_blocks), dim3(kRsBlock), 0, s, f, n_units);
+  PXT_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(rf_triangle_kernel, dim3((a.T + kRsTriBlock - 1) / kRsTriBlock, a.P), dim3(kRsTriBlock), 0, s, f);
+  PXT_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(rf_list_kernel, dim3((unsigned)tiles, a.P), dim3(kRsBlock), 0, s, f);
+  PXT_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(rf_resolve_kernel<Attr>, dim3((unsigned)res, a.P), dim3(kRsBlock), 0, s, f, attr);
+  PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}
 
 }  // namespace
 }  // namespace pxt
@@ -697,4 +1034,78 @@ extern "C" int pxt_mesh_render_textured(const float* vertices, int32_t n_vertice
                   tex_width <= kRsMaxTexture && tex_height >= 1 && tex_height <= kRsMaxTexture;
   return rs_render(vertices, n_vertices, triangles, n_triangles, attr, ok, views, n_views, width, height, out_rgba,
                    out_rgb_u8, out_depth, out_depth_nz, out_tri, records, workspace, stream);
+}
+
+extern "C" int64_t pxt_mesh_render_frame_workspace_bytes(int32_t n_views, int32_t n_triangles, const int32_t* geometry) {
+  int64_t n_keys;
+  if (!rf_geometry_ok(n_views, n_triangles, geometry, &n_keys)) return PXT_E_ARG;
+  return n_keys * 8 + rs_count_bytes(n_views) + (int64_t)n_views * rf_cap(n_triangles) * 16;
+}
+
+extern "C" int pxt_mesh_render_frame(const float* vertices, int32_t n_vertices, const int32_t* triangles,
+                                     int32_t n_triangles, const float* colors, const float* uvs, int32_t n_uvs,
+                                     const int32_t* triangle_uvs, const uint8_t* texture, int32_t tex_width,
+                                     int32_t tex_height, const float* views, int32_t n_views, const int32_t* geometry,
+                                     const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8, float* out_depth,
+                                     uint8_t* out_depth_nz, const int64_t* out_bytes, uint32_t* records, void* workspace,
+                                     void* stream) {
+  int64_t n_keys;
+  if (!rf_geometry_ok(n_views, n_triangles, geometry, &n_keys) || n_vertices < 1 || n_vertices > kRsMaxCount) return PXT_E_ARG;
+  if (!vertices || !triangles || !views || !out_offsets || !out_bytes || !records || !workspace) return PXT_E_ARG;
+  const bool textured = uvs || triangle_uvs || texture;
+  if ((colors != nullptr) == textured) return PXT_E_ARG;  // vertex colours or a texture map, one of the two
+  if (textured && !(uvs && triangle_uvs && texture && ((uintptr_t)uvs % 4) == 0 && ((uintptr_t)triangle_uvs % 4) == 0 &&
+                    ((uintptr_t)texture % 4) == 0 && n_uvs >= 1 && n_uvs <= kRsMaxCount && tex_width >= 1 &&
+                    tex_width <= kRsMaxTexture && tex_height >= 1 && tex_height <= kRsMaxTexture))
+    return PXT_E_ARG;
+  if (((uintptr_t)vertices % 4) != 0 || ((uintptr_t)triangles % 4) != 0 || ((uintptr_t)colors % 4) != 0 ||
+      ((uintptr_t)views % 4) != 0 || ((uintptr_t)records % 4) != 0 || ((uintptr_t)out_rgb_u8 % 4) != 0 ||
+      ((uintptr_t)out_depth_nz % 4) != 0 || ((uintptr_t)out_rgba % 16) != 0 || ((uintptr_t)out_depth % 16) != 0 ||
+      ((uintptr_t)workspace % 16) != 0)
+    return PXT_E_ARG;
+  RfArgs f;
+  RsArgs& a = f.a;
+  a.vertices = vertices; a.triangles = (const int*)triangles; a.views = views;
+  a.V = n_vertices; a.T = n_triangles; a.P = n_views; a.W = 0; a.H = 0; a.cap = rf_cap(n_triangles);
+  a.keys = (unsigned long long*)workspace;
+  a.list_count = (unsigned*)((char*)workspace + n_keys * 8);
+  a.list = (uint4*)((char*)workspace + n_keys * 8 + rs_count_bytes(n_views));
+  a.out_depth = nullptr; a.out_tri = nullptr; a.records = (unsigned*)records;
+  char* const base[4] = {(char*)out_rgba, (char*)out_rgb_u8, (char*)out_depth, (char*)out_depth_nz};
+  const int64_t pixel_bytes[4] = {16, 3, 16, 1}, align[4] = {16, 4, 16, 4};
+  int64_t key_off = 0;
+  for (int p = 0; p < PXT_MESH_FRAME_MAX_VIEWS; ++p) {
+    RfView& g = f.g[p];
+    g = RfView{};
+    if (p >= n_views) continue;
+    g.W = geometry[3 * p]; g.H = geometry[3 * p + 1]; g.S = geometry[3 * p + 2];
+    g.Wf = g.W * g.S; g.Hf = g.H * g.S;
+    g.key_off = (size_t)key_off;
+    key_off += ((int64_t)g.Wf * g.Hf + 1) / 2 * 2;
+    char* out[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool any = false;
+    for (int k = 0; k < 4; ++k) {
+      const int64_t off = out_offsets[4 * p + k];
+      if (off < 0) continue;
+      const int64_t bytes = (int64_t)g.W * g.H * pixel_bytes[k];
+      if (!base[k] || (off % align[k]) != 0 || out_bytes[k] < 0 || off > out_bytes[k] || bytes > out_bytes[k] - off)
+        return PXT_E_ARG;
+      if (k >= 2 && g.S != 1) return PXT_E_ARG;  // the depth outputs exist for S = 1 alone
+      out[k] = base[k] + off;
+      any = true;
+    }
+    if (!any) return PXT_E_ARG;
+    g.out_rgba = (float*)out[0]; g.out_rgb_u8 = (unsigned char*)out[1];
+    g.out_depth = (float*)out[2]; g.out_nz = (unsigned char*)out[3];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (textured) {
+    RsTexture attr;
+    attr.uvs = uvs; attr.triangle_uvs = (const int*)triangle_uvs; attr.texture = (const unsigned*)texture;
+    attr.n_uvs = n_uvs; attr.Wt = tex_width; attr.Ht = tex_height;
+    return rf_launch(f, attr, n_keys, s);
+  }
+  RsVertexColors attr;
+  attr.colors = colors;
+  return rf_launch(f, attr, n_keys, s);
 }

@@ -18,7 +18,8 @@ defaults are the reference's numbers (``create_sfm_from_obj.py:154-159``); ``cx,
 render goes through ``Camera.from_colmap``: pixel centres at integers, ``cx - 0.5``).
 
 This is the SfM half of an object directory.  ``nerf2sfm.pkl``, a NeRF snapshot and the ``aug_sfm`` augmentation are not
-produced.  A mesh with vertex colours is drawn with them (``mesh_render.read_mesh_colors``); one without is drawn with
+produced; the tracker's mesh template (``--template mesh --mesh FILE --reference_sfm D/ref``, ``mesh_template.py``) needs
+none of them.  A mesh with vertex colours is drawn with them (``mesh_render.read_mesh_colors``); one without is drawn with
 its texture map (``mesh_render.read_mesh_textured``; ``--texture`` names another image for the same UVs); one with
 neither is refused.
 """

@@ -20,6 +20,11 @@ pxt_mesh_render_textured): the same call with the colour read from one texture m
 pytorch3d's ``TexturesUV`` defaults as the reference's ``load_objs_as_meshes`` + ``render_image`` use them - row 0 of the
 map is v = 1, corners aligned, bilinear, the border clamped.  ``read_mesh_textured`` reads YCB's ``textured.obj`` with its
 ``.mtl`` and BOP's ``texture_u`` / ``texture_v`` PLYs.
+
+A frame's views (``MeshRenderer.render_frame``, ``supersampled_view``, ``frame_reference``, pxt_mesh_render_frame): up to
+eight views of the mesh in one call, each with its own size, its own outputs and ``supersample`` x ``supersample``
+samples per pixel, box-filtered in a fixed order - the tracker's ``depth_nz`` plane and its anti-aliased reference image
+from one call (``mesh_template.py``).
 """
 from __future__ import annotations
 
@@ -354,6 +359,78 @@ def shade_textured_reference(V, F, UV, FUV, texture, views, width: int, height: 
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# a frame's views: per-view sizes and supersampling (pxt_mesh_render_frame)
+# ---------------------------------------------------------------------------------------------------------------------
+FRAME_OUTPUTS = ("rgba", "rgb_u8", "depth", "depth_nz")
+FRAME_MAX_VIEWS = _lib.PXT_MESH_FRAME_MAX_VIEWS
+
+
+def supersampled_view(view20, S: int) -> np.ndarray:
+    """The fine view of pxt_mesh_render_frame: the 20 floats of a view and ``S`` in {1, 2, 4} -> the 20 floats of the
+    ``S W x S H`` view whose pixel ``(S i + a, S j + b)`` is the sample of pixel ``(i, j)`` at offset ``((a + 0.5) / S -
+    0.5, (b + 0.5) / S - 0.5)``; each step one float32 operation."""
+    if int(S) not in (1, 2, 4):
+        raise ValueError(f"supersample is 1, 2 or 4 (got {S})")
+    v = np.array(np.asarray(view20, np.float32).reshape(VIEW), np.float32)
+    s, h = _F(int(S)), _F(0.5) * _F(int(S) - 1)
+    with np.errstate(all="ignore"):
+        v[12] = v[12] * s
+        v[13] = v[13] * s
+        v[14] = (v[14] * s).astype(_F) + h
+        v[15] = (v[15] * s).astype(_F) + h
+    return v
+
+
+def _frame_request(request):
+    view, W, H, S, want = request
+    W, H, S, want = int(W), int(H), int(S), tuple(want)
+    if S not in (1, 2, 4):
+        raise ValueError(f"supersample is 1, 2 or 4 (got {S})")
+    if W < 1 or H < 1 or W * S * H * S > 1 << 26:
+        raise ValueError(f"{W} x {H} at supersample {S} is not supported (1..2^26 fine pixels)")
+    if not want or any(w not in FRAME_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"want names outputs of {FRAME_OUTPUTS} (got {want})")
+    if S > 1 and ("depth" in want or "depth_nz" in want):
+        raise ValueError(f"depth and depth_nz exist for supersample 1 alone (got {S})")
+    return np.asarray(view, np.float32).reshape(VIEW), W, H, S, want
+
+
+def box_sum(fine: np.ndarray, S: int) -> np.ndarray:
+    """``fine`` [S H, S W, C] float32 -> [H, W, C]: the S x S blocks summed in row-major order from the first sample on,
+    one float32 add each, then times ``1 / S^2``."""
+    acc = None
+    for b in range(S):
+        for a in range(S):
+            c = fine[b::S, a::S]
+            acc = c.astype(_F) if acc is None else (acc + c).astype(_F)
+    return (acc * _F(1.0 / (S * S))).astype(_F)
+
+
+def frame_reference(V, F, shading: dict, requests) -> list:
+    """The rule of pxt_mesh_render_frame in numpy: ``shade_reference`` (``shading = {"colors": C}``) or
+    ``shade_textured_reference`` (``{"uvs": UV, "triangle_uvs": FUV, "texture": tex}``) on each request's fine view,
+    then the ordered box sum.  ``requests``: ``(view20, width, height, supersample, want)`` each -> one dict per request
+    with the outputs it names and ``records`` [16] uint32 (the fine view's)."""
+    out = []
+    for request in requests:
+        view, W, H, S, want = _frame_request(request)
+        fine = supersampled_view(view, S)
+        if "colors" in shading:
+            rgba, _, depth, nz, _, recs = shade_reference(V, F, shading["colors"], fine[None], W * S, H * S)
+        else:
+            triangle_uvs = shading.get("triangle_uvs")
+            rgba, _, depth, nz, _, recs = shade_textured_reference(
+                V, F, shading["uvs"], np.asarray(F) if triangle_uvs is None else triangle_uvs, shading["texture"],
+                fine[None], W * S, H * S)
+        image = box_sum(rgba[0], S)
+        full = {"rgba": image, "rgb_u8": _u8(image[..., :3]), "depth": depth[0], "depth_nz": nz[0]}
+        res = {k: full[k] for k in want}
+        res["records"] = recs[0]
+        out.append(res)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the GPU renderer
 # ---------------------------------------------------------------------------------------------------------------------
 class MeshRenderer:
@@ -414,6 +491,7 @@ class MeshRenderer:
         self.vertices = torch.from_numpy(Vn).to(dev)
         self.triangles = torch.from_numpy(np.ascontiguousarray(Fn.astype(np.int32))).to(dev)
         self._workspace: Optional[torch.Tensor] = None
+        self._frame_plans: dict = {}
         self.colors = None if colors is None else torch.from_numpy(Cn).to(dev)
         self.uvs = self.triangle_uvs = self.texture = None
         if colors is None and uvs is not None:
@@ -458,6 +536,64 @@ class MeshRenderer:
             self._ops.mesh_render_textured(self.vertices, self.triangles, self.uvs, self.triangle_uvs, self.texture, v, W, H,
                                            *outs, records, self._workspace)
         out["records"] = records.cpu().numpy().view(np.uint32) if download_records else records
+        return out
+
+    def render_frame(self, requests, download_records: bool = True) -> list:
+        """Several views of the mesh, each with its own size, supersampling and outputs, in one call of four launches
+        (``torch.ops.pixtrack.mesh_render_frame``): ``requests`` = up to 8 of ``(view20, width, height, supersample in
+        {1, 2, 4}, want)``, ``want`` naming outputs of ``rgba`` [H, W, 4], ``rgb_u8`` uint8 [H, W, 3] and, for supersample
+        1, ``depth`` [H, W, 4] and ``depth_nz`` uint8 [H, W] -> one dict per request of device tensors and ``records``
+        ([16] uint32 numpy, or the int32 device tensor with ``download_records=False``).  A supersampled view is drawn on
+        the ``S W x S H`` lattice and box-filtered: colour premultiplied over black, alpha the covered fraction."""
+        if self.colors is None and self.texture is None:
+            raise _lib.PxtError("render_frame needs vertex colours or a texture map")
+        try:
+            reqs = [_frame_request(r) for r in requests]
+        except ValueError as e:
+            raise _lib.PxtError(f"render_frame: {e}") from None
+        P = len(reqs)
+        if not (1 <= P <= FRAME_MAX_VIEWS):
+            raise _lib.PxtError(f"render_frame takes 1..{FRAME_MAX_VIEWS} views (got {P})")
+        shape_key = tuple((W, H, S, want) for _, W, H, S, want in reqs)
+        plan = self._frame_plans.get(shape_key)
+        if plan is None:  # the planes' places in the four buffers and the workspace, once per shape set
+            sizes, offsets, geometry = [0, 0, 0, 0], [], []
+            for _, W, H, S, want in reqs:
+                geometry += [W, H, S]
+                for k, (name, px) in enumerate(zip(FRAME_OUTPUTS, (16, 3, 16, 1))):
+                    if name in want:
+                        offsets.append(sizes[k])
+                        sizes[k] += (W * H * px + 15) // 16 * 16
+                    else:
+                        offsets.append(-1)
+            need = int(_lib.lib().pxt_mesh_render_frame_workspace_bytes(P, self.n_triangles,
+                                                                        (_lib.C.c_int32 * len(geometry))(*geometry)))
+            if need <= 0:
+                raise _lib.PxtError(f"render_frame: the views {geometry} are not supported")
+            plan = (geometry, offsets, sizes, need)
+            self._frame_plans[shape_key] = plan
+        geometry, offsets, sizes, need = plan
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        views = torch.from_numpy(np.ascontiguousarray(np.stack([r[0] for r in reqs]))).to(self.device)
+        bufs = [None if n == 0 else torch.empty(n // (4 if k in (0, 2) else 1),
+                                                dtype=torch.float32 if k in (0, 2) else torch.uint8, device=self.device)
+                for k, n in enumerate(sizes)]
+        records = torch.empty((P, RECORD), dtype=torch.int32, device=self.device)
+        self._ops.mesh_render_frame(self.vertices, self.triangles, self.colors, self.uvs, self.triangle_uvs, self.texture,
+                                    views, geometry, offsets, *bufs, records, self._workspace)
+        rec = records.cpu().numpy().view(np.uint32) if download_records else records
+        out = []
+        for p, (_, W, H, S, want) in enumerate(reqs):
+            res = {}
+            for k, (name, px) in enumerate(zip(FRAME_OUTPUTS, (16, 3, 16, 1))):
+                if name in want:
+                    o, ch = offsets[4 * p + k], (4, 3, 4, 1)[k]
+                    e = px // ch  # bytes per element
+                    plane = bufs[k][o // e:o // e + W * H * ch]
+                    res[name] = plane.view(H, W) if ch == 1 else plane.view(H, W, ch)
+            res["records"] = rec[p]
+            out.append(res)
         return out
 
     @property

@@ -1,0 +1,89 @@
+"""The tracker's per-frame template from a mesh instead of a NeRF.
+
+Per frame ``PixLocPoseTrackerR9`` asks its renderer for two images at one pose: a ``depth_nz`` plane at the query camera
+(``depth_mask_plane`` makes the query mask of it) and an 8-bit image at the reference camera (SfM camera 1 x
+``reference_scale``), which the UNet encodes as the frame's reference.  ``MeshTemplate`` draws both from a coloured or
+textured mesh in one ``MeshRenderer.render_frame`` call (pxt_mesh_render_frame, four launches): view 0 is the query camera
+at one sample per pixel and gives ``depth_nz``; view 1 is the reference camera, anti-aliased by ``supersample`` x
+``supersample`` samples per pixel, and gives ``rgb_u8``.  The SfM model ``mesh_dataset`` builds from the same mesh is in the
+mesh's own frame, so the tracker's pose goes into the view record as it is: no ``nerf2sfm``, no snapshot.
+
+``supersample`` defaults to 2.  That is an untuned starting value: the NeRF template is rendered with ``spp = 8``, and
+which of 1, 2 and 4 tracks best on real sequences has not been measured.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import mesh_render as R
+from .geometry import Camera
+
+
+class MeshTemplate:
+    """``renderer``: a ``MeshRenderer`` with vertex colours or a texture map.  ``near``: the near plane of the view
+    records (a triangle with a vertex at or behind it is culled whole, as in pxt_mesh_raster)."""
+
+    def __init__(self, renderer: R.MeshRenderer, supersample: int = 2, near: float = 1e-6):
+        if int(supersample) not in (1, 2, 4):
+            raise ValueError(f"supersample is 1, 2 or 4 (got {supersample})")
+        if renderer.colors is None and renderer.texture is None:
+            raise ValueError("a mesh template needs a MeshRenderer with vertex colours or a texture map")
+        self.renderer = renderer
+        self.supersample = int(supersample)
+        self.near = float(near)
+        # the farthest a vertex lies from the mesh frame's origin: bounds a frame's depths, see depth_q
+        self.radius = float(np.linalg.norm(renderer.vertices_host.astype(np.float64), axis=1).max())
+
+    @classmethod
+    def from_files(cls, mesh, texture=None, mesh_scale: float = 1.0, device="cuda:0", supersample: int = 2,
+                   near: float = 1e-6) -> "MeshTemplate":
+        """A mesh file as ``mesh_dataset`` reads it: vertex colours (``read_mesh_colors``) or, without them, texture
+        coordinates and a map (``read_mesh_textured``; ``texture`` names another image for the same UVs)."""
+        V, F, C = R.read_mesh_colors(mesh)
+        if C is not None:
+            if texture:
+                raise ValueError(f"{mesh} has vertex colours; a texture goes with a mesh that has texture coordinates")
+            return cls(R.MeshRenderer(V * float(mesh_scale), F, device, colors=C), supersample, near)
+        textured = R.read_mesh_textured(mesh, require_image=texture is None)
+        if textured is None:
+            raise ValueError(f"{mesh} has no vertex colours and no texture coordinates")
+        V, F, uvs, triangle_uvs, image = textured
+        return cls(R.MeshRenderer(V * float(mesh_scale), F, device, uvs=uvs, triangle_uvs=triangle_uvs,
+                                  texture=R.read_texture(texture or image)), supersample, near)
+
+    def depth_q(self, pose) -> float:
+        """The factor on a frame's depths: 1 / (the origin's distance + the mesh's radius), so that every depth d lies in
+        (0, 1] and the ``depth_nz`` rule ``uint8(d * 255) != 0`` never wraps to 0 on a covered pixel farther than 1 / 255
+        of that bound."""
+        _, t = R._pose_Rt(pose)
+        return 1.0 / (float(np.linalg.norm(t)) + self.radius)
+
+    @staticmethod
+    def _same_view(a: Camera, b: Camera) -> bool:
+        da, db = (c._data.detach().cpu().double().numpy() for c in (a, b))
+        return da.ndim == 1 and db.ndim == 1 and np.array_equal(np.rint(da[:2]), np.rint(db[:2])) and np.array_equal(da[2:6], db[2:6])
+
+    def requests(self, pose, query_camera: Camera, reference_camera: Camera, want_depth: bool = False) -> list:
+        """The frame's ``render_frame`` requests: one view with both outputs when ``supersample`` is 1 and the two
+        cameras agree in size, fx, fy, cx and cy; else the query view (S = 1) and the reference view.  A camera with
+        lens terms is refused (``view_record``)."""
+        q = self.depth_q(pose)
+        size = lambda cam: tuple(int(round(float(x))) for x in cam.size.tolist())
+        vq = R.view_record(query_camera, pose, self.near, q)
+        vr = R.view_record(reference_camera, pose, self.near, q)
+        depth_outputs = ("depth_nz", "depth") if want_depth else ("depth_nz",)
+        if self.supersample == 1 and self._same_view(query_camera, reference_camera):
+            return [(vq, *size(query_camera), 1, depth_outputs + ("rgb_u8",))]
+        return [(vq, *size(query_camera), 1, depth_outputs), (vr, *size(reference_camera), self.supersample, ("rgb_u8",))]
+
+    def frame(self, pose, query_camera: Camera, reference_camera: Camera, want_depth: bool = False):
+        """-> ``(depth_nz uint8 [Hq, Wq], rgb_u8 uint8 [Hr, Wr, 3])`` device tensors at ``pose`` (world -> camera, a
+        ``Pose`` or 4x4), and with ``want_depth`` the query view's float depth image [Hq, Wq, 4] (depths times
+        ``depth_q(pose)``) as a third.  One call, four launches, nothing downloaded."""
+        out = self.renderer.render_frame(self.requests(pose, query_camera, reference_camera, want_depth),
+                                         download_records=False)
+        res = (out[0]["depth_nz"], out[-1]["rgb_u8"])
+        return res + (out[0]["depth"],) if want_depth else res

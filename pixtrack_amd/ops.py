@@ -201,6 +201,15 @@ SCHEMAS = {
         "(Tensor vertices, Tensor triangles, Tensor uvs, Tensor triangle_uvs, Tensor texture, Tensor views, int width, "
         "int height, Tensor(a!)? rgba, Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, "
         "Tensor(e!)? triangle_ids, Tensor(f!) records, Tensor(g!) workspace) -> ()"),
+    # a tracker frame's views of one mesh in one call (pxt_mesh_render_frame): colors, or uvs + triangle_uvs + texture;
+    # views [P, 20], P <= 8; geometry = P x (width, height, supersample in 1, 2, 4); offsets = P x (rgba, rgb_u8,
+    # depth, depth_nz): the byte offset of the view's plane in the flat buffer of that name (rgba, depth: float32;
+    # rgb_u8, depth_nz: uint8), -1 for an output the view does not ask for; records int32 [P, 16]; workspace: uint8,
+    # pxt_mesh_render_frame_workspace_bytes(P, T, geometry)
+    "mesh_render_frame": (
+        "(Tensor vertices, Tensor triangles, Tensor? colors, Tensor? uvs, Tensor? triangle_uvs, Tensor? texture, "
+        "Tensor views, int[] geometry, int[] offsets, Tensor(a!)? rgba, Tensor(b!)? rgb_u8, Tensor(c!)? depth, "
+        "Tensor(d!)? depth_nz, Tensor(e!) records, Tensor(f!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -1381,8 +1390,122 @@ def _mesh_render_textured(vertices, triangles, uvs, triangle_uvs, texture, views
         workspace.data_ptr(), _stream(vertices)), "pxt_mesh_render_textured")
 
 
+def mesh_frame_planes(geometry, offsets, what="mesh_render_frame"):
+    """The argument checks of mesh_render_frame that need no tensor: ``geometry`` = P x (width, height, supersample),
+    ``offsets`` = P x (rgba, rgb_u8, depth, depth_nz) byte offsets or -1 -> (P, the bytes each of the four buffers
+    must hold)."""
+    geometry, offsets = [int(x) for x in geometry], [int(x) for x in offsets]
+    P = len(geometry) // 3
+    if not (1 <= P <= _lib.PXT_MESH_FRAME_MAX_VIEWS) or len(geometry) != 3 * P or len(offsets) != 4 * P:
+        raise _lib.PxtError(f"{what}: geometry holds (width, height, supersample) and offsets four byte offsets for "
+                            f"each of 1..{_lib.PXT_MESH_FRAME_MAX_VIEWS} views (got {len(geometry)} and {len(offsets)} "
+                            "numbers)")
+    need = [0, 0, 0, 0]
+    spans = [[], [], [], []]
+    names = ("rgba", "rgb_u8", "depth", "depth_nz")
+    for p in range(P):
+        W, H, S = geometry[3 * p:3 * p + 3]
+        if S not in (1, 2, 4):
+            raise _lib.PxtError(f"{what}: view {p}: supersample is 1, 2 or 4 (got {S})")
+        if W < 1 or H < 1 or W * S * H * S > 1 << 26:
+            raise _lib.PxtError(f"{what}: view {p}: {W} x {H} at supersample {S} is not supported (1..2^26 fine pixels)")
+        off = offsets[4 * p:4 * p + 4]
+        if all(o < 0 for o in off):
+            raise _lib.PxtError(f"{what}: view {p} asks for no output")
+        if S > 1 and (off[2] >= 0 or off[3] >= 0):
+            raise _lib.PxtError(f"{what}: view {p}: depth and depth_nz exist for supersample 1 alone (got {S})")
+        for k, (o, px, al) in enumerate(zip(off, (16, 3, 16, 1), (16, 4, 16, 4))):
+            if o < 0:
+                continue
+            if o % al:
+                raise _lib.PxtError(f"{what}: view {p}: the {names[k]} offset {o} is not a multiple of {al}")
+            need[k] = max(need[k], o + W * H * px)
+            spans[k].append((o, o + W * H * px))
+    for k in range(4):
+        sp = sorted(spans[k])
+        if any(a[1] > b[0] for a, b in zip(sp, sp[1:])):
+            raise _lib.PxtError(f"{what}: two views' {names[k]} planes overlap")
+    return P, need
+
+
+def _mesh_render_frame(vertices, triangles, colors, uvs, triangle_uvs, texture, views, geometry, offsets, rgba, rgb_u8,
+                       depth, depth_nz, records, workspace):
+    what = "mesh_render_frame"
+    L = _lib.lib()
+    _f32c(vertices, "vertices")
+    _f32c(views, "views")
+    if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or triangles.dim() != 2 or int(triangles.shape[1]) != 3
+            or triangles.dtype != torch.int32 or not triangles.is_contiguous() or views.dim() != 2
+            or int(views.shape[1]) != _lib.PXT_MESH_VIEW):
+        raise _lib.PxtError(f"{what}: vertices {tuple(vertices.shape)} / triangles {tuple(triangles.shape)} "
+                            f"{triangles.dtype} / views {tuple(views.shape)}, expected float32 [V, 3] / contiguous int32 "
+                            f"[T, 3] / float32 [P, {_lib.PXT_MESH_VIEW}]")
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    P, need = mesh_frame_planes(geometry, offsets, what)
+    if int(views.shape[0]) != P:
+        raise _lib.PxtError(f"{what}: {int(views.shape[0])} views for {P} geometry entries")
+    textured = uvs is not None or triangle_uvs is not None or texture is not None
+    if (colors is not None) == textured:
+        raise _lib.PxtError(f"{what}: a mesh is drawn with colors or with uvs + triangle_uvs + texture, one of the two")
+    attrs = []
+    if textured:
+        if uvs is None or triangle_uvs is None or texture is None:
+            raise _lib.PxtError(f"{what}: a textured mesh needs uvs, triangle_uvs and texture")
+        _f32c(uvs, "uvs")
+        if uvs.dim() != 2 or int(uvs.shape[1]) != 2 or not (1 <= int(uvs.shape[0]) <= 1 << 24):
+            raise _lib.PxtError(f"{what}: uvs is {tuple(uvs.shape)}, expected float32 [1..2^24, 2]")
+        if triangle_uvs.dtype != torch.int32 or not triangle_uvs.is_contiguous() or tuple(triangle_uvs.shape) != (T, 3):
+            raise _lib.PxtError(f"{what}: triangle_uvs is a contiguous int32 [{T}, 3] tensor (got "
+                                f"{tuple(triangle_uvs.shape)}, {triangle_uvs.dtype})")
+        if (texture.dtype != torch.uint8 or not texture.is_contiguous() or texture.dim() != 3 or int(texture.shape[2]) != 4
+                or not (1 <= int(texture.shape[0]) <= 16384 and 1 <= int(texture.shape[1]) <= 16384)):
+            raise _lib.PxtError(f"{what}: texture is a contiguous uint8 [1..16384, 1..16384, 4] tensor (got "
+                                f"{tuple(texture.shape)}, {texture.dtype})")
+        attrs = [(uvs, "uvs"), (triangle_uvs, "triangle_uvs"), (texture, "texture")]
+    else:
+        _f32c(colors, "colors")
+        if tuple(colors.shape) != (V, 3):
+            raise _lib.PxtError(f"{what}: colors is {tuple(colors.shape)}, expected float32 [{V}, 3]")
+        attrs = [(colors, "colors")]
+    outs = [(rgba, "rgba", torch.float32), (rgb_u8, "rgb_u8", torch.uint8), (depth, "depth", torch.float32),
+            (depth_nz, "depth_nz", torch.uint8)]
+    out_bytes = []
+    for (t, name, dtype), n in zip(outs, need):
+        have = 0 if t is None else t.numel() * t.element_size()
+        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
+            raise _lib.PxtError(f"{what}: {name} is a contiguous {dtype} buffer (got {t.dtype})")
+        if have < n:
+            raise _lib.PxtError(f"{what}: {name} holds {have} bytes, the views' planes need {n}")
+        out_bytes.append(have)
+    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
+        raise _lib.PxtError(f"{what}: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
+                            f"(got {tuple(records.shape)}, {records.dtype})")
+    geo = (C.c_int32 * (3 * P))(*[int(x) for x in geometry])
+    off = (C.c_int64 * (4 * P))(*[int(x) for x in offsets])
+    cap = (C.c_int64 * 4)(*out_bytes)
+    bytes_needed = int(L.pxt_mesh_render_frame_workspace_bytes(P, T, geo)) if T >= 1 else -1
+    if bytes_needed <= 0 or not (1 <= V <= 1 << 24):
+        raise _lib.PxtError(f"{what}: {V} vertices, {T} triangles are not supported (1..2^24 vertices and triangles)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < bytes_needed:
+        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {bytes_needed} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    named = [(vertices, "vertices"), (triangles, "triangles"), *attrs, (views, "views"), (records, "records"),
+             (workspace, "workspace")] + [(t, name) for t, name, _ in outs if t is not None]
+    for t, name in named:
+        _lib.require_gpu(t, name)
+        if t.device != vertices.device:
+            raise _lib.PxtError(f"{what}: {name} is on {t.device}, the vertices on {vertices.device}")
+    _lib.check(L.pxt_mesh_render_frame(
+        vertices.data_ptr(), V, triangles.data_ptr(), T, _lib.dptr(colors), _lib.dptr(uvs),
+        0 if uvs is None else int(uvs.shape[0]), _lib.dptr(triangle_uvs), _lib.dptr(texture),
+        0 if texture is None else int(texture.shape[1]), 0 if texture is None else int(texture.shape[0]), views.data_ptr(),
+        P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth), _lib.dptr(depth_nz), cap, records.data_ptr(),
+        workspace.data_ptr(), _stream(vertices)), "pxt_mesh_render_frame")
+
+
 _IMPLS = {
     "mesh_raster": _mesh_raster,
+    "mesh_render_frame": _mesh_render_frame,
     "mesh_render": _mesh_render,
     "mesh_render_textured": _mesh_render_textured,
     "ngp_query": _ngp_query,

@@ -87,6 +87,9 @@ class MultiObjectTracker:
             if getattr(tr, "occlusion", None) is not None:
                 # (the batched render chain carries no float Depth image, and the step launches the LM itself)
                 raise ValueError("occlusion is not supported by lock-step tracking yet")
+            if getattr(tr, "template", None) is not None:
+                # (the step's batched render chain is the NeRF renderer's)
+                raise ValueError("a mesh template is not supported by lock-step tracking yet")
         # one UNet context runs every image of a group's step: the trackers must hold the same checkpoint in the same
         # precision (pixloc_megadepth is one network for all objects; reference pixloc_pose_refiners.py:49-60; the
         # signature names the precision)

@@ -54,7 +54,8 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
 class PixLocPoseTrackerR9(PoseTracker):
     def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
                  unet_precision="fp16", relocalizer=None, uncertainty=False, reference_points="sfm",
-                 point_report=False, depth_refine=None, occlusion=None):
+                 point_report=False, depth_refine=None, occlusion=None, template=None, reference_sfm=None,
+                 upright_ref_img=None):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
         synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
         ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet).
@@ -101,11 +102,23 @@ class PixLocPoseTrackerR9(PoseTracker):
         The cost gate, success and ``tracked`` are decided as ever.  ``render_ahead`` stays on: the render queued
         behind the LM launch keeps its float Depth image, and the pass runs in get_mask of the frame that consumes it.
         Shares the frame's one sensor upload with ``depth_refine`` (the two options must then name the same lookup and
-        scale).  Not combined with a relocalizer yet."""
+        scale).  Not combined with a relocalizer yet.
+        ``template``: None / "nerf" (default: the frame's mask and reference image are NeRF renders) or a
+        mesh_template.MeshTemplate - they are renders of a coloured or textured mesh, the reference image anti-aliased
+        by the template's ``supersample``, both from one pxt_mesh_render_frame call.  The SfM model is then one
+        mesh_dataset built from that mesh (it is in the mesh's own frame), no snapshot, ``nerf2sfm.pkl`` or $OBJ_AABB is
+        read (``assets`` may omit ``snapshot``, ``nerf2sfm`` and ``aabb``), ``testbed`` is None and ``render_ahead`` is
+        off: the queued render takes its camera from a NeRF camera slot.  Everything downstream of the two images is
+        unchanged.  A frame's history gains ``template`` ("mesh") and ``template_supersample``; nothing on the policy
+        path reads them.  Not combined with ``relocalizer``, ``reference_points="render"``, ``depth_refine`` or
+        ``occlusion`` yet (ValueError).
+        ``reference_sfm``: the directory of the SfM model (the ``ref/`` directory mesh_dataset wrote) in place of
+        ``loc_path/aug_sfm``; ``upright_ref_img``: the upright reference image's name in place of $UPRIGHT_REF_IMG."""
         point_report = parse_mode(point_report)  # (a bad value: ValueError before anything is built)
         self._check_reference_points(reference_points, relocalizer, uncertainty)
         self._check_depth_refine(depth_refine, relocalizer)
         self._check_occlusion(occlusion, relocalizer, depth_refine)
+        self.template = self._check_template(template, relocalizer, reference_points, depth_refine, occlusion)
         self.reference_points = reference_points
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
                               query_list="*_with_intrinsics.txt", global_descriptors="features.h5",
@@ -122,6 +135,9 @@ class PixLocPoseTrackerR9(PoseTracker):
         self.debug = debug
         self.device = torch.device(device if device is not None else "cuda:0")
         paths = default_paths.add_prefixes(Path(data_path), Path(loc_path), Path(eval_path))
+        if reference_sfm is not None:
+            paths["reference_sfm"] = Path(reference_sfm)
+        self._upright_ref_img = upright_ref_img
         if assets is not None:
             pixloc_conf["weights"] = assets["weights"]
             model3d = assets["model3d"]
@@ -149,13 +165,16 @@ class PixLocPoseTrackerR9(PoseTracker):
         self.reference_ids = self._initial_reference_ids(assets)
         self.reference_scale = 0.5
         self.localizer.refiner.reference_scale = self.reference_scale
-        if assets is not None:
-            self.nerf2sfm = assets["nerf2sfm"]
-            snapshot = assets["snapshot"]
+        if self.template is not None:  # the mesh is in the SfM model's frame: nothing of the NeRF is read
+            self.nerf2sfm = self.testbed = None
         else:
-            self.nerf2sfm = load_nerf2sfm(str(Path(data_path) / "nerf2sfm.pkl"))
-            snapshot = str(Path(object_path) / "pixtrack/instant-ngp/snapshots/weights.msgpack")
-        self.testbed = initialize_ingp(snapshot, self._render_aabb(assets), device=self.device)
+            if assets is not None:
+                self.nerf2sfm = assets["nerf2sfm"]
+                snapshot = assets["snapshot"]
+            else:
+                self.nerf2sfm = load_nerf2sfm(str(Path(data_path) / "nerf2sfm.pkl"))
+                snapshot = str(Path(object_path) / "pixtrack/instant-ngp/snapshots/weights.msgpack")
+            self.testbed = initialize_ingp(snapshot, self._render_aabb(assets), device=self.device)
         self.uncertainty = bool(uncertainty)
         self.localizer.refiner.information = self.uncertainty
         self.point_report = self.localizer.refiner.point_report = point_report
@@ -180,7 +199,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         # after the host has read the result, run the policy and converted the pose (~0.1 ms of GPU idle per frame).  They
         # are consumed only if the host, once it knows the pose, arrives at the same 12 camera floats; otherwise (failed
         # frame, cost gate, relocalisation, a different last bit) the frame renders as before.  PXT_RENDER_AHEAD=0: off.
-        self.render_ahead = os.environ.get("PXT_RENDER_AHEAD", "1") != "0"
+        self.render_ahead = os.environ.get("PXT_RENDER_AHEAD", "1") != "0" and self.template is None
         self._ahead_cam = None   # the pinned camera record the LM epilogue of this frame writes
         self._ahead = None       # the render queued behind the last LM launch
         self._ahead_ok = None    # ... once verified: (pose object it is valid for, mask, uint8 reference image, views, depth)
@@ -245,6 +264,30 @@ class PixLocPoseTrackerR9(PoseTracker):
                                  "built from the SfM points)")
             if uncertainty:
                 raise ValueError("reference_points='render' is not combined with uncertainty=True yet")
+
+    @staticmethod
+    def _check_template(template, relocalizer, reference_points, depth_refine, occlusion):
+        """-> None (the NeRF template) or the MeshTemplate; the options a mesh template is not combined with yet are
+        refused by name."""
+        if template is None or (isinstance(template, str) and template == "nerf"):
+            return None
+        from ..mesh_template import MeshTemplate
+
+        if not isinstance(template, MeshTemplate):
+            raise ValueError(f"template must be None, 'nerf' or a mesh_template.MeshTemplate (got {template!r})")
+        if relocalizer is not None and relocalizer != "off":
+            raise ValueError("a mesh template is not combined with a relocalizer yet (its hypothesis renders are NeRF "
+                             "renders)")
+        if reference_points == "render":
+            raise ValueError("a mesh template is not combined with reference_points='render' yet (the back-projection "
+                             "reads the NeRF renderer's view record)")
+        if depth_refine is not None:
+            raise ValueError("a mesh template is not combined with depth_refine yet (the option is measured and gated "
+                             "on NeRF sequences only)")
+        if occlusion is not None:
+            raise ValueError("a mesh template is not combined with occlusion yet (the pass compares the sensor with the "
+                             "NeRF's Depth render and its depth scale)")
+        return template
 
     supports_depth_refine = True  # (the YCB policy does not yet: its refine() does not end in _frame_policy)
 
@@ -377,7 +420,10 @@ class PixLocPoseTrackerR9(PoseTracker):
 
     def _initial_reference_ids(self, assets):
         """r9: the upright reference image named by $UPRIGHT_REF_IMG (:77-78)."""
-        upright_ref_img = assets["upright_ref_img"] if assets is not None else os.environ["UPRIGHT_REF_IMG"]
+        if assets is not None:
+            upright_ref_img = assets["upright_ref_img"]
+        else:
+            upright_ref_img = self._upright_ref_img if self._upright_ref_img else os.environ["UPRIGHT_REF_IMG"]
         return [self.localizer.model3d.name2id[upright_ref_img]]
 
     def _render_aabb(self, assets):
@@ -513,6 +559,10 @@ class PixLocPoseTrackerR9(PoseTracker):
             img = self._fused_reference[1]
             self._fused_reference = None
             return img
+        if self.template is not None:  # (a frame that rendered no mask: cold start, the frame after a failed one)
+            ref_u8 = self._mask_and_reference(pose, from_slot=False)[1]
+            self._fused_reference = None
+            return ref_u8
         ref_camera = self._reference_camera()
         rgba = get_nerf_image_device(self.testbed, self._nerf_pose(pose), ref_camera, spp=self.spp)
         return rgba_to_u8(rgba, 0.0)
@@ -612,7 +662,14 @@ class PixLocPoseTrackerR9(PoseTracker):
         launches on this stream.  ``from_slot``: the camera is the one the LM kernel ahead in the stream derived from its
         final pose (render-ahead); otherwise the host's conversion of ``pose``.  Sets ``_fused_reference`` when a pose
         object is given; returns (mask, ref_u8).  With reference_points="render" the Depth render also keeps its float
-        image (``_fused_depth`` / ``_last_depth``)."""
+        image (``_fused_depth`` / ``_last_depth``).  With a mesh template both planes come from one
+        ``MeshTemplate.frame`` call instead; everything after them is the same."""
+        if self.template is not None:
+            nz, ref_u8 = self.template.frame(pose, self.camera, self._reference_camera())
+            mask = self._mask_of(nz)
+            self._last_depth = None
+            self._fused_reference, self._fused_depth = (pose, ref_u8), None
+            return mask, ref_u8
         tb, spp = self.testbed, int(self.spp)
         want_depth = self.reference_points == "render" or self.occlusion is not None
         if not from_slot:
@@ -866,6 +923,8 @@ class PixLocPoseTrackerR9(PoseTracker):
             # the pinned record of this frame's extraction: its kernels ran ahead of the LM launch whose result is here
             rec = refiner.last_points_record
             ret["n_reference_points"], ret["reference_point_stride"] = (int(rec[2]), int(rec[1])) if rec is not None else (0, 0)
+        if self.template is not None:  # (added keys only where the option is on)
+            ret["template"], ret["template_supersample"] = "mesh", int(self.template.supersample)
         ret["reference_ids"] = self.reference_ids
         ret["query_path"] = query_path
         ret["cost"] = costs[best_ref_id]
@@ -933,7 +992,35 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--relocalize", choices=("off", "views"), default="off",
                         help="off (default: cold start from the upright view, a lost track stays lost) or views "
                              "(relocalise the cold start and the frame after a failed frame against the mapping views)")
+    parser.add_argument("--template", choices=("nerf", "mesh"), default="nerf",
+                        help="what a frame's mask and reference image are rendered from: nerf (default: the object's "
+                             "instant-ngp snapshot) or mesh (--mesh; no snapshot, nerf2sfm.pkl or $OBJ_AABB is read)")
+    parser.add_argument("--mesh", type=Path, default=None,
+                        help="--template mesh: the mesh, as mesh_dataset reads it (vertex colours, or a texture map)")
+    parser.add_argument("--texture", type=Path, default=None, help="the texture map, in place of the one the mesh names")
+    parser.add_argument("--mesh_scale", type=float, default=1.0, help="factor on the mesh's vertices (BOP's models are in mm)")
+    parser.add_argument("--mesh_supersample", type=int, choices=(1, 2, 4), default=2,
+                        help="samples per pixel and axis of the mesh template's reference image (default 2, untuned)")
+    parser.add_argument("--reference_sfm", type=Path, default=None,
+                        help="the SfM model's directory (the ref/ directory mesh_dataset wrote), in place of "
+                             "<object_path>/pixtrack/aug_nerf_sfm/aug_sfm")
+    parser.add_argument("--upright_ref_img", default=None,
+                        help="the name of the upright reference image (default: $UPRIGHT_REF_IMG)")
     return parser
+
+
+def template_from_args(args, device="cuda:0"):
+    """--template mesh and its companions -> a mesh_template.MeshTemplate (None for the NeRF template)."""
+    if getattr(args, "template", "nerf") != "mesh":
+        if getattr(args, "mesh", None) is not None:
+            raise ValueError("--mesh goes with --template mesh")
+        return None
+    if args.mesh is None:
+        raise ValueError("--template mesh needs --mesh")
+    from ..mesh_template import MeshTemplate
+
+    return MeshTemplate.from_files(args.mesh, texture=args.texture, mesh_scale=args.mesh_scale, device=device,
+                                   supersample=args.mesh_supersample)
 
 
 def _sensor_lookup_from_args(args, flag: str):
@@ -1000,7 +1087,9 @@ def main(argv=None):
         from ..parallel import bind_to_device_numa
 
         bind_to_device_numa(0)
-    tracker = PixLocPoseTrackerR9(depth_refine=depth_option_from_args(args), occlusion=occlusion_option_from_args(args),
+    tracker = PixLocPoseTrackerR9(template=template_from_args(args), reference_sfm=args.reference_sfm,
+                                  upright_ref_img=args.upright_ref_img,
+                                  depth_refine=depth_option_from_args(args), occlusion=occlusion_option_from_args(args),
                                   object_path=str(args.object_path), data_path=str(data_path),
                                   eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
                                   unet_precision=args.unet_precision, relocalizer=args.relocalize,

@@ -59,12 +59,12 @@ class GTFrameIterator:
 class PixLocPoseTrackerYCB(PixLocPoseTrackerR9):
     def __init__(self, data_path, loc_path, eval_path, object_path, debug=False, device=None, assets=None,
                  ycb_root=None, unet_precision="fp16", uncertainty=False, reference_points="sfm",
-                 point_report=False, depth_refine=None, occlusion=None):
+                 point_report=False, depth_refine=None, occlusion=None, **kw):
         self.object_path = object_path
         self.ycb_root = Path(ycb_root or os.environ.get("YCB_ROOT", "/data/ycb/"))
         super().__init__(object_path, data_path, loc_path, eval_path, debug=int(debug), device=device, assets=assets,
                          unet_precision=unet_precision, uncertainty=uncertainty, reference_points=reference_points,
-                         point_report=point_report, depth_refine=depth_refine, occlusion=occlusion)
+                         point_report=point_report, depth_refine=depth_refine, occlusion=occlusion, **kw)
         self.reference_scale = 0.3
         self.localizer.refiner.reference_scale = self.reference_scale
         self.localizer.refiner.conf.multiscale = [1]

@@ -638,6 +638,122 @@ def render_query_frames(assets, testbed, noise_sigma: float = 2.0, seed: int = 5
     return frames
 
 
+def make_bumpy_mesh(seed: int = 1002, subdivisions: int = 4, extent: float = 1.6, texture_size=(512, 256),
+                    texture_sigma: float = 6.0):
+    """A seeded, clearly asymmetric textured mesh: an icosphere pushed to an ellipsoid with a few smooth bumps, its
+    largest extent ``extent`` -> ``(V [n, 3], F [m, 3], UV [3 m, 2], FUV [m, 3], texture uint8 [Ht, Wt, 3])``.  The
+    UVs are per corner: two azimuthal-equidistant charts, z >= 0 on the map's left half and z < 0 on its right, a
+    triangle on the chart of its centroid; the map is a ``smooth_field``."""
+    from .mesh_render import icosphere
+
+    rng = np.random.default_rng(seed)
+    N, F = icosphere(subdivisions)
+    centres = rng.normal(size=(5, 3))
+    centres /= np.linalg.norm(centres, axis=1, keepdims=True)
+    amps, widths = rng.uniform(0.12, 0.3, size=5) * rng.choice([-1.0, 1.0], size=5, p=[0.3, 0.7]), rng.uniform(0.3, 0.55, size=5)
+    bump = sum(a * np.exp(-((N - c) ** 2).sum(1) / (2 * w * w)) for a, c, w in zip(amps, centres, widths))
+    V = N * np.asarray([0.62, 0.45, 1.0]) * (1.0 + bump)[:, None]
+    V *= extent / float((V.max(0) - V.min(0)).max())
+    up = N[F].mean(1)[:, 2] >= 0  # the chart of each triangle
+    n = N[F]  # [m, 3, 3]
+    theta = np.arccos(np.clip(np.where(up[:, None], n[..., 2], -n[..., 2]), -1.0, 1.0)) / (0.5 * np.pi)
+    phi = np.arctan2(n[..., 1], n[..., 0])
+    u = np.where(up[:, None], 0.25, 0.75) + 0.24 * theta * np.cos(phi)
+    v = 0.5 + 0.48 * theta * np.sin(phi)
+    UV = np.stack([u, v], -1).reshape(-1, 2)
+    FUV = np.arange(3 * len(F), dtype=np.int64).reshape(-1, 3)
+    Wt, Ht = texture_size
+    tex = np.clip(127.5 + 55.0 * smooth_field(rng, 3, Ht, Wt, texture_sigma), 0, 255).astype(np.uint8)
+    return V, F, UV, FUV, np.ascontiguousarray(tex.transpose(1, 2, 0))
+
+
+def make_mesh_tracking_assets(seed: int = 1002, width: int = 640, height: int = 480, n_frames: int = 200, out_dir=None,
+                              device="cuda:0", step_deg: float = 0.5, jitter_deg: float = 0.3, jitter_trans: float = 0.003,
+                              unet_seed: int = 7, reference_scale: float = 0.5, subdivisions: int = 4,
+                              texture_sigma: float = 6.0, ref_focal: Optional[float] = None):
+    """``make_tracking_assets`` for an object given as a mesh: the dict ``PixLocPoseTrackerR9(assets=..., template=
+    MeshTemplate(...))`` consumes - model3d, weights, covis, upright_ref_img; no snapshot, nerf2sfm or aabb - plus
+    ``mesh`` (``make_bumpy_mesh``'s tuple), ``mesh_shading`` (the keywords of ``MeshRenderer`` /
+    ``mesh_render.frame_reference``), ``gt_poses``, ``query_camera``, ``center``, ``width``, ``height`` and
+    ``reference_dir``.  All seeded.
+
+    The reference model is ``mesh_dataset.build_reference_from_mesh``'s (written to ``out_dir``, on ``device``): 42 views
+    of the reference size ``width / reference_scale x height / reference_scale``, loaded with ``Model3D``.  Its camera is
+    ``make_tracking_assets``' stand-in, ``f = 1.2 max(W, H)`` (``ref_focal`` names another), so that camera 1 x
+    ``reference_scale`` is the query camera: the synthetic UNet's random features are not scale-invariant, and a
+    reference image drawn 1.6 times the query's size (the focal length at which the builder's views would sit at
+    ``make_tracking_assets``' distance) biased every pose by 1.2 % in depth.  The query camera and the orbit + jitter
+    trajectory are ``make_tracking_assets``' own, starting beside mapping view 1 - and therefore at the builder's
+    look-at distance (the mesh's bounding sphere fills the narrower field of view), not at ``make_tracking_assets``'
+    distance rule, which no focal length reconciles with it at this reference camera."""
+    from pathlib import Path
+
+    from .mesh_dataset import build_reference_from_mesh
+    from .mesh_render import icosphere
+    from .model3d import Model3D
+    from .unet import make_synthetic_unet_weights
+
+    if out_dir is None:
+        raise ValueError("make_mesh_tracking_assets writes the reference model: out_dir is needed")
+    rng = np.random.default_rng(seed)
+    V, F, UV, FUV, tex = make_bumpy_mesh(seed + 10, subdivisions, texture_sigma=texture_sigma)
+    lo, hi = V.min(0), V.max(0)
+    center = 0.5 * (lo + hi)
+    f_q = 1.2 * max(width, height)
+    Wr, Hr = int(round(width / reference_scale)), int(round(height / reference_scale))
+    fr = 1.2 * max(Wr, Hr) if ref_focal is None else float(ref_focal)
+    out = Path(out_dir)
+    build_reference_from_mesh(V, F, None, out, Wr, Hr, fr, Wr / 2.0, Hr / 2.0, subdivisions=1, device=device, uvs=UV,
+                              triangle_uvs=FUV, texture=tex)
+    model3d = Model3D(out / "ref")
+
+    weights = make_synthetic_unet_weights(unet_seed)
+    wrng = np.random.default_rng(seed + 20)
+    for i in range(3):  # damping constants of the three per-level optimizers (absent checkpoint)
+        weights[f"optimizer.{i}.dampingnet.const"] = torch.from_numpy(wrng.uniform(-2.5, -1.5, size=6)).float()
+
+    # the trajectory: make_tracking_assets' orbit about the object's long axis (z) from mapping view 1, plus its jitter
+    up_axis = np.array([0.0, 0.0, 1.0])
+    R0, t0 = model3d.dbs[1].qvec2rotmat(), np.asarray(model3d.dbs[1].tvec, np.float64)
+    gt = []
+    Rc, tc = perturb_pose(R0, t0, rng, 0.8, 0.004, center)
+    for i in range(n_frames):
+        gt.append((Rc.copy(), tc.copy()))
+        dR = rodrigues(up_axis * math.radians(step_deg))
+        Rn = Rc @ dR
+        tn = Rc @ (center - dR @ center) + tc
+        Rc, tc = perturb_pose(Rn, tn, rng, jitter_deg * rng.uniform(), jitter_trans * rng.uniform(), center)
+    qcam = dict(model="SIMPLE_RADIAL", width=width, height=height, params=np.array([f_q, width / 2.0, height / 2.0, 0.0]))
+    return dict(model3d=model3d, weights=weights, covis=None, upright_ref_img=model3d.dbs[1].name, gt_poses=gt,
+                query_camera=qcam, center=center, width=width, height=height, mesh=(V, F, UV, FUV, tex),
+                mesh_shading=dict(uvs=UV, triangle_uvs=FUV, texture=tex), reference_dir=out / "ref")
+
+
+def render_mesh_query_frames(assets, renderer, noise_sigma: float = 2.0, seed: int = 5, first_frame_sigma: float = 12.0,
+                             cold_start_indices=(0,)):
+    """``render_query_frames`` for ``make_mesh_tracking_assets``: mesh renders at the GT poses with 4 x 4 samples per
+    pixel - a query is never the template's own image, which has at most 2 x 2 by default - plus the same noise scheme,
+    the noisier first frame included and for the same cost-gate reason.  ``renderer``: a ``MeshRenderer`` of the
+    assets' mesh.  float32 HWC 0..255 device tensors.  Setup only."""
+    from .mesh_render import view_record
+
+    cam = Camera.from_colmap(assets["query_camera"])
+    W, H = int(assets["width"]), int(assets["height"])
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    frames = []
+    for (Rg, tg) in assets["gt_poses"]:
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = Rg, tg
+        u8 = renderer.render_frame([(view_record(cam, T), W, H, 4, ("rgb_u8",))], download_records=False)[0]["rgb_u8"]
+        img = u8.float()
+        sigma = first_frame_sigma if (len(frames) in cold_start_indices and first_frame_sigma is not None) else noise_sigma
+        if sigma > 0:
+            noise = torch.randn(img.shape, generator=g) * sigma
+            img = (img + noise.to(img.device)).clamp_(0, 255).round_()
+        frames.append(img.contiguous())
+    return frames
+
+
 def write_object_dir(assets, object_path, query_dir=None, frames=None, ngp_layout: bool = True,
                      pixloc_checkpoint: bool = True):
     """Writes ``assets`` in the reference's on-disk layout (SURVEY 8b "CLI to preserve"):
