@@ -1332,6 +1332,56 @@ int pxt_mesh_render_frame(const float* vertices, int32_t n_vertices, const int32
                           uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
                           uint32_t* records, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Lock-step tracking from mesh templates: n_views (<= PXT_MESH_BATCH_MAX_VIEWS) views of up to
+ * PXT_MESH_BATCH_MAX_MESHES DIFFERENT meshes in ONE chain of launches on ONE stream (opt-in; csrc/pxt_raster.hip,
+ * mesh_render.render_frame_batch, MeshTemplate.frames, MultiObjectTracker).  Each view names its mesh and has its own
+ * size, supersample and choice of outputs.
+ *
+ * meshes [M] (HOST array): per mesh what pxt_mesh_render_frame takes - vertices, n_vertices, triangles, n_triangles and
+ *   exactly one shading group: colors (uvs, triangle_uvs, texture NULL) or uvs, n_uvs, triangle_uvs, texture, tex_width,
+ *   tex_height (colors NULL).  The pointers are device memory.  A mesh that no view names is allowed (it is still
+ *   checked), and so are descriptors that name the same arrays.
+ * view_mesh [P] int32 (HOST): the mesh of each view, 0 <= view_mesh[p] < M.
+ * views [P][20] float32 (HOST memory, unlike pxt_mesh_render_frame's): the 20 floats of every view travel in the
+ *   call's parameter record, so the per-frame view uploads of K trackers are one.
+ * geometry [P][3], out_offsets [P][4], out_rgba / out_rgb_u8 / out_depth / out_depth_nz, out_bytes [4] and
+ *   records [P][16] are exactly pxt_mesh_render_frame's.
+ * The rule.  Every output plane and the record of view p equal, bit for bit, what pxt_mesh_render_frame writes for that
+ *   view alone on mesh view_mesh[p]: a view's outputs are a pure function of its mesh, its 20 floats, its size and S -
+ *   they do not depend on M, P, the view's index, the other meshes or scheduling.
+ * Bounds: pxt_mesh_render_frame's per view and per mesh, 1 <= M <= 16, 1 <= P <= 32, 0 <= view_mesh[p] < M.  Anything
+ *   else is PXT_E_ARG and nothing is launched or written.
+ * workspace: device memory of pxt_mesh_render_frame_batch_workspace_bytes(M, n_triangles [M], P, view_mesh, geometry)
+ *   bytes (< 0: unsupported), 16-byte aligned: the views' key planes, every view's own triangle list of
+ *   min(T of its mesh, 16384) entries, and the call's parameter record (the mesh table, the view table, the views'
+ *   floats), which is uploaded with one asynchronous copy on `stream` ahead of the launches.  The workspace must stay
+ *   untouched until the chain has finished: one workspace per stream is enough, two streams must not share one.
+ * Launches on `stream`: clear, triangle (the grid's first dimension is the largest mesh's, the second the view; a
+ *   workgroup beyond its own mesh's triangles exits at once), list, and one resolve per shading kind that occurs -
+ *   four when all meshes share a kind, five when they are mixed, for any M and P.  No host synchronisation other than
+ *   the wait for the staging block's previous copy (a ring of pinned blocks per thread and device, allocated on first
+ *   use), no other allocation.  Measured on the MI355X: DESIGN.md 3.19.
+ * ---------------------------------------------------------------------- */
+#define PXT_MESH_BATCH_MAX_MESHES 16
+#define PXT_MESH_BATCH_MAX_VIEWS 32
+typedef struct pxt_mesh_desc {
+  const float* vertices;        /* [n_vertices][3] */
+  const int32_t* triangles;     /* [n_triangles][3] */
+  const float* colors;          /* [n_vertices][3], or NULL for a textured mesh */
+  const float* uvs;             /* [n_uvs][2] */
+  const int32_t* triangle_uvs;  /* [n_triangles][3] */
+  const uint8_t* texture;       /* [tex_height][tex_width][4] */
+  int32_t n_vertices, n_triangles, n_uvs, tex_width, tex_height, reserved;
+} pxt_mesh_desc;
+int64_t pxt_mesh_render_frame_batch_workspace_bytes(int32_t n_meshes, const int32_t* n_triangles, int32_t n_views,
+                                                    const int32_t* view_mesh, const int32_t* geometry);
+int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh,
+                                const float* views, int32_t n_views, const int32_t* geometry,
+                                const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8, float* out_depth,
+                                uint8_t* out_depth_nz, const int64_t* out_bytes, uint32_t* records, void* workspace,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,8 @@ PXT_ISO_CASE_TABLE_WORDS = 6 * 16 * 7
 PXT_MESH_VIEW = 20
 PXT_MESH_RASTER_RECORD = 16
 PXT_MESH_FRAME_MAX_VIEWS = 8
+PXT_MESH_BATCH_MAX_MESHES = 16
+PXT_MESH_BATCH_MAX_VIEWS = 32
 
 
 class PxtError(RuntimeError):
@@ -155,6 +157,25 @@ class NgpModel(C.Structure):
         ("cone_angle", C.c_float),
         ("depth_scale", C.c_float),
         ("linear_colors", C.c_int32),
+    ]
+
+
+class MeshDesc(C.Structure):
+    """pxt_mesh_desc: one mesh of pxt_mesh_render_frame_batch (device pointers; colors, or uvs + triangle_uvs +
+    texture)."""
+    _fields_ = [
+        ("vertices", C.c_void_p),
+        ("triangles", C.c_void_p),
+        ("colors", C.c_void_p),
+        ("uvs", C.c_void_p),
+        ("triangle_uvs", C.c_void_p),
+        ("texture", C.c_void_p),
+        ("n_vertices", C.c_int32),
+        ("n_triangles", C.c_int32),
+        ("n_uvs", C.c_int32),
+        ("tex_width", C.c_int32),
+        ("tex_height", C.c_int32),
+        ("reserved", C.c_int32),
     ]
 
 
@@ -374,6 +395,9 @@ PROTOTYPES = {
     "pxt_mesh_render_frame_workspace_bytes": (_I64, [_I32, _I32, _VP]),
     "pxt_mesh_render_frame": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _I32, _VP, _VP,
                                         _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pxt_mesh_render_frame_batch_workspace_bytes": (_I64, [_I32, _VP, _I32, _VP, _VP]),
+    "pxt_mesh_render_frame_batch": (C.c_int, [C.POINTER(MeshDesc), _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                              _VP, _VP, _VP, _VP]),
 }
 
 

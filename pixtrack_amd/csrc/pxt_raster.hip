@@ -646,8 +646,9 @@ __device__ __forceinline__ bool rf_load_view(const float* __restrict__ v20, cons
   return ok && rs_finite(v->fx) && rs_finite(v->fy) && rs_finite(v->cx) && rs_finite(v->cy);
 }
 
-__global__ __launch_bounds__(kRsBlock) void rf_clear_kernel(const RfArgs f, const size_t n_units) {
-  const RsArgs& a = f.a;
+// The work of one lane of launch 1 on a.P views whose floats are a.views; supersample(view) -> the view's S.
+template <class SupersampleOf>
+__device__ __forceinline__ void rf_clear(const RsArgs& a, const size_t n_units, const SupersampleOf& supersample) {
   const size_t stride = (size_t)gridDim.x * kRsBlock;
   const size_t g = (size_t)blockIdx.x * kRsBlock + threadIdx.x;
   ulonglong2* k2 = (ulonglong2*)a.keys;
@@ -658,11 +659,15 @@ __global__ __launch_bounds__(kRsBlock) void rf_clear_kernel(const RfArgs f, cons
     if (w == RS_W_ZMIN) val = 0xffffffffu;
     if (w == RS_W_STATUS) {
       RsView v;
-      val = rf_load_view(a.views + (size_t)view * PXT_MESH_VIEW, f.g[view].S, &v) ? 0u : 0xffffffffu;
+      val = rf_load_view(a.views + (size_t)view * PXT_MESH_VIEW, supersample(view), &v) ? 0u : 0xffffffffu;
     }
     a.records[g] = val;
   }
   if (g < (size_t)a.P) a.list_count[g] = 0u;
+}
+
+__global__ __launch_bounds__(kRsBlock) void rf_clear_kernel(const RfArgs f, const size_t n_units) {
+  rf_clear(f.a, n_units, [&f](int view) { return f.g[view].S; });
 }
 
 __global__ __launch_bounds__(kRsTriBlock) void rf_triangle_kernel(const RfArgs f) {
@@ -679,12 +684,9 @@ __global__ __launch_bounds__(kRsTriBlock) void rf_triangle_kernel(const RfArgs f
 // it entry by entry: the workgroup tests 256 entries at once, one per lane, gathers the few whose box meets its tile in
 // LDS, and only those are set up and evaluated by every lane.  The smallest key is kept in a register as in
 // rs_list_view; the order in which the entries arrive does not matter to a minimum.
-__global__ __launch_bounds__(kRsBlock) void rf_list_kernel(const RfArgs f) {
-  __shared__ unsigned hits[kRsBlock];
-  __shared__ unsigned n_hits;
-  const int view = blockIdx.y, tid = threadIdx.x;
-  const RfView& g = f.g[view];
-  const RsArgs& a = f.a;
+// `g` is the view's table entry; a.list_count[view], a.list + view * a.cap and the mesh of `a` are the view's.
+__device__ __forceinline__ void rf_list_view(const RsArgs& a, const RfView& g, const int view, unsigned* hits, unsigned* n_hits) {
+  const int tid = threadIdx.x;
   const int W = g.Wf, H = g.Hf;
   const int tiles_x = (W + kRsTile - 1) / kRsTile, tiles_y = (H + kRsTile - 1) / kRsTile;
   if ((int)blockIdx.x >= tiles_x * tiles_y) return;  // the grid is the largest view's
@@ -697,15 +699,15 @@ __global__ __launch_bounds__(kRsBlock) void rf_list_kernel(const RfArgs f) {
   const uint4* list = a.list + (size_t)view * a.cap;
   unsigned long long best = kRsEmpty;
   for (int base = 0; base < n; base += kRsBlock) {  // the whole workgroup alike
-    if (tid == 0) n_hits = 0u;
+    if (tid == 0) *n_hits = 0u;
     __syncthreads();
     if (base + tid < n) {
       const uint4 ent = list[base + tid];
       const int bx0 = (int)(ent.y & 0xffffu), bx1 = (int)(ent.y >> 16), by0 = (int)(ent.z & 0xffffu), by1 = (int)(ent.z >> 16);
-      if (!(bx1 < tx0 || bx0 >= tx0 + kRsTile || by1 < ty0 || by0 >= ty0 + kRsTile)) hits[atomicAdd(&n_hits, 1u)] = ent.x;
+      if (!(bx1 < tx0 || bx0 >= tx0 + kRsTile || by1 < ty0 || by0 >= ty0 + kRsTile)) hits[atomicAdd(n_hits, 1u)] = ent.x;
     }
     __syncthreads();
-    const int m = (int)n_hits;  // <= kRsBlock
+    const int m = (int)*n_hits;  // <= kRsBlock
     for (int e = 0; e < m; ++e) {
       const int t = (int)hits[e];
       if (t < 0 || t >= a.T) continue;
@@ -720,18 +722,24 @@ __global__ __launch_bounds__(kRsBlock) void rf_list_kernel(const RfArgs f) {
   if (best != kRsEmpty && i < W && j < H) atomicMin(a.keys + g.key_off + (size_t)j * W + i, best);
 }
 
+__global__ __launch_bounds__(kRsBlock) void rf_list_kernel(const RfArgs f) {
+  __shared__ unsigned hits[kRsBlock];
+  __shared__ unsigned n_hits;
+  rf_list_view(f.a, f.g[blockIdx.y], (int)blockIdx.y, hits, &n_hits);
+}
+
 // The work of one workgroup of the resolve on a view whose supersample is S (a template argument: a row of the block
 // is unrolled and its keys are loaded before the first is used).
 template <class Attr, int S>
-__device__ __forceinline__ void rf_resolve_view(const RfArgs& f, const Attr& attr, const RfView& g, const int view,
+__device__ __forceinline__ void rf_resolve_view(const RsArgs& a, const Attr& attr, const RfView& g, const int view,
                                                 const int wh, const int p0, unsigned (*red)[kRsWaves], unsigned* packed) {
   const int tid = threadIdx.x;
   const int Wf = g.Wf;
   const bool want_rgb = g.out_rgba || g.out_rgb_u8, want_bytes = g.out_rgb_u8 || g.out_nz;
-  const unsigned long long* __restrict__ keys = f.a.keys + g.key_off;
+  const unsigned long long* __restrict__ keys = a.keys + g.key_off;
   const float scale = 1.0f / (float)(S * S);  // exact
   RsView v;
-  rf_load_view(f.a.views + (size_t)view * PXT_MESH_VIEW, S, &v);  // a view that is not finite has no covered pixel
+  rf_load_view(a.views + (size_t)view * PXT_MESH_VIEW, S, &v);  // a view that is not finite has no covered pixel
   unsigned mn = 0xffffffffu, mx = 0u, cnt = 0u;
   unsigned long long ahead[4] = {kRsEmpty, kRsEmpty, kRsEmpty, kRsEmpty};
   if (S == 1) {  // one key per pixel: the lane's four are in flight together, as in rs_shade_resolve_kernel
@@ -775,7 +783,7 @@ __device__ __forceinline__ void rf_resolve_view(const RfArgs& f, const Attr& att
             d = __builtin_bit_cast(float, zb) * v.depth_q;  // read for S == 1 alone
             if (want_rgb) {
               if (!have || t != tri_t) {  // neighbouring subsamples mostly share their triangle
-                rs_shade_setup(f.a, v, t, &tri);
+                rs_shade_setup(a, v, t, &tri);
                 tri_t = t;
                 have = true;
               }
@@ -847,7 +855,7 @@ __device__ __forceinline__ void rf_resolve_view(const RfArgs& f, const Attr& att
       hi = max(hi, red[2][w]);
     }
     if (c) {  // as rs_resolve_kernel
-      unsigned* rec = f.a.records + (size_t)view * PXT_MESH_RASTER_RECORD;
+      unsigned* rec = a.records + (size_t)view * PXT_MESH_RASTER_RECORD;
       atomicAdd(rec + RS_W_COVERED, c);
       if (lo < __hip_atomic_load(rec + RS_W_ZMIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(rec + RS_W_ZMIN, lo);
       if (hi > __hip_atomic_load(rec + RS_W_ZMAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(rec + RS_W_ZMAX, hi);
@@ -864,9 +872,108 @@ __global__ __launch_bounds__(kRsBlock) void rf_resolve_kernel(const RfArgs f, co
   const int wh = g.W * g.H;  // <= 2^26
   const int p0 = (int)blockIdx.x * kRsShadePixels;
   if (p0 >= wh) return;  // the grid is the largest view's; the whole workgroup alike
-  if (g.S == 1) rf_resolve_view<Attr, 1>(f, attr, g, view, wh, p0, red, packed);
-  else if (g.S == 2) rf_resolve_view<Attr, 2>(f, attr, g, view, wh, p0, red, packed);
-  else rf_resolve_view<Attr, 4>(f, attr, g, view, wh, p0, red, packed);
+  if (g.S == 1) rf_resolve_view<Attr, 1>(f.a, attr, g, view, wh, p0, red, packed);
+  else if (g.S == 2) rf_resolve_view<Attr, 2>(f.a, attr, g, view, wh, p0, red, packed);
+  else rf_resolve_view<Attr, 4>(f.a, attr, g, view, wh, p0, red, packed);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// pxt_mesh_render_frame_batch: the frame call for views of up to PXT_MESH_BATCH_MAX_MESHES different meshes - K objects
+// tracked in lock-step - in one chain.  A view's table entry gains the mesh it draws, its own list and that list's cap;
+// the mesh table holds what pxt_mesh_render_frame takes per mesh.  The tables and the views' floats are one record in
+// the workspace (at 32 views they do not fit the kernel-argument segment), uploaded ahead of the chain, read-only for
+// all of it and addressed uniformly per workgroup.  A workgroup forms the RsArgs of its one view - the view's mesh, its
+// 20 floats, its list, its record - and runs the frame call's bodies on it as view 0: the arithmetic is theirs.
+struct RbMesh {
+  const float* vertices;
+  const int* triangles;
+  RsVertexColors colors;
+  RsTexture texture;
+  int V, T, textured;
+};
+
+struct RbView {
+  RfView g;
+  size_t list_off;  // the view's first list entry
+  int mesh, cap;    // cap = min(T of the mesh, kRfListCap)
+};
+
+struct RbRecord {
+  RbMesh mesh[PXT_MESH_BATCH_MAX_MESHES];
+  RbView view[PXT_MESH_BATCH_MAX_VIEWS];
+  float views[PXT_MESH_BATCH_MAX_VIEWS * PXT_MESH_VIEW];
+};
+
+struct RbArgs {
+  unsigned long long* keys;
+  unsigned* list_count;  // [P]
+  uint4* list;           // the views' lists, one after the other
+  unsigned* records;
+  int P;
+};
+
+__device__ __forceinline__ RsArgs rb_view_args(const RbRecord* __restrict__ rec, const RbArgs& b, const int view) {
+  const RbView& w = rec->view[view];
+  const RbMesh& m = rec->mesh[w.mesh];
+  RsArgs a;
+  a.vertices = m.vertices; a.triangles = m.triangles; a.views = rec->views + (size_t)view * PXT_MESH_VIEW;
+  a.V = m.V; a.T = m.T; a.P = 1; a.W = 0; a.H = 0; a.cap = w.cap;
+  a.keys = b.keys;
+  a.list_count = b.list_count + view;
+  a.list = b.list + w.list_off;
+  a.out_depth = nullptr; a.out_tri = nullptr;
+  a.records = b.records + (size_t)view * PXT_MESH_RASTER_RECORD;
+  return a;
+}
+
+__device__ __forceinline__ const RsVertexColors& rb_attr(const RbMesh& m, const RsVertexColors*) { return m.colors; }
+__device__ __forceinline__ const RsTexture& rb_attr(const RbMesh& m, const RsTexture*) { return m.texture; }
+__device__ __forceinline__ bool rb_takes(const RbMesh& m, const RsVertexColors*) { return !m.textured; }
+__device__ __forceinline__ bool rb_takes(const RbMesh& m, const RsTexture*) { return m.textured != 0; }
+
+__global__ __launch_bounds__(kRsBlock) void rb_clear_kernel(const RbRecord* __restrict__ rec, const RbArgs b, const size_t n_units) {
+  RsArgs a{};
+  a.views = rec->views; a.P = b.P; a.keys = b.keys; a.list_count = b.list_count; a.records = b.records;
+  rf_clear(a, n_units, [rec](int view) { return rec->view[view].g.S; });
+}
+
+__global__ __launch_bounds__(kRsTriBlock) void rb_triangle_kernel(const RbRecord* __restrict__ rec, const RbArgs b) {
+  __shared__ unsigned counts[6];
+  const int view = blockIdx.y;
+  const RsArgs a = rb_view_args(rec, b, view);
+  if ((int)blockIdx.x * kRsTriBlock >= a.T) return;  // the grid is the largest mesh's; the whole workgroup alike
+  const RfView g = rec->view[view].g;
+  RsView v;
+  if (!rf_load_view(a.views, g.S, &v)) return;  // the whole workgroup alike
+  rs_triangle_view(a, v, 0, g.Wf, g.Hf, a.keys + g.key_off, counts, kRfWaveMax);
+}
+
+__global__ __launch_bounds__(kRsBlock) void rb_list_kernel(const RbRecord* __restrict__ rec, const RbArgs b) {
+  __shared__ unsigned hits[kRsBlock];
+  __shared__ unsigned n_hits;
+  const int view = blockIdx.y;
+  const RsArgs a = rb_view_args(rec, b, view);
+  const RfView g = rec->view[view].g;
+  rf_list_view(a, g, 0, hits, &n_hits);
+}
+
+// One launch per shading kind that the call's views use; a view of the other kind exits at once.
+template <class Attr>
+__global__ __launch_bounds__(kRsBlock) void rb_resolve_kernel(const RbRecord* __restrict__ rec, const RbArgs b) {
+  __shared__ unsigned red[3][kRsWaves];
+  __shared__ __attribute__((aligned(16))) unsigned packed[kRsShadePixels];
+  const int view = blockIdx.y;
+  const RbMesh& m = rec->mesh[rec->view[view].mesh];
+  if (!rb_takes(m, (const Attr*)nullptr)) return;  // the whole workgroup alike
+  const RfView g = rec->view[view].g;
+  const int wh = g.W * g.H;  // <= 2^26
+  const int p0 = (int)blockIdx.x * kRsShadePixels;
+  if (p0 >= wh) return;  // the grid is the largest view's; the whole workgroup alike
+  const RsArgs a = rb_view_args(rec, b, view);
+  const Attr attr = rb_attr(m, (const Attr*)nullptr);
+  if (g.S == 1) rf_resolve_view<Attr, 1>(a, attr, g, 0, wh, p0, red, packed);
+  else if (g.S == 2) rf_resolve_view<Attr, 2>(a, attr, g, 0, wh, p0, red, packed);
+  else rf_resolve_view<Attr, 4>(a, attr, g, 0, wh, p0, red, packed);
 }
 
 constexpr int64_t kRsMaxPixels = (int64_t)1 << 26;
@@ -882,8 +989,8 @@ int64_t rs_count_bytes(int P) { return ((int64_t)P * 4 + 15) / 16 * 16; }
 
 // pxt_mesh_render_frame's geometry [P][3] (width, height, S) -> the fine sizes are supported; *keys: the key planes'
 // total, each padded to an even number of keys.
-bool rf_geometry_ok(int P, int T, const int32_t* geometry, int64_t* keys) {
-  if (P < 1 || P > PXT_MESH_FRAME_MAX_VIEWS || T < 1 || T > kRsMaxCount || !geometry) return false;
+bool rf_geometry_ok(int P, int T, const int32_t* geometry, int64_t* keys, int max_views = PXT_MESH_FRAME_MAX_VIEWS) {
+  if (P < 1 || P > max_views || T < 1 || T > kRsMaxCount || !geometry) return false;
   int64_t n = 0;
   for (int p = 0; p < P; ++p) {
     const int64_t W = geometry[3 * p], H = geometry[3 * p + 1], S = geometry[3 * p + 2];
@@ -893,6 +1000,43 @@ bool rf_geometry_ok(int P, int T, const int32_t* geometry, int64_t* keys) {
   }
   *keys = n;
   return true;
+}
+
+// View p's table entry from geometry and out_offsets (pxt_mesh_render_frame's rules); *key_off: the running key offset.
+// -> the view's planes are aligned, fit their buffers and are at least one.
+bool rf_place_view(int p, const int32_t* geometry, const int64_t* out_offsets, char* const* base, const int64_t* out_bytes,
+                   int64_t* key_off, RfView* gp) {
+  const int64_t pixel_bytes[4] = {16, 3, 16, 1}, align[4] = {16, 4, 16, 4};
+  RfView& g = *gp;
+  g = RfView{};
+  g.W = geometry[3 * p]; g.H = geometry[3 * p + 1]; g.S = geometry[3 * p + 2];
+  g.Wf = g.W * g.S; g.Hf = g.H * g.S;
+  g.key_off = (size_t)*key_off;
+  *key_off += ((int64_t)g.Wf * g.Hf + 1) / 2 * 2;
+  char* out[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool any = false;
+  for (int k = 0; k < 4; ++k) {
+    const int64_t off = out_offsets[4 * p + k];
+    if (off < 0) continue;
+    const int64_t bytes = (int64_t)g.W * g.H * pixel_bytes[k];
+    if (!base[k] || (off % align[k]) != 0 || out_bytes[k] < 0 || off > out_bytes[k] || bytes > out_bytes[k] - off)
+      return false;
+    if (k >= 2 && g.S != 1) return false;  // the depth outputs exist for S = 1 alone
+    out[k] = base[k] + off;
+    any = true;
+  }
+  if (!any) return false;
+  g.out_rgba = (float*)out[0]; g.out_rgb_u8 = (unsigned char*)out[1];
+  g.out_depth = (float*)out[2]; g.out_nz = (unsigned char*)out[3];
+  return true;
+}
+
+// A mesh's texture arguments are complete, aligned and in range.
+bool rs_texture_ok(const float* uvs, int32_t n_uvs, const int32_t* triangle_uvs, const uint8_t* texture, int32_t tex_width,
+                   int32_t tex_height) {
+  return uvs && triangle_uvs && texture && ((uintptr_t)uvs % 4) == 0 && ((uintptr_t)triangle_uvs % 4) == 0 &&
+         ((uintptr_t)texture % 4) == 0 && n_uvs >= 1 && n_uvs <= kRsMaxCount && tex_width >= 1 &&
+         tex_width <= kRsMaxTexture && tex_height >= 1 && tex_height <= kRsMaxTexture;
 }
 
 template <class Attr>
@@ -917,6 +1061,39 @@ int rf_launch(const RfArgs& f, const Attr& attr, int64_t n_keys, hipStream_t s) 
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;
 }
+
+// pxt_mesh_render_frame_batch's workspace: the key planes, the list counters, every view's own list (placed by a prefix
+// sum of the caps), the parameter record.
+struct RbLayout {
+  int64_t n_keys, count_off, list_off, record_off, bytes;
+  int64_t view_list[PXT_MESH_BATCH_MAX_VIEWS];  // first entry of each view's list
+};
+
+bool rb_layout(int M, const int32_t* n_triangles, int P, const int32_t* view_mesh, const int32_t* geometry, RbLayout* l) {
+  if (M < 1 || M > PXT_MESH_BATCH_MAX_MESHES || !n_triangles || !view_mesh) return false;
+  for (int m = 0; m < M; ++m)
+    if (n_triangles[m] < 1 || n_triangles[m] > kRsMaxCount) return false;
+  if (!rf_geometry_ok(P, 1, geometry, &l->n_keys, PXT_MESH_BATCH_MAX_VIEWS)) return false;
+  int64_t entries = 0;
+  for (int p = 0; p < P; ++p) {
+    if (view_mesh[p] < 0 || view_mesh[p] >= M) return false;
+    l->view_list[p] = entries;
+    entries += rf_cap(n_triangles[view_mesh[p]]);
+  }
+  l->count_off = l->n_keys * 8;
+  l->list_off = l->count_off + rs_count_bytes(P);
+  l->record_off = l->list_off + entries * 16;
+  l->bytes = l->record_off + (int64_t)(sizeof(RbRecord) + 15) / 16 * 16;
+  return true;
+}
+
+// The pinned blocks the parameter record is staged in: a ring per thread and device; a block is reused once its
+// previous copy has been made (pxt_ngp_render_frame_batch's scheme).
+struct RbStageSlot {
+  RbRecord* host = nullptr;
+  hipEvent_t copied = nullptr;
+};
+constexpr int kRbStageSlots = 4, kRbStageDevices = 16;
 
 }  // namespace
 }  // namespace pxt
@@ -1029,9 +1206,7 @@ extern "C" int pxt_mesh_render_textured(const float* vertices, int32_t n_vertice
   RsTexture attr;
   attr.uvs = uvs; attr.triangle_uvs = (const int*)triangle_uvs; attr.texture = (const unsigned*)texture;
   attr.n_uvs = n_uvs; attr.Wt = tex_width; attr.Ht = tex_height;
-  const bool ok = uvs && triangle_uvs && texture && ((uintptr_t)uvs % 4) == 0 && ((uintptr_t)triangle_uvs % 4) == 0 &&
-                  ((uintptr_t)texture % 4) == 0 && n_uvs >= 1 && n_uvs <= kRsMaxCount && tex_width >= 1 &&
-                  tex_width <= kRsMaxTexture && tex_height >= 1 && tex_height <= kRsMaxTexture;
+  const bool ok = rs_texture_ok(uvs, n_uvs, triangle_uvs, texture, tex_width, tex_height);
   return rs_render(vertices, n_vertices, triangles, n_triangles, attr, ok, views, n_views, width, height, out_rgba,
                    out_rgb_u8, out_depth, out_depth_nz, out_tri, records, workspace, stream);
 }
@@ -1054,10 +1229,7 @@ extern "C" int pxt_mesh_render_frame(const float* vertices, int32_t n_vertices, 
   if (!vertices || !triangles || !views || !out_offsets || !out_bytes || !records || !workspace) return PXT_E_ARG;
   const bool textured = uvs || triangle_uvs || texture;
   if ((colors != nullptr) == textured) return PXT_E_ARG;  // vertex colours or a texture map, one of the two
-  if (textured && !(uvs && triangle_uvs && texture && ((uintptr_t)uvs % 4) == 0 && ((uintptr_t)triangle_uvs % 4) == 0 &&
-                    ((uintptr_t)texture % 4) == 0 && n_uvs >= 1 && n_uvs <= kRsMaxCount && tex_width >= 1 &&
-                    tex_width <= kRsMaxTexture && tex_height >= 1 && tex_height <= kRsMaxTexture))
-    return PXT_E_ARG;
+  if (textured && !rs_texture_ok(uvs, n_uvs, triangle_uvs, texture, tex_width, tex_height)) return PXT_E_ARG;
   if (((uintptr_t)vertices % 4) != 0 || ((uintptr_t)triangles % 4) != 0 || ((uintptr_t)colors % 4) != 0 ||
       ((uintptr_t)views % 4) != 0 || ((uintptr_t)records % 4) != 0 || ((uintptr_t)out_rgb_u8 % 4) != 0 ||
       ((uintptr_t)out_depth_nz % 4) != 0 || ((uintptr_t)out_rgba % 16) != 0 || ((uintptr_t)out_depth % 16) != 0 ||
@@ -1072,31 +1244,10 @@ extern "C" int pxt_mesh_render_frame(const float* vertices, int32_t n_vertices, 
   a.list = (uint4*)((char*)workspace + n_keys * 8 + rs_count_bytes(n_views));
   a.out_depth = nullptr; a.out_tri = nullptr; a.records = (unsigned*)records;
   char* const base[4] = {(char*)out_rgba, (char*)out_rgb_u8, (char*)out_depth, (char*)out_depth_nz};
-  const int64_t pixel_bytes[4] = {16, 3, 16, 1}, align[4] = {16, 4, 16, 4};
   int64_t key_off = 0;
   for (int p = 0; p < PXT_MESH_FRAME_MAX_VIEWS; ++p) {
-    RfView& g = f.g[p];
-    g = RfView{};
-    if (p >= n_views) continue;
-    g.W = geometry[3 * p]; g.H = geometry[3 * p + 1]; g.S = geometry[3 * p + 2];
-    g.Wf = g.W * g.S; g.Hf = g.H * g.S;
-    g.key_off = (size_t)key_off;
-    key_off += ((int64_t)g.Wf * g.Hf + 1) / 2 * 2;
-    char* out[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool any = false;
-    for (int k = 0; k < 4; ++k) {
-      const int64_t off = out_offsets[4 * p + k];
-      if (off < 0) continue;
-      const int64_t bytes = (int64_t)g.W * g.H * pixel_bytes[k];
-      if (!base[k] || (off % align[k]) != 0 || out_bytes[k] < 0 || off > out_bytes[k] || bytes > out_bytes[k] - off)
-        return PXT_E_ARG;
-      if (k >= 2 && g.S != 1) return PXT_E_ARG;  // the depth outputs exist for S = 1 alone
-      out[k] = base[k] + off;
-      any = true;
-    }
-    if (!any) return PXT_E_ARG;
-    g.out_rgba = (float*)out[0]; g.out_rgb_u8 = (unsigned char*)out[1];
-    g.out_depth = (float*)out[2]; g.out_nz = (unsigned char*)out[3];
+    f.g[p] = RfView{};
+    if (p < n_views && !rf_place_view(p, geometry, out_offsets, base, out_bytes, &key_off, &f.g[p])) return PXT_E_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
   if (textured) {
@@ -1108,4 +1259,112 @@ extern "C" int pxt_mesh_render_frame(const float* vertices, int32_t n_vertices, 
   RsVertexColors attr;
   attr.colors = colors;
   return rf_launch(f, attr, n_keys, s);
+}
+
+extern "C" int64_t pxt_mesh_render_frame_batch_workspace_bytes(int32_t n_meshes, const int32_t* n_triangles, int32_t n_views,
+                                                               const int32_t* view_mesh, const int32_t* geometry) {
+  RbLayout l;
+  if (!rb_layout(n_meshes, n_triangles, n_views, view_mesh, geometry, &l)) return PXT_E_ARG;
+  return l.bytes;
+}
+
+extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh,
+                                           const float* views, int32_t n_views, const int32_t* geometry,
+                                           const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8,
+                                           float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
+                                           uint32_t* records, void* workspace, void* stream) {
+  if (!meshes || n_meshes < 1 || n_meshes > PXT_MESH_BATCH_MAX_MESHES) return PXT_E_ARG;
+  int32_t n_triangles[PXT_MESH_BATCH_MAX_MESHES];
+  for (int m = 0; m < n_meshes; ++m) n_triangles[m] = meshes[m].n_triangles;
+  RbLayout l;
+  if (!rb_layout(n_meshes, n_triangles, n_views, view_mesh, geometry, &l)) return PXT_E_ARG;
+  if (!views || !out_offsets || !out_bytes || !records || !workspace) return PXT_E_ARG;
+  if (((uintptr_t)views % 4) != 0 || ((uintptr_t)records % 4) != 0 || ((uintptr_t)out_rgb_u8 % 4) != 0 ||
+      ((uintptr_t)out_depth_nz % 4) != 0 || ((uintptr_t)out_rgba % 16) != 0 || ((uintptr_t)out_depth % 16) != 0 ||
+      ((uintptr_t)workspace % 16) != 0)
+    return PXT_E_ARG;
+  bool kind[2] = {false, false};  // vertex colours, texture: a mesh counts where a view draws it
+  for (int m = 0; m < n_meshes; ++m) {
+    const pxt_mesh_desc& d = meshes[m];
+    if (d.n_vertices < 1 || d.n_vertices > kRsMaxCount || !d.vertices || !d.triangles) return PXT_E_ARG;
+    if (((uintptr_t)d.vertices % 4) != 0 || ((uintptr_t)d.triangles % 4) != 0 || ((uintptr_t)d.colors % 4) != 0) return PXT_E_ARG;
+    const bool textured = d.uvs || d.triangle_uvs || d.texture;
+    if ((d.colors != nullptr) == textured) return PXT_E_ARG;  // vertex colours or a texture map, one of the two
+    if (textured && !rs_texture_ok(d.uvs, d.n_uvs, d.triangle_uvs, d.texture, d.tex_width, d.tex_height)) return PXT_E_ARG;
+  }
+  RbView table[PXT_MESH_BATCH_MAX_VIEWS];
+  char* const base[4] = {(char*)out_rgba, (char*)out_rgb_u8, (char*)out_depth, (char*)out_depth_nz};
+  int64_t key_off = 0, tiles = 1, res = 1;
+  int max_T = 1;
+  for (int p = 0; p < n_views; ++p) {
+    RbView& w = table[p];
+    if (!rf_place_view(p, geometry, out_offsets, base, out_bytes, &key_off, &w.g)) return PXT_E_ARG;
+    w.mesh = view_mesh[p];
+    w.cap = rf_cap(n_triangles[w.mesh]);
+    w.list_off = (size_t)l.view_list[p];
+    kind[meshes[w.mesh].colors ? 0 : 1] = true;
+    max_T = std::max(max_T, (int)n_triangles[w.mesh]);
+    tiles = std::max<int64_t>(tiles, (int64_t)((w.g.Wf + kRsTile - 1) / kRsTile) * ((w.g.Hf + kRsTile - 1) / kRsTile));
+    res = std::max<int64_t>(res, ((int64_t)w.g.W * w.g.H + kRsShadePixels - 1) / kRsShadePixels);
+  }
+  // every argument is checked: from here on the call writes
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local RbStageSlot stage[kRbStageDevices][kRbStageSlots];
+  static thread_local int stage_next[kRbStageDevices] = {0};
+  int dev_id = 0;
+  PXT_HIP_CHECK(hipGetDevice(&dev_id));
+  if (dev_id < 0 || dev_id >= kRbStageDevices) return PXT_E_ARG;
+  RbStageSlot& slot = stage[dev_id][stage_next[dev_id]];
+  stage_next[dev_id] = (stage_next[dev_id] + 1) % kRbStageSlots;
+  if (!slot.host) {
+    PXT_HIP_CHECK(hipHostMalloc((void**)&slot.host, sizeof(RbRecord), hipHostMallocDefault));
+    PXT_HIP_CHECK(hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
+  } else {
+    PXT_HIP_CHECK(hipEventSynchronize(slot.copied));
+  }
+  RbRecord* const h = slot.host;
+  for (int m = 0; m < PXT_MESH_BATCH_MAX_MESHES; ++m) {
+    RbMesh& o = h->mesh[m];
+    o = RbMesh{};
+    if (m >= n_meshes) continue;
+    const pxt_mesh_desc& d = meshes[m];
+    o.vertices = d.vertices; o.triangles = (const int*)d.triangles; o.V = d.n_vertices; o.T = d.n_triangles;
+    o.textured = d.colors ? 0 : 1;
+    o.colors.colors = d.colors;
+    if (o.textured) {
+      o.texture.uvs = d.uvs; o.texture.triangle_uvs = (const int*)d.triangle_uvs; o.texture.texture = (const unsigned*)d.texture;
+      o.texture.n_uvs = d.n_uvs; o.texture.Wt = d.tex_width; o.texture.Ht = d.tex_height;
+    }
+  }
+  for (int p = 0; p < PXT_MESH_BATCH_MAX_VIEWS; ++p) h->view[p] = p < n_views ? table[p] : RbView{};
+  std::copy(views, views + (size_t)n_views * PXT_MESH_VIEW, h->views);
+  std::fill(h->views + (size_t)n_views * PXT_MESH_VIEW, h->views + PXT_MESH_BATCH_MAX_VIEWS * PXT_MESH_VIEW, 0.f);
+  char* const ws = (char*)workspace;
+  const RbRecord* rec = (const RbRecord*)(ws + l.record_off);
+  PXT_HIP_CHECK(hipMemcpyAsync(ws + l.record_off, h, sizeof(RbRecord), hipMemcpyHostToDevice, s));
+  PXT_HIP_CHECK(hipEventRecord(slot.copied, s));
+  RbArgs b;
+  b.keys = (unsigned long long*)ws;
+  b.list_count = (unsigned*)(ws + l.count_off);
+  b.list = (uint4*)(ws + l.list_off);
+  b.records = (unsigned*)records;
+  b.P = n_views;
+  const size_t n_units = (size_t)(l.n_keys / 2);
+  const size_t clear_work = std::max(n_units, (size_t)n_views * PXT_MESH_RASTER_RECORD);
+  const unsigned clear_blocks = (unsigned)std::min<size_t>((clear_work + kRsBlock - 1) / kRsBlock, 8192);
+  hipLaunchKernelGGL(rb_clear_kernel, dim3(clear_blocks), dim3(kRsBlock), 0, s, rec, b, n_units);
+  PXT_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(rb_triangle_kernel, dim3((max_T + kRsTriBlock - 1) / kRsTriBlock, n_views), dim3(kRsTriBlock), 0, s, rec, b);
+  PXT_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(rb_list_kernel, dim3((unsigned)tiles, n_views), dim3(kRsBlock), 0, s, rec, b);
+  PXT_HIP_CHECK(hipGetLastError());
+  if (kind[0]) {
+    hipLaunchKernelGGL(rb_resolve_kernel<RsVertexColors>, dim3((unsigned)res, n_views), dim3(kRsBlock), 0, s, rec, b);
+    PXT_HIP_CHECK(hipGetLastError());
+  }
+  if (kind[1]) {
+    hipLaunchKernelGGL(rb_resolve_kernel<RsTexture>, dim3((unsigned)res, n_views), dim3(kRsBlock), 0, s, rec, b);
+    PXT_HIP_CHECK(hipGetLastError());
+  }
+  return PXT_OK;
 }

@@ -583,18 +583,7 @@ class MeshRenderer:
         self._ops.mesh_render_frame(self.vertices, self.triangles, self.colors, self.uvs, self.triangle_uvs, self.texture,
                                     views, geometry, offsets, *bufs, records, self._workspace)
         rec = records.cpu().numpy().view(np.uint32) if download_records else records
-        out = []
-        for p, (_, W, H, S, want) in enumerate(reqs):
-            res = {}
-            for k, (name, px) in enumerate(zip(FRAME_OUTPUTS, (16, 3, 16, 1))):
-                if name in want:
-                    o, ch = offsets[4 * p + k], (4, 3, 4, 1)[k]
-                    e = px // ch  # bytes per element
-                    plane = bufs[k][o // e:o // e + W * H * ch]
-                    res[name] = plane.view(H, W) if ch == 1 else plane.view(H, W, ch)
-            res["records"] = rec[p]
-            out.append(res)
-        return out
+        return [_frame_planes(bufs, offsets, p, W, H, want, rec) for p, (_, W, H, S, want) in enumerate(reqs)]
 
     @property
     def n_vertices(self) -> int:
@@ -616,6 +605,130 @@ class MeshRenderer:
         records = torch.empty((P, RECORD), dtype=torch.int32, device=self.device)
         self._ops.mesh_raster(self.vertices, self.triangles, v, out, ids, records, self._workspace)
         return out, ids, (records.cpu().numpy().view(np.uint32) if download_records else records)
+
+
+def frame_batch_reference(items) -> list:
+    """The rule of pxt_mesh_render_frame_batch: ``frame_reference`` per item.  ``items`` = ``[(V, F, shading,
+    requests)]`` -> one list of dicts per item.  A view of a batch is that view alone on its mesh: nothing is added."""
+    return [frame_reference(V, F, shading, requests) for V, F, shading, requests in items]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# several meshes' frames in one call (pxt_mesh_render_frame_batch)
+# ---------------------------------------------------------------------------------------------------------------------
+BATCH_MAX_MESHES = _lib.PXT_MESH_BATCH_MAX_MESHES
+BATCH_MAX_VIEWS = _lib.PXT_MESH_BATCH_MAX_VIEWS
+_BATCH_PLANS: dict = {}
+
+
+class FrameBatchWorkspace:
+    """The device memory of ``render_frame_batch`` calls on ONE stream, grown to the largest batch seen.  The call's
+    parameter record lives in it until the chain has finished: two streams must not share one."""
+
+    def __init__(self):
+        self.tensor: Optional[torch.Tensor] = None
+
+    def ensure(self, n_bytes: int, device) -> torch.Tensor:
+        if self.tensor is None or self.tensor.numel() < n_bytes or self.tensor.device != torch.device(device):
+            self.tensor = torch.empty(int(n_bytes), dtype=torch.uint8, device=device)
+        return self.tensor
+
+
+def _batch_plan(shapes):
+    """``shapes`` = per item (triangles, ((W, H, S, want), ...)) -> the consecutive calls that serve them: per call
+    (first item, item count, view_mesh, geometry, offsets, buffer sizes, workspace bytes)."""
+    calls, a = [], 0
+    while a < len(shapes):
+        b, P = a, 0
+        while b < len(shapes) and b - a < BATCH_MAX_MESHES and P + len(shapes[b][1]) <= BATCH_MAX_VIEWS:
+            P += len(shapes[b][1])
+            b += 1
+        if b == a:
+            raise _lib.PxtError(f"render_frame_batch: an item takes 1..{BATCH_MAX_VIEWS} views (got {len(shapes[a][1])})")
+        view_mesh, geometry, offsets, sizes = [], [], [], [0, 0, 0, 0]
+        for m in range(a, b):
+            for W, H, S, want in shapes[m][1]:
+                view_mesh.append(m - a)
+                geometry += [W, H, S]
+                for k, (name, px) in enumerate(zip(FRAME_OUTPUTS, (16, 3, 16, 1))):
+                    if name in want:
+                        offsets.append(sizes[k])
+                        sizes[k] += (W * H * px + 15) // 16 * 16
+                    else:
+                        offsets.append(-1)
+        C = _lib.C
+        need = int(_lib.lib().pxt_mesh_render_frame_batch_workspace_bytes(
+            b - a, (C.c_int32 * (b - a))(*[shapes[m][0] for m in range(a, b)]), len(view_mesh),
+            (C.c_int32 * len(view_mesh))(*view_mesh), (C.c_int32 * len(geometry))(*geometry)))
+        if need <= 0:
+            raise _lib.PxtError(f"render_frame_batch: the views {geometry} are not supported")
+        calls.append((a, b - a, view_mesh, geometry, offsets, sizes, need))
+        a = b
+    return calls
+
+
+def render_frame_batch(items, workspace: Optional[FrameBatchWorkspace] = None, download_records: bool = True) -> list:
+    """``MeshRenderer.render_frame`` for several meshes in one chain of launches
+    (``torch.ops.pixtrack.mesh_render_frame_batch``): ``items`` = ``[(MeshRenderer, requests)]``, the requests as
+    ``render_frame`` takes them -> one list of dicts per item, each dict what ``render_frame`` returns for that request,
+    bit for bit.  The views' 20 floats travel in the call's parameter record: one upload for all items.  More than 16
+    meshes or 32 views are served in consecutive calls.  ``workspace``: a ``FrameBatchWorkspace`` of the stream the
+    call is made on (None: one for this call)."""
+    items = [(r, list(requests)) for r, requests in items]
+    if not items:
+        return []
+    device = items[0][0].device
+    reqs = []
+    for r, requests in items:
+        if r.colors is None and r.texture is None:
+            raise _lib.PxtError("render_frame_batch needs vertex colours or a texture map on every mesh")
+        if r.device != device:
+            raise _lib.PxtError(f"render_frame_batch: the meshes share one device (got {r.device} and {device})")
+        try:
+            reqs.append([_frame_request(q) for q in requests])
+        except ValueError as e:
+            raise _lib.PxtError(f"render_frame_batch: {e}") from None
+        if not reqs[-1]:
+            raise _lib.PxtError("render_frame_batch: an item without requests")
+    shapes = tuple((r.n_triangles, tuple((W, H, S, want) for _, W, H, S, want in q)) for (r, _), q in zip(items, reqs))
+    plan = _BATCH_PLANS.get(shapes)
+    if plan is None:  # the planes' places, the calls and their workspace, once per shape set
+        plan = _BATCH_PLANS[shapes] = _batch_plan(shapes)
+    ws = (workspace or FrameBatchWorkspace()).ensure(max(c[-1] for c in plan), device)
+    op = items[0][0]._ops.mesh_render_frame_batch
+    out = []
+    for a, n, view_mesh, geometry, offsets, sizes, _need in plan:
+        part, part_reqs = [r for r, _ in items[a:a + n]], reqs[a:a + n]
+        views = torch.from_numpy(np.ascontiguousarray(np.stack([q[0] for qs in part_reqs for q in qs])))
+        bufs = [None if size == 0 else torch.empty(size // (4 if k in (0, 2) else 1),
+                                                   dtype=torch.float32 if k in (0, 2) else torch.uint8, device=device)
+                for k, size in enumerate(sizes)]
+        records = torch.empty((len(view_mesh), RECORD), dtype=torch.int32, device=device)
+        op([r.vertices for r in part], [r.triangles for r in part], [r.colors for r in part], [r.uvs for r in part],
+           [r.triangle_uvs for r in part], [r.texture for r in part], view_mesh, views, geometry, offsets, *bufs, records,
+           ws)
+        rec = records.cpu().numpy().view(np.uint32) if download_records else records
+        p = 0
+        for qs in part_reqs:
+            res_item = []
+            for _, W, H, S, want in qs:
+                res_item.append(_frame_planes(bufs, offsets, p, W, H, want, rec))
+                p += 1
+            out.append(res_item)
+    return out
+
+
+def _frame_planes(bufs, offsets, p: int, W: int, H: int, want, rec) -> dict:
+    """View p's planes in the four flat buffers of a frame call -> the dict ``render_frame`` returns for it."""
+    res = {}
+    for k, (name, px) in enumerate(zip(FRAME_OUTPUTS, (16, 3, 16, 1))):
+        if name in want:
+            o, ch = offsets[4 * p + k], (4, 3, 4, 1)[k]
+            e = px // ch  # bytes per element
+            plane = bufs[k][o // e:o // e + W * H * ch]
+            res[name] = plane.view(H, W) if ch == 1 else plane.view(H, W, ch)
+    res["records"] = rec[p]
+    return res
 
 
 # ---------------------------------------------------------------------------------------------------------------------

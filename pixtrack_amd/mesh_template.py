@@ -87,3 +87,14 @@ class MeshTemplate:
                                          download_records=False)
         res = (out[0]["depth_nz"], out[-1]["rgb_u8"])
         return res + (out[0]["depth"],) if want_depth else res
+
+    @staticmethod
+    def frames(templates, poses, query_cameras, reference_cameras, workspace=None) -> list:
+        """``frame`` for several templates - K objects tracked in lock-step - in ONE ``mesh_render.render_frame_batch``
+        call: every template's ``requests`` as ``frame`` forms them, one chain of launches, one upload of all views ->
+        ``[(depth_nz, rgb_u8)]`` per template, the planes ``frame`` returns bit for bit.  ``workspace``: the calling
+        stream's ``mesh_render.FrameBatchWorkspace`` (None: one for this call)."""
+        items = [(t.renderer, t.requests(pose, qc, rc)) for t, pose, qc, rc in zip(templates, poses, query_cameras,
+                                                                                    reference_cameras)]
+        outs = R.render_frame_batch(items, workspace=workspace, download_records=False)
+        return [(out[0]["depth_nz"], out[-1]["rgb_u8"]) for out in outs]

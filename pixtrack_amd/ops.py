@@ -210,6 +210,15 @@ SCHEMAS = {
         "(Tensor vertices, Tensor triangles, Tensor? colors, Tensor? uvs, Tensor? triangle_uvs, Tensor? texture, "
         "Tensor views, int[] geometry, int[] offsets, Tensor(a!)? rgba, Tensor(b!)? rgb_u8, Tensor(c!)? depth, "
         "Tensor(d!)? depth_nz, Tensor(e!) records, Tensor(f!) workspace) -> ()"),
+    # mesh_render_frame for views of up to 16 DIFFERENT meshes in one chain (pxt_mesh_render_frame_batch): one list
+    # entry per mesh (colors[m], or uvs[m] + triangle_uvs[m] + texture[m]; the others None); view_mesh = the mesh of
+    # each of the P <= 32 views; views: a CPU float32 [P, 20] tensor - the floats travel in the call's parameter record;
+    # geometry, offsets, the four flat buffers and records as mesh_render_frame; workspace: uint8,
+    # pxt_mesh_render_frame_batch_workspace_bytes(...), one per stream
+    "mesh_render_frame_batch": (
+        "(Tensor[] vertices, Tensor[] triangles, Tensor?[] colors, Tensor?[] uvs, Tensor?[] triangle_uvs, "
+        "Tensor?[] texture, int[] view_mesh, Tensor views, int[] geometry, int[] offsets, Tensor(a!)? rgba, "
+        "Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, Tensor(e!) records, Tensor(f!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -1390,15 +1399,15 @@ def _mesh_render_textured(vertices, triangles, uvs, triangle_uvs, texture, views
         workspace.data_ptr(), _stream(vertices)), "pxt_mesh_render_textured")
 
 
-def mesh_frame_planes(geometry, offsets, what="mesh_render_frame"):
+def mesh_frame_planes(geometry, offsets, what="mesh_render_frame", max_views=_lib.PXT_MESH_FRAME_MAX_VIEWS):
     """The argument checks of mesh_render_frame that need no tensor: ``geometry`` = P x (width, height, supersample),
     ``offsets`` = P x (rgba, rgb_u8, depth, depth_nz) byte offsets or -1 -> (P, the bytes each of the four buffers
     must hold)."""
     geometry, offsets = [int(x) for x in geometry], [int(x) for x in offsets]
     P = len(geometry) // 3
-    if not (1 <= P <= _lib.PXT_MESH_FRAME_MAX_VIEWS) or len(geometry) != 3 * P or len(offsets) != 4 * P:
+    if not (1 <= P <= max_views) or len(geometry) != 3 * P or len(offsets) != 4 * P:
         raise _lib.PxtError(f"{what}: geometry holds (width, height, supersample) and offsets four byte offsets for "
-                            f"each of 1..{_lib.PXT_MESH_FRAME_MAX_VIEWS} views (got {len(geometry)} and {len(offsets)} "
+                            f"each of 1..{max_views} views (got {len(geometry)} and {len(offsets)} "
                             "numbers)")
     need = [0, 0, 0, 0]
     spans = [[], [], [], []]
@@ -1444,39 +1453,8 @@ def _mesh_render_frame(vertices, triangles, colors, uvs, triangle_uvs, texture, 
     P, need = mesh_frame_planes(geometry, offsets, what)
     if int(views.shape[0]) != P:
         raise _lib.PxtError(f"{what}: {int(views.shape[0])} views for {P} geometry entries")
-    textured = uvs is not None or triangle_uvs is not None or texture is not None
-    if (colors is not None) == textured:
-        raise _lib.PxtError(f"{what}: a mesh is drawn with colors or with uvs + triangle_uvs + texture, one of the two")
-    attrs = []
-    if textured:
-        if uvs is None or triangle_uvs is None or texture is None:
-            raise _lib.PxtError(f"{what}: a textured mesh needs uvs, triangle_uvs and texture")
-        _f32c(uvs, "uvs")
-        if uvs.dim() != 2 or int(uvs.shape[1]) != 2 or not (1 <= int(uvs.shape[0]) <= 1 << 24):
-            raise _lib.PxtError(f"{what}: uvs is {tuple(uvs.shape)}, expected float32 [1..2^24, 2]")
-        if triangle_uvs.dtype != torch.int32 or not triangle_uvs.is_contiguous() or tuple(triangle_uvs.shape) != (T, 3):
-            raise _lib.PxtError(f"{what}: triangle_uvs is a contiguous int32 [{T}, 3] tensor (got "
-                                f"{tuple(triangle_uvs.shape)}, {triangle_uvs.dtype})")
-        if (texture.dtype != torch.uint8 or not texture.is_contiguous() or texture.dim() != 3 or int(texture.shape[2]) != 4
-                or not (1 <= int(texture.shape[0]) <= 16384 and 1 <= int(texture.shape[1]) <= 16384)):
-            raise _lib.PxtError(f"{what}: texture is a contiguous uint8 [1..16384, 1..16384, 4] tensor (got "
-                                f"{tuple(texture.shape)}, {texture.dtype})")
-        attrs = [(uvs, "uvs"), (triangle_uvs, "triangle_uvs"), (texture, "texture")]
-    else:
-        _f32c(colors, "colors")
-        if tuple(colors.shape) != (V, 3):
-            raise _lib.PxtError(f"{what}: colors is {tuple(colors.shape)}, expected float32 [{V}, 3]")
-        attrs = [(colors, "colors")]
-    outs = [(rgba, "rgba", torch.float32), (rgb_u8, "rgb_u8", torch.uint8), (depth, "depth", torch.float32),
-            (depth_nz, "depth_nz", torch.uint8)]
-    out_bytes = []
-    for (t, name, dtype), n in zip(outs, need):
-        have = 0 if t is None else t.numel() * t.element_size()
-        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
-            raise _lib.PxtError(f"{what}: {name} is a contiguous {dtype} buffer (got {t.dtype})")
-        if have < n:
-            raise _lib.PxtError(f"{what}: {name} holds {have} bytes, the views' planes need {n}")
-        out_bytes.append(have)
+    attrs = _mesh_shading_checked(what, V, T, colors, uvs, triangle_uvs, texture)
+    outs, out_bytes = _mesh_frame_buffers(what, need, rgba, rgb_u8, depth, depth_nz)
     if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
         raise _lib.PxtError(f"{what}: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
                             f"(got {tuple(records.shape)}, {records.dtype})")
@@ -1503,7 +1481,125 @@ def _mesh_render_frame(vertices, triangles, colors, uvs, triangle_uvs, texture, 
         workspace.data_ptr(), _stream(vertices)), "pxt_mesh_render_frame")
 
 
+def mesh_batch_planes(view_mesh, n_meshes, geometry, offsets, what="mesh_render_frame_batch"):
+    """The argument checks of mesh_render_frame_batch that need no tensor: ``view_mesh`` = the mesh of each of the P
+    views, ``n_meshes`` = M, ``geometry`` and ``offsets`` as ``mesh_frame_planes`` -> (P, the bytes each of the four
+    buffers must hold)."""
+    view_mesh, M = [int(x) for x in view_mesh], int(n_meshes)
+    if not (1 <= M <= _lib.PXT_MESH_BATCH_MAX_MESHES):
+        raise _lib.PxtError(f"{what}: 1..{_lib.PXT_MESH_BATCH_MAX_MESHES} meshes per call (got {M})")
+    P, need = mesh_frame_planes(geometry, offsets, what, _lib.PXT_MESH_BATCH_MAX_VIEWS)
+    if len(view_mesh) != P:
+        raise _lib.PxtError(f"{what}: view_mesh names the mesh of each of the {P} views (got {len(view_mesh)} numbers)")
+    bad = [(p, m) for p, m in enumerate(view_mesh) if not (0 <= m < M)]
+    if bad:
+        raise _lib.PxtError(f"{what}: view {bad[0][0]} names mesh {bad[0][1]} of {M}")
+    return P, need
+
+
+def _mesh_shading_checked(what, V, T, colors, uvs, triangle_uvs, texture):
+    """One mesh's shading inputs -> the tensors the kernels dereference, named."""
+    textured = uvs is not None or triangle_uvs is not None or texture is not None
+    if (colors is not None) == textured:
+        raise _lib.PxtError(f"{what}: a mesh is drawn with colors or with uvs + triangle_uvs + texture, one of the two")
+    if not textured:
+        _f32c(colors, "colors")
+        if tuple(colors.shape) != (V, 3):
+            raise _lib.PxtError(f"{what}: colors is {tuple(colors.shape)}, expected float32 [{V}, 3]")
+        return [(colors, "colors")]
+    if uvs is None or triangle_uvs is None or texture is None:
+        raise _lib.PxtError(f"{what}: a textured mesh needs uvs, triangle_uvs and texture")
+    _f32c(uvs, "uvs")
+    if uvs.dim() != 2 or int(uvs.shape[1]) != 2 or not (1 <= int(uvs.shape[0]) <= 1 << 24):
+        raise _lib.PxtError(f"{what}: uvs is {tuple(uvs.shape)}, expected float32 [1..2^24, 2]")
+    if triangle_uvs.dtype != torch.int32 or not triangle_uvs.is_contiguous() or tuple(triangle_uvs.shape) != (T, 3):
+        raise _lib.PxtError(f"{what}: triangle_uvs is a contiguous int32 [{T}, 3] tensor (got "
+                            f"{tuple(triangle_uvs.shape)}, {triangle_uvs.dtype})")
+    if (texture.dtype != torch.uint8 or not texture.is_contiguous() or texture.dim() != 3 or int(texture.shape[2]) != 4
+            or not (1 <= int(texture.shape[0]) <= 16384 and 1 <= int(texture.shape[1]) <= 16384)):
+        raise _lib.PxtError(f"{what}: texture is a contiguous uint8 [1..16384, 1..16384, 4] tensor (got "
+                            f"{tuple(texture.shape)}, {texture.dtype})")
+    return [(uvs, "uvs"), (triangle_uvs, "triangle_uvs"), (texture, "texture")]
+
+
+def _mesh_frame_buffers(what, need, rgba, rgb_u8, depth, depth_nz):
+    """The four flat output buffers hold the views' planes -> (the buffers named, their sizes in bytes)."""
+    outs = [(rgba, "rgba", torch.float32), (rgb_u8, "rgb_u8", torch.uint8), (depth, "depth", torch.float32),
+            (depth_nz, "depth_nz", torch.uint8)]
+    out_bytes = []
+    for (t, name, dtype), n in zip(outs, need):
+        have = 0 if t is None else t.numel() * t.element_size()
+        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
+            raise _lib.PxtError(f"{what}: {name} is a contiguous {dtype} buffer (got {t.dtype})")
+        if have < n:
+            raise _lib.PxtError(f"{what}: {name} holds {have} bytes, the views' planes need {n}")
+        out_bytes.append(have)
+    return outs, out_bytes
+
+
+def _mesh_render_frame_batch(vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh, views, geometry, offsets,
+                             rgba, rgb_u8, depth, depth_nz, records, workspace):
+    what = "mesh_render_frame_batch"
+    L = _lib.lib()
+    M = len(vertices)
+    if not all(len(x) == M for x in (triangles, colors, uvs, triangle_uvs, texture)):
+        raise _lib.PxtError(f"{what}: vertices, triangles, colors, uvs, triangle_uvs and texture hold one entry per mesh "
+                            f"(got {[len(x) for x in (vertices, triangles, colors, uvs, triangle_uvs, texture)]})")
+    P, need = mesh_batch_planes(view_mesh, M, geometry, offsets, what)
+    if (views.is_cuda or views.dtype != torch.float32 or not views.is_contiguous()
+            or tuple(views.shape) != (P, _lib.PXT_MESH_VIEW)):
+        raise _lib.PxtError(f"{what}: views is a contiguous float32 CPU tensor [{P}, {_lib.PXT_MESH_VIEW}] (got "
+                            f"{tuple(views.shape)}, {views.dtype}, {views.device})")
+    named, descs, counts = [], (_lib.MeshDesc * M)(), []
+    for m in range(M):
+        v, t = vertices[m], triangles[m]
+        _f32c(v, f"vertices[{m}]")
+        if (v.dim() != 2 or int(v.shape[1]) != 3 or t.dim() != 2 or int(t.shape[1]) != 3 or t.dtype != torch.int32
+                or not t.is_contiguous()):
+            raise _lib.PxtError(f"{what}: mesh {m}: vertices {tuple(v.shape)} / triangles {tuple(t.shape)} {t.dtype}, "
+                                "expected float32 [V, 3] / contiguous int32 [T, 3]")
+        V, T = int(v.shape[0]), int(t.shape[0])
+        if not (1 <= V <= 1 << 24 and 1 <= T <= 1 << 24):
+            raise _lib.PxtError(f"{what}: mesh {m}: {V} vertices, {T} triangles are not supported (1..2^24 vertices and "
+                                "triangles)")
+        attrs = _mesh_shading_checked(f"{what}: mesh {m}", V, T, colors[m], uvs[m], triangle_uvs[m], texture[m])
+        named += [(v, f"vertices[{m}]"), (t, f"triangles[{m}]")] + [(a, f"{n}[{m}]") for a, n in attrs]
+        d = descs[m]
+        d.vertices, d.triangles, d.n_vertices, d.n_triangles = v.data_ptr(), t.data_ptr(), V, T
+        d.colors, d.uvs = _lib.dptr(colors[m]), _lib.dptr(uvs[m])
+        d.triangle_uvs, d.texture = _lib.dptr(triangle_uvs[m]), _lib.dptr(texture[m])
+        d.n_uvs = 0 if uvs[m] is None else int(uvs[m].shape[0])
+        d.tex_width = 0 if texture[m] is None else int(texture[m].shape[1])
+        d.tex_height = 0 if texture[m] is None else int(texture[m].shape[0])
+        counts.append(T)
+    outs, out_bytes = _mesh_frame_buffers(what, need, rgba, rgb_u8, depth, depth_nz)
+    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
+        raise _lib.PxtError(f"{what}: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
+                            f"(got {tuple(records.shape)}, {records.dtype})")
+    geo = (C.c_int32 * (3 * P))(*[int(x) for x in geometry])
+    off = (C.c_int64 * (4 * P))(*[int(x) for x in offsets])
+    cap = (C.c_int64 * 4)(*out_bytes)
+    vm = (C.c_int32 * P)(*[int(x) for x in view_mesh])
+    bytes_needed = int(L.pxt_mesh_render_frame_batch_workspace_bytes(M, (C.c_int32 * M)(*counts), P, vm, geo))
+    if bytes_needed <= 0:
+        raise _lib.PxtError(f"{what}: the views {list(geometry)} are not supported")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < bytes_needed:
+        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {bytes_needed} bytes")
+    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+    named += [(records, "records"), (workspace, "workspace")] + [(t, name) for t, name, _ in outs if t is not None]
+    device = vertices[0].device
+    for t, name in named:
+        _lib.require_gpu(t, name)
+        if t.device != device:
+            raise _lib.PxtError(f"{what}: {name} is on {t.device}, vertices[0] on {device}")
+    _lib.check(L.pxt_mesh_render_frame_batch(
+        descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
+        _lib.dptr(depth_nz), cap, records.data_ptr(), workspace.data_ptr(), _stream(vertices[0])),
+        "pxt_mesh_render_frame_batch")
+
+
 _IMPLS = {
+    "mesh_render_frame_batch": _mesh_render_frame_batch,
     "mesh_raster": _mesh_raster,
     "mesh_render_frame": _mesh_render_frame,
     "mesh_render": _mesh_render,

@@ -15,7 +15,10 @@ methods - and only the device work of a frame step is merged:
   problem i mod K, an iteration's exchange and solve are paid once for all K;
 * renders stay one renderer context per object (each object has its own NeRF), the render of step
   t + 1 queued behind the batched LM launch with the camera from the LM epilogue's slot, as in the
-  one-object tracker.
+  one-object tracker;
+* trackers with a mesh template (``template=MeshTemplate(...)``) have no NeRF: the frames of a group's
+  mesh trackers - each one's depth_nz plane and reference image - are drawn at the head of the step in
+  ONE call (``MeshTemplate.frames``, ``pxt_mesh_render_frame_batch``).  Both kinds may share a group.
 
 A tracker in cold start (image scales [4, 1]: two dependent refinements) runs that frame by itself
 through ``run_single_frame``; everything else is lock-step.  Per object the results are those of the
@@ -48,6 +51,7 @@ class _Group:
         self.info_ws: Optional[torch.Tensor] = None  # parameter records and partial sums of the step's information launch
         self.report_ws: Optional[torch.Tensor] = None  # ... and of the step's point-report launch
         self.render_ws: Optional[torch.Tensor] = None  # parameter records of the batched render chain
+        self.mesh_ws = None  # mesh_render.FrameBatchWorkspace of the group's mesh-template frames (made on first use)
         self.unet_done: Optional[torch.cuda.Event] = None
         self.pend = None  # what _enqueue left for _finish
 
@@ -87,9 +91,14 @@ class MultiObjectTracker:
             if getattr(tr, "occlusion", None) is not None:
                 # (the batched render chain carries no float Depth image, and the step launches the LM itself)
                 raise ValueError("occlusion is not supported by lock-step tracking yet")
-            if getattr(tr, "template", None) is not None:
-                # (the step's batched render chain is the NeRF renderer's)
-                raise ValueError("a mesh template is not supported by lock-step tracking yet")
+            template = getattr(tr, "template", None)
+            if template is not None:
+                from ..mesh_template import MeshTemplate
+
+                # (phase A draws the frames of a group's mesh templates in one MeshTemplate.frames call)
+                if not isinstance(template, MeshTemplate):
+                    raise ValueError("lock-step tracking takes a mesh template that is a mesh_template.MeshTemplate "
+                                     f"(got {template!r})")
         # one UNet context runs every image of a group's step: the trackers must hold the same checkpoint in the same
         # precision (pixloc_megadepth is one network for all objects; reference pixloc_pose_refiners.py:49-60; the
         # signature names the precision)
@@ -202,12 +211,12 @@ class MultiObjectTracker:
         live = []
         grp.pend = []
         # ---- phase A: per-object frame set-up (policy head, mask + reference render or the render queued last step)
+        self._prime_mesh_frames(grp, frames)
         for k in grp.members:
             tr, frame = self.trackers[k], frames[k]
             if frame is None:
                 continue
-            scales = tr.steady_multiscale if tr.success else tr.localizer.refiner.conf.multiscale
-            if tr.cold_start or len(tr.reference_ids) != 1 or list(scales or [1]) != [1]:
+            if not self._takes_lockstep(tr, frame):
                 tr.run_single_frame(frame)
                 out[k] = bool(tr.success)
                 self.solo_frames += 1
@@ -294,6 +303,33 @@ class MultiObjectTracker:
                                                            asked[0][0]["conf"], grp.report_ws, pool_key=("group", grp.index))
             for i, (x, _h, _rf) in enumerate(asked):
                 x["report"] = (report, i)
+
+    @staticmethod
+    def _takes_lockstep(tr, frame) -> bool:
+        """This step, the tracker's frame goes through the merged device work (else: through run_single_frame)."""
+        if frame is None:
+            return False
+        scales = tr.steady_multiscale if tr.success else tr.localizer.refiner.conf.multiscale
+        return not (tr.cold_start or len(tr.reference_ids) != 1 or list(scales or [1]) != [1])
+
+    def _prime_mesh_frames(self, grp: _Group, frames) -> None:
+        """The frames of the group's mesh-template trackers that take the lock-step path, at their poses, in ONE
+        MeshTemplate.frames call on the group's stream; each tracker's _mask_and_reference then takes its planes instead
+        of making its own call.  (A tracker that renders no mask this frame - the frame after a failed one - still needs
+        its reference image: it rides along with the same requests and drops its depth_nz plane.)"""
+        part = [self.trackers[k] for k in grp.members
+                if self.trackers[k].template is not None and self._takes_lockstep(self.trackers[k], frames[k])]
+        if not part:  # (NeRF trackers only: nothing of the mesh path is touched)
+            return
+        from ..mesh_render import FrameBatchWorkspace
+        from ..mesh_template import MeshTemplate
+
+        if grp.mesh_ws is None:
+            grp.mesh_ws = FrameBatchWorkspace()
+        planes = MeshTemplate.frames([tr.template for tr in part], [tr.pose for tr in part], [tr.camera for tr in part],
+                                     [tr._reference_camera() for tr in part], workspace=grp.mesh_ws)
+        for tr, (nz, ref_u8) in zip(part, planes):
+            tr._primed_frame = (tr.pose, nz, ref_u8)
 
     def _batched_renders_ahead(self, grp: _Group) -> set:
         """The group's queued renders (behind the batched LM launch, cameras from its epilogue's slots) in one batched
@@ -406,7 +442,26 @@ def build_parser():
     ap.add_argument("--point_report", choices=("off", "summary", "full"), default="off",
                     help="add every frame's valid / inlier point counts and mean robust weight to poses.pkl (summary), and "
                          "the per-point projections, residuals and weights as well (full)")
+    ap.add_argument("--template", choices=("nerf", "mesh"), default="nerf",
+                    help="what every object's mask and reference image are rendered from: nerf (default) or mesh (--mesh; "
+                         "no snapshot, nerf2sfm.pkl or OBJ_AABB is read; a group's frames are drawn in one call)")
+    ap.add_argument("--mesh", type=Path, nargs="+", default=None, help="--template mesh: the mesh of each object")
+    ap.add_argument("--texture", type=Path, nargs="+", default=None, help="the texture map of each object's mesh")
+    ap.add_argument("--mesh_scale", type=float, nargs="+", default=[1.0], help="factor on each mesh's vertices")
+    ap.add_argument("--mesh_supersample", type=int, nargs="+", choices=(1, 2, 4), default=[2],
+                    help="samples per pixel and axis of each mesh template's reference image (default 2, untuned)")
+    ap.add_argument("--reference_sfm", type=Path, nargs="+", default=None,
+                    help="each object's SfM model directory (the ref/ directory mesh_dataset wrote)")
     return ap
+
+
+def _per_object(values, k: int, K: int, flag: str):
+    """A list option's entry for object k: one entry per object, or one entry for all (None: not given)."""
+    if values is None:
+        return None
+    if len(values) not in (1, K):
+        raise ValueError(f"{flag} takes one entry per object or one entry for all (got {len(values)} for {K} objects)")
+    return values[k if len(values) == K else 0]
 
 
 def main(argv=None):
@@ -420,7 +475,9 @@ def main(argv=None):
 
     import numpy as np
 
-    from .pixloc_tracker_r9 import _dump
+    import argparse
+
+    from .pixloc_tracker_r9 import _dump, template_from_args
 
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -438,12 +495,23 @@ def main(argv=None):
             conf["OBJ_AABB"] = args.obj_aabb[k]
         if args.upright_ref_img:
             conf["UPRIGHT_REF_IMG"] = args.upright_ref_img[k]
-        if "OBJ_AABB" not in conf or "UPRIGHT_REF_IMG" not in conf:
-            ap.error(f"object {k}: OBJ_AABB and UPRIGHT_REF_IMG are needed (--config, or --obj_aabb / --upright_ref_img)")
-        os.environ.update(OBJ_AABB=conf["OBJ_AABB"], UPRIGHT_REF_IMG=conf["UPRIGHT_REF_IMG"])  # read in the constructor (:77, :85)
+        needed = ("UPRIGHT_REF_IMG",) if args.template == "mesh" else ("OBJ_AABB", "UPRIGHT_REF_IMG")
+        if any(name not in conf for name in needed):
+            ap.error(f"object {k}: {' and '.join(needed)} needed (--config, or --obj_aabb / --upright_ref_img)")
+        os.environ.update({name: conf[name] for name in needed})  # read in the constructor (:77, :85)
         obj = args.object_path[k]
         os.makedirs(args.out_dir[k], exist_ok=True)
-        trackers.append(PixLocPoseTrackerR9(object_path=str(obj), data_path=str(obj / "pixtrack/pixsfm/dataset"),
+        try:
+            one = argparse.Namespace(template=args.template, mesh=_per_object(args.mesh, k, K, "--mesh"),
+                                     texture=_per_object(args.texture, k, K, "--texture"),
+                                     mesh_scale=_per_object(args.mesh_scale, k, K, "--mesh_scale"),
+                                     mesh_supersample=_per_object(args.mesh_supersample, k, K, "--mesh_supersample"))
+            template = template_from_args(one)
+            reference_sfm = _per_object(args.reference_sfm, k, K, "--reference_sfm")
+        except ValueError as e:
+            ap.error(str(e))
+        trackers.append(PixLocPoseTrackerR9(template=template, reference_sfm=reference_sfm,
+                                            object_path=str(obj), data_path=str(obj / "pixtrack/pixsfm/dataset"),
                                             eval_path=str(args.out_dir[k]), loc_path=str(obj / "pixtrack/aug_nerf_sfm"),
                                             debug=args.debug, unet_precision=args.unet_precision,
                                             uncertainty=args.uncertainty, point_report=args.point_report))

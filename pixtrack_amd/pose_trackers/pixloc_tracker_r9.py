@@ -185,6 +185,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         self.spp = 8  # run_vis_on_poses.py:29
         self.batch_frame_images = True  # reference render + masked query in one batched UNet pass
         self._fused_reference = None  # (pose object, uint8 image) handed from get_mask to get_reference_image
+        # (pose object, depth_nz, rgb_u8): a mesh template's frame at that pose, drawn by lock-step tracking in one call
+        # with the other objects' (multi_object_tracker.py); _mask_and_reference takes it instead of its own call
+        self._primed_frame = None
+        self.template_frames_batched = 0
         self._fused_depth = None  # (pose object, float Depth render) beside it: reference_points="render" only
         self._ref_cam_cache = self._coincide_cache = None
         self.keep_feature_history = False  # the reference leaks one entry per frame (Appendix D.2)
@@ -665,7 +669,12 @@ class PixLocPoseTrackerR9(PoseTracker):
         image (``_fused_depth`` / ``_last_depth``).  With a mesh template both planes come from one
         ``MeshTemplate.frame`` call instead; everything after them is the same."""
         if self.template is not None:
-            nz, ref_u8 = self.template.frame(pose, self.camera, self._reference_camera())
+            primed, self._primed_frame = self._primed_frame, None
+            if primed is not None and pose is not None and primed[0] is pose:  # drawn with the other objects' frames
+                nz, ref_u8 = primed[1], primed[2]
+                self.template_frames_batched += 1
+            else:
+                nz, ref_u8 = self.template.frame(pose, self.camera, self._reference_camera())
             mask = self._mask_of(nz)
             self._last_depth = None
             self._fused_reference, self._fused_depth = (pose, ref_u8), None
