@@ -1061,6 +1061,16 @@ int pxt_depth_refine(const pxt_depth_problem* problems_host, int32_t n_problems,
  *   (valid_in set) and [10] n_points_out (valid_out set) are written; integer counts by ballot, no atomics.
  *   Bounds: 0 <= N <= 2^24 (N = 0 writes the three words only; p3d and valid_out may then be NULL), ndist 0 / 2 / 4,
  *   sizes as above; anything else is PXT_E_ARG and nothing is launched or written.
+ *
+ * pxt_mask_exclude - a mask minus an occluder plane that another call made (pxt_mesh_render_scene_batch's: the other
+ *   tracked objects of the image): mask_out [H][W] uint8 = (mask_in != 0) && !(occluder != 0), dense 0 / 1; mask_out may
+ *   be mask_in, not occluder.  record (device or pinned host, 4-byte aligned): [0] n_mask_in, [1] n_mask_out; nothing
+ *   else is written.  The rule is elementwise, so the planes are walked as H * W bytes: 16 at a time where mask_in,
+ *   occluder and mask_out are all 16-byte aligned, four where 4-byte, the remainder (and unaligned planes) bytewise.
+ *   mask_exclude_reference (pixtrack_amd/occlusion.py) restates it; the two agree bit for bit.
+ *   Bounds: width, height >= 1 and width * height <= 2^28, no NULL; anything else is PXT_E_ARG and nothing is launched
+ *   or written.  One launch of one workgroup on `stream`, counts by population count, no atomics, no workspace.
+ *   Measured on the MI355X: DESIGN.md 3.20.
  * Measured on the MI355X: DESIGN.md 3.13.
  * ---------------------------------------------------------------------- */
 #define PXT_OCCLUSION_RECORD 16
@@ -1073,6 +1083,8 @@ int pxt_occlusion_mask(const float* depth, const uint16_t* sensor, const uint8_t
 int pxt_points_visible(const float* p3d, const uint8_t* valid_in, int32_t n_points, const float* pose12_host,
                        const float* cam10_host, int32_t ndist, const uint8_t* occluder, int32_t width, int32_t height,
                        uint8_t* valid_out, int32_t* record, void* stream);
+int pxt_mask_exclude(const uint8_t* mask_in, const uint8_t* occluder, int32_t width, int32_t height, uint8_t* mask_out,
+                     int32_t* record, void* stream);
 
 /* -------------------------------------------------------------------------
  * NeRF mesh extraction: the iso-surface of a scalar lattice as an indexed triangle mesh, and BOP's diameter of a point
@@ -1184,7 +1196,7 @@ int pxt_max_pairwise_distance(const float* points, int32_t n_points, void* works
  *   [0] covered pixels  [1] triangles drawn  [2] near  [3] guard  [4] zero area  [5] bad index  [6] off-screen
  *   [7] the bits of the smallest z written (0xffffffff when no pixel is covered)  [8] of the largest (0 likewise)
  *   [9] status: 0, or 0xffffffff (-1) when one of the view's 20 floats is not finite - that view's image is all
- *   background and its counts are 0  [10..15] 0.
+ *   background and its counts are 0  [10..15] 0 ([10], [11]: pxt_mesh_render_scene_batch's counts).
  * Deterministic: every pixel owns a 64-bit key (z bits << 32 | triangle index) in the workspace, resolved with a vector
  *   atomicMin (z > 0: the bits order as the floats; the minimum of a total order does not depend on arrival); the counts
  *   are integer adds, min / max z bit-pattern atomics.  A view's outputs are a pure function of the mesh and its 20
@@ -1381,6 +1393,55 @@ int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t n_meshes, c
                                 const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8, float* out_depth,
                                 uint8_t* out_depth_nz, const int64_t* out_bytes, uint32_t* records, void* workspace,
                                 void* stream);
+
+/* -------------------------------------------------------------------------
+ * Lock-step tracking of objects that share an image: pxt_mesh_render_frame_batch plus, per view, the pixels where
+ * ANOTHER view of the same scene lies in front (opt-in; csrc/pxt_raster.hip, mesh_render.render_frame_batch(scenes=),
+ * MeshTemplate.frames, MultiObjectTracker(mutual_occlusion=)).  The occluders of a lock-step step are known exactly:
+ * they are the other tracked meshes, and their per-pixel z already sits in the call's key planes.
+ *
+ * Everything pxt_mesh_render_frame_batch takes, and:
+ *   view_scene [P] int32 (HOST): the scene of each view, -1 = the view is in no scene.  A scene id is any number in
+ *       [0, P); the views that name the same number are that scene's members.
+ *   r_grow: the occluder plane is grown by the (2 r_grow + 1)^2 box, 0 <= r_grow <= 8.
+ *   out_occluder: the base of a uint8 device buffer of occluder_bytes bytes (may be NULL when no view wants a plane);
+ *   occluder_offsets [P] int64 (HOST): the byte offset of the view's [H][W] uint8 plane in it, a multiple of 4, or -1
+ *       for a view that does not want the plane.  The planes of one call must not overlap.
+ * The rule (mesh_render.scene_reference restates it in numpy on its own key planes; the two agree bit for bit, no
+ * tolerance, no excluded pixel):
+ *   Every output plane and record words [0..9] of every view equal, bit for bit, what pxt_mesh_render_frame_batch writes
+ *       for the same arguments: a scene changes nothing that exists.
+ *   For view k with view_scene[k] = s >= 0, the other members are the views j != k with view_scene[j] = s;
+ *       H_k(x) = key_k(x) != empty && exists j: key_j(x) != empty && zbits_j(x) < zbits_k(x), zbits the high 32 bits of
+ *       the 64-bit key: the bits of the UNSCALED camera z (near and depth_q may differ between members).  Equal bits do
+ *       NOT hide: two copies of one mesh at one pose hide nothing of each other.  The plane of a view is a pure function
+ *       of its own inputs and the SET of the other members - not of the view order, M, P, views outside the scene or
+ *       scheduling.  A scene of one member yields an all-zero plane.
+ *   G_k = the dilation of H_k with the (2 r_grow + 1)^2 box, pixels outside the image ignored (pxt_occlusion_mask's G).
+ *   out_occluder of view k = G_k, dense 0 / 1 bytes (four bytes as one dword when W % 4 == 0).
+ *   records [P][16]: [10] n_hidden = the population of H_k, [11] n_occluder = of G_k, for scene views that want the
+ *       plane, 0 otherwise; integer adds, deterministic.
+ * Bounds, in addition to pxt_mesh_render_frame_batch's: a scene member with S != 1; members of one scene that differ in
+ *   width or height or whose view floats [12..15] (fx fy cx cy) are not bit-equal; view_scene[p] outside [-1, P); an
+ *   occluder offset on a view with view_scene = -1; r_grow outside 0..8; a plane that is not 4-byte aligned or does not
+ *   fit the buffer; view_scene or occluder_offsets NULL.  Anything else is PXT_E_ARG and nothing is launched or written.
+ * workspace: pxt_mesh_render_scene_batch_workspace_bytes(...) bytes (the batch call's plus the scene table, which
+ *   travels in the same parameter record and the same one copy).
+ * Launches: pxt_mesh_render_frame_batch's, and ONE more when at least one view wants a plane - 64 x 16 tiles with an
+ *   r_grow halo, H from the members' keys (their high words alone) as wave ballots, shift-OR / row-OR dilation on bit
+ *   planes, counts by population count.  It reads only finished keys and runs between the list launch and the resolves:
+ *   the S = 1 key planes it reads were written last and are read again next.  No host synchronisation and no allocation
+ *   beyond the batch call's.  Measured on the MI355X: DESIGN.md 3.20.
+ * ---------------------------------------------------------------------- */
+#define PXT_MESH_SCENE_MAX_GROW 8
+int64_t pxt_mesh_render_scene_batch_workspace_bytes(int32_t n_meshes, const int32_t* n_triangles, int32_t n_views,
+                                                    const int32_t* view_mesh, const int32_t* geometry);
+int pxt_mesh_render_scene_batch(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh,
+                                const float* views, int32_t n_views, const int32_t* geometry,
+                                const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8, float* out_depth,
+                                uint8_t* out_depth_nz, const int64_t* out_bytes, const int32_t* view_scene,
+                                int32_t r_grow, uint8_t* out_occluder, int64_t occluder_bytes,
+                                const int64_t* occluder_offsets, uint32_t* records, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -51,6 +51,7 @@ PXT_MESH_RASTER_RECORD = 16
 PXT_MESH_FRAME_MAX_VIEWS = 8
 PXT_MESH_BATCH_MAX_MESHES = 16
 PXT_MESH_BATCH_MAX_VIEWS = 32
+PXT_MESH_SCENE_MAX_GROW = 8
 
 
 class PxtError(RuntimeError):
@@ -381,6 +382,7 @@ PROTOTYPES = {
                                      _VP, _VP, _VP, _VP, _VP]),
     "pxt_points_visible": (C.c_int, [_VP, _VP, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _VP, _I32, _I32,
                                      _VP, _VP, _VP]),
+    "pxt_mask_exclude": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     "pxt_iso_case_table": (C.c_int, [C.POINTER(_I32)]),
     "pxt_iso_surface_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "pxt_iso_surface_count": (C.c_int, [_VP, C.POINTER(IsoGrid), _VP, _VP, _VP]),
@@ -398,6 +400,9 @@ PROTOTYPES = {
     "pxt_mesh_render_frame_batch_workspace_bytes": (_I64, [_I32, _VP, _I32, _VP, _VP]),
     "pxt_mesh_render_frame_batch": (C.c_int, [C.POINTER(MeshDesc), _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP,
                                               _VP, _VP, _VP, _VP]),
+    "pxt_mesh_render_scene_batch_workspace_bytes": (_I64, [_I32, _VP, _I32, _VP, _VP]),
+    "pxt_mesh_render_scene_batch": (C.c_int, [C.POINTER(MeshDesc), _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                              _VP, _VP, _I32, _VP, _I64, _VP, _VP, _VP, _VP]),
 }
 
 

@@ -32,6 +32,10 @@
 // (u, v) under the LM's addressing - texel k's centre is at coordinate k, so it is floor(u + 0.5), floor(v + 0.5); the
 // centre tap of pxt_depth_refine's bilinear footprint has weight 1 exactly there - one byte of the occluder plane, one
 // byte out.  The three counts by ballot + population count, folded over the 16 waves through LDS by index.
+//
+// pxt_mask_exclude: a mask minus an occluder plane that some other call made (pxt_mesh_render_scene_batch's: the other
+// tracked objects of the image); see mask_exclude_kernel below.
+#include "pxt_bitrow.h"
 #include "pxt_common.h"
 #include "pxt_lm_point.h"
 
@@ -49,20 +53,6 @@ constexpr int kOcMaxShift = 32767;
 constexpr int kPvBlock = 1024;
 constexpr int kPvMaxPoints = 1 << 24;
 static_assert(kOcMaxR == 16 && kOcBand <= PXT_WAVE && kOcRec == 16, "band rows are served by one wave; record layout");
-
-struct OcRow {
-  unsigned long long lo, hi;
-};
-__device__ inline OcRow oc_and(OcRow a, OcRow b) { return {a.lo & b.lo, a.hi & b.hi}; }
-__device__ inline OcRow oc_or(OcRow a, OcRow b) { return {a.lo | b.lo, a.hi | b.hi}; }
-__device__ inline OcRow oc_shl(OcRow a, int s) {  // towards higher columns; 0 < s < 64
-  return {a.lo << s, (a.hi << s) | (a.lo >> (64 - s))};
-}
-__device__ inline OcRow oc_shr(OcRow a, int s) {
-  return {(a.lo >> s) | (a.hi << (64 - s)), a.hi >> s};
-}
-// the tile's own 64 columns: bits 32..95
-__device__ inline unsigned long long oc_core(OcRow a) { return (a.lo >> 32) | (a.hi << 32); }
 
 struct OcArgs {
   const float4* depth;      // [H][W]: .x = composited depth * depth_scale, .w = alpha
@@ -160,17 +150,7 @@ __global__ __launch_bounds__(256) void occlusion_mask_kernel(const OcArgs a) {
     sB[tid] = e;
   }
   __syncthreads();
-  // the image's columns 0 .. W - 1 are bits 32 - x0 .. 32 - x0 + W - 1, clipped to [0, 128)
-  OcRow in_cols = {0ull, 0ull};
-  {
-    const int b_lo = max(32 - x0, 0), b_hi = (int)min((long long)32 - x0 + W, (long long)128);
-    for (int b = 0; b < 2; ++b) {
-      const int lo = max(b_lo - 64 * b, 0), hi = min(b_hi - 64 * b, 64);
-      unsigned long long mbits = 0ull;
-      if (hi > lo) mbits = ((hi - lo) == 64 ? ~0ull : ((1ull << (hi - lo)) - 1ull)) << lo;
-      (b == 0 ? in_cols.lo : in_cols.hi) = mbits;
-    }
-  }
+  const OcRow in_cols = oc_image_columns(x0, W);
   if (tid < ah) {
     OcRow e = {~0ull, ~0ull};
     for (int d = -re; d <= re; ++d) {
@@ -186,12 +166,7 @@ __global__ __launch_bounds__(256) void occlusion_mask_kernel(const OcArgs a) {
   __syncthreads();
   // ---- dilation along x (radius rd in doubling shifts), then along y
   if (tid < ah) {
-    OcRow d = sA[tid];
-    for (int covered = 0, step = 1; covered < rd; step *= 2) {
-      const int sft = min(step, rd - covered);
-      d = oc_or(d, oc_or(oc_shl(d, sft), oc_shr(d, sft)));
-      covered += sft;
-    }
+    const OcRow d = oc_dilate_x(sA[tid], rd);
     sB[tid] = d;
   }
   __syncthreads();
@@ -213,7 +188,7 @@ __global__ __launch_bounds__(256) void occlusion_mask_kernel(const OcArgs a) {
     const unsigned long long g = oc_core(sA[r]);
     const int yy = y0 + r, xx = x0 + c4;
     const unsigned gb4 = (unsigned)((g >> c4) & 15ull);
-    const unsigned gbytes = (gb4 & 1u) | ((gb4 & 2u) << 7) | ((gb4 & 4u) << 14) | ((gb4 & 8u) << 21);
+    const unsigned gbytes = oc_bytes(gb4);
     // four bytes as one dword where every row starts 4-byte aligned (uniform)
     const bool vec = (W & 3) == 0 &&
                      ((((uintptr_t)a.mask_in) | ((uintptr_t)a.mask_out) | ((uintptr_t)a.occluder)) & 3u) == 0;
@@ -342,6 +317,95 @@ __global__ __launch_bounds__(kPvBlock) void points_visible_kernel(const PvArgs a
   }
 }
 
+// pxt_mask_exclude: mask_out = (mask_in != 0) && !occluder over the H * W bytes of a plane, which is elementwise: the
+// planes are walked as one row of vectors of V bytes (16 or 4 where all three are that aligned, else none) by ONE
+// workgroup of 1024 threads, four vectors of each input in flight per lane and trip, and the last H * W % V bytes one by
+// one.  The two counts by population count, folded over the 16 waves through LDS by index: no atomics, one launch.
+struct MxArgs {
+  const uint8_t* mask_in;
+  const uint8_t* occluder;
+  uint8_t* mask_out;
+  int32_t* record;
+  size_t n;  // H * W
+};
+
+// bit 0 of every byte: that byte of m is not 0
+__device__ inline unsigned mx_nonzero(unsigned m) {
+  return ((((m & 0x7f7f7f7fu) + 0x7f7f7f7fu) | m) & 0x80808080u) >> 7;
+}
+
+__device__ inline void mx_fold(unsigned m, unsigned g, unsigned* out, uint32_t* n_in, uint32_t* n_out) {
+  const unsigned in = mx_nonzero(m);
+  *out = in & ~mx_nonzero(g);
+  *n_in += (uint32_t)__popc(in);
+  *n_out += (uint32_t)__popc(*out);
+}
+__device__ inline unsigned mx_apply(unsigned m, unsigned g, uint32_t* n_in, uint32_t* n_out) {
+  unsigned o;
+  mx_fold(m, g, &o, n_in, n_out);
+  return o;
+}
+__device__ inline uint4 mx_apply(uint4 m, uint4 g, uint32_t* n_in, uint32_t* n_out) {
+  uint4 o;
+  mx_fold(m.x, g.x, &o.x, n_in, n_out);
+  mx_fold(m.y, g.y, &o.y, n_in, n_out);
+  mx_fold(m.z, g.z, &o.z, n_in, n_out);
+  mx_fold(m.w, g.w, &o.w, n_in, n_out);
+  return o;
+}
+
+template <class V>  // uint4 or unsigned; n_vec = 0: bytes alone
+__global__ __launch_bounds__(kPvBlock) void mask_exclude_kernel(const MxArgs a, const size_t n_vec) {
+  __shared__ uint32_t red[kPvBlock / PXT_WAVE][2];
+  constexpr int kAhead = 4;
+  const int tid = threadIdx.x;
+  uint32_t n_in = 0, n_out = 0;
+  const V* mi = (const V*)a.mask_in;
+  const V* oc = (const V*)a.occluder;
+  V* mo = (V*)a.mask_out;
+  for (size_t base = 0; base < n_vec; base += (size_t)kPvBlock * kAhead) {  // the whole workgroup alike
+    V m[kAhead], g[kAhead];
+#pragma unroll
+    for (int k = 0; k < kAhead; ++k) {
+      const size_t v = base + (size_t)k * kPvBlock + tid;
+      if (v < n_vec) {
+        m[k] = mi[v];
+        g[k] = oc[v];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kAhead; ++k) {
+      const size_t v = base + (size_t)k * kPvBlock + tid;
+      if (v < n_vec) mo[v] = mx_apply(m[k], g[k], &n_in, &n_out);
+    }
+  }
+  for (size_t i = n_vec * sizeof(V) + tid; i < a.n; i += kPvBlock) {
+    const bool in = a.mask_in[i] != 0, out = in && a.occluder[i] == 0;
+    n_in += in;
+    n_out += out;
+    a.mask_out[i] = out ? 1 : 0;
+  }
+#pragma unroll
+  for (int m = 1; m < PXT_WAVE; m <<= 1) {
+    n_in += (uint32_t)__shfl_xor((int)n_in, m, PXT_WAVE);
+    n_out += (uint32_t)__shfl_xor((int)n_out, m, PXT_WAVE);
+  }
+  if ((tid & (PXT_WAVE - 1)) == 0) {
+    red[tid / PXT_WAVE][0] = n_in;
+    red[tid / PXT_WAVE][1] = n_out;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t s_in = 0, s_out = 0;
+    for (int w = 0; w < kPvBlock / PXT_WAVE; ++w) {
+      s_in += red[w][0];
+      s_out += red[w][1];
+    }
+    a.record[0] = (int32_t)s_in;
+    a.record[1] = (int32_t)s_out;
+  }
+}
+
 bool oc_sizes_ok(int width, int height) {
   return width >= 1 && height >= 1 && (int64_t)width * height <= kOcMaxPixels;
 }
@@ -420,6 +484,25 @@ extern "C" int pxt_points_visible(const float* p3d, const uint8_t* valid_in, int
   for (int k = 0; k < 12; ++k) a.T[k] = pose12_host[k];
   for (int k = 0; k < 10; ++k) a.cam[k] = cam10_host[k];
   hipLaunchKernelGGL(points_visible_kernel, dim3(1), dim3(kPvBlock), 0, (hipStream_t)stream, a);
+  PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}
+
+extern "C" int pxt_mask_exclude(const uint8_t* mask_in, const uint8_t* occluder, int32_t width, int32_t height,
+                                uint8_t* mask_out, int32_t* record, void* stream) {
+  if (!mask_in || !occluder || !mask_out || !record) return PXT_E_ARG;
+  if (!oc_sizes_ok(width, height)) return PXT_E_ARG;
+  if (((uintptr_t)record % 4) != 0 || mask_out == occluder) return PXT_E_ARG;
+  MxArgs a;
+  a.mask_in = mask_in;
+  a.occluder = occluder;
+  a.mask_out = mask_out;
+  a.record = record;
+  a.n = (size_t)width * height;
+  const uintptr_t all = (uintptr_t)mask_in | (uintptr_t)occluder | (uintptr_t)mask_out;
+  hipStream_t s = (hipStream_t)stream;
+  if ((all & 15u) == 0) hipLaunchKernelGGL(mask_exclude_kernel<uint4>, dim3(1), dim3(kPvBlock), 0, s, a, a.n / 16);
+  else hipLaunchKernelGGL(mask_exclude_kernel<unsigned>, dim3(1), dim3(kPvBlock), 0, s, a, (all & 3u) == 0 ? a.n / 4 : (size_t)0);
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;
 }

@@ -29,9 +29,11 @@
 //
 // This file is compiled with -ffp-contract=off (pixtrack_amd/_build.py EXTRA): every product, sum and quotient is
 // rounded on its own, as numpy does it.
+#include "pxt_bitrow.h"
 #include "pxt_common.h"
 
 #include <algorithm>
+#include <cstring>
 
 namespace pxt {
 namespace {
@@ -976,6 +978,131 @@ __global__ __launch_bounds__(kRsBlock) void rb_resolve_kernel(const RbRecord* __
   else rf_resolve_view<Attr, 4>(a, attr, g, 0, wh, p0, red, packed);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// pxt_mesh_render_scene_batch: the batch call for objects that share an image.  Views that name the same scene are the
+// same camera (checked on the host: size and fx fy cx cy bit for bit, S = 1), so their key planes can be compared pixel
+// by pixel: view k is hidden at a pixel where it is covered and another member's z bits are smaller.  The high word of
+// an empty key is 0xffffffff, above the bits of every positive finite z: the smallest high word among the other members
+// decides, and only the keys' high words are read.
+//
+// rb_scene_kernel, one workgroup of 256 threads per 64 x 16 tile and view (pxt_occlusion_mask's mapping): the band of
+// 16 + 2 r_grow rows x 64 + 2 r_grow columns becomes one 128-bit word per row from two wave ballots of H (outside the
+// image H is 0, neutral for the dilation); kScRows band rows per wave trip, their four loads per member in flight
+// together.  Dilation by shift-OR along x and row-OR along y, the tile's 16 x 64 bits go out as bytes, four per thread.
+// n_hidden is the population of the ballots' own columns on the tile's own rows, n_occluder of the dilated core: one
+// integer atomicAdd per workgroup and word onto the record the clear zeroed.  It is launched between the list kernel,
+// which finishes the keys, and the resolves: the S = 1 planes it reads were written last and are read again next.
+struct RbSceneView {
+  unsigned char* occluder;  // [H][W], or NULL: the view wants no plane
+  unsigned others;          // bit j: view j is another member of this view's scene
+  int reserved;
+};
+
+struct RbSceneRecord {
+  RbRecord base;
+  RbSceneView scene[PXT_MESH_BATCH_MAX_VIEWS];
+};
+static_assert(PXT_MESH_BATCH_MAX_VIEWS <= 32, "RbSceneView::others holds one bit per view");
+
+constexpr int kScW = 64, kScH = 16, kScMaxR = PXT_MESH_SCENE_MAX_GROW;
+constexpr int kScBand = kScH + 2 * kScMaxR;  // staged rows at most
+constexpr int kScRows = 2;                   // band rows in flight per wave trip
+enum { RS_W_HIDDEN = 10, RS_W_OCCLUDER = 11 };
+
+__global__ __launch_bounds__(kRsBlock) void rb_scene_kernel(const RbSceneRecord* __restrict__ rec, const RbArgs b, const int R) {
+  __shared__ OcRow sA[kScBand], sB[kScBand];
+  __shared__ unsigned sHidden[kRsWaves], sGrown[kScH];
+  const int view = blockIdx.y;
+  unsigned char* const out = rec->scene[view].occluder;
+  if (!out) return;  // the whole workgroup alike
+  const int W = rec->base.view[view].g.W, H = rec->base.view[view].g.H;
+  const int tiles_x = (W + kScW - 1) / kScW, tiles_y = (H + kScH - 1) / kScH;
+  if ((int)blockIdx.x >= tiles_x * tiles_y) return;  // the grid is the largest view's
+  const unsigned others = rec->scene[view].others;
+  const unsigned* __restrict__ own_keys = (const unsigned*)(b.keys + rec->base.view[view].g.key_off);
+  const int x0 = ((int)blockIdx.x % tiles_x) * kScW, y0 = ((int)blockIdx.x / tiles_x) * kScH;
+  const int ah = kScH + 2 * R;  // rows y0 - R .. y0 + kScH + R - 1
+  const int tid = threadIdx.x, lane = tid & (PXT_WAVE - 1), wave = tid / PXT_WAVE;
+  // band column c of a row sits in ballot c / 64 at bit c % 64; the tile's own columns are c = R .. R + 63
+  const unsigned long long core0 = ~0ull << R, core1 = R ? ((1ull << R) - 1ull) : 0ull;
+  unsigned n_hidden = 0u;  // wave-uniform
+  for (int rb = wave; rb < ah; rb += kRsWaves * kScRows) {
+    size_t at[kScRows][2];
+    bool inside[kScRows][2];
+    unsigned own[kScRows][2], front[kScRows][2];
+#pragma unroll
+    for (int k = 0; k < kScRows; ++k) {
+      const int r = rb + kRsWaves * k, yy = y0 - R + r;
+#pragma unroll
+      for (int part = 0; part < 2; ++part) {
+        const int c = part * 64 + lane, xx = x0 - R + c;
+        inside[k][part] = r < ah && c < kScW + 2 * R && yy >= 0 && yy < H && xx >= 0 && xx < W;
+        at[k][part] = inside[k][part] ? 2 * ((size_t)yy * W + xx) + 1 : 0;  // the key's high word
+        own[k][part] = inside[k][part] ? own_keys[at[k][part]] : 0xffffffffu;
+        front[k][part] = 0xffffffffu;
+      }
+    }
+    for (unsigned m = others; m; m &= m - 1u) {  // the whole workgroup alike
+      const int j = __ffs((int)m) - 1;
+      const unsigned* __restrict__ kj = (const unsigned*)(b.keys + rec->base.view[j].g.key_off);  // W x H as this view's
+      unsigned z[kScRows][2];
+#pragma unroll
+      for (int k = 0; k < kScRows; ++k)
+#pragma unroll
+        for (int part = 0; part < 2; ++part) z[k][part] = inside[k][part] ? kj[at[k][part]] : 0xffffffffu;
+#pragma unroll
+      for (int k = 0; k < kScRows; ++k)
+#pragma unroll
+        for (int part = 0; part < 2; ++part) front[k][part] = min(front[k][part], z[k][part]);
+    }
+#pragma unroll
+    for (int k = 0; k < kScRows; ++k) {
+      const int r = rb + kRsWaves * k;
+      if (r >= ah) break;  // wave-uniform
+      const unsigned long long w0 = __ballot(own[k][0] != 0xffffffffu && front[k][0] < own[k][0]);
+      const unsigned long long w1 = __ballot(own[k][1] != 0xffffffffu && front[k][1] < own[k][1]);
+      if (r >= R && r < R + kScH) n_hidden += (unsigned)(__popcll(w0 & core0) + __popcll(w1 & core1));
+      if (lane == 0) sA[r] = oc_shl(OcRow{w0, w1}, 32 - R);  // column c to bit 32 - R + c; 24 <= 32 - R <= 32
+    }
+  }
+  if (lane == 0) sHidden[wave] = n_hidden;
+  __syncthreads();
+  if (tid < ah) sB[tid] = oc_dilate_x(sA[tid], R);
+  __syncthreads();
+  if (tid < kScH) {
+    OcRow d = {0ull, 0ull};
+    const int rc = tid + R;  // this tile row in the staged band
+    for (int q = rc - R; q <= rc + R; ++q) d = oc_or(d, sB[q]);  // 0 <= rc - R, rc + R < ah
+    d = oc_and(d, y0 + tid < H ? oc_image_columns(x0, W) : OcRow{0ull, 0ull});  // G lives inside the image
+    sA[tid] = d;
+    sGrown[tid] = (unsigned)__popcll(oc_core(d));
+  }
+  __syncthreads();
+  {
+    const int r = tid >> 4, c4 = (tid & 15) * 4;
+    const int yy = y0 + r, xx = x0 + c4;
+    const unsigned gbytes = oc_bytes((unsigned)((oc_core(sA[r]) >> c4) & 15ull));
+    if (yy < H && xx < W) {
+      const size_t px = (size_t)yy * W + xx;
+      if ((W & 3) == 0) {  // every row starts 4-byte aligned, as the plane does
+        *(unsigned*)(out + px) = gbytes;
+      } else {
+        for (int j = 0; j < 4 && xx + j < W; ++j) out[px + j] = (unsigned char)((gbytes >> (8 * j)) & 1u);
+      }
+    }
+  }
+  if (tid == 0) {
+    unsigned h = 0u, g = 0u;
+#pragma unroll
+    for (int w = 0; w < kRsWaves; ++w) h += sHidden[w];
+#pragma unroll
+    for (int r = 0; r < kScH; ++r) g += sGrown[r];
+    unsigned* record = b.records + (size_t)view * PXT_MESH_RASTER_RECORD;
+    if (h) atomicAdd(record + RS_W_HIDDEN, h);
+    if (g) atomicAdd(record + RS_W_OCCLUDER, g);
+  }
+}
+
 constexpr int64_t kRsMaxPixels = (int64_t)1 << 26;
 constexpr int kRsMaxViews = 4096, kRsMaxCount = 1 << 24, kRsMaxTexture = 16384;
 
@@ -1063,13 +1190,14 @@ int rf_launch(const RfArgs& f, const Attr& attr, int64_t n_keys, hipStream_t s) 
 }
 
 // pxt_mesh_render_frame_batch's workspace: the key planes, the list counters, every view's own list (placed by a prefix
-// sum of the caps), the parameter record.
+// sum of the caps), the parameter record (pxt_mesh_render_scene_batch's is the longer RbSceneRecord).
 struct RbLayout {
   int64_t n_keys, count_off, list_off, record_off, bytes;
   int64_t view_list[PXT_MESH_BATCH_MAX_VIEWS];  // first entry of each view's list
 };
 
-bool rb_layout(int M, const int32_t* n_triangles, int P, const int32_t* view_mesh, const int32_t* geometry, RbLayout* l) {
+bool rb_layout(int M, const int32_t* n_triangles, int P, const int32_t* view_mesh, const int32_t* geometry, RbLayout* l,
+               size_t record_bytes = sizeof(RbRecord)) {
   if (M < 1 || M > PXT_MESH_BATCH_MAX_MESHES || !n_triangles || !view_mesh) return false;
   for (int m = 0; m < M; ++m)
     if (n_triangles[m] < 1 || n_triangles[m] > kRsMaxCount) return false;
@@ -1083,17 +1211,63 @@ bool rb_layout(int M, const int32_t* n_triangles, int P, const int32_t* view_mes
   l->count_off = l->n_keys * 8;
   l->list_off = l->count_off + rs_count_bytes(P);
   l->record_off = l->list_off + entries * 16;
-  l->bytes = l->record_off + (int64_t)(sizeof(RbRecord) + 15) / 16 * 16;
+  l->bytes = l->record_off + (int64_t)(record_bytes + 15) / 16 * 16;
   return true;
 }
 
 // The pinned blocks the parameter record is staged in: a ring per thread and device; a block is reused once its
 // previous copy has been made (pxt_ngp_render_frame_batch's scheme).
 struct RbStageSlot {
-  RbRecord* host = nullptr;
+  RbSceneRecord* host = nullptr;  // the scene table is copied by pxt_mesh_render_scene_batch alone
   hipEvent_t copied = nullptr;
 };
 constexpr int kRbStageSlots = 4, kRbStageDevices = 16;
+
+// pxt_mesh_render_scene_batch's own arguments.
+struct RbSceneCall {
+  const int32_t* view_scene;
+  int32_t r_grow;
+  uint8_t* out_occluder;
+  int64_t occluder_bytes;
+  const int64_t* occluder_offsets;
+};
+
+// The scene table of the P placed views `table` whose floats are `views`; -> every bound of the header holds.
+bool rb_place_scenes(const RbSceneCall& c, int P, const RbView* table, const float* views, RbSceneView* scene, bool* any,
+                     int64_t* tiles) {
+  if (!c.view_scene || !c.occluder_offsets || c.r_grow < 0 || c.r_grow > kScMaxR) return false;
+  if (((uintptr_t)c.out_occluder % 4) != 0) return false;
+  *any = false;
+  for (int p = 0; p < P; ++p) {
+    RbSceneView& v = scene[p];
+    v = RbSceneView{};
+    const int s = c.view_scene[p];
+    const int64_t off = c.occluder_offsets[p];
+    const RfView& g = table[p].g;
+    if (s < -1 || s >= P) return false;
+    if (s < 0) {
+      if (off >= 0) return false;
+      continue;
+    }
+    if (g.S != 1) return false;
+    for (int j = 0; j < P; ++j) {
+      if (j == p || c.view_scene[j] != s) continue;
+      const RfView& o = table[j].g;
+      if (o.W != g.W || o.H != g.H) return false;
+      if (std::memcmp(views + (size_t)j * PXT_MESH_VIEW + 12, views + (size_t)p * PXT_MESH_VIEW + 12, 4 * sizeof(float)) != 0)
+        return false;
+      v.others |= 1u << j;
+    }
+    if (off < 0) continue;
+    const int64_t bytes = (int64_t)g.W * g.H;
+    if (!c.out_occluder || (off % 4) != 0 || c.occluder_bytes < 0 || off > c.occluder_bytes || bytes > c.occluder_bytes - off)
+      return false;
+    v.occluder = c.out_occluder + off;
+    *any = true;
+    *tiles = std::max<int64_t>(*tiles, (int64_t)((g.W + kScW - 1) / kScW) * ((g.H + kScH - 1) / kScH));
+  }
+  return true;
+}
 
 }  // namespace
 }  // namespace pxt
@@ -1268,16 +1442,17 @@ extern "C" int64_t pxt_mesh_render_frame_batch_workspace_bytes(int32_t n_meshes,
   return l.bytes;
 }
 
-extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh,
-                                           const float* views, int32_t n_views, const int32_t* geometry,
-                                           const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8,
-                                           float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
-                                           uint32_t* records, void* workspace, void* stream) {
+// The two batch calls: `scene` is pxt_mesh_render_scene_batch's own arguments, NULL for pxt_mesh_render_frame_batch.
+static int rb_render(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh, const float* views,
+                     int32_t n_views, const int32_t* geometry, const int64_t* out_offsets, float* out_rgba,
+                     uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
+                     uint32_t* records, void* workspace, void* stream, const RbSceneCall* scene) {
   if (!meshes || n_meshes < 1 || n_meshes > PXT_MESH_BATCH_MAX_MESHES) return PXT_E_ARG;
   int32_t n_triangles[PXT_MESH_BATCH_MAX_MESHES];
   for (int m = 0; m < n_meshes; ++m) n_triangles[m] = meshes[m].n_triangles;
   RbLayout l;
-  if (!rb_layout(n_meshes, n_triangles, n_views, view_mesh, geometry, &l)) return PXT_E_ARG;
+  const size_t record_bytes = scene ? sizeof(RbSceneRecord) : sizeof(RbRecord);
+  if (!rb_layout(n_meshes, n_triangles, n_views, view_mesh, geometry, &l, record_bytes)) return PXT_E_ARG;
   if (!views || !out_offsets || !out_bytes || !records || !workspace) return PXT_E_ARG;
   if (((uintptr_t)views % 4) != 0 || ((uintptr_t)records % 4) != 0 || ((uintptr_t)out_rgb_u8 % 4) != 0 ||
       ((uintptr_t)out_depth_nz % 4) != 0 || ((uintptr_t)out_rgba % 16) != 0 || ((uintptr_t)out_depth % 16) != 0 ||
@@ -1307,6 +1482,10 @@ extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t 
     tiles = std::max<int64_t>(tiles, (int64_t)((w.g.Wf + kRsTile - 1) / kRsTile) * ((w.g.Hf + kRsTile - 1) / kRsTile));
     res = std::max<int64_t>(res, ((int64_t)w.g.W * w.g.H + kRsShadePixels - 1) / kRsShadePixels);
   }
+  RbSceneView scenes[PXT_MESH_BATCH_MAX_VIEWS] = {};
+  bool any_plane = false;
+  int64_t scene_tiles = 1;
+  if (scene && !rb_place_scenes(*scene, n_views, table, views, scenes, &any_plane, &scene_tiles)) return PXT_E_ARG;
   // every argument is checked: from here on the call writes
   hipStream_t s = (hipStream_t)stream;
   static thread_local RbStageSlot stage[kRbStageDevices][kRbStageSlots];
@@ -1317,12 +1496,12 @@ extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t 
   RbStageSlot& slot = stage[dev_id][stage_next[dev_id]];
   stage_next[dev_id] = (stage_next[dev_id] + 1) % kRbStageSlots;
   if (!slot.host) {
-    PXT_HIP_CHECK(hipHostMalloc((void**)&slot.host, sizeof(RbRecord), hipHostMallocDefault));
+    PXT_HIP_CHECK(hipHostMalloc((void**)&slot.host, sizeof(RbSceneRecord), hipHostMallocDefault));
     PXT_HIP_CHECK(hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
   } else {
     PXT_HIP_CHECK(hipEventSynchronize(slot.copied));
   }
-  RbRecord* const h = slot.host;
+  RbRecord* const h = &slot.host->base;
   for (int m = 0; m < PXT_MESH_BATCH_MAX_MESHES; ++m) {
     RbMesh& o = h->mesh[m];
     o = RbMesh{};
@@ -1340,8 +1519,9 @@ extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t 
   std::copy(views, views + (size_t)n_views * PXT_MESH_VIEW, h->views);
   std::fill(h->views + (size_t)n_views * PXT_MESH_VIEW, h->views + PXT_MESH_BATCH_MAX_VIEWS * PXT_MESH_VIEW, 0.f);
   char* const ws = (char*)workspace;
-  const RbRecord* rec = (const RbRecord*)(ws + l.record_off);
-  PXT_HIP_CHECK(hipMemcpyAsync(ws + l.record_off, h, sizeof(RbRecord), hipMemcpyHostToDevice, s));
+  if (scene) std::copy(scenes, scenes + PXT_MESH_BATCH_MAX_VIEWS, slot.host->scene);
+  const RbRecord* rec = (const RbRecord*)(ws + l.record_off);  // the first member of an RbSceneRecord
+  PXT_HIP_CHECK(hipMemcpyAsync(ws + l.record_off, slot.host, record_bytes, hipMemcpyHostToDevice, s));
   PXT_HIP_CHECK(hipEventRecord(slot.copied, s));
   RbArgs b;
   b.keys = (unsigned long long*)ws;
@@ -1358,6 +1538,11 @@ extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t 
   PXT_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(rb_list_kernel, dim3((unsigned)tiles, n_views), dim3(kRsBlock), 0, s, rec, b);
   PXT_HIP_CHECK(hipGetLastError());
+  if (any_plane) {  // the keys are final; before the resolves (see rb_scene_kernel)
+    hipLaunchKernelGGL(rb_scene_kernel, dim3((unsigned)scene_tiles, n_views), dim3(kRsBlock), 0, s,
+                       (const RbSceneRecord*)(ws + l.record_off), b, (int)scene->r_grow);
+    PXT_HIP_CHECK(hipGetLastError());
+  }
   if (kind[0]) {
     hipLaunchKernelGGL(rb_resolve_kernel<RsVertexColors>, dim3((unsigned)res, n_views), dim3(kRsBlock), 0, s, rec, b);
     PXT_HIP_CHECK(hipGetLastError());
@@ -1367,4 +1552,32 @@ extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t 
     PXT_HIP_CHECK(hipGetLastError());
   }
   return PXT_OK;
+}
+
+extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh,
+                                           const float* views, int32_t n_views, const int32_t* geometry,
+                                           const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8,
+                                           float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
+                                           uint32_t* records, void* workspace, void* stream) {
+  return rb_render(meshes, n_meshes, view_mesh, views, n_views, geometry, out_offsets, out_rgba, out_rgb_u8, out_depth,
+                   out_depth_nz, out_bytes, records, workspace, stream, nullptr);
+}
+
+extern "C" int64_t pxt_mesh_render_scene_batch_workspace_bytes(int32_t n_meshes, const int32_t* n_triangles, int32_t n_views,
+                                                               const int32_t* view_mesh, const int32_t* geometry) {
+  RbLayout l;
+  if (!rb_layout(n_meshes, n_triangles, n_views, view_mesh, geometry, &l, sizeof(RbSceneRecord))) return PXT_E_ARG;
+  return l.bytes;
+}
+
+extern "C" int pxt_mesh_render_scene_batch(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh,
+                                           const float* views, int32_t n_views, const int32_t* geometry,
+                                           const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8,
+                                           float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
+                                           const int32_t* view_scene, int32_t r_grow, uint8_t* out_occluder,
+                                           int64_t occluder_bytes, const int64_t* occluder_offsets, uint32_t* records,
+                                           void* workspace, void* stream) {
+  const RbSceneCall scene = {view_scene, r_grow, out_occluder, occluder_bytes, occluder_offsets};
+  return rb_render(meshes, n_meshes, view_mesh, views, n_views, geometry, out_offsets, out_rgba, out_rgb_u8, out_depth,
+                   out_depth_nz, out_bytes, records, workspace, stream, &scene);
 }

@@ -25,6 +25,10 @@ A frame's views (``MeshRenderer.render_frame``, ``supersampled_view``, ``frame_r
 eight views of the mesh in one call, each with its own size, its own outputs and ``supersample`` x ``supersample``
 samples per pixel, box-filtered in a fixed order - the tracker's ``depth_nz`` plane and its anti-aliased reference image
 from one call (``mesh_template.py``).
+
+Several meshes' frames in one call (``render_frame_batch``, ``frame_batch_reference``, pxt_mesh_render_frame_batch), and
+with ``scenes=`` the objects of one image hiding each other (``scene_reference``, pxt_mesh_render_scene_batch): per view
+of a scene the pixels where another member has the smaller z bits in the call's own key planes, grown by a box.
 """
 from __future__ import annotations
 
@@ -44,6 +48,7 @@ SUB = 256  # sub-pixel steps per pixel
 GUARD = float(1 << 23)
 # record words
 W_COVERED, W_DRAWN, W_NEAR, W_GUARD, W_ZERO, W_INDEX, W_OFF, W_ZMIN, W_ZMAX, W_STATUS = range(10)
+W_HIDDEN, W_OCCLUDER = 10, 11  # pxt_mesh_render_scene_batch's
 _EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 _F = np.float32
 
@@ -613,12 +618,85 @@ def frame_batch_reference(items) -> list:
     return [frame_reference(V, F, shading, requests) for V, F, shading, requests in items]
 
 
+def dilate_box(plane: np.ndarray, r: int) -> np.ndarray:
+    """``plane`` bool [H, W] -> its dilation with the ``(2 r + 1)^2`` box, pixels outside the image ignored."""
+    H, W = plane.shape
+    padded = np.pad(np.asarray(plane, bool), int(r))
+    out = np.zeros((H, W), bool)
+    for dy in range(2 * int(r) + 1):
+        for dx in range(2 * int(r) + 1):
+            out |= padded[dy:dy + H, dx:dx + W]
+    return out
+
+
+SCENE_MAX_GROW = _lib.PXT_MESH_SCENE_MAX_GROW
+
+
+def _scene_ids(scenes, counts, what):
+    """``scenes`` = per item one scene id (an int >= 0, or None) per request -> the same as a list of lists."""
+    scenes = [list(s) for s in scenes]
+    if [len(s) for s in scenes] != list(counts):
+        raise ValueError(f"{what}: scenes holds one id or None per item and request ({list(counts)}; got "
+                         f"{[len(s) for s in scenes]})")
+    for s in scenes:
+        for v in s:
+            if v is not None and (int(v) != v or int(v) < 0):
+                raise ValueError(f"{what}: a scene id is None or an int >= 0 (got {v!r})")
+    return [[None if v is None else int(v) for v in s] for s in scenes]
+
+
+def scene_reference(items, scenes, r_grow: int = 0) -> list:
+    """The rule of pxt_mesh_render_scene_batch in numpy: ``frame_batch_reference`` and, for every request with a scene id,
+    ``"occluder"`` (uint8 [H, W]) and record words 10 (hidden pixels) and 11 (occluder pixels).  ``scenes``: per item, one
+    scene id or None per request.  The views of one scene are one camera (same size, ``fx fy cx cy`` bit-equal,
+    supersample 1; anything else is a ValueError).  View k is hidden at a pixel where it is covered and another member
+    of its scene is covered with SMALLER z bits - read from the numpy rasteriser's own key planes, unscaled, so ``near``
+    and ``depth_q`` may differ; equal bits do not hide.  The plane is that, grown by the ``(2 r_grow + 1)^2`` box inside
+    the image."""
+    items = [(V, F, shading, list(requests)) for V, F, shading, requests in items]
+    scenes = _scene_ids(scenes, [len(it[3]) for it in items], "scene_reference")
+    if not (0 <= int(r_grow) <= SCENE_MAX_GROW):
+        raise ValueError(f"r_grow is 0..{SCENE_MAX_GROW} (got {r_grow})")
+    out = frame_batch_reference(items)
+    members: dict = {}
+    for m, (V, F, _, requests) in enumerate(items):
+        for q, request in enumerate(requests):
+            if scenes[m][q] is None:
+                continue
+            view, W, H, S, _ = _frame_request(request)
+            if S != 1:
+                raise ValueError(f"a scene's views have supersample 1 (item {m}, request {q}: {S})")
+            key, _, _ = _raster_view(np.ascontiguousarray(np.asarray(V, np.float32).reshape(-1, 3)),
+                                     np.asarray(F).reshape(-1, 3).astype(np.int64), view, W, H, False)
+            members.setdefault(scenes[m][q], []).append((m, q, view, W, H, key))
+    for s, views in members.items():
+        _, _, view0, W, H, _ = views[0]
+        for m, q, view, Wv, Hv, _ in views:
+            if (Wv, Hv) != (W, H) or view[12:16].tobytes() != view0[12:16].tobytes():
+                raise ValueError(f"scene {s}: item {m}, request {q} is not the camera of the scene's first view")
+        covered = [key != _EMPTY for *_, key in views]
+        zbits = [(key >> np.uint64(32)).astype(np.uint32) for *_, key in views]
+        for k, (m, q, *_rest) in enumerate(views):
+            hidden = np.zeros(H * W, bool)
+            for j in range(len(views)):
+                if j != k:
+                    hidden |= covered[j] & (zbits[j] < zbits[k])
+            hidden &= covered[k]
+            grown = dilate_box(hidden.reshape(H, W), r_grow)
+            res = out[m][q]
+            res["occluder"] = grown.astype(np.uint8)
+            res["records"] = np.array(res["records"], np.uint32)
+            res["records"][W_HIDDEN], res["records"][W_OCCLUDER] = hidden.sum(), grown.sum()
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
-# several meshes' frames in one call (pxt_mesh_render_frame_batch)
+# several meshes' frames in one call (pxt_mesh_render_frame_batch, pxt_mesh_render_scene_batch)
 # ---------------------------------------------------------------------------------------------------------------------
 BATCH_MAX_MESHES = _lib.PXT_MESH_BATCH_MAX_MESHES
 BATCH_MAX_VIEWS = _lib.PXT_MESH_BATCH_MAX_VIEWS
 _BATCH_PLANS: dict = {}
+_SCENE_PLANS: dict = {}
 
 
 class FrameBatchWorkspace:
@@ -667,13 +745,50 @@ def _batch_plan(shapes):
     return calls
 
 
-def render_frame_batch(items, workspace: Optional[FrameBatchWorkspace] = None, download_records: bool = True) -> list:
+def _scene_plan(shapes, plan, scenes):
+    """What the calls of ``plan`` need for ``scenes`` (per item, one id or None per request): per call (view_scene,
+    occluder offsets, occluder bytes, workspace bytes).  A scene whose views fall into two calls is refused."""
+    call_of = {}
+    out = []
+    for c, (a, n, view_mesh, geometry, _offsets, _sizes, _need) in enumerate(plan):
+        ids = [s for m in range(a, a + n) for s in scenes[m]]
+        first, view_scene, occ_offsets, occ_bytes = {}, [], [], 0
+        for p, s in enumerate(ids):
+            if s is None:
+                view_scene.append(-1)
+                occ_offsets.append(-1)
+                continue
+            if call_of.setdefault(s, c) != c:
+                raise _lib.PxtError(f"render_frame_batch: scene {s} would be split across two calls ({BATCH_MAX_MESHES} "
+                                    f"meshes / {BATCH_MAX_VIEWS} views each): order the items so that it fits one")
+            view_scene.append(first.setdefault(s, p))
+            occ_offsets.append(occ_bytes)
+            occ_bytes += (geometry[3 * p] * geometry[3 * p + 1] + 15) // 16 * 16
+        C = _lib.C
+        need = int(_lib.lib().pxt_mesh_render_scene_batch_workspace_bytes(
+            n, (C.c_int32 * n)(*[shapes[m][0] for m in range(a, a + n)]), len(view_mesh),
+            (C.c_int32 * len(view_mesh))(*view_mesh), (C.c_int32 * len(geometry))(*geometry)))
+        if need <= 0:
+            raise _lib.PxtError(f"render_frame_batch: the views {geometry} are not supported")
+        out.append((view_scene, occ_offsets, occ_bytes, need))
+    return out
+
+
+def render_frame_batch(items, workspace: Optional[FrameBatchWorkspace] = None, download_records: bool = True,
+                       scenes=None, r_grow: int = 0) -> list:
     """``MeshRenderer.render_frame`` for several meshes in one chain of launches
     (``torch.ops.pixtrack.mesh_render_frame_batch``): ``items`` = ``[(MeshRenderer, requests)]``, the requests as
     ``render_frame`` takes them -> one list of dicts per item, each dict what ``render_frame`` returns for that request,
     bit for bit.  The views' 20 floats travel in the call's parameter record: one upload for all items.  More than 16
     meshes or 32 views are served in consecutive calls.  ``workspace``: a ``FrameBatchWorkspace`` of the stream the
-    call is made on (None: one for this call)."""
+    call is made on (None: one for this call).
+
+    ``scenes`` (per item, one scene id or None per request; None: exactly the call above): objects that share an image.
+    The requests that name one id are one camera at supersample 1; each of their dicts gains ``"occluder"`` (uint8
+    [H, W]: where another member of the scene lies in front, grown by the ``(2 r_grow + 1)^2`` box) and record words 10
+    and 11 (hidden pixels, occluder pixels) - ``torch.ops.pixtrack.mesh_render_scene_batch``, one more launch,
+    ``scene_reference`` bit for bit.  A scene that the 16-mesh / 32-view limits would split across two calls is a
+    ``PxtError``: an incomplete scene is not drawn."""
     items = [(r, list(requests)) for r, requests in items]
     if not items:
         return []
@@ -694,25 +809,45 @@ def render_frame_batch(items, workspace: Optional[FrameBatchWorkspace] = None, d
     plan = _BATCH_PLANS.get(shapes)
     if plan is None:  # the planes' places, the calls and their workspace, once per shape set
         plan = _BATCH_PLANS[shapes] = _batch_plan(shapes)
-    ws = (workspace or FrameBatchWorkspace()).ensure(max(c[-1] for c in plan), device)
-    op = items[0][0]._ops.mesh_render_frame_batch
+    scene_plan = None
+    if scenes is not None:
+        try:
+            scenes = _scene_ids(scenes, [len(q) for q in reqs], "render_frame_batch")
+        except ValueError as e:
+            raise _lib.PxtError(str(e)) from None
+        scene_key = (shapes, tuple(tuple(s) for s in scenes))
+        scene_plan = _SCENE_PLANS.get(scene_key)
+        if scene_plan is None:
+            scene_plan = _SCENE_PLANS[scene_key] = _scene_plan(shapes, plan, scenes)
+    ws = (workspace or FrameBatchWorkspace()).ensure(max(c[-1] for c in (scene_plan or plan)), device)
+    ops = items[0][0]._ops
     out = []
-    for a, n, view_mesh, geometry, offsets, sizes, _need in plan:
+    for c, (a, n, view_mesh, geometry, offsets, sizes, _need) in enumerate(plan):
         part, part_reqs = [r for r, _ in items[a:a + n]], reqs[a:a + n]
         views = torch.from_numpy(np.ascontiguousarray(np.stack([q[0] for qs in part_reqs for q in qs])))
         bufs = [None if size == 0 else torch.empty(size // (4 if k in (0, 2) else 1),
                                                    dtype=torch.float32 if k in (0, 2) else torch.uint8, device=device)
                 for k, size in enumerate(sizes)]
         records = torch.empty((len(view_mesh), RECORD), dtype=torch.int32, device=device)
-        op([r.vertices for r in part], [r.triangles for r in part], [r.colors for r in part], [r.uvs for r in part],
-           [r.triangle_uvs for r in part], [r.texture for r in part], view_mesh, views, geometry, offsets, *bufs, records,
-           ws)
+        meshes = ([r.vertices for r in part], [r.triangles for r in part], [r.colors for r in part], [r.uvs for r in part],
+                  [r.triangle_uvs for r in part], [r.texture for r in part])
+        occluder, occ_offsets = None, None
+        if scene_plan is None:
+            ops.mesh_render_frame_batch(*meshes, view_mesh, views, geometry, offsets, *bufs, records, ws)
+        else:
+            view_scene, occ_offsets, occ_bytes, _ = scene_plan[c]
+            occluder = torch.empty(occ_bytes, dtype=torch.uint8, device=device) if occ_bytes else None
+            ops.mesh_render_scene_batch(*meshes, view_mesh, views, geometry, offsets, view_scene, int(r_grow), occ_offsets,
+                                        *bufs, occluder, records, ws)
         rec = records.cpu().numpy().view(np.uint32) if download_records else records
         p = 0
         for qs in part_reqs:
             res_item = []
             for _, W, H, S, want in qs:
-                res_item.append(_frame_planes(bufs, offsets, p, W, H, want, rec))
+                res = _frame_planes(bufs, offsets, p, W, H, want, rec)
+                if occ_offsets is not None and occ_offsets[p] >= 0:
+                    res["occluder"] = occluder[occ_offsets[p]:occ_offsets[p] + W * H].view(H, W)
+                res_item.append(res)
                 p += 1
             out.append(res_item)
     return out

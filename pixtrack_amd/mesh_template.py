@@ -89,12 +89,25 @@ class MeshTemplate:
         return res + (out[0]["depth"],) if want_depth else res
 
     @staticmethod
-    def frames(templates, poses, query_cameras, reference_cameras, workspace=None) -> list:
+    def frames(templates, poses, query_cameras, reference_cameras, workspace=None, scenes=None, r_grow: int = 0,
+               records: bool = False) -> list:
         """``frame`` for several templates - K objects tracked in lock-step - in ONE ``mesh_render.render_frame_batch``
         call: every template's ``requests`` as ``frame`` forms them, one chain of launches, one upload of all views ->
         ``[(depth_nz, rgb_u8)]`` per template, the planes ``frame`` returns bit for bit.  ``workspace``: the calling
-        stream's ``mesh_render.FrameBatchWorkspace`` (None: one for this call)."""
-        items = [(t.renderer, t.requests(pose, qc, rc)) for t, pose, qc, rc in zip(templates, poses, query_cameras,
-                                                                                    reference_cameras)]
-        outs = R.render_frame_batch(items, workspace=workspace, download_records=False)
-        return [(out[0]["depth_nz"], out[-1]["rgb_u8"]) for out in outs]
+        stream's ``mesh_render.FrameBatchWorkspace`` (None: one for this call).
+
+        ``scenes`` (one scene id or None per template; None: exactly the call above): templates that name one id are
+        objects in one image.  The scene view is the query view, view 0 of ``requests``; the templates of a scene share
+        the query camera.  -> ``[(depth_nz, rgb_u8, occluder or None)]``: ``occluder`` uint8 [Hq, Wq] marks the pixels
+        where another template of the scene lies in front of this one, grown by the ``(2 r_grow + 1)^2`` box
+        (pxt_mesh_render_scene_batch, one more launch).  ``records``: the query view's record (int32 [16] on the
+        device; words 0, 10, 11: covered, hidden, occluder pixels) is appended to every tuple."""
+        reqs = [t.requests(pose, qc, rc) for t, pose, qc, rc in zip(templates, poses, query_cameras, reference_cameras)]
+        items = [(t.renderer, q) for t, q in zip(templates, reqs)]
+        if scenes is None:
+            outs = R.render_frame_batch(items, workspace=workspace, download_records=False)
+            return [(out[0]["depth_nz"], out[-1]["rgb_u8"]) + ((out[0]["records"],) if records else ()) for out in outs]
+        view_scenes = [[s] + [None] * (len(q) - 1) for s, q in zip(scenes, reqs)]
+        outs = R.render_frame_batch(items, workspace=workspace, download_records=False, scenes=view_scenes, r_grow=r_grow)
+        return [(out[0]["depth_nz"], out[-1]["rgb_u8"], out[0].get("occluder")) + ((out[0]["records"],) if records else ())
+                for out in outs]

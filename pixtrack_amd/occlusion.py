@@ -17,6 +17,8 @@ and a reference point whose projection's nearest texel lies in G leaves the LM's
 
 * ``occlusion_mask`` / ``points_visible``: the device wrappers of ``torch.ops.pixtrack.occlusion_mask`` /
   ``points_visible``; both only enqueue.
+* ``mask_exclude`` / ``mask_exclude_reference``: a mask minus an occluder plane that some other call made - the lock-step
+  tracker's mutual occlusion takes the plane from the other tracked meshes (``pxt_mesh_render_scene_batch``).
 * ``occlusion_mask_reference`` / ``points_visible_reference``: the numpy float32 restatements - the oracles of the
   tests.  The mask rules are single IEEE operations and are restated exactly; the projection is not (the kernel's FMA
   contraction), so a point within 1e-3 px of a texel boundary is *fragile* (``points_visible_reference`` marks it).
@@ -205,6 +207,17 @@ def points_visible_reference(p3d, valid_in, T12, camera, occluder, dtype=np.floa
             "near_edge": near_edge}
 
 
+def mask_exclude_reference(mask_in, occluder) -> Dict:
+    """numpy restatement of ``pxt_mask_exclude``: uint8 [H, W] planes -> dict(mask uint8 [H, W] = ``(mask_in != 0) &
+    (occluder == 0)``, record (n_mask_in, n_mask_out))."""
+    m, g = np.asarray(mask_in), np.asarray(occluder)
+    if m.ndim != 2 or m.shape != g.shape:
+        raise ValueError(f"mask_in and occluder are [H, W] planes of one size (got {m.shape}, {g.shape})")
+    mi = m != 0
+    mo = mi & (g == 0)
+    return {"mask": mo.astype(np.uint8), "record": (int(mi.sum()), int(mo.sum()))}
+
+
 def decode_record(rec) -> Dict[str, int]:
     """The 16-word record -> {name: count} (``RECORD_NAMES``)."""
     r = np.asarray(rec.detach().cpu().numpy() if hasattr(rec, "detach") else rec).reshape(-1)
@@ -244,6 +257,22 @@ def occlusion_mask(depth, sensor, mask_in, shift, min_alpha: float, sensor_q: fl
     ops.occlusion_mask(depth, sensor, mask_in, [int(shift[0]), int(shift[1])], float(min_alpha), float(sensor_q),
                        float(delta_q), [ro, rg], mask, occluder, record, workspace)
     return {"mask": mask, "occluder": occluder, "record": record, "workspace": workspace}
+
+
+def mask_exclude(mask_in, occluder, mask=None, record=None):
+    """Enqueue ``torch.ops.pixtrack.mask_exclude`` on the current stream: ``mask_in`` minus an ``occluder`` plane that
+    another call made (uint8 [H, W] device tensors) -> (mask uint8 [H, W] - ``mask`` may be ``mask_in``; default: a fresh
+    plane -, record: int32, words 0 and 1 = n_mask_in, n_mask_out; default: a fresh one on the device)."""
+    import torch
+
+    from .ops import ops
+
+    if mask is None:
+        mask = torch.empty_like(mask_in)
+    if record is None:
+        record = torch.zeros(2, dtype=torch.int32, device=mask_in.device)
+    ops.mask_exclude(mask_in, occluder, mask, record)
+    return mask, record
 
 
 def points_visible(p3d, valid_in, pose, camera, occluder, record=None, valid=None):

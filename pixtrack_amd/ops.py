@@ -34,6 +34,9 @@ Reference call sites the ops stand in for:
                        image lies in front of the mask view's Depth render, opened and grown (occlusion.py)
   points_visible       (opt-in, no reference counterpart) the LM's point mask minus the points that project onto that
                        occluder plane
+  mesh_render_scene_batch  (opt-in, no reference counterpart) mesh_render_frame_batch for objects that share an image:
+                       per view also the pixels where another tracked mesh of its scene lies in front, grown
+  mask_exclude         (opt-in, no reference counterpart) a mask minus such an occluder plane
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -167,6 +170,9 @@ SCHEMAS = {
     "points_visible": (
         "(Tensor p3d, Tensor? valid_in, float[] pose, float[] camera, int ndist, Tensor occluder, Tensor(a!) valid, "
         "Tensor(b!) record) -> ()"),
+    # mask_in uint8 [H, W] minus an occluder plane uint8 [H, W] that another call made -> mask uint8 [H, W] (may be
+    # mask_in) and words 0, 1 of record (int32, >= 2 words, device or pinned): n_mask_in, n_mask_out (pxt_mask_exclude)
+    "mask_exclude": "(Tensor mask_in, Tensor occluder, Tensor(a!) mask, Tensor(b!) record) -> ()",
     # network query (pxt_ngp_query): pos, dir [n, 3] (ngp coordinates, unit view directions) -> out [n, 4] = (density
     # logit, r, g, b)
     "ngp_query": "(int ctx, Tensor pos, Tensor dir, Tensor(a!) out) -> ()",
@@ -219,6 +225,17 @@ SCHEMAS = {
         "(Tensor[] vertices, Tensor[] triangles, Tensor?[] colors, Tensor?[] uvs, Tensor?[] triangle_uvs, "
         "Tensor?[] texture, int[] view_mesh, Tensor views, int[] geometry, int[] offsets, Tensor(a!)? rgba, "
         "Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, Tensor(e!) records, Tensor(f!) workspace) -> ()"),
+    # mesh_render_frame_batch for objects that share an image (pxt_mesh_render_scene_batch): view_scene = the scene of
+    # each view (-1: none; the views of one scene are one camera, supersample 1), occluder_offsets = the byte offset of
+    # each view's uint8 [H, W] plane in the flat buffer occluder (a multiple of 4; -1: the view wants none) -> where
+    # another member of the view's scene lies in front, grown by r_grow in 0..8; records words 10, 11 = hidden pixels,
+    # occluder pixels.  Everything else as mesh_render_frame_batch, bit for bit; workspace:
+    # pxt_mesh_render_scene_batch_workspace_bytes(...)
+    "mesh_render_scene_batch": (
+        "(Tensor[] vertices, Tensor[] triangles, Tensor?[] colors, Tensor?[] uvs, Tensor?[] triangle_uvs, "
+        "Tensor?[] texture, int[] view_mesh, Tensor views, int[] geometry, int[] offsets, int[] view_scene, int r_grow, "
+        "int[] occluder_offsets, Tensor(a!)? rgba, Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, "
+        "Tensor(e!)? occluder, Tensor(f!) records, Tensor(g!) workspace) -> ()"),
 }
 for _name, _schema in SCHEMAS.items():
     _DEF.define(_name + _schema)
@@ -1148,6 +1165,32 @@ def _occlusion_mask(depth, sensor, mask_in, shift, min_alpha, sensor_q, delta_q,
                                     workspace.data_ptr(), _stream(depth)), "pxt_occlusion_mask")
 
 
+def _mask_exclude(mask_in, occluder, mask, record):
+    L = _lib.lib()
+    if mask_in.dtype != torch.uint8 or mask_in.dim() != 2 or not mask_in.is_contiguous():
+        raise _lib.PxtError("mask_exclude: mask_in is a contiguous uint8 [H, W] tensor")
+    H, W = int(mask_in.shape[0]), int(mask_in.shape[1])
+    for t, name in ((occluder, "occluder"), (mask, "mask")):
+        if t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != (H, W):
+            raise _lib.PxtError(f"mask_exclude: {name} is a contiguous uint8 [{H}, {W}] tensor (got {tuple(t.shape)}, "
+                                f"{t.dtype})")
+        _lib.require_gpu(t, name)
+        if t.device != mask_in.device:
+            raise _lib.PxtError(f"mask_exclude: {name} is on {t.device}, mask_in on {mask_in.device}")
+    _lib.require_gpu(mask_in, "mask_in")
+    if H < 1 or W < 1 or H * W > 1 << 28:
+        raise _lib.PxtError(f"mask_exclude: {W} x {H} is not supported (1..2^28 pixels)")
+    if mask.data_ptr() == occluder.data_ptr():
+        raise _lib.PxtError("mask_exclude: mask may be mask_in, not occluder")
+    if record.dtype != torch.int32 or not record.is_contiguous() or record.numel() < 2 \
+            or not (record.is_cuda or record.is_pinned()):
+        raise _lib.PxtError("mask_exclude: record needs 2 contiguous int32 words in device or pinned memory")
+    if record.is_cuda and record.device != mask_in.device:
+        raise _lib.PxtError(f"mask_exclude: record is on {record.device}, mask_in on {mask_in.device}")
+    _lib.check(L.pxt_mask_exclude(mask_in.data_ptr(), occluder.data_ptr(), W, H, mask.data_ptr(), record.data_ptr(),
+                                  _stream(mask_in)), "pxt_mask_exclude")
+
+
 def _points_visible(p3d, valid_in, pose, camera, ndist, occluder, valid, record):
     L = _lib.lib()
     _f32c(p3d, "p3d")
@@ -1537,9 +1580,59 @@ def _mesh_frame_buffers(what, need, rgba, rgb_u8, depth, depth_nz):
     return outs, out_bytes
 
 
+def mesh_scene_planes(view_scene, r_grow, occluder_offsets, geometry, what="mesh_render_scene_batch"):
+    """The argument checks of mesh_render_scene_batch that need no tensor and no view floats: ``view_scene`` = the scene
+    of each of the P views (-1: none), ``occluder_offsets`` = where each view's [H, W] uint8 plane starts in the flat
+    occluder buffer (-1: none), ``geometry`` as ``mesh_frame_planes`` -> the bytes that buffer must hold."""
+    P = len(geometry) // 3
+    view_scene, offs, r_grow = [int(x) for x in view_scene], [int(x) for x in occluder_offsets], int(r_grow)
+    if len(view_scene) != P or len(offs) != P:
+        raise _lib.PxtError(f"{what}: view_scene and occluder_offsets hold one number per view ({P}; got {len(view_scene)}, "
+                            f"{len(offs)})")
+    if not (0 <= r_grow <= _lib.PXT_MESH_SCENE_MAX_GROW):
+        raise _lib.PxtError(f"{what}: r_grow is 0..{_lib.PXT_MESH_SCENE_MAX_GROW} (got {r_grow})")
+    first, spans = {}, []
+    for p, (s, off) in enumerate(zip(view_scene, offs)):
+        W, H, S = (int(x) for x in geometry[3 * p:3 * p + 3])
+        if not (-1 <= s < P):
+            raise _lib.PxtError(f"{what}: view {p} names scene {s}; a scene id is -1 (none) or 0..{P - 1}")
+        if s < 0:
+            if off >= 0:
+                raise _lib.PxtError(f"{what}: view {p} asks for an occluder plane but is in no scene")
+            continue
+        if S != 1:
+            raise _lib.PxtError(f"{what}: view {p} of scene {s} has supersample {S}; a scene's views have supersample 1")
+        q = first.setdefault(s, p)
+        if tuple(geometry[3 * q:3 * q + 2]) != tuple(geometry[3 * p:3 * p + 2]):
+            raise _lib.PxtError(f"{what}: views {q} and {p} of scene {s} differ in size: a scene is one camera")
+        if off >= 0:
+            if off % 4:
+                raise _lib.PxtError(f"{what}: view {p}'s occluder plane starts at byte {off}, not a multiple of 4")
+            spans.append((off, off + W * H, p))
+    spans.sort()
+    for (a0, a1, p), (b0, b1, q) in zip(spans, spans[1:]):
+        if b0 < a1:
+            raise _lib.PxtError(f"{what}: the occluder planes of views {p} and {q} overlap")
+    return max([e for _, e, _ in spans], default=0)
+
+
 def _mesh_render_frame_batch(vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh, views, geometry, offsets,
                              rgba, rgb_u8, depth, depth_nz, records, workspace):
-    what = "mesh_render_frame_batch"
+    _mesh_batch_call("mesh_render_frame_batch", vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh, views,
+                     geometry, offsets, rgba, rgb_u8, depth, depth_nz, records, workspace, None)
+
+
+def _mesh_render_scene_batch(vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh, views, geometry, offsets,
+                             view_scene, r_grow, occluder_offsets, rgba, rgb_u8, depth, depth_nz, occluder, records,
+                             workspace):
+    _mesh_batch_call("mesh_render_scene_batch", vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh, views,
+                     geometry, offsets, rgba, rgb_u8, depth, depth_nz, records, workspace,
+                     (view_scene, r_grow, occluder_offsets, occluder))
+
+
+def _mesh_batch_call(what, vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh, views, geometry, offsets,
+                     rgba, rgb_u8, depth, depth_nz, records, workspace, scene):
+    """The two batch ops: ``scene`` = (view_scene, r_grow, occluder_offsets, occluder) for mesh_render_scene_batch."""
     L = _lib.lib()
     M = len(vertices)
     if not all(len(x) == M for x in (triangles, colors, uvs, triangle_uvs, texture)):
@@ -1580,7 +1673,24 @@ def _mesh_render_frame_batch(vertices, triangles, colors, uvs, triangle_uvs, tex
     off = (C.c_int64 * (4 * P))(*[int(x) for x in offsets])
     cap = (C.c_int64 * 4)(*out_bytes)
     vm = (C.c_int32 * P)(*[int(x) for x in view_mesh])
-    bytes_needed = int(L.pxt_mesh_render_frame_batch_workspace_bytes(M, (C.c_int32 * M)(*counts), P, vm, geo))
+    occluder = None
+    if scene is not None:
+        view_scene, r_grow, occluder_offsets, occluder = scene
+        occ_need = mesh_scene_planes(view_scene, r_grow, occluder_offsets, geometry, what)
+        scenes = {}
+        for p, s in enumerate(view_scene):
+            q = scenes.setdefault(int(s), p)
+            if int(s) >= 0 and not torch.equal(views[p, 12:16].view(torch.int32), views[q, 12:16].view(torch.int32)):
+                raise _lib.PxtError(f"{what}: views {q} and {p} of scene {int(s)} differ in fx fy cx cy: a scene is one camera")
+        occ_have = 0 if occluder is None else occluder.numel()
+        if occluder is not None and (occluder.dtype != torch.uint8 or not occluder.is_contiguous()):
+            raise _lib.PxtError(f"{what}: occluder is a contiguous uint8 buffer (got {occluder.dtype})")
+        if occ_have < occ_need:
+            raise _lib.PxtError(f"{what}: occluder holds {occ_have} bytes, the views' planes need {occ_need}")
+        if occluder is not None:
+            named.append((occluder, "occluder"))
+    size_fn = L.pxt_mesh_render_frame_batch_workspace_bytes if scene is None else L.pxt_mesh_render_scene_batch_workspace_bytes
+    bytes_needed = int(size_fn(M, (C.c_int32 * M)(*counts), P, vm, geo))
     if bytes_needed <= 0:
         raise _lib.PxtError(f"{what}: the views {list(geometry)} are not supported")
     if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < bytes_needed:
@@ -1592,14 +1702,23 @@ def _mesh_render_frame_batch(vertices, triangles, colors, uvs, triangle_uvs, tex
         _lib.require_gpu(t, name)
         if t.device != device:
             raise _lib.PxtError(f"{what}: {name} is on {t.device}, vertices[0] on {device}")
-    _lib.check(L.pxt_mesh_render_frame_batch(
+    if scene is None:
+        _lib.check(L.pxt_mesh_render_frame_batch(
+            descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
+            _lib.dptr(depth_nz), cap, records.data_ptr(), workspace.data_ptr(), _stream(vertices[0])),
+            "pxt_mesh_render_frame_batch")
+        return
+    _lib.check(L.pxt_mesh_render_scene_batch(
         descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
-        _lib.dptr(depth_nz), cap, records.data_ptr(), workspace.data_ptr(), _stream(vertices[0])),
-        "pxt_mesh_render_frame_batch")
+        _lib.dptr(depth_nz), cap, (C.c_int32 * P)(*[int(x) for x in view_scene]), int(r_grow), _lib.dptr(occluder),
+        occ_have, (C.c_int64 * P)(*[int(x) for x in occluder_offsets]), records.data_ptr(), workspace.data_ptr(),
+        _stream(vertices[0])), "pxt_mesh_render_scene_batch")
 
 
 _IMPLS = {
     "mesh_render_frame_batch": _mesh_render_frame_batch,
+    "mesh_render_scene_batch": _mesh_render_scene_batch,
+    "mask_exclude": _mask_exclude,
     "mesh_raster": _mesh_raster,
     "mesh_render_frame": _mesh_render_frame,
     "mesh_render": _mesh_render,

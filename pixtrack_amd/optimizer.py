@@ -313,7 +313,8 @@ class PixTrackOptimizer:
             ref, levels = pr["ref"], pr["packs"]
             _lib.require_gpu(ref.p3d, "p3d")
             p3ds.append(ref.p3d.to(torch.float32).contiguous())
-            masks.append(None if ref.valid is None else ref.valid.to(dev, torch.uint8).contiguous())
+            mask = ref.valid if pr.get("mask") is None else pr["mask"]  # (a point_gate's mask: refiner._point_mask)
+            masks.append(None if mask is None else mask.to(dev, torch.uint8).contiguous())
             n_levels.append(len(levels))
             for lp in levels:
                 assert lp.fref.shape == (ref.p3d.shape[0], lp.fmap.shape[2])

@@ -19,6 +19,10 @@ methods - and only the device work of a frame step is merged:
 * trackers with a mesh template (``template=MeshTemplate(...)``) have no NeRF: the frames of a group's
   mesh trackers - each one's depth_nz plane and reference image - are drawn at the head of the step in
   ONE call (``MeshTemplate.frames``, ``pxt_mesh_render_frame_batch``).  Both kinds may share a group.
+* ``mutual_occlusion=MutualOcclusion(scenes=[...])`` (opt-in): mesh trackers that name one scene are objects in ONE
+  image.  That call then also tells, per object, the pixels where another object of its scene lies in front
+  (``pxt_mesh_render_scene_batch``); they leave the object's query mask, and the reference points that project onto them
+  leave its LM's point mask.
 
 A tracker in cold start (image scales [4, 1]: two dependent refinements) runs that frame by itself
 through ``run_single_frame``; everything else is lock-step.  Per object the results are those of the
@@ -29,6 +33,7 @@ workgroups per problem) equal up to fp32 summation order.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import os
@@ -40,6 +45,26 @@ from ..optimizer import PixTrackOptimizer
 from ..tracker import DebugTracker
 from ..point_report import parse_mode
 from .pixloc_tracker_r9 import PixLocPoseTrackerR9
+
+
+@dataclass
+class MutualOcclusion:
+    """The lock-step option: ``scenes[k]`` = the scene of tracker k (any hashable; None: the tracker is alone).  The
+    trackers of a scene see ONE image: same query camera (size, f, c; no lens terms), mesh templates.  ``r_grow``: the box
+    radius by which the plane of hidden pixels is grown before it leaves the mask and gates the points (0..8).  The
+    default 2 is an untuned starting value: nobody has run this on real multi-object sequences."""
+    scenes: Sequence
+    r_grow: int = 2
+
+
+MUTUAL_HISTORY_KEYS = ("mutual_occlusion_applied", "n_mutually_hidden_pixels", "mutually_hidden_fraction",
+                       "n_mutual_occluder_pixels", "n_points_gated_mutual")
+
+
+def _same_scene_camera(a, b) -> bool:
+    """Two query cameras see one image: equal size, f and c, no lens terms."""
+    da, db = (c._data.detach().cpu().double().reshape(-1) for c in (a, b))
+    return bool(torch.equal(da[:6], db[:6]) and not da[6:].any() and not db[6:].any())
 
 
 class _Group:
@@ -59,8 +84,16 @@ class _Group:
 class MultiObjectTracker:
     def __init__(self, trackers: Sequence[PixLocPoseTrackerR9], lm_workgroups: int = 0, per_image_plan: bool = False,
                  max_unet_batch: int = _lib.PXT_UNET_MAX_BATCH, n_groups: int = 1, batch_renders: Optional[bool] = None,
-                 uncertainty: Optional[bool] = None, point_report=None):
-        """``uncertainty``: None keeps each tracker's own setting, True / False sets it for all of them (the ``uncertainty``
+                 uncertainty: Optional[bool] = None, point_report=None, mutual_occlusion: Optional[MutualOcclusion] = None):
+        """``mutual_occlusion``: None (default) changes nothing - the same op, the same launches, the same poses and
+        histories.  A ``MutualOcclusion`` assigns the mesh-template trackers to scenes.  Per step, the members of a scene
+        that take the lock-step path are drawn as that scene (if there are at least two of them); a member that sits
+        the step out or goes through ``run_single_frame`` (cold start, the frame after a failed frame, multiscale) is not
+        part of the scene that step: it neither hides anything nor is hidden.  Each history entry gains
+        ``MUTUAL_HISTORY_KEYS``.  ValueError: a scene with a tracker that has no mesh template; query cameras of a scene
+        that differ in size, f or c or have lens terms (checked here where a tracker already has its camera, else at the
+        first step that draws the scene); a scene that cannot be kept in one group.
+        ``uncertainty``: None keeps each tracker's own setting, True / False sets it for all of them (the ``uncertainty``
         option of PixLocPoseTrackerR9): the information problems of a group's step then go out as ONE pxt_lm_information
         launch behind its batched LM launch and its queued renders.
         ``point_report``: None keeps each tracker's own setting; False / "off", "summary" or "full" sets it for all of
@@ -99,6 +132,10 @@ class MultiObjectTracker:
                 if not isinstance(template, MeshTemplate):
                     raise ValueError("lock-step tracking takes a mesh template that is a mesh_template.MeshTemplate "
                                      f"(got {template!r})")
+        self.mutual_occlusion = mutual_occlusion
+        self._scene_of: List = [None] * len(self.trackers)
+        if mutual_occlusion is not None:
+            self._scene_of = self._checked_scenes(mutual_occlusion)  # (ValueError before anything is touched)
         # one UNet context runs every image of a group's step: the trackers must hold the same checkpoint in the same
         # precision (pixloc_megadepth is one network for all objects; reference pixloc_pose_refiners.py:49-60; the
         # signature names the precision)
@@ -112,6 +149,9 @@ class MultiObjectTracker:
         if point_report is not None:
             for tr in self.trackers:
                 tr.point_report = tr.localizer.refiner.point_report = point_report
+        for k, s in enumerate(self._scene_of):
+            if s is not None:
+                self.trackers[k].enable_mutual_occlusion()  # (its frames may now come with an occluder plane)
         self.groups: List[_Group] = []
         # a group's queued renders as ONE chain of launches carrying the rays of all its objects (pxt_ngp_render_frame_batch;
         # bit for bit the single renders); PXT_BATCH_RENDERS=0: one chain per object, one after the other
@@ -125,20 +165,78 @@ class MultiObjectTracker:
         self.lockstep_frames = 0
         self.timing = None         # set to {} to collect HIP-event pairs per phase (bench.py's untimed diagnostic pass)
 
+    def _checked_scenes(self, option: MutualOcclusion) -> list:
+        """The option's scene of every tracker, checked (ValueError); nothing is touched."""
+        from ..mesh_render import BATCH_MAX_MESHES, SCENE_MAX_GROW
+        from ..mesh_template import MeshTemplate
+
+        scenes = list(option.scenes)
+        if len(scenes) != len(self.trackers):
+            raise ValueError(f"mutual_occlusion.scenes names one scene (or None) per tracker ({len(self.trackers)}; got "
+                             f"{len(scenes)})")
+        if int(option.r_grow) != option.r_grow or not (0 <= int(option.r_grow) <= SCENE_MAX_GROW):
+            raise ValueError(f"mutual_occlusion.r_grow is an integer in 0..{SCENE_MAX_GROW} (got {option.r_grow})")
+        members: dict = {}
+        for k, s in enumerate(scenes):
+            if s is not None:
+                members.setdefault(s, []).append(k)
+        for s, ks in members.items():
+            for k in ks:
+                if not isinstance(getattr(self.trackers[k], "template", None), MeshTemplate):
+                    raise ValueError(f"mutual occlusion: tracker {k} of scene {s!r} has no mesh template; a scene's trackers "
+                                     "are all mesh-template trackers (NeRF-template trackers are not part of a scene yet)")
+            if len(ks) > BATCH_MAX_MESHES:
+                raise ValueError(f"mutual occlusion: scene {s!r} has {len(ks)} trackers; a scene is drawn in one call of "
+                                 f"at most {BATCH_MAX_MESHES} meshes")
+            self._check_scene_cameras(s, ks)
+        return scenes
+
+    def _check_scene_cameras(self, scene, ks) -> None:
+        """The trackers ``ks`` of ``scene`` that have a camera (it comes with a tracker's first frame) see one image."""
+        cams = [(k, self.trackers[k].camera) for k in ks if getattr(self.trackers[k], "camera", None) is not None]
+        for k, cam in cams[1:]:
+            if not _same_scene_camera(cams[0][1], cam):
+                raise ValueError(f"mutual occlusion: trackers {cams[0][0]} and {k} of scene {scene!r} have different query "
+                                 "cameras (size, f, c; no lens terms): a scene is one image")
+        if len(cams) == 1 and not _same_scene_camera(cams[0][1], cams[0][1]):
+            raise ValueError(f"mutual occlusion: tracker {cams[0][0]} of scene {scene!r} has a query camera with lens terms")
+
+    def _check_scene_groups(self) -> None:
+        """Every scene's trackers sit in one group: a scene is drawn in one call on one stream."""
+        group_of = {k: g.index for g in self.groups for k in g.members}
+        seen: dict = {}
+        for k, s in enumerate(self._scene_of):
+            if s is not None and seen.setdefault(s, group_of[k]) != group_of[k]:
+                raise ValueError(f"mutual occlusion: the trackers of scene {s!r} have been placed in different groups "
+                                 f"({seen[s]} and {group_of[k]}); a scene stays in one group")
+
     def set_groups(self, n_groups: int) -> None:
-        """(Re)deals the trackers to ``n_groups`` groups, tracker k to group k mod n_groups.  Synchronises the device: a
-        tracker's tensors of the last step were produced on its old group's stream."""
+        """(Re)deals the trackers to ``n_groups`` groups, tracker k to group k mod n_groups - with ``mutual_occlusion`` a
+        scene stays together: its trackers follow its first one (ValueError if a group would then hold more trackers
+        than one batched LM launch takes).  Synchronises the device: a tracker's tensors of the last step were produced
+        on its old group's stream."""
         n_groups = max(1, min(int(n_groups), len(self.trackers)))
         if any(g.pend for g in self.groups):
             raise _lib.PxtError("set_groups between steps only")
         torch.cuda.synchronize(self.device)
+        dealt = [k % n_groups for k in range(len(self.trackers))]
+        first: dict = {}
+        for k, s in enumerate(self._scene_of):
+            if s is not None:
+                dealt[k] = first.setdefault(s, dealt[k])
+        if first and max(dealt.count(g) for g in range(n_groups)) > _lib.PXT_LM_MAX_BATCH:
+            raise ValueError(f"mutual occlusion: keeping every scene in one of {n_groups} groups puts more than "
+                             f"{_lib.PXT_LM_MAX_BATCH} trackers into a group")
         self.groups = []
         for g in range(n_groups):
-            members = list(range(g, len(self.trackers), n_groups))
+            members = [k for k in range(len(self.trackers)) if dealt[k] == g]
+            if not members:  # (scenes kept together may leave a group empty)
+                continue
             stream = None if n_groups == 1 else _group_stream(self.device, g)
             self.groups.append(_Group(g, members, stream, self.trackers[members[0]].localizer.extractor.model))
         self.model = self.groups[0].model
         self._last_unet_done = None
+        self._check_scene_groups()
 
     # ------------------------------------------------------------------ helpers
     def _lm_batch_ws(self, grp: _Group) -> torch.Tensor:
@@ -326,10 +424,32 @@ class MultiObjectTracker:
 
         if grp.mesh_ws is None:
             grp.mesh_ws = FrameBatchWorkspace()
-        planes = MeshTemplate.frames([tr.template for tr in part], [tr.pose for tr in part], [tr.camera for tr in part],
-                                     [tr._reference_camera() for tr in part], workspace=grp.mesh_ws)
-        for tr, (nz, ref_u8) in zip(part, planes):
-            tr._primed_frame = (tr.pose, nz, ref_u8)
+        scenes = self._step_scenes(grp, frames) if self.mutual_occlusion is not None else None
+        views = ([tr.template for tr in part], [tr.pose for tr in part], [tr.camera for tr in part],
+                 [tr._reference_camera() for tr in part])
+        if scenes is None:  # (also: no scene has two members in this step - the call is the one made without the option)
+            for tr, (nz, ref_u8) in zip(part, MeshTemplate.frames(*views, workspace=grp.mesh_ws)):
+                tr._primed_frame = (tr.pose, nz, ref_u8)
+            return
+        planes = MeshTemplate.frames(*views, workspace=grp.mesh_ws, scenes=scenes, r_grow=int(self.mutual_occlusion.r_grow),
+                                     records=True)
+        for tr, (nz, ref_u8, occluder, record) in zip(part, planes):
+            tr._primed_frame = (tr.pose, nz, ref_u8, None if occluder is None else (occluder, record))
+
+    def _step_scenes(self, grp: _Group, frames):
+        """The scene of each of the group's mesh trackers that take the lock-step path this step (the order of
+        _prime_mesh_frames' ``part``), None where the tracker is alone: a scene counts only with two members in the
+        step.  None: no scene is drawn this step."""
+        ks = [k for k in grp.members
+              if self.trackers[k].template is not None and self._takes_lockstep(self.trackers[k], frames[k])]
+        ids = [self._scene_of[k] for k in ks]
+        scenes = [s if s is not None and ids.count(s) >= 2 else None for s in ids]
+        if all(s is None for s in scenes):
+            return None
+        for s in {s for s in scenes if s is not None}:
+            self._check_scene_cameras(s, [k for k, t in zip(ks, scenes) if t == s])
+        index = {s: i for i, s in enumerate(dict.fromkeys(s for s in scenes if s is not None))}
+        return [None if s is None else index[s] for s in scenes]
 
     def _batched_renders_ahead(self, grp: _Group) -> set:
         """The group's queued renders (behind the batched LM launch, cameras from its epilogue's slots) in one batched
@@ -452,6 +572,11 @@ def build_parser():
                     help="samples per pixel and axis of each mesh template's reference image (default 2, untuned)")
     ap.add_argument("--reference_sfm", type=Path, nargs="+", default=None,
                     help="each object's SfM model directory (the ref/ directory mesh_dataset wrote)")
+    ap.add_argument("--mutual_occlusion", action="store_true",
+                    help="--template mesh: objects whose --query paths are equal share an image; the pixels where another of "
+                         "them lies in front leave an object's mask and gate its points")
+    ap.add_argument("--mutual_occlusion_grow", type=int, default=2,
+                    help="box radius by which the hidden pixels are grown, 0..8 (default 2, untuned)")
     return ap
 
 
@@ -462,6 +587,17 @@ def _per_object(values, k: int, K: int, flag: str):
     if len(values) not in (1, K):
         raise ValueError(f"{flag} takes one entry per object or one entry for all (got {len(values)} for {K} objects)")
     return values[k if len(values) == K else 0]
+
+
+def mutual_occlusion_from_args(args) -> Optional[MutualOcclusion]:
+    """--mutual_occlusion [--mutual_occlusion_grow R] -> the option (None when off): the objects whose --query paths are
+    equal share a scene; an object whose query path is its own is in none."""
+    if not getattr(args, "mutual_occlusion", False):
+        return None
+    if args.template != "mesh":
+        raise ValueError("--mutual_occlusion goes with --template mesh")
+    paths = [os.path.normpath(str(q)) for q in args.query]
+    return MutualOcclusion(scenes=[p if paths.count(p) >= 2 else None for p in paths], r_grow=args.mutual_occlusion_grow)
 
 
 def main(argv=None):
@@ -515,7 +651,11 @@ def main(argv=None):
                                             eval_path=str(args.out_dir[k]), loc_path=str(obj / "pixtrack/aug_nerf_sfm"),
                                             debug=args.debug, unet_precision=args.unet_precision,
                                             uncertainty=args.uncertainty, point_report=args.point_report))
-    multi = MultiObjectTracker(trackers, n_groups=args.groups)
+    try:
+        mutual = mutual_occlusion_from_args(args)
+    except ValueError as e:
+        ap.error(str(e))
+    multi = MultiObjectTracker(trackers, n_groups=args.groups, mutual_occlusion=mutual)
     its = [tr.get_query_frame_iterator(q, args.frames if args.frames is not None else np.inf)
            for tr, q in zip(trackers, args.query)]
     gc.collect()

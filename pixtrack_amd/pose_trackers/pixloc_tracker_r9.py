@@ -99,6 +99,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         frame without a mask (cold start, after a failed frame) or without a sensor image runs as without the option.
         The history entry gains ``occluded_fraction``, ``n_occluder_pixels``, ``n_points_gated`` and
         ``occlusion_applied`` (None / 0 / 0 / False where no pass ran); ``last_occlusion`` keeps the frame's tensors.
+        The option still refuses a mesh template; the objects of one image that hide each other are lock-step
+        tracking's ``mutual_occlusion`` (multi_object_tracker.py), which feeds the same mask fold and point gate.
         The cost gate, success and ``tracked`` are decided as ever.  ``render_ahead`` stays on: the render queued
         behind the LM launch keeps its float Depth image, and the pass runs in get_mask of the frame that consumes it.
         Shares the frame's one sensor upload with ``depth_refine`` (the two options must then name the same lookup and
@@ -253,6 +255,11 @@ class PixLocPoseTrackerR9(PoseTracker):
             self._occ_record = torch.zeros(OCC_RECORD, dtype=torch.int32).pin_memory()
             self._occ_done = torch.cuda.Event()
             self.localizer.refiner.point_gate = self._gate_points
+        # Mutual occlusion between the tracked objects of one image (lock-step tracking of mesh templates:
+        # MultiObjectTracker(mutual_occlusion=...) calls enable_mutual_occlusion).  Off: nothing below is touched.
+        self.mutual_occlusion = False
+        self.last_mutual_occlusion = None  # the tensors and figures of the last frame's pass (None: none ran)
+        self._mut_frame = self._mut_record = self._mut_scene = self._mut_done = None
 
     # ------------------------------------------------------------------ per-variant set-up
     supports_render_points = True  # (the YCB policy does not yet)
@@ -347,6 +354,38 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._depth_sensor = self._depth_dev
         self.sensor_uploads += 1
 
+    def enable_mutual_occlusion(self):
+        """Lock-step tracking draws this tracker's frames as part of a scene (multi_object_tracker.MutualOcclusion): a
+        primed frame then carries the plane G of the pixels where another tracked mesh lies in front, which leaves the
+        frame's mask (pxt_mask_exclude) and gates the LM's points (pxt_points_visible) as the sensor option's plane
+        does.  A mesh template only: the plane comes out of the mesh frames' key planes."""
+        from ..occlusion import RECORD as OCC_RECORD
+
+        if self.template is None:
+            raise ValueError("mutual occlusion needs a mesh template (the occluder plane is made from the mesh frames' "
+                             "depth keys); NeRF-template trackers are not part of a scene yet")
+        self.mutual_occlusion = True
+        # words 0, 1: pxt_mask_exclude's; 8..10: pxt_points_visible's (the sensor option's record layout)
+        self._mut_record = torch.zeros(OCC_RECORD, dtype=torch.int32).pin_memory()
+        self._mut_scene = torch.zeros(16, dtype=torch.int32).pin_memory()  # the query view's render record
+        self._mut_done = torch.cuda.Event()
+        self.localizer.refiner.point_gate = self._gate_points
+
+    def _apply_mutual_occlusion(self, mask, mutual):
+        """_mask_and_reference's tail on a primed frame that was drawn as part of a scene: ``mutual`` = (G uint8 [H, W],
+        the query view's render record on the device).  One launch on the frame's stream and one copy into pinned
+        memory, nothing awaited; the records are read in _frame_policy."""
+        from ..occlusion import mask_exclude
+
+        occluder, scene_record = mutual
+        self._mut_record.zero_()  # (the last frame's were read in its _frame_policy)
+        mask_exclude(mask, occluder, mask=mask, record=self._mut_record)
+        self._mut_scene.copy_(scene_record, non_blocking=True)
+        self._mut_frame = {"occluder": occluder, "mask": mask, "gates": [], "record_buffer": self._mut_record,
+                           "done": self._mut_done}
+        self._mut_done.record(torch.cuda.current_stream(self.device))
+        return mask
+
     def _apply_occlusion(self, mask, depth):
         """get_mask's tail with the option on: the frame's plain mask minus the pixels where the sensor image - staged
         before the frame's first launch - lies in front of the mask view's Depth render.  Two launches on the frame's
@@ -372,22 +411,29 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._occ_frame = {"depth": depth, "sensor": sensor, "mask_in": mask, "mask": out["mask"],
                            "occluder": out["occluder"], "shift": (sx, sy), "min_alpha": conf.min_alpha,
                            "sensor_q": self._occ_q[0], "delta_q": self._occ_q[1], "radii": (conf.r_open, conf.r_grow),
-                           "gates": []}
+                           "gates": [], "record_buffer": self._occ_record, "done": self._occ_done}
         self._occ_done.record(torch.cuda.current_stream(self.device))
         return out["mask"]
 
     def _gate_points(self, ref, T_init, qcamera):
         """The refiner's point_gate: the LM's point mask of a frame whose occlusion pass ran - ref.valid minus the
         points whose projection at the start pose falls on the occluder plane (one launch, ahead of the LM's).  None:
-        no pass ran this frame, the LM takes ref.valid."""
-        frame = self._occ_frame
-        if frame is None:
-            return None
+        no pass ran this frame, the LM takes ref.valid.  The plane is the sensor option's (_apply_occlusion) or the
+        other tracked meshes' (_apply_mutual_occlusion); each pass has its own record and event."""
+        valid = None
+        for frame in (self._occ_frame, self._mut_frame):
+            if frame is not None:
+                valid = self._gate_on_plane(frame, ref, ref.valid if valid is None else valid, T_init, qcamera)
+        return valid
+
+    def _gate_on_plane(self, frame, ref, valid_in, T_init, qcamera):
+        """What the two occluder sources share: one pxt_points_visible launch on the frame's plane G, counted in the
+        frame's own record, remembered in its ``gates``."""
         from ..occlusion import points_visible
 
-        valid, _ = points_visible(ref.p3d, ref.valid, T_init, qcamera, frame["occluder"], record=self._occ_record)
-        frame["gates"].append({"p3d": ref.p3d, "valid_in": ref.valid, "valid": valid, "T_init": T_init, "camera": qcamera})
-        self._occ_done.record(torch.cuda.current_stream(self.device))
+        valid, _ = points_visible(ref.p3d, valid_in, T_init, qcamera, frame["occluder"], record=frame["record_buffer"])
+        frame["gates"].append({"p3d": ref.p3d, "valid_in": valid_in, "valid": valid, "T_init": T_init, "camera": qcamera})
+        frame["done"].record(torch.cuda.current_stream(self.device))
         return valid
 
     def _enqueue_depth_refine(self, prob, pending, qcamera):
@@ -670,12 +716,16 @@ class PixLocPoseTrackerR9(PoseTracker):
         ``MeshTemplate.frame`` call instead; everything after them is the same."""
         if self.template is not None:
             primed, self._primed_frame = self._primed_frame, None
+            mutual = None
             if primed is not None and pose is not None and primed[0] is pose:  # drawn with the other objects' frames
                 nz, ref_u8 = primed[1], primed[2]
+                mutual = primed[3] if len(primed) > 3 else None  # ... as part of a scene (mutual occlusion)
                 self.template_frames_batched += 1
             else:
                 nz, ref_u8 = self.template.frame(pose, self.camera, self._reference_camera())
             mask = self._mask_of(nz)
+            if mutual is not None:
+                mask = self._apply_mutual_occlusion(mask, mutual)
             self._last_depth = None
             self._fused_reference, self._fused_depth = (pose, ref_u8), None
             return mask, ref_u8
@@ -778,7 +828,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         query_path, query_image = query
         refiner = self.localizer.refiner
         self._depth_frame_name = query_path
-        self._occ_frame = None
+        self._occ_frame = self._mut_frame = None
         if self.depth_refine is not None or self.occlusion is not None:
             self._stage_depth_sensor(query_path)
         self._frame_setup(query)
@@ -916,6 +966,22 @@ class PixLocPoseTrackerR9(PoseTracker):
             if frame is not None:
                 frame["record"] = rec
             self.last_occlusion = frame
+        if self.mutual_occlusion:  # (added keys only where the option is on; nothing above read them)
+            # the pinned records: their launches sit ahead of the LM launch whose result is here (the sensor option's
+            # pattern: the event is over by then)
+            frame, self._mut_frame = self._mut_frame, None
+            rec = scene = None
+            if frame is not None:
+                self._mut_done.synchronize()
+                rec = [int(x) for x in self._mut_record.tolist()]
+                scene = [int(x) for x in self._mut_scene.tolist()]
+                frame["record"], frame["scene_record"] = rec, scene
+            ret["mutual_occlusion_applied"] = frame is not None
+            ret["n_mutually_hidden_pixels"] = 0 if scene is None else scene[10]
+            ret["mutually_hidden_fraction"] = None if scene is None else (scene[10] / scene[0] if scene[0] else 0.0)
+            ret["n_mutual_occluder_pixels"] = 0 if scene is None else scene[11]
+            ret["n_points_gated_mutual"] = 0 if rec is None else rec[9] - rec[10]
+            self.last_mutual_occlusion = frame
         if success:
             self.pose = self._accepted_pose = ret["T_refined"]
         self.success = success

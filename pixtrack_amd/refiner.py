@@ -768,6 +768,9 @@ class PoseTrackerRefiner:
         plan = self.conf.level_plan
         levels = None if not plan else plan.get(image_scale, plan.get(str(image_scale)))
         prob = self.lm_problem(maps_q, scales_q, qcamera, pose_init, ref, levels)
+        gated = self.point_gate(ref, pose_init, qcamera) if self.point_gate is not None else None
+        if gated is not None:
+            prob["mask"] = gated  # (the batched launch and the problems queued behind it read it: _point_mask)
         prob["dbids"], prob["qname"] = dbids, qname
         return "lm", prob
 
