@@ -780,6 +780,44 @@ int pxt_points_from_depth(const float* depth, int32_t width, int32_t height, con
                           uint8_t* slot_valid, int32_t* record, void* workspace, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Reference points from the depth planes of a mesh template's frame call (opt-in; csrc/pxt_points.hip).
+ *
+ * pxt_points_from_depth for the planes the mesh rasteriser writes (pxt_mesh_render_frame's `depth` output: a covered
+ * pixel holds z * depth_q in channel 0 and 1.0 in channel 3, background four zeros), up to PXT_POINTS_MAX_VIEWS views of
+ * different sizes in ONE chain of three launches - the points of all the mesh objects a lock-step step tracks.
+ *   depth: host array of n_views device pointers, view k's plane [H_k][W_k][4] float32 (16-byte aligned each);
+ *   sizes [n_views][2] int32 (host): W_k, H_k, each 1..16384;
+ *   views [n_views][PXT_MESH_VIEW] float32 (host): the 20 floats the frame call drew the plane with - [0..8] R row-major,
+ *       [9..11] t (world -> camera), [12..15] fx fy cx cy, [16] near, [17] depth_q.  All finite, fx, fy, depth_q > 0.
+ *   selection, per view, exactly pxt_points_from_depth's: base test of a pixel .w >= min_alpha && .x > 0; ACCEPTED: the
+ *       base test holds on the whole (2 erode + 1)^2 square around it (erode 0..2; a square that leaves the image
+ *       fails); stride s: the smallest integer >= 1 with s * s * n_max >= A, A = the view's accepted pixels; candidates:
+ *       accepted pixels with x % s == s / 2 && y % s == s / 2; points: the first n_max candidates in row-major order.
+ *   point of pixel (x, y), the mesh rasteriser's pixel rule (pixel centres at integer coordinates), every step a single
+ *       fp32 operation (no contraction, IEEE division):
+ *           z = d.x / depth_q;   xn = ((float) x - cx) / fx, yn = ((float) y - cy) / fy;
+ *           c = (z * xn, z * yn, z);   q_k = c_k - t_k;   p_j = (R_0j q_0 + R_1j q_1) + R_2j q_2   (R^T q: object frame)
+ *       mesh_render.points_reference restates selection and arithmetic in numpy; the two agree bit for bit.
+ *   p3d [n_views][n_max][3], slot_valid [n_views][n_max]: view k's slots >= n_points get slot_valid 0 and the camera
+ *       centre (the last line with q = -t), which pxt_sample_sparse rejects at the frame's pose.
+ *   records [n_views][4] int32 (device or pinned host) = {A, s, n_points, n_candidates} per view.
+ *   A view's p3d, slot_valid and record are a pure function of its plane, its 20 floats and (min_alpha, erode, n_max):
+ *       they do not depend on n_views, on the view's index or on the other views; no atomics, slots in row-major order.
+ *   workspace: device memory of pxt_points_from_depth_views_workspace_bytes(n_views, sizes) bytes (< 0: a count or size
+ *       out of range), 16-byte aligned, untouched until the launches have finished; one workspace serves one call at a
+ *       time.  The view table travels in the kernel arguments: three launches on `stream`, no upload, no host
+ *       synchronisation, no allocation.
+ * Bounds: 1 <= n_views <= PXT_POINTS_MAX_VIEWS, erode 0..2, 1 <= n_max <= 2^24, no NULL, p3d, slot_valid and records
+ *   4-byte aligned; anything else is PXT_E_ARG and nothing is launched or written.
+ * Measured on the MI355X: DESIGN.md 3.21.
+ * ---------------------------------------------------------------------- */
+#define PXT_POINTS_MAX_VIEWS 16
+int64_t pxt_points_from_depth_views_workspace_bytes(int32_t n_views, const int32_t* sizes);
+int pxt_points_from_depth_views(const float* const* depth, const int32_t* sizes, const float* views, int32_t n_views,
+                                float min_alpha, int32_t erode, int32_t n_max, float* p3d, uint8_t* slot_valid,
+                                int32_t* records, void* workspace, void* stream);
+
+/* -------------------------------------------------------------------------
  * Pose-error evaluation (opt-in; csrc/pxt_eval.hip).
  *
  * Replaces, for a whole run in one call, the per-frame Python loop of the reference's notebooks/GetMetrics.ipynb

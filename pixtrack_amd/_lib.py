@@ -52,6 +52,7 @@ PXT_MESH_FRAME_MAX_VIEWS = 8
 PXT_MESH_BATCH_MAX_MESHES = 16
 PXT_MESH_BATCH_MAX_VIEWS = 32
 PXT_MESH_SCENE_MAX_GROW = 8
+PXT_POINTS_MAX_VIEWS = 16
 
 
 class PxtError(RuntimeError):
@@ -366,6 +367,9 @@ PROTOTYPES = {
     "pxt_points_from_depth_workspace_bytes": (_I64, [_I32, _I32]),
     "pxt_points_from_depth": (C.c_int, [_VP, _I32, _I32, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, _I32, _I32,
                                         _VP, _VP, _VP, _VP, _VP]),
+    "pxt_points_from_depth_views_workspace_bytes": (_I64, [_I32, C.POINTER(_I32)]),
+    "pxt_points_from_depth_views": (C.c_int, [C.POINTER(_VP), C.POINTER(_I32), C.POINTER(C.c_float), _I32, C.c_float, _I32,
+                                              _I32, _VP, _VP, _VP, _VP, _VP]),
     "pxt_pose_errors_workspace_bytes": (_I64, [_I32, _I32]),
     "pxt_pose_errors": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _VP, _VP]),
     "pxt_depth_agreement_workspace_bytes": (_I64, [_I32, _I32, _I32]),

@@ -15,6 +15,8 @@
 //            atomic decides an index, so the output is a pure function of the input.
 #include "pxt_common.h"
 
+#include <cmath>
+
 namespace pxt {
 
 constexpr int kPtsSeg = 1024;             // pixels per workgroup: 256 lanes x 4 trips
@@ -219,6 +221,258 @@ extern "C" int pxt_points_from_depth(const float* depth, int32_t width, int32_t 
   hipLaunchKernelGGL(points_accept_kernel, dim3(a.nseg), dim3(256), 0, s, a);
   hipLaunchKernelGGL(points_stride_kernel, dim3(a.nseg), dim3(256), 0, s, a);
   hipLaunchKernelGGL(points_compact_kernel, dim3(a.nseg), dim3(256), 0, s, a, pj, p3d, slot_valid, (int*)record);
+  PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same selection for up to PXT_POINTS_MAX_VIEWS depth planes of a mesh template's frame call in ONE chain of three
+// launches (pxt_points_from_depth_views).  The grid is the concatenation of the views' 1024-pixel segments; a workgroup
+// finds its view in the per-view first-segment table (uniform per workgroup), the stride pass sums and the compact pass
+// prefixes over its own view's segments only.  The back-projection follows the mesh rasteriser's pixel rule (pixel
+// centres at integer coordinates, fx fy cx cy) in single fp32 operations, so that mesh_render.points_reference restates
+// it bit for bit.  The view table travels in the kernel arguments: no upload, no staging block.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace pxt {
+
+struct PtvView {
+  float f[PXT_MESH_VIEW];  // R row-major, t, fx fy cx cy, near, depth_q, 0 0: what the frame call drew the plane with
+  const float4* depth;     // [H][W]: .x = z * depth_q, .w = 1 on a covered pixel
+  int W, H, npix;
+  int seg0;  // the view's first segment in the grid
+};
+
+struct PtvArgs {
+  PtvView v[PXT_POINTS_MAX_VIEWS];
+  int n_views, nseg, erode, n_max;  // nseg: all views' segments
+  float min_alpha;
+  int* head;                 // [PXT_POINTS_MAX_VIEWS][2]: A, s per view
+  int* seg_accepted;         // [nseg]
+  int* seg_candidates;       // [nseg]
+  unsigned long long* bits;  // [nseg * kPtsWords]
+};
+
+// The workgroup's view: the last one whose first segment is not behind blockIdx.x (every view has a segment).
+__device__ __forceinline__ int ptv_view_of(const PtvArgs& a) {
+  int v = 0;
+  for (int k = 1; k < a.n_views; ++k)
+    if ((int)blockIdx.x >= a.v[k].seg0) v = k;
+  return v;
+}
+
+__device__ __forceinline__ int ptv_segments(const PtvArgs& a, int v) { return (a.v[v].npix + kPtsSeg - 1) / kPtsSeg; }
+
+// pts_candidate_word for the segment `lb` of a view of width W (the bits of pixels >= npix are 0).
+__device__ __forceinline__ unsigned long long ptv_candidate_word(const PtvArgs& a, int W, int lb, int s, int j, int& x, int& y) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lb * kPtsSeg + j * 256 + threadIdx.x;
+  const unsigned long long w = a.bits[(size_t)blockIdx.x * kPtsWords + j * 4 + wave];
+  y = i / W;
+  x = i - y * W;
+  const bool cand = ((w >> lane) & 1ull) != 0ull && (x % s) == s / 2 && (y % s) == s / 2;
+  return __ballot(cand);
+}
+
+// R^T q in the order the header states: p_j = (R_0j q_0 + R_1j q_1) + R_2j q_2, every step one fp32 operation.
+__device__ __forceinline__ void ptv_to_object(const float* f, float q0, float q1, float q2, float* p) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) p[j] = (f[j] * q0 + f[3 + j] * q1) + f[6 + j] * q2;
+}
+
+__device__ __forceinline__ void ptv_back_project(const float* f, float d, int x, int y, float* p) {
+#pragma clang fp contract(off)
+  const float z = d / f[17];
+  const float xn = ((float)x - f[14]) / f[12];
+  const float yn = ((float)y - f[15]) / f[13];
+  const float c0 = z * xn, c1 = z * yn;
+  ptv_to_object(f, c0 - f[9], c1 - f[10], z - f[11], p);
+}
+
+__global__ __launch_bounds__(256) void points_views_accept_kernel(const PtvArgs a) {
+  __shared__ int s_cnt[kPtsWords];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int v = ptv_view_of(a);
+  const float4* __restrict__ depth = a.v[v].depth;
+  const int W = a.v[v].W, H = a.v[v].H, npix = a.v[v].npix, lb = blockIdx.x - a.v[v].seg0;
+  const int e = a.erode;
+#pragma unroll
+  for (int j = 0; j < kPtsTrips; ++j) {
+    const int i = lb * kPtsSeg + j * 256 + threadIdx.x;
+    bool ok = false;
+    if (i < npix) {
+      ok = pts_base_test(depth[i], a.min_alpha);
+      const int y = i / W, x = i - y * W;
+      // the (2e + 1)^2 square: one that leaves the image fails; every pixel of it passes the base test
+      if (ok && e > 0 && (x < e || y < e || x + e >= W || y + e >= H)) ok = false;
+      if (ok && e > 0) {
+        for (int dy = -e; dy <= e; ++dy)
+          for (int dx = -e; dx <= e; ++dx)
+            if ((dx != 0 || dy != 0) && ok) ok = pts_base_test(depth[i + dy * W + dx], a.min_alpha);
+      }
+    }
+    const unsigned long long m = __ballot(ok);
+    if (lane == 0) {
+      a.bits[(size_t)blockIdx.x * kPtsWords + j * 4 + wave] = m;
+      s_cnt[j * 4 + wave] = __popcll(m);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0;
+    for (int k = 0; k < kPtsWords; ++k) c += s_cnt[k];
+    a.seg_accepted[blockIdx.x] = c;
+  }
+}
+
+__global__ __launch_bounds__(256) void points_views_stride_kernel(const PtvArgs a) {
+  __shared__ int s4[4];
+  const int v = ptv_view_of(a);
+  const int seg0 = a.v[v].seg0, nseg = ptv_segments(a, v), lb = blockIdx.x - seg0;
+  int part = 0;
+  for (int b = threadIdx.x; b < nseg; b += 256) part += a.seg_accepted[seg0 + b];
+  const int A = pts_block_sum(part, s4);
+  const int s = pts_stride(A, a.n_max);
+  int c = 0, x, y;
+#pragma unroll
+  for (int j = 0; j < kPtsTrips; ++j) c += __popcll(ptv_candidate_word(a, a.v[v].W, lb, s, j, x, y));
+  c = pts_block_sum((threadIdx.x & 63) == 0 ? c : 0, s4);
+  if (threadIdx.x == 0) {
+    a.seg_candidates[blockIdx.x] = c;
+    if (lb == 0) {
+      a.head[2 * v] = A;
+      a.head[2 * v + 1] = s;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void points_views_compact_kernel(const PtvArgs a, float* __restrict__ p3d_all,
+                                                                   uint8_t* __restrict__ valid_all, int* __restrict__ records) {
+  __shared__ int s4[4];
+  __shared__ int s_cnt[kPtsWords];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int v = ptv_view_of(a);
+  const int seg0 = a.v[v].seg0, nseg = ptv_segments(a, v), lb = blockIdx.x - seg0;
+  float f[PXT_MESH_VIEW];
+#pragma unroll
+  for (int k = 0; k < 18; ++k) f[k] = a.v[v].f[k];
+  const float4* __restrict__ depth = a.v[v].depth;
+  float* __restrict__ p3d = p3d_all + (size_t)v * a.n_max * 3;
+  uint8_t* __restrict__ slot_valid = valid_all + (size_t)v * a.n_max;
+  const int A = a.head[2 * v], s = a.head[2 * v + 1];
+  int before = 0, all = 0;
+  for (int b = threadIdx.x; b < nseg; b += 256) {
+    const int c = a.seg_candidates[seg0 + b];
+    all += c;
+    if (b < lb) before += c;
+  }
+  before = pts_block_sum(before, s4);
+  all = pts_block_sum(all, s4);
+  unsigned long long m[kPtsTrips];
+  int xs[kPtsTrips], ys[kPtsTrips];
+#pragma unroll
+  for (int j = 0; j < kPtsTrips; ++j) {
+    m[j] = ptv_candidate_word(a, a.v[v].W, lb, s, j, xs[j], ys[j]);
+    if (lane == 0) s_cnt[j * 4 + wave] = __popcll(m[j]);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kPtsTrips; ++j) {
+    if (((m[j] >> lane) & 1ull) == 0ull) continue;
+    int slot = before;  // the segment's words come in pixel order: trip-major, then wave
+    for (int k = 0; k < j * 4 + wave; ++k) slot += s_cnt[k];
+    slot += __popcll(m[j] & ((1ull << lane) - 1ull));
+    if (slot >= a.n_max) continue;  // the tail is cut (record[3] > n_max tells)
+    const float4 d = depth[lb * kPtsSeg + j * 256 + threadIdx.x];
+    float p[3];
+    ptv_back_project(f, d.x, xs[j], ys[j], p);
+    p3d[3 * (size_t)slot + 0] = p[0];
+    p3d[3 * (size_t)slot + 1] = p[1];
+    p3d[3 * (size_t)slot + 2] = p[2];
+    slot_valid[slot] = 1;
+  }
+  // unused slots: the camera centre R^T (-t), which the sampler rejects at the frame's pose (z > kCamEps fails)
+  const int n_points = min(all, a.n_max);
+  float c[3];
+  ptv_to_object(f, -f[9], -f[10], -f[11], c);
+  for (int slot = n_points + lb * 256 + threadIdx.x; slot < a.n_max; slot += nseg * 256) {
+    p3d[3 * (size_t)slot + 0] = c[0];
+    p3d[3 * (size_t)slot + 1] = c[1];
+    p3d[3 * (size_t)slot + 2] = c[2];
+    slot_valid[slot] = 0;
+  }
+  if (lb == nseg - 1 && threadIdx.x == 0) {
+    int* record = records + 4 * v;
+    record[0] = A;
+    record[1] = s;
+    record[2] = n_points;
+    record[3] = all;
+  }
+}
+
+constexpr int kPtvHeadBytes = PXT_POINTS_MAX_VIEWS * 2 * 4;  // (a multiple of 64)
+
+// The segments of all views, or -1 when a count or a size is out of range.
+static inline int64_t ptv_total_segments(int32_t n_views, const int32_t* sizes) {
+  if (n_views < 1 || n_views > PXT_POINTS_MAX_VIEWS || !sizes) return -1;
+  int64_t nseg = 0;
+  for (int k = 0; k < n_views; ++k) {
+    if (!pts_size_ok(sizes[2 * k], sizes[2 * k + 1])) return -1;
+    nseg += ((int64_t)sizes[2 * k] * sizes[2 * k + 1] + kPtsSeg - 1) / kPtsSeg;
+  }
+  return nseg;
+}
+
+}  // namespace pxt
+
+extern "C" int64_t pxt_points_from_depth_views_workspace_bytes(int32_t n_views, const int32_t* sizes) {
+  const int64_t nseg = ptv_total_segments(n_views, sizes);
+  if (nseg < 0) return -1;
+  return kPtvHeadBytes + pts_round64(2 * nseg * 4) + nseg * kPtsWords * 8;
+}
+
+extern "C" int pxt_points_from_depth_views(const float* const* depth, const int32_t* sizes, const float* views, int32_t n_views,
+                                           float min_alpha, int32_t erode, int32_t n_max, float* p3d, uint8_t* slot_valid,
+                                           int32_t* records, void* workspace, void* stream) {
+  if (!depth || !sizes || !views || !p3d || !slot_valid || !records || !workspace) return PXT_E_ARG;
+  const int64_t nseg = ptv_total_segments(n_views, sizes);
+  if (nseg < 0) return PXT_E_ARG;
+  if (erode < 0 || erode > 2 || n_max < 1 || n_max > (1 << 24)) return PXT_E_ARG;
+  if (((uintptr_t)workspace % 16) != 0 || ((uintptr_t)p3d % 4) != 0 || ((uintptr_t)slot_valid % 4) != 0 ||
+      ((uintptr_t)records % 4) != 0)
+    return PXT_E_ARG;
+  PtvArgs a;
+  int seg0 = 0;
+  for (int k = 0; k < n_views; ++k) {
+    const float* f = views + (size_t)k * PXT_MESH_VIEW;
+    for (int i = 0; i < PXT_MESH_VIEW; ++i)
+      if (!std::isfinite(f[i])) return PXT_E_ARG;
+    if (!(f[12] > 0.f) || !(f[13] > 0.f) || !(f[17] > 0.f)) return PXT_E_ARG;
+    if (!depth[k] || ((uintptr_t)depth[k] % 16) != 0) return PXT_E_ARG;
+    PtvView& v = a.v[k];
+    for (int i = 0; i < PXT_MESH_VIEW; ++i) v.f[i] = f[i];
+    v.depth = (const float4*)depth[k];
+    v.W = sizes[2 * k];
+    v.H = sizes[2 * k + 1];
+    v.npix = v.W * v.H;
+    v.seg0 = seg0;
+    seg0 += (v.npix + kPtsSeg - 1) / kPtsSeg;
+  }
+  for (int k = n_views; k < PXT_POINTS_MAX_VIEWS; ++k) a.v[k] = PtvView{};
+  a.n_views = n_views;
+  a.nseg = (int)nseg;
+  a.erode = erode;
+  a.n_max = n_max;
+  a.min_alpha = min_alpha;
+  char* ws = (char*)workspace;
+  a.head = (int*)ws;
+  a.seg_accepted = (int*)(ws + kPtvHeadBytes);
+  a.seg_candidates = a.seg_accepted + a.nseg;
+  a.bits = (unsigned long long*)(ws + kPtvHeadBytes + pts_round64(2 * nseg * 4));
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(points_views_accept_kernel, dim3(a.nseg), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(points_views_stride_kernel, dim3(a.nseg), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(points_views_compact_kernel, dim3(a.nseg), dim3(256), 0, s, a, p3d, slot_valid, (int*)records);
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;
 }

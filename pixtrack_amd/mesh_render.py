@@ -436,6 +436,61 @@ def frame_reference(V, F, shading: dict, requests) -> list:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# reference points from a frame's depth plane (pxt_points_from_depth_views)
+# ---------------------------------------------------------------------------------------------------------------------
+POINTS_MAX_VIEWS = _lib.PXT_POINTS_MAX_VIEWS
+
+
+def _object_from_camera(view, q0, q1, q2) -> np.ndarray:
+    """``p_j = (R_0j q_0 + R_1j q_1) + R_2j q_2`` in float32, one operation per step -> [n, 3]."""
+    R = view[:9].reshape(3, 3)
+    with np.errstate(all="ignore"):
+        return np.stack([((R[0, j] * q0).astype(_F) + (R[1, j] * q1).astype(_F)).astype(_F) + (R[2, j] * q2).astype(_F)
+                         for j in range(3)], -1).astype(_F)
+
+
+def points_reference(depth, view20, min_alpha: float, erode: int, n_max: int):
+    """The rule of pxt_points_from_depth_views for one view in numpy: ``depth`` [H, W, 4] float32 (the ``depth`` output
+    of a frame call), ``view20`` the 20 floats it was drawn with -> ``(p3d float32 [n_max, 3], slot_valid uint8 [n_max],
+    record int64 [4] = {accepted pixels, stride, points, candidates})``.  The selection works on whole boolean images
+    (no segments, no ballot words); the back-projection is the header's, one float32 operation per step."""
+    d = np.asarray(depth, np.float32)
+    v = np.asarray(view20, np.float32).reshape(VIEW)
+    H, W, e, n_max = int(d.shape[0]), int(d.shape[1]), int(erode), int(n_max)
+    with np.errstate(invalid="ignore"):
+        base = (d[..., 3] >= _F(min_alpha)) & (d[..., 0] > 0)
+    accepted = np.zeros((H, W), bool)
+    if H > 2 * e and W > 2 * e:  # a square that leaves the image fails
+        inner = np.ones((H - 2 * e, W - 2 * e), bool)
+        for dy in range(-e, e + 1):
+            for dx in range(-e, e + 1):
+                inner &= base[e + dy:H - e + dy, e + dx:W - e + dx]
+        accepted[e:H - e, e:W - e] = inner
+    A = int(accepted.sum())
+    s = 1
+    while s * s * n_max < A:
+        s += 1
+    ys, xs = np.nonzero(accepted)  # row-major order
+    lattice = (xs % s == s // 2) & (ys % s == s // 2)
+    xs, ys = xs[lattice], ys[lattice]
+    n_candidates = len(xs)
+    n = min(n_candidates, n_max)
+    xs, ys = xs[:n], ys[:n]
+    t = v[9:12]
+    p3d = np.empty((n_max, 3), np.float32)
+    with np.errstate(all="ignore"):
+        z = (d[ys, xs, 0] / v[17]).astype(_F)
+        xn = ((xs.astype(_F) - v[14]).astype(_F) / v[12]).astype(_F)
+        yn = ((ys.astype(_F) - v[15]).astype(_F) / v[13]).astype(_F)
+        c0, c1 = (z * xn).astype(_F), (z * yn).astype(_F)
+        p3d[:n] = _object_from_camera(v, (c0 - t[0]).astype(_F), (c1 - t[1]).astype(_F), (z - t[2]).astype(_F))
+        p3d[n:] = _object_from_camera(v, -t[0:1], -t[1:2], -t[2:3])  # the camera centre
+    slot_valid = np.zeros(n_max, np.uint8)
+    slot_valid[:n] = 1
+    return p3d, slot_valid, np.array([A, s, n, n_candidates], np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the GPU renderer
 # ---------------------------------------------------------------------------------------------------------------------
 class MeshRenderer:

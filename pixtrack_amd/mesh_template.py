@@ -79,18 +79,21 @@ class MeshTemplate:
             return [(vq, *size(query_camera), 1, depth_outputs + ("rgb_u8",))]
         return [(vq, *size(query_camera), 1, depth_outputs), (vr, *size(reference_camera), self.supersample, ("rgb_u8",))]
 
-    def frame(self, pose, query_camera: Camera, reference_camera: Camera, want_depth: bool = False):
+    def frame(self, pose, query_camera: Camera, reference_camera: Camera, want_depth: bool = False, requests=None):
         """-> ``(depth_nz uint8 [Hq, Wq], rgb_u8 uint8 [Hr, Wr, 3])`` device tensors at ``pose`` (world -> camera, a
         ``Pose`` or 4x4), and with ``want_depth`` the query view's float depth image [Hq, Wq, 4] (depths times
-        ``depth_q(pose)``) as a third.  One call, four launches, nothing downloaded."""
-        out = self.renderer.render_frame(self.requests(pose, query_camera, reference_camera, want_depth),
-                                         download_records=False)
+        ``depth_q(pose)``) as a third.  One call, four launches, nothing downloaded.  ``requests``: what ``requests``
+        returned for these arguments, for a caller that also reads the view records (``requests[0][0]``: the query
+        view's 20 floats, which ``mesh_render.points_reference`` / pxt_points_from_depth_views back-project through)."""
+        if requests is None:
+            requests = self.requests(pose, query_camera, reference_camera, want_depth)
+        out = self.renderer.render_frame(requests, download_records=False)
         res = (out[0]["depth_nz"], out[-1]["rgb_u8"])
         return res + (out[0]["depth"],) if want_depth else res
 
     @staticmethod
     def frames(templates, poses, query_cameras, reference_cameras, workspace=None, scenes=None, r_grow: int = 0,
-               records: bool = False) -> list:
+               records: bool = False, want_depth=None) -> list:
         """``frame`` for several templates - K objects tracked in lock-step - in ONE ``mesh_render.render_frame_batch``
         call: every template's ``requests`` as ``frame`` forms them, one chain of launches, one upload of all views ->
         ``[(depth_nz, rgb_u8)]`` per template, the planes ``frame`` returns bit for bit.  ``workspace``: the calling
@@ -101,13 +104,23 @@ class MeshTemplate:
         the query camera.  -> ``[(depth_nz, rgb_u8, occluder or None)]``: ``occluder`` uint8 [Hq, Wq] marks the pixels
         where another template of the scene lies in front of this one, grown by the ``(2 r_grow + 1)^2`` box
         (pxt_mesh_render_scene_batch, one more launch).  ``records``: the query view's record (int32 [16] on the
-        device; words 0, 10, 11: covered, hidden, occluder pixels) is appended to every tuple."""
-        reqs = [t.requests(pose, qc, rc) for t, pose, qc, rc in zip(templates, poses, query_cameras, reference_cameras)]
+        device; words 0, 10, 11: covered, hidden, occluder pixels) is appended to every tuple.
+
+        ``want_depth`` (one bool per template; None: exactly the calls above): a template that asks also gets its query
+        view's float depth plane, as ``frame(..., want_depth=True)`` returns it.  Every tuple then ends in ``(depth or
+        None, view20 or None)``: the plane and the 20 floats of the view record it was drawn with."""
+        if want_depth is None:
+            reqs = [t.requests(pose, qc, rc) for t, pose, qc, rc in zip(templates, poses, query_cameras, reference_cameras)]
+        else:
+            reqs = [t.requests(pose, qc, rc, bool(d))
+                    for t, pose, qc, rc, d in zip(templates, poses, query_cameras, reference_cameras, want_depth)]
         items = [(t.renderer, q) for t, q in zip(templates, reqs)]
+        tail = lambda out, q: () if want_depth is None else ((out[0]["depth"], q[0][0]) if "depth" in q[0][4] else (None, None))
         if scenes is None:
             outs = R.render_frame_batch(items, workspace=workspace, download_records=False)
-            return [(out[0]["depth_nz"], out[-1]["rgb_u8"]) + ((out[0]["records"],) if records else ()) for out in outs]
+            return [(out[0]["depth_nz"], out[-1]["rgb_u8"]) + ((out[0]["records"],) if records else ()) + tail(out, q)
+                    for out, q in zip(outs, reqs)]
         view_scenes = [[s] + [None] * (len(q) - 1) for s, q in zip(scenes, reqs)]
         outs = R.render_frame_batch(items, workspace=workspace, download_records=False, scenes=view_scenes, r_grow=r_grow)
         return [(out[0]["depth_nz"], out[-1]["rgb_u8"], out[0].get("occluder")) + ((out[0]["records"],) if records else ())
-                for out in outs]
+                + tail(out, q) for out, q in zip(outs, reqs)]

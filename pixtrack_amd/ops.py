@@ -19,6 +19,8 @@ Reference call sites the ops stand in for:
   resize_linear        pixloc resize(image, size, max, "linear") (feature_extractor.py:45)
   points_from_depth    (opt-in) stands in for the SfM points of the nearest mapping image as the points a frame is
                        refined on (pixloc_pose_refiners.py:282-290): a lattice of the Depth render, back-projected
+  points_from_depth_views  (opt-in) the same from the depth planes a mesh template's frame call drew, up to 16 views of
+                       different sizes in one chain of three launches (mesh_render.points_reference restates it)
   pose_errors          (opt-in) ADD / ADD-S of F frames against ground truth in one call: the per-frame loop of
                        notebooks/GetMetrics.ipynb (get_metrics) and evaluation.adds_distance
   depth_agreement      (opt-in, no reference counterpart) P pairs of Depth renders compared pixel by pixel: the counts
@@ -127,6 +129,13 @@ SCHEMAS = {
     "points_from_depth": (
         "(Tensor depth, float[] xform, float focal, float depth_scale, float min_alpha, int erode, int n_max, "
         "Tensor(a!) p3d, Tensor(b!) slot_valid, Tensor(c!) record, Tensor(d!) workspace) -> ()"),
+    # depth: K <= 16 planes [H_k, W_k, 4] of a mesh frame call, views = K x 20 floats (the records the planes were drawn
+    # with) -> p3d [K, n_max, 3], slot_valid uint8 [K, n_max], record int32 [K, 4] (device or pinned): per view
+    # {accepted pixels, stride, points, candidates} (pxt_points_from_depth_views); workspace: uint8,
+    # pxt_points_from_depth_views_workspace_bytes(K, sizes)
+    "points_from_depth_views": (
+        "(Tensor[] depth, float[] views, float min_alpha, int erode, int n_max, Tensor(a!) p3d, Tensor(b!) slot_valid, "
+        "Tensor(c!) record, Tensor(d!) workspace) -> ()"),
     # centred vertices [V, 3], rel_poses [F, 12] (evaluation.relative_poses) -> records [F, 8]: ADD, its max, ADD-S, its
     # max, V, 0, 0, status (pxt_pose_errors); workspace: uint8, pxt_pose_errors_workspace_bytes(F, V)
     "pose_errors": (
@@ -921,6 +930,54 @@ def _points_from_depth(depth, xform, focal, depth_scale, min_alpha, erode, n_max
     _lib.check(L.pxt_points_from_depth(depth.data_ptr(), W, H, xf, float(focal), float(depth_scale), float(min_alpha),
                                        int(erode), n_max, p3d.data_ptr(), slot_valid.data_ptr(), record.data_ptr(),
                                        workspace.data_ptr(), _stream(depth)), "pxt_points_from_depth")
+
+
+def _points_from_depth_views(depth, views, min_alpha, erode, n_max, p3d, slot_valid, record, workspace):
+    L = _lib.lib()
+    what = "points_from_depth_views"
+    K, n_max = len(depth), int(n_max)
+    if not (1 <= K <= _lib.PXT_POINTS_MAX_VIEWS):
+        raise _lib.PxtError(f"{what}: 1..{_lib.PXT_POINTS_MAX_VIEWS} depth planes (got {K})")
+    sizes = []
+    for k, d in enumerate(depth):
+        _f32c(d, f"depth[{k}]")
+        if d.dim() != 3 or int(d.shape[2]) != 4:
+            raise _lib.PxtError(f"{what}: depth[{k}] is [H, W, 4] (got {tuple(d.shape)})")
+        sizes += [int(d.shape[1]), int(d.shape[0])]
+    _f32c(p3d, "p3d")
+    if len(views) != K * _lib.PXT_MESH_VIEW:
+        raise _lib.PxtError(f"{what}: views holds {_lib.PXT_MESH_VIEW} floats per plane ({K * _lib.PXT_MESH_VIEW}; got "
+                            f"{len(views)})")
+    if int(erode) not in (0, 1, 2) or n_max < 1:
+        raise _lib.PxtError(f"{what}: erode is 0, 1 or 2 and n_max >= 1")
+    if tuple(p3d.shape) != (K, n_max, 3):
+        raise _lib.PxtError(f"{what}: p3d is {tuple(p3d.shape)}, expected {(K, n_max, 3)}")
+    if slot_valid.dtype != torch.uint8 or tuple(slot_valid.shape) != (K, n_max) or not slot_valid.is_contiguous():
+        raise _lib.PxtError(f"{what}: slot_valid is a contiguous uint8 [{K}, n_max]")
+    if record.dtype != torch.int32 or tuple(record.shape) != (K, 4) or not record.is_contiguous():
+        raise _lib.PxtError(f"{what}: record is a contiguous int32 [{K}, 4]")
+    size_arr = (C.c_int32 * (2 * K))(*sizes)
+    need = int(L.pxt_points_from_depth_views_workspace_bytes(K, size_arr))
+    if need <= 0:
+        raise _lib.PxtError(f"{what}: planes of {list(zip(sizes[0::2], sizes[1::2]))} are not supported")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {need} bytes")
+    # what the kernels dereference must be memory of the depth planes' device (a host pointer there is a memory fault,
+    # not an error); the record may also be pinned host memory
+    device = depth[0].device
+    named = [(d, f"depth[{k}]") for k, d in enumerate(depth)] + [(p3d, "p3d"), (slot_valid, "slot_valid"),
+                                                                  (workspace, "workspace")]
+    for t, name in named:
+        _lib.require_gpu(t, name)
+        if t.device != device:
+            raise _lib.PxtError(f"{what}: {name} is on {t.device}, depth[0] on {device}")
+    if not ((record.is_cuda and record.device == device) or record.is_pinned()):
+        raise _lib.PxtError(f"{what}: record must be memory of the depth planes' device or pinned host memory")
+    planes = (C.c_void_p * K)(*[d.data_ptr() for d in depth])
+    vf = (C.c_float * len(views))(*[float(x) for x in views])
+    _lib.check(L.pxt_points_from_depth_views(planes, size_arr, vf, K, float(min_alpha), int(erode), n_max, p3d.data_ptr(),
+                                             slot_valid.data_ptr(), record.data_ptr(), workspace.data_ptr(),
+                                             _stream(depth[0])), "pxt_points_from_depth_views")
 
 
 def _pose_errors(vertices, rel_poses, want_adds, records, workspace):
@@ -1735,6 +1792,7 @@ _IMPLS = {
     "depth_agreement": _depth_agreement,
     "pose_errors": _pose_errors,
     "points_from_depth": _points_from_depth,
+    "points_from_depth_views": _points_from_depth_views,
     "lm_refine": _lm_refine,
     "lm_refine_batch": _lm_refine_batch,
     "lm_information": _lm_information,

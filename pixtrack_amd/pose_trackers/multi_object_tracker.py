@@ -23,6 +23,9 @@ methods - and only the device work of a frame step is merged:
   image.  That call then also tells, per object, the pixels where another object of its scene lies in front
   (``pxt_mesh_render_scene_batch``); they leave the object's query mask, and the reference points that project onto them
   leave its LM's point mask.
+* mesh trackers with ``reference_points="template"`` refine on a lattice of their own frame's depth plane: that call
+  then also writes their query views' float depth planes, and ONE ``pxt_points_from_depth_views`` call behind it
+  extracts the points of all of them (three launches for the group instead of three per object).
 
 A tracker in cold start (image scales [4, 1]: two dependent refinements) runs that frame by itself
 through ``run_single_frame``; everything else is lock-step.  Per object the results are those of the
@@ -41,6 +44,7 @@ import os
 import torch
 
 from .. import _lib
+from ..ops import ops
 from ..optimizer import PixTrackOptimizer
 from ..tracker import DebugTracker
 from ..point_report import parse_mode
@@ -77,6 +81,9 @@ class _Group:
         self.report_ws: Optional[torch.Tensor] = None  # ... and of the step's point-report launch
         self.render_ws: Optional[torch.Tensor] = None  # parameter records of the batched render chain
         self.mesh_ws = None  # mesh_render.FrameBatchWorkspace of the group's mesh-template frames (made on first use)
+        self.points_ws: Optional[torch.Tensor] = None  # workspace of the step's pxt_points_from_depth_views call(s)
+        self.points_records = None  # pinned [16, 4] records of those calls, recycled round-robin
+        self.points_next = 0
         self.unet_done: Optional[torch.cuda.Event] = None
         self.pend = None  # what _enqueue left for _finish
 
@@ -92,7 +99,12 @@ class MultiObjectTracker:
         part of the scene that step: it neither hides anything nor is hidden.  Each history entry gains
         ``MUTUAL_HISTORY_KEYS``.  ValueError: a scene with a tracker that has no mesh template; query cameras of a scene
         that differ in size, f or c or have lens terms (checked here where a tracker already has its camera, else at the
-        first step that draws the scene); a scene that cannot be kept in one group.
+        first step that draws the scene); a scene that cannot be kept in one group; any tracker with
+        ``reference_points="template"`` (not combined yet).
+        Trackers built with ``reference_points="template"`` (mesh templates only; ``"render"`` stays refused) are accepted
+        beside ``"sfm"`` ones: per step and group the points of all of them that take the lock-step path come from ONE
+        pxt_points_from_depth_views call behind the frame call (``points_calls`` counts them); a tracker that runs a step
+        alone extracts its own.
         ``uncertainty``: None keeps each tracker's own setting, True / False sets it for all of them (the ``uncertainty``
         option of PixLocPoseTrackerR9): the information problems of a group's step then go out as ONE pxt_lm_information
         launch behind its batched LM launch and its queued renders.
@@ -115,9 +127,20 @@ class MultiObjectTracker:
             # ground-truth-gated updates, pixloc_tracker_ycb.py:241-295) would silently run r9's policy here
             if type(tr).refine is not PixLocPoseTrackerR9.refine or type(tr)._frame_policy is not PixLocPoseTrackerR9._frame_policy:
                 raise _lib.PxtError(f"{type(tr).__name__} overrides refine(): lock-step tracking implements PixLocPoseTrackerR9's policy only")
-            if getattr(tr, "reference_points", "sfm") != "sfm":
+            points = getattr(tr, "reference_points", "sfm")
+            if points == "template":
+                # (phase A extracts the points of a group's "template" trackers in one call, from the planes of their
+                # mesh templates' one frame call)
+                from ..mesh_template import MeshTemplate
+
+                if not isinstance(getattr(tr, "template", None), MeshTemplate):
+                    raise ValueError("reference_points='template' in lock-step tracking needs a tracker with a mesh template")
+                if mutual_occlusion is not None:
+                    raise ValueError("mutual_occlusion is not combined with a reference_points='template' tracker yet (the "
+                                     "scene call does not hand out the depth planes)")
+            elif points != "sfm":
                 # (the batched render chain carries no float Depth image and the batched reference pass encodes the SfM window)
-                raise ValueError("reference_points='render' is not supported by lock-step tracking yet")
+                raise ValueError(f"reference_points={points!r} is not supported by lock-step tracking yet")
             if getattr(tr, "depth_refine", None) is not None:
                 # (the lock-step step launches the LM itself: nothing queues the depth problem behind it)
                 raise ValueError("depth_refine is not supported by lock-step tracking yet")
@@ -163,6 +186,7 @@ class MultiObjectTracker:
         self.steps = 0
         self.solo_frames = 0       # frames that ran through run_single_frame (cold starts, several references)
         self.lockstep_frames = 0
+        self.points_calls = 0      # pxt_points_from_depth_views calls made for "template" trackers (one per group and step)
         self.timing = None         # set to {} to collect HIP-event pairs per phase (bench.py's untimed diagnostic pass)
 
     def _checked_scenes(self, option: MutualOcclusion) -> list:
@@ -334,9 +358,12 @@ class MultiObjectTracker:
             # - but a reference render of the query's own size goes through the UNet with everybody else's: a window
             # would take it out of the batch (one 14-image pass became a 13-image pass + two small ones: 4.5 -> 5.3 ms)
             refiner = tr.localizer.refiner
-            if tuple(ref_u8.shape[:2]) == tuple(image.shape[:2]):
-                refiner._window_memo = (ref_u8, tr.pose, ref_u8, None)
-            ref_in, _win = refiner.reference_window(tr.reference_ids, tr.pose, ref_u8)
+            if refiner.render_points:  # ("template": the points are not the SfM table's - the whole image, as solo)
+                ref_in = ref_u8
+            else:
+                if tuple(ref_u8.shape[:2]) == tuple(image.shape[:2]):
+                    refiner._window_memo = (ref_u8, tr.pose, ref_u8, None)
+                ref_in, _win = refiner.reference_window(tr.reference_ids, tr.pose, ref_u8)
             jobs.append((ex, ref_in, 1, None, False))                               # extract_reference_features
             jobs.append((ex, image, 1, tr.localizer.refiner.query_mask, True))      # refine_query_pose's query pass
         self._unet_batch(grp, jobs)
@@ -427,6 +454,14 @@ class MultiObjectTracker:
         scenes = self._step_scenes(grp, frames) if self.mutual_occlusion is not None else None
         views = ([tr.template for tr in part], [tr.pose for tr in part], [tr.camera for tr in part],
                  [tr._reference_camera() for tr in part])
+        want_depth = [tr.reference_points == "template" for tr in part]
+        if any(want_depth):  # (never with mutual_occlusion: refused at construction)
+            planes = MeshTemplate.frames(*views, workspace=grp.mesh_ws, want_depth=want_depth)
+            for tr, (nz, ref_u8, _depth, _view) in zip(part, planes):
+                tr._primed_frame = (tr.pose, nz, ref_u8)
+            self._prime_template_points(grp, [(tr, depth, view) for tr, (_nz, _ref, depth, view) in zip(part, planes)
+                                              if depth is not None])
+            return
         if scenes is None:  # (also: no scene has two members in this step - the call is the one made without the option)
             for tr, (nz, ref_u8) in zip(part, MeshTemplate.frames(*views, workspace=grp.mesh_ws)):
                 tr._primed_frame = (tr.pose, nz, ref_u8)
@@ -435,6 +470,44 @@ class MultiObjectTracker:
                                      records=True)
         for tr, (nz, ref_u8, occluder, record) in zip(part, planes):
             tr._primed_frame = (tr.pose, nz, ref_u8, None if occluder is None else (occluder, record))
+
+    def _prime_template_points(self, grp: _Group, items) -> None:
+        """``items`` = [(tracker, depth plane, view record)] of the group's "template" trackers in this step: their
+        points in ONE pxt_points_from_depth_views call behind the frame call (one per distinct (n_max, erode, min_alpha),
+        normally one; more than 16 views in chunks); each tracker keeps its (pose, p3d, slot_valid, record), which its
+        get_dynamic_id consumes in phase C instead of extracting again."""
+        by_conf: dict = {}
+        for item in items:
+            conf = item[0].localizer.refiner.conf
+            key = (int(conf.reference_points_max), int(conf.reference_points_erode), float(conf.reference_points_min_alpha))
+            by_conf.setdefault(key, []).append(item)
+        L, C = _lib.lib(), _lib.C
+        for (n_max, erode, min_alpha), members in by_conf.items():
+            for a in range(0, len(members), _lib.PXT_POINTS_MAX_VIEWS):
+                chunk = members[a:a + _lib.PXT_POINTS_MAX_VIEWS]
+                n = len(chunk)
+                sizes = [x for _tr, depth, _v in chunk for x in (int(depth.shape[1]), int(depth.shape[0]))]
+                need = int(L.pxt_points_from_depth_views_workspace_bytes(n, (C.c_int32 * (2 * n))(*sizes)))
+                if need <= 0:
+                    raise _lib.PxtError(f"depth planes of {sizes} are not supported by pxt_points_from_depth_views")
+                # (one workspace serves one call at a time: the group's calls follow each other on its stream)
+                if grp.points_ws is None or grp.points_ws.numel() < need:
+                    grp.points_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                if grp.points_records is None:
+                    # the kernel receives the raw pointer: the records live as long as the group and are recycled - a
+                    # step's were read (in its _frame_policy) long before eight more calls are queued
+                    grp.points_records = [torch.zeros(_lib.PXT_POINTS_MAX_VIEWS, 4, dtype=torch.int32).pin_memory()
+                                          for _ in range(8)]
+                record = grp.points_records[grp.points_next][:n]
+                grp.points_next = (grp.points_next + 1) % len(grp.points_records)
+                p3d = torch.empty(n, n_max, 3, dtype=torch.float32, device=self.device)
+                slot_valid = torch.empty(n, n_max, dtype=torch.uint8, device=self.device)
+                ops.points_from_depth_views([depth for _tr, depth, _v in chunk],
+                                            [float(x) for _tr, _d, view in chunk for x in view.reshape(-1)], min_alpha, erode,
+                                            n_max, p3d, slot_valid, record, grp.points_ws)
+                self.points_calls += 1
+                for i, (tr, _depth, _view) in enumerate(chunk):
+                    tr._primed_points = (tr.pose, p3d[i], slot_valid[i], record[i])
 
     def _step_scenes(self, grp: _Group, frames):
         """The scene of each of the group's mesh trackers that take the lock-step path this step (the order of
@@ -572,6 +645,10 @@ def build_parser():
                     help="samples per pixel and axis of each mesh template's reference image (default 2, untuned)")
     ap.add_argument("--reference_sfm", type=Path, nargs="+", default=None,
                     help="each object's SfM model directory (the ref/ directory mesh_dataset wrote)")
+    ap.add_argument("--reference_points", choices=("sfm", "template"), default="sfm",
+                    help="the points every object's frames are refined on: sfm (default: the SfM points of the nearest "
+                         "mapping image) or template (--template mesh: a lattice of the depth plane the mesh template draws "
+                         "for the frame; a group's points are extracted in one call)")
     ap.add_argument("--mutual_occlusion", action="store_true",
                     help="--template mesh: objects whose --query paths are equal share an image; the pixels where another of "
                          "them lies in front leave an object's mask and gate its points")
@@ -650,7 +727,8 @@ def main(argv=None):
                                             object_path=str(obj), data_path=str(obj / "pixtrack/pixsfm/dataset"),
                                             eval_path=str(args.out_dir[k]), loc_path=str(obj / "pixtrack/aug_nerf_sfm"),
                                             debug=args.debug, unet_precision=args.unet_precision,
-                                            uncertainty=args.uncertainty, point_report=args.point_report))
+                                            uncertainty=args.uncertainty, point_report=args.point_report,
+                                            reference_points=args.reference_points))
     try:
         mutual = mutual_occlusion_from_args(args)
     except ValueError as e:

@@ -72,7 +72,11 @@ class PixLocPoseTrackerR9(PoseTracker):
         frame's own Depth render (refiner.points_from_render): they cover the visible side, do not change when
         update_reference_ids switches and need no triangulated points.  A frame's history entry then gains
         ``n_reference_points`` and ``reference_point_stride``; nothing on the policy path reads them.  Not combined
-        with ``relocalizer`` or ``uncertainty`` yet (ValueError).
+        with ``relocalizer`` or ``uncertainty`` yet (ValueError).  "template" is "render" for a mesh template: the
+        lattice is taken from the float depth plane the template's frame call draws for the query view
+        (``MeshTemplate.frame(..., want_depth=True)``) and back-projected through the very view record it was drawn
+        with (refiner.points_from_template, pxt_points_from_depth_views); same history keys, same refusals, and it needs
+        ``template=MeshTemplate(...)`` - with the NeRF template the value is refused and "render" is the one to use.
         ``point_report``: False / "off" (default: nothing changes), "summary" or "full" - every LM launch is followed by
         one pxt_lm_point_report problem at the pose it returns (its last level), and a frame's history entry gains
         ``n_valid_points``, ``n_inliers``, ``inlier_ratio``, ``mean_robust_weight`` and ``rejected_points``
@@ -112,8 +116,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         read (``assets`` may omit ``snapshot``, ``nerf2sfm`` and ``aabb``), ``testbed`` is None and ``render_ahead`` is
         off: the queued render takes its camera from a NeRF camera slot.  Everything downstream of the two images is
         unchanged.  A frame's history gains ``template`` ("mesh") and ``template_supersample``; nothing on the policy
-        path reads them.  Not combined with ``relocalizer``, ``reference_points="render"``, ``depth_refine`` or
-        ``occlusion`` yet (ValueError).
+        path reads them.  Not combined with ``relocalizer``, ``reference_points="render"`` (its mesh counterpart is
+        ``reference_points="template"``), ``depth_refine`` or ``occlusion`` yet (ValueError).
         ``reference_sfm``: the directory of the SfM model (the ``ref/`` directory mesh_dataset wrote) in place of
         ``loc_path/aug_sfm``; ``upright_ref_img``: the upright reference image's name in place of $UPRIGHT_REF_IMG."""
         point_report = parse_mode(point_report)  # (a bad value: ValueError before anything is built)
@@ -192,6 +196,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._primed_frame = None
         self.template_frames_batched = 0
         self._fused_depth = None  # (pose object, float Depth render) beside it: reference_points="render" only
+        # reference_points="template": _fused_depth is (pose object, the template's depth plane, its view record), and
+        # (pose object, p3d, slot_valid, record) are the frame's points where lock-step tracking extracted them in one call
+        # with the other objects' (multi_object_tracker.py); create_dynamic_reference_image takes them instead of its own call
+        self._primed_points = None
         self._ref_cam_cache = self._coincide_cache = None
         self.keep_feature_history = False  # the reference leaks one entry per frame (Appendix D.2)
         self.steady_multiscale = [1]  # image scales of a tracked (non-cold-start) frame (:223)
@@ -265,22 +273,25 @@ class PixLocPoseTrackerR9(PoseTracker):
     supports_render_points = True  # (the YCB policy does not yet)
 
     def _check_reference_points(self, reference_points, relocalizer, uncertainty):
-        if reference_points not in ("sfm", "render"):
-            raise ValueError(f"reference_points must be 'sfm' or 'render' (got {reference_points!r})")
-        if reference_points == "render":
+        if reference_points not in ("sfm", "render", "template"):
+            raise ValueError(f"reference_points must be 'sfm', 'render' or 'template' (got {reference_points!r})")
+        if reference_points != "sfm":  # ("template" is "render" for a mesh template: the same refusals)
             if not self.supports_render_points:
-                raise ValueError(f"reference_points='render' is not supported by {type(self).__name__} yet")
+                raise ValueError(f"reference_points={reference_points!r} is not supported by {type(self).__name__} yet")
             if relocalizer is not None and relocalizer != "off":
-                raise ValueError("reference_points='render' is not combined with a relocalizer yet (its feature bank is "
-                                 "built from the SfM points)")
+                raise ValueError(f"reference_points={reference_points!r} is not combined with a relocalizer yet (its "
+                                 "feature bank is built from the SfM points)")
             if uncertainty:
-                raise ValueError("reference_points='render' is not combined with uncertainty=True yet")
+                raise ValueError(f"reference_points={reference_points!r} is not combined with uncertainty=True yet")
 
     @staticmethod
     def _check_template(template, relocalizer, reference_points, depth_refine, occlusion):
         """-> None (the NeRF template) or the MeshTemplate; the options a mesh template is not combined with yet are
         refused by name."""
         if template is None or (isinstance(template, str) and template == "nerf"):
+            if reference_points == "template":
+                raise ValueError("reference_points='template' takes its points from a mesh template's depth plane: it needs "
+                                 "template=MeshTemplate(...); with the NeRF template use reference_points='render'")
             return None
         from ..mesh_template import MeshTemplate
 
@@ -620,6 +631,8 @@ class PixLocPoseTrackerR9(PoseTracker):
     def create_dynamic_reference_image(self, pose):
         if self.reference_points == "render":
             return self._create_dynamic_reference_from_render(pose)
+        if self.reference_points == "template":
+            return self._create_dynamic_reference_from_template(pose)
         nerf_img = self.get_reference_image(pose)
         # (the reference hashes str(R); the id is only a dictionary key - the bytes of R serve, without numpy's
         # array printer on the per-frame host path)
@@ -638,6 +651,26 @@ class PixLocPoseTrackerR9(PoseTracker):
         dynamic_id = hash(pose.numpy()[0].tobytes())
         features = self.localizer.refiner.extract_reference_features(self.reference_ids, pose, nerf_img, depth=depth,
                                                                      depth_view=self._depth_view(pose))
+        return dynamic_id, features
+
+    def _create_dynamic_reference_from_template(self, pose):
+        """create_dynamic_reference_image with reference_points="template": the points come from the depth plane the
+        mesh template drew for the query view at ``pose`` and the view record it was drawn with - the ones
+        _mask_and_reference kept; a frame that renders no mask (cold start, the frame after a failed one) draws its frame
+        here.  Points that lock-step tracking already extracted for this pose object are taken as they are."""
+        primed, self._primed_points = self._primed_points, None
+        points = depth = view20 = None
+        if primed is not None and primed[0] is pose:
+            points = primed[1:]
+        else:
+            if self._fused_depth is None or self._fused_depth[0] is not pose:
+                self._mask_and_reference(pose, from_slot=False)
+            _, depth, view20 = self._fused_depth
+        self._fused_depth = None
+        ref_u8 = self.get_reference_image(pose)
+        dynamic_id = hash(pose.numpy()[0].tobytes())
+        features = self.localizer.refiner.extract_reference_features(self.reference_ids, pose, ref_u8, depth=depth,
+                                                                     depth_view=view20, points=points)
         return dynamic_id, features
 
     def _depth_view(self, pose) -> dict:
@@ -713,21 +746,28 @@ class PixLocPoseTrackerR9(PoseTracker):
         final pose (render-ahead); otherwise the host's conversion of ``pose``.  Sets ``_fused_reference`` when a pose
         object is given; returns (mask, ref_u8).  With reference_points="render" the Depth render also keeps its float
         image (``_fused_depth`` / ``_last_depth``).  With a mesh template both planes come from one
-        ``MeshTemplate.frame`` call instead; everything after them is the same."""
+        ``MeshTemplate.frame`` call instead; everything after them is the same.  With reference_points="template" that
+        call also writes the query view's float depth plane, kept with its view record in ``_fused_depth``."""
         if self.template is not None:
             primed, self._primed_frame = self._primed_frame, None
-            mutual = None
+            mutual = depth = None
             if primed is not None and pose is not None and primed[0] is pose:  # drawn with the other objects' frames
                 nz, ref_u8 = primed[1], primed[2]
                 mutual = primed[3] if len(primed) > 3 else None  # ... as part of a scene (mutual occlusion)
                 self.template_frames_batched += 1
+            elif self.reference_points == "template":
+                # (the view record the plane is drawn with is the one the points are back-projected through)
+                requests = self.template.requests(pose, self.camera, self._reference_camera(), want_depth=True)
+                nz, ref_u8, plane = self.template.frame(pose, self.camera, self._reference_camera(), want_depth=True,
+                                                        requests=requests)
+                depth = (pose, plane, requests[0][0])
             else:
                 nz, ref_u8 = self.template.frame(pose, self.camera, self._reference_camera())
             mask = self._mask_of(nz)
             if mutual is not None:
                 mask = self._apply_mutual_occlusion(mask, mutual)
             self._last_depth = None
-            self._fused_reference, self._fused_depth = (pose, ref_u8), None
+            self._fused_reference, self._fused_depth = (pose, ref_u8), depth
             return mask, ref_u8
         tb, spp = self.testbed, int(self.spp)
         want_depth = self.reference_points == "render" or self.occlusion is not None
@@ -896,7 +936,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         if self._query_tile_rest > 0:
             self._query_tile_rest -= 1
         elif (self.query_tiles and steady and not lockstep and self.batch_frame_images and self.debug < 2
-              and self.relocalizer is None and self.reference_points != "render"):
+              and self.relocalizer is None and self.reference_points == "sfm"):
             refiner.query_tiles = {"pose": self._frame_pose_init(), "camera": self.camera,
                                    "margin": int(self.query_tile_margin)}
         return "steady" if steady else kind
@@ -994,7 +1034,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         ret["camera"] = self.camera
         if self.relocalizer is not None:  # (an added key only where the option is on: the default history is unchanged)
             ret["relocalized"], self._relocalized_frame = self._relocalized_frame, False
-        if self.reference_points == "render":  # (added keys only where the option is on)
+        if self.reference_points != "sfm":  # (added keys only where the option is on)
             # the pinned record of this frame's extraction: its kernels ran ahead of the LM launch whose result is here
             rec = refiner.last_points_record
             ret["n_reference_points"], ret["reference_point_stride"] = (int(rec[2]), int(rec[1])) if rec is not None else (0, 0)
@@ -1043,9 +1083,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--point_report", choices=("off", "summary", "full"), default="off",
                         help="add every frame's valid / inlier point counts and mean robust weight to poses.pkl (summary), "
                              "and the per-point projections, residuals and weights as well (full)")
-    parser.add_argument("--reference_points", choices=("sfm", "render"), default="sfm",
-                        help="the points a frame is refined on: sfm (default: the SfM points of the nearest mapping image) "
-                             "or render (a lattice of the frame's own depth render, back-projected)")
+    parser.add_argument("--reference_points", choices=("sfm", "render", "template"), default="sfm",
+                        help="the points a frame is refined on: sfm (default: the SfM points of the nearest mapping image), "
+                             "render (a lattice of the frame's own depth render, back-projected) or template (--template "
+                             "mesh: the same lattice of the depth plane the mesh template draws for the frame)")
     parser.add_argument("--depth_refine", action="store_true",
                         help="refine every frame's pose on its sensor depth image after the LM (needs --sensor_depth_dir "
                              "and --sensor_depth_scale)")

@@ -84,9 +84,10 @@ class PoseTrackerRefiner:
         level_plan=None,
         reference_window=True,  # encode only the window of the reference render the sampled points depend on (see reference_window)
         # where the points a frame is refined on come from: "sfm" (the reference: the SfM points of the nearest mapping
-        # image, _points_of) or "render" (a lattice of the frame's own Depth render, back-projected: points_from_render)
+        # image, _points_of), "render" (a lattice of the frame's own Depth render, back-projected: points_from_render) or
+        # "template" (the same lattice of the depth plane a mesh template drew for the frame: points_from_template)
         reference_points="sfm",
-        reference_points_max=2048,       # point slots of a "render" frame (the benchmark's LM problem size)
+        reference_points_max=2048,       # point slots of a "render" / "template" frame (the benchmark's LM problem size)
         reference_points_min_alpha=0.5,  # a pixel's base test: alpha >= this and depth > 0 ...
         reference_points_erode=1,        # ... on the whole (2 erode + 1)^2 square around it (keeps silhouette pixels out)
         # the opt-in point report counts a valid point as an inlier when its robust weight rho' is at least this: for the
@@ -111,9 +112,10 @@ class PoseTrackerRefiner:
         self.paths = paths
         self.conf = merge(self.base_default_config, self.default_config, conf or {})
         assert self.conf.normalize_descriptors and self.conf.compute_uncertainty
-        if self.conf.reference_points not in ("sfm", "render"):
-            raise ValueError(f"reference_points must be 'sfm' or 'render' (got {self.conf.reference_points!r})")
+        if self.conf.reference_points not in ("sfm", "render", "template"):
+            raise ValueError(f"reference_points must be 'sfm', 'render' or 'template' (got {self.conf.reference_points!r})")
         self._points_ws: Dict[Tuple[int, int], torch.Tensor] = {}  # (w, h) -> workspace of pxt_points_from_depth
+        self._points_views_ws: Dict[Tuple[int, int], torch.Tensor] = {}  # ... of a one-view pxt_points_from_depth_views
         self._points_records = None  # pinned {A, s, n_points, n_candidates} records, recycled round-robin
         self._points_next = 0
         self.last_points_record: Optional[torch.Tensor] = None  # the record of the last "render" extraction
@@ -175,7 +177,13 @@ class PoseTrackerRefiner:
 
     @property
     def render_points(self) -> bool:
-        return self.conf.reference_points == "render"
+        """The frame's points are a lattice of its own depth image ("render": the NeRF's Depth render; "template": the
+        plane a mesh template drew), not the SfM points of the nearest mapping image."""
+        return self.conf.reference_points in ("render", "template")
+
+    @property
+    def template_points(self) -> bool:
+        return self.conf.reference_points == "template"
 
     def _next_points_record(self) -> torch.Tensor:
         """A pinned int32 [4] record for pxt_points_from_depth.  The kernel receives the raw pointer, so the records
@@ -213,6 +221,29 @@ class PoseTrackerRefiner:
                               int(self.conf.reference_points_erode), n_max, p3d, slot_valid, record, ws)
         self.last_points_record = record
         return p3d, slot_valid, record
+
+    def points_from_template(self, depth: torch.Tensor, view20):
+        """The points of a "template" frame: -> (p3d [n_max, 3] in the mesh's (= the SfM model's) coordinates, slot_valid
+        uint8 [n_max], record): the same lattice of the accepted pixels of ``depth`` - the float depth plane a mesh
+        template drew for the frame, [H, W, 4] - back-projected through ``view20``, the 20 floats of the view record it
+        was drawn with (pxt_points_from_depth_views, one view).  Enqueued on the current stream like
+        points_from_render; the pinned record may be read once a later result of the stream has arrived."""
+        n_max = int(self.conf.reference_points_max)
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        ws = self._points_views_ws.get((W, H))
+        if ws is None:
+            need = int(_lib.lib().pxt_points_from_depth_views_workspace_bytes(1, (C.c_int32 * 2)(W, H)))
+            if need <= 0:
+                raise _lib.PxtError(f"a {W} x {H} depth plane is not supported by pxt_points_from_depth_views")
+            ws = self._points_views_ws[(W, H)] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        p3d = torch.empty(1, n_max, 3, dtype=torch.float32, device=self.device)
+        slot_valid = torch.empty(1, n_max, dtype=torch.uint8, device=self.device)
+        record = self._next_points_record()
+        ops.points_from_depth_views([depth], [float(x) for x in np.asarray(view20, np.float32).reshape(-1)],
+                                    float(self.conf.reference_points_min_alpha), int(self.conf.reference_points_erode),
+                                    n_max, p3d, slot_valid, record.view(1, 4), ws)
+        self.last_points_record = record
+        return p3d[0], slot_valid[0], record
 
     # ---- the reference pass on a window of the reference render ---------------------------------------------
     # The reference computes the reference image's dense maps only to sample them at the projected 3-D points
@@ -379,10 +410,14 @@ class PoseTrackerRefiner:
         return SparseReferenceFeatures(outs, valid, list(p3dids), p3d, OUTPUT_DIMS)
 
     def extract_reference_features(self, dbids, pose: Optional[Pose] = None, reference_image=None, depth=None,
-                                   depth_view=None):
+                                   depth_view=None, points=None):
         """``depth`` / ``depth_view`` (conf.reference_points == "render" only): the float Depth render at ``pose`` and
         its view record (points_from_render); the points then come from it instead of the SfM model, their ids are the
-        slot indices, and the whole reference render is encoded (reference_window is derived from the SfM points)."""
+        slot indices, and the whole reference render is encoded (reference_window is derived from the SfM points).
+        With "template" ``depth`` is the depth plane the mesh template drew at ``pose`` and ``depth_view`` the 20
+        floats of its view record (points_from_template) - or ``points`` = (p3d, slot_valid, record), already
+        extracted for this pose (lock-step tracking extracts a step's points in one call): nothing is launched for
+        them here."""
         multiscales = self.conf.multiscale or [1]
         if reference_image is None:
             raise NotImplementedError("static reference images on disk (r5/r7 mode) are out of scope: "
@@ -392,9 +427,16 @@ class PoseTrackerRefiner:
             pose = Pose.from_Rt(ref_img.qvec2rotmat(), ref_img.tvec)
         render_points = self.render_points
         if render_points:
-            if depth is None or depth_view is None:
-                raise ValueError("reference_points='render' needs the frame's Depth render (depth, depth_view)")
-            p3d, slot_valid, record = self.points_from_render(depth, depth_view)
+            if self.template_points and points is not None:
+                p3d, slot_valid, record = points
+                self.last_points_record = record
+            elif depth is None or depth_view is None:
+                raise ValueError(f"reference_points={self.conf.reference_points!r} needs the frame's depth image (depth, "
+                                 "depth_view)")
+            elif self.template_points:
+                p3d, slot_valid, record = self.points_from_template(depth, depth_view)
+            else:
+                p3d, slot_valid, record = self.points_from_render(depth, depth_view)
             p3dids = self.__dict__.get("_slot_ids")
             if p3dids is None or len(p3dids) != int(p3d.shape[0]):
                 p3dids = self._slot_ids = list(range(int(p3d.shape[0])))
@@ -753,8 +795,8 @@ class PoseTrackerRefiner:
         ("done", ret) when the reference's early exits apply (too few points), else ("lm", problem) - the problem goes
         into a batched launch and comes back through finish_refine.  Same calls in the same order as refine()."""
         fail = {"success": False, "T_init": pose_init, "dbids": dbids, **self._no_information(), **self._no_point_report()}
-        p3dids, _ = self._points_of(dbids)
-        if len(p3dids) < self.conf.min_points_opt:
+        # (points of the frame's own depth plane are counted on the device, as in refine())
+        if not self.render_points and len(self._points_of(dbids)[0]) < self.conf.min_points_opt:
             logger.debug("Not enough valid 3D points to optimize")
             return "done", fail
         multiscales = self.conf.multiscale or [1]
