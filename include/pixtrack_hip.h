@@ -1481,6 +1481,58 @@ int pxt_mesh_render_scene_batch(const pxt_mesh_desc* meshes, int32_t n_meshes, c
                                 int32_t r_grow, uint8_t* out_occluder, int64_t occluder_bytes,
                                 const int64_t* occluder_offsets, uint32_t* records, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Render-ahead for mesh templates: pxt_mesh_render_frame_batch whose views take their pose ON THE DEVICE from the
+ * output record of an LM launch queued ahead of the call on the same stream (opt-in; csrc/pxt_raster.hip,
+ * mesh_render.render_frame_batch(poses=), MeshTemplate.frames_ahead, PixLocPoseTrackerR9 with a
+ * MeshTemplate(render_ahead=True)).  The host forms the part of a view record that does not change between frames;
+ * the pose and depth_q are filled in by one small launch once the refinement has written them, so the host need not
+ * wait for the pose before it queues the frame's renders.
+ *
+ * Every argument of pxt_mesh_render_frame_batch, and:
+ *   view_pose [P] (HOST array): per view the record its pose comes from.  pose_record: >= 16 float32 that the device
+ *       can read (device memory or pinned host memory), laid out as pxt_lm_refine's `out` - [0..11] the pose (R
+ *       row-major, then t), [12] failed, [13] status - or NULL for a view drawn from its 20 host floats.  radius: the
+ *       farthest a vertex of the view's mesh lies from the mesh frame's origin (MeshTemplate.radius); ignored when
+ *       pose_record is NULL.  Several views may name one record.
+ *   views_out [P][PXT_MESH_VIEW_OUT] float32, pinned host or device memory, or NULL.
+ * The rule (mesh_render.posed_view_reference restates it in float64; the two agree bit for bit):
+ *   A view with pose_record == NULL is drawn from views[p][0..19], exactly as pxt_mesh_render_frame_batch draws it.
+ *   A posed view p is drawn from the 20 floats v with
+ *       v[12..16] = views[p][12..16] (fx fy cx cy near), v[18..19] = views[p][18..19],
+ *       v[0..11]  = pose_record[0..11], a bit copy; with t = pose_record[9..11]
+ *       v[17]     = (float)(1.0 / (sqrt(((double)t0*t0 + (double)t1*t1) + (double)t2*t2) + radius)):
+ *                   every step one IEEE float64 operation in that order, nothing contracted, rounded to float32 once.
+ *       views[p][0..11] and views[p][17] of a posed view are ignored.
+ *   Every plane and record of a view equal, bit for bit, what pxt_mesh_render_frame_batch draws from the same 20
+ *       floats: the rendering launches are that call's own kernels.
+ *   views_out[p][0..19] = v for a posed view; [20] = 1.0 when pose_record[12] == 0 && pose_record[13] == 0, else
+ *       -1.0; [21..23] = 0.  Word [20] is stored last, with a system-scope release (pxt_lm_refine_cam's cam_out13
+ *       convention): a host that polls pinned memory may read the row once it sees the word.  Rows of un-posed views
+ *       are not written.
+ *   A posed view is drawn whatever the flag says: after a failed refinement out[0..11] holds a finite pose, and the
+ *       caller discards the planes.  Non-finite floats in the record are not special-cased: they fall under the view
+ *       rule of pxt_mesh_raster (record status -1, an all-background image).
+ * Bounds: pxt_mesh_render_frame_batch's, and view_pose not NULL; a posed view's radius finite and >= 0; pose_record
+ *   and views_out 4-byte aligned.  Anything else is PXT_E_ARG and nothing is launched or written.
+ * workspace: pxt_mesh_render_frame_batch_workspace_bytes(...) bytes serve this call too - the posed views' floats are
+ *   overwritten in place inside the uploaded parameter record, nothing is added to it.
+ * Launches on `stream`: pxt_mesh_render_frame_batch's plus ONE - a single wave, one lane per view, after the
+ *   parameter record's asynchronous upload and before the clear launch (no launch is added when no view is posed).
+ *   No host synchronisation beyond the staging ring's, no allocation.  Measured on the MI355X: DESIGN.md 3.22.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  const float* pose_record; /* device-readable (device or pinned host) LM output record, >= 16 floats, or NULL */
+  double radius;            /* MeshTemplate.radius of the view's mesh; ignored when pose_record == NULL */
+} pxt_mesh_view_pose;
+#define PXT_MESH_VIEW_OUT 24   /* 20 view floats, [20] completion word, [21..23] 0 */
+int pxt_mesh_render_frame_batch_posed(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh,
+                                      const float* views, int32_t n_views, const int32_t* geometry,
+                                      const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8,
+                                      float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
+                                      uint32_t* records, void* workspace, const pxt_mesh_view_pose* view_pose,
+                                      float* views_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

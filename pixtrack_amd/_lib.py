@@ -52,6 +52,7 @@ PXT_MESH_FRAME_MAX_VIEWS = 8
 PXT_MESH_BATCH_MAX_MESHES = 16
 PXT_MESH_BATCH_MAX_VIEWS = 32
 PXT_MESH_SCENE_MAX_GROW = 8
+PXT_MESH_VIEW_OUT = 24
 PXT_POINTS_MAX_VIEWS = 16
 
 
@@ -179,6 +180,12 @@ class MeshDesc(C.Structure):
         ("tex_height", C.c_int32),
         ("reserved", C.c_int32),
     ]
+
+
+class MeshViewPose(C.Structure):
+    """pxt_mesh_view_pose: where a view of pxt_mesh_render_frame_batch_posed takes its pose from (NULL: its host
+    floats)."""
+    _fields_ = [("pose_record", C.c_void_p), ("radius", C.c_double)]
 
 
 class NgpView(C.Structure):
@@ -404,6 +411,8 @@ PROTOTYPES = {
     "pxt_mesh_render_frame_batch_workspace_bytes": (_I64, [_I32, _VP, _I32, _VP, _VP]),
     "pxt_mesh_render_frame_batch": (C.c_int, [C.POINTER(MeshDesc), _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP,
                                               _VP, _VP, _VP, _VP]),
+    "pxt_mesh_render_frame_batch_posed": (C.c_int, [C.POINTER(MeshDesc), _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                                    _VP, _VP, _VP, _VP, C.POINTER(MeshViewPose), _VP, _VP]),
     "pxt_mesh_render_scene_batch_workspace_bytes": (_I64, [_I32, _VP, _I32, _VP, _VP]),
     "pxt_mesh_render_scene_batch": (C.c_int, [C.POINTER(MeshDesc), _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP,
                                               _VP, _VP, _I32, _VP, _I64, _VP, _VP, _VP, _VP]),

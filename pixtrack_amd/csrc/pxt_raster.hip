@@ -33,6 +33,8 @@
 #include "pxt_common.h"
 
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
 #include <cstring>
 
 namespace pxt {
@@ -978,6 +980,44 @@ __global__ __launch_bounds__(kRsBlock) void rb_resolve_kernel(const RbRecord* __
   else rf_resolve_view<Attr, 4>(a, attr, g, 0, wh, p0, red, packed);
 }
 
+// pxt_mesh_render_frame_batch_posed: the views whose pose is the output record of an LM launch queued ahead of the
+// call.  One wave, one lane per view, between the parameter record's upload and the clear launch: a posed view's lane
+// copies the record's 12 pose floats into the view's floats inside the uploaded parameter record, forms depth_q from t
+// and the mesh's radius in float64 (the header's order; the file is compiled -ffp-contract=off, and sqrt and the
+// quotient are correctly rounded) and mirrors the 20 floats to views_out, its completion word last.  The rendering
+// kernels that follow read the floats from the parameter record as they always do.
+struct RbPoseTable {
+  const float* record[PXT_MESH_BATCH_MAX_VIEWS];
+  double radius[PXT_MESH_BATCH_MAX_VIEWS];
+};
+
+__global__ __launch_bounds__(64) void rb_pose_kernel(float* __restrict__ views, const RbPoseTable t, float* views_out, const int P) {
+  const int p = threadIdx.x;
+  if (p >= P) return;
+  const float* rec = t.record[p];
+  if (!rec) return;
+  float* v = views + (size_t)p * PXT_MESH_VIEW;
+  float pose[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose[i] = rec[i];
+  const float failed = rec[12], status = rec[13];
+  const double t0 = (double)pose[9], t1 = (double)pose[10], t2 = (double)pose[11];
+  const double norm = __builtin_sqrt((t0 * t0 + t1 * t1) + t2 * t2);
+  const float depth_q = (float)(1.0 / (norm + t.radius[p]));
+#pragma unroll
+  for (int i = 0; i < 12; ++i) v[i] = pose[i];
+  v[17] = depth_q;
+  if (!views_out) return;
+  float* o = views_out + (size_t)p * PXT_MESH_VIEW_OUT;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) o[i] = pose[i];
+#pragma unroll
+  for (int i = 12; i < PXT_MESH_VIEW; ++i) o[i] = i == 17 ? depth_q : v[i];
+  o[21] = o[22] = o[23] = 0.f;
+  // the row (all written by this lane) is visible system-wide before the word: a host may poll it in pinned memory
+  __hip_atomic_store(&o[20], (failed == 0.f && status == 0.f) ? 1.f : -1.f, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // pxt_mesh_render_scene_batch: the batch call for objects that share an image.  Views that name the same scene are the
 // same camera (checked on the host: size and fx fy cx cy bit for bit, S = 1), so their key planes can be compared pixel
@@ -1223,6 +1263,12 @@ struct RbStageSlot {
 };
 constexpr int kRbStageSlots = 4, kRbStageDevices = 16;
 
+// pxt_mesh_render_frame_batch_posed's own arguments.
+struct RbPoseCall {
+  const pxt_mesh_view_pose* view_pose;
+  float* views_out;
+};
+
 // pxt_mesh_render_scene_batch's own arguments.
 struct RbSceneCall {
   const int32_t* view_scene;
@@ -1446,7 +1492,8 @@ extern "C" int64_t pxt_mesh_render_frame_batch_workspace_bytes(int32_t n_meshes,
 static int rb_render(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh, const float* views,
                      int32_t n_views, const int32_t* geometry, const int64_t* out_offsets, float* out_rgba,
                      uint8_t* out_rgb_u8, float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
-                     uint32_t* records, void* workspace, void* stream, const RbSceneCall* scene) {
+                     uint32_t* records, void* workspace, void* stream, const RbSceneCall* scene,
+                     const RbPoseCall* posed = nullptr) {
   if (!meshes || n_meshes < 1 || n_meshes > PXT_MESH_BATCH_MAX_MESHES) return PXT_E_ARG;
   int32_t n_triangles[PXT_MESH_BATCH_MAX_MESHES];
   for (int m = 0; m < n_meshes; ++m) n_triangles[m] = meshes[m].n_triangles;
@@ -1486,6 +1533,19 @@ static int rb_render(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_
   bool any_plane = false;
   int64_t scene_tiles = 1;
   if (scene && !rb_place_scenes(*scene, n_views, table, views, scenes, &any_plane, &scene_tiles)) return PXT_E_ARG;
+  RbPoseTable poses = {};
+  bool any_posed = false;
+  if (posed) {
+    if (!posed->view_pose || ((uintptr_t)posed->views_out % 4) != 0) return PXT_E_ARG;
+    for (int p = 0; p < n_views; ++p) {
+      const pxt_mesh_view_pose& q = posed->view_pose[p];
+      if (!q.pose_record) continue;
+      if (((uintptr_t)q.pose_record % 4) != 0 || !std::isfinite(q.radius) || q.radius < 0.0) return PXT_E_ARG;
+      poses.record[p] = q.pose_record;
+      poses.radius[p] = q.radius;
+      any_posed = true;
+    }
+  }
   // every argument is checked: from here on the call writes
   hipStream_t s = (hipStream_t)stream;
   static thread_local RbStageSlot stage[kRbStageDevices][kRbStageSlots];
@@ -1523,6 +1583,11 @@ static int rb_render(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_
   const RbRecord* rec = (const RbRecord*)(ws + l.record_off);  // the first member of an RbSceneRecord
   PXT_HIP_CHECK(hipMemcpyAsync(ws + l.record_off, slot.host, record_bytes, hipMemcpyHostToDevice, s));
   PXT_HIP_CHECK(hipEventRecord(slot.copied, s));
+  if (any_posed) {  // behind the upload, ahead of every launch that reads the views' floats
+    hipLaunchKernelGGL(rb_pose_kernel, dim3(1), dim3(64), 0, s, (float*)(ws + l.record_off + offsetof(RbRecord, views)),
+                       poses, posed->views_out, (int)n_views);
+    PXT_HIP_CHECK(hipGetLastError());
+  }
   RbArgs b;
   b.keys = (unsigned long long*)ws;
   b.list_count = (unsigned*)(ws + l.count_off);
@@ -1561,6 +1626,17 @@ extern "C" int pxt_mesh_render_frame_batch(const pxt_mesh_desc* meshes, int32_t 
                                            uint32_t* records, void* workspace, void* stream) {
   return rb_render(meshes, n_meshes, view_mesh, views, n_views, geometry, out_offsets, out_rgba, out_rgb_u8, out_depth,
                    out_depth_nz, out_bytes, records, workspace, stream, nullptr);
+}
+
+extern "C" int pxt_mesh_render_frame_batch_posed(const pxt_mesh_desc* meshes, int32_t n_meshes, const int32_t* view_mesh,
+                                                 const float* views, int32_t n_views, const int32_t* geometry,
+                                                 const int64_t* out_offsets, float* out_rgba, uint8_t* out_rgb_u8,
+                                                 float* out_depth, uint8_t* out_depth_nz, const int64_t* out_bytes,
+                                                 uint32_t* records, void* workspace, const pxt_mesh_view_pose* view_pose,
+                                                 float* views_out, void* stream) {
+  const RbPoseCall posed = {view_pose, views_out};
+  return rb_render(meshes, n_meshes, view_mesh, views, n_views, geometry, out_offsets, out_rgba, out_rgb_u8, out_depth,
+                   out_depth_nz, out_bytes, records, workspace, stream, nullptr, &posed);
 }
 
 extern "C" int64_t pxt_mesh_render_scene_batch_workspace_bytes(int32_t n_meshes, const int32_t* n_triangles, int32_t n_views,

@@ -29,6 +29,10 @@ from one call (``mesh_template.py``).
 Several meshes' frames in one call (``render_frame_batch``, ``frame_batch_reference``, pxt_mesh_render_frame_batch), and
 with ``scenes=`` the objects of one image hiding each other (``scene_reference``, pxt_mesh_render_scene_batch): per view
 of a scene the pixels where another member has the smaller z bits in the call's own key planes, grown by a box.
+
+Views whose pose is still on its way (``render_frame_batch(poses=)``, ``posed_view_reference``,
+pxt_mesh_render_frame_batch_posed): the batch call with one small launch ahead of it that forms the views' records on the
+device from the output record of an LM launch queued before it - render-ahead for mesh templates.
 """
 from __future__ import annotations
 
@@ -829,8 +833,30 @@ def _scene_plan(shapes, plan, scenes):
     return out
 
 
+VIEW_OUT = _lib.PXT_MESH_VIEW_OUT
+W_VIEW_DONE = 20  # views_out's completion word
+
+
+def posed_view_reference(pose_record, view20_host, radius) -> Tuple[np.ndarray, float]:
+    """The rule of pxt_mesh_render_frame_batch_posed for one posed view: ``pose_record`` = the >= 16 floats of an LM
+    output record ([0..11] the pose, [12] failed, [13] status), ``view20_host`` = the host floats of the view (fx fy cx
+    cy near at [12..16] and [18..19] are taken), ``radius`` = the mesh's -> (the 20 float32 the view is drawn with, the
+    completion word 1.0 / -1.0).  The pose is a bit copy; ``depth_q = 1 / (sqrt((t0 t0 + t1 t1) + t2 t2) + radius)``,
+    every step one float64 operation in that order, rounded to float32 once.  The kernel's oracle: no tolerance."""
+    rec = pose_record.detach().cpu().numpy() if torch.is_tensor(pose_record) else np.asarray(pose_record)
+    rec = np.ascontiguousarray(rec, np.float32).reshape(-1)
+    if rec.shape[0] < 16:
+        raise ValueError(f"an LM output record holds >= 16 floats (got {rec.shape[0]})")
+    v = np.array(np.asarray(view20_host, np.float32).reshape(VIEW), np.float32)
+    v[:12] = rec[:12]
+    t0, t1, t2 = (np.float64(x) for x in rec[9:12])
+    with np.errstate(all="ignore"):
+        v[17] = np.float32(np.float64(1.0) / (np.sqrt((t0 * t0 + t1 * t1) + t2 * t2) + np.float64(radius)))
+    return v, 1.0 if rec[12] == 0 and rec[13] == 0 else -1.0
+
+
 def render_frame_batch(items, workspace: Optional[FrameBatchWorkspace] = None, download_records: bool = True,
-                       scenes=None, r_grow: int = 0) -> list:
+                       scenes=None, r_grow: int = 0, poses=None, views_out: Optional[torch.Tensor] = None) -> list:
     """``MeshRenderer.render_frame`` for several meshes in one chain of launches
     (``torch.ops.pixtrack.mesh_render_frame_batch``): ``items`` = ``[(MeshRenderer, requests)]``, the requests as
     ``render_frame`` takes them -> one list of dicts per item, each dict what ``render_frame`` returns for that request,
@@ -843,10 +869,29 @@ def render_frame_batch(items, workspace: Optional[FrameBatchWorkspace] = None, d
     [H, W]: where another member of the scene lies in front, grown by the ``(2 r_grow + 1)^2`` box) and record words 10
     and 11 (hidden pixels, occluder pixels) - ``torch.ops.pixtrack.mesh_render_scene_batch``, one more launch,
     ``scene_reference`` bit for bit.  A scene that the 16-mesh / 32-view limits would split across two calls is a
-    ``PxtError``: an incomplete scene is not drawn."""
+    ``PxtError``: an incomplete scene is not drawn.
+
+    ``poses`` (per item, per request ``None`` or ``(record, radius)``; None: exactly the call above): a request with a
+    record takes its pose ON THE DEVICE from that float32 LM output record (device or pinned host memory, written by a
+    launch queued ahead on this stream) and ``depth_q`` from the pose and ``radius`` - ``posed_view_reference``,
+    ``torch.ops.pixtrack.mesh_render_frame_batch_posed``, one small launch more; the pose floats and ``depth_q`` of
+    its host view record are ignored.  ``views_out``: float32 [all views, 24], device or pinned host - per posed view
+    the 20 floats it was drawn with and the completion word (``W_VIEW_DONE``); rows in request order.  Not with
+    ``scenes``."""
     items = [(r, list(requests)) for r, requests in items]
     if not items:
         return []
+    if poses is None and views_out is not None:
+        raise _lib.PxtError("render_frame_batch: views_out goes with poses")
+    if poses is not None:
+        if scenes is not None:
+            raise _lib.PxtError("render_frame_batch: poses and scenes do not combine (a scene is not drawn ahead)")
+        poses = [list(q) for q in poses]
+        if [len(q) for q in poses] != [len(requests) for _, requests in items]:
+            raise _lib.PxtError("render_frame_batch: poses holds None or (record, radius) per item and request")
+        n_all = sum(len(q) for q in poses)
+        if views_out is not None and tuple(views_out.shape) != (n_all, VIEW_OUT):
+            raise _lib.PxtError(f"render_frame_batch: views_out is float32 [{n_all}, {VIEW_OUT}] (got {tuple(views_out.shape)})")
     device = items[0][0].device
     reqs = []
     for r, requests in items:
@@ -887,7 +932,14 @@ def render_frame_batch(items, workspace: Optional[FrameBatchWorkspace] = None, d
         meshes = ([r.vertices for r in part], [r.triangles for r in part], [r.colors for r in part], [r.uvs for r in part],
                   [r.triangle_uvs for r in part], [r.texture for r in part])
         occluder, occ_offsets = None, None
-        if scene_plan is None:
+        if poses is not None:
+            flat = [q for qs in poses[a:a + n] for q in qs]
+            row = sum(len(qs) for qs in poses[:a])
+            ops.mesh_render_frame_batch_posed(
+                *meshes, view_mesh, views, geometry, offsets, [None if q is None else q[0] for q in flat],
+                [0.0 if q is None else float(q[1]) for q in flat], *bufs, records, ws,
+                None if views_out is None else views_out[row:row + len(flat)])
+        elif scene_plan is None:
             ops.mesh_render_frame_batch(*meshes, view_mesh, views, geometry, offsets, *bufs, records, ws)
         else:
             view_scene, occ_offsets, occ_bytes, _ = scene_plan[c]

@@ -26,7 +26,7 @@ class MeshTemplate:
     """``renderer``: a ``MeshRenderer`` with vertex colours or a texture map.  ``near``: the near plane of the view
     records (a triangle with a vertex at or behind it is culled whole, as in pxt_mesh_raster)."""
 
-    def __init__(self, renderer: R.MeshRenderer, supersample: int = 2, near: float = 1e-6):
+    def __init__(self, renderer: R.MeshRenderer, supersample: int = 2, near: float = 1e-6, render_ahead: bool = False):
         if int(supersample) not in (1, 2, 4):
             raise ValueError(f"supersample is 1, 2 or 4 (got {supersample})")
         if renderer.colors is None and renderer.texture is None:
@@ -34,25 +34,27 @@ class MeshTemplate:
         self.renderer = renderer
         self.supersample = int(supersample)
         self.near = float(near)
+        # opt-in: a tracker queues the next frame's views behind this frame's LM launch (frames_ahead)
+        self.render_ahead = bool(render_ahead)
         # the farthest a vertex lies from the mesh frame's origin: bounds a frame's depths, see depth_q
         self.radius = float(np.linalg.norm(renderer.vertices_host.astype(np.float64), axis=1).max())
 
     @classmethod
     def from_files(cls, mesh, texture=None, mesh_scale: float = 1.0, device="cuda:0", supersample: int = 2,
-                   near: float = 1e-6) -> "MeshTemplate":
+                   near: float = 1e-6, render_ahead: bool = False) -> "MeshTemplate":
         """A mesh file as ``mesh_dataset`` reads it: vertex colours (``read_mesh_colors``) or, without them, texture
         coordinates and a map (``read_mesh_textured``; ``texture`` names another image for the same UVs)."""
         V, F, C = R.read_mesh_colors(mesh)
         if C is not None:
             if texture:
                 raise ValueError(f"{mesh} has vertex colours; a texture goes with a mesh that has texture coordinates")
-            return cls(R.MeshRenderer(V * float(mesh_scale), F, device, colors=C), supersample, near)
+            return cls(R.MeshRenderer(V * float(mesh_scale), F, device, colors=C), supersample, near, render_ahead)
         textured = R.read_mesh_textured(mesh, require_image=texture is None)
         if textured is None:
             raise ValueError(f"{mesh} has no vertex colours and no texture coordinates")
         V, F, uvs, triangle_uvs, image = textured
         return cls(R.MeshRenderer(V * float(mesh_scale), F, device, uvs=uvs, triangle_uvs=triangle_uvs,
-                                  texture=R.read_texture(texture or image)), supersample, near)
+                                  texture=R.read_texture(texture or image)), supersample, near, render_ahead)
 
     def depth_q(self, pose) -> float:
         """The factor on a frame's depths: 1 / (the origin's distance + the mesh's radius), so that every depth d lies in
@@ -78,6 +80,23 @@ class MeshTemplate:
         if self.supersample == 1 and self._same_view(query_camera, reference_camera):
             return [(vq, *size(query_camera), 1, depth_outputs + ("rgb_u8",))]
         return [(vq, *size(query_camera), 1, depth_outputs), (vr, *size(reference_camera), self.supersample, ("rgb_u8",))]
+
+    def requests_ahead(self, query_camera: Camera, reference_camera: Camera, want_depth: bool = False) -> list:
+        """The requests of ``requests`` for a frame whose pose is not known on the host yet: the same views, sizes,
+        supersample and outputs, each with a pose-free view record - intrinsics and near filled, the pose and
+        ``depth_q`` zero (pxt_mesh_render_frame_batch_posed takes those from the LM's output record on the device)."""
+        size = lambda cam: tuple(int(round(float(x))) for x in cam.size.tolist())
+
+        def record(cam):
+            v = R.view_record(cam, np.eye(4), self.near, 0.0)
+            v[:12] = 0.0
+            return v
+
+        depth_outputs = ("depth_nz", "depth") if want_depth else ("depth_nz",)
+        if self.supersample == 1 and self._same_view(query_camera, reference_camera):
+            return [(record(query_camera), *size(query_camera), 1, depth_outputs + ("rgb_u8",))]
+        return [(record(query_camera), *size(query_camera), 1, depth_outputs),
+                (record(reference_camera), *size(reference_camera), self.supersample, ("rgb_u8",))]
 
     def frame(self, pose, query_camera: Camera, reference_camera: Camera, want_depth: bool = False, requests=None):
         """-> ``(depth_nz uint8 [Hq, Wq], rgb_u8 uint8 [Hr, Wr, 3])`` device tensors at ``pose`` (world -> camera, a
@@ -124,3 +143,24 @@ class MeshTemplate:
         outs = R.render_frame_batch(items, workspace=workspace, download_records=False, scenes=view_scenes, r_grow=r_grow)
         return [(out[0]["depth_nz"], out[-1]["rgb_u8"], out[0].get("occluder")) + ((out[0]["records"],) if records else ())
                 + tail(out, q) for out, q in zip(outs, reqs)]
+
+    @staticmethod
+    def frames_ahead(templates, pose_records, query_cameras, reference_cameras, workspace, views_out, want_depth=None,
+                     requests=None) -> list:
+        """``frames`` for poses that are still on their way: template k's views take their pose on the device from
+        ``pose_records[k]`` - the float32 output record of the LM launch queued ahead on this stream (device or pinned
+        host memory) - and ``depth_q`` from that pose and the template's radius (``mesh_render.posed_view_reference``).
+        ONE ``mesh_render.render_frame_batch(poses=)`` call (split only by the 16-mesh / 32-view limits); the query and
+        the reference view of a template share its record.  ``views_out``: float32 [all views, 24], pinned host or device
+        - per view, in request order, the 20 floats it was drawn with and the completion word (1.0: the refinement
+        succeeded, -1.0: it did not; stored last): the caller compares them with its own ``view_record`` once it knows the
+        pose and keeps the planes only if they are the same bits.  ``requests``: per template what ``requests_ahead``
+        returned.  -> ``[(depth_nz, rgb_u8)]``, with ``want_depth`` ``[(depth_nz, rgb_u8, depth or None)]``."""
+        want = [False] * len(templates) if want_depth is None else [bool(d) for d in want_depth]
+        if requests is None:
+            requests = [t.requests_ahead(qc, rc, d) for t, qc, rc, d in zip(templates, query_cameras, reference_cameras, want)]
+        items = [(t.renderer, q) for t, q in zip(templates, requests)]
+        poses = [[(rec, t.radius)] * len(q) for t, rec, q in zip(templates, pose_records, requests)]
+        outs = R.render_frame_batch(items, workspace=workspace, download_records=False, poses=poses, views_out=views_out)
+        tail = lambda out, q: () if want_depth is None else (out[0].get("depth"),)
+        return [(out[0]["depth_nz"], out[-1]["rgb_u8"]) + tail(out, q) for out, q in zip(outs, requests)]

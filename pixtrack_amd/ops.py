@@ -39,6 +39,9 @@ Reference call sites the ops stand in for:
   mesh_render_scene_batch  (opt-in, no reference counterpart) mesh_render_frame_batch for objects that share an image:
                        per view also the pixels where another tracked mesh of its scene lies in front, grown
   mask_exclude         (opt-in, no reference counterpart) a mask minus such an occluder plane
+  mesh_render_frame_batch_posed  (opt-in, no reference counterpart) mesh_render_frame_batch whose views take their pose
+                       on the device from the record of an lm_refine launch queued ahead of it (render-ahead for mesh
+                       templates)
 
 All ops are out-variants (they write into tensors the caller allocated and mutate nothing else), so
 the caller decides buffer reuse.  Context handles (``pxt_unet*`` / ``pxt_ngp*``) travel as ints.
@@ -48,6 +51,7 @@ CPU tensors fails in the dispatcher, and a missing library raises ``PxtError`` a
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Sequence
 
 import torch
@@ -234,6 +238,18 @@ SCHEMAS = {
         "(Tensor[] vertices, Tensor[] triangles, Tensor?[] colors, Tensor?[] uvs, Tensor?[] triangle_uvs, "
         "Tensor?[] texture, int[] view_mesh, Tensor views, int[] geometry, int[] offsets, Tensor(a!)? rgba, "
         "Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, Tensor(e!) records, Tensor(f!) workspace) -> ()"),
+    # mesh_render_frame_batch whose views take their pose on the device (pxt_mesh_render_frame_batch_posed):
+    # pose_records = per view None (the view is drawn from its 20 host floats) or the float32 output record of an LM
+    # launch queued ahead on the same stream (>= 16 floats, device or pinned host memory: [0..11] the pose, [12] failed,
+    # [13] status); radii = per view the mesh's radius (depth_q = 1 / (|t| + radius), ignored for an un-posed view);
+    # views_out: None or float32 [P, 24], device or pinned host - the floats each posed view was drawn with and, stored
+    # last, word 20 = 1.0 (the refinement succeeded) or -1.0.  Everything else as mesh_render_frame_batch, workspace
+    # included
+    "mesh_render_frame_batch_posed": (
+        "(Tensor[] vertices, Tensor[] triangles, Tensor?[] colors, Tensor?[] uvs, Tensor?[] triangle_uvs, "
+        "Tensor?[] texture, int[] view_mesh, Tensor views, int[] geometry, int[] offsets, Tensor?[] pose_records, "
+        "float[] radii, Tensor(a!)? rgba, Tensor(b!)? rgb_u8, Tensor(c!)? depth, Tensor(d!)? depth_nz, "
+        "Tensor(e!) records, Tensor(f!) workspace, Tensor(g!)? views_out) -> ()"),
     # mesh_render_frame_batch for objects that share an image (pxt_mesh_render_scene_batch): view_scene = the scene of
     # each view (-1: none; the views of one scene are one camera, supersample 1), occluder_offsets = the byte offset of
     # each view's uint8 [H, W] plane in the flat buffer occluder (a multiple of 4; -1: the view wants none) -> where
@@ -1687,9 +1703,47 @@ def _mesh_render_scene_batch(vertices, triangles, colors, uvs, triangle_uvs, tex
                      (view_scene, r_grow, occluder_offsets, occluder))
 
 
+def _mesh_render_frame_batch_posed(vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh, views, geometry,
+                                   offsets, pose_records, radii, rgba, rgb_u8, depth, depth_nz, records, workspace,
+                                   views_out):
+    _mesh_batch_call("mesh_render_frame_batch_posed", vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh,
+                     views, geometry, offsets, rgba, rgb_u8, depth, depth_nz, records, workspace, None,
+                     (pose_records, radii, views_out))
+
+
+def mesh_view_poses(pose_records, radii, views_out, P, device, what="mesh_render_frame_batch_posed"):
+    """The checks of mesh_render_frame_batch_posed's own arguments -> the ``pxt_mesh_view_pose`` array.  A record or
+    ``views_out`` is memory the kernel dereferences: of ``device``, or pinned host memory."""
+    def reachable(t, name):
+        if not (t.is_cuda and t.device == device) and not (not t.is_cuda and t.is_pinned()):
+            raise _lib.PxtError(f"{what}: {name} is memory of {device} or pinned host memory (got {t.device}, unpinned)")
+    if len(pose_records) != P or len(radii) != P:
+        raise _lib.PxtError(f"{what}: pose_records and radii hold one entry per view ({P}; got {len(pose_records)}, "
+                            f"{len(radii)})")
+    table = (_lib.MeshViewPose * P)()
+    for p, (rec, radius) in enumerate(zip(pose_records, radii)):
+        if rec is None:
+            continue
+        _f32c(rec, f"pose_records[{p}]")
+        if rec.numel() < 16:
+            raise _lib.PxtError(f"{what}: pose_records[{p}] holds {rec.numel()} floats, an LM output record has >= 16")
+        reachable(rec, f"pose_records[{p}]")
+        radius = float(radius)
+        if not (math.isfinite(radius) and radius >= 0.0):
+            raise _lib.PxtError(f"{what}: view {p}'s radius is finite and >= 0 (got {radius})")
+        table[p].pose_record, table[p].radius = rec.data_ptr(), radius
+    if views_out is not None:
+        _f32c(views_out, "views_out")
+        if tuple(views_out.shape) != (P, _lib.PXT_MESH_VIEW_OUT):
+            raise _lib.PxtError(f"{what}: views_out is float32 [{P}, {_lib.PXT_MESH_VIEW_OUT}] (got {tuple(views_out.shape)})")
+        reachable(views_out, "views_out")
+    return table
+
+
 def _mesh_batch_call(what, vertices, triangles, colors, uvs, triangle_uvs, texture, view_mesh, views, geometry, offsets,
-                     rgba, rgb_u8, depth, depth_nz, records, workspace, scene):
-    """The two batch ops: ``scene`` = (view_scene, r_grow, occluder_offsets, occluder) for mesh_render_scene_batch."""
+                     rgba, rgb_u8, depth, depth_nz, records, workspace, scene, posed=None):
+    """The batch ops: ``scene`` = (view_scene, r_grow, occluder_offsets, occluder) for mesh_render_scene_batch,
+    ``posed`` = (pose_records, radii, views_out) for mesh_render_frame_batch_posed."""
     L = _lib.lib()
     M = len(vertices)
     if not all(len(x) == M for x in (triangles, colors, uvs, triangle_uvs, texture)):
@@ -1759,6 +1813,14 @@ def _mesh_batch_call(what, vertices, triangles, colors, uvs, triangle_uvs, textu
         _lib.require_gpu(t, name)
         if t.device != device:
             raise _lib.PxtError(f"{what}: {name} is on {t.device}, vertices[0] on {device}")
+    if posed is not None:
+        pose_records, radii, views_out = posed
+        table = mesh_view_poses(pose_records, radii, views_out, P, device, what)
+        _lib.check(L.pxt_mesh_render_frame_batch_posed(
+            descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
+            _lib.dptr(depth_nz), cap, records.data_ptr(), workspace.data_ptr(), table, _lib.dptr(views_out),
+            _stream(vertices[0])), "pxt_mesh_render_frame_batch_posed")
+        return
     if scene is None:
         _lib.check(L.pxt_mesh_render_frame_batch(
             descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
@@ -1774,6 +1836,7 @@ def _mesh_batch_call(what, vertices, triangles, colors, uvs, triangle_uvs, textu
 
 _IMPLS = {
     "mesh_render_frame_batch": _mesh_render_frame_batch,
+    "mesh_render_frame_batch_posed": _mesh_render_frame_batch_posed,
     "mesh_render_scene_batch": _mesh_render_scene_batch,
     "mask_exclude": _mask_exclude,
     "mesh_raster": _mesh_raster,

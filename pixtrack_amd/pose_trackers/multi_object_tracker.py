@@ -23,6 +23,12 @@ methods - and only the device work of a frame step is merged:
   image.  That call then also tells, per object, the pixels where another object of its scene lies in front
   (``pxt_mesh_render_scene_batch``); they leave the object's query mask, and the reference points that project onto them
   leave its LM's point mask.
+* mesh templates built with ``render_ahead=True`` (opt-in): behind the batched LM launch the NEXT frames of the group's
+  mesh trackers are drawn in ONE call whose view records are formed on the device from the LM's output records
+  (``MeshTemplate.frames_ahead``, ``pxt_mesh_render_frame_batch_posed``); the next step's head-of-step call then draws
+  only the trackers whose queued frame was not verified for their pose.  Not with ``mutual_occlusion``: a step's scenes
+  are formed from who takes the lock-step path in that step, so its mesh trackers are not drawn ahead (tracking is
+  unchanged).
 * mesh trackers with ``reference_points="template"`` refine on a lattice of their own frame's depth plane: that call
   then also writes their query views' float depth planes, and ONE ``pxt_points_from_depth_views`` call behind it
   extracts the points of all of them (three launches for the group instead of three per object).
@@ -84,6 +90,8 @@ class _Group:
         self.points_ws: Optional[torch.Tensor] = None  # workspace of the step's pxt_points_from_depth_views call(s)
         self.points_records = None  # pinned [16, 4] records of those calls, recycled round-robin
         self.points_next = 0
+        self.ahead_rows = None  # pinned views_out blocks of the group's MeshTemplate.frames_ahead calls, recycled round-robin
+        self.ahead_next = 0
         self.unet_done: Optional[torch.cuda.Event] = None
         self.pend = None  # what _enqueue left for _finish
 
@@ -186,6 +194,8 @@ class MultiObjectTracker:
         self.steps = 0
         self.solo_frames = 0       # frames that ran through run_single_frame (cold starts, several references)
         self.lockstep_frames = 0
+        self.mesh_prime_calls = 0  # MeshTemplate.frames calls made at the head of a step (one per group that needs one)
+        self.mesh_ahead_calls = 0  # MeshTemplate.frames_ahead calls queued behind a step's LM launch (one per group)
         self.points_calls = 0      # pxt_points_from_depth_views calls made for "template" trackers (one per group and step)
         self.timing = None         # set to {} to collect HIP-event pairs per phase (bench.py's untimed diagnostic pass)
 
@@ -344,6 +354,9 @@ class MultiObjectTracker:
                 self.solo_frames += 1
                 continue
             tr._frame_setup(frame, lockstep=True)
+            if self.mutual_occlusion is not None and tr.template is not None:
+                # (a step's scenes are formed from who takes the lock-step path in THAT step: not drawn ahead)
+                tr.localizer.refiner.after_lm_enqueued = None
             ref_u8 = tr.get_reference_image(tr.pose)
             tr._fused_reference = (tr.pose, ref_u8)  # get_dynamic_id asks for it again: the same tensor object
             live.append((k, tr, frame, ref_u8))
@@ -401,6 +414,7 @@ class MultiObjectTracker:
         grp.pend = [(k, tr, path, ref_id, dbg, status, x, next(it) if status == "lm" else None)
                     for (k, tr, path, ref_id, dbg, status, x) in pend]
         batched = self._batched_renders_ahead(grp) if self.batch_renders else set()
+        batched |= self._mesh_frames_ahead(grp)
         for k, tr, path, ref_id, dbg, status, x, handle in grp.pend:
             hook = getattr(tr.localizer.refiner, "after_lm_enqueued", None)
             if handle is not None and hook is not None and k not in batched:
@@ -444,8 +458,16 @@ class MultiObjectTracker:
         its reference image: it rides along with the same requests and drops its depth_nz plane.)"""
         part = [self.trackers[k] for k in grp.members
                 if self.trackers[k].template is not None and self._takes_lockstep(self.trackers[k], frames[k])]
-        if not part:  # (NeRF trackers only: nothing of the mesh path is touched)
+        # a tracker whose frame was drawn ahead, behind the last step's LM launch, and verified for its pose keeps that
+        # frame (its get_mask takes it); with "template" points its plane still joins the step's one points call
+        ahead = [tr for tr in part if self._served_ahead(tr)]
+        part = [tr for tr in part if not any(tr is a for a in ahead)]
+        ahead_points = [(tr, *tr._ahead_ok[4]) for tr in ahead if tr.reference_points == "template" and tr._ahead_ok[4] is not None]
+        if not part:  # (NeRF trackers only: nothing of the mesh path is touched; or every mesh frame was drawn ahead)
+            if ahead_points:
+                self._prime_template_points(grp, ahead_points)
             return
+        self.mesh_prime_calls += 1
         from ..mesh_render import FrameBatchWorkspace
         from ..mesh_template import MeshTemplate
 
@@ -459,9 +481,11 @@ class MultiObjectTracker:
             planes = MeshTemplate.frames(*views, workspace=grp.mesh_ws, want_depth=want_depth)
             for tr, (nz, ref_u8, _depth, _view) in zip(part, planes):
                 tr._primed_frame = (tr.pose, nz, ref_u8)
-            self._prime_template_points(grp, [(tr, depth, view) for tr, (_nz, _ref, depth, view) in zip(part, planes)
-                                              if depth is not None])
+            self._prime_template_points(grp, ahead_points + [(tr, depth, view) for tr, (_nz, _ref, depth, view)
+                                                             in zip(part, planes) if depth is not None])
             return
+        if ahead_points:
+            self._prime_template_points(grp, ahead_points)
         if scenes is None:  # (also: no scene has two members in this step - the call is the one made without the option)
             for tr, (nz, ref_u8) in zip(part, MeshTemplate.frames(*views, workspace=grp.mesh_ws)):
                 tr._primed_frame = (tr.pose, nz, ref_u8)
@@ -470,6 +494,49 @@ class MultiObjectTracker:
                                      records=True)
         for tr, (nz, ref_u8, occluder, record) in zip(part, planes):
             tr._primed_frame = (tr.pose, nz, ref_u8, None if occluder is None else (occluder, record))
+
+    @staticmethod
+    def _served_ahead(tr) -> bool:
+        """The tracker holds a frame that was drawn ahead and verified for its present pose and view settings (what its
+        get_mask will take this step)."""
+        ok = tr._ahead_ok
+        return bool(tr.success and ok is not None and ok[0] is tr.pose and ok[3] == tr._ahead_views_now())
+
+    def _mesh_frames_ahead(self, grp: _Group) -> set:
+        """The next frames of the group's mesh trackers whose hook is the mesh render-ahead, behind the batched LM launch
+        in ONE MeshTemplate.frames_ahead call on the group's stream and workspace (more than 16 meshes or 32 views: in
+        consecutive calls); every view takes its pose on the device from its tracker's LM record.  Returns the members
+        served."""
+        items = []
+        for k, tr, path, ref_id, dbg, status, x, handle in grp.pend:
+            hook = getattr(tr.localizer.refiner, "after_lm_enqueued", None)
+            if handle is not None and hook is not None and getattr(hook, "__func__", None) is PixLocPoseTrackerR9._render_ahead_mesh:
+                items.append((k, tr, handle, *tr._render_ahead_mesh_request()))
+        if not items:
+            return set()
+        from ..mesh_render import VIEW_OUT, W_VIEW_DONE, FrameBatchWorkspace
+        from ..mesh_template import MeshTemplate
+
+        if grp.mesh_ws is None:
+            grp.mesh_ws = FrameBatchWorkspace()
+        n_views = sum(len(requests) for _k, _tr, _h, requests, _d, _keys in items)
+        if grp.ahead_rows is None or grp.ahead_rows[0].shape[0] < n_views:
+            # the kernel receives the raw pointer: the blocks live as long as the group and are recycled - a step's rows
+            # are read at that step's end
+            grp.ahead_rows = [torch.zeros(max(64, n_views), VIEW_OUT, dtype=torch.float32).pin_memory() for _ in range(8)]
+        rows = grp.ahead_rows[grp.ahead_next][:n_views]
+        grp.ahead_next = (grp.ahead_next + 1) % len(grp.ahead_rows)
+        rows[:, W_VIEW_DONE] = 0.0
+        planes = MeshTemplate.frames_ahead([tr.template for _k, tr, *_ in items], [h.buf for _k, _tr, h, *_ in items],
+                                           [tr.camera for _k, tr, *_ in items], [tr._reference_camera() for _k, tr, *_ in items],
+                                           grp.mesh_ws, rows, want_depth=[d for *_, d, _keys in items],
+                                           requests=[requests for _k, _tr, _h, requests, _d, _keys in items])
+        self.mesh_ahead_calls += 1
+        first = 0
+        for (k, tr, _h, requests, _d, keys), out in zip(items, planes):
+            tr._render_ahead_mesh_accept(rows[first:first + len(requests)], out if out[-1] is not None else out[:2], keys)
+            first += len(requests)
+        return {k for k, *_ in items}
 
     def _prime_template_points(self, grp: _Group, items) -> None:
         """``items`` = [(tracker, depth plane, view record)] of the group's "template" trackers in this step: their
@@ -643,6 +710,9 @@ def build_parser():
     ap.add_argument("--mesh_scale", type=float, nargs="+", default=[1.0], help="factor on each mesh's vertices")
     ap.add_argument("--mesh_supersample", type=int, nargs="+", choices=(1, 2, 4), default=[2],
                     help="samples per pixel and axis of each mesh template's reference image (default 2, untuned)")
+    ap.add_argument("--mesh_render_ahead", action="store_true",
+                    help="--template mesh: draw every object's next frame in one call queued behind the step's LM launch "
+                         "(default: off; not with --mutual_occlusion, whose scenes are drawn at the head of a step)")
     ap.add_argument("--reference_sfm", type=Path, nargs="+", default=None,
                     help="each object's SfM model directory (the ref/ directory mesh_dataset wrote)")
     ap.add_argument("--reference_points", choices=("sfm", "template"), default="sfm",
@@ -718,7 +788,8 @@ def main(argv=None):
             one = argparse.Namespace(template=args.template, mesh=_per_object(args.mesh, k, K, "--mesh"),
                                      texture=_per_object(args.texture, k, K, "--texture"),
                                      mesh_scale=_per_object(args.mesh_scale, k, K, "--mesh_scale"),
-                                     mesh_supersample=_per_object(args.mesh_supersample, k, K, "--mesh_supersample"))
+                                     mesh_supersample=_per_object(args.mesh_supersample, k, K, "--mesh_supersample"),
+                                     mesh_render_ahead=args.mesh_render_ahead)
             template = template_from_args(one)
             reference_sfm = _per_object(args.reference_sfm, k, K, "--reference_sfm")
         except ValueError as e:

@@ -114,7 +114,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         by the template's ``supersample``, both from one pxt_mesh_render_frame call.  The SfM model is then one
         mesh_dataset built from that mesh (it is in the mesh's own frame), no snapshot, ``nerf2sfm.pkl`` or $OBJ_AABB is
         read (``assets`` may omit ``snapshot``, ``nerf2sfm`` and ``aabb``), ``testbed`` is None and ``render_ahead`` is
-        off: the queued render takes its camera from a NeRF camera slot.  Everything downstream of the two images is
+        the template's own option, off by default: with ``MeshTemplate(..., render_ahead=True)`` the next frame's views
+        are ONE posed call queued behind the LM launch, their view records formed on the device from the LM's output
+        record (pxt_mesh_render_frame_batch_posed), and used only if the host arrives at the same 20 floats per view.
+        Everything downstream of the two images is
         unchanged.  A frame's history gains ``template`` ("mesh") and ``template_supersample``; nothing on the policy
         path reads them.  Not combined with ``relocalizer``, ``reference_points="render"`` (its mesh counterpart is
         ``reference_points="template"``), ``depth_refine`` or ``occlusion`` yet (ValueError).
@@ -213,7 +216,12 @@ class PixLocPoseTrackerR9(PoseTracker):
         # after the host has read the result, run the policy and converted the pose (~0.1 ms of GPU idle per frame).  They
         # are consumed only if the host, once it knows the pose, arrives at the same 12 camera floats; otherwise (failed
         # frame, cost gate, relocalisation, a different last bit) the frame renders as before.  PXT_RENDER_AHEAD=0: off.
-        self.render_ahead = os.environ.get("PXT_RENDER_AHEAD", "1") != "0" and self.template is None
+        # With a mesh template the option is the template's (MeshTemplate(render_ahead=True), off by default): the frame's
+        # views are ONE posed call (pxt_mesh_render_frame_batch_posed) whose view records are formed on the device from the
+        # LM's output record, and the host compares the 20 floats of every view it was drawn with.
+        self.render_ahead = self._render_ahead_default(self.template)
+        self._ahead_ws = None         # mesh template: the FrameBatchWorkspace of the queued calls (this tracker's stream)
+        self._ahead_rows, self._ahead_row_next = None, 0  # ... and the ring of pinned views_out blocks
         self._ahead_cam = None   # the pinned camera record the LM epilogue of this frame writes
         self._ahead = None       # the render queued behind the last LM launch
         self._ahead_ok = None    # ... once verified: (pose object it is valid for, mask, uint8 reference image, views, depth)
@@ -271,6 +279,12 @@ class PixLocPoseTrackerR9(PoseTracker):
 
     # ------------------------------------------------------------------ per-variant set-up
     supports_render_points = True  # (the YCB policy does not yet)
+
+    @staticmethod
+    def _render_ahead_default(template) -> bool:
+        """``render_ahead`` as the constructor sets it: on for the NeRF template, a mesh template's own option for a mesh
+        template (off unless it was built with render_ahead=True); PXT_RENDER_AHEAD=0 switches both off."""
+        return os.environ.get("PXT_RENDER_AHEAD", "1") != "0" and (template is None or bool(template.render_ahead))
 
     def _check_reference_points(self, reference_points, relocalizer, uncertainty):
         if reference_points not in ("sfm", "render", "template"):
@@ -719,8 +733,12 @@ class PixLocPoseTrackerR9(PoseTracker):
             # when it was enqueued: it stands in for this frame's render only if they are what this frame would use)
             if views == self._ahead_views_now():
                 self._fused_reference = (pose, ref_u8)
-                self._fused_depth = (pose, depth) if (depth is not None and self.reference_points == "render") else None
                 self.renders_ahead_used += 1
+                if self.template is not None:  # depth = (the query view's depth plane, the host's bit-equal view record)
+                    self._fused_depth = (pose, *depth) if (depth is not None and self.reference_points == "template") else None
+                    self._last_depth = None
+                    return mask
+                self._fused_depth = (pose, depth) if (depth is not None and self.reference_points == "render") else None
                 return self._apply_occlusion(mask, depth)
             self.renders_ahead_stale += 1
         self._ahead_ok = None
@@ -819,6 +837,52 @@ class PixLocPoseTrackerR9(PoseTracker):
         mask, ref_u8 = self._mask_and_reference(None, from_slot=True)
         self._ahead = ([self._ahead_cam], mask, ref_u8, views, self._last_depth)
 
+    def _next_views_out(self, n_views: int) -> torch.Tensor:
+        """A pinned [n_views, 24] block for a queued mesh call's views_out, its completion words zeroed.  The kernel gets
+        the raw pointer: the blocks live as long as the tracker and are recycled round-robin (Testbed._next_cam_out's
+        scheme) - one is written per frame and read back at that frame's end."""
+        from ..mesh_render import VIEW_OUT, W_VIEW_DONE
+
+        if self._ahead_rows is None:
+            self._ahead_rows = [torch.zeros(2, VIEW_OUT, dtype=torch.float32).pin_memory() for _ in range(8)]
+        block = self._ahead_rows[self._ahead_row_next]
+        self._ahead_row_next = (self._ahead_row_next + 1) % len(self._ahead_rows)
+        block[:, W_VIEW_DONE] = 0.0
+        return block[:n_views]
+
+    def _render_ahead_mesh_request(self):
+        """The mesh template's queued frame for a caller that draws several trackers' in one call (lock-step tracking,
+        MeshTemplate.frames_ahead): -> (requests, want_depth, the view keys the frame bakes in)."""
+        want_depth = self.reference_points == "template"
+        requests = self.template.requests_ahead(self.camera, self._reference_camera(), want_depth)
+        return requests, want_depth, self._ahead_view_keys(requests)
+
+    def _render_ahead_mesh_accept(self, rows, planes, keys):
+        """What _render_ahead_mesh() does after its call: ``rows`` = the views_out rows of this tracker's views,
+        ``planes`` = (depth_nz, rgb_u8[, depth])."""
+        depth = planes[2] if len(planes) > 2 else None
+        self._ahead = (rows, self._mask_of(planes[0]), planes[1], keys, depth)
+
+    def _render_ahead_mesh(self, pending):
+        """_render_ahead with a mesh template: ONE posed call on this stream behind the LM launch, whose output record
+        (``pending.buf``) the call's first launch turns into the views' records on the device."""
+        from ..mesh_render import FrameBatchWorkspace
+        from ..mesh_template import MeshTemplate
+
+        if self._ahead_ws is None:
+            self._ahead_ws = FrameBatchWorkspace()
+        requests, want_depth, keys = self._render_ahead_mesh_request()
+        rows = self._next_views_out(len(requests))
+        planes = MeshTemplate.frames_ahead([self.template], [pending.buf], [self.camera], [self._reference_camera()],
+                                           self._ahead_ws, rows, want_depth=[want_depth], requests=[requests])[0]
+        self._render_ahead_mesh_accept(rows, planes, keys)
+
+    def _ahead_view_keys(self, requests):
+        """Per view of a mesh template's frame what a queued call bakes in besides the pose: size, supersample, outputs,
+        fx fy cx cy, near and the renderer."""
+        return [(tuple(float(x) for x in v[12:17]), int(W), int(H), int(S), tuple(want), id(self.template.renderer))
+                for v, W, H, S, want in requests]
+
     def _render_ahead_request(self):
         """For a caller that merges the queued renders of several trackers into one batched chain (lock-step tracking,
         Testbed.render_frame_batch_device): (width, height, spp) of this tracker's one-march mask + reference render with
@@ -837,6 +901,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         """What a render queued now bakes in besides the camera pose, per render of the frame: focal length, lens, render
         box, background, minimum transmittance (floats 12.. of the view record), image size and spp - the keys
         get_mask / get_reference_image would render with right now."""
+        if self.template is not None:
+            return self._render_ahead_mesh_request()[2]
         spp = int(self.spp)
         return [(tuple(self.testbed._view_for(w, h, fov)[12:]), w, h, spp) for w, h, fov in self._frame_views()]
 
@@ -848,6 +914,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         if ahead is None or not success:
             return
         cams, mask, ref_u8, views, depth = ahead
+        if self.template is not None:
+            return self._verify_mesh_render_ahead(cams, mask, ref_u8, views, depth)
         self.testbed.set_nerf_camera_matrix(np.asarray(self._nerf_pose(self.pose))[:3, :])
         want = np.asarray(self.testbed._cam_ngp, np.float32).reshape(-1)
         for cam_out in cams:
@@ -862,6 +930,31 @@ class PixLocPoseTrackerR9(PoseTracker):
                 self.renders_ahead_rejected += 1
                 return
         self._ahead_ok = (self.pose, mask, ref_u8, views, depth)
+
+    def _verify_mesh_render_ahead(self, rows, mask, ref_u8, views, depth):
+        """_verify_render_ahead with a mesh template: every view of the queued call was drawn with the 20 floats the host
+        forms from the accepted pose - ``view_record`` with ``template.depth_q`` - bit for bit, or the planes are not
+        used.  With reference_points="template" the host's query record goes with the depth plane: it is the record the
+        plane was drawn with."""
+        from ..mesh_render import W_VIEW_DONE, view_record
+
+        got = rows.numpy()
+        cameras = [self.camera] if len(views) == 1 else [self.camera, self._reference_camera()]
+        q = self.template.depth_q(self.pose)
+        want_q = None
+        for row, camera in zip(got, cameras):
+            for _ in range(200000):  # the call's first launch runs right behind the LM kernel whose result is already here
+                if row[W_VIEW_DONE] != 0.0:
+                    break
+            else:  # never arrived: the queued frame is dropped (and counted), the frame renders as usual
+                self.renders_ahead_dropped += 1
+                return
+            want = view_record(camera, self.pose, self.template.near, q)
+            if row[W_VIEW_DONE] != 1.0 or not np.array_equal(want.view(np.uint32), row[:20].view(np.uint32)):
+                self.renders_ahead_rejected += 1
+                return
+            want_q = want if want_q is None else want_q
+        self._ahead_ok = (self.pose, mask, ref_u8, views, None if depth is None else (depth, want_q))
 
     # ------------------------------------------------------------------ one frame
     def refine(self, query):
@@ -927,8 +1020,12 @@ class PixLocPoseTrackerR9(PoseTracker):
         steady = (kind != "cold" and self.success and refiner.query_mask is not None
                   and refiner.conf.multiscale == [1] and len(self.reference_ids) == 1)
         self._ahead = None
-        refiner.after_lm_enqueued = self._render_ahead if (self.render_ahead and steady) else None
-        refiner.lm_camera = self._lm_camera if (self.render_ahead and steady) else None
+        # (a mesh template's queued call reads the LM's pose record itself: no camera epilogue.  Objects that hide each
+        # other are drawn as scenes at the head of a step: not ahead)
+        mesh = self.template is not None
+        ahead = self.render_ahead and steady and not (mesh and self.mutual_occlusion)
+        refiner.after_lm_enqueued = (self._render_ahead_mesh if mesh else self._render_ahead) if ahead else None
+        refiner.lm_camera = self._lm_camera if (ahead and not mesh) else None
         # the query computes only its LM's tiles on a steady frame of the staged pair pass, where nothing else reads its
         # fine map: no dense-map log, no relocaliser scoring, none of the opt-ins the refiner itself checks
         refiner.query_tiles = None
@@ -1117,6 +1214,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--mesh_scale", type=float, default=1.0, help="factor on the mesh's vertices (BOP's models are in mm)")
     parser.add_argument("--mesh_supersample", type=int, choices=(1, 2, 4), default=2,
                         help="samples per pixel and axis of the mesh template's reference image (default 2, untuned)")
+    parser.add_argument("--mesh_render_ahead", action="store_true",
+                        help="--template mesh: queue the next frame's mesh views behind this frame's LM launch; their view "
+                             "records are formed on the device from the LM's output record (default: off)")
     parser.add_argument("--reference_sfm", type=Path, default=None,
                         help="the SfM model's directory (the ref/ directory mesh_dataset wrote), in place of "
                              "<object_path>/pixtrack/aug_nerf_sfm/aug_sfm")
@@ -1136,7 +1236,8 @@ def template_from_args(args, device="cuda:0"):
     from ..mesh_template import MeshTemplate
 
     return MeshTemplate.from_files(args.mesh, texture=args.texture, mesh_scale=args.mesh_scale, device=device,
-                                   supersample=args.mesh_supersample)
+                                   supersample=args.mesh_supersample,
+                                   render_ahead=bool(getattr(args, "mesh_render_ahead", False)))
 
 
 def _sensor_lookup_from_args(args, flag: str):

@@ -114,7 +114,9 @@ class PixLocPoseTrackerYCB(PixLocPoseTrackerR9):
             refiner.feature_extractor.unstage()
         # the next frame's mask + reference renders need only this frame's pose: queued behind the LM launch, used next
         # frame if the pose is accepted and the host arrives at the same camera (pixloc_tracker_r9._render_ahead)
-        steady = self.render_ahead and list(refiner.conf.multiscale or [1]) == [1] and len(self.reference_ids) == 1
+        # (a mesh template's render-ahead is PixLocPoseTrackerR9's own frame set-up: not part of this policy)
+        steady = (self.render_ahead and self.template is None and list(refiner.conf.multiscale or [1]) == [1]
+                  and len(self.reference_ids) == 1)
         self._ahead = None
         refiner.after_lm_enqueued = self._render_ahead if steady else None
         refiner.lm_camera = self._lm_camera if steady else None
