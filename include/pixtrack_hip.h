@@ -1110,9 +1110,39 @@ int pxt_depth_refine(const pxt_depth_problem* problems_host, int32_t n_problems,
  *   or written.  One launch of one workgroup on `stream`, counts by population count, no atomics, no workspace.
  *   Measured on the MI355X: DESIGN.md 3.20.
  * Measured on the MI355X: DESIGN.md 3.13.
+ *
+ * pxt_occlusion_mask_views - 1..PXT_OCCLUSION_MAX_VIEWS image pairs of different sizes in ONE chain of two launches
+ *   (the K mesh objects of one RGB-D frame in lock-step tracking):
+ *   views_host [n_views]: per view the five planes of pxt_occlusion_mask, its size, shift and quanta (host; the table
+ *       travels in the kernel arguments: no upload).  Several views may name ONE sensor image (and one depth plane or
+ *       one mask_in).  min_alpha, r_open, r_grow hold for the whole call.
+ *   records [n_views][PXT_OCCLUSION_RECORD] int32 (device or pinned host); workspace: device memory of
+ *       pxt_occlusion_mask_views_workspace_bytes(n_views, sizes) bytes, sizes = n_views x (width, height) (< 0: a count
+ *       or a size out of range); one workspace serves one call at a time.
+ *   View k's mask_out, occluder and 16 record words are bit for bit what pxt_occlusion_mask writes for that pair alone,
+ *   whatever k is and whatever the other views are: the tile grids of the views are concatenated, a workgroup runs the
+ *   single call's tile on its view's own tile, and one wave per view folds the view's partials in the single call's
+ *   order.  No atomics.
+ *   Bounds: those of pxt_occlusion_mask per view; every mask_out / occluder plane overlaps no other output plane, no
+ *       input plane of any view (a view's mask_out may BE its own mask_in), nor records or workspace; anything else is
+ *       PXT_E_ARG and nothing is launched or written.  Two launches on `stream`, no host synchronisation, no allocation.
  * ---------------------------------------------------------------------- */
 #define PXT_OCCLUSION_RECORD 16
 #define PXT_OCCLUSION_MAX_RADIUS 16
+#define PXT_OCCLUSION_MAX_VIEWS 16
+typedef struct pxt_occlusion_view {
+  const float* depth;     /* [height][width][4] float32, 16-byte aligned */
+  const uint16_t* sensor; /* [height][width] */
+  const uint8_t* mask_in; /* [height][width] */
+  uint8_t* mask_out;      /* [height][width] */
+  uint8_t* occluder;      /* [height][width] */
+  int32_t width, height;
+  int32_t shift_x, shift_y;
+  float sensor_q, delta_q;
+} pxt_occlusion_view;
+int64_t pxt_occlusion_mask_views_workspace_bytes(int32_t n_views, const int32_t* sizes);
+int pxt_occlusion_mask_views(const pxt_occlusion_view* views_host, int32_t n_views, float min_alpha, int32_t r_open,
+                             int32_t r_grow, int32_t* records, void* workspace, void* stream);
 int64_t pxt_occlusion_mask_workspace_bytes(int32_t width, int32_t height);
 int pxt_occlusion_mask(const float* depth, const uint16_t* sensor, const uint8_t* mask_in, int32_t width,
                        int32_t height, int32_t shift_x, int32_t shift_y, float min_alpha, float sensor_q,

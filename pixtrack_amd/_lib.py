@@ -45,6 +45,7 @@ PXT_DEPTH_RECORD = 32
 PXT_DEPTH_LOG_STRIDE = 20
 PXT_OCCLUSION_RECORD = 16
 PXT_OCCLUSION_MAX_RADIUS = 16
+PXT_OCCLUSION_MAX_VIEWS = 16
 PXT_ISO_CASE_TABLE_WORDS = 6 * 16 * 7
 PXT_MESH_VIEW = 20
 PXT_MESH_RASTER_RECORD = 16
@@ -243,6 +244,13 @@ class DepthProblem(C.Structure):
                 ("out", C.c_void_p), ("log", C.c_void_p), ("codes", C.c_void_p)]
 
 
+class OcclusionView(C.Structure):
+    """pxt_occlusion_view: one image pair of pxt_occlusion_mask_views (device pointers)."""
+    _fields_ = [("depth", C.c_void_p), ("sensor", C.c_void_p), ("mask_in", C.c_void_p), ("mask_out", C.c_void_p),
+                ("occluder", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("shift_x", C.c_int32),
+                ("shift_y", C.c_int32), ("sensor_q", C.c_float), ("delta_q", C.c_float)]
+
+
 class IsoGrid(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("iso", C.c_float), ("origin", C.c_float * 3),
                 ("spacing", C.c_float * 3)]
@@ -391,6 +399,8 @@ PROTOTYPES = {
     "pxt_occlusion_mask_workspace_bytes": (_I64, [_I32, _I32]),
     "pxt_occlusion_mask": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, C.c_float, C.c_float, C.c_float, _I32, _I32,
                                      _VP, _VP, _VP, _VP, _VP]),
+    "pxt_occlusion_mask_views_workspace_bytes": (_I64, [_I32, C.POINTER(_I32)]),
+    "pxt_occlusion_mask_views": (C.c_int, [C.POINTER(OcclusionView), _I32, C.c_float, _I32, _I32, _VP, _VP, _VP]),
     "pxt_points_visible": (C.c_int, [_VP, _VP, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _VP, _I32, _I32,
                                      _VP, _VP, _VP]),
     "pxt_mask_exclude": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP]),

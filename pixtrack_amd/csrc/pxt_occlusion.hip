@@ -27,6 +27,10 @@
 //    (lane l takes blocks l, l + 64, ...; then the butterfly) and writes the 16-word record.  Integer sums only, no
 //    atomics: the record depends on the call's own inputs, not on the launch geometry or on a neighbouring call.
 //
+// pxt_occlusion_mask_views: the same for up to 16 image pairs of different sizes in one chain of two launches - the tile
+// above is a device function of a view (oc_tile), the views' tile grids are concatenated, and one wave per view folds
+// (oc_fold); see occlusion_mask_views_kernel below.
+//
 // pxt_points_visible: one workgroup of 1024 threads; point n belongs to thread n % 1024.  transform_point and
 // project_point (pxt_lm_point.h / pxt_common.h: the LM's own statement, distortion included), the nearest texel of
 // (u, v) under the LM's addressing - texel k's centre is at coordinate k, so it is floor(u + 0.5), floor(v + 0.5); the
@@ -65,7 +69,10 @@ struct OcArgs {
   float min_alpha, sensor_q, delta_q;
 };
 
-__global__ __launch_bounds__(256) void occlusion_mask_kernel(const OcArgs a) {
+// One 64 x 16 tile of an image pair: tile `block` of the pair's own grid (row-major, a.tiles_x per row); its partial goes
+// to a.partials[block].  The body of both occlusion_mask_kernel (block = blockIdx.x) and occlusion_mask_views_kernel
+// (block = blockIdx.x minus the view's first tile): a view's bits are the single call's by construction.
+__device__ __forceinline__ void oc_tile(const OcArgs& a, const int block) {
   __shared__ OcRow sA[kOcBand], sB[kOcBand];
   __shared__ unsigned long long sSil[kOcH];
   __shared__ uint32_t sWave[4][5];      // per wave: n_sil, n_measured, n_occluded, n_mask_in, n_mask_out
@@ -73,7 +80,7 @@ __global__ __launch_bounds__(256) void occlusion_mask_kernel(const OcArgs a) {
   const int H = a.H, W = a.W, re = a.r_open, rd = a.r_grow;
   const int R = re + rd;                 // <= 16
   const int ah = kOcH + 2 * R;           // rows y0 - R .. y0 + kOcH + R - 1
-  const int bx = blockIdx.x % a.tiles_x, by = blockIdx.x / a.tiles_x;
+  const int bx = block % a.tiles_x, by = block / a.tiles_x;
   const int x0 = bx * kOcW, y0 = by * kOcH;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // band column c of a row sits in ballot c / 64 at bit c % 64; the tile's own columns are c = R .. R + 63
@@ -236,13 +243,15 @@ __global__ __launch_bounds__(256) void occlusion_mask_kernel(const OcArgs a) {
       const int k = tid == 7 ? 2 : tid - 3;
       for (int r = 0; r < kOcH; ++r) v += sRow[k][r];
     }
-    a.partials[(size_t)blockIdx.x * kOcPart + tid] = v;
+    a.partials[(size_t)block * kOcPart + tid] = v;
   }
 }
 
+__global__ __launch_bounds__(256) void occlusion_mask_kernel(const OcArgs a) { oc_tile(a, (int)blockIdx.x); }
+
 // One wave: lane l folds blocks l, l + 64, ... in order, the butterfly folds the lanes, lane 0 writes the record.
-__global__ __launch_bounds__(PXT_WAVE) void occlusion_fold_kernel(const uint32_t* __restrict__ partials, const int n_blocks,
-                                                                  int32_t* __restrict__ record) {
+__device__ __forceinline__ void oc_fold(const uint32_t* __restrict__ partials, const int n_blocks,
+                                        int32_t* __restrict__ record) {
   const int lane = threadIdx.x;
   const uint4* p = (const uint4*)partials;
   uint32_t v[kOcPart];
@@ -265,6 +274,66 @@ __global__ __launch_bounds__(PXT_WAVE) void occlusion_fold_kernel(const uint32_t
 #pragma unroll
     for (int w = kOcPart; w < kOcRec; ++w) record[w] = 0;  // (8..10: the point gate's words)
   }
+}
+
+__global__ __launch_bounds__(PXT_WAVE) void occlusion_fold_kernel(const uint32_t* __restrict__ partials, const int n_blocks,
+                                                                  int32_t* __restrict__ record) {
+  oc_fold(partials, n_blocks, record);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// pxt_occlusion_mask_views: up to PXT_OCCLUSION_MAX_VIEWS image pairs of different sizes in ONE chain of two launches.
+// The grid is the concatenation of the views' tile grids; a workgroup finds its view in the per-view first-tile table
+// (uniform per workgroup: scalar loads from the kernel arguments, which carry the whole table - no upload), forms that
+// view's OcArgs in scalar registers and runs oc_tile on its own tile of it.  The partials of view k start at its first
+// tile; the fold is one wave per view, oc_fold on the view's own partials: the order of the single call.
+// ---------------------------------------------------------------------------------------------------------------------
+struct OcView {
+  const float4* depth;
+  const uint16_t* sensor;
+  const uint8_t* mask_in;
+  uint8_t* mask_out;
+  uint8_t* occluder;
+  int H, W, tiles_x, n_tiles, tile0, shift_x, shift_y;  // tile0: the view's first tile in the grid
+  float sensor_q, delta_q;
+};
+
+struct OcvArgs {
+  OcView v[PXT_OCCLUSION_MAX_VIEWS];
+  uint32_t* partials;  // [all views' tiles][kOcPart]
+  int32_t* records;    // [n_views][kOcRec]
+  int n_views, r_open, r_grow;
+  float min_alpha;
+};
+
+__global__ __launch_bounds__(256) void occlusion_mask_views_kernel(const OcvArgs g) {
+  int v = 0;  // the last view whose first tile is not behind blockIdx.x (every view has a tile)
+  for (int k = 1; k < g.n_views; ++k)
+    if ((int)blockIdx.x >= g.v[k].tile0) v = k;
+  const OcView& w = g.v[v];
+  OcArgs a;
+  a.depth = w.depth;
+  a.sensor = w.sensor;
+  a.mask_in = w.mask_in;
+  a.mask_out = w.mask_out;
+  a.occluder = w.occluder;
+  a.partials = g.partials + (size_t)w.tile0 * kOcPart;
+  a.H = w.H;
+  a.W = w.W;
+  a.tiles_x = w.tiles_x;
+  a.shift_x = w.shift_x;
+  a.shift_y = w.shift_y;
+  a.r_open = g.r_open;
+  a.r_grow = g.r_grow;
+  a.min_alpha = g.min_alpha;
+  a.sensor_q = w.sensor_q;
+  a.delta_q = w.delta_q;
+  oc_tile(a, (int)blockIdx.x - w.tile0);
+}
+
+__global__ __launch_bounds__(PXT_WAVE) void occlusion_fold_views_kernel(const OcvArgs g) {
+  const OcView& w = g.v[blockIdx.x];
+  oc_fold(g.partials + (size_t)w.tile0 * kOcPart, w.n_tiles, g.records + (size_t)blockIdx.x * kOcRec);
 }
 
 struct PvArgs {
@@ -413,6 +482,27 @@ int64_t oc_blocks(int width, int height) {
   return (int64_t)((width + kOcW - 1) / kOcW) * ((height + kOcH - 1) / kOcH);
 }
 
+bool oc_radii_ok(int r_open, int r_grow) {
+  return r_open >= 0 && r_grow >= 0 && r_open <= kOcMaxR && r_grow <= kOcMaxR && r_open + r_grow <= kOcMaxR;
+}
+bool oc_shift_ok(int s) { return s >= -kOcMaxShift && s <= kOcMaxShift; }
+
+// The tiles of all views, or -1 when a count or a size is out of range.
+int64_t ocv_total_tiles(int32_t n_views, const int32_t* sizes) {
+  if (n_views < 1 || n_views > PXT_OCCLUSION_MAX_VIEWS || !sizes) return -1;
+  int64_t n = 0;
+  for (int k = 0; k < n_views; ++k) {
+    if (!oc_sizes_ok(sizes[2 * k], sizes[2 * k + 1])) return -1;
+    n += oc_blocks(sizes[2 * k], sizes[2 * k + 1]);
+  }
+  return n;
+}
+
+struct OcRange {
+  uintptr_t lo, hi;  // bytes [lo, hi)
+};
+bool oc_overlap(const OcRange& p, const OcRange& q) { return p.lo < q.hi && q.lo < p.hi; }
+
 }  // namespace
 }  // namespace pxt
 
@@ -429,8 +519,8 @@ extern "C" int pxt_occlusion_mask(const float* depth, const uint16_t* sensor, co
                                   int32_t* record, void* workspace, void* stream) {
   if (!depth || !sensor || !mask_in || !mask_out || !occluder || !record || !workspace) return PXT_E_ARG;
   if (!oc_sizes_ok(width, height)) return PXT_E_ARG;
-  if (r_open < 0 || r_grow < 0 || r_open > kOcMaxR || r_grow > kOcMaxR || r_open + r_grow > kOcMaxR) return PXT_E_ARG;
-  if (shift_x < -kOcMaxShift || shift_x > kOcMaxShift || shift_y < -kOcMaxShift || shift_y > kOcMaxShift) return PXT_E_ARG;
+  if (!oc_radii_ok(r_open, r_grow)) return PXT_E_ARG;
+  if (!oc_shift_ok(shift_x) || !oc_shift_ok(shift_y)) return PXT_E_ARG;
   if (((uintptr_t)depth % 16) != 0 || ((uintptr_t)sensor % 2) != 0 || ((uintptr_t)record % 4) != 0 ||
       ((uintptr_t)workspace % 16) != 0)
     return PXT_E_ARG;
@@ -457,6 +547,79 @@ extern "C" int pxt_occlusion_mask(const float* depth, const uint16_t* sensor, co
   hipLaunchKernelGGL(occlusion_mask_kernel, dim3(n_blocks), dim3(256), 0, s, a);
   PXT_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(occlusion_fold_kernel, dim3(1), dim3(PXT_WAVE), 0, s, (const uint32_t*)a.partials, n_blocks, record);
+  PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}
+
+extern "C" int64_t pxt_occlusion_mask_views_workspace_bytes(int32_t n_views, const int32_t* sizes) {
+  const int64_t n = ocv_total_tiles(n_views, sizes);
+  if (n < 0) return PXT_E_ARG;
+  return n * kOcPart * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int pxt_occlusion_mask_views(const pxt_occlusion_view* views_host, int32_t n_views, float min_alpha,
+                                        int32_t r_open, int32_t r_grow, int32_t* records, void* workspace, void* stream) {
+  if (!views_host || !records || !workspace) return PXT_E_ARG;
+  if (n_views < 1 || n_views > PXT_OCCLUSION_MAX_VIEWS) return PXT_E_ARG;
+  if (!oc_radii_ok(r_open, r_grow)) return PXT_E_ARG;
+  if (((uintptr_t)records % 4) != 0 || ((uintptr_t)workspace % 16) != 0) return PXT_E_ARG;
+  OcvArgs g;
+  OcRange out[2 * PXT_OCCLUSION_MAX_VIEWS], in[3 * PXT_OCCLUSION_MAX_VIEWS];
+  int64_t tile0 = 0;
+  for (int k = 0; k < n_views; ++k) {
+    const pxt_occlusion_view& p = views_host[k];
+    if (!p.depth || !p.sensor || !p.mask_in || !p.mask_out || !p.occluder) return PXT_E_ARG;
+    if (!oc_sizes_ok(p.width, p.height)) return PXT_E_ARG;
+    if (!oc_shift_ok(p.shift_x) || !oc_shift_ok(p.shift_y)) return PXT_E_ARG;
+    if (((uintptr_t)p.depth % 16) != 0 || ((uintptr_t)p.sensor % 2) != 0) return PXT_E_ARG;
+    const uintptr_t npix = (uintptr_t)p.width * (uintptr_t)p.height;
+    out[2 * k] = OcRange{(uintptr_t)p.mask_out, (uintptr_t)p.mask_out + npix};
+    out[2 * k + 1] = OcRange{(uintptr_t)p.occluder, (uintptr_t)p.occluder + npix};
+    in[3 * k] = OcRange{(uintptr_t)p.depth, (uintptr_t)p.depth + 16 * npix};
+    in[3 * k + 1] = OcRange{(uintptr_t)p.sensor, (uintptr_t)p.sensor + 2 * npix};
+    in[3 * k + 2] = OcRange{(uintptr_t)p.mask_in, (uintptr_t)p.mask_in + npix};
+    OcView& w = g.v[k];
+    w.depth = (const float4*)p.depth;
+    w.sensor = p.sensor;
+    w.mask_in = p.mask_in;
+    w.mask_out = p.mask_out;
+    w.occluder = p.occluder;
+    w.H = p.height;
+    w.W = p.width;
+    w.tiles_x = (p.width + kOcW - 1) / kOcW;
+    w.n_tiles = (int)oc_blocks(p.width, p.height);
+    w.tile0 = (int)tile0;
+    w.shift_x = p.shift_x;
+    w.shift_y = p.shift_y;
+    w.sensor_q = p.sensor_q;
+    w.delta_q = p.delta_q;
+    tile0 += w.n_tiles;  // <= 16 * 2^24
+  }
+  // every output plane is written by its own view alone and read by nobody: it overlaps no other output, no input of
+  // any view - except that a view's mask_out may BE its mask_in, as in the single call - nor the records or the partials
+  const OcRange rec = {(uintptr_t)records, (uintptr_t)records + (uintptr_t)n_views * kOcRec * sizeof(int32_t)};
+  const OcRange ws = {(uintptr_t)workspace, (uintptr_t)workspace + (uintptr_t)tile0 * kOcPart * sizeof(uint32_t)};
+  if (oc_overlap(rec, ws)) return PXT_E_ARG;
+  for (int i = 0; i < 2 * n_views; ++i) {
+    if (oc_overlap(out[i], rec) || oc_overlap(out[i], ws)) return PXT_E_ARG;
+    for (int j = i + 1; j < 2 * n_views; ++j)
+      if (oc_overlap(out[i], out[j])) return PXT_E_ARG;
+    for (int j = 0; j < 3 * n_views; ++j) {
+      const bool own_mask = (i % 2) == 0 && j == 3 * (i / 2) + 2 && out[i].lo == in[j].lo;
+      if (!own_mask && oc_overlap(out[i], in[j])) return PXT_E_ARG;
+    }
+  }
+  for (int k = n_views; k < PXT_OCCLUSION_MAX_VIEWS; ++k) g.v[k] = OcView{};
+  g.partials = (uint32_t*)workspace;
+  g.records = records;
+  g.n_views = n_views;
+  g.r_open = r_open;
+  g.r_grow = r_grow;
+  g.min_alpha = min_alpha;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(occlusion_mask_views_kernel, dim3((unsigned)tile0), dim3(256), 0, s, g);
+  PXT_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(occlusion_fold_views_kernel, dim3(n_views), dim3(PXT_WAVE), 0, s, g);
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;
 }

@@ -17,6 +17,9 @@ and a reference point whose projection's nearest texel lies in G leaves the LM's
 
 * ``occlusion_mask`` / ``points_visible``: the device wrappers of ``torch.ops.pixtrack.occlusion_mask`` /
   ``points_visible``; both only enqueue.
+* ``occlusion_mask_views``: the same pass for up to 16 image pairs of different sizes in one chain of two launches
+  (``pxt_occlusion_mask_views``) - the mesh objects of one RGB-D frame; ``mesh_quanta``: the quanta of a mesh template's
+  float depth plane.
 * ``mask_exclude`` / ``mask_exclude_reference``: a mask minus an occluder plane that some other call made - the lock-step
   tracker's mutual occlusion takes the plane from the other tracked meshes (``pxt_mesh_render_scene_batch``).
 * ``occlusion_mask_reference`` / ``points_visible_reference``: the numpy float32 restatements - the oracles of the
@@ -39,6 +42,7 @@ from .sensor_evaluation import MAX_RESIDUAL_PX, sensor_alignment, shifted_sensor
 
 RECORD = 16          # PXT_OCCLUSION_RECORD
 MAX_RADIUS = 16      # PXT_OCCLUSION_MAX_RADIUS: r_open + r_grow
+MAX_VIEWS = 16       # PXT_OCCLUSION_MAX_VIEWS: image pairs of one occlusion_mask_views call
 RECORD_NAMES = ("n_sil", "n_measured", "n_occluded", "n_opened", "n_occluder", "n_mask_in", "n_mask_out",
                 "n_sil_occluder", "n_points", "n_points_in", "n_points_out")
 FRAGILE_PX = 1e-3
@@ -97,6 +101,21 @@ def quantize(delta: float, sensor_depth_scale: float, z_scale: float) -> Tuple[f
     if not (zs > 0.0 and np.isfinite(zs)) or not float(sensor_depth_scale) > 0.0:
         raise ValueError(f"z_scale and sensor_depth_scale must be positive (got {z_scale}, {sensor_depth_scale})")
     return float(np.float32(float(sensor_depth_scale) / zs)), float(np.float32(float(delta) / zs))
+
+
+def mesh_quanta(delta: float, sensor_depth_scale: float, view_record) -> Tuple[float, float]:
+    """``(sensor_q, delta_q)`` for the float depth plane of a MESH template's frame call (``MeshTemplate.frame(...,
+    want_depth=True)``: ``(d, d, d, 1)`` on covered pixels, d = z * depth_q).  One unit of ``q = v.x / v.w`` is
+    ``1 / depth_q`` SfM units, ``depth_q`` being the float32 word [17] of the view record the plane was drawn with, taken
+    to float64: ``quantize(delta, sensor_depth_scale, 1.0 / depth_q)``.  ``depth_q`` changes with every frame, so the
+    quanta are formed per frame.  The view is drawn with the camera's true cx, cy, so the shift is (0, 0)."""
+    rec = np.asarray(view_record.detach().cpu().numpy() if hasattr(view_record, "detach") else view_record).reshape(-1)
+    if rec.size < 18:
+        raise ValueError(f"a mesh view record holds 20 floats (got {rec.size})")
+    depth_q = float(np.float32(rec[17]))
+    if not (depth_q > 0.0 and np.isfinite(depth_q)):
+        raise ValueError(f"the view record's depth_q must be positive and finite (got {depth_q})")
+    return quantize(delta, sensor_depth_scale, 1.0 / depth_q)
 
 
 def alignment(camera, allow_misaligned: bool = False) -> Tuple[int, int, float]:
@@ -257,6 +276,61 @@ def occlusion_mask(depth, sensor, mask_in, shift, min_alpha: float, sensor_q: fl
     ops.occlusion_mask(depth, sensor, mask_in, [int(shift[0]), int(shift[1])], float(min_alpha), float(sensor_q),
                        float(delta_q), [ro, rg], mask, occluder, record, workspace)
     return {"mask": mask, "occluder": occluder, "record": record, "workspace": workspace}
+
+
+def occlusion_mask_views(depth, sensors, masks_in, shifts, min_alpha: float, quanta, r_open: int, r_grow: int,
+                         masks=None, occluders=None, records=None, workspace=None) -> Dict:
+    """Enqueue ``torch.ops.pixtrack.occlusion_mask_views`` on the current stream: ``occlusion_mask`` for K <= 16 image
+    pairs of different sizes in one chain of two launches (the K mesh objects of one RGB-D frame).  Per view: ``depth``
+    float32 [H_k, W_k, 4], ``sensors`` uint16 (or int16) [H_k, W_k] (several views may name ONE tensor) and ``masks_in``
+    uint8 [H_k, W_k] device tensors, ``shifts[k]`` = (shift_x, shift_y), ``quanta[k]`` = (sensor_q, delta_q);
+    ``min_alpha`` and the radii hold for the call.  ``masks`` / ``occluders`` (lists) / ``records`` (int32 [K, 16],
+    device or pinned) / ``workspace``: buffers a caller keeps across frames (default: fresh ones, the records on the
+    device).  View k's planes and record are bit for bit what ``occlusion_mask`` gives for that pair alone.  Nothing is
+    awaited.
+
+    -> dict(masks, occluders, records, workspace)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from .ops import ops
+
+    ro, rg = check_radii(r_open, r_grow)
+    K = len(depth)
+    if not (1 <= K <= MAX_VIEWS):
+        raise ValueError(f"occlusion_mask_views takes 1..{MAX_VIEWS} views (got {K})")
+    if not (len(sensors) == len(masks_in) == len(shifts) == len(quanta) == K):
+        raise ValueError(f"sensors, masks_in, shifts and quanta hold one entry per view ({K}; got {len(sensors)}, "
+                         f"{len(masks_in)}, {len(shifts)}, {len(quanta)})")
+    for name, given in (("masks", masks), ("occluders", occluders)):
+        if given is not None and len(given) != K:
+            raise ValueError(f"{name} holds one plane per view ({K}; got {len(given)})")
+    for k, (sh, qu) in enumerate(zip(shifts, quanta)):
+        if len(sh) != 2 or len(qu) != 2:
+            raise ValueError(f"shifts[{k}] is (shift_x, shift_y) and quanta[{k}] (sensor_q, delta_q)")
+    dev = depth[0].device
+    sizes = []
+    for d in depth:
+        if d.dim() != 3 or int(d.shape[2]) != 4:
+            raise ValueError(f"every depth plane is [H, W, 4] (got {tuple(d.shape)})")
+        sizes += [int(d.shape[1]), int(d.shape[0])]
+    if masks is None:
+        masks = [torch.empty(h, w, dtype=torch.uint8, device=dev) for w, h in zip(sizes[0::2], sizes[1::2])]
+    if occluders is None:
+        occluders = [torch.empty(h, w, dtype=torch.uint8, device=dev) for w, h in zip(sizes[0::2], sizes[1::2])]
+    if records is None:
+        records = torch.zeros(K, RECORD, dtype=torch.int32, device=dev)
+    if workspace is None:
+        need = int(_lib.lib().pxt_occlusion_mask_views_workspace_bytes(K, (C.c_int32 * (2 * K))(*sizes)))
+        if need <= 0:
+            raise ValueError(f"planes of {list(zip(sizes[0::2], sizes[1::2]))} are not supported (1..2^28 pixels)")
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    ops.occlusion_mask_views(list(depth), list(sensors), list(masks_in), [int(v) for sh in shifts for v in sh],
+                             float(min_alpha), [float(v) for qu in quanta for v in qu], [ro, rg], list(masks),
+                             list(occluders), records, workspace)
+    return {"masks": masks, "occluders": occluders, "records": records, "workspace": workspace}
 
 
 def mask_exclude(mask_in, occluder, mask=None, record=None):

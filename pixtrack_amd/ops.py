@@ -34,6 +34,8 @@ Reference call sites the ops stand in for:
                        12 floats or at an lm_refine record read on the device (depth_refinement.py)
   occlusion_mask       (opt-in, no reference counterpart) get_mask's plane minus the pixels where the frame's sensor depth
                        image lies in front of the mask view's Depth render, opened and grown (occlusion.py)
+  occlusion_mask_views (opt-in) occlusion_mask for up to 16 image pairs of different sizes in one chain of two
+                       launches, each pair's outputs bit for bit the single call's: the mesh objects of one RGB-D frame
   points_visible       (opt-in, no reference counterpart) the LM's point mask minus the points that project onto that
                        occluder plane
   mesh_render_scene_batch  (opt-in, no reference counterpart) mesh_render_frame_batch for objects that share an image:
@@ -178,6 +180,14 @@ SCHEMAS = {
     "occlusion_mask": (
         "(Tensor depth, Tensor sensor, Tensor mask_in, int[] shift, float min_alpha, float sensor_q, float delta_q, "
         "int[] radii, Tensor(a!) mask, Tensor(b!) occluder, Tensor(c!) record, Tensor(d!) workspace) -> ()"),
+    # occlusion_mask for K <= 16 image pairs of different sizes in one chain of two launches (pxt_occlusion_mask_views):
+    # per view depth [H_k, W_k, 4], sensor [H_k, W_k] (several views may name one tensor), the plain mask, shifts = K x
+    # (shift_x, shift_y), quanta = K x (sensor_q, delta_q); min_alpha and radii hold for the call -> per view mask and
+    # occluder, records int32 [K, 16] (device or pinned); workspace: uint8, pxt_occlusion_mask_views_workspace_bytes(K,
+    # sizes).  View k's outputs are bit for bit occlusion_mask's on that pair alone
+    "occlusion_mask_views": (
+        "(Tensor[] depth, Tensor[] sensors, Tensor[] masks_in, int[] shifts, float min_alpha, float[] quanta, "
+        "int[] radii, Tensor(a!)[] masks, Tensor(b!)[] occluders, Tensor(c!) records, Tensor(d!) workspace) -> ()"),
     # p3d [N, 3], an optional uint8 mask [N], 12 pose floats, the unscaled query camera (10 floats, ndist), the occluder
     # plane of occlusion_mask -> valid uint8 [N] and words 8..10 of the same record (pxt_points_visible)
     "points_visible": (
@@ -1238,6 +1248,65 @@ def _occlusion_mask(depth, sensor, mask_in, shift, min_alpha, sensor_q, delta_q,
                                     workspace.data_ptr(), _stream(depth)), "pxt_occlusion_mask")
 
 
+def _occlusion_mask_views(depth, sensors, masks_in, shifts, min_alpha, quanta, radii, masks, occluders, records, workspace):
+    L = _lib.lib()
+    what = "occlusion_mask_views"
+    K = len(depth)
+    if not (1 <= K <= _lib.PXT_OCCLUSION_MAX_VIEWS):
+        raise _lib.PxtError(f"{what}: 1..{_lib.PXT_OCCLUSION_MAX_VIEWS} views (got {K})")
+    if not (len(sensors) == len(masks_in) == len(masks) == len(occluders) == K) or len(shifts) != 2 * K or len(quanta) != 2 * K:
+        raise _lib.PxtError(f"{what}: sensors, masks_in, masks and occluders hold one tensor, shifts (shift_x, shift_y) "
+                            f"and quanta (sensor_q, delta_q) two values per view ({K} views)")
+    if len(radii) != 2 or min(int(r) for r in radii) < 0 or int(radii[0]) + int(radii[1]) > _lib.PXT_OCCLUSION_MAX_RADIUS:
+        raise _lib.PxtError(f"{what}: radii are (r_open, r_grow) >= 0 with r_open + r_grow <= "
+                            f"{_lib.PXT_OCCLUSION_MAX_RADIUS} (got {list(radii)})")
+    if any(abs(int(v)) > 32767 for v in shifts):
+        raise _lib.PxtError(f"{what}: every shift is within +-32767 (got {list(shifts)})")
+    device = depth[0].device
+    views = (_lib.OcclusionView * K)()
+    sizes, spans = [], []
+    for k in range(K):
+        d, sen, mi, mo, oc = depth[k], sensors[k], masks_in[k], masks[k], occluders[k]
+        _f32c(d, f"depth[{k}]")
+        if d.dim() != 3 or int(d.shape[2]) != 4:
+            raise _lib.PxtError(f"{what}: depth[{k}] is [H, W, 4] (got {tuple(d.shape)})")
+        H, W = int(d.shape[0]), int(d.shape[1])
+        if sen.dtype not in (torch.uint16, torch.int16) or not sen.is_contiguous() or tuple(sen.shape) != (H, W):
+            raise _lib.PxtError(f"{what}: sensors[{k}] is a contiguous uint16 (or int16) [{H}, {W}] tensor "
+                                f"(got {tuple(sen.shape)}, {sen.dtype})")
+        if mi.dtype != torch.uint8 or not mi.is_contiguous() or tuple(mi.shape) != (H, W):
+            raise _lib.PxtError(f"{what}: masks_in[{k}] is a contiguous uint8 [{H}, {W}] tensor")
+        _mask_out(mo, H, W, d, what)
+        _mask_out(oc, H, W, d, what)
+        # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
+        for t, name in ((d, "depth"), (sen, "sensors"), (mi, "masks_in")):
+            _lib.require_gpu(t, f"{name}[{k}]")
+            if t.device != device:
+                raise _lib.PxtError(f"{what}: {name}[{k}] is on {t.device}, depth[0] on {device}")
+        sizes += [W, H]
+        spans += [(mo.data_ptr(), mo.data_ptr() + H * W, f"masks[{k}]"), (oc.data_ptr(), oc.data_ptr() + H * W, f"occluders[{k}]")]
+        v = views[k]
+        v.depth, v.sensor, v.mask_in, v.mask_out, v.occluder = d.data_ptr(), sen.data_ptr(), mi.data_ptr(), mo.data_ptr(), oc.data_ptr()
+        v.width, v.height, v.shift_x, v.shift_y = W, H, int(shifts[2 * k]), int(shifts[2 * k + 1])
+        v.sensor_q, v.delta_q = float(quanta[2 * k]), float(quanta[2 * k + 1])
+    spans.sort()
+    for (_lo, hi, a), (lo, _hi, b) in zip(spans, spans[1:]):
+        if lo < hi:
+            raise _lib.PxtError(f"{what}: {a} and {b} overlap; every view writes planes of its own")
+    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (K, _lib.PXT_OCCLUSION_RECORD) \
+            or not ((records.is_cuda and records.device == device) or records.is_pinned()):
+        raise _lib.PxtError(f"{what}: records is a contiguous int32 [{K}, {_lib.PXT_OCCLUSION_RECORD}] tensor on the depth "
+                            "planes' device or in pinned memory")
+    need = int(L.pxt_occlusion_mask_views_workspace_bytes(K, (C.c_int32 * (2 * K))(*sizes)))
+    if need <= 0:
+        raise _lib.PxtError(f"{what}: planes of {list(zip(sizes[0::2], sizes[1::2]))} are not supported (1..2^28 pixels)")
+    _lib.require_gpu(workspace, "workspace")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != device:
+        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {need} bytes on {device}")
+    _lib.check(L.pxt_occlusion_mask_views(views, K, float(min_alpha), int(radii[0]), int(radii[1]), records.data_ptr(),
+                                          workspace.data_ptr(), _stream(depth[0])), "pxt_occlusion_mask_views")
+
+
 def _mask_exclude(mask_in, occluder, mask, record):
     L = _lib.lib()
     if mask_in.dtype != torch.uint8 or mask_in.dim() != 2 or not mask_in.is_contiguous():
@@ -1848,6 +1917,7 @@ _IMPLS = {
     "iso_surface_emit": _iso_surface_emit,
     "max_pairwise_distance": _max_pairwise_distance,
     "occlusion_mask": _occlusion_mask,
+    "occlusion_mask_views": _occlusion_mask_views,
     "points_visible": _points_visible,
     "depth_refine": _depth_refine,
     "sensor_vsd": _sensor_vsd,

@@ -90,10 +90,26 @@ class _Group:
         self.points_ws: Optional[torch.Tensor] = None  # workspace of the step's pxt_points_from_depth_views call(s)
         self.points_records = None  # pinned [16, 4] records of those calls, recycled round-robin
         self.points_next = 0
+        self.occ_ws: Optional[torch.Tensor] = None  # workspace of the step's pxt_occlusion_mask_views call(s)
+        self.occ_records = None  # pinned [16, 16] records of those calls, recycled round-robin
+        self.occ_next = 0
+        self.depth_ws: Optional[torch.Tensor] = None  # workspace of the step's pxt_depth_refine call(s)
+        self.sensor_slots: list = []  # per distinct sensor image of a step: (pinned buffer, device buffer, upload event)
         self.ahead_rows = None  # pinned views_out blocks of the group's MeshTemplate.frames_ahead calls, recycled round-robin
         self.ahead_next = 0
         self.unet_done: Optional[torch.cuda.Event] = None
         self.pend = None  # what _enqueue left for _finish
+
+
+class _OneDepth:
+    """One problem's share of a batched pxt_depth_refine call, with the interface of the solo tracker's handle:
+    ``result()`` waits for the call and returns [that problem's record]."""
+
+    def __init__(self, pending, index: int):
+        self.pending, self.index = pending, index
+
+    def result(self):
+        return [self.pending.result()[self.index]]
 
 
 class MultiObjectTracker:
@@ -113,6 +129,14 @@ class MultiObjectTracker:
         beside ``"sfm"`` ones: per step and group the points of all of them that take the lock-step path come from ONE
         pxt_points_from_depth_views call behind the frame call (``points_calls`` counts them); a tracker that runs a step
         alone extracts its own.
+        Mesh-template trackers with ``reference_points="template"`` may carry ``occlusion`` and ``depth_refine`` (DESIGN
+        3.23; NeRF-template trackers with either stay refused).  Per step and group: the trackers whose options name the
+        same ``lookup`` object and frame name share ONE staged sensor image (``sensor_uploads``); behind the frame call
+        and the points call comes ONE pxt_occlusion_mask_views call for every tracker that takes a mask
+        (``occlusion_view_calls``), behind the batched LM launch ONE pxt_depth_refine call with the problems of all that
+        asked (``depth_refine_calls``); history keys, point gate and policy are each tracker's own, as solo.  Not with
+        ``mutual_occlusion`` (which refuses "template" trackers): the sensor's plane already contains the other objects,
+        so the two kinds of occluder plane never meet.
         ``uncertainty``: None keeps each tracker's own setting, True / False sets it for all of them (the ``uncertainty``
         option of PixLocPoseTrackerR9): the information problems of a group's step then go out as ONE pxt_lm_information
         launch behind its batched LM launch and its queued renders.
@@ -149,12 +173,14 @@ class MultiObjectTracker:
             elif points != "sfm":
                 # (the batched render chain carries no float Depth image and the batched reference pass encodes the SfM window)
                 raise ValueError(f"reference_points={points!r} is not supported by lock-step tracking yet")
-            if getattr(tr, "depth_refine", None) is not None:
-                # (the lock-step step launches the LM itself: nothing queues the depth problem behind it)
-                raise ValueError("depth_refine is not supported by lock-step tracking yet")
-            if getattr(tr, "occlusion", None) is not None:
-                # (the batched render chain carries no float Depth image, and the step launches the LM itself)
-                raise ValueError("occlusion is not supported by lock-step tracking yet")
+            # the sensor options ride on the float depth planes of the mesh frame call and on its points: a mesh template
+            # with reference_points="template" (the batched NeRF render chain carries no float Depth image)
+            if getattr(tr, "depth_refine", None) is not None and points != "template":
+                raise ValueError("depth_refine is supported by lock-step tracking for mesh-template trackers with "
+                                 "reference_points='template' only")
+            if getattr(tr, "occlusion", None) is not None and points != "template":
+                raise ValueError("occlusion is supported by lock-step tracking for mesh-template trackers with "
+                                 "reference_points='template' only")
             template = getattr(tr, "template", None)
             if template is not None:
                 from ..mesh_template import MeshTemplate
@@ -197,6 +223,9 @@ class MultiObjectTracker:
         self.mesh_prime_calls = 0  # MeshTemplate.frames calls made at the head of a step (one per group that needs one)
         self.mesh_ahead_calls = 0  # MeshTemplate.frames_ahead calls queued behind a step's LM launch (one per group)
         self.points_calls = 0      # pxt_points_from_depth_views calls made for "template" trackers (one per group and step)
+        self.occlusion_view_calls = 0  # pxt_occlusion_mask_views calls (one per group and step once masks exist)
+        self.depth_refine_calls = 0    # pxt_depth_refine calls behind a step's LM launch (one per group and step)
+        self.sensor_uploads = 0        # sensor images staged for lock-step frames (one per (lookup, frame name) and step)
         self.timing = None         # set to {} to collect HIP-event pairs per phase (bench.py's untimed diagnostic pass)
 
     def _checked_scenes(self, option: MutualOcclusion) -> list:
@@ -343,6 +372,7 @@ class MultiObjectTracker:
         live = []
         grp.pend = []
         # ---- phase A: per-object frame set-up (policy head, mask + reference render or the render queued last step)
+        self._stage_sensors(grp, frames)  # (the sensor options: before the step's first launch)
         self._prime_mesh_frames(grp, frames)
         for k in grp.members:
             tr, frame = self.trackers[k], frames[k]
@@ -442,6 +472,8 @@ class MultiObjectTracker:
                                                            asked[0][0]["conf"], grp.report_ws, pool_key=("group", grp.index))
             for i, (x, _h, _rf) in enumerate(asked):
                 x["report"] = (report, i)
+        # ---- the step's sensor-depth refinements (opt-in): ONE launch for every object that asked, next to them
+        self._enqueue_depth_refinements(grp)
 
     @staticmethod
     def _takes_lockstep(tr, frame) -> bool:
@@ -463,9 +495,13 @@ class MultiObjectTracker:
         ahead = [tr for tr in part if self._served_ahead(tr)]
         part = [tr for tr in part if not any(tr is a for a in ahead)]
         ahead_points = [(tr, *tr._ahead_ok[4]) for tr in ahead if tr.reference_points == "template" and tr._ahead_ok[4] is not None]
+        # the occlusion option's pass for the trackers that take a mask this step: their planes, with the plain masks
+        ahead_occ = [(tr, tr._ahead_ok[1], *tr._ahead_ok[4]) for tr in ahead
+                     if self._takes_occlusion(tr) and tr._ahead_ok[4] is not None]
         if not part:  # (NeRF trackers only: nothing of the mesh path is touched; or every mesh frame was drawn ahead)
             if ahead_points:
                 self._prime_template_points(grp, ahead_points)
+            self._prime_occlusion(grp, ahead_occ)
             return
         self.mesh_prime_calls += 1
         from ..mesh_render import FrameBatchWorkspace
@@ -483,6 +519,8 @@ class MultiObjectTracker:
                 tr._primed_frame = (tr.pose, nz, ref_u8)
             self._prime_template_points(grp, ahead_points + [(tr, depth, view) for tr, (_nz, _ref, depth, view)
                                                              in zip(part, planes) if depth is not None])
+            self._prime_occlusion(grp, ahead_occ + [(tr, tr._mask_of(nz), depth, view) for tr, (nz, _ref, depth, view)
+                                                    in zip(part, planes) if depth is not None and self._takes_occlusion(tr)])
             return
         if ahead_points:
             self._prime_template_points(grp, ahead_points)
@@ -576,6 +614,133 @@ class MultiObjectTracker:
                 for i, (tr, _depth, _view) in enumerate(chunk):
                     tr._primed_points = (tr.pose, p3d[i], slot_valid[i], record[i])
 
+    @staticmethod
+    def _takes_occlusion(tr) -> bool:
+        """This step, the tracker's _frame_setup asks for a mask (a tracked frame) and the occlusion option has a
+        sensor image to hold against it."""
+        return bool(tr.occlusion is not None and tr._depth_sensor is not None and tr.success and not tr._lost)
+
+    def _stage_sensors(self, grp: _Group, frames) -> None:
+        """Before the step's first launch: the sensor image of every tracker of the group that takes the lock-step path
+        with ``depth_refine`` or ``occlusion``.  Trackers whose options name the same ``lookup`` object and the same
+        frame name share ONE staged image - the K objects of one RGB-D frame: one fetch, one upload
+        (``sensor_uploads`` counts images).  A tracker that runs the step alone stages its own (run_single_frame)."""
+        import numpy as np
+
+        staged = {}
+        for k in grp.members:
+            tr, frame = self.trackers[k], frames[k]
+            if not self._takes_lockstep(tr, frame):
+                continue
+            option = tr.depth_refine if tr.depth_refine is not None else tr.occlusion  # (one lookup: _check_occlusion)
+            if option is None:
+                continue
+            name = os.path.basename(str(frame[0]))
+            key = (id(option.lookup), name)
+            if key not in staged:
+                sensor = option.lookup(name)
+                if sensor is not None:
+                    sensor = np.ascontiguousarray(np.asarray(sensor))
+                    if sensor.dtype != np.uint16 or sensor.ndim != 2:
+                        raise ValueError(f"the sensor depth image of {frame[0]} is {sensor.dtype} {sensor.shape}, not "
+                                         "uint16 [H, W]")
+                    slot = sum(v is not None for v in staged.values())
+                    if slot == len(grp.sensor_slots):
+                        grp.sensor_slots.append(None)
+                    buf = grp.sensor_slots[slot]
+                    if buf is None or tuple(buf[0].shape) != sensor.shape:
+                        buf = grp.sensor_slots[slot] = (torch.empty(sensor.shape, dtype=torch.int16).pin_memory(),
+                                                        torch.empty(sensor.shape, dtype=torch.int16, device=self.device),
+                                                        torch.cuda.Event())
+                    else:
+                        buf[2].synchronize()  # (the last step's upload: over long ago)
+                    buf[0].numpy()[...] = sensor.view(np.int16)
+                    buf[1].copy_(buf[0], non_blocking=True)
+                    buf[2].record(torch.cuda.current_stream(self.device))
+                    self.sensor_uploads += 1
+                    sensor = buf[1]
+                staged[key] = sensor
+            tr._adopt_depth_sensor(frame[0], staged[key])
+
+    def _prime_occlusion(self, grp: _Group, items) -> None:
+        """``items`` = [(tracker, plain mask, depth plane, view record)] of the group's trackers whose occlusion pass
+        runs this step: ONE pxt_occlusion_mask_views call behind the frame call and the points call (one per distinct
+        (min_alpha, r_open, r_grow), normally one; more than 16 views in chunks).  Each tracker keeps (pose, plain mask,
+        the pass's frame) - its get_mask takes them instead of making its own call, and its point gate, history keys
+        and ``last_occlusion`` are the solo tracker's."""
+        if not items:
+            return
+        from .. import occlusion as OC
+
+        by_conf: dict = {}
+        for item in items:
+            conf = item[0]._occ_conf
+            by_conf.setdefault((float(conf.min_alpha), int(conf.r_open), int(conf.r_grow)), []).append(item)
+        L, C = _lib.lib(), _lib.C
+        for (min_alpha, r_open, r_grow), members in by_conf.items():
+            for a in range(0, len(members), OC.MAX_VIEWS):
+                chunk = members[a:a + OC.MAX_VIEWS]
+                n = len(chunk)
+                per_view = [tr._occlusion_view(depth, view) for tr, _m, depth, view in chunk]
+                sizes = [x for _tr, _m, depth, _v in chunk for x in (int(depth.shape[1]), int(depth.shape[0]))]
+                need = int(L.pxt_occlusion_mask_views_workspace_bytes(n, (C.c_int32 * (2 * n))(*sizes)))
+                if need <= 0:
+                    raise _lib.PxtError(f"depth planes of {sizes} are not supported by pxt_occlusion_mask_views")
+                # (one workspace serves one call at a time: the group's calls follow each other on its stream)
+                if grp.occ_ws is None or grp.occ_ws.numel() < need:
+                    grp.occ_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                if grp.occ_records is None:
+                    # the kernels receive the raw pointer: the records live as long as the group and are recycled - a
+                    # step's are read (in its _frame_policy) long before eight more calls are queued
+                    grp.occ_records = [torch.zeros(OC.MAX_VIEWS, OC.RECORD, dtype=torch.int32).pin_memory() for _ in range(8)]
+                records = grp.occ_records[grp.occ_next][:n]
+                grp.occ_next = (grp.occ_next + 1) % len(grp.occ_records)
+                out = OC.occlusion_mask_views([depth for _tr, _m, depth, _v in chunk], [s for s, _q in per_view],
+                                              [m for _tr, m, _d, _v in chunk], [(0, 0)] * n, min_alpha,
+                                              [q for _s, q in per_view], r_open, r_grow, records=records,
+                                              workspace=grp.occ_ws)
+                self.occlusion_view_calls += 1
+                cur = torch.cuda.current_stream(self.device)
+                for i, (tr, mask_in, depth, view) in enumerate(chunk):
+                    sensor, (sensor_q, delta_q) = per_view[i]
+                    frame = {"depth": depth, "sensor": sensor, "mask_in": mask_in, "mask": out["masks"][i],
+                             "occluder": out["occluders"][i], "shift": (0, 0), "min_alpha": min_alpha,
+                             "sensor_q": sensor_q, "delta_q": delta_q, "radii": (r_open, r_grow), "gates": [],
+                             "record_buffer": records[i], "done": tr._occ_done, "view": view}
+                    tr._occ_done.record(cur)
+                    tr._primed_occlusion = (tr.pose, mask_in, frame)
+
+    def _enqueue_depth_refinements(self, grp: _Group) -> None:
+        """Behind the step's batched LM launch: ONE pxt_depth_refine call with the problems of all the group's trackers
+        that asked (one per distinct conf; more than the call's maximum in chunks).  Each problem reads its own LM record
+        on the device; each tracker's _frame_policy reads its own record."""
+        from ..depth_refinement import MAX_PROBLEMS, depth_refine_batch
+
+        by_conf = []
+        for _k, tr, _p, _r, _d, status, x, handle in grp.pend:
+            if status != "lm" or tr.depth_refine is None:
+                continue
+            item = tr._depth_problem(x, handle, tr.camera)
+            if item is None:  # (the frame has no depth image: its pose stays the LM's)
+                continue
+            for conf, members in by_conf:
+                if conf == tr._depth_conf:
+                    members.append((x, item))
+                    break
+            else:
+                by_conf.append((tr._depth_conf, [(x, item)]))
+        for conf, members in by_conf:
+            for a in range(0, len(members), MAX_PROBLEMS):
+                chunk = members[a:a + MAX_PROBLEMS]
+                if grp.depth_ws is None:
+                    grp.depth_ws = torch.zeros(int(_lib.lib().pxt_depth_refine_workspace_bytes(MAX_PROBLEMS)),
+                                               dtype=torch.uint8, device=self.device)
+                pending = depth_refine_batch([item[0] for _x, item in chunk], conf, workspace=grp.depth_ws,
+                                             records=[item[1] for _x, item in chunk])
+                self.depth_refine_calls += 1
+                for i, (x, _item) in enumerate(chunk):
+                    x["depth"] = _OneDepth(pending, i)
+
     def _step_scenes(self, grp: _Group, frames):
         """The scene of each of the group's mesh trackers that take the lock-step path this step (the order of
         _prime_mesh_frames' ``part``), None where the tracker is alone: a scene counts only with two members in the
@@ -625,6 +790,8 @@ class MultiObjectTracker:
         for k, tr, path, ref_id, dbg, status, x, handle in grp.pend or []:
             refiner = tr.localizer.refiner
             ret = refiner.finish_refine(x, handle.result()) if handle is not None else x
+            if handle is not None and x.get("depth") is not None:
+                ret["depth_pending"] = x["depth"]  # (read, and waited for, by the tracker's _frame_policy)
             ok = tr._frame_policy(path, {ref_id: ret}, {ref_id: tr._frame_cost()}, {ref_id: dbg})
             if not ok:
                 tr.relocalize(frames[k])
@@ -719,6 +886,28 @@ def build_parser():
                     help="the points every object's frames are refined on: sfm (default: the SfM points of the nearest "
                          "mapping image) or template (--template mesh: a lattice of the depth plane the mesh template draws "
                          "for the frame; a group's points are extracted in one call)")
+    ap.add_argument("--depth_refine", action="store_true",
+                    help="--template mesh --reference_points template: refine every object's pose on its sensor depth image "
+                         "after the LM; a group's problems go out in one call (needs --sensor_depth_dir and "
+                         "--sensor_depth_scale)")
+    ap.add_argument("--occlusion_mask", action="store_true",
+                    help="--template mesh --reference_points template: take the pixels where the sensor depth image lies in "
+                         "front of an object out of its mask and point set; a group's passes go out in one call (needs "
+                         "--sensor_depth_dir and --sensor_depth_scale)")
+    ap.add_argument("--sensor_depth_dir", type=Path, nargs="+", default=None,
+                    help="the 16-bit depth images, one per frame: one directory per object or one for all - objects with "
+                         "equal directory, template and substitution share one image upload per step")
+    ap.add_argument("--sensor_depth_scale", type=float, nargs="+", default=None, help="SfM units per raw count, per object or one for all")
+    ap.add_argument("--sensor_depth_template", nargs="+", default=None,
+                    help="file name of a frame's depth image: {stem} / {name} of the frame (default {stem}.png)")
+    ap.add_argument("--sensor_depth_sub", nargs=2, metavar=("OLD", "NEW"), default=None,
+                    help="replace OLD by NEW in the frame's name first (YCB-Video: color depth)")
+    ap.add_argument("--depth_prior", nargs=2, type=float, metavar=("WT", "WR"), default=None,
+                    help="diagonal prior on the depth refinement's accumulated update: translation, rotation weight")
+    ap.add_argument("--occlusion_delta", type=float, nargs="+", default=None,
+                    help="how much closer the sensor's surface must be, as a fraction of the model's extent (default 0.1)")
+    ap.add_argument("--occlusion_radii", nargs=2, type=int, metavar=("OPEN", "GROW"), default=None,
+                    help="box radii of the opening and the growth of the occluder plane (default 1 3)")
     ap.add_argument("--mutual_occlusion", action="store_true",
                     help="--template mesh: objects whose --query paths are equal share an image; the pixels where another of "
                          "them lies in front leave an object's mask and gate its points")
@@ -734,6 +923,32 @@ def _per_object(values, k: int, K: int, flag: str):
     if len(values) not in (1, K):
         raise ValueError(f"{flag} takes one entry per object or one entry for all (got {len(values)} for {K} objects)")
     return values[k if len(values) == K else 0]
+
+
+def sensor_options_from_args(args, k: int, K: int, shared: dict) -> dict:
+    """--depth_refine / --occlusion_mask and their companions -> the two options of object k (``{}`` when both are off).
+    ``shared``: the lookups made so far, by (directory, template, substitution) - objects that agree in the three get ONE
+    lookup object, so that lock-step tracking uploads their frame's image once."""
+    import argparse
+
+    from .pixloc_tracker_r9 import depth_option_from_args, occlusion_option_from_args
+
+    if not (getattr(args, "depth_refine", False) or getattr(args, "occlusion_mask", False)):
+        return {}
+    if args.template != "mesh" or args.reference_points != "template":
+        raise ValueError("--depth_refine and --occlusion_mask go with --template mesh --reference_points template")
+    directory = _per_object(args.sensor_depth_dir, k, K, "--sensor_depth_dir")
+    template = _per_object(args.sensor_depth_template, k, K, "--sensor_depth_template") or "{stem}.png"
+    sub = tuple(args.sensor_depth_sub) if args.sensor_depth_sub else None
+    key = (None if directory is None else os.path.normpath(str(directory)), template, sub)
+    one = argparse.Namespace(depth_refine=args.depth_refine, occlusion_mask=args.occlusion_mask, sensor_depth_dir=directory,
+                             sensor_depth_scale=_per_object(args.sensor_depth_scale, k, K, "--sensor_depth_scale"),
+                             sensor_depth_template=template, sensor_depth_sub=sub, depth_prior=args.depth_prior,
+                             occlusion_delta=_per_object(args.occlusion_delta, k, K, "--occlusion_delta"),
+                             occlusion_radii=args.occlusion_radii, _sensor_lookup=shared.get(key))
+    out = {"depth_refine": depth_option_from_args(one), "occlusion": occlusion_option_from_args(one)}
+    shared[key] = one._sensor_lookup
+    return out
 
 
 def mutual_occlusion_from_args(args) -> Optional[MutualOcclusion]:
@@ -771,7 +986,7 @@ def main(argv=None):
         from ..parallel import bind_to_device_numa
 
         bind_to_device_numa(0)
-    trackers = []
+    trackers, lookups = [], {}
     for k in range(K):
         conf = parse_config_sh(args.config[k]) if args.config else {}
         if args.obj_aabb:
@@ -792,6 +1007,7 @@ def main(argv=None):
                                      mesh_render_ahead=args.mesh_render_ahead)
             template = template_from_args(one)
             reference_sfm = _per_object(args.reference_sfm, k, K, "--reference_sfm")
+            sensor = sensor_options_from_args(args, k, K, lookups)
         except ValueError as e:
             ap.error(str(e))
         trackers.append(PixLocPoseTrackerR9(template=template, reference_sfm=reference_sfm,
@@ -799,7 +1015,7 @@ def main(argv=None):
                                             eval_path=str(args.out_dir[k]), loc_path=str(obj / "pixtrack/aug_nerf_sfm"),
                                             debug=args.debug, unet_precision=args.unet_precision,
                                             uncertainty=args.uncertainty, point_report=args.point_report,
-                                            reference_points=args.reference_points))
+                                            reference_points=args.reference_points, **sensor))
     try:
         mutual = mutual_occlusion_from_args(args)
     except ValueError as e:

@@ -94,7 +94,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         ``T_refined`` is the pose carried forward.  The sensor image is fetched and its upload queued before the frame's
         first launch; a frame with more than 4096 points uses the first 4096 (logged once).  Switches ``render_ahead`` off: the render queued behind the LM launch
         takes its camera from the LM kernel's epilogue, which is no longer the pose the next frame starts from.  Not
-        combined with a relocalizer yet.
+        combined with a relocalizer yet.  With a mesh template the option needs ``reference_points="template"``, whose
+        points lie on the surface the sensor sees.
         ``occlusion``: None (default: nothing changes) or an occlusion.OcclusionMask (a conf, the sensor's scale and a
         ``lookup(frame_name) -> uint16 [H, W]``): on a frame that gets a mask, the pixels where the frame's sensor depth
         image lies in front of the mask view's Depth render - opened and grown, pxt_occlusion_mask - leave the query
@@ -103,7 +104,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         frame without a mask (cold start, after a failed frame) or without a sensor image runs as without the option.
         The history entry gains ``occluded_fraction``, ``n_occluder_pixels``, ``n_points_gated`` and
         ``occlusion_applied`` (None / 0 / 0 / False where no pass ran); ``last_occlusion`` keeps the frame's tensors.
-        The option still refuses a mesh template; the objects of one image that hide each other are lock-step
+        With a mesh template the option needs ``reference_points="template"``: the pass then runs on the float depth
+        plane that setting's frame call draws, whose unit is 1 / depth_q SfM units - depth_q the word [17] of the view
+        record the plane was drawn with - so the quanta are formed per frame (occlusion.mesh_quanta) and the shift is
+        (0, 0); the template's ``render_ahead`` stays usable.  The objects of one image that hide each other are lock-step
         tracking's ``mutual_occlusion`` (multi_object_tracker.py), which feeds the same mask fold and point gate.
         The cost gate, success and ``tracked`` are decided as ever.  ``render_ahead`` stays on: the render queued
         behind the LM launch keeps its float Depth image, and the pass runs in get_mask of the frame that consumes it.
@@ -119,8 +123,9 @@ class PixLocPoseTrackerR9(PoseTracker):
         record (pxt_mesh_render_frame_batch_posed), and used only if the host arrives at the same 20 floats per view.
         Everything downstream of the two images is
         unchanged.  A frame's history gains ``template`` ("mesh") and ``template_supersample``; nothing on the policy
-        path reads them.  Not combined with ``relocalizer``, ``reference_points="render"`` (its mesh counterpart is
-        ``reference_points="template"``), ``depth_refine`` or ``occlusion`` yet (ValueError).
+        path reads them.  Not combined with ``relocalizer`` or ``reference_points="render"`` (its mesh counterpart is
+        ``reference_points="template"``) yet, and with ``depth_refine`` or ``occlusion`` only when
+        ``reference_points="template"`` (ValueError).
         ``reference_sfm``: the directory of the SfM model (the ``ref/`` directory mesh_dataset wrote) in place of
         ``loc_path/aug_sfm``; ``upright_ref_img``: the upright reference image's name in place of $UPRIGHT_REF_IMG."""
         point_report = parse_mode(point_report)  # (a bad value: ValueError before anything is built)
@@ -203,6 +208,9 @@ class PixLocPoseTrackerR9(PoseTracker):
         # (pose object, p3d, slot_valid, record) are the frame's points where lock-step tracking extracted them in one call
         # with the other objects' (multi_object_tracker.py); create_dynamic_reference_image takes them instead of its own call
         self._primed_points = None
+        # (pose object, plain mask, the _occ_frame of an occlusion pass) where lock-step tracking ran the pass of this
+        # frame in one pxt_occlusion_mask_views call with the other objects'; get_mask takes it instead of its own call
+        self._primed_occlusion = None
         self._ref_cam_cache = self._coincide_cache = None
         self.keep_feature_history = False  # the reference leaks one entry per frame (Appendix D.2)
         self.steady_multiscale = [1]  # image scales of a tracked (non-cold-start) frame (:223)
@@ -266,8 +274,11 @@ class PixLocPoseTrackerR9(PoseTracker):
 
             pts = np.array([p.xyz for p in self.localizer.model3d.points3D.values()])
             self._occ_conf = occlusion.conf if not occlusion.conf.relative else occlusion.conf.resolve(points_extent(pts))
-            # sensor_q, delta_q: formed in float64, rounded once (as sensor_evaluation does)
-            self._occ_q = quantize(self._occ_conf.delta, occlusion.sensor_depth_scale, z_scale(self.testbed, self.nerf2sfm))
+            # sensor_q, delta_q: formed in float64, rounded once (as sensor_evaluation does); a mesh template's plane is
+            # scaled by its frame's own depth_q, so its quanta are formed per frame (occlusion.mesh_quanta)
+            if self.template is None:
+                self._occ_q = quantize(self._occ_conf.delta, occlusion.sensor_depth_scale,
+                                       z_scale(self.testbed, self.nerf2sfm))
             self._occ_record = torch.zeros(OCC_RECORD, dtype=torch.int32).pin_memory()
             self._occ_done = torch.cuda.Event()
             self.localizer.refiner.point_gate = self._gate_points
@@ -317,12 +328,16 @@ class PixLocPoseTrackerR9(PoseTracker):
         if reference_points == "render":
             raise ValueError("a mesh template is not combined with reference_points='render' yet (the back-projection "
                              "reads the NeRF renderer's view record)")
-        if depth_refine is not None:
-            raise ValueError("a mesh template is not combined with depth_refine yet (the option is measured and gated "
-                             "on NeRF sequences only)")
-        if occlusion is not None:
-            raise ValueError("a mesh template is not combined with occlusion yet (the pass compares the sensor with the "
-                             "NeRF's Depth render and its depth scale)")
+        # the sensor options read the float depth plane of the query view and refine on points of the sensed surface:
+        # both come with reference_points="template" alone
+        if depth_refine is not None and reference_points != "template":
+            raise ValueError("a mesh template is not combined with depth_refine unless reference_points='template' (its "
+                             "points lie on the surface the sensor sees; the SfM points of a mesh model do not): pass "
+                             "reference_points='template'")
+        if occlusion is not None and reference_points != "template":
+            raise ValueError("a mesh template is not combined with occlusion unless reference_points='template' (the pass "
+                             "compares the sensor with the float depth plane that setting's frame call draws): pass "
+                             "reference_points='template'")
         return template
 
     supports_depth_refine = True  # (the YCB policy does not yet: its refine() does not end in _frame_policy)
@@ -379,6 +394,13 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._depth_sensor = self._depth_dev
         self.sensor_uploads += 1
 
+    def _adopt_depth_sensor(self, query_path, sensor):
+        """_stage_depth_sensor for a frame of lock-step tracking: ``sensor`` is the frame's image on the device (None:
+        the frame has none), staged once by the caller for every tracker that names it (multi_object_tracker.py)."""
+        self._depth_frame_name = query_path
+        self._depth_sensor, self._depth_slot = sensor, 0
+        self._occ_frame = self._primed_occlusion = None
+
     def enable_mutual_occlusion(self):
         """Lock-step tracking draws this tracker's frames as part of a scene (multi_object_tracker.MutualOcclusion): a
         primed frame then carries the plane G of the pixels where another tracked mesh lies in front, which leaves the
@@ -411,23 +433,29 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._mut_done.record(torch.cuda.current_stream(self.device))
         return mask
 
-    def _apply_occlusion(self, mask, depth):
+    def _apply_occlusion(self, mask, depth, view20=None):
         """get_mask's tail with the option on: the frame's plain mask minus the pixels where the sensor image - staged
         before the frame's first launch - lies in front of the mask view's Depth render.  Two launches on the frame's
         stream, nothing awaited; the pinned record is read in _frame_policy.  The plain mask as it is when the option
-        is off, the frame has no sensor image or no float Depth image came with the mask."""
+        is off, the frame has no sensor image or no float Depth image came with the mask.  ``view20``: ``depth`` is a
+        mesh template's float plane and this the view record it was drawn with - its word [17], depth_q, scales the
+        plane, so the quanta are this frame's, and the view has the camera's true cx, cy: no shift."""
         if self.occlusion is None or self._depth_sensor is None or depth is None:
             return mask
-        from ..occlusion import alignment, occlusion_mask
+        from ..occlusion import alignment, mesh_quanta, occlusion_mask
 
         sensor, conf = self._depth_sensor, self._occ_conf
         H, W = int(depth.shape[0]), int(depth.shape[1])
         if tuple(sensor.shape) != (H, W):
             raise ValueError(f"the sensor depth image of {self._depth_frame_name} is {tuple(sensor.shape)}, the query "
                              f"{(H, W)}")
-        if self._occ_shift is None or self._occ_shift[0] is not self.camera:
-            self._occ_shift = (self.camera, alignment(self.camera, conf.allow_misaligned))
-        sx, sy, _ = self._occ_shift[1]
+        if view20 is not None:
+            sx = sy = 0
+            self._occ_q = mesh_quanta(conf.delta, self.occlusion.sensor_depth_scale, view20)
+        else:
+            if self._occ_shift is None or self._occ_shift[0] is not self.camera:
+                self._occ_shift = (self.camera, alignment(self.camera, conf.allow_misaligned))
+            sx, sy, _ = self._occ_shift[1]
         if self._occ_ws is None or self._occ_ws[0] != (W, H):
             self._occ_ws = ((W, H), torch.empty(int(_lib.lib().pxt_occlusion_mask_workspace_bytes(W, H)), dtype=torch.uint8,
                                                  device=self.device))
@@ -436,9 +464,34 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._occ_frame = {"depth": depth, "sensor": sensor, "mask_in": mask, "mask": out["mask"],
                            "occluder": out["occluder"], "shift": (sx, sy), "min_alpha": conf.min_alpha,
                            "sensor_q": self._occ_q[0], "delta_q": self._occ_q[1], "radii": (conf.r_open, conf.r_grow),
-                           "gates": [], "record_buffer": self._occ_record, "done": self._occ_done}
+                           "gates": [], "record_buffer": self._occ_record, "done": self._occ_done, "view": view20}
         self._occ_done.record(torch.cuda.current_stream(self.device))
         return out["mask"]
+
+    def _apply_template_occlusion(self, mask, pose):
+        """_apply_occlusion on a mesh template's frame: the plane and the record are the ones ``_fused_depth`` holds
+        for ``pose`` (drawn by this frame's call, or by the verified call queued behind the last LM launch)."""
+        primed, self._primed_occlusion = self._primed_occlusion, None
+        if primed is not None and primed[0] is pose and self.occlusion is not None:
+            self._occ_frame = primed[2]
+            return primed[2]["mask"]
+        held = self._fused_depth
+        if self.occlusion is None or held is None or held[0] is not pose:
+            return mask
+        return self._apply_occlusion(mask, held[1], view20=held[2])
+
+    def _occlusion_view(self, depth, view20):
+        """What one view of a batched occlusion pass takes from this tracker for a mesh template's plane and its view
+        record: (sensor, (sensor_q, delta_q)); None when the option is off or the frame has no sensor image."""
+        if self.occlusion is None or self._depth_sensor is None:
+            return None
+        from ..occlusion import mesh_quanta
+
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        if tuple(self._depth_sensor.shape) != (H, W):
+            raise ValueError(f"the sensor depth image of {self._depth_frame_name} is {tuple(self._depth_sensor.shape)}, "
+                             f"the query {(H, W)}")
+        return self._depth_sensor, mesh_quanta(self._occ_conf.delta, self.occlusion.sensor_depth_scale, view20)
 
     def _gate_points(self, ref, T_init, qcamera):
         """The refiner's point_gate: the LM's point mask of a frame whose occlusion pass ran - ref.valid minus the
@@ -466,10 +519,23 @@ class PixLocPoseTrackerR9(PoseTracker):
         them, on the sensor image `_stage_depth_sensor` uploaded.  None when the frame has no depth image (its pose
         stays the LM's).  A frame refined against several references queues one problem per reference; `_frame_policy`
         waits for all of them, so that the records and the sensor buffer are free when the next frame begins."""
-        from ..depth_refinement import MAX_POINTS, RECORD, depth_refine_batch
+        from ..depth_refinement import depth_refine_batch
 
-        opt = self.depth_refine
-        sensor = self._depth_sensor
+        item = self._depth_problem(prob, pending, qcamera)
+        if item is None:
+            return None
+        if self._depth_ws is None:
+            self._depth_ws = torch.zeros(int(_lib.lib().pxt_depth_refine_workspace_bytes(1)), dtype=torch.uint8,
+                                         device=self.device)
+        return depth_refine_batch([item[0]], self._depth_conf, workspace=self._depth_ws, records=[item[1]])
+
+    def _depth_problem(self, prob, pending, qcamera):
+        """The problem _enqueue_depth_refine would launch, for a caller that launches the problems of several trackers
+        in ONE pxt_depth_refine call (lock-step tracking): -> (problem dict, its pinned record), or None when the
+        frame has no depth image."""
+        from ..depth_refinement import MAX_POINTS, RECORD
+
+        opt, sensor = self.depth_refine, self._depth_sensor
         if sensor is None:
             return None
         w, h = (int(round(float(x))) for x in qcamera.size.tolist())
@@ -482,16 +548,12 @@ class PixLocPoseTrackerR9(PoseTracker):
             logger.warning(f"depth_refine: {ref.p3d.shape[0]} points in a frame, the first {MAX_POINTS} are used")
         valid = prob.get("mask") if prob.get("mask") is not None else ref.valid  # (the occlusion option's gated mask)
         p3d, mask = ref.p3d[:MAX_POINTS], (None if valid is None else valid[:MAX_POINTS])
-        if self._depth_ws is None:
-            self._depth_ws = torch.zeros(int(_lib.lib().pxt_depth_refine_workspace_bytes(1)), dtype=torch.uint8,
-                                         device=self.device)
         if self._depth_slot == len(self._depth_recs):
             self._depth_recs.append(torch.zeros(RECORD, dtype=torch.float32).pin_memory())
         rec = self._depth_recs[self._depth_slot]
         self._depth_slot += 1
-        return depth_refine_batch([dict(points=p3d, mask=mask, sensor=sensor, sensor_scale=float(opt.sensor_depth_scale),
-                                        camera=qcamera, pose=pending, prior=opt.prior)], self._depth_conf,
-                                  workspace=self._depth_ws, records=[rec])
+        return dict(points=p3d, mask=mask, sensor=sensor, sensor_scale=float(opt.sensor_depth_scale), camera=qcamera,
+                    pose=pending, prior=opt.prior), rec
 
     def _initial_reference_ids(self, assets):
         """r9: the upright reference image named by $UPRIGHT_REF_IMG (:77-78)."""
@@ -737,12 +799,14 @@ class PixLocPoseTrackerR9(PoseTracker):
                 if self.template is not None:  # depth = (the query view's depth plane, the host's bit-equal view record)
                     self._fused_depth = (pose, *depth) if (depth is not None and self.reference_points == "template") else None
                     self._last_depth = None
-                    return mask
+                    return self._apply_template_occlusion(mask, pose)
                 self._fused_depth = (pose, depth) if (depth is not None and self.reference_points == "render") else None
                 return self._apply_occlusion(mask, depth)
             self.renders_ahead_stale += 1
         self._ahead_ok = None
         mask = self._mask_and_reference(pose, from_slot=False)[0]
+        if self.template is not None:
+            return self._apply_template_occlusion(mask, pose)
         return self._apply_occlusion(mask, self._last_depth)
 
     def _frame_views(self):
@@ -781,7 +845,9 @@ class PixLocPoseTrackerR9(PoseTracker):
                 depth = (pose, plane, requests[0][0])
             else:
                 nz, ref_u8 = self.template.frame(pose, self.camera, self._reference_camera())
-            mask = self._mask_of(nz)
+            occ = self._primed_occlusion
+            # (a primed occlusion pass of this pose was fed the plain mask of this very plane: not made again)
+            mask = occ[1] if (occ is not None and pose is not None and occ[0] is pose) else self._mask_of(nz)
             if mutual is not None:
                 mask = self._apply_mutual_occlusion(mask, mutual)
             self._last_depth = None
@@ -961,7 +1027,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         query_path, query_image = query
         refiner = self.localizer.refiner
         self._depth_frame_name = query_path
-        self._occ_frame = self._mut_frame = None
+        self._occ_frame = self._mut_frame = self._primed_occlusion = None
         if self.depth_refine is not None or self.occlusion is not None:
             self._stage_depth_sensor(query_path)
         self._frame_setup(query)
@@ -1094,8 +1160,8 @@ class PixLocPoseTrackerR9(PoseTracker):
             # it is waited for only on a frame that ended before any LM launch)
             frame, self._occ_frame = self._occ_frame, None
             if frame is not None:
-                self._occ_done.synchronize()
-            rec = None if frame is None else [int(x) for x in self._occ_record.tolist()]
+                frame["done"].synchronize()
+            rec = None if frame is None else [int(x) for x in frame["record_buffer"].tolist()]
             ret["occluded_fraction"] = None if rec is None else (rec[2] / rec[0] if rec[0] else 0.0)
             ret["n_occluder_pixels"] = 0 if rec is None else rec[4]
             ret["n_points_gated"] = 0 if rec is None else rec[9] - rec[10]
@@ -1186,7 +1252,7 @@ def build_parser() -> argparse.ArgumentParser:
                              "mesh: the same lattice of the depth plane the mesh template draws for the frame)")
     parser.add_argument("--depth_refine", action="store_true",
                         help="refine every frame's pose on its sensor depth image after the LM (needs --sensor_depth_dir "
-                             "and --sensor_depth_scale)")
+                             "and --sensor_depth_scale; with --template mesh: --reference_points template)")
     parser.add_argument("--sensor_depth_dir", type=Path, default=None, help="the 16-bit depth images, one per frame")
     parser.add_argument("--sensor_depth_scale", type=float, default=None, help="SfM units per raw count")
     parser.add_argument("--sensor_depth_template", default="{stem}.png",
@@ -1197,7 +1263,8 @@ def build_parser() -> argparse.ArgumentParser:
                         help="diagonal prior on the depth refinement's accumulated update: translation, rotation weight")
     parser.add_argument("--occlusion_mask", action="store_true",
                         help="take the pixels where the sensor depth image lies in front of the object out of every "
-                             "frame's mask and point set (needs --sensor_depth_dir and --sensor_depth_scale)")
+                             "frame's mask and point set (needs --sensor_depth_dir and --sensor_depth_scale; with "
+                             "--template mesh: --reference_points template)")
     parser.add_argument("--occlusion_delta", type=float, default=None,
                         help="how much closer the sensor's surface must be, as a fraction of the model's extent (default 0.1)")
     parser.add_argument("--occlusion_radii", nargs=2, type=int, metavar=("OPEN", "GROW"), default=None,
