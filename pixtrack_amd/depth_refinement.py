@@ -497,8 +497,7 @@ def depth_refine_batch(problems: Sequence[Dict], conf: DepthRefineConf, workspac
             staged = torch.zeros(16, dtype=torch.float32).pin_memory()
             staged[:12] = T
             poses.append(staged)
-    recs = list(records) if records is not None else [torch.zeros(RECORD, dtype=torch.float32).pin_memory()
-                                                      for _ in range(K)]
+    recs = list(records if records is not None else torch.zeros(K, RECORD, dtype=torch.float32).pin_memory())
     if len(recs) != K or any(r.dtype != torch.float32 or r.numel() < RECORD or not r.is_pinned() for r in recs):
         raise ValueError(f"records: {K} pinned float32 tensors of {RECORD} floats")
     logs = [torch.zeros(conf.num_iters, LOG_STRIDE, dtype=torch.float32, device=dev) if want_log else None

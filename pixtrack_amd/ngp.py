@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from .ops import ops
+from .pinned import PinnedRing
 
 N_MLP_PARAMS = 64 * 32 + 16 * 64 + 64 * 32 + 64 * 64 + 16 * 64
 MLP_SHAPES = [("d1", 64, 32), ("d2", 16, 64), ("c1", 64, 32), ("c2", 64, 64), ("c3", 16, 64)]
@@ -370,18 +371,11 @@ class Testbed:
         self._stats = None
         self.stats_accum = None
         self.n_renders = 0
-        self._cam_ring = None  # pinned camera records of pose-driven renders (see _next_cam_out)
-        self._cam_next = 0
+        self._cam_ring = PinnedRing((16,), torch.float32)  # camera records of pose-driven renders (see _next_cam_out)
 
     def _next_cam_out(self) -> torch.Tensor:
-        """A pinned 16-float record for the camera kernel of a pose-driven render.  The kernel receives the raw
-        pointer, so torch's host allocator cannot know when the block is free again; the records therefore live
-        as long as the testbed and are recycled round-robin - eight of them, at most two are written per frame and
-        a frame's kernels have finished (its LM result was read) long before eight more renders are queued."""
-        if self._cam_ring is None:
-            self._cam_ring = [torch.zeros(16, dtype=torch.float32).pin_memory() for _ in range(8)]
-        buf = self._cam_ring[self._cam_next]
-        self._cam_next = (self._cam_next + 1) % len(self._cam_ring)
+        """A pinned 16-float record, zeroed, for the camera kernel of a pose-driven render (at most two per frame)."""
+        buf = self._cam_ring.next()
         buf.zero_()
         return buf
 

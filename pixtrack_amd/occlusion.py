@@ -243,6 +243,17 @@ def decode_record(rec) -> Dict[str, int]:
     return {name: int(r[i]) for i, name in enumerate(RECORD_NAMES)}
 
 
+def pass_frame(depth, sensor, mask_in, mask, occluder, shift, min_alpha, quanta, radii, record_buffer, done, view) -> Dict:
+    """What a tracker keeps of one occlusion pass (one ``occlusion_mask`` call, or one view of an
+    ``occlusion_mask_views`` call): its inputs, its two planes, the pinned record its launches count in and the event
+    recorded behind them.  The point gate appends to ``gates`` and counts in the same record; the frame's policy adds
+    ``record`` (the decoded words) and exposes the dict as ``last_occlusion``.  ``view``: the view record a mesh
+    template's ``depth`` plane was drawn with (None for a NeRF Depth render)."""
+    return {"depth": depth, "sensor": sensor, "mask_in": mask_in, "mask": mask, "occluder": occluder, "shift": shift,
+            "min_alpha": min_alpha, "sensor_q": quanta[0], "delta_q": quanta[1], "radii": radii, "gates": [],
+            "record_buffer": record_buffer, "done": done, "view": view}
+
+
 # --------------------------------------------------------------------------------------------------------- GPU
 def occlusion_mask(depth, sensor, mask_in, shift, min_alpha: float, sensor_q: float, delta_q: float, r_open: int,
                    r_grow: int, mask=None, occluder=None, record=None, workspace=None) -> Dict:

@@ -52,6 +52,7 @@ import torch
 from .. import _lib
 from ..ops import ops
 from ..optimizer import PixTrackOptimizer
+from ..pinned import PinnedRing, SensorStage
 from ..tracker import DebugTracker
 from ..point_report import parse_mode
 from .pixloc_tracker_r9 import PixLocPoseTrackerR9
@@ -77,10 +78,31 @@ def _same_scene_camera(a, b) -> bool:
     return bool(torch.equal(da[:6], db[:6]) and not da[6:].any() and not db[6:].any())
 
 
+def _chunks_by(items, key, limit: int):
+    """What the step's batched calls share: ``items`` grouped by ``key(item)`` - the settings one call holds for all its
+    views or problems; keys in first-seen order, compared with ``==`` - and each group cut into chunks of at most
+    ``limit``, one chunk per call.  Yields (key, chunk)."""
+    groups: list = []
+    for item in items:
+        k = key(item)
+        for k0, members in groups:
+            if k0 == k:
+                members.append(item)
+                break
+        else:
+            groups.append((k, [item]))
+    for k, members in groups:
+        for a in range(0, len(members), limit):
+            yield k, members[a:a + limit]
+
+
 class _Group:
     """The objects whose device work is merged: one stream, one UNet context (workspace), one LM batch workspace."""
 
     def __init__(self, index, members, stream, model):
+        from ..mesh_render import VIEW_OUT
+        from ..occlusion import MAX_VIEWS as OCC_MAX_VIEWS, RECORD as OCC_RECORD
+
         self.index, self.members, self.stream, self.model = index, members, stream, model
         self.batch_ws: Optional[torch.Tensor] = None
         self.info_ws: Optional[torch.Tensor] = None  # parameter records and partial sums of the step's information launch
@@ -88,15 +110,13 @@ class _Group:
         self.render_ws: Optional[torch.Tensor] = None  # parameter records of the batched render chain
         self.mesh_ws = None  # mesh_render.FrameBatchWorkspace of the group's mesh-template frames (made on first use)
         self.points_ws: Optional[torch.Tensor] = None  # workspace of the step's pxt_points_from_depth_views call(s)
-        self.points_records = None  # pinned [16, 4] records of those calls, recycled round-robin
-        self.points_next = 0
+        self.points_records = PinnedRing((_lib.PXT_POINTS_MAX_VIEWS, 4), torch.int32)  # the records of those calls
         self.occ_ws: Optional[torch.Tensor] = None  # workspace of the step's pxt_occlusion_mask_views call(s)
-        self.occ_records = None  # pinned [16, 16] records of those calls, recycled round-robin
-        self.occ_next = 0
+        self.occ_records = PinnedRing((OCC_MAX_VIEWS, OCC_RECORD), torch.int32)  # the records of those calls
         self.depth_ws: Optional[torch.Tensor] = None  # workspace of the step's pxt_depth_refine call(s)
-        self.sensor_slots: list = []  # per distinct sensor image of a step: (pinned buffer, device buffer, upload event)
-        self.ahead_rows = None  # pinned views_out blocks of the group's MeshTemplate.frames_ahead calls, recycled round-robin
-        self.ahead_next = 0
+        self.sensor_slots: List[SensorStage] = []  # one per distinct sensor image of a step
+        # views_out blocks of the group's MeshTemplate.frames_ahead calls (a step's rows are read at that step's end)
+        self.ahead_rows = PinnedRing((64, VIEW_OUT), torch.float32)
         self.unet_done: Optional[torch.cuda.Event] = None
         self.pend = None  # what _enqueue left for _finish
 
@@ -387,8 +407,7 @@ class MultiObjectTracker:
             if self.mutual_occlusion is not None and tr.template is not None:
                 # (a step's scenes are formed from who takes the lock-step path in THAT step: not drawn ahead)
                 tr.localizer.refiner.after_lm_enqueued = None
-            ref_u8 = tr.get_reference_image(tr.pose)
-            tr._fused_reference = (tr.pose, ref_u8)  # get_dynamic_id asks for it again: the same tensor object
+            ref_u8 = tr.get_reference_image(tr.pose, keep=True)  # (get_dynamic_id asks again: the same tensor object)
             live.append((k, tr, frame, ref_u8))
         self._mark("renders_enqueued")
         if not live:
@@ -492,12 +511,12 @@ class MultiObjectTracker:
                 if self.trackers[k].template is not None and self._takes_lockstep(self.trackers[k], frames[k])]
         # a tracker whose frame was drawn ahead, behind the last step's LM launch, and verified for its pose keeps that
         # frame (its get_mask takes it); with "template" points its plane still joins the step's one points call
-        ahead = [tr for tr in part if self._served_ahead(tr)]
-        part = [tr for tr in part if not any(tr is a for a in ahead)]
-        ahead_points = [(tr, *tr._ahead_ok[4]) for tr in ahead if tr.reference_points == "template" and tr._ahead_ok[4] is not None]
+        ahead = [(tr, tr.verified_ahead()) for tr in part]
+        part = [tr for tr, ok in ahead if ok is None]
+        ahead = [(tr, ok) for tr, ok in ahead if ok is not None]
+        ahead_points = [(tr, ok.depth, ok.view) for tr, ok in ahead if tr.reference_points == "template" and ok.depth is not None]
         # the occlusion option's pass for the trackers that take a mask this step: their planes, with the plain masks
-        ahead_occ = [(tr, tr._ahead_ok[1], *tr._ahead_ok[4]) for tr in ahead
-                     if self._takes_occlusion(tr) and tr._ahead_ok[4] is not None]
+        ahead_occ = [(tr, ok.mask, ok.depth, ok.view) for tr, ok in ahead if self._takes_occlusion(tr) and ok.depth is not None]
         if not part:  # (NeRF trackers only: nothing of the mesh path is touched; or every mesh frame was drawn ahead)
             if ahead_points:
                 self._prime_template_points(grp, ahead_points)
@@ -516,7 +535,7 @@ class MultiObjectTracker:
         if any(want_depth):  # (never with mutual_occlusion: refused at construction)
             planes = MeshTemplate.frames(*views, workspace=grp.mesh_ws, want_depth=want_depth)
             for tr, (nz, ref_u8, _depth, _view) in zip(part, planes):
-                tr._primed_frame = (tr.pose, nz, ref_u8)
+                tr.prime(tr.pose, depth_nz=nz, ref_u8=ref_u8)
             self._prime_template_points(grp, ahead_points + [(tr, depth, view) for tr, (_nz, _ref, depth, view)
                                                              in zip(part, planes) if depth is not None])
             self._prime_occlusion(grp, ahead_occ + [(tr, tr._mask_of(nz), depth, view) for tr, (nz, _ref, depth, view)
@@ -526,19 +545,12 @@ class MultiObjectTracker:
             self._prime_template_points(grp, ahead_points)
         if scenes is None:  # (also: no scene has two members in this step - the call is the one made without the option)
             for tr, (nz, ref_u8) in zip(part, MeshTemplate.frames(*views, workspace=grp.mesh_ws)):
-                tr._primed_frame = (tr.pose, nz, ref_u8)
+                tr.prime(tr.pose, depth_nz=nz, ref_u8=ref_u8)
             return
         planes = MeshTemplate.frames(*views, workspace=grp.mesh_ws, scenes=scenes, r_grow=int(self.mutual_occlusion.r_grow),
                                      records=True)
         for tr, (nz, ref_u8, occluder, record) in zip(part, planes):
-            tr._primed_frame = (tr.pose, nz, ref_u8, None if occluder is None else (occluder, record))
-
-    @staticmethod
-    def _served_ahead(tr) -> bool:
-        """The tracker holds a frame that was drawn ahead and verified for its present pose and view settings (what its
-        get_mask will take this step)."""
-        ok = tr._ahead_ok
-        return bool(tr.success and ok is not None and ok[0] is tr.pose and ok[3] == tr._ahead_views_now())
+            tr.prime(tr.pose, depth_nz=nz, ref_u8=ref_u8, mutual=None if occluder is None else (occluder, record))
 
     def _mesh_frames_ahead(self, grp: _Group) -> set:
         """The next frames of the group's mesh trackers whose hook is the mesh render-ahead, behind the batched LM launch
@@ -547,23 +559,17 @@ class MultiObjectTracker:
         served."""
         items = []
         for k, tr, path, ref_id, dbg, status, x, handle in grp.pend:
-            hook = getattr(tr.localizer.refiner, "after_lm_enqueued", None)
-            if handle is not None and hook is not None and getattr(hook, "__func__", None) is PixLocPoseTrackerR9._render_ahead_mesh:
+            if handle is not None and tr.armed_ahead() == "mesh":
                 items.append((k, tr, handle, *tr._render_ahead_mesh_request()))
         if not items:
             return set()
-        from ..mesh_render import VIEW_OUT, W_VIEW_DONE, FrameBatchWorkspace
+        from ..mesh_render import W_VIEW_DONE, FrameBatchWorkspace
         from ..mesh_template import MeshTemplate
 
         if grp.mesh_ws is None:
             grp.mesh_ws = FrameBatchWorkspace()
         n_views = sum(len(requests) for _k, _tr, _h, requests, _d, _keys in items)
-        if grp.ahead_rows is None or grp.ahead_rows[0].shape[0] < n_views:
-            # the kernel receives the raw pointer: the blocks live as long as the group and are recycled - a step's rows
-            # are read at that step's end
-            grp.ahead_rows = [torch.zeros(max(64, n_views), VIEW_OUT, dtype=torch.float32).pin_memory() for _ in range(8)]
-        rows = grp.ahead_rows[grp.ahead_next][:n_views]
-        grp.ahead_next = (grp.ahead_next + 1) % len(grp.ahead_rows)
+        rows = grp.ahead_rows.next(n_views)
         rows[:, W_VIEW_DONE] = 0.0
         planes = MeshTemplate.frames_ahead([tr.template for _k, tr, *_ in items], [h.buf for _k, _tr, h, *_ in items],
                                            [tr.camera for _k, tr, *_ in items], [tr._reference_camera() for _k, tr, *_ in items],
@@ -572,7 +578,7 @@ class MultiObjectTracker:
         self.mesh_ahead_calls += 1
         first = 0
         for (k, tr, _h, requests, _d, keys), out in zip(items, planes):
-            tr._render_ahead_mesh_accept(rows[first:first + len(requests)], out if out[-1] is not None else out[:2], keys)
+            tr._render_ahead_mesh_accept(rows[first:first + len(requests)], keys, *out)
             first += len(requests)
         return {k for k, *_ in items}
 
@@ -581,38 +587,29 @@ class MultiObjectTracker:
         points in ONE pxt_points_from_depth_views call behind the frame call (one per distinct (n_max, erode, min_alpha),
         normally one; more than 16 views in chunks); each tracker keeps its (pose, p3d, slot_valid, record), which its
         get_dynamic_id consumes in phase C instead of extracting again."""
-        by_conf: dict = {}
-        for item in items:
+        def settings(item):
             conf = item[0].localizer.refiner.conf
-            key = (int(conf.reference_points_max), int(conf.reference_points_erode), float(conf.reference_points_min_alpha))
-            by_conf.setdefault(key, []).append(item)
+            return int(conf.reference_points_max), int(conf.reference_points_erode), float(conf.reference_points_min_alpha)
+
         L, C = _lib.lib(), _lib.C
-        for (n_max, erode, min_alpha), members in by_conf.items():
-            for a in range(0, len(members), _lib.PXT_POINTS_MAX_VIEWS):
-                chunk = members[a:a + _lib.PXT_POINTS_MAX_VIEWS]
-                n = len(chunk)
-                sizes = [x for _tr, depth, _v in chunk for x in (int(depth.shape[1]), int(depth.shape[0]))]
-                need = int(L.pxt_points_from_depth_views_workspace_bytes(n, (C.c_int32 * (2 * n))(*sizes)))
-                if need <= 0:
-                    raise _lib.PxtError(f"depth planes of {sizes} are not supported by pxt_points_from_depth_views")
-                # (one workspace serves one call at a time: the group's calls follow each other on its stream)
-                if grp.points_ws is None or grp.points_ws.numel() < need:
-                    grp.points_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                if grp.points_records is None:
-                    # the kernel receives the raw pointer: the records live as long as the group and are recycled - a
-                    # step's were read (in its _frame_policy) long before eight more calls are queued
-                    grp.points_records = [torch.zeros(_lib.PXT_POINTS_MAX_VIEWS, 4, dtype=torch.int32).pin_memory()
-                                          for _ in range(8)]
-                record = grp.points_records[grp.points_next][:n]
-                grp.points_next = (grp.points_next + 1) % len(grp.points_records)
-                p3d = torch.empty(n, n_max, 3, dtype=torch.float32, device=self.device)
-                slot_valid = torch.empty(n, n_max, dtype=torch.uint8, device=self.device)
-                ops.points_from_depth_views([depth for _tr, depth, _v in chunk],
-                                            [float(x) for _tr, _d, view in chunk for x in view.reshape(-1)], min_alpha, erode,
-                                            n_max, p3d, slot_valid, record, grp.points_ws)
-                self.points_calls += 1
-                for i, (tr, _depth, _view) in enumerate(chunk):
-                    tr._primed_points = (tr.pose, p3d[i], slot_valid[i], record[i])
+        for (n_max, erode, min_alpha), chunk in _chunks_by(items, settings, _lib.PXT_POINTS_MAX_VIEWS):
+            n = len(chunk)
+            sizes = [x for _tr, depth, _v in chunk for x in (int(depth.shape[1]), int(depth.shape[0]))]
+            need = int(L.pxt_points_from_depth_views_workspace_bytes(n, (C.c_int32 * (2 * n))(*sizes)))
+            if need <= 0:
+                raise _lib.PxtError(f"depth planes of {sizes} are not supported by pxt_points_from_depth_views")
+            # (one workspace serves one call at a time: the group's calls follow each other on its stream)
+            if grp.points_ws is None or grp.points_ws.numel() < need:
+                grp.points_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            record = grp.points_records.next(n)  # (read in the step's _frame_policy)
+            p3d = torch.empty(n, n_max, 3, dtype=torch.float32, device=self.device)
+            slot_valid = torch.empty(n, n_max, dtype=torch.uint8, device=self.device)
+            ops.points_from_depth_views([depth for _tr, depth, _v in chunk],
+                                        [float(x) for _tr, _d, view in chunk for x in view.reshape(-1)], min_alpha, erode,
+                                        n_max, p3d, slot_valid, record, grp.points_ws)
+            self.points_calls += 1
+            for i, (tr, _depth, _view) in enumerate(chunk):
+                tr.prime(tr.pose, points=(p3d[i], slot_valid[i], record[i]))
 
     @staticmethod
     def _takes_occlusion(tr) -> bool:
@@ -625,8 +622,6 @@ class MultiObjectTracker:
         with ``depth_refine`` or ``occlusion``.  Trackers whose options name the same ``lookup`` object and the same
         frame name share ONE staged image - the K objects of one RGB-D frame: one fetch, one upload
         (``sensor_uploads`` counts images).  A tracker that runs the step alone stages its own (run_single_frame)."""
-        import numpy as np
-
         staged = {}
         for k in grp.members:
             tr, frame = self.trackers[k], frames[k]
@@ -640,25 +635,11 @@ class MultiObjectTracker:
             if key not in staged:
                 sensor = option.lookup(name)
                 if sensor is not None:
-                    sensor = np.ascontiguousarray(np.asarray(sensor))
-                    if sensor.dtype != np.uint16 or sensor.ndim != 2:
-                        raise ValueError(f"the sensor depth image of {frame[0]} is {sensor.dtype} {sensor.shape}, not "
-                                         "uint16 [H, W]")
                     slot = sum(v is not None for v in staged.values())
                     if slot == len(grp.sensor_slots):
-                        grp.sensor_slots.append(None)
-                    buf = grp.sensor_slots[slot]
-                    if buf is None or tuple(buf[0].shape) != sensor.shape:
-                        buf = grp.sensor_slots[slot] = (torch.empty(sensor.shape, dtype=torch.int16).pin_memory(),
-                                                        torch.empty(sensor.shape, dtype=torch.int16, device=self.device),
-                                                        torch.cuda.Event())
-                    else:
-                        buf[2].synchronize()  # (the last step's upload: over long ago)
-                    buf[0].numpy()[...] = sensor.view(np.int16)
-                    buf[1].copy_(buf[0], non_blocking=True)
-                    buf[2].record(torch.cuda.current_stream(self.device))
+                        grp.sensor_slots.append(SensorStage(self.device))
+                    sensor = grp.sensor_slots[slot].upload(sensor, frame[0])
                     self.sensor_uploads += 1
-                    sensor = buf[1]
                 staged[key] = sensor
             tr._adopt_depth_sensor(frame[0], staged[key])
 
@@ -672,43 +653,34 @@ class MultiObjectTracker:
             return
         from .. import occlusion as OC
 
-        by_conf: dict = {}
-        for item in items:
+        def settings(item):
             conf = item[0]._occ_conf
-            by_conf.setdefault((float(conf.min_alpha), int(conf.r_open), int(conf.r_grow)), []).append(item)
+            return float(conf.min_alpha), int(conf.r_open), int(conf.r_grow)
+
         L, C = _lib.lib(), _lib.C
-        for (min_alpha, r_open, r_grow), members in by_conf.items():
-            for a in range(0, len(members), OC.MAX_VIEWS):
-                chunk = members[a:a + OC.MAX_VIEWS]
-                n = len(chunk)
-                per_view = [tr._occlusion_view(depth, view) for tr, _m, depth, view in chunk]
-                sizes = [x for _tr, _m, depth, _v in chunk for x in (int(depth.shape[1]), int(depth.shape[0]))]
-                need = int(L.pxt_occlusion_mask_views_workspace_bytes(n, (C.c_int32 * (2 * n))(*sizes)))
-                if need <= 0:
-                    raise _lib.PxtError(f"depth planes of {sizes} are not supported by pxt_occlusion_mask_views")
-                # (one workspace serves one call at a time: the group's calls follow each other on its stream)
-                if grp.occ_ws is None or grp.occ_ws.numel() < need:
-                    grp.occ_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                if grp.occ_records is None:
-                    # the kernels receive the raw pointer: the records live as long as the group and are recycled - a
-                    # step's are read (in its _frame_policy) long before eight more calls are queued
-                    grp.occ_records = [torch.zeros(OC.MAX_VIEWS, OC.RECORD, dtype=torch.int32).pin_memory() for _ in range(8)]
-                records = grp.occ_records[grp.occ_next][:n]
-                grp.occ_next = (grp.occ_next + 1) % len(grp.occ_records)
-                out = OC.occlusion_mask_views([depth for _tr, _m, depth, _v in chunk], [s for s, _q in per_view],
-                                              [m for _tr, m, _d, _v in chunk], [(0, 0)] * n, min_alpha,
-                                              [q for _s, q in per_view], r_open, r_grow, records=records,
-                                              workspace=grp.occ_ws)
-                self.occlusion_view_calls += 1
-                cur = torch.cuda.current_stream(self.device)
-                for i, (tr, mask_in, depth, view) in enumerate(chunk):
-                    sensor, (sensor_q, delta_q) = per_view[i]
-                    frame = {"depth": depth, "sensor": sensor, "mask_in": mask_in, "mask": out["masks"][i],
-                             "occluder": out["occluders"][i], "shift": (0, 0), "min_alpha": min_alpha,
-                             "sensor_q": sensor_q, "delta_q": delta_q, "radii": (r_open, r_grow), "gates": [],
-                             "record_buffer": records[i], "done": tr._occ_done, "view": view}
-                    tr._occ_done.record(cur)
-                    tr._primed_occlusion = (tr.pose, mask_in, frame)
+        for (min_alpha, r_open, r_grow), chunk in _chunks_by(items, settings, OC.MAX_VIEWS):
+            n = len(chunk)
+            per_view = [tr._occlusion_view(depth, view) for tr, _m, depth, view in chunk]
+            sizes = [x for _tr, _m, depth, _v in chunk for x in (int(depth.shape[1]), int(depth.shape[0]))]
+            need = int(L.pxt_occlusion_mask_views_workspace_bytes(n, (C.c_int32 * (2 * n))(*sizes)))
+            if need <= 0:
+                raise _lib.PxtError(f"depth planes of {sizes} are not supported by pxt_occlusion_mask_views")
+            # (one workspace serves one call at a time: the group's calls follow each other on its stream)
+            if grp.occ_ws is None or grp.occ_ws.numel() < need:
+                grp.occ_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            records = grp.occ_records.next(n)  # (read in the step's _frame_policy)
+            out = OC.occlusion_mask_views([depth for _tr, _m, depth, _v in chunk], [s for s, _q in per_view],
+                                          [m for _tr, m, _d, _v in chunk], [(0, 0)] * n, min_alpha,
+                                          [q for _s, q in per_view], r_open, r_grow, records=records,
+                                          workspace=grp.occ_ws)
+            self.occlusion_view_calls += 1
+            cur = torch.cuda.current_stream(self.device)
+            for i, (tr, mask_in, depth, view) in enumerate(chunk):
+                sensor, quanta = per_view[i]
+                frame = OC.pass_frame(depth, sensor, mask_in, out["masks"][i], out["occluders"][i], (0, 0), min_alpha,
+                                      quanta, (r_open, r_grow), records[i], tr._occ_done, view)
+                tr._occ_done.record(cur)
+                tr.prime(tr.pose, occlusion=frame)
 
     def _enqueue_depth_refinements(self, grp: _Group) -> None:
         """Behind the step's batched LM launch: ONE pxt_depth_refine call with the problems of all the group's trackers
@@ -716,30 +688,22 @@ class MultiObjectTracker:
         on the device; each tracker's _frame_policy reads its own record."""
         from ..depth_refinement import MAX_PROBLEMS, depth_refine_batch
 
-        by_conf = []
+        asked = []
         for _k, tr, _p, _r, _d, status, x, handle in grp.pend:
             if status != "lm" or tr.depth_refine is None:
                 continue
             item = tr._depth_problem(x, handle, tr.camera)
-            if item is None:  # (the frame has no depth image: its pose stays the LM's)
-                continue
-            for conf, members in by_conf:
-                if conf == tr._depth_conf:
-                    members.append((x, item))
-                    break
-            else:
-                by_conf.append((tr._depth_conf, [(x, item)]))
-        for conf, members in by_conf:
-            for a in range(0, len(members), MAX_PROBLEMS):
-                chunk = members[a:a + MAX_PROBLEMS]
-                if grp.depth_ws is None:
-                    grp.depth_ws = torch.zeros(int(_lib.lib().pxt_depth_refine_workspace_bytes(MAX_PROBLEMS)),
-                                               dtype=torch.uint8, device=self.device)
-                pending = depth_refine_batch([item[0] for _x, item in chunk], conf, workspace=grp.depth_ws,
-                                             records=[item[1] for _x, item in chunk])
-                self.depth_refine_calls += 1
-                for i, (x, _item) in enumerate(chunk):
-                    x["depth"] = _OneDepth(pending, i)
+            if item is not None:  # (None: the frame has no depth image - its pose stays the LM's)
+                asked.append((tr._depth_conf, x, item))
+        for conf, chunk in _chunks_by(asked, lambda a: a[0], MAX_PROBLEMS):
+            if grp.depth_ws is None:
+                grp.depth_ws = torch.zeros(int(_lib.lib().pxt_depth_refine_workspace_bytes(MAX_PROBLEMS)),
+                                           dtype=torch.uint8, device=self.device)
+            pending = depth_refine_batch([item[0] for _c, _x, item in chunk], conf, workspace=grp.depth_ws,
+                                         records=[item[1] for _c, _x, item in chunk])
+            self.depth_refine_calls += 1
+            for i, (_c, x, _item) in enumerate(chunk):
+                x["depth"] = _OneDepth(pending, i)
 
     def _step_scenes(self, grp: _Group, frames):
         """The scene of each of the group's mesh trackers that take the lock-step path this step (the order of
@@ -763,8 +727,7 @@ class MultiObjectTracker:
 
         by_spp = {}
         for k, tr, path, ref_id, dbg, status, x, handle in grp.pend:
-            hook = getattr(tr.localizer.refiner, "after_lm_enqueued", None)
-            if handle is None or hook is None or getattr(hook, "__func__", None) is not PixLocPoseTrackerR9._render_ahead:
+            if handle is None or tr.armed_ahead() != "nerf":
                 continue
             req = tr._render_ahead_request()
             if req is not None:

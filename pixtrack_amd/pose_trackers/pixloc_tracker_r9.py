@@ -19,6 +19,7 @@ import ast
 import logging
 import os
 import pickle as pkl
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Optional
 
@@ -30,6 +31,7 @@ from .. import _lib
 from ..ops import ops
 from ..geometry import Camera as PixCamera, Pose
 from ..model3d import Model3D, extract_covisibility
+from ..pinned import PinnedRing, SensorStage
 from ..refiner import Paths, PoseTrackerLocalizer
 from ..point_report import parse_mode
 from ..tracker import DebugTracker
@@ -49,6 +51,46 @@ def infer_camera_from_image(width: int, height: int) -> ColmapCamera:
     principal point at the image centre, k = 0."""
     f = 1.2 * max(width, height)
     return ColmapCamera(None, "SIMPLE_RADIAL", int(width), int(height), np.array([f, width / 2.0, height / 2.0, 0.0]))
+
+
+@dataclass(slots=True, eq=False)
+class FramePlanes:
+    """The device tensors of one frame of one object at one pose, on their way from who made them to who uses them.
+    Records are compared by identity, and ``pose`` is compared with ``is``: planes made for another Pose object are not
+    used.  Every other field is None until set and None again once handed out.  A tracker holds at most four records:
+
+    ``_own`` - what this frame's own call produced for the current pose.  Set by ``_draw_frame`` (pose, mask, ref_u8;
+    depth where a float depth image was drawn; view with a mesh template's depth plane), or it is the ``_ahead_ok``
+    record that ``get_mask`` took.  ``get_reference_image`` hands out and clears ref_u8 (``keep=True``: leaves it for
+    the next call); ``_create_dynamic_reference_from_render`` / ``_from_template`` hand out and clear depth and view;
+    ``_apply_template_occlusion`` reads depth and view and leaves them.
+
+    ``_primed`` - what lock-step tracking made in one call with the other objects'.  Set by ``prime`` alone, which empties
+    the one holder a tracker has for a new pose object.  depth_nz, ref_u8 and mutual (occluder plane, scene record): taken, or
+    dropped, by ``_draw_frame`` of a mesh template.  points (p3d, slot_valid, record): by
+    ``_create_dynamic_reference_from_template``.  occlusion (the pass's frame dict, occlusion.pass_frame; its "mask_in"
+    is the plain mask ``_draw_frame`` then does not make again): by ``_apply_template_occlusion``; also cleared by
+    ``refine`` and ``_adopt_depth_sensor``.
+
+    ``_ahead`` - the frame queued behind the last LM launch, its pose known to the device alone.  Set by
+    ``_render_ahead``, ``_render_ahead_accept`` and ``_render_ahead_mesh_accept``: mask, ref_u8, depth, ``cams`` (the
+    pinned camera records, or a mesh call's views_out rows, to verify) and ``keys`` (the view settings it baked in).
+    Cleared by ``_frame_setup``, ``_query_tile_fallback`` and ``_verify_render_ahead``.
+
+    ``_ahead_ok`` - that record once ``_verify_render_ahead`` has set pose (and, for a mesh depth plane, view: the
+    host's record, proved bit-equal to the one the plane was drawn with).  ``get_mask`` takes it, as ``_own``, or drops
+    it; assigning None discards it."""
+    pose: Optional[Pose] = None
+    depth_nz: Optional[torch.Tensor] = None   # uint8 [H, W]: the `uint8(depth * 255) != 0` plane a mesh frame call wrote
+    mask: Optional[torch.Tensor] = None       # uint8 [H, W]: its morphology (_mask_of), before any occlusion pass
+    ref_u8: Optional[torch.Tensor] = None     # uint8 [H, W, 3]: the reference image
+    depth: Optional[torch.Tensor] = None      # float32 [H, W, 4]: the query view's Depth render / depth plane
+    view: object = None                       # 20 floats: the view record a mesh template's ``depth`` was drawn with
+    mutual: Optional[tuple] = None
+    points: Optional[tuple] = None
+    occlusion: Optional[dict] = None
+    cams: object = None
+    keys: Optional[list] = None
 
 
 class PixLocPoseTrackerR9(PoseTracker):
@@ -198,19 +240,11 @@ class PixLocPoseTrackerR9(PoseTracker):
         self.success = True
         self.spp = 8  # run_vis_on_poses.py:29
         self.batch_frame_images = True  # reference render + masked query in one batched UNet pass
-        self._fused_reference = None  # (pose object, uint8 image) handed from get_mask to get_reference_image
-        # (pose object, depth_nz, rgb_u8): a mesh template's frame at that pose, drawn by lock-step tracking in one call
-        # with the other objects' (multi_object_tracker.py); _mask_and_reference takes it instead of its own call
-        self._primed_frame = None
+        # a frame's planes between producer and consumer (FramePlanes has the table): this frame's own call, and what
+        # lock-step tracking drew, extracted or masked in one call with the other objects' (multi_object_tracker.py)
+        self._own: Optional[FramePlanes] = None
+        self._primed = FramePlanes()
         self.template_frames_batched = 0
-        self._fused_depth = None  # (pose object, float Depth render) beside it: reference_points="render" only
-        # reference_points="template": _fused_depth is (pose object, the template's depth plane, its view record), and
-        # (pose object, p3d, slot_valid, record) are the frame's points where lock-step tracking extracted them in one call
-        # with the other objects' (multi_object_tracker.py); create_dynamic_reference_image takes them instead of its own call
-        self._primed_points = None
-        # (pose object, plain mask, the _occ_frame of an occlusion pass) where lock-step tracking ran the pass of this
-        # frame in one pxt_occlusion_mask_views call with the other objects'; get_mask takes it instead of its own call
-        self._primed_occlusion = None
         self._ref_cam_cache = self._coincide_cache = None
         self.keep_feature_history = False  # the reference leaks one entry per frame (Appendix D.2)
         self.steady_multiscale = [1]  # image scales of a tracked (non-cold-start) frame (:223)
@@ -229,10 +263,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         # LM's output record, and the host compares the 20 floats of every view it was drawn with.
         self.render_ahead = self._render_ahead_default(self.template)
         self._ahead_ws = None         # mesh template: the FrameBatchWorkspace of the queued calls (this tracker's stream)
-        self._ahead_rows, self._ahead_row_next = None, 0  # ... and the ring of pinned views_out blocks
+        self._ahead_rows = None       # ... and the PinnedRing of their views_out blocks
         self._ahead_cam = None   # the pinned camera record the LM epilogue of this frame writes
-        self._ahead = None       # the render queued behind the last LM launch
-        self._ahead_ok = None    # ... once verified: (pose object it is valid for, mask, uint8 reference image, views, depth)
+        self._ahead: Optional[FramePlanes] = None     # the frame queued behind the last LM launch
+        self._ahead_ok: Optional[FramePlanes] = None  # ... once verified for a pose (None: none, or discarded)
         # queued renders: consumed / camera record never arrived within the poll bound / host and device disagree on a camera
         # bit / view settings changed between enqueue and use
         self.renders_ahead_used = self.renders_ahead_dropped = self.renders_ahead_rejected = self.renders_ahead_stale = 0
@@ -252,7 +286,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         self.last_relocalization = None  # RelocResult of the last relocalisation
         self._relocalized_frame = False  # this frame's pose came from the relocaliser (history key "relocalized")
         self.depth_refine = depth_refine
-        self._depth_conf = self._depth_ws = self._depth_host = self._depth_dev = self._depth_sensor = None
+        self._depth_conf = self._depth_ws = self._depth_sensor = None
+        self._sensor_stage = SensorStage(self.device)  # one image per frame, whichever sensor option reads it
         self._depth_recs, self._depth_slot, self._depth_warned_points = [], 0, False
         if depth_refine is not None:
             from ..depth_refinement import points_extent
@@ -379,19 +414,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         sensor = option.lookup(os.path.basename(str(query_path)))
         if sensor is None:
             return
-        sensor = np.ascontiguousarray(np.asarray(sensor))
-        if sensor.dtype != np.uint16 or sensor.ndim != 2:
-            raise ValueError(f"the sensor depth image of {query_path} is {sensor.dtype} {sensor.shape}, not uint16 [H, W]")
-        if self._depth_host is None or tuple(self._depth_host.shape) != sensor.shape:
-            self._depth_host = torch.empty(sensor.shape, dtype=torch.int16).pin_memory()
-            self._depth_dev = torch.empty(sensor.shape, dtype=torch.int16, device=self.device)
-            self._depth_uploaded = torch.cuda.Event()
-        else:
-            self._depth_uploaded.synchronize()  # (the last frame's upload: over long ago, unless that frame ended early)
-        self._depth_host.numpy()[...] = sensor.view(np.int16)
-        self._depth_dev.copy_(self._depth_host, non_blocking=True)
-        self._depth_uploaded.record(torch.cuda.current_stream(self.device))
-        self._depth_sensor = self._depth_dev
+        self._depth_sensor = self._sensor_stage.upload(sensor, query_path)
         self.sensor_uploads += 1
 
     def _adopt_depth_sensor(self, query_path, sensor):
@@ -399,7 +422,30 @@ class PixLocPoseTrackerR9(PoseTracker):
         the frame has none), staged once by the caller for every tracker that names it (multi_object_tracker.py)."""
         self._depth_frame_name = query_path
         self._depth_sensor, self._depth_slot = sensor, 0
-        self._occ_frame = self._primed_occlusion = None
+        self._occ_frame = self._primed.occlusion = None
+
+    def _check_sensor_size(self, h: int, w: int) -> None:
+        """The frame's staged sensor image has the size of the query (ValueError: a wrong sensor directory)."""
+        if tuple(self._depth_sensor.shape) != (h, w):
+            raise ValueError(f"the sensor depth image of {self._depth_frame_name} is {tuple(self._depth_sensor.shape)}, "
+                             f"the query {(h, w)}")
+
+    def prime(self, pose, depth_nz=None, ref_u8=None, mutual=None, points=None, occlusion=None) -> None:
+        """Lock-step tracking hands over what it made for this tracker's frame at ``pose`` in one call with the other
+        objects': a mesh frame's planes (``depth_nz``, ``ref_u8``; ``mutual`` = (occluder plane, scene record) where it
+        was drawn as part of a scene), its ``points`` (p3d, slot_valid, record), its ``occlusion`` pass
+        (occlusion.pass_frame).  Each part is used once, by the method that would otherwise make its own call, and only
+        for this very pose object."""
+        primed = self._primed  # (one holder per tracker: a new pose object empties it)
+        if primed.pose is not pose:
+            primed.pose = pose
+            primed.depth_nz = primed.ref_u8 = primed.mutual = primed.points = primed.occlusion = None
+        if depth_nz is not None:
+            primed.depth_nz, primed.ref_u8, primed.mutual = depth_nz, ref_u8, mutual
+        if points is not None:
+            primed.points = points
+        if occlusion is not None:
+            primed.occlusion = occlusion
 
     def enable_mutual_occlusion(self):
         """Lock-step tracking draws this tracker's frames as part of a scene (multi_object_tracker.MutualOcclusion): a
@@ -442,13 +488,11 @@ class PixLocPoseTrackerR9(PoseTracker):
         plane, so the quanta are this frame's, and the view has the camera's true cx, cy: no shift."""
         if self.occlusion is None or self._depth_sensor is None or depth is None:
             return mask
-        from ..occlusion import alignment, mesh_quanta, occlusion_mask
+        from ..occlusion import alignment, mesh_quanta, occlusion_mask, pass_frame
 
         sensor, conf = self._depth_sensor, self._occ_conf
         H, W = int(depth.shape[0]), int(depth.shape[1])
-        if tuple(sensor.shape) != (H, W):
-            raise ValueError(f"the sensor depth image of {self._depth_frame_name} is {tuple(sensor.shape)}, the query "
-                             f"{(H, W)}")
+        self._check_sensor_size(H, W)
         if view20 is not None:
             sx = sy = 0
             self._occ_q = mesh_quanta(conf.delta, self.occlusion.sensor_depth_scale, view20)
@@ -461,24 +505,23 @@ class PixLocPoseTrackerR9(PoseTracker):
                                                  device=self.device))
         out = occlusion_mask(depth, sensor, mask, (sx, sy), conf.min_alpha, self._occ_q[0], self._occ_q[1], conf.r_open,
                              conf.r_grow, record=self._occ_record, workspace=self._occ_ws[1])
-        self._occ_frame = {"depth": depth, "sensor": sensor, "mask_in": mask, "mask": out["mask"],
-                           "occluder": out["occluder"], "shift": (sx, sy), "min_alpha": conf.min_alpha,
-                           "sensor_q": self._occ_q[0], "delta_q": self._occ_q[1], "radii": (conf.r_open, conf.r_grow),
-                           "gates": [], "record_buffer": self._occ_record, "done": self._occ_done, "view": view20}
+        self._occ_frame = pass_frame(depth, sensor, mask, out["mask"], out["occluder"], (sx, sy), conf.min_alpha,
+                                     self._occ_q, (conf.r_open, conf.r_grow), self._occ_record, self._occ_done, view20)
         self._occ_done.record(torch.cuda.current_stream(self.device))
         return out["mask"]
 
     def _apply_template_occlusion(self, mask, pose):
-        """_apply_occlusion on a mesh template's frame: the plane and the record are the ones ``_fused_depth`` holds
-        for ``pose`` (drawn by this frame's call, or by the verified call queued behind the last LM launch)."""
-        primed, self._primed_occlusion = self._primed_occlusion, None
-        if primed is not None and primed[0] is pose and self.occlusion is not None:
-            self._occ_frame = primed[2]
-            return primed[2]["mask"]
-        held = self._fused_depth
-        if self.occlusion is None or held is None or held[0] is not pose:
+        """_apply_occlusion on a mesh template's frame: the plane and the record are the ones ``_own`` holds for
+        ``pose`` (drawn by this frame's call, or by the verified call queued behind the last LM launch) - unless
+        lock-step tracking already ran the pass for this pose object."""
+        primed, self._primed.occlusion = self._primed.occlusion, None
+        if primed is not None and self._primed.pose is pose and self.occlusion is not None:
+            self._occ_frame = primed
+            return primed["mask"]
+        own = self._own
+        if self.occlusion is None or own is None or own.pose is not pose or own.depth is None:
             return mask
-        return self._apply_occlusion(mask, held[1], view20=held[2])
+        return self._apply_occlusion(mask, own.depth, view20=own.view)
 
     def _occlusion_view(self, depth, view20):
         """What one view of a batched occlusion pass takes from this tracker for a mesh template's plane and its view
@@ -487,10 +530,7 @@ class PixLocPoseTrackerR9(PoseTracker):
             return None
         from ..occlusion import mesh_quanta
 
-        H, W = int(depth.shape[0]), int(depth.shape[1])
-        if tuple(self._depth_sensor.shape) != (H, W):
-            raise ValueError(f"the sensor depth image of {self._depth_frame_name} is {tuple(self._depth_sensor.shape)}, "
-                             f"the query {(H, W)}")
+        self._check_sensor_size(int(depth.shape[0]), int(depth.shape[1]))
         return self._depth_sensor, mesh_quanta(self._occ_conf.delta, self.occlusion.sensor_depth_scale, view20)
 
     def _gate_points(self, ref, T_init, qcamera):
@@ -539,9 +579,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         if sensor is None:
             return None
         w, h = (int(round(float(x))) for x in qcamera.size.tolist())
-        if tuple(sensor.shape) != (h, w):
-            raise ValueError(f"the sensor depth image of {self._depth_frame_name} is {tuple(sensor.shape)}, the query "
-                             f"{(h, w)}")
+        self._check_sensor_size(h, w)
         ref = prob["ref"]
         if ref.p3d.shape[0] > MAX_POINTS and not self._depth_warned_points:
             self._depth_warned_points = True
@@ -690,19 +728,25 @@ class PixLocPoseTrackerR9(PoseTracker):
             self._coincide_cache = (key, vk(self._reference_camera()) == vk(self.camera))
         return self._coincide_cache[1]
 
-    def get_reference_image(self, pose) -> torch.Tensor:
-        """uint8 [H,W,3] NeRF render at ``pose`` with SfM camera 1 scaled by reference_scale."""
-        if self._fused_reference is not None and self._fused_reference[0] is pose:
-            img = self._fused_reference[1]
-            self._fused_reference = None
-            return img
-        if self.template is not None:  # (a frame that rendered no mask: cold start, the frame after a failed one)
-            ref_u8 = self._mask_and_reference(pose, from_slot=False)[1]
-            self._fused_reference = None
-            return ref_u8
-        ref_camera = self._reference_camera()
-        rgba = get_nerf_image_device(self.testbed, self._nerf_pose(pose), ref_camera, spp=self.spp)
-        return rgba_to_u8(rgba, 0.0)
+    def get_reference_image(self, pose, keep: bool = False) -> torch.Tensor:
+        """uint8 [H,W,3] NeRF render at ``pose`` with SfM camera 1 scaled by reference_scale.  The image the frame's mask
+        call already made for this pose object is handed out once; ``keep``: it stays held for one more call (lock-step
+        tracking asks in its phase A, get_dynamic_id again in phase C: the same tensor object)."""
+        own = self._own if (self._own is not None and self._own.pose is pose) else None
+        if own is not None and own.ref_u8 is not None:
+            img = own.ref_u8
+        elif self.template is not None:  # (a frame that rendered no mask: cold start, the frame after a failed one)
+            own = self._draw_frame(pose, from_slot=False)
+            img = own.ref_u8
+        else:
+            ref_camera = self._reference_camera()
+            rgba = get_nerf_image_device(self.testbed, self._nerf_pose(pose), ref_camera, spp=self.spp)
+            img = rgba_to_u8(rgba, 0.0)
+            if keep and own is None:
+                own = self._own = FramePlanes(pose=pose)
+        if own is not None:
+            own.ref_u8 = img if keep else None
+        return img
 
     def create_dynamic_reference_image(self, pose):
         if self.reference_points == "render":
@@ -720,9 +764,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         """create_dynamic_reference_image with reference_points="render": the points come from the frame's Depth render
         at ``pose`` - the one get_mask made (or the render queued behind the last LM launch); a frame that renders no
         mask (cold start, the frame after a failed one) renders Depth + reference here."""
-        if self._fused_depth is None or self._fused_depth[0] is not pose:
-            self._mask_and_reference(pose, from_slot=False)
-        depth, self._fused_depth = self._fused_depth[1], None
+        own = self._own
+        if own is None or own.pose is not pose or own.depth is None:
+            own = self._draw_frame(pose, from_slot=False)
+        depth, own.depth = own.depth, None
         nerf_img = self.get_reference_image(pose)
         dynamic_id = hash(pose.numpy()[0].tobytes())
         features = self.localizer.refiner.extract_reference_features(self.reference_ids, pose, nerf_img, depth=depth,
@@ -734,15 +779,16 @@ class PixLocPoseTrackerR9(PoseTracker):
         mesh template drew for the query view at ``pose`` and the view record it was drawn with - the ones
         _mask_and_reference kept; a frame that renders no mask (cold start, the frame after a failed one) draws its frame
         here.  Points that lock-step tracking already extracted for this pose object are taken as they are."""
-        primed, self._primed_points = self._primed_points, None
-        points = depth = view20 = None
-        if primed is not None and primed[0] is pose:
-            points = primed[1:]
-        else:
-            if self._fused_depth is None or self._fused_depth[0] is not pose:
-                self._mask_and_reference(pose, from_slot=False)
-            _, depth, view20 = self._fused_depth
-        self._fused_depth = None
+        points, self._primed.points = self._primed.points, None
+        depth = view20 = None
+        own = self._own
+        if points is None or self._primed.pose is not pose:
+            points = None
+            if own is None or own.pose is not pose or own.depth is None:
+                own = self._draw_frame(pose, from_slot=False)
+            depth, view20 = own.depth, own.view
+        if own is not None:
+            own.depth = own.view = None
         ref_u8 = self.get_reference_image(pose)
         dynamic_id = hash(pose.numpy()[0].tobytes())
         features = self.localizer.refiner.extract_reference_features(self.reference_ids, pose, ref_u8, depth=depth,
@@ -788,26 +834,23 @@ class PixLocPoseTrackerR9(PoseTracker):
 
     def get_mask(self, pose) -> torch.Tensor:
         """uint8 [H,W] on the device: depth render != 0, erode 5x5 x1, dilate 5x5 x5."""
-        if self._ahead_ok is not None and self._ahead_ok[0] is pose:
-            _, mask, ref_u8, views, depth = self._ahead_ok
-            self._ahead_ok = None
+        ok, self._ahead_ok = self._ahead_ok, None
+        if ok is not None and ok.pose is pose:
             # (it also baked in focal length, size, spp, lens, render box, background and minimum transmittance as they were
             # when it was enqueued: it stands in for this frame's render only if they are what this frame would use)
-            if views == self._ahead_views_now():
-                self._fused_reference = (pose, ref_u8)
+            if ok.keys == self._ahead_views_now():
                 self.renders_ahead_used += 1
-                if self.template is not None:  # depth = (the query view's depth plane, the host's bit-equal view record)
-                    self._fused_depth = (pose, *depth) if (depth is not None and self.reference_points == "template") else None
-                    self._last_depth = None
-                    return self._apply_template_occlusion(mask, pose)
-                self._fused_depth = (pose, depth) if (depth is not None and self.reference_points == "render") else None
-                return self._apply_occlusion(mask, depth)
+                self._own, depth = ok, ok.depth
+                if self.reference_points != ("render" if self.template is None else "template"):
+                    ok.depth = ok.view = None  # (the frame's points are not taken from it: not held)
+                if self.template is not None:  # (with its depth plane comes the host's bit-equal view record)
+                    return self._apply_template_occlusion(ok.mask, pose)
+                return self._apply_occlusion(ok.mask, depth)
             self.renders_ahead_stale += 1
-        self._ahead_ok = None
-        mask = self._mask_and_reference(pose, from_slot=False)[0]
+        planes = self._draw_frame(pose, from_slot=False)
         if self.template is not None:
-            return self._apply_template_occlusion(mask, pose)
-        return self._apply_occlusion(mask, self._last_depth)
+            return self._apply_template_occlusion(planes.mask, pose)
+        return self._apply_occlusion(planes.mask, planes.depth)
 
     def _frame_views(self):
         """(width, height, fov in degrees on x) of the frame's renders as get_nerf_image sets them up
@@ -822,37 +865,43 @@ class PixLocPoseTrackerR9(PoseTracker):
         return [fov_of(self.camera)] if self._views_coincide() else [fov_of(self.camera), fov_of(self._reference_camera())]
 
     def _mask_and_reference(self, pose, from_slot: bool):
+        """(mask, ref_u8) of ``_draw_frame``."""
+        planes = self._draw_frame(pose, from_slot)
+        return planes.mask, planes.ref_u8
+
+    def _draw_frame(self, pose, from_slot: bool) -> FramePlanes:
         """The frame's mask and 8-bit reference image at one pose (reference :145-152, :207-214): ONE march when the two
         views coincide, otherwise the Depth render (query camera) and the Shade render (reference camera) as one chain of
         launches on this stream.  ``from_slot``: the camera is the one the LM kernel ahead in the stream derived from its
-        final pose (render-ahead); otherwise the host's conversion of ``pose``.  Sets ``_fused_reference`` when a pose
-        object is given; returns (mask, ref_u8).  With reference_points="render" the Depth render also keeps its float
-        image (``_fused_depth`` / ``_last_depth``).  With a mesh template both planes come from one
-        ``MeshTemplate.frame`` call instead; everything after them is the same.  With reference_points="template" that
-        call also writes the query view's float depth plane, kept with its view record in ``_fused_depth``."""
+        final pose (render-ahead); otherwise the host's conversion of ``pose``.  Returns the planes as a record, which is
+        also kept as ``_own`` when a pose object is given.  With reference_points="render" or ``occlusion`` the Depth
+        render also keeps its float image (``depth``).  With a mesh template both planes come from one
+        ``MeshTemplate.frame`` call instead - or from the call lock-step tracking made for this pose object (``_primed``);
+        everything after them is the same.  With reference_points="template" that call also writes the query view's
+        float depth plane, kept with the view record it was drawn with (``depth``, ``view``)."""
         if self.template is not None:
-            primed, self._primed_frame = self._primed_frame, None
-            mutual = depth = None
-            if primed is not None and pose is not None and primed[0] is pose:  # drawn with the other objects' frames
-                nz, ref_u8 = primed[1], primed[2]
-                mutual = primed[3] if len(primed) > 3 else None  # ... as part of a scene (mutual occlusion)
+            primed = self._primed
+            mutual = depth = view20 = None
+            if primed.depth_nz is not None and pose is not None and primed.pose is pose:
+                # drawn with the other objects' frames (``mutual``: ... as part of a scene)
+                nz, ref_u8, mutual = primed.depth_nz, primed.ref_u8, primed.mutual
                 self.template_frames_batched += 1
             elif self.reference_points == "template":
                 # (the view record the plane is drawn with is the one the points are back-projected through)
                 requests = self.template.requests(pose, self.camera, self._reference_camera(), want_depth=True)
-                nz, ref_u8, plane = self.template.frame(pose, self.camera, self._reference_camera(), want_depth=True,
+                nz, ref_u8, depth = self.template.frame(pose, self.camera, self._reference_camera(), want_depth=True,
                                                         requests=requests)
-                depth = (pose, plane, requests[0][0])
+                view20 = requests[0][0]
             else:
                 nz, ref_u8 = self.template.frame(pose, self.camera, self._reference_camera())
-            occ = self._primed_occlusion
+            primed.depth_nz = primed.ref_u8 = primed.mutual = None  # (handed out once; for another pose: dropped)
+            occ = primed.occlusion
             # (a primed occlusion pass of this pose was fed the plain mask of this very plane: not made again)
-            mask = occ[1] if (occ is not None and pose is not None and occ[0] is pose) else self._mask_of(nz)
+            mask = occ["mask_in"] if (occ is not None and pose is not None and primed.pose is pose) else self._mask_of(nz)
             if mutual is not None:
                 mask = self._apply_mutual_occlusion(mask, mutual)
-            self._last_depth = None
-            self._fused_reference, self._fused_depth = (pose, ref_u8), depth
-            return mask, ref_u8
+            planes = self._own = FramePlanes(pose=pose, mask=mask, ref_u8=ref_u8, depth=depth, view=view20)
+            return planes
         tb, spp = self.testbed, int(self.spp)
         want_depth = self.reference_points == "render" or self.occlusion is not None
         if not from_slot:
@@ -869,12 +918,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         else:
             nz, ref_u8 = tb.render_frame_pair_device(views[0], views[1], spp, from_slot=from_slot)
             depth = None
-        mask = self._mask_of(nz)
-        self._last_depth = depth
+        planes = FramePlanes(pose=pose, mask=self._mask_of(nz), ref_u8=ref_u8, depth=depth)
         if pose is not None:
-            self._fused_reference = (pose, ref_u8)
-            self._fused_depth = (pose, depth) if self.reference_points == "render" else None
-        return mask, ref_u8
+            self._own = planes
+        return planes
 
     def _mask_of(self, nz):
         """get_mask's morphology on the `uint8(depth * 255) != 0` plane a render wrote: erode 5x5 once, dilate 5x5 five
@@ -899,22 +946,9 @@ class PixLocPoseTrackerR9(PoseTracker):
     def _render_ahead(self, pending):
         """Called between the LM launch and the wait for its result: the mask + reference render(s) of the NEXT frame, whose
         camera the LM kernel's epilogue writes into the renderer's camera slot(s)."""
-        views = self._ahead_views_now()
-        mask, ref_u8 = self._mask_and_reference(None, from_slot=True)
-        self._ahead = ([self._ahead_cam], mask, ref_u8, views, self._last_depth)
-
-    def _next_views_out(self, n_views: int) -> torch.Tensor:
-        """A pinned [n_views, 24] block for a queued mesh call's views_out, its completion words zeroed.  The kernel gets
-        the raw pointer: the blocks live as long as the tracker and are recycled round-robin (Testbed._next_cam_out's
-        scheme) - one is written per frame and read back at that frame's end."""
-        from ..mesh_render import VIEW_OUT, W_VIEW_DONE
-
-        if self._ahead_rows is None:
-            self._ahead_rows = [torch.zeros(2, VIEW_OUT, dtype=torch.float32).pin_memory() for _ in range(8)]
-        block = self._ahead_rows[self._ahead_row_next]
-        self._ahead_row_next = (self._ahead_row_next + 1) % len(self._ahead_rows)
-        block[:, W_VIEW_DONE] = 0.0
-        return block[:n_views]
+        keys = self._ahead_views_now()
+        self._ahead = self._draw_frame(None, from_slot=True)
+        self._ahead.cams, self._ahead.keys = [self._ahead_cam], keys
 
     def _render_ahead_mesh_request(self):
         """The mesh template's queued frame for a caller that draws several trackers' in one call (lock-step tracking,
@@ -923,25 +957,25 @@ class PixLocPoseTrackerR9(PoseTracker):
         requests = self.template.requests_ahead(self.camera, self._reference_camera(), want_depth)
         return requests, want_depth, self._ahead_view_keys(requests)
 
-    def _render_ahead_mesh_accept(self, rows, planes, keys):
-        """What _render_ahead_mesh() does after its call: ``rows`` = the views_out rows of this tracker's views,
-        ``planes`` = (depth_nz, rgb_u8[, depth])."""
-        depth = planes[2] if len(planes) > 2 else None
-        self._ahead = (rows, self._mask_of(planes[0]), planes[1], keys, depth)
+    def _render_ahead_mesh_accept(self, rows, keys, depth_nz, ref_u8, depth=None):
+        """What _render_ahead_mesh() does after its call: ``rows`` = the views_out rows of this tracker's views, then
+        the planes the call drew for them."""
+        self._ahead = FramePlanes(mask=self._mask_of(depth_nz), ref_u8=ref_u8, depth=depth, cams=rows, keys=keys)
 
     def _render_ahead_mesh(self, pending):
         """_render_ahead with a mesh template: ONE posed call on this stream behind the LM launch, whose output record
         (``pending.buf``) the call's first launch turns into the views' records on the device."""
-        from ..mesh_render import FrameBatchWorkspace
+        from ..mesh_render import VIEW_OUT, W_VIEW_DONE, FrameBatchWorkspace
         from ..mesh_template import MeshTemplate
 
         if self._ahead_ws is None:
-            self._ahead_ws = FrameBatchWorkspace()
+            self._ahead_ws, self._ahead_rows = FrameBatchWorkspace(), PinnedRing((2, VIEW_OUT), torch.float32)
         requests, want_depth, keys = self._render_ahead_mesh_request()
-        rows = self._next_views_out(len(requests))
+        rows = self._ahead_rows.next(len(requests))  # (one block per frame, read back at that frame's end)
+        rows[:, W_VIEW_DONE] = 0.0
         planes = MeshTemplate.frames_ahead([self.template], [pending.buf], [self.camera], [self._reference_camera()],
                                            self._ahead_ws, rows, want_depth=[want_depth], requests=[requests])[0]
-        self._render_ahead_mesh_accept(rows, planes, keys)
+        self._render_ahead_mesh_accept(rows, keys, *planes)
 
     def _ahead_view_keys(self, requests):
         """Per view of a mesh template's frame what a queued call bakes in besides the pose: size, supersample, outputs,
@@ -961,7 +995,8 @@ class PixLocPoseTrackerR9(PoseTracker):
 
     def _render_ahead_accept(self, out):
         """What _render_ahead() does after its render, for a render that was part of a batched chain."""
-        self._ahead = ([self._ahead_cam], self._mask_of(out["depth_nz"]), out["rgb_u8"], self._ahead_views_now(), None)
+        self._ahead = FramePlanes(mask=self._mask_of(out["depth_nz"]), ref_u8=out["rgb_u8"], cams=[self._ahead_cam],
+                                  keys=self._ahead_views_now())
 
     def _ahead_views_now(self):
         """What a render queued now bakes in besides the camera pose, per render of the frame: focal length, lens, render
@@ -972,6 +1007,19 @@ class PixLocPoseTrackerR9(PoseTracker):
         spp = int(self.spp)
         return [(tuple(self.testbed._view_for(w, h, fov)[12:]), w, h, spp) for w, h, fov in self._frame_views()]
 
+    def verified_ahead(self) -> Optional[FramePlanes]:
+        """The frame that was drawn ahead and verified, if it is valid for the present pose and view settings - what
+        get_mask will take this frame - else None."""
+        ok = self._ahead_ok
+        return ok if (self.success and ok is not None and ok.pose is self.pose and ok.keys == self._ahead_views_now()) else None
+
+    def armed_ahead(self) -> Optional[str]:
+        """Which render-ahead this frame's set-up armed behind the LM launch: "nerf" (_render_ahead), "mesh"
+        (_render_ahead_mesh) or None."""
+        if getattr(self.localizer.refiner, "after_lm_enqueued", None) is None:
+            return None
+        return "nerf" if self.template is None else "mesh"
+
     def _verify_render_ahead(self, success: bool):
         """The render queued behind the LM launch is kept for the next frame only if the pose was accepted and the
         host, going through the reference's own conversion chain, arrives at the 12 camera floats the device used."""
@@ -979,12 +1027,11 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._ahead_ok = None
         if ahead is None or not success:
             return
-        cams, mask, ref_u8, views, depth = ahead
         if self.template is not None:
-            return self._verify_mesh_render_ahead(cams, mask, ref_u8, views, depth)
+            return self._verify_mesh_render_ahead(ahead)
         self.testbed.set_nerf_camera_matrix(np.asarray(self._nerf_pose(self.pose))[:3, :])
         want = np.asarray(self.testbed._cam_ngp, np.float32).reshape(-1)
-        for cam_out in cams:
+        for cam_out in ahead.cams:
             got = cam_out.numpy()
             for _ in range(200000):  # the camera kernel runs right behind the LM kernel whose result is already here
                 if got[12] != 0.0:
@@ -995,17 +1042,18 @@ class PixLocPoseTrackerR9(PoseTracker):
             if not np.array_equal(want.view(np.uint32), got[:12].view(np.uint32)):
                 self.renders_ahead_rejected += 1
                 return
-        self._ahead_ok = (self.pose, mask, ref_u8, views, depth)
+        ahead.pose, ahead.cams = self.pose, None
+        self._ahead_ok = ahead
 
-    def _verify_mesh_render_ahead(self, rows, mask, ref_u8, views, depth):
+    def _verify_mesh_render_ahead(self, ahead):
         """_verify_render_ahead with a mesh template: every view of the queued call was drawn with the 20 floats the host
         forms from the accepted pose - ``view_record`` with ``template.depth_q`` - bit for bit, or the planes are not
         used.  With reference_points="template" the host's query record goes with the depth plane: it is the record the
         plane was drawn with."""
         from ..mesh_render import W_VIEW_DONE, view_record
 
-        got = rows.numpy()
-        cameras = [self.camera] if len(views) == 1 else [self.camera, self._reference_camera()]
+        got = ahead.cams.numpy()
+        cameras = [self.camera] if len(ahead.keys) == 1 else [self.camera, self._reference_camera()]
         q = self.template.depth_q(self.pose)
         want_q = None
         for row, camera in zip(got, cameras):
@@ -1020,23 +1068,22 @@ class PixLocPoseTrackerR9(PoseTracker):
                 self.renders_ahead_rejected += 1
                 return
             want_q = want if want_q is None else want_q
-        self._ahead_ok = (self.pose, mask, ref_u8, views, None if depth is None else (depth, want_q))
+        ahead.pose, ahead.cams, ahead.view = self.pose, None, (None if ahead.depth is None else want_q)
+        self._ahead_ok = ahead
 
     # ------------------------------------------------------------------ one frame
     def refine(self, query):
         query_path, query_image = query
         refiner = self.localizer.refiner
         self._depth_frame_name = query_path
-        self._occ_frame = self._mut_frame = self._primed_occlusion = None
+        self._occ_frame = self._mut_frame = self._primed.occlusion = None
         if self.depth_refine is not None or self.occlusion is not None:
             self._stage_depth_sensor(query_path)
         self._frame_setup(query)
         if self.occlusion is not None and self._depth_sensor is not None:
             # (on every frame, also one that gets no mask: a wrong sensor directory is not found out frames later)
             w, h = (int(round(float(x))) for x in self.camera.size.tolist())
-            if tuple(self._depth_sensor.shape) != (h, w):
-                raise ValueError(f"the sensor depth image of {query_path} is {tuple(self._depth_sensor.shape)}, the query "
-                                 f"{(h, w)}")
+            self._check_sensor_size(h, w)
         self.dynamic_id = self.get_dynamic_id(self.pose)
         trackers, rets, costs = {}, {}, {}
         for ref_id in self.reference_ids:

@@ -25,9 +25,7 @@ import os
 from pathlib import Path
 
 import numpy as np
-from scipy.spatial.transform import Rotation as R
 
-from ..geometry import Pose
 from ..tracker import DebugTracker
 from ..utils.ingp_utils import get_nerf_aabb_from_sfm
 from ..utils.io import YCBVideoIterator
@@ -122,17 +120,14 @@ class PixLocPoseTrackerYCB(PixLocPoseTrackerR9):
         refiner.lm_camera = self._lm_camera if steady else None
 
         self.dynamic_id = self.get_dynamic_id(self.pose)
-        rotation, translation = self.pose.numpy()
-        rotation = R.from_matrix(rotation).as_matrix()
         trackers, rets, costs = {}, {}, {}
         for ref_id in self.reference_ids:
-            pose_init = Pose.from_Rt(rotation, translation)
+            pose_init = self._frame_pose_init()
             tracker = DebugTracker(refiner, self.debug)
             ret = self.localizer.run_query(query_path, self.camera, pose_init, [ref_id], image_query=query_image,
                                            pose=self.pose, reference_images_raw=None, dynamic_id=self.dynamic_id)
             rets[ref_id], trackers[ref_id] = ret, tracker
-            last = [c[-1] for res in refiner.last_lm for c in res.costs if len(c)]
-            costs[ref_id] = float(np.mean(last)) if last else float("nan")
+            costs[ref_id] = self._frame_cost()
         best_ref_id = min(costs, key=costs.get)
         ret = rets[best_ref_id]
         self.calculate_error()

@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from .ops import ops
+from .pinned import PinnedRing
 from .feature_extractor import PixTrackFeatureExtractor
 from .geometry import Camera, Pose
 from .model3d import Model3D
@@ -116,8 +117,7 @@ class PoseTrackerRefiner:
             raise ValueError(f"reference_points must be 'sfm', 'render' or 'template' (got {self.conf.reference_points!r})")
         self._points_ws: Dict[Tuple[int, int], torch.Tensor] = {}  # (w, h) -> workspace of pxt_points_from_depth
         self._points_views_ws: Dict[Tuple[int, int], torch.Tensor] = {}  # ... of a one-view pxt_points_from_depth_views
-        self._points_records = None  # pinned {A, s, n_points, n_candidates} records, recycled round-robin
-        self._points_next = 0
+        self._points_records = PinnedRing((4,), torch.int32)  # {A, s, n_points, n_candidates}: one per frame
         self.last_points_record: Optional[torch.Tensor] = None  # the record of the last "render" extraction
         self.query_mask: Optional[torch.Tensor] = None  # device uint8 [H,W], set by the tracker
         self._p3d_cache: Dict[int, Tuple[List[int], torch.Tensor]] = {}
@@ -185,16 +185,6 @@ class PoseTrackerRefiner:
     def template_points(self) -> bool:
         return self.conf.reference_points == "template"
 
-    def _next_points_record(self) -> torch.Tensor:
-        """A pinned int32 [4] record for pxt_points_from_depth.  The kernel receives the raw pointer, so the records
-        live as long as the refiner and are recycled round-robin: one is written per frame, and a frame's kernels have
-        finished (its LM result was read) long before eight more extractions are queued."""
-        if self._points_records is None:
-            self._points_records = [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(8)]
-        rec = self._points_records[self._points_next]
-        self._points_next = (self._points_next + 1) % len(self._points_records)
-        return rec
-
     def points_from_render(self, depth: torch.Tensor, depth_view: Dict):
         """The points of a "render" frame: -> (p3d [n_max, 3] in SfM object coordinates, slot_valid uint8 [n_max],
         record): a lattice of the accepted pixels of ``depth`` (the float image of a Depth render, [H, W, 4]),
@@ -215,7 +205,7 @@ class PoseTrackerRefiner:
             ws = self._points_ws[(W, H)] = torch.empty(need, dtype=torch.uint8, device=self.device)
         p3d = torch.empty(n_max, 3, dtype=torch.float32, device=self.device)
         slot_valid = torch.empty(n_max, dtype=torch.uint8, device=self.device)
-        record = self._next_points_record()
+        record = self._points_records.next()
         ops.points_from_depth(depth, [float(x) for x in depth_view["xform"]], float(depth_view["focal"]),
                               float(depth_view["depth_scale"]), float(self.conf.reference_points_min_alpha),
                               int(self.conf.reference_points_erode), n_max, p3d, slot_valid, record, ws)
@@ -238,7 +228,7 @@ class PoseTrackerRefiner:
             ws = self._points_views_ws[(W, H)] = torch.empty(need, dtype=torch.uint8, device=self.device)
         p3d = torch.empty(1, n_max, 3, dtype=torch.float32, device=self.device)
         slot_valid = torch.empty(1, n_max, dtype=torch.uint8, device=self.device)
-        record = self._next_points_record()
+        record = self._points_records.next()
         ops.points_from_depth_views([depth], [float(x) for x in np.asarray(view20, np.float32).reshape(-1)],
                                     float(self.conf.reference_points_min_alpha), int(self.conf.reference_points_erode),
                                     n_max, p3d, slot_valid, record.view(1, 4), ws)

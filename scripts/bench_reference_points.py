@@ -67,7 +67,7 @@ def part_a(dev):
         tr.camera = Camera.from_colmap(assets["query_camera"])
         pose = Pose.from_Rt(*assets["gt_poses"][0])
         tr._mask_and_reference(pose, from_slot=False)
-        depth, view = tr._fused_depth[1], tr._depth_view(pose)
+        depth, view = tr._own.depth, tr._depth_view(pose)
         refiner = tr.localizer.refiner
         row = {"width": w, "height": h, "points_from_depth": _device_us(lambda: refiner.points_from_render(depth, view), per=20)}
         torch.cuda.synchronize()

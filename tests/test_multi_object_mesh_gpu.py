@@ -104,15 +104,16 @@ def test_the_primed_planes_are_each_trackers_own_frame(device, objects):
         assert nz.shape == (H, W) and ref_u8.shape == (H, W, 3) and 0.03 < float(nz.float().mean()) < 0.9 and int(ref_u8.max()) > 150
         assert torch.equal(nz, own_nz) and torch.equal(ref_u8, own_ref)
         # a tracker takes primed planes at the primed pose object alone
-        tr._primed_frame = (tr.pose, nz, ref_u8)
+        tr.prime(tr.pose, depth_nz=nz, ref_u8=ref_u8)
         mask, ref = tr._mask_and_reference(tr.pose, from_slot=False)
-        assert ref is ref_u8 and tr._primed_frame is None and tr.template_frames_batched == 1
+        frame_part_gone = lambda: tr._primed.depth_nz is None and tr._primed.ref_u8 is None and tr._primed.mutual is None
+        assert ref is ref_u8 and frame_part_gone() and tr.template_frames_batched == 1
         assert torch.equal(mask, tr._mask_of(own_nz))
-        tr._primed_frame = (object(), nz, ref_u8)
+        tr.prime(object(), depth_nz=nz, ref_u8=ref_u8)
         mask, ref = tr._mask_and_reference(tr.pose, from_slot=False)
         torch.cuda.synchronize()
-        assert ref is not ref_u8 and torch.equal(ref, own_ref) and tr._primed_frame is None and tr.template_frames_batched == 1
-        tr._fused_reference = None
+        assert ref is not ref_u8 and torch.equal(ref, own_ref) and frame_part_gone() and tr.template_frames_batched == 1
+        tr._own = None
 
 
 def test_nerf_and_mesh_trackers_share_one_lock_step_tracker(device, objects):

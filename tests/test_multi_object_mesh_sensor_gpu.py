@@ -88,7 +88,7 @@ def test_lockstep_equals_solo_runs_with_both_options(device, pair):
     for j, (tr, ref) in enumerate(zip(trackers, want)):
         got, exp = _poses(tr, NAMES[:STEPS]), _poses(ref, NAMES[:STEPS])
         assert np.array_equal(got.view(np.uint64), exp.view(np.uint64)), (j, np.abs(got - exp).max())
-        assert tr._primed_occlusion is None and tr._primed_points is None
+        assert tr._primed.occlusion is None and tr._primed.points is None
         for n in NAMES[:STEPS]:
             a, b = tr.pose_history[n], ref.pose_history[n]
             assert set(a) == set(b)

@@ -73,7 +73,7 @@ def _render_at_gt(device, k=0):
     Rg, tg = _assets()["gt_poses"][k]
     pose = Pose.from_Rt(Rg, tg)
     _, ref_u8 = tr._mask_and_reference(pose, from_slot=False)
-    depth = tr._fused_depth[1]
+    depth = tr._own.depth
     return tr, pose, depth, tr._depth_view(pose), ref_u8
 
 
@@ -130,7 +130,7 @@ def test_points_land_on_their_pixels(device):
     tr._coincide_cache = None
     assert len(tr._frame_views()) == 2
     tr._mask_and_reference(pose, from_slot=False)
-    assert torch.equal(tr._fused_depth[1].view(torch.int32), depth.view(torch.int32))
+    assert tr._own.pose is pose and torch.equal(tr._own.depth.view(torch.int32), depth.view(torch.int32))
 
 
 def test_extract_reference_features_from_render(device):

@@ -111,7 +111,7 @@ def test_the_features_are_the_samplers_on_the_whole_reference_image(device, obje
     tr.camera = Camera.from_colmap(assets["query_camera"])
     pose = Pose.from_Rt(*assets["gt_poses"][1])
     _, ref_u8 = tr._mask_and_reference(pose, from_slot=False)
-    held, depth, view20 = tr._fused_depth
+    held, depth, view20 = tr._own.pose, tr._own.depth, tr._own.view
     assert held is pose and tuple(depth.shape) == (H, W, 4) and view20.shape == (20,)
     # the record is the one the plane was drawn with: the template's own request for this pose
     assert np.array_equal(view20, tr.template.requests(pose, tr.camera, tr._reference_camera(), want_depth=True)[0][0])
@@ -155,7 +155,7 @@ def test_the_default_is_untouched(device, objects):
     for n in NAMES:
         assert list(a.pose_history[n]) == list(b.pose_history[n]) and "n_reference_points" not in a.pose_history[n]
         assert "reference_point_stride" not in a.pose_history[n]
-    assert a.localizer.refiner.last_points_record is None and a._primed_points is None
+    assert a.localizer.refiner.last_points_record is None and a._primed.points is None
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -207,7 +207,7 @@ def test_lockstep_equals_solo_runs(device, objects, monkeypatch, per_image_plan,
     assert multi.points_calls == n_groups * (N_FRAMES - 1)
     for j, tr in enumerate(trackers):
         check_against_solo(_poses(tr, NAMES), want[j], per_image_plan, f"object {j}")
-        assert tr.template_frames_batched >= 4 and tr._primed_points is None
+        assert tr.template_frames_batched >= 4 and tr._primed.points is None
         gt = objects["objs"][j][0]["gt_poses"]
         r_err, t_err = errors(tr, gt)
         assert r_err < 2e-2 and t_err < 2e-2, (j, r_err, t_err)

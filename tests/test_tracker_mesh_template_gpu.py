@@ -45,8 +45,8 @@ def frame_planes(tr, pose):
     mask, ref_again = tr._mask_and_reference(pose, from_slot=False)
     torch.cuda.synchronize(tr.device)
     assert torch.equal(ref_u8, ref_again) and torch.equal(mask, tr._mask_of(nz))
-    assert tr._fused_reference[0] is pose and tr._fused_reference[1] is ref_again
-    tr._fused_reference = None
+    assert tr._own.pose is pose and tr._own.ref_u8 is ref_again
+    tr._own = None
     return nz.cpu().numpy(), ref_u8.cpu().numpy()
 
 
