@@ -472,12 +472,17 @@ def require_gpu(t: torch.Tensor, name: str) -> None:
         raise PxtError(f"{name} must live on a ROCm device (got {t.device}); no CPU path exists")
 
 
-def host_pose12(T) -> "C.Array":
-    """12 host floats (row-major R, then t) from a Pose / tensor / array, for *_host arguments."""
+def pose_floats(T) -> list:
+    """The host floats (row-major R, then t) of a Pose / tensor / sequence; the op they go to checks that they are 12."""
     data = T.as12() if hasattr(T, "as12") else T
     if torch.is_tensor(data):
         data = data.detach().cpu().reshape(-1).tolist()
-    vals = [float(x) for x in data]
+    return [float(x) for x in data]
+
+
+def host_pose12(T) -> "C.Array":
+    """`pose_floats` as a C array of exactly 12, for *_host arguments."""
+    vals = pose_floats(T)
     assert len(vals) == 12
     return (C.c_float * 12)(*vals)
 

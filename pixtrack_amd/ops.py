@@ -7,6 +7,7 @@ hot path (pointers, sizes, the current HIP stream).
 Reference call sites the ops stand in for:
   lm_refine            pixloc BaseRefiner.refine_pose_using_features -> opt.run per level
                        (pixtrack/localization/pixloc_pose_refiners.py:255-262)
+  lm_refine_batch      (no reference counterpart) K such refinements, the objects of lock-step tracking, in one launch
   lm_information       (no reference counterpart) the LM's normal equations at a given pose, K problems per launch
   lm_point_report      (opt-in) the per-point terms of one LM iteration at a given pose, K problems per launch: what
                        DebugTracker keeps of a refinement's points at debug >= 2 (pixtrack/localization/tracker.py:26-30)
@@ -14,9 +15,17 @@ Reference call sites the ops stand in for:
   score_pose_hypotheses  (no reference counterpart) M pose hypotheses scored in one launch (relocalizer.py)
   unet_forward_batch   self.model({"image": ...}) (pixtrack/localization/feature_extractor.py:48)
   ngp_render[_both]    testbed.render(w, h, spp, True) (pixtrack/visualization/run_vis_on_poses.py:51)
-  depth_mask           get_mask morphology (pixtrack/pose_trackers/pixloc_tracker_r9.py:207-214)
+  ngp_render_both_from_pose, ngp_render_frame[_batch]  the same renders with the camera derived on the device from an
+                       lm_refine record, with the 8-bit planes the tracker consumes written by the last kernel, and K
+                       of those for K contexts in one chain
+  ngp_query            (no reference counterpart) the network's density and colour at given points (parity tests, mesh extraction)
+  depth_mask[_plane]   get_mask morphology (pixtrack/pose_trackers/pixloc_tracker_r9.py:207-214), from the float Depth
+                       image or from its nonzero plane
   rgba_to_u8           get_nerf_image's alpha threshold / *255 / uint8 (run_vis_on_poses.py:52-54)
   resize_linear        pixloc resize(image, size, max, "linear") (feature_extractor.py:45)
+  resize_activity      (no reference counterpart) which pixels of a resized image can be non-zero: the mask the UNet's
+                       constant-tile skipping reads for images above the extractor's size limit
+  conv3x3_nhwc_f16     one convolution layer of that model on its own (tests, microbenchmarks)
   points_from_depth    (opt-in) stands in for the SfM points of the nearest mapping image as the points a frame is
                        refined on (pixloc_pose_refiners.py:282-290): a lattice of the Depth render, back-projected
   points_from_depth_views  (opt-in) the same from the depth planes a mesh template's frame call drew, up to 16 views of
@@ -38,6 +47,12 @@ Reference call sites the ops stand in for:
                        launches, each pair's outputs bit for bit the single call's: the mesh objects of one RGB-D frame
   points_visible       (opt-in, no reference counterpart) the LM's point mask minus the points that project onto that
                        occluder plane
+  iso_surface_count, iso_surface_emit, max_pairwise_distance  (opt-in, no reference counterpart) a mesh from a lattice
+                       of densities in two passes, and its diameter (mesh.py)
+  mesh_raster, mesh_render[_textured]  (opt-in, no reference counterpart) depth, triangle ids and colour of a triangle
+                       mesh from P views (mesh_render.py, mesh_evaluation.py)
+  mesh_render_frame[_batch]  (opt-in) a tracker frame's views of one mesh, or of up to 16 meshes, in one call: a mesh
+                       template in the NeRF's place (mesh_template.py)
   mesh_render_scene_batch  (opt-in, no reference counterpart) mesh_render_frame_batch for objects that share an image:
                        per view also the pixels where another tracked mesh of its scene lies in front, grown
   mask_exclude         (opt-in, no reference counterpart) a mask minus such an occluder plane
@@ -282,13 +297,146 @@ def _stream(t: torch.Tensor) -> int:
     return int(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def _f32c(t: torch.Tensor, what: str) -> torch.Tensor:
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise _lib.PxtError(f"{what} must be a contiguous float32 tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
-    return t
+# ------------------------------------------------------------------------- argument checks
+# The vocabulary every op body below checks its arguments with: plain functions that raise PxtError
+# with "<op>: <argument> is <expected> (got ...)".  Inside a body the order is: lengths and counts, then dtype / shape /
+# contiguity, then the workspace's size, then devices.
+_SENSOR_DTYPES = (torch.uint16, torch.int16)  # raw depth counts; int16 holds the same bits
+_ANY3 = (None, None, None)
+
+
+def _dense(op, t, name, dtype=torch.float32, shape=None, where=""):
+    """``t`` is a contiguous tensor of ``dtype`` (one, or a tuple of them) and of ``shape``, where an entry of None
+    stands for any extent (the pattern still fixes the rank) -> t.  ``where`` (a string, or a tuple of parts) follows
+    the name in the message.  The passing path is kept short: it runs dozens of times per launch on a frame's
+    critical path."""
+    if (t.dtype == dtype or (dtype.__class__ is tuple and t.dtype in dtype)) and t.is_contiguous():
+        if shape is None:
+            return t
+        have = t.shape
+        if len(have) == len(shape):
+            for d, s in zip(have, shape):
+                if s is not None and d != s:
+                    break
+            else:
+                return t
+    dtypes = " or ".join(str(d)[6:] for d in (dtype if dtype.__class__ is tuple else (dtype,)))
+    want = "" if shape is None else " [" + ", ".join("*" if s is None else str(s) for s in shape) + "]"
+    where = "".join(str(w) for w in where) if where.__class__ is tuple else where
+    raise _lib.PxtError(f"{op}: {name}{where} is a contiguous {dtypes}{want} tensor (got {tuple(t.shape)}, {t.dtype}, "
+                        f"contiguous={t.is_contiguous()})")
+
+
+def _point_mask(op, t, n, name="point_mask"):
+    """A point mask is None or contiguous uint8 with one byte per point: the kernels read ``n`` bytes of it."""
+    if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != n):
+        raise _lib.PxtError(f"{op}: {name} is contiguous uint8 [n_points = {n}] (got {tuple(t.shape)}, {t.dtype})")
+
+
+def _sensor(op, t, name, shape):
+    return _dense(op, t, name, _SENSOR_DTYPES, shape)
+
+
+def _shifts(op, shift, pairs=1):
+    if len(shift) != 2 * pairs or any(abs(int(v)) > 32767 for v in shift):
+        raise _lib.PxtError(f"{op}: shift is (shift_x, shift_y){' per view' if pairs > 1 else ''}, each within +-32767 "
+                            f"(got {list(shift)})")
+
+
+def _radii(op, radii):
+    if len(radii) != 2 or min(int(r) for r in radii) < 0 or int(radii[0]) + int(radii[1]) > _lib.PXT_OCCLUSION_MAX_RADIUS:
+        raise _lib.PxtError(f"{op}: radii are (r_open, r_grow) >= 0 with r_open + r_grow <= "
+                            f"{_lib.PXT_OCCLUSION_MAX_RADIUS} (got {list(radii)})")
+
+
+def _record(op, t, name, dtype, count, device, shape=None):
+    """A record the host reads: ``count`` contiguous words of ``dtype`` at least (or exactly ``shape``), in memory of
+    ``device`` or in pinned host memory - a kernel on ``device`` stores to it -> its address."""
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < count or (shape is not None and tuple(t.shape) != shape) \
+            or not ((t.is_cuda and t.device == device) or t.is_pinned()):
+        size = f"{count} contiguous {str(dtype)[6:]} words" if shape is None else f"a contiguous {str(dtype)[6:]} {list(shape)}"
+        raise _lib.PxtError(f"{op}: {name} needs {size} in memory of {device} or pinned host memory (got "
+                            f"{tuple(t.shape)}, {t.dtype}, {t.device})")
+    return t.data_ptr()
+
+
+def _workspace(op, workspace, need, unsupported, any_dtype=""):
+    """``need`` = what the op's size query answered; <= 0 says that it does not support the problem.  Two forms: a
+    contiguous uint8 tensor of that many bytes, or (``any_dtype`` = what to call it) a tensor of any dtype with that
+    many - all the LM and depth-refinement ops ever asked."""
+    if need <= 0:
+        raise _lib.PxtError(f"{op}: {unsupported}")
+    if any_dtype:
+        if workspace.numel() * workspace.element_size() < need:
+            raise _lib.PxtError(f"{op}: {any_dtype} holds {workspace.numel() * workspace.element_size()} bytes, {need} needed")
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.PxtError(f"{op}: workspace is a contiguous uint8 tensor of >= {need} bytes (got {workspace.numel()}, "
+                            f"{workspace.dtype})")
+
+
+def _one_device(op, anchor, named, where=""):
+    """Every tensor of ``named`` = (tensor or None, name) pairs lives on the ROCm device of ``anchor``.  The
+    dispatcher only guarantees that SOME argument is a device tensor, and a kernel dereferences them all: a host
+    pointer or another device's there is a memory fault, not an error."""
+    index = anchor.get_device()  # (-1: host memory; comparing indices is the cheap way to pass)
+    for t, name in named:
+        if t is None or (t.get_device() == index and index >= 0):
+            continue
+        _lib.require_gpu(t, name)
+        if t.device != anchor.device:
+            raise _lib.PxtError(f"{op}: {name}{where} is on {t.device}, not on {anchor.device}")
 
 
 # ------------------------------------------------------------------------------------------- LM
+_LM_HEADER = 16 + _lib.PXT_MAX_LEVELS  # the floats of an LM output record ahead of its iteration log
+
+
+def _lm_conf(pad, loss, loss_alpha, loss_scale, min_valid=0, num_iters=0, grad_stop=0.0, dt_stop=0.0, dR_stop=0.0,
+             n_workgroups=0, spin_limit=0, lm_path=0):
+    conf = _lib.LmConf()
+    conf.num_iters, conf.pad, conf.loss = int(num_iters), int(pad), int(loss)
+    conf.loss_alpha, conf.loss_scale = float(loss_alpha), float(loss_scale)
+    conf.grad_stop, conf.dt_stop, conf.dR_stop = float(grad_stop), float(dt_stop), float(dR_stop)
+    conf.min_valid, conf.n_workgroups, conf.spin_limit = int(min_valid), int(n_workgroups), int(spin_limit)
+    conf.path = int(lm_path)
+    return conf
+
+
+def _lm_level(op, lv, where, fmap, table, n, channels, camera, ndist, lambdas=None, field="fref"):
+    """One level: the query map [h, w, cstride] and a table [n, cstride] of per-point records - the reference
+    records, or sample_sparse's output - checked and written into the level record ``lv`` (pxt_lm_level,
+    pxt_sample_level, pxt_reloc_map; ``field``: where the table's pointer goes, None for a record without one)."""
+    _dense(op, fmap, "fmap", torch.float32, _ANY3, where)
+    h, w, cs = fmap.shape
+    if table.shape != (n, cs) or table.dtype != torch.float32 or not table.is_contiguous():  # (per level, K x levels per
+        _dense(op, table, field or "fref", torch.float32, (n, cs), where)                    # launch: refusing is _dense's)
+    lv.fmap, lv.h, lv.w, lv.C, lv.cstride = fmap.data_ptr(), h, w, int(channels), cs
+    if field is not None:
+        setattr(lv, field, table.data_ptr())
+    lv.cam[:] = camera
+    lv.ndist = int(ndist)
+    if lambdas is not None:
+        lv.lambda_[:] = lambdas
+
+
+def _lm_camera(op, conv27, slots, cam_out, device):
+    """pxt_lm_camera: the kernel's epilogue also derives the next render's camera and stores it in up to two renderer
+    slots (0: none) and in ``cam_out`` (13 floats the host reads, or None)."""
+    cam = _lib.LmCamera()
+    cam.conv27[:] = [float(x) for x in conv27]
+    for k in range(2):
+        cam.cam_slot[k] = (int(slots[k]) or None) if k < len(slots) else None
+    cam.cam_out13 = None if cam_out is None else _record(op, cam_out, "cam_out", torch.float32, 13, device)
+    return cam
+
+
+def _lm_record(op, record, name, n_levels, num_iters, want_log, device):
+    """An LM output record: the header, then the iteration log when wanted -> the addresses of the two."""
+    log = n_levels * int(num_iters) * _lib.PXT_LM_LOG_STRIDE if want_log else 0
+    out = _record(op, record, name, torch.float32, _LM_HEADER + log, device)
+    return out, out + 4 * _LM_HEADER if want_log else None
+
+
 def _lm_refine(p3d, point_mask, fmaps, frefs, channels, cameras, ndist, lambdas, T_init, num_iters, pad, loss,
                loss_alpha, loss_scale, grad_stop, dt_stop, dR_stop, min_valid, n_workgroups, record, workspace,
                want_log, spin_limit=0, cam_conv=None, cam_slots=None, cam_out=None, lm_path=0, guard_level=-1,
@@ -296,180 +444,112 @@ def _lm_refine(p3d, point_mask, fmaps, frefs, channels, cameras, ndist, lambdas,
     """``guard_level`` (index in execution order), ``guard_flags`` (uint8 device tensor) and ``guard_geo`` = [tile_rows,
     tiles_per_row, tile_x0, tile_y0]: that level's map holds data only in the tiles whose flag is 1
     (pxt_lm_tile_guard, pxt_lm_refine_guarded); a launch that reads another tile ends with status PXT_E_GUARD."""
-    L = _lib.lib()
+    op = "lm_refine"
     n_levels = len(fmaps)
     if not (1 <= n_levels <= _lib.PXT_MAX_LEVELS) or len(frefs) != n_levels or len(channels) != n_levels:
-        raise _lib.PxtError(f"lm_refine: {n_levels} levels (1..{_lib.PXT_MAX_LEVELS}), {len(frefs)} frefs, {len(channels)} channels")
+        raise _lib.PxtError(f"{op}: {n_levels} levels (1..{_lib.PXT_MAX_LEVELS}), {len(frefs)} frefs, {len(channels)} channels")
     if len(cameras) != 10 * n_levels or len(lambdas) != 6 * n_levels or len(ndist) != n_levels or len(T_init) != 12:
-        raise _lib.PxtError("lm_refine: cameras need 10, lambdas 6 floats per level, T_init 12 floats")
-    _f32c(p3d, "p3d")
-    n = int(p3d.shape[0])
+        raise _lib.PxtError(f"{op}: cameras need 10, lambdas 6 floats per level, T_init 12 floats")
+    n = int(_dense(op, p3d, "p3d").shape[0])
     arr = (_lib.LmLevel * n_levels)()
     for i in range(n_levels):
-        fm, fr = _f32c(fmaps[i], "fmap"), _f32c(frefs[i], "fref")
-        h, w, cs = fm.shape
-        if tuple(fr.shape) != (n, cs):
-            raise _lib.PxtError(f"lm_refine: fref of level {i} is {tuple(fr.shape)}, expected {(n, cs)}")
-        arr[i].fmap, arr[i].fref = fm.data_ptr(), fr.data_ptr()
-        arr[i].h, arr[i].w, arr[i].C, arr[i].cstride = h, w, int(channels[i]), cs
-        arr[i].cam[:] = cameras[10 * i:10 * i + 10]
-        arr[i].ndist = int(ndist[i])
-        arr[i].lambda_[:] = lambdas[6 * i:6 * i + 6]
+        _lm_level(op, arr[i], (" of level ", i), fmaps[i], frefs[i], n, channels[i], cameras[10 * i:10 * i + 10], ndist[i],
+                  lambdas[6 * i:6 * i + 6])
     guard = None
     if guard_flags is not None:
         if guard_geo is None or len(guard_geo) != 4:
-            raise _lib.PxtError("lm_refine: guard_geo holds tile_rows, tiles_per_row, tile_x0, tile_y0")
-        gl, flags = guard_level, guard_flags
-        tile_rows, tiles_per_row, tile_x0, tile_y0 = guard_geo
-        if not (0 <= int(gl) < n_levels) or flags.dtype != torch.uint8 or not flags.is_cuda or not flags.is_contiguous():
-            raise _lib.PxtError("lm_refine: tile_guard names a level and a contiguous uint8 device tensor of flags")
-        rows = (int(tile_y0) + arr[int(gl)].h - 1) // max(int(tile_rows), 1) + 1
-        if int(tile_rows) < 1 or flags.numel() < rows * int(tiles_per_row):
-            raise _lib.PxtError(f"lm_refine: tile_guard needs {rows} x {int(tiles_per_row)} flags, got {flags.numel()}")
-        guard = _lib.LmTileGuard()
-        guard.level, guard.tile_flags = int(gl), flags.data_ptr()
-        guard.tile_rows, guard.tiles_per_row, guard.tile_x0, guard.tile_y0 = (int(tile_rows), int(tiles_per_row),
-                                                                              int(tile_x0), int(tile_y0))
-    conf = _lib.LmConf()
-    conf.num_iters, conf.pad, conf.loss = int(num_iters), int(pad), int(loss)
-    conf.loss_alpha, conf.loss_scale = float(loss_alpha), float(loss_scale)
-    conf.grad_stop, conf.dt_stop, conf.dR_stop = float(grad_stop), float(dt_stop), float(dR_stop)
-    conf.min_valid, conf.n_workgroups, conf.spin_limit = int(min_valid), int(n_workgroups), int(spin_limit)
-    conf.path = int(lm_path)
-    nh = 16 + _lib.PXT_MAX_LEVELS
-    need = nh + (n_levels * int(num_iters) * _lib.PXT_LM_LOG_STRIDE if want_log else 0)
-    if record.dtype != torch.float32 or record.numel() < need or not record.is_contiguous():
-        raise _lib.PxtError(f"lm_refine: record needs {need} contiguous float32 values")
-    if not (record.is_cuda or record.is_pinned()):
-        raise _lib.PxtError("lm_refine: record must be device memory or pinned host memory")
-    if point_mask is not None and (point_mask.dtype != torch.uint8 or not point_mask.is_contiguous()):
-        raise _lib.PxtError("lm_refine: point_mask must be contiguous uint8")
-    base = record.data_ptr()
-    T0 = (C.c_float * 12)(*[float(x) for x in T_init])
+            raise _lib.PxtError(f"{op}: guard_geo holds tile_rows, tiles_per_row, tile_x0, tile_y0")
+        gl, flags = int(guard_level), guard_flags
+        tile_rows, tiles_per_row, tile_x0, tile_y0 = (int(x) for x in guard_geo)
+        if not (0 <= gl < n_levels) or flags.dtype != torch.uint8 or not flags.is_cuda or not flags.is_contiguous():
+            raise _lib.PxtError(f"{op}: tile_guard names a level and a contiguous uint8 device tensor of flags")
+        rows = (tile_y0 + arr[gl].h - 1) // max(tile_rows, 1) + 1
+        if tile_rows < 1 or flags.numel() < rows * tiles_per_row:
+            raise _lib.PxtError(f"{op}: tile_guard needs {rows} x {tiles_per_row} flags, got {flags.numel()}")
+        guard = _lib.LmTileGuard(gl, flags.data_ptr(), tile_rows, tiles_per_row, tile_x0, tile_y0)
+    conf = _lm_conf(pad, loss, loss_alpha, loss_scale, min_valid, num_iters, grad_stop, dt_stop, dR_stop, n_workgroups,
+                    spin_limit, lm_path)
+    out, log = _lm_record(op, record, "record", n_levels, num_iters, want_log, p3d.device)
+    _point_mask(op, point_mask, n)
     cam = None
-    if cam_conv is not None:  # the kernel's epilogue also derives the next render's camera (pxt_lm_refine_cam)
+    if cam_conv is not None:  # the kernel's epilogue also derives the next render's camera
+        slots = cam_slots or []
         if len(cam_conv) != 27:
-            raise _lib.PxtError("lm_refine: cam_conv holds 27 doubles (Testbed.pose_conversion)")
-        slots = [int(x) for x in (cam_slots or [])]
+            raise _lib.PxtError(f"{op}: cam_conv holds 27 doubles (Testbed.pose_conversion)")
         if len(slots) > 2 or (not slots and cam_out is None):
-            raise _lib.PxtError("lm_refine: at most two camera slots; at least one slot or cam_out")
-        cam = _lib.LmCamera()
-        cam.conv27[:] = [float(x) for x in cam_conv]
-        for k in range(2):
-            cam.cam_slot[k] = slots[k] if k < len(slots) and slots[k] else None
-        cam.cam_out13 = None
-        if cam_out is not None:
-            if cam_out.dtype != torch.float32 or cam_out.numel() < 13 or not (cam_out.is_cuda or cam_out.is_pinned()):
-                raise _lib.PxtError("lm_refine: cam_out must be a pinned host (or device) float32 tensor of >= 13 elements")
-            cam.cam_out13 = cam_out.data_ptr()
-        if guard is None:
-            _lib.check(
-                L.pxt_lm_refine_cam(p3d.data_ptr(), _lib.dptr(point_mask), n, arr, n_levels, T0, C.byref(conf), base,
-                                    base + 4 * nh if want_log else None, workspace.data_ptr(), C.byref(cam), _stream(p3d)),
-                "pxt_lm_refine_cam")
-            return
-    if guard is not None:
-        _lib.check(
-            L.pxt_lm_refine_guarded(p3d.data_ptr(), _lib.dptr(point_mask), n, arr, n_levels, T0, C.byref(conf), base,
-                                    base + 4 * nh if want_log else None, workspace.data_ptr(),
-                                    C.byref(cam) if cam is not None else None, C.byref(guard), _stream(p3d)),
-            "pxt_lm_refine_guarded")
-        return
-    _lib.check(
-        L.pxt_lm_refine(p3d.data_ptr(), _lib.dptr(point_mask), n, arr, n_levels, T0, C.byref(conf), base,
-                        base + 4 * nh if want_log else None, workspace.data_ptr(), _stream(p3d)),
-        "pxt_lm_refine")
+            raise _lib.PxtError(f"{op}: at most two camera slots; at least one slot or cam_out")
+        cam = _lm_camera(op, cam_conv, slots, cam_out, p3d.device)
+    T0 = (C.c_float * 12)(*[float(x) for x in T_init])
+    # (pxt_lm_refine and pxt_lm_refine_cam are this entry with no camera and no guard)
+    _lib.check(_lib.lib().pxt_lm_refine_guarded(
+        p3d.data_ptr(), _lib.dptr(point_mask), n, arr, n_levels, T0, C.byref(conf), out, log, workspace.data_ptr(),
+        None if cam is None else C.byref(cam), None if guard is None else C.byref(guard), _stream(p3d)),
+        "pxt_lm_refine_guarded")
 
 
 def _lm_refine_batch(p3d, point_masks, n_levels, fmaps, frefs, channels, cameras, ndist, lambdas, T_init, num_iters, pad,
                      loss, loss_alpha, loss_scale, grad_stop, dt_stop, dR_stop, min_valid, n_workgroups, records,
                      workspaces, batch_workspace, want_log, spin_limit=0, cam_conv=None, cam_slots=None, cam_outs=None,
                      lm_path=0, cam_enabled=None):
+    op = "lm_refine_batch"
     L = _lib.lib()
     K = len(p3d)
     n_levels = [int(x) for x in n_levels]
     nl_tot = sum(n_levels)
     if not (1 <= K <= _lib.PXT_LM_MAX_BATCH) or len(n_levels) != K or len(records) != K or len(workspaces) != K \
             or len(point_masks) != K or len(T_init) != 12 * K:
-        raise _lib.PxtError(f"lm_refine_batch: {K} problems (1..{_lib.PXT_LM_MAX_BATCH}) need one record, workspace, mask slot "
+        raise _lib.PxtError(f"{op}: {K} problems (1..{_lib.PXT_LM_MAX_BATCH}) need one record, workspace, mask slot "
                             "and 12 pose floats each")
     if len(fmaps) != nl_tot or len(frefs) != nl_tot or len(channels) != nl_tot or len(cameras) != 10 * nl_tot \
             or len(lambdas) != 6 * nl_tot or len(ndist) != nl_tot:
-        raise _lib.PxtError("lm_refine_batch: per level one fmap, fref, channel count, ndist, 10 camera and 6 lambda floats")
-    conf = _lib.LmConf()
-    conf.num_iters, conf.pad, conf.loss = int(num_iters), int(pad), int(loss)
-    conf.loss_alpha, conf.loss_scale = float(loss_alpha), float(loss_scale)
-    conf.grad_stop, conf.dt_stop, conf.dR_stop = float(grad_stop), float(dt_stop), float(dR_stop)
-    conf.min_valid, conf.n_workgroups, conf.spin_limit = int(min_valid), int(n_workgroups), int(spin_limit)
-    conf.path = int(lm_path)
-    nh = 16 + _lib.PXT_MAX_LEVELS
+        raise _lib.PxtError(f"{op}: per level one fmap, fref, channel count, ndist, 10 camera and 6 lambda floats")
+    conf = _lm_conf(pad, loss, loss_alpha, loss_scale, min_valid, num_iters, grad_stop, dt_stop, dR_stop, n_workgroups,
+                    spin_limit, lm_path)
     if cam_conv is not None and (len(cam_conv) != 27 * K or len(cam_slots or []) != 2 * K
                                  or (cam_outs is not None and len(cam_outs) != K)):
-        raise _lib.PxtError("lm_refine_batch: cam_conv holds 27 doubles, cam_slots 2 pointers (0 = none) per problem")
+        raise _lib.PxtError(f"{op}: cam_conv holds 27 doubles, cam_slots 2 pointers (0 = none) per problem")
+    device = p3d[0].device
     probs = (_lib.LmProblem * K)()
     keep = []  # ctypes records the problem array points to
     li = 0
     for k in range(K):
-        _f32c(p3d[k], "p3d")
-        n = int(p3d[k].shape[0])
-        nl = n_levels[k]
+        where, nl, mk = f" of problem {k}", n_levels[k], point_masks[k]
+        n = int(_dense(op, p3d[k], "p3d" + where).shape[0])
         if not (1 <= nl <= _lib.PXT_MAX_LEVELS):
-            raise _lib.PxtError(f"lm_refine_batch: problem {k} has {nl} levels")
+            raise _lib.PxtError(f"{op}: problem {k} has {nl} levels")
         arr = (_lib.LmLevel * nl)()
         for i in range(nl):
-            fm, fr = _f32c(fmaps[li], "fmap"), _f32c(frefs[li], "fref")
-            h, w, cs = fm.shape
-            if tuple(fr.shape) != (n, cs):
-                raise _lib.PxtError(f"lm_refine_batch: fref of problem {k} level {i} is {tuple(fr.shape)}, expected {(n, cs)}")
-            arr[i].fmap, arr[i].fref = fm.data_ptr(), fr.data_ptr()
-            arr[i].h, arr[i].w, arr[i].C, arr[i].cstride = h, w, int(channels[li]), cs
-            arr[i].cam[:] = cameras[10 * li:10 * li + 10]
-            arr[i].ndist = int(ndist[li])
-            arr[i].lambda_[:] = lambdas[6 * li:6 * li + 6]
+            _lm_level(op, arr[i], (where, " level ", i), fmaps[li], frefs[li], n, channels[li], cameras[10 * li:10 * li + 10],
+                      ndist[li], lambdas[6 * li:6 * li + 6])
             li += 1
-        rec = records[k]
-        need = nh + (nl * int(num_iters) * _lib.PXT_LM_LOG_STRIDE if want_log else 0)
-        if rec.dtype != torch.float32 or rec.numel() < need or not rec.is_contiguous() or not (rec.is_cuda or rec.is_pinned()):
-            raise _lib.PxtError(f"lm_refine_batch: record {k} needs {need} contiguous float32 values in device or pinned memory")
-        mk = point_masks[k]
-        if mk is not None and (mk.dtype != torch.uint8 or not mk.is_contiguous() or mk.numel() != n):
-            raise _lib.PxtError("lm_refine_batch: point masks are contiguous uint8 [n_points]")
-        T0 = (C.c_float * 12)(*[float(x) for x in T_init[12 * k:12 * k + 12]])
         q = probs[k]
+        q.out, q.log = _lm_record(op, records[k], f"record {k}", nl, num_iters, want_log, device)
+        _point_mask(op, mk, n, "point_mask" + where)
+        T0 = (C.c_float * 12)(*[float(x) for x in T_init[12 * k:12 * k + 12]])
         q.p3d, q.point_mask, q.n_points = p3d[k].data_ptr(), _lib.dptr(mk), n
         q.levels_host, q.n_levels, q.T_init_host = arr, nl, T0
-        q.out = rec.data_ptr()
-        q.log = rec.data_ptr() + 4 * nh if want_log else None
         q.workspace = workspaces[k].data_ptr()
         cam = None
         if cam_conv is not None and (cam_enabled is None or cam_enabled[k]):
-            cam = _lib.LmCamera()
-            cam.conv27[:] = [float(x) for x in cam_conv[27 * k:27 * k + 27]]
-            for j in range(2):
-                cam.cam_slot[j] = int(cam_slots[2 * k + j]) or None
-            cam.cam_out13 = None
-            if cam_outs is not None:
-                co = cam_outs[k]
-                if co.dtype != torch.float32 or co.numel() < 13 or not (co.is_cuda or co.is_pinned()):
-                    raise _lib.PxtError("lm_refine_batch: cam_outs are pinned host (or device) float32 tensors of >= 13 elements")
-                cam.cam_out13 = co.data_ptr()
+            cam = _lm_camera(op, cam_conv[27 * k:27 * k + 27], cam_slots[2 * k:2 * k + 2],
+                             None if cam_outs is None else cam_outs[k], device)
             q.cam_host = C.pointer(cam)
         keep.append((arr, T0, cam))
-    if batch_workspace.numel() * batch_workspace.element_size() < int(L.pxt_lm_batch_workspace_bytes(K)):
-        raise _lib.PxtError("lm_refine_batch: batch_workspace smaller than pxt_lm_batch_workspace_bytes(K)")
+    # (K is in range: the size query cannot answer "not supported" here, nor in the two bodies below that pass any_dtype)
+    _workspace(op, batch_workspace, int(L.pxt_lm_batch_workspace_bytes(K)), f"{K} problems are not supported",
+               any_dtype="batch_workspace")
     _lib.check(L.pxt_lm_refine_batch(probs, K, C.byref(conf), batch_workspace.data_ptr(), _stream(p3d[0])),
                "pxt_lm_refine_batch")
 
 
 def _lm_evaluate(op, problems, conf, records, workspace, *, entry, workspace_bytes, Problem, max_problems, record_name,
-                 n_record, own, extras=(), extra_names=""):
+                 record_field, n_record, own=None, extras=(), extra_names=""):
     """The K (points, level, pose) problems of lm_information / lm_point_report: checked, packed and launched through
     ``entry``.  ``problems`` = the ops' common per-problem arguments in schema order (p3d ... pose_is_lm_record),
-    ``conf`` = (pad, loss, loss_alpha, loss_scale, min_valid).  ``own(q, k, n)`` checks and sets what only ``op`` has
-    (one list per problem in ``extras``, and the record's pointer) and returns the (tensor, name) pairs the kernel
-    dereferences besides."""
+    ``conf`` = (pad, loss, loss_alpha, loss_scale, min_valid); problem k's record goes into ``record_field``.
+    ``own(q, k, n)`` checks and sets what only ``op`` has (one list per problem in ``extras``) and returns the
+    (tensor, name) pairs the kernel dereferences besides."""
     p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record = problems
-    pad, loss, loss_alpha, loss_scale, min_valid = conf
     K = len(p3d)
     if not (1 <= K <= max_problems):
         raise _lib.PxtError(f"{op}: {K} problems (1..{max_problems})")
@@ -477,153 +557,97 @@ def _lm_evaluate(op, problems, conf, records, workspace, *, entry, workspace_byt
             or len(cameras) != 10 * K:
         raise _lib.PxtError(f"{op}: per problem one mask slot, map, reference table, channel count, ndist, pose, "
                             f"{extra_names}{record_name} and 10 camera floats")
-    _lib.require_gpu(workspace, "workspace")
-    dev = workspace.device
+    _one_device(op, workspace, [(workspace, "workspace")])
     probs = (Problem * K)()
     for k in range(K):
-        pts, fm, fr = _f32c(p3d[k], "p3d"), _f32c(fmaps[k], "fmap"), _f32c(frefs[k], "fref")
-        n = int(pts.shape[0])
-        if fm.dim() != 3 or tuple(pts.shape) != (n, 3) or tuple(fr.shape) != (n, int(fm.shape[2])):
-            raise _lib.PxtError(f"{op}: problem {k}: p3d {tuple(pts.shape)}, fmap {tuple(fm.shape)}, fref "
-                                f"{tuple(fr.shape)}; expected [N, 3], [h, w, cstride], [N, cstride]")
-        mk = point_masks[k]
-        if mk is not None and (mk.dtype != torch.uint8 or not mk.is_contiguous() or mk.numel() != n):
-            raise _lib.PxtError(f"{op}: point masks are contiguous uint8 [n_points]")
-        q = probs[k]
-        more = own(q, k, n)
-        # what the kernel dereferences must be device memory of one device (a host pointer there is a memory fault,
-        # not an error); the pose and the record may also be pinned host memory
-        for t, name in ((pts, "p3d"), (fm, "fmap"), (fr, "fref"), (mk, "point_mask"), *more):
-            if t is None:
-                continue
-            _lib.require_gpu(t, name)
-            if t.device != dev:
-                raise _lib.PxtError(f"{op}: {name} of problem {k} is on {t.device}, the workspace on {dev}")
-        need = 16 if pose_is_lm_record else 12
-        for t, name, count in ((poses[k], "pose", need), (records[k], record_name, n_record)):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < count \
-                    or not ((t.is_cuda and t.device == dev) or t.is_pinned()):
-                raise _lib.PxtError(f"{op}: {name} {k} needs {count} contiguous float32 values in device or pinned memory")
-        q.p3d, q.point_mask, q.n_points = pts.data_ptr(), _lib.dptr(mk), n
-        h, w, cs = (int(x) for x in fm.shape)
-        q.level.fmap, q.level.fref = fm.data_ptr(), fr.data_ptr()
-        q.level.h, q.level.w, q.level.C, q.level.cstride = h, w, int(channels[k]), cs
-        q.level.cam[:] = [float(x) for x in cameras[10 * k:10 * k + 10]]
-        q.level.ndist = int(ndist[k])
-        q.pose, q.pose_is_lm_record = poses[k].data_ptr(), int(bool(pose_is_lm_record))
-    if workspace.numel() * workspace.element_size() < int(workspace_bytes(K)):
-        raise _lib.PxtError(f"{op}: workspace smaller than {workspace_bytes.__name__}(K)")
-    conf = _lib.LmConf()
-    conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale = int(pad), int(loss), float(loss_alpha), float(loss_scale)
-    conf.min_valid = int(min_valid)
-    _lib.check(entry(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), entry.__name__)
+        where, q, mk = f" of problem {k}", probs[k], point_masks[k]
+        n = int(_dense(op, p3d[k], "p3d" + where, shape=(None, 3)).shape[0])
+        _lm_level(op, q.level, where, fmaps[k], frefs[k], n, channels[k], cameras[10 * k:10 * k + 10], ndist[k])
+        _point_mask(op, mk, n, "point_mask" + where)
+        more = own(q, k, n) if own is not None else ()
+        # (the pose and the record may also be pinned host memory)
+        _one_device(op, workspace, [(p3d[k], "p3d"), (fmaps[k], "fmap"), (frefs[k], "fref"), (mk, "point_mask"), *more], where)
+        q.pose = _record(op, poses[k], f"pose {k}", torch.float32, 16 if pose_is_lm_record else 12, workspace.device)
+        setattr(q, record_field, _record(op, records[k], f"{record_name} {k}", torch.float32, n_record, workspace.device))
+        q.p3d, q.point_mask, q.n_points = p3d[k].data_ptr(), _lib.dptr(mk), n
+        q.pose_is_lm_record = int(bool(pose_is_lm_record))
+    _workspace(op, workspace, int(workspace_bytes(K)), f"{K} problems are not supported", any_dtype="workspace")
+    _lib.check(entry(probs, K, C.byref(_lm_conf(*conf)), workspace.data_ptr(), _stream(workspace)), entry.__name__)
 
 
 def _lm_information(p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record, pad, loss,
                     loss_alpha, loss_scale, min_valid, records, workspace):
-    def own(q, k, n):
-        q.out = records[k].data_ptr()
-        return ()
-
     L = _lib.lib()
     _lm_evaluate("lm_information", (p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record),
                  (pad, loss, loss_alpha, loss_scale, min_valid), records, workspace, entry=L.pxt_lm_information,
                  workspace_bytes=L.pxt_lm_information_workspace_bytes, Problem=_lib.LmInfoProblem,
-                 max_problems=_lib.PXT_LM_INFO_MAX_PROBLEMS, record_name="record", n_record=_lib.PXT_LM_INFO_RECORD, own=own)
+                 max_problems=_lib.PXT_LM_INFO_MAX_PROBLEMS, record_name="record", record_field="out",
+                 n_record=_lib.PXT_LM_INFO_RECORD)
 
 
 def _lm_point_report(p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record, pad, loss,
                      loss_alpha, loss_scale, min_valid, inlier_weights, points, summaries, workspace):
     def own(q, k, n):
         out = points[k]
-        if out is not None and (out.dtype != torch.float32 or not out.is_contiguous()
-                                or tuple(out.shape) != (n, _lib.PXT_LM_POINT_RECORD)):
-            raise _lib.PxtError(f"lm_point_report: points of problem {k} are a contiguous float32 [{n}, "
-                                f"{_lib.PXT_LM_POINT_RECORD}] tensor (got {tuple(out.shape)}, {out.dtype})")
-        q.inlier_weight, q.points, q.summary = float(inlier_weights[k]), _lib.dptr(out), summaries[k].data_ptr()
+        if out is not None:
+            _dense("lm_point_report", out, f"points of problem {k}", shape=(n, _lib.PXT_LM_POINT_RECORD))
+        q.inlier_weight, q.points = float(inlier_weights[k]), _lib.dptr(out)
         return ((out, "points"),)
 
     L = _lib.lib()
     _lm_evaluate("lm_point_report", (p3d, point_masks, fmaps, frefs, channels, cameras, ndist, poses, pose_is_lm_record),
                  (pad, loss, loss_alpha, loss_scale, min_valid), summaries, workspace, entry=L.pxt_lm_point_report,
                  workspace_bytes=L.pxt_lm_point_report_workspace_bytes, Problem=_lib.LmReportProblem,
-                 max_problems=_lib.PXT_LM_REPORT_MAX_PROBLEMS, record_name="summary", n_record=_lib.PXT_LM_REPORT_SUMMARY,
-                 own=own, extras=(inlier_weights, points), extra_names="inlier weight, points slot, ")
+                 max_problems=_lib.PXT_LM_REPORT_MAX_PROBLEMS, record_name="summary", record_field="summary",
+                 n_record=_lib.PXT_LM_REPORT_SUMMARY, own=own, extras=(inlier_weights, points),
+                 extra_names="inlier weight, points slot, ")
 
 
 # ------------------------------------------------------------------------------------ sampling
 def _sample_sparse(p3d, T, fmaps, channels, cameras, ndist, pad, normalize, outs, valid, windows=None):
-    L = _lib.lib()
+    op = "sample_sparse"
     n_levels = len(fmaps)
     if len(outs) != n_levels or len(cameras) != 10 * n_levels or len(T) != 12:
-        raise _lib.PxtError("sample_sparse: one out tensor and 10 camera floats per level, T of 12 floats")
+        raise _lib.PxtError(f"{op}: one out tensor and 10 camera floats per level, T of 12 floats")
     if windows is not None and len(windows) != 4 * n_levels:
-        raise _lib.PxtError("sample_sparse: windows holds (x0, y0, full_w, full_h) per level")
-    _f32c(p3d, "p3d")
-    n = int(p3d.shape[0])
+        raise _lib.PxtError(f"{op}: windows holds (x0, y0, full_w, full_h) per level")
+    n = int(_dense(op, p3d, "p3d").shape[0])
     arr = (_lib.SampleLevel * n_levels)()
     for i in range(n_levels):
-        fm, out = _f32c(fmaps[i], "fmap"), _f32c(outs[i], "out")
-        h, w, cs = fm.shape
-        if tuple(out.shape) != (n, cs):
-            raise _lib.PxtError(f"sample_sparse: out of level {i} is {tuple(out.shape)}, expected {(n, cs)}")
-        arr[i].fmap, arr[i].out = fm.data_ptr(), out.data_ptr()
-        arr[i].h, arr[i].w, arr[i].C, arr[i].cstride = h, w, int(channels[i]), cs
-        arr[i].cam[:] = cameras[10 * i:10 * i + 10]
-        arr[i].ndist = int(ndist[i])
+        _lm_level(op, arr[i], (" of level ", i), fmaps[i], outs[i], n, channels[i], cameras[10 * i:10 * i + 10], ndist[i],
+                  field="out")
         if windows is not None:  # (x0, y0, full_w, full_h) per level: the map is a window of the full level
             arr[i].x0, arr[i].y0, arr[i].full_w, arr[i].full_h = (int(x) for x in windows[4 * i:4 * i + 4])
     if valid.dtype != torch.uint8 or valid.numel() != n:
-        raise _lib.PxtError("sample_sparse: valid must be uint8 [n_points]")
+        raise _lib.PxtError(f"{op}: valid must be uint8 [n_points]")
     T12 = (C.c_float * 12)(*[float(x) for x in T])
-    _lib.check(L.pxt_sample_sparse(p3d.data_ptr(), n, T12, arr, n_levels, int(pad), int(bool(normalize)),
-                                   valid.data_ptr(), _stream(p3d)), "pxt_sample_sparse")
+    _lib.check(_lib.lib().pxt_sample_sparse(p3d.data_ptr(), n, T12, arr, n_levels, int(pad), int(bool(normalize)),
+                                            valid.data_ptr(), _stream(p3d)), "pxt_sample_sparse")
 
 
 # ------------------------------------------------------------------------------ relocalisation
 def _score_pose_hypotheses(fmap, channels, camera, ndist, p3d, fref, valid, poses, ranges, pad, loss, loss_alpha, loss_scale,
                            out):
-    L = _lib.lib()
-    _f32c(fmap, "fmap")
-    _f32c(p3d, "p3d")
-    _f32c(fref, "fref")
-    _f32c(poses, "poses")
-    _f32c(out, "out")
-    if fmap.dim() != 3 or len(camera) != 10:
-        raise _lib.PxtError("score_pose_hypotheses: fmap is [h, w, cstride], camera 10 floats")
-    h, w, cs = (int(x) for x in fmap.shape)
-    n = int(p3d.shape[0])
-    if tuple(p3d.shape) != (n, 3) or tuple(fref.shape) != (n, cs):
-        raise _lib.PxtError(f"score_pose_hypotheses: p3d {tuple(p3d.shape)} / fref {tuple(fref.shape)}, expected "
-                            f"{(n, 3)} / {(n, cs)}")
-    if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or valid.numel() != n):
-        raise _lib.PxtError("score_pose_hypotheses: valid must be contiguous uint8 [n_points]")
-    M = int(poses.shape[0]) if poses.dim() == 2 else -1
-    if M < 1 or tuple(poses.shape) != (M, 12):
-        raise _lib.PxtError(f"score_pose_hypotheses: poses is {tuple(poses.shape)}, expected [M >= 1, 12]")
-    if ranges.dtype != torch.int32 or not ranges.is_contiguous() or tuple(ranges.shape) != (M, 2):
-        raise _lib.PxtError("score_pose_hypotheses: ranges must be contiguous int32 [M, 2]")
-    if out.numel() != 4 * M:
-        raise _lib.PxtError("score_pose_hypotheses: out holds 4 floats per hypothesis")
-    # every buffer the kernel reads or writes must be device memory of the map's device (a host pointer in the kernel
-    # would be a memory fault, not an error)
-    for t, name in ((fmap, "fmap"), (p3d, "p3d"), (fref, "fref"), (valid, "valid"), (poses, "poses"), (ranges, "ranges"),
-                    (out, "out")):
-        if t is None:
-            continue
-        _lib.require_gpu(t, name)
-        if t.device != fmap.device:
-            raise _lib.PxtError(f"score_pose_hypotheses: {name} is on {t.device}, the map on {fmap.device}")
+    op = "score_pose_hypotheses"
+    if len(camera) != 10:
+        raise _lib.PxtError(f"{op}: camera holds 10 floats")
+    n = int(_dense(op, p3d, "p3d", shape=(None, 3)).shape[0])
     mp = _lib.RelocMap()
-    mp.fmap, mp.h, mp.w, mp.C, mp.cstride = fmap.data_ptr(), h, w, int(channels), cs
-    mp.cam[:] = [float(x) for x in camera]
-    mp.ndist = int(ndist)
-    bank = _lib.RelocBank()
-    bank.p3d, bank.fref, bank.valid, bank.n_points = p3d.data_ptr(), fref.data_ptr(), _lib.dptr(valid), n
-    conf = _lib.LmConf()
-    conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale = int(pad), int(loss), float(loss_alpha), float(loss_scale)
-    _lib.check(L.pxt_score_pose_hypotheses(C.byref(mp), C.byref(bank), poses.data_ptr(), ranges.data_ptr(), M, C.byref(conf),
-                                           out.data_ptr(), _stream(fmap)), "pxt_score_pose_hypotheses")
+    _lm_level(op, mp, "", fmap, fref, n, channels, camera, ndist, field=None)
+    _point_mask(op, valid, n, "valid")
+    M = int(_dense(op, poses, "poses", shape=(None, 12)).shape[0])
+    if M < 1:
+        raise _lib.PxtError(f"{op}: poses is {tuple(poses.shape)}, expected [M >= 1, 12]")
+    _dense(op, ranges, "ranges", torch.int32, (M, 2))
+    if _dense(op, out, "out").numel() != 4 * M:
+        raise _lib.PxtError(f"{op}: out holds 4 floats per hypothesis")
+    _one_device(op, fmap, [(fmap, "fmap"), (p3d, "p3d"), (fref, "fref"), (valid, "valid"), (poses, "poses"),
+                           (ranges, "ranges"), (out, "out")])
+    bank = _lib.RelocBank(p3d.data_ptr(), fref.data_ptr(), _lib.dptr(valid), n)
+    conf = _lm_conf(pad, loss, loss_alpha, loss_scale)
+    _lib.check(_lib.lib().pxt_score_pose_hypotheses(C.byref(mp), C.byref(bank), poses.data_ptr(), ranges.data_ptr(), M,
+                                                    C.byref(conf), out.data_ptr(), _stream(fmap)),
+               "pxt_score_pose_hypotheses")
 
 
 # ---------------------------------------------------------------------------------------- UNet
@@ -633,10 +657,8 @@ def _unet_points(images, n, sample_p3d, sample_pose_camera, sample_ints):
         if n > 2 or sample_pose_camera is None or sample_ints is None or len(sample_pose_camera) != 22 or len(sample_ints) < 6:
             raise _lib.PxtError("unet_forward_batch: sample points go with one image or a pair, 22 floats (pose, camera) "
                                 "and 6 ints (ndist, pad, x0, y0, full_w, full_h)")
-        _f32c(sample_p3d, "sample_p3d")
-        _lib.require_gpu(sample_p3d, "sample_p3d")
-        if sample_p3d.dim() != 2 or sample_p3d.shape[1] != 3 or sample_p3d.device != images[0].device:
-            raise _lib.PxtError("unet_forward_batch: sample_p3d is [N, 3] on the images' device")
+        _dense("unet_forward_batch", sample_p3d, "sample_p3d", shape=(None, 3))
+        _one_device("unet_forward_batch", images[0], [(sample_p3d, "sample_p3d")])
         points = _lib.UnetSamplePoints()
         points.p3d, points.n_points = sample_p3d.data_ptr(), int(sample_p3d.shape[0])
         points.T[:] = [float(x) for x in sample_pose_camera[:12]]
@@ -686,7 +708,7 @@ def _unet_forward_batch(ctx, images, masks, normalize, outs, workspace, sample_p
     if workspace.numel() * workspace.element_size() < need:
         raise _lib.PxtError(f"unet_forward_batch: workspace holds {workspace.numel()} bytes, {need} needed")
     for o in outs:
-        _f32c(o, "out map")
+        _dense("unet_forward_batch", o, "out map")
     imgs = (C.c_void_p * n)(*[im.data_ptr() for im in images])
     is_u8 = (C.c_int32 * n)(*[int(im.dtype == torch.uint8) for im in images])
     mks = (C.c_void_p * n)(*[_lib.dptr(m) for m in masks])
@@ -734,22 +756,16 @@ def _view(view: Sequence[float], width, height, spp, mode) -> "_lib.NgpView":
     return v
 
 
-def _check_frame(t: torch.Tensor, width, height, what):
-    _f32c(t, what)
-    if tuple(t.shape) != (height, width, 4):
-        raise _lib.PxtError(f"{what} must be [{height}, {width}, 4] (got {tuple(t.shape)})")
-
-
 def _ngp_render(ctx, view, width, height, spp, mode, out, stats):
-    _check_frame(out, width, height, "out")
+    _dense("ngp_render", out, "out", shape=(height, width, 4))
     v = _view(view, width, height, spp, mode)
     _lib.check(_lib.lib().pxt_ngp_render(ctx, C.byref(v), out.data_ptr(), _lib.dptr(stats), _stream(out)),
                "pxt_ngp_render")
 
 
 def _ngp_render_both(ctx, view, width, height, spp, rgba, depth, stats):
-    _check_frame(rgba, width, height, "rgba")
-    _check_frame(depth, width, height, "depth")
+    _dense("ngp_render_both", rgba, "rgba", shape=(height, width, 4))
+    _dense("ngp_render_both", depth, "depth", shape=(height, width, 4))
     v = _view(view, width, height, spp, 0)
     _lib.check(_lib.lib().pxt_ngp_render_both(ctx, C.byref(v), rgba.data_ptr(), depth.data_ptr(), _lib.dptr(stats),
                                               _stream(rgba)), "pxt_ngp_render_both")
@@ -760,9 +776,9 @@ def _ngp_render_both_from_pose(ctx, view, pose_record, conv, width, height, spp,
     the record pxt_lm_refine writes), so that the render can be enqueued behind the LM launch.  `cam_out`: pinned
     float32 [>= 13], receives the camera + a completion word.  `depth` given: Shade + Depth in one march (`mode`
     ignored); None: one render in `mode` (0 Shade, 1 Depth) into `rgba`."""
-    _check_frame(rgba, width, height, "rgba")
+    _dense("ngp_render_both_from_pose", rgba, "rgba", shape=(height, width, 4))
     if depth is not None:
-        _check_frame(depth, width, height, "depth")
+        _dense("ngp_render_both_from_pose", depth, "depth", shape=(height, width, 4))
     for t, n, what in ((pose_record, 12, "pose_record"), (cam_out, 13, "cam_out")):
         if t.dtype != torch.float32 or t.numel() < n or t.is_cuda or not t.is_pinned():
             raise _lib.PxtError(f"{what} must be a pinned host float32 tensor of >= {n} elements")
@@ -785,7 +801,7 @@ def _ngp_render_frame(ctx, view, width, height, spp, mode, camera_from_slot, rgb
         raise _lib.PxtError("ngp_render_frame: mode is 0 (Shade), 1 (Depth) or 2 (both)")
     for t, what in ((rgba, "rgba"), (depth, "depth")):
         if t is not None:
-            _check_frame(t, width, height, what)
+            _dense("ngp_render_frame", t, what, shape=(height, width, 4))
     if rgb_u8 is not None and (rgb_u8.dtype != torch.uint8 or tuple(rgb_u8.shape) != (height, width, 3)
                                or not rgb_u8.is_contiguous() or not rgb_u8.is_cuda):
         raise _lib.PxtError("ngp_render_frame: rgb_u8 is a contiguous device uint8 [H, W, 3]")
@@ -837,7 +853,7 @@ def _ngp_render_frame_batch(ctxs, views, sizes, spp, modes, camera_from_slot, rg
             nz, i_nz = depth_nz[i_nz], i_nz + 1
             if depth_float is not None:
                 df = depth_float[i_nz - 1]
-                _check_frame(df, w, h, "depth_float")
+                _dense("ngp_render_frame_batch", df, "depth_float", shape=(h, w, 4))
                 if df.device != workspace.device:
                     raise _lib.PxtError("ngp_render_frame_batch: depth_float lives on the workspace's device")
         if u8 is not None and (u8.dtype != torch.uint8 or tuple(u8.shape) != (h, w, 3) or not u8.is_contiguous()
@@ -882,7 +898,7 @@ def _depth_mask_plane(depth_nz, n_erode, n_dilate, mask):
 
 
 def _depth_mask(depth_rgba, n_erode, n_dilate, mask, scratch):
-    _f32c(depth_rgba, "depth_rgba")
+    _dense("depth_mask", depth_rgba, "depth_rgba")
     H, W = int(depth_rgba.shape[0]), int(depth_rgba.shape[1])
     _mask_out(mask, H, W, depth_rgba, "depth_mask")
     if scratch.numel() < 2 * H * W:
@@ -892,7 +908,7 @@ def _depth_mask(depth_rgba, n_erode, n_dilate, mask, scratch):
 
 
 def _rgba_to_u8(rgba, alpha_thresh, out):
-    _f32c(rgba, "rgba")
+    _dense("rgba_to_u8", rgba, "rgba")
     H, W = int(rgba.shape[0]), int(rgba.shape[1])
     if out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3):
         raise _lib.PxtError("rgba_to_u8: out is uint8 [H, W, 3]")
@@ -901,8 +917,8 @@ def _rgba_to_u8(rgba, alpha_thresh, out):
 
 
 def _resize_linear(src, dst):
-    _f32c(src, "src")
-    _f32c(dst, "dst")
+    _dense("resize_linear", src, "src")
+    _dense("resize_linear", dst, "dst")
     H, W, Cc = (int(s) for s in src.shape)
     Ho, Wo, Co = (int(s) for s in dst.shape)
     if Co != Cc:
@@ -923,276 +939,174 @@ def _resize_activity(mask, image_u8, H, W, active):
 
 
 def _points_from_depth(depth, xform, focal, depth_scale, min_alpha, erode, n_max, p3d, slot_valid, record, workspace):
+    op = "points_from_depth"
     L = _lib.lib()
-    _f32c(depth, "depth")
-    _f32c(p3d, "p3d")
-    if depth.dim() != 3 or int(depth.shape[2]) != 4:
-        raise _lib.PxtError(f"points_from_depth: depth is [H, W, 4] (got {tuple(depth.shape)})")
+    _dense(op, depth, "depth", shape=(None, None, 4))
     H, W, n_max = int(depth.shape[0]), int(depth.shape[1]), int(n_max)
     if len(xform) != 12:
-        raise _lib.PxtError("points_from_depth: xform holds 12 floats ([M | b], 3 x 4 row-major)")
+        raise _lib.PxtError(f"{op}: xform holds 12 floats ([M | b], 3 x 4 row-major)")
     if int(erode) not in (0, 1, 2) or n_max < 1:
-        raise _lib.PxtError("points_from_depth: erode is 0, 1 or 2 and n_max >= 1")
-    if tuple(p3d.shape) != (n_max, 3):
-        raise _lib.PxtError(f"points_from_depth: p3d is {tuple(p3d.shape)}, expected {(n_max, 3)}")
-    if slot_valid.dtype != torch.uint8 or slot_valid.numel() != n_max or not slot_valid.is_contiguous():
-        raise _lib.PxtError("points_from_depth: slot_valid is a contiguous uint8 [n_max]")
-    if record.dtype != torch.int32 or record.numel() < 4 or not record.is_contiguous():
-        raise _lib.PxtError("points_from_depth: record holds 4 contiguous int32 values")
-    need = int(L.pxt_points_from_depth_workspace_bytes(W, H))
-    if need <= 0:
-        raise _lib.PxtError(f"points_from_depth: a {W} x {H} image is not supported")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"points_from_depth: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of the depth image's device (a host pointer there is a memory fault,
-    # not an error); the record may also be pinned host memory
-    for t, name in ((depth, "depth"), (p3d, "p3d"), (slot_valid, "slot_valid"), (workspace, "workspace")):
-        _lib.require_gpu(t, name)
-        if t.device != depth.device:
-            raise _lib.PxtError(f"points_from_depth: {name} is on {t.device}, the depth image on {depth.device}")
-    if not ((record.is_cuda and record.device == depth.device) or record.is_pinned()):
-        raise _lib.PxtError("points_from_depth: record must be memory of the depth image's device or pinned host memory")
+        raise _lib.PxtError(f"{op}: erode is 0, 1 or 2 and n_max >= 1")
+    _dense(op, p3d, "p3d", shape=(n_max, 3))
+    _point_mask(op, slot_valid, n_max, "slot_valid")  # (one byte per slot in any shape; the schema rules None out)
+    rec = _record(op, record, "record", torch.int32, 4, depth.device)
+    _workspace(op, workspace, int(L.pxt_points_from_depth_workspace_bytes(W, H)), f"a {W} x {H} image is not supported")
+    _one_device(op, depth, [(depth, "depth"), (p3d, "p3d"), (slot_valid, "slot_valid"), (workspace, "workspace")])
     xf = (C.c_float * 12)(*[float(x) for x in xform])
     _lib.check(L.pxt_points_from_depth(depth.data_ptr(), W, H, xf, float(focal), float(depth_scale), float(min_alpha),
-                                       int(erode), n_max, p3d.data_ptr(), slot_valid.data_ptr(), record.data_ptr(),
+                                       int(erode), n_max, p3d.data_ptr(), slot_valid.data_ptr(), rec,
                                        workspace.data_ptr(), _stream(depth)), "pxt_points_from_depth")
 
 
 def _points_from_depth_views(depth, views, min_alpha, erode, n_max, p3d, slot_valid, record, workspace):
+    op = "points_from_depth_views"
     L = _lib.lib()
-    what = "points_from_depth_views"
     K, n_max = len(depth), int(n_max)
     if not (1 <= K <= _lib.PXT_POINTS_MAX_VIEWS):
-        raise _lib.PxtError(f"{what}: 1..{_lib.PXT_POINTS_MAX_VIEWS} depth planes (got {K})")
+        raise _lib.PxtError(f"{op}: 1..{_lib.PXT_POINTS_MAX_VIEWS} depth planes (got {K})")
     sizes = []
     for k, d in enumerate(depth):
-        _f32c(d, f"depth[{k}]")
-        if d.dim() != 3 or int(d.shape[2]) != 4:
-            raise _lib.PxtError(f"{what}: depth[{k}] is [H, W, 4] (got {tuple(d.shape)})")
+        _dense(op, d, f"depth[{k}]", shape=(None, None, 4))
         sizes += [int(d.shape[1]), int(d.shape[0])]
-    _f32c(p3d, "p3d")
     if len(views) != K * _lib.PXT_MESH_VIEW:
-        raise _lib.PxtError(f"{what}: views holds {_lib.PXT_MESH_VIEW} floats per plane ({K * _lib.PXT_MESH_VIEW}; got "
+        raise _lib.PxtError(f"{op}: views holds {_lib.PXT_MESH_VIEW} floats per plane ({K * _lib.PXT_MESH_VIEW}; got "
                             f"{len(views)})")
     if int(erode) not in (0, 1, 2) or n_max < 1:
-        raise _lib.PxtError(f"{what}: erode is 0, 1 or 2 and n_max >= 1")
-    if tuple(p3d.shape) != (K, n_max, 3):
-        raise _lib.PxtError(f"{what}: p3d is {tuple(p3d.shape)}, expected {(K, n_max, 3)}")
-    if slot_valid.dtype != torch.uint8 or tuple(slot_valid.shape) != (K, n_max) or not slot_valid.is_contiguous():
-        raise _lib.PxtError(f"{what}: slot_valid is a contiguous uint8 [{K}, n_max]")
-    if record.dtype != torch.int32 or tuple(record.shape) != (K, 4) or not record.is_contiguous():
-        raise _lib.PxtError(f"{what}: record is a contiguous int32 [{K}, 4]")
+        raise _lib.PxtError(f"{op}: erode is 0, 1 or 2 and n_max >= 1")
+    _dense(op, p3d, "p3d", shape=(K, n_max, 3))
+    _dense(op, slot_valid, "slot_valid", torch.uint8, (K, n_max))
+    rec = _record(op, record, "record", torch.int32, 0, depth[0].device, shape=(K, 4))
     size_arr = (C.c_int32 * (2 * K))(*sizes)
-    need = int(L.pxt_points_from_depth_views_workspace_bytes(K, size_arr))
-    if need <= 0:
-        raise _lib.PxtError(f"{what}: planes of {list(zip(sizes[0::2], sizes[1::2]))} are not supported")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of the depth planes' device (a host pointer there is a memory fault,
-    # not an error); the record may also be pinned host memory
-    device = depth[0].device
-    named = [(d, f"depth[{k}]") for k, d in enumerate(depth)] + [(p3d, "p3d"), (slot_valid, "slot_valid"),
-                                                                  (workspace, "workspace")]
-    for t, name in named:
-        _lib.require_gpu(t, name)
-        if t.device != device:
-            raise _lib.PxtError(f"{what}: {name} is on {t.device}, depth[0] on {device}")
-    if not ((record.is_cuda and record.device == device) or record.is_pinned()):
-        raise _lib.PxtError(f"{what}: record must be memory of the depth planes' device or pinned host memory")
+    _workspace(op, workspace, int(L.pxt_points_from_depth_views_workspace_bytes(K, size_arr)),
+               f"planes of {list(zip(sizes[0::2], sizes[1::2]))} are not supported")
+    _one_device(op, depth[0], [(d, f"depth[{k}]") for k, d in enumerate(depth)]
+                + [(p3d, "p3d"), (slot_valid, "slot_valid"), (workspace, "workspace")])
     planes = (C.c_void_p * K)(*[d.data_ptr() for d in depth])
     vf = (C.c_float * len(views))(*[float(x) for x in views])
     _lib.check(L.pxt_points_from_depth_views(planes, size_arr, vf, K, float(min_alpha), int(erode), n_max, p3d.data_ptr(),
-                                             slot_valid.data_ptr(), record.data_ptr(), workspace.data_ptr(),
-                                             _stream(depth[0])), "pxt_points_from_depth_views")
+                                             slot_valid.data_ptr(), rec, workspace.data_ptr(), _stream(depth[0])),
+               "pxt_points_from_depth_views")
 
 
 def _pose_errors(vertices, rel_poses, want_adds, records, workspace):
+    op = "pose_errors"
     L = _lib.lib()
-    _f32c(vertices, "vertices")
-    _f32c(rel_poses, "rel_poses")
-    _f32c(records, "records")
-    if vertices.dim() != 2 or int(vertices.shape[1]) != 3 or rel_poses.dim() != 2 or int(rel_poses.shape[1]) != 12:
-        raise _lib.PxtError(f"pose_errors: vertices {tuple(vertices.shape)} / rel_poses {tuple(rel_poses.shape)}, expected "
-                            "[V, 3] / [F, 12]")
-    V, F = int(vertices.shape[0]), int(rel_poses.shape[0])
-    if tuple(records.shape) != (F, _lib.PXT_POSE_ERR_RECORD):
-        raise _lib.PxtError(f"pose_errors: records is {tuple(records.shape)}, expected {(F, _lib.PXT_POSE_ERR_RECORD)}")
-    need = int(L.pxt_pose_errors_workspace_bytes(F, V))
-    if need <= 0:
-        raise _lib.PxtError(f"pose_errors: {F} frames x {V} vertices is not supported (1..65535 frames, 1..2^20 vertices)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"pose_errors: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    for t, name in ((vertices, "vertices"), (rel_poses, "rel_poses"), (records, "records"), (workspace, "workspace")):
-        _lib.require_gpu(t, name)
-        if t.device != vertices.device:
-            raise _lib.PxtError(f"pose_errors: {name} is on {t.device}, the vertices on {vertices.device}")
+    V = int(_dense(op, vertices, "vertices", shape=(None, 3)).shape[0])
+    F = int(_dense(op, rel_poses, "rel_poses", shape=(None, 12)).shape[0])
+    _dense(op, records, "records", shape=(F, _lib.PXT_POSE_ERR_RECORD))
+    _workspace(op, workspace, int(L.pxt_pose_errors_workspace_bytes(F, V)),
+               f"{F} frames x {V} vertices is not supported (1..65535 frames, 1..2^20 vertices)")
+    _one_device(op, vertices, [(vertices, "vertices"), (rel_poses, "rel_poses"), (records, "records"),
+                               (workspace, "workspace")])
     _lib.check(L.pxt_pose_errors(vertices.data_ptr(), V, rel_poses.data_ptr(), F, int(bool(want_adds)), records.data_ptr(),
                                  workspace.data_ptr(), _stream(vertices)), "pxt_pose_errors")
 
 
+def _depth_pairs(op, depth_est, depth_gt):
+    """The P pairs of Depth renders depth_agreement and sensor_vsd compare -> (P, H, W)."""
+    _dense(op, depth_est, "depth_est", shape=(None, None, None, 4))
+    _dense(op, depth_gt, "depth_gt", shape=tuple(depth_est.shape))
+    return (int(x) for x in depth_est.shape[:3])
+
+
 def _depth_agreement(depth_est, depth_gt, min_alpha, tq, records, workspace):
+    op = "depth_agreement"
     L = _lib.lib()
-    _f32c(depth_est, "depth_est")
-    _f32c(depth_gt, "depth_gt")
-    if depth_est.dim() != 4 or int(depth_est.shape[3]) != 4 or tuple(depth_gt.shape) != tuple(depth_est.shape):
-        raise _lib.PxtError(f"depth_agreement: depth_est {tuple(depth_est.shape)} / depth_gt {tuple(depth_gt.shape)}, "
-                            "expected two [P, H, W, 4] tensors of one shape")
-    P, H, W = (int(x) for x in depth_est.shape[:3])
+    P, H, W = _depth_pairs(op, depth_est, depth_gt)
     if not (1 <= len(tq) <= _lib.PXT_DEPTH_AGREE_MAX_TAUS):
-        raise _lib.PxtError(f"depth_agreement: {len(tq)} thresholds (1..{_lib.PXT_DEPTH_AGREE_MAX_TAUS})")
-    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_DEPTH_AGREE_RECORD):
-        raise _lib.PxtError(f"depth_agreement: records is a contiguous int32 [{P}, {_lib.PXT_DEPTH_AGREE_RECORD}] tensor "
-                            f"(got {tuple(records.shape)}, {records.dtype})")
-    need = int(L.pxt_depth_agreement_workspace_bytes(P, W, H))
-    if need <= 0:
-        raise _lib.PxtError(f"depth_agreement: {P} pairs of {W} x {H} are not supported (1..65535 pairs, 1..2^28 pixels)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"depth_agreement: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    for t, name in ((depth_est, "depth_est"), (depth_gt, "depth_gt"), (records, "records"), (workspace, "workspace")):
-        _lib.require_gpu(t, name)
-        if t.device != depth_est.device:
-            raise _lib.PxtError(f"depth_agreement: {name} is on {t.device}, depth_est on {depth_est.device}")
+        raise _lib.PxtError(f"{op}: {len(tq)} thresholds (1..{_lib.PXT_DEPTH_AGREE_MAX_TAUS})")
+    _dense(op, records, "records", torch.int32, (P, _lib.PXT_DEPTH_AGREE_RECORD))
+    _workspace(op, workspace, int(L.pxt_depth_agreement_workspace_bytes(P, W, H)),
+               f"{P} pairs of {W} x {H} are not supported (1..65535 pairs, 1..2^28 pixels)")
+    _one_device(op, depth_est, [(depth_est, "depth_est"), (depth_gt, "depth_gt"), (records, "records"),
+                                (workspace, "workspace")])
     tqs = (C.c_float * len(tq))(*[float(x) for x in tq])
     _lib.check(L.pxt_depth_agreement(depth_est.data_ptr(), depth_gt.data_ptr(), P, W, H, float(min_alpha), tqs, len(tq),
                                      records.data_ptr(), workspace.data_ptr(), _stream(depth_est)), "pxt_depth_agreement")
 
 
 def _symmetric_pose_errors(vertices, syms, frames, records, workspace):
+    op = "symmetric_pose_errors"
     L = _lib.lib()
-    _f32c(vertices, "vertices")
-    _f32c(syms, "syms")
-    _f32c(frames, "frames")
-    _f32c(records, "records")
-    if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or syms.dim() != 2 or int(syms.shape[1]) != 12
-            or frames.dim() != 2 or int(frames.shape[1]) != _lib.PXT_SYM_ERR_FRAME):
-        raise _lib.PxtError(f"symmetric_pose_errors: vertices {tuple(vertices.shape)} / syms {tuple(syms.shape)} / frames "
-                            f"{tuple(frames.shape)}, expected [V, 3] / [S, 12] / [F, {_lib.PXT_SYM_ERR_FRAME}]")
-    V, S, F = int(vertices.shape[0]), int(syms.shape[0]), int(frames.shape[0])
-    if tuple(records.shape) != (F, _lib.PXT_SYM_ERR_RECORD):
-        raise _lib.PxtError(f"symmetric_pose_errors: records is {tuple(records.shape)}, expected "
-                            f"{(F, _lib.PXT_SYM_ERR_RECORD)}")
-    need = int(L.pxt_symmetric_pose_errors_workspace_bytes(F, S, V))
-    if need <= 0:
-        raise _lib.PxtError(f"symmetric_pose_errors: {F} frames x {S} symmetries x {V} vertices is not supported "
-                            f"(1..65535 frames, 1..{_lib.PXT_SYM_ERR_MAX_SYMS} symmetries, 1..2^20 vertices)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"symmetric_pose_errors: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    for t, name in ((vertices, "vertices"), (syms, "syms"), (frames, "frames"), (records, "records"),
-                    (workspace, "workspace")):
-        _lib.require_gpu(t, name)
-        if t.device != vertices.device:
-            raise _lib.PxtError(f"symmetric_pose_errors: {name} is on {t.device}, the vertices on {vertices.device}")
+    V = int(_dense(op, vertices, "vertices", shape=(None, 3)).shape[0])
+    S = int(_dense(op, syms, "syms", shape=(None, 12)).shape[0])
+    F = int(_dense(op, frames, "frames", shape=(None, _lib.PXT_SYM_ERR_FRAME)).shape[0])
+    _dense(op, records, "records", shape=(F, _lib.PXT_SYM_ERR_RECORD))
+    _workspace(op, workspace, int(L.pxt_symmetric_pose_errors_workspace_bytes(F, S, V)),
+               f"{F} frames x {S} symmetries x {V} vertices is not supported (1..65535 frames, "
+               f"1..{_lib.PXT_SYM_ERR_MAX_SYMS} symmetries, 1..2^20 vertices)")
+    _one_device(op, vertices, [(vertices, "vertices"), (syms, "syms"), (frames, "frames"), (records, "records"),
+                               (workspace, "workspace")])
     _lib.check(L.pxt_symmetric_pose_errors(vertices.data_ptr(), V, syms.data_ptr(), S, frames.data_ptr(), F,
                                            records.data_ptr(), workspace.data_ptr(), _stream(vertices)),
                "pxt_symmetric_pose_errors")
 
 
 def _sensor_vsd(depth_est, depth_gt, sensor, ray, shift, min_alpha, sensor_q, delta_q, tq, records, workspace):
+    op = "sensor_vsd"
     L = _lib.lib()
-    _f32c(depth_est, "depth_est")
-    _f32c(depth_gt, "depth_gt")
-    if depth_est.dim() != 4 or int(depth_est.shape[3]) != 4 or tuple(depth_gt.shape) != tuple(depth_est.shape):
-        raise _lib.PxtError(f"sensor_vsd: depth_est {tuple(depth_est.shape)} / depth_gt {tuple(depth_gt.shape)}, "
-                            "expected two [P, H, W, 4] tensors of one shape")
-    P, H, W = (int(x) for x in depth_est.shape[:3])
-    if sensor.dtype not in (torch.uint16, torch.int16) or not sensor.is_contiguous() or tuple(sensor.shape) != (P, H, W):
-        raise _lib.PxtError(f"sensor_vsd: sensor is a contiguous uint16 (or int16) [{P}, {H}, {W}] tensor "
-                            f"(got {tuple(sensor.shape)}, {sensor.dtype})")
+    P, H, W = _depth_pairs(op, depth_est, depth_gt)
+    _sensor(op, sensor, "sensor", (P, H, W))
     if ray is not None:
-        _f32c(ray, "ray")
-        if tuple(ray.shape) != (H, W):
-            raise _lib.PxtError(f"sensor_vsd: ray is {tuple(ray.shape)}, expected {(H, W)}")
-    if len(shift) != 2 or any(abs(int(v)) > 32767 for v in shift):
-        raise _lib.PxtError(f"sensor_vsd: shift is (shift_x, shift_y), each within +-32767 (got {list(shift)})")
+        _dense(op, ray, "ray", shape=(H, W))
+    _shifts(op, shift)
     if not (1 <= len(tq) <= _lib.PXT_SENSOR_VSD_MAX_TAUS):
-        raise _lib.PxtError(f"sensor_vsd: {len(tq)} thresholds (1..{_lib.PXT_SENSOR_VSD_MAX_TAUS})")
-    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_SENSOR_VSD_RECORD):
-        raise _lib.PxtError(f"sensor_vsd: records is a contiguous int32 [{P}, {_lib.PXT_SENSOR_VSD_RECORD}] tensor "
-                            f"(got {tuple(records.shape)}, {records.dtype})")
-    need = int(L.pxt_sensor_vsd_workspace_bytes(P, W, H))
-    if need <= 0:
-        raise _lib.PxtError(f"sensor_vsd: {P} pairs of {W} x {H} are not supported (1..65535 pairs, 1..2^28 pixels)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"sensor_vsd: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    named = [(depth_est, "depth_est"), (depth_gt, "depth_gt"), (sensor, "sensor"), (records, "records"),
-             (workspace, "workspace")] + ([(ray, "ray")] if ray is not None else [])
-    for t, name in named:
-        _lib.require_gpu(t, name)
-        if t.device != depth_est.device:
-            raise _lib.PxtError(f"sensor_vsd: {name} is on {t.device}, depth_est on {depth_est.device}")
+        raise _lib.PxtError(f"{op}: {len(tq)} thresholds (1..{_lib.PXT_SENSOR_VSD_MAX_TAUS})")
+    _dense(op, records, "records", torch.int32, (P, _lib.PXT_SENSOR_VSD_RECORD))
+    _workspace(op, workspace, int(L.pxt_sensor_vsd_workspace_bytes(P, W, H)),
+               f"{P} pairs of {W} x {H} are not supported (1..65535 pairs, 1..2^28 pixels)")
+    _one_device(op, depth_est, [(depth_est, "depth_est"), (depth_gt, "depth_gt"), (sensor, "sensor"), (records, "records"),
+                                (workspace, "workspace"), (ray, "ray")])
     tqs = (C.c_float * len(tq))(*[float(x) for x in tq])
-    _lib.check(L.pxt_sensor_vsd(depth_est.data_ptr(), depth_gt.data_ptr(), sensor.data_ptr(),
-                                None if ray is None else ray.data_ptr(), P, W, H, int(shift[0]), int(shift[1]),
-                                float(min_alpha), float(sensor_q), float(delta_q), tqs, len(tq), records.data_ptr(),
-                                workspace.data_ptr(), _stream(depth_est)), "pxt_sensor_vsd")
+    _lib.check(L.pxt_sensor_vsd(depth_est.data_ptr(), depth_gt.data_ptr(), sensor.data_ptr(), _lib.dptr(ray), P, W, H,
+                                int(shift[0]), int(shift[1]), float(min_alpha), float(sensor_q), float(delta_q), tqs,
+                                len(tq), records.data_ptr(), workspace.data_ptr(), _stream(depth_est)), "pxt_sensor_vsd")
 
 
 def _depth_refine(p3d, point_masks, sensors, sensor_scales, cameras, ndist, poses, pose_is_lm_record, priors, num_iters,
                   pad, loss, loss_alpha, loss_scale, lambdas, max_residual, max_edge, grad_stop, dt_stop, dR_stop,
                   min_valid, records, logs, codes, workspace):
+    op = "depth_refine"
     L = _lib.lib()
     K = len(p3d)
     if not (1 <= K <= _lib.PXT_DEPTH_MAX_PROBLEMS):
-        raise _lib.PxtError(f"depth_refine: {K} problems (1..{_lib.PXT_DEPTH_MAX_PROBLEMS})")
+        raise _lib.PxtError(f"{op}: {K} problems (1..{_lib.PXT_DEPTH_MAX_PROBLEMS})")
     if any(len(x) != K for x in (point_masks, sensors, sensor_scales, ndist, poses, records, logs, codes)) \
             or len(cameras) != 10 * K or len(priors) != 21 * K or len(lambdas) != 6:
-        raise _lib.PxtError("depth_refine: per problem one mask slot, sensor image, scale, ndist, pose, record, log slot, "
+        raise _lib.PxtError(f"{op}: per problem one mask slot, sensor image, scale, ndist, pose, record, log slot, "
                             "codes slot, 10 camera floats and 21 prior floats; 6 lambdas")
     if not (0 <= int(num_iters) <= _lib.PXT_DEPTH_MAX_ITERS):
-        raise _lib.PxtError(f"depth_refine: num_iters {num_iters} (0..{_lib.PXT_DEPTH_MAX_ITERS})")
-    _lib.require_gpu(workspace, "workspace")
+        raise _lib.PxtError(f"{op}: num_iters {num_iters} (0..{_lib.PXT_DEPTH_MAX_ITERS})")
+    _one_device(op, workspace, [(workspace, "workspace")])
     dev = workspace.device
     rows = int(num_iters)
     probs = (_lib.DepthProblem * K)()
     for k in range(K):
-        pts = _f32c(p3d[k], "p3d")
-        n = int(pts.shape[0])
-        if tuple(pts.shape) != (n, 3) or not (1 <= n <= _lib.PXT_DEPTH_MAX_POINTS):
-            raise _lib.PxtError(f"depth_refine: problem {k}: p3d {tuple(pts.shape)}, expected [N, 3] with 1 <= N <= "
-                                f"{_lib.PXT_DEPTH_MAX_POINTS}")
-        mk, sen, lg, cd = point_masks[k], sensors[k], logs[k], codes[k]
-        if mk is not None and (mk.dtype != torch.uint8 or not mk.is_contiguous() or mk.numel() != n):
-            raise _lib.PxtError("depth_refine: point masks are contiguous uint8 [n_points]")
-        if sen.dtype not in (torch.uint16, torch.int16) or not sen.is_contiguous() or sen.dim() != 2 \
-                or min(int(x) for x in sen.shape) < 4:
-            raise _lib.PxtError(f"depth_refine: sensor {k} is a contiguous uint16 (or int16) [H, W] tensor, H, W >= 4 "
-                                f"(got {tuple(sen.shape)}, {sen.dtype})")
-        if lg is not None and (lg.dtype != torch.float32 or not lg.is_contiguous()
-                               or tuple(lg.shape) != (rows, _lib.PXT_DEPTH_LOG_STRIDE)):
-            raise _lib.PxtError(f"depth_refine: log {k} is a contiguous float32 [{rows}, {_lib.PXT_DEPTH_LOG_STRIDE}] tensor")
-        if cd is not None and (cd.dtype != torch.uint8 or not cd.is_contiguous() or tuple(cd.shape) != (rows + 1, n)):
-            raise _lib.PxtError(f"depth_refine: codes {k} is a contiguous uint8 [{rows + 1}, {n}] tensor")
-        # what the kernel dereferences must be device memory of one device (a host pointer there is a memory fault,
-        # not an error); the pose, the record and the log may also be pinned host memory
-        for t, name in ((pts, "p3d"), (mk, "point_mask"), (sen, "sensor"), (cd, "codes")):
-            if t is None:
-                continue
-            _lib.require_gpu(t, name)
-            if t.device != dev:
-                raise _lib.PxtError(f"depth_refine: {name} of problem {k} is on {t.device}, the workspace on {dev}")
-        need = 16 if pose_is_lm_record else 12
-        for t, name, count in ((poses[k], "pose", need), (records[k], "record", _lib.PXT_DEPTH_RECORD), (lg, "log", 0)):
-            if t is None:
-                continue
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < count \
-                    or not ((t.is_cuda and t.device == dev) or t.is_pinned()):
-                raise _lib.PxtError(f"depth_refine: {name} {k} needs {count} contiguous float32 values in device or pinned "
-                                    "memory")
+        where, mk, sen, lg, cd = f" of problem {k}", point_masks[k], sensors[k], logs[k], codes[k]
+        n = int(_dense(op, p3d[k], "p3d" + where, shape=(None, 3)).shape[0])
+        if not (1 <= n <= _lib.PXT_DEPTH_MAX_POINTS):
+            raise _lib.PxtError(f"{op}: problem {k}: {n} points (1..{_lib.PXT_DEPTH_MAX_POINTS})")
+        _point_mask(op, mk, n, "point_mask" + where)
+        if min(int(x) for x in _sensor(op, sen, "sensor" + where, (None, None)).shape) < 4:
+            raise _lib.PxtError(f"{op}: sensor {k} is {tuple(sen.shape)}; H, W >= 4")
+        if cd is not None:
+            _dense(op, cd, "codes" + where, torch.uint8, (rows + 1, n))
+        # (the pose, the record and the log may also be pinned host memory)
+        _one_device(op, workspace, [(p3d[k], "p3d"), (mk, "point_mask"), (sen, "sensor"), (cd, "codes")], where)
         q = probs[k]
-        q.p3d, q.point_mask, q.n_points = pts.data_ptr(), _lib.dptr(mk), n
+        q.pose = _record(op, poses[k], f"pose {k}", torch.float32, 16 if pose_is_lm_record else 12, dev)
+        q.out = _record(op, records[k], f"record {k}", torch.float32, _lib.PXT_DEPTH_RECORD, dev)
+        q.log = None if lg is None else _record(op, lg, f"log {k}", torch.float32, 0, dev,
+                                                shape=(rows, _lib.PXT_DEPTH_LOG_STRIDE))
+        q.p3d, q.point_mask, q.n_points = p3d[k].data_ptr(), _lib.dptr(mk), n
         q.sensor, q.height, q.width = sen.data_ptr(), int(sen.shape[0]), int(sen.shape[1])
         q.sensor_scale = float(sensor_scales[k])
         q.cam[:] = [float(x) for x in cameras[10 * k:10 * k + 10]]
         q.ndist = int(ndist[k])
-        q.pose, q.pose_is_lm_record = poses[k].data_ptr(), int(bool(pose_is_lm_record))
+        q.pose_is_lm_record = int(bool(pose_is_lm_record))
         q.prior[:] = [float(x) for x in priors[21 * k:21 * k + 21]]
-        q.out, q.log, q.codes = records[k].data_ptr(), _lib.dptr(lg), _lib.dptr(cd)
-    if workspace.numel() * workspace.element_size() < int(L.pxt_depth_refine_workspace_bytes(K)):
-        raise _lib.PxtError("depth_refine: workspace smaller than pxt_depth_refine_workspace_bytes(K)")
+        q.codes = _lib.dptr(cd)
+    _workspace(op, workspace, int(L.pxt_depth_refine_workspace_bytes(K)), f"{K} problems are not supported", any_dtype="workspace")
     conf = _lib.DepthConf()
     conf.num_iters, conf.pad, conf.loss = int(num_iters), int(pad), int(loss)
     conf.loss_alpha, conf.loss_scale = float(loss_alpha), float(loss_scale)
@@ -1202,87 +1116,52 @@ def _depth_refine(p3d, point_masks, sensors, sensor_scales, cameras, ndist, pose
     _lib.check(L.pxt_depth_refine(probs, K, C.byref(conf), workspace.data_ptr(), _stream(workspace)), "pxt_depth_refine")
 
 
-def _occlusion_record(record, what):
-    if record.dtype != torch.int32 or not record.is_contiguous() or record.numel() < _lib.PXT_OCCLUSION_RECORD \
-            or not (record.is_cuda or record.is_pinned()):
-        raise _lib.PxtError(f"{what}: record needs {_lib.PXT_OCCLUSION_RECORD} contiguous int32 words in device or pinned "
-                            "memory")
+def _occlusion_pair(op, where, depth, sensor, mask_in, mask, occluder):
+    """One image pair of the occlusion ops: the Depth render [H, W, 4], the sensor image and the plain mask of its
+    size, and the two planes the kernels write -> (H, W)."""
+    _dense(op, depth, "depth" + where, shape=(None, None, 4))
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    _sensor(op, sensor, "sensor" + where, (H, W))
+    _dense(op, mask_in, "mask_in" + where, torch.uint8, (H, W))
+    _mask_out(mask, H, W, depth, op)
+    _mask_out(occluder, H, W, depth, op)
+    return H, W
 
 
 def _occlusion_mask(depth, sensor, mask_in, shift, min_alpha, sensor_q, delta_q, radii, mask, occluder, record, workspace):
+    op = "occlusion_mask"
     L = _lib.lib()
-    _f32c(depth, "depth")
-    if depth.dim() != 3 or int(depth.shape[2]) != 4:
-        raise _lib.PxtError(f"occlusion_mask: depth is {tuple(depth.shape)}, expected [H, W, 4]")
-    H, W = int(depth.shape[0]), int(depth.shape[1])
-    if sensor.dtype not in (torch.uint16, torch.int16) or not sensor.is_contiguous() or tuple(sensor.shape) != (H, W):
-        raise _lib.PxtError(f"occlusion_mask: sensor is a contiguous uint16 (or int16) [{H}, {W}] tensor "
-                            f"(got {tuple(sensor.shape)}, {sensor.dtype})")
-    if mask_in.dtype != torch.uint8 or not mask_in.is_contiguous() or tuple(mask_in.shape) != (H, W):
-        raise _lib.PxtError(f"occlusion_mask: mask_in is a contiguous uint8 [{H}, {W}] tensor")
-    _mask_out(mask, H, W, depth, "occlusion_mask")
-    _mask_out(occluder, H, W, depth, "occlusion_mask")
+    H, W = _occlusion_pair(op, "", depth, sensor, mask_in, mask, occluder)
     if mask.data_ptr() == occluder.data_ptr():
-        raise _lib.PxtError("occlusion_mask: mask and occluder are two tensors")
-    if len(shift) != 2 or any(abs(int(v)) > 32767 for v in shift):
-        raise _lib.PxtError(f"occlusion_mask: shift is (shift_x, shift_y), each within +-32767 (got {list(shift)})")
-    if len(radii) != 2 or min(int(r) for r in radii) < 0 or int(radii[0]) + int(radii[1]) > _lib.PXT_OCCLUSION_MAX_RADIUS:
-        raise _lib.PxtError(f"occlusion_mask: radii are (r_open, r_grow) >= 0 with r_open + r_grow <= "
-                            f"{_lib.PXT_OCCLUSION_MAX_RADIUS} (got {list(radii)})")
-    _occlusion_record(record, "occlusion_mask")
-    need = int(L.pxt_occlusion_mask_workspace_bytes(W, H))
-    if need <= 0:
-        raise _lib.PxtError(f"occlusion_mask: {W} x {H} is not supported (1..2^28 pixels)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"occlusion_mask: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    for t, name in ((depth, "depth"), (sensor, "sensor"), (mask_in, "mask_in"), (workspace, "workspace")):
-        _lib.require_gpu(t, name)
-        if t.device != depth.device:
-            raise _lib.PxtError(f"occlusion_mask: {name} is on {t.device}, depth on {depth.device}")
-    if record.is_cuda and record.device != depth.device:
-        raise _lib.PxtError(f"occlusion_mask: record is on {record.device}, depth on {depth.device}")
+        raise _lib.PxtError(f"{op}: mask and occluder are two tensors")
+    _shifts(op, shift)
+    _radii(op, radii)
+    rec = _record(op, record, "record", torch.int32, _lib.PXT_OCCLUSION_RECORD, depth.device)
+    _workspace(op, workspace, int(L.pxt_occlusion_mask_workspace_bytes(W, H)), f"{W} x {H} is not supported (1..2^28 pixels)")
+    _one_device(op, depth, [(depth, "depth"), (sensor, "sensor"), (mask_in, "mask_in"), (workspace, "workspace")])
     _lib.check(L.pxt_occlusion_mask(depth.data_ptr(), sensor.data_ptr(), mask_in.data_ptr(), W, H, int(shift[0]),
                                     int(shift[1]), float(min_alpha), float(sensor_q), float(delta_q), int(radii[0]),
-                                    int(radii[1]), mask.data_ptr(), occluder.data_ptr(), record.data_ptr(),
-                                    workspace.data_ptr(), _stream(depth)), "pxt_occlusion_mask")
+                                    int(radii[1]), mask.data_ptr(), occluder.data_ptr(), rec, workspace.data_ptr(),
+                                    _stream(depth)), "pxt_occlusion_mask")
 
 
 def _occlusion_mask_views(depth, sensors, masks_in, shifts, min_alpha, quanta, radii, masks, occluders, records, workspace):
+    op = "occlusion_mask_views"
     L = _lib.lib()
-    what = "occlusion_mask_views"
     K = len(depth)
     if not (1 <= K <= _lib.PXT_OCCLUSION_MAX_VIEWS):
-        raise _lib.PxtError(f"{what}: 1..{_lib.PXT_OCCLUSION_MAX_VIEWS} views (got {K})")
-    if not (len(sensors) == len(masks_in) == len(masks) == len(occluders) == K) or len(shifts) != 2 * K or len(quanta) != 2 * K:
-        raise _lib.PxtError(f"{what}: sensors, masks_in, masks and occluders hold one tensor, shifts (shift_x, shift_y) "
-                            f"and quanta (sensor_q, delta_q) two values per view ({K} views)")
-    if len(radii) != 2 or min(int(r) for r in radii) < 0 or int(radii[0]) + int(radii[1]) > _lib.PXT_OCCLUSION_MAX_RADIUS:
-        raise _lib.PxtError(f"{what}: radii are (r_open, r_grow) >= 0 with r_open + r_grow <= "
-                            f"{_lib.PXT_OCCLUSION_MAX_RADIUS} (got {list(radii)})")
-    if any(abs(int(v)) > 32767 for v in shifts):
-        raise _lib.PxtError(f"{what}: every shift is within +-32767 (got {list(shifts)})")
-    device = depth[0].device
+        raise _lib.PxtError(f"{op}: 1..{_lib.PXT_OCCLUSION_MAX_VIEWS} views (got {K})")
+    if not (len(sensors) == len(masks_in) == len(masks) == len(occluders) == K) or len(quanta) != 2 * K:
+        raise _lib.PxtError(f"{op}: sensors, masks_in, masks and occluders hold one tensor and quanta (sensor_q, delta_q) "
+                            f"two values per view ({K} views)")
+    _radii(op, radii)
+    _shifts(op, shifts, K)
     views = (_lib.OcclusionView * K)()
-    sizes, spans = [], []
+    sizes, spans, named = [], [], [(workspace, "workspace")]
     for k in range(K):
         d, sen, mi, mo, oc = depth[k], sensors[k], masks_in[k], masks[k], occluders[k]
-        _f32c(d, f"depth[{k}]")
-        if d.dim() != 3 or int(d.shape[2]) != 4:
-            raise _lib.PxtError(f"{what}: depth[{k}] is [H, W, 4] (got {tuple(d.shape)})")
-        H, W = int(d.shape[0]), int(d.shape[1])
-        if sen.dtype not in (torch.uint16, torch.int16) or not sen.is_contiguous() or tuple(sen.shape) != (H, W):
-            raise _lib.PxtError(f"{what}: sensors[{k}] is a contiguous uint16 (or int16) [{H}, {W}] tensor "
-                                f"(got {tuple(sen.shape)}, {sen.dtype})")
-        if mi.dtype != torch.uint8 or not mi.is_contiguous() or tuple(mi.shape) != (H, W):
-            raise _lib.PxtError(f"{what}: masks_in[{k}] is a contiguous uint8 [{H}, {W}] tensor")
-        _mask_out(mo, H, W, d, what)
-        _mask_out(oc, H, W, d, what)
-        # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-        for t, name in ((d, "depth"), (sen, "sensors"), (mi, "masks_in")):
-            _lib.require_gpu(t, f"{name}[{k}]")
-            if t.device != device:
-                raise _lib.PxtError(f"{what}: {name}[{k}] is on {t.device}, depth[0] on {device}")
+        H, W = _occlusion_pair(op, f"[{k}]", d, sen, mi, mo, oc)
+        named += [(d, f"depth[{k}]"), (sen, f"sensors[{k}]"), (mi, f"masks_in[{k}]")]
         sizes += [W, H]
         spans += [(mo.data_ptr(), mo.data_ptr() + H * W, f"masks[{k}]"), (oc.data_ptr(), oc.data_ptr() + H * W, f"occluders[{k}]")]
         v = views[k]
@@ -1292,145 +1171,93 @@ def _occlusion_mask_views(depth, sensors, masks_in, shifts, min_alpha, quanta, r
     spans.sort()
     for (_lo, hi, a), (lo, _hi, b) in zip(spans, spans[1:]):
         if lo < hi:
-            raise _lib.PxtError(f"{what}: {a} and {b} overlap; every view writes planes of its own")
-    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (K, _lib.PXT_OCCLUSION_RECORD) \
-            or not ((records.is_cuda and records.device == device) or records.is_pinned()):
-        raise _lib.PxtError(f"{what}: records is a contiguous int32 [{K}, {_lib.PXT_OCCLUSION_RECORD}] tensor on the depth "
-                            "planes' device or in pinned memory")
-    need = int(L.pxt_occlusion_mask_views_workspace_bytes(K, (C.c_int32 * (2 * K))(*sizes)))
-    if need <= 0:
-        raise _lib.PxtError(f"{what}: planes of {list(zip(sizes[0::2], sizes[1::2]))} are not supported (1..2^28 pixels)")
-    _lib.require_gpu(workspace, "workspace")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != device:
-        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {need} bytes on {device}")
-    _lib.check(L.pxt_occlusion_mask_views(views, K, float(min_alpha), int(radii[0]), int(radii[1]), records.data_ptr(),
+            raise _lib.PxtError(f"{op}: {a} and {b} overlap; every view writes planes of its own")
+    rec = _record(op, records, "records", torch.int32, 0, depth[0].device, shape=(K, _lib.PXT_OCCLUSION_RECORD))
+    _workspace(op, workspace, int(L.pxt_occlusion_mask_views_workspace_bytes(K, (C.c_int32 * (2 * K))(*sizes))),
+               f"planes of {list(zip(sizes[0::2], sizes[1::2]))} are not supported (1..2^28 pixels)")
+    _one_device(op, depth[0], named)
+    _lib.check(L.pxt_occlusion_mask_views(views, K, float(min_alpha), int(radii[0]), int(radii[1]), rec,
                                           workspace.data_ptr(), _stream(depth[0])), "pxt_occlusion_mask_views")
 
 
 def _mask_exclude(mask_in, occluder, mask, record):
-    L = _lib.lib()
-    if mask_in.dtype != torch.uint8 or mask_in.dim() != 2 or not mask_in.is_contiguous():
-        raise _lib.PxtError("mask_exclude: mask_in is a contiguous uint8 [H, W] tensor")
+    op = "mask_exclude"
+    _dense(op, mask_in, "mask_in", torch.uint8, (None, None))
     H, W = int(mask_in.shape[0]), int(mask_in.shape[1])
-    for t, name in ((occluder, "occluder"), (mask, "mask")):
-        if t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != (H, W):
-            raise _lib.PxtError(f"mask_exclude: {name} is a contiguous uint8 [{H}, {W}] tensor (got {tuple(t.shape)}, "
-                                f"{t.dtype})")
-        _lib.require_gpu(t, name)
-        if t.device != mask_in.device:
-            raise _lib.PxtError(f"mask_exclude: {name} is on {t.device}, mask_in on {mask_in.device}")
-    _lib.require_gpu(mask_in, "mask_in")
+    _dense(op, occluder, "occluder", torch.uint8, (H, W))
+    _dense(op, mask, "mask", torch.uint8, (H, W))
     if H < 1 or W < 1 or H * W > 1 << 28:
-        raise _lib.PxtError(f"mask_exclude: {W} x {H} is not supported (1..2^28 pixels)")
+        raise _lib.PxtError(f"{op}: {W} x {H} is not supported (1..2^28 pixels)")
     if mask.data_ptr() == occluder.data_ptr():
-        raise _lib.PxtError("mask_exclude: mask may be mask_in, not occluder")
-    if record.dtype != torch.int32 or not record.is_contiguous() or record.numel() < 2 \
-            or not (record.is_cuda or record.is_pinned()):
-        raise _lib.PxtError("mask_exclude: record needs 2 contiguous int32 words in device or pinned memory")
-    if record.is_cuda and record.device != mask_in.device:
-        raise _lib.PxtError(f"mask_exclude: record is on {record.device}, mask_in on {mask_in.device}")
-    _lib.check(L.pxt_mask_exclude(mask_in.data_ptr(), occluder.data_ptr(), W, H, mask.data_ptr(), record.data_ptr(),
-                                  _stream(mask_in)), "pxt_mask_exclude")
+        raise _lib.PxtError(f"{op}: mask may be mask_in, not occluder")
+    rec = _record(op, record, "record", torch.int32, 2, mask_in.device)
+    _one_device(op, mask_in, [(mask_in, "mask_in"), (occluder, "occluder"), (mask, "mask")])
+    _lib.check(_lib.lib().pxt_mask_exclude(mask_in.data_ptr(), occluder.data_ptr(), W, H, mask.data_ptr(), rec,
+                                           _stream(mask_in)), "pxt_mask_exclude")
 
 
 def _points_visible(p3d, valid_in, pose, camera, ndist, occluder, valid, record):
-    L = _lib.lib()
-    _f32c(p3d, "p3d")
-    n = int(p3d.shape[0])
-    if tuple(p3d.shape) != (n, 3):
-        raise _lib.PxtError(f"points_visible: p3d is {tuple(p3d.shape)}, expected [N, 3]")
-    if occluder.dtype != torch.uint8 or occluder.dim() != 2 or not occluder.is_contiguous():
-        raise _lib.PxtError("points_visible: occluder is a contiguous uint8 [H, W]")
+    op = "points_visible"
+    n = int(_dense(op, p3d, "p3d", shape=(None, 3)).shape[0])
+    _dense(op, occluder, "occluder", torch.uint8, (None, None))
     H, W = int(occluder.shape[0]), int(occluder.shape[1])
     if len(pose) != 12 or len(camera) != 10:
-        raise _lib.PxtError("points_visible: pose holds 12 floats, camera 10")
+        raise _lib.PxtError(f"{op}: pose holds 12 floats, camera 10")
     if (float(camera[0]), float(camera[1])) != (float(W), float(H)):
-        raise _lib.PxtError(f"points_visible: the camera is {camera[0]:g} x {camera[1]:g}, the occluder plane {W} x {H}")
+        raise _lib.PxtError(f"{op}: the camera is {camera[0]:g} x {camera[1]:g}, the occluder plane {W} x {H}")
     for t, name in ((valid_in, "valid_in"), (valid, "valid")):
-        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != (n,)):
-            raise _lib.PxtError(f"points_visible: {name} is a contiguous uint8 [{n}] tensor")
-    _occlusion_record(record, "points_visible")
-    _lib.require_gpu(occluder, "occluder")
-    for t, name in ((p3d, "p3d"), (valid_in, "valid_in"), (valid, "valid")):
-        if t is None:
-            continue
-        _lib.require_gpu(t, name)
-        if t.device != occluder.device:
-            raise _lib.PxtError(f"points_visible: {name} is on {t.device}, the occluder plane on {occluder.device}")
-    if record.is_cuda and record.device != occluder.device:
-        raise _lib.PxtError(f"points_visible: record is on {record.device}, the occluder plane on {occluder.device}")
+        if t is not None:
+            _dense(op, t, name, torch.uint8, (n,))
+    rec = _record(op, record, "record", torch.int32, _lib.PXT_OCCLUSION_RECORD, occluder.device)
+    _one_device(op, occluder, [(occluder, "occluder"), (p3d, "p3d"), (valid_in, "valid_in"), (valid, "valid")])
     T = (C.c_float * 12)(*[float(x) for x in pose])
     cam = (C.c_float * 10)(*[float(x) for x in camera])
-    _lib.check(L.pxt_points_visible(p3d.data_ptr() if n else None, _lib.dptr(valid_in) if n else None, n, T, cam,
-                                    int(ndist), occluder.data_ptr(), W, H, valid.data_ptr() if n else None,
-                                    record.data_ptr(), _stream(occluder)), "pxt_points_visible")
+    _lib.check(_lib.lib().pxt_points_visible(p3d.data_ptr() if n else None, _lib.dptr(valid_in) if n else None, n, T, cam,
+                                             int(ndist), occluder.data_ptr(), W, H, valid.data_ptr() if n else None, rec,
+                                             _stream(occluder)), "pxt_points_visible")
 
 
 def _ngp_query(ctx, pos, dir, out):
-    _f32c(pos, "pos")
-    _f32c(dir, "dir")
-    _f32c(out, "out")
-    n = int(pos.shape[0])
-    if tuple(pos.shape) != (n, 3) or tuple(dir.shape) != (n, 3) or tuple(out.shape) != (n, 4) or n < 1:
-        raise _lib.PxtError(f"ngp_query: pos {tuple(pos.shape)} / dir {tuple(dir.shape)} / out {tuple(out.shape)}, expected "
-                            "[n, 3] / [n, 3] / [n, 4], n >= 1")
-    for t, name in ((pos, "pos"), (dir, "dir"), (out, "out")):
-        _lib.require_gpu(t, name)
-        if t.device != pos.device:
-            raise _lib.PxtError(f"ngp_query: {name} is on {t.device}, pos on {pos.device}")
+    op = "ngp_query"
+    n = int(_dense(op, pos, "pos", shape=(None, 3)).shape[0])
+    _dense(op, dir, "dir", shape=(n, 3))
+    _dense(op, out, "out", shape=(n, 4))
+    if n < 1:
+        raise _lib.PxtError(f"{op}: no point to query")
+    _one_device(op, pos, [(pos, "pos"), (dir, "dir"), (out, "out")])
     _lib.check(_lib.lib().pxt_ngp_query(int(ctx), pos.data_ptr(), dir.data_ptr(), n, out.data_ptr(), _stream(pos)),
                "pxt_ngp_query")
 
 
-def _iso_grid(values, grid, what):
-    _f32c(values, "values")
-    if values.dim() != 3 or len(grid) != 7:
-        raise _lib.PxtError(f"{what}: values is [nz, ny, nx] (got {tuple(values.shape)}), grid holds iso, origin xyz, "
-                            "spacing xyz")
+def _iso_grid(op, values, grid, workspace):
+    """What iso_surface_count and iso_surface_emit check alike: the lattice, its grid record and the workspace the
+    pair shares -> pxt_iso_grid."""
+    _dense(op, values, "values", shape=(None, None, None))
+    if len(grid) != 7:
+        raise _lib.PxtError(f"{op}: grid holds iso, origin xyz, spacing xyz")
     nz, ny, nx = (int(v) for v in values.shape)
     need = int(_lib.lib().pxt_iso_surface_workspace_bytes(nx, ny, nz)) if min(nx, ny, nz) >= 1 else -1
-    if need <= 0:
-        raise _lib.PxtError(f"{what}: a {nz} x {ny} x {nx} lattice is not supported (every extent >= 1, <= 2^27 points)")
+    _workspace(op, workspace, need, f"a {nz} x {ny} x {nx} lattice is not supported (every extent >= 1, <= 2^27 points)")
+    _one_device(op, values, [(values, "values"), (workspace, "workspace")])
     g = [float(v) for v in grid]
-    return _lib.IsoGrid(nx, ny, nz, g[0], (C.c_float * 3)(*g[1:4]), (C.c_float * 3)(*g[4:7])), need
-
-
-def _iso_workspace(workspace, need, values, what):
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    for t, name in ((values, "values"), (workspace, "workspace")):
-        _lib.require_gpu(t, name)
-        if t.device != values.device:
-            raise _lib.PxtError(f"{what}: {name} is on {t.device}, the values on {values.device}")
+    return _lib.IsoGrid(nx, ny, nz, g[0], (C.c_float * 3)(*g[1:4]), (C.c_float * 3)(*g[4:7]))
 
 
 def _iso_surface_count(values, grid, workspace, counts):
-    g, need = _iso_grid(values, grid, "iso_surface_count")
-    _iso_workspace(workspace, need, values, "iso_surface_count")
-    if counts.dtype != torch.int32 or not counts.is_contiguous() or counts.numel() < 2 \
-            or not ((counts.is_cuda and counts.device == values.device) or counts.is_pinned()):
-        raise _lib.PxtError("iso_surface_count: counts needs 2 contiguous int32 words on the values' device or in pinned memory")
-    _lib.check(_lib.lib().pxt_iso_surface_count(values.data_ptr(), C.byref(g), workspace.data_ptr(), counts.data_ptr(),
-                                                _stream(values)), "pxt_iso_surface_count")
+    g = _iso_grid("iso_surface_count", values, grid, workspace)
+    rec = _record("iso_surface_count", counts, "counts", torch.int32, 2, values.device)
+    _lib.check(_lib.lib().pxt_iso_surface_count(values.data_ptr(), C.byref(g), workspace.data_ptr(), rec, _stream(values)),
+               "pxt_iso_surface_count")
 
 
 def _iso_surface_emit(values, grid, workspace, vertices, normals, triangles):
-    g, need = _iso_grid(values, grid, "iso_surface_emit")
-    _iso_workspace(workspace, need, values, "iso_surface_emit")
-    _f32c(vertices, "vertices")
-    n, m = int(vertices.shape[0]), int(triangles.shape[0])
-    if tuple(vertices.shape) != (n, 3) or triangles.dtype != torch.int32 or not triangles.is_contiguous() \
-            or tuple(triangles.shape) != (m, 3):
-        raise _lib.PxtError(f"iso_surface_emit: vertices is float32 [n, 3], triangles contiguous int32 [m, 3] (got "
-                            f"{tuple(vertices.shape)}, {tuple(triangles.shape)} {triangles.dtype})")
-    if normals is not None and (_f32c(normals, "normals").shape != vertices.shape):
-        raise _lib.PxtError(f"iso_surface_emit: normals is float32 {tuple(vertices.shape)}")
-    for t, name in ((vertices, "vertices"), (normals, "normals"), (triangles, "triangles")):
-        if t is None:
-            continue
-        _lib.require_gpu(t, name)
-        if t.device != values.device:
-            raise _lib.PxtError(f"iso_surface_emit: {name} is on {t.device}, the values on {values.device}")
+    op = "iso_surface_emit"
+    g = _iso_grid(op, values, grid, workspace)
+    n = int(_dense(op, vertices, "vertices", shape=(None, 3)).shape[0])
+    m = int(_dense(op, triangles, "triangles", torch.int32, (None, 3)).shape[0])
+    if normals is not None:
+        _dense(op, normals, "normals", shape=(n, 3))
+    _one_device(op, values, [(vertices, "vertices"), (normals, "normals"), (triangles, "triangles")])
     _lib.check(_lib.lib().pxt_iso_surface_emit(values.data_ptr(), C.byref(g), workspace.data_ptr(),
                                                vertices.data_ptr() if n else None, n,
                                                _lib.dptr(normals) if n else None, triangles.data_ptr() if m else None, m,
@@ -1438,120 +1265,73 @@ def _iso_surface_emit(values, grid, workspace, vertices, normals, triangles):
 
 
 def _max_pairwise_distance(points, out, workspace):
+    op = "max_pairwise_distance"
     L = _lib.lib()
-    _f32c(points, "points")
-    n = int(points.shape[0])
-    if tuple(points.shape) != (n, 3):
-        raise _lib.PxtError(f"max_pairwise_distance: points is {tuple(points.shape)}, expected [n, 3]")
-    need = int(L.pxt_max_pairwise_distance_workspace_bytes(n))
-    if need <= 0:
-        raise _lib.PxtError(f"max_pairwise_distance: {n} points is not supported (1..2^22)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"max_pairwise_distance: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() < 4 \
-            or not ((out.is_cuda and out.device == points.device) or out.is_pinned()):
-        raise _lib.PxtError("max_pairwise_distance: out needs 4 contiguous int32 words on the points' device or in pinned "
-                            "memory")
-    for t, name in ((points, "points"), (workspace, "workspace")):
-        _lib.require_gpu(t, name)
-        if t.device != points.device:
-            raise _lib.PxtError(f"max_pairwise_distance: {name} is on {t.device}, the points on {points.device}")
-    _lib.check(L.pxt_max_pairwise_distance(points.data_ptr(), n, workspace.data_ptr(), out.data_ptr(), _stream(points)),
+    n = int(_dense(op, points, "points", shape=(None, 3)).shape[0])
+    _workspace(op, workspace, int(L.pxt_max_pairwise_distance_workspace_bytes(n)), f"{n} points is not supported (1..2^22)")
+    rec = _record(op, out, "out", torch.int32, 4, points.device)
+    _one_device(op, points, [(points, "points"), (workspace, "workspace")])
+    _lib.check(L.pxt_max_pairwise_distance(points.data_ptr(), n, workspace.data_ptr(), rec, _stream(points)),
                "pxt_max_pairwise_distance")
 
 
+def _mesh_inputs(op, vertices, triangles, views=None):
+    """A mesh's vertices float32 [V, 3] and triangles int32 [T, 3], and the device tensor of view records -> (V, T)."""
+    _dense(op, vertices, "vertices", shape=(None, 3))
+    _dense(op, triangles, "triangles", torch.int32, (None, 3))
+    if views is not None:
+        _dense(op, views, "views", shape=(None, _lib.PXT_MESH_VIEW))
+    return int(vertices.shape[0]), int(triangles.shape[0])
+
+
+def _mesh_raster_workspace(op, workspace, P, V, T, W, H):
+    need = int(_lib.lib().pxt_mesh_raster_workspace_bytes(P, T, W, H)) if min(P, T, W, H) >= 1 and 1 <= V <= 1 << 24 else -1
+    _workspace(op, workspace, need, f"{P} views of {W} x {H}, {V} vertices, {T} triangles are not supported "
+                                    "(1..4096 views, 1..2^26 pixels, 1..2^24 vertices and triangles)")
+
+
 def _mesh_raster(vertices, triangles, views, depth, triangle_ids, records, workspace):
-    L = _lib.lib()
-    _f32c(vertices, "vertices")
-    _f32c(views, "views")
-    _f32c(depth, "depth")
-    if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or triangles.dim() != 2 or int(triangles.shape[1]) != 3
-            or triangles.dtype != torch.int32 or not triangles.is_contiguous() or views.dim() != 2
-            or int(views.shape[1]) != _lib.PXT_MESH_VIEW):
-        raise _lib.PxtError(f"mesh_raster: vertices {tuple(vertices.shape)} / triangles {tuple(triangles.shape)} "
-                            f"{triangles.dtype} / views {tuple(views.shape)}, expected float32 [V, 3] / contiguous int32 "
-                            f"[T, 3] / float32 [P, {_lib.PXT_MESH_VIEW}]")
-    V, T, P = int(vertices.shape[0]), int(triangles.shape[0]), int(views.shape[0])
-    if depth.dim() != 4 or int(depth.shape[0]) != P or int(depth.shape[3]) != 4:
-        raise _lib.PxtError(f"mesh_raster: depth is {tuple(depth.shape)}, expected [{P}, H, W, 4]")
+    op = "mesh_raster"
+    V, T = _mesh_inputs(op, vertices, triangles, views)
+    P = int(views.shape[0])
+    _dense(op, depth, "depth", shape=(P, None, None, 4))
     H, W = int(depth.shape[1]), int(depth.shape[2])
-    if triangle_ids is not None and (triangle_ids.dtype != torch.int32 or not triangle_ids.is_contiguous()
-                                     or tuple(triangle_ids.shape) != (P, H, W)):
-        raise _lib.PxtError(f"mesh_raster: triangle_ids is a contiguous int32 [{P}, {H}, {W}] tensor (got "
-                            f"{tuple(triangle_ids.shape)}, {triangle_ids.dtype})")
-    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
-        raise _lib.PxtError(f"mesh_raster: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
-                            f"(got {tuple(records.shape)}, {records.dtype})")
-    need = int(L.pxt_mesh_raster_workspace_bytes(P, T, W, H)) if min(P, T, W, H) >= 1 else -1
-    if need <= 0 or not (1 <= V <= 1 << 24):
-        raise _lib.PxtError(f"mesh_raster: {P} views of {W} x {H}, {V} vertices, {T} triangles are not supported "
-                            "(1..4096 views, 1..2^26 pixels, 1..2^24 vertices and triangles)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"mesh_raster: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    named = [(vertices, "vertices"), (triangles, "triangles"), (views, "views"), (depth, "depth"), (records, "records"),
-             (workspace, "workspace")] + ([(triangle_ids, "triangle_ids")] if triangle_ids is not None else [])
-    for t, name in named:
-        _lib.require_gpu(t, name)
-        if t.device != vertices.device:
-            raise _lib.PxtError(f"mesh_raster: {name} is on {t.device}, the vertices on {vertices.device}")
-    _lib.check(L.pxt_mesh_raster(vertices.data_ptr(), V, triangles.data_ptr(), T, views.data_ptr(), P, W, H,
-                                 depth.data_ptr(), _lib.dptr(triangle_ids), records.data_ptr(), workspace.data_ptr(),
-                                 _stream(vertices)), "pxt_mesh_raster")
+    if triangle_ids is not None:
+        _dense(op, triangle_ids, "triangle_ids", torch.int32, (P, H, W))
+    _dense(op, records, "records", torch.int32, (P, _lib.PXT_MESH_RASTER_RECORD))
+    _mesh_raster_workspace(op, workspace, P, V, T, W, H)
+    _one_device(op, vertices, [(vertices, "vertices"), (triangles, "triangles"), (views, "views"), (depth, "depth"),
+                               (records, "records"), (workspace, "workspace"), (triangle_ids, "triangle_ids")])
+    _lib.check(_lib.lib().pxt_mesh_raster(vertices.data_ptr(), V, triangles.data_ptr(), T, views.data_ptr(), P, W, H,
+                                          depth.data_ptr(), _lib.dptr(triangle_ids), records.data_ptr(),
+                                          workspace.data_ptr(), _stream(vertices)), "pxt_mesh_raster")
 
 
-def _mesh_render_checked(what, vertices, triangles, attrs, check_attrs, views, width, height, rgba, rgb_u8, depth,
-                         depth_nz, triangle_ids, records, workspace):
-    """The checks mesh_render and mesh_render_textured share -> (V, T, P, W, H).  ``attrs``: [(tensor, name)] of the
-    call's own inputs, ``check_attrs(V, T)`` their shapes."""
-    L = _lib.lib()
-    _f32c(vertices, "vertices")
-    _f32c(views, "views")
-    if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or triangles.dim() != 2 or int(triangles.shape[1]) != 3
-            or triangles.dtype != torch.int32 or not triangles.is_contiguous() or views.dim() != 2
-            or int(views.shape[1]) != _lib.PXT_MESH_VIEW):
-        raise _lib.PxtError(f"{what}: vertices {tuple(vertices.shape)} / triangles {tuple(triangles.shape)} "
-                            f"{triangles.dtype} / views {tuple(views.shape)}, expected float32 [V, 3] / contiguous int32 "
-                            f"[T, 3] / float32 [P, {_lib.PXT_MESH_VIEW}]")
-    V, T, P, W, H = int(vertices.shape[0]), int(triangles.shape[0]), int(views.shape[0]), int(width), int(height)
-    check_attrs(V, T)
+def _mesh_render_checked(op, vertices, triangles, shading, views, width, height, rgba, rgb_u8, depth, depth_nz,
+                         triangle_ids, records, workspace):
+    """The checks mesh_render and mesh_render_textured share -> (V, T, P, W, H).  ``shading`` = (colors, uvs,
+    triangle_uvs, texture), the call's own inputs."""
+    V, T = _mesh_inputs(op, vertices, triangles, views)
+    P, W, H = int(views.shape[0]), int(width), int(height)
+    attrs = _mesh_shading_checked(op, V, T, *shading)
     outs = [(rgba, "rgba", torch.float32, (P, H, W, 4)), (rgb_u8, "rgb_u8", torch.uint8, (P, H, W, 3)),
             (depth, "depth", torch.float32, (P, H, W, 4)), (depth_nz, "depth_nz", torch.uint8, (P, H, W)),
             (triangle_ids, "triangle_ids", torch.int32, (P, H, W))]
     for t, name, dtype, shape in outs:
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape):
-            raise _lib.PxtError(f"{what}: {name} is a contiguous {dtype} {list(shape)} tensor (got "
-                                f"{tuple(t.shape)}, {t.dtype})")
+        if t is not None:
+            _dense(op, t, name, dtype, shape)
     if all(t is None for t, *_ in outs):
-        raise _lib.PxtError(f"{what}: no output was asked for")
-    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
-        raise _lib.PxtError(f"{what}: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
-                            f"(got {tuple(records.shape)}, {records.dtype})")
-    need = int(L.pxt_mesh_raster_workspace_bytes(P, T, W, H)) if min(P, T, W, H) >= 1 else -1
-    if need <= 0 or not (1 <= V <= 1 << 24):
-        raise _lib.PxtError(f"{what}: {P} views of {W} x {H}, {V} vertices, {T} triangles are not supported "
-                            "(1..4096 views, 1..2^26 pixels, 1..2^24 vertices and triangles)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {need} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    named = [(vertices, "vertices"), (triangles, "triangles"), *attrs, (views, "views"), (records, "records"),
-             (workspace, "workspace")] + [(t, name) for t, name, *_ in outs if t is not None]
-    for t, name in named:
-        _lib.require_gpu(t, name)
-        if t.device != vertices.device:
-            raise _lib.PxtError(f"{what}: {name} is on {t.device}, the vertices on {vertices.device}")
+        raise _lib.PxtError(f"{op}: no output was asked for")
+    _dense(op, records, "records", torch.int32, (P, _lib.PXT_MESH_RASTER_RECORD))
+    _mesh_raster_workspace(op, workspace, P, V, T, W, H)
+    _one_device(op, vertices, [(vertices, "vertices"), (triangles, "triangles"), *attrs, (views, "views"),
+                               (records, "records"), (workspace, "workspace"), *[(t, name) for t, name, *_ in outs]])
     return V, T, P, W, H
 
 
 def _mesh_render(vertices, triangles, colors, views, width, height, rgba, rgb_u8, depth, depth_nz, triangle_ids,
                  records, workspace):
-    _f32c(colors, "colors")
-
-    def check(V, T):
-        if tuple(colors.shape) != (V, 3):
-            raise _lib.PxtError(f"mesh_render: colors is {tuple(colors.shape)}, expected float32 [{V}, 3]")
-
-    V, T, P, W, H = _mesh_render_checked("mesh_render", vertices, triangles, [(colors, "colors")], check, views, width,
+    V, T, P, W, H = _mesh_render_checked("mesh_render", vertices, triangles, (colors, None, None, None), views, width,
                                          height, rgba, rgb_u8, depth, depth_nz, triangle_ids, records, workspace)
     _lib.check(_lib.lib().pxt_mesh_render(
         vertices.data_ptr(), V, triangles.data_ptr(), T, colors.data_ptr(), views.data_ptr(), P, W, H, _lib.dptr(rgba),
@@ -1561,22 +1341,9 @@ def _mesh_render(vertices, triangles, colors, views, width, height, rgba, rgb_u8
 
 def _mesh_render_textured(vertices, triangles, uvs, triangle_uvs, texture, views, width, height, rgba, rgb_u8, depth,
                           depth_nz, triangle_ids, records, workspace):
-    _f32c(uvs, "uvs")
-
-    def check(V, T):
-        if uvs.dim() != 2 or int(uvs.shape[1]) != 2 or not (1 <= int(uvs.shape[0]) <= 1 << 24):
-            raise _lib.PxtError(f"mesh_render_textured: uvs is {tuple(uvs.shape)}, expected float32 [1..2^24, 2]")
-        if triangle_uvs.dtype != torch.int32 or not triangle_uvs.is_contiguous() or tuple(triangle_uvs.shape) != (T, 3):
-            raise _lib.PxtError(f"mesh_render_textured: triangle_uvs is a contiguous int32 [{T}, 3] tensor (got "
-                                f"{tuple(triangle_uvs.shape)}, {triangle_uvs.dtype})")
-        if (texture.dtype != torch.uint8 or not texture.is_contiguous() or texture.dim() != 3 or int(texture.shape[2]) != 4
-                or not (1 <= int(texture.shape[0]) <= 16384 and 1 <= int(texture.shape[1]) <= 16384)):
-            raise _lib.PxtError("mesh_render_textured: texture is a contiguous uint8 [1..16384, 1..16384, 4] tensor (got "
-                                f"{tuple(texture.shape)}, {texture.dtype})")
-
     V, T, P, W, H = _mesh_render_checked(
-        "mesh_render_textured", vertices, triangles, [(uvs, "uvs"), (triangle_uvs, "triangle_uvs"), (texture, "texture")],
-        check, views, width, height, rgba, rgb_u8, depth, depth_nz, triangle_ids, records, workspace)
+        "mesh_render_textured", vertices, triangles, (None, uvs, triangle_uvs, texture), views, width, height, rgba,
+        rgb_u8, depth, depth_nz, triangle_ids, records, workspace)
     _lib.check(_lib.lib().pxt_mesh_render_textured(
         vertices.data_ptr(), V, triangles.data_ptr(), T, uvs.data_ptr(), int(uvs.shape[0]), triangle_uvs.data_ptr(),
         texture.data_ptr(), int(texture.shape[1]), int(texture.shape[0]), views.data_ptr(), P, W, H, _lib.dptr(rgba),
@@ -1624,40 +1391,21 @@ def mesh_frame_planes(geometry, offsets, what="mesh_render_frame", max_views=_li
 
 def _mesh_render_frame(vertices, triangles, colors, uvs, triangle_uvs, texture, views, geometry, offsets, rgba, rgb_u8,
                        depth, depth_nz, records, workspace):
-    what = "mesh_render_frame"
+    op = "mesh_render_frame"
     L = _lib.lib()
-    _f32c(vertices, "vertices")
-    _f32c(views, "views")
-    if (vertices.dim() != 2 or int(vertices.shape[1]) != 3 or triangles.dim() != 2 or int(triangles.shape[1]) != 3
-            or triangles.dtype != torch.int32 or not triangles.is_contiguous() or views.dim() != 2
-            or int(views.shape[1]) != _lib.PXT_MESH_VIEW):
-        raise _lib.PxtError(f"{what}: vertices {tuple(vertices.shape)} / triangles {tuple(triangles.shape)} "
-                            f"{triangles.dtype} / views {tuple(views.shape)}, expected float32 [V, 3] / contiguous int32 "
-                            f"[T, 3] / float32 [P, {_lib.PXT_MESH_VIEW}]")
-    V, T = int(vertices.shape[0]), int(triangles.shape[0])
-    P, need = mesh_frame_planes(geometry, offsets, what)
+    V, T = _mesh_inputs(op, vertices, triangles, views)
+    P, need = mesh_frame_planes(geometry, offsets, op)
     if int(views.shape[0]) != P:
-        raise _lib.PxtError(f"{what}: {int(views.shape[0])} views for {P} geometry entries")
-    attrs = _mesh_shading_checked(what, V, T, colors, uvs, triangle_uvs, texture)
-    outs, out_bytes = _mesh_frame_buffers(what, need, rgba, rgb_u8, depth, depth_nz)
-    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
-        raise _lib.PxtError(f"{what}: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
-                            f"(got {tuple(records.shape)}, {records.dtype})")
+        raise _lib.PxtError(f"{op}: {int(views.shape[0])} views for {P} geometry entries")
+    attrs = _mesh_shading_checked(op, V, T, colors, uvs, triangle_uvs, texture)
+    outs, cap = _mesh_frame_buffers(op, need, rgba, rgb_u8, depth, depth_nz)
+    _dense(op, records, "records", torch.int32, (P, _lib.PXT_MESH_RASTER_RECORD))
     geo = (C.c_int32 * (3 * P))(*[int(x) for x in geometry])
     off = (C.c_int64 * (4 * P))(*[int(x) for x in offsets])
-    cap = (C.c_int64 * 4)(*out_bytes)
-    bytes_needed = int(L.pxt_mesh_render_frame_workspace_bytes(P, T, geo)) if T >= 1 else -1
-    if bytes_needed <= 0 or not (1 <= V <= 1 << 24):
-        raise _lib.PxtError(f"{what}: {V} vertices, {T} triangles are not supported (1..2^24 vertices and triangles)")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < bytes_needed:
-        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {bytes_needed} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    named = [(vertices, "vertices"), (triangles, "triangles"), *attrs, (views, "views"), (records, "records"),
-             (workspace, "workspace")] + [(t, name) for t, name, _ in outs if t is not None]
-    for t, name in named:
-        _lib.require_gpu(t, name)
-        if t.device != vertices.device:
-            raise _lib.PxtError(f"{what}: {name} is on {t.device}, the vertices on {vertices.device}")
+    _workspace(op, workspace, int(L.pxt_mesh_render_frame_workspace_bytes(P, T, geo)) if T >= 1 and 1 <= V <= 1 << 24 else -1,
+               f"{V} vertices, {T} triangles are not supported (1..2^24 vertices and triangles)")
+    _one_device(op, vertices, [(vertices, "vertices"), (triangles, "triangles"), *attrs, (views, "views"),
+                               (records, "records"), (workspace, "workspace"), *outs])
     _lib.check(L.pxt_mesh_render_frame(
         vertices.data_ptr(), V, triangles.data_ptr(), T, _lib.dptr(colors), _lib.dptr(uvs),
         0 if uvs is None else int(uvs.shape[0]), _lib.dptr(triangle_uvs), _lib.dptr(texture),
@@ -1688,22 +1436,15 @@ def _mesh_shading_checked(what, V, T, colors, uvs, triangle_uvs, texture):
     if (colors is not None) == textured:
         raise _lib.PxtError(f"{what}: a mesh is drawn with colors or with uvs + triangle_uvs + texture, one of the two")
     if not textured:
-        _f32c(colors, "colors")
-        if tuple(colors.shape) != (V, 3):
-            raise _lib.PxtError(f"{what}: colors is {tuple(colors.shape)}, expected float32 [{V}, 3]")
-        return [(colors, "colors")]
+        return [(_dense(what, colors, "colors", shape=(V, 3)), "colors")]
     if uvs is None or triangle_uvs is None or texture is None:
         raise _lib.PxtError(f"{what}: a textured mesh needs uvs, triangle_uvs and texture")
-    _f32c(uvs, "uvs")
-    if uvs.dim() != 2 or int(uvs.shape[1]) != 2 or not (1 <= int(uvs.shape[0]) <= 1 << 24):
-        raise _lib.PxtError(f"{what}: uvs is {tuple(uvs.shape)}, expected float32 [1..2^24, 2]")
-    if triangle_uvs.dtype != torch.int32 or not triangle_uvs.is_contiguous() or tuple(triangle_uvs.shape) != (T, 3):
-        raise _lib.PxtError(f"{what}: triangle_uvs is a contiguous int32 [{T}, 3] tensor (got "
-                            f"{tuple(triangle_uvs.shape)}, {triangle_uvs.dtype})")
-    if (texture.dtype != torch.uint8 or not texture.is_contiguous() or texture.dim() != 3 or int(texture.shape[2]) != 4
-            or not (1 <= int(texture.shape[0]) <= 16384 and 1 <= int(texture.shape[1]) <= 16384)):
-        raise _lib.PxtError(f"{what}: texture is a contiguous uint8 [1..16384, 1..16384, 4] tensor (got "
-                            f"{tuple(texture.shape)}, {texture.dtype})")
+    _dense(what, uvs, "uvs", shape=(None, 2))
+    _dense(what, triangle_uvs, "triangle_uvs", torch.int32, (T, 3))
+    _dense(what, texture, "texture", torch.uint8, (None, None, 4))
+    if not (1 <= int(uvs.shape[0]) <= 1 << 24) or not (1 <= int(texture.shape[0]) <= 16384 and 1 <= int(texture.shape[1]) <= 16384):
+        raise _lib.PxtError(f"{what}: uvs {tuple(uvs.shape)} / texture {tuple(texture.shape)}, expected [1..2^24, 2] / "
+                            "[1..16384, 1..16384, 4]")
     return [(uvs, "uvs"), (triangle_uvs, "triangle_uvs"), (texture, "texture")]
 
 
@@ -1713,13 +1454,11 @@ def _mesh_frame_buffers(what, need, rgba, rgb_u8, depth, depth_nz):
             (depth_nz, "depth_nz", torch.uint8)]
     out_bytes = []
     for (t, name, dtype), n in zip(outs, need):
-        have = 0 if t is None else t.numel() * t.element_size()
-        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
-            raise _lib.PxtError(f"{what}: {name} is a contiguous {dtype} buffer (got {t.dtype})")
+        have = 0 if t is None else _dense(what, t, name, dtype).numel() * t.element_size()
         if have < n:
             raise _lib.PxtError(f"{what}: {name} holds {have} bytes, the views' planes need {n}")
         out_bytes.append(have)
-    return outs, out_bytes
+    return [(t, name) for t, name, _ in outs], (C.c_int64 * 4)(*out_bytes)
 
 
 def mesh_scene_planes(view_scene, r_grow, occluder_offsets, geometry, what="mesh_render_scene_batch"):
@@ -1783,9 +1522,6 @@ def _mesh_render_frame_batch_posed(vertices, triangles, colors, uvs, triangle_uv
 def mesh_view_poses(pose_records, radii, views_out, P, device, what="mesh_render_frame_batch_posed"):
     """The checks of mesh_render_frame_batch_posed's own arguments -> the ``pxt_mesh_view_pose`` array.  A record or
     ``views_out`` is memory the kernel dereferences: of ``device``, or pinned host memory."""
-    def reachable(t, name):
-        if not (t.is_cuda and t.device == device) and not (not t.is_cuda and t.is_pinned()):
-            raise _lib.PxtError(f"{what}: {name} is memory of {device} or pinned host memory (got {t.device}, unpinned)")
     if len(pose_records) != P or len(radii) != P:
         raise _lib.PxtError(f"{what}: pose_records and radii hold one entry per view ({P}; got {len(pose_records)}, "
                             f"{len(radii)})")
@@ -1793,19 +1529,12 @@ def mesh_view_poses(pose_records, radii, views_out, P, device, what="mesh_render
     for p, (rec, radius) in enumerate(zip(pose_records, radii)):
         if rec is None:
             continue
-        _f32c(rec, f"pose_records[{p}]")
-        if rec.numel() < 16:
-            raise _lib.PxtError(f"{what}: pose_records[{p}] holds {rec.numel()} floats, an LM output record has >= 16")
-        reachable(rec, f"pose_records[{p}]")
-        radius = float(radius)
+        table[p].pose_record = _record(what, rec, f"pose_records[{p}]", torch.float32, 16, device)
+        table[p].radius = radius = float(radius)
         if not (math.isfinite(radius) and radius >= 0.0):
             raise _lib.PxtError(f"{what}: view {p}'s radius is finite and >= 0 (got {radius})")
-        table[p].pose_record, table[p].radius = rec.data_ptr(), radius
     if views_out is not None:
-        _f32c(views_out, "views_out")
-        if tuple(views_out.shape) != (P, _lib.PXT_MESH_VIEW_OUT):
-            raise _lib.PxtError(f"{what}: views_out is float32 [{P}, {_lib.PXT_MESH_VIEW_OUT}] (got {tuple(views_out.shape)})")
-        reachable(views_out, "views_out")
+        _record(what, views_out, "views_out", torch.float32, 0, device, shape=(P, _lib.PXT_MESH_VIEW_OUT))
     return table
 
 
@@ -1819,19 +1548,13 @@ def _mesh_batch_call(what, vertices, triangles, colors, uvs, triangle_uvs, textu
         raise _lib.PxtError(f"{what}: vertices, triangles, colors, uvs, triangle_uvs and texture hold one entry per mesh "
                             f"(got {[len(x) for x in (vertices, triangles, colors, uvs, triangle_uvs, texture)]})")
     P, need = mesh_batch_planes(view_mesh, M, geometry, offsets, what)
-    if (views.is_cuda or views.dtype != torch.float32 or not views.is_contiguous()
-            or tuple(views.shape) != (P, _lib.PXT_MESH_VIEW)):
-        raise _lib.PxtError(f"{what}: views is a contiguous float32 CPU tensor [{P}, {_lib.PXT_MESH_VIEW}] (got "
-                            f"{tuple(views.shape)}, {views.dtype}, {views.device})")
+    if views.is_cuda:  # (the floats travel in the call's parameter record)
+        raise _lib.PxtError(f"{what}: views is a CPU tensor (got {views.device})")
+    _dense(what, views, "views", shape=(P, _lib.PXT_MESH_VIEW))
     named, descs, counts = [], (_lib.MeshDesc * M)(), []
     for m in range(M):
         v, t = vertices[m], triangles[m]
-        _f32c(v, f"vertices[{m}]")
-        if (v.dim() != 2 or int(v.shape[1]) != 3 or t.dim() != 2 or int(t.shape[1]) != 3 or t.dtype != torch.int32
-                or not t.is_contiguous()):
-            raise _lib.PxtError(f"{what}: mesh {m}: vertices {tuple(v.shape)} / triangles {tuple(t.shape)} {t.dtype}, "
-                                "expected float32 [V, 3] / contiguous int32 [T, 3]")
-        V, T = int(v.shape[0]), int(t.shape[0])
+        V, T = _mesh_inputs(f"{what}: mesh {m}", v, t)
         if not (1 <= V <= 1 << 24 and 1 <= T <= 1 << 24):
             raise _lib.PxtError(f"{what}: mesh {m}: {V} vertices, {T} triangles are not supported (1..2^24 vertices and "
                                 "triangles)")
@@ -1845,13 +1568,10 @@ def _mesh_batch_call(what, vertices, triangles, colors, uvs, triangle_uvs, textu
         d.tex_width = 0 if texture[m] is None else int(texture[m].shape[1])
         d.tex_height = 0 if texture[m] is None else int(texture[m].shape[0])
         counts.append(T)
-    outs, out_bytes = _mesh_frame_buffers(what, need, rgba, rgb_u8, depth, depth_nz)
-    if records.dtype != torch.int32 or not records.is_contiguous() or tuple(records.shape) != (P, _lib.PXT_MESH_RASTER_RECORD):
-        raise _lib.PxtError(f"{what}: records is a contiguous int32 [{P}, {_lib.PXT_MESH_RASTER_RECORD}] tensor "
-                            f"(got {tuple(records.shape)}, {records.dtype})")
+    outs, cap = _mesh_frame_buffers(what, need, rgba, rgb_u8, depth, depth_nz)
+    _dense(what, records, "records", torch.int32, (P, _lib.PXT_MESH_RASTER_RECORD))
     geo = (C.c_int32 * (3 * P))(*[int(x) for x in geometry])
     off = (C.c_int64 * (4 * P))(*[int(x) for x in offsets])
-    cap = (C.c_int64 * 4)(*out_bytes)
     vm = (C.c_int32 * P)(*[int(x) for x in view_mesh])
     occluder = None
     if scene is not None:
@@ -1862,45 +1582,29 @@ def _mesh_batch_call(what, vertices, triangles, colors, uvs, triangle_uvs, textu
             q = scenes.setdefault(int(s), p)
             if int(s) >= 0 and not torch.equal(views[p, 12:16].view(torch.int32), views[q, 12:16].view(torch.int32)):
                 raise _lib.PxtError(f"{what}: views {q} and {p} of scene {int(s)} differ in fx fy cx cy: a scene is one camera")
-        occ_have = 0 if occluder is None else occluder.numel()
-        if occluder is not None and (occluder.dtype != torch.uint8 or not occluder.is_contiguous()):
-            raise _lib.PxtError(f"{what}: occluder is a contiguous uint8 buffer (got {occluder.dtype})")
+        occ_have = 0 if occluder is None else _dense(what, occluder, "occluder", torch.uint8).numel()
         if occ_have < occ_need:
             raise _lib.PxtError(f"{what}: occluder holds {occ_have} bytes, the views' planes need {occ_need}")
-        if occluder is not None:
-            named.append((occluder, "occluder"))
     size_fn = L.pxt_mesh_render_frame_batch_workspace_bytes if scene is None else L.pxt_mesh_render_scene_batch_workspace_bytes
-    bytes_needed = int(size_fn(M, (C.c_int32 * M)(*counts), P, vm, geo))
-    if bytes_needed <= 0:
-        raise _lib.PxtError(f"{what}: the views {list(geometry)} are not supported")
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < bytes_needed:
-        raise _lib.PxtError(f"{what}: workspace is a contiguous uint8 tensor of >= {bytes_needed} bytes")
-    # what the kernels dereference must be memory of one device (a host pointer there is a memory fault, not an error)
-    named += [(records, "records"), (workspace, "workspace")] + [(t, name) for t, name, _ in outs if t is not None]
-    device = vertices[0].device
-    for t, name in named:
-        _lib.require_gpu(t, name)
-        if t.device != device:
-            raise _lib.PxtError(f"{what}: {name} is on {t.device}, vertices[0] on {device}")
+    _workspace(what, workspace, int(size_fn(M, (C.c_int32 * M)(*counts), P, vm, geo)),
+               f"the views {list(geometry)} are not supported")
+    _one_device(what, vertices[0], named + [(occluder, "occluder"), (records, "records"), (workspace, "workspace"), *outs])
+    common = (descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
+              _lib.dptr(depth_nz), cap)
     if posed is not None:
         pose_records, radii, views_out = posed
-        table = mesh_view_poses(pose_records, radii, views_out, P, device, what)
-        _lib.check(L.pxt_mesh_render_frame_batch_posed(
-            descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
-            _lib.dptr(depth_nz), cap, records.data_ptr(), workspace.data_ptr(), table, _lib.dptr(views_out),
-            _stream(vertices[0])), "pxt_mesh_render_frame_batch_posed")
-        return
-    if scene is None:
-        _lib.check(L.pxt_mesh_render_frame_batch(
-            descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
-            _lib.dptr(depth_nz), cap, records.data_ptr(), workspace.data_ptr(), _stream(vertices[0])),
-            "pxt_mesh_render_frame_batch")
-        return
-    _lib.check(L.pxt_mesh_render_scene_batch(
-        descs, M, vm, views.data_ptr(), P, geo, off, _lib.dptr(rgba), _lib.dptr(rgb_u8), _lib.dptr(depth),
-        _lib.dptr(depth_nz), cap, (C.c_int32 * P)(*[int(x) for x in view_scene]), int(r_grow), _lib.dptr(occluder),
-        occ_have, (C.c_int64 * P)(*[int(x) for x in occluder_offsets]), records.data_ptr(), workspace.data_ptr(),
-        _stream(vertices[0])), "pxt_mesh_render_scene_batch")
+        table = mesh_view_poses(pose_records, radii, views_out, P, vertices[0].device, what)
+        _lib.check(L.pxt_mesh_render_frame_batch_posed(*common, records.data_ptr(), workspace.data_ptr(), table,
+                                                       _lib.dptr(views_out), _stream(vertices[0])),
+                   "pxt_mesh_render_frame_batch_posed")
+    elif scene is None:
+        _lib.check(L.pxt_mesh_render_frame_batch(*common, records.data_ptr(), workspace.data_ptr(), _stream(vertices[0])),
+                   "pxt_mesh_render_frame_batch")
+    else:
+        _lib.check(L.pxt_mesh_render_scene_batch(
+            *common, (C.c_int32 * P)(*[int(x) for x in view_scene]), int(r_grow), _lib.dptr(occluder), occ_have,
+            (C.c_int64 * P)(*[int(x) for x in occluder_offsets]), records.data_ptr(), workspace.data_ptr(),
+            _stream(vertices[0])), "pxt_mesh_render_scene_batch")
 
 
 _IMPLS = {

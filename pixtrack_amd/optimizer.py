@@ -79,6 +79,19 @@ class LMResult:
     guard: bool = False  # the launch ended on its tile guard (PXT_E_GUARD): T is the pose before that iteration
 
 
+def flat_levels(levels: Sequence[LevelPack], n_points: Optional[int] = None, lambdas: bool = True):
+    """The per-level lists the LM ops take, levels in the given order
+    -> (fmaps, frefs, channels, cameras (10 floats each), ndist, lambdas (6 floats each; none unless asked for))."""
+    cams, ndist, lams = [], [], []
+    for lp in levels:
+        assert n_points is None or lp.fref.shape == (n_points, lp.fmap.shape[2])
+        cams += lp.camera.as10().tolist()
+        ndist.append(int(lp.camera._data.shape[-1] - 6))
+        if lambdas:
+            lams += lp.lambda_.float().tolist()
+    return [lp.fmap for lp in levels], [lp.fref for lp in levels], [int(lp.C) for lp in levels], cams, ndist, lams
+
+
 class Interpolator:
     """pixloc Interpolator surface: ``obs, mask, grads = interp(tensor[C,h,w], pts[N,2])``.
     Implemented on the sparse-sampling kernel with an identity camera (u = x, v = y)."""
@@ -260,12 +273,7 @@ class PixTrackOptimizer:
         dev = p3d.device
         n_levels = len(levels)
         assert 1 <= n_levels <= _lib.PXT_MAX_LEVELS
-        cams, lambdas, ndist = [], [], []
-        for lp in levels:
-            assert lp.fref.shape == (p3d.shape[0], lp.fmap.shape[2])
-            cams += lp.camera.as10().tolist()
-            ndist.append(int(lp.camera._data.shape[-1] - 6))
-            lambdas += lp.lambda_.float().tolist()
+        fmaps, frefs, chans, cams, ndist, lambdas = flat_levels(levels, p3d.shape[0])
         # One buffer for the output record and the iteration log, in pinned host memory: the
         # kernel's (write-only) stores land on the host directly, so the frame's critical path
         # has no device->host copy to enqueue and wait for after the kernel - only the event.
@@ -276,11 +284,9 @@ class PixTrackOptimizer:
         p3d = p3d.to(torch.float32).contiguous()
         if mask is not None:
             mask = mask.to(dev, torch.uint8).contiguous()
-        T0 = T_init.as12().detach().cpu().reshape(-1).tolist() if hasattr(T_init, "as12") else [float(x) for x in T_init]
-        ops.lm_refine(p3d, mask, [lp.fmap for lp in levels], [lp.fref for lp in levels], [int(lp.C) for lp in levels],
-                      cams, ndist, lambdas, T0, conf.num_iters, conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale,
-                      conf.grad_stop, conf.dt_stop, conf.dR_stop, conf.min_valid, conf.n_workgroups, buf, workspace,
-                      bool(want_log), int(conf.spin_limit),
+        ops.lm_refine(p3d, mask, fmaps, frefs, chans, cams, ndist, lambdas, _lib.pose_floats(T_init), conf.num_iters,
+                      conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale, conf.grad_stop, conf.dt_stop, conf.dR_stop,
+                      conf.min_valid, conf.n_workgroups, buf, workspace, bool(want_log), int(conf.spin_limit),
                       None if camera is None else [float(x) for x in camera[0]],
                       None if camera is None else [int(x) for x in camera[1]],
                       None if camera is None else camera[2], int(conf.path),
@@ -316,16 +322,9 @@ class PixTrackOptimizer:
             mask = ref.valid if pr.get("mask") is None else pr["mask"]  # (a point_gate's mask: refiner._point_mask)
             masks.append(None if mask is None else mask.to(dev, torch.uint8).contiguous())
             n_levels.append(len(levels))
-            for lp in levels:
-                assert lp.fref.shape == (ref.p3d.shape[0], lp.fmap.shape[2])
-                fmaps.append(lp.fmap)
-                frefs.append(lp.fref)
-                chans.append(int(lp.C))
-                cams += lp.camera.as10().tolist()
-                ndist.append(int(lp.camera._data.shape[-1] - 6))
-                lambdas += lp.lambda_.float().tolist()
-            T = pr["T_init"]
-            T0 += T.as12().detach().cpu().reshape(-1).tolist() if hasattr(T, "as12") else [float(x) for x in T]
+            for flat, more in zip((fmaps, frefs, chans, cams, ndist, lambdas), flat_levels(levels, ref.p3d.shape[0])):
+                flat += more
+            T0 += _lib.pose_floats(pr["T_init"])
             buf[:nh].zero_()
             recs.append(buf)
             wss.append(pr["workspace"])
@@ -354,25 +353,21 @@ class PixTrackOptimizer:
         """What information_levels and point_report_levels hand to their op: K pinned records of n_rec floats (a ring
         of two per (kind, pool_key, K), completion word - the last - cleared), the poses (PendingLM records, or 12
         floats each staged in pinned memory), cameras, ndist, contiguous p3d and masks.
-        -> (recs, poses, from_lm, cams, ndist, p3ds, masks)"""
+        -> (recs, poses, from_lm, (fmaps, frefs, channels, cameras, ndist), p3ds, masks)"""
         K = len(items)
         from_lm = isinstance(items[0]["pose"], PendingLM)
         recs = _pinned_records([n_rec] * K + ([] if from_lm else [16] * K), (kind, pool_key))
-        poses, cams, ndist = [], [], []
+        poses = []
         for k, it in enumerate(items):
             recs[k][n_rec - 1] = 0.0
-            lp = it["pack"]
-            cams += lp.camera.as10().tolist()
-            ndist.append(int(lp.camera._data.shape[-1] - 6))
             if from_lm:
                 poses.append(it["pose"].buf)
             else:
-                T = it["pose"]
-                recs[K + k][:12] = (T.as12() if hasattr(T, "as12") else torch.as_tensor(T)).detach().cpu().reshape(-1).float()
+                recs[K + k][:12] = torch.tensor(_lib.pose_floats(it["pose"]))
                 poses.append(recs[K + k])
         p3ds = [it["p3d"].to(torch.float32).contiguous() for it in items]
         masks = [None if it.get("mask") is None else it["mask"].to(p3ds[0].device, torch.uint8).contiguous() for it in items]
-        return recs[:K], poses, from_lm, cams, ndist, p3ds, masks
+        return recs[:K], poses, from_lm, flat_levels([it["pack"] for it in items], lambdas=False)[:5], p3ds, masks
 
     @staticmethod
     def information_levels(items: Sequence[dict], conf: _lib.LmConf, workspace: torch.Tensor, pool_key=0) -> "PendingInfo":
@@ -384,11 +379,10 @@ class PixTrackOptimizer:
         pool_key may be in flight - await a launch's result before enqueueing the launch after next (every caller in
         this package awaits each launch before the next)."""
         assert 1 <= len(items) <= _lib.PXT_LM_INFO_MAX_PROBLEMS
-        recs, poses, from_lm, cams, ndist, p3ds, masks = PixTrackOptimizer._stage_evaluation(
+        recs, poses, from_lm, levels, p3ds, masks = PixTrackOptimizer._stage_evaluation(
             "info", items, _lib.PXT_LM_INFO_RECORD, pool_key)
-        ops.lm_information(p3ds, masks, [it["pack"].fmap for it in items], [it["pack"].fref for it in items],
-                           [int(it["pack"].C) for it in items], cams, ndist, poses, from_lm, conf.pad, conf.loss,
-                           conf.loss_alpha, conf.loss_scale, conf.min_valid, recs, workspace)
+        ops.lm_information(p3ds, masks, *levels, poses, from_lm, conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale,
+                           conf.min_valid, recs, workspace)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(p3ds[0].device))
         return PendingInfo(recs, (p3ds, masks, [it["pack"] for it in items], poses, workspace), done)
@@ -401,14 +395,13 @@ class PixTrackOptimizer:
         ``.result()`` waits for the K pinned 16-float summaries; the records are recycled as information_levels' are
         (a ring of two per (K, pool_key): await a launch's result before enqueueing the launch after next)."""
         assert 1 <= len(items) <= _lib.PXT_LM_REPORT_MAX_PROBLEMS
-        recs, poses, from_lm, cams, ndist, p3ds, masks = PixTrackOptimizer._stage_evaluation(
+        recs, poses, from_lm, levels, p3ds, masks = PixTrackOptimizer._stage_evaluation(
             "report", items, _lib.PXT_LM_REPORT_SUMMARY, pool_key)
         dev = p3ds[0].device
         points = [torch.empty(int(p.shape[0]), _lib.PXT_LM_POINT_RECORD, dtype=torch.float32, device=dev)
                   if it.get("points") else None for it, p in zip(items, p3ds)]
-        ops.lm_point_report(p3ds, masks, [it["pack"].fmap for it in items], [it["pack"].fref for it in items],
-                            [int(it["pack"].C) for it in items], cams, ndist, poses, from_lm, conf.pad, conf.loss,
-                            conf.loss_alpha, conf.loss_scale, conf.min_valid,
+        ops.lm_point_report(p3ds, masks, *levels, poses, from_lm, conf.pad, conf.loss, conf.loss_alpha, conf.loss_scale,
+                            conf.min_valid,
                             [float(it.get("inlier_weight", 0.5)) for it in items], points, recs, workspace)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
