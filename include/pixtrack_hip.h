@@ -249,6 +249,29 @@ int pxt_score_pose_hypotheses(const pxt_reloc_map* map_host, const pxt_reloc_ban
                               int32_t n_hypotheses, const pxt_lm_conf* conf_host, float* out /* device [M][4] */,
                               void* stream);
 
+/* pxt_score_pose_hypotheses_depth - the depth counterpart (opt-in: relocalizer.RelocDepth): the same
+ * poses, ranges and bank points scored against the frame's sensor depth image.  Per point n of hypothesis h (n in
+ * [begin, begin + count), skipped where bank->valid[n] == 0):
+ *   p = transform_point(T_h, X_n); (u, v) = project_point(p) (the LM's projection, lens terms included).  A point
+ *   project_point refuses or whose pixel (floor(u + 0.5), floor(v + 0.5)) - pxt_points_visible's addressing - is outside
+ *   the image counts nowhere.  Otherwise it counts in n_in; raw = sensor[y][x], raw != 0 counts in n_measured;
+ *   d = float(raw) * sensor_scale and r = d - p.z are ONE fp32 operation each (no contraction); |r| <= tolerance
+ *   counts in n_agree (equality agrees), r > tolerance in n_behind (the sensor sees past the point).  A NaN counts in
+ *   neither.
+ *   out[h] = {n_in, n_measured, n_agree, n_behind}; a range outside the bank gives {-1, -1, -1, -1} and reads nothing.
+ * One wave per hypothesis, integer counts by ballot: no atomics, no workspace; a hypothesis's four words depend on its
+ * own inputs only.  bank->fref is ignored.  cam10_host / ndist: the UNSCALED query camera as pxt_points_visible takes it,
+ * cam[0] == width and cam[1] == height.
+ * Bounds: 1 <= M <= 2^22, width, height >= 1 and width * height <= 2^28, ndist 0 / 2 / 4, bank->n_points >= 1, poses and
+ * out 16-byte, ranges 8-byte, sensor 2-byte aligned, no NULL except bank->valid; anything else is PXT_E_ARG and nothing
+ * is launched or written. */
+int pxt_score_pose_hypotheses_depth(const pxt_reloc_bank* bank_host, const float* poses /* device [M][12] */,
+                                    const int32_t* ranges /* device [M][2] */, int32_t n_hypotheses,
+                                    const uint16_t* sensor /* device [height][width], 0 = no measurement */, int32_t width,
+                                    int32_t height, float sensor_scale /* SfM units per count */,
+                                    float tolerance /* SfM units */, const float* cam10_host, int32_t ndist,
+                                    int32_t* out /* device [M][4] */, void* stream);
+
 /* -------------------------------------------------------------------------
  * Pose information (the LM's normal equations at a given pose, evaluated once).
  *

@@ -303,6 +303,9 @@ PROTOTYPES = {
     "pxt_sample_sparse": (C.c_int, [_VP, _I32, _VP, C.POINTER(SampleLevel), _I32, _I32, _I32, _VP, _VP]),
     "pxt_score_pose_hypotheses": (
         C.c_int, [C.POINTER(RelocMap), C.POINTER(RelocBank), _VP, _VP, _I32, C.POINTER(LmConf), _VP, _VP]),
+    "pxt_score_pose_hypotheses_depth": (
+        C.c_int, [C.POINTER(RelocBank), _VP, _VP, _I32, _VP, _I32, _I32, C.c_float, C.c_float, C.POINTER(C.c_float),
+                  _I32, _VP, _VP]),
     "pxt_unet_create": (C.c_int, [_VP, _I64, C.POINTER(_VP)]),
     "pxt_unet_create_f32": (C.c_int, [_VP, _I64, C.POINTER(_VP)]),
     "pxt_unet_precision": (C.c_int, [_VP]),

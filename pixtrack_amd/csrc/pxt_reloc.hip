@@ -17,6 +17,26 @@
 // The camera (kernel argument), the pose and the range of a hypothesis (device arrays: M is bounded by memory, not by
 // the kernel-argument segment) are read through vector loads (pointers made opaque VGPR values, as the renderer's
 // camera is: DESIGN.md section 7).
+//
+// pxt_score_pose_hypotheses_depth is the depth counterpart: the same poses, ranges and bank
+// points, scored against the frame's SENSOR DEPTH image instead of a feature map.  A point of a hypothesis either lies
+// on the sensed surface or it does not: per point one 12-byte read of the point, one byte of the mask and ONE 2-byte
+// gather - no descriptors - so a whole placement grid (lateral position x distance per bank entry, relocalizer.py) is
+// scored in one launch and only its best go on to the feature scorer above.  Per point n of hypothesis h (skipped
+// where valid[n] == 0): p = transform_point(T_h, X_n), (u, v) = project_point(p) - the LM's projection - and the pixel
+// (floor(u + 0.5), floor(v + 0.5)), pxt_points_visible's addressing (texel k's centre is at coordinate k); a point the
+// projection refuses or whose pixel is outside the image counts nowhere.  Otherwise n_in counts it, raw = sensor[y][x],
+// raw != 0 counts in n_measured, and with d = float(raw) * sensor_scale and r = d - p.z (each ONE fp32 operation, not
+// contracted): |r| <= tolerance counts in n_agree (equality agrees), r > tolerance in n_behind (the sensor sees past
+// the point: the object is not there); a NaN counts in neither.  out[h] = {n_in, n_measured, n_agree, n_behind}, a
+// range outside the bank {-1, -1, -1, -1} without a read.
+//
+// Mapping: ONE WAVE per hypothesis, four hypotheses per workgroup of 256 threads; the lanes stride over the points,
+// four points per lane and trip, so that four independent 2-byte gathers are in flight per lane (the kernel is bound by
+// the latency of those gathers: a placement grid's hypotheses land all over the image).  The four counts are integers
+// from ballot and population count, kept wave-uniform: no atomics, no LDS, and a hypothesis's four words depend on its
+// own inputs only - not on M, its index, its neighbours in the workgroup or the run.  Lane 0 stores them as one 16-byte
+// vector store.
 #include "pxt_common.h"
 #include "pxt_lm_point.h"
 
@@ -137,6 +157,105 @@ __global__ __launch_bounds__(kRelocBlock) void reloc_score_kernel(const RelocPar
   }
 }
 
+constexpr int kDepthWaves = 4;                       // hypotheses per workgroup
+constexpr int kDepthBlock = kDepthWaves * PXT_WAVE;
+constexpr int kDepthFlight = 4;                      // points per lane and trip
+constexpr int kDepthMaxHypotheses = 1 << 22;
+constexpr long long kDepthMaxPixels = 1ll << 28;
+
+struct RelocDepthParams {
+  const float* p3d;
+  const uint8_t* valid;
+  const float* poses;      // [M][12]
+  const int32_t* ranges;   // [M][2] {begin, count}
+  const uint16_t* sensor;  // [H][W]
+  int32_t* out;            // [M][4]
+  int M, W, H, ndist, n_total;
+  float sensor_scale, tolerance;
+  float cam[10];
+};
+
+// r = raw * scale - pz as two fp32 operations: whatever the file's flags, the product is rounded before the difference.
+__device__ __forceinline__ float depth_residual(unsigned raw, float scale, float pz) {
+#pragma clang fp contract(off)
+  const float d = (float)raw * scale;
+  const float r = d - pz;
+  return r;
+}
+
+__global__ __launch_bounds__(kDepthBlock) void reloc_depth_kernel(const RelocDepthParams P) {
+  const int lane = threadIdx.x & (PXT_WAVE - 1);
+  const int hyp = blockIdx.x * kDepthWaves + threadIdx.x / PXT_WAVE;  // wave-uniform
+  if (hyp >= P.M) return;
+
+  float c10[10];
+  {  // (through the kernarg segment pointer: taking the address of the by-value argument would copy it to scratch)
+    const float* c = vector_pointer(((const RelocDepthParams*)__builtin_amdgcn_kernarg_segment_ptr())->cam);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) c10[i] = c[i];
+  }
+  const Cam cam = make_cam(c10, P.ndist);
+  float T[12];
+  load_pose12(vector_pointer(P.poses + (size_t)hyp * 12), T);
+  const int2 rg = *(const int2*)vector_pointer(P.ranges + (size_t)hyp * 2);
+  const int begin = rg.x, count = rg.y;
+  int4* const out = (int4*)(P.out + (size_t)hyp * 4);
+  // a range outside the bank is reported instead of read
+  if (begin < 0 || count < 0 || (long long)begin + count > (long long)P.n_total) {
+    if (lane == 0) *out = make_int4(-1, -1, -1, -1);
+    return;
+  }
+
+  const int W = P.W, H = P.H;
+  const float scale = P.sensor_scale, tol = P.tolerance;
+  int n_in = 0, n_measured = 0, n_agree = 0, n_behind = 0;  // wave-uniform
+  // without a mask the byte of the point's index is read from the points themselves (n < n_total <= their bytes) and
+  // ignored: the load stays unconditional, so it is issued with the point's and not waited for on its own
+  const uint8_t* const mask_bytes = P.valid ? P.valid : (const uint8_t*)P.p3d;
+  const unsigned no_mask = P.valid ? 0u : 1u;
+
+#pragma unroll 1
+  for (int base = 0; base < count; base += PXT_WAVE * kDepthFlight) {
+    // Three branch-free phases, each over the trip's four points: a wait for one point's loads is a wait for every load
+    // issued before it (one in-order counter), so the loads of a phase are issued together and consumed together.  A
+    // lane past the end of the range re-reads the range's last point and a point that is not in the image reads
+    // sensor[0]; neither counts.
+    bool in[kDepthFlight];
+    float X[kDepthFlight], Y[kDepthFlight], Z[kDepthFlight], pz[kDepthFlight];
+    unsigned mask[kDepthFlight], raw[kDepthFlight];
+#pragma unroll
+    for (int k = 0; k < kDepthFlight; ++k) {  // 1. the points and their mask bytes
+      const int i = base + k * PXT_WAVE + lane;
+      const size_t n = (size_t)begin + min(i, count - 1);
+      X[k] = P.p3d[3 * n];
+      Y[k] = P.p3d[3 * n + 1];
+      Z[k] = P.p3d[3 * n + 2];
+      mask[k] = mask_bytes[n] | no_mask;
+      in[k] = i < count;
+    }
+#pragma unroll
+    for (int k = 0; k < kDepthFlight; ++k) {  // 2. the projections; the four 2-byte gathers
+      float px, py, u, v;
+      transform_point(T, X[k], Y[k], Z[k], px, py, pz[k]);
+      const bool projects = project_point(cam, px, py, pz[k], u, v, nullptr);
+      const float xt = floorf(u + 0.5f), yt = floorf(v + 0.5f);  // the nearest texel: texel k's centre is at k
+      const bool inside = (xt >= 0.f) & (yt >= 0.f) & (xt < (float)W) & (yt < (float)H);
+      in[k] = in[k] & (mask[k] != 0u) & projects & inside;
+      const size_t texel = in[k] ? (size_t)(int)yt * W + (int)xt : 0;
+      raw[k] = P.sensor[texel];
+    }
+#pragma unroll
+    for (int k = 0; k < kDepthFlight; ++k) {  // 3. the four counts
+      const float r = depth_residual(raw[k], scale, pz[k]);
+      n_in += __popcll(__ballot(in[k]));
+      n_measured += __popcll(__ballot(in[k] & (raw[k] != 0u)));
+      n_agree += __popcll(__ballot(in[k] & (fabsf(r) <= tol)));
+      n_behind += __popcll(__ballot(in[k] & (r > tol)));
+    }
+  }
+  if (lane == 0) *out = make_int4(n_in, n_measured, n_agree, n_behind);
+}
+
 }  // namespace
 }  // namespace pxt
 
@@ -171,6 +290,41 @@ extern "C" int pxt_score_pose_hypotheses(const pxt_reloc_map* map, const pxt_rel
     hipLaunchKernelGGL(reloc_score_kernel<8>, dim3(n_hypotheses), dim3(kRelocBlock), 0, s, P);
   else
     hipLaunchKernelGGL(reloc_score_kernel<32>, dim3(n_hypotheses), dim3(kRelocBlock), 0, s, P);
+  PXT_HIP_CHECK(hipGetLastError());
+  return PXT_OK;
+}
+
+extern "C" int pxt_score_pose_hypotheses_depth(const pxt_reloc_bank* bank, const float* poses, const int32_t* ranges,
+                                               int32_t n_hypotheses, const uint16_t* sensor, int32_t width, int32_t height,
+                                               float sensor_scale, float tolerance, const float* cam10_host, int32_t ndist,
+                                               int32_t* out, void* stream) {
+  if (!bank || !poses || !ranges || !sensor || !cam10_host || !out) return PXT_E_ARG;
+  if (n_hypotheses < 1 || n_hypotheses > kDepthMaxHypotheses) return PXT_E_ARG;
+  if (width < 1 || height < 1 || (long long)width * height > kDepthMaxPixels) return PXT_E_ARG;
+  if (ndist != 0 && ndist != 2 && ndist != 4) return PXT_E_ARG;
+  if (!bank->p3d || bank->n_points < 1 || ((uintptr_t)bank->p3d % 4) != 0) return PXT_E_ARG;
+  if (((uintptr_t)poses % 16) != 0 || ((uintptr_t)ranges % 8) != 0 || ((uintptr_t)out % 16) != 0 ||
+      ((uintptr_t)sensor % 2) != 0)
+    return PXT_E_ARG;
+  // the camera is the one the sensor image was taken with (as pxt_points_visible holds it to its plane)
+  if (!(cam10_host[0] == (float)width && cam10_host[1] == (float)height)) return PXT_E_ARG;
+  RelocDepthParams P;
+  P.p3d = bank->p3d;
+  P.valid = bank->valid;
+  P.poses = poses;
+  P.ranges = ranges;
+  P.sensor = sensor;
+  P.out = out;
+  P.M = n_hypotheses;
+  P.W = width;
+  P.H = height;
+  P.ndist = ndist;
+  P.n_total = bank->n_points;
+  P.sensor_scale = sensor_scale;
+  P.tolerance = tolerance;
+  for (int i = 0; i < 10; ++i) P.cam[i] = cam10_host[i];
+  const unsigned grid = ((unsigned)n_hypotheses + kDepthWaves - 1) / kDepthWaves;
+  hipLaunchKernelGGL(reloc_depth_kernel, dim3(grid), dim3(kDepthBlock), 0, (hipStream_t)stream, P);
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;
 }

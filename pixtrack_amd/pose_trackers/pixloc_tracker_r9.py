@@ -97,13 +97,27 @@ class PixLocPoseTrackerR9(PoseTracker):
     def __init__(self, object_path, data_path, loc_path, eval_path, debug=0, device=None, assets=None,
                  unet_precision="fp16", relocalizer=None, uncertainty=False, reference_points="sfm",
                  point_report=False, depth_refine=None, occlusion=None, template=None, reference_sfm=None,
-                 upright_ref_img=None):
+                 upright_ref_img=None, reloc_depth=None, reloc_options=None):
         """``assets`` (optional) supplies everything that otherwise comes from disk, for the
         synthetic runs: dict(model3d, nerf2sfm, snapshot, weights, covis=None, aabb, upright_ref_img).
         ``unet_precision``: "fp16" (default) or "fp32" - the UNet pass the localizer builds (unet.UNet).
         ``relocalizer``: None / "off" (default: the reference's behaviour - cold start from the upright view, nothing
         relocalises), "views" (a relocalizer.Relocalizer over the mapping views) or a Relocalizer instance: the cold
-        start and the frame after a failed frame then take their pose from Relocalizer.localize.
+        start and the frame after a failed frame then take their pose from Relocalizer.localize.  "mesh": the same for a
+        mesh template (``template=MeshTemplate(...)``; ValueError without one), with ``reference_points`` "sfm" or
+        "template" and with the sensor options: the bank is the mapping views of the mesh-built SfM model, its reference
+        views drawn by the template itself, 32 per render_frame_batch call, beside the frame's own planes.
+        From the first relocalisation of a segment on, the frame's reference image is the mapping image on the SIDE the
+        camera sees instead of the nearest by rotation (_nearest_reference_ids says why); a tracker that never
+        relocalises chooses as before.
+        ``reloc_options``: keywords for that Relocalizer (views, rolls, shifts, top_k, max_views, ...).
+        ``reloc_depth``: None or a relocalizer.RelocDepth (``relocalizer="mesh"`` only) - a relocalised frame that has a
+        sensor image first scores a placement grid (lateral cell x distance per bank entry) against it in one
+        pxt_score_pose_hypotheses_depth launch and hands the best to the feature scorer.  Shares the
+        frame's one sensor upload with ``depth_refine`` / ``occlusion`` (the same lookup and scale, ValueError
+        otherwise).  The history entry of a relocalised frame gains ``reloc_n_placed`` and ``reloc_n_geometric`` (None
+        without the depth stage); nothing on the policy path reads them and the cost gate is untouched - it stays
+        frozen at the cold start's cost, so a relocalised frame may refine well and still go untracked.
         ``uncertainty``: False (default: nothing changes) or True - every LM launch is followed by one
         pxt_lm_information problem at the pose it returns, and a frame's history entry gains ``pose_info`` (6 x 6),
         ``pose_cov`` (6 x 6 or None), ``observability``, ``info_level`` and ``info_n_valid`` from the frame's last LM
@@ -175,6 +189,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._check_depth_refine(depth_refine, relocalizer)
         self._check_occlusion(occlusion, relocalizer, depth_refine)
         self.template = self._check_template(template, relocalizer, reference_points, depth_refine, occlusion)
+        self._check_reloc_depth(reloc_depth, relocalizer, depth_refine, occlusion)
+        self.reloc_depth, self._reloc_options = reloc_depth, dict(reloc_options or {})
         self.reference_points = reference_points
         default_paths = Paths(query_images="query/", reference_images=loc_path, reference_sfm="aug_sfm",
                               query_list="*_with_intrinsics.txt", global_descriptors="features.h5",
@@ -281,6 +297,8 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._query_tile_rest = 0  # frames the option still stays off after a fallback
         self.unet_precision = unet_precision
         self.relocalizer = self._make_relocalizer(relocalizer)
+        self._mesh_relocalizer = isinstance(relocalizer, str) and relocalizer == "mesh"
+        self._reference_by_side = False  # set by a relocalisation with relocalizer="mesh" (_nearest_reference_ids)
         self._lost = False  # a frame failed: the next one is relocalised (relocalizer on only)
         self._accepted_pose = None  # the last pose a frame accepted (the relocaliser scores it as one more hypothesis)
         self.last_relocalization = None  # RelocResult of the last relocalisation
@@ -338,9 +356,10 @@ class PixLocPoseTrackerR9(PoseTracker):
         if reference_points != "sfm":  # ("template" is "render" for a mesh template: the same refusals)
             if not self.supports_render_points:
                 raise ValueError(f"reference_points={reference_points!r} is not supported by {type(self).__name__} yet")
-            if relocalizer is not None and relocalizer != "off":
+            if relocalizer is not None and relocalizer != "off" and not (relocalizer == "mesh" and reference_points == "template"):
                 raise ValueError(f"reference_points={reference_points!r} is not combined with a relocalizer yet (its "
-                                 "feature bank is built from the SfM points)")
+                                 "feature bank is built from the SfM points), except relocalizer='mesh' with "
+                                 "reference_points='template'")
             if uncertainty:
                 raise ValueError(f"reference_points={reference_points!r} is not combined with uncertainty=True yet")
 
@@ -349,6 +368,9 @@ class PixLocPoseTrackerR9(PoseTracker):
         """-> None (the NeRF template) or the MeshTemplate; the options a mesh template is not combined with yet are
         refused by name."""
         if template is None or (isinstance(template, str) and template == "nerf"):
+            if isinstance(relocalizer, str) and relocalizer == "mesh":
+                raise ValueError("relocalizer='mesh' draws its bank with a mesh template: it needs "
+                                 "template=MeshTemplate(...); with the NeRF template use relocalizer='views'")
             if reference_points == "template":
                 raise ValueError("reference_points='template' takes its points from a mesh template's depth plane: it needs "
                                  "template=MeshTemplate(...); with the NeRF template use reference_points='render'")
@@ -357,9 +379,9 @@ class PixLocPoseTrackerR9(PoseTracker):
 
         if not isinstance(template, MeshTemplate):
             raise ValueError(f"template must be None, 'nerf' or a mesh_template.MeshTemplate (got {template!r})")
-        if relocalizer is not None and relocalizer != "off":
+        if relocalizer is not None and relocalizer != "off" and not (isinstance(relocalizer, str) and relocalizer == "mesh"):
             raise ValueError("a mesh template is not combined with a relocalizer yet (its hypothesis renders are NeRF "
-                             "renders)")
+                             "renders), except relocalizer='mesh'")
         if reference_points == "render":
             raise ValueError("a mesh template is not combined with reference_points='render' yet (the back-projection "
                              "reads the NeRF renderer's view record)")
@@ -382,8 +404,8 @@ class PixLocPoseTrackerR9(PoseTracker):
             return
         if not self.supports_depth_refine:
             raise ValueError(f"depth_refine is not supported by {type(self).__name__} yet")
-        if relocalizer is not None and relocalizer != "off":
-            raise ValueError("depth_refine is not combined with a relocalizer yet")
+        if relocalizer is not None and relocalizer != "off" and not (isinstance(relocalizer, str) and relocalizer == "mesh"):
+            raise ValueError("depth_refine is not combined with a relocalizer yet, except relocalizer='mesh'")
         if not callable(getattr(depth_refine, "lookup", None)) or not float(depth_refine.sensor_depth_scale) > 0:
             raise ValueError("depth_refine: a depth_refinement.DepthRefine with a lookup and a positive sensor_depth_scale")
 
@@ -394,8 +416,8 @@ class PixLocPoseTrackerR9(PoseTracker):
             return
         if not self.supports_occlusion:
             raise ValueError(f"occlusion is not supported by {type(self).__name__} yet")
-        if relocalizer is not None and relocalizer != "off":
-            raise ValueError("occlusion is not combined with a relocalizer yet")
+        if relocalizer is not None and relocalizer != "off" and not (isinstance(relocalizer, str) and relocalizer == "mesh"):
+            raise ValueError("occlusion is not combined with a relocalizer yet, except relocalizer='mesh'")
         if not callable(getattr(occlusion, "lookup", None)) or not float(occlusion.sensor_depth_scale) > 0 \
                 or not hasattr(getattr(occlusion, "conf", None), "resolve"):
             raise ValueError("occlusion: an occlusion.OcclusionMask with a lookup, a positive sensor_depth_scale and a conf")
@@ -404,13 +426,29 @@ class PixLocPoseTrackerR9(PoseTracker):
             raise ValueError("depth_refine and occlusion read ONE sensor image per frame: they must be given the same "
                              "lookup and the same sensor_depth_scale")
 
+    @staticmethod
+    def _check_reloc_depth(reloc_depth, relocalizer, depth_refine, occlusion):
+        if reloc_depth is None:
+            return
+        if not (isinstance(relocalizer, str) and relocalizer == "mesh"):
+            raise ValueError("reloc_depth is the depth stage of relocalizer='mesh'")
+        if not callable(getattr(reloc_depth, "lookup", None)) or not float(reloc_depth.sensor_depth_scale) > 0 \
+                or not hasattr(reloc_depth, "n_geometric"):
+            raise ValueError("reloc_depth: a relocalizer.RelocDepth with a lookup and a positive sensor_depth_scale")
+        for name, other in (("depth_refine", depth_refine), ("occlusion", occlusion)):
+            if other is not None and (other.lookup is not reloc_depth.lookup or float(other.sensor_depth_scale) != float(
+                    reloc_depth.sensor_depth_scale)):
+                raise ValueError(f"reloc_depth and {name} read ONE sensor image per frame: they must be given the same "
+                                 "lookup and the same sensor_depth_scale")
+
     def _stage_depth_sensor(self, query_path):
         """Before the frame's first launch: fetch the frame's sensor image and queue its upload, from a pinned buffer
         into a device buffer that both live as long as the tracker.  What then stands between the LM launch and the
         depth problem is the enqueue alone.  Either option (depth_refine, occlusion) triggers it; one upload per frame
         serves both - they name the same lookup (_check_occlusion)."""
         self._depth_sensor, self._depth_slot = None, 0
-        option = self.depth_refine if self.depth_refine is not None else self.occlusion  # (one lookup: _check_occlusion)
+        # (one lookup, whoever names it: _check_occlusion, _check_reloc_depth)
+        option = next(o for o in (self.depth_refine, self.occlusion, self.reloc_depth) if o is not None)
         sensor = option.lookup(os.path.basename(str(query_path)))
         if sensor is None:
             return
@@ -612,10 +650,29 @@ class PixLocPoseTrackerR9(PoseTracker):
         if relocalizer == "views":
             from ..relocalizer import Relocalizer
 
-            return Relocalizer(self.localizer, render=self.get_reference_image)
+            return Relocalizer(self.localizer, render=self.get_reference_image, **self._reloc_options)
+        if relocalizer == "mesh":
+            from ..relocalizer import Relocalizer
+
+            return Relocalizer(self.localizer, render_batch=self._draw_bank_views, depth=self.reloc_depth,
+                               **self._reloc_options)
         if isinstance(relocalizer, str):
-            raise ValueError(f"relocalizer must be 'off', 'views' or a Relocalizer (got {relocalizer!r})")
+            raise ValueError(f"relocalizer must be 'off', 'views', 'mesh' or a Relocalizer (got {relocalizer!r})")
         return relocalizer
+
+    def _draw_bank_views(self, poses):
+        """The relocaliser's bank views of a mesh template: the reference view of ``MeshTemplate.requests`` at every
+        pose (the reference camera, the template's supersample), up to 32 of them in ONE render_frame_batch call ->
+        [uint8 [H, W, 3]].  The frame's own planes (_own, _primed) are not touched."""
+        from .. import mesh_render as MR
+
+        t, rcam = self.template, self._reference_camera()
+        w, h = (int(round(float(x))) for x in rcam.size.tolist())
+        requests = [(MR.view_record(rcam, pose, t.near, t.depth_q(pose)), w, h, t.supersample, ("rgb_u8",)) for pose in poses]
+        if self.__dict__.get("_bank_ws") is None:
+            self._bank_ws = MR.FrameBatchWorkspace()
+        out = MR.render_frame_batch([(t.renderer, requests)], workspace=self._bank_ws, download_records=False)[0]
+        return [o["rgb_u8"] for o in out]
 
     def relocalize(self, query):
         if self.relocalizer is not None and not self.cold_start:
@@ -642,7 +699,13 @@ class PixLocPoseTrackerR9(PoseTracker):
 
             image = read_image(image)
         # (the last ACCEPTED pose: self.pose may be a relocalised pose whose frame then failed the gate)
-        res = self.relocalizer.localize(image, self.camera, last_pose=self._accepted_pose)
+        if self.reloc_depth is not None and self._depth_sensor is not None:
+            # (the frame's one staged upload, which depth_refine / occlusion read as well)
+            w, h = (int(round(float(x))) for x in self.camera.size.tolist())
+            self._check_sensor_size(h, w)
+            res = self.relocalizer.localize(image, self.camera, last_pose=self._accepted_pose, sensor=self._depth_sensor)
+        else:
+            res = self.relocalizer.localize(image, self.camera, last_pose=self._accepted_pose)
         self.last_relocalization = res
         self._relocalized_frame = True
         self.relocalization_count += 1
@@ -656,11 +719,31 @@ class PixLocPoseTrackerR9(PoseTracker):
         if not self.keep_feature_history:
             self.localizer.refiner.features_dicts.pop(self.dynamic_id, None)
         self.dynamic_id, self.cache_hit = None, False
+        # relocalizer="mesh": from here on the reference image is chosen by the side the camera sees (below)
+        self._reference_by_side = self._mesh_relocalizer
         self.reference_ids = self._nearest_reference_ids(self.pose)
 
+    def _view_sides(self, Rs, ts):
+        """Unit vectors from the object's centre (the mean of the SfM points) to the camera centres of poses
+        ``Rs`` [n, 3, 3], ``ts`` [n, 3]: which side of the object a camera sees, whatever its roll."""
+        centre = self.__dict__.get("_object_centre")
+        if centre is None:
+            centre = self._object_centre = np.mean([p.xyz for p in self.localizer.model3d.points3D.values()], axis=0)
+        d = -np.einsum("nji,nj->ni", np.asarray(Rs, np.float64), np.asarray(ts, np.float64)) - centre
+        return d / np.linalg.norm(d, axis=1, keepdims=True)
+
     def _nearest_reference_ids(self, pose):
-        R_qry = pose.numpy()[0]
+        """The mapping image nearest to ``pose`` by rotation (as the reference ranks them).  After a relocalisation with
+        relocalizer="mesh" the nearest by SIDE instead: a relocalised camera may be rolled by any angle against the
+        mapping views (the bank holds rolls for that reason), a roll is a large geodesic distance to EVERY mapping
+        image, and the nearest by rotation is then an image of another side of the object, most of whose points the
+        frame does not see (measured: DESIGN 3.26)."""
+        R_qry, t_qry = pose.numpy()
         dbs = self.localizer.model3d.dbs
+        if self._reference_by_side:
+            ids = sorted(dbs)
+            sides = self._view_sides([dbs[r].qvec2rotmat() for r in ids], [dbs[r].tvec for r in ids])
+            return [ids[int(np.argmax(sides @ self._view_sides([R_qry], [t_qry])[0]))]]
         return sorted(dbs, key=lambda r: geodesic_distance_for_rotations(R_qry, dbs[r].qvec2rotmat()))[:1]
 
     def start_segment(self, pose_init: Optional[Pose]):
@@ -676,6 +759,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         self._accepted_pose = pose_init
         self.cost_threshold, self.dynamic_id, self.cache_hit = None, None, False
         self._lost = False
+        self._reference_by_side = False
         if pose_init is not None:
             self.reference_ids = self._nearest_reference_ids(pose_init)
 
@@ -703,6 +787,11 @@ class PixLocPoseTrackerR9(PoseTracker):
             ids = list(dict.fromkeys([curr] + [k for k, v in self.covis[curr].items() if v > 50]))
             cand = cache[curr] = (ids, np.stack([dbs[r].qvec2rotmat() for r in ids]))
         ids, rots = cand
+        if self._reference_by_side:  # (after a relocalisation with relocalizer="mesh": _nearest_reference_ids says why)
+            dbs = self.localizer.model3d.dbs
+            sides = self._view_sides(rots, [dbs[r].tvec for r in ids])
+            self.reference_ids = [ids[int(np.argmax(sides @ self._view_sides(*[[x] for x in self.pose.numpy()])[0]))]]
+            return self.reference_ids
         gd = geodesic_distances_to(self.pose.numpy()[0], rots)
         self.reference_ids = [ids[int(np.argmin(gd))]]
         return self.reference_ids
@@ -1077,7 +1166,7 @@ class PixLocPoseTrackerR9(PoseTracker):
         refiner = self.localizer.refiner
         self._depth_frame_name = query_path
         self._occ_frame = self._mut_frame = self._primed.occlusion = None
-        if self.depth_refine is not None or self.occlusion is not None:
+        if self.depth_refine is not None or self.occlusion is not None or self.reloc_depth is not None:
             self._stage_depth_sensor(query_path)
         self._frame_setup(query)
         if self.occlusion is not None and self._depth_sensor is not None:
@@ -1244,6 +1333,9 @@ class PixLocPoseTrackerR9(PoseTracker):
         ret["camera"] = self.camera
         if self.relocalizer is not None:  # (an added key only where the option is on: the default history is unchanged)
             ret["relocalized"], self._relocalized_frame = self._relocalized_frame, False
+            if ret["relocalized"]:  # (None without the depth stage; nothing on the policy path reads them)
+                res = self.last_relocalization
+                ret["reloc_n_placed"], ret["reloc_n_geometric"] = res.n_placed, res.n_geometric
         if self.reference_points != "sfm":  # (added keys only where the option is on)
             # the pinned record of this frame's extraction: its kernels ran ahead of the LM launch whose result is here
             rec = refiner.last_points_record
@@ -1316,9 +1408,14 @@ def build_parser() -> argparse.ArgumentParser:
                         help="how much closer the sensor's surface must be, as a fraction of the model's extent (default 0.1)")
     parser.add_argument("--occlusion_radii", nargs=2, type=int, metavar=("OPEN", "GROW"), default=None,
                         help="box radii of the opening and the growth of the occluder plane (default 1 3)")
-    parser.add_argument("--relocalize", choices=("off", "views"), default="off",
-                        help="off (default: cold start from the upright view, a lost track stays lost) or views "
-                             "(relocalise the cold start and the frame after a failed frame against the mapping views)")
+    parser.add_argument("--relocalize", choices=("off", "views", "mesh"), default="off",
+                        help="off (default: cold start from the upright view, a lost track stays lost), views "
+                             "(relocalise the cold start and the frame after a failed frame against the mapping views) or "
+                             "mesh (the same with --template mesh: the bank's views are drawn by the mesh template)")
+    parser.add_argument("--relocalize_depth", action="store_true",
+                        help="--relocalize mesh: score a placement grid (lateral cell x distance per bank entry) against "
+                             "the frame's sensor depth image first (needs --sensor_depth_dir and --sensor_depth_scale; "
+                             "untuned defaults, relocalizer.RelocDepth)")
     parser.add_argument("--template", choices=("nerf", "mesh"), default="nerf",
                         help="what a frame's mask and reference image are rendered from: nerf (default: the object's "
                              "instant-ngp snapshot) or mesh (--mesh; no snapshot, nerf2sfm.pkl or $OBJ_AABB is read)")
@@ -1408,6 +1505,16 @@ def occlusion_option_from_args(args):
     return OcclusionMask(lookup=lookup, sensor_depth_scale=float(args.sensor_depth_scale), conf=OcclusionConf(**kw))
 
 
+def reloc_depth_option_from_args(args):
+    """--relocalize_depth and its companions -> a relocalizer.RelocDepth (None when the option is off)."""
+    if not getattr(args, "relocalize_depth", False):
+        return None
+    lookup = _sensor_lookup_from_args(args, "--relocalize_depth")
+    from ..relocalizer import RelocDepth
+
+    return RelocDepth(lookup=lookup, sensor_depth_scale=float(args.sensor_depth_scale))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     data_path = args.object_path / "pixtrack/pixsfm/dataset"
@@ -1421,6 +1528,7 @@ def main(argv=None):
     tracker = PixLocPoseTrackerR9(template=template_from_args(args), reference_sfm=args.reference_sfm,
                                   upright_ref_img=args.upright_ref_img,
                                   depth_refine=depth_option_from_args(args), occlusion=occlusion_option_from_args(args),
+                                  reloc_depth=reloc_depth_option_from_args(args),
                                   object_path=str(args.object_path), data_path=str(data_path),
                                   eval_path=str(eval_path), loc_path=str(loc_path), debug=args.debug,
                                   unet_precision=args.unet_precision, relocalizer=args.relocalize,
