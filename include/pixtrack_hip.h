@@ -419,6 +419,18 @@ typedef struct {
 int pxt_unet_layer_views(const pxt_unet* ctx, int32_t n_images, int32_t H, int32_t W, int32_t peers,
                          pxt_unet_layer_view* out /* [21] */);
 
+/* The same for an fp32 context (pxt_unet_create_f32), whose pass has its own layout: where pxt_unet_forward_batch over
+ * n_images images of H x W leaves its buffers, fp32 [n_images][h][w][c] at `offset` bytes into the workspace, all
+ * in_memory.  out[0..16]: the 17 convolutions' outputs, with `cfg` the configuration pxt_conv3x3_f32_cfg names for the
+ * layer (0 for layer 0, which has none), splits = 1, pool_fused = 0, deep_ring = 0, decoder = 1 for 13..16;
+ * out[17..20]: the pooled inputs of encoder blocks 1..4; out[21]: the decoder-input buffer (upsampled previous layer,
+ * then the cropped skip) as the last decoder layer leaves it, [n_images][h of 16][w of 16][input channels of 16] - the
+ * four decoder layers share it.  A pair pass is two single passes (n_images = 1 each): the second image's workspace
+ * starts at pxt_unet_workspace_bytes(ctx, H[0], W[0]).  PXT_E_ARG for a NULL argument, an fp16 context or a size the
+ * pass refuses; nothing is launched. */
+int pxt_unet_layer_views_f32(const pxt_unet* ctx, int32_t n_images, int32_t H, int32_t W,
+                             pxt_unet_layer_view* out /* [22] */);
+
 /* image: HWC, 3 channels, values 0..255 (float32 if image_is_u8 == 0, else uint8).
  * mask: optional H x W uint8 (0/1) multiplied into the image first
  *       (pixloc_tracker_r9.py:224-225), NULL for none.
@@ -591,6 +603,17 @@ int pxt_conv3x3_nhwc_f16(const void* in, int32_t H, int32_t W, int32_t Cin, cons
  * (+ReLU).  The taps are repacked into the kernel's fragment order on every call. */
 int pxt_conv3x3_nhwc_f32(const void* in, int32_t H, int32_t W, int32_t Cin, const void* weights,
                          const float* bias, int32_t Cout, int32_t relu, void* out, void* stream);
+
+/* The tile configuration the fp32 pass runs a 3x3 layer of H x W with Cout output channels in (host arithmetic only; the
+ * pass's own choice function): 1..5 = conv3x3_f32_kernel<CB, PB, WC, WP> <2,2,2,2>, <2,1,2,2>, <2,2,1,4>, <2,1,1,4>,
+ * <1,2,1,4>, whose workgroups span 128, 128, 64, 64 and 32 output channels; PXT_E_ARG for a shape the pass refuses
+ * (H or W < 1, Cout < 32 or no multiple of 32).
+ * pxt_conv3x3_nhwc_f32_cfg is pxt_conv3x3_nhwc_f32 with that choice as an argument, for tests: cfg 0 = the pass's
+ * choice, 1..5 = that configuration whatever the map size; PXT_E_ARG for another value or when Cout is no multiple of
+ * the configuration's span.  Every configuration forms each output value by the same chain, so all give the same bits. */
+int pxt_conv3x3_f32_cfg(int32_t H, int32_t W, int32_t Cout);
+int pxt_conv3x3_nhwc_f32_cfg(const void* in, int32_t H, int32_t W, int32_t Cin, const void* weights,
+                             const float* bias, int32_t Cout, int32_t relu, void* out, int32_t cfg, void* stream);
 
 /* The same layer with the taps already in the kernel's MFMA-fragment order (what pxt_unet_create
  * prepares once for every layer of the pyramid), for profiling the convolution alone and for

@@ -344,6 +344,7 @@ PROTOTYPES = {
     "pxt_unet_pair_join": (C.c_int, [_VP, _VP]),
     "pxt_unet_activation_stats": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
     "pxt_unet_layer_views": (C.c_int, [_VP, _I32, _I32, _I32, _I32, C.POINTER(UnetLayerView)]),
+    "pxt_unet_layer_views_f32": (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(UnetLayerView)]),
     "pxt_unet_workspace_bytes_batch": (_I64, [_VP, _I32, _I32, _I32]),
     "pxt_unet_forward_batch": (
         C.c_int,
@@ -358,6 +359,8 @@ PROTOTYPES = {
     ),
     "pxt_conv3x3_nhwc_f16": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP]),
     "pxt_conv3x3_nhwc_f32": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP]),
+    "pxt_conv3x3_f32_cfg": (C.c_int, [_I32, _I32, _I32]),
+    "pxt_conv3x3_nhwc_f32_cfg": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _I32, _VP]),
     "pxt_conv3x3_packed_bytes": (_I64, [_I32, _I32]),
     "pxt_conv3x3_pack_weights": (C.c_int, [_VP, _I32, _I32, _VP, _VP]),
     "pxt_conv3x3_packed": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _I64, _VP]),

@@ -1899,6 +1899,12 @@ extern "C" int pxt_unet_layer_views(const pxt_unet* ctx, int32_t n_images, int32
   return PXT_OK;
 }
 
+extern "C" int pxt_unet_layer_views_f32(const pxt_unet* ctx, int32_t n_images, int32_t H, int32_t W,
+                                        pxt_unet_layer_view* out) {
+  if (!ctx || !out || !ctx->f32) return PXT_E_ARG;
+  return pxt::f32_layer_views(ctx->f32, n_images, H, W, out);
+}
+
 extern "C" int64_t pxt_conv3x3_packed_bytes(int32_t Cin, int32_t Cout) {
   if (Cin < 32 || Cout < 32 || Cin % 32 != 0 || Cout % 32 != 0) return PXT_E_ARG;
   return (int64_t)2 * Cout * 9 * Cin * (int64_t)sizeof(half_t);  // the second kernel's layout, then the third's

@@ -20,5 +20,6 @@ int f32_forward_pair(UnetF32* net, const void* const* images, const int32_t* ima
                      const int32_t H[2], const int32_t W[2], float* const* out_maps, const int32_t out_cstride[3],
                      const int32_t* normalize, void* workspace, hipStream_t s);
 int f32_activation_stats(UnetF32* net, int H, int W, const void* workspace, float* stats, hipStream_t s);
+int f32_layer_views(const UnetF32* net, int n_images, int H, int W, pxt_unet_layer_view* out /* [22] */);
 
 }  // namespace pxt

@@ -482,18 +482,35 @@ void launch_conv_cfg(const float* in, int n, int H, int W, int cin, const float*
                      cin, (const float4*)wpk, bias, cout, relu, out);
 }
 
-int launch_conv(const float* in, int n, int H, int W, int cin, const float* wpk, const float* bias, int cout, int relu,
-                float* out, hipStream_t s) {
-  if (cin < kKC || cin % kKC != 0 || cout < 32 || cout % 32 != 0 || H < 1 || W < 1) return PXT_E_ARG;
+// The configurations, numbered from 1 in the order launch_conv lists them, and the output channels one workgroup of each
+// covers (32 CB WC): 1 = <2,2,2,2>, 2 = <2,1,2,2>, 3 = <2,2,1,4>, 4 = <2,1,1,4>, 5 = <1,2,1,4>.
+constexpr int kNumCfg = 5;
+constexpr int kCfgSpan[kNumCfg + 1] = {0, 128, 128, 64, 64, 32};
+
+// The configuration a layer of H x W with cout output channels runs (host arithmetic; launch_conv and the layer views
+// both ask here), PXT_E_ARG for a shape launch_conv refuses.
+int f32_conv_cfg(int H, int W, int cout) {
+  if (cout < 32 || cout % 32 != 0 || H < 1 || W < 1) return PXT_E_ARG;
   const long long px16 = (long long)((H + 15) / 16) * ((W + 15) / 16);  // 16 x 16 tiles of one image
-  if (cout % 128 == 0) {
-    if (px16 * 2 * (cout / 128) >= 1024) launch_conv_cfg<2, 2, 2, 2>(in, n, H, W, cin, wpk, bias, cout, relu, out, s);
-    else launch_conv_cfg<2, 1, 2, 2>(in, n, H, W, cin, wpk, bias, cout, relu, out, s);
-  } else if (cout % 64 == 0) {
-    if (px16 * (cout / 64) >= 1024) launch_conv_cfg<2, 2, 1, 4>(in, n, H, W, cin, wpk, bias, cout, relu, out, s);
-    else launch_conv_cfg<2, 1, 1, 4>(in, n, H, W, cin, wpk, bias, cout, relu, out, s);
-  } else {
-    launch_conv_cfg<1, 2, 1, 4>(in, n, H, W, cin, wpk, bias, cout, relu, out, s);
+  if (cout % 128 == 0) return px16 * 2 * (cout / 128) >= 1024 ? 1 : 2;
+  if (cout % 64 == 0) return px16 * (cout / 64) >= 1024 ? 3 : 4;
+  return 5;
+}
+
+// cfg 0: the configuration f32_conv_cfg picks; 1..5: that one (tests), refused when cout is no multiple of its span.
+int launch_conv(const float* in, int n, int H, int W, int cin, const float* wpk, const float* bias, int cout, int relu,
+                float* out, hipStream_t s, int cfg = 0) {
+  if (cin < kKC || cin % kKC != 0) return PXT_E_ARG;
+  const int planned = f32_conv_cfg(H, W, cout);
+  if (planned < 0) return planned;
+  if (cfg == 0) cfg = planned;
+  if (cfg < 1 || cfg > kNumCfg || cout % kCfgSpan[cfg] != 0) return PXT_E_ARG;
+  switch (cfg) {
+    case 1: launch_conv_cfg<2, 2, 2, 2>(in, n, H, W, cin, wpk, bias, cout, relu, out, s); break;
+    case 2: launch_conv_cfg<2, 1, 2, 2>(in, n, H, W, cin, wpk, bias, cout, relu, out, s); break;
+    case 3: launch_conv_cfg<2, 2, 1, 4>(in, n, H, W, cin, wpk, bias, cout, relu, out, s); break;
+    case 4: launch_conv_cfg<2, 1, 1, 4>(in, n, H, W, cin, wpk, bias, cout, relu, out, s); break;
+    default: launch_conv_cfg<1, 2, 1, 4>(in, n, H, W, cin, wpk, bias, cout, relu, out, s); break;
   }
   return PXT_OK;
 }
@@ -728,15 +745,54 @@ int f32_activation_stats(UnetF32* net, int H, int W, const void* workspace, floa
   return PXT_OK;
 }
 
+// Where f32_forward_batch leaves every buffer of a pass, from the same make_plan, and the configuration launch_conv
+// takes for each 3x3 layer, from the same f32_conv_cfg (host arithmetic only, nothing is launched).
+int f32_layer_views(const UnetF32* net, int n, int H, int W, pxt_unet_layer_view* out) {
+  PlanF32 P;
+  if (!net || !out || !make_plan(net, n, H, W, P)) return PXT_E_ARG;
+  std::memset(out, 0, (kNumConv + 5) * sizeof(pxt_unet_layer_view));
+  auto fill = [&](pxt_unet_layer_view& v, size_t off, int h, int w, int c) {
+    v.offset = (int64_t)off; v.h = h; v.w = w; v.c = c; v.in_memory = 1; v.splits = 1;
+  };
+  for (int li = 0; li < kNumConv; ++li) {
+    pxt_unet_layer_view& v = out[li];
+    if (li < 13) {
+      const int b = block_of(li);
+      fill(v, P.enc[li], P.h[b], P.w[b], net->conv[li].cout);
+    } else {
+      fill(v, P.dec[li - 13], P.dh[li - 13], P.dw[li - 13], net->conv[li].cout);
+      v.decoder = 1;
+    }
+    if (li == 0) continue;  // (conv_first_f32_kernel: no tile configuration)
+    const int cfg = f32_conv_cfg(v.h, v.w, v.c);
+    if (cfg < 0) return cfg;
+    v.cfg = cfg;
+  }
+  for (int b = 1; b < 5; ++b)  // the pooled input of block b (maxpool2_f32_kernel)
+    fill(out[kNumConv + b - 1], P.pool[b], P.h[b], P.w[b], net->conv[kEncF32[b].first].cin);
+  // the decoder-input buffer, shared by the four decoder layers: what the last one's upcat_f32_kernel left in it
+  fill(out[kNumConv + 4], P.upcat, P.dh[3], P.dw[3], net->conv[16].cin);
+  return PXT_OK;
+}
+
 }  // namespace pxt
+
+extern "C" int pxt_conv3x3_f32_cfg(int32_t H, int32_t W, int32_t Cout) { return pxt::f32k::f32_conv_cfg(H, W, Cout); }
 
 // ---------------------------------------------------------------------------
 // One fp32 3x3 convolution of the pass as a stand-alone call (layer parity tests against F.conv2d).
 // ---------------------------------------------------------------------------
 extern "C" int pxt_conv3x3_nhwc_f32(const void* in, int32_t H, int32_t W, int32_t Cin, const void* weights,
                                     const float* bias, int32_t Cout, int32_t relu, void* out, void* stream) {
+  return pxt_conv3x3_nhwc_f32_cfg(in, H, W, Cin, weights, bias, Cout, relu, out, 0, stream);
+}
+
+extern "C" int pxt_conv3x3_nhwc_f32_cfg(const void* in, int32_t H, int32_t W, int32_t Cin, const void* weights,
+                                        const float* bias, int32_t Cout, int32_t relu, void* out, int32_t cfg,
+                                        void* stream) {
   using namespace pxt::f32k;
   if (!in || !weights || !bias || !out || H < 1 || W < 1) return PXT_E_ARG;
+  if (cfg < 0 || cfg > kNumCfg || (cfg > 0 && Cout % kCfgSpan[cfg] != 0)) return PXT_E_ARG;
   if (Cin < kKC || Cin % kKC != 0 || Cout < 32 || Cout % 32 != 0) return PXT_E_ARG;
   const long long n = (long long)Cout * 9 * Cin;
   // the taps are repacked on every call into a scratch that lives as long as the process (the pyramid packs once)
@@ -753,7 +809,7 @@ extern "C" int pxt_conv3x3_nhwc_f32(const void* in, int32_t H, int32_t W, int32_
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(pack_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)weights, Cin, Cout,
                      (float*)scratch);
-  const int rc = launch_conv((const float*)in, 1, H, W, Cin, (const float*)scratch, bias, Cout, relu, (float*)out, s);
+  const int rc = launch_conv((const float*)in, 1, H, W, Cin, (const float*)scratch, bias, Cout, relu, (float*)out, s, cfg);
   if (rc != PXT_OK) return rc;
   PXT_HIP_CHECK(hipGetLastError());
   return PXT_OK;

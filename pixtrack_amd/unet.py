@@ -504,6 +504,17 @@ class UNet:
         _lib.check(_lib.lib().pxt_unet_layer_views(self._ctx, n_images, H, W, peers, views), "pxt_unet_layer_views")
         return [{name: int(getattr(v, name)) for name, _ in _lib.UnetLayerView._fields_} for v in views]
 
+    def layer_views_f32(self, n_images: int, H: int, W: int) -> List[Dict[str, int]]:
+        """Where an fp32 pass over ``n_images`` images of H x W leaves its buffers in the workspace
+        (pxt_unet_layer_views_f32; fp32 only, nothing is launched): 22 dicts with the fields of layer_views - the 17
+        convolutions (``cfg``: the configuration pxt_conv3x3_f32_cfg names, 0 for layer 0), the pooled inputs of encoder
+        blocks 1..4, then the decoder-input buffer as the last decoder layer leaves it - all fp32 [n_images][h][w][c].  A
+        two-image call of two sizes is two single passes; the second one's workspace starts ``pxt_unet_workspace_bytes``
+        of the first one's size further on."""
+        views = (_lib.UnetLayerView * 22)()
+        _lib.check(_lib.lib().pxt_unet_layer_views_f32(self._ctx, n_images, H, W, views), "pxt_unet_layer_views_f32")
+        return [{name: int(getattr(v, name)) for name, _ in _lib.UnetLayerView._fields_} for v in views]
+
     def __call__(self, data: Dict[str, torch.Tensor]) -> Dict[str, List[torch.Tensor]]:
         image = data["image"]  # 1 x 3 x H x W in [0, 1]
         assert image.dim() == 4 and image.shape[0] == 1 and image.shape[1] == 3

@@ -13,7 +13,8 @@ from pixtrack_amd.unet import (HEAD_INPUTS, OUTPUT_DIMS, conv_layer_dims, conv_l
                                pack_unet_weights)
 
 ROOT = Path(__file__).resolve().parent.parent
-NEW_SYMBOLS = ["pxt_unet_create_f32", "pxt_unet_precision", "pxt_conv3x3_nhwc_f32"]
+NEW_SYMBOLS = ["pxt_unet_create_f32", "pxt_unet_precision", "pxt_conv3x3_nhwc_f32", "pxt_conv3x3_f32_cfg",
+               "pxt_conv3x3_nhwc_f32_cfg", "pxt_unet_layer_views_f32"]
 
 
 def _arrays(blob):
@@ -78,6 +79,61 @@ def test_create_f32_refuses_an_fp16_pack():
     assert L.pxt_unet_create_f32(b16, len(b16), C.byref(ctx)) == -1  # PXT_E_ARG before any device call
     b32 = bytearray(pack_unet_weights(w, precision="fp32"))
     assert L.pxt_unet_create_f32(bytes(b32[:4096]), 4096, C.byref(ctx)) == -1  # truncated
+
+
+def _tiles(H, W):
+    return ((H + 15) // 16) * ((W + 15) // 16)
+
+
+def test_conv3x3_f32_cfg_at_the_thresholds_and_production_sizes():
+    """pxt_conv3x3_f32_cfg (the function launch_conv itself asks): 1 = <2,2,2,2>, 2 = <2,1,2,2>, 3 = <2,2,1,4>,
+    4 = <2,1,1,4>, 5 = <1,2,1,4>.  The large-map configurations start at tiles * 2 * (Cout / 128) >= 1024 and
+    tiles * (Cout / 64) >= 1024, tiles counted as 16 x 16 with partial ones."""
+    cfg = _lib.lib().pxt_conv3x3_f32_cfg
+    # Cout = 512: 128 tiles and up
+    for H, W, tiles, want in [(16, 127 * 16, 127, 2), (16, 127 * 16 + 1, 128, 1), (16, 128 * 16, 128, 1), (125, 240, 120, 2),
+                              (125, 250, 128, 1), (113, 241, 128, 1), (112, 241, 112, 2)]:
+        assert _tiles(H, W) == tiles and cfg(H, W, 512) == want, (H, W)
+    # Cout = 64: 1024 tiles and up
+    assert _tiles(33 * 16, 31 * 16) == 1023 and _tiles(512, 512) == 1024 and _tiles(497, 497) == 1024
+    assert cfg(33 * 16, 31 * 16, 64) == 4 and cfg(512, 512, 64) == 3 and cfg(497, 497, 64) == 3
+    assert cfg(33 * 16, 31 * 16 + 1, 64) == 3  # one column more: 33 x 32 tiles
+    # the channel groups count: Cout = 192 is three groups of 64, Cout = 256 two of 128
+    assert _tiles(273, 290) == 342 and cfg(273, 290, 192) == 3 and cfg(272, 288, 192) == 4  # 342 x 3 / 306 x 3
+    assert cfg(16, 255 * 16, 256) == 2 and cfg(16, 256 * 16, 256) == 1
+    # no multiple of 64: one configuration at any size
+    for cout in (96, 160, 32):
+        for H, W in [(1, 1), (75, 100), (480, 640), (4096, 4096)]:
+            assert cfg(H, W, cout) == 5, (H, W, cout)
+    # production: 640 x 480 block 0, 1024 x 576 block 1, 320 x 240 at 128 channels
+    assert cfg(480, 640, 64) == 3 and cfg(288, 512, 128) == 1 and cfg(240, 320, 128) == 2
+    assert cfg(576, 1024, 64) == 3 and cfg(240, 320, 64) == 4
+    # what launch_conv refuses
+    for H, W, cout in [(0, 16, 64), (16, 0, 64), (-1, 16, 64), (16, 16, 0), (16, 16, 16), (16, 16, 48), (16, 16, -64),
+                       (16, 16, 100)]:
+        assert cfg(H, W, cout) == -1, (H, W, cout)
+
+
+def test_forced_configuration_entry_refuses_before_any_device_call():
+    """pxt_conv3x3_nhwc_f32_cfg: a configuration out of range or one whose channel span (128 / 128 / 64 / 64 / 32) does not
+    divide Cout is PXT_E_ARG, like a null pointer or a bad shape - all before the first device call."""
+    L = _lib.lib()
+    p = 256  # (never dereferenced: every call below is refused)
+
+    def call(H=16, W=16, cin=16, cout=128, cfg=0, x=p, w=p, b=p, o=p):
+        return L.pxt_conv3x3_nhwc_f32_cfg(x, H, W, cin, w, b, cout, 1, o, cfg, None)
+
+    assert call(cfg=-1) == -1 and call(cfg=6) == -1
+    for cfg, cout in [(1, 64), (2, 64), (1, 192), (2, 96), (3, 96), (4, 32), (3, 160), (4, 160)]:
+        assert call(cfg=cfg, cout=cout) == -1, (cfg, cout)
+    for cfg in range(6):
+        assert call(cfg=cfg, cin=8) == -1 and call(cfg=cfg, cin=24) == -1 and call(cfg=cfg, cout=48) == -1
+        assert call(cfg=cfg, H=0) == -1 and call(cfg=cfg, W=0) == -1
+        assert call(cfg=cfg, x=None) == -1 and call(cfg=cfg, w=None) == -1 and call(cfg=cfg, b=None) == -1
+        assert call(cfg=cfg, o=None) == -1
+    assert L.pxt_conv3x3_nhwc_f32(p, 16, 16, 8, p, p, 128, 1, p, None) == -1  # the old entry: the same checks
+    out = (_lib.UnetLayerView * 22)()
+    assert L.pxt_unet_layer_views_f32(None, 1, 64, 64, out) == -1
 
 
 class _Stop(Exception):
